@@ -17,9 +17,13 @@ ONE JSON line.
             hipMemcpyPeerAsync) is timed at every N as well and reported as `tile_scaling` (strong scaling);
             `--workload 8k --gpus N` (or --strong) makes that leg the headline;
 * value     total ray-steps of all ranks / max-over-ranks wall time of the K timed steps.
-* beside it (never as `value`): `kernel_ms` / `roofline` / `roofline_valu` from isolated launches of the same scene,
-            `other_math` (the opt-in fast arithmetic), `tile_scaling`, `video_loop` (N = 1: frames of the video driver's
-            loop, configs[4], PNG files written) and `cpu_baseline` (N = 1: the CPU restatement on the host's threads).
+* a plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the line;
+* --full    adds, beside it (never as `value`): `kernel_ms` / `roofline` / `roofline_valu` from isolated launches of the
+            same scene, `stream_map`, `other_math` (the other arithmetics), `tile_scaling`, `config2_4k`, `video_loop`
+            (N = 1: frames of the video driver's loop, configs[4], PNG files written) and `cpu_baseline` (N = 1: the CPU
+            restatement on the host's threads).
+* --dump-outputs DIR   the final image of the last timed step as DIR/final.npy (float32, (H, W, 3)); frames larger than
+            64 MB as a fixed, seeded sample of pixels: DIR/final.npy (n, 3) and their flat indices DIR/final_pixel_index.npy.
 """
 import argparse
 import json
@@ -56,6 +60,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="fhd", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (isolated kernel times and rooflines, stream map, other "
+                         "arithmetics, row-block leg, 4k leg, video loop, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final image of the last timed step to DIR/final.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--persistent", action="store_true", help="A/B: persistent waves + queue refill instead of the tile schedule")
     ap.add_argument("--no-other-math", action="store_true", help="skip the informational A/B leg (profiling)")
@@ -75,7 +84,7 @@ def parse():
     ap.add_argument("--math", default="hybrid", choices=["fast", "strict", "hybrid"],
                     help="march arithmetic of the headline (default hybrid: strict on the tiles whose rays pass near the photon "
                          "sphere, fast elsewhere; certified within the north-star tolerance by tests/test_gpu_hybrid.py).  The other "
-                         "two are timed beside it as `other_math`")
+                         "two are timed beside it as `other_math` (--full)")
     ap.add_argument("--spin-up-ms", type=float, default=300.0,
                     help="un-timed frames rendered for this long BEFORE the --warmup steps: the scene set-up leaves the GPU idle "
                          "and its clocks low; the march reaches its steady duration after ~25 ms of load and the last 3 % after "
@@ -123,7 +132,7 @@ def cpu_baseline(wl, sky, tex):
             "march_only_skip_diff_mray_steps_per_s": steps / t_skip / 1e6}
 
 
-def tile_leg(wl, n, frames, math=None, warmup=3):
+def tile_leg(wl, n, frames, math=None, warmup=3, dump=None):
     """BASELINE.json configs[3]: ONE frame of ``wl`` cut into n cost-balanced row blocks, block k on device k.  Rank 0
     drives all n devices from this process through bhr_group_render: every tile marches and H-blurs its rows
     concurrently, neighbours exchange the bloom halo rows and every tile pushes its final rows to device 0 with
@@ -150,6 +159,8 @@ def tile_leg(wl, n, frames, math=None, warmup=3):
             multigpu.group_render(tiles, wl["cam_pos"], wl["fov"], gather="peer_u8", wait=False)
         multigpu.group_sync(tiles)
         el = time.perf_counter() - t0
+        if dump is not None:                             # the gathered u8 frame of the last timed frame, its values as float32
+            dump(multigpu.read_gathered_u8(tiles))
         t0 = time.perf_counter()
         for _ in range(frames):
             multigpu.group_render(tiles, wl["cam_pos"], wl["fov"], gather="peer_u8")   # synchronises every tile's stream
@@ -193,7 +204,7 @@ def tile_leg_in_child(workload, n, frames, math, timeout_s=600):
     return json.loads(lines[-1])
 
 
-def tile_leg_per_rank(wl, rank, world, local_rank, dist, frames, math=None, warmup=3):
+def tile_leg_per_rank(wl, rank, world, local_rank, dist, frames, math=None, warmup=3, dump=None):
     """The same row-block frame with one PROCESS per tile (multigpu.TileLink: HIP IPC memory handles for the neighbours'
     halo rows and rank 0's frame buffer, shared-memory counters for the pacing): what `--strong` runs when a rank sees
     only its own GPU.  Every rank calls this; rank 0 gets the result, the others None."""
@@ -212,6 +223,8 @@ def tile_leg_per_rank(wl, rank, world, local_rank, dist, frames, math=None, warm
         for _ in range(frames):
             link.render(wl["cam_pos"], wl["fov"])
         el = time.perf_counter() - t0
+        if dump is not None and rank == 0:               # rank 0's gathered u8 frame of the last timed frame, as float32
+            dump(link.read_gathered())
         link.render(wl["cam_pos"], wl["fov"], time_march=True)       # un-timed: per-tile march durations
         c = tile.counters()
         cs = [pickle.loads(b) for b in D.host_all_gather_bytes(pickle.dumps((c["ray_steps"], c["march_ms"], c["frame_ms"], el)), dist)]
@@ -389,6 +402,24 @@ def config2_leg(math=None, frames=40):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, final):
+    """--dump-outputs: the (H, W, 3) final image a caller of the timed path receives, as float32.  A frame larger than
+    DUMP_MAX_BYTES is written as a fixed sample of pixels (seed 0, sorted flat indices), the indices beside it."""
+    os.makedirs(directory, exist_ok=True)
+    final = np.asarray(final, dtype=np.float32)
+    if final.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(directory, "final.npy"), final)
+        return
+    pixels = final.shape[0] * final.shape[1]
+    n = (DUMP_MAX_BYTES // 2) // (3 * 4 + 8)                 # sample + its float64 indices within half the budget
+    idx = np.sort(np.random.default_rng(0).choice(pixels, size=min(n, pixels), replace=False))
+    np.save(os.path.join(directory, "final.npy"), final.reshape(pixels, 3)[idx])
+    np.save(os.path.join(directory, "final_pixel_index.npy"), idx.astype(np.float64))
+
+
 def main():
     args = parse()
     # Only the JSON line may reach stdout: RCCL prints a version banner there when NCCL_DEBUG is set, the scene
@@ -429,10 +460,11 @@ def main():
         have = int(L.load().bhr_device_count())
         per_rank = world > 1 and (have < world or os.environ.get("BHR_STRONG_PER_RANK") == "1") and not os.environ.get("BHR_TILE_DEVICES")
         t = None
+        dump = (lambda frame: dump_outputs(args.dump_outputs, frame)) if args.dump_outputs else None
         if per_rank:
-            t = tile_leg_per_rank(wl, rank, world, local_rank, dist, args.steps, math=args.math, warmup=args.warmup)
+            t = tile_leg_per_rank(wl, rank, world, local_rank, dist, args.steps, math=args.math, warmup=args.warmup, dump=dump)
         elif rank == 0:
-            t = tile_leg(wl, world, args.steps, math=args.math, warmup=args.warmup)
+            t = tile_leg(wl, world, args.steps, math=args.math, warmup=args.warmup, dump=dump)
             if "skipped" in t:
                 raise SystemExit("strong-scaling leg: " + t["skipped"])
         if rank == 0:
@@ -514,9 +546,13 @@ def main():
                            + (f"; guards on, {hi['repaired_pixels']} pixels marched again strict" if hi.get("repair_capacity") else ""))
         except Exception:      # no hybrid march has run on this context (a Disk V2 source or the persistent schedule: strict)
             hybrid_note = "no hybrid march on this context: this view ran strict (Disk V2 source or persistent schedule)"
+    if args.dump_outputs and rank == 0:                 # the last timed step's frame, before anything else renders
+        from bhr_amd import _lib as L
+        dump_outputs(args.dump_outputs, renderer.read_layer(L.LAYER_FINAL))
 
+    # what follows under args.full is measured beside the headline (--full), never as part of `value`
     # same scene, same process, the other arithmetics: reported beside the headline, never as `value`
-    n_other = 0 if args.no_other_math else max(args.steps // 4, 10)
+    n_other = 0 if (args.no_other_math or not args.full) else max(args.steps // 4, 10)
     others = []
     for other in [m for m in ("strict", "hybrid", "fast") if m != renderer.math] if n_other else []:
         for _ in range(3):
@@ -536,7 +572,7 @@ def main():
     # chip to themselves: the same scene and view on a second context created with one frame slot, outside the
     # timed region.  (`rocprofv3 --kernel-trace` of `bench.py --frame-slots 1` is the matching profile.)
     iso = None
-    if renderer.frame_slots != 1 and rank == 0:
+    if args.full and renderer.frame_slots != 1 and rank == 0:
         solo, _, _, _ = workloads.make_scene(wl, device_index=local_rank, math=args.math, frame_slots=1)
         n_iso = max(min(args.steps, 100), 10)
         t_spin = time.perf_counter()                   # the second scene set-up idled the chip again: spin up as above
@@ -564,7 +600,7 @@ def main():
     # the row-block leg (configs[3]): reported beside the headline at every N, so that the per-N bench lines carry the
     # tile-scaling curve as well as the frame-sharding one.  Every rank's GPU is idle while rank 0 times it.
     tile = None
-    if args.tile_workload != "none" and not args.no_other_math:
+    if args.full and args.tile_workload != "none" and not args.no_other_math:
         D.host_barrier(dist)
         from bhr_amd import _lib as L
         have = int(L.load().bhr_device_count())
@@ -589,31 +625,8 @@ def main():
         n_frames = c["frames_timed"]
         overlapped = {"march": c["march_ms_sum"] / max(n_frames, 1), "post": c["bloom_ms_sum"] / max(n_frames, 1),
                       "frames_timed": n_frames}
-        if iso is not None:
-            march_ms, bloom_ms, k_frames, k_steps = iso["march_ms"], iso["post_ms"], iso["frames"], iso["ray_steps"]
-        else:   # one frame slot: the timed region's own launches are isolated
-            march_ms, bloom_ms, k_frames = overlapped["march"], overlapped["post"], n_frames
-            k_steps = c["ray_steps_sum"] / max(n_frames, 1)
         pixels = wl["width"] * wl["height"]
         alg_bytes = MARCH_BYTES_PER_PIXEL * pixels
-        achieved_gbs = alg_bytes / (march_ms * 1e-3) / 1e9
-        traffic = traffic_source = executed_flop = None
-        tpath = os.path.join(ROOT, "profiles", "march_traffic.json")
-        if os.path.isfile(tpath):
-            try:
-                tj = json.load(open(tpath))
-                key = f"{args.workload}/{renderer.math}"
-                traffic = tj.get(key, tj.get(args.workload) if renderer.math == "strict" else None)
-                traffic_source = (tj.get("source", "") + f"; key {key}: " + json.dumps(tj.get(f"_{key}_detail", tj.get(f"_{args.workload}_detail")))) if traffic else None
-                det = tj.get(f"_{key}_detail") or {}
-                executed_flop = det.get("executed_fp32_flop_per_frame")
-            except Exception:
-                traffic = None
-        valu_tflops = MARCH_FLOP_PER_RAY_STEP * k_steps / (march_ms * 1e-3) / 1e12
-        try:
-            stream_map = renderer.stream_map()      # after the timed region: which of the context's streams share a hardware queue
-        except Exception as e:
-            stream_map = {"error": str(e)}
         stream_cal = renderer.stream_calibration()
         out = {
             "metric": "Mray-steps/s", "value": total_steps / elapsed / 1e6, "unit": "Mray-steps/s",
@@ -631,19 +644,12 @@ def main():
                        "spin_up": f"{n_spin} un-timed frames ({args.spin_up_ms:g} ms) before the {args.warmup} warm-up steps",
 
                        "ray_steps_per_frame": int(steps_per_frame), "steps_per_ray": steps_per_frame / pixels},
-            "stream_map": stream_map, "stream_calibration": stream_cal,
-            "kernel_ms": {"march": march_ms, "bloom_combine_flare" if flare else "bloom_and_combine": bloom_ms, "frames_timed": k_frames,
-                          "march_vgprs": c["march_vgprs"],
-                          "how": "HIP events on the launching stream, isolated launches (one frame slot)"
-                                 + ("" if iso is None else f", {iso['fps']:.0f} fps one frame at a time")},
+            "stream_calibration": stream_cal,
             "kernel_ms_in_timed_region": dict(overlapped, march_busy_ms=c["march_busy_ms"], span_ms=c["span_ms"],
                                               note="event brackets of overlapping launches (two frame slots): each covers time shared "
                                                    "with the other frame's kernels; march_busy_ms = union of the march intervals"),
             "timed_region_ms": dict(region_ms, total=elapsed * 1e3,
                                     note="host stamps: the K submissions, then the closing bracket's parts in the order they run"),
-            "roofline": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": "march", "algorithmic_bytes_per_launch": alg_bytes},
             # the same two ratios over the TIMED REGION itself: all march launches of the region / the time during which
             # at least one of them was running (union of their event brackets; launches of successive frames overlap)
             "roofline_in_timed_region": {
@@ -653,17 +659,51 @@ def main():
                 "valu_tflops": MARCH_FLOP_PER_RAY_STEP * c["ray_steps_sum"] / (c["march_busy_ms"] * 1e-3) / 1e12 if c["march_busy_ms"] > 0 else None,
                 "valu_frac": MARCH_FLOP_PER_RAY_STEP * c["ray_steps_sum"] / (c["march_busy_ms"] * 1e-3) / 1e12 / VALU_FP32_PEAK_TFLOPS if c["march_busy_ms"] > 0 else None,
                 "march_launches": n_frames, "march_busy_ms": c["march_busy_ms"]},
-            # the march is not HBM bound: the governing ceiling is non-matrix FP32
-            "roofline_valu": {"bound": "valu_fp32", "achieved": valu_tflops, "peak": VALU_FP32_PEAK_TFLOPS,
-                              "unit": "TFLOP/s", "frac": valu_tflops / VALU_FP32_PEAK_TFLOPS,
-                              "flop_per_ray_step": MARCH_FLOP_PER_RAY_STEP,
-                              # what the kernels EXECUTE (the 205 above is the reference's 3-D formulation; the fast list marches in
-                              # the 2-D orbital plane): 64 x (2 FMA + MUL + ADD wave-instructions) of the march kernels, from the
-                              # PMC pass of the profile named in roofline.traffic_source, over this run's march time
-                              "executed_flop_per_frame": executed_flop,
-                              "executed_tflops": (executed_flop / (march_ms * 1e-3) / 1e12) if executed_flop else None,
-                              "executed_frac": (executed_flop / (march_ms * 1e-3) / 1e12 / VALU_FP32_PEAK_TFLOPS) if executed_flop else None},
         }
+        if args.full:
+            if iso is not None:
+                march_ms, bloom_ms, k_frames, k_steps = iso["march_ms"], iso["post_ms"], iso["frames"], iso["ray_steps"]
+            else:   # one frame slot: the timed region's own launches are isolated
+                march_ms, bloom_ms, k_frames = overlapped["march"], overlapped["post"], n_frames
+                k_steps = c["ray_steps_sum"] / max(n_frames, 1)
+            achieved_gbs = alg_bytes / (march_ms * 1e-3) / 1e9
+            traffic = traffic_source = executed_flop = None
+            tpath = os.path.join(ROOT, "profiles", "march_traffic.json")
+            if os.path.isfile(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    key = f"{args.workload}/{renderer.math}"
+                    traffic = tj.get(key, tj.get(args.workload) if renderer.math == "strict" else None)
+                    traffic_source = (tj.get("source", "") + f"; key {key}: " + json.dumps(tj.get(f"_{key}_detail", tj.get(f"_{args.workload}_detail")))) if traffic else None
+                    det = tj.get(f"_{key}_detail") or {}
+                    executed_flop = det.get("executed_fp32_flop_per_frame")
+                except Exception:
+                    traffic = None
+            valu_tflops = MARCH_FLOP_PER_RAY_STEP * k_steps / (march_ms * 1e-3) / 1e12
+            try:
+                stream_map = renderer.stream_map()      # after the timed region: which of the context's streams share a hardware queue
+            except Exception as e:
+                stream_map = {"error": str(e)}
+            out["stream_map"] = stream_map
+            out.update({
+                "kernel_ms": {"march": march_ms, "bloom_combine_flare" if flare else "bloom_and_combine": bloom_ms, "frames_timed": k_frames,
+                              "march_vgprs": c["march_vgprs"],
+                              "how": "HIP events on the launching stream, isolated launches (one frame slot)"
+                                     + ("" if iso is None else f", {iso['fps']:.0f} fps one frame at a time")},
+                "roofline": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                             "kernel": "march", "algorithmic_bytes_per_launch": alg_bytes},
+                # the march is not HBM bound: the governing ceiling is non-matrix FP32
+                "roofline_valu": {"bound": "valu_fp32", "achieved": valu_tflops, "peak": VALU_FP32_PEAK_TFLOPS,
+                                  "unit": "TFLOP/s", "frac": valu_tflops / VALU_FP32_PEAK_TFLOPS,
+                                  "flop_per_ray_step": MARCH_FLOP_PER_RAY_STEP,
+                                  # what the kernels EXECUTE (the 205 above is the reference's 3-D formulation; the fast list marches in
+                                  # the 2-D orbital plane): 64 x (2 FMA + MUL + ADD wave-instructions) of the march kernels, from the
+                                  # PMC pass of the profile named in roofline.traffic_source, over this run's march time
+                                  "executed_flop_per_frame": executed_flop,
+                                  "executed_tflops": (executed_flop / (march_ms * 1e-3) / 1e12) if executed_flop else None,
+                                  "executed_frac": (executed_flop / (march_ms * 1e-3) / 1e12 / VALU_FP32_PEAK_TFLOPS) if executed_flop else None},
+            })
         if others:
             out["other_math"] = {"runs": others,
                                  "note": "informational A/B in the same process and scene; `value` above is --math " + renderer.math}
@@ -692,17 +732,17 @@ def main():
                                 "neighbours' planes and the frame buffer are local HBM, on N they are peer memory over xGMI"}
                 except Exception as e:
                     tile["one_tile_alone"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_other_math and not args.no_config2:
+        if args.full and world == 1 and not args.no_other_math and not args.no_config2:
             try:
                 out["config2_4k"] = config2_leg(math=args.math)
             except Exception as e:      # the headline stands on its own
                 out["config2_4k"] = {"error": f"{type(e).__name__}: {e}"}
-        if args.video_frames > 0 and world == 1 and not args.no_other_math:
+        if args.full and args.video_frames > 0 and world == 1 and not args.no_other_math:
             try:
                 out["video_loop"] = video_leg(args.video_frames, math=args.math)
             except Exception as e:      # the headline stands on its own
                 out["video_loop"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(wl, sky, tex)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

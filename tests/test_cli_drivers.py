@@ -239,7 +239,7 @@ def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, BHR_DIST_BACKEND="gloo", BHR_FORCE_DEVICE="0")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29534", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "20", "--warmup", "3", "--workload", "sd", "--no-other-math"],
+                        "--gpus", "2", "--steps", "20", "--warmup", "3", "--workload", "sd", "--no-other-math", "--full"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -261,7 +261,7 @@ def test_bench_row_block_leg_rehearsal(strong):
     env = dict(os.environ, BHR_DIST_BACKEND="gloo", BHR_FORCE_DEVICE="0", BHR_TILE_DEVICES="0,0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29535" if strong else "29536", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "20", "--warmup", "3", "--workload", "sd", "--tile-workload", "sd", "--no-cpu-baseline"]
+           "--steps", "20", "--warmup", "3", "--workload", "sd", "--tile-workload", "sd", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd + (["--strong"] if strong else []), capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -287,7 +287,7 @@ def test_bench_row_block_leg_one_process_per_tile(strong):
     env.pop("BHR_TILE_DEVICES", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29537" if strong else "29538", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "20", "--warmup", "3", "--workload", "sd", "--tile-workload", "sd", "--no-cpu-baseline"]
+           "--steps", "20", "--warmup", "3", "--workload", "sd", "--tile-workload", "sd", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd + (["--strong"] if strong else []), capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]

@@ -3,7 +3,7 @@
 # alternating, ROUNDS rounds; prints fps (two frames in flight) and the isolated march bracket
 ROUNDS=${ROUNDS:-3}
 for r in $(seq $ROUNDS); do for lib in "$@"; do
-  BHR_HIP_LIBRARY=$(realpath $lib) python bench.py --no-cpu-baseline --no-other-math --tile-workload none ${BENCH_ARGS} 2>/dev/null > /tmp/ab.json
+  BHR_HIP_LIBRARY=$(realpath $lib) python bench.py --full --no-cpu-baseline --no-other-math --tile-workload none ${BENCH_ARGS} 2>/dev/null > /tmp/ab.json
   python - "$lib" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

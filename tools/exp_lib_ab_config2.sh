@@ -1,6 +1,6 @@
 #!/bin/bash
 for r in 1 2 3; do for lib in "$@"; do
-  BHR_HIP_LIBRARY=$(realpath $lib) python bench.py --no-cpu-baseline --tile-workload none --video-frames 0 --steps 40 2>/dev/null > /tmp/ab.json
+  BHR_HIP_LIBRARY=$(realpath $lib) python bench.py --full --no-cpu-baseline --tile-workload none --video-frames 0 --steps 40 2>/dev/null > /tmp/ab.json
   python - "$lib" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

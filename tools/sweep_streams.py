@@ -25,7 +25,7 @@ def main():
             for kv in envs.split():
                 a, b = kv.split("=", 1)
                 env[a] = b
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-other-math", "--no-config2", "--tile-workload", "none",
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-other-math", "--no-config2", "--tile-workload", "none",
                                 "--video-frames", "0"] + extra, env=env, capture_output=True, text=True)
             try:
                 d = json.loads(p.stdout.strip().splitlines()[-1])
