@@ -26,16 +26,17 @@
  *   _noise_eval_kernel           render.py:3305-3326
  *   _generate_background_kernel  render.py:3332-3451
  *
- * Parity pinning (see DESIGN.md "Oracle"): the Taichi kernels cannot be
- * executed in the build container (taichi is not installed, no network), and
- * the reference's only pin for the march/bloom is an MD5 of float bytes from
- * the author's LLVM fast-math build (tests/e2e_baseline.txt) which carries no
- * values.  => march/bloom/background: PARITY UNPINNED by reference vectors;
- * pinned by physics known-answer tests and the reference's own property tests
- * restated in tests/.  compose + mipmaps ARE pinned: tests/golden holds
- * outputs of the reference's importable NumPy twin
- * (_generate_disk_texture_rotating_from_state, generate_disk_mipmaps), the
- * same comparison the reference makes in tests/unit/test_gpu_texture_compose.py.
+ * Parity pinning (see DESIGN.md "Oracle"): march, bloom and background are
+ * pinned by the reference-statement fixtures in tests/golden/
+ * (march_ref_*.npz, bloom_ref.npz, texture_ref.npz, made by
+ * tests/golden/make_kernel_golden.py): the reference's own kernel functions
+ * executed as plain Python in IEEE f32 and in f64 on small scenes, their
+ * layers, per-pixel step counts and escape directions stored as data.
+ * tests/test_reference_kernels.py holds this file and the HIP kernels to
+ * them.  compose + mipmaps are pinned by outputs of the reference's
+ * importable NumPy twin (_generate_disk_texture_rotating_from_state,
+ * generate_disk_mipmaps), the comparison the reference itself makes in
+ * tests/unit/test_gpu_texture_compose.py.
  *
  * Build: see oracle/Makefile.  Strict variant: -O2 -ffp-contract=off
  * (checker).  Fast variant: -O3 -ffast-math -fopenmp (cpu_baseline timing;

@@ -126,7 +126,7 @@ def test_hybrid_whole_fhd_frame_vs_strict(hip_lib):
 
 def test_hybrid_strict_tiles_are_bit_identical_to_strict(hip_lib):
     """Inside the strict band the hybrid frame IS the strict frame: with a band that covers every tile the two marches
-    give identical layers and step counts; with the default band the pixels of the strict tiles are identical."""
+    give identical frames (with the default band the pixels of the strict tiles are identical: the test below)."""
     import os
     from bhr_amd import HipRenderer, _lib, scenes
     s = scenes.SCENES["default"]
@@ -144,6 +144,45 @@ def test_hybrid_strict_tiles_are_bit_identical_to_strict(hip_lib):
         os.environ.pop("BHR_HYBRID_BAND", None)
     assert info["strict_tiles"] == info["tiles"]
     np.testing.assert_array_equal(a, b)
+
+
+@pytest.mark.parametrize("view", ["fhd", "8k", "cam2.6", "rows", "4k_aa"])
+def test_hybrid_strict_tiles_are_the_strict_frame_at_the_default_band(view, hip_lib):
+    """With the DEFAULT band, every pixel of the strict list's tiles has the strict march's bg and disk values bit for bit:
+    the strict list is marched by the strict kernel (march_tile_plain_ilp; march_tile_aa_ilp for an anti-aliased view --
+    the kernels math="strict" launches), only over a sub-list of the tiles."""
+    from bhr_amd import HipRenderer, _lib, scenes
+    sky, tex = scenes.analytic_skybox(), scenes.noisy_disk(256, 1024)
+    kw = dict(step_size=0.1, r_max=10.0, r_disk_inner=2.0, r_disk_outer=15.0, disk_tilt=0.0)
+    W, H, cam, fov, rows = 1920, 1080, [6.0, 0.0, 0.5], 90.0, None
+    if view == "8k":
+        W, H, kw["step_size"] = 7680, 4320, 0.05
+    elif view == "cam2.6":
+        W, H, cam, fov = 960, 540, [2.6, 0.3, 0.2], 110.0
+    elif view == "rows":
+        rows = (97, 251 + 8 * 40)
+    elif view == "4k_aa":
+        W, H, kw = 3840, 2160, dict(kw, disk_tilt=25.0, anti_alias="lod_radius")
+    r = HipRenderer(W, H, sky, tex, rows=rows, frame_slots=1, **kw)
+    mask = None
+    for layer, name in ((_lib.LAYER_BG, "bg"), (_lib.LAYER_DISK, "disk")):      # one layer pair on the host at a time (8k)
+        r.render_async(cam, fov, skip_bloom=True, math="strict")
+        want = r.read_layer(layer)
+        r.render_async(cam, fov, skip_bloom=True, math="hybrid")
+        got = r.read_layer(layer)
+        if mask is None:
+            info, order = r.hybrid_info(), r.hybrid_launch_order()
+            assert (info["band_below"], info["band_above"]) == (0.085, 0.36), info
+            assert 0 < info["strict_tiles"] < info["tiles"], info
+            tiles_x, rows_n = (W + 7) // 8, got.shape[0]
+            ty, tx = np.divmod(order[:info["strict_tiles"]], tiles_x)
+            tiles = np.zeros(((rows_n + 7) // 8, tiles_x), bool)
+            tiles[ty, tx] = True
+            mask = np.repeat(np.repeat(tiles, 8, axis=0), 8, axis=1)[:rows_n, :W]
+        same = (got == want).all(axis=2)
+        del got, want
+        assert same[mask].all(), f"{view} {name}: {int((~same & mask).sum())} pixels of strict tiles differ from the strict frame"
+    r.close()
 
 
 def test_hybrid_in_row_blocks(hip_lib):
@@ -357,3 +396,179 @@ def test_view_change_costs_a_tenth_of_a_millisecond_at_8k(hip_lib):
         cost[where] = (min(moved) - min(same)) * 1e3
     print(f"\n8k view change: device {cost[1]:.3f} ms, host {cost[0]:.3f} ms on the submit path")
     assert cost[1] <= 0.2 and cost[1] < cost[0] / 20, cost
+
+
+def _frame_stats(a, b, chunk=256):
+    """Per-channel RMSE of a - b and the per-pixel max |a - b| over channels, reduced in row chunks."""
+    sq = np.zeros(3)
+    dmax = np.empty(a.shape[:2], np.float32)
+    for y in range(0, a.shape[0], chunk):
+        d = a[y:y + chunk].astype(np.float64) - b[y:y + chunk]
+        sq += (d * d).sum(axis=(0, 1))
+        dmax[y:y + chunk] = np.abs(d).max(axis=2)
+    return np.sqrt(sq / (a.shape[0] * a.shape[1])), dmax
+
+
+def _hybrid_vs_strict(wl, variants):
+    """The bench scene of wl on one frame_slots=1 context: the strict frame against the hybrid one under each
+    hybrid_repair value of `variants`, layer by layer (at most three frame-sized f32 layers on the host at once).
+    Returns {repair: dict(rmse={layer: per-channel RMSE}, beyond_1e3=pixels of the final layer beyond 1e-3, max=largest
+    difference there, steps, strict_steps, info)}."""
+    from bhr_amd import _lib, workloads
+    r, _, _, _ = workloads.make_scene(wl, frame_slots=1)
+    out = {rep: dict(rmse={}) for rep in variants}
+    try:
+        for name, layer in (("bg", _lib.LAYER_BG), ("disk", _lib.LAYER_DISK), ("blur", _lib.LAYER_BLUR), ("final", _lib.LAYER_FINAL)):
+            r.set_option("hybrid_repair", -1)
+            r.render_async(wl["cam_pos"], wl["fov"], math="strict")
+            want, strict_steps = r.read_layer(layer), r.counters()["ray_steps"]
+            for rep in variants:
+                r.set_option("hybrid_repair", rep)
+                r.render_async(wl["cam_pos"], wl["fov"], math="hybrid")
+                got = r.read_layer(layer)
+                o = out[rep]
+                o["rmse"][name], d = _frame_stats(got, want)
+                del got
+                o.update(steps=r.counters()["ray_steps"], strict_steps=strict_steps, info=r.hybrid_info())
+                if name == "final":
+                    o.update(beyond_1e3=int((d > 1e-3).sum()), max=float(d.max()))
+            del want
+    finally:
+        r.close()
+    return out
+
+
+_WHOLE = {}
+
+
+def _whole_frame(W, H, step, variants=(-1,)):
+    """_hybrid_vs_strict on the bench scene at W x H, cached for the tests of this module that read the same frames."""
+    import bench
+    key = (W, H, step, tuple(variants))
+    if key not in _WHOLE:
+        _WHOLE[key] = _hybrid_vs_strict(dict(bench.WORKLOADS["fhd"], width=W, height=H, step_size=step), variants)
+        for rep, o in _WHOLE[key].items():
+            print(f"\n[hybrid {W}x{H} step {step}, repair {rep}] strict tiles {o['info']['strict_tiles']} of {o['info']['tiles']}, "
+                  f"repaired {o['info']['repaired_pixels']}; pixels beyond 1e-3: {o['beyond_1e3']}, max {o['max']:.3g}; steps "
+                  f"{o['steps']} vs {o['strict_steps']}; worst-channel RMSE " + ", ".join(f"{k} {float(v.max()):.3g}" for k, v in o["rmse"].items()))
+    return _WHOLE[key]
+
+
+def _check_whole(o, known, tag):
+    """Steps within 2e-4 of strict; every layer's worst-channel RMSE, the final layer's pixels beyond 1e-3 and its largest
+    difference within `known` (measured ceilings of the bars a frame is known to miss) or else the certified bars."""
+    assert abs(o["steps"] - o["strict_steps"]) <= 2e-4 * o["strict_steps"], (tag, o["steps"], o["strict_steps"])
+    for k, e in o["rmse"].items():
+        assert float(e.max()) <= known.get(k, MARGIN), (tag, k, e)
+    assert o["beyond_1e3"] <= known["beyond_1e3"] and o["max"] <= known["max"], (tag, o["beyond_1e3"], o["max"])
+
+
+# Measured on the 8k frame (7680 x 4320, step 0.05, bench scene): the differing pixels lie at b - b_c = 0.5 ... 2.1, outside the
+# strict band (whose classification is sound and exact there: test_gpu_hybrid_band.py) -- the fast arithmetic's rounding on
+# the 8k frame's finer disk texture, and with the guards off (the default at tilt 0) disk-colour flips at the algorithm's
+# own switches.  Ceilings a little above the measured values, so that a regression turns red.
+# guards off: 603 pixels beyond 1e-3, max 0.485, RMSE disk 2.0e-4, final 1.6e-4 (bg 1.4e-5, blur 1.5e-6 hold the margin);
+# guards on (16 812 pixels repaired): 589 pixels beyond 1e-3, max 0.013, RMSE disk 4.2e-5, final 3.2e-5 (bg 5.5e-6, blur 6.7e-7)
+KNOWN_8K = {-1: dict(disk=2.5e-4, final=2.0e-4, beyond_1e3=700, max=0.5),
+            1: dict(disk=5e-5, final=4e-5, beyond_1e3=700, max=0.016)}
+
+
+def test_hybrid_whole_8k_frame_vs_strict(hip_lib):
+    """BASELINE.json configs[3] (7680 x 4320, step 0.05: the bench's row-block workload) under hybrid, whole frame against
+    strict on one context, with the guards at their default (off at tilt 0) and forced on (hybrid_repair 1): ray-step
+    totals within 2e-4, bg and blur RMSE <= 3e-5 per channel, disk / final RMSE and the final layer's single pixels within
+    the measured ceilings of KNOWN_8K (the certified bars they miss: the xfail tests below); the guards repair pixels only
+    when on; strict tiles a small share.  The 8k ring tiles span ~0.02 r_s of b, a quarter of fhd's: tile_pad pads them least."""
+    res = _whole_frame(7680, 4320, 0.05, (-1, 1))
+    for rep, o in res.items():
+        _check_whole(o, KNOWN_8K[rep], f"8k repair {rep}")
+        assert (o["info"]["repaired_pixels"] > 0) == (rep == 1), (rep, o["info"])
+    assert res[-1]["info"]["strict_tiles"] / res[-1]["info"]["tiles"] <= 0.12, res[-1]["info"]
+
+
+@pytest.mark.xfail(strict=True, raises=AssertionError, reason="measured RMSE from strict: guards off disk 2.0e-4, final 1.6e-4 "
+                   "(beyond the 1e-4 north star); guards on disk 4.2e-5, final 3.2e-5 -- from pixels outside the strict band (KNOWN_8K)")
+@pytest.mark.parametrize("repair", [-1, 1])
+def test_hybrid_whole_8k_frame_within_the_certified_margin(repair, hip_lib):
+    """The certified bar on the 8k frame, guards at their default and forced on: every layer within 3e-5 per channel of strict."""
+    o = _whole_frame(7680, 4320, 0.05, (-1, 1))[repair]
+    for k, e in o["rmse"].items():
+        assert (e <= MARGIN).all(), (k, e)
+
+
+@pytest.mark.xfail(strict=True, raises=AssertionError, reason="measured: the guarded 8k frame keeps 589 pixels beyond 1e-3 "
+                   "of strict (max 0.013), outside the strict band (KNOWN_8K)")
+def test_hybrid_guarded_8k_frame_has_no_pixel_beyond_1e_3(hip_lib):
+    """The guarded fhd frame's bar at 8k: with hybrid_repair 1, no pixel of the final layer beyond 1e-3 of strict."""
+    o = _whole_frame(7680, 4320, 0.05, (-1, 1))[1]
+    assert o["beyond_1e3"] == 0, (o["beyond_1e3"], o["max"])
+
+
+# The tile-span sweep, default guards.  Measured misses of the certified bars (RMSE <= 3e-5, no pixel beyond 2e-2, pixels
+# beyond 1e-3 at the fhd rate), all from pixels far outside the band (b - b_c >= 0.4): 3840 x 2160 disk RMSE 6.5e-5 (max 0.067,
+# 9 pixels beyond 1e-3); 512 x 288 and 1366 x 766 one mirror pair each of disk-colour flips at b - b_c = 1.4 / 1.7 (max 0.24 /
+# 0.26; RMSE disk 8.6e-4 / 3.3e-4, final 8.7e-4 / 3.2e-4, blur 8.6e-5 at 512 x 288, whose bloom spreads the pair over 142 pixels
+# beyond 1e-3).  Ceilings a little above the measured values; the other sizes meet the bars.
+SWEEP = [(h * 16 // 9, h) for h in (2160, 1080, 720, 540, 432, 360, 288, 216)] + [(1366, 766)]
+KNOWN_SWEEP = {(3840, 2160): dict(disk=8e-5, beyond_1e3=12, max=0.08),
+               (512, 288): dict(disk=1.1e-3, final=1.1e-3, blur=1.1e-4, beyond_1e3=170, max=0.28),
+               (1366, 766): dict(disk=4e-4, final=4e-4, max=0.3)}
+
+
+def _fhd_bars(W, H):
+    return dict(beyond_1e3=max(4, int(4 * W * H / 2073600)), max=2e-2)
+
+
+@pytest.mark.parametrize("W,H", SWEEP, ids=[f"{w}x{h}" for w, h in SWEEP])
+def test_hybrid_whole_frames_vs_strict_across_tile_spans(W, H, hip_lib):
+    """The default pov from 216 to 2160 rows: the ring tiles' span of b crosses tile_pad's 0.1 and 0.2 r_s regimes.  Whole
+    frame hybrid (default guards) vs strict: steps within 2e-4; RMSE <= 3e-5 per channel, no pixel beyond 2e-2, pixels
+    beyond 1e-3 at most at the fhd frame's rate (4 per 2 073 600, and at least 4) -- or, for the sizes known to miss one of
+    these, within its measured ceiling (KNOWN_SWEEP; the certified bars themselves: the xfail test below)."""
+    o = _whole_frame(W, H, 0.1)[-1]
+    _check_whole(o, dict(_fhd_bars(W, H), **KNOWN_SWEEP.get((W, H), {})), f"{W}x{H}")
+
+
+@pytest.mark.xfail(strict=True, raises=AssertionError, reason="measured misses of the certified bars, pixels outside the strict band (KNOWN_SWEEP)")
+@pytest.mark.parametrize("W,H", sorted(KNOWN_SWEEP), ids=[f"{w}x{h}" for w, h in sorted(KNOWN_SWEEP)])
+def test_hybrid_whole_frames_across_tile_spans_meet_the_certified_bars(W, H, hip_lib):
+    o = _whole_frame(W, H, 0.1)[-1]
+    _check_whole(o, _fhd_bars(W, H), f"{W}x{H}")
+
+
+def test_hybrid_8k_row_bands_match_oracle(oracle, hip_lib):
+    """configs[3] under hybrid against the oracle on rows where a misclassified tile would show: the midline, the 8-row
+    tile bands where the ring b = b_c touches the tile rows at its top and bottom, and one through b = b_c + hi.  The bars
+    of the fhd whole frame (test_gpu_fullsize.test_hybrid_whole_frames_match_oracle): RMSE <= 3e-5 per channel, at most 4
+    pixels beyond 1e-3, none beyond 2e-2."""
+    import hybrid_band as hb
+    from bhr_amd import HipRenderer, _lib, scenes
+    W, H = 7680, 4320
+    cam, fov = [6.0, 0.0, 0.5], 90.0
+    kw = dict(step_size=0.05, r_max=10.0, r_disk_inner=2.0, r_disk_outer=15.0, disk_tilt=0.0, anti_alias="disabled")
+    u = hb.uniforms(cam, fov, W, H)
+    lo, hi = hb.effective_band(kw["step_size"])
+    ys = np.arange(H)
+    b = np.array([hb.pixel_geometry(u, W, H, y, y + 1)["b"][0].min() for y in ys[::8]])      # min of b along a row, every 8th row
+    inside = np.nonzero(b < hb.B_CRIT)[0]
+    top, bot = int(inside.min()) * 8, int(inside.max()) * 8
+    # refine to the exact first / last row whose minimum b is below b_c, and take its tile band
+    top = next(y for y in range(max(0, top - 8), top + 9) if hb.pixel_geometry(u, W, H, y, y + 1)["b"].min() < hb.B_CRIT)
+    bot = next(y for y in range(min(H - 1, bot + 8), bot - 9, -1) if hb.pixel_geometry(u, W, H, y, y + 1)["b"].min() < hb.B_CRIT)
+    outer = int(np.nonzero(b < hb.B_CRIT + hi)[0].min()) * 8
+    bands = [(2158, 2162), (top // 8 * 8, top // 8 * 8 + 8), (bot // 8 * 8, bot // 8 * 8 + 8), (outer // 8 * 8, outer // 8 * 8 + 8)]
+    sky, tex = scenes.analytic_skybox(), scenes.noisy_disk(256, 1024)
+    hip = HipRenderer(W, H, sky, tex, math="hybrid", frame_slots=1, **kw)
+    hip.render_async(cam, fov, skip_bloom=True)
+    lay = {"bg": hip.read_layer(_lib.LAYER_BG), "disk": hip.read_layer(_lib.LAYER_DISK)}
+    info = hip.hybrid_info()
+    hip.close()
+    assert (info["band_below"], info["band_above"]) == (lo, hi), info
+    ora = oracle.OracleRenderer(W, H, sky, tex, **kw)
+    for (r0, r1) in bands:
+        rbg, rdisk = ora.march(cam, fov, rows=(r0, r1), want_steps=False, skip_differentials=True)
+        ref = {"bg": rbg.transpose(1, 0, 2)[r0:r1], "disk": rdisk.transpose(1, 0, 2)[r0:r1]}
+        for k in ("bg", "disk"):
+            e, d = _frame_stats(lay[k][r0:r1], ref[k])
+            print(f"\n[hybrid 8k vs oracle, rows {r0}-{r1} {k}] RMSE {e}, max {d.max():.3g}, pixels > 1e-3: {int((d > 1e-3).sum())}")
+            assert (e <= MARGIN).all() and (d > 1e-3).sum() <= 4 and d.max() <= 2e-2, ((r0, r1), k, e, float(d.max()), int((d > 1e-3).sum()))

@@ -139,11 +139,12 @@ def test_subset_render_leaves_the_frame_unchanged(hip_lib):
         t.close()
 
 
-def test_8k_frame_in_eight_blocks_equals_one_context(hip_lib):
+@pytest.mark.parametrize("math", ["strict", "hybrid"])
+def test_8k_frame_in_eight_blocks_equals_one_context(math, hip_lib):
     """BASELINE.json configs[3] at full size: the 7680x4320 step-0.05 frame cut into 8 cost-balanced row blocks (all on
     device 0 here), pipelined schedule, against the same frame from one context: every pixel of the gathered f32 frame to
     1e-6 (the bloom sums its taps tile by tile), the quantised gather equal to the truncation of the f32 gather, ray-step
-    totals equal."""
+    totals equal.  Under both arithmetics: the bench's row-block leg runs hybrid blocks."""
     from bhr_amd import HipRenderer, multigpu
     W, H = 7680, 4320
     sky, tex = scenes.analytic_skybox(256, 512), scenes.noisy_disk(256, 1024)
@@ -151,11 +152,11 @@ def test_8k_frame_in_eight_blocks_equals_one_context(hip_lib):
     cam, fov = [6.0, 0.0, 0.5], 90.0
     per_row, band_rows = multigpu.probe_row_costs(W, H, cam, fov, **kw)
     blocks = multigpu.balanced_row_blocks(H, 8, per_row, band_rows, fixed_cost_per_row=0.1 * float(per_row.mean()))
-    full = HipRenderer(W, H, sky, tex, frame_slots=1, **kw)
+    full = HipRenderer(W, H, sky, tex, frame_slots=1, math=math, **kw)
     ref = full.render(cam, fov)
     ref_steps = full.counters()["ray_steps"]
     full.close()
-    tiles = [HipRenderer(W, H, sky, tex, rows=b, frame_slots=1, **kw) for b in blocks]
+    tiles = [HipRenderer(W, H, sky, tex, rows=b, frame_slots=1, math=math, **kw) for b in blocks]
     multigpu.group_render(tiles, cam, fov, gather="peer")
     got = multigpu.read_gathered(tiles)
     assert sum(t.counters()["ray_steps"] for t in tiles) == ref_steps
