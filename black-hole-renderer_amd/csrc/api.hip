@@ -53,9 +53,6 @@ void activate_slot(bhr_ctx *ctx, int k) {
     ctx->active_slot = k;
 }
 
-// experiment (BHR_STREAM_PAD="a,b,c"): idle streams created in front of frame slot 0's, slot 1's and the second march
-// streams -- HIP hands streams to its hardware queues in creation order, and which queues the frame slots land on decides
-// how their launches interleave
 // ---- do two streams sit on ONE hardware queue? ------------------------------------------------------------------------------
 // HIP hands its streams to a small pool of hardware queues (four per priority by default) by rules of its own; two streams
 // on one queue run their kernels strictly one after the other, two on different queues side by side -- which decides how the
@@ -95,10 +92,6 @@ int32_t bhr_streams_share_queue(hipStream_t a, hipStream_t b, int32_t *share) {
 }
 namespace {
 
-static void pad_streams(const bhr_ctx *ctx, int which) {
-    for (int k = 0; k < ctx->opt.stream_pad[which] && k < 8; ++k) { hipStream_t s; (void)hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }   // leaked on purpose
-}
-
 // the environment, once (bhr_create): nothing on the bhr_render path calls getenv
 static void read_options(bhr_options *o) {
     memset(o, 0, sizeof(*o));
@@ -123,17 +116,9 @@ static void read_options(bhr_options *o) {
     if (o->hybrid_streams != 1 && o->hybrid_streams != 2) o->hybrid_streams = -1;
     o->calibrate_streams = num("BHR_CALIBRATE_STREAMS", 1) != 0;
     o->hybrid_classify = num("BHR_HYBRID_CLASSIFY", 1) != 0;
-    o->hybrid_swap = num("BHR_HYBRID_SWAP", 1) != 0;
     o->mip_lds = num("BHR_MIP_LDS", 0) != 0;
-    { const char *e = getenv("BHR_TILE_ORDER"); o->tile_order_rows = e && e[0] == 'r'; }
-    o->tile_block = num("BHR_TILE_BLOCK", 256);
-    if (o->tile_block != 64 && o->tile_block != 128 && o->tile_block != 256) o->tile_block = 256;
     o->group_threads = num("BHR_GROUP_THREADS", -1);
     { const char *e = getenv("BHR_GROUP_SCHEDULE"); o->group_schedule = e && e[0] ? (e[0] == 's' ? 0 : 1) : -1; }
-    o->aux_priority = 0;
-    o->aux_per_slot = 1;
-    if (const char *e = getenv("BHR_AUX_STREAMS")) (void)sscanf(e, "%d,%d", &o->aux_priority, &o->aux_per_slot);
-    if (const char *e = getenv("BHR_STREAM_PAD")) (void)sscanf(e, "%d,%d,%d", &o->stream_pad[0], &o->stream_pad[1], &o->stream_pad[2]);
 }
 
 int32_t alloc_slot(bhr_ctx *ctx, int k) {
@@ -142,7 +127,7 @@ int32_t alloc_slot(bhr_ctx *ctx, int k) {
     const size_t W = ctx->cfg.width, rows = ctx->rows, R = ctx->bloom_R, px3 = rows * W * 3;
     if (!f.stream) {
         if (k == 0 && ctx->n_slots == 1) f.stream = ctx->scene_stream;
-        else { pad_streams(ctx, k == 0 ? 0 : 1); BHR_HIP(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking)); }
+        else BHR_HIP(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
     }
     if (!f.done) BHR_HIP(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
     int32_t rc = BHR_OK;
@@ -292,11 +277,7 @@ int32_t bhr_activate_slot(bhr_ctx *ctx, int32_t k) {
 }
 
 int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags) {
-    int mode = ctx->cfg.math_mode;
-    if (flags & BHR_FORCE_FAST) mode = BHR_MATH_FAST;
-    if (flags & BHR_FORCE_STRICT) mode = BHR_MATH_STRICT;
-    if (flags & BHR_FORCE_HYBRID) mode = BHR_MATH_HYBRID;
-    if (mode == BHR_MATH_HYBRID && (ctx->disk_source != BHR_DISK_TEXTURE || (flags & BHR_PERSISTENT))) mode = BHR_MATH_STRICT;
+    const int mode = bhr_resolve_math(ctx, flags);
     // the frame's post-pass follows its march: exact f32 chains under strict, the split-f16 matrix-core kernels (bloom.hip)
     // under fast and hybrid; BHR_BLOOM_SPLIT=0 / 1 forces either for every arithmetic
     int split = ctx->opt.bloom_split >= 0 ? ctx->opt.bloom_split : (mode != BHR_MATH_STRICT ? 1 : 0);
@@ -380,21 +361,14 @@ int32_t bhr_fail(int32_t code, const char *fmt, ...) {
 int32_t bhr_aux_fork(bhr_ctx *ctx) {
     const int k = ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0;
     if (!ctx->aux_streams[0]) {
-        int lo = 0, hi = 0;
-        BHR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));       // lo = least priority
-        // BHR_AUX_STREAMS="<priority>,<per slot>" (experiments of DESIGN 7): -1 least / 0 normal / 1 highest; 0 one stream
-        // for both frame slots / 1 one each
-        const int prio_sel = ctx->opt.aux_priority, per_slot = ctx->opt.aux_per_slot;
-        ctx->aux_per_slot = per_slot != 0;
-        const int prio = prio_sel == 0 ? 0 : (prio_sel > 0 ? hi : lo);
-        pad_streams(ctx, 2);
+        // normal priority, one stream per frame slot
         for (int q = 0; q < BHR_MAX_FRAME_SLOTS; ++q) {
-            BHR_HIP(hipStreamCreateWithPriority(&ctx->aux_streams[q], hipStreamNonBlocking, prio));
+            BHR_HIP(hipStreamCreateWithPriority(&ctx->aux_streams[q], hipStreamNonBlocking, 0));
             BHR_HIP(hipEventCreateWithFlags(&ctx->aux_fork[q], hipEventDisableTiming));
             BHR_HIP(hipEventCreateWithFlags(&ctx->aux_done[q], hipEventDisableTiming));
         }
     }
-    ctx->aux_stream = ctx->aux_streams[ctx->aux_per_slot ? k : 0];
+    ctx->aux_stream = ctx->aux_streams[k];
     BHR_HIP(hipEventRecord(ctx->aux_fork[k], ctx->stream));
     BHR_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork[k], 0));
     return BHR_OK;
@@ -518,9 +492,7 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
     int32_t v = 0, l = 0;
     if (cfg->math_mode != BHR_MATH_FAST && cfg->math_mode != BHR_MATH_STRICT && cfg->math_mode != BHR_MATH_HYBRID)
         return bail(bhr_fail(BHR_ERR_INVALID, "bhr_create: math_mode %d", cfg->math_mode));
-    if ((cfg->math_mode != BHR_MATH_FAST ? (cfg->anti_alias != 0 ? bhr_march_resources_strict_ilp(&v, &l, 1)
-                                                                   : bhr_march_resources_strict_ilp(&v, &l, 0))
-                                           : bhr_march_resources(&v, &l, cfg->anti_alias != 0)) == BHR_OK) {
+    if (bhr_march_resources(cfg->math_mode, cfg->anti_alias != 0, &v, &l) == BHR_OK) {
         ctx->counters.march_vgprs = v;
         ctx->counters.march_lds_bytes = l;
     }
@@ -805,7 +777,7 @@ int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
 // ragged end of its march run under the next frame's march -- and how well they do is decided by which HARDWARE queues HIP
 // gave the two slots' streams: measured on one binary, 2200-2360 fps (pairs of queues on which the second frame's
 // workgroups interleave with the first's from the start) or 2740-2770 (pairs on which they fill in behind), by nothing but
-// the number of idle streams the process had created before (tools/sweep_streams.py; round 3 shipped whatever the library's
+// the number of idle streams the process had created before (profiles/r04_stream_mapping.txt; round 3 shipped whatever the library's
 // own creation order happened to give).  HIP does not tell which queue a stream got and the good pairs are not simply
 // "different queues" (bhr_streams_share_queue finds those): so the context MEASURES.  Once eight two-slot frames have been
 // asked for, six candidate streams (created back to back: they go round HIP's queues) take turns as slot 1's stream for 24
@@ -1033,9 +1005,7 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     else if (n == "hybrid_streams") o.hybrid_streams = v == 1 ? 1 : (v == 2 ? 2 : -1);
     else if (n == "calibrate_streams") o.calibrate_streams = v != 0;
     else if (n == "hybrid_classify") o.hybrid_classify = v != 0;
-    else if (n == "hybrid_swap") o.hybrid_swap = v != 0;
     else if (n == "mip_lds") o.mip_lds = v != 0;
-    else if (n == "tile_order_rows") o.tile_order_rows = v != 0;
     else if (n == "group_threads") o.group_threads = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "group_schedule") o.group_schedule = v < 0 ? -1 : (v ? 1 : 0);
     else return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: unknown option '%s'", name);

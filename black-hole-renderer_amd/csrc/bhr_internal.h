@@ -32,7 +32,7 @@
 #define BHR_STEP_STRIDE 32          // in u64 words
 #define BHR_STEP_CELL (BHR_STEP_LANES * BHR_STEP_STRIDE)
 
-// hybrid march: guard bands around the algorithm's switches; a lane inside one is re-marched strict (march.hip: march_tile_hybrid)
+// hybrid march: guard bands around the algorithm's switches; a lane inside one is re-marched strict (march.hip: march_tile_guard_kernel)
 #ifndef BHR_LOD_GUARD
 #define BHR_LOD_GUARD 1e-2f         // |lod - level boundary|: the fast differentials are good to ~1e-5 in lod at the BASELINE views, but a camera
                                     // 15-50 r_s away behind a long lens carries them through hundreds of steps -- fuzzed 512x320 views flipped
@@ -100,17 +100,29 @@ struct BhrMarchArgs {
     int32_t fix_cap;
 };
 
-// A partial march launch: the tiles of `d_list` only.  Set by the callers that split one march into several launches --
-// bhr_launch_march_hybrid (strict list + fast list) and the pipelined row-block path (halo bands first) -- and consumed
-// by the three compilations of the launcher in march.hip.
+// A partial march launch: the tiles of `d_list` only.  Set by bhr_launch_march_hybrid for each of its launches (strict
+// list, fast list, fix list and the empty parts that bracket them) and consumed by bhr_launch_march (march_launch.hip).
 struct bhr_march_part {
     const int32_t *d_list;   // device list of this launch
-    const int32_t *h_list;   // the same list on the host (the hybrid launcher partitions it further)
     int32_t n;
-    int32_t id;              // which base list: 0 whole block, 1 halo bands, 2 the rows between them
     int32_t active, first, last;
-    int32_t math_resolved;   // the arithmetic has been chosen by the caller (the two launches of a hybrid march)
+    int32_t math;            // the arithmetic of this launch: BHR_MATH_FAST or BHR_MATH_STRICT
     int32_t repair;          // 1: the fast object's guard kernel (marks lanes on a discontinuity, appends them to the fix list); 2: the strict fix kernel over that list
+};
+
+// The march kernels by what they do; each compilation of march.hip returns its own instantiation of a name (or null) from
+// bhr_march_kernel_fast / _strict / _strict_ilp.  diff: the instantiation that integrates the ray differentials.
+enum bhr_march_kernel {
+    BHR_MK_VOLUME,        // march_tile_kernel<false, 2>: finite-thickness Disk V2 (never differentials)          fast, strict
+    BHR_MK_DV2,           // march_tile_kernel<diff, 1>: analytic Disk V2                                        fast, strict
+    BHR_MK_PERSISTENT,    // march_persistent_kernel<diff>: waves pull tiles from a queue (BHR_PERSISTENT)       fast, strict
+    BHR_MK_TILE,          // strict march_tile_kernel<diff, 0>; fast march_tile_kernel<true, 0> / march_tile_plain_fast
+    BHR_MK_TILE_COSTS,    // march_tile_kernel<diff, 0, true>: fills the row-cost profile (BHR_ROW_COSTS)          fast
+    BHR_MK_GUARD,         // march_tile_guard_kernel<diff>: the fast list of a hybrid march with guards           fast
+    BHR_MK_GUARD_COSTS,   // march_tile_guard_kernel<diff, true>: the same with row costs                         fast
+    BHR_MK_MIPSTAGED,     // march_tile_mipstaged_kernel: coarse mip levels in LDS (BHR_MIP_LDS, diff only)       fast
+    BHR_MK_TILE_ILP,      // march_tile_aa_ilp / march_tile_plain_ilp: the strict texture march                   strict_ilp
+    BHR_MK_FIX,           // march_fix_kernel<diff>: the fix list of a hybrid march                              strict_ilp
 };
 
 // what a frame's V pass stores (bhr_launch_bloom_v_rows); bhr_ensure_outputs re-runs it for layers nobody asked for up front
@@ -129,15 +141,10 @@ struct bhr_options {
     double hybrid_pad;          // share of its own span of b a small tile is padded by in the strict-band test (BHR_HYBRID_PAD, default 0.5; hybrid.hip: tile_pad)
     int32_t hybrid_streams;     // BHR_HYBRID_STREAMS: 1 both lists of a hybrid march on one stream, 2 on two, -1 (default) 1 where two frame slots overlap frames, else 2
     int32_t calibrate_streams;  // BHR_CALIBRATE_STREAMS: 1 (default) a two-slot context picks slot 1's stream by timing candidates (api.hip)
-    int32_t hybrid_swap;        // BHR_HYBRID_SWAP: 1 (default) the fast list on the frame's stream and the strict one on the second, 0 the other way round
     int32_t hybrid_classify;    // BHR_HYBRID_CLASSIFY: 1 (default) the tiles are classified and the launch order partitioned on the device, 0 on the host
     int32_t mip_lds;            // BHR_MIP_LDS=1: anti-aliased fast frames stage the coarse mip levels in LDS
-    int32_t tile_order_rows;    // BHR_TILE_ORDER=row: row-major march launch order (A/B runs)
-    int32_t tile_block;         // BHR_TILE_BLOCK: threads per march workgroup (64 / 128 / 256)
     int32_t group_threads;      // BHR_GROUP_THREADS: -1 by device layout (default), 0 / 1 one submitting thread / one per tile
     int32_t group_schedule;     // BHR_GROUP_SCHEDULE: -1 by flags (default), 0 serial, 1 pipelined
-    int32_t aux_priority, aux_per_slot;   // BHR_AUX_STREAMS="<priority>,<per slot>": the second march stream(s) of hybrid frames
-    int32_t stream_pad[3];      // BHR_STREAM_PAD="a,b,c": idle streams created in front of slot 0's, slot 1's, the second march streams (experiment)
 };
 
 // geometry of a context's split-f16 bloom buffers (bloom.hip)
@@ -264,11 +271,10 @@ struct bhr_ctx {
     int32_t *h_tile_order;     // host copy (malloc)
     int32_t tile_order_n;
     bhr_march_part part;       // partial launch in progress (inactive: whole block)
-    // second march stream (lowest priority): the other half of a split march -- the fast tiles of a hybrid march, the middle
-    // rows of a pipelined row block -- runs beside the first half instead of behind its ragged end (bhr_aux_fork / _join)
+    // second march stream (one per frame slot): the strict tiles of a two-stream hybrid march run on it beside the fast ones
+    // instead of ahead of them (bhr_aux_fork / _join)
     hipStream_t aux_stream;    // the active slot's second march stream (set by bhr_aux_fork)
     hipStream_t aux_streams[BHR_MAX_FRAME_SLOTS];
-    int32_t aux_per_slot;
     hipEvent_t aux_fork[BHR_MAX_FRAME_SLOTS], aux_done[BHR_MAX_FRAME_SLOTS];
     void *hybrid;              // hybrid.hip: tile classification cache
     unsigned int *fix_count;   // fix list of the hybrid march being launched (owned by hybrid.hip, per frame slot)
@@ -330,13 +336,14 @@ int32_t bhr_enter_frame(bhr_ctx *ctx);
 int32_t bhr_leave_frame(bhr_ctx *ctx);
 
 // launchers (each lives next to its kernels)
-int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);         // dispatches on math_mode
-int32_t bhr_launch_march_strict(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);  // march_strict.o
-int32_t bhr_march_resources_strict(int32_t *vgprs, int32_t *lds, int32_t diff);
-int32_t bhr_launch_march_strict_ilp(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);   // march_strict_ilp.o
-int32_t bhr_march_resources_strict_ilp(int32_t *vgprs, int32_t *lds, int32_t diff);
-int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);
-int32_t bhr_ensure_tile_order(bhr_ctx *ctx);                                               // march.o: builds d_/h_tile_order
+int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags);                          // march_launch.hip: BHR_MATH_* of a frame
+int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);         // march_launch.hip: every march launch
+int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds); // march_launch.hip: registers / LDS of the frame kernel
+const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff);                   // march.o
+const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff);                 // march_strict.o
+const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff);             // march_strict_ilp.o
+int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.o
+int32_t bhr_ensure_tile_order(bhr_ctx *ctx);                                           // march_launch.hip: builds d_/h_tile_order
 int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);     // hybrid.hip
 void bhr_hybrid_free(bhr_ctx *ctx);
 int32_t bhr_hybrid_active_list(bhr_ctx *ctx, const int32_t **list, int32_t *n);   // hybrid.o: the active slot's partitioned launch order (tests)
@@ -375,7 +382,6 @@ int32_t bhr_launch_background(bhr_ctx *ctx, float t);
 int32_t bhr_launch_compose(bhr_ctx *ctx, float t_offset, int32_t enable_rt, float color_temp);
 int32_t bhr_launch_fill(bhr_ctx *ctx, float *dst, int64_t n, float v);
 int32_t bhr_launch_noise(bhr_ctx *ctx, int64_t n, int32_t mode, int32_t octaves, float pers, float lac);
-int32_t bhr_march_resources(int32_t *vgprs, int32_t *lds, int32_t diff);
 int32_t bhr_launch_disk_v2(bhr_ctx *ctx, const bhr_disk_v2_params *p, const double *d_r, const double *d_z,
                            const double *d_phi, int64_t n, int32_t field, double *d_out, double *d_aux,
                            double *d_maxabs, double norm0, double norm1);

@@ -28,8 +28,6 @@ namespace {
 constexpr double B_CRIT = 2.598076211353316;   // 3 sqrt(3) / 2 r_s, r_s = 1
 constexpr double PLANE_SIN = 0.02;             // orbital planes within 1.1 degrees of the disk plane march strict (classify)
 
-constexpr int HYBRID_LISTS = 3;   // base lists a march can be launched over: whole block, halo bands, the rest (bhr_march_part.id)
-
 struct FixList {           // per frame slot: pixels the fast list's guard kernel leaves to the strict fix kernel
     unsigned int *d_count;
     int32_t *d_list;
@@ -38,7 +36,7 @@ struct FixList {           // per frame slot: pixels the fast list's guard kerne
 
 constexpr int LIST_RING = 4;
 struct SlotLists {
-    int32_t *d_list;       // the base list partitioned: strict tiles first (launch order kept), then the fast ones
+    int32_t *d_list;       // the context's tile order partitioned: strict tiles first (launch order kept), then the fast ones
     int32_t *h_pinned;
     hipEvent_t copied;     // the last upload from h_pinned
     double key[12];
@@ -54,7 +52,7 @@ struct SlotLists {
 };
 
 struct Hybrid {
-    SlotLists slot[BHR_MAX_FRAME_SLOTS][HYBRID_LISTS];
+    SlotLists slot[BHR_MAX_FRAME_SLOTS];
     FixList fix[BHR_MAX_FRAME_SLOTS];
     // last classification on the host
     std::vector<uint8_t> strict;   // per tile of the row block: marched strict
@@ -349,22 +347,20 @@ __global__ __launch_bounds__(PART_BLOCK) void hybrid_scatter_kernel(const int32_
 void bhr_hybrid_free(bhr_ctx *ctx) {
     Hybrid *h = (Hybrid *)ctx->hybrid;
     if (!h) return;
-    for (auto &row : h->slot)
-        for (auto &s : row) {
-            if (s.d_list) (void)hipFree(s.d_list);
-            if (s.h_pinned) (void)hipHostFree(s.h_pinned);
-            if (s.copied) (void)hipEventDestroy(s.copied);
-        }
+    for (auto &s : h->slot) {
+        if (s.d_list) (void)hipFree(s.d_list);
+        if (s.h_pinned) (void)hipHostFree(s.h_pinned);
+        if (s.copied) (void)hipEventDestroy(s.copied);
+    }
     for (auto &f : h->fix) {
         if (f.d_count) (void)hipFree(f.d_count);
         if (f.d_list) (void)hipFree(f.d_list);
     }
-    for (auto &row : h->slot)
-        for (auto &sl : row)
-            for (int k = 0; k < LIST_RING; ++k) {
-                if (sl.d_ring[k]) (void)hipFree(sl.d_ring[k]);
-                if (sl.used[k]) (void)hipEventDestroy(sl.used[k]);
-            }
+    for (auto &sl : h->slot)
+        for (int k = 0; k < LIST_RING; ++k) {
+            if (sl.d_ring[k]) (void)hipFree(sl.d_ring[k]);
+            if (sl.used[k]) (void)hipEventDestroy(sl.used[k]);
+        }
     if (h->cls_stream) { (void)hipStreamSynchronize(h->cls_stream); (void)hipStreamDestroy(h->cls_stream); }
     if (h->d_flags) (void)hipFree(h->d_flags);
     if (h->d_counts) (void)hipFree(h->d_counts);
@@ -377,9 +373,9 @@ void bhr_hybrid_free(bhr_ctx *ctx) {
 int32_t bhr_hybrid_active_list(bhr_ctx *ctx, const int32_t **list, int32_t *n) {
     Hybrid *h = (Hybrid *)ctx->hybrid;
     const int k = ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0;
-    if (!h || !h->slot[k][0].valid || !h->slot[k][0].d_active) return bhr_fail(BHR_ERR_STATE, "no hybrid march has run on this context's active slot");
-    *list = h->slot[k][0].d_active;
-    *n = h->slot[k][0].base_n;
+    if (!h || !h->slot[k].valid || !h->slot[k].d_active) return bhr_fail(BHR_ERR_STATE, "no hybrid march has run on this context's active slot");
+    *list = h->slot[k].d_active;
+    *n = h->slot[k].base_n;
     return BHR_OK;
 }
 
@@ -419,8 +415,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     if (!h) {
         h = new Hybrid();
         memset(h->slot, 0, sizeof(h->slot));
-        for (auto &row : h->slot)
-            for (auto &sl : row) sl.cur = -1;
+        for (auto &sl : h->slot) sl.cur = -1;
         h->n_tiles = 0;
         h->on_device = -1;
         memset(h->fix, 0, sizeof(h->fix));
@@ -437,12 +432,9 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     h->lo = 0.085;           // in the orbit's own b (classify): the band certified in round 3 on |pos x dir| at the 6 r_s pov,
     h->hi = 0.36;            // [2.478, 2.898], is [b_c - 0.084, b_c + 0.357] there
     if (ctx->opt.hybrid_band_set) { h->lo = ctx->opt.hybrid_band[0]; h->hi = ctx->opt.hybrid_band[1]; }   // BHR_HYBRID_BAND="lo,hi" at bhr_create, or bhr_set_option
-    // the list to split: the whole row block, or the sub-list of a pipelined launch (halo bands / the rest)
-    const bhr_march_part base = ctx->part;
-    const int32_t *base_list = base.active ? base.h_list : ctx->h_tile_order;
-    const int base_n = base.active ? base.n : ctx->tile_order_n;
-    const int id = base.active ? base.id : 0;
-    if (id < 0 || id >= HYBRID_LISTS || !base_list) return bhr_fail(BHR_ERR_INVALID, "hybrid march: bad base list %d", id);
+    // the list to split: the context's tile order
+    const int32_t *base_list = ctx->h_tile_order;
+    const int base_n = ctx->tile_order_n;
     double key[12];
     // the band was certified at step sizes up to 0.1; a coarser march amplifies more per step around the ring (a 0.3 march
     // lost a faint crossing at b_c + 0.59 that the binary64 evaluation keeps): the band widens with the step
@@ -454,14 +446,13 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     view_key(cam, lo, hi, pad_f, (double)ctx->cfg.disk_tilt_deg, key);
     const int n_tiles = ctx->tile_order_n;
     const bool on_device = ctx->opt.hybrid_classify != 0;
-    SlotLists &s = h->slot[ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0][id];
+    SlotLists &s = h->slot[ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0];
     const bool new_view = !h->valid || h->on_device != (int32_t)on_device || !same_view(h->key, key);
     if (on_device) {
-        const int32_t *d_base = base.active ? base.d_list : ctx->d_tile_order;
-        if (!d_base) return bhr_fail(BHR_ERR_INVALID, "hybrid march: the base list has no device copy");
+        const int32_t *d_base = ctx->d_tile_order;
         if (!h->cls_stream) {
             // highest priority: the host waits for these four kernels; and HIP keeps a pool of hardware queues per priority, so this
-            // stream does not move the frame streams' places in the normal-priority pool (api.hip: pad_streams)
+            // stream does not move the frame streams' places in the normal-priority pool
             int lo_p = 0, hi_p = 0;
             BHR_HIP(hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
             BHR_HIP(hipStreamCreateWithPriority(&h->cls_stream, hipStreamNonBlocking, hi_p));
@@ -570,18 +561,13 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     }
     const uint32_t f = flags & ~(BHR_FORCE_FAST | BHR_FORCE_STRICT | BHR_FORCE_HYBRID);
     bhr_march_part p;
-    p.h_list = nullptr;
-    p.id = id;
     p.active = 1;
-    p.math_resolved = 1;
-    p.repair = 0;
     // Two launches.  On ONE stream the fast list waits for the last strict wave (the chip drains in between); on TWO the
-    // fast tiles run on the context's low-priority second stream beside the strict ones and fill the slots they leave.
+    // strict tiles run on the context's second stream beside the fast ones, which fill the slots they leave.
     // The bracket (start event, counter clear / end event) is an empty first / last part on the frame's own stream.
     // one stream where two frame slots keep frames in flight (the other frame's kernels fill this one's gaps, and every further
     // stream is one more place in HIP's queue lottery: DESIGN 7), two where a frame runs alone (row blocks, one slot)
     int streams = ctx->opt.hybrid_streams > 0 ? ctx->opt.hybrid_streams : (ctx->n_slots > 1 && ctx->cur_slot >= 0 ? 1 : 2);
-    if (base.active) streams = 1;                    // a pipelined row block already runs its two halves on two streams
     if (s.n_strict == 0) streams = 1;                // nothing for a second stream to do (row blocks away from the hole's image)
     int32_t rc = BHR_OK;
     // The fast list's kernel carries guards: a lane that comes within a guard band of one of the algorithm's switches -- the
@@ -615,29 +601,28 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     ctx->fix_cap = repair ? fx.cap : 0;
     auto launch = [&](const int32_t *list, int n, int first, int last, int kind) -> int32_t {   // kind 0 strict list, 1 fast list, 2 fix list
         p.d_list = list; p.n = n; p.first = first; p.last = last;
+        p.math = kind == 1 ? BHR_MATH_FAST : BHR_MATH_STRICT;
         p.repair = kind == 0 ? 0 : (repair ? kind : 0);
         ctx->part = p;
-        return (kind == 0 || kind == 2) ? bhr_launch_march_strict(ctx, cam, f) : bhr_launch_march(ctx, cam, f);
+        return bhr_launch_march(ctx, cam, f);
     };
-    const int first0 = base.active ? base.first : 1, last0 = base.active ? base.last : 1;
     if (streams == 1) {
         // longest rays first: the strict tiles are the ones around the photon ring
-        rc = launch(s.d_active, s.n_strict, first0, 0, 0);
+        rc = launch(s.d_active, s.n_strict, 1, 0, 0);
         if (rc == BHR_OK && repair) rc = hipMemsetAsync(fx.d_count, 0, sizeof(unsigned int), ctx->stream) == hipSuccess ? BHR_OK : bhr_fail(BHR_ERR_HIP, "hipMemsetAsync failed");
-        if (rc == BHR_OK) rc = launch(s.d_active + s.n_strict, base_n - s.n_strict, 0, repair ? 0 : last0, 1);
-        if (rc == BHR_OK && repair) rc = launch(nullptr, 0, 0, last0, 2);
+        if (rc == BHR_OK) rc = launch(s.d_active + s.n_strict, base_n - s.n_strict, 0, repair ? 0 : 1, 1);
+        if (rc == BHR_OK && repair) rc = launch(nullptr, 0, 0, 1, 2);
     } else {
         hipStream_t main_stream = ctx->stream;
         rc = launch(nullptr, 0, 1, 0, 0);                                          // prologue on the frame's stream
         if (rc == BHR_OK) rc = bhr_aux_fork(ctx);
-        // which list rides the frame's own stream: the one that ends last, so that the post-pass follows it on the same
-        // hardware queue (a wait on another queue's event costs ~10 us after that queue's kernel has ended; on a finished one,
-        // nothing).  That is the fast list -- ten times the tiles of the strict one -- except under option "hybrid_swap" 0.
-        const bool fast_on_main = ctx->opt.hybrid_swap != 0;
-        if (fast_on_main) ctx->stream = ctx->aux_stream;
+        // the fast list -- ten times the tiles of the strict one, it ends last -- rides the frame's own stream, so that the
+        // post-pass follows it on the same hardware queue (a wait on another queue's event costs ~10 us after that queue's
+        // kernel has ended; on a finished one, nothing); the strict list runs on the second stream
+        ctx->stream = ctx->aux_stream;
         if (rc == BHR_OK) rc = launch(s.d_active, s.n_strict, 0, 0, 0);
         if (rc == BHR_OK) {
-            ctx->stream = fast_on_main ? main_stream : ctx->aux_stream;
+            ctx->stream = main_stream;
             if (repair && hipMemsetAsync(fx.d_count, 0, sizeof(unsigned int), ctx->stream) != hipSuccess) rc = bhr_fail(BHR_ERR_HIP, "hipMemsetAsync failed");
             if (rc == BHR_OK) rc = launch(s.d_active + s.n_strict, base_n - s.n_strict, 0, 0, 1);
             if (rc == BHR_OK && repair) rc = launch(nullptr, 0, 0, 0, 2);
@@ -646,7 +631,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
         if (rc == BHR_OK) rc = bhr_aux_join(ctx);
         if (rc == BHR_OK) rc = launch(nullptr, 0, 0, 1, 0);                        // epilogue: the end event
     }
-    ctx->part = base;
+    ctx->part.active = 0;
     ctx->fix_count = nullptr;
     ctx->fix_list = nullptr;
     ctx->fix_cap = 0;

@@ -25,20 +25,17 @@
 // v_rsq/v_rcp/v_sqrt instead of IEEE sqrt + divide inside the RK4 stages, FMA contraction, and the
 // re-use of |new_pos| as the next step's |pos| (same value in the reference).
 //
-// This file is compiled twice (csrc/Makefile):
-//   march.o         fast arithmetic  -- v_rsq/v_rcp/v_sqrt, FMA contraction, stage values shared
-//                                       between the main and the variational right-hand sides;
-//   march_strict.o  -DBHR_MARCH_STRICT=1 -ffp-contract=off -- every operation of the RK4 loop in
-//                   the reference's order with IEEE sqrt and divide, so that positions, step
-//                   counts and hit points are bit-identical to a strict f32 evaluation of
-//                   render.py:2854-3006 (selected with bhr_config.math_mode = 1).
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <utility>
-#include <vector>
-
+// This file holds device code only and is compiled three times (csrc/Makefile):
+//   march.o             fast arithmetic  -- v_rsq/v_rcp/v_sqrt, FMA contraction, stage values shared
+//                                           between the main and the variational right-hand sides;
+//   march_strict.o      -DBHR_MARCH_STRICT=1 -ffp-contract=off -- every operation of the RK4 loop in
+//                       the reference's order with IEEE sqrt and divide, so that positions, step
+//                       counts and hit points are bit-identical to a strict f32 evaluation of
+//                       render.py:2854-3006 (selected with bhr_config.math_mode = 1);
+//   march_strict_ilp.o  the strict source once more with the ILP-first machine scheduler (-DBHR_MARCH_ILP=1): the strict
+//                       texture kernels and the fix kernel of a hybrid march.
+// Each compilation instantiates only the kernels it launches and hands them to the one host launcher
+// (march_launch.hip) through a table: bhr_march_kernel_fast / _strict / _strict_ilp at the end of this file.
 #include "bhr_internal.h"
 #include "disk_v2_device.h"
 
@@ -52,20 +49,9 @@
 #define BHR_WAVE_STAMPS_BUILD 0
 #endif
 
-#if BHR_MARCH_STRICT && BHR_MARCH_ILP
-// third compilation: the strict source scheduled with -mllvm -amdgpu-sched-strategy=max-ilp.  Its two texture kernels
-// are launched (march_tile_plain_ilp, march_tile_aa_ilp, each with its own occupancy target): the plain one gains 4 %
-// from the ILP-first schedule, the AA one 1-2 % once held to 4 waves per SIMD (unconstrained it took 134 VGPRs and
-// lost 1.6 %); the fast build loses 3 % and keeps the default scheduler, as do the Disk V2 and persistent kernels.
-#define BHR_LAUNCH_MARCH bhr_launch_march_strict_ilp
-#define BHR_MARCH_RESOURCES bhr_march_resources_strict_ilp
-#elif BHR_MARCH_STRICT
-#define BHR_LAUNCH_MARCH bhr_launch_march_strict
-#define BHR_MARCH_RESOURCES bhr_march_resources_strict
-#else
-#define BHR_LAUNCH_MARCH bhr_launch_march
-#define BHR_MARCH_RESOURCES bhr_march_resources
-#endif
+// The third compilation's two texture kernels (march_tile_plain_ilp, march_tile_aa_ilp, each with its own occupancy target):
+// the plain one gains 4 % from the ILP-first schedule, the AA one 1-2 % once held to 4 waves per SIMD (unconstrained it took
+// 134 VGPRs and lost 1.6 %); the fast build loses 3 % and keeps the default scheduler, as do the Disk V2 and persistent kernels.
 
 namespace {
 
@@ -1071,7 +1057,7 @@ __device__ __forceinline__ void march_tile_body(const BhrMarchArgs &a, const int
     const int i = tx * 8 + (lane & 7);
     const int j = ty * 8 + (lane >> 3);
     const bool valid = tile < a.n_tiles && i < a.width && j < a.rows;
-    // (slot, tile, tx, ty are wave-uniform: march_tile_kernel / march_tiles_of_wave hand over a readfirstlane'd slot)
+    // (slot, tile, tx, ty are wave-uniform: march_tile_kernel / march_tile_of_wave hand over a readfirstlane'd slot)
 
 #if BHR_WAVE_STAMPS_BUILD
     const unsigned long long t_start = a.wave_stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -1187,11 +1173,8 @@ __global__ __launch_bounds__(256) void march_tile_mipstaged_kernel(BhrMarchArgs 
 }
 
 // The plain fast march (no differentials, texture source) as an entry of its own, so that its occupancy target can be set
-// without touching the other instantiations of the template: BHR_FAST_WAVES waves per SIMD (512 / waves registers per lane).
-#ifndef BHR_FAST_WAVES
-#define BHR_FAST_WAVES 6
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BHR_FAST_WAVES, BHR_FAST_WAVES))) void march_tile_plain_fast(BhrMarchArgs a) {
+// without touching the other instantiations of the template: 6 waves per SIMD (80 registers per lane).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void march_tile_plain_fast(BhrMarchArgs a) {
     march_tile_body<false, 0, false, false>(a, blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
 
@@ -1201,7 +1184,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DIFF ? 4 : 
 }
 #endif
 
-#if BHR_MARCH_STRICT && BHR_MARCH_ILP
+#if BHR_MARCH_ILP
 // Second half of the hybrid march's fast list: the pixels march_tile_guard_kernel put on the fix list, 64 per wave whatever
 // tile they came from, marched with the strict Ray -- bit-identical to math_mode 1.  Launched with a grid for the list's
 // capacity; waves beyond the count the device holds exit at once.
@@ -1234,32 +1217,24 @@ __global__ __launch_bounds__(256) void march_fix_kernel(BhrMarchArgs a) {
 // The ILP-scheduled object launches two kernels, each with the occupancy its register allocation should aim for
 // (A/B on fhd / 4k, isolated launches): plain texture march at 5 waves per SIMD (96 VGPRs, no spills; 0.697 -> 0.692 ms,
 // 6 waves: 0.695), AA march at 4 (128 VGPRs; 6.50 -> 6.39 ms at 4k against the default scheduler).
-// BHR_TPW tiles per wave, one after the other (a fixed, uniform trip count; wave w takes tiles w, w + W, w + 2W ... of
-// the launch order, W = waves in the launch).  Measured for the default: the per-wave timeline (tools/wave_timeline.py)
-// shows 88-92 % slot occupancy in the body of an fhd launch and a ~90 us ragged end; blocks of 64 threads (4x the
-// workgroups) take 0.89 ms instead of 0.69, so the workgroup dispatcher matters -- but 2 / 3 / 4 tiles per wave do not
-// buy it back (0.696 / 0.717 / 0.726 ms against 0.679 at one; 1501 fps with two frames in flight at 2, 1498 at 1).
-// One tile per wave stays.  A dynamic tile queue (resident waves popping tiles from a counter) was tried twice: with a
-// data-dependent exit it compiled into a non-terminating loop, with a fixed trip count it ran correctly at 1.08-1.23 ms
-// whatever the grid (each wave is latency-bound at ~15 cycles per instruction, so fewer, longer-lived waves only
-// lengthen the critical path); both removed.
-#ifndef BHR_TPW
-#define BHR_TPW 1
-#endif
+// One tile per wave: the per-wave timeline (tools/wave_timeline.py) shows 88-92 % slot occupancy in the body of an fhd
+// launch and a ~90 us ragged end; blocks of 64 threads (4x the workgroups) take 0.89 ms instead of 0.69, so the workgroup
+// dispatcher matters -- but 2 / 3 / 4 tiles per wave do not buy it back (0.696 / 0.717 / 0.726 ms against 0.679 at one).
+// A dynamic tile queue (resident waves popping tiles from a counter) was tried twice: with a data-dependent exit it compiled
+// into a non-terminating loop, with a fixed trip count it ran correctly at 1.08-1.23 ms whatever the grid (each wave is
+// latency-bound at ~15 cycles per instruction, so fewer, longer-lived waves only lengthen the critical path); both removed.
+// (The single-trip loop is the form the two kernels were tuned in, a loop over tiles per wave: without it hipcc allocates
+// their registers differently.)
 template <bool DIFF>
-__device__ __forceinline__ void march_tiles_of_wave(const BhrMarchArgs &a) {
-    const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n_waves = gridDim.x * (blockDim.x >> 6);
-#pragma unroll 1
-    for (int t = 0; t < BHR_TPW; ++t) {
-        const int slot = wave + t * n_waves;
+__device__ __forceinline__ void march_tile_of_wave(const BhrMarchArgs &a) {
+    const int slot = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (int t = 0; t < 1; ++t)
         if (slot < a.n_list) march_tile_body<DIFF, 0>(a, slot);
-    }
 }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void march_tile_plain_ilp(BhrMarchArgs a) { march_tiles_of_wave<false>(a); }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void march_tile_aa_ilp(BhrMarchArgs a) { march_tiles_of_wave<true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void march_tile_plain_ilp(BhrMarchArgs a) { march_tile_of_wave<false>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void march_tile_aa_ilp(BhrMarchArgs a) { march_tile_of_wave<true>(a); }
 
-#endif
-
+#else  // the fast and strict objects
 // ---------------------------------------------------------------------------
 // persistent schedule: waves pull pixels from a queue (8x8-tile-major order, so refilled lanes
 // stay spatially coherent) and refill dead lanes when fewer than `refill_below` are alive:
@@ -1366,315 +1341,48 @@ __global__ void selftest_kernel(unsigned long long *out, unsigned int div_rounds
     atomicAdd(out + 3, n);
 }
 #endif
+#endif  // BHR_MARCH_ILP
 
 }  // namespace
 
-#if BHR_MARCH_STRICT && !BHR_MARCH_ILP
+// ---- the kernels of this compilation, by the launcher's names (march_launch.hip); null: not in this object ----------
+#if BHR_MARCH_ILP
+const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff) {
+    switch (k) {
+    case BHR_MK_TILE_ILP: return diff ? (const void *)march_tile_aa_ilp : (const void *)march_tile_plain_ilp;
+    case BHR_MK_FIX: return diff ? (const void *)march_fix_kernel<true> : (const void *)march_fix_kernel<false>;
+    default: return nullptr;
+    }
+}
+#elif BHR_MARCH_STRICT
+const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff) {
+    switch (k) {
+    case BHR_MK_VOLUME: return (const void *)march_tile_kernel<false, 2>;
+    case BHR_MK_DV2: return diff ? (const void *)march_tile_kernel<true, 1> : (const void *)march_tile_kernel<false, 1>;
+    case BHR_MK_PERSISTENT: return diff ? (const void *)march_persistent_kernel<true> : (const void *)march_persistent_kernel<false>;
+    case BHR_MK_TILE: return diff ? (const void *)march_tile_kernel<true, 0> : (const void *)march_tile_kernel<false, 0>;
+    default: return nullptr;
+    }
+}
+
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4) {
     BHR_HIP(hipMemsetAsync(d_out4, 0, 4 * sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(selftest_kernel, dim3(2048), dim3(256), 0, ctx->stream, d_out4, 2048u);
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }
-#endif
-
-// Tile order of this context: 8x8 tiles sorted by the distance of their centre from the centre of the FULL
-// image (the camera looks at the hole, build_camera), nearest first.  Built once per context.
-static int32_t ensure_tile_order(bhr_ctx *ctx, int tiles_x, int n_tiles) {
-    if (ctx->d_tile_order && ctx->tile_order_n == n_tiles) return BHR_OK;
-    if (ctx->d_tile_order) (void)hipFree(ctx->d_tile_order);
-    ctx->d_tile_order = nullptr;
-    std::vector<std::pair<float, int>> key((size_t)n_tiles);
-    const float cx = 0.5f * (float)ctx->cfg.width, cy = 0.5f * (float)ctx->cfg.height;
-    for (int t = 0; t < n_tiles; ++t) {
-        const float x = (float)((t % tiles_x) * 8 + 4) - cx, y = (float)(ctx->cfg.row0 + (t / tiles_x) * 8 + 4) - cy;
-        key[(size_t)t] = {x * x + y * y, t};
+#else
+const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff) {
+    switch (k) {
+    case BHR_MK_VOLUME: return (const void *)march_tile_kernel<false, 2>;
+    case BHR_MK_DV2: return diff ? (const void *)march_tile_kernel<true, 1> : (const void *)march_tile_kernel<false, 1>;
+    case BHR_MK_PERSISTENT: return diff ? (const void *)march_persistent_kernel<true> : (const void *)march_persistent_kernel<false>;
+    case BHR_MK_TILE: return diff ? (const void *)march_tile_kernel<true, 0> : (const void *)march_tile_plain_fast;
+    case BHR_MK_TILE_COSTS: return diff ? (const void *)march_tile_kernel<true, 0, true> : (const void *)march_tile_kernel<false, 0, true>;
+    case BHR_MK_GUARD: return diff ? (const void *)march_tile_guard_kernel<true> : (const void *)march_tile_guard_kernel<false>;
+    case BHR_MK_GUARD_COSTS: return diff ? (const void *)march_tile_guard_kernel<true, true> : (const void *)march_tile_guard_kernel<false, true>;
+    case BHR_MK_MIPSTAGED: return diff ? (const void *)march_tile_mipstaged_kernel : nullptr;
+    default: return nullptr;
     }
-    std::stable_sort(key.begin(), key.end(),
-                     [](const std::pair<float, int> &l, const std::pair<float, int> &r) { return l.first < r.first; });
-    // the host keeps a copy: hybrid and pipelined launches partition this order into sub-lists (api.hip, hybrid.hip)
-    free(ctx->h_tile_order);
-    ctx->h_tile_order = (int32_t *)malloc((size_t)n_tiles * sizeof(int32_t));
-    if (!ctx->h_tile_order) return bhr_fail(BHR_ERR_NOMEM, "tile order: out of host memory");
-    for (int t = 0; t < n_tiles; ++t) ctx->h_tile_order[t] = key[(size_t)t].second;
-    BHR_HIP(hipMalloc((void **)&ctx->d_tile_order, (size_t)n_tiles * sizeof(int32_t)));
-    BHR_HIP(hipMemcpy(ctx->d_tile_order, ctx->h_tile_order, (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice));
-    ctx->tile_order_n = n_tiles;
-    return BHR_OK;
-}
-
-#if !BHR_MARCH_STRICT
-int32_t bhr_ensure_tile_order(bhr_ctx *ctx) {
-    const int tiles_x = (ctx->cfg.width + 7) / 8;
-    return ensure_tile_order(ctx, tiles_x, tiles_x * ((ctx->rows + 7) / 8));
 }
 #endif
-
-int32_t BHR_MARCH_RESOURCES(int32_t *vgprs, int32_t *lds, int32_t diff) {
-    hipFuncAttributes at;
-#if BHR_MARCH_STRICT && BHR_MARCH_ILP
-    const void *f = diff ? (const void *)march_tile_aa_ilp : (const void *)march_tile_plain_ilp;
-#elif !BHR_MARCH_STRICT
-    const void *f = diff ? (const void *)march_tile_kernel<true, 0> : (const void *)march_tile_plain_fast;
-#else
-    const void *f = diff ? (const void *)march_tile_kernel<true, 0> : (const void *)march_tile_kernel<false, 0>;
-#endif
-    BHR_HIP(hipFuncGetAttributes(&at, f));
-    *vgprs = at.numRegs;
-    *lds = (int32_t)at.sharedSizeBytes;
-    return BHR_OK;
-}
-
-int32_t BHR_LAUNCH_MARCH(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
-    const bhr_config &c = ctx->cfg;
-#if !BHR_MARCH_STRICT
-    if (!(ctx->part.active && (ctx->part.math_resolved || ctx->part.n <= 0))) {   // an empty part only records the bracket events
-        int mode = c.math_mode;
-        if (flags & BHR_FORCE_FAST) mode = BHR_MATH_FAST;
-        if (flags & BHR_FORCE_STRICT) mode = BHR_MATH_STRICT;
-        if (flags & BHR_FORCE_HYBRID) mode = BHR_MATH_HYBRID;
-        // hybrid = two launches over complementary tile lists (hybrid.hip); schedules and disk sources that have no
-        // list form run strict
-        if (mode == BHR_MATH_HYBRID && (ctx->disk_source != BHR_DISK_TEXTURE || (flags & BHR_PERSISTENT))) mode = BHR_MATH_STRICT;
-        // (the frame's post-pass kernels were chosen by bhr_frame_begin from the same decision: api.hip)
-        if (mode == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, cam, flags);
-        if (mode == BHR_MATH_STRICT) return bhr_launch_march_strict(ctx, cam, flags);
-    }
-#endif
-#if BHR_MARCH_STRICT && !BHR_MARCH_ILP
-    // the texture kernels (plain and AA) live in the ILP-scheduled object (see the top of this file)
-    if (ctx->disk_source == BHR_DISK_TEXTURE && !(flags & BHR_PERSISTENT))
-        return bhr_launch_march_strict_ilp(ctx, cam, flags);
-#endif
-    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
-    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_render: no disk texture set (bhr_set_disk_texture)");
-
-    BhrMarchArgs a;
-    for (int k = 0; k < 3; ++k) {
-        a.cp[k] = cam->pos[k];
-        a.cr[k] = cam->right[k];
-        a.cu[k] = cam->up[k];
-        a.cf[k] = cam->forward[k];
-    }
-    a.pw = cam->pixel_width;
-    a.ph = cam->pixel_height;
-    a.r_esc = cam->r_escape;
-    a.r_esc2 = a.r_esc * a.r_esc;
-    a.h_base = c.step_size;
-    a.r_inner = c.r_disk_inner;
-    a.r_outer = c.r_disk_outer;
-    a.t_offset = cam->t_offset;
-    // render.py:2808: tilt_rad = disk_tilt * pi / 180 in f32
-    a.tilt_rad = c.disk_tilt_deg * BHR_PI_F / 180.0f;
-    a.tan_t = tanf(a.tilt_rad);
-    a.sin_t = sinf(a.tilt_rad);
-    a.cos_t = cosf(a.tilt_rad);
-    a.aa_strength = c.aa_strength;
-    // orbital-plane basis shared by all rays (fast build): e1 = cam / |cam|
-    a.r0 = sqrtf(a.cp[0] * a.cp[0] + a.cp[1] * a.cp[1] + a.cp[2] * a.cp[2]);
-    for (int k = 0; k < 3; ++k) a.e1[k] = a.cp[k] / a.r0;
-    a.A = a.e1[2] - a.e1[1] * a.tan_t;
-    // render.py:2817-2818
-    a.max_iter = (int32_t)(a.r_esc * 40.0f / a.h_base);
-    a.max_affine = a.r_esc * 40.0f;
-    a.max_affine_u = a.max_affine / a.h_base;      // fast build: the affine parameter in units of h_base
-    a.width = c.width;
-    a.height = c.height;
-    a.row0 = c.row0;
-    a.rows = ctx->rows;
-    a.sc.skybox = ctx->d_skybox;
-    a.sc.sky_h = ctx->sky_h;
-    a.sc.sky_w = ctx->sky_w;
-    a.sc.mips = ctx->d_mips;
-    for (int l = 0; l < BHR_NUM_MIP_LEVELS; ++l) {
-        a.sc.mip_off[l] = ctx->mip_off[l];
-        a.sc.mip_h[l] = ctx->mip_h[l];
-        a.sc.mip_w[l] = ctx->mip_w[l];
-    }
-    a.sc.n_r = ctx->n_r;
-    a.sc.n_phi = ctx->n_phi;
-    a.bg = ctx->d_bg;
-    a.disk = ctx->d_disk;
-    a.diskp = nullptr;
-    a.dp_yb = a.dp_gp = a.dp_g0 = 0;
-    a.sum = nullptr;
-    if (ctx->bloom_split && ctx->d_pa && ctx->d_sum && !(flags & BHR_SKIP_BLOOM)) {      // split-f16 post-pass: the march feeds its H pass directly
-        bhr_split_geom g;
-        bhr_split_geometry(ctx, &g);
-        a.diskp = (_Float16 *)ctx->d_pa;
-        a.dp_yb = g.YB;
-        a.dp_gp = g.GP;
-        a.dp_g0 = g.g0;
-        a.sum = ctx->d_sum;
-        ctx->slots[ctx->active_slot].sum_valid = 1;
-    }
-    // timed launches (bhr_render) count into their ring slot; group launches into the scalar
-    const int slot = ctx->cur_slot;
-    a.ray_steps = slot >= 0 ? ctx->d_steps_ring + (size_t)slot * BHR_STEP_CELL : ctx->d_ray_steps;
-    a.queue = ctx->d_queue;
-    a.dv2 = ctx->disk_source != BHR_DISK_TEXTURE ? ctx->d_dv2_params : nullptr;
-    a.vol_absorption = ctx->vol_opts[0];
-    a.vol_grazing_gain = ctx->vol_opts[1];
-    a.vol_h_max = ctx->vol_opts[2];
-    a.vol_r_max = ctx->vol_opts[3];
-    a.vol_substeps = ctx->vol_substeps;
-    a.dv2_norm_shear = ctx->dv2_norm[0];
-    a.dv2_norm_hotspot = ctx->dv2_norm[1];
-    a.dv2_t_peak = ctx->dv2_norm[2];
-    a.tiles_x = (c.width + 7) / 8;
-    a.n_tiles = a.tiles_x * ((ctx->rows + 7) / 8);
-    a.n_list = a.n_tiles;
-    a.fix_count = ctx->fix_count;
-    a.mip_lds_from = -1;
-    a.fix_list = ctx->fix_list;
-    a.fix_cap = ctx->fix_cap;
-    // a partial launch (ctx->part: hybrid arithmetic, pipelined row bands) marches the tiles of a caller-made list; the
-    // first part records the start event and clears an untimed counter, the last part records the end event
-    const bhr_march_part part = ctx->part;
-    const bool first_part = !part.active || part.first, last_part = !part.active || part.last;
-    a.row_steps = nullptr;
-    if (flags & BHR_ROW_COSTS) {
-        // two profiles side by side: [0, n) the steps taken by the fast arithmetic, [n, 2n) by the strict one (a hybrid frame
-        // fills both, from its two tile lists); cleared by the frame's first part, on the stream every other part follows
-        const size_t n = (size_t)((ctx->rows + 7) / 8);
-        if (!ctx->d_row_steps) BHR_HIP(hipMalloc((void **)&ctx->d_row_steps, 2 * n * sizeof(unsigned long long)));
-        if (first_part) BHR_HIP(hipMemsetAsync(ctx->d_row_steps, 0, 2 * n * sizeof(unsigned long long), ctx->stream));
-        a.row_steps = ctx->d_row_steps + (BHR_MARCH_STRICT ? n : 0);
-    }
-    a.wave_stamps = nullptr;
-    // diagnostic (builds with -DBHR_WAVE_STAMPS_BUILD=1 only: the stamps cost the plain kernel three spilled registers):
-    // BHR_WAVE_STAMPS=<file> dumps per-wave start / end times of THIS launch (tools/wave_timeline.py)
-#if BHR_WAVE_STAMPS_BUILD
-    const char *stamp_path = getenv("BHR_WAVE_STAMPS");
-#else
-    const char *stamp_path = nullptr;                          // the shipped library reads no environment on the render path
-#endif
-    unsigned long long *d_stamps = nullptr;
-    if (stamp_path && stamp_path[0]) {
-        BHR_HIP(hipMalloc((void **)&d_stamps, (size_t)a.n_tiles * 4 * sizeof(unsigned long long)));
-        BHR_HIP(hipMemsetAsync(d_stamps, 0, (size_t)a.n_tiles * 4 * sizeof(unsigned long long), ctx->stream));
-        a.wave_stamps = d_stamps;
-    }
-    a.tile_order = nullptr;
-    if (part.active) {
-        a.tile_order = part.d_list;
-        a.n_list = part.n;
-    } else {
-        if (!ctx->opt.tile_order_rows) {                    // BHR_TILE_ORDER: "centre" (default) | "row": row-major, for A/B runs
-            BHR_TRY(ensure_tile_order(ctx, a.tiles_x, a.n_tiles));
-            a.tile_order = ctx->d_tile_order;
-        }
-    }
-
-    // anti_alias "disabled": the reference still integrates the differentials (skip_diff = 0 on
-    // the CLI path) but never reads them (render.py:2957-2959) => skipping them is pixel-identical.
-    const bool want_diff = c.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS);
-
-    // ring cells are cleared ahead of time (at reset, then by the previous frame's last kernel)
-    if (slot < 0 && first_part) BHR_HIP(hipMemsetAsync(a.ray_steps, 0, sizeof(unsigned long long) * BHR_STEP_CELL, ctx->stream));
-    if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(ctx->d_queue, 0, sizeof(unsigned int), ctx->stream));
-    // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
-    if (first_part) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 0] : ctx->ev[0], ctx->stream));
-    if (part.active && part.n <= 0 && part.repair != 2) {
-        // empty list: nothing to launch
-    } else if (!(flags & BHR_PERSISTENT) || a.dv2 || a.row_steps || part.active) {   // the persistent schedule has no Disk V2 / row-cost variant
-        // waves per block: a block keeps its CU slot until its slowest wave has finished, so small
-        // blocks shorten the tail; BHR_TILE_BLOCK overrides for experiments
-        const int bt = ctx->opt.tile_block;               // 256; BHR_TILE_BLOCK = 64 / 128 for experiments
-        const int wpb = bt / 64;
-        dim3 grid((a.n_list + wpb - 1) / wpb), block(bt);
-        if (ctx->disk_source == BHR_DISK_V2_VOLUME) {   // finite-thickness Disk V2: no texture footprint to track
-            hipLaunchKernelGGL((march_tile_kernel<false, 2>), grid, block, 0, ctx->stream, a);
-        } else if (a.dv2) {   // analytic Disk V2 source: its own instantiations
-            if (want_diff)
-                hipLaunchKernelGGL((march_tile_kernel<true, 1>), grid, block, 0, ctx->stream, a);
-            else
-                hipLaunchKernelGGL((march_tile_kernel<false, 1>), grid, block, 0, ctx->stream, a);
-#if BHR_MARCH_STRICT && BHR_MARCH_ILP
-        } else {
-            const int waves = (a.n_list + BHR_TPW - 1) / BHR_TPW;          // BHR_TPW tiles per wave
-            const dim3 g((waves + wpb - 1) / wpb);
-            if (part.active && part.repair == 2) {                          // the fix list of a hybrid march
-                const dim3 gf((a.fix_cap / 64 + wpb - 1) / wpb);
-                if (want_diff) hipLaunchKernelGGL(march_fix_kernel<true>, gf, block, 0, ctx->stream, a);
-                else hipLaunchKernelGGL(march_fix_kernel<false>, gf, block, 0, ctx->stream, a);
-            } else if (want_diff)
-                hipLaunchKernelGGL(march_tile_aa_ilp, g, block, 0, ctx->stream, a);
-            else
-                hipLaunchKernelGGL(march_tile_plain_ilp, g, block, 0, ctx->stream, a);
-        }
-#else
-#if !BHR_MARCH_STRICT
-        } else if (part.active && part.repair == 1) {           // fast list of a hybrid march: guards + fix list
-            if (a.row_steps) {                                  // the row-cost probe: the instantiations that count shading passes
-                if (want_diff) hipLaunchKernelGGL((march_tile_guard_kernel<true, true>), grid, block, 0, ctx->stream, a);
-                else hipLaunchKernelGGL((march_tile_guard_kernel<false, true>), grid, block, 0, ctx->stream, a);
-            } else if (want_diff) hipLaunchKernelGGL((march_tile_guard_kernel<true>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((march_tile_guard_kernel<false>), grid, block, 0, ctx->stream, a);
-        } else if (a.row_steps) {
-            if (want_diff) hipLaunchKernelGGL((march_tile_kernel<true, 0, true>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((march_tile_kernel<false, 0, true>), grid, block, 0, ctx->stream, a);
-#endif
-        } else if (want_diff) {
-#if !BHR_MARCH_STRICT
-            // BHR_MIP_LDS=1: the coarse mip levels through LDS where any of them fits 44 KB (see the kernel)
-            size_t staged_bytes = 0;
-            {
-                if (ctx->opt.mip_lds && !part.active && bt == 256) {
-                    const int last = 3;                                     // int(clamp(lod, 0, 3)): the coarsest level ever sampled
-                    for (int l = last; l >= 1; --l) {
-                        if (a.sc.mip_h[last] <= 0 || a.sc.mip_w[last] <= 0) break;                  // a texture too small to have it
-                        const size_t bytes = ((size_t)a.sc.mip_off[last] + (size_t)a.sc.mip_h[last] * a.sc.mip_w[last] - (size_t)a.sc.mip_off[l]) * sizeof(float4);
-                        if (bytes > 44 * 1024) break;                       // 64 KB per block less the 18 KB of parking slots
-                        a.mip_lds_from = l;
-                        staged_bytes = bytes;
-                    }
-                }
-            }
-            if (a.mip_lds_from >= 0) {
-                ctx->mip_lds_from = a.mip_lds_from;
-                hipLaunchKernelGGL(march_tile_mipstaged_kernel, grid, block, staged_bytes, ctx->stream, a);
-            } else {
-                ctx->mip_lds_from = -1;
-                hipLaunchKernelGGL((march_tile_kernel<true, 0>), grid, block, 0, ctx->stream, a);
-            }
-#else
-            hipLaunchKernelGGL((march_tile_kernel<true, 0>), grid, block, 0, ctx->stream, a);
-#endif
-        } else {
-#if !BHR_MARCH_STRICT
-            hipLaunchKernelGGL(march_tile_plain_fast, grid, block, 0, ctx->stream, a);
-#else
-            hipLaunchKernelGGL((march_tile_kernel<false, 0>), grid, block, 0, ctx->stream, a);
-#endif
-        }
-#endif
-    } else {
-        // enough resident waves to fill the chip; every wave drains the queue and exits
-        int blocks = (a.n_tiles + 3) / 4;
-        const int max_blocks = 256 * 8;
-        if (blocks > max_blocks) blocks = max_blocks;
-        if (blocks < 1) blocks = 1;
-        dim3 grid(blocks), block(256);
-        const int refill_below = 40;
-        if (want_diff)
-            hipLaunchKernelGGL(march_persistent_kernel<true>, grid, block, 0, ctx->stream, a, refill_below);
-        else
-            hipLaunchKernelGGL(march_persistent_kernel<false>, grid, block, 0, ctx->stream, a, refill_below);
-    }
-    BHR_HIP(hipGetLastError());
-    // group / tile renders (slot < 0) record the march's end only on request: the event is a ~5 us bubble between the march and
-    // the H pass of a tile whose whole tail is ~0.12 ms
-    if (last_part && (slot >= 0 || ctx->group_time_march)) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1], ctx->stream));
-    if (last_part) ctx->march_end_recorded = slot >= 0 || ctx->group_time_march;
-    if (d_stamps) {
-        std::vector<unsigned long long> h((size_t)a.n_tiles * 4);
-        BHR_HIP(hipMemcpyAsync(h.data(), d_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        BHR_HIP(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(d_stamps);
-        if (FILE *f = fopen(stamp_path, "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
-    }
-    ctx->last_steps_ptr = a.ray_steps;
-    ctx->counters.rays = (uint64_t)c.width * ctx->rows;
-    return BHR_OK;
-}

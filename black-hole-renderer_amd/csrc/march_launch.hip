@@ -1,0 +1,316 @@
+// march_launch.hip -- the host half of the ray march: every march launch goes through bhr_launch_march.
+//
+// march.hip is device code compiled three times (csrc/Makefile: fast, strict, strict with the ILP-first scheduler); each
+// object hands its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp).  This file resolves the
+// arithmetic, builds the kernel arguments, keeps the tile order, the ray-step counters and the timing events, and picks
+// the kernel of a launch (march_kernel).
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <xmmintrin.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "bhr_internal.h"
+
+#ifndef BHR_WAVE_STAMPS_BUILD
+#define BHR_WAVE_STAMPS_BUILD 0
+#endif
+
+namespace {
+
+// Tile order of this context: 8x8 tiles sorted by the distance of their centre from the centre of the FULL
+// image (the camera looks at the hole, build_camera), nearest first.  Built once per context.
+int32_t ensure_tile_order(bhr_ctx *ctx, int tiles_x, int n_tiles) {
+    if (ctx->d_tile_order && ctx->tile_order_n == n_tiles) return BHR_OK;
+    if (ctx->d_tile_order) (void)hipFree(ctx->d_tile_order);
+    ctx->d_tile_order = nullptr;
+    std::vector<std::pair<float, int>> key((size_t)n_tiles);
+    const float cx = 0.5f * (float)ctx->cfg.width, cy = 0.5f * (float)ctx->cfg.height;
+    for (int t = 0; t < n_tiles; ++t) {
+        const float x = (float)((t % tiles_x) * 8 + 4) - cx, y = (float)(ctx->cfg.row0 + (t / tiles_x) * 8 + 4) - cy;
+        key[(size_t)t] = {x * x + y * y, t};
+    }
+    std::stable_sort(key.begin(), key.end(),
+                     [](const std::pair<float, int> &l, const std::pair<float, int> &r) { return l.first < r.first; });
+    // the host keeps a copy: a hybrid march partitions this order into its strict and fast lists (hybrid.hip)
+    free(ctx->h_tile_order);
+    ctx->h_tile_order = (int32_t *)malloc((size_t)n_tiles * sizeof(int32_t));
+    if (!ctx->h_tile_order) return bhr_fail(BHR_ERR_NOMEM, "tile order: out of host memory");
+    for (int t = 0; t < n_tiles; ++t) ctx->h_tile_order[t] = key[(size_t)t].second;
+    BHR_HIP(hipMalloc((void **)&ctx->d_tile_order, (size_t)n_tiles * sizeof(int32_t)));
+    BHR_HIP(hipMemcpy(ctx->d_tile_order, ctx->h_tile_order, (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice));
+    ctx->tile_order_n = n_tiles;
+    return BHR_OK;
+}
+
+// The fast arithmetic's tilt and |cam| as its launches have always computed them (host code built with -ffast-math): the
+// tilt times the folded constant pi / 180, |cam| from the SSE reciprocal-square-root estimate and one Newton step.  Every
+// fast ray starts from 1 / |cam| and the tilt's tangent, so these bits reach every pixel of a fast frame.
+float fast_tilt_rad(float deg) { return deg * (BHR_PI_F * (1.0f / 180.0f)); }
+float fast_sqrt(float s) {
+#pragma clang fp contract(off)
+    if (fabsf(s) < 1.17549435e-38f) return 0.0f;               // below FLT_MIN the estimate is not used
+    const float y = _mm_cvtss_f32(_mm_rsqrt_ss(_mm_set_ss(s)));
+    const float sy = s * y;
+    return (sy * -0.5f) * (sy * y + -3.0f);
+}
+
+// The kernel of a launch and its grid (fn null: the part only records its bracket events).
+//
+//   arithmetic     request                                              kernel (object)
+//   any            hybrid part with n <= 0, not the fix list            none
+//   strict         hybrid fix list (part.repair == 2)                   march_fix_kernel<diff> (strict_ilp)
+//   fast / strict  Disk V2 volume source                                march_tile_kernel<false, 2> (own object)
+//   fast / strict  Disk V2 analytic source                              march_tile_kernel<diff, 1> (own object)
+//   fast / strict  BHR_PERSISTENT, texture, no row costs, no part       march_persistent_kernel<diff> (own object)
+//   strict         texture, BHR_PERSISTENT with row costs or a part     march_tile_kernel<diff, 0> (strict)
+//   strict         texture, otherwise                                   march_tile_aa_ilp / march_tile_plain_ilp (strict_ilp)
+//   fast           hybrid fast list with guards (part.repair == 1)      march_tile_guard_kernel<diff, row costs>
+//   fast           row costs                                            march_tile_kernel<diff, 0, true>
+//   fast           AA, mip_lds on, no part, a level fits 44 KB          march_tile_mipstaged_kernel (sets ctx->mip_lds_from)
+//   fast           AA otherwise                                         march_tile_kernel<true, 0> (ctx->mip_lds_from = -1)
+//   fast           plain                                                march_tile_plain_fast
+//
+// diff: anti_alias && !BHR_SKIP_DIFFERENTIALS.  Grids: blocks of 4 waves, a wave per tile of the launch's list; a wave per 64
+// entries of the fix list's capacity; the persistent kernel enough blocks to fill the chip.
+struct MarchKernel {
+    const void *fn = nullptr;
+    dim3 grid;
+    size_t lds = 0;
+};
+MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part &part, int math, uint32_t flags, bool diff) {
+    MarchKernel k;
+    k.grid = dim3((a.n_list + 3) / 4);
+    const bool persistent = (flags & BHR_PERSISTENT) != 0;
+    const auto own = math == BHR_MATH_FAST ? bhr_march_kernel_fast : bhr_march_kernel_strict;
+    if (part.active && part.n <= 0 && part.repair != 2) return k;
+    if (part.active && part.repair == 2) {
+        k.fn = bhr_march_kernel_strict_ilp(BHR_MK_FIX, diff);
+        k.grid = dim3((a.fix_cap / 64 + 3) / 4);
+        return k;
+    }
+    if (ctx->disk_source == BHR_DISK_V2_VOLUME) { k.fn = own(BHR_MK_VOLUME, 0); return k; }
+    if (a.dv2) { k.fn = own(BHR_MK_DV2, diff); return k; }
+    if (persistent && !a.row_steps && !part.active) {
+        k.fn = own(BHR_MK_PERSISTENT, diff);
+        k.grid = dim3(std::min(std::max((a.n_tiles + 3) / 4, 1), 256 * 8));
+        return k;
+    }
+    switch (math) {
+    case BHR_MATH_STRICT:
+        k.fn = persistent ? bhr_march_kernel_strict(BHR_MK_TILE, diff) : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff);
+        return k;
+    case BHR_MATH_FAST:
+        if (part.active && part.repair == 1) {
+            k.fn = bhr_march_kernel_fast(a.row_steps ? BHR_MK_GUARD_COSTS : BHR_MK_GUARD, diff);
+        } else if (a.row_steps) {
+            k.fn = bhr_march_kernel_fast(BHR_MK_TILE_COSTS, diff);
+        } else if (diff) {
+            // BHR_MIP_LDS=1: the coarse mip levels through LDS where any of them fits 44 KB (see the kernel)
+            if (ctx->opt.mip_lds && !part.active) {
+                const int last = 3;                                     // int(clamp(lod, 0, 3)): the coarsest level ever sampled
+                for (int l = last; l >= 1; --l) {
+                    if (a.sc.mip_h[last] <= 0 || a.sc.mip_w[last] <= 0) break;                  // a texture too small to have it
+                    const size_t bytes = ((size_t)a.sc.mip_off[last] + (size_t)a.sc.mip_h[last] * a.sc.mip_w[last] - (size_t)a.sc.mip_off[l]) * sizeof(float4);
+                    if (bytes > 44 * 1024) break;                       // 64 KB per block less the 18 KB of parking slots
+                    a.mip_lds_from = l;
+                    k.lds = bytes;
+                }
+            }
+            ctx->mip_lds_from = a.mip_lds_from;
+            k.fn = bhr_march_kernel_fast(a.mip_lds_from >= 0 ? BHR_MK_MIPSTAGED : BHR_MK_TILE, 1);
+        } else {
+            k.fn = bhr_march_kernel_fast(BHR_MK_TILE, 0);
+        }
+        return k;
+    }
+    return k;
+}
+
+}  // namespace
+
+// The arithmetic of a march: the context's math_mode unless the call forces one.  Hybrid is launches over complementary tile
+// lists (hybrid.hip); the schedules and disk sources that have no list form run strict.  bhr_frame_begin picks the frame's
+// post-pass kernels from the same decision (api.hip).
+int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags) {
+    int32_t mode = ctx->cfg.math_mode;
+    if (flags & BHR_FORCE_FAST) mode = BHR_MATH_FAST;
+    if (flags & BHR_FORCE_STRICT) mode = BHR_MATH_STRICT;
+    if (flags & BHR_FORCE_HYBRID) mode = BHR_MATH_HYBRID;
+    if (mode == BHR_MATH_HYBRID && (ctx->disk_source != BHR_DISK_TEXTURE || (flags & BHR_PERSISTENT))) mode = BHR_MATH_STRICT;
+    return mode;
+}
+
+int32_t bhr_ensure_tile_order(bhr_ctx *ctx) {
+    const int tiles_x = (ctx->cfg.width + 7) / 8;
+    return ensure_tile_order(ctx, tiles_x, tiles_x * ((ctx->rows + 7) / 8));
+}
+
+// registers / LDS of the kernel that marches a whole texture frame: the fast object's under fast arithmetic, the ILP
+// object's under strict and hybrid (bhr_create reports them)
+int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds) {
+    const void *f = math == BHR_MATH_FAST ? bhr_march_kernel_fast(BHR_MK_TILE, diff) : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff);
+    hipFuncAttributes at;
+    BHR_HIP(hipFuncGetAttributes(&at, f));
+    *vgprs = at.numRegs;
+    *lds = (int32_t)at.sharedSizeBytes;
+    return BHR_OK;
+}
+
+int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
+    const bhr_config &c = ctx->cfg;
+    // a partial launch (ctx->part: one list of a hybrid march) marches the tiles of a caller-made list under the arithmetic the
+    // caller chose; the first part records the start event and clears an untimed counter, the last part records the end event
+    const bhr_march_part part = ctx->part;
+    const int math = part.active ? part.math : bhr_resolve_math(ctx, flags);
+    if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, cam, flags);
+    const bool fast = math == BHR_MATH_FAST;
+    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
+    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_render: no disk texture set (bhr_set_disk_texture)");
+
+    BhrMarchArgs a;
+    for (int k = 0; k < 3; ++k) {
+        a.cp[k] = cam->pos[k];
+        a.cr[k] = cam->right[k];
+        a.cu[k] = cam->up[k];
+        a.cf[k] = cam->forward[k];
+    }
+    a.pw = cam->pixel_width;
+    a.ph = cam->pixel_height;
+    a.r_esc = cam->r_escape;
+    a.r_esc2 = a.r_esc * a.r_esc;
+    a.h_base = c.step_size;
+    a.r_inner = c.r_disk_inner;
+    a.r_outer = c.r_disk_outer;
+    a.t_offset = cam->t_offset;
+    // render.py:2808: tilt_rad = disk_tilt * pi / 180 in f32
+    a.tilt_rad = fast ? fast_tilt_rad(c.disk_tilt_deg) : c.disk_tilt_deg * BHR_PI_F / 180.0f;
+    a.tan_t = tanf(a.tilt_rad);
+    a.sin_t = sinf(a.tilt_rad);
+    a.cos_t = cosf(a.tilt_rad);
+    a.aa_strength = c.aa_strength;
+    // orbital-plane basis shared by all rays (fast build): e1 = cam / |cam|
+    const float r0sq = a.cp[0] * a.cp[0] + a.cp[1] * a.cp[1] + a.cp[2] * a.cp[2];
+    a.r0 = fast ? fast_sqrt(r0sq) : sqrtf(r0sq);
+    for (int k = 0; k < 3; ++k) a.e1[k] = a.cp[k] / a.r0;
+    a.A = a.e1[2] - a.e1[1] * a.tan_t;
+    // render.py:2817-2818
+    a.max_iter = (int32_t)(a.r_esc * 40.0f / a.h_base);
+    a.max_affine = a.r_esc * 40.0f;
+    a.max_affine_u = a.max_affine / a.h_base;      // fast build: the affine parameter in units of h_base
+    a.width = c.width;
+    a.height = c.height;
+    a.row0 = c.row0;
+    a.rows = ctx->rows;
+    a.sc.skybox = ctx->d_skybox;
+    a.sc.sky_h = ctx->sky_h;
+    a.sc.sky_w = ctx->sky_w;
+    a.sc.mips = ctx->d_mips;
+    for (int l = 0; l < BHR_NUM_MIP_LEVELS; ++l) {
+        a.sc.mip_off[l] = ctx->mip_off[l];
+        a.sc.mip_h[l] = ctx->mip_h[l];
+        a.sc.mip_w[l] = ctx->mip_w[l];
+    }
+    a.sc.n_r = ctx->n_r;
+    a.sc.n_phi = ctx->n_phi;
+    a.bg = ctx->d_bg;
+    a.disk = ctx->d_disk;
+    a.diskp = nullptr;
+    a.dp_yb = a.dp_gp = a.dp_g0 = 0;
+    a.sum = nullptr;
+    if (ctx->bloom_split && ctx->d_pa && ctx->d_sum && !(flags & BHR_SKIP_BLOOM)) {      // split-f16 post-pass: the march feeds its H pass directly
+        bhr_split_geom g;
+        bhr_split_geometry(ctx, &g);
+        a.diskp = (_Float16 *)ctx->d_pa;
+        a.dp_yb = g.YB;
+        a.dp_gp = g.GP;
+        a.dp_g0 = g.g0;
+        a.sum = ctx->d_sum;
+        ctx->slots[ctx->active_slot].sum_valid = 1;
+    }
+    // timed launches (bhr_render) count into their ring slot; group launches into the scalar
+    const int slot = ctx->cur_slot;
+    a.ray_steps = slot >= 0 ? ctx->d_steps_ring + (size_t)slot * BHR_STEP_CELL : ctx->d_ray_steps;
+    a.queue = ctx->d_queue;
+    a.dv2 = ctx->disk_source != BHR_DISK_TEXTURE ? ctx->d_dv2_params : nullptr;
+    a.vol_absorption = ctx->vol_opts[0];
+    a.vol_grazing_gain = ctx->vol_opts[1];
+    a.vol_h_max = ctx->vol_opts[2];
+    a.vol_r_max = ctx->vol_opts[3];
+    a.vol_substeps = ctx->vol_substeps;
+    a.dv2_norm_shear = ctx->dv2_norm[0];
+    a.dv2_norm_hotspot = ctx->dv2_norm[1];
+    a.dv2_t_peak = ctx->dv2_norm[2];
+    a.tiles_x = (c.width + 7) / 8;
+    a.n_tiles = a.tiles_x * ((ctx->rows + 7) / 8);
+    a.n_list = a.n_tiles;
+    a.fix_count = ctx->fix_count;
+    a.mip_lds_from = -1;
+    a.fix_list = ctx->fix_list;
+    a.fix_cap = ctx->fix_cap;
+    const bool first_part = !part.active || part.first, last_part = !part.active || part.last;
+    a.row_steps = nullptr;
+    if (flags & BHR_ROW_COSTS) {
+        // two profiles side by side: [0, n) the steps taken by the fast arithmetic, [n, 2n) by the strict one (a hybrid frame
+        // fills both, from its two tile lists); cleared by the frame's first part, on the stream every other part follows
+        const size_t n = (size_t)((ctx->rows + 7) / 8);
+        if (!ctx->d_row_steps) BHR_HIP(hipMalloc((void **)&ctx->d_row_steps, 2 * n * sizeof(unsigned long long)));
+        if (first_part) BHR_HIP(hipMemsetAsync(ctx->d_row_steps, 0, 2 * n * sizeof(unsigned long long), ctx->stream));
+        a.row_steps = ctx->d_row_steps + (fast ? 0 : n);
+    }
+    a.wave_stamps = nullptr;
+    // diagnostic (builds with -DBHR_WAVE_STAMPS_BUILD=1 only: the stamps cost the plain kernel three spilled registers):
+    // BHR_WAVE_STAMPS=<file> dumps per-wave start / end times of THIS launch (tools/wave_timeline.py)
+#if BHR_WAVE_STAMPS_BUILD
+    const char *stamp_path = getenv("BHR_WAVE_STAMPS");
+#else
+    const char *stamp_path = nullptr;                          // the shipped library reads no environment on the render path
+#endif
+    unsigned long long *d_stamps = nullptr;
+    if (stamp_path && stamp_path[0]) {
+        BHR_HIP(hipMalloc((void **)&d_stamps, (size_t)a.n_tiles * 4 * sizeof(unsigned long long)));
+        BHR_HIP(hipMemsetAsync(d_stamps, 0, (size_t)a.n_tiles * 4 * sizeof(unsigned long long), ctx->stream));
+        a.wave_stamps = d_stamps;
+    }
+    if (part.active) {
+        a.tile_order = part.d_list;
+        a.n_list = part.n;
+    } else {
+        BHR_TRY(ensure_tile_order(ctx, a.tiles_x, a.n_tiles));
+        a.tile_order = ctx->d_tile_order;
+    }
+
+    // anti_alias "disabled": the reference still integrates the differentials (skip_diff = 0 on
+    // the CLI path) but never reads them (render.py:2957-2959) => skipping them is pixel-identical.
+    const bool want_diff = c.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS);
+
+    // ring cells are cleared ahead of time (at reset, then by the previous frame's last kernel)
+    if (slot < 0 && first_part) BHR_HIP(hipMemsetAsync(a.ray_steps, 0, sizeof(unsigned long long) * BHR_STEP_CELL, ctx->stream));
+    if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(ctx->d_queue, 0, sizeof(unsigned int), ctx->stream));
+    // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
+    if (first_part) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 0] : ctx->ev[0], ctx->stream));
+    const MarchKernel k = march_kernel(ctx, a, part, math, flags, want_diff);
+    if (k.fn) {
+        int refill_below = 40;                                 // persistent schedule: refill a wave below 40 live lanes
+        void *args[] = {&a, &refill_below};                    // (the second argument is the persistent kernel's alone)
+        (void)hipLaunchKernel(k.fn, k.grid, dim3(256), args, k.lds, ctx->stream);
+    }
+    BHR_HIP(hipGetLastError());
+    // group / tile renders (slot < 0) record the march's end only on request: the event is a ~5 us bubble between the march and
+    // the H pass of a tile whose whole tail is ~0.12 ms
+    if (last_part && (slot >= 0 || ctx->group_time_march)) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1], ctx->stream));
+    if (last_part) ctx->march_end_recorded = slot >= 0 || ctx->group_time_march;
+    if (d_stamps) {
+        std::vector<unsigned long long> h((size_t)a.n_tiles * 4);
+        BHR_HIP(hipMemcpyAsync(h.data(), d_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        BHR_HIP(hipStreamSynchronize(ctx->stream));
+        (void)hipFree(d_stamps);
+        if (FILE *f = fopen(stamp_path, "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
+    }
+    ctx->last_steps_ptr = a.ray_steps;
+    ctx->counters.rays = (uint64_t)c.width * ctx->rows;
+    return BHR_OK;
+}

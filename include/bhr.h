@@ -267,16 +267,13 @@ BHR_API int32_t bhr_set_outputs(bhr_ctx *ctx, uint32_t mask);
  *                                         frames and on two where a frame runs alone; 1 / 2 force
  *   "calibrate_streams" BHR_CALIBRATE_STREAMS 1 (default) a context with two frame slots times six candidate streams for slot 1 on
  *                                         its ninth frame and keeps the fastest (~0.15 s once; csrc/api.hip: calibrate_slot_streams)
- *   "hybrid_swap"     BHR_HYBRID_SWAP     1 (default) the fast list of a two-stream hybrid march on the frame's own stream (the
- *                                         post-pass follows it on one hardware queue), the strict list on the second; 0 swapped
  *   "hybrid_classify" BHR_HYBRID_CLASSIFY 1 (default) a view change classifies the tiles and partitions the launch order on the
  *                                         device (~0.05 ms whatever the size), 0 on the submitting thread (the same lists)
  *   "mip_lds"         BHR_MIP_LDS         1 anti-aliased fast frames stage the coarse mip levels in LDS
- *   "tile_order_rows" BHR_TILE_ORDER=row  1 row-major march launch order
  *   "group_threads"   BHR_GROUP_THREADS   -1 one submitting thread per tile where the tiles sit on distinct devices, 0 / 1 force
  *   "group_schedule"  BHR_GROUP_SCHEDULE  -1 by flags, else pipelined where a halo copy can hide (exact-f32 post-pass on distinct
  *                                         devices) and serial otherwise; 0 serial, 1 pipelined (explicit flags still win)
- * (bhr_create only: BHR_FRAME_SLOTS, BHR_TILE_BLOCK, BHR_AUX_STREAMS, BHR_STREAM_PAD.) */
+ * (bhr_create only: BHR_FRAME_SLOTS.) */
 BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
 /* Diagnostics (tests): the split-f16 post-pass's packed intermediates of the last frame as raw bytes -- which = 0 the H pass's
  * input (csrc/bloom.hip: pa), 1 its output / the V pass's input (pb) -- and the layout's geometry: geom[10] = {NT, n_tx, WP, YB,
