@@ -457,6 +457,7 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
     ctx->rows = cfg->row1 - cfg->row0;
     ctx->bloom_R = (int32_t)(cfg->width * 0.02);  // int(self.width * 0.02), render.py:3914
     ctx->mip_lds_from = -1;
+    ctx->ss = 1;
 
     auto bail = [&](int32_t rc) { bhr_destroy(ctx); return rc; };
     if (hipSetDevice(cfg->device) != hipSuccess) return bail(bhr_fail(BHR_ERR_HIP, "hipSetDevice(%d) failed", cfg->device));
@@ -878,6 +879,8 @@ static int32_t calibrate_slot_streams(bhr_ctx *ctx, const bhr_camera *cam, uint3
 
 int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_render: null argument");
+    if (ctx->ss > 1 && (flags & (BHR_PERSISTENT | BHR_ROW_COSTS)))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_render: BHR_PERSISTENT and BHR_ROW_COSTS are not available with supersampling (factor %d)", ctx->ss);
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     if (ctx->n_slots > 1 && ctx->opt.calibrate_streams && !ctx->streams_calibrated && !ctx->calibrating &&
         !(flags & (BHR_PERSISTENT | BHR_ROW_COSTS)) && ++ctx->two_slot_frames > 8)
@@ -1009,6 +1012,29 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     else if (n == "group_threads") o.group_threads = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "group_schedule") o.group_schedule = v < 0 ? -1 : (v ? 1 : 0);
     else return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: unknown option '%s'", name);
+    return BHR_OK;
+}
+
+int32_t bhr_set_supersample(bhr_ctx *ctx, int32_t k) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_supersample: null ctx");
+    if (k != 1 && k != 2 && k != 4 && k != 8) return bhr_fail(BHR_ERR_INVALID, "bhr_set_supersample: factor %d (1, 2, 4 or 8)", k);
+    if (k > 1 && ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_set_supersample: a row-block context (rows %d of %d) renders one sample per pixel", ctx->rows, ctx->cfg.height);
+    if ((int64_t)k * k * ctx->cfg.width * ctx->cfg.height >= ((int64_t)1 << 31))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_set_supersample: %d x %d rays of a %dx%d frame exceed 2^31", k, k, ctx->cfg.width, ctx->cfg.height);
+    if (k == ctx->ss) return BHR_OK;
+    // the tile order, the hybrid lists and the fix lists belong to the marched frame: the frames in flight still march over them
+    BHR_TRY(bhr_enter(ctx));
+    for (auto &f : ctx->slots)
+        if (f.stream) BHR_HIP(hipStreamSynchronize(f.stream));
+    for (hipStream_t s : ctx->aux_streams)
+        if (s) BHR_HIP(hipStreamSynchronize(s));
+    BHR_HIP(hipStreamSynchronize(ctx->scene_stream));
+    bhr_hybrid_free(ctx);
+    if (ctx->d_tile_order) BHR_HIP(hipFree(ctx->d_tile_order));
+    ctx->d_tile_order = nullptr;
+    ctx->tile_order_n = 0;
+    ctx->ss = k;
     return BHR_OK;
 }
 

@@ -74,7 +74,7 @@ struct BhrMarchArgs {
     float aa_strength;
     float max_affine, max_affine_u;   // max_affine_u = max_affine / h_base (fast build)
     int32_t max_iter;
-    int32_t width, height;   // full image
+    int32_t width, height;   // full image -- the FINE frame under supersampling (ss > 1), as are row0, rows and the tile grid
     int32_t row0, rows;      // this context's row block
     BhrScene sc;
     float *bg;               // (rows, width, 3)
@@ -98,6 +98,10 @@ struct BhrMarchArgs {
     unsigned int *fix_count; // hybrid march: pixels the guard kernel handed over to the strict fix kernel
     int32_t *fix_list;
     int32_t fix_cap;
+    // supersampling (bhr_set_supersample): k = ss rays per output pixel along x and y, 2^ss_log2; 1 outside the ss kernels
+    int32_t ss, ss_log2;
+    float ss_inv;            // 1 / k^2
+    int32_t out_width, out_rows;   // the output frame's row block: the store pitch and rows of bg / disk / sum
 };
 
 // A partial march launch: the tiles of `d_list` only.  Set by bhr_launch_march_hybrid for each of its launches (strict
@@ -269,7 +273,8 @@ struct bhr_ctx {
     unsigned long long *d_row_steps;   // ray-steps per 8-row band of the last BHR_ROW_COSTS launch
     int32_t *d_tile_order;     // march launch order of the 8x8 tiles
     int32_t *h_tile_order;     // host copy (malloc)
-    int32_t tile_order_n;
+    int32_t tile_order_n, tile_order_ss;   // ... built for this many tiles of the frame marched with this supersampling factor
+    int32_t ss;                // bhr_set_supersample: k x k rays per pixel (1, 2, 4, 8)
     bhr_march_part part;       // partial launch in progress (inactive: whole block)
     // second march stream (one per frame slot): the strict tiles of a two-stream hybrid march run on it beside the fast ones
     // instead of ahead of them (bhr_aux_fork / _join)
@@ -302,6 +307,23 @@ struct bhr_ctx {
     int32_t group_time_march;  // group / tile renders: also record the march-end event (BHR_GROUP_TIME_MARCH); off, the tile's stream carries no event between march and H pass
     int32_t march_end_recorded;
 };
+
+// The frame the march marches: the context's own, or under supersampling (ctx->ss = k > 1) the one k times finer along
+// both axes, at pixel pitch / k.  The tile grid, the tile order, the hybrid classification and the fix lists live on it.
+struct bhr_fine_frame {
+    int32_t width, height, row0, rows;
+};
+inline bhr_fine_frame bhr_fine(const bhr_ctx *ctx) {
+    const int32_t k = ctx->ss;
+    return {ctx->cfg.width * k, ctx->cfg.height * k, ctx->cfg.row0 * k, ctx->rows * k};
+}
+// k is a power of two: the fine pitch is exact, and the pitch of build_camera(k W, k H) bit for bit
+inline bhr_camera bhr_fine_camera(const bhr_ctx *ctx, const bhr_camera *cam) {
+    bhr_camera c = *cam;
+    c.pixel_width /= (float)ctx->ss;
+    c.pixel_height /= (float)ctx->ss;
+    return c;
+}
 
 // error plumbing (api.hip)
 int32_t bhr_fail(int32_t code, const char *fmt, ...);
@@ -339,9 +361,9 @@ int32_t bhr_leave_frame(bhr_ctx *ctx);
 int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags);                          // march_launch.hip: BHR_MATH_* of a frame
 int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);         // march_launch.hip: every march launch
 int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds); // march_launch.hip: registers / LDS of the frame kernel
-const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff);                   // march.o
-const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff);                 // march_strict.o
-const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff);             // march_strict_ilp.o
+const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);       // march.o (ss: the supersampled twin)
+const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.o
+const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.o
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.o
 int32_t bhr_ensure_tile_order(bhr_ctx *ctx);                                           // march_launch.hip: builds d_/h_tile_order
 int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);     // hybrid.hip

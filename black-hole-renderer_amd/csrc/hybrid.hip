@@ -116,9 +116,11 @@ __host__ __device__ inline double tile_pad(double span, double pad_f) {
     return (pad_f + (1.0 - pad_f) * t) * span + 1e-3;
 }
 
-// strict[t] = 1 for the tiles of this row block whose rays may have b in [b_c - lo, b_c + hi]
+// strict[t] = 1 for the tiles of this row block whose rays may have b in [b_c - lo, b_c + hi]; the tiles and `cam` are those of the
+// marched frame (bhr_fine, bhr_fine_camera)
 void classify(const bhr_ctx *ctx, const bhr_camera *cam, double lo, double hi, double pad_f, std::vector<uint8_t> &strict) {
-    const int W = ctx->cfg.width, H = ctx->cfg.height, row0 = ctx->cfg.row0, rows = ctx->rows;
+    const bhr_fine_frame fr = bhr_fine(ctx);
+    const int W = fr.width, H = fr.height, row0 = fr.row0, rows = fr.rows;
     const int tiles_x = (W + 7) / 8, tiles_y = (rows + 7) / 8;
     double cp[3], cr[3], cu[3], cf[3], tl[3];
     for (int k = 0; k < 3; ++k) { cp[k] = cam->pos[k]; cr[k] = cam->right[k]; cu[k] = cam->up[k]; cf[k] = cam->forward[k]; }
@@ -404,12 +406,19 @@ extern "C" int32_t bhr_hybrid_repairs(bhr_ctx *ctx, int32_t out[2]) {
     unsigned int n = 0;
     BHR_HIP(hipMemcpyAsync(&n, fx.d_count, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
     BHR_HIP(hipStreamSynchronize(ctx->stream));
+    // the list holds rays; under supersampling whole k x k groups of them, one per output pixel
+    const unsigned int group = (unsigned int)(ctx->ss * ctx->ss);
+    n /= group;
     out[0] = (int32_t)(n > 0x7fffffffu ? 0x7fffffffu : n);
-    out[1] = fx.cap;
+    out[1] = fx.cap / (int32_t)group;
     return BHR_OK;
 }
 
-int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
+int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_t flags) {
+    // the lists, the classification and the view key are those of the marched frame (supersampling: the fine one)
+    const bhr_camera fine_cam = bhr_fine_camera(ctx, out_cam);
+    const bhr_camera *cam = &fine_cam;
+    const bhr_fine_frame fr = bhr_fine(ctx);
     BHR_TRY(bhr_ensure_tile_order(ctx));
     Hybrid *h = (Hybrid *)ctx->hybrid;
     if (!h) {
@@ -479,7 +488,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
             if (s.used_set[nxt]) BHR_HIP(hipStreamWaitEvent(h->cls_stream, s.used[nxt], 0));
             if (new_view) {
                 ClassifyArgs ca;
-                const int W = ctx->cfg.width, H = ctx->cfg.height;
+                const int W = fr.width, H = fr.height;
                 double cf[3];
                 for (int k = 0; k < 3; ++k) { ca.cp[k] = cam->pos[k]; ca.cr[k] = cam->right[k]; ca.cu[k] = cam->up[k]; cf[k] = cam->forward[k]; }
                 ca.pw = cam->pixel_width; ca.ph = cam->pixel_height;
@@ -490,8 +499,8 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
                 ca.nrm[0] = 0.0; ca.nrm[1] = -sin(tilt); ca.nrm[2] = cos(tilt);
                 ca.cpn = ca.cp[0] * ca.nrm[0] + ca.cp[1] * ca.nrm[1] + ca.cp[2] * ca.nrm[2];
                 ca.lo = lo; ca.hi = hi; ca.pad_f = pad_f;
-                ca.W = W; ca.rows = ctx->rows; ca.row0 = ctx->cfg.row0;
-                ca.tiles_x = (W + 7) / 8; ca.tiles_y = (ctx->rows + 7) / 8;
+                ca.W = W; ca.rows = fr.rows; ca.row0 = fr.row0;
+                ca.tiles_x = (W + 7) / 8; ca.tiles_y = (fr.rows + 7) / 8;
                 ca.far_cam = ca.r0sq > 9.0;
                 if ((long long)ca.tiles_x * ca.tiles_y != n_tiles) return bhr_fail(BHR_ERR_STATE, "hybrid march: %d x %d tiles, launch order of %d", ca.tiles_x, ca.tiles_y, n_tiles);
                 BHR_HIP(hipMemsetAsync(h->d_total + 1, 0, sizeof(int32_t), h->cls_stream));
@@ -587,7 +596,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     const int slot_k = ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0;
     FixList &fx = h->fix[slot_k];
     if (repair && !fx.d_list) {
-        const long long px = (long long)ctx->cfg.width * ctx->rows;
+        const long long px = (long long)fr.width * fr.rows;        // rays: a multiple of 256 is one of k^2 too
         // an eighth of the block's pixels (measured shares: 0.1-0.4 % on the BASELINE views, up to 3 % on fuzzed anti-aliased
         // ones with the 1e-2 level guard); the guard kernel counts past it and bhr_hybrid_repairs tells
         fx.cap = (int32_t)(px / 8 < 4096 ? 4096 : (px / 8 > (1 << 23) ? (1 << 23) : px / 8));
@@ -604,7 +613,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
         p.math = kind == 1 ? BHR_MATH_FAST : BHR_MATH_STRICT;
         p.repair = kind == 0 ? 0 : (repair ? kind : 0);
         ctx->part = p;
-        return bhr_launch_march(ctx, cam, f);
+        return bhr_launch_march(ctx, out_cam, f);
     };
     if (streams == 1) {
         // longest rays first: the strict tiles are the ones around the photon ring

@@ -484,17 +484,25 @@ __device__ __forceinline__ void volume_segment(const BhrMarchArgs &a, Shade &sh,
     }
 }
 
-// render.py:3008-3018: background through the accumulated opacity + clamped disk layer.  (i, j) = column, local row.
-__device__ __forceinline__ void write_pixel(const BhrMarchArgs &a, int i, int j, bool escaped, V3 esc_dir, const Shade &sh) {
+// render.py:3008-3018: background through the accumulated opacity + clamped disk layer -- the two values a ray leaves
+__device__ __forceinline__ void pixel_values(const BhrMarchArgs &a, bool escaped, V3 esc_dir, const Shade &sh, float bk[3], float dk[3]) {
     V3 bg = mk(0, 0, 0);
     if (escaped) bg = sample_skybox(a.sc, normalized(esc_dir));
     float k = 1.0f - sh.alpha_total;
-    size_t o = ((size_t)j * a.width + i) * 3;
-    const float bk[3] = {__fmul_rn(bg.x, k), __fmul_rn(bg.y, k), __fmul_rn(bg.z, k)};
+    bk[0] = __fmul_rn(bg.x, k);
+    bk[1] = __fmul_rn(bg.y, k);
+    bk[2] = __fmul_rn(bg.z, k);
+    dk[0] = fminf(fmaxf(sh.accum.x, 0.0f), 1.0f);
+    dk[1] = fminf(fmaxf(sh.accum.y, 0.0f), 1.0f);
+    dk[2] = fminf(fmaxf(sh.accum.z, 0.0f), 1.0f);
+}
+
+// Stores the pixel (i, j) = column, local row of a frame `width` pixels wide.
+__device__ __forceinline__ void store_pixel(const BhrMarchArgs &a, int i, int j, int width, const float bk[3], const float dk[3]) {
+    size_t o = ((size_t)j * width + i) * 3;
     a.bg[o + 0] = bk[0];
     a.bg[o + 1] = bk[1];
     a.bg[o + 2] = bk[2];
-    const float dk[3] = {fminf(fmaxf(sh.accum.x, 0.0f), 1.0f), fminf(fmaxf(sh.accum.y, 0.0f), 1.0f), fminf(fmaxf(sh.accum.z, 0.0f), 1.0f)};
     a.disk[o + 0] = dk[0];
     a.disk[o + 1] = dk[1];
     a.disk[o + 2] = dk[2];
@@ -522,6 +530,39 @@ __device__ __forceinline__ void write_pixel(const BhrMarchArgs &a, int i, int j,
             q[(size_t)(2 * c + 1) * part] = (_Float16)(v - (float)hi);
         }
     }
+}
+
+__device__ __forceinline__ void write_pixel(const BhrMarchArgs &a, int i, int j, bool escaped, V3 esc_dir, const Shade &sh) {
+    float bk[3], dk[3];
+    pixel_values(a, escaped, esc_dir, sh, bk, dk);
+    store_pixel(a, i, j, a.width, bk, dk);
+}
+
+// Supersampling (bhr_set_supersample, a.ss = k > 1): the march runs on the fine frame, k x k rays per output pixel, and
+// resolves each group inside the wave.  The values of the group's rays are summed by a butterfly -- lane-xor masks
+// 1 .. k/2 along x, then ystride .. ystride k/2 along y (ystride 8 in an 8x8 tile, k on a fix list) -- which is a pairwise
+// tree over each sub-sample row and then one over the row sums; both lanes of a pair hold the same sum (f32 addition
+// commutes).  The product with 1/k^2 is exact.  Every lane of the wave must be here; `have`: the lane holds a ray, `store`:
+// its group is to be stored, by the lane at sub-sample (0, 0); (i, j) is the lane's fine pixel.
+template <class RAY>
+__device__ __forceinline__ void resolve_store(const BhrMarchArgs &a, const RAY &ray, bool have, bool store, int i, int j, int ystride) {
+    float v[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (have) ray.values(a, v, v + 3);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        asm volatile("" : "+v"(v[c]));         // the products are rounded before they are summed (no contraction into the adds)
+        for (int m = 1; m < a.ss; m <<= 1) {
+            v[c] = v[c] + __shfl_xor(v[c], m, BHR_WAVE);
+            asm volatile("" : "+v"(v[c]));     // ... and the tree keeps its order
+        }
+        for (int m = ystride; m < ystride * a.ss; m <<= 1) {
+            v[c] = v[c] + __shfl_xor(v[c], m, BHR_WAVE);
+            asm volatile("" : "+v"(v[c]));
+        }
+        v[c] = v[c] * a.ss_inv;
+    }
+    const int io = i >> a.ss_log2, jo = j >> a.ss_log2;
+    if (store && ((i | j) & (a.ss - 1)) == 0 && io < a.out_width && jo < a.out_rows) store_pixel(a, io, jo, a.out_width, v, v + 3);
 }
 
 // Pixel -> ray (render.py:2811-2840).  Returns the unit direction; dx1/dy1 = directions through
@@ -745,6 +786,7 @@ struct Ray {
     }
     __device__ __forceinline__ void finish(const BhrMarchArgs &a) { write_pixel(a, pix % a.width, pix / a.width, escaped(), d, sh); }
     __device__ __forceinline__ void finish_at(const BhrMarchArgs &a, int i, int j) { write_pixel(a, i, j, escaped(), d, sh); }
+    __device__ __forceinline__ void values(const BhrMarchArgs &a, float bk[3], float dk[3]) const { pixel_values(a, escaped(), d, sh, bk, dk); }
 };
 
 #else
@@ -1022,6 +1064,7 @@ struct Ray {
     }
     __device__ __forceinline__ void finish(const BhrMarchArgs &a) { write_pixel(a, pix % a.width, pix / a.width, escaped(), to3d(du, dw), sh); }
     __device__ __forceinline__ void finish_at(const BhrMarchArgs &a, int i, int j) { write_pixel(a, i, j, escaped(), to3d(du, dw), sh); }
+    __device__ __forceinline__ void values(const BhrMarchArgs &a, float bk[3], float dk[3]) const { pixel_values(a, escaped(), to3d(du, dw), sh, bk, dk); }
 };
 #endif  // BHR_MARCH_STRICT
 
@@ -1045,7 +1088,9 @@ __device__ __forceinline__ unsigned long long wave_sum_u32(unsigned int v) {
 // GUARD (the fast list of a hybrid march, fast object only): a lane that came within a guard band of one of the
 // algorithm's switches (Shade.unsure) does not write its pixel; it appends it to the context's fix list, which
 // march_fix_kernel (strict objects) marches again with the strict Ray.
-template <bool DIFF, int SRC = 0, bool GUARD = false, bool COSTS = true>
+// SS (supersampled instantiations, a.ss > 1): the tile is one of the fine frame, its k x k groups are resolved in the wave
+// (resolve_store); the guard appends whole groups.
+template <bool DIFF, int SRC = 0, bool GUARD = false, bool COSTS = true, bool SS = false>
 __device__ __forceinline__ void march_tile_body(const BhrMarchArgs &a, const int slot) {
     const int lane = threadIdx.x & 63;
     // one 8x8 tile per wave; `slot` is its position in the launch order
@@ -1118,19 +1163,37 @@ __device__ __forceinline__ void march_tile_body(const BhrMarchArgs &a, const int
         bool again = false;
         if (GUARD) {
             again = valid2 && ray.sh.unsure != 0;
+            if (SS) {                                  // a group is re-marched whole when any of its rays is flagged
+                int u = again ? 1 : 0;
+                for (int m = 1; m < a.ss; m <<= 1) u |= __shfl_xor(u, m, BHR_WAVE);
+                for (int m = 8; m < 8 * a.ss; m <<= 1) u |= __shfl_xor(u, m, BHR_WAVE);
+                again = valid2 && u != 0;
+            }
             const unsigned long long m = __ballot(again);
             if (m) {                                   // wave-aggregated append
                 const int lane2 = t2 & 63, first = __ffsll((long long)m) - 1;
-                unsigned int base = 0;
-                if (lane2 == first) base = atomicAdd(a.fix_count, (unsigned int)__popcll(m));
-                base = __shfl(base, first, BHR_WAVE);
-                const unsigned int at = base + (unsigned int)__popcll(m & ((1ull << lane2) - 1ull));
+                unsigned int base = 0, at;
+                if (SS) {
+                    // k^2 consecutive entries per group, in sub-sample order (sy k + sx), groups in the order of their (0, 0) lanes
+                    const int km = a.ss - 1, sx = lane2 & km, sy = (lane2 >> 3) & km;
+                    const unsigned long long lead = __ballot(again && sx == 0 && sy == 0);
+                    if (lane2 == first) base = atomicAdd(a.fix_count, (unsigned int)__popcll(lead) << (2 * a.ss_log2));
+                    base = __shfl(base, first, BHR_WAVE);
+                    const int l0 = lane2 - sx - 8 * sy;
+                    at = base + ((unsigned int)__popcll(lead & ((1ull << l0) - 1ull)) << (2 * a.ss_log2)) + (unsigned int)((sy << a.ss_log2) + sx);
+                } else {
+                    if (lane2 == first) base = atomicAdd(a.fix_count, (unsigned int)__popcll(m));
+                    base = __shfl(base, first, BHR_WAVE);
+                    at = base + (unsigned int)__popcll(m & ((1ull << lane2) - 1ull));
+                }
+                // (with SS the count and the capacity are multiples of k^2: a group is listed whole or not at all)
                 if (again && at < (unsigned int)a.fix_cap) a.fix_list[at] = j2 * a.width + i2;
                 else again = false;                    // list full: the fast pixel stands
             }
             if (again) ray.step_count = 0;             // its steps are counted by the strict re-march
         }
-        if (valid2 && !again) ray.finish_at(a, i2, j2);
+        if (SS) resolve_store(a, ray, valid2, valid2 && !again, i2, j2, 8);
+        else if (valid2 && !again) ray.finish_at(a, i2, j2);
     }
     // a lane executes one step per loop iteration: its step count is the number of steps it executed (0: no ray)
     unsigned long long tot = wave_sum_u32((unsigned int)ray.step_count);
@@ -1156,6 +1219,12 @@ __global__ __launch_bounds__(256) void march_tile_kernel(BhrMarchArgs a) {
     march_tile_body<DIFF, SRC, false, COSTS>(a, blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
 
+// The supersampled twins of the tile kernels (a.ss > 1) are instantiations of their own: the k = 1 kernels stay as they were.
+template <bool DIFF, int SRC = 0>
+__global__ __launch_bounds__(256) void march_tile_ss_kernel(BhrMarchArgs a) {
+    march_tile_body<DIFF, SRC, false, false, true>(a, blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+}
+
 #if !BHR_MARCH_STRICT
 // BASELINE.json's north star asks for "mipmap levels staged through LDS".  Opt-in (BHR_MIP_LDS=1, fast arithmetic,
 // anti-aliased views): every block copies the coarse levels of the packed mip stack -- as many of levels 3, 2, 1 as fit
@@ -1177,10 +1246,17 @@ __global__ __launch_bounds__(256) void march_tile_mipstaged_kernel(BhrMarchArgs 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void march_tile_plain_fast(BhrMarchArgs a) {
     march_tile_body<false, 0, false, false>(a, blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void march_tile_plain_fast_ss(BhrMarchArgs a) {
+    march_tile_body<false, 0, false, false, true>(a, blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+}
 
 template <bool DIFF, bool COSTS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DIFF ? 4 : 5, DIFF ? 4 : 5))) void march_tile_guard_kernel(BhrMarchArgs a) {
     march_tile_body<DIFF, 0, true, COSTS>(a, blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+}
+template <bool DIFF>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DIFF ? 4 : 5, DIFF ? 4 : 5))) void march_tile_guard_ss_kernel(BhrMarchArgs a) {
+    march_tile_body<DIFF, 0, true, false, true>(a, blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
 #endif
 
@@ -1188,8 +1264,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DIFF ? 4 : 
 // Second half of the hybrid march's fast list: the pixels march_tile_guard_kernel put on the fix list, 64 per wave whatever
 // tile they came from, marched with the strict Ray -- bit-identical to math_mode 1.  Launched with a grid for the list's
 // capacity; waves beyond the count the device holds exit at once.
-template <bool DIFF>
-__global__ __launch_bounds__(256) void march_fix_kernel(BhrMarchArgs a) {
+// SS: the list holds whole k x k groups (march_tile_body), k^2 consecutive entries in sub-sample order, k^2-aligned; they are
+// resolved like the tile's groups, with the sub-sample rows k lanes apart.
+template <bool DIFF, bool SS>
+__device__ __forceinline__ void march_fix_body(const BhrMarchArgs &a) {
     const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     unsigned int n = *a.fix_count;
     if (n > (unsigned int)a.fix_cap) n = (unsigned int)a.fix_cap;
@@ -1207,12 +1285,17 @@ __global__ __launch_bounds__(256) void march_fix_kernel(BhrMarchArgs a) {
     }
     if (__ballot(ray.n_pend > 0)) ray.flush_one(a);
     if (__ballot(ray.n_pend > 0)) ray.flush_one(a);
-    if (valid) ray.finish_at(a, pix % a.width, pix / a.width);
+    if (SS) resolve_store(a, ray, valid, valid, pix % a.width, pix / a.width, a.ss);
+    else if (valid) ray.finish_at(a, pix % a.width, pix / a.width);
     // the row-cost profile (BHR_ROW_COSTS): the guard kernel left these pixels' steps out, they are strict steps of their row band
     if (a.row_steps && valid) atomicAdd(a.row_steps + (pix / a.width) / 8, (unsigned long long)ray.step_count);
     const unsigned long long tot = wave_sum_u32((unsigned int)ray.step_count);
     if (lane == 0) atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
 }
+template <bool DIFF>
+__global__ __launch_bounds__(256) void march_fix_kernel(BhrMarchArgs a) { march_fix_body<DIFF, false>(a); }
+template <bool DIFF>
+__global__ __launch_bounds__(256) void march_fix_ss_kernel(BhrMarchArgs a) { march_fix_body<DIFF, true>(a); }
 
 // The ILP-scheduled object launches two kernels, each with the occupancy its register allocation should aim for
 // (A/B on fhd / 4k, isolated launches): plain texture march at 5 waves per SIMD (96 VGPRs, no spills; 0.697 -> 0.692 ms,
@@ -1225,14 +1308,16 @@ __global__ __launch_bounds__(256) void march_fix_kernel(BhrMarchArgs a) {
 // latency-bound at ~15 cycles per instruction, so fewer, longer-lived waves only lengthen the critical path); both removed.
 // (The single-trip loop is the form the two kernels were tuned in, a loop over tiles per wave: without it hipcc allocates
 // their registers differently.)
-template <bool DIFF>
+template <bool DIFF, bool SS = false>
 __device__ __forceinline__ void march_tile_of_wave(const BhrMarchArgs &a) {
     const int slot = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int t = 0; t < 1; ++t)
-        if (slot < a.n_list) march_tile_body<DIFF, 0>(a, slot);
+        if (slot < a.n_list) march_tile_body<DIFF, 0, false, true, SS>(a, slot);
 }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void march_tile_plain_ilp(BhrMarchArgs a) { march_tile_of_wave<false>(a); }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void march_tile_aa_ilp(BhrMarchArgs a) { march_tile_of_wave<true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void march_tile_plain_ilp_ss(BhrMarchArgs a) { march_tile_of_wave<false, true>(a); }
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void march_tile_aa_ilp_ss(BhrMarchArgs a) { march_tile_of_wave<true, true>(a); }
 
 #else  // the fast and strict objects
 // ---------------------------------------------------------------------------
@@ -1346,16 +1431,28 @@ __global__ void selftest_kernel(unsigned long long *out, unsigned int div_rounds
 }  // namespace
 
 // ---- the kernels of this compilation, by the launcher's names (march_launch.hip); null: not in this object ----------
+// ss: the supersampled twin (a.ss > 1; the schedules refused with supersampling have none)
 #if BHR_MARCH_ILP
-const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff) {
+const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss) {
     switch (k) {
-    case BHR_MK_TILE_ILP: return diff ? (const void *)march_tile_aa_ilp : (const void *)march_tile_plain_ilp;
-    case BHR_MK_FIX: return diff ? (const void *)march_fix_kernel<true> : (const void *)march_fix_kernel<false>;
+    case BHR_MK_TILE_ILP:
+        if (ss) return diff ? (const void *)march_tile_aa_ilp_ss : (const void *)march_tile_plain_ilp_ss;
+        return diff ? (const void *)march_tile_aa_ilp : (const void *)march_tile_plain_ilp;
+    case BHR_MK_FIX:
+        if (ss) return diff ? (const void *)march_fix_ss_kernel<true> : (const void *)march_fix_ss_kernel<false>;
+        return diff ? (const void *)march_fix_kernel<true> : (const void *)march_fix_kernel<false>;
     default: return nullptr;
     }
 }
 #elif BHR_MARCH_STRICT
-const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff) {
+const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss) {
+    if (ss) {
+        switch (k) {
+        case BHR_MK_VOLUME: return (const void *)march_tile_ss_kernel<false, 2>;
+        case BHR_MK_DV2: return diff ? (const void *)march_tile_ss_kernel<true, 1> : (const void *)march_tile_ss_kernel<false, 1>;
+        default: return nullptr;
+        }
+    }
     switch (k) {
     case BHR_MK_VOLUME: return (const void *)march_tile_kernel<false, 2>;
     case BHR_MK_DV2: return diff ? (const void *)march_tile_kernel<true, 1> : (const void *)march_tile_kernel<false, 1>;
@@ -1372,7 +1469,16 @@ int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4) {
     return BHR_OK;
 }
 #else
-const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff) {
+const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss) {
+    if (ss) {
+        switch (k) {
+        case BHR_MK_VOLUME: return (const void *)march_tile_ss_kernel<false, 2>;
+        case BHR_MK_DV2: return diff ? (const void *)march_tile_ss_kernel<true, 1> : (const void *)march_tile_ss_kernel<false, 1>;
+        case BHR_MK_TILE: return diff ? (const void *)march_tile_ss_kernel<true, 0> : (const void *)march_tile_plain_fast_ss;
+        case BHR_MK_GUARD: return diff ? (const void *)march_tile_guard_ss_kernel<true> : (const void *)march_tile_guard_ss_kernel<false>;
+        default: return nullptr;
+        }
+    }
     switch (k) {
     case BHR_MK_VOLUME: return (const void *)march_tile_kernel<false, 2>;
     case BHR_MK_DV2: return diff ? (const void *)march_tile_kernel<true, 1> : (const void *)march_tile_kernel<false, 1>;

@@ -21,16 +21,18 @@
 
 namespace {
 
-// Tile order of this context: 8x8 tiles sorted by the distance of their centre from the centre of the FULL
-// image (the camera looks at the hole, build_camera), nearest first.  Built once per context.
+// Tile order of this context: 8x8 tiles of the marched frame (bhr_fine) sorted by the distance of their centre from the
+// centre of the FULL image (the camera looks at the hole, build_camera), nearest first.  Built once per context and
+// supersampling factor (bhr_set_supersample releases it).
 int32_t ensure_tile_order(bhr_ctx *ctx, int tiles_x, int n_tiles) {
-    if (ctx->d_tile_order && ctx->tile_order_n == n_tiles) return BHR_OK;
+    if (ctx->d_tile_order && ctx->tile_order_n == n_tiles && ctx->tile_order_ss == ctx->ss) return BHR_OK;
     if (ctx->d_tile_order) (void)hipFree(ctx->d_tile_order);
     ctx->d_tile_order = nullptr;
     std::vector<std::pair<float, int>> key((size_t)n_tiles);
-    const float cx = 0.5f * (float)ctx->cfg.width, cy = 0.5f * (float)ctx->cfg.height;
+    const bhr_fine_frame fr = bhr_fine(ctx);
+    const float cx = 0.5f * (float)fr.width, cy = 0.5f * (float)fr.height;
     for (int t = 0; t < n_tiles; ++t) {
-        const float x = (float)((t % tiles_x) * 8 + 4) - cx, y = (float)(ctx->cfg.row0 + (t / tiles_x) * 8 + 4) - cy;
+        const float x = (float)((t % tiles_x) * 8 + 4) - cx, y = (float)(fr.row0 + (t / tiles_x) * 8 + 4) - cy;
         key[(size_t)t] = {x * x + y * y, t};
     }
     std::stable_sort(key.begin(), key.end(),
@@ -43,6 +45,7 @@ int32_t ensure_tile_order(bhr_ctx *ctx, int tiles_x, int n_tiles) {
     BHR_HIP(hipMalloc((void **)&ctx->d_tile_order, (size_t)n_tiles * sizeof(int32_t)));
     BHR_HIP(hipMemcpy(ctx->d_tile_order, ctx->h_tile_order, (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice));
     ctx->tile_order_n = n_tiles;
+    ctx->tile_order_ss = ctx->ss;
     return BHR_OK;
 }
 
@@ -85,32 +88,33 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part &pa
     MarchKernel k;
     k.grid = dim3((a.n_list + 3) / 4);
     const bool persistent = (flags & BHR_PERSISTENT) != 0;
+    const int ss = a.ss > 1;                                   // the supersampled twins (bhr_render refuses the schedules they lack)
     const auto own = math == BHR_MATH_FAST ? bhr_march_kernel_fast : bhr_march_kernel_strict;
     if (part.active && part.n <= 0 && part.repair != 2) return k;
     if (part.active && part.repair == 2) {
-        k.fn = bhr_march_kernel_strict_ilp(BHR_MK_FIX, diff);
+        k.fn = bhr_march_kernel_strict_ilp(BHR_MK_FIX, diff, ss);
         k.grid = dim3((a.fix_cap / 64 + 3) / 4);
         return k;
     }
-    if (ctx->disk_source == BHR_DISK_V2_VOLUME) { k.fn = own(BHR_MK_VOLUME, 0); return k; }
-    if (a.dv2) { k.fn = own(BHR_MK_DV2, diff); return k; }
+    if (ctx->disk_source == BHR_DISK_V2_VOLUME) { k.fn = own(BHR_MK_VOLUME, 0, ss); return k; }
+    if (a.dv2) { k.fn = own(BHR_MK_DV2, diff, ss); return k; }
     if (persistent && !a.row_steps && !part.active) {
-        k.fn = own(BHR_MK_PERSISTENT, diff);
+        k.fn = own(BHR_MK_PERSISTENT, diff, ss);
         k.grid = dim3(std::min(std::max((a.n_tiles + 3) / 4, 1), 256 * 8));
         return k;
     }
     switch (math) {
     case BHR_MATH_STRICT:
-        k.fn = persistent ? bhr_march_kernel_strict(BHR_MK_TILE, diff) : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff);
+        k.fn = persistent ? bhr_march_kernel_strict(BHR_MK_TILE, diff, ss) : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff, ss);
         return k;
     case BHR_MATH_FAST:
         if (part.active && part.repair == 1) {
-            k.fn = bhr_march_kernel_fast(a.row_steps ? BHR_MK_GUARD_COSTS : BHR_MK_GUARD, diff);
+            k.fn = bhr_march_kernel_fast(a.row_steps ? BHR_MK_GUARD_COSTS : BHR_MK_GUARD, diff, ss);
         } else if (a.row_steps) {
-            k.fn = bhr_march_kernel_fast(BHR_MK_TILE_COSTS, diff);
+            k.fn = bhr_march_kernel_fast(BHR_MK_TILE_COSTS, diff, ss);
         } else if (diff) {
-            // BHR_MIP_LDS=1: the coarse mip levels through LDS where any of them fits 44 KB (see the kernel)
-            if (ctx->opt.mip_lds && !part.active) {
+            // BHR_MIP_LDS=1: the coarse mip levels through LDS where any of them fits 44 KB (see the kernel; not supersampled)
+            if (ctx->opt.mip_lds && !part.active && !ss) {
                 const int last = 3;                                     // int(clamp(lod, 0, 3)): the coarsest level ever sampled
                 for (int l = last; l >= 1; --l) {
                     if (a.sc.mip_h[last] <= 0 || a.sc.mip_w[last] <= 0) break;                  // a texture too small to have it
@@ -121,9 +125,9 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part &pa
                 }
             }
             ctx->mip_lds_from = a.mip_lds_from;
-            k.fn = bhr_march_kernel_fast(a.mip_lds_from >= 0 ? BHR_MK_MIPSTAGED : BHR_MK_TILE, 1);
+            k.fn = bhr_march_kernel_fast(a.mip_lds_from >= 0 ? BHR_MK_MIPSTAGED : BHR_MK_TILE, 1, ss);
         } else {
-            k.fn = bhr_march_kernel_fast(BHR_MK_TILE, 0);
+            k.fn = bhr_march_kernel_fast(BHR_MK_TILE, 0, ss);
         }
         return k;
     }
@@ -145,14 +149,15 @@ int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags) {
 }
 
 int32_t bhr_ensure_tile_order(bhr_ctx *ctx) {
-    const int tiles_x = (ctx->cfg.width + 7) / 8;
-    return ensure_tile_order(ctx, tiles_x, tiles_x * ((ctx->rows + 7) / 8));
+    const bhr_fine_frame fr = bhr_fine(ctx);
+    const int tiles_x = (fr.width + 7) / 8;
+    return ensure_tile_order(ctx, tiles_x, tiles_x * ((fr.rows + 7) / 8));
 }
 
 // registers / LDS of the kernel that marches a whole texture frame: the fast object's under fast arithmetic, the ILP
 // object's under strict and hybrid (bhr_create reports them)
 int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds) {
-    const void *f = math == BHR_MATH_FAST ? bhr_march_kernel_fast(BHR_MK_TILE, diff) : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff);
+    const void *f = math == BHR_MATH_FAST ? bhr_march_kernel_fast(BHR_MK_TILE, diff, 0) : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff, 0);
     hipFuncAttributes at;
     BHR_HIP(hipFuncGetAttributes(&at, f));
     *vgprs = at.numRegs;
@@ -178,8 +183,11 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
         a.cu[k] = cam->up[k];
         a.cf[k] = cam->forward[k];
     }
-    a.pw = cam->pixel_width;
-    a.ph = cam->pixel_height;
+    // supersampling: the march marches the fine frame (bhr_fine) at the fine pitch, and stores the resolved output frame
+    const bhr_fine_frame fr = bhr_fine(ctx);
+    const bhr_camera fcam = bhr_fine_camera(ctx, cam);
+    a.pw = fcam.pixel_width;
+    a.ph = fcam.pixel_height;
     a.r_esc = cam->r_escape;
     a.r_esc2 = a.r_esc * a.r_esc;
     a.h_base = c.step_size;
@@ -201,10 +209,15 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     a.max_iter = (int32_t)(a.r_esc * 40.0f / a.h_base);
     a.max_affine = a.r_esc * 40.0f;
     a.max_affine_u = a.max_affine / a.h_base;      // fast build: the affine parameter in units of h_base
-    a.width = c.width;
-    a.height = c.height;
-    a.row0 = c.row0;
-    a.rows = ctx->rows;
+    a.width = fr.width;
+    a.height = fr.height;
+    a.row0 = fr.row0;
+    a.rows = fr.rows;
+    a.ss = ctx->ss;
+    a.ss_log2 = ctx->ss == 8 ? 3 : ctx->ss == 4 ? 2 : ctx->ss == 2 ? 1 : 0;
+    a.ss_inv = 1.0f / (float)(ctx->ss * ctx->ss);
+    a.out_width = c.width;
+    a.out_rows = ctx->rows;
     a.sc.skybox = ctx->d_skybox;
     a.sc.sky_h = ctx->sky_h;
     a.sc.sky_w = ctx->sky_w;
@@ -244,8 +257,8 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     a.dv2_norm_shear = ctx->dv2_norm[0];
     a.dv2_norm_hotspot = ctx->dv2_norm[1];
     a.dv2_t_peak = ctx->dv2_norm[2];
-    a.tiles_x = (c.width + 7) / 8;
-    a.n_tiles = a.tiles_x * ((ctx->rows + 7) / 8);
+    a.tiles_x = (fr.width + 7) / 8;
+    a.n_tiles = a.tiles_x * ((fr.rows + 7) / 8);
     a.n_list = a.n_tiles;
     a.fix_count = ctx->fix_count;
     a.mip_lds_from = -1;
@@ -293,6 +306,8 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
     if (first_part) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 0] : ctx->ev[0], ctx->stream));
     const MarchKernel k = march_kernel(ctx, a, part, math, flags, want_diff);
+    if (!k.fn && !(part.active && part.n <= 0 && part.repair != 2))
+        return bhr_fail(BHR_ERR_STATE, "bhr_render: no march kernel for this launch (supersampling %d, flags %u)", ctx->ss, flags);
     if (k.fn) {
         int refill_below = 40;                                 // persistent schedule: refill a wave below 40 live lanes
         void *args[] = {&a, &refill_below};                    // (the second argument is the persistent kernel's alone)
@@ -311,6 +326,6 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
         if (FILE *f = fopen(stamp_path, "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
     }
     ctx->last_steps_ptr = a.ray_steps;
-    ctx->counters.rays = (uint64_t)c.width * ctx->rows;
+    ctx->counters.rays = (uint64_t)fr.width * fr.rows;
     return BHR_OK;
 }

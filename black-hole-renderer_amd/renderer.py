@@ -33,6 +33,14 @@ class _FieldView:
         return self._reader()
 
 
+SUPERSAMPLE_FACTORS = (1, 2, 4, 8)
+
+
+def _check_supersample(k) -> None:
+    if isinstance(k, bool) or k not in SUPERSAMPLE_FACTORS:
+        raise ValueError(f"supersample must be one of {SUPERSAMPLE_FACTORS}, got {k!r}")
+
+
 class HipRenderer:
     """Renders Schwarzschild black-hole frames on one MI355X (or one row block of a frame).
 
@@ -48,7 +56,10 @@ class HipRenderer:
                  disk_tilt=0.0, lens_flare=False, anti_alias="disabled", aa_strength=1.0,
                  disk_rotation_speed=0.1, ignore_taichi_cache=False,
                  device_index: int = 0, rows: Optional[Sequence[int]] = None, math: str = "strict",
-                 frame_slots: Optional[int] = None, outputs: Optional[str] = None, options: Optional[dict] = None):
+                 frame_slots: Optional[int] = None, outputs: Optional[str] = None, options: Optional[dict] = None,
+                 supersample: int = 1):
+        # supersample=k: k x k rays per pixel, box-filtered inside the march (bhr_set_supersample; include/bhr.h states the filter)
+        _check_supersample(supersample)
         if device not in ("hip", "gpu"):
             raise ValueError(f"HipRenderer runs on the GPU only (device={device!r}); there is no CPU path")
         # math="strict" (default): the RK4 loop in the reference's operation order with IEEE sqrt and
@@ -103,6 +114,13 @@ class HipRenderer:
             self.set_outputs(outputs)
         for name, value in (options or {}).items():
             self.set_option(name, value)
+        self._supersample = 1
+        if supersample != 1:
+            try:
+                self.set_supersample(supersample)
+            except Exception:
+                self.close()
+                raise
 
         skybox = np.ascontiguousarray(skybox, dtype=np.float32)
         disk_tex = np.ascontiguousarray(disk_tex, dtype=np.float32)
@@ -399,6 +417,17 @@ class HipRenderer:
                 raise ValueError(f"outputs: 'f32', 'blur', 'u8' joined by '+', got {outputs!r}")
             mask |= bits[part]
         _lib.check(self._lib.bhr_set_outputs(self._ctx, mask))
+
+    @property
+    def supersample(self) -> int:
+        """k: every pixel is the box filter of k x k rays (1: one ray per pixel)."""
+        return self._supersample
+
+    def set_supersample(self, k: int) -> None:
+        """k x k rays per pixel for the frames rendered from now on (bhr_set_supersample): 1, 2, 4 or 8; whole-frame contexts only."""
+        _check_supersample(k)
+        _lib.check(self._lib.bhr_set_supersample(self._ctx, int(k)))
+        self._supersample = int(k)
 
     def set_option(self, name: str, value) -> None:
         """One of the library's switches for this context (bhr_set_option; include/bhr.h lists them)."""

@@ -256,6 +256,19 @@ BHR_API int32_t bhr_bloom(bhr_ctx *ctx);
 #define BHR_OUTPUT_BLUR 2u
 #define BHR_OUTPUT_U8 4u
 BHR_API int32_t bhr_set_outputs(bhr_ctx *ctx, uint32_t mask);
+/* Supersampling: k x k rays per pixel on an ordered grid, k = 1 (default: one ray per pixel), 2, 4 or 8.  The BG and DISK
+ * layers of a W x H frame with factor k are the k x k box filter of those a k = 1 context renders of the same view at
+ * kW x kH (same camera, skybox, disk source and math mode), bit for bit: the sample (sx, sy) of output pixel (i, j) is the
+ * ray of fine pixel (k i + sx, k j + sy), with the value the single-sample march stores for it (bg (1 - A) rounded once,
+ * clamp(accum, 0, 1)); per channel each sub-sample row is summed as a pairwise tree (adjacent pairs, then pairs of those
+ * sums, ...), the k row sums by the same tree, and the sum multiplied once by 1 / k^2.  The march takes the context's
+ * camera (pitch pw, ph) and marches the fine grid at pw / k, ph / k.  Everything after the march -- bloom, combine, lens
+ * flare, u8 quantisation, PNG and video sinks -- runs at W x H on the resolved layers.  A hybrid frame with guards
+ * re-marches a k x k group with the strict arithmetic as soon as one of its rays is flagged (bhr_hybrid_repairs counts
+ * output pixels).  Counters: rays = k^2 W H, ray_steps those of the kW x kH march.  Ordered behind the frames in flight.
+ * BHR_ERR_INVALID: k not in {1, 2, 4, 8}, a row-block context (k > 1), or k^2 W H >= 2^31.  With k > 1, bhr_render with
+ * BHR_PERSISTENT or BHR_ROW_COSTS, bhr_group_render*, bhr_tile_export and bhr_tile_render return BHR_ERR_INVALID. */
+BHR_API int32_t bhr_set_supersample(bhr_ctx *ctx, int32_t k);
 /* The library's switches.  Each has an environment variable that bhr_create reads ONCE (no entry point calls getenv
  * afterwards) and can be changed per context later with this call -- what tests and A/B tools use:
  *   "bloom_split"     BHR_BLOOM_SPLIT     -1 post-pass by arithmetic (exact f32 under strict, split f16 under fast / hybrid), 0 / 1 force
