@@ -1,4 +1,5 @@
 // api.hip -- the extern "C" surface declared in include/bhr.h.
+#include <float.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -932,14 +933,27 @@ int32_t bhr_write_layer(bhr_ctx *ctx, int32_t layer, const float *in) {
     BHR_TRY(use_device(ctx));
     float *dst = nullptr;
     bhr_frame_slot &f = ctx->slots[ctx->active_slot];
+    const size_t n = (size_t)ctx->rows * ctx->cfg.width * 3;
+    int32_t wide = 0;
+    if (layer == BHR_LAYER_DISK) {
+        // the bloom folds the reference's `lum > 0` test away (bloom.hip), which holds for non-negative layers only; values
+        // above what the split kernels' f16 halves carry send the stand-alone pass to the exact kernels (bhr_bloom)
+        for (size_t k = 0; k < n; ++k) {
+            const float v = in[k];
+            if (!(v >= 0.0f && v <= FLT_MAX))
+                return bhr_fail(BHR_ERR_INVALID, "bhr_write_layer: disk value %g at row %zu, column %zu (finite values >= 0 only)",
+                                (double)v, k / 3 / ctx->cfg.width, k / 3 % ctx->cfg.width);
+            wide |= v > BHR_SPLIT_DISK_MAX;
+        }
+    }
     switch (layer) {
         case BHR_LAYER_FINAL: dst = ctx->d_final; f.have = (f.have | BHR_OUT_F32) & ~BHR_OUT_U8; break;   // the u8 rows follow the written frame
         case BHR_LAYER_BG: dst = ctx->d_bg; f.sum_valid = 0; break;      // a later V pass adds the two layers itself
-        case BHR_LAYER_DISK: dst = ctx->d_disk; f.sum_valid = 0; break;
+        case BHR_LAYER_DISK: dst = ctx->d_disk; f.sum_valid = 0; f.disk_wide = wide; break;
         case BHR_LAYER_BLUR: dst = ctx->d_blur; f.have |= BHR_OUT_BLUR; break;
         default: return bhr_fail(BHR_ERR_INVALID, "bhr_write_layer: unknown layer %d", layer);
     }
-    return upload(ctx, dst, in, (size_t)ctx->rows * ctx->cfg.width * 3 * sizeof(float));
+    return upload(ctx, dst, in, n * sizeof(float));
 }
 
 int32_t bhr_bloom(bhr_ctx *ctx) {
@@ -947,7 +961,13 @@ int32_t bhr_bloom(bhr_ctx *ctx) {
     if (ctx->rows != ctx->cfg.height)
         return bhr_fail(BHR_ERR_INVALID, "bhr_bloom: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
     BHR_TRY(use_device(ctx));
-    BHR_TRY(bhr_frame_begin(ctx, 0));                          // the context's arithmetic decides the kernels, as for a rendered frame
+    // the context's arithmetic decides the kernels, as for a rendered frame -- except for a written disk layer the split
+    // kernels cannot carry: the pass stays one function of its input whatever the arithmetic
+    const int32_t forced = ctx->opt.bloom_split;
+    if (ctx->slots[ctx->active_slot].disk_wide) ctx->opt.bloom_split = 0;
+    const int32_t rc = bhr_frame_begin(ctx, 0);
+    ctx->opt.bloom_split = forced;
+    BHR_TRY(rc);
     if (ctx->bloom_split) BHR_TRY(bhr_launch_bloom_pack(ctx)); // the disk layer may be the caller's (bhr_write_layer)
     BHR_TRY(bhr_launch_bloom_h(ctx));
     return bhr_frame_post(ctx, 1, BHR_OUT_F32 | BHR_OUT_BLUR);

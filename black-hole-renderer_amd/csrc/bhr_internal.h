@@ -28,6 +28,9 @@
 // rows of zeros in front of and behind the (3, rows + 2R, W) H-blur planes of the exact-f32 post-pass (the IPC handles of
 // csrc/group.hip name the allocation: the planes start this many rows in)
 #define BHR_HBLUR_PAD_ROWS 16
+// the largest disk value the split-f16 post-pass carries: two f16 halves of x 2^14 (bloom.hip); a written DISK layer with a
+// larger one goes through the exact f32 kernels (bhr_write_layer, bhr_bloom)
+#define BHR_SPLIT_DISK_MAX 3.99f
 #define BHR_STEP_LANES 128
 #define BHR_STEP_STRIDE 32          // in u64 words
 #define BHR_STEP_CELL (BHR_STEP_LANES * BHR_STEP_STRIDE)
@@ -176,6 +179,7 @@ struct bhr_frame_slot {
     void *d_pa, *d_pb;         // split-f16 bloom (bloom.hip): the march's packed copy of the disk layer, the packed H-blur planes; on first use
     float *d_sum;              // ... and bg + disk of the frame (rows, W, 3); sum_valid: written by this frame's march / pack kernel
     int32_t sum_valid;
+    int32_t disk_wide;         // the DISK layer is a caller's (bhr_write_layer) with a value above BHR_SPLIT_DISK_MAX; a march clears it
     uint8_t *d_final_u8;
     uint32_t have;             // BHR_OUT_* layers of the slot's last frame that are in memory (the V pass stores what was asked for; the rest on demand)
     int32_t frame_split, frame_with_bloom;   // how that frame's post-pass ran (bhr_ensure_outputs re-runs its V pass)

@@ -431,9 +431,10 @@ __global__ void bloom_pack_kernel(const float *__restrict__ disk, const float *_
         for (int j = 0; j < 8; ++j) {
             const int x = g * 8 + j;
             _Float16 a, b;
-            // the march's disk layer is clamp(accum, 0, 1) (render.py:3018); a caller's own layer is held to what the scaled f16
-            // halves can carry (3.99) rather than turned into infinities
-            cut2(x < W ? fminf(fmaxf(disk[((size_t)y * W + x) * 3 + c], 0.0f), 3.99f) * PIX_SCALE : 0.0f, a, b);
+            // the march's disk layer is clamp(accum, 0, 1) (render.py:3018); a caller's own layer holds finite values in
+            // [0, BHR_SPLIT_DISK_MAX] here (bhr_write_layer refuses the others, bhr_bloom sends larger ones to the exact
+            // kernels): the clamp only keeps a stray value from becoming an infinity
+            cut2(x < W ? fminf(fmaxf(disk[((size_t)y * W + x) * 3 + c], 0.0f), BHR_SPLIT_DISK_MAX) * PIX_SCALE : 0.0f, a, b);
             hi[j] = a;
             lo[j] = b;
         }

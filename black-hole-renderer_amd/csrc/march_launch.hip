@@ -231,6 +231,7 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     a.sc.n_phi = ctx->n_phi;
     a.bg = ctx->d_bg;
     a.disk = ctx->d_disk;
+    ctx->slots[ctx->active_slot].disk_wide = 0;          // the march's disk layer lies in [0, 1]
     a.diskp = nullptr;
     a.dp_yb = a.dp_gp = a.dp_g0 = 0;
     a.sum = nullptr;

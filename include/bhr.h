@@ -239,12 +239,18 @@ BHR_API int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
  * for the context's rows: (row1-row0, width, 3) f32.  Synchronises. */
 BHR_API int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out);
 /* field.from_numpy() for a frame layer: replaces the context's rows of FINAL, BG, DISK or BLUR with
- * caller data, e.g. to post-process a frame composed elsewhere.  Synchronises. */
+ * caller data, e.g. to post-process a frame composed elsewhere.  Synchronises.  A DISK layer holds finite values >= 0
+ * (a march writes clamp(accum, 0, 1)): one with a negative or non-finite value is refused with BHR_ERR_INVALID and the
+ * layer keeps its contents -- the bloom folds the reference's `lum > 0` test away, which holds for non-negative layers
+ * only. */
 BHR_API int32_t bhr_write_layer(bhr_ctx *ctx, int32_t layer, const float *in);
 /* self._bloom_kernel(disk_layer_field, bright_field, blur_field, 0, 0.4, int(0.02 W), (W / 640)^2) followed by
  * clip(img + disk + blur, 0, 1) (render.py:3914-3918), standalone on the layers currently in the context:
  * BLUR <- bloom(DISK), FINAL <- clip(BG + DISK + BLUR, 0, 1).  Whole-frame context (row blocks need their
- * neighbours' halo rows: bhr_group_render).  Asynchronous. */
+ * neighbours' halo rows: bhr_group_render).  Asynchronous.  The kernels follow the context's arithmetic as for a
+ * rendered frame (and the "bloom_split" option), except that a DISK layer written with a value above 3.99 -- more than
+ * the split-f16 kernels' halves carry -- goes through the exact f32 kernels until a march or another write replaces
+ * it: the result is the same function of the layers under every arithmetic. */
 BHR_API int32_t bhr_bloom(bhr_ctx *ctx);
 /* What bhr_render keeps in memory of a frame besides the bg / disk layers.  TaichiRenderer.render() returns the f32 frame
  * (BHR_OUTPUT_F32, the default); the video loop, the PNG sink and the u8 row-block gather only ever read the quantised
