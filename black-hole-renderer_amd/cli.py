@@ -60,6 +60,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "everywhere (the analogue of Taichi's fast_math=True)")
     p.add_argument("--supersample", type=int, default=1, choices=[1, 2, 4, 8],
                    help="k x k rays per pixel, box-filtered inside the march (default: 1; one GPU)")
+    p.add_argument("--supersample_threshold", type=float, default=None,
+                   help="adaptive supersampling: the k x k rays of --supersample only for the pixels whose largest difference to an "
+                        "edge neighbour in the one-ray frame exceeds this value (omitted: every pixel)")
     p.add_argument("--video_stream", type=str, default="auto", choices=["auto", "y4m", "off"],
                    help="--video: also hand the frames to the encoder as a yuv420p stream converted on the device "
                         "(auto: pipe into ffmpeg when it is on PATH; y4m: write <output stem>.y4m; off: PNG frames only)")
@@ -108,6 +111,14 @@ def validate_args(args) -> None:
         raise ValueError(f"gpus must be >= 1, got {args.gpus}")
     if getattr(args, "supersample", 1) > 1 and getattr(args, "gpus", 1) > 1:
         raise ValueError("--supersample renders on one GPU: it does not combine with --gpus > 1")
+    thr = getattr(args, "supersample_threshold", None)
+    if thr is not None:
+        if thr != thr:
+            raise ValueError("--supersample_threshold must not be NaN")
+        if getattr(args, "supersample", 1) <= 1:
+            raise ValueError("--supersample_threshold needs --supersample 2, 4 or 8")
+        if getattr(args, "gpus", 1) > 1:
+            raise ValueError("--supersample_threshold renders on one GPU: it does not combine with --gpus > 1")
     if getattr(args, "interactive", False):
         raise ValueError("--interactive needs the Taichi GUI and is not part of this build")
 
@@ -134,7 +145,8 @@ def main(argv=None) -> int:
         renderer, _, _, _ = drivers.make_renderer(
             width, height, args.pov, fov, args.step_size, args.texture, args.n_stars, 2048, 1024, args.r_max, None,
             args.disk_inner_radius, args.disk_outer_radius, args.disk_tilt, args.lens_flare, args.anti_alias,
-            args.aa_strength, args.disk_rotation_speed, device_index=local_rank, math=args.math, supersample=args.supersample)
+            args.aa_strength, args.disk_rotation_speed, device_index=local_rank, math=args.math, supersample=args.supersample,
+            supersample_threshold=args.supersample_threshold)
         print(f"Rendering video: {args.n_frames} frames at {width}x{height} (rank {rank}/{world})")
         drivers.render_video(renderer, width, height, n_frames=args.n_frames, fps=args.fps,
                              output_path=args.output, fov=fov, static_cam_pos=args.pov, orbit=args.orbit,
@@ -161,6 +173,7 @@ def main(argv=None) -> int:
         disk_texture_path=args.disk_texture, r_disk_inner=args.disk_inner_radius,
         r_disk_outer=args.disk_outer_radius, disk_tilt=args.disk_tilt, lens_flare=args.lens_flare,
         anti_alias=args.anti_alias, aa_strength=args.aa_strength, disk_rotation_speed=args.disk_rotation_speed,
-        gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample)
+        gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
+        supersample_threshold=args.supersample_threshold)
     drivers.save_image(img, args.output)
     return 0

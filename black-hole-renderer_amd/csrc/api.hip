@@ -459,6 +459,7 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
     ctx->bloom_R = (int32_t)(cfg->width * 0.02);  // int(self.width * 0.02), render.py:3914
     ctx->mip_lds_from = -1;
     ctx->ss = 1;
+    ctx->ada_last_slot = -1;
 
     auto bail = [&](int32_t rc) { bhr_destroy(ctx); return rc; };
     if (hipSetDevice(cfg->device) != hipSuccess) return bail(bhr_fail(BHR_ERR_HIP, "hipSetDevice(%d) failed", cfg->device));
@@ -516,6 +517,11 @@ void bhr_destroy(bhr_ctx *ctx) {
     bhr_png_dev_free(ctx);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);
+    for (auto &l : ctx->ada) {
+        if (l.d_list) (void)hipFree(l.d_list);
+        if (l.d_mask) (void)hipFree(l.d_mask);
+        if (l.d_counts) (void)hipFree(l.d_counts);
+    }
     bhr_pipe_free(ctx);
     for (int q = 0; q < BHR_MAX_FRAME_SLOTS; ++q)
         if (ctx->aux_streams[q]) { (void)hipStreamSynchronize(ctx->aux_streams[q]); (void)hipStreamDestroy(ctx->aux_streams[q]); }
@@ -745,7 +751,13 @@ int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     bhr_frame_slot &f = ctx->slots[k];
     const int with_bloom = (flags & BHR_SKIP_BLOOM) ? 0 : 1;
     BHR_TRY(bhr_frame_begin(ctx, flags));
-    BHR_TRY(bhr_launch_march(ctx, cam, flags));  // records the ring slot's march events
+    // an adaptively supersampled frame: the k = 1 march, then detect + refinement inside the same march bracket
+    ctx->defer_march_end = ctx->ada_k > 1;
+    ctx->ada_frame = ctx->ada_k > 1;
+    int32_t rc_m = bhr_launch_march(ctx, cam, flags);  // records the ring slot's march events
+    ctx->defer_march_end = 0;
+    BHR_TRY(rc_m);
+    if (ctx->ada_k > 1) BHR_TRY(bhr_launch_adaptive(ctx, cam, flags));
     // the march's end is the timing ring's event (recorded by the launcher): an event of its own between the march and the
     // H pass is another ~5 us barrier packet in the frame's stream (kernel-trace gaps: 10 us with two records, 0 with none)
     f.march_done = ctx->ring_ev[ring * 3 + 1];
@@ -880,8 +892,8 @@ static int32_t calibrate_slot_streams(bhr_ctx *ctx, const bhr_camera *cam, uint3
 
 int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_render: null argument");
-    if (ctx->ss > 1 && (flags & (BHR_PERSISTENT | BHR_ROW_COSTS)))
-        return bhr_fail(BHR_ERR_INVALID, "bhr_render: BHR_PERSISTENT and BHR_ROW_COSTS are not available with supersampling (factor %d)", ctx->ss);
+    if ((ctx->ss > 1 || ctx->ada_k > 1) && (flags & (BHR_PERSISTENT | BHR_ROW_COSTS)))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_render: BHR_PERSISTENT and BHR_ROW_COSTS are not available with supersampling (factor %d)", ctx->ss > 1 ? ctx->ss : ctx->ada_k);
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     if (ctx->n_slots > 1 && ctx->opt.calibrate_streams && !ctx->streams_calibrated && !ctx->calibrating &&
         !(flags & (BHR_PERSISTENT | BHR_ROW_COSTS)) && ++ctx->two_slot_frames > 8)
@@ -1035,14 +1047,16 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     return BHR_OK;
 }
 
-int32_t bhr_set_supersample(bhr_ctx *ctx, int32_t k) {
-    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_supersample: null ctx");
-    if (k != 1 && k != 2 && k != 4 && k != 8) return bhr_fail(BHR_ERR_INVALID, "bhr_set_supersample: factor %d (1, 2, 4 or 8)", k);
+// Both supersampling settings: `ss` rays per pixel everywhere (ada_k = 0), or one ray per pixel and ada_k x ada_k where the
+// neighbours differ by more than T.
+static int32_t set_sampling(bhr_ctx *ctx, const char *who, int32_t k, int32_t adaptive, float T) {
+    if (k != 1 && k != 2 && k != 4 && k != 8) return bhr_fail(BHR_ERR_INVALID, "%s: factor %d (1, 2, 4 or 8)", who, k);
     if (k > 1 && ctx->rows != ctx->cfg.height)
-        return bhr_fail(BHR_ERR_INVALID, "bhr_set_supersample: a row-block context (rows %d of %d) renders one sample per pixel", ctx->rows, ctx->cfg.height);
+        return bhr_fail(BHR_ERR_INVALID, "%s: a row-block context (rows %d of %d) renders one sample per pixel", who, ctx->rows, ctx->cfg.height);
     if ((int64_t)k * k * ctx->cfg.width * ctx->cfg.height >= ((int64_t)1 << 31))
-        return bhr_fail(BHR_ERR_INVALID, "bhr_set_supersample: %d x %d rays of a %dx%d frame exceed 2^31", k, k, ctx->cfg.width, ctx->cfg.height);
-    if (k == ctx->ss) return BHR_OK;
+        return bhr_fail(BHR_ERR_INVALID, "%s: %d x %d rays of a %dx%d frame exceed 2^31", who, k, k, ctx->cfg.width, ctx->cfg.height);
+    const int32_t ss = adaptive ? 1 : k, ada_k = adaptive && k > 1 ? k : 0;
+    if (ss == ctx->ss && ada_k == ctx->ada_k && (ada_k == 0 || memcmp(&T, &ctx->ada_threshold, sizeof(T)) == 0)) return BHR_OK;
     // the tile order, the hybrid lists and the fix lists belong to the marched frame: the frames in flight still march over them
     BHR_TRY(bhr_enter(ctx));
     for (auto &f : ctx->slots)
@@ -1054,7 +1068,36 @@ int32_t bhr_set_supersample(bhr_ctx *ctx, int32_t k) {
     if (ctx->d_tile_order) BHR_HIP(hipFree(ctx->d_tile_order));
     ctx->d_tile_order = nullptr;
     ctx->tile_order_n = 0;
-    ctx->ss = k;
+    ctx->ss = ss;
+    ctx->ada_k = ada_k;
+    ctx->ada_threshold = ada_k ? T : 0.0f;
+    ctx->ada_last_slot = -1;
+    ctx->ada_frame = 0;
+    return BHR_OK;
+}
+
+int32_t bhr_set_supersample(bhr_ctx *ctx, int32_t k) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_supersample: null ctx");
+    return set_sampling(ctx, "bhr_set_supersample", k, 0, 0.0f);
+}
+
+int32_t bhr_set_adaptive_supersample(bhr_ctx *ctx, int32_t k, float threshold) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_adaptive_supersample: null ctx");
+    if (threshold != threshold) return bhr_fail(BHR_ERR_INVALID, "bhr_set_adaptive_supersample: the threshold is NaN");
+    return set_sampling(ctx, "bhr_set_adaptive_supersample", k, 1, threshold);
+}
+
+// {refined pixels of the last adaptive frame, those of them marched strict, pixels of the frame}.  Synchronises.
+int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]) {
+    if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_adaptive_info: bad argument");
+    if (ctx->ada_k <= 1 || ctx->ada_last_slot < 0 || !ctx->ada[ctx->ada_last_slot].d_counts)
+        return bhr_fail(BHR_ERR_STATE, "bhr_adaptive_info: no adaptively supersampled frame has been rendered (bhr_set_adaptive_supersample)");
+    BHR_TRY(use_device(ctx));
+    unsigned int n[4] = {0, 0, 0, 0};            // tiles in the two lists, refined pixels in them
+    BHR_TRY(download(ctx, n, ctx->ada[ctx->ada_last_slot].d_counts, sizeof(n)));
+    out[0] = (int64_t)n[2] + (int64_t)n[3];
+    out[1] = ctx->ada_last_math == BHR_MATH_FAST ? 0 : (int64_t)n[2];
+    out[2] = (int64_t)ctx->cfg.width * ctx->rows;
     return BHR_OK;
 }
 
@@ -1162,6 +1205,12 @@ int32_t bhr_get_counters(bhr_ctx *ctx, bhr_counters *out) {
         if (hipEventQuery(ctx->ev[7]) == hipSuccess) ctx->counters.compose_ms = ev_ms(ctx->ev[6], ctx->ev[7]);
     }
     *out = ctx->counters;
+    if (ctx->ada_frame && ctx->ada_last_slot >= 0 && ctx->ada[ctx->ada_last_slot].d_counts) {
+        // an adaptive frame: the base march's W H rays (bhr_launch_march) and k^2 per refined pixel
+        unsigned int n[4] = {0, 0, 0, 0};
+        BHR_TRY(download(ctx, n, ctx->ada[ctx->ada_last_slot].d_counts, sizeof(n)));
+        out->rays += ((uint64_t)n[2] + n[3]) * (uint64_t)(ctx->ada_k * ctx->ada_k);
+    }
     return BHR_OK;
 }
 

@@ -130,6 +130,25 @@ enum bhr_march_kernel {
     BHR_MK_MIPSTAGED,     // march_tile_mipstaged_kernel: coarse mip levels in LDS (BHR_MIP_LDS, diff only)       fast
     BHR_MK_TILE_ILP,      // march_tile_aa_ilp / march_tile_plain_ilp: the strict texture march                   strict_ilp
     BHR_MK_FIX,           // march_fix_kernel<diff>: the fix list of a hybrid march                              strict_ilp
+    // adaptive supersampling (bhr_set_adaptive_supersample): the kernels of the refinement, whatever the `ss` argument
+    BHR_MK_LIST,          // march_list_kernel<diff, 0>: the refined groups of a list of fine tiles, texture       fast, strict_ilp
+    BHR_MK_LIST_DV2,      // march_list_kernel<diff, 1>: analytic Disk V2                                        fast, strict
+    BHR_MK_LIST_VOLUME,   // march_list_kernel<false, 2>: finite-thickness Disk V2                               fast, strict
+    BHR_MK_DETECT,        // adaptive_detect_kernel: lists the output pixels whose neighbours differ             strict
+};
+
+// Kernel argument block of adaptive_detect_kernel (march.hip).
+struct BhrDetectArgs {
+    const float *bg, *disk;      // the k = 1 frame: (height, width, 3)
+    int32_t width, height;
+    float threshold;             // T: a pixel is refined iff c(p) > T
+    int32_t k_log2;
+    const uint8_t *flags;        // hybrid: strict flag per 8x8 tile of the FINE frame (null: every tile goes to the first list)
+    int32_t fine_tiles_x;
+    unsigned char *mask;         // (height, width): 1 = refined
+    int32_t *list;               // 2 cap entries: fine tiles that hold a refined pixel; [0, cap) strict (or all), [cap, 2 cap) fast
+    int32_t cap;                 // = tiles of the fine frame
+    unsigned int *counts;        // [0], [1] tiles in the two lists; [2], [3] refined pixels in them
 };
 
 // what a frame's V pass stores (bhr_launch_bloom_v_rows); bhr_ensure_outputs re-runs it for layers nobody asked for up front
@@ -279,6 +298,15 @@ struct bhr_ctx {
     int32_t *h_tile_order;     // host copy (malloc)
     int32_t tile_order_n, tile_order_ss;   // ... built for this many tiles of the frame marched with this supersampling factor
     int32_t ss;                // bhr_set_supersample: k x k rays per pixel (1, 2, 4, 8)
+    // bhr_set_adaptive_supersample: the frame is marched with ss = 1, then the pixels whose neighbours differ by more than
+    // ada_threshold are marched again with ada_k x ada_k rays (march_launch.hip: bhr_launch_adaptive).  ada_k = 0: off.
+    int32_t ada_k;
+    float ada_threshold;
+    struct { int32_t *d_list; unsigned char *d_mask; unsigned int *d_counts; } ada[BHR_MAX_FRAME_SLOTS];   // per frame slot, on first use: two lists of fine tiles, the mask, four counts
+    int32_t ada_last_slot;     // frame slot of the last adaptive frame (-1: none since the setting changed), and
+    int32_t ada_last_math;     // the arithmetic bhr_resolve_math gave it
+    int32_t ada_frame;         // the last bhr_render was an adaptive frame (bhr_get_counters adds the refinement's rays)
+    int32_t defer_march_end;   // bhr_launch_march leaves the march-end event to its caller (the refinement follows the base march)
     bhr_march_part part;       // partial launch in progress (inactive: whole block)
     // second march stream (one per frame slot): the strict tiles of a two-stream hybrid march run on it beside the fast ones
     // instead of ahead of them (bhr_aux_fork / _join)
@@ -371,6 +399,11 @@ const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.o
 int32_t bhr_ensure_tile_order(bhr_ctx *ctx);                                           // march_launch.hip: builds d_/h_tile_order
 int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);     // hybrid.hip
+// march_launch.hip: detect + refinement of an adaptively supersampled frame, behind its base march on ctx->stream; records the march-end event
+int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
+// hybrid.hip: strict flag per 8x8 tile of the frame k times finer than the context's (the rule a bhr_set_supersample(k) hybrid
+// frame classifies its tiles by), in a buffer of the active frame slot, made on ctx->stream and cached on the view key
+int32_t bhr_hybrid_fine_flags(bhr_ctx *ctx, const bhr_camera *cam, int32_t k, const uint8_t **d_flags, int32_t *tiles_x);
 void bhr_hybrid_free(bhr_ctx *ctx);
 int32_t bhr_hybrid_active_list(bhr_ctx *ctx, const int32_t **list, int32_t *n);   // hybrid.o: the active slot's partitioned launch order (tests)
 int32_t bhr_bloom_prepare(bhr_ctx *ctx);

@@ -488,7 +488,7 @@ int32_t bhr_group_render_subset(bhr_ctx **ctxs, int32_t n, const bhr_camera *cam
     int expect = 0;
     for (int k = 0; k < n; ++k) {
         if (!ctxs[k]) return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: null ctx %d", k);
-        if (ctxs[k]->ss > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d is supersampled (row blocks render one sample per pixel)", k);
+        if (ctxs[k]->ss > 1 || ctxs[k]->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d is supersampled (row blocks render one sample per pixel)", k);
         if (ctxs[k]->cfg.width != W || ctxs[k]->cfg.height != H || ctxs[k]->cfg.row0 != expect)
             return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d does not continue the image (row0 %d, expected %d)", k, ctxs[k]->cfg.row0, expect);
         expect = ctxs[k]->cfg.row1;
@@ -542,7 +542,7 @@ int32_t bhr_group_sync(bhr_ctx **ctxs, int32_t n) {
 // publishing `done`; a rank returns when all have (nobody stores into a neighbour's planes while they are still read).
 int32_t bhr_tile_export(bhr_ctx *ctx, uint32_t gather_flags, bhr_tile_handles *out) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_export: bad argument");
-    if (ctx->ss > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_export: the context is supersampled (row blocks render one sample per pixel)");
+    if (ctx->ss > 1 || ctx->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_export: the context is supersampled (row blocks render one sample per pixel)");
     BHR_TRY(bhr_enter(ctx));
     BHR_TRY(bhr_activate_slot(ctx, 0));                                      // tile renders use slot 0, whatever bhr_render left active
     BHR_TRY(bhr_frame_begin(ctx, 0));                                        // the context's arithmetic picks the post-pass, allocates its planes
@@ -730,7 +730,7 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
 
 int32_t bhr_tile_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: bad argument");
-    if (ctx->ss > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the context is supersampled (row blocks render one sample per pixel)");
+    if (ctx->ss > 1 || ctx->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the context is supersampled (row blocks render one sample per pixel)");
     TilePipe *p = (TilePipe *)ctx->pipe;
     if (!p || !p->linked) return bhr_fail(BHR_ERR_STATE, "bhr_tile_render: call bhr_tile_connect first (a failed frame breaks the link: connect again)");
     if (flags & BHR_LENS_FLARE) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the lens flare needs the one-process path (bhr_group_render)");

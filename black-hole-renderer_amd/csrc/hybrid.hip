@@ -66,6 +66,9 @@ struct Hybrid {
     uint8_t *d_flags;
     int32_t *d_counts, *d_total, *h_total;
     int32_t n_tiles_alloc;
+    // adaptive supersampling (bhr_hybrid_fine_flags): per frame slot, the flags of the tiles of the frame k times finer than
+    // the marched one, made on the slot's own stream and kept while the view key stands
+    struct { uint8_t *d_flags; int32_t *d_total; double key[12]; int32_t k, valid; } fine[BHR_MAX_FRAME_SLOTS];
 };
 
 void view_key(const bhr_camera *cam, double lo, double hi, double pad, double tilt_deg, double key[12]) {
@@ -290,6 +293,36 @@ __global__ __launch_bounds__(CLS_EDGE * CLS_EDGE) void hybrid_classify_kernel(Cl
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(total_all, __popcll(m));
 }
 
+// the classification kernel's arguments for the frame `fr` seen through `cam` (both of the frame whose tiles are classified)
+ClassifyArgs classify_args(const bhr_camera *cam, const bhr_fine_frame &fr, double tilt_deg, double lo, double hi, double pad_f) {
+    ClassifyArgs ca;
+    const int W = fr.width, H = fr.height;
+    double cf[3];
+    for (int k = 0; k < 3; ++k) { ca.cp[k] = cam->pos[k]; ca.cr[k] = cam->right[k]; ca.cu[k] = cam->up[k]; cf[k] = cam->forward[k]; }
+    ca.pw = cam->pixel_width; ca.ph = cam->pixel_height;
+    const double half_w = ca.pw * W / 2, half_h = ca.ph * H / 2;
+    for (int k = 0; k < 3; ++k) ca.tl[k] = ca.cp[k] + cf[k] - half_w * ca.cr[k] + half_h * ca.cu[k];
+    ca.r0sq = ca.cp[0] * ca.cp[0] + ca.cp[1] * ca.cp[1] + ca.cp[2] * ca.cp[2];
+    const double tilt = tilt_deg * 3.14159265358979323846 / 180.0;
+    ca.nrm[0] = 0.0; ca.nrm[1] = -sin(tilt); ca.nrm[2] = cos(tilt);
+    ca.cpn = ca.cp[0] * ca.nrm[0] + ca.cp[1] * ca.nrm[1] + ca.cp[2] * ca.nrm[2];
+    ca.lo = lo; ca.hi = hi; ca.pad_f = pad_f;
+    ca.W = W; ca.rows = fr.rows; ca.row0 = fr.row0;
+    ca.tiles_x = (W + 7) / 8; ca.tiles_y = (fr.rows + 7) / 8;
+    ca.far_cam = ca.r0sq > 9.0;
+    return ca;
+}
+
+// the strict band below / above b_c of this context's hybrid marches (BHR_HYBRID_BAND="lo,hi" at bhr_create, or bhr_set_option):
+// certified at step sizes up to 0.1, it widens with a coarser step (bhr_launch_march_hybrid)
+void effective_band(const bhr_ctx *ctx, double *lo, double *hi) {
+    double l = 0.085, h = 0.36;
+    if (ctx->opt.hybrid_band_set) { l = ctx->opt.hybrid_band[0]; h = ctx->opt.hybrid_band[1]; }
+    const double widen = ctx->cfg.step_size > 0.1f ? (double)ctx->cfg.step_size / 0.1 : 1.0;
+    *lo = l * widen;
+    *hi = h * widen;
+}
+
 constexpr int PART_BLOCK = 256;
 // counts[b] = strict tiles among launch-order positions [256 b, 256 b + 256)
 __global__ __launch_bounds__(PART_BLOCK) void hybrid_count_kernel(const int32_t *__restrict__ order, int n, const uint8_t *__restrict__ flags,
@@ -365,6 +398,10 @@ void bhr_hybrid_free(bhr_ctx *ctx) {
         }
     if (h->cls_stream) { (void)hipStreamSynchronize(h->cls_stream); (void)hipStreamDestroy(h->cls_stream); }
     if (h->d_flags) (void)hipFree(h->d_flags);
+    for (auto &f : h->fine) {
+        if (f.d_flags) (void)hipFree(f.d_flags);
+        if (f.d_total) (void)hipFree(f.d_total);
+    }
     if (h->d_counts) (void)hipFree(h->d_counts);
     if (h->d_total) (void)hipFree(h->d_total);
     if (h->h_total) (void)hipHostFree(h->h_total);
@@ -435,6 +472,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
         h->valid = 0;
         h->n_strict = 0;
         h->last_fix_slot = -1;
+        memset(h->fine, 0, sizeof(h->fine));
         // band around b_c, in r_s: measured on the fixtures and the fhd / 4k / e2e frames (tools/hybrid_sweep.py)
         ctx->hybrid = h;
     }
@@ -447,8 +485,8 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
     double key[12];
     // the band was certified at step sizes up to 0.1; a coarser march amplifies more per step around the ring (a 0.3 march
     // lost a faint crossing at b_c + 0.59 that the binary64 evaluation keeps): the band widens with the step
-    const double widen = ctx->cfg.step_size > 0.1f ? (double)ctx->cfg.step_size / 0.1 : 1.0;
-    const double lo = h->lo * widen, hi = h->hi * widen;
+    double lo, hi;
+    effective_band(ctx, &lo, &hi);
     h->eff_lo = lo;
     h->eff_hi = hi;
     const double pad_f = ctx->opt.hybrid_pad;
@@ -487,21 +525,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
             }
             if (s.used_set[nxt]) BHR_HIP(hipStreamWaitEvent(h->cls_stream, s.used[nxt], 0));
             if (new_view) {
-                ClassifyArgs ca;
-                const int W = fr.width, H = fr.height;
-                double cf[3];
-                for (int k = 0; k < 3; ++k) { ca.cp[k] = cam->pos[k]; ca.cr[k] = cam->right[k]; ca.cu[k] = cam->up[k]; cf[k] = cam->forward[k]; }
-                ca.pw = cam->pixel_width; ca.ph = cam->pixel_height;
-                const double half_w = ca.pw * W / 2, half_h = ca.ph * H / 2;
-                for (int k = 0; k < 3; ++k) ca.tl[k] = ca.cp[k] + cf[k] - half_w * ca.cr[k] + half_h * ca.cu[k];
-                ca.r0sq = ca.cp[0] * ca.cp[0] + ca.cp[1] * ca.cp[1] + ca.cp[2] * ca.cp[2];
-                const double tilt = (double)ctx->cfg.disk_tilt_deg * 3.14159265358979323846 / 180.0;
-                ca.nrm[0] = 0.0; ca.nrm[1] = -sin(tilt); ca.nrm[2] = cos(tilt);
-                ca.cpn = ca.cp[0] * ca.nrm[0] + ca.cp[1] * ca.nrm[1] + ca.cp[2] * ca.nrm[2];
-                ca.lo = lo; ca.hi = hi; ca.pad_f = pad_f;
-                ca.W = W; ca.rows = fr.rows; ca.row0 = fr.row0;
-                ca.tiles_x = (W + 7) / 8; ca.tiles_y = (fr.rows + 7) / 8;
-                ca.far_cam = ca.r0sq > 9.0;
+                const ClassifyArgs ca = classify_args(cam, fr, (double)ctx->cfg.disk_tilt_deg, lo, hi, pad_f);
                 if ((long long)ca.tiles_x * ca.tiles_y != n_tiles) return bhr_fail(BHR_ERR_STATE, "hybrid march: %d x %d tiles, launch order of %d", ca.tiles_x, ca.tiles_y, n_tiles);
                 BHR_HIP(hipMemsetAsync(h->d_total + 1, 0, sizeof(int32_t), h->cls_stream));
                 hipLaunchKernelGGL(hybrid_classify_kernel, dim3((ca.tiles_x + CLS_EDGE - 1) / CLS_EDGE, (ca.tiles_y + CLS_EDGE - 1) / CLS_EDGE), dim3(CLS_EDGE * CLS_EDGE), 0,
@@ -645,4 +669,42 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
     ctx->fix_list = nullptr;
     ctx->fix_cap = 0;
     return rc;
+}
+
+// Adaptive supersampling under hybrid: which k x k groups the refinement marches strict.  The rule is the one a
+// bhr_set_supersample(k) hybrid frame classifies its tiles by -- the same kernel over the same arguments (fine frame, fine
+// pitch, the context's band and padding) -- written into a flag buffer of the frame slot on the frame's own stream (no host
+// wait: nobody needs the count) and kept while the view key stands.  The base march has run: the context's Hybrid exists.
+int32_t bhr_hybrid_fine_flags(bhr_ctx *ctx, const bhr_camera *out_cam, int32_t k, const uint8_t **d_flags, int32_t *tiles_x) {
+    Hybrid *h = (Hybrid *)ctx->hybrid;
+    if (!h) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: no hybrid march has run on this context");
+    bhr_camera cam = *out_cam;
+    cam.pixel_width /= (float)k;
+    cam.pixel_height /= (float)k;
+    const bhr_fine_frame fr = {ctx->cfg.width * k, ctx->cfg.height * k, ctx->cfg.row0 * k, ctx->rows * k};
+    double lo, hi, key[12];
+    effective_band(ctx, &lo, &hi);
+    const double pad_f = ctx->opt.hybrid_pad;
+    view_key(&cam, lo, hi, pad_f, (double)ctx->cfg.disk_tilt_deg, key);
+    auto &f = h->fine[ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0];
+    const ClassifyArgs ca = classify_args(&cam, fr, (double)ctx->cfg.disk_tilt_deg, lo, hi, pad_f);
+    if (!f.d_flags || f.k != k) {
+        // (a change of k has drained the context and freed the Hybrid: the buffer is allocated once per setting)
+        if (f.d_flags) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: the factor changed under a live classification");
+        BHR_HIP(hipMalloc((void **)&f.d_flags, (size_t)ca.tiles_x * ca.tiles_y));
+        BHR_HIP(hipMalloc((void **)&f.d_total, 64));
+        f.k = k;
+        f.valid = 0;
+    }
+    if (!f.valid || !same_view(f.key, key)) {
+        BHR_HIP(hipMemsetAsync(f.d_total, 0, sizeof(int32_t), ctx->stream));
+        hipLaunchKernelGGL(hybrid_classify_kernel, dim3((ca.tiles_x + CLS_EDGE - 1) / CLS_EDGE, (ca.tiles_y + CLS_EDGE - 1) / CLS_EDGE), dim3(CLS_EDGE * CLS_EDGE), 0,
+                           ctx->stream, ca, f.d_flags, f.d_total);
+        BHR_HIP(hipGetLastError());
+        memcpy(f.key, key, sizeof(key));
+        f.valid = 1;
+    }
+    *d_flags = f.d_flags;
+    *tiles_x = ca.tiles_x;
+    return BHR_OK;
 }

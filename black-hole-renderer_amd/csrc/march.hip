@@ -1090,18 +1090,30 @@ __device__ __forceinline__ unsigned long long wave_sum_u32(unsigned int v) {
 // march_fix_kernel (strict objects) marches again with the strict Ray.
 // SS (supersampled instantiations, a.ss > 1): the tile is one of the fine frame, its k x k groups are resolved in the wave
 // (resolve_store); the guard appends whole groups.
-template <bool DIFF, int SRC = 0, bool GUARD = false, bool COSTS = true, bool SS = false>
-__device__ __forceinline__ void march_tile_body(const BhrMarchArgs &a, const int slot) {
+// LIST (march_list_kernel, the refinement of an adaptively supersampled frame): the launch's tiles are the fine tiles the detect
+// kernel listed (a.tile_order, list_n of them: a count the device holds), and only the k x k groups of refined output pixels
+// are marched and stored -- a.fix_list is then the detect kernel's mask, one byte per OUTPUT pixel; the other lanes sit the
+// march out like the lanes beyond the frame's edge.  The wave is a tile of the fine frame exactly as in the frame's own
+// supersampled kernel, and everything between the two places that name the lane's pixel is that kernel's code: under
+// fast-math the form of the code around the march decides how it is contracted and re-associated, and a refined pixel has to
+// be the supersampled frame's bit for bit.
+__device__ __forceinline__ bool list_refined(const BhrMarchArgs &a, int i, int j) {
+    return ((const unsigned char *)a.fix_list)[(size_t)(j >> a.ss_log2) * a.out_width + (i >> a.ss_log2)] != 0;
+}
+
+template <bool DIFF, int SRC = 0, bool GUARD = false, bool COSTS = true, bool SS = false, bool LIST = false>
+__device__ __forceinline__ void march_tile_body(const BhrMarchArgs &a, const int slot, const int list_n = 0) {
     const int lane = threadIdx.x & 63;
     // one 8x8 tile per wave; `slot` is its position in the launch order
     // tiles are handed out longest first (tile_order: by distance from the image of the hole, where rays take the
     // most steps), so that the launch does not end on a few late, long waves
     // n_list = launch slots of THIS launch: all tiles of the row block, or the sub-list a hybrid launch hands this kernel
-    const int tile = slot < a.n_list ? (a.tile_order ? a.tile_order[slot] : slot) : a.n_tiles;
+    const int tile = slot < (LIST ? list_n : a.n_list) ? (a.tile_order ? a.tile_order[slot] : slot) : a.n_tiles;
     const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
     const int i = tx * 8 + (lane & 7);
     const int j = ty * 8 + (lane >> 3);
-    const bool valid = tile < a.n_tiles && i < a.width && j < a.rows;
+    bool valid = tile < a.n_tiles && i < a.width && j < a.rows;
+    if (LIST) valid = valid && list_refined(a, i, j);
     // (slot, tile, tx, ty are wave-uniform: march_tile_kernel / march_tile_of_wave hand over a readfirstlane'd slot)
 
 #if BHR_WAVE_STAMPS_BUILD
@@ -1159,7 +1171,8 @@ __device__ __forceinline__ void march_tile_body(const BhrMarchArgs &a, const int
         int t2 = threadIdx.x;
         asm volatile("" : "+v"(t2));
         const int i2 = tx * 8 + (t2 & 7), j2 = ty * 8 + ((t2 & 63) >> 3);
-        const bool valid2 = tile < a.n_tiles && i2 < a.width && j2 < a.rows;
+        bool valid2 = tile < a.n_tiles && i2 < a.width && j2 < a.rows;
+        if (LIST) valid2 = valid2 && list_refined(a, i2, j2);
         bool again = false;
         if (GUARD) {
             again = valid2 && ray.sh.unsure != 0;
@@ -1259,6 +1272,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DIFF ? 4 : 
     march_tile_body<DIFF, 0, true, false, true>(a, blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
 #endif
+
+// The refinement of an adaptively supersampled frame: the fine tiles the detect kernel listed, marched by the tile body in its
+// LIST form (every object).  The host does not know the list's length (frames stay in flight): like the fix kernel it is
+// launched with a grid for the list's capacity -- every tile of the fine frame -- and the waves beyond the count the detect
+// kernel left exit at once.  No loop over the list around the body: in the fast object a trip loop changed how the march's
+// arithmetic was contracted (the loop-invariant parts of the ray set-up were hoisted and re-associated).
+template <bool DIFF, int SRC>
+__global__ __launch_bounds__(256) void march_list_kernel(BhrMarchArgs a) {
+    const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int n = (int)__builtin_amdgcn_readfirstlane(*a.fix_count);
+    if (n > a.n_list) n = a.n_list;
+    if (wave >= n) return;
+    march_tile_body<DIFF, SRC, false, false, true, true>(a, wave, n);
+}
 
 #if BHR_MARCH_ILP
 // Second half of the hybrid march's fast list: the pixels march_tile_guard_kernel put on the fix list, 64 per wave whatever
@@ -1394,6 +1421,68 @@ __global__ __launch_bounds__(256) void march_persistent_kernel(BhrMarchArgs a, i
 }
 
 #if BHR_MARCH_STRICT
+// ---- adaptive supersampling (bhr_set_adaptive_supersample): which output pixels get k x k rays ---------------------------
+// c(p) = the largest |L[p] - L[n]| over the edge neighbours n of p inside the frame, both layers L of the k = 1 frame and the
+// three channels (each difference one f32 subtraction); p is refined iff c(p) > T.  One wave per 8 x 8 block of output pixels.
+// It writes the mask (one byte per output pixel) and lists the 8 x 8 tiles of the FINE frame that hold a refined pixel -- k
+// divides 8, so a block is (k x k) whole fine tiles of (8 / k) x (8 / k) output pixels each; the lane of a tile's first pixel
+// lists it -- wave-aggregated: one atomicAdd per wave and list.  Under hybrid a tile goes to the strict list (list, counts[0])
+// or the fast one (list + cap, counts[1]) by its flag; otherwise everything goes to the first.  counts[2], [3]: refined pixels
+// in tiles of the first / second list.  Each list has room for every fine tile.  Built without fast-math: T may be +inf.
+__global__ __launch_bounds__(256) void adaptive_detect_kernel(BhrDetectArgs d) {
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bx_n = (d.width + 7) / 8;
+    const int bx = wave % bx_n, by = wave / bx_n;
+    const int i = bx * 8 + (lane & 7), j = by * 8 + (lane >> 3);
+    const bool valid = i < d.width && j < d.height;
+    float c = 0.0f;
+    if (valid) {
+        const size_t o = ((size_t)j * d.width + i) * 3;
+        const int di[4] = {-1, 1, 0, 0}, dj[4] = {0, 0, -1, 1};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int ni = i + di[q], nj = j + dj[q];
+            if (ni < 0 || ni >= d.width || nj < 0 || nj >= d.height) continue;
+            const size_t m = ((size_t)nj * d.width + ni) * 3;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                c = fmaxf(c, fabsf(__fsub_rn(d.bg[o + ch], d.bg[m + ch])));
+                c = fmaxf(c, fabsf(__fsub_rn(d.disk[o + ch], d.disk[m + ch])));
+            }
+        }
+    }
+    const bool refine = valid && c > d.threshold;
+    if (valid) d.mask[(size_t)j * d.width + i] = refine ? 1 : 0;
+    // the lane's fine tile: s x s output pixels, s = 8 / k; its lanes inside the wave
+    const int s_log2 = 3 - d.k_log2, s = 1 << s_log2;
+    const int lx = (lane & 7) & ~(s - 1), ly = (lane >> 3) & ~(s - 1);
+    const unsigned long long row = ((1ull << s) - 1ull) << lx;
+    unsigned long long tile_lanes = 0;
+    for (int r = 0; r < s; ++r) tile_lanes |= row << ((ly + r) * 8);
+    const unsigned long long mr = __ballot(refine);
+    const int n_ref = __popcll(mr & tile_lanes);                       // refined pixels of the lane's tile
+    const bool lead = valid && (lane & 7) == lx && (lane >> 3) == ly && n_ref > 0;
+    const int tile = ((j << d.k_log2) >> 3) * d.fine_tiles_x + ((i << d.k_log2) >> 3);
+    bool second = false;
+    if (d.flags && lead) second = d.flags[tile] == 0;
+    const unsigned long long m0 = __ballot(lead && !second), m1 = __ballot(lead && second);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // refined pixels per list: the leaders' counts, summed over the wave
+    int p0 = lead && !second ? n_ref : 0, p1 = lead && second ? n_ref : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { p0 += __shfl_xor(p0, off, BHR_WAVE); p1 += __shfl_xor(p1, off, BHR_WAVE); }
+    unsigned int base0 = 0, base1 = 0;
+    if (lane == 0 && m0) { base0 = atomicAdd(d.counts + 0, (unsigned int)__popcll(m0)); atomicAdd(d.counts + 2, (unsigned int)p0); }
+    if (lane == 0 && m1) { base1 = atomicAdd(d.counts + 1, (unsigned int)__popcll(m1)); atomicAdd(d.counts + 3, (unsigned int)p1); }
+    base0 = __shfl(base0, 0, BHR_WAVE);
+    base1 = __shfl(base1, 0, BHR_WAVE);
+    if (lead) {
+        const unsigned int at = second ? base1 + (unsigned int)__popcll(m1 & below) : base0 + (unsigned int)__popcll(m0 & below);
+        if (at < (unsigned int)d.cap) d.list[(second ? (size_t)d.cap : 0) + at] = tile;
+    }
+}
+
 // ---- self-test of the hand-written exact arithmetic against hipcc's IEEE sequences ----------
 __device__ __forceinline__ unsigned int lcg(unsigned int &s) { s = s * 1664525u + 1013904223u; return s; }
 __global__ void selftest_kernel(unsigned long long *out, unsigned int div_rounds) {
@@ -1441,11 +1530,18 @@ const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_
     case BHR_MK_FIX:
         if (ss) return diff ? (const void *)march_fix_ss_kernel<true> : (const void *)march_fix_ss_kernel<false>;
         return diff ? (const void *)march_fix_kernel<true> : (const void *)march_fix_kernel<false>;
+    case BHR_MK_LIST: return diff ? (const void *)march_list_kernel<true, 0> : (const void *)march_list_kernel<false, 0>;
     default: return nullptr;
     }
 }
 #elif BHR_MARCH_STRICT
 const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss) {
+    switch (k) {   // adaptive supersampling: the detect kernel and the list kernels of the Disk V2 sources (a.ss > 1 always)
+    case BHR_MK_DETECT: return (const void *)adaptive_detect_kernel;
+    case BHR_MK_LIST_VOLUME: return (const void *)march_list_kernel<false, 2>;
+    case BHR_MK_LIST_DV2: return diff ? (const void *)march_list_kernel<true, 1> : (const void *)march_list_kernel<false, 1>;
+    default: break;
+    }
     if (ss) {
         switch (k) {
         case BHR_MK_VOLUME: return (const void *)march_tile_ss_kernel<false, 2>;
@@ -1470,6 +1566,12 @@ int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4) {
 }
 #else
 const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss) {
+    switch (k) {   // adaptive supersampling: the list kernels (a.ss > 1 always)
+    case BHR_MK_LIST: return diff ? (const void *)march_list_kernel<true, 0> : (const void *)march_list_kernel<false, 0>;
+    case BHR_MK_LIST_VOLUME: return (const void *)march_list_kernel<false, 2>;
+    case BHR_MK_LIST_DV2: return diff ? (const void *)march_list_kernel<true, 1> : (const void *)march_list_kernel<false, 1>;
+    default: break;
+    }
     if (ss) {
         switch (k) {
         case BHR_MK_VOLUME: return (const void *)march_tile_ss_kernel<false, 2>;

@@ -76,6 +76,11 @@ float fast_sqrt(float s) {
 //   fast           AA, mip_lds on, no part, a level fits 44 KB          march_tile_mipstaged_kernel (sets ctx->mip_lds_from)
 //   fast           AA otherwise                                         march_tile_kernel<true, 0> (ctx->mip_lds_from = -1)
 //   fast           plain                                                march_tile_plain_fast
+// The refinement of an adaptively supersampled frame (bhr_launch_adaptive) launches, behind the base march's kernels above:
+//   strict         the detect kernel                                    adaptive_detect_kernel (strict)
+//   fast / strict  Disk V2 volume / analytic source                     march_list_kernel<false, 2> / <diff, 1> (own object)
+//   strict         texture (and the strict list of a hybrid frame)      march_list_kernel<diff, 0> (strict_ilp)
+//   fast           texture (and the fast list of a hybrid frame)        march_list_kernel<diff, 0> (fast)
 //
 // diff: anti_alias && !BHR_SKIP_DIFFERENTIALS.  Grids: blocks of 4 waves, a wave per tile of the launch's list; a wave per 64
 // entries of the fix list's capacity; the persistent kernel enough blocks to fill the chip.
@@ -165,18 +170,10 @@ int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t 
     return BHR_OK;
 }
 
-int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
+// The kernel argument block of a march of the frame bhr_fine(ctx) under the fast or the strict arithmetic: everything but the
+// launch's own list, row-cost and diagnostic pointers.
+static void march_args(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, bool fast, BhrMarchArgs &a) {
     const bhr_config &c = ctx->cfg;
-    // a partial launch (ctx->part: one list of a hybrid march) marches the tiles of a caller-made list under the arithmetic the
-    // caller chose; the first part records the start event and clears an untimed counter, the last part records the end event
-    const bhr_march_part part = ctx->part;
-    const int math = part.active ? part.math : bhr_resolve_math(ctx, flags);
-    if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, cam, flags);
-    const bool fast = math == BHR_MATH_FAST;
-    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
-    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_render: no disk texture set (bhr_set_disk_texture)");
-
-    BhrMarchArgs a;
     for (int k = 0; k < 3; ++k) {
         a.cp[k] = cam->pos[k];
         a.cr[k] = cam->right[k];
@@ -265,8 +262,27 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     a.mip_lds_from = -1;
     a.fix_list = ctx->fix_list;
     a.fix_cap = ctx->fix_cap;
-    const bool first_part = !part.active || part.first, last_part = !part.active || part.last;
     a.row_steps = nullptr;
+    a.wave_stamps = nullptr;
+    a.tile_order = nullptr;
+}
+
+int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
+    const bhr_config &c = ctx->cfg;
+    // a partial launch (ctx->part: one list of a hybrid march) marches the tiles of a caller-made list under the arithmetic the
+    // caller chose; the first part records the start event and clears an untimed counter, the last part records the end event
+    const bhr_march_part part = ctx->part;
+    const int math = part.active ? part.math : bhr_resolve_math(ctx, flags);
+    if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, cam, flags);
+    const bool fast = math == BHR_MATH_FAST;
+    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
+    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_render: no disk texture set (bhr_set_disk_texture)");
+
+    BhrMarchArgs a;
+    march_args(ctx, cam, flags, fast, a);
+    const bhr_fine_frame fr = bhr_fine(ctx);
+    const int slot = ctx->cur_slot;
+    const bool first_part = !part.active || part.first, last_part = !part.active || part.last;
     if (flags & BHR_ROW_COSTS) {
         // two profiles side by side: [0, n) the steps taken by the fast arithmetic, [n, 2n) by the strict one (a hybrid frame
         // fills both, from its two tile lists); cleared by the frame's first part, on the stream every other part follows
@@ -275,7 +291,6 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
         if (first_part) BHR_HIP(hipMemsetAsync(ctx->d_row_steps, 0, 2 * n * sizeof(unsigned long long), ctx->stream));
         a.row_steps = ctx->d_row_steps + (fast ? 0 : n);
     }
-    a.wave_stamps = nullptr;
     // diagnostic (builds with -DBHR_WAVE_STAMPS_BUILD=1 only: the stamps cost the plain kernel three spilled registers):
     // BHR_WAVE_STAMPS=<file> dumps per-wave start / end times of THIS launch (tools/wave_timeline.py)
 #if BHR_WAVE_STAMPS_BUILD
@@ -317,7 +332,7 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     BHR_HIP(hipGetLastError());
     // group / tile renders (slot < 0) record the march's end only on request: the event is a ~5 us bubble between the march and
     // the H pass of a tile whose whole tail is ~0.12 ms
-    if (last_part && (slot >= 0 || ctx->group_time_march)) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1], ctx->stream));
+    if (last_part && !ctx->defer_march_end && (slot >= 0 || ctx->group_time_march)) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1], ctx->stream));
     if (last_part) ctx->march_end_recorded = slot >= 0 || ctx->group_time_march;
     if (d_stamps) {
         std::vector<unsigned long long> h((size_t)a.n_tiles * 4);
@@ -328,5 +343,82 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     }
     ctx->last_steps_ptr = a.ray_steps;
     ctx->counters.rays = (uint64_t)fr.width * fr.rows;
+    return BHR_OK;
+}
+
+// Adaptive supersampling (bhr_set_adaptive_supersample), behind the frame's k = 1 march on ctx->stream: clear the counts ->
+// [hybrid: flags of the fine frame's tiles] -> detect (mask + lists of fine tiles) -> refine (first list, second list) -> march-end event.  Nothing here
+// waits for the device: the refinement's grids are sized for the lists' capacity, and waves beyond what the detect kernel listed exit at once.
+int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
+    const int k = ctx->ada_k, W = ctx->cfg.width, H = ctx->rows;
+    const int math = bhr_resolve_math(ctx, flags);
+    const int slot_k = ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0;
+    auto &l = ctx->ada[slot_k];
+    const int32_t fine_tiles_x = (W * k + 7) / 8, cap = fine_tiles_x * ((H * k + 7) / 8);   // tiles of the fine frame
+    if (!l.d_list) {
+        // for every factor: the buffers outlive a change of k, and ceil(k W / 8) ceil(k H / 8) <= W H for k <= 8
+        BHR_HIP(hipMalloc((void **)&l.d_list, 2 * (size_t)W * H * sizeof(int32_t)));
+        BHR_HIP(hipMalloc((void **)&l.d_mask, (size_t)W * H));
+        BHR_HIP(hipMalloc((void **)&l.d_counts, 64));
+    }
+    if ((long long)cap > (long long)W * H) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: %d fine tiles for %d x %d pixels", cap, W, H);
+    BHR_HIP(hipMemsetAsync(l.d_counts, 0, 4 * sizeof(unsigned int), ctx->stream));
+    BhrDetectArgs d;
+    d.bg = ctx->d_bg;
+    d.disk = ctx->d_disk;
+    d.width = W;
+    d.height = H;
+    d.threshold = ctx->ada_threshold;
+    d.k_log2 = k == 8 ? 3 : k == 4 ? 2 : 1;
+    d.flags = nullptr;
+    d.fine_tiles_x = fine_tiles_x;
+    int32_t flag_tiles_x = fine_tiles_x;
+    if (math == BHR_MATH_HYBRID) BHR_TRY(bhr_hybrid_fine_flags(ctx, cam, k, &d.flags, &flag_tiles_x));
+    if (flag_tiles_x != fine_tiles_x) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: %d flag columns for %d tile columns", flag_tiles_x, fine_tiles_x);
+    d.mask = l.d_mask;
+    d.list = l.d_list;
+    d.cap = cap;
+    d.counts = l.d_counts;
+    {
+        const int blocks = ((W + 7) / 8) * ((H + 7) / 8);            // a wave per 8 x 8 block of output pixels
+        void *args[] = {&d};
+        (void)hipLaunchKernel(bhr_march_kernel_strict(BHR_MK_DETECT, 0, 0), dim3((blocks + 3) / 4), dim3(256), args, 0, ctx->stream);
+        BHR_HIP(hipGetLastError());
+    }
+    // the refinement marches the fine frame: the second argument block of the frame (ss = k, stores into the output frame)
+    const bool want_diff = ctx->cfg.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS);
+    auto refine = [&](bool fast, int which) -> int32_t {
+        BhrMarchArgs a;
+        ctx->ss = k;
+        march_args(ctx, cam, flags, fast, a);
+        ctx->ss = 1;
+        // a tile per wave, a grid for the list's capacity (every fine tile): waves beyond the list's length exit at once
+        a.tile_order = l.d_list + (size_t)which * cap;
+        a.n_list = cap;
+        a.fix_count = l.d_counts + which;
+        a.fix_list = (int32_t *)l.d_mask;                           // LIST kernels read it as the mask (march.hip: list_refined)
+        a.fix_cap = 0;
+        if (a.n_tiles != cap) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: %d fine tiles, lists for %d", a.n_tiles, cap);
+        const auto own = fast ? bhr_march_kernel_fast : bhr_march_kernel_strict;
+        const void *fn = ctx->disk_source == BHR_DISK_V2_VOLUME ? own(BHR_MK_LIST_VOLUME, 0, 1)
+                         : a.dv2                                 ? own(BHR_MK_LIST_DV2, want_diff, 1)
+                         : fast                                  ? bhr_march_kernel_fast(BHR_MK_LIST, want_diff, 1)
+                                                                 : bhr_march_kernel_strict_ilp(BHR_MK_LIST, want_diff, 1);
+        if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_render: no list kernel for the refinement of this frame");
+        void *args[] = {&a};
+        (void)hipLaunchKernel(fn, dim3((cap + 3) / 4), dim3(256), args, 0, ctx->stream);
+        BHR_HIP(hipGetLastError());
+        return BHR_OK;
+    };
+    if (math == BHR_MATH_HYBRID) {
+        BHR_TRY(refine(false, 0));       // longest rays first, as the base march has it
+        BHR_TRY(refine(true, 1));
+    } else {
+        BHR_TRY(refine(math == BHR_MATH_FAST, 0));
+    }
+    const int slot = ctx->cur_slot;
+    if (slot >= 0 || ctx->group_time_march) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1], ctx->stream));
+    ctx->ada_last_slot = slot_k;
+    ctx->ada_last_math = math;
     return BHR_OK;
 }

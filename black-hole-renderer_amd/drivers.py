@@ -83,7 +83,7 @@ def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, 
                   tex_h=1024, r_max=10.0, disk_texture_path=None, r_disk_inner=R_DISK_INNER_DEFAULT,
                   r_disk_outer=R_DISK_OUTER_DEFAULT, disk_tilt=0.0, lens_flare=False, anti_alias="disabled",
                   aa_strength=1.0, disk_rotation_speed=0.1, device_index=0, rows=None, frame_slots=None, math=None,
-                  supersample=1):
+                  supersample=1, supersample_threshold=None):
     """Renderer with a placeholder (or file) disk texture, as the reference's entry points build it
     (render.py:4044-4064, 4627-4644).  Returns (renderer, use_lifecycle, n_r, n_phi)."""
     # procedural sky: the host draws its random tables, the device rasterises them (nebula resize, star blobs in
@@ -106,7 +106,8 @@ def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, 
                            r_disk_inner=r_disk_inner, r_disk_outer=r_disk_outer, disk_tilt=disk_tilt,
                            lens_flare=lens_flare, anti_alias=anti_alias, aa_strength=aa_strength,
                            disk_rotation_speed=disk_rotation_speed, device_index=device_index, rows=rows,
-                           frame_slots=frame_slots, supersample=supersample, **({} if math is None else {"math": math}))
+                           frame_slots=frame_slots, supersample=supersample, supersample_threshold=supersample_threshold,
+                           **({} if math is None else {"math": math}))
     if procedural_sky:
         renderer.build_procedural_skybox(seed=42, n_stars=n_stars)
     return renderer, use_lifecycle, n_r, n_phi
@@ -120,11 +121,12 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  aa_strength: float = 1.0, disk_rotation_speed: float = 0.1, disk_generation_scale: int = 2,
                  force_regenerate_disk_texture: bool = False, ignore_taichi_cache: bool = False,
                  gpus: int = 1, disk_model: str = "texture", math: Optional[str] = None,
-                 supersample: int = 1) -> np.ndarray:
+                 supersample: int = 1, supersample_threshold: Optional[float] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
-    pixel (one device only)."""
+    pixel (one device only); ``supersample_threshold``: adaptive -- only for the pixels whose k = 1 neighbours differ by more
+    than it (HipRenderer.set_supersample; None: every pixel)."""
     if gpus > 1 and supersample != 1:
         raise ValueError("supersample > 1 renders on one GPU: row-block tiles march one ray per pixel")
     if gpus > 1:
@@ -138,7 +140,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     renderer, use_lifecycle, n_r, n_phi = make_renderer(
         width, height, cam_pos, fov, step_size, skybox_path, n_stars, tex_w, tex_h, r_max, disk_texture_path,
         r_disk_inner, r_disk_outer, disk_tilt, lens_flare, anti_alias, aa_strength, disk_rotation_speed, math=math,
-        supersample=supersample)
+        supersample=supersample, supersample_threshold=supersample_threshold)
     if use_analytic_disk(renderer, disk_model):
         pass
     elif use_lifecycle:
@@ -234,7 +236,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  disk_rotation_speed: float = 0.1, orbit_degrees: float = 360.0, rank: int = 0, world: int = 1,
                  assemble: bool = True, png_level: int = DEVICE, sink_slots: int = 0, sink_workers: int = 0,
                  video_stream: str = "auto", stats: Optional[dict] = None, supersample: Optional[int] = None,
-                 **_deprecated_kwargs) -> None:
+                 supersample_threshold: Optional[float] = None, **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -248,9 +250,12 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     sink's threads only fetch and write the finished files); 0..9 selects the host encoder at that zlib level
     (smaller files, ~50 ms of a host core per fhd frame at level 1).
 
-    ``supersample``: k x k rays per pixel for the frames of the video (None: as the renderer is set)."""
+    ``supersample``: k x k rays per pixel for the frames of the video (None: as the renderer is set);
+    ``supersample_threshold``: with it, adaptive (only the pixels whose k = 1 neighbours differ by more than it)."""
     if supersample is not None:
-        renderer.set_supersample(supersample)
+        renderer.set_supersample(supersample, supersample_threshold)
+    elif supersample_threshold is not None:
+        renderer.set_supersample(renderer.supersample, supersample_threshold)
     os.makedirs(os.path.dirname(output_path) or ".", exist_ok=True)
     temp_dir = _frames_dir(output_path)
     submitted: List[int] = []

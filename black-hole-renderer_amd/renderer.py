@@ -41,6 +41,13 @@ def _check_supersample(k) -> None:
         raise ValueError(f"supersample must be one of {SUPERSAMPLE_FACTORS}, got {k!r}")
 
 
+def _check_threshold(t) -> None:
+    if t is None:
+        return
+    if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or t != t:
+        raise ValueError(f"supersample_threshold must be a number (not NaN) or None, got {t!r}")
+
+
 class HipRenderer:
     """Renders Schwarzschild black-hole frames on one MI355X (or one row block of a frame).
 
@@ -57,9 +64,12 @@ class HipRenderer:
                  disk_rotation_speed=0.1, ignore_taichi_cache=False,
                  device_index: int = 0, rows: Optional[Sequence[int]] = None, math: str = "strict",
                  frame_slots: Optional[int] = None, outputs: Optional[str] = None, options: Optional[dict] = None,
-                 supersample: int = 1):
+                 supersample: int = 1, supersample_threshold: Optional[float] = None):
         # supersample=k: k x k rays per pixel, box-filtered inside the march (bhr_set_supersample; include/bhr.h states the filter)
+        # supersample_threshold=T: adaptive -- k x k rays only for the pixels whose k = 1 neighbours differ by more than T
+        # (bhr_set_adaptive_supersample); None: every pixel
         _check_supersample(supersample)
+        _check_threshold(supersample_threshold)
         if device not in ("hip", "gpu"):
             raise ValueError(f"HipRenderer runs on the GPU only (device={device!r}); there is no CPU path")
         # math="strict" (default): the RK4 loop in the reference's operation order with IEEE sqrt and
@@ -115,9 +125,10 @@ class HipRenderer:
         for name, value in (options or {}).items():
             self.set_option(name, value)
         self._supersample = 1
-        if supersample != 1:
+        self._supersample_threshold = None
+        if supersample != 1 or supersample_threshold is not None:
             try:
-                self.set_supersample(supersample)
+                self.set_supersample(supersample, supersample_threshold)
             except Exception:
                 self.close()
                 raise
@@ -423,11 +434,30 @@ class HipRenderer:
         """k: every pixel is the box filter of k x k rays (1: one ray per pixel)."""
         return self._supersample
 
-    def set_supersample(self, k: int) -> None:
-        """k x k rays per pixel for the frames rendered from now on (bhr_set_supersample): 1, 2, 4 or 8; whole-frame contexts only."""
+    @property
+    def supersample_threshold(self) -> Optional[float]:
+        """T of adaptive supersampling: only pixels whose k = 1 neighbours differ by more than T get the k x k rays (None: all)."""
+        return self._supersample_threshold
+
+    def set_supersample(self, k: int, threshold: Optional[float] = None) -> None:
+        """k x k rays per pixel for the frames rendered from now on (bhr_set_supersample): 1, 2, 4 or 8; whole-frame contexts
+        only.  threshold=T: adaptive (bhr_set_adaptive_supersample; include/bhr.h states the function) -- one ray per pixel,
+        k x k for the pixels whose largest difference to an edge neighbour in the k = 1 frame exceeds T."""
         _check_supersample(k)
-        _lib.check(self._lib.bhr_set_supersample(self._ctx, int(k)))
+        _check_threshold(threshold)
+        if threshold is None:
+            _lib.check(self._lib.bhr_set_supersample(self._ctx, int(k)))
+        else:
+            _lib.check(self._lib.bhr_set_adaptive_supersample(self._ctx, int(k), float(threshold)))
         self._supersample = int(k)
+        self._supersample_threshold = None if threshold is None or int(k) == 1 else float(np.float32(threshold))
+
+    def adaptive_info(self) -> dict:
+        """The last adaptively supersampled frame: pixels refined, how many of them were marched strict, pixels of the frame
+        (bhr_adaptive_info; synchronises)."""
+        out = (C.c_int64 * 3)()
+        _lib.check(self._lib.bhr_adaptive_info(self._ctx, out))
+        return dict(refined=int(out[0]), strict=int(out[1]), pixels=int(out[2]))
 
     def set_option(self, name: str, value) -> None:
         """One of the library's switches for this context (bhr_set_option; include/bhr.h lists them)."""

@@ -275,6 +275,33 @@ BHR_API int32_t bhr_set_outputs(bhr_ctx *ctx, uint32_t mask);
  * BHR_ERR_INVALID: k not in {1, 2, 4, 8}, a row-block context (k > 1), or k^2 W H >= 2^31.  With k > 1, bhr_render with
  * BHR_PERSISTENT or BHR_ROW_COSTS, bhr_group_render*, bhr_tile_export and bhr_tile_render return BHR_ERR_INVALID. */
 BHR_API int32_t bhr_set_supersample(bhr_ctx *ctx, int32_t k);
+/* Adaptive supersampling: one ray per pixel, and k x k rays only where the k = 1 frame's neighbours differ.  k = 2, 4 or 8
+ * and a threshold T (f32); k = 1 turns supersampling off.  bhr_set_supersample keeps its meaning (every pixel) and turns
+ * adaptivity off.  A frame of a W x H whole-frame context is then this function of (view, k, T):
+ *  1. Base frame.  The context's ordinary k = 1 march (its arithmetic, hybrid lists, guards and fix list included) gives the
+ *     layers BG1, DISK1.
+ *  2. Contrast.  For pixel p = (i, j), over its edge neighbours n in {(i-1, j), (i+1, j), (i, j-1), (i, j+1)} inside the
+ *     frame, both layers L in {BG1, DISK1} and the three channels: c(p) = max |L[p] - L[n]|, each difference one f32
+ *     subtraction.  A 1 x 1 frame has c = 0.
+ *  3. Refined set.  R = {p : c(p) > T}, an f32 comparison: T = +inf refines nothing, any T < 0 every pixel; NaN is refused.
+ *  4. Refined pixels.  For p in R, BG and DISK are the values pixel p has in the frame bhr_set_supersample(k) renders of the
+ *     same view (same fine grid at pitch pw / k, ph / k, same pairwise tree, same 1 / k^2), the k x k group marched with: the
+ *     strict arithmetic under strict (and wherever hybrid resolves to strict: Disk V2 sources); the fast one under fast;
+ *     under hybrid the strict one if the 8 x 8 tile of the FINE frame that holds the group (k divides 8: exactly one does) is
+ *     a strict tile by the rule a bhr_set_supersample(k) hybrid frame classifies by (same band, padding and edge-on wedge),
+ *     else the fast one -- WITHOUT guards: one ray on a switch weighs 1 / k^2.  Disk V2 sources: the base march's.
+ *  5. Other pixels keep BG1, DISK1.  Everything the march stores besides the two layers (the split-f16 post-pass's inputs) is
+ *     rewritten for refined pixels: bloom, combine, lens flare, quantisation, PNG and video sinks run unchanged.
+ * The frame does not depend on the order in which the device listed R.  A contrast criterion cannot see what no k = 1 ray
+ * hit: a star (or any feature) smaller than a pixel that falls between the k = 1 rays of a smooth neighbourhood is not
+ * refined, whatever T >= 0.  Counters: rays = W H + k^2 |R|, ray_steps = base march + refinement; the march's time includes
+ * detection and refinement.  Ordered behind the frames in flight.  BHR_ERR_INVALID: NaN threshold, k not in {1, 2, 4, 8}, a
+ * row-block context (k > 1), k^2 W H >= 2^31.  While adaptive, bhr_render with BHR_PERSISTENT or BHR_ROW_COSTS,
+ * bhr_group_render*, bhr_tile_export and bhr_tile_render return BHR_ERR_INVALID, as with bhr_set_supersample(k > 1). */
+BHR_API int32_t bhr_set_adaptive_supersample(bhr_ctx *ctx, int32_t k, float threshold);
+/* out = {refined pixels |R| of the last adaptive frame, those of them marched with the strict arithmetic, pixels of the
+ * frame}.  Synchronises.  BHR_ERR_STATE before the first frame rendered under bhr_set_adaptive_supersample(k > 1). */
+BHR_API int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]);
 /* The library's switches.  Each has an environment variable that bhr_create reads ONCE (no entry point calls getenv
  * afterwards) and can be changed per context later with this call -- what tests and A/B tools use:
  *   "bloom_split"     BHR_BLOOM_SPLIT     -1 post-pass by arithmetic (exact f32 under strict, split f16 under fast / hybrid), 0 / 1 force
