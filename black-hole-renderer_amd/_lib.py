@@ -28,6 +28,7 @@ SYMBOLS = (
     "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
     "bhr_stats_prepare", "bhr_stats_select", "bhr_stats_row_statistics",
     "bhr_png_bound", "bhr_png_encode", "bhr_png_write", "bhr_png_device_bound", "bhr_png_device_max_width", "bhr_png_encode_device", "bhr_png_device_menu",
+    "bhr_jpeg_device_bound", "bhr_jpeg_restart_interval", "bhr_jpeg_tables", "bhr_jpeg_encode_device", "bhr_sink_create_jpeg",
     "bhr_sink_create", "bhr_sink_submit", "bhr_sink_drain",
     "bhr_sink_destroy", "bhr_y4m_open", "bhr_y4m_submit", "bhr_y4m_drain", "bhr_y4m_close",
 )
@@ -150,6 +151,11 @@ def load() -> C.CDLL:
     lib.bhr_png_encode_device.argtypes = [P, U8, I64, C.POINTER(I64)]
     U32P = C.POINTER(C.c_uint32)
     lib.bhr_png_device_menu.argtypes = [I32, U32P, U32P, U32P, C.POINTER(I32)]
+    lib.bhr_jpeg_device_bound.argtypes = [I32, I32]
+    lib.bhr_jpeg_restart_interval.argtypes = [I32]
+    lib.bhr_jpeg_tables.argtypes = [I32, U8, U8, U8]
+    lib.bhr_jpeg_encode_device.argtypes = [P, I32, U8, I64, C.POINTER(I64)]
+    lib.bhr_sink_create_jpeg.argtypes = [P, I32, I32, I32, C.POINTER(P)]
     lib.bhr_sink_create.argtypes = [P, I32, I32, I32, C.POINTER(P)]
     lib.bhr_sink_submit.argtypes = [P, C.c_char_p]
     lib.bhr_sink_drain.argtypes = [P, C.POINTER(I64), C.POINTER(I64)]
@@ -160,10 +166,11 @@ def load() -> C.CDLL:
     lib.bhr_y4m_close.argtypes = [P]
     for name in SYMBOLS:
         fn = getattr(lib, name)
-        if name not in ("bhr_last_error", "bhr_destroy", "bhr_sink_destroy", "bhr_png_bound", "bhr_png_device_bound", "bhr_y4m_close"):
+        if name not in ("bhr_last_error", "bhr_destroy", "bhr_sink_destroy", "bhr_png_bound", "bhr_png_device_bound", "bhr_jpeg_device_bound", "bhr_y4m_close"):
             fn.restype = I32
     lib.bhr_png_bound.restype = I64
     lib.bhr_png_device_bound.restype = I64
+    lib.bhr_jpeg_device_bound.restype = I64
     lib.bhr_sink_destroy.restype = None
     lib.bhr_y4m_close.restype = None
     _lib = lib

@@ -69,6 +69,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--png_encoder", type=str, default="device", choices=["device", "host"],
                    help="--video: PNG frames are filtered and Huffman-coded on the GPU (device, default) or by zlib on "
                         "host threads (host: ~10 %% smaller files, ~50 ms of a core per fhd frame)")
+    p.add_argument("--video_codec", type=str, default="auto", choices=["auto", "mjpeg"],
+                   help="--video: auto = PNG frames, and H.264 where an encoder exists (default); mjpeg = every frame is "
+                        "JPEG-coded on the GPU and the frames are muxed into the MP4 as Motion-JPEG (no external encoder needed)")
+    p.add_argument("--video_quality", type=int, default=90, help="--video_codec mjpeg: JPEG quality 1..100 (default: 90)")
     p.add_argument("--ignore_taichi_cache", action="store_true", help="accepted for compatibility; no effect")
     p.add_argument("--video", action="store_true", help="render frames and assemble a video")
     p.add_argument("--interactive", action="store_true", help="not available in this build (needs ti.GUI)")
@@ -99,6 +103,8 @@ def validate_args(args) -> None:
         raise ValueError(f"n_frames must be positive, got {args.n_frames}")
     if args.fps <= 0:
         raise ValueError(f"fps must be positive, got {args.fps}")
+    if not (1 <= getattr(args, "video_quality", 90) <= 100):
+        raise ValueError(f"video_quality must be between 1 and 100, got {args.video_quality}")
     if not math.isfinite(args.orbit_degrees):
         raise ValueError(f"orbit_degrees must be finite, got {args.orbit_degrees}")
     if args.disk_texture and (args.video or args.interactive):
@@ -152,7 +158,8 @@ def main(argv=None) -> int:
                              output_path=args.output, fov=fov, static_cam_pos=args.pov, orbit=args.orbit,
                              resume=args.resume, disk_rotation_speed=args.disk_rotation_speed,
                              orbit_degrees=args.orbit_degrees, rank=rank, world=world, video_stream=args.video_stream,
-                             png_level=(drivers.DEVICE if args.png_encoder == "device" else drivers.VIDEO_LEVEL))
+                             png_level=(drivers.DEVICE if args.png_encoder == "device" else drivers.VIDEO_LEVEL),
+                             video_codec=args.video_codec, video_quality=args.video_quality)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -160,7 +167,8 @@ def main(argv=None) -> int:
             if rank == 0:
                 done = D.merge_progress(drivers._frames_dir(args.output), world)
                 if len(done) == args.n_frames:
-                    drivers.assemble_video(drivers._frames_dir(args.output), args.n_frames, args.fps, args.output)
+                    drivers.assemble_video(drivers._frames_dir(args.output), args.n_frames, args.fps, args.output,
+                                           codec=args.video_codec)
                 else:
                     print(f"Warning: only {len(done)}/{args.n_frames} frames completed. Run again with --resume.")
             dist.barrier()

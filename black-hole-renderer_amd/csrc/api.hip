@@ -515,6 +515,7 @@ void bhr_destroy(bhr_ctx *ctx) {
     free_bg(ctx);
     for (int k = 0; k < BHR_MAX_FRAME_SLOTS; ++k) free_slot(ctx, k);
     bhr_png_dev_free(ctx);
+    bhr_jpeg_dev_free(ctx);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);
     for (auto &l : ctx->ada) {

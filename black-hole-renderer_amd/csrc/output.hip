@@ -212,12 +212,13 @@ struct bhr_sink {
     bhr_ctx *ctx = nullptr;
     int w = 0, h = 0, level = 1;
     size_t frame_bytes = 0;
-    bool on_device = false;        // level BHR_PNG_DEVICE: the slot receives finished PNG bytes (png_device.hip)
+    bool on_device = false;        // level BHR_PNG_DEVICE, or a JPEG sink: the slot receives finished file bytes
+    int jpeg_quality = 0;          // 1..100: a sink made by bhr_sink_create_jpeg (jpeg_device.hip); 0: PNG
     size_t host_bytes = 0;         // size of a slot's pinned buffer: the raw frame, or the bound of the device encoder
     struct Slot {
         uint8_t *host = nullptr;
         hipEvent_t ev = nullptr;
-        uint8_t *dev = nullptr;    // device encoder: PNG bytes in HBM
+        uint8_t *dev = nullptr;    // device encoder: file bytes in HBM
         uint32_t *d_meta = nullptr, *h_meta = nullptr;   // {length, error, ..}: device, and its pinned copy
     };
     std::vector<Slot> slots;
@@ -493,21 +494,21 @@ int32_t bhr_png_write(const char *path, const uint8_t *rgb, int32_t w, int32_t h
     return write_file_atomic(path, png.data(), (size_t)len);
 }
 
-int32_t bhr_sink_create(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t level, bhr_sink **out) {
-    if (!ctx || !out || slots < 1 || slots > 256 || workers < 1 || workers > 256 || level < BHR_PNG_DEVICE || level > 9)
-        return bhr_fail(BHR_ERR_INVALID, "bhr_sink_create: bad argument (slots %d, workers %d, level %d)", slots, workers, level);
-    if (level == BHR_PNG_DEVICE && ctx->cfg.width > bhr_png_device_max_width())
-        return bhr_fail(BHR_ERR_INVALID, "bhr_sink_create: the device PNG encoder takes frames up to %d pixels wide, this one has %d; "
-                        "use a zlib level (host encoder)", bhr_png_device_max_width(), ctx->cfg.width);
+}  // extern "C"
+
+// A sink of either codec: jpeg_quality 0 = PNG at `level`, 1..100 = JPEG on the device (level is BHR_PNG_DEVICE then).
+static int32_t sink_create(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t level, int32_t jpeg_quality, bhr_sink **out) {
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     bhr_sink *s = new bhr_sink();
     s->ctx = ctx;
     s->w = ctx->cfg.width;
     s->h = ctx->rows;
     s->level = level;
+    s->jpeg_quality = jpeg_quality;
     s->on_device = level == BHR_PNG_DEVICE;
     s->frame_bytes = (size_t)s->w * s->h * 3;
-    s->host_bytes = s->on_device ? (size_t)bhr_png_device_bound(s->w, s->h) : s->frame_bytes;
+    s->host_bytes = jpeg_quality ? (size_t)bhr_jpeg_device_bound(s->w, s->h)
+                                 : (s->on_device ? (size_t)bhr_png_device_bound(s->w, s->h) : s->frame_bytes);
     s->slots.resize(slots);
     for (int k = 0; k < slots; ++k) {
         hipError_t e = hipHostMalloc((void **)&s->slots[k].host, s->host_bytes, hipHostMallocDefault);
@@ -528,6 +529,26 @@ int32_t bhr_sink_create(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t le
     return BHR_OK;
 }
 
+extern "C" {
+
+int32_t bhr_sink_create(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t level, bhr_sink **out) {
+    if (!ctx || !out || slots < 1 || slots > 256 || workers < 1 || workers > 256 || level < BHR_PNG_DEVICE || level > 9)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_sink_create: bad argument (slots %d, workers %d, level %d)", slots, workers, level);
+    if (level == BHR_PNG_DEVICE && ctx->cfg.width > bhr_png_device_max_width())
+        return bhr_fail(BHR_ERR_INVALID, "bhr_sink_create: the device PNG encoder takes frames up to %d pixels wide, this one has %d; "
+                        "use a zlib level (host encoder)", bhr_png_device_max_width(), ctx->cfg.width);
+    return sink_create(ctx, slots, workers, level, 0, out);
+}
+
+int32_t bhr_sink_create_jpeg(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t quality, bhr_sink **out) {
+    if (!ctx || !out || slots < 1 || slots > 256 || workers < 1 || workers > 256 || quality < 1 || quality > 100)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_sink_create_jpeg: bad argument (slots %d, workers %d, quality %d)", slots, workers, quality);
+    if (ctx->cfg.width > 65535 || ctx->rows > 65535)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_sink_create_jpeg: a JPEG frame is at most 65535 pixels wide and high, this one is %dx%d",
+                        ctx->cfg.width, ctx->rows);
+    return sink_create(ctx, slots, workers, BHR_PNG_DEVICE, quality, out);
+}
+
 int32_t bhr_sink_submit(bhr_sink *s, const char *path) {
     if (!s || !path) return bhr_fail(BHR_ERR_INVALID, "bhr_sink_submit: bad argument");
     int slot;
@@ -544,7 +565,8 @@ int32_t bhr_sink_submit(bhr_sink *s, const char *path) {
     if (rc == BHR_OK) rc = bhr_launch_quantize(ctx);
     if (rc == BHR_OK && s->on_device) {
         bhr_sink::Slot &sl = s->slots[slot];
-        rc = bhr_launch_png_encode(ctx, ctx->d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta);
+        rc = s->jpeg_quality ? bhr_launch_jpeg_encode(ctx, s->jpeg_quality, ctx->d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta)
+                             : bhr_launch_png_encode(ctx, ctx->d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta);
         if (rc == BHR_OK) {
             e = hipMemcpyAsync(sl.h_meta, sl.d_meta, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipEventRecord(sl.ev, ctx->stream);

@@ -167,16 +167,31 @@ def _frames_dir(output_path: str) -> str:
     return os.path.join(os.path.dirname(output_path), name)
 
 
-def assemble_video(temp_dir: str, n_frames: int, fps: int, output_path: str) -> bool:
-    """PNG frames -> MP4 (render.py:4497-4503: libx264 through imageio's pyav plugin).  In order of preference: imageio +
+VIDEO_CODECS = ("auto", "mjpeg")
+
+
+def assemble_video(temp_dir: str, n_frames: int, fps: int, output_path: str, codec: str = "auto") -> bool:
+    """Frames -> MP4.  ``codec="mjpeg"``: the frame_%04d.jpg files of render_video(video_codec="mjpeg") become the samples
+    of a Motion-JPEG track as they are (mp4.write_jpeg_mp4, object type 0x6C); nothing is re-coded and no external
+    encoder is looked for.  ``codec="auto"``:
+    PNG frames -> MP4 (render.py:4497-4503: libx264 through imageio's pyav plugin).  In order of preference: imageio +
     pyav as the reference; an ``ffmpeg`` binary on PATH (same codec, same pixel format); failing both, the frames
     themselves muxed into an MP4 as PNG-coded samples (mp4.write_png_mp4: lossless, plays in ffmpeg / mpv / VLC, and is one
     ffmpeg call away from the H.264 file).  Returns False only when a frame is missing."""
-    frames = [os.path.join(temp_dir, f"frame_{frame:04d}.png") for frame in range(n_frames)]
+    if codec not in VIDEO_CODECS:
+        raise ValueError(f"codec must be one of {VIDEO_CODECS}, got {codec!r}")
+    ext = ".jpg" if codec == "mjpeg" else ".png"
+    frames = [os.path.join(temp_dir, f"frame_{frame:04d}{ext}") for frame in range(n_frames)]
     missing = [p for p in frames if not os.path.isfile(p)]
     if missing:
         print(f"{len(missing)} of {n_frames} frames are missing (first: {missing[0]}): no video assembled")
         return False
+    if codec == "mjpeg":
+        from .mp4 import jpeg_size, write_jpeg_mp4
+        w, h = jpeg_size(frames[0])
+        nbytes = write_jpeg_mp4(frames, fps, output_path, w, h)
+        print(f"Video saved: {output_path} ({n_frames} JPEG-coded frames, {nbytes / 1e6:.0f} MB, Motion-JPEG in MP4)")
+        return True
     try:
         import imageio.v3 as iio
         import av  # noqa: F401
@@ -236,7 +251,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  disk_rotation_speed: float = 0.1, orbit_degrees: float = 360.0, rank: int = 0, world: int = 1,
                  assemble: bool = True, png_level: int = DEVICE, sink_slots: int = 0, sink_workers: int = 0,
                  video_stream: str = "auto", stats: Optional[dict] = None, supersample: Optional[int] = None,
-                 supersample_threshold: Optional[float] = None, **_deprecated_kwargs) -> None:
+                 supersample_threshold: Optional[float] = None, video_codec: str = "auto", video_quality: int = 90,
+                 **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -251,7 +267,20 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     (smaller files, ~50 ms of a host core per fhd frame at level 1).
 
     ``supersample``: k x k rays per pixel for the frames of the video (None: as the renderer is set);
-    ``supersample_threshold``: with it, adaptive (only the pixels whose k = 1 neighbours differ by more than it)."""
+    ``supersample_threshold``: with it, adaptive (only the pixels whose k = 1 neighbours differ by more than it).
+
+    ``video_codec``: "auto" is everything above.  "mjpeg" makes the video without any external encoder: every frame is
+    coded as baseline JPEG of ``video_quality`` (1..100) on the device (csrc/jpeg_device.hip), the frame files are
+    ``frame_%04d.jpg`` in the same frames directory, and assemble_video muxes them into the MP4 as Motion-JPEG.  No PNG
+    is written, the yuv420p stream and the search for ffmpeg / pyav are skipped, resume looks for the .jpg files, and the
+    progress record's params carry the codec and the quality (a resume across codecs or qualities starts over).  In this
+    mode the renderer's outputs selection is restored on return ("auto" leaves it at "u8", as it always has)."""
+    if video_codec not in VIDEO_CODECS:
+        raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
+    mjpeg = video_codec == "mjpeg"
+    if mjpeg and not (isinstance(video_quality, int) and 1 <= video_quality <= 100):
+        raise ValueError(f"video_quality must be an integer between 1 and 100, got {video_quality!r}")
+    ext = ".jpg" if mjpeg else ".png"
     if supersample is not None:
         renderer.set_supersample(supersample, supersample_threshold)
     elif supersample_threshold is not None:
@@ -262,6 +291,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
     params = {"n_frames": n_frames, "fov": fov, "orbit": orbit, "disk_rotation_speed": disk_rotation_speed,
               "orbit_degrees": orbit_degrees}
+    if mjpeg:
+        params.update(video_codec=video_codec, video_quality=video_quality)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -281,7 +312,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             print("Warning: parameters changed, starting over")
             for fr in range(rank, n_frames, world):                  # this rank's own frames
                 try:
-                    os.remove(os.path.join(temp_dir, f"frame_{fr:04d}.png"))
+                    os.remove(os.path.join(temp_dir, f"frame_{fr:04d}{ext}"))
                 except OSError:
                     pass
             # every stale record goes -- also the ones a run with another world size left under the other naming
@@ -300,23 +331,29 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             done = set()
             for r in records:                                        # a different world size last time: still counted
                 done |= set(r.get("completed", []))
-            completed = {f for f in done if os.path.isfile(os.path.join(temp_dir, f"frame_{f:04d}.png"))}
+            completed = {f for f in done if os.path.isfile(os.path.join(temp_dir, f"frame_{f:04d}{ext}"))}
             print(f"Resuming: {len(completed)}/{n_frames} frames already rendered")
 
     total_t0 = time.time()
     rendered = 0
     # the reference saves through a 2-thread PIL pool (render.py:4412-4413); here the frame is quantised
     # on the device, copied into a pinned ring and encoded by worker threads while the next frames render
-    if png_level == DEVICE and width > _lib_max_png_width():
+    if mjpeg:
+        png_level = DEVICE                               # the JPEG coder runs on the device only
+    if png_level == DEVICE and not mjpeg and width > _lib_max_png_width():
         print(f"  frames wider than {_lib_max_png_width()} pixels are PNG-encoded on the host (zlib level {VIDEO_LEVEL})")
         png_level = VIDEO_LEVEL
     if png_level == DEVICE and sink_workers <= 0:
         sink_workers = 4                                 # copy + write only
-    sink = FrameSink(renderer, slots=sink_slots, workers=sink_workers, level=png_level)
+    if mjpeg:
+        outputs_before = renderer.outputs
+        sink = FrameSink(renderer, slots=sink_slots, workers=sink_workers, codec="jpeg", quality=video_quality)
+    else:
+        sink = FrameSink(renderer, slots=sink_slots, workers=sink_workers, level=png_level)
     if video_stream not in ("auto", "y4m", "off"):
         raise ValueError(f"video_stream must be 'auto', 'y4m' or 'off', got {video_stream!r}")
     stream = encoder = None
-    streamable = world == 1 and not completed and width % 2 == 0 and height % 2 == 0
+    streamable = world == 1 and not completed and width % 2 == 0 and height % 2 == 0 and not mjpeg
     if streamable and video_stream == "y4m":
         stream = Y4MStream(renderer, os.path.splitext(output_path)[0] + ".y4m", fps)
     elif streamable and video_stream == "auto" and assemble and shutil.which("ffmpeg"):
@@ -345,7 +382,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         cam_pos = orbit_position(static_cam_pos, frame, n_frames, orbit_degrees) if orbit else static_cam_pos
         t0 = time.time()
         renderer.render_async(cam_pos, fov, frame=0)   # lens flare, when enabled, is applied on the device
-        sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}.png"))
+        sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))
         if stream is not None:
             try:
                 stream.submit()
@@ -365,6 +402,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
 
     frames_written, bytes_written = sink.drain()
     sink.close()
+    if mjpeg:
+        renderer.set_outputs(outputs_before)
     if stats is not None:
         stats.update(setup_s=t_loop0 - total_t0, loop_s=time.time() - t_loop0, frames=rendered)
     streamed = False
@@ -387,7 +426,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         json.dump({"params": params, "completed": sorted(completed)}, f)
     if rendered:
         print(f"Session rendered {rendered} frames in {time.time() - total_t0:.1f} s "
-              f"({rendered / (time.time() - total_t0):.1f} fps incl. PNG encode {'on the device' if png_level == DEVICE else f'(zlib level {png_level})'}, "
+              f"({rendered / (time.time() - total_t0):.1f} fps incl. {'JPEG' if mjpeg else 'PNG'} encode "
+              f"{'on the device' if png_level == DEVICE else f'(zlib level {png_level})'}, "
               f"{bytes_written / max(frames_written, 1) / 1e6:.2f} MB/frame, {sink.workers} encoder threads)")
     if world > 1 or not assemble:
         return       # rank 0 assembles after a barrier (cli.py)
@@ -395,4 +435,4 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         print(f"Warning: only {len(completed)}/{n_frames} frames completed. Run again to resume.")
         return
     if not streamed:
-        assemble_video(temp_dir, n_frames, fps, output_path)
+        assemble_video(temp_dir, n_frames, fps, output_path, codec=video_codec)

@@ -6,6 +6,10 @@ PNG frames themselves, one per sample, in an 'mp4v' track whose decoder configur
 MP4 registration authority's code point for PNG, which ffmpeg / mpv / VLC decode.  Lossless, large (the frames are not
 re-coded), and one ``ffmpeg -i in.mp4 -c:v libx264 -pix_fmt yuv420p out.mp4`` away from the reference's file.
 
+``write_jpeg_mp4`` does the same with baseline JPEG frames (the device encoder's, csrc/jpeg_device.hip): Motion-JPEG in MP4, object
+type 0x6C (ISO/IEC 10918-1), a fifth of the PNG file's size at quality 90.  No player, ffmpeg or MP4 demuxer exists where
+this was developed: what the tests verify is the box structure and that every sample decodes with libjpeg.
+
 Only what such a file needs: ftyp, moov (mvhd, one trak: tkhd, mdia: mdhd, hdlr, minf: vmhd, dinf/dref, stbl: stsd
 [mp4v + esds], stts, stsc, stsz, co64), mdat with a 64-bit size.  ``read_samples`` walks the same boxes back (tests).
 """
@@ -15,6 +19,8 @@ from typing import Iterable, List, Sequence, Tuple
 
 PNG_OBJECT_TYPE = 0x6D          # ISO/IEC 14496-1 objectTypeIndication registered for PNG
 PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+JPEG_OBJECT_TYPE = 0x6C         # ISO/IEC 14496-1 objectTypeIndication for ISO/IEC 10918-1 (JPEG)
+JPEG_MAGIC = b"\xff\xd8\xff"
 
 
 def _box(kind: bytes, payload: bytes) -> bytes:
@@ -34,7 +40,8 @@ def _descr(tag: int, payload: bytes) -> bytes:
 MATRIX = struct.pack(">9i", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000)
 
 
-def _moov(width: int, height: int, fps: int, sizes: Sequence[int], first_offset: int) -> bytes:
+def _moov(width: int, height: int, fps: int, sizes: Sequence[int], first_offset: int, object_type: int = PNG_OBJECT_TYPE,
+          name: bytes = b"PNG frames (bhr)") -> bytes:
     n = len(sizes)
     timescale, duration = int(fps), n                       # one tick per frame
     mvhd = _full(b"mvhd", 0, 0, struct.pack(">IIII", 0, 0, timescale, duration) + struct.pack(">IH", 0x10000, 0x0100) +
@@ -47,10 +54,9 @@ def _moov(width: int, height: int, fps: int, sizes: Sequence[int], first_offset:
     dinf = _box(b"dinf", _full(b"dref", 0, 0, struct.pack(">I", 1) + _full(b"url ", 0, 1, b"")))
     peak = max(sizes) if n else 0
     avg_bitrate = min(int(sum(sizes) * 8 * fps / max(n, 1)), 0xFFFFFFFF)
-    dec = _descr(0x04, bytes([PNG_OBJECT_TYPE, (0x04 << 2) | 1]) + struct.pack(">I", min(peak, 0xFFFFFF))[1:] +
+    dec = _descr(0x04, bytes([object_type, (0x04 << 2) | 1]) + struct.pack(">I", min(peak, 0xFFFFFF))[1:] +
                  struct.pack(">II", min(peak * 8 * fps, 0xFFFFFFFF), avg_bitrate))
     esds = _full(b"esds", 0, 0, _descr(0x03, struct.pack(">HB", 1, 0) + dec + _descr(0x06, b"\x02")))
-    name = b"PNG frames (bhr)"
     mp4v = _box(b"mp4v", b"\0" * 6 + struct.pack(">H", 1) + b"\0" * 16 + struct.pack(">HHIIIH", width, height, 0x480000, 0x480000, 0, 1) +
                 bytes([len(name)]) + name + b"\0" * (31 - len(name)) + struct.pack(">Hh", 24, -1) + esds)
     stsd = _full(b"stsd", 0, 0, struct.pack(">I", 1) + mp4v)
@@ -68,18 +74,18 @@ def _moov(width: int, height: int, fps: int, sizes: Sequence[int], first_offset:
     return _box(b"moov", mvhd + _box(b"trak", tkhd + mdia))
 
 
-def write_png_mp4(frame_paths: Sequence[str], fps: int, output_path: str, width: int, height: int) -> int:
-    """Muxes the PNG files (in order, one sample each) into ``output_path``; returns the bytes written.  The sample
-    table comes first (players start without reading the whole file), the frames are streamed through, never held."""
+def _write_mp4(who: str, kind: str, magic: bytes, object_type: int, name: bytes, frame_paths: Sequence[str], fps: int,
+               output_path: str, width: int, height: int) -> int:
+    """One sample per frame file in an 'mp4v' track of the given object type; every file must begin with ``magic``."""
     sizes = [os.path.getsize(p) for p in frame_paths]
     if not sizes:
-        raise ValueError("write_png_mp4: no frames")
+        raise ValueError(f"{who}: no frames")
     if any(s >= 1 << 32 for s in sizes):
-        raise ValueError("write_png_mp4: a frame of 4 GiB or more does not fit a sample size")
+        raise ValueError(f"{who}: a frame of 4 GiB or more does not fit a sample size")
     ftyp = _box(b"ftyp", b"isom" + struct.pack(">I", 0x200) + b"isomiso2mp41")
-    moov_len = len(_moov(width, height, fps, sizes, 0))
+    moov_len = len(_moov(width, height, fps, sizes, 0, object_type, name))
     first = len(ftyp) + moov_len + 16                        # mdat header with a 64-bit size
-    moov = _moov(width, height, fps, sizes, first)
+    moov = _moov(width, height, fps, sizes, first, object_type, name)
     assert len(moov) == moov_len
     total = sum(sizes)
     tmp = output_path + ".part"
@@ -89,19 +95,51 @@ def write_png_mp4(frame_paths: Sequence[str], fps: int, output_path: str, width:
         out.write(struct.pack(">I4sQ", 1, b"mdat", 16 + total))
         for p, s in zip(frame_paths, sizes):
             with open(p, "rb") as f:
-                head = f.read(8)
-                if head != PNG_MAGIC:
-                    raise ValueError(f"write_png_mp4: {p} is not a PNG file")
+                head = f.read(len(magic))
+                if head != magic:
+                    raise ValueError(f"{who}: {p} is not a {kind} file")
                 out.write(head)
-                left = s - 8
+                left = s - len(magic)
                 while left > 0:
                     chunk = f.read(min(left, 1 << 22))
                     if not chunk:
-                        raise IOError(f"write_png_mp4: {p} changed size while being read")
+                        raise IOError(f"{who}: {p} changed size while being read")
                     out.write(chunk)
                     left -= len(chunk)
     os.replace(tmp, output_path)
     return first + total
+
+
+def write_png_mp4(frame_paths: Sequence[str], fps: int, output_path: str, width: int, height: int) -> int:
+    """Muxes the PNG files (in order, one sample each) into ``output_path``; returns the bytes written.  The sample
+    table comes first (players start without reading the whole file), the frames are streamed through, never held."""
+    return _write_mp4("write_png_mp4", "PNG", PNG_MAGIC, PNG_OBJECT_TYPE, b"PNG frames (bhr)", frame_paths, fps, output_path,
+                      width, height)
+
+
+def write_jpeg_mp4(frame_paths: Sequence[str], fps: int, output_path: str, width: int, height: int) -> int:
+    """Muxes baseline JPEG files (in order, one sample each) into ``output_path`` as Motion-JPEG (object type 0x6C);
+    returns the bytes written.  Same layout as write_png_mp4."""
+    return _write_mp4("write_jpeg_mp4", "JPEG", JPEG_MAGIC, JPEG_OBJECT_TYPE, b"Motion JPEG (bhr)", frame_paths, fps, output_path,
+                      width, height)
+
+
+def jpeg_size(path: str) -> Tuple[int, int]:
+    """(width, height) from the SOF0 segment of a baseline JPEG file."""
+    with open(path, "rb") as f:
+        buf = f.read(1 << 16)                                # the frame header sits in front of the scan
+    if buf[:3] != JPEG_MAGIC:
+        raise ValueError(f"{path} is not a JPEG file")
+    at = 2
+    while at + 4 <= len(buf) and buf[at] == 0xFF:
+        marker, n = buf[at + 1], struct.unpack_from(">H", buf, at + 2)[0]
+        if marker == 0xC0:
+            h, w = struct.unpack_from(">HH", buf, at + 5)
+            return w, h
+        if marker == 0xDA:
+            break
+        at += 2 + n
+    raise ValueError(f"{path}: no baseline frame header (SOF0)")
 
 
 def png_size(path: str) -> Tuple[int, int]:
@@ -140,7 +178,7 @@ def _find(buf: bytes, start: int, end: int, path: Sequence[bytes]) -> Tuple[int,
 
 def read_samples(path: str) -> dict:
     """{'width', 'height', 'timescale', 'duration', 'object_type', 'samples': [(offset, size)], 'file_size'} of a file
-    written by write_png_mp4 (any single-track file with stsz + co64/stco and one sample per chunk)."""
+    written by write_png_mp4 or write_jpeg_mp4 (any single-track file with stsz + co64/stco and one sample per chunk)."""
     size = os.path.getsize(path)
     with open(path, "rb") as f:
         head = f.read(min(size, 64 << 20))                  # ftyp + moov sit in front of the frames

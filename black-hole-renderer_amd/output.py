@@ -16,6 +16,7 @@ from . import _lib
 DEFAULT_LEVEL = 6          # PIL's default zlib level for PNG
 VIDEO_LEVEL = 1            # frames that are re-encoded into an MP4 anyway
 DEVICE = -1                # BHR_PNG_DEVICE: filter + Huffman-code the frame on the GPU (csrc/png_device.hip)
+JPEG_QUALITY = 90          # default quality of the device JPEG encoder (csrc/jpeg_device.hip)
 
 
 def _u8(a: np.ndarray) -> np.ndarray:
@@ -74,19 +75,50 @@ def png_device_menu():
             return out
 
 
+def jpeg_encode_device(renderer, quality: int = JPEG_QUALITY) -> bytes:
+    """JFIF file bytes (baseline, 4:2:0, standard Huffman tables) of the renderer's FINAL layer, colour-converted,
+    transformed and entropy coded on the device (bhr_jpeg_encode_device; the format is fixed in include/bhr_output.h)."""
+    lib = _lib.load()
+    cap = lib.bhr_jpeg_device_bound(renderer.width, renderer.rows)
+    out = np.empty(cap, dtype=np.uint8)
+    n = C.c_int64(0)
+    _lib.check(lib.bhr_jpeg_encode_device(renderer._ctx, int(quality), out.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(n)))
+    return out[:n.value].tobytes()
+
+
+def jpeg_tables(quality: int = JPEG_QUALITY):
+    """The encoder's tables (host only): (luma, chroma) quantisation tables of ``quality``, 64 entries each in zig-zag
+    order, and the four Huffman tables in DHT order (DC luma, AC luma, DC chroma, AC chroma) as (BITS[16], HUFFVAL)."""
+    lib = _lib.load()
+    q, counts, vals = np.zeros((2, 64), np.uint8), np.zeros((4, 16), np.uint8), np.zeros((4, 162), np.uint8)
+    p8 = C.POINTER(C.c_uint8)
+    _lib.check(lib.bhr_jpeg_tables(int(quality), q.ctypes.data_as(p8), counts.ctypes.data_as(p8), vals.ctypes.data_as(p8)))
+    huff = [(counts[k].tolist(), vals[k, :int(counts[k].sum())].tolist()) for k in range(4)]
+    return (q[0].tolist(), q[1].tolist()), huff
+
+
+def jpeg_restart_interval(width: int) -> int:
+    """MCUs per restart interval of a frame that wide (part of the file format; bhr_jpeg_restart_interval)."""
+    return int(_lib.load().bhr_jpeg_restart_interval(int(width)))
+
+
 def quantize(image: np.ndarray) -> np.ndarray:
     """save_image's 8-bit conversion: truncation, not rounding (render.py:423)."""
     return (np.clip(image, 0, 1) * 255).astype(np.uint8)
 
 
 class FrameSink:
-    """Device frame -> PNG file without stalling the render stream.
+    """Device frame -> PNG (or, with ``codec="jpeg"``, JPEG) file without stalling the render stream.
 
     ``submit(path)`` quantises the renderer's FINAL layer on the device, starts the copy into a pinned
     host slot and returns; worker threads encode and write.  ``drain()`` waits for the files.
-    ``level=DEVICE`` encodes on the GPU as well: the workers only fetch the finished bytes and write them."""
+    ``level=DEVICE`` encodes on the GPU as well: the workers only fetch the finished bytes and write them.
+    ``codec="jpeg"``: baseline JPEG of ``quality`` 1..100, always coded on the GPU (``level`` is not used)."""
 
-    def __init__(self, renderer, slots: int = 0, workers: int = 0, level: int = VIDEO_LEVEL):
+    def __init__(self, renderer, slots: int = 0, workers: int = 0, level: int = VIDEO_LEVEL, codec: str = "png",
+                 quality: int = JPEG_QUALITY):
+        if codec not in ("png", "jpeg"):
+            raise ValueError(f"codec must be 'png' or 'jpeg', got {codec!r}")
         if workers <= 0:
             workers = max(1, min(16, len(os.sched_getaffinity(0)) - 1))
         if slots <= 0:
@@ -94,8 +126,11 @@ class FrameSink:
         self._lib = _lib.load()
         self._sink = C.c_void_p()
         self._renderer = renderer          # keeps the context alive
-        _lib.check(self._lib.bhr_sink_create(renderer._ctx, slots, workers, level, C.byref(self._sink)))
-        self.workers, self.slots, self.level = workers, slots, level
+        if codec == "jpeg":
+            _lib.check(self._lib.bhr_sink_create_jpeg(renderer._ctx, slots, workers, int(quality), C.byref(self._sink)))
+        else:
+            _lib.check(self._lib.bhr_sink_create(renderer._ctx, slots, workers, level, C.byref(self._sink)))
+        self.workers, self.slots, self.level, self.codec, self.quality = workers, slots, level, codec, quality
         import weakref
         if not hasattr(renderer, "_sinks"):
             renderer._sinks = []

@@ -120,6 +120,7 @@ class HipRenderer:
         # outputs: what a frame keeps in memory besides the bg / disk layers -- "f32" (default: what render() returns),
         # "u8" (the quantised rows only: video loop, PNG sink, u8 gather), or several joined by "+" ("f32+blur+u8");
         # anything not kept is produced on demand by the call that reads it.  options: {name: value} for bhr_set_option.
+        self._outputs = "f32"
         if outputs is not None:
             self.set_outputs(outputs)
         for name, value in (options or {}).items():
@@ -428,6 +429,12 @@ class HipRenderer:
                 raise ValueError(f"outputs: 'f32', 'blur', 'u8' joined by '+', got {outputs!r}")
             mask |= bits[part]
         _lib.check(self._lib.bhr_set_outputs(self._ctx, mask))
+        self._outputs = outputs
+
+    @property
+    def outputs(self) -> str:
+        """The layers last chosen with set_outputs ("f32" on a new renderer)."""
+        return self._outputs
 
     @property
     def supersample(self) -> int:

@@ -57,6 +57,43 @@ BHR_API int32_t bhr_sink_submit(bhr_sink *sink, const char *path);
 BHR_API int32_t bhr_sink_drain(bhr_sink *sink, int64_t *frames_written, int64_t *bytes_written);
 BHR_API void bhr_sink_destroy(bhr_sink *sink);
 
+/* Baseline JPEG encoding on the device (csrc/jpeg_device.hip): the Motion-JPEG path of the video driver.  One JFIF file
+ * per frame, fixed so that tests/jpeg_ref.py restates it byte for byte:
+ *   SOI, APP0 (JFIF 1.01, density 1:1), one DQT with two 8-bit tables, SOF0 (8 bit, Y 2x2, Cb 1x1, Cr 1x1 = 4:2:0, tables
+ *   0 / 1 / 1), one DHT with the four standard Huffman tables of ITU T.81 Annex K (never built per frame), DRI, SOS,
+ *   entropy-coded data, EOI.  No 4:4:4, no progressive, optimised or arithmetic coding, no grey scale.
+ *   Quantisation tables: Annex K.1 scaled as libjpeg does, s = 5000 / q for q < 50, else 200 - 2 q,
+ *     entry = clamp((base s + 50) / 100, 1, 255).
+ *   Colour: from the u8 frame of bhr_read_final_u8, padded to multiples of 16 by repeating its last column and row.
+ *     Full-range BT.601 in integers: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16; chroma from the 2x2 block's rounded mean
+ *     RGB ((sum + 2) >> 2, as bhr_y4m_submit): Cb = clamp((-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16, 0, 255),
+ *     Cr = clamp((32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16, 0, 255).
+ *   DCT, int32 only: MI[u][x] = round(8192 c(u) / 2 cos((2x + 1) u pi / 16)); rows t = (MI . p + 1024) >> 11 on the
+ *     level-shifted samples, columns f8 = (MI . t + 2048) >> 12 (eight times the coefficient),
+ *     q = sign(f8) ((|f8| + 4 Q) / (8 Q)).  |t| < 2^15 and every sum stays below 2^31 for every 8-bit block.
+ *   Entropy coding: MCU = Y00 Y01 Y10 Y11 Cb Cr in raster order; DC differences against the previous block of the same
+ *     component, 0 at every restart; ZRL for runs above 15, EOB unless coefficient 63 is non-zero; 0x00 behind every 0xFF
+ *     data byte; the last byte of an interval padded with 1-bits; RSTm, m counting modulo 8, between intervals.
+ *   Restart interval R = bhr_jpeg_restart_interval(w) MCUs: the encoder's unit of parallelism (one wave codes one
+ *     interval, one lane per 8x8 block) and part of the file format.  It is a function of the frame's width only; today
+ *     it is 10 for every width (60 of a wave's 64 lanes busy; 816 intervals at 1920x1080, 12 960 at 7680x4320), and
+ *     intervals run on across MCU rows.  Decoded pixels do not depend on it; it costs about 3 bytes per interval.
+ * bhr_jpeg_device_bound: capacity that always suffices: a block codes in at most 20 + 63 x 26 = 1658 bits, an MCU in
+ *   1244 bytes, doubled by stuffing, + a padding byte and two marker bytes per interval, + 640 bytes for the headers.
+ * bhr_jpeg_tables (host only, no GPU needed; for inspection and tests): the two quantisation tables of `quality` in
+ *   zig-zag order and the four Huffman tables in DHT order (DC luma, AC luma, DC chroma, AC chroma): BITS, and HUFFVAL
+ *   padded with zeros to 162 entries.
+ * bhr_jpeg_encode_device: quantise the context's FINAL layer and encode it, as bhr_png_encode_device does for PNG.  A
+ *   row-block context encodes its own rows as a `rows`-high image.  There is no width limit below the format's 65535.
+ * bhr_sink_create_jpeg: an ordinary bhr_sink (submit, drain, destroy below) whose submits encode JPEG on the device.
+ * quality outside 1..100: BHR_ERR_INVALID. */
+BHR_API int64_t bhr_jpeg_device_bound(int32_t w, int32_t h);
+BHR_API int32_t bhr_jpeg_restart_interval(int32_t w);
+BHR_API int32_t bhr_jpeg_tables(int32_t quality, uint8_t *qtab /* [2][64] */, uint8_t *huff_counts /* [4][16] */,
+                                uint8_t *huff_values /* [4][162] */);
+BHR_API int32_t bhr_jpeg_encode_device(bhr_ctx *ctx, int32_t quality, uint8_t *out, int64_t cap, int64_t *out_len);
+BHR_API int32_t bhr_sink_create_jpeg(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t quality, bhr_sink **out);
+
 /* Video stream without the PNG detour (replaces render.py:4497-4503, where the reference re-reads every PNG and
  * feeds libx264 through imageio/pyav with pixelformat yuv420p).  bhr_y4m_submit converts the context's FINAL layer
  * on the device -- the reference's u8 quantisation (render.py:4463), then BT.601 limited-range Y'CbCr with the
