@@ -32,28 +32,6 @@ int32_t dev_alloc(T **p, size_t count) {
 
 int32_t use_device(bhr_ctx *ctx) { return bhr_enter(ctx); }
 
-// points the launchers' view of the frame buffers (ctx->d_bg ...) at slot k
-void activate_slot(bhr_ctx *ctx, int k) {
-    const bhr_frame_slot &f = ctx->slots[k];
-    ctx->d_bg = f.d_bg;
-    ctx->d_disk = f.d_disk;
-    ctx->d_hblur = f.d_hblur;
-    ctx->d_pa = f.d_pa;
-    ctx->d_pb = f.d_pb;
-    ctx->d_sum = f.d_sum;
-    ctx->d_blur = f.d_blur;
-    ctx->d_final = f.d_final;
-    ctx->d_final_u8 = f.d_final_u8;
-    ctx->d_queue = f.d_queue;
-    ctx->d_glow_hw = f.d_glow_hw;          // allocated on first use by flare.hip, which stores them back into the slot
-    ctx->d_glow_wh = f.d_glow_wh;
-    ctx->d_flare_c0 = f.d_flare_c0;
-    ctx->d_flare_c12 = f.d_flare_c12;
-    ctx->d_flare_sums = f.d_flare_sums;
-    ctx->flare_glow_rows = f.flare_glow_rows;
-    ctx->active_slot = k;
-}
-
 // ---- do two streams sit on ONE hardware queue? ------------------------------------------------------------------------------
 // HIP hands its streams to a small pool of hardware queues (four per priority by default) by rules of its own; two streams
 // on one queue run their kernels strictly one after the other, two on different queues side by side -- which decides how the
@@ -125,14 +103,13 @@ static void read_options(bhr_options *o) {
 int32_t alloc_slot(bhr_ctx *ctx, int k) {
     bhr_frame_slot &f = ctx->slots[k];
     if (f.allocated) return BHR_OK;
-    const size_t W = ctx->cfg.width, rows = ctx->rows, R = ctx->bloom_R, px3 = rows * W * 3;
+    const size_t px3 = (size_t)ctx->rows * ctx->cfg.width * 3;
     if (!f.stream) {
         if (k == 0 && ctx->n_slots == 1) f.stream = ctx->scene_stream;
         else BHR_HIP(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
     }
     if (!f.done) BHR_HIP(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
     int32_t rc = BHR_OK;
-    (void)R;
     if ((rc = dev_alloc(&f.d_bg, px3)) || (rc = dev_alloc(&f.d_disk, px3)) || (rc = dev_alloc(&f.d_blur, px3)) ||
         (rc = dev_alloc(&f.d_final, px3)) || (rc = dev_alloc(&f.d_final_u8, px3)) || (rc = dev_alloc(&f.d_queue, 1))) {
         void *bufs[] = {f.d_bg, f.d_disk, f.d_blur, f.d_final, f.d_final_u8, f.d_queue};   // a later retry starts clean
@@ -176,11 +153,14 @@ int32_t ensure_bloom_buffers(bhr_ctx *ctx, int k, bool split) {
 void free_slot(bhr_ctx *ctx, int k) {
     bhr_frame_slot &f = ctx->slots[k];
     void *bufs[] = {f.d_bg, f.d_disk, f.d_blur, f.d_final, f.d_final_u8, f.d_hblur_base, f.d_pa, f.d_pb, f.d_sum, f.d_queue,
-                    f.d_glow_hw, f.d_glow_wh, f.d_flare_c0, f.d_flare_c12, f.d_flare_sums};
+                    f.d_glow_hw, f.d_glow_wh, f.d_flare_c0, f.d_flare_c12, f.d_flare_sums, f.d_ada_list, f.d_ada_mask, f.d_ada_counts};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (f.done) (void)hipEventDestroy(f.done);
     if (f.stream && f.stream != ctx->scene_stream) (void)hipStreamDestroy(f.stream);
+    if (f.aux_stream) (void)hipStreamDestroy(f.aux_stream);      // idle: bhr_destroy has waited for every slot's
+    if (f.aux_fork) (void)hipEventDestroy(f.aux_fork);
+    if (f.aux_done) (void)hipEventDestroy(f.aux_done);
     memset(&f, 0, sizeof(f));
 }
 
@@ -245,26 +225,22 @@ int32_t fold_cells(bhr_ctx *ctx, const unsigned long long *cells, int n, unsigne
 int32_t bhr_launch_quantize(bhr_ctx *ctx) { return bhr_ensure_outputs(ctx, BHR_OUT_U8); }
 
 int32_t bhr_ensure_outputs(bhr_ctx *ctx, uint32_t need) {
-    bhr_frame_slot &f = ctx->slots[ctx->active_slot];
+    bhr_frame_slot &f = bhr_slot(ctx);
     uint32_t missing = need & ~f.have;
     if (!missing) return BHR_OK;
     if ((missing & BHR_OUT_U8) && ((f.have | missing) & BHR_OUT_F32)) {
         // the f32 frame is (or is about to be) the authority -- it may carry a lens flare the V pass knows nothing of
         if (missing & BHR_OUT_F32) BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_F32));
         const long long n = (long long)ctx->rows * ctx->cfg.width * 3;
-        hipLaunchKernelGGL(quantize_u8_kernel, dim3(2048), dim3(256), 0, ctx->stream, ctx->d_final, ctx->d_final_u8, n);
+        hipLaunchKernelGGL(quantize_u8_kernel, dim3(2048), dim3(256), 0, ctx->stream, f.d_final, f.d_final_u8, n);
         BHR_HIP(hipGetLastError());
         f.have |= BHR_OUT_U8;
         missing &= ~(BHR_OUT_U8 | BHR_OUT_F32);
         if (!missing) return BHR_OK;
     }
     // re-run the frame's V pass for what nobody asked for up front (its inputs -- bg, disk, the H-blur planes -- are still the
-    // slot's): same kernels, same bits
-    const int32_t split = ctx->bloom_split;
-    ctx->bloom_split = f.frame_split;
-    const int32_t rc = bhr_launch_bloom_v_rows(ctx, f.frame_with_bloom, 0, ctx->rows, missing, nullptr, nullptr);
-    ctx->bloom_split = split;
-    BHR_TRY(rc);
+    // slot's, and it records which post-pass the frame ran): same kernels, same bits
+    BHR_TRY(bhr_launch_bloom_v_rows(ctx, f.frame_with_bloom, 0, ctx->rows, missing, nullptr, nullptr));
     f.have |= missing;
     return BHR_OK;
 }
@@ -273,26 +249,18 @@ int32_t bhr_ensure_outputs(bhr_ctx *ctx, uint32_t need) {
 int32_t bhr_activate_slot(bhr_ctx *ctx, int32_t k) {
     if (k < 0 || k >= BHR_MAX_FRAME_SLOTS) return bhr_fail(BHR_ERR_INVALID, "frame slot %d", k);
     BHR_TRY(alloc_slot(ctx, k));
-    activate_slot(ctx, k);
+    ctx->active_slot = k;
     return BHR_OK;
 }
 
-int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags) {
+int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags, bool exact) {
     const int mode = bhr_resolve_math(ctx, flags);
     // the frame's post-pass follows its march: exact f32 chains under strict, the split-f16 matrix-core kernels (bloom.hip)
     // under fast and hybrid; BHR_BLOOM_SPLIT=0 / 1 forces either for every arithmetic
     int split = ctx->opt.bloom_split >= 0 ? ctx->opt.bloom_split : (mode != BHR_MATH_STRICT ? 1 : 0);
-    if (!ctx->split_ok || (flags & BHR_SKIP_BLOOM)) split = 0;
-    ctx->bloom_split = split;
-    if (!(flags & BHR_SKIP_BLOOM)) {
-        BHR_TRY(ensure_bloom_buffers(ctx, ctx->active_slot, split != 0));
-        bhr_frame_slot &f = ctx->slots[ctx->active_slot];
-        ctx->d_hblur = f.d_hblur;
-        ctx->d_pa = f.d_pa;
-        ctx->d_pb = f.d_pb;
-        ctx->d_sum = f.d_sum;
-    }
-    bhr_frame_slot &f = ctx->slots[ctx->active_slot];
+    if (exact || !ctx->split_ok || (flags & BHR_SKIP_BLOOM)) split = 0;
+    if (!(flags & BHR_SKIP_BLOOM)) BHR_TRY(ensure_bloom_buffers(ctx, ctx->active_slot, split != 0));
+    bhr_frame_slot &f = bhr_slot(ctx);
     f.have = 0;
     f.sum_valid = 0;
     f.frame_split = split;
@@ -302,7 +270,7 @@ int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags) {
 
 int32_t bhr_frame_post(bhr_ctx *ctx, int32_t with_bloom, uint32_t want) {
     BHR_TRY(bhr_launch_bloom_v_rows(ctx, with_bloom, 0, ctx->rows, want, nullptr, nullptr));
-    ctx->slots[ctx->active_slot].have = want;
+    bhr_slot(ctx).have = want;
     return BHR_OK;
 }
 
@@ -360,25 +328,24 @@ int32_t bhr_fail(int32_t code, const char *fmt, ...) {
 }
 
 int32_t bhr_aux_fork(bhr_ctx *ctx) {
-    const int k = ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0;
-    if (!ctx->aux_streams[0]) {
-        // normal priority, one stream per frame slot
-        for (int q = 0; q < BHR_MAX_FRAME_SLOTS; ++q) {
-            BHR_HIP(hipStreamCreateWithPriority(&ctx->aux_streams[q], hipStreamNonBlocking, 0));
-            BHR_HIP(hipEventCreateWithFlags(&ctx->aux_fork[q], hipEventDisableTiming));
-            BHR_HIP(hipEventCreateWithFlags(&ctx->aux_done[q], hipEventDisableTiming));
+    if (!ctx->slots[0].aux_stream) {
+        // normal priority, one stream per frame slot, all created now
+        for (auto &q : ctx->slots) {
+            BHR_HIP(hipStreamCreateWithPriority(&q.aux_stream, hipStreamNonBlocking, 0));
+            BHR_HIP(hipEventCreateWithFlags(&q.aux_fork, hipEventDisableTiming));
+            BHR_HIP(hipEventCreateWithFlags(&q.aux_done, hipEventDisableTiming));
         }
     }
-    ctx->aux_stream = ctx->aux_streams[k];
-    BHR_HIP(hipEventRecord(ctx->aux_fork[k], ctx->stream));
-    BHR_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork[k], 0));
+    bhr_frame_slot &f = bhr_slot(ctx);
+    BHR_HIP(hipEventRecord(f.aux_fork, ctx->stream));
+    BHR_HIP(hipStreamWaitEvent(f.aux_stream, f.aux_fork, 0));
     return BHR_OK;
 }
 
 int32_t bhr_aux_join(bhr_ctx *ctx) {
-    const int k = ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0;
-    BHR_HIP(hipEventRecord(ctx->aux_done[k], ctx->aux_stream));
-    BHR_HIP(hipStreamWaitEvent(ctx->stream, ctx->aux_done[k], 0));
+    bhr_frame_slot &f = bhr_slot(ctx);
+    BHR_HIP(hipEventRecord(f.aux_done, f.aux_stream));
+    BHR_HIP(hipStreamWaitEvent(ctx->stream, f.aux_done, 0));
     return BHR_OK;
 }
 
@@ -410,7 +377,7 @@ int32_t bhr_enter_scene_write(bhr_ctx *ctx) {
 }
 
 int32_t bhr_enter_frame(bhr_ctx *ctx) {
-    bhr_frame_slot &f = ctx->slots[ctx->active_slot];
+    bhr_frame_slot &f = bhr_slot(ctx);
     if (!f.allocated || !f.stream || f.stream == ctx->scene_stream) return bhr_enter(ctx);
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     BHR_HIP(hipEventRecord(ctx->scene_ev, ctx->scene_stream));      // e.g. a bhr_write_layer(FINAL) since the render
@@ -420,7 +387,7 @@ int32_t bhr_enter_frame(bhr_ctx *ctx) {
 }
 
 int32_t bhr_leave_frame(bhr_ctx *ctx) {
-    bhr_frame_slot &f = ctx->slots[ctx->active_slot];
+    bhr_frame_slot &f = bhr_slot(ctx);
     if (ctx->stream != ctx->scene_stream && ctx->stream == f.stream) {
         BHR_HIP(hipEventRecord(f.done, f.stream));                  // joins now wait for this work too
         f.in_flight = 1;
@@ -476,12 +443,9 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
     for (auto &e : ctx->ring_ev)
         if (hipEventCreate(&e) != hipSuccess) return bail(bhr_fail(BHR_ERR_HIP, "hipEventCreate failed"));
 
-    const size_t W = cfg->width, H = cfg->height, rows = ctx->rows, R = ctx->bloom_R;
-    const size_t px3 = rows * W * 3;
+    const size_t W = cfg->width, H = cfg->height, R = ctx->bloom_R;
     int32_t rc;
-    (void)px3;
-    if ((rc = alloc_slot(ctx, 0))) return bail(rc);
-    activate_slot(ctx, 0);
+    if ((rc = bhr_activate_slot(ctx, 0))) return bail(rc);
     if ((rc = dev_alloc(&ctx->d_wtab, 3 * (R + 1 + 64)))) return bail(rc);
     if ((rc = dev_alloc(&ctx->d_wext, 3 * (2 * (R + 4) + 8)))) return bail(rc);
     if ((rc = dev_alloc(&ctx->d_wsum_h, 6 * W))) return bail(rc);
@@ -507,8 +471,10 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
 void bhr_destroy(bhr_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->cfg.device);
-    for (auto &f : ctx->slots)
+    for (auto &f : ctx->slots) {
         if (f.stream) (void)hipStreamSynchronize(f.stream);
+        if (f.aux_stream) (void)hipStreamSynchronize(f.aux_stream);
+    }
     if (ctx->scene_stream) (void)hipStreamSynchronize(ctx->scene_stream);
     ctx->stream = ctx->scene_stream;
     free_scene(ctx);
@@ -518,20 +484,9 @@ void bhr_destroy(bhr_ctx *ctx) {
     bhr_jpeg_dev_free(ctx);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);
-    for (auto &l : ctx->ada) {
-        if (l.d_list) (void)hipFree(l.d_list);
-        if (l.d_mask) (void)hipFree(l.d_mask);
-        if (l.d_counts) (void)hipFree(l.d_counts);
-    }
     bhr_pipe_free(ctx);
-    for (int q = 0; q < BHR_MAX_FRAME_SLOTS; ++q)
-        if (ctx->aux_streams[q]) { (void)hipStreamSynchronize(ctx->aux_streams[q]); (void)hipStreamDestroy(ctx->aux_streams[q]); }
     for (int q = 0; q < ctx->n_calib_idle; ++q) (void)hipStreamDestroy(ctx->calib_idle[q]);
     ctx->n_calib_idle = 0;
-    for (int q = 0; q < BHR_MAX_FRAME_SLOTS; ++q) {
-        if (ctx->aux_fork[q]) (void)hipEventDestroy(ctx->aux_fork[q]);
-        if (ctx->aux_done[q]) (void)hipEventDestroy(ctx->aux_done[q]);
-    }
     if (ctx->d_gather_u8) (void)hipFree(ctx->d_gather_u8);
     free(ctx->h_tile_order);
     if (ctx->scene_ev) (void)hipEventDestroy(ctx->scene_ev);
@@ -539,7 +494,7 @@ void bhr_destroy(bhr_ctx *ctx) {
     void *bufs[] = {ctx->d_skybox,
                     ctx->d_wtab, ctx->d_wsum_h, ctx->d_wsum_v, ctx->d_ray_steps, ctx->d_noise_in,
                     ctx->d_noise_out, ctx->d_steps_ring, ctx->d_steps_fold, ctx->d_pool, ctx->d_pairs, ctx->d_stats_scratch, ctx->d_wext, ctx->d_w16, ctx->d_dv2_params,
-                    ctx->d_flare_prog, ctx->d_tile_order, ctx->d_row_steps, ctx->d_gather};   // the flare's per-frame scratch belongs to the slots
+                    ctx->d_flare_prog, ctx->d_tile_order, ctx->d_row_steps, ctx->d_gather};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -913,7 +868,7 @@ int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     }
     const int ring = (int)(ctx->ring_head % BHR_TIMING_RING);
     ctx->cur_slot = ring;
-    activate_slot(ctx, k);
+    ctx->active_slot = k;
     ctx->stream = f.stream;
     const int32_t rc = render_on_slot(ctx, cam, flags, k, ring);
     ctx->stream = ctx->scene_stream;
@@ -931,11 +886,12 @@ int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_read_layer: bad argument");
     BHR_TRY(use_device(ctx));
     const float *src = nullptr;
+    const bhr_frame_slot &f = bhr_slot(ctx);
     switch (layer) {
-        case BHR_LAYER_FINAL: src = ctx->d_final; BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_F32)); break;
-        case BHR_LAYER_BG: src = ctx->d_bg; break;
-        case BHR_LAYER_DISK: src = ctx->d_disk; break;
-        case BHR_LAYER_BLUR: src = ctx->d_blur; BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_BLUR)); break;
+        case BHR_LAYER_FINAL: src = f.d_final; BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_F32)); break;
+        case BHR_LAYER_BG: src = f.d_bg; break;
+        case BHR_LAYER_DISK: src = f.d_disk; break;
+        case BHR_LAYER_BLUR: src = f.d_blur; BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_BLUR)); break;
         default: return bhr_fail(BHR_ERR_INVALID, "bhr_read_layer: unknown layer %d", layer);
     }
     return download(ctx, out, src, (size_t)ctx->rows * ctx->cfg.width * 3 * sizeof(float));
@@ -945,7 +901,7 @@ int32_t bhr_write_layer(bhr_ctx *ctx, int32_t layer, const float *in) {
     if (!ctx || !in) return bhr_fail(BHR_ERR_INVALID, "bhr_write_layer: bad argument");
     BHR_TRY(use_device(ctx));
     float *dst = nullptr;
-    bhr_frame_slot &f = ctx->slots[ctx->active_slot];
+    bhr_frame_slot &f = bhr_slot(ctx);
     const size_t n = (size_t)ctx->rows * ctx->cfg.width * 3;
     int32_t wide = 0;
     if (layer == BHR_LAYER_DISK) {
@@ -960,10 +916,10 @@ int32_t bhr_write_layer(bhr_ctx *ctx, int32_t layer, const float *in) {
         }
     }
     switch (layer) {
-        case BHR_LAYER_FINAL: dst = ctx->d_final; f.have = (f.have | BHR_OUT_F32) & ~BHR_OUT_U8; break;   // the u8 rows follow the written frame
-        case BHR_LAYER_BG: dst = ctx->d_bg; f.sum_valid = 0; break;      // a later V pass adds the two layers itself
-        case BHR_LAYER_DISK: dst = ctx->d_disk; f.sum_valid = 0; f.disk_wide = wide; break;
-        case BHR_LAYER_BLUR: dst = ctx->d_blur; f.have |= BHR_OUT_BLUR; break;
+        case BHR_LAYER_FINAL: dst = f.d_final; f.have = (f.have | BHR_OUT_F32) & ~BHR_OUT_U8; break;   // the u8 rows follow the written frame
+        case BHR_LAYER_BG: dst = f.d_bg; f.sum_valid = 0; break;      // a later V pass adds the two layers itself
+        case BHR_LAYER_DISK: dst = f.d_disk; f.sum_valid = 0; f.disk_wide = wide; break;
+        case BHR_LAYER_BLUR: dst = f.d_blur; f.have |= BHR_OUT_BLUR; break;
         default: return bhr_fail(BHR_ERR_INVALID, "bhr_write_layer: unknown layer %d", layer);
     }
     return upload(ctx, dst, in, n * sizeof(float));
@@ -976,12 +932,8 @@ int32_t bhr_bloom(bhr_ctx *ctx) {
     BHR_TRY(use_device(ctx));
     // the context's arithmetic decides the kernels, as for a rendered frame -- except for a written disk layer the split
     // kernels cannot carry: the pass stays one function of its input whatever the arithmetic
-    const int32_t forced = ctx->opt.bloom_split;
-    if (ctx->slots[ctx->active_slot].disk_wide) ctx->opt.bloom_split = 0;
-    const int32_t rc = bhr_frame_begin(ctx, 0);
-    ctx->opt.bloom_split = forced;
-    BHR_TRY(rc);
-    if (ctx->bloom_split) BHR_TRY(bhr_launch_bloom_pack(ctx)); // the disk layer may be the caller's (bhr_write_layer)
+    BHR_TRY(bhr_frame_begin(ctx, 0, bhr_slot(ctx).disk_wide != 0));
+    if (bhr_slot(ctx).frame_split) BHR_TRY(bhr_launch_bloom_pack(ctx)); // the disk layer may be the caller's (bhr_write_layer)
     BHR_TRY(bhr_launch_bloom_h(ctx));
     return bhr_frame_post(ctx, 1, BHR_OUT_F32 | BHR_OUT_BLUR);
 }
@@ -1000,7 +952,7 @@ int32_t bhr_debug_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes, in
     }
     if (which == 3) {                                   // geom[0..9]: do pairs of the context's streams share a hardware queue (-1: no such stream)
         if (!geom) return bhr_fail(BHR_ERR_INVALID, "bhr_debug_read: stream map needs geom");
-        hipStream_t st[5] = {ctx->scene_stream, ctx->slots[0].stream, ctx->n_slots > 1 ? ctx->slots[1].stream : nullptr, ctx->aux_streams[0], ctx->aux_streams[1]};
+        hipStream_t st[5] = {ctx->scene_stream, ctx->slots[0].stream, ctx->n_slots > 1 ? ctx->slots[1].stream : nullptr, ctx->slots[0].aux_stream, ctx->slots[1].aux_stream};
         int q = 0;                                      // pairs in the order (0,1) (0,2) (0,3) (0,4) (1,2) (1,3) (1,4) (2,3) (2,4) (3,4); 0 scene, 1 / 2 frame slots, 3 / 4 second march streams
         for (int i = 0; i < 5; ++i)
             for (int j = i + 1; j < 5; ++j, ++q) {
@@ -1018,7 +970,7 @@ int32_t bhr_debug_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes, in
         if (bytes > (int64_t)n * 4) return bhr_fail(BHR_ERR_INVALID, "bhr_debug_read: %lld bytes asked, the list holds %d tiles", (long long)bytes, n);
         return download(ctx, out, list, (size_t)bytes);
     }
-    const void *src = which == 0 ? ctx->d_pa : which == 1 ? ctx->d_pb : nullptr;
+    const void *src = which == 0 ? bhr_slot(ctx).d_pa : which == 1 ? bhr_slot(ctx).d_pb : nullptr;
     const size_t have = which == 0 ? g.pa_halfs * 2 : g.pb_halfs * 2;
     if (!out || bytes == 0) return BHR_OK;
     if (!src) return bhr_fail(BHR_ERR_STATE, "bhr_debug_read: buffer %d does not exist (no split-f16 frame yet)", which);
@@ -1060,10 +1012,10 @@ static int32_t set_sampling(bhr_ctx *ctx, const char *who, int32_t k, int32_t ad
     if (ss == ctx->ss && ada_k == ctx->ada_k && (ada_k == 0 || memcmp(&T, &ctx->ada_threshold, sizeof(T)) == 0)) return BHR_OK;
     // the tile order, the hybrid lists and the fix lists belong to the marched frame: the frames in flight still march over them
     BHR_TRY(bhr_enter(ctx));
-    for (auto &f : ctx->slots)
+    for (auto &f : ctx->slots) {
         if (f.stream) BHR_HIP(hipStreamSynchronize(f.stream));
-    for (hipStream_t s : ctx->aux_streams)
-        if (s) BHR_HIP(hipStreamSynchronize(s));
+        if (f.aux_stream) BHR_HIP(hipStreamSynchronize(f.aux_stream));
+    }
     BHR_HIP(hipStreamSynchronize(ctx->scene_stream));
     bhr_hybrid_free(ctx);
     if (ctx->d_tile_order) BHR_HIP(hipFree(ctx->d_tile_order));
@@ -1091,11 +1043,11 @@ int32_t bhr_set_adaptive_supersample(bhr_ctx *ctx, int32_t k, float threshold) {
 // {refined pixels of the last adaptive frame, those of them marched strict, pixels of the frame}.  Synchronises.
 int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_adaptive_info: bad argument");
-    if (ctx->ada_k <= 1 || ctx->ada_last_slot < 0 || !ctx->ada[ctx->ada_last_slot].d_counts)
+    if (ctx->ada_k <= 1 || ctx->ada_last_slot < 0 || !ctx->slots[ctx->ada_last_slot].d_ada_counts)
         return bhr_fail(BHR_ERR_STATE, "bhr_adaptive_info: no adaptively supersampled frame has been rendered (bhr_set_adaptive_supersample)");
     BHR_TRY(use_device(ctx));
     unsigned int n[4] = {0, 0, 0, 0};            // tiles in the two lists, refined pixels in them
-    BHR_TRY(download(ctx, n, ctx->ada[ctx->ada_last_slot].d_counts, sizeof(n)));
+    BHR_TRY(download(ctx, n, ctx->slots[ctx->ada_last_slot].d_ada_counts, sizeof(n)));
     out[0] = (int64_t)n[2] + (int64_t)n[3];
     out[1] = ctx->ada_last_math == BHR_MATH_FAST ? 0 : (int64_t)n[2];
     out[2] = (int64_t)ctx->cfg.width * ctx->rows;
@@ -1115,7 +1067,7 @@ int32_t bhr_lens_flare(bhr_ctx *ctx) {
         return bhr_fail(BHR_ERR_INVALID, "bhr_lens_flare: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
     BHR_TRY(use_device(ctx));
     BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_F32));
-    ctx->slots[ctx->active_slot].have &= ~BHR_OUT_U8;          // the u8 rows follow the flared frame
+    bhr_slot(ctx).have &= ~BHR_OUT_U8;          // the u8 rows follow the flared frame
     BHR_TRY(bhr_launch_flare_glow(ctx, true));
     BHR_TRY(bhr_launch_flare_sums(ctx));
     return bhr_launch_flare_apply(ctx, nullptr);
@@ -1128,7 +1080,7 @@ int32_t bhr_lens_flare_sums(bhr_ctx *ctx, double *out3) {
     BHR_TRY(use_device(ctx));
     BHR_TRY(bhr_launch_flare_glow(ctx, true));
     BHR_TRY(bhr_launch_flare_sums(ctx));
-    return download(ctx, out3, ctx->d_flare_sums, 3 * sizeof(double));
+    return download(ctx, out3, bhr_slot(ctx).d_flare_sums, 3 * sizeof(double));
 }
 
 int32_t bhr_read_gathered(bhr_ctx *ctx, float *out) {
@@ -1142,7 +1094,7 @@ int32_t bhr_read_final_u8(bhr_ctx *ctx, uint8_t *out) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_read_final_u8: bad argument");
     BHR_TRY(use_device(ctx));
     BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_U8));
-    return download(ctx, out, ctx->d_final_u8, (size_t)ctx->rows * ctx->cfg.width * 3);
+    return download(ctx, out, bhr_slot(ctx).d_final_u8, (size_t)ctx->rows * ctx->cfg.width * 3);
 }
 
 int32_t bhr_get_counters(bhr_ctx *ctx, bhr_counters *out) {
@@ -1206,10 +1158,10 @@ int32_t bhr_get_counters(bhr_ctx *ctx, bhr_counters *out) {
         if (hipEventQuery(ctx->ev[7]) == hipSuccess) ctx->counters.compose_ms = ev_ms(ctx->ev[6], ctx->ev[7]);
     }
     *out = ctx->counters;
-    if (ctx->ada_frame && ctx->ada_last_slot >= 0 && ctx->ada[ctx->ada_last_slot].d_counts) {
+    if (ctx->ada_frame && ctx->ada_last_slot >= 0 && ctx->slots[ctx->ada_last_slot].d_ada_counts) {
         // an adaptive frame: the base march's W H rays (bhr_launch_march) and k^2 per refined pixel
         unsigned int n[4] = {0, 0, 0, 0};
-        BHR_TRY(download(ctx, n, ctx->ada[ctx->ada_last_slot].d_counts, sizeof(n)));
+        BHR_TRY(download(ctx, n, ctx->slots[ctx->ada_last_slot].d_ada_counts, sizeof(n)));
         out->rays += ((uint64_t)n[2] + n[3]) * (uint64_t)(ctx->ada_k * ctx->ada_k);
     }
     return BHR_OK;

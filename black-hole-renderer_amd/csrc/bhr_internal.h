@@ -184,29 +184,44 @@ struct bhr_split_geom {
     int32_t table_bytes;
 };
 
-// Frame slot: the buffers one frame in flight owns.  bhr_render alternates between two slots, each with its own
-// stream, so that the tail and the bloom of frame n run under the march of frame n + 1; the scene (skybox, mip
-// stack, comp planes ...) is shared and read-only while frames are in flight (bhr_enter orders every other entry
-// point behind them).  Slot 1 is allocated at the second bhr_render; BHR_FRAME_SLOTS=1 keeps one slot on the
-// context's own stream (round 1 behaviour, isolated per-kernel timing).
+// Frame slot: everything one frame in flight owns -- its buffers, its streams and events, how its post-pass ran.  The
+// slot is the only home of that state: the launchers reach the active one through bhr_slot(ctx).  bhr_render alternates
+// between two slots, each with its own stream, so that the tail and the bloom of frame n run under the march of frame
+// n + 1; the scene (skybox, mip stack, comp planes ...) is shared and read-only while frames are in flight (bhr_enter
+// orders every other entry point behind them).  Slot 1 is allocated at the second bhr_render; BHR_FRAME_SLOTS=1 keeps one
+// slot on the context's own stream (round 1 behaviour, isolated per-kernel timing).
 // two is the measured optimum (fhd strict: 1291 fps with one frame in flight, 1452 with two, 1389 / 1400 with three / four)
 #define BHR_MAX_FRAME_SLOTS 2
 struct bhr_frame_slot {
     hipStream_t stream;
-    float *d_bg, *d_disk, *d_hblur, *d_blur, *d_final;
+    float *d_bg, *d_disk, *d_blur, *d_final;   // (rows, W, 3) each: rows [row0, row1)
+    float *d_hblur;            // planar (3, rows + 2R, W): rows [row0 - R, row1 + R)
     float *d_hblur_base;       // the allocation d_hblur points BHR_HBLUR_PAD_ROWS rows into (zero rows in front of plane 0 and behind plane 2); exact-f32 bloom, on first use
     void *d_pa, *d_pb;         // split-f16 bloom (bloom.hip): the march's packed copy of the disk layer, the packed H-blur planes; on first use
     float *d_sum;              // ... and bg + disk of the frame (rows, W, 3); sum_valid: written by this frame's march / pack kernel
     int32_t sum_valid;
     int32_t disk_wide;         // the DISK layer is a caller's (bhr_write_layer) with a value above BHR_SPLIT_DISK_MAX; a march clears it
-    uint8_t *d_final_u8;
+    uint8_t *d_final_u8;       // (rows, W, 3)
     uint32_t have;             // BHR_OUT_* layers of the slot's last frame that are in memory (the V pass stores what was asked for; the rest on demand)
-    int32_t frame_split, frame_with_bloom;   // how that frame's post-pass ran (bhr_ensure_outputs re-runs its V pass)
+    // the post-pass of the slot's frame, set by bhr_frame_begin: frame_split 0 exact f32 kernels (strict), 1 split-f16
+    // matrix-core kernels (fast / hybrid); bhr_ensure_outputs re-runs its V pass
+    int32_t frame_split, frame_with_bloom;
     unsigned int *d_queue;
-    // lens flare scratch of the frame (flare.hip): glow rows, their transpose, chunk sums, the three frame sums
-    float *d_glow_hw, *d_glow_wh, *d_flare_c0;
-    double *d_flare_c12, *d_flare_sums;
+    // lens flare scratch of the frame (flare.hip), on first use
+    float *d_glow_hw;          // glow rows (rows, W); (H, W) on the context that sums the frame
     int64_t flare_glow_rows;
+    float *d_glow_wh;          // (W, H): the reference's memory order, summed the way NumPy sums it
+    float *d_flare_c0;         // per 8192-element chunk: sum glow (f32)
+    double *d_flare_c12;       // per chunk: sum x glow | sum y glow
+    double *d_flare_sums;      // S0, S1, S2
+    // adaptive supersampling (march_launch.hip: bhr_launch_adaptive), on first use: two lists of fine tiles, the mask, four counts
+    int32_t *d_ada_list;
+    unsigned char *d_ada_mask;
+    unsigned int *d_ada_counts;
+    // second march stream: the strict tiles of a two-stream hybrid march run on it beside the fast ones instead of ahead of
+    // them (bhr_aux_fork / _join, which creates the streams of all slots on first use)
+    hipStream_t aux_stream;
+    hipEvent_t aux_fork, aux_done;
     hipEvent_t done;        // end of the slot's last bhr_render (and of frame work queued behind it: bhr_leave_frame)
     hipEvent_t march_done;  // end of its last march: the last reader of the scene (bhr_enter_scene_write); borrowed from the timing ring
     int32_t allocated;
@@ -218,8 +233,9 @@ struct bhr_ctx {
     int32_t rows;
     hipStream_t stream;                 // the stream launchers use: the scene stream, or a slot's during bhr_render
     hipStream_t scene_stream;           // scene updates, read-backs, group renders
-    bhr_frame_slot slots[BHR_MAX_FRAME_SLOTS];
-    int32_t n_slots, next_slot, active_slot;
+    bhr_frame_slot slots[BHR_MAX_FRAME_SLOTS];   // the per-frame state; the context keeps no copy of it
+    int32_t n_slots, next_slot;
+    int32_t active_slot;                // the slot the launchers work on (bhr_slot): always a valid, allocated one (bhr_activate_slot)
     int32_t two_slot_frames, streams_calibrated, calibrating;   // calibrate_slot_streams (api.hip)
     int32_t calib_choice, calib_fps[8];
     hipStream_t calib_idle[8];
@@ -268,19 +284,11 @@ struct bhr_ctx {
     double vol_opts[4];        // absorption Ca, grazing gain kg, max half thickness, max spherical radius of the volume
     int32_t vol_substeps;
 
-    // frame buffers for rows [row0,row1)
-    float *d_bg, *d_disk;      // (rows, W, 3)
-    float *d_hblur;            // planar (3, rows + 2R, W): rows [row0-R, row1+R)
-    float *d_blur;             // (rows, W, 3)
-    float *d_final;            // (rows, W, 3)
-    uint8_t *d_final_u8;       // (rows, W, 3)
+    // bloom tables (bloom.hip: bhr_bloom_prepare)
     float *d_wtab;             // bloom weights (3, R + pad)
     float *d_wext;             // unfolded weights (3, 2 R4 + 8)
     unsigned short *d_w16;     // split-f16 weight table: 3 channels x 2 halves x 8 shifted copies (bloom.hip: bloom_tables_kernel)
-    void *d_pa, *d_pb;         // the active slot's packed bloom operands (null until a split frame needs them)
-    float *d_sum;
     int32_t mip_lds_from;      // first mip level the last anti-aliased fast march staged in LDS (BHR_MIP_LDS), -1: none
-    int32_t bloom_split;       // post-pass of the current frame: 0 exact f32 kernels (strict), 1 split-f16 matrix-core kernels (fast / hybrid)
     int32_t split_ok;          // the context's radius fits the split kernels' table (R <= 176)
     uint32_t out_want;         // BHR_OUT_* the frames of this context store (bhr_set_outputs; default: the f32 frame)
     // rows of this block that neighbouring row blocks need for their V pass: the H pass writes them straight into those
@@ -292,7 +300,6 @@ struct bhr_ctx {
     float *d_wsum_v;           // (3, H), then (3, H) the split V pass's multiplier 2^-24 / sum
     int32_t bloom_R, bloom_ready;
     unsigned long long *d_ray_steps;
-    unsigned int *d_queue;
     unsigned long long *d_row_steps;   // ray-steps per 8-row band of the last BHR_ROW_COSTS launch
     int32_t *d_tile_order;     // march launch order of the 8x8 tiles
     int32_t *h_tile_order;     // host copy (malloc)
@@ -302,31 +309,18 @@ struct bhr_ctx {
     // ada_threshold are marched again with ada_k x ada_k rays (march_launch.hip: bhr_launch_adaptive).  ada_k = 0: off.
     int32_t ada_k;
     float ada_threshold;
-    struct { int32_t *d_list; unsigned char *d_mask; unsigned int *d_counts; } ada[BHR_MAX_FRAME_SLOTS];   // per frame slot, on first use: two lists of fine tiles, the mask, four counts
     int32_t ada_last_slot;     // frame slot of the last adaptive frame (-1: none since the setting changed), and
     int32_t ada_last_math;     // the arithmetic bhr_resolve_math gave it
     int32_t ada_frame;         // the last bhr_render was an adaptive frame (bhr_get_counters adds the refinement's rays)
     int32_t defer_march_end;   // bhr_launch_march leaves the march-end event to its caller (the refinement follows the base march)
     bhr_march_part part;       // partial launch in progress (inactive: whole block)
-    // second march stream (one per frame slot): the strict tiles of a two-stream hybrid march run on it beside the fast ones
-    // instead of ahead of them (bhr_aux_fork / _join)
-    hipStream_t aux_stream;    // the active slot's second march stream (set by bhr_aux_fork)
-    hipStream_t aux_streams[BHR_MAX_FRAME_SLOTS];
-    hipEvent_t aux_fork[BHR_MAX_FRAME_SLOTS], aux_done[BHR_MAX_FRAME_SLOTS];
     void *hybrid;              // hybrid.hip: tile classification cache
     unsigned int *fix_count;   // fix list of the hybrid march being launched (owned by hybrid.hip, per frame slot)
     int32_t *fix_list;
     int32_t fix_cap;
     void *pipe;                // group.hip: streams, events and band lists of the pipelined row-block path
     uint8_t *d_gather_u8;      // (H, W, 3) u8: quantised frame gathered from the tiles (BHR_GATHER_U8), on tile 0
-    // lens flare (flare.hip)
-    float *d_glow_hw;          // glow rows (rows, W); (H, W) on the context that sums the frame
-    int64_t flare_glow_rows;
-    float *d_glow_wh;          // (W, H): the reference's memory order, summed the way NumPy sums it
-    float *d_flare_c0;         // per 8192-element chunk: sum glow (f32)
-    double *d_flare_c12;       // per chunk: sum x glow | sum y glow
-    int32_t *d_flare_prog;     // pairwise tree of the ragged last chunk
-    double *d_flare_sums;      // S0, S1, S2
+    int32_t *d_flare_prog;     // lens flare (flare.hip): pairwise tree of the ragged last chunk; shared by the slots, read-only
     float *d_gather;           // (H, W, 3): full frame gathered from the tiles of a group render (BHR_GATHER_PEER), on tile 0
     void *png_dev;             // device PNG encoder state (png_device.hip), created on first use
     void *jpeg_dev;            // device JPEG encoder state (jpeg_device.hip), created on first use
@@ -340,6 +334,10 @@ struct bhr_ctx {
     int32_t group_time_march;  // group / tile renders: also record the march-end event (BHR_GROUP_TIME_MARCH); off, the tile's stream carries no event between march and H pass
     int32_t march_end_recorded;
 };
+
+// The active frame slot: the one bhr_activate_slot / bhr_render last pointed the launchers at.
+inline bhr_frame_slot &bhr_slot(bhr_ctx *ctx) { return ctx->slots[ctx->active_slot]; }
+inline const bhr_frame_slot &bhr_slot(const bhr_ctx *ctx) { return ctx->slots[ctx->active_slot]; }
 
 // The frame the march marches: the context's own, or under supersampling (ctx->ss = k > 1) the one k times finer along
 // both axes, at pixel pitch / k.  The tile grid, the tile order, the hybrid classification and the fix lists live on it.
@@ -417,8 +415,9 @@ int32_t bhr_launch_bloom_h(bhr_ctx *ctx);
 int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, int32_t r1, uint32_t want, uint8_t *gather_u8, float *gather_f32);
 int32_t bhr_bloom_v_tile_rows(bhr_ctx *ctx);                               // output rows per V-pass block
 int32_t bhr_activate_slot(bhr_ctx *ctx, int32_t k);                        // api.hip: points the launchers at frame slot k (allocating it)
-// api.hip: decides the frame's arithmetic / post-pass kernels and makes sure their buffers exist (before the march is launched)
-int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags);
+// api.hip: decides the frame's arithmetic / post-pass kernels (exact: the exact f32 ones whatever the arithmetic) and makes
+// sure their buffers exist (before the march is launched)
+int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags, bool exact = false);
 // api.hip: the whole-block V pass of a frame into the context's own buffers, recording what it stored
 int32_t bhr_frame_post(bhr_ctx *ctx, int32_t with_bloom, uint32_t want);
 // api.hip: makes the BHR_OUT_* layers in `need` of the active slot's last frame exist (re-runs its V pass for what is missing)

@@ -856,10 +856,11 @@ int32_t bhr_launch_bloom_pack(bhr_ctx *ctx) {
     bhr_split_geom g;
     bhr_split_geometry(ctx, &g);
     const int groups = (ctx->cfg.width + 7) / 8;
-    hipLaunchKernelGGL(bloom_pack_kernel, dim3((groups + 63) / 64, ctx->rows), dim3(64), 0, ctx->stream, ctx->d_disk,
-                       ctx->d_bg, ctx->d_sum, (_Float16 *)ctx->d_pa, ctx->cfg.width, ctx->rows, g.YB, g.GP, g.g0);
+    bhr_frame_slot &f = bhr_slot(ctx);
+    hipLaunchKernelGGL(bloom_pack_kernel, dim3((groups + 63) / 64, ctx->rows), dim3(64), 0, ctx->stream, f.d_disk,
+                       f.d_bg, f.d_sum, (_Float16 *)f.d_pa, ctx->cfg.width, ctx->rows, g.YB, g.GP, g.g0);
     BHR_HIP(hipGetLastError());
-    ctx->slots[ctx->active_slot].sum_valid = 1;
+    f.sum_valid = 1;
     return BHR_OK;
 }
 
@@ -867,12 +868,13 @@ int32_t bhr_launch_bloom_pack(bhr_ctx *ctx) {
 int32_t bhr_launch_bloom_h(bhr_ctx *ctx) {
     const int W = ctx->cfg.width, R = ctx->bloom_R;
     BHR_TRY(bhr_bloom_prepare(ctx));
-    if (ctx->bloom_split) {
+    const bhr_frame_slot &f = bhr_slot(ctx);
+    if (f.frame_split) {
         bhr_split_geom g;
         bhr_split_geometry(ctx, &g);
         HSplitArgs a;
-        a.pa = (const _Float16 *)ctx->d_pa;
-        a.pb = (_Float16 *)ctx->d_pb;
+        a.pa = (const _Float16 *)f.d_pa;
+        a.pb = (_Float16 *)f.d_pb;
         a.w16 = ctx->d_w16;
         a.wsum_h = ctx->d_wsum_h;
         a.W = W; a.WP = g.WP; a.rows = ctx->rows; a.row0 = ctx->cfg.row0;
@@ -900,7 +902,7 @@ int32_t bhr_launch_bloom_h(bhr_ctx *ctx) {
     dim3 grid((W + pix - 1) / pix, ctx->rows), block(256);
     const size_t lds = ((size_t)3 * (pix + 2 * R4 + 4) + 3 * (2 * R4 + 8)) * sizeof(float);
     BHR_TRY(allow_lds((const void *)bloom_h_f32_kernel, lds));
-    hipLaunchKernelGGL(bloom_h_f32_kernel, grid, block, lds, ctx->stream, ctx->d_disk, ctx->d_hblur, ctx->d_wext, ctx->d_wsum_h, W, ctx->rows, R, 0);
+    hipLaunchKernelGGL(bloom_h_f32_kernel, grid, block, lds, ctx->stream, f.d_disk, f.d_hblur, ctx->d_wext, ctx->d_wsum_h, W, ctx->rows, R, 0);
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }
@@ -915,25 +917,26 @@ int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, in
     BHR_TRY(bhr_bloom_prepare(ctx));
     if (r0 < 0 || r1 > ctx->rows || r0 > r1) return bhr_fail(BHR_ERR_INVALID, "bloom V: rows [%d,%d) of %d", r0, r1, ctx->rows);
     if (r0 == r1) return BHR_OK;
+    bhr_frame_slot &f = bhr_slot(ctx);
     VOut out;
     const size_t row0_off = (size_t)ctx->cfg.row0 * W * 3;
-    out.final_f32 = (want & BHR_OUT_F32) ? (gather_f32 ? gather_f32 + row0_off : ctx->d_final) : nullptr;
-    out.blur = (want & BHR_OUT_BLUR) ? ctx->d_blur : nullptr;
-    out.u8 = (want & BHR_OUT_U8) ? (gather_u8 ? gather_u8 + row0_off : ctx->d_final_u8) : nullptr;
-    if (ctx->bloom_split && with_bloom) {
+    out.final_f32 = (want & BHR_OUT_F32) ? (gather_f32 ? gather_f32 + row0_off : f.d_final) : nullptr;
+    out.blur = (want & BHR_OUT_BLUR) ? f.d_blur : nullptr;
+    out.u8 = (want & BHR_OUT_U8) ? (gather_u8 ? gather_u8 + row0_off : f.d_final_u8) : nullptr;
+    if (f.frame_split && with_bloom) {
         bhr_split_geom g;
         bhr_split_geometry(ctx, &g);
         VSplitArgs a;
-        a.pb = (const _Float16 *)ctx->d_pb;
+        a.pb = (const _Float16 *)f.d_pb;
         a.w16 = ctx->d_w16;
         a.wsum_v = ctx->d_wsum_v;
-        if (!ctx->slots[ctx->active_slot].sum_valid) {          // layers the caller wrote after the march (bhr_write_layer)
+        if (!f.sum_valid) {          // layers the caller wrote after the march (bhr_write_layer)
             const long long n = (long long)ctx->rows * W * 3;
-            hipLaunchKernelGGL(bloom_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_bg, ctx->d_disk, ctx->d_sum, n);
+            hipLaunchKernelGGL(bloom_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, f.d_bg, f.d_disk, f.d_sum, n);
             BHR_HIP(hipGetLastError());
-            ctx->slots[ctx->active_slot].sum_valid = 1;
+            f.sum_valid = 1;
         }
-        a.sum = ctx->d_sum;
+        a.sum = f.d_sum;
         a.out = out;
         a.zero_cell = ctx->v_zero_cell;
         a.W = W; a.WP = g.WP; a.H = H; a.row0 = ctx->cfg.row0;
@@ -955,7 +958,7 @@ int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, in
     }
     dim3 grid((W + 127) / 128, (r1 - r0 + 31) / 32), block(256);
     const size_t lds = with_bloom ? (size_t)3 * (2 * R + 64 + 44) * sizeof(float) : 0;
-    hipLaunchKernelGGL(bloom_v_f32_kernel, grid, block, lds, ctx->stream, ctx->d_hblur, ctx->d_bg, ctx->d_disk, out, ctx->d_wtab,
+    hipLaunchKernelGGL(bloom_v_f32_kernel, grid, block, lds, ctx->stream, f.d_hblur, f.d_bg, f.d_disk, out, ctx->d_wtab,
                        ctx->d_wsum_v, W, H, ctx->cfg.row0, ctx->rows, R, with_bloom, ctx->v_zero_cell, r0, r1);
     BHR_HIP(hipGetLastError());
     return BHR_OK;

@@ -264,24 +264,24 @@ int build_tree(int off, int n, std::vector<int> &leaves, std::vector<int> &ops) 
     return a;
 }
 
-// ctx->d_glow_* / d_flare_c* / d_flare_sums are the ACTIVE frame slot's (api.hip: activate_slot); what is allocated
-// here is stored back into the slot.  The tail program is read-only and shared.
-int32_t ensure_buffers_(bhr_ctx *ctx, bool whole_frame) {
+// the scratch of the active frame slot; the tail program is read-only and shared by the slots
+int32_t ensure_buffers(bhr_ctx *ctx, bool whole_frame) {
+    bhr_frame_slot &f = bhr_slot(ctx);
     const int W = ctx->cfg.width, H = ctx->cfg.height;
     const size_t want_rows = whole_frame ? (size_t)H : (size_t)ctx->rows;
-    if (ctx->flare_glow_rows < (int64_t)want_rows) {
-        if (ctx->d_glow_hw) (void)hipFree(ctx->d_glow_hw);
-        ctx->d_glow_hw = nullptr;
-        BHR_HIP(hipMalloc((void **)&ctx->d_glow_hw, want_rows * W * sizeof(float)));
-        ctx->flare_glow_rows = (int64_t)want_rows;
+    if (f.flare_glow_rows < (int64_t)want_rows) {
+        if (f.d_glow_hw) (void)hipFree(f.d_glow_hw);
+        f.d_glow_hw = nullptr;
+        BHR_HIP(hipMalloc((void **)&f.d_glow_hw, want_rows * W * sizeof(float)));
+        f.flare_glow_rows = (int64_t)want_rows;
     }
-    if (!ctx->d_flare_sums) BHR_HIP(hipMalloc((void **)&ctx->d_flare_sums, 3 * sizeof(double)));
-    if (whole_frame && !ctx->d_glow_wh) {
+    if (!f.d_flare_sums) BHR_HIP(hipMalloc((void **)&f.d_flare_sums, 3 * sizeof(double)));
+    if (whole_frame && !f.d_glow_wh) {
         const long long n = (long long)W * H;
         const int n_chunks = (int)(n / CHUNK);
-        BHR_HIP(hipMalloc((void **)&ctx->d_glow_wh, (size_t)n * sizeof(float)));
-        BHR_HIP(hipMalloc((void **)&ctx->d_flare_c0, (size_t)(n_chunks + 1) * sizeof(float)));
-        BHR_HIP(hipMalloc((void **)&ctx->d_flare_c12, (size_t)(n_chunks + 1) * 2 * sizeof(double)));
+        BHR_HIP(hipMalloc((void **)&f.d_glow_wh, (size_t)n * sizeof(float)));
+        BHR_HIP(hipMalloc((void **)&f.d_flare_c0, (size_t)(n_chunks + 1) * sizeof(float)));
+        BHR_HIP(hipMalloc((void **)&f.d_flare_c12, (size_t)(n_chunks + 1) * 2 * sizeof(double)));
     }
     if (whole_frame && !ctx->d_flare_prog) {
         const long long n = (long long)W * H;
@@ -298,26 +298,15 @@ int32_t ensure_buffers_(bhr_ctx *ctx, bool whole_frame) {
     return BHR_OK;
 }
 
-int32_t ensure_buffers(bhr_ctx *ctx, bool whole_frame) {
-    const int32_t rc = ensure_buffers_(ctx, whole_frame);
-    bhr_frame_slot &f = ctx->slots[ctx->active_slot];
-    f.d_glow_hw = ctx->d_glow_hw;
-    f.d_glow_wh = ctx->d_glow_wh;
-    f.d_flare_c0 = ctx->d_flare_c0;
-    f.d_flare_c12 = ctx->d_flare_c12;
-    f.d_flare_sums = ctx->d_flare_sums;
-    f.flare_glow_rows = ctx->flare_glow_rows;
-    return rc;
-}
-
 }  // namespace
 
 // glow of this context's rows -> its d_glow_hw (whole-frame context: at the rows' place in the frame)
 int32_t bhr_launch_flare_glow(bhr_ctx *ctx, bool whole_frame) {
     if (int32_t rc = ensure_buffers(ctx, whole_frame)) return rc;
     const long long n = (long long)ctx->rows * ctx->cfg.width;
-    float *dst = ctx->d_glow_hw + (whole_frame ? (size_t)ctx->cfg.row0 * ctx->cfg.width : 0);
-    hipLaunchKernelGGL(flare_glow_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_disk, dst, n);
+    const bhr_frame_slot &f = bhr_slot(ctx);
+    float *dst = f.d_glow_hw + (whole_frame ? (size_t)ctx->cfg.row0 * ctx->cfg.width : 0);
+    hipLaunchKernelGGL(flare_glow_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, f.d_disk, dst, n);
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }
@@ -328,13 +317,14 @@ int32_t bhr_launch_flare_sums(bhr_ctx *ctx) {
     const int W = ctx->cfg.width, H = ctx->cfg.height;
     const long long n = (long long)W * H;
     const int n_chunks = (int)(n / CHUNK);
-    hipLaunchKernelGGL(flare_transpose_kernel, dim3((W + 31) / 32, (H + 31) / 32), dim3(256), 0, ctx->stream, ctx->d_glow_hw,
-                       ctx->d_glow_wh, H, W);
-    double *c1 = ctx->d_flare_c12, *c2 = ctx->d_flare_c12 + n_chunks + 1;
+    const bhr_frame_slot &f = bhr_slot(ctx);
+    hipLaunchKernelGGL(flare_transpose_kernel, dim3((W + 31) / 32, (H + 31) / 32), dim3(256), 0, ctx->stream, f.d_glow_hw,
+                       f.d_glow_wh, H, W);
+    double *c1 = f.d_flare_c12, *c2 = f.d_flare_c12 + n_chunks + 1;
     if (n_chunks > 0)
-        hipLaunchKernelGGL(flare_chunk_kernel, dim3(n_chunks), dim3(64), 0, ctx->stream, ctx->d_glow_wh, H, ctx->d_flare_c0, c1, c2);
-    hipLaunchKernelGGL(flare_fold_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->d_glow_wh, H, (long long)n_chunks * CHUNK,
-                       ctx->d_flare_prog, n_chunks, ctx->d_flare_c0, c1, c2, ctx->d_flare_sums);
+        hipLaunchKernelGGL(flare_chunk_kernel, dim3(n_chunks), dim3(64), 0, ctx->stream, f.d_glow_wh, H, f.d_flare_c0, c1, c2);
+    hipLaunchKernelGGL(flare_fold_kernel, dim3(1), dim3(256), 0, ctx->stream, f.d_glow_wh, H, (long long)n_chunks * CHUNK,
+                       ctx->d_flare_prog, n_chunks, f.d_flare_c0, c1, c2, f.d_flare_sums);
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }
@@ -345,8 +335,9 @@ int32_t bhr_launch_flare_apply(bhr_ctx *ctx, const double *sums) {
     FlareSums hs{0.0, 0.0, 0.0};
     if (sums) hs = FlareSums{sums[0], sums[1], sums[2]};
     const long long n = (long long)ctx->rows * ctx->cfg.width;
-    hipLaunchKernelGGL(flare_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_final, ctx->cfg.width,
-                       ctx->cfg.height, ctx->cfg.row0, ctx->rows, ctx->d_flare_sums, hs, sums ? 1 : 0);
+    const bhr_frame_slot &f = bhr_slot(ctx);
+    hipLaunchKernelGGL(flare_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, f.d_final, ctx->cfg.width,
+                       ctx->cfg.height, ctx->cfg.row0, ctx->rows, f.d_flare_sums, hs, sums ? 1 : 0);
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }

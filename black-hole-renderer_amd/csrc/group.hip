@@ -86,7 +86,7 @@ int plan_chunks(const bhr_ctx *c, bool has_up, bool has_down, int vb, bool pipel
     const int rows = c->rows;
     if (!pipelined || (!has_up && !has_down)) { out[0] = Chunk{0, rows, (has_up || has_down) ? 1 : 0}; return 1; }
     // reach of a neighbour's rows into this tile: the bloom radius, or the padded radius of the split kernels' 16-tap chunks
-    const int R = c->bloom_split ? 16 * (bhr_split_nt(c->bloom_R) - 1) : c->bloom_R;
+    const int R = bhr_slot(c).frame_split ? 16 * (bhr_split_nt(c->bloom_R) - 1) : c->bloom_R;
     int n = 0;
     // first / last local row whose V-pass tile is clear of the neighbours: tiles are `vb` image rows, aligned globally
     int m0 = 0, m1 = rows;
@@ -173,13 +173,13 @@ int32_t queue_halo_pull(bhr_ctx **ctxs, int n, int k, hipStream_t stream, const 
             const size_t take = (size_t)nb->rows < need ? (size_t)nb->rows : need;
             const TilePipe *np = (const TilePipe *)nb->pipe;
             if (np && (!live || live[q])) BHR_HIP(hipStreamWaitEvent(stream, np->halo_ready, 0));   // a resting tile has nothing in flight
-            if (!nb->d_hblur) return bhr_fail(BHR_ERR_STATE, "group render: tile %d has no H-blur planes to pull from (render every tile once first)", q);
+            if (!bhr_slot(nb).d_hblur) return bhr_fail(BHR_ERR_STATE, "group render: tile %d has no H-blur planes to pull from (render every tile once first)", q);
             const size_t nb_plane = ((size_t)nb->rows + 2 * R) * W, my_plane = (my_rows + 2 * R) * W;
             const size_t src_row = side == 0 ? R + nb->rows - take : R;          // neighbour's own rows live at [R, R + rows)
             const size_t dst_row = side == 0 ? R - got - take : R + my_rows + got;
             for (int c = 0; c < 3; ++c)
-                BHR_HIP(hipMemcpyPeerAsync(me->d_hblur + c * my_plane + dst_row * W, me->cfg.device,
-                                           nb->d_hblur + c * nb_plane + src_row * W, nb->cfg.device, take * W * sizeof(float), stream));
+                BHR_HIP(hipMemcpyPeerAsync(bhr_slot(me).d_hblur + c * my_plane + dst_row * W, me->cfg.device,
+                                           bhr_slot(nb).d_hblur + c * nb_plane + src_row * W, nb->cfg.device, take * W * sizeof(float), stream));
             need -= take;
             got += take;
             q += side == 0 ? -1 : 1;
@@ -203,18 +203,18 @@ int32_t flare_pass(bhr_ctx **ctxs, int n, const int32_t *live) {
     for (int k = 1; k < n; ++k) {
         if (live && !live[k]) continue;            // a tile that is not live left its glow rows on tile 0 last time
         BHR_HIP(hipStreamWaitEvent(head->stream, ctxs[k]->ev[3], 0));
-        BHR_HIP(hipMemcpyPeerAsync(head->d_glow_hw + (size_t)ctxs[k]->cfg.row0 * W, head->cfg.device, ctxs[k]->d_glow_hw,
+        BHR_HIP(hipMemcpyPeerAsync(bhr_slot(head).d_glow_hw + (size_t)ctxs[k]->cfg.row0 * W, head->cfg.device, bhr_slot(ctxs[k]).d_glow_hw,
                                    ctxs[k]->cfg.device, (size_t)ctxs[k]->rows * W * sizeof(float), head->stream));
     }
     BHR_TRY(bhr_launch_flare_sums(head));
     double tot[3];
-    BHR_HIP(hipMemcpyAsync(tot, head->d_flare_sums, sizeof(tot), hipMemcpyDeviceToHost, head->stream));
+    BHR_HIP(hipMemcpyAsync(tot, bhr_slot(head).d_flare_sums, sizeof(tot), hipMemcpyDeviceToHost, head->stream));
     BHR_HIP(hipStreamSynchronize(head->stream));
     for (int k = 0; k < n; ++k) {
         if (live && !live[k]) continue;
         BHR_HIP(hipSetDevice(ctxs[k]->cfg.device));
         BHR_TRY(bhr_launch_flare_apply(ctxs[k], tot));
-        ctxs[k]->slots[ctxs[k]->active_slot].have &= ~BHR_OUT_U8;
+        bhr_slot(ctxs[k]).have &= ~BHR_OUT_U8;
     }
     return BHR_OK;
 }
@@ -232,9 +232,9 @@ int32_t ensure_gather(bhr_ctx *head, uint32_t flags) {
 int32_t queue_push(bhr_ctx *head, bhr_ctx *t, uint32_t flags, hipStream_t stream) {
     const size_t W3 = (size_t)t->cfg.width * 3, cnt = (size_t)t->rows * W3, dst = (size_t)t->cfg.row0 * W3;
     if (flags & BHR_GATHER_U8)
-        BHR_HIP(hipMemcpyPeerAsync(head->d_gather_u8 + dst, head->cfg.device, t->d_final_u8, t->cfg.device, cnt, stream));
+        BHR_HIP(hipMemcpyPeerAsync(head->d_gather_u8 + dst, head->cfg.device, bhr_slot(t).d_final_u8, t->cfg.device, cnt, stream));
     if (flags & BHR_GATHER_PEER)
-        BHR_HIP(hipMemcpyPeerAsync(head->d_gather + dst, head->cfg.device, t->d_final, t->cfg.device, cnt * sizeof(float), stream));
+        BHR_HIP(hipMemcpyPeerAsync(head->d_gather + dst, head->cfg.device, bhr_slot(t).d_final, t->cfg.device, cnt * sizeof(float), stream));
     return BHR_OK;
 }
 
@@ -248,7 +248,7 @@ int32_t finish(bhr_ctx **ctxs, int n, const int32_t *live, float *out_host) {
             BHR_HIP(hipSetDevice(ctxs[k]->cfg.device));
             const size_t bytes = (size_t)ctxs[k]->rows * W * 3 * sizeof(float);
             BHR_TRY(bhr_ensure_pinned(ctxs[k], bytes));
-            BHR_HIP(hipMemcpyAsync(ctxs[k]->h_pinned, ctxs[k]->d_final, bytes, hipMemcpyDeviceToHost, ctxs[k]->stream));
+            BHR_HIP(hipMemcpyAsync(ctxs[k]->h_pinned, bhr_slot(ctxs[k]).d_final, bytes, hipMemcpyDeviceToHost, ctxs[k]->stream));
         }
     for (int k = 0; k < n; ++k) {
         if (live && !live[k]) continue;
@@ -264,7 +264,7 @@ int32_t finish(bhr_ctx **ctxs, int n, const int32_t *live, float *out_host) {
 int32_t set_mirrors(bhr_ctx **ctxs, int n, int k) {
     bhr_ctx *c = ctxs[k];
     c->n_mirrors = 0;
-    if (!c->bloom_split) return BHR_OK;
+    if (!bhr_slot(c).frame_split) return BHR_OK;
     const int reach = 16 * (bhr_split_nt(c->bloom_R) - 1);
     for (int q = 0; q < n; ++q) {
         if (q == k || !needs_rows_of(ctxs[q], c, reach + 32)) continue;   // + 32: planes start on 32-row tile boundaries
@@ -299,12 +299,6 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
     for (int k = 0; k < n && all_peer; ++k)
         for (int q = 0; q < n && all_peer; ++q)
             if (k != q && !peer_ok(ctxs[k], ctxs[q])) all_peer = false;
-    struct RestoreSplit {                     // the option is the context's own: put back whatever the frame does
-        bhr_ctx **c; int n; int32_t saved[64]; bool on;
-        ~RestoreSplit() { if (on) for (int k = 0; k < n && k < 64; ++k) c[k]->opt.bloom_split = saved[k]; }
-    } restore{ctxs, n, {}, !all_peer && n <= 64};
-    if (restore.on)
-        for (int k = 0; k < n; ++k) { restore.saved[k] = ctxs[k]->opt.bloom_split; ctxs[k]->opt.bloom_split = 0; }
 
     // every tile chooses its post-pass kernels and makes sure their buffers exist BEFORE any H pass may store into them
     for (int k = 0; k < n; ++k) {
@@ -315,7 +309,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
         c->cur_slot = -1;
         c->last_slot = -1;
         BHR_TRY(ensure_pipe(c));
-        BHR_TRY(bhr_frame_begin(c, flags));
+        BHR_TRY(bhr_frame_begin(c, flags, !all_peer));
         c->group_time_march = (flags & BHR_GROUP_TIME_MARCH) ? 1 : 0;
     }
     const bool halo = with_bloom && n > 1;
@@ -328,7 +322,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
     // the slowest tile's own V pass either way, and one launch saves the chunks' fixed costs (~20 us per tile at 8k).
     bool any_split = false;
     for (int k = 0; k < n; ++k)
-        if (!live || live[k]) any_split = any_split || ctxs[k]->bloom_split != 0;
+        if (!live || live[k]) any_split = any_split || bhr_slot(ctxs[k]).frame_split != 0;
     const bool pipelined = schedule >= 0 ? schedule != 0 : (schedule == -2 && !any_split);      // -2: tiles on distinct devices
 
     // phase 1: march and H pass (+ the neighbours' halo rows of a split frame) on the tile's stream
@@ -339,7 +333,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
         BHR_TRY(bhr_launch_march(c, cam, flags));
         // frames in flight (BHR_GROUP_ASYNC): this H pass stores into its neighbours' halo rows, which their previous frame's V
         // passes may still be reading -- wait for those on the device
-        if (with_bloom && c->bloom_split)
+        if (with_bloom && bhr_slot(c).frame_split)
             for (int q = 0; q < n; ++q) {
                 TilePipe *pq = q == k ? nullptr : (TilePipe *)ctxs[q]->pipe;
                 if (pq && pq->in_flight && needs_rows_of(ctxs[q], c, 16 * (bhr_split_nt(c->bloom_R) - 1) + 32)) BHR_HIP(hipStreamWaitEvent(c->stream, pq->frame_done, 0));
@@ -348,7 +342,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
         // `halo_ready` (this tile's H pass is done: its neighbours may run the V pass of their edge rows).  An event record is a
         // ~5 us bubble in the stream: the pipelined schedule records it BEHIND the V pass of the middle rows (phase 3) -- the
         // neighbours are busy with their own middle rows until then -- the serial one here
-        if (!pipelined || !with_bloom || !c->bloom_split) BHR_HIP(hipEventRecord(p->halo_ready, c->stream));
+        if (!pipelined || !with_bloom || !bhr_slot(c).frame_split) BHR_HIP(hipEventRecord(p->halo_ready, c->stream));
         return BHR_OK;
     }));
     for (int k = 0; k < n; ++k)
@@ -358,7 +352,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
     // (copy stream) in the pipelined schedule
     if (halo)
         for (int k = 0; k < n; ++k) {
-            if ((live && !live[k]) || ctxs[k]->bloom_split) continue;
+            if ((live && !live[k]) || bhr_slot(ctxs[k]).frame_split) continue;
             TilePipe *p = (TilePipe *)ctxs[k]->pipe;
             BHR_HIP(hipSetDevice(ctxs[k]->cfg.device));
             hipStream_t s = pipelined ? p->copy : ctxs[k]->stream;
@@ -388,11 +382,11 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
                     if (!chunks[ci].needs_halo)
                         BHR_TRY(bhr_launch_bloom_v_rows(c, with_bloom, chunks[ci].r0, chunks[ci].r1, want, direct ? head->d_gather_u8 : nullptr,
                                                         direct ? head->d_gather : nullptr));
-                if (pipelined && with_bloom && c->bloom_split) BHR_HIP(hipEventRecord(p->halo_ready, c->stream));
+                if (pipelined && with_bloom && bhr_slot(c).frame_split) BHR_HIP(hipEventRecord(p->halo_ready, c->stream));
                 continue;
             }
             if (halo) {
-                if (!c->bloom_split) {
+                if (!bhr_slot(c).frame_split) {
                     BHR_HIP(hipStreamWaitEvent(c->stream, p->halo_in, 0));
                 } else {
                     const int reach = 16 * (bhr_split_nt(c->bloom_R) - 1) + 32;
@@ -406,7 +400,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
                 if (chunks[ci].needs_halo)
                     BHR_TRY(bhr_launch_bloom_v_rows(c, with_bloom, chunks[ci].r0, chunks[ci].r1, want, direct ? head->d_gather_u8 : nullptr,
                                                     direct ? head->d_gather : nullptr));
-            c->slots[c->active_slot].have = direct ? 0u : want;           // what sits in the tile's OWN buffers
+            bhr_slot(c).have = direct ? 0u : want;           // what sits in the tile's OWN buffers
             c->last_flags = (int32_t)flags;
             c->timing_valid = 1;
         }
@@ -430,7 +424,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
     // the whole frame
     bool async = (flags & BHR_GROUP_ASYNC) && gather && !flare && !out_host && with_bloom;
     for (int k = 0; k < n && async; ++k)
-        if ((!live || live[k]) && (!ctxs[k]->bloom_split || !peer_ok(ctxs[k], head))) async = false;
+        if ((!live || live[k]) && (!bhr_slot(ctxs[k]).frame_split || !peer_ok(ctxs[k], head))) async = false;
     for (int k = 0; k < n; ++k) {
         if (live && !live[k]) continue;
         TilePipe *p = (TilePipe *)ctxs[k]->pipe;
@@ -549,7 +543,7 @@ int32_t bhr_tile_export(bhr_ctx *ctx, uint32_t gather_flags, bhr_tile_handles *o
     memset(out, 0, sizeof(*out));
     static_assert(sizeof(hipIpcMemHandle_t) <= sizeof(out->hblur), "handle size");
     hipIpcMemHandle_t h;
-    if (ctx->bloom_split) {
+    if (bhr_slot(ctx).frame_split) {
         bhr_split_geom g;
         bhr_split_geometry(ctx, &g);
         BHR_HIP(hipIpcGetMemHandle(&h, ctx->slots[0].d_pb));
@@ -584,7 +578,7 @@ int32_t bhr_tile_connect(bhr_ctx *ctx, int32_t rank, int32_t world, const bhr_ti
     BHR_TRY(bhr_enter(ctx));
     BHR_TRY(bhr_activate_slot(ctx, 0));
     BHR_TRY(bhr_frame_begin(ctx, 0));
-    const int split = ctx->bloom_split;
+    const int split = bhr_slot(ctx).frame_split;
     const int min_rows = split ? 16 * bhr_split_nt(ctx->bloom_R) + 16 : ctx->bloom_R;   // a tile's planes must not reach past its neighbours
     int expect = 0;
     for (int k = 0; k < world; ++k) {
@@ -666,7 +660,7 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
     ctx->last_slot = -1;
     BHR_TRY(bhr_frame_begin(ctx, flags));
     ctx->group_time_march = (flags & BHR_GROUP_TIME_MARCH) ? 1 : 0;
-    if (with_bloom && ctx->bloom_split != p->split)
+    if (with_bloom && bhr_slot(ctx).frame_split != p->split)
         return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the flags select the other post-pass arithmetic than the one the tiles were connected for");
     const bool halo = with_bloom && world > 1;
     ctx->n_mirrors = 0;
@@ -709,14 +703,14 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
             const size_t src_row = side == 0 ? nb_rows : R;                  // its last / first R rows (own rows live at [R, R + rows))
             const size_t dst_row = side == 0 ? 0 : R + rows;
             for (int c = 0; c < 3; ++c)
-                BHR_HIP(hipMemcpyAsync(ctx->d_hblur + c * my_plane + dst_row * W, p->nb_hblur[side] + c * nb_plane + src_row * W,
+                BHR_HIP(hipMemcpyAsync(bhr_slot(ctx).d_hblur + c * my_plane + dst_row * W, p->nb_hblur[side] + c * nb_plane + src_row * W,
                                        R * W * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
         }
     }
     for (int ci = 0; ci < n_chunks; ++ci)
         if (chunks[ci].needs_halo) BHR_TRY(v_chunk(ci));
     BHR_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
-    ctx->slots[ctx->active_slot].have = direct ? 0u : want;
+    bhr_slot(ctx).have = direct ? 0u : want;
     ctx->last_flags = (int32_t)flags;
     ctx->timing_valid = 1;
     BHR_HIP(hipStreamSynchronize(ctx->stream));

@@ -411,7 +411,7 @@ void bhr_hybrid_free(bhr_ctx *ctx) {
 
 int32_t bhr_hybrid_active_list(bhr_ctx *ctx, const int32_t **list, int32_t *n) {
     Hybrid *h = (Hybrid *)ctx->hybrid;
-    const int k = ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0;
+    const int k = ctx->active_slot;
     if (!h || !h->slot[k].valid || !h->slot[k].d_active) return bhr_fail(BHR_ERR_STATE, "no hybrid march has run on this context's active slot");
     *list = h->slot[k].d_active;
     *n = h->slot[k].base_n;
@@ -493,7 +493,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
     view_key(cam, lo, hi, pad_f, (double)ctx->cfg.disk_tilt_deg, key);
     const int n_tiles = ctx->tile_order_n;
     const bool on_device = ctx->opt.hybrid_classify != 0;
-    SlotLists &s = h->slot[ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0];
+    SlotLists &s = h->slot[ctx->active_slot];
     const bool new_view = !h->valid || h->on_device != (int32_t)on_device || !same_view(h->key, key);
     if (on_device) {
         const int32_t *d_base = ctx->d_tile_order;
@@ -617,8 +617,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
     const bool aa = ctx->cfg.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS);
     bool repair = aa || ctx->cfg.disk_tilt_deg != 0.0f;
     if (ctx->opt.hybrid_repair >= 0) repair = ctx->opt.hybrid_repair != 0;
-    const int slot_k = ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0;
-    FixList &fx = h->fix[slot_k];
+    FixList &fx = h->fix[ctx->active_slot];
     if (repair && !fx.d_list) {
         const long long px = (long long)fr.width * fr.rows;        // rays: a multiple of 256 is one of k^2 too
         // an eighth of the block's pixels (measured shares: 0.1-0.4 % on the BASELINE views, up to 3 % on fuzzed anti-aliased
@@ -628,7 +627,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
         BHR_HIP(hipMalloc((void **)&fx.d_count, 64));
         BHR_HIP(hipMalloc((void **)&fx.d_list, (size_t)fx.cap * sizeof(int32_t)));
     }
-    h->last_fix_slot = repair ? slot_k : -1;
+    h->last_fix_slot = repair ? ctx->active_slot : -1;
     ctx->fix_count = repair ? fx.d_count : nullptr;
     ctx->fix_list = repair ? fx.d_list : nullptr;
     ctx->fix_cap = repair ? fx.cap : 0;
@@ -652,7 +651,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
         // the fast list -- ten times the tiles of the strict one, it ends last -- rides the frame's own stream, so that the
         // post-pass follows it on the same hardware queue (a wait on another queue's event costs ~10 us after that queue's
         // kernel has ended; on a finished one, nothing); the strict list runs on the second stream
-        ctx->stream = ctx->aux_stream;
+        ctx->stream = bhr_slot(ctx).aux_stream;
         if (rc == BHR_OK) rc = launch(s.d_active, s.n_strict, 0, 0, 0);
         if (rc == BHR_OK) {
             ctx->stream = main_stream;
@@ -686,7 +685,7 @@ int32_t bhr_hybrid_fine_flags(bhr_ctx *ctx, const bhr_camera *out_cam, int32_t k
     effective_band(ctx, &lo, &hi);
     const double pad_f = ctx->opt.hybrid_pad;
     view_key(&cam, lo, hi, pad_f, (double)ctx->cfg.disk_tilt_deg, key);
-    auto &f = h->fine[ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0];
+    auto &f = h->fine[ctx->active_slot];
     const ClassifyArgs ca = classify_args(&cam, fr, (double)ctx->cfg.disk_tilt_deg, lo, hi, pad_f);
     if (!f.d_flags || f.k != k) {
         // (a change of k has drained the context and freed the Hybrid: the buffer is allocated once per setting)

@@ -532,7 +532,7 @@ int32_t bhr_jpeg_encode_device(bhr_ctx *ctx, int32_t quality, uint8_t *out, int6
         d->out_cap = bound;
     }
     BHR_TRY(bhr_launch_quantize(ctx));
-    BHR_TRY(bhr_launch_jpeg_encode(ctx, quality, ctx->d_final_u8, d->d_out, bound, d->d_meta));
+    BHR_TRY(bhr_launch_jpeg_encode(ctx, quality, bhr_slot(ctx).d_final_u8, d->d_out, bound, d->d_meta));
     uint32_t meta[4] = {0, 0, 0, 0};
     BHR_HIP(hipMemcpyAsync(meta, d->d_meta, sizeof(meta), hipMemcpyDeviceToHost, ctx->stream));
     BHR_HIP(hipStreamSynchronize(ctx->stream));

@@ -226,26 +226,27 @@ static void march_args(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, bool
     }
     a.sc.n_r = ctx->n_r;
     a.sc.n_phi = ctx->n_phi;
-    a.bg = ctx->d_bg;
-    a.disk = ctx->d_disk;
-    ctx->slots[ctx->active_slot].disk_wide = 0;          // the march's disk layer lies in [0, 1]
+    bhr_frame_slot &f = bhr_slot(ctx);
+    a.bg = f.d_bg;
+    a.disk = f.d_disk;
+    f.disk_wide = 0;          // the march's disk layer lies in [0, 1]
     a.diskp = nullptr;
     a.dp_yb = a.dp_gp = a.dp_g0 = 0;
     a.sum = nullptr;
-    if (ctx->bloom_split && ctx->d_pa && ctx->d_sum && !(flags & BHR_SKIP_BLOOM)) {      // split-f16 post-pass: the march feeds its H pass directly
+    if (f.frame_split && f.d_pa && f.d_sum && !(flags & BHR_SKIP_BLOOM)) {      // split-f16 post-pass: the march feeds its H pass directly
         bhr_split_geom g;
         bhr_split_geometry(ctx, &g);
-        a.diskp = (_Float16 *)ctx->d_pa;
+        a.diskp = (_Float16 *)f.d_pa;
         a.dp_yb = g.YB;
         a.dp_gp = g.GP;
         a.dp_g0 = g.g0;
-        a.sum = ctx->d_sum;
-        ctx->slots[ctx->active_slot].sum_valid = 1;
+        a.sum = f.d_sum;
+        f.sum_valid = 1;
     }
     // timed launches (bhr_render) count into their ring slot; group launches into the scalar
     const int slot = ctx->cur_slot;
     a.ray_steps = slot >= 0 ? ctx->d_steps_ring + (size_t)slot * BHR_STEP_CELL : ctx->d_ray_steps;
-    a.queue = ctx->d_queue;
+    a.queue = f.d_queue;
     a.dv2 = ctx->disk_source != BHR_DISK_TEXTURE ? ctx->d_dv2_params : nullptr;
     a.vol_absorption = ctx->vol_opts[0];
     a.vol_grazing_gain = ctx->vol_opts[1];
@@ -318,7 +319,7 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
 
     // ring cells are cleared ahead of time (at reset, then by the previous frame's last kernel)
     if (slot < 0 && first_part) BHR_HIP(hipMemsetAsync(a.ray_steps, 0, sizeof(unsigned long long) * BHR_STEP_CELL, ctx->stream));
-    if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(ctx->d_queue, 0, sizeof(unsigned int), ctx->stream));
+    if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(bhr_slot(ctx).d_queue, 0, sizeof(unsigned int), ctx->stream));
     // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
     if (first_part) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 0] : ctx->ev[0], ctx->stream));
     const MarchKernel k = march_kernel(ctx, a, part, math, flags, want_diff);
@@ -352,20 +353,19 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
 int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     const int k = ctx->ada_k, W = ctx->cfg.width, H = ctx->rows;
     const int math = bhr_resolve_math(ctx, flags);
-    const int slot_k = ctx->active_slot >= 0 && ctx->active_slot < BHR_MAX_FRAME_SLOTS ? ctx->active_slot : 0;
-    auto &l = ctx->ada[slot_k];
+    bhr_frame_slot &f = bhr_slot(ctx);
     const int32_t fine_tiles_x = (W * k + 7) / 8, cap = fine_tiles_x * ((H * k + 7) / 8);   // tiles of the fine frame
-    if (!l.d_list) {
+    if (!f.d_ada_list) {
         // for every factor: the buffers outlive a change of k, and ceil(k W / 8) ceil(k H / 8) <= W H for k <= 8
-        BHR_HIP(hipMalloc((void **)&l.d_list, 2 * (size_t)W * H * sizeof(int32_t)));
-        BHR_HIP(hipMalloc((void **)&l.d_mask, (size_t)W * H));
-        BHR_HIP(hipMalloc((void **)&l.d_counts, 64));
+        BHR_HIP(hipMalloc((void **)&f.d_ada_list, 2 * (size_t)W * H * sizeof(int32_t)));
+        BHR_HIP(hipMalloc((void **)&f.d_ada_mask, (size_t)W * H));
+        BHR_HIP(hipMalloc((void **)&f.d_ada_counts, 64));
     }
     if ((long long)cap > (long long)W * H) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: %d fine tiles for %d x %d pixels", cap, W, H);
-    BHR_HIP(hipMemsetAsync(l.d_counts, 0, 4 * sizeof(unsigned int), ctx->stream));
+    BHR_HIP(hipMemsetAsync(f.d_ada_counts, 0, 4 * sizeof(unsigned int), ctx->stream));
     BhrDetectArgs d;
-    d.bg = ctx->d_bg;
-    d.disk = ctx->d_disk;
+    d.bg = f.d_bg;
+    d.disk = f.d_disk;
     d.width = W;
     d.height = H;
     d.threshold = ctx->ada_threshold;
@@ -375,10 +375,10 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags)
     int32_t flag_tiles_x = fine_tiles_x;
     if (math == BHR_MATH_HYBRID) BHR_TRY(bhr_hybrid_fine_flags(ctx, cam, k, &d.flags, &flag_tiles_x));
     if (flag_tiles_x != fine_tiles_x) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: %d flag columns for %d tile columns", flag_tiles_x, fine_tiles_x);
-    d.mask = l.d_mask;
-    d.list = l.d_list;
+    d.mask = f.d_ada_mask;
+    d.list = f.d_ada_list;
     d.cap = cap;
-    d.counts = l.d_counts;
+    d.counts = f.d_ada_counts;
     {
         const int blocks = ((W + 7) / 8) * ((H + 7) / 8);            // a wave per 8 x 8 block of output pixels
         void *args[] = {&d};
@@ -393,10 +393,10 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags)
         march_args(ctx, cam, flags, fast, a);
         ctx->ss = 1;
         // a tile per wave, a grid for the list's capacity (every fine tile): waves beyond the list's length exit at once
-        a.tile_order = l.d_list + (size_t)which * cap;
+        a.tile_order = f.d_ada_list + (size_t)which * cap;
         a.n_list = cap;
-        a.fix_count = l.d_counts + which;
-        a.fix_list = (int32_t *)l.d_mask;                           // LIST kernels read it as the mask (march.hip: list_refined)
+        a.fix_count = f.d_ada_counts + which;
+        a.fix_list = (int32_t *)f.d_ada_mask;                           // LIST kernels read it as the mask (march.hip: list_refined)
         a.fix_cap = 0;
         if (a.n_tiles != cap) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: %d fine tiles, lists for %d", a.n_tiles, cap);
         const auto own = fast ? bhr_march_kernel_fast : bhr_march_kernel_strict;
@@ -418,7 +418,7 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags)
     }
     const int slot = ctx->cur_slot;
     if (slot >= 0 || ctx->group_time_march) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1], ctx->stream));
-    ctx->ada_last_slot = slot_k;
+    ctx->ada_last_slot = ctx->active_slot;
     ctx->ada_last_math = math;
     return BHR_OK;
 }

@@ -416,7 +416,7 @@ int32_t bhr_y4m_submit(bhr_y4m *s) {
     if (rc == BHR_OK) rc = bhr_ensure_outputs(ctx, BHR_OUT_F32);     // the conversion reads the f32 frame (a context that keeps only u8 rows gets it on demand)
     if (rc == BHR_OK) {
         dim3 block(32, 8), grid(((s->w >> 1) + 31) / 32, ((s->h >> 1) + 7) / 8);
-        hipLaunchKernelGGL(rgb_to_yuv420_kernel, grid, block, 0, ctx->stream, ctx->d_final, s->slots[slot].dev, s->w, s->h);
+        hipLaunchKernelGGL(rgb_to_yuv420_kernel, grid, block, 0, ctx->stream, bhr_slot(ctx).d_final, s->slots[slot].dev, s->w, s->h);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(s->slots[slot].host, s->slots[slot].dev, s->frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(s->slots[slot].ev, ctx->stream);
@@ -565,14 +565,14 @@ int32_t bhr_sink_submit(bhr_sink *s, const char *path) {
     if (rc == BHR_OK) rc = bhr_launch_quantize(ctx);
     if (rc == BHR_OK && s->on_device) {
         bhr_sink::Slot &sl = s->slots[slot];
-        rc = s->jpeg_quality ? bhr_launch_jpeg_encode(ctx, s->jpeg_quality, ctx->d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta)
-                             : bhr_launch_png_encode(ctx, ctx->d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta);
+        rc = s->jpeg_quality ? bhr_launch_jpeg_encode(ctx, s->jpeg_quality, bhr_slot(ctx).d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta)
+                             : bhr_launch_png_encode(ctx, bhr_slot(ctx).d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta);
         if (rc == BHR_OK) {
             e = hipMemcpyAsync(sl.h_meta, sl.d_meta, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipEventRecord(sl.ev, ctx->stream);
         }
     } else if (rc == BHR_OK) {
-        e = hipMemcpyAsync(s->slots[slot].host, ctx->d_final_u8, s->frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        e = hipMemcpyAsync(s->slots[slot].host, bhr_slot(ctx).d_final_u8, s->frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(s->slots[slot].ev, ctx->stream);
     }
     {
