@@ -18,6 +18,7 @@ FORCE_HYBRID, GATHER_U8, GROUP_SERIAL, GROUP_PIPELINED, GROUP_TIME_MARCH, GROUP_
 MATH_FAST, MATH_STRICT, MATH_HYBRID = 0, 1, 2
 LAYER_FINAL, LAYER_BG, LAYER_DISK, LAYER_BLUR = 0, 1, 2, 3
 OUTPUT_F32, OUTPUT_BLUR, OUTPUT_U8 = 1, 2, 4
+DITHER_NONE, DITHER_BLUE = 0, 1
 
 # every symbol include/bhr.h declares (tests check the .so exports exactly these)
 SYMBOLS = (
@@ -25,8 +26,9 @@ SYMBOLS = (
     "bhr_set_skybox", "bhr_skybox_add_glow", "bhr_skybox_build", "bhr_get_skybox", "bhr_set_disk_texture", "bhr_get_disk_texture", "bhr_get_disk_mip", "bhr_num_mip_levels",
     "bhr_bg_init", "bhr_generate_background", "bhr_set_entity_staging", "bhr_set_comp", "bhr_read_comp",
     "bhr_fill_comp_slice", "bhr_set_compose_stats", "bhr_compose_texture", "bhr_eval_noise", "bhr_render",
-    "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
+    "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_read_final_u16", "bhr_set_dither", "bhr_dither_matrix", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
     "bhr_stats_prepare", "bhr_stats_select", "bhr_stats_row_statistics",
+    "bhr_png_bound16", "bhr_png_encode16", "bhr_png_write16", "bhr_png16_device_bound", "bhr_png16_device_max_width", "bhr_png16_encode_device", "bhr_sink_create_png16",
     "bhr_png_bound", "bhr_png_encode", "bhr_png_write", "bhr_png_device_bound", "bhr_png_device_max_width", "bhr_png_encode_device", "bhr_png_device_menu",
     "bhr_jpeg_device_bound", "bhr_jpeg_restart_interval", "bhr_jpeg_tables", "bhr_jpeg_encode_device", "bhr_sink_create_jpeg",
     "bhr_sink_create", "bhr_sink_submit", "bhr_sink_drain",
@@ -125,6 +127,9 @@ def load() -> C.CDLL:
     lib.bhr_lens_flare.argtypes = [P]
     lib.bhr_lens_flare_sums.argtypes = [P, C.POINTER(C.c_double)]
     lib.bhr_read_final_u8.argtypes = [P, C.POINTER(C.c_uint8)]
+    lib.bhr_read_final_u16.argtypes = [P, C.POINTER(C.c_uint16)]
+    lib.bhr_set_dither.argtypes = [P, I32]
+    lib.bhr_dither_matrix.argtypes = [C.POINTER(C.c_uint16)]
     lib.bhr_get_counters.argtypes = [P, C.POINTER(Counters)]
     lib.bhr_timing_reset.argtypes = [P]
     lib.bhr_timing_dump.argtypes = [P, F, I32]
@@ -146,6 +151,14 @@ def load() -> C.CDLL:
     lib.bhr_png_bound.argtypes = [I32, I32]
     lib.bhr_png_encode.argtypes = [U8, I32, I32, I32, I32, U8, I64, C.POINTER(I64)]
     lib.bhr_png_write.argtypes = [C.c_char_p, U8, I32, I32, I32, I32]
+    U16 = C.POINTER(C.c_uint16)
+    lib.bhr_png_bound16.argtypes = [I32, I32]
+    lib.bhr_png_encode16.argtypes = [U16, I32, I32, I32, I32, U8, I64, C.POINTER(I64)]
+    lib.bhr_png_write16.argtypes = [C.c_char_p, U16, I32, I32, I32, I32]
+    lib.bhr_png16_device_bound.argtypes = [I32, I32]
+    lib.bhr_png16_device_max_width.argtypes = []
+    lib.bhr_png16_encode_device.argtypes = [P, U8, I64, C.POINTER(I64)]
+    lib.bhr_sink_create_png16.argtypes = [P, I32, I32, I32, C.POINTER(P)]
     lib.bhr_png_device_bound.argtypes = [I32, I32]
     lib.bhr_png_device_max_width.argtypes = []
     lib.bhr_png_encode_device.argtypes = [P, U8, I64, C.POINTER(I64)]
@@ -166,10 +179,13 @@ def load() -> C.CDLL:
     lib.bhr_y4m_close.argtypes = [P]
     for name in SYMBOLS:
         fn = getattr(lib, name)
-        if name not in ("bhr_last_error", "bhr_destroy", "bhr_sink_destroy", "bhr_png_bound", "bhr_png_device_bound", "bhr_jpeg_device_bound", "bhr_y4m_close"):
+        if name not in ("bhr_last_error", "bhr_destroy", "bhr_sink_destroy", "bhr_png_bound", "bhr_png_device_bound", "bhr_jpeg_device_bound", "bhr_y4m_close",
+                        "bhr_png_bound16", "bhr_png16_device_bound"):
             fn.restype = I32
     lib.bhr_png_bound.restype = I64
     lib.bhr_png_device_bound.restype = I64
+    lib.bhr_png_bound16.restype = I64
+    lib.bhr_png16_device_bound.restype = I64
     lib.bhr_jpeg_device_bound.restype = I64
     lib.bhr_sink_destroy.restype = None
     lib.bhr_y4m_close.restype = None

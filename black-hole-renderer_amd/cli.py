@@ -73,6 +73,12 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="--video: auto = PNG frames, and H.264 where an encoder exists (default); mjpeg = every frame is "
                         "JPEG-coded on the GPU and the frames are muxed into the MP4 as Motion-JPEG (no external encoder needed)")
     p.add_argument("--video_quality", type=int, default=90, help="--video_codec mjpeg: JPEG quality 1..100 (default: 90)")
+    p.add_argument("--bit_depth", type=int, default=8, choices=[8, 16],
+                   help="bits per sample of the PNG output: 8 (default), or 16 -- (uint16)(clip(x, 0, 1) * 65535), still images and "
+                        "--video frames alike (the yuv420p stream stays 8-bit); not with --dither blue or --video_codec mjpeg")
+    p.add_argument("--dither", type=str, default="none", choices=["none", "blue"],
+                   help="8-bit quantisation: none = truncation as the reference (default); blue = a 64x64 blue-noise threshold is "
+                        "added before the floor, so that smooth dark gradients come out as fine noise instead of bands")
     p.add_argument("--ignore_taichi_cache", action="store_true", help="accepted for compatibility; no effect")
     p.add_argument("--video", action="store_true", help="render frames and assemble a video")
     p.add_argument("--interactive", action="store_true", help="not available in this build (needs ti.GUI)")
@@ -125,6 +131,12 @@ def validate_args(args) -> None:
             raise ValueError("--supersample_threshold needs --supersample 2, 4 or 8")
         if getattr(args, "gpus", 1) > 1:
             raise ValueError("--supersample_threshold renders on one GPU: it does not combine with --gpus > 1")
+    if getattr(args, "bit_depth", 8) == 16 and getattr(args, "dither", "none") != "none":
+        raise ValueError("--bit_depth 16 is not dithered: --dither blue applies to 8-bit output")
+    if getattr(args, "bit_depth", 8) == 16 and getattr(args, "video_codec", "auto") == "mjpeg":
+        raise ValueError("--bit_depth 16 does not combine with --video_codec mjpeg: JPEG frames are 8-bit")
+    if getattr(args, "bit_depth", 8) == 16 and not args.video and not args.output.lower().endswith(".png"):
+        raise ValueError(f"--bit_depth 16 writes PNG files, got {args.output!r}")
     if getattr(args, "interactive", False):
         raise ValueError("--interactive needs the Taichi GUI and is not part of this build")
 
@@ -159,7 +171,8 @@ def main(argv=None) -> int:
                              resume=args.resume, disk_rotation_speed=args.disk_rotation_speed,
                              orbit_degrees=args.orbit_degrees, rank=rank, world=world, video_stream=args.video_stream,
                              png_level=(drivers.DEVICE if args.png_encoder == "device" else drivers.VIDEO_LEVEL),
-                             video_codec=args.video_codec, video_quality=args.video_quality)
+                             video_codec=args.video_codec, video_quality=args.video_quality, bit_depth=args.bit_depth,
+                             dither=args.dither)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -182,6 +195,6 @@ def main(argv=None) -> int:
         r_disk_outer=args.disk_outer_radius, disk_tilt=args.disk_tilt, lens_flare=args.lens_flare,
         anti_alias=args.anti_alias, aa_strength=args.aa_strength, disk_rotation_speed=args.disk_rotation_speed,
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
-        supersample_threshold=args.supersample_threshold)
-    drivers.save_image(img, args.output)
+        supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither)
+    drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

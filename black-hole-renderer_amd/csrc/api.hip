@@ -98,6 +98,7 @@ static void read_options(bhr_options *o) {
     o->mip_lds = num("BHR_MIP_LDS", 0) != 0;
     o->group_threads = num("BHR_GROUP_THREADS", -1);
     { const char *e = getenv("BHR_GROUP_SCHEDULE"); o->group_schedule = e && e[0] ? (e[0] == 's' ? 0 : 1) : -1; }
+    o->png16_menu = num("BHR_PNG16_MENU", 1) != 0;
 }
 
 int32_t alloc_slot(bhr_ctx *ctx, int k) {
@@ -152,7 +153,7 @@ int32_t ensure_bloom_buffers(bhr_ctx *ctx, int k, bool split) {
 
 void free_slot(bhr_ctx *ctx, int k) {
     bhr_frame_slot &f = ctx->slots[k];
-    void *bufs[] = {f.d_bg, f.d_disk, f.d_blur, f.d_final, f.d_final_u8, f.d_hblur_base, f.d_pa, f.d_pb, f.d_sum, f.d_queue,
+    void *bufs[] = {f.d_bg, f.d_disk, f.d_blur, f.d_final, f.d_final_u8, f.d_final_u16, f.d_hblur_base, f.d_pa, f.d_pb, f.d_sum, f.d_queue,
                     f.d_glow_hw, f.d_glow_wh, f.d_flare_c0, f.d_flare_c12, f.d_flare_sums, f.d_ada_list, f.d_ada_mask, f.d_ada_counts};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -228,6 +229,16 @@ int32_t bhr_ensure_outputs(bhr_ctx *ctx, uint32_t need) {
     bhr_frame_slot &f = bhr_slot(ctx);
     uint32_t missing = need & ~f.have;
     if (!missing) return BHR_OK;
+    // the quantisers of their own (quantize.hip) read the f32 frame: the 16-bit rows always, the u8 rows while dither is on
+    const uint32_t from_f32 = missing & (BHR_OUT_U16 | (ctx->dither ? BHR_OUT_U8 : 0u));
+    if (from_f32) {
+        BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_F32));
+        if (from_f32 & BHR_OUT_U16) BHR_TRY(bhr_launch_quantize_u16(ctx));
+        if (from_f32 & BHR_OUT_U8) BHR_TRY(bhr_launch_quantize_dither(ctx));
+        f.have |= from_f32;
+        missing = need & ~f.have;
+        if (!missing) return BHR_OK;
+    }
     if ((missing & BHR_OUT_U8) && ((f.have | missing) & BHR_OUT_F32)) {
         // the f32 frame is (or is about to be) the authority -- it may carry a lens flare the V pass knows nothing of
         if (missing & BHR_OUT_F32) BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_F32));
@@ -494,7 +505,7 @@ void bhr_destroy(bhr_ctx *ctx) {
     void *bufs[] = {ctx->d_skybox,
                     ctx->d_wtab, ctx->d_wsum_h, ctx->d_wsum_v, ctx->d_ray_steps, ctx->d_noise_in,
                     ctx->d_noise_out, ctx->d_steps_ring, ctx->d_steps_fold, ctx->d_pool, ctx->d_pairs, ctx->d_stats_scratch, ctx->d_wext, ctx->d_w16, ctx->d_dv2_params,
-                    ctx->d_flare_prog, ctx->d_tile_order, ctx->d_row_steps, ctx->d_gather};
+                    ctx->d_flare_prog, ctx->d_tile_order, ctx->d_row_steps, ctx->d_gather, ctx->d_dither};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -725,6 +736,7 @@ int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     // frame, so a flared frame keeps it and quantises afterwards
     uint32_t want = ctx->out_want;
     if (flags & BHR_LENS_FLARE) want = (want | BHR_OUT_F32) & ~BHR_OUT_U8;
+    if (ctx->dither) want = (want | BHR_OUT_F32) & ~BHR_OUT_U8;      // dithered rows: the same route (quantize.hip)
     const int32_t rc_v = bhr_frame_post(ctx, with_bloom, want);
     ctx->v_zero_cell = nullptr;
     BHR_TRY(rc_v);
@@ -736,6 +748,8 @@ int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
         BHR_TRY(bhr_launch_flare_sums(ctx));
         BHR_TRY(bhr_launch_flare_apply(ctx, nullptr));
         if (ctx->out_want & BHR_OUT_U8) BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_U8));
+    } else if (ctx->dither && (ctx->out_want & BHR_OUT_U8)) {
+        BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_U8));
     }
     BHR_HIP(hipEventRecord(ctx->ring_ev[ring * 3 + 2], f.stream));
     BHR_HIP(hipEventRecord(f.done, f.stream));
@@ -916,7 +930,7 @@ int32_t bhr_write_layer(bhr_ctx *ctx, int32_t layer, const float *in) {
         }
     }
     switch (layer) {
-        case BHR_LAYER_FINAL: dst = f.d_final; f.have = (f.have | BHR_OUT_F32) & ~BHR_OUT_U8; break;   // the u8 rows follow the written frame
+        case BHR_LAYER_FINAL: dst = f.d_final; f.have = (f.have | BHR_OUT_F32) & ~(BHR_OUT_U8 | BHR_OUT_U16); break;   // the u8 / u16 rows follow the written frame
         case BHR_LAYER_BG: dst = f.d_bg; f.sum_valid = 0; break;      // a later V pass adds the two layers itself
         case BHR_LAYER_DISK: dst = f.d_disk; f.sum_valid = 0; f.disk_wide = wide; break;
         case BHR_LAYER_BLUR: dst = f.d_blur; f.have |= BHR_OUT_BLUR; break;
@@ -996,6 +1010,12 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     else if (n == "mip_lds") o.mip_lds = v != 0;
     else if (n == "group_threads") o.group_threads = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "group_schedule") o.group_schedule = v < 0 ? -1 : (v ? 1 : 0);
+    else if (n == "png16_menu") {   // the tables are rebuilt at the next encode; no encode may be running on the old ones
+        BHR_TRY(bhr_enter(ctx));
+        BHR_HIP(hipStreamSynchronize(ctx->scene_stream));
+        o.png16_menu = v != 0;
+        bhr_png_dev_free(ctx);
+    }
     else return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: unknown option '%s'", name);
     return BHR_OK;
 }
@@ -1067,7 +1087,7 @@ int32_t bhr_lens_flare(bhr_ctx *ctx) {
         return bhr_fail(BHR_ERR_INVALID, "bhr_lens_flare: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
     BHR_TRY(use_device(ctx));
     BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_F32));
-    bhr_slot(ctx).have &= ~BHR_OUT_U8;          // the u8 rows follow the flared frame
+    bhr_slot(ctx).have &= ~(BHR_OUT_U8 | BHR_OUT_U16);          // the u8 / u16 rows follow the flared frame
     BHR_TRY(bhr_launch_flare_glow(ctx, true));
     BHR_TRY(bhr_launch_flare_sums(ctx));
     return bhr_launch_flare_apply(ctx, nullptr);

@@ -154,7 +154,9 @@ struct BhrDetectArgs {
 // what a frame's V pass stores (bhr_launch_bloom_v_rows); bhr_ensure_outputs re-runs it for layers nobody asked for up front
 #define BHR_OUT_F32 1u    // clip(bg + disk + blur) as f32: what TaichiRenderer.render() returns
 #define BHR_OUT_BLUR 2u   // blur_field
-#define BHR_OUT_U8 4u     // the frame quantised as save_image does (render.py:423)
+#define BHR_OUT_U8 4u     // the frame quantised as save_image does (render.py:423); blue-noise dithered while bhr_set_dither(1)
+// internal only (no bhr_set_outputs bit): the 16-bit rows, always made on demand from the f32 frame (quantize.hip)
+#define BHR_OUT_U16 8u
 
 // The library's environment switches, read ONCE by bhr_create (nothing on the bhr_render path calls getenv).
 struct bhr_options {
@@ -171,6 +173,7 @@ struct bhr_options {
     int32_t mip_lds;            // BHR_MIP_LDS=1: anti-aliased fast frames stage the coarse mip levels in LDS
     int32_t group_threads;      // BHR_GROUP_THREADS: -1 by device layout (default), 0 / 1 one submitting thread / one per tile
     int32_t group_schedule;     // BHR_GROUP_SCHEDULE: -1 by flags (default), 0 serial, 1 pipelined
+    int32_t png16_menu;         // BHR_PNG16_MENU: 1 (default) the 16-bit device PNG codes from its own menu, 0 from the 8-bit one (A/B runs)
 };
 
 // geometry of a context's split-f16 bloom buffers (bloom.hip)
@@ -202,6 +205,7 @@ struct bhr_frame_slot {
     int32_t sum_valid;
     int32_t disk_wide;         // the DISK layer is a caller's (bhr_write_layer) with a value above BHR_SPLIT_DISK_MAX; a march clears it
     uint8_t *d_final_u8;       // (rows, W, 3)
+    uint16_t *d_final_u16;     // (rows, W, 3) 16-bit rows, native endian (bhr_read_final_u16, the 16-bit PNG paths); on first use
     uint32_t have;             // BHR_OUT_* layers of the slot's last frame that are in memory (the V pass stores what was asked for; the rest on demand)
     // the post-pass of the slot's frame, set by bhr_frame_begin: frame_split 0 exact f32 kernels (strict), 1 split-f16
     // matrix-core kernels (fast / hybrid); bhr_ensure_outputs re-runs its V pass
@@ -290,6 +294,10 @@ struct bhr_ctx {
     unsigned short *d_w16;     // split-f16 weight table: 3 channels x 2 halves x 8 shifted copies (bloom.hip: bloom_tables_kernel)
     int32_t mip_lds_from;      // first mip level the last anti-aliased fast march staged in LDS (BHR_MIP_LDS), -1: none
     int32_t split_ok;          // the context's radius fits the split kernels' table (R <= 176)
+    // bhr_set_dither: 1 = the u8 rows are the blue-noise dithered quantisation of the f32 frame (quantize.hip); the frame then
+    // takes the route of a flared frame: the V pass keeps f32, the rows are quantised afterwards
+    int32_t dither;
+    uint16_t *d_dither;        // the 64 x 64 rank matrix on the device, on first use
     uint32_t out_want;         // BHR_OUT_* the frames of this context store (bhr_set_outputs; default: the f32 frame)
     // rows of this block that neighbouring row blocks need for their V pass: the H pass writes them straight into those
     // blocks' planes (set by group.hip for the duration of a group / tile render)
@@ -434,7 +442,12 @@ int32_t bhr_launch_flare_apply(bhr_ctx *ctx, const double *sums);    // sums == 
 int32_t bhr_launch_quantize(bhr_ctx *ctx);                           // api.hip: the frame's u8 rows, on the stream (from the V pass, or FINAL -> u8)
 // png_device.hip: (rows, W, 3) u8 at d_rgb -> PNG file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
 int32_t bhr_launch_png_encode(bhr_ctx *ctx, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
+// the same for the (rows, W, 3) u16 rows at d_rgb16 (native endian): a 16-bit PNG, samples big-endian in the file
+int32_t bhr_launch_png16_encode(bhr_ctx *ctx, const uint16_t *d_rgb16, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
 void bhr_png_dev_free(bhr_ctx *ctx);
+// quantize.hip: the two quantisers that read the f32 FINAL frame, on ctx->stream (bhr_ensure_outputs calls them)
+int32_t bhr_launch_quantize_u16(bhr_ctx *ctx);      // d_final -> d_final_u16 (allocated here on first use)
+int32_t bhr_launch_quantize_dither(bhr_ctx *ctx);   // d_final -> d_final_u8, blue-noise dithered
 // jpeg_device.hip: (rows, W, 3) u8 at d_rgb -> JFIF file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
 int32_t bhr_launch_jpeg_encode(bhr_ctx *ctx, int32_t quality, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
 void bhr_jpeg_dev_free(bhr_ctx *ctx);

@@ -214,7 +214,7 @@ int32_t flare_pass(bhr_ctx **ctxs, int n, const int32_t *live) {
         if (live && !live[k]) continue;
         BHR_HIP(hipSetDevice(ctxs[k]->cfg.device));
         BHR_TRY(bhr_launch_flare_apply(ctxs[k], tot));
-        bhr_slot(ctxs[k]).have &= ~BHR_OUT_U8;
+        bhr_slot(ctxs[k]).have &= ~(BHR_OUT_U8 | BHR_OUT_U16);
     }
     return BHR_OK;
 }
@@ -483,6 +483,9 @@ int32_t bhr_group_render_subset(bhr_ctx **ctxs, int32_t n, const bhr_camera *cam
     for (int k = 0; k < n; ++k) {
         if (!ctxs[k]) return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: null ctx %d", k);
         if (ctxs[k]->ss > 1 || ctxs[k]->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d is supersampled (row blocks render one sample per pixel)", k);
+        if (ctxs[k]->dither && (flags & BHR_GATHER_U8))
+            return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d dithers (bhr_set_dither) and BHR_GATHER_U8 stores the undithered rows from inside the "
+                            "V pass; gather the f32 frame, or switch dither off", k);
         if (ctxs[k]->cfg.width != W || ctxs[k]->cfg.height != H || ctxs[k]->cfg.row0 != expect)
             return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d does not continue the image (row0 %d, expected %d)", k, ctxs[k]->cfg.row0, expect);
         expect = ctxs[k]->cfg.row1;
@@ -725,6 +728,8 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
 int32_t bhr_tile_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: bad argument");
     if (ctx->ss > 1 || ctx->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the context is supersampled (row blocks render one sample per pixel)");
+    if (ctx->dither)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the context dithers (bhr_set_dither) and a tile stores its u8 rows from inside the V pass; switch dither off");
     TilePipe *p = (TilePipe *)ctx->pipe;
     if (!p || !p->linked) return bhr_fail(BHR_ERR_STATE, "bhr_tile_render: call bhr_tile_connect first (a failed frame breaks the link: connect again)");
     if (flags & BHR_LENS_FLARE) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the lens flare needs the one-process path (bhr_group_render)");

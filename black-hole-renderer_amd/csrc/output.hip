@@ -35,19 +35,20 @@ size_t put_chunk(uint8_t *out, const char type[4], const uint8_t *data, uint32_t
     return (size_t)len + 12;
 }
 
-// Filter one row (bpp = 3) with the type that minimises the sum of absolute signed residuals -- the
+// Filter one row (BPP = 3 bytes per pixel, or 6 for 16-bit samples) with the type that minimises the sum of absolute signed residuals -- the
 // heuristic of the PNG specification (12.8).  dst gets the filter byte + the filtered row.  `up` is the
 // previous row or a row of zeros; the loops are branch-free so that the compiler vectorises them.
+template <int BPP>
 void filter_row(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ up, int nbytes, uint8_t *__restrict__ dst,
                 uint8_t *__restrict__ scratch) {
     uint8_t *cand[5];
     for (int f = 0; f < 5; ++f) cand[f] = scratch + (size_t)f * nbytes;
-    const int head = nbytes < 3 ? nbytes : 3;
+    const int head = nbytes < BPP ? nbytes : BPP;
     memcpy(cand[0], cur, nbytes);
     {
         uint8_t *o = cand[1];
         for (int i = 0; i < head; ++i) o[i] = cur[i];
-        for (int i = 3; i < nbytes; ++i) o[i] = (uint8_t)(cur[i] - cur[i - 3]);
+        for (int i = BPP; i < nbytes; ++i) o[i] = (uint8_t)(cur[i] - cur[i - BPP]);
     }
     {
         uint8_t *o = cand[2];
@@ -56,13 +57,13 @@ void filter_row(const uint8_t *__restrict__ cur, const uint8_t *__restrict__ up,
     {
         uint8_t *o = cand[3];
         for (int i = 0; i < head; ++i) o[i] = (uint8_t)(cur[i] - (up[i] >> 1));
-        for (int i = 3; i < nbytes; ++i) o[i] = (uint8_t)(cur[i] - (((int)cur[i - 3] + (int)up[i]) >> 1));
+        for (int i = BPP; i < nbytes; ++i) o[i] = (uint8_t)(cur[i] - (((int)cur[i - BPP] + (int)up[i]) >> 1));
     }
     {
         uint8_t *o = cand[4];
         for (int i = 0; i < head; ++i) o[i] = (uint8_t)(cur[i] - up[i]);          // paeth(0, b, 0) = b
-        for (int i = 3; i < nbytes; ++i) {
-            const int a = cur[i - 3], b = up[i], c = up[i - 3];
+        for (int i = BPP; i < nbytes; ++i) {
+            const int a = cur[i - BPP], b = up[i], c = up[i - BPP];
             const int p = a + b - c;
             const int pa = p > a ? p - a : a - p, pb = p > b ? p - b : b - p, pc = p > c ? p - c : c - p;
             const int pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
@@ -93,12 +94,13 @@ struct Band {
 
 // Filter + raw-deflate rows [r0, r1).  Non-final bands end on a sync flush (byte aligned, no final bit),
 // so that the bands concatenate into one valid deflate stream.
+template <int BPP>
 void deflate_band(const uint8_t *rgb, int w, int r0, int r1, int level, bool last, Band *band) {
-    const int nbytes = 3 * w;
+    const int nbytes = BPP * w;
     const size_t line = (size_t)nbytes + 1;
     std::vector<uint8_t> filt((size_t)(r1 - r0) * line), scratch((size_t)5 * nbytes), zero_row((size_t)nbytes, 0);
     for (int r = r0; r < r1; ++r)
-        filter_row(rgb + (size_t)r * nbytes, r > 0 ? rgb + (size_t)(r - 1) * nbytes : zero_row.data(), nbytes,
+        filter_row<BPP>(rgb + (size_t)r * nbytes, r > 0 ? rgb + (size_t)(r - 1) * nbytes : zero_row.data(), nbytes,
                    filt.data() + (size_t)(r - r0) * line, scratch.data());
     band->raw_len = filt.size();
     {   // adler32 takes uInt lengths
@@ -140,10 +142,12 @@ void deflate_band(const uint8_t *rgb, int w, int r0, int r1, int level, bool las
     band->comp.resize(out_done);
 }
 
-int32_t encode_png(const uint8_t *rgb, int w, int h, int level, int threads, uint8_t *out, int64_t cap, int64_t *out_len) {
+// rgb: the scanlines as the file holds them -- BPP = 3: u8 samples; 6: 16-bit samples, big-endian
+template <int BPP>
+int32_t encode_png_bytes(const uint8_t *rgb, int w, int h, int level, int threads, uint8_t *out, int64_t cap, int64_t *out_len) {
     if (!rgb || !out || !out_len || w <= 0 || h <= 0) return bhr_fail(BHR_ERR_INVALID, "bhr_png_encode: bad argument");
     if (level < 0 || level > 9) return bhr_fail(BHR_ERR_INVALID, "bhr_png_encode: zlib level %d outside 0..9", level);
-    if (cap < bhr_png_bound(w, h)) return bhr_fail(BHR_ERR_INVALID, "bhr_png_encode: buffer smaller than bhr_png_bound");
+    if (cap < (BPP == 6 ? bhr_png_bound16(w, h) : bhr_png_bound(w, h))) return bhr_fail(BHR_ERR_INVALID, "bhr_png_encode: buffer smaller than bhr_png_bound");
     if (threads < 1) threads = 1;
     if (threads > 64) threads = 64;
     int bands = threads;
@@ -152,8 +156,8 @@ int32_t encode_png(const uint8_t *rgb, int w, int h, int level, int threads, uin
     std::vector<std::thread> pool;
     for (int b = 0; b < bands; ++b) {
         const int r0 = (int)((int64_t)h * b / bands), r1 = (int)((int64_t)h * (b + 1) / bands);
-        if (b + 1 < bands) pool.emplace_back(deflate_band, rgb, w, r0, r1, level, false, &band[b]);
-        else deflate_band(rgb, w, r0, r1, level, true, &band[b]);
+        if (b + 1 < bands) pool.emplace_back(deflate_band<BPP>, rgb, w, r0, r1, level, false, &band[b]);
+        else deflate_band<BPP>(rgb, w, r0, r1, level, true, &band[b]);
     }
     for (auto &t : pool) t.join();
     for (int b = 0; b < bands; ++b)
@@ -166,7 +170,7 @@ int32_t encode_png(const uint8_t *rgb, int w, int h, int level, int threads, uin
     uint8_t ihdr[13];
     put32(ihdr, (uint32_t)w);
     put32(ihdr + 4, (uint32_t)h);
-    ihdr[8] = 8; ihdr[9] = 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;   // 8-bit, colour type 2 (RGB), no interlace
+    ihdr[8] = BPP == 6 ? 16 : 8; ihdr[9] = 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;   // 8 or 16 bit, colour type 2 (RGB), no interlace
     p += put_chunk(p, "IHDR", ihdr, 13);
 
     // zlib stream = 2-byte header + the spliced raw deflate bands + adler32 of all filtered bytes
@@ -195,6 +199,22 @@ int32_t encode_png(const uint8_t *rgb, int w, int h, int level, int threads, uin
     return BHR_OK;
 }
 
+int32_t encode_png(const uint8_t *rgb, int w, int h, int level, int threads, uint8_t *out, int64_t cap, int64_t *out_len) {
+    return encode_png_bytes<3>(rgb, w, h, level, threads, out, cap, out_len);
+}
+
+// native-endian u16 samples -> the file's big-endian bytes, then the same encoder at six bytes per pixel
+int32_t encode_png16(const uint16_t *rgb, int w, int h, int level, int threads, uint8_t *out, int64_t cap, int64_t *out_len) {
+    if (!rgb || !out || !out_len || w <= 0 || h <= 0) return bhr_fail(BHR_ERR_INVALID, "bhr_png_encode16: bad argument");
+    const size_t n = (size_t)w * h * 3;
+    std::vector<uint8_t> be(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        be[2 * i] = (uint8_t)(rgb[i] >> 8);
+        be[2 * i + 1] = (uint8_t)rgb[i];
+    }
+    return encode_png_bytes<6>(be.data(), w, h, level, threads, out, cap, out_len);
+}
+
 int32_t write_file_atomic(const char *path, const uint8_t *data, size_t len) {
     const std::string tmp = std::string(path) + ".tmp";
     FILE *f = fopen(tmp.c_str(), "wb");
@@ -214,6 +234,7 @@ struct bhr_sink {
     size_t frame_bytes = 0;
     bool on_device = false;        // level BHR_PNG_DEVICE, or a JPEG sink: the slot receives finished file bytes
     int jpeg_quality = 0;          // 1..100: a sink made by bhr_sink_create_jpeg (jpeg_device.hip); 0: PNG
+    int bit_depth = 8;             // 16: a sink made by bhr_sink_create_png16: the context's u16 rows, 16-bit PNG files
     size_t host_bytes = 0;         // size of a slot's pinned buffer: the raw frame, or the bound of the device encoder
     struct Slot {
         uint8_t *host = nullptr;
@@ -236,7 +257,7 @@ struct bhr_sink {
 
     void work() {
         (void)hipSetDevice(ctx->cfg.device);
-        std::vector<uint8_t> png(on_device ? 0 : (size_t)bhr_png_bound(w, h));
+        std::vector<uint8_t> png(on_device ? 0 : (size_t)(bit_depth == 16 ? bhr_png_bound16(w, h) : bhr_png_bound(w, h)));
         hipStream_t copy_stream = nullptr;          // device encoder: each worker fetches exactly the bytes of its file
         if (on_device) (void)hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking);
         for (;;) {
@@ -264,7 +285,9 @@ struct bhr_sink {
                 }
                 if (rc == BHR_OK) rc = write_file_atomic(job.path.c_str(), sl.host, (size_t)len);
             } else {
-                if (rc == BHR_OK) rc = encode_png(sl.host, w, h, level, 1, png.data(), (int64_t)png.size(), &len);
+                if (rc == BHR_OK)
+                    rc = bit_depth == 16 ? encode_png16((const uint16_t *)sl.host, w, h, level, 1, png.data(), (int64_t)png.size(), &len)
+                                         : encode_png(sl.host, w, h, level, 1, png.data(), (int64_t)png.size(), &len);
                 if (rc == BHR_OK) rc = write_file_atomic(job.path.c_str(), png.data(), (size_t)len);
             }
             {
@@ -300,6 +323,29 @@ __global__ void rgb_to_yuv420_kernel(const float *__restrict__ rgb, uint8_t *__r
             const int x = 2 * bx + dx, y = 2 * by + dy;
             const float *p = rgb + ((size_t)y * w + x) * 3;
             const int r = q8(p[0]), g = q8(p[1]), b = q8(p[2]);
+            Y[(size_t)y * w + x] = (uint8_t)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16);
+            sr += r; sg += g; sb += b;
+        }
+    const int r = (sr + 2) >> 2, g = (sg + 2) >> 2, b = (sb + 2) >> 2;
+    U[(size_t)by * cw + bx] = (uint8_t)(((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128);
+    V[(size_t)by * cw + bx] = (uint8_t)(((112 * r - 94 * g - 18 * b + 128) >> 8) + 128);
+}
+
+// The same conversion from the context's u8 rows: the stream of a dithering context (bhr_set_dither) carries the
+// dithered frame, which only exists as those rows.
+__global__ void u8_to_yuv420_kernel(const uint8_t *__restrict__ rgb, uint8_t *__restrict__ out, int w, int h) {
+    const int bx = blockIdx.x * blockDim.x + threadIdx.x, by = blockIdx.y * blockDim.y + threadIdx.y;
+    const int cw = w >> 1, ch = h >> 1;
+    if (bx >= cw || by >= ch) return;
+    uint8_t *Y = out, *U = out + (size_t)w * h, *V = U + (size_t)cw * ch;
+    int sr = 0, sg = 0, sb = 0;
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            const int x = 2 * bx + dx, y = 2 * by + dy;
+            const uint8_t *p = rgb + ((size_t)y * w + x) * 3;
+            const int r = p[0], g = p[1], b = p[2];
             Y[(size_t)y * w + x] = (uint8_t)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16);
             sr += r; sg += g; sb += b;
         }
@@ -413,10 +459,14 @@ int32_t bhr_y4m_submit(bhr_y4m *s) {
     bhr_ctx *ctx = s->ctx;
     int32_t rc = bhr_enter_frame(ctx);       // the stream that rendered the last frame (behind its post-passes)
     hipError_t e = hipSuccess;
-    if (rc == BHR_OK) rc = bhr_ensure_outputs(ctx, BHR_OUT_F32);     // the conversion reads the f32 frame (a context that keeps only u8 rows gets it on demand)
+    // the conversion reads the f32 frame (a context that keeps only u8 rows gets it on demand); with dither on, the dithered u8 rows
+    if (rc == BHR_OK) rc = bhr_ensure_outputs(ctx, ctx->dither ? BHR_OUT_U8 : BHR_OUT_F32);
     if (rc == BHR_OK) {
         dim3 block(32, 8), grid(((s->w >> 1) + 31) / 32, ((s->h >> 1) + 7) / 8);
-        hipLaunchKernelGGL(rgb_to_yuv420_kernel, grid, block, 0, ctx->stream, bhr_slot(ctx).d_final, s->slots[slot].dev, s->w, s->h);
+        if (ctx->dither)
+            hipLaunchKernelGGL(u8_to_yuv420_kernel, grid, block, 0, ctx->stream, bhr_slot(ctx).d_final_u8, s->slots[slot].dev, s->w, s->h);
+        else
+            hipLaunchKernelGGL(rgb_to_yuv420_kernel, grid, block, 0, ctx->stream, bhr_slot(ctx).d_final, s->slots[slot].dev, s->w, s->h);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(s->slots[slot].host, s->slots[slot].dev, s->frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(s->slots[slot].ev, ctx->stream);
@@ -485,6 +535,26 @@ int32_t bhr_png_encode(const uint8_t *rgb, int32_t w, int32_t h, int32_t level, 
     return encode_png(rgb, w, h, level, threads, out, cap, out_len);
 }
 
+int64_t bhr_png_bound16(int32_t w, int32_t h) {
+    if (w <= 0 || h <= 0) return 0;
+    const int64_t raw = (int64_t)h * (6 * (int64_t)w + 1);
+    return raw + raw / 128 + 65536;
+}
+
+int32_t bhr_png_encode16(const uint16_t *rgb, int32_t w, int32_t h, int32_t level, int32_t threads, uint8_t *out, int64_t cap,
+                         int64_t *out_len) {
+    return encode_png16(rgb, w, h, level, threads, out, cap, out_len);
+}
+
+int32_t bhr_png_write16(const char *path, const uint16_t *rgb, int32_t w, int32_t h, int32_t level, int32_t threads) {
+    if (!path) return bhr_fail(BHR_ERR_INVALID, "bhr_png_write16: null path");
+    if (w <= 0 || h <= 0) return bhr_fail(BHR_ERR_INVALID, "bhr_png_write16: bad size %dx%d", w, h);
+    std::vector<uint8_t> png((size_t)bhr_png_bound16(w, h));
+    int64_t len = 0;
+    BHR_TRY(encode_png16(rgb, w, h, level, threads, png.data(), (int64_t)png.size(), &len));
+    return write_file_atomic(path, png.data(), (size_t)len);
+}
+
 int32_t bhr_png_write(const char *path, const uint8_t *rgb, int32_t w, int32_t h, int32_t level, int32_t threads) {
     if (!path) return bhr_fail(BHR_ERR_INVALID, "bhr_png_write: null path");
     if (w <= 0 || h <= 0) return bhr_fail(BHR_ERR_INVALID, "bhr_png_write: bad size %dx%d", w, h);
@@ -497,7 +567,8 @@ int32_t bhr_png_write(const char *path, const uint8_t *rgb, int32_t w, int32_t h
 }  // extern "C"
 
 // A sink of either codec: jpeg_quality 0 = PNG at `level`, 1..100 = JPEG on the device (level is BHR_PNG_DEVICE then).
-static int32_t sink_create(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t level, int32_t jpeg_quality, bhr_sink **out) {
+static int32_t sink_create(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t level, int32_t jpeg_quality, bhr_sink **out,
+                           int32_t bit_depth = 8) {
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     bhr_sink *s = new bhr_sink();
     s->ctx = ctx;
@@ -506,9 +577,11 @@ static int32_t sink_create(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t
     s->level = level;
     s->jpeg_quality = jpeg_quality;
     s->on_device = level == BHR_PNG_DEVICE;
-    s->frame_bytes = (size_t)s->w * s->h * 3;
+    s->bit_depth = bit_depth;
+    s->frame_bytes = (size_t)s->w * s->h * 3 * (bit_depth == 16 ? 2 : 1);
     s->host_bytes = jpeg_quality ? (size_t)bhr_jpeg_device_bound(s->w, s->h)
-                                 : (s->on_device ? (size_t)bhr_png_device_bound(s->w, s->h) : s->frame_bytes);
+                                 : (s->on_device ? (size_t)(bit_depth == 16 ? bhr_png16_device_bound(s->w, s->h) : bhr_png_device_bound(s->w, s->h))
+                                                 : s->frame_bytes);
     s->slots.resize(slots);
     for (int k = 0; k < slots; ++k) {
         hipError_t e = hipHostMalloc((void **)&s->slots[k].host, s->host_bytes, hipHostMallocDefault);
@@ -540,6 +613,15 @@ int32_t bhr_sink_create(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t le
     return sink_create(ctx, slots, workers, level, 0, out);
 }
 
+int32_t bhr_sink_create_png16(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t level, bhr_sink **out) {
+    if (!ctx || !out || slots < 1 || slots > 256 || workers < 1 || workers > 256 || level < BHR_PNG_DEVICE || level > 9)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_sink_create_png16: bad argument (slots %d, workers %d, level %d)", slots, workers, level);
+    if (level == BHR_PNG_DEVICE && ctx->cfg.width > bhr_png16_device_max_width())
+        return bhr_fail(BHR_ERR_INVALID, "bhr_sink_create_png16: the 16-bit device PNG encoder takes frames up to %d pixels wide, this one has %d; "
+                        "use a zlib level (host encoder)", bhr_png16_device_max_width(), ctx->cfg.width);
+    return sink_create(ctx, slots, workers, level, 0, out, 16);
+}
+
 int32_t bhr_sink_create_jpeg(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t quality, bhr_sink **out) {
     if (!ctx || !out || slots < 1 || slots > 256 || workers < 1 || workers > 256 || quality < 1 || quality > 100)
         return bhr_fail(BHR_ERR_INVALID, "bhr_sink_create_jpeg: bad argument (slots %d, workers %d, quality %d)", slots, workers, quality);
@@ -562,17 +644,20 @@ int32_t bhr_sink_submit(bhr_sink *s, const char *path) {
     bhr_ctx *ctx = s->ctx;
     hipError_t e = hipSuccess;
     int32_t rc = bhr_enter_frame(ctx);      // quantise, encode and copy ride the stream that rendered the frame
-    if (rc == BHR_OK) rc = bhr_launch_quantize(ctx);
+    const bool deep = s->bit_depth == 16;
+    if (rc == BHR_OK) rc = deep ? bhr_ensure_outputs(ctx, BHR_OUT_U16) : bhr_launch_quantize(ctx);
     if (rc == BHR_OK && s->on_device) {
         bhr_sink::Slot &sl = s->slots[slot];
-        rc = s->jpeg_quality ? bhr_launch_jpeg_encode(ctx, s->jpeg_quality, bhr_slot(ctx).d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta)
+        rc = deep ? bhr_launch_png16_encode(ctx, bhr_slot(ctx).d_final_u16, sl.dev, (int64_t)s->host_bytes, sl.d_meta) :
+             s->jpeg_quality ? bhr_launch_jpeg_encode(ctx, s->jpeg_quality, bhr_slot(ctx).d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta)
                              : bhr_launch_png_encode(ctx, bhr_slot(ctx).d_final_u8, sl.dev, (int64_t)s->host_bytes, sl.d_meta);
         if (rc == BHR_OK) {
             e = hipMemcpyAsync(sl.h_meta, sl.d_meta, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipEventRecord(sl.ev, ctx->stream);
         }
     } else if (rc == BHR_OK) {
-        e = hipMemcpyAsync(s->slots[slot].host, bhr_slot(ctx).d_final_u8, s->frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        const void *rows = deep ? (const void *)bhr_slot(ctx).d_final_u16 : (const void *)bhr_slot(ctx).d_final_u8;
+        e = hipMemcpyAsync(s->slots[slot].host, rows, s->frame_bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(s->slots[slot].ev, ctx->stream);
     }
     {

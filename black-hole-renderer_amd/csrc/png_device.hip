@@ -61,14 +61,14 @@ struct RowPlan {
 };
 
 struct PngDev {
-    PngTables *d_tab = nullptr;
+    PngTables *d_tab[2] = {nullptr, nullptr};   // [0] the 8-bit encoder's tables, [1] the 16-bit one's (its own menu and IHDR)
     // scanline plans and chunk offsets, one set per frame slot: encodes of successive frames run on different streams
     RowPlan *d_plan[BHR_MAX_FRAME_SLOTS] = {nullptr, nullptr};
     uint32_t *d_offs[BHR_MAX_FRAME_SLOTS] = {nullptr, nullptr};
     uint32_t *d_meta = nullptr;    // [0] file length, [1] error (1: output buffer too small), [2] adler
     int32_t plan_rows = 0;
-    int32_t head_w = 0, head_h = 0;
-    bool lds_attr = false;         // large dynamic LDS enabled for the kernels on this context's device
+    int32_t head_w[2] = {0, 0}, head_h[2] = {0, 0};
+    bool lds_attr[2] = {false, false};   // large dynamic LDS enabled for the 8-bit / 16-bit kernels on this context's device
     uint8_t *d_out = nullptr;      // scratch for bhr_png_encode_device
     int64_t out_cap = 0;
 };
@@ -194,12 +194,19 @@ uint32_t multmodp_host(uint32_t a, uint32_t b) {
     return p;
 }
 
-bool fill_tables(PngTables *t) {
+// menu16: the menu of the 16-bit encoder.  A filtered 16-bit scanline interleaves two populations: the residuals of the high
+// bytes (the 8-bit picture: a spike at zero and a short tail) and those of the low bytes, which a rendered frame spreads
+// almost evenly over 0..255.  No entry of the 8-bit menu fits that: its peaked codes spend 12-15 bits on every low byte, its
+// flat code 8-9 on every high byte.  Entry k < 15 is therefore the code of the MIXTURE: half the symbols from the 8-bit
+// entry's model with (q, b), half from a two-sided geometric of scale B (16, 48 or uniform) -- low bytes of smooth rows
+// are not quite uniform either.  Entry 15 stays the flat code that bounds the worst case.
+bool fill_tables(PngTables *t, bool menu16 = false) {
     memset(t, 0, sizeof(*t));
     static const double qs[5] = {0.15, 0.3, 0.45, 0.6, 0.8}, bs[3] = {0.7, 1.5, 4.0};
+    static const double qs16[5] = {0.05, 0.2, 0.4, 0.6, 0.8}, low16[3] = {16.0, 48.0, 0.0};
     for (int k = 0; k < kTables; ++k) {
         std::vector<uint64_t> freq(kSyms, 1);
-        if (k < 15) {
+        if (k < 15 && !menu16) {
             const double q = qs[k / 3], b = bs[k % 3];
             double norm = 0.0;
             for (int s = 1; s < 256; ++s) norm += std::exp(-(double)(s < 128 ? s : 256 - s) / b);
@@ -207,6 +214,18 @@ bool fill_tables(PngTables *t) {
                 freq[s] = std::max<uint64_t>((uint64_t)(std::exp(-(double)(s < 128 ? s : 256 - s) / b) / norm * q * 16777216.0), 1);
             freq[0] = (uint64_t)((1.0 - q) * 16777216.0);
             freq[256] = 16777216 / 5761;          // one end-of-block per scanline
+        } else if (k < 15) {
+            const double q = qs16[k / 3], b = 1.0, B = low16[k % 3];
+            double norm = 0.0, norm_low = 0.0;
+            for (int s = 1; s < 256; ++s) norm += std::exp(-(double)(s < 128 ? s : 256 - s) / b);
+            for (int s = 0; s < 256; ++s) norm_low += B > 0.0 ? std::exp(-(double)(s < 128 ? s : 256 - s) / B) : 1.0;
+            for (int s = 0; s < 256; ++s) {
+                const double d = (double)(s < 128 ? s : 256 - s);
+                const double high = s == 0 ? 1.0 - q : std::exp(-d / b) / norm * q;
+                const double low = (B > 0.0 ? std::exp(-d / B) : 1.0) / norm_low;
+                freq[s] = std::max<uint64_t>((uint64_t)((0.5 * high + 0.5 * low) * 16777216.0), 1);
+            }
+            freq[256] = 16777216 / 11521;         // one end-of-block per scanline
         }
         const std::vector<int> len = huffman_lengths(freq, 15);
         const std::vector<uint32_t> code = canonical_reversed(len);
@@ -230,7 +249,7 @@ bool fill_tables(PngTables *t) {
     return true;
 }
 
-void fill_head(uint8_t *head, int w, int h) {
+void fill_head(uint8_t *head, int w, int h, int bit_depth = 8) {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     memcpy(head, sig, 8);
     uint8_t *c = head + 8;
@@ -239,7 +258,7 @@ void fill_head(uint8_t *head, int w, int h) {
     memcpy(c + 4, "IHDR", 4);
     for (int k = 0; k < 2; ++k)
         for (int b = 0; b < 4; ++b) c[8 + 4 * k + b] = (uint8_t)(fields[k] >> (24 - 8 * b));
-    c[16] = 8; c[17] = 2; c[18] = 0; c[19] = 0; c[20] = 0;     // 8-bit, colour type 2 (RGB), deflate, adaptive filters, no interlace
+    c[16] = (uint8_t)bit_depth; c[17] = 2; c[18] = 0; c[19] = 0; c[20] = 0;     // 8 or 16 bit, colour type 2 (RGB), deflate, adaptive filters, no interlace
     const uint32_t crc = (uint32_t)crc32(0L, c + 4, 17);
     for (int b = 0; b < 4; ++b) c[21 + b] = (uint8_t)(crc >> (24 - 8 * b));
 }
@@ -259,6 +278,10 @@ __device__ __forceinline__ int row_stride(int n) { return kRowPrefix + ((n + 15)
 
 // The scanline and the one above it -> LDS (cur, up point behind the prefix).  16-byte loads when the rows are 16-byte
 // aligned (every width that is a multiple of 16: all BASELINE sizes); otherwise bytes, eight loads in flight per thread.
+// BPP = bytes per pixel: 3, or 6 for the 16-bit encoder, whose rows are native-endian u16 samples in memory and big-endian in
+// the file: the two bytes of every sample change places on the way into LDS (n is even then).
+__device__ __forceinline__ uint32_t swap16(uint32_t v) { return __byte_perm(v, 0u, 0x2301); }
+template <int BPP>
 __device__ __forceinline__ void load_rows(const uint8_t *__restrict__ rgb, int row, int n, uint8_t *cur, uint8_t *up) {
     const uint8_t *g = rgb + (size_t)row * n;
     const int npad = (n + 15) & ~15;
@@ -270,8 +293,13 @@ __device__ __forceinline__ void load_rows(const uint8_t *__restrict__ rgb, int r
         const uint4 *g4 = (const uint4 *)g, *u4 = (const uint4 *)(g - n);
         uint4 *c4 = (uint4 *)cur, *p4 = (uint4 *)up;
         for (int v = threadIdx.x; v < (n >> 4); v += kThreads) {
-            c4[v] = g4[v];
-            p4[v] = row > 0 ? u4[v] : make_uint4(0u, 0u, 0u, 0u);
+            uint4 a = g4[v], b = row > 0 ? u4[v] : make_uint4(0u, 0u, 0u, 0u);
+            if (BPP == 6) {
+                a = make_uint4(swap16(a.x), swap16(a.y), swap16(a.z), swap16(a.w));
+                b = make_uint4(swap16(b.x), swap16(b.y), swap16(b.z), swap16(b.w));
+            }
+            c4[v] = a;
+            p4[v] = b;
         }
         return;
     }
@@ -279,9 +307,9 @@ __device__ __forceinline__ void load_rows(const uint8_t *__restrict__ rgb, int r
         uint8_t a[8], b[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const int i = i0 + k * kThreads + (int)threadIdx.x;
-            a[k] = i < n ? g[i] : (uint8_t)0;
-            b[k] = (i < n && row > 0) ? g[i - n] : (uint8_t)0;
+            const int i = i0 + k * kThreads + (int)threadIdx.x, s = BPP == 6 ? (i ^ 1) : i;   // i < n, n even => (i ^ 1) < n
+            a[k] = i < n ? g[s] : (uint8_t)0;
+            b[k] = (i < n && row > 0) ? g[s - n] : (uint8_t)0;
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -291,16 +319,22 @@ __device__ __forceinline__ void load_rows(const uint8_t *__restrict__ rgb, int r
     }
 }
 
-// Operands of bytes i .. i + 3 (i a multiple of 4): x = the bytes, a = three to the left, b = above, c = above-left.
+// Operands of bytes i .. i + 3 (i a multiple of 4): x = the bytes, a = BPP to the left (one pixel), b = above, c = above-left.
 struct Quad { uint32_t x, a, b, c; };
+template <int BPP>
 __device__ __forceinline__ Quad load_quad(const uint8_t *cur, const uint8_t *up, int i) {
     const uint32_t x = *(const uint32_t *)(cur + i), xp = *(const uint32_t *)(cur + i - 4);
     const uint32_t b = *(const uint32_t *)(up + i), bp = *(const uint32_t *)(up + i - 4);
     Quad q;
     q.x = x;
     q.b = b;
-    q.a = __byte_perm(xp, x, 0x4321);      // bytes i-3, i-2, i-1, i
-    q.c = __byte_perm(bp, b, 0x4321);
+    if (BPP == 3) {
+        q.a = __byte_perm(xp, x, 0x4321);      // bytes i-3, i-2, i-1, i
+        q.c = __byte_perm(bp, b, 0x4321);
+    } else {                                   // bytes i-6 .. i-3 (the zero prefix is 16 bytes: i - 8 >= -8 is inside it)
+        q.a = __byte_perm(*(const uint32_t *)(cur + i - 8), xp, 0x5432);
+        q.c = __byte_perm(*(const uint32_t *)(up + i - 8), bp, 0x5432);
+    }
     return q;
 }
 
@@ -331,6 +365,7 @@ __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
 }
 
 // K1: per scanline -- filter choice, histogram, code choice, size, Adler partial sums.
+template <int BPP>
 __global__ __launch_bounds__(kThreads) void png_plan_kernel(const uint8_t *__restrict__ rgb, int n, int h,
                                                             const PngTables *__restrict__ tab, RowPlan *__restrict__ plan) {
     extern __shared__ uint8_t smem[];
@@ -344,13 +379,13 @@ __global__ __launch_bounds__(kThreads) void png_plan_kernel(const uint8_t *__res
     if (tid < 5) cost[tid] = 0;
     if (tid < kTables) bits[tid] = 0;
     if (tid < 2) ab[tid] = 0;
-    load_rows(rgb, row, n, cur, up);
+    load_rows<BPP>(rgb, row, n, cur, up);
     __syncthreads();
     {   // sum of |signed residual| for the five filters; neighbouring lanes read neighbouring words
         uint32_t c[5] = {0, 0, 0, 0, 0};
 #pragma unroll 2
         for (int i = 4 * tid; i < n; i += 4 * kThreads) {
-            const Quad q = load_quad(cur, up, i);
+            const Quad q = load_quad<BPP>(cur, up, i);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (i + k < n)
@@ -377,7 +412,7 @@ __global__ __launch_bounds__(kThreads) void png_plan_kernel(const uint8_t *__res
         unsigned long long b = 0;
 #pragma unroll 2
         for (int i = 4 * tid; i < n; i += 4 * kThreads) {
-            const Quad q = load_quad(cur, up, i);
+            const Quad q = load_quad<BPP>(cur, up, i);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (i + k < n) {
@@ -506,6 +541,7 @@ __device__ __forceinline__ uint32_t multmodp(uint32_t a, uint32_t b) {
 }
 
 // K3: code one scanline into its IDAT chunk.
+template <int BPP>
 __global__ __launch_bounds__(kThreads) void png_encode_kernel(const uint8_t *__restrict__ rgb, int n, int h,
                                                               const PngTables *__restrict__ tab, const RowPlan *__restrict__ plan,
                                                               const uint32_t *__restrict__ offs, const uint32_t *__restrict__ meta,
@@ -527,10 +563,10 @@ __global__ __launch_bounds__(kThreads) void png_encode_kernel(const uint8_t *__r
     for (int i = tid; i < kSyms; i += kThreads) codes[i] = tab->code[p.table][i];
     crc_tab[tid] = tab->crc_table[tid];
     if (tid == 0) crc_acc = 0;
-    load_rows(rgb, row, n, cur, up);
+    load_rows<BPP>(rgb, row, n, cur, up);
     __syncthreads();
     for (int i = 4 * tid; i < n; i += 4 * kThreads) {
-        const Quad q = load_quad(cur, up, i);
+        const Quad q = load_quad<BPP>(cur, up, i);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (i + k < n) fb[i + 1 + k] = (uint8_t)residual((int)p.filter, q, k);
@@ -649,10 +685,10 @@ int chunk_words_for(int n) { return (int)(((size_t)n + 1) * 9 / 8 / 4 + 96); }  
 }  // namespace
 
 // Widest frame the encode kernel can hold: two padded rows (or the chunk) + the filtered row in 150 KB of LDS.
-extern "C" int32_t bhr_png_device_max_width(void) {
+static int32_t max_width_for(int bpp) {
     int lo = 1, hi = 1 << 16;
-    auto fits = [](int w) {
-        const size_t n = 3 * (size_t)w, npad = (n + 15) & ~(size_t)15;
+    auto fits = [bpp](int w) {
+        const size_t n = (size_t)bpp * (size_t)w, npad = (n + 15) & ~(size_t)15;
         const size_t rows = 2 * (16 + npad), chunk = 4 * (size_t)chunk_words_for((int)n);
         return ((std::max(rows, chunk) + 15) & ~(size_t)15) + ((n + 1 + 15) & ~(size_t)15) <= 150 * 1024;
     };
@@ -662,16 +698,22 @@ extern "C" int32_t bhr_png_device_max_width(void) {
     }
     return lo;
 }
+extern "C" int32_t bhr_png_device_max_width(void) { return max_width_for(3); }
+extern "C" int32_t bhr_png16_device_max_width(void) { return max_width_for(6); }
 
 extern "C" int64_t bhr_png_device_bound(int32_t w, int32_t h) {
     if (w <= 0 || h <= 0) return 0;
     return (int64_t)h * (4 * (int64_t)chunk_words_for(3 * w)) + 64;
 }
+extern "C" int64_t bhr_png16_device_bound(int32_t w, int32_t h) {
+    if (w <= 0 || h <= 0 || w > max_width_for(6)) return 0;
+    return (int64_t)h * (4 * (int64_t)chunk_words_for(6 * w)) + 64;
+}
 
 void bhr_png_dev_free(bhr_ctx *ctx) {
     PngDev *d = dev_of(ctx);
     if (!d) return;
-    void *bufs[] = {d->d_tab, d->d_meta, d->d_out};
+    void *bufs[] = {d->d_tab[0], d->d_tab[1], d->d_meta, d->d_out};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (int k = 0; k < BHR_MAX_FRAME_SLOTS; ++k) {
@@ -682,23 +724,23 @@ void bhr_png_dev_free(bhr_ctx *ctx) {
     ctx->png_dev = nullptr;
 }
 
-// Tables and per-scanline scratch for this context's frame size (idempotent).
-int32_t bhr_png_dev_prepare(bhr_ctx *ctx) {
+// Tables and per-scanline scratch for this context's frame size (idempotent).  deep: the 16-bit encoder's tables.
+int32_t bhr_png_dev_prepare(bhr_ctx *ctx, int deep = 0) {
     const int w = ctx->cfg.width, h = ctx->rows;
     PngDev *d = dev_of(ctx);
     if (!d) {
         d = new PngDev();
         ctx->png_dev = d;
     }
-    if (!d->d_tab || d->head_w != w || d->head_h != h) {
+    if (!d->d_tab[deep] || d->head_w[deep] != w || d->head_h[deep] != h) {
         std::vector<PngTables> t(1);
-        if (!fill_tables(&t[0])) return bhr_fail(BHR_ERR_STATE, "device PNG encoder: a block header exceeds %d words", kHdrWords);
-        fill_head(t[0].head, w, h);
-        if (!d->d_tab) BHR_HIP(hipMalloc((void **)&d->d_tab, sizeof(PngTables)));
-        BHR_HIP(hipMemcpyAsync(d->d_tab, &t[0], sizeof(PngTables), hipMemcpyHostToDevice, ctx->stream));
+        if (!fill_tables(&t[0], deep && ctx->opt.png16_menu)) return bhr_fail(BHR_ERR_STATE, "device PNG encoder: a block header exceeds %d words", kHdrWords);
+        fill_head(t[0].head, w, h, deep ? 16 : 8);
+        if (!d->d_tab[deep]) BHR_HIP(hipMalloc((void **)&d->d_tab[deep], sizeof(PngTables)));
+        BHR_HIP(hipMemcpyAsync(d->d_tab[deep], &t[0], sizeof(PngTables), hipMemcpyHostToDevice, ctx->stream));
         BHR_HIP(hipStreamSynchronize(ctx->stream));        // the host copy goes out of scope
-        d->head_w = w;
-        d->head_h = h;
+        d->head_w[deep] = w;
+        d->head_h[deep] = h;
     }
     if (d->plan_rows < h) {
         for (int k = 0; k < BHR_MAX_FRAME_SLOTS; ++k) {
@@ -718,33 +760,81 @@ int32_t bhr_png_dev_prepare(bhr_ctx *ctx) {
     return BHR_OK;
 }
 
-// Encodes the (rows, W, 3) u8 image at d_rgb into d_out (cap bytes) on ctx->stream; d_meta_out (4 words, device)
-// receives {file length, error, adler, 0}.  The plan / offsets scratch is the active frame slot's.
-int32_t bhr_launch_png_encode(bhr_ctx *ctx, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta_out) {
-    BHR_TRY(bhr_png_dev_prepare(ctx));
+// Encodes the (rows, W, 3) image at d_rgb -- BPP = 3: u8 samples; 6: native-endian u16 samples -- into d_out (cap bytes) on
+// ctx->stream; d_meta_out (4 words, device) receives {file length, error, adler, 0}.  The plan / offsets scratch is the active
+// frame slot's.
+template <int BPP>
+static int32_t launch_png_encode(bhr_ctx *ctx, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta_out) {
+    constexpr int deep = BPP == 6 ? 1 : 0;
+    if (max_width_for(BPP) < ctx->cfg.width)
+        return bhr_fail(BHR_ERR_INVALID, "device PNG encoder: a %d-bit scanline of %d pixels does not fit LDS (at most %d); use the host encoder",
+                        deep ? 16 : 8, ctx->cfg.width, max_width_for(BPP));
+    BHR_TRY(bhr_png_dev_prepare(ctx, deep));
     PngDev *d = dev_of(ctx);
-    const int n = 3 * ctx->cfg.width, h = ctx->rows;
+    const int n = BPP * ctx->cfg.width, h = ctx->rows;
     const int npad = (n + 15) & ~15;
     const int cwords = chunk_words_for(n);
     const size_t row_buf = 16 + (size_t)npad;                       // kRowPrefix + padded row (row_stride)
     const size_t lds_plan = 2 * row_buf;
     const size_t lds_enc = ((std::max(2 * row_buf, (size_t)4 * cwords) + 15) & ~(size_t)15) + ((n + 1 + 15) & ~15);
-    if (bhr_png_device_max_width() < ctx->cfg.width)
-        return bhr_fail(BHR_ERR_INVALID, "device PNG encoder: a scanline of %d pixels does not fit LDS (at most %d); use the host encoder",
-                        ctx->cfg.width, bhr_png_device_max_width());
-    if (!d->lds_attr) {
-        BHR_HIP(hipFuncSetAttribute((const void *)png_encode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        BHR_HIP(hipFuncSetAttribute((const void *)png_plan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        d->lds_attr = true;
+    if (!d->lds_attr[deep]) {
+        BHR_HIP(hipFuncSetAttribute((const void *)png_encode_kernel<BPP>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        BHR_HIP(hipFuncSetAttribute((const void *)png_plan_kernel<BPP>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        d->lds_attr[deep] = true;
     }
     RowPlan *plan = d->d_plan[ctx->active_slot];
     uint32_t *offs = d->d_offs[ctx->active_slot];
-    hipLaunchKernelGGL(png_plan_kernel, dim3(h), dim3(kThreads), lds_plan, ctx->stream, d_rgb, n, h, d->d_tab, plan);
-    hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, plan, n, h, d->d_tab, offs, d_meta_out, d_out,
+    const PngTables *tab = d->d_tab[deep];
+    hipLaunchKernelGGL(png_plan_kernel<BPP>, dim3(h), dim3(kThreads), lds_plan, ctx->stream, d_rgb, n, h, tab, plan);
+    hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, plan, n, h, tab, offs, d_meta_out, d_out,
                        (long long)cap);
-    hipLaunchKernelGGL(png_encode_kernel, dim3(h), dim3(kThreads), lds_enc, ctx->stream, d_rgb, n, h, d->d_tab, plan, offs,
+    hipLaunchKernelGGL(png_encode_kernel<BPP>, dim3(h), dim3(kThreads), lds_enc, ctx->stream, d_rgb, n, h, tab, plan, offs,
                        d_meta_out, d_out, cwords);
     BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}
+
+int32_t bhr_launch_png_encode(bhr_ctx *ctx, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta_out) {
+    return launch_png_encode<3>(ctx, d_rgb, d_out, cap, d_meta_out);
+}
+int32_t bhr_launch_png16_encode(bhr_ctx *ctx, const uint16_t *d_rgb16, uint8_t *d_out, int64_t cap, uint32_t *d_meta_out) {
+    return launch_png_encode<6>(ctx, (const uint8_t *)d_rgb16, d_out, cap, d_meta_out);
+}
+
+// bhr_png_encode_device / bhr_png16_encode_device: quantise, encode into the context's scratch, fetch the exact length.
+static int32_t encode_device(bhr_ctx *ctx, int deep, uint8_t *out, int64_t cap, int64_t *out_len) {
+    const char *who = deep ? "bhr_png16_encode_device" : "bhr_png_encode_device";
+    if (!ctx || !out || !out_len) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    if (deep && ctx->cfg.width > max_width_for(6))
+        return bhr_fail(BHR_ERR_INVALID, "%s: a 16-bit scanline of %d pixels does not fit LDS (at most %d); use the host encoder", who,
+                        ctx->cfg.width, max_width_for(6));
+    BHR_TRY(bhr_enter(ctx));
+    BHR_TRY(bhr_png_dev_prepare(ctx, deep));
+    PngDev *d = dev_of(ctx);
+    const int64_t bound = deep ? bhr_png16_device_bound(ctx->cfg.width, ctx->rows) : bhr_png_device_bound(ctx->cfg.width, ctx->rows);
+    if (d->out_cap < bound) {
+        if (d->d_out) (void)hipFree(d->d_out);
+        d->d_out = nullptr;
+        d->out_cap = 0;
+        BHR_HIP(hipMalloc((void **)&d->d_out, (size_t)bound));
+        d->out_cap = bound;
+    }
+    if (deep) {
+        BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_U16));
+        BHR_TRY(bhr_launch_png16_encode(ctx, bhr_slot(ctx).d_final_u16, d->d_out, bound, d->d_meta));
+    } else {
+        BHR_TRY(bhr_launch_quantize(ctx));
+        BHR_TRY(bhr_launch_png_encode(ctx, bhr_slot(ctx).d_final_u8, d->d_out, bound, d->d_meta));
+    }
+    uint32_t meta[4] = {0, 0, 0, 0};
+    BHR_HIP(hipMemcpyAsync(meta, d->d_meta, sizeof(meta), hipMemcpyDeviceToHost, ctx->stream));
+    BHR_HIP(hipStreamSynchronize(ctx->stream));
+    if (meta[1]) return bhr_fail(BHR_ERR_STATE, "%s: the encoded frame exceeds its bound", who);
+    if ((int64_t)meta[0] > cap)
+        return bhr_fail(BHR_ERR_INVALID, "%s: %u bytes do not fit the caller's %lld", who, meta[0], (long long)cap);
+    BHR_HIP(hipMemcpyAsync(out, d->d_out, meta[0], hipMemcpyDeviceToHost, ctx->stream));
+    BHR_HIP(hipStreamSynchronize(ctx->stream));
+    *out_len = (int64_t)meta[0];
     return BHR_OK;
 }
 
@@ -762,31 +852,7 @@ int32_t bhr_png_device_menu(int32_t k, uint32_t *codes, uint32_t *hdr_words, uin
     return BHR_OK;
 }
 
-int32_t bhr_png_encode_device(bhr_ctx *ctx, uint8_t *out, int64_t cap, int64_t *out_len) {
-    if (!ctx || !out || !out_len) return bhr_fail(BHR_ERR_INVALID, "bhr_png_encode_device: null argument");
-    BHR_TRY(bhr_enter(ctx));
-    BHR_TRY(bhr_png_dev_prepare(ctx));
-    PngDev *d = dev_of(ctx);
-    const int64_t bound = bhr_png_device_bound(ctx->cfg.width, ctx->rows);
-    if (d->out_cap < bound) {
-        if (d->d_out) (void)hipFree(d->d_out);
-        d->d_out = nullptr;
-        d->out_cap = 0;
-        BHR_HIP(hipMalloc((void **)&d->d_out, (size_t)bound));
-        d->out_cap = bound;
-    }
-    BHR_TRY(bhr_launch_quantize(ctx));
-    BHR_TRY(bhr_launch_png_encode(ctx, bhr_slot(ctx).d_final_u8, d->d_out, bound, d->d_meta));
-    uint32_t meta[4] = {0, 0, 0, 0};
-    BHR_HIP(hipMemcpyAsync(meta, d->d_meta, sizeof(meta), hipMemcpyDeviceToHost, ctx->stream));
-    BHR_HIP(hipStreamSynchronize(ctx->stream));
-    if (meta[1]) return bhr_fail(BHR_ERR_STATE, "bhr_png_encode_device: the encoded frame exceeds bhr_png_device_bound");
-    if ((int64_t)meta[0] > cap)
-        return bhr_fail(BHR_ERR_INVALID, "bhr_png_encode_device: %u bytes do not fit the caller's %lld", meta[0], (long long)cap);
-    BHR_HIP(hipMemcpyAsync(out, d->d_out, meta[0], hipMemcpyDeviceToHost, ctx->stream));
-    BHR_HIP(hipStreamSynchronize(ctx->stream));
-    *out_len = (int64_t)meta[0];
-    return BHR_OK;
-}
+int32_t bhr_png_encode_device(bhr_ctx *ctx, uint8_t *out, int64_t cap, int64_t *out_len) { return encode_device(ctx, 0, out, cap, out_len); }
+int32_t bhr_png16_encode_device(bhr_ctx *ctx, uint8_t *out, int64_t cap, int64_t *out_len) { return encode_device(ctx, 1, out, cap, out_len); }
 
 }  // extern "C"

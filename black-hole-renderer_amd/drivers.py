@@ -21,21 +21,41 @@ import numpy as np
 
 from .camera import orbit_position
 from .lifecycle import make_factories
-from .output import Y4MStream, FrameSink, VIDEO_LEVEL, DEVICE, png_write, quantize
+from .output import Y4MStream, FrameSink, VIDEO_LEVEL, DEVICE, DITHERS, png_write, quantize, quantize16
 from .renderer import HipRenderer, R_DISK_INNER_DEFAULT, R_DISK_OUTER_DEFAULT
 from .skybox import load_or_generate_skybox
 from .textures import compute_disk_texture_resolution, load_disk_texture
 
 
-def save_image(image: np.ndarray, path: str) -> None:
+def check_depth_and_dither(bit_depth: int, dither: str, video_codec: str = "auto") -> None:
+    """The combinations the output side takes: 16-bit output is neither dithered (65536 levels need none) nor JPEG-coded."""
+    if bit_depth not in (8, 16):
+        raise ValueError(f"bit_depth must be 8 or 16, got {bit_depth!r}")
+    if dither not in DITHERS:
+        raise ValueError(f"dither must be one of {DITHERS}, got {dither!r}")
+    if bit_depth == 16 and dither != "none":
+        raise ValueError("--bit_depth 16 is not dithered: --dither blue applies to 8-bit output")
+    if bit_depth == 16 and video_codec == "mjpeg":
+        raise ValueError("--bit_depth 16 does not combine with --video_codec mjpeg: JPEG frames are 8-bit")
+
+
+def save_image(image: np.ndarray, path: str, bit_depth: int = 8, dither: str = "none") -> None:
     """float image -> 8-bit PNG with truncation, not rounding (render.py:420-425).  Encoded by the
-    library (row bands deflated in parallel); non-PNG extensions go through PIL as in the reference."""
+    library (row bands deflated in parallel); non-PNG extensions go through PIL as in the reference.
+    ``bit_depth=16``: a 16-bit PNG of output.quantize16(image) (PNG only).  ``dither="blue"``: the 8-bit values are
+    output.quantize(image, dither="blue").  Both quantise on the host with the device's formulas restated, whichever way
+    the image was rendered."""
+    check_depth_and_dither(bit_depth, dither)
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    if path.lower().endswith(".png"):
-        png_write(path, quantize(image))
+    if bit_depth == 16:
+        if not path.lower().endswith(".png"):
+            raise ValueError(f"bit_depth 16 writes PNG files, got {path!r}")
+        png_write(path, quantize16(image))
+    elif path.lower().endswith(".png"):
+        png_write(path, quantize(image, dither=dither))
     else:
         from PIL import Image
-        Image.fromarray(quantize(image)).save(path)
+        Image.fromarray(quantize(image, dither=dither)).save(path)
     print(f"Saved: {path}")
 
 
@@ -121,12 +141,15 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  aa_strength: float = 1.0, disk_rotation_speed: float = 0.1, disk_generation_scale: int = 2,
                  force_regenerate_disk_texture: bool = False, ignore_taichi_cache: bool = False,
                  gpus: int = 1, disk_model: str = "texture", math: Optional[str] = None,
-                 supersample: int = 1, supersample_threshold: Optional[float] = None) -> np.ndarray:
+                 supersample: int = 1, supersample_threshold: Optional[float] = None, bit_depth: int = 8,
+                 dither: str = "none") -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
     pixel (one device only); ``supersample_threshold``: adaptive -- only for the pixels whose k = 1 neighbours differ by more
-    than it (HipRenderer.set_supersample; None: every pixel)."""
+    than it (HipRenderer.set_supersample; None: every pixel).  ``bit_depth`` / ``dither`` are checked here and applied by
+    save_image to the frame this returns (the f32 frame does not depend on them)."""
+    check_depth_and_dither(bit_depth, dither)
     if gpus > 1 and supersample != 1:
         raise ValueError("supersample > 1 renders on one GPU: row-block tiles march one ray per pixel")
     if gpus > 1:
@@ -157,9 +180,10 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     return img
 
 
-def _lib_max_png_width() -> int:
+def _lib_max_png_width(bit_depth: int = 8) -> int:
     from . import _lib
-    return int(_lib.load().bhr_png_device_max_width())
+    lib = _lib.load()
+    return int(lib.bhr_png16_device_max_width() if bit_depth == 16 else lib.bhr_png_device_max_width())
 
 
 def _frames_dir(output_path: str) -> str:
@@ -221,6 +245,22 @@ def assemble_video(temp_dir: str, n_frames: int, fps: int, output_path: str, cod
     return True
 
 
+def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
+                    bit_depth=8, dither="none") -> dict:
+    """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
+    where they are not the defaults -- a record written before those settings existed still matches a default run.  A
+    resume whose params differ from the record's starts over."""
+    params = {"n_frames": n_frames, "fov": fov, "orbit": orbit, "disk_rotation_speed": disk_rotation_speed,
+              "orbit_degrees": orbit_degrees}
+    if video_codec == "mjpeg":
+        params.update(video_codec=video_codec, video_quality=video_quality)
+    if bit_depth != 8:
+        params.update(bit_depth=bit_depth)
+    if dither != "none":
+        params.update(dither=dither)
+    return params
+
+
 def _drop_stream(stream, encoder, err) -> None:
     """The yuv420p stream is an extra: when its consumer dies (an ffmpeg without libx264 exits at once and every later
     write fails with EPIPE) the stream is closed, the encoder reaped, and the render goes on with the PNG frames, from
@@ -252,7 +292,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  assemble: bool = True, png_level: int = DEVICE, sink_slots: int = 0, sink_workers: int = 0,
                  video_stream: str = "auto", stats: Optional[dict] = None, supersample: Optional[int] = None,
                  supersample_threshold: Optional[float] = None, video_codec: str = "auto", video_quality: int = 90,
-                 **_deprecated_kwargs) -> None:
+                 bit_depth: int = 8, dither: str = "none", **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -274,9 +314,16 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     ``frame_%04d.jpg`` in the same frames directory, and assemble_video muxes them into the MP4 as Motion-JPEG.  No PNG
     is written, the yuv420p stream and the search for ffmpeg / pyav are skipped, resume looks for the .jpg files, and the
     progress record's params carry the codec and the quality (a resume across codecs or qualities starts over).  In this
-    mode the renderer's outputs selection is restored on return ("auto" leaves it at "u8", as it always has)."""
+    mode the renderer's outputs selection is restored on return ("auto" leaves it at "u8", as it always has).
+
+    ``bit_depth=16``: the frame files are 16-bit PNGs (bhr_sink_create_png16; on the device up to its width limit, else on the
+    host); the yuv420p stream stays 8-bit, and the PNG-in-MP4 fallback muxes the files as it muxes any PNG.  ``dither="blue"``:
+    every 8-bit consumer of the loop -- PNG or JPEG frames, the yuv420p stream -- gets the blue-noise dithered rows
+    (HipRenderer.set_dither; the renderer's mode is restored on return).  The progress record carries the two only when
+    they are not the defaults, as it does the codec: a resume with other values starts over."""
     if video_codec not in VIDEO_CODECS:
         raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
+    check_depth_and_dither(bit_depth, dither, video_codec)
     mjpeg = video_codec == "mjpeg"
     if mjpeg and not (isinstance(video_quality, int) and 1 <= video_quality <= 100):
         raise ValueError(f"video_quality must be an integer between 1 and 100, got {video_quality!r}")
@@ -289,10 +336,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     temp_dir = _frames_dir(output_path)
     submitted: List[int] = []
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
-    params = {"n_frames": n_frames, "fov": fov, "orbit": orbit, "disk_rotation_speed": disk_rotation_speed,
-              "orbit_degrees": orbit_degrees}
-    if mjpeg:
-        params.update(video_codec=video_codec, video_quality=video_quality)
+    params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -340,8 +384,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     # on the device, copied into a pinned ring and encoded by worker threads while the next frames render
     if mjpeg:
         png_level = DEVICE                               # the JPEG coder runs on the device only
-    if png_level == DEVICE and not mjpeg and width > _lib_max_png_width():
-        print(f"  frames wider than {_lib_max_png_width()} pixels are PNG-encoded on the host (zlib level {VIDEO_LEVEL})")
+    if png_level == DEVICE and not mjpeg and width > _lib_max_png_width(bit_depth):
+        print(f"  frames wider than {_lib_max_png_width(bit_depth)} pixels are PNG-encoded on the host (zlib level {VIDEO_LEVEL})")
         png_level = VIDEO_LEVEL
     if png_level == DEVICE and sink_workers <= 0:
         sink_workers = 4                                 # copy + write only
@@ -349,7 +393,10 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         outputs_before = renderer.outputs
         sink = FrameSink(renderer, slots=sink_slots, workers=sink_workers, codec="jpeg", quality=video_quality)
     else:
-        sink = FrameSink(renderer, slots=sink_slots, workers=sink_workers, level=png_level)
+        sink = FrameSink(renderer, slots=sink_slots, workers=sink_workers, level=png_level, bit_depth=bit_depth)
+    dither_before = renderer.dither
+    if dither != dither_before:
+        renderer.set_dither(dither)
     if video_stream not in ("auto", "y4m", "off"):
         raise ValueError(f"video_stream must be 'auto', 'y4m' or 'off', got {video_stream!r}")
     stream = encoder = None
@@ -364,7 +411,11 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
 
     # the loop's consumers read the quantised rows (PNG sink) and, with a yuv420p stream, the f32 frame: the V pass of every
     # frame stores exactly those (12 bytes per pixel less to write without a stream, 24 with the blur layer nobody reads)
-    renderer.set_outputs("u8" if stream is None else "f32+u8")
+    # (16-bit frames and dithered rows are quantised from the f32 frame by kernels of their own: the frame keeps f32)
+    if bit_depth == 16:
+        renderer.set_outputs("f32")
+    else:
+        renderer.set_outputs("u8" if stream is None else "f32+u8")
     n_r, n_phi = renderer.dtex_h, renderer.dtex_w
     factories = init_lifecycle_system(renderer, n_r, n_phi, seed=42)
     dt = disk_rotation_speed
@@ -404,6 +455,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     sink.close()
     if mjpeg:
         renderer.set_outputs(outputs_before)
+    if dither != dither_before:
+        renderer.set_dither(dither_before)
     if stats is not None:
         stats.update(setup_s=t_loop0 - total_t0, loop_s=time.time() - t_loop0, frames=rendered)
     streamed = False

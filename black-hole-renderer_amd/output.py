@@ -26,11 +26,25 @@ def _u8(a: np.ndarray) -> np.ndarray:
     return a
 
 
+def _u8_or_u16(a: np.ndarray) -> np.ndarray:
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "u" and a.dtype.itemsize == 2 and a.ndim == 3 and a.shape[2] == 3:
+        return a.astype("=u2", copy=False)          # native endian: what the library reads
+    return _u8(a)
+
+
 def png_encode(rgb_u8: np.ndarray, level: int = DEFAULT_LEVEL, threads: int = 1) -> bytes:
-    """(H, W, 3) uint8 -> PNG file bytes."""
-    a = _u8(rgb_u8)
+    """(H, W, 3) uint8 -> PNG file bytes; an (H, W, 3) uint16 array -> a 16-bit PNG (bhr_png_encode16)."""
+    a = _u8_or_u16(rgb_u8)
     h, w = a.shape[:2]
     lib = _lib.load()
+    if a.dtype == np.uint16:
+        cap = lib.bhr_png_bound16(w, h)
+        out = np.empty(cap, dtype=np.uint8)
+        n = C.c_int64(0)
+        _lib.check(lib.bhr_png_encode16(a.ctypes.data_as(C.POINTER(C.c_uint16)), w, h, level, threads,
+                                        out.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(n)))
+        return out[:n.value].tobytes()
     cap = lib.bhr_png_bound(w, h)
     out = np.empty(cap, dtype=np.uint8)
     n = C.c_int64(0)
@@ -41,22 +55,33 @@ def png_encode(rgb_u8: np.ndarray, level: int = DEFAULT_LEVEL, threads: int = 1)
 
 def png_write(path: str, rgb_u8: np.ndarray, level: int = DEFAULT_LEVEL, threads: int = 0) -> None:
     """Image.fromarray(rgb_u8).save(path) with row bands deflated on ``threads`` threads
-    (0: one per 256 rows, at most the CPUs of this process)."""
-    a = _u8(rgb_u8)
+    (0: one per 256 rows, at most the CPUs of this process).  A uint16 array is written as a 16-bit PNG."""
+    a = _u8_or_u16(rgb_u8)
     h, w = a.shape[:2]
     if threads <= 0:
         threads = max(1, min(len(os.sched_getaffinity(0)), h // 256))
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    if a.dtype == np.uint16:
+        _lib.check(_lib.load().bhr_png_write16(os.fsencode(path), a.ctypes.data_as(C.POINTER(C.c_uint16)), w, h, level, threads))
+        return
     _lib.check(_lib.load().bhr_png_write(os.fsencode(path), a.ctypes.data_as(C.POINTER(C.c_uint8)), w, h, level, threads))
 
 
-def png_encode_device(renderer) -> bytes:
-    """PNG file bytes of the renderer's FINAL layer, filtered and entropy coded on the device (bhr_png_encode_device)."""
+def png_encode_device(renderer, bit_depth: int = 8) -> bytes:
+    """PNG file bytes of the renderer's FINAL layer, filtered and entropy coded on the device (bhr_png_encode_device;
+    ``bit_depth=16``: bhr_png16_encode_device, the samples of ``renderer.read_final_u16()``)."""
+    if bit_depth not in (8, 16):
+        raise ValueError(f"bit_depth must be 8 or 16, got {bit_depth!r}")
     lib = _lib.load()
-    cap = lib.bhr_png_device_bound(renderer.width, renderer.rows)
+    if bit_depth == 16 and renderer.width > lib.bhr_png16_device_max_width():
+        raise ValueError(f"the 16-bit device PNG encoder takes frames up to {lib.bhr_png16_device_max_width()} pixels wide, "
+                         f"this one has {renderer.width}; use the host encoder")
+    bound, encode = ((lib.bhr_png16_device_bound, lib.bhr_png16_encode_device) if bit_depth == 16
+                     else (lib.bhr_png_device_bound, lib.bhr_png_encode_device))
+    cap = bound(renderer.width, renderer.rows)
     out = np.empty(cap, dtype=np.uint8)
     n = C.c_int64(0)
-    _lib.check(lib.bhr_png_encode_device(renderer._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(n)))
+    _lib.check(encode(renderer._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8)), cap, C.byref(n)))
     return out[:n.value].tobytes()
 
 
@@ -102,9 +127,50 @@ def jpeg_restart_interval(width: int) -> int:
     return int(_lib.load().bhr_jpeg_restart_interval(int(width)))
 
 
-def quantize(image: np.ndarray) -> np.ndarray:
-    """save_image's 8-bit conversion: truncation, not rounding (render.py:423)."""
-    return (np.clip(image, 0, 1) * 255).astype(np.uint8)
+DITHERS = ("none", "blue")
+_DITHER_OFFSETS = ((0, 0), (21, 37), (43, 11))          # (ox, oy) of the R, G and B channels
+
+
+def dither_matrix() -> np.ndarray:
+    """The (64, 64) uint16 blue-noise rank matrix of the dithered quantiser (bhr_dither_matrix; host only)."""
+    m = np.empty(4096, dtype=np.uint16)
+    _lib.check(_lib.load().bhr_dither_matrix(m.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return m.reshape(64, 64)
+
+
+def _clip01(image: np.ndarray) -> np.ndarray:
+    """clip(x, 0, 1) in f32 with NaN -> 0, as the device's fminf(fmaxf(x, 0), 1)."""
+    x = np.asarray(image, dtype=np.float32)
+    return np.minimum(np.maximum(np.where(np.isnan(x), np.float32(0), x), np.float32(0)), np.float32(1))
+
+
+def dither_thresholds(height: int, width: int, row0: int = 0) -> np.ndarray:
+    """t(c, X, Y) = (M[(Y + oy_c) & 63][(X + ox_c) & 63] + 0.5) / 4096 for rows row0 .. row0 + height - 1 of the full image:
+    (height, width, 3) float32 (exact: 13 significant bits)."""
+    m = dither_matrix().astype(np.float32)
+    ys, xs = np.arange(row0, row0 + height)[:, None], np.arange(width)[None, :]
+    t = np.empty((height, width, 3), dtype=np.float32)
+    for c, (ox, oy) in enumerate(_DITHER_OFFSETS):
+        t[..., c] = (m[(ys + oy) & 63, (xs + ox) & 63] + np.float32(0.5)) / np.float32(4096.0)
+    return t
+
+
+def quantize(image: np.ndarray, dither: str = "none", row0: int = 0) -> np.ndarray:
+    """save_image's 8-bit conversion: truncation, not rounding (render.py:423).  ``dither="blue"``: the device's dithered
+    quantiser restated (bhr_set_dither): floor(clip(x, 0, 1) * 255 + t) in f32, the product and the sum rounded once each;
+    ``row0``: the image's first row in the full frame (a row block dithers as the whole frame does)."""
+    if dither not in DITHERS:
+        raise ValueError(f"dither must be one of {DITHERS}, got {dither!r}")
+    if dither == "none":
+        return (np.clip(image, 0, 1) * 255).astype(np.uint8)
+    x = _clip01(image)
+    v = x * np.float32(255.0)
+    return np.floor(v + dither_thresholds(x.shape[0], x.shape[1], row0)).astype(np.uint8)
+
+
+def quantize16(image: np.ndarray) -> np.ndarray:
+    """The 16-bit conversion of bhr_read_final_u16: (uint16)(clip(x, 0, 1) * 65535) in f32, truncated; NaN -> 0."""
+    return (_clip01(image) * np.float32(65535.0)).astype(np.uint16)
 
 
 class FrameSink:
@@ -113,12 +179,15 @@ class FrameSink:
     ``submit(path)`` quantises the renderer's FINAL layer on the device, starts the copy into a pinned
     host slot and returns; worker threads encode and write.  ``drain()`` waits for the files.
     ``level=DEVICE`` encodes on the GPU as well: the workers only fetch the finished bytes and write them.
-    ``codec="jpeg"``: baseline JPEG of ``quality`` 1..100, always coded on the GPU (``level`` is not used)."""
+    ``codec="jpeg"``: baseline JPEG of ``quality`` 1..100, always coded on the GPU (``level`` is not used).
+    ``bit_depth=16`` (PNG only): the files are 16-bit PNGs of the renderer's 16-bit rows (bhr_sink_create_png16)."""
 
     def __init__(self, renderer, slots: int = 0, workers: int = 0, level: int = VIDEO_LEVEL, codec: str = "png",
-                 quality: int = JPEG_QUALITY):
+                 quality: int = JPEG_QUALITY, bit_depth: int = 8):
         if codec not in ("png", "jpeg"):
             raise ValueError(f"codec must be 'png' or 'jpeg', got {codec!r}")
+        if bit_depth not in (8, 16) or (bit_depth == 16 and codec != "png"):
+            raise ValueError(f"bit_depth must be 8, or 16 with codec 'png'; got {bit_depth!r} with {codec!r}")
         if workers <= 0:
             workers = max(1, min(16, len(os.sched_getaffinity(0)) - 1))
         if slots <= 0:
@@ -128,9 +197,12 @@ class FrameSink:
         self._renderer = renderer          # keeps the context alive
         if codec == "jpeg":
             _lib.check(self._lib.bhr_sink_create_jpeg(renderer._ctx, slots, workers, int(quality), C.byref(self._sink)))
+        elif bit_depth == 16:
+            _lib.check(self._lib.bhr_sink_create_png16(renderer._ctx, slots, workers, level, C.byref(self._sink)))
         else:
             _lib.check(self._lib.bhr_sink_create(renderer._ctx, slots, workers, level, C.byref(self._sink)))
         self.workers, self.slots, self.level, self.codec, self.quality = workers, slots, level, codec, quality
+        self.bit_depth = bit_depth
         import weakref
         if not hasattr(renderer, "_sinks"):
             renderer._sinks = []

@@ -521,6 +521,27 @@ class HipRenderer:
         _lib.check(self._lib.bhr_read_final_u8(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
+    def read_final_u16(self) -> np.ndarray:
+        """The last frame at 16 bits per sample, (rows, width, 3) uint16: (uint16)(clip(x, 0, 1) * 65535), truncated
+        (bhr_read_final_u16; output.quantize16 restates it)."""
+        out = np.empty((self.rows, self.width, 3), dtype=np.uint16)
+        _lib.check(self._lib.bhr_read_final_u16(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint16))))
+        return out
+
+    def set_dither(self, mode) -> None:
+        """Quantisation of the u8 rows: "none" / 0 (default: truncation) or "blue" / 1 (blue-noise dither, bhr_set_dither).
+        Every consumer of the u8 rows -- read_final_u8, the PNG and JPEG encoders, the sinks, the y4m stream -- follows."""
+        names = {"none": 0, "blue": 1, 0: 0, 1: 1}
+        if isinstance(mode, bool) or mode not in names:
+            raise ValueError(f"dither must be 'none' (0) or 'blue' (1), got {mode!r}")
+        _lib.check(self._lib.bhr_set_dither(self._ctx, names[mode]))
+        self._dither = ("none", "blue")[names[mode]]
+
+    @property
+    def dither(self) -> str:
+        """"none" or "blue": the mode last chosen with set_dither."""
+        return getattr(self, "_dither", "none")
+
     def render(self, cam_pos: List[float], fov: float, frame: int = 0,
                skip_differentials: bool = False, skip_bloom: bool = False) -> np.ndarray:
         """One frame -> (rows, width, 3) float32 in [0, 1]  (render.py:3865-3923)."""

@@ -319,6 +319,7 @@ BHR_API int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]);
  *   "group_threads"   BHR_GROUP_THREADS   -1 one submitting thread per tile where the tiles sit on distinct devices, 0 / 1 force
  *   "group_schedule"  BHR_GROUP_SCHEDULE  -1 by flags, else pipelined where a halo copy can hide (exact-f32 post-pass on distinct
  *                                         devices) and serial otherwise; 0 serial, 1 pipelined (explicit flags still win)
+ *   "png16_menu"      BHR_PNG16_MENU      1 (default) the 16-bit device PNG encoder codes from its own menu, 0 from the 8-bit one (A/B runs)
  * (bhr_create only: BHR_FRAME_SLOTS.) */
 BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
 /* Diagnostics (tests): the split-f16 post-pass's packed intermediates of the last frame as raw bytes -- which = 0 the H pass's
@@ -338,6 +339,33 @@ BHR_API int32_t bhr_lens_flare_sums(bhr_ctx *ctx, double *out3);
 /* save_image()'s quantisation (clip*255 truncated to u8, render.py:423) done
  * on the device: (row1-row0, width, 3) u8.  Synchronises. */
 BHR_API int32_t bhr_read_final_u8(bhr_ctx *ctx, uint8_t *out);
+/* The frame at 16 bits per sample: q16 = (uint16)(int)(clip(x, 0, 1) * 65535.0f), the truncation of the 8-bit path with
+ * 65536 levels (the product rounded to f32; NaN -> 0).  (row1-row0, width, 3) u16, native endian.  A kernel of its own
+ * quantises the f32 FINAL frame on demand (a frame that kept only its u8 rows gets the f32 frame from its V pass first) into
+ * a buffer of the frame slot that exists from the first use on; nothing changes for a context that never asks.  Row-block
+ * contexts and two frame slots work as for bhr_read_final_u8.  Synchronises.  The 16-bit PNG encoders (bhr_output.h) read
+ * the same rows. */
+BHR_API int32_t bhr_read_final_u16(bhr_ctx *ctx, uint16_t *out);
+/* Dithered 8-bit quantisation.  mode BHR_DITHER_NONE (default): the u8 rows are save_image's truncation, as ever.
+ * BHR_DITHER_BLUE: q8 = (uint8)floorf(clip(x, 0, 1) * 255.0f + t(c, X, Y)) with
+ *   t(c, X, Y) = (M[(Y + oy_c) & 63][(X + ox_c) & 63] + 0.5f) / 4096.0f,
+ * M the 64 x 64 blue-noise rank matrix of bhr_dither_matrix, (X, Y) the pixel's coordinates in the FULL image (a row block
+ * dithers exactly as the whole frame does) and (ox, oy) = (0, 0) for R, (21, 37) for G, (43, 11) for B.  f32 arithmetic, the
+ * product and then the sum rounded once each; the largest value is 255 + 4095.5 / 4096 < 256.  A flat value v thus rounds up
+ * in exactly the share frac(255 v) of the pixels (to 1 / 4096), and the pattern that decides which has no energy at low
+ * spatial frequencies: bands become fine noise.  The pattern does not depend on the frame.
+ * While dither is on EVERY consumer of the context's u8 rows sees the dithered rows: bhr_read_final_u8, the device and host
+ * PNG paths, the sinks, the JPEG encoder and the y4m stream.  The frame takes the route of a flared frame: its V pass keeps
+ * f32 and a kernel of its own quantises afterwards.  bhr_group_render* with BHR_GATHER_U8 and bhr_tile_render store their u8
+ * rows from inside the V pass into peer memory: with dither on they return BHR_ERR_INVALID.  Changing the mode drains the
+ * frames in flight and invalidates the u8 rows in memory (the next reader gets them under the new mode, bit for bit what a
+ * context that never changed mode gives).  bhr_read_final_u16 is not dithered. */
+#define BHR_DITHER_NONE 0
+#define BHR_DITHER_BLUE 1
+BHR_API int32_t bhr_set_dither(bhr_ctx *ctx, int32_t mode);
+/* The rank matrix M, row-major (out[64 y + x] = M[y][x]): every value of 0 .. 4095 once; void-and-cluster on a torus with a
+ * Gaussian energy, generated by tools/make_blue_noise.py and compiled in.  Host only, needs no GPU. */
+BHR_API int32_t bhr_dither_matrix(uint16_t out[4096]);
 BHR_API int32_t bhr_get_counters(bhr_ctx *ctx, bhr_counters *out);
 /* Last BHR_MATH_HYBRID march of this context: out_tiles = {tiles marched strict, tiles of the row block},
  * out_band = {lo, hi}: the strict band [b_c - lo, b_c + hi] of impact parameters, in r_s. */

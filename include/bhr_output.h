@@ -23,6 +23,14 @@ BHR_API int32_t bhr_png_encode(const uint8_t *rgb, int32_t w, int32_t h, int32_t
 /* Image.fromarray(rgb).save(path): encode and write atomically (path.tmp, then rename). */
 BHR_API int32_t bhr_png_write(const char *path, const uint8_t *rgb, int32_t w, int32_t h, int32_t level, int32_t threads);
 
+/* The same three for 16 bits per sample: rgb is (h, w, 3) u16, native endian; the file is colour type 2 at bit depth 16 with the
+ * samples big-endian, as PNG wants them.  Same adaptive filters (at a filter distance of 6 bytes: one pixel), parallel row bands
+ * and atomic write.  The decoded samples equal the input exactly. */
+BHR_API int64_t bhr_png_bound16(int32_t w, int32_t h);
+BHR_API int32_t bhr_png_encode16(const uint16_t *rgb, int32_t w, int32_t h, int32_t level, int32_t threads,
+                                 uint8_t *out, int64_t cap, int64_t *out_len);
+BHR_API int32_t bhr_png_write16(const char *path, const uint16_t *rgb, int32_t w, int32_t h, int32_t level, int32_t threads);
+
 /* PNG encoding on the device (csrc/png_device.hip).  The frame is filtered (the five PNG filters, the minimum sum of
  * absolute residuals per scanline) and entropy coded in HBM: one dynamic-Huffman deflate block and one IDAT chunk per
  * scanline, the prefix code of each scanline picked from a menu of 16 static codes (no LZ77 matches), chunk CRC-32 and
@@ -45,12 +53,28 @@ BHR_API int32_t bhr_png_encode_device(bhr_ctx *ctx, uint8_t *out, int64_t cap, i
  * the deflate block header announcing that code, LSB first.  *n_tables receives the menu size. */
 BHR_API int32_t bhr_png_device_menu(int32_t k, uint32_t *codes, uint32_t *hdr_words, uint32_t *hdr_bits, int32_t *n_tables);
 
+/* 16-bit PNG on the device: the same scheme -- one scanline = one deflate block = one IDAT chunk, the five filters by the
+ * minimum sum of absolute residuals (filter distance 6 bytes), Huffman coding only from a static menu, CRC-32 and Adler-32 on
+ * the device -- over the context's 16-bit rows (bhr_read_final_u16; big-endian in the file).  The menu is the encoder's own:
+ * 15 codes fitted to the mixture a filtered 16-bit scanline is (peaked high bytes, nearly uniform low bytes) + the flat code.
+ * Any PNG reader decodes the file to exactly the samples of bhr_read_final_u16.
+ *   bhr_png16_device_bound: capacity that always suffices for a w x h frame (0 beyond the width limit).
+ *   bhr_png16_device_max_width: the same LDS budget holds half as many pixels as at 8 bits: 8530 (7680 fits).
+ *   bhr_png16_encode_device: quantise the context's FINAL layer to 16 bits and encode it; BHR_ERR_INVALID beyond the width limit.
+ *   bhr_sink_create_png16: an ordinary bhr_sink (submit, drain, destroy below) whose files are 16-bit PNGs; level is
+ *     BHR_PNG_DEVICE or a zlib level 0..9 (the host encoder, bhr_png_encode16, on the sink's workers). */
+BHR_API int64_t bhr_png16_device_bound(int32_t w, int32_t h);
+BHR_API int32_t bhr_png16_device_max_width(void);
+BHR_API int32_t bhr_png16_encode_device(bhr_ctx *ctx, uint8_t *out, int64_t cap, int64_t *out_len);
+
 /* Frame sink.  bhr_sink_submit quantises the context's FINAL layer on the device (save_image's
  * truncation), starts an asynchronous copy into one of `slots` pinned host buffers and returns; `workers`
  * host threads wait for the copy, encode and write `path`.  The caller goes on to render the next frame
  * on the same stream meanwhile.  submit blocks only while every slot is busy. */
 typedef struct bhr_sink bhr_sink;
 BHR_API int32_t bhr_sink_create(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t level, bhr_sink **out);
+/* The sink of 16-bit PNG files (see bhr_png16_encode_device above). */
+BHR_API int32_t bhr_sink_create_png16(bhr_ctx *ctx, int32_t slots, int32_t workers, int32_t level, bhr_sink **out);
 BHR_API int32_t bhr_sink_submit(bhr_sink *sink, const char *path);
 /* Wait until every submitted frame is on disk; returns the first error a worker met, if any.
  * frames_written / bytes_written may be NULL. */
