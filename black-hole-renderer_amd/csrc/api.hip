@@ -251,7 +251,7 @@ int32_t bhr_ensure_outputs(bhr_ctx *ctx, uint32_t need) {
     }
     // re-run the frame's V pass for what nobody asked for up front (its inputs -- bg, disk, the H-blur planes -- are still the
     // slot's, and it records which post-pass the frame ran): same kernels, same bits
-    BHR_TRY(bhr_launch_bloom_v_rows(ctx, f.frame_with_bloom, 0, ctx->rows, missing, nullptr, nullptr));
+    BHR_TRY(bhr_launch_bloom_v_rows(ctx, f.frame_with_bloom, 0, ctx->rows, missing, nullptr, nullptr, nullptr));
     f.have |= missing;
     return BHR_OK;
 }
@@ -279,8 +279,8 @@ int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags, bool exact) {
     return BHR_OK;
 }
 
-int32_t bhr_frame_post(bhr_ctx *ctx, int32_t with_bloom, uint32_t want) {
-    BHR_TRY(bhr_launch_bloom_v_rows(ctx, with_bloom, 0, ctx->rows, want, nullptr, nullptr));
+int32_t bhr_frame_post(bhr_ctx *ctx, int32_t with_bloom, uint32_t want, unsigned long long *zero_cell) {
+    BHR_TRY(bhr_launch_bloom_v_rows(ctx, with_bloom, 0, ctx->rows, want, nullptr, nullptr, zero_cell));
     bhr_slot(ctx).have = want;
     return BHR_OK;
 }
@@ -719,27 +719,24 @@ int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     const int with_bloom = (flags & BHR_SKIP_BLOOM) ? 0 : 1;
     BHR_TRY(bhr_frame_begin(ctx, flags));
     // an adaptively supersampled frame: the k = 1 march, then detect + refinement inside the same march bracket
-    ctx->defer_march_end = ctx->ada_k > 1;
-    ctx->ada_frame = ctx->ada_k > 1;
-    int32_t rc_m = bhr_launch_march(ctx, cam, flags);  // records the ring slot's march events
-    ctx->defer_march_end = 0;
-    BHR_TRY(rc_m);
-    if (ctx->ada_k > 1) BHR_TRY(bhr_launch_adaptive(ctx, cam, flags));
+    const bool adaptive = ctx->ada_k > 1;
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss};
+    ctx->ada_frame = adaptive;
+    BHR_TRY(bhr_launch_march(ctx, call));              // records the ring slot's march events
+    if (adaptive) BHR_TRY(bhr_launch_adaptive(ctx, call));
     // the march's end is the timing ring's event (recorded by the launcher): an event of its own between the march and the
     // H pass is another ~5 us barrier packet in the frame's stream (kernel-trace gaps: 10 us with two records, 0 with none)
     f.march_done = ctx->ring_ev[ring * 3 + 1];
-    if (with_bloom) BHR_TRY(bhr_launch_bloom_h(ctx));
+    if (with_bloom) BHR_TRY(bhr_launch_bloom_h(ctx, nullptr, 0));
     // the V kernel clears the counter cell BHR_MAX_FRAME_SLOTS frames ahead: no frame that may be in flight on another
     // slot's stream is counting into it (the next frames' marches may already be running)
-    ctx->v_zero_cell = ctx->d_steps_ring + (size_t)((ring + BHR_MAX_FRAME_SLOTS) % BHR_TIMING_RING) * BHR_STEP_CELL;
+    unsigned long long *zero_cell = ctx->d_steps_ring + (size_t)((ring + BHR_MAX_FRAME_SLOTS) % BHR_TIMING_RING) * BHR_STEP_CELL;
     // what the frame stores: the layers the context's consumers asked for (bhr_set_outputs); the lens flare works on the f32
     // frame, so a flared frame keeps it and quantises afterwards
     uint32_t want = ctx->out_want;
     if (flags & BHR_LENS_FLARE) want = (want | BHR_OUT_F32) & ~BHR_OUT_U8;
     if (ctx->dither) want = (want | BHR_OUT_F32) & ~BHR_OUT_U8;      // dithered rows: the same route (quantize.hip)
-    const int32_t rc_v = bhr_frame_post(ctx, with_bloom, want);
-    ctx->v_zero_cell = nullptr;
-    BHR_TRY(rc_v);
+    BHR_TRY(bhr_frame_post(ctx, with_bloom, want, zero_cell));
     if (flags & BHR_LENS_FLARE) {
         if (ctx->rows != ctx->cfg.height)
             return bhr_fail(BHR_ERR_INVALID, "bhr_render: the lens flare needs whole-frame sums; use bhr_group_render for row blocks");
@@ -881,7 +878,6 @@ int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
         BHR_HIP(hipStreamWaitEvent(f.stream, ctx->scene_ev, 0));
     }
     const int ring = (int)(ctx->ring_head % BHR_TIMING_RING);
-    ctx->cur_slot = ring;
     ctx->active_slot = k;
     ctx->stream = f.stream;
     const int32_t rc = render_on_slot(ctx, cam, flags, k, ring);
@@ -948,8 +944,8 @@ int32_t bhr_bloom(bhr_ctx *ctx) {
     // kernels cannot carry: the pass stays one function of its input whatever the arithmetic
     BHR_TRY(bhr_frame_begin(ctx, 0, bhr_slot(ctx).disk_wide != 0));
     if (bhr_slot(ctx).frame_split) BHR_TRY(bhr_launch_bloom_pack(ctx)); // the disk layer may be the caller's (bhr_write_layer)
-    BHR_TRY(bhr_launch_bloom_h(ctx));
-    return bhr_frame_post(ctx, 1, BHR_OUT_F32 | BHR_OUT_BLUR);
+    BHR_TRY(bhr_launch_bloom_h(ctx, nullptr, 0));
+    return bhr_frame_post(ctx, 1, BHR_OUT_F32 | BHR_OUT_BLUR, nullptr);
 }
 
 int32_t bhr_debug_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes, int32_t *geom) {

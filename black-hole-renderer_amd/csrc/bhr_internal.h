@@ -107,14 +107,28 @@ struct BhrMarchArgs {
     int32_t out_width, out_rows;   // the output frame's row block: the store pitch and rows of bg / disk / sum
 };
 
-// A partial march launch: the tiles of `d_list` only.  Set by bhr_launch_march_hybrid for each of its launches (strict
-// list, fast list, fix list and the empty parts that bracket them) and consumed by bhr_launch_march (march_launch.hip).
+// A partial march launch: the tiles of `d_list` only.  bhr_launch_march_hybrid builds one for each of its launches (strict
+// list, fast list, fix list and the empty parts that bracket them) and passes it to bhr_launch_march (null: the whole block).
 struct bhr_march_part {
     const int32_t *d_list;   // device list of this launch
     int32_t n;
-    int32_t active, first, last;
+    int32_t first, last;     // the first part records the start event and clears an untimed counter, the last one records the end event
     int32_t math;            // the arithmetic of this launch: BHR_MATH_FAST or BHR_MATH_STRICT
     int32_t repair;          // 1: the fast object's guard kernel (marks lanes on a discontinuity, appends them to the fix list); 2: the strict fix kernel over that list
+    unsigned int *fix_count; // the frame slot's fix list (owned by hybrid.hip), null / 0 without guards
+    int32_t *fix_list;
+    int32_t fix_cap;
+};
+
+// One march call, built by the caller: what bhr_launch_march, bhr_launch_march_hybrid and bhr_launch_adaptive work from.
+struct bhr_march_call {
+    const bhr_camera *cam;
+    uint32_t flags;
+    hipStream_t stream;      // the stream of the launch
+    int32_t slot;            // timing-ring slot of a bhr_render (its events and counter cell), -1: untimed (the context's scalar ones)
+    bool time_untimed;       // an untimed launch records its march-end event too (BHR_GROUP_TIME_MARCH); off, the tile's stream carries no event between march and H pass
+    bool defer_end;          // the caller records the march-end event (adaptive frames: the refinement follows the base march)
+    int32_t ss;              // supersampling factor of the frame being marched
 };
 
 // The march kernels by what they do; each compilation of march.hip returns its own instantiation of a name (or null) from
@@ -251,10 +265,8 @@ struct bhr_ctx {
     hipEvent_t ring_ev[BHR_TIMING_RING * 3];
     unsigned long long *d_steps_ring;   // one ray-step counter cell (BHR_STEP_CELL words) per ring slot
     unsigned long long *d_steps_fold;   // folded cells (BHR_TIMING_RING words)
-    unsigned long long *v_zero_cell;    // counter cell the next bloom V launch clears (next ring slot), or null
     int64_t ring_head;                  // frames recorded since reset
     unsigned long long *last_steps_ptr; // counter the last march accumulated into
-    int32_t cur_slot;                   // ring slot of the bhr_render in flight (-1: untimed launch)
     int32_t last_slot;                  // ring slot of the last completed bhr_render, -1 after a group render
 
     // scene
@@ -299,10 +311,6 @@ struct bhr_ctx {
     int32_t dither;
     uint16_t *d_dither;        // the 64 x 64 rank matrix on the device, on first use
     uint32_t out_want;         // BHR_OUT_* the frames of this context store (bhr_set_outputs; default: the f32 frame)
-    // rows of this block that neighbouring row blocks need for their V pass: the H pass writes them straight into those
-    // blocks' planes (set by group.hip for the duration of a group / tile render)
-    struct { void *pb; int32_t pbr, gr; } mirrors[6];
-    int32_t n_mirrors;
     bhr_options opt;           // the BHR_* environment switches, read once by bhr_create
     float *d_wsum_h;           // (3, W) in-bounds weight sums, then (3, W) the split H pass's multiplier 2^-10 / sum
     float *d_wsum_v;           // (3, H), then (3, H) the split V pass's multiplier 2^-24 / sum
@@ -320,12 +328,7 @@ struct bhr_ctx {
     int32_t ada_last_slot;     // frame slot of the last adaptive frame (-1: none since the setting changed), and
     int32_t ada_last_math;     // the arithmetic bhr_resolve_math gave it
     int32_t ada_frame;         // the last bhr_render was an adaptive frame (bhr_get_counters adds the refinement's rays)
-    int32_t defer_march_end;   // bhr_launch_march leaves the march-end event to its caller (the refinement follows the base march)
-    bhr_march_part part;       // partial launch in progress (inactive: whole block)
     void *hybrid;              // hybrid.hip: tile classification cache
-    unsigned int *fix_count;   // fix list of the hybrid march being launched (owned by hybrid.hip, per frame slot)
-    int32_t *fix_list;
-    int32_t fix_cap;
     void *pipe;                // group.hip: streams, events and band lists of the pipelined row-block path
     uint8_t *d_gather_u8;      // (H, W, 3) u8: quantised frame gathered from the tiles (BHR_GATHER_U8), on tile 0
     int32_t *d_flare_prog;     // lens flare (flare.hip): pairwise tree of the ragged last chunk; shared by the slots, read-only
@@ -339,7 +342,6 @@ struct bhr_ctx {
     bhr_counters counters;
     int32_t last_flags;
     int32_t timing_valid;
-    int32_t group_time_march;  // group / tile renders: also record the march-end event (BHR_GROUP_TIME_MARCH); off, the tile's stream carries no event between march and H pass
     int32_t march_end_recorded;
 };
 
@@ -347,22 +349,37 @@ struct bhr_ctx {
 inline bhr_frame_slot &bhr_slot(bhr_ctx *ctx) { return ctx->slots[ctx->active_slot]; }
 inline const bhr_frame_slot &bhr_slot(const bhr_ctx *ctx) { return ctx->slots[ctx->active_slot]; }
 
-// The frame the march marches: the context's own, or under supersampling (ctx->ss = k > 1) the one k times finer along
+// The frame the march marches: the context's own, or under supersampling (factor k > 1) the one k times finer along
 // both axes, at pixel pitch / k.  The tile grid, the tile order, the hybrid classification and the fix lists live on it.
 struct bhr_fine_frame {
     int32_t width, height, row0, rows;
 };
-inline bhr_fine_frame bhr_fine(const bhr_ctx *ctx) {
-    const int32_t k = ctx->ss;
+inline bhr_fine_frame bhr_fine(const bhr_ctx *ctx, int32_t k) {
     return {ctx->cfg.width * k, ctx->cfg.height * k, ctx->cfg.row0 * k, ctx->rows * k};
 }
 // k is a power of two: the fine pitch is exact, and the pitch of build_camera(k W, k H) bit for bit
-inline bhr_camera bhr_fine_camera(const bhr_ctx *ctx, const bhr_camera *cam) {
+inline bhr_camera bhr_fine_camera(const bhr_camera *cam, int32_t k) {
     bhr_camera c = *cam;
-    c.pixel_width /= (float)ctx->ss;
-    c.pixel_height /= (float)ctx->ss;
+    c.pixel_width /= (float)k;
+    c.pixel_height /= (float)k;
     return c;
 }
+inline int32_t bhr_log2(int32_t k) { return k == 8 ? 3 : k == 4 ? 2 : k == 2 ? 1 : 0; }   // of a supersampling factor (1, 2, 4, 8)
+
+// The march events of a call: timed launches (bhr_render) use their ring slot's, the others the context's scalar ones.
+inline hipEvent_t bhr_march_start_event(const bhr_ctx *ctx, int32_t slot) { return slot >= 0 ? ctx->ring_ev[slot * 3 + 0] : ctx->ev[0]; }
+inline hipEvent_t bhr_march_end_event(const bhr_ctx *ctx, int32_t slot) { return slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1]; }
+// anti_alias "disabled": the reference still integrates the differentials (skip_diff = 0 on
+// the CLI path) but never reads them (render.py:2957-2959) => skipping them is pixel-identical.
+inline bool bhr_want_diff(const bhr_ctx *ctx, uint32_t flags) { return ctx->cfg.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS); }
+
+// A row block's packed H-blur planes as a neighbour's split-f16 H pass stores its halo rows into them (bhr_launch_bloom_h;
+// group.hip fills the array for the duration of one group / tile render)
+#define BHR_MAX_MIRRORS 6
+struct bhr_mirror {
+    void *pb;
+    int32_t pbr, gr;
+};
 
 // error plumbing (api.hip)
 int32_t bhr_fail(int32_t code, const char *fmt, ...);
@@ -398,16 +415,16 @@ int32_t bhr_leave_frame(bhr_ctx *ctx);
 
 // launchers (each lives next to its kernels)
 int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags);                          // march_launch.hip: BHR_MATH_* of a frame
-int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);         // march_launch.hip: every march launch
+int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part = nullptr);   // march_launch.hip: every march launch
 int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds); // march_launch.hip: registers / LDS of the frame kernel
 const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);       // march.o (ss: the supersampled twin)
 const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.o
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.o
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.o
-int32_t bhr_ensure_tile_order(bhr_ctx *ctx);                                           // march_launch.hip: builds d_/h_tile_order
-int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);     // hybrid.hip
-// march_launch.hip: detect + refinement of an adaptively supersampled frame, behind its base march on ctx->stream; records the march-end event
-int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
+int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss);                               // march_launch.hip: builds d_/h_tile_order of the frame marched with factor ss
+int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_march_call &call);             // hybrid.hip
+// march_launch.hip: detect + refinement (ctx->ada_k) of an adaptively supersampled frame, behind its base march `call` on the same stream; records the march-end event
+int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call);
 // hybrid.hip: strict flag per 8x8 tile of the frame k times finer than the context's (the rule a bhr_set_supersample(k) hybrid
 // frame classifies its tiles by), in a buffer of the active frame slot, made on ctx->stream and cached on the view key
 int32_t bhr_hybrid_fine_flags(bhr_ctx *ctx, const bhr_camera *cam, int32_t k, const uint8_t **d_flags, int32_t *tiles_x);
@@ -417,17 +434,20 @@ int32_t bhr_bloom_prepare(bhr_ctx *ctx);
 int32_t bhr_split_nt(int32_t R);
 void bhr_split_geometry(const bhr_ctx *ctx, bhr_split_geom *g);
 int32_t bhr_launch_bloom_pack(bhr_ctx *ctx);                               // d_disk -> d_pa
-int32_t bhr_launch_bloom_h(bhr_ctx *ctx);
+// H pass; split frames: also into the n_mirrors planes of neighbouring row blocks that need rows of this one for their V pass
+int32_t bhr_launch_bloom_h(bhr_ctx *ctx, const bhr_mirror *mirrors, int32_t n_mirrors);
 // V pass + combine over local rows [r0, r1) storing the BHR_OUT_* layers in `want`; gather_u8 / gather_f32 non-null: the
-// u8 / f32 rows go into that (H, W, 3) frame buffer (a row-block gather, possibly on a peer device) instead of the context's own
-int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, int32_t r1, uint32_t want, uint8_t *gather_u8, float *gather_f32);
+// u8 / f32 rows go into that (H, W, 3) frame buffer (a row-block gather, possibly on a peer device) instead of the context's own;
+// zero_cell non-null: the ray-step counter cell the launch clears (bhr_render: a ring slot ahead)
+int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, int32_t r1, uint32_t want, uint8_t *gather_u8, float *gather_f32,
+                                unsigned long long *zero_cell);
 int32_t bhr_bloom_v_tile_rows(bhr_ctx *ctx);                               // output rows per V-pass block
 int32_t bhr_activate_slot(bhr_ctx *ctx, int32_t k);                        // api.hip: points the launchers at frame slot k (allocating it)
 // api.hip: decides the frame's arithmetic / post-pass kernels (exact: the exact f32 ones whatever the arithmetic) and makes
 // sure their buffers exist (before the march is launched)
 int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags, bool exact = false);
 // api.hip: the whole-block V pass of a frame into the context's own buffers, recording what it stored
-int32_t bhr_frame_post(bhr_ctx *ctx, int32_t with_bloom, uint32_t want);
+int32_t bhr_frame_post(bhr_ctx *ctx, int32_t with_bloom, uint32_t want, unsigned long long *zero_cell);
 // api.hip: makes the BHR_OUT_* layers in `need` of the active slot's last frame exist (re-runs its V pass for what is missing)
 int32_t bhr_ensure_outputs(bhr_ctx *ctx, uint32_t need);
 void bhr_pipe_free(bhr_ctx *ctx);                                          // group.hip

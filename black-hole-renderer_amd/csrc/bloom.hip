@@ -333,7 +333,7 @@ struct Mirror {                // a neighbouring row block's pb planes, written 
     _Float16 *pb;
     int32_t pbr, pend, gr;     // its plane: first / past-the-last global row, groups per (channel, half)
 };
-constexpr int MAX_MIRRORS = 6;
+constexpr int MAX_MIRRORS = BHR_MAX_MIRRORS;
 #ifndef BHR_SPLIT_SUBS
 #define BHR_SPLIT_SUBS 2
 #endif
@@ -864,8 +864,8 @@ int32_t bhr_launch_bloom_pack(bhr_ctx *ctx) {
     return BHR_OK;
 }
 
-// H pass over the context's rows.  Split frames: also into the planes of the row blocks in ctx->mirrors (group.hip).
-int32_t bhr_launch_bloom_h(bhr_ctx *ctx) {
+// H pass over the context's rows.  Split frames: also into the planes of the row blocks in `mirrors` (group.hip).
+int32_t bhr_launch_bloom_h(bhr_ctx *ctx, const bhr_mirror *mirrors, int32_t n_mirrors) {
     const int W = ctx->cfg.width, R = ctx->bloom_R;
     BHR_TRY(bhr_bloom_prepare(ctx));
     const bhr_frame_slot &f = bhr_slot(ctx);
@@ -881,14 +881,14 @@ int32_t bhr_launch_bloom_h(bhr_ctx *ctx) {
         a.YB = g.YB; a.GP = g.GP; a.GR = g.GR; a.pbr = g.pbr;
         a.NT = g.NT; a.table_bytes = g.table_bytes; a.n_tx = g.n_tx;
         a.n_mirror = 0;
-        for (int m = 0; m < ctx->n_mirrors && m < MAX_MIRRORS; ++m) {
-            a.mirror[a.n_mirror].pb = (_Float16 *)ctx->mirrors[m].pb;
-            a.mirror[a.n_mirror].pbr = ctx->mirrors[m].pbr;
-            a.mirror[a.n_mirror].pend = ctx->mirrors[m].pbr + 8 * ctx->mirrors[m].gr;
-            a.mirror[a.n_mirror].gr = ctx->mirrors[m].gr;
+        for (int m = 0; m < n_mirrors && m < MAX_MIRRORS; ++m) {
+            a.mirror[a.n_mirror].pb = (_Float16 *)mirrors[m].pb;
+            a.mirror[a.n_mirror].pbr = mirrors[m].pbr;
+            a.mirror[a.n_mirror].pend = mirrors[m].pbr + 8 * mirrors[m].gr;
+            a.mirror[a.n_mirror].gr = mirrors[m].gr;
             ++a.n_mirror;
         }
-        if (ctx->n_mirrors > MAX_MIRRORS) return bhr_fail(BHR_ERR_INVALID, "bloom H: %d mirror planes (at most %d)", ctx->n_mirrors, MAX_MIRRORS);
+        if (n_mirrors > MAX_MIRRORS) return bhr_fail(BHR_ERR_INVALID, "bloom H: %d mirror planes (at most %d)", n_mirrors, MAX_MIRRORS);
         const SplitPlan pl = plan_segments(g.n_tx, g.YB, g.NT, ctx->opt.bloom_tiles);
         a.seg = pl.seg;
         a.n_seg = pl.n_seg;
@@ -912,7 +912,8 @@ int32_t bhr_bloom_v_tile_rows(bhr_ctx *ctx) { (void)ctx; return 32; }
 
 // V pass + combine over the local rows [r0, r1), storing what `want` names (BHR_OUT_*) into the context's buffers -- or,
 // for BHR_OUT_U8 / BHR_OUT_F32 with a non-null gather base, into the (H, W, 3) frame buffer of a row-block gather.
-int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, int32_t r1, uint32_t want, uint8_t *gather_u8, float *gather_f32) {
+int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, int32_t r1, uint32_t want, uint8_t *gather_u8, float *gather_f32,
+                                unsigned long long *zero_cell) {
     const int W = ctx->cfg.width, H = ctx->cfg.height, R = ctx->bloom_R;
     BHR_TRY(bhr_bloom_prepare(ctx));
     if (r0 < 0 || r1 > ctx->rows || r0 > r1) return bhr_fail(BHR_ERR_INVALID, "bloom V: rows [%d,%d) of %d", r0, r1, ctx->rows);
@@ -938,7 +939,7 @@ int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, in
         }
         a.sum = f.d_sum;
         a.out = out;
-        a.zero_cell = ctx->v_zero_cell;
+        a.zero_cell = zero_cell;
         a.W = W; a.WP = g.WP; a.H = H; a.row0 = ctx->cfg.row0;
         a.GR = g.GR; a.t_first = g.t_first;
         a.NT = g.NT; a.table_bytes = g.table_bytes; a.R = R;
@@ -959,7 +960,7 @@ int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, in
     dim3 grid((W + 127) / 128, (r1 - r0 + 31) / 32), block(256);
     const size_t lds = with_bloom ? (size_t)3 * (2 * R + 64 + 44) * sizeof(float) : 0;
     hipLaunchKernelGGL(bloom_v_f32_kernel, grid, block, lds, ctx->stream, f.d_hblur, f.d_bg, f.d_disk, out, ctx->d_wtab,
-                       ctx->d_wsum_v, W, H, ctx->cfg.row0, ctx->rows, R, with_bloom, ctx->v_zero_cell, r0, r1);
+                       ctx->d_wsum_v, W, H, ctx->cfg.row0, ctx->rows, R, with_bloom, zero_cell, r0, r1);
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }

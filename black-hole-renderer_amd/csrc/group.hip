@@ -48,7 +48,7 @@ struct TilePipe {
     int32_t linked, rank, world, split;
     float *nb_hblur[2];           // exact-f32 post-pass: the planes of the tile above [0] / below [1] (nullptr: none)
     int32_t nb_rows[2];
-    struct { void *pb; int32_t pbr, gr; } nb_split[2];   // split-f16 post-pass: their packed planes
+    bhr_mirror nb_split[2];   // split-f16 post-pass: their packed planes
     float *gather_f32;            // frame buffers on tile 0's device (its own pointers on rank 0)
     uint8_t *gather_u8;
     void *opened[4];              // what hipIpcCloseMemHandle has to release
@@ -260,10 +260,16 @@ int32_t finish(bhr_ctx **ctxs, int n, const int32_t *live, float *out_host) {
     return BHR_OK;
 }
 
-// the planes of the other tiles that hold rows of tile k: its H pass writes them there itself
-int32_t set_mirrors(bhr_ctx **ctxs, int n, int k) {
+// The march of a tile, on its stream: untimed (the context's scalar events and counter), and its end is recorded only on
+// request -- the event is a bubble between the march and the H pass (bhr_launch_march).
+bhr_march_call tile_march(bhr_ctx *c, const bhr_camera *cam, uint32_t flags) {
+    return {cam, flags, c->stream, /* slot */ -1, /* time_untimed */ (flags & BHR_GROUP_TIME_MARCH) != 0, /* defer_end */ false, c->ss};
+}
+
+// the planes of the other tiles that hold rows of tile k: its H pass writes them there itself (mirrors: BHR_MAX_MIRRORS entries)
+int32_t set_mirrors(bhr_ctx **ctxs, int n, int k, bhr_mirror *mirrors, int32_t *n_mirrors) {
     bhr_ctx *c = ctxs[k];
-    c->n_mirrors = 0;
+    *n_mirrors = 0;
     if (!bhr_slot(c).frame_split) return BHR_OK;
     const int reach = 16 * (bhr_split_nt(c->bloom_R) - 1);
     for (int q = 0; q < n; ++q) {
@@ -274,12 +280,9 @@ int32_t set_mirrors(bhr_ctx **ctxs, int n, int k) {
         if (!peer_ok(c, nb)) return bhr_fail(BHR_ERR_STATE, "group render: device %d cannot store into device %d's memory (no peer access)", c->cfg.device, nb->cfg.device);
         bhr_split_geom g;
         bhr_split_geometry(nb, &g);
-        if (c->n_mirrors >= (int)(sizeof(c->mirrors) / sizeof(c->mirrors[0])))
-            return bhr_fail(BHR_ERR_INVALID, "group render: tile %d feeds more than %d neighbouring tiles (row blocks thinner than the bloom radius / 3?)", k, c->n_mirrors);
-        c->mirrors[c->n_mirrors].pb = pb;
-        c->mirrors[c->n_mirrors].pbr = g.pbr;
-        c->mirrors[c->n_mirrors].gr = g.GR;
-        c->n_mirrors += 1;
+        if (*n_mirrors >= BHR_MAX_MIRRORS)
+            return bhr_fail(BHR_ERR_INVALID, "group render: tile %d feeds more than %d neighbouring tiles (row blocks thinner than the bloom radius / 3?)", k, *n_mirrors);
+        mirrors[(*n_mirrors)++] = {pb, g.pbr, g.GR};
     }
     return BHR_OK;
 }
@@ -306,16 +309,16 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
         bhr_ctx *c = ctxs[k];
         BHR_TRY(bhr_enter(c));
         BHR_TRY(bhr_activate_slot(c, 0));
-        c->cur_slot = -1;
         c->last_slot = -1;
         BHR_TRY(ensure_pipe(c));
         BHR_TRY(bhr_frame_begin(c, flags, !all_peer));
-        c->group_time_march = (flags & BHR_GROUP_TIME_MARCH) ? 1 : 0;
     }
     const bool halo = with_bloom && n > 1;
+    std::vector<bhr_mirror> mirrors((size_t)n * BHR_MAX_MIRRORS);      // per tile: BHR_MAX_MIRRORS entries, n_mirrors[k] of them set
+    std::vector<int32_t> n_mirrors((size_t)n, 0);
     if (halo)
         for (int k = 0; k < n; ++k)
-            if (!live || live[k]) BHR_TRY(set_mirrors(ctxs, n, k));
+            if (!live || live[k]) BHR_TRY(set_mirrors(ctxs, n, k, &mirrors[(size_t)k * BHR_MAX_MIRRORS], &n_mirrors[(size_t)k]));
     // schedule < 0: by what there is to hide.  The exact-f32 post-pass PULLS its halo rows (a copy stage: worth running under
     // the V pass of the middle rows on distinct devices); the split-f16 post-pass has none -- its neighbours' H kernels store
     // the rows themselves -- and its V pass in ONE launch behind the wait is never later than in chunks: the frame ends with
@@ -330,7 +333,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
         bhr_ctx *c = ctxs[k];
         BHR_HIP(hipSetDevice(c->cfg.device));
         TilePipe *p = (TilePipe *)c->pipe;
-        BHR_TRY(bhr_launch_march(c, cam, flags));
+        BHR_TRY(bhr_launch_march(c, tile_march(c, cam, flags)));
         // frames in flight (BHR_GROUP_ASYNC): this H pass stores into its neighbours' halo rows, which their previous frame's V
         // passes may still be reading -- wait for those on the device
         if (with_bloom && bhr_slot(c).frame_split)
@@ -338,15 +341,13 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
                 TilePipe *pq = q == k ? nullptr : (TilePipe *)ctxs[q]->pipe;
                 if (pq && pq->in_flight && needs_rows_of(ctxs[q], c, 16 * (bhr_split_nt(c->bloom_R) - 1) + 32)) BHR_HIP(hipStreamWaitEvent(c->stream, pq->frame_done, 0));
             }
-        if (with_bloom) BHR_TRY(bhr_launch_bloom_h(c));
+        if (with_bloom) BHR_TRY(bhr_launch_bloom_h(c, &mirrors[(size_t)k * BHR_MAX_MIRRORS], n_mirrors[(size_t)k]));
         // `halo_ready` (this tile's H pass is done: its neighbours may run the V pass of their edge rows).  An event record is a
         // ~5 us bubble in the stream: the pipelined schedule records it BEHIND the V pass of the middle rows (phase 3) -- the
         // neighbours are busy with their own middle rows until then -- the serial one here
         if (!pipelined || !with_bloom || !bhr_slot(c).frame_split) BHR_HIP(hipEventRecord(p->halo_ready, c->stream));
         return BHR_OK;
     }));
-    for (int k = 0; k < n; ++k)
-        if (!live || live[k]) ctxs[k]->n_mirrors = 0;
 
     // phase 2 (exact-f32 post-pass only): halo pulls behind the neighbours' H passes -- under the V pass of the middle rows
     // (copy stream) in the pipelined schedule
@@ -381,7 +382,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
                 for (int ci = 0; ci < n_chunks; ++ci)
                     if (!chunks[ci].needs_halo)
                         BHR_TRY(bhr_launch_bloom_v_rows(c, with_bloom, chunks[ci].r0, chunks[ci].r1, want, direct ? head->d_gather_u8 : nullptr,
-                                                        direct ? head->d_gather : nullptr));
+                                                        direct ? head->d_gather : nullptr, nullptr));
                 if (pipelined && with_bloom && bhr_slot(c).frame_split) BHR_HIP(hipEventRecord(p->halo_ready, c->stream));
                 continue;
             }
@@ -399,7 +400,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
             for (int ci = 0; ci < n_chunks; ++ci)
                 if (chunks[ci].needs_halo)
                     BHR_TRY(bhr_launch_bloom_v_rows(c, with_bloom, chunks[ci].r0, chunks[ci].r1, want, direct ? head->d_gather_u8 : nullptr,
-                                                    direct ? head->d_gather : nullptr));
+                                                    direct ? head->d_gather : nullptr, nullptr));
             bhr_slot(c).have = direct ? 0u : want;           // what sits in the tile's OWN buffers
             c->last_flags = (int32_t)flags;
             c->timing_valid = 1;
@@ -659,27 +660,19 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
     volatile uint64_t *mine = p->shm + (size_t)rank * BHR_TILE_SHM_WORDS;
     BHR_TRY(bhr_enter(ctx));
     BHR_TRY(bhr_activate_slot(ctx, 0));
-    ctx->cur_slot = -1;
     ctx->last_slot = -1;
     BHR_TRY(bhr_frame_begin(ctx, flags));
-    ctx->group_time_march = (flags & BHR_GROUP_TIME_MARCH) ? 1 : 0;
     if (with_bloom && bhr_slot(ctx).frame_split != p->split)
         return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the flags select the other post-pass arithmetic than the one the tiles were connected for");
     const bool halo = with_bloom && world > 1;
-    ctx->n_mirrors = 0;
+    bhr_mirror mirrors[2];
+    int32_t n_mirrors = 0;
     if (halo && p->split)
         for (int side = 0; side < 2; ++side)
-            if (p->nb_split[side].pb) {
-                ctx->mirrors[ctx->n_mirrors].pb = p->nb_split[side].pb;
-                ctx->mirrors[ctx->n_mirrors].pbr = p->nb_split[side].pbr;
-                ctx->mirrors[ctx->n_mirrors].gr = p->nb_split[side].gr;
-                ctx->n_mirrors += 1;
-            }
+            if (p->nb_split[side].pb) mirrors[n_mirrors++] = p->nb_split[side];
     // march -> H pass (the neighbours' halo rows with it) on the tile's stream
-    int32_t rc = bhr_launch_march(ctx, cam, flags);
-    if (rc == BHR_OK && with_bloom) rc = bhr_launch_bloom_h(ctx);
-    ctx->n_mirrors = 0;
-    BHR_TRY(rc);
+    BHR_TRY(bhr_launch_march(ctx, tile_march(ctx, cam, flags)));
+    if (with_bloom) BHR_TRY(bhr_launch_bloom_h(ctx, mirrors, n_mirrors));
     BHR_HIP(hipEventRecord(p->halo_ready, ctx->stream));
     uint32_t want = ((flags & BHR_GATHER_U8) ? BHR_OUT_U8 : 0u) | ((flags & BHR_GATHER_PEER) ? BHR_OUT_F32 : 0u);
     const bool direct = want != 0;
@@ -687,7 +680,7 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
     Chunk chunks[PIPE_MAX_CHUNKS];
     const int n_chunks = plan_chunks(ctx, halo && rank > 0, halo && rank < world - 1, bhr_bloom_v_tile_rows(ctx), true, chunks);
     auto v_chunk = [&](int ci) -> int32_t {
-        return bhr_launch_bloom_v_rows(ctx, with_bloom, chunks[ci].r0, chunks[ci].r1, want, direct ? p->gather_u8 : nullptr, direct ? p->gather_f32 : nullptr);
+        return bhr_launch_bloom_v_rows(ctx, with_bloom, chunks[ci].r0, chunks[ci].r1, want, direct ? p->gather_u8 : nullptr, direct ? p->gather_f32 : nullptr, nullptr);
     };
     // the rows that need no halo are queued now: they run while this rank waits for its neighbours below
     for (int ci = 0; ci < n_chunks; ++ci)

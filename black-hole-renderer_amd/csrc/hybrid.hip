@@ -120,9 +120,8 @@ __host__ __device__ inline double tile_pad(double span, double pad_f) {
 }
 
 // strict[t] = 1 for the tiles of this row block whose rays may have b in [b_c - lo, b_c + hi]; the tiles and `cam` are those of the
-// marched frame (bhr_fine, bhr_fine_camera)
-void classify(const bhr_ctx *ctx, const bhr_camera *cam, double lo, double hi, double pad_f, std::vector<uint8_t> &strict) {
-    const bhr_fine_frame fr = bhr_fine(ctx);
+// marched frame `fr` (bhr_fine, bhr_fine_camera)
+void classify(const bhr_ctx *ctx, const bhr_fine_frame &fr, const bhr_camera *cam, double lo, double hi, double pad_f, std::vector<uint8_t> &strict) {
     const int W = fr.width, H = fr.height, row0 = fr.row0, rows = fr.rows;
     const int tiles_x = (W + 7) / 8, tiles_y = (rows + 7) / 8;
     double cp[3], cr[3], cu[3], cf[3], tl[3];
@@ -451,12 +450,12 @@ extern "C" int32_t bhr_hybrid_repairs(bhr_ctx *ctx, int32_t out[2]) {
     return BHR_OK;
 }
 
-int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_t flags) {
+int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_march_call &call) {
     // the lists, the classification and the view key are those of the marched frame (supersampling: the fine one)
-    const bhr_camera fine_cam = bhr_fine_camera(ctx, out_cam);
+    const bhr_camera fine_cam = bhr_fine_camera(call.cam, call.ss);
     const bhr_camera *cam = &fine_cam;
-    const bhr_fine_frame fr = bhr_fine(ctx);
-    BHR_TRY(bhr_ensure_tile_order(ctx));
+    const bhr_fine_frame fr = bhr_fine(ctx, call.ss);
+    BHR_TRY(bhr_ensure_tile_order(ctx, call.ss));
     Hybrid *h = (Hybrid *)ctx->hybrid;
     if (!h) {
         h = new Hybrid();
@@ -515,7 +514,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
             // every march that reads the list this slot used so far has been submitted: its buffer is free once the slot's
             // stream has passed this point.  The next buffer of the ring was released that way three view changes ago.
             if (s.cur >= 0) {
-                BHR_HIP(hipEventRecord(s.used[s.cur], ctx->stream));
+                BHR_HIP(hipEventRecord(s.used[s.cur], call.stream));
                 s.used_set[s.cur] = 1;
             }
             const int nxt = (s.cur + 1) % LIST_RING;
@@ -558,7 +557,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
         }
     } else {
         if (new_view) {
-            classify(ctx, cam, lo, hi, pad_f, h->strict);
+            classify(ctx, fr, cam, lo, hi, pad_f, h->strict);
             int n = 0;
             for (int k = 0; k < ctx->tile_order_n; ++k) n += h->strict[(size_t)k];
             h->n_strict = n;
@@ -582,8 +581,8 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
             s.n_strict = n;
             for (int k = 0; k < base_n; ++k)
                 if (!h->strict[(size_t)base_list[k]]) s.h_pinned[n++] = base_list[k];
-            BHR_HIP(hipMemcpyAsync(s.d_list, s.h_pinned, (size_t)base_n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-            BHR_HIP(hipEventRecord(s.copied, ctx->stream));
+            BHR_HIP(hipMemcpyAsync(s.d_list, s.h_pinned, (size_t)base_n * sizeof(int32_t), hipMemcpyHostToDevice, call.stream));
+            BHR_HIP(hipEventRecord(s.copied, call.stream));
             s.pending = 1;
             memcpy(s.key, h->key, sizeof(s.key));
             s.base_n = base_n;
@@ -592,15 +591,14 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
             s.d_active = s.d_list;
         }
     }
-    const uint32_t f = flags & ~(BHR_FORCE_FAST | BHR_FORCE_STRICT | BHR_FORCE_HYBRID);
-    bhr_march_part p;
-    p.active = 1;
+    bhr_march_call part_call = call;                  // the parts' call: the arithmetic is the part's, the stream the list's
+    part_call.flags = call.flags & ~(BHR_FORCE_FAST | BHR_FORCE_STRICT | BHR_FORCE_HYBRID);
     // Two launches.  On ONE stream the fast list waits for the last strict wave (the chip drains in between); on TWO the
     // strict tiles run on the context's second stream beside the fast ones, which fill the slots they leave.
     // The bracket (start event, counter clear / end event) is an empty first / last part on the frame's own stream.
     // one stream where two frame slots keep frames in flight (the other frame's kernels fill this one's gaps, and every further
     // stream is one more place in HIP's queue lottery: DESIGN 7), two where a frame runs alone (row blocks, one slot)
-    int streams = ctx->opt.hybrid_streams > 0 ? ctx->opt.hybrid_streams : (ctx->n_slots > 1 && ctx->cur_slot >= 0 ? 1 : 2);
+    int streams = ctx->opt.hybrid_streams > 0 ? ctx->opt.hybrid_streams : (ctx->n_slots > 1 && call.slot >= 0 ? 1 : 2);
     if (s.n_strict == 0) streams = 1;                // nothing for a second stream to do (row blocks away from the hole's image)
     int32_t rc = BHR_OK;
     // The fast list's kernel carries guards: a lane that comes within a guard band of one of the algorithm's switches -- the
@@ -614,8 +612,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
     // relative precision at the plane: no exact zeros, and the third, dependent launch would cost 17 % of the fhd frame
     // rate (guard kernel +25 us, fix kernel 55 us: one strict wave's lifetime that nothing overlaps) -- off.
     // BHR_HYBRID_REPAIR=1 / 0 (environment of bhr_create) forces it on / off.
-    const bool aa = ctx->cfg.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS);
-    bool repair = aa || ctx->cfg.disk_tilt_deg != 0.0f;
+    bool repair = bhr_want_diff(ctx, call.flags) || ctx->cfg.disk_tilt_deg != 0.0f;
     if (ctx->opt.hybrid_repair >= 0) repair = ctx->opt.hybrid_repair != 0;
     FixList &fx = h->fix[ctx->active_slot];
     if (repair && !fx.d_list) {
@@ -628,45 +625,37 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
         BHR_HIP(hipMalloc((void **)&fx.d_list, (size_t)fx.cap * sizeof(int32_t)));
     }
     h->last_fix_slot = repair ? ctx->active_slot : -1;
-    ctx->fix_count = repair ? fx.d_count : nullptr;
-    ctx->fix_list = repair ? fx.d_list : nullptr;
-    ctx->fix_cap = repair ? fx.cap : 0;
-    auto launch = [&](const int32_t *list, int n, int first, int last, int kind) -> int32_t {   // kind 0 strict list, 1 fast list, 2 fix list
+    auto launch = [&](hipStream_t stream, const int32_t *list, int n, int first, int last, int kind) -> int32_t {   // kind 0 strict list, 1 fast list, 2 fix list
+        bhr_march_part p;
         p.d_list = list; p.n = n; p.first = first; p.last = last;
         p.math = kind == 1 ? BHR_MATH_FAST : BHR_MATH_STRICT;
         p.repair = kind == 0 ? 0 : (repair ? kind : 0);
-        ctx->part = p;
-        return bhr_launch_march(ctx, out_cam, f);
+        p.fix_count = repair ? fx.d_count : nullptr;
+        p.fix_list = repair ? fx.d_list : nullptr;
+        p.fix_cap = repair ? fx.cap : 0;
+        part_call.stream = stream;
+        return bhr_launch_march(ctx, part_call, &p);
     };
+    const hipStream_t main_stream = call.stream;
     if (streams == 1) {
         // longest rays first: the strict tiles are the ones around the photon ring
-        rc = launch(s.d_active, s.n_strict, 1, 0, 0);
-        if (rc == BHR_OK && repair) rc = hipMemsetAsync(fx.d_count, 0, sizeof(unsigned int), ctx->stream) == hipSuccess ? BHR_OK : bhr_fail(BHR_ERR_HIP, "hipMemsetAsync failed");
-        if (rc == BHR_OK) rc = launch(s.d_active + s.n_strict, base_n - s.n_strict, 0, repair ? 0 : 1, 1);
-        if (rc == BHR_OK && repair) rc = launch(nullptr, 0, 0, 1, 2);
+        rc = launch(main_stream, s.d_active, s.n_strict, 1, 0, 0);
+        if (rc == BHR_OK && repair) rc = hipMemsetAsync(fx.d_count, 0, sizeof(unsigned int), main_stream) == hipSuccess ? BHR_OK : bhr_fail(BHR_ERR_HIP, "hipMemsetAsync failed");
+        if (rc == BHR_OK) rc = launch(main_stream, s.d_active + s.n_strict, base_n - s.n_strict, 0, repair ? 0 : 1, 1);
+        if (rc == BHR_OK && repair) rc = launch(main_stream, nullptr, 0, 0, 1, 2);
     } else {
-        hipStream_t main_stream = ctx->stream;
-        rc = launch(nullptr, 0, 1, 0, 0);                                          // prologue on the frame's stream
+        rc = launch(main_stream, nullptr, 0, 1, 0, 0);                             // prologue on the frame's stream
         if (rc == BHR_OK) rc = bhr_aux_fork(ctx);
         // the fast list -- ten times the tiles of the strict one, it ends last -- rides the frame's own stream, so that the
         // post-pass follows it on the same hardware queue (a wait on another queue's event costs ~10 us after that queue's
         // kernel has ended; on a finished one, nothing); the strict list runs on the second stream
-        ctx->stream = bhr_slot(ctx).aux_stream;
-        if (rc == BHR_OK) rc = launch(s.d_active, s.n_strict, 0, 0, 0);
-        if (rc == BHR_OK) {
-            ctx->stream = main_stream;
-            if (repair && hipMemsetAsync(fx.d_count, 0, sizeof(unsigned int), ctx->stream) != hipSuccess) rc = bhr_fail(BHR_ERR_HIP, "hipMemsetAsync failed");
-            if (rc == BHR_OK) rc = launch(s.d_active + s.n_strict, base_n - s.n_strict, 0, 0, 1);
-            if (rc == BHR_OK && repair) rc = launch(nullptr, 0, 0, 0, 2);
-        }
-        ctx->stream = main_stream;
+        if (rc == BHR_OK) rc = launch(bhr_slot(ctx).aux_stream, s.d_active, s.n_strict, 0, 0, 0);
+        if (rc == BHR_OK && repair && hipMemsetAsync(fx.d_count, 0, sizeof(unsigned int), main_stream) != hipSuccess) rc = bhr_fail(BHR_ERR_HIP, "hipMemsetAsync failed");
+        if (rc == BHR_OK) rc = launch(main_stream, s.d_active + s.n_strict, base_n - s.n_strict, 0, 0, 1);
+        if (rc == BHR_OK && repair) rc = launch(main_stream, nullptr, 0, 0, 0, 2);
         if (rc == BHR_OK) rc = bhr_aux_join(ctx);
-        if (rc == BHR_OK) rc = launch(nullptr, 0, 0, 1, 0);                        // epilogue: the end event
+        if (rc == BHR_OK) rc = launch(main_stream, nullptr, 0, 0, 1, 0);           // epilogue: the end event
     }
-    ctx->part.active = 0;
-    ctx->fix_count = nullptr;
-    ctx->fix_list = nullptr;
-    ctx->fix_cap = 0;
     return rc;
 }
 
@@ -677,10 +666,8 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_camera *out_cam, uint32_
 int32_t bhr_hybrid_fine_flags(bhr_ctx *ctx, const bhr_camera *out_cam, int32_t k, const uint8_t **d_flags, int32_t *tiles_x) {
     Hybrid *h = (Hybrid *)ctx->hybrid;
     if (!h) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: no hybrid march has run on this context");
-    bhr_camera cam = *out_cam;
-    cam.pixel_width /= (float)k;
-    cam.pixel_height /= (float)k;
-    const bhr_fine_frame fr = {ctx->cfg.width * k, ctx->cfg.height * k, ctx->cfg.row0 * k, ctx->rows * k};
+    const bhr_camera cam = bhr_fine_camera(out_cam, k);
+    const bhr_fine_frame fr = bhr_fine(ctx, k);
     double lo, hi, key[12];
     effective_band(ctx, &lo, &hi);
     const double pad_f = ctx->opt.hybrid_pad;

@@ -3,7 +3,9 @@
 // march.hip is device code compiled three times (csrc/Makefile: fast, strict, strict with the ILP-first scheduler); each
 // object hands its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp).  This file resolves the
 // arithmetic, builds the kernel arguments, keeps the tile order, the ray-step counters and the timing events, and picks
-// the kernel of a launch (march_kernel).
+// the kernel of a launch (march_kernel).  What a launch works from is in its arguments -- the caller's bhr_march_call
+// (camera, flags, stream, timing slot, end-event policy, supersampling factor) and, for one list of a hybrid march, a
+// bhr_march_part -- never in fields a caller left in the context.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -21,15 +23,15 @@
 
 namespace {
 
-// Tile order of this context: 8x8 tiles of the marched frame (bhr_fine) sorted by the distance of their centre from the
-// centre of the FULL image (the camera looks at the hole, build_camera), nearest first.  Built once per context and
+// Tile order of this context: 8x8 tiles of the marched frame (bhr_fine with factor ss) sorted by the distance of their centre
+// from the centre of the FULL image (the camera looks at the hole, build_camera), nearest first.  Built once per context and
 // supersampling factor (bhr_set_supersample releases it).
-int32_t ensure_tile_order(bhr_ctx *ctx, int tiles_x, int n_tiles) {
-    if (ctx->d_tile_order && ctx->tile_order_n == n_tiles && ctx->tile_order_ss == ctx->ss) return BHR_OK;
+int32_t ensure_tile_order(bhr_ctx *ctx, int ss, int tiles_x, int n_tiles) {
+    if (ctx->d_tile_order && ctx->tile_order_n == n_tiles && ctx->tile_order_ss == ss) return BHR_OK;
     if (ctx->d_tile_order) (void)hipFree(ctx->d_tile_order);
     ctx->d_tile_order = nullptr;
     std::vector<std::pair<float, int>> key((size_t)n_tiles);
-    const bhr_fine_frame fr = bhr_fine(ctx);
+    const bhr_fine_frame fr = bhr_fine(ctx, ss);
     const float cx = 0.5f * (float)fr.width, cy = 0.5f * (float)fr.height;
     for (int t = 0; t < n_tiles; ++t) {
         const float x = (float)((t % tiles_x) * 8 + 4) - cx, y = (float)(fr.row0 + (t / tiles_x) * 8 + 4) - cy;
@@ -45,7 +47,7 @@ int32_t ensure_tile_order(bhr_ctx *ctx, int tiles_x, int n_tiles) {
     BHR_HIP(hipMalloc((void **)&ctx->d_tile_order, (size_t)n_tiles * sizeof(int32_t)));
     BHR_HIP(hipMemcpy(ctx->d_tile_order, ctx->h_tile_order, (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice));
     ctx->tile_order_n = n_tiles;
-    ctx->tile_order_ss = ctx->ss;
+    ctx->tile_order_ss = ss;
     return BHR_OK;
 }
 
@@ -65,13 +67,13 @@ float fast_sqrt(float s) {
 //
 //   arithmetic     request                                              kernel (object)
 //   any            hybrid part with n <= 0, not the fix list            none
-//   strict         hybrid fix list (part.repair == 2)                   march_fix_kernel<diff> (strict_ilp)
+//   strict         hybrid fix list (part->repair == 2)                  march_fix_kernel<diff> (strict_ilp)
 //   fast / strict  Disk V2 volume source                                march_tile_kernel<false, 2> (own object)
 //   fast / strict  Disk V2 analytic source                              march_tile_kernel<diff, 1> (own object)
 //   fast / strict  BHR_PERSISTENT, texture, no row costs, no part       march_persistent_kernel<diff> (own object)
 //   strict         texture, BHR_PERSISTENT with row costs or a part     march_tile_kernel<diff, 0> (strict)
 //   strict         texture, otherwise                                   march_tile_aa_ilp / march_tile_plain_ilp (strict_ilp)
-//   fast           hybrid fast list with guards (part.repair == 1)      march_tile_guard_kernel<diff, row costs>
+//   fast           hybrid fast list with guards (part->repair == 1)     march_tile_guard_kernel<diff, row costs>
 //   fast           row costs                                            march_tile_kernel<diff, 0, true>
 //   fast           AA, mip_lds on, no part, a level fits 44 KB          march_tile_mipstaged_kernel (sets ctx->mip_lds_from)
 //   fast           AA otherwise                                         march_tile_kernel<true, 0> (ctx->mip_lds_from = -1)
@@ -82,28 +84,29 @@ float fast_sqrt(float s) {
 //   strict         texture (and the strict list of a hybrid frame)      march_list_kernel<diff, 0> (strict_ilp)
 //   fast           texture (and the fast list of a hybrid frame)        march_list_kernel<diff, 0> (fast)
 //
-// diff: anti_alias && !BHR_SKIP_DIFFERENTIALS.  Grids: blocks of 4 waves, a wave per tile of the launch's list; a wave per 64
-// entries of the fix list's capacity; the persistent kernel enough blocks to fill the chip.
+// part: the bhr_march_part of a hybrid march's launch (null: whole block).  diff: bhr_want_diff.  Grids: blocks of 4 waves, a
+// wave per tile of the launch's list; a wave per 64 entries of the fix list's capacity; the persistent kernel enough blocks
+// to fill the chip.
 struct MarchKernel {
     const void *fn = nullptr;
     dim3 grid;
     size_t lds = 0;
 };
-MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part &part, int math, uint32_t flags, bool diff) {
+MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *part, int math, uint32_t flags, bool diff) {
     MarchKernel k;
     k.grid = dim3((a.n_list + 3) / 4);
     const bool persistent = (flags & BHR_PERSISTENT) != 0;
     const int ss = a.ss > 1;                                   // the supersampled twins (bhr_render refuses the schedules they lack)
     const auto own = math == BHR_MATH_FAST ? bhr_march_kernel_fast : bhr_march_kernel_strict;
-    if (part.active && part.n <= 0 && part.repair != 2) return k;
-    if (part.active && part.repair == 2) {
+    if (part && part->n <= 0 && part->repair != 2) return k;
+    if (part && part->repair == 2) {
         k.fn = bhr_march_kernel_strict_ilp(BHR_MK_FIX, diff, ss);
         k.grid = dim3((a.fix_cap / 64 + 3) / 4);
         return k;
     }
     if (ctx->disk_source == BHR_DISK_V2_VOLUME) { k.fn = own(BHR_MK_VOLUME, 0, ss); return k; }
     if (a.dv2) { k.fn = own(BHR_MK_DV2, diff, ss); return k; }
-    if (persistent && !a.row_steps && !part.active) {
+    if (persistent && !a.row_steps && !part) {
         k.fn = own(BHR_MK_PERSISTENT, diff, ss);
         k.grid = dim3(std::min(std::max((a.n_tiles + 3) / 4, 1), 256 * 8));
         return k;
@@ -113,13 +116,13 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part &pa
         k.fn = persistent ? bhr_march_kernel_strict(BHR_MK_TILE, diff, ss) : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff, ss);
         return k;
     case BHR_MATH_FAST:
-        if (part.active && part.repair == 1) {
+        if (part && part->repair == 1) {
             k.fn = bhr_march_kernel_fast(a.row_steps ? BHR_MK_GUARD_COSTS : BHR_MK_GUARD, diff, ss);
         } else if (a.row_steps) {
             k.fn = bhr_march_kernel_fast(BHR_MK_TILE_COSTS, diff, ss);
         } else if (diff) {
             // BHR_MIP_LDS=1: the coarse mip levels through LDS where any of them fits 44 KB (see the kernel; not supersampled)
-            if (ctx->opt.mip_lds && !part.active && !ss) {
+            if (ctx->opt.mip_lds && !part && !ss) {
                 const int last = 3;                                     // int(clamp(lod, 0, 3)): the coarsest level ever sampled
                 for (int l = last; l >= 1; --l) {
                     if (a.sc.mip_h[last] <= 0 || a.sc.mip_w[last] <= 0) break;                  // a texture too small to have it
@@ -153,10 +156,10 @@ int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags) {
     return mode;
 }
 
-int32_t bhr_ensure_tile_order(bhr_ctx *ctx) {
-    const bhr_fine_frame fr = bhr_fine(ctx);
+int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss) {
+    const bhr_fine_frame fr = bhr_fine(ctx, ss);
     const int tiles_x = (fr.width + 7) / 8;
-    return ensure_tile_order(ctx, tiles_x, tiles_x * ((fr.rows + 7) / 8));
+    return ensure_tile_order(ctx, ss, tiles_x, tiles_x * ((fr.rows + 7) / 8));
 }
 
 // registers / LDS of the kernel that marches a whole texture frame: the fast object's under fast arithmetic, the ILP
@@ -170,10 +173,11 @@ int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t 
     return BHR_OK;
 }
 
-// The kernel argument block of a march of the frame bhr_fine(ctx) under the fast or the strict arithmetic: everything but the
-// launch's own list, row-cost and diagnostic pointers.
-static void march_args(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, bool fast, BhrMarchArgs &a) {
+// The kernel argument block of a march of the frame bhr_fine(ctx, ss) under the fast or the strict arithmetic: everything but
+// the launch's own list, row-cost and diagnostic pointers.  ss: the call's factor for the base march, ada_k for the refinement.
+static void march_args(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part, int32_t ss, bool fast, BhrMarchArgs &a) {
     const bhr_config &c = ctx->cfg;
+    const bhr_camera *cam = call.cam;
     for (int k = 0; k < 3; ++k) {
         a.cp[k] = cam->pos[k];
         a.cr[k] = cam->right[k];
@@ -181,8 +185,8 @@ static void march_args(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, bool
         a.cf[k] = cam->forward[k];
     }
     // supersampling: the march marches the fine frame (bhr_fine) at the fine pitch, and stores the resolved output frame
-    const bhr_fine_frame fr = bhr_fine(ctx);
-    const bhr_camera fcam = bhr_fine_camera(ctx, cam);
+    const bhr_fine_frame fr = bhr_fine(ctx, ss);
+    const bhr_camera fcam = bhr_fine_camera(cam, ss);
     a.pw = fcam.pixel_width;
     a.ph = fcam.pixel_height;
     a.r_esc = cam->r_escape;
@@ -210,9 +214,9 @@ static void march_args(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, bool
     a.height = fr.height;
     a.row0 = fr.row0;
     a.rows = fr.rows;
-    a.ss = ctx->ss;
-    a.ss_log2 = ctx->ss == 8 ? 3 : ctx->ss == 4 ? 2 : ctx->ss == 2 ? 1 : 0;
-    a.ss_inv = 1.0f / (float)(ctx->ss * ctx->ss);
+    a.ss = ss;
+    a.ss_log2 = bhr_log2(ss);
+    a.ss_inv = 1.0f / (float)(ss * ss);
     a.out_width = c.width;
     a.out_rows = ctx->rows;
     a.sc.skybox = ctx->d_skybox;
@@ -233,7 +237,7 @@ static void march_args(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, bool
     a.diskp = nullptr;
     a.dp_yb = a.dp_gp = a.dp_g0 = 0;
     a.sum = nullptr;
-    if (f.frame_split && f.d_pa && f.d_sum && !(flags & BHR_SKIP_BLOOM)) {      // split-f16 post-pass: the march feeds its H pass directly
+    if (f.frame_split && f.d_pa && f.d_sum && !(call.flags & BHR_SKIP_BLOOM)) {      // split-f16 post-pass: the march feeds its H pass directly
         bhr_split_geom g;
         bhr_split_geometry(ctx, &g);
         a.diskp = (_Float16 *)f.d_pa;
@@ -244,8 +248,7 @@ static void march_args(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, bool
         f.sum_valid = 1;
     }
     // timed launches (bhr_render) count into their ring slot; group launches into the scalar
-    const int slot = ctx->cur_slot;
-    a.ray_steps = slot >= 0 ? ctx->d_steps_ring + (size_t)slot * BHR_STEP_CELL : ctx->d_ray_steps;
+    a.ray_steps = call.slot >= 0 ? ctx->d_steps_ring + (size_t)call.slot * BHR_STEP_CELL : ctx->d_ray_steps;
     a.queue = f.d_queue;
     a.dv2 = ctx->disk_source != BHR_DISK_TEXTURE ? ctx->d_dv2_params : nullptr;
     a.vol_absorption = ctx->vol_opts[0];
@@ -259,37 +262,37 @@ static void march_args(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, bool
     a.tiles_x = (fr.width + 7) / 8;
     a.n_tiles = a.tiles_x * ((fr.rows + 7) / 8);
     a.n_list = a.n_tiles;
-    a.fix_count = ctx->fix_count;
     a.mip_lds_from = -1;
-    a.fix_list = ctx->fix_list;
-    a.fix_cap = ctx->fix_cap;
+    a.fix_count = part ? part->fix_count : nullptr;
+    a.fix_list = part ? part->fix_list : nullptr;
+    a.fix_cap = part ? part->fix_cap : 0;
     a.row_steps = nullptr;
     a.wave_stamps = nullptr;
     a.tile_order = nullptr;
 }
 
-int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
-    const bhr_config &c = ctx->cfg;
-    // a partial launch (ctx->part: one list of a hybrid march) marches the tiles of a caller-made list under the arithmetic the
+int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part) {
+    const uint32_t flags = call.flags;
+    const hipStream_t stream = call.stream;
+    // a partial launch (part: one list of a hybrid march) marches the tiles of a caller-made list under the arithmetic the
     // caller chose; the first part records the start event and clears an untimed counter, the last part records the end event
-    const bhr_march_part part = ctx->part;
-    const int math = part.active ? part.math : bhr_resolve_math(ctx, flags);
-    if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, cam, flags);
+    const int math = part ? part->math : bhr_resolve_math(ctx, flags);
+    if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, call);
     const bool fast = math == BHR_MATH_FAST;
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
     if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_render: no disk texture set (bhr_set_disk_texture)");
 
     BhrMarchArgs a;
-    march_args(ctx, cam, flags, fast, a);
-    const bhr_fine_frame fr = bhr_fine(ctx);
-    const int slot = ctx->cur_slot;
-    const bool first_part = !part.active || part.first, last_part = !part.active || part.last;
+    march_args(ctx, call, part, call.ss, fast, a);
+    const bhr_fine_frame fr = bhr_fine(ctx, call.ss);
+    const int slot = call.slot;
+    const bool first_part = !part || part->first, last_part = !part || part->last;
     if (flags & BHR_ROW_COSTS) {
         // two profiles side by side: [0, n) the steps taken by the fast arithmetic, [n, 2n) by the strict one (a hybrid frame
         // fills both, from its two tile lists); cleared by the frame's first part, on the stream every other part follows
         const size_t n = (size_t)((ctx->rows + 7) / 8);
         if (!ctx->d_row_steps) BHR_HIP(hipMalloc((void **)&ctx->d_row_steps, 2 * n * sizeof(unsigned long long)));
-        if (first_part) BHR_HIP(hipMemsetAsync(ctx->d_row_steps, 0, 2 * n * sizeof(unsigned long long), ctx->stream));
+        if (first_part) BHR_HIP(hipMemsetAsync(ctx->d_row_steps, 0, 2 * n * sizeof(unsigned long long), stream));
         a.row_steps = ctx->d_row_steps + (fast ? 0 : n);
     }
     // diagnostic (builds with -DBHR_WAVE_STAMPS_BUILD=1 only: the stamps cost the plain kernel three spilled registers):
@@ -302,43 +305,40 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     unsigned long long *d_stamps = nullptr;
     if (stamp_path && stamp_path[0]) {
         BHR_HIP(hipMalloc((void **)&d_stamps, (size_t)a.n_tiles * 4 * sizeof(unsigned long long)));
-        BHR_HIP(hipMemsetAsync(d_stamps, 0, (size_t)a.n_tiles * 4 * sizeof(unsigned long long), ctx->stream));
+        BHR_HIP(hipMemsetAsync(d_stamps, 0, (size_t)a.n_tiles * 4 * sizeof(unsigned long long), stream));
         a.wave_stamps = d_stamps;
     }
-    if (part.active) {
-        a.tile_order = part.d_list;
-        a.n_list = part.n;
+    if (part) {
+        a.tile_order = part->d_list;
+        a.n_list = part->n;
     } else {
-        BHR_TRY(ensure_tile_order(ctx, a.tiles_x, a.n_tiles));
+        BHR_TRY(ensure_tile_order(ctx, call.ss, a.tiles_x, a.n_tiles));
         a.tile_order = ctx->d_tile_order;
     }
 
-    // anti_alias "disabled": the reference still integrates the differentials (skip_diff = 0 on
-    // the CLI path) but never reads them (render.py:2957-2959) => skipping them is pixel-identical.
-    const bool want_diff = c.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS);
-
     // ring cells are cleared ahead of time (at reset, then by the previous frame's last kernel)
-    if (slot < 0 && first_part) BHR_HIP(hipMemsetAsync(a.ray_steps, 0, sizeof(unsigned long long) * BHR_STEP_CELL, ctx->stream));
-    if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(bhr_slot(ctx).d_queue, 0, sizeof(unsigned int), ctx->stream));
+    if (slot < 0 && first_part) BHR_HIP(hipMemsetAsync(a.ray_steps, 0, sizeof(unsigned long long) * BHR_STEP_CELL, stream));
+    if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(bhr_slot(ctx).d_queue, 0, sizeof(unsigned int), stream));
     // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
-    if (first_part) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 0] : ctx->ev[0], ctx->stream));
-    const MarchKernel k = march_kernel(ctx, a, part, math, flags, want_diff);
-    if (!k.fn && !(part.active && part.n <= 0 && part.repair != 2))
-        return bhr_fail(BHR_ERR_STATE, "bhr_render: no march kernel for this launch (supersampling %d, flags %u)", ctx->ss, flags);
+    if (first_part) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, slot), stream));
+    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags));
+    if (!k.fn && !(part && part->n <= 0 && part->repair != 2))
+        return bhr_fail(BHR_ERR_STATE, "bhr_render: no march kernel for this launch (supersampling %d, flags %u)", call.ss, flags);
     if (k.fn) {
         int refill_below = 40;                                 // persistent schedule: refill a wave below 40 live lanes
         void *args[] = {&a, &refill_below};                    // (the second argument is the persistent kernel's alone)
-        (void)hipLaunchKernel(k.fn, k.grid, dim3(256), args, k.lds, ctx->stream);
+        (void)hipLaunchKernel(k.fn, k.grid, dim3(256), args, k.lds, stream);
     }
     BHR_HIP(hipGetLastError());
     // group / tile renders (slot < 0) record the march's end only on request: the event is a ~5 us bubble between the march and
     // the H pass of a tile whose whole tail is ~0.12 ms
-    if (last_part && !ctx->defer_march_end && (slot >= 0 || ctx->group_time_march)) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1], ctx->stream));
-    if (last_part) ctx->march_end_recorded = slot >= 0 || ctx->group_time_march;
+    const bool timed = slot >= 0 || call.time_untimed;
+    if (last_part && !call.defer_end && timed) BHR_HIP(hipEventRecord(bhr_march_end_event(ctx, slot), stream));
+    if (last_part) ctx->march_end_recorded = timed;
     if (d_stamps) {
         std::vector<unsigned long long> h((size_t)a.n_tiles * 4);
-        BHR_HIP(hipMemcpyAsync(h.data(), d_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        BHR_HIP(hipStreamSynchronize(ctx->stream));
+        BHR_HIP(hipMemcpyAsync(h.data(), d_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        BHR_HIP(hipStreamSynchronize(stream));
         (void)hipFree(d_stamps);
         if (FILE *f = fopen(stamp_path, "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
     }
@@ -347,11 +347,13 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     return BHR_OK;
 }
 
-// Adaptive supersampling (bhr_set_adaptive_supersample), behind the frame's k = 1 march on ctx->stream: clear the counts ->
+// Adaptive supersampling (bhr_set_adaptive_supersample), behind the frame's k = 1 march `call` on its stream: clear the counts ->
 // [hybrid: flags of the fine frame's tiles] -> detect (mask + lists of fine tiles) -> refine (first list, second list) -> march-end event.  Nothing here
 // waits for the device: the refinement's grids are sized for the lists' capacity, and waves beyond what the detect kernel listed exit at once.
-int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
+int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
     const int k = ctx->ada_k, W = ctx->cfg.width, H = ctx->rows;
+    const uint32_t flags = call.flags;
+    const hipStream_t stream = call.stream;
     const int math = bhr_resolve_math(ctx, flags);
     bhr_frame_slot &f = bhr_slot(ctx);
     const int32_t fine_tiles_x = (W * k + 7) / 8, cap = fine_tiles_x * ((H * k + 7) / 8);   // tiles of the fine frame
@@ -362,18 +364,18 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags)
         BHR_HIP(hipMalloc((void **)&f.d_ada_counts, 64));
     }
     if ((long long)cap > (long long)W * H) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: %d fine tiles for %d x %d pixels", cap, W, H);
-    BHR_HIP(hipMemsetAsync(f.d_ada_counts, 0, 4 * sizeof(unsigned int), ctx->stream));
+    BHR_HIP(hipMemsetAsync(f.d_ada_counts, 0, 4 * sizeof(unsigned int), stream));
     BhrDetectArgs d;
     d.bg = f.d_bg;
     d.disk = f.d_disk;
     d.width = W;
     d.height = H;
     d.threshold = ctx->ada_threshold;
-    d.k_log2 = k == 8 ? 3 : k == 4 ? 2 : 1;
+    d.k_log2 = bhr_log2(k);
     d.flags = nullptr;
     d.fine_tiles_x = fine_tiles_x;
     int32_t flag_tiles_x = fine_tiles_x;
-    if (math == BHR_MATH_HYBRID) BHR_TRY(bhr_hybrid_fine_flags(ctx, cam, k, &d.flags, &flag_tiles_x));
+    if (math == BHR_MATH_HYBRID) BHR_TRY(bhr_hybrid_fine_flags(ctx, call.cam, k, &d.flags, &flag_tiles_x));
     if (flag_tiles_x != fine_tiles_x) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: %d flag columns for %d tile columns", flag_tiles_x, fine_tiles_x);
     d.mask = f.d_ada_mask;
     d.list = f.d_ada_list;
@@ -382,16 +384,14 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags)
     {
         const int blocks = ((W + 7) / 8) * ((H + 7) / 8);            // a wave per 8 x 8 block of output pixels
         void *args[] = {&d};
-        (void)hipLaunchKernel(bhr_march_kernel_strict(BHR_MK_DETECT, 0, 0), dim3((blocks + 3) / 4), dim3(256), args, 0, ctx->stream);
+        (void)hipLaunchKernel(bhr_march_kernel_strict(BHR_MK_DETECT, 0, 0), dim3((blocks + 3) / 4), dim3(256), args, 0, stream);
         BHR_HIP(hipGetLastError());
     }
     // the refinement marches the fine frame: the second argument block of the frame (ss = k, stores into the output frame)
-    const bool want_diff = ctx->cfg.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS);
+    const bool want_diff = bhr_want_diff(ctx, flags);
     auto refine = [&](bool fast, int which) -> int32_t {
         BhrMarchArgs a;
-        ctx->ss = k;
-        march_args(ctx, cam, flags, fast, a);
-        ctx->ss = 1;
+        march_args(ctx, call, nullptr, k, fast, a);
         // a tile per wave, a grid for the list's capacity (every fine tile): waves beyond the list's length exit at once
         a.tile_order = f.d_ada_list + (size_t)which * cap;
         a.n_list = cap;
@@ -406,7 +406,7 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags)
                                                                  : bhr_march_kernel_strict_ilp(BHR_MK_LIST, want_diff, 1);
         if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_render: no list kernel for the refinement of this frame");
         void *args[] = {&a};
-        (void)hipLaunchKernel(fn, dim3((cap + 3) / 4), dim3(256), args, 0, ctx->stream);
+        (void)hipLaunchKernel(fn, dim3((cap + 3) / 4), dim3(256), args, 0, stream);
         BHR_HIP(hipGetLastError());
         return BHR_OK;
     };
@@ -416,8 +416,7 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags)
     } else {
         BHR_TRY(refine(math == BHR_MATH_FAST, 0));
     }
-    const int slot = ctx->cur_slot;
-    if (slot >= 0 || ctx->group_time_march) BHR_HIP(hipEventRecord(slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1], ctx->stream));
+    if (call.slot >= 0 || call.time_untimed) BHR_HIP(hipEventRecord(bhr_march_end_event(ctx, call.slot), stream));
     ctx->ada_last_slot = ctx->active_slot;
     ctx->ada_last_math = math;
     return BHR_OK;

@@ -331,6 +331,29 @@ def test_hybrid_repairs_are_counted_and_fit_their_list(hip_lib):
     assert info["repaired_pixels"] == 0 and info["repair_capacity"] == 0, info
 
 
+@pytest.mark.parametrize("repair", [-1, 0])
+def test_one_and_two_march_streams_give_the_same_frame(repair, hip_lib):
+    """Option "hybrid_streams": the strict list of a hybrid march ahead of the fast one on the frame's stream (1), or beside it
+    on the slot's second stream (2).  Both settings run the same three kernels over the same lists -- a tilted disk turns
+    the guards and the fix list on by default; hybrid_repair 0 takes them out -- so the frame and the repair count are
+    identical bit for bit."""
+    from bhr_amd import HipRenderer, _lib, scenes
+    sky, tex = scenes.analytic_skybox(), scenes.noisy_disk()
+    r = HipRenderer(256, 160, sky, tex, math="hybrid", frame_slots=2, step_size=0.1, r_max=10.0, r_disk_inner=2.0, r_disk_outer=15.0, disk_tilt=25.0)
+    r.set_option("hybrid_repair", repair)
+    got = {}
+    for streams in (1, 2):
+        r.set_option("hybrid_streams", streams)
+        r.render_async([6.0, 0.0, 0.5], 90.0)
+        info = r.hybrid_info()
+        got[streams] = (r.read_layer(_lib.LAYER_FINAL), (info["repaired_pixels"], info["repair_capacity"]), info["strict_tiles"])
+    r.close()
+    assert 0 < got[1][2] < (256 // 8) * (160 // 8)                 # both lists hold tiles: there is something for the second stream
+    assert (got[1][1][0] > 0) == (repair != 0) and (got[1][1][1] > 0) == (repair != 0), got[1][1]
+    assert got[1][1] == got[2][1], (got[1][1], got[2][1])
+    np.testing.assert_array_equal(got[1][0], got[2][0])
+
+
 def test_device_classification_makes_the_host_s_lists(hip_lib):
     """The tiles are classified and the launch order partitioned on the device by default (csrc/hybrid.hip: four small
     kernels on a stream of their own, the host waits for the strict count alone); option "hybrid_classify" 0 keeps the

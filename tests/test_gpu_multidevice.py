@@ -60,6 +60,60 @@ def test_group_render_across_two_devices(hip_lib):
         t.close()
 
 
+def test_failed_group_render_leaves_nothing_behind(hip_lib):
+    """A group render that fails part-way -- tile 1 has no skybox: an error return of the host launcher before any of its
+    kernels -- leaves no per-call input of the group behind in tile 0: a later bhr_render on tile 0 alone stores nothing
+    into tile 1's packed H-blur planes (the split-f16 H pass of a group render writes the neighbours' halo rows itself),
+    and renders what a fresh tile-0 context renders."""
+    import ctypes as C
+    from bhr_amd import HipRenderer, _lib
+    lib = _lib.load()
+    W, H, cut = 256, 128, 64
+    kw = dict(step_size=0.1, r_max=10.0, r_disk_inner=2.0, r_disk_outer=15.0, disk_tilt=0.0)
+    sky, tex = scenes.analytic_skybox(), scenes.noisy_disk()
+    t0 = HipRenderer(W, H, sky, tex, rows=(0, cut), math="fast", **kw)
+    t0.set_option("group_threads", 0)                  # the tiles are submitted in order
+    ctx1 = C.c_void_p()                                # tile 1: its disk texture, no skybox
+    cfg = _lib.Config(W, H, cut, H, kw["step_size"], kw["r_max"], kw["r_disk_inner"], kw["r_disk_outer"], kw["disk_tilt"], 0, 1.0, 0.1, 0, _lib.MATH_FAST)
+    _lib.check(lib.bhr_create(C.byref(cfg), C.byref(ctx1)))
+    fresh = None
+    try:
+        disk = np.ascontiguousarray(tex, dtype=np.float32)
+        _lib.check(lib.bhr_set_disk_texture(ctx1, _lib.fptr(disk), disk.shape[0], disk.shape[1]))
+        cam = t0.camera_uniforms([6.0, 0.0, 0.5], 90.0, 0)
+        arr = (C.c_void_p * 2)(t0._ctx, ctx1)
+        rc = lib.bhr_group_render(arr, 2, C.byref(cam), 0, None)
+        assert rc == _lib.BHR_ERR_STATE and b"no skybox set" in lib.bhr_last_error(), (rc, lib.bhr_last_error())
+        t0.sync()                                       # tile 0's own march and H pass of the failed call have ended
+
+        geom = (C.c_int32 * 10)()
+        _lib.check(lib.bhr_debug_read(ctx1, 1, None, 0, geom))
+        nbytes = 6 * geom[9] * geom[2] * 8 * 2          # 6 GR WP 8 halves: the packed H-blur planes (bhr_split_geom)
+
+        def planes():
+            out = np.empty(nbytes, np.uint8)
+            _lib.check(lib.bhr_debug_read(ctx1, 1, out.ctypes.data, nbytes, None))
+            return out
+
+        before = planes()
+        assert before.any()                             # the group render's H pass of tile 0 did store its halo rows there
+        other = ([5.0, 2.0, 1.0], 80.0)
+        t0.render_async(*other)
+        t0.sync()
+        after = planes()
+        got = t0.read_layer(_lib.LAYER_FINAL)
+        fresh = HipRenderer(W, H, sky, tex, rows=(0, cut), math="fast", **kw)
+        fresh.render_async(*other)
+        want = fresh.read_layer(_lib.LAYER_FINAL)
+        np.testing.assert_array_equal(after, before)
+        np.testing.assert_array_equal(got, want)
+    finally:
+        t0.close()
+        if fresh is not None:
+            fresh.close()
+        lib.bhr_destroy(ctx1)
+
+
 def test_make_tiles_cost_balanced_blocks(hip_lib):
     """bench.py's row-block leg at a small size: blocks cover the frame, cuts fall on tile rows, the gathered frame
     equals the one-context frame of the same scene."""
