@@ -60,11 +60,15 @@
 struct BhrScene {
     const float *skybox;   // (sky_h, sky_w, 3)
     int32_t sky_h, sky_w;
-    const float4 *mips;    // packed levels 0..4, level l at mip_off[l], dims (mip_h[l], mip_w[l])
+    const float4 *mips;    // packed levels 0..4, level l at mip_off[l], dims (mip_h[l], mip_w[l]); (0, 0) beyond mip_last
     int32_t mip_off[BHR_NUM_MIP_LEVELS];
     int32_t mip_h[BHR_NUM_MIP_LEVELS];
     int32_t mip_w[BHR_NUM_MIP_LEVELS];
     int32_t n_r, n_phi;
+    // the last level the texture's mip chain really has (alloc_mips: a chain stops at a side below 2): what _sample_disk_mip
+    // clamps the level to (num_mip_levels - 1, render.py:2613).  Read by the anti-aliased kernels only; it sits in what was the
+    // struct's tail padding, so every other kernel argument keeps its offset
+    int32_t mip_last;
 };
 
 // Kernel argument block of the march (passed by value -> SGPRs).

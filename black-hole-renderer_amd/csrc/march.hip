@@ -420,6 +420,11 @@ __device__ __forceinline__ void shade_hit(const BhrMarchArgs &a, Shade &sh, floa
         }
         lod = fminf(fmaxf(lod, 0.0f), 3.0f);
         lod_i = (int)fminf(fmaxf(lod, 0.0f), (float)(BHR_NUM_MIP_LEVELS - 1));
+        // _sample_disk_mip clamps to num_mip_levels - 1 with the levels the chain HAS (render.py:2613): a 4 x 12 texture stops at
+        // level 2 (1 x 3), and the levels beyond the last hold nothing -- their offset is the end of the stack.  As an integer
+        // minimum with the scalar argument (int(min(x, n)) = min(int(x), n) for x >= 0): the float form keeps (float)mip_last
+        // in a VGPR across the march loop
+        lod_i = min(lod_i, a.sc.mip_last);
     }
     // SRC == 1 is a separate kernel instantiation: the binary64 model code (and its registers) never
     // touches the texture kernels

@@ -230,6 +230,8 @@ static void march_args(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march
     }
     a.sc.n_r = ctx->n_r;
     a.sc.n_phi = ctx->n_phi;
+    a.sc.mip_last = 0;
+    for (int l = 1; l < BHR_NUM_MIP_LEVELS && ctx->mip_h[l] > 0 && ctx->mip_w[l] > 0; ++l) a.sc.mip_last = l;
     bhr_frame_slot &f = bhr_slot(ctx);
     a.bg = f.d_bg;
     a.disk = f.d_disk;

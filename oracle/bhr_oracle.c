@@ -679,6 +679,11 @@ static void volume_segment(v3 p0, v3 p1, v3 dir0, float tilt_rad, float t_offset
  * rays store zeros).  Used by the convergence test against an independent geodesic integrator. */
 static double *g_escape_out;
 ORACLE_API void oracle_set_escape_out(double *buf) { g_escape_out = buf; }
+/* Test hook: when set, every pixel stores the largest lod (after its clamp to [0, 3], before _sample_disk_mip clamps it to
+ * the chain) that a disk crossing of its ray asked for ((W, H) binary32; -1: no crossing, or no anti-aliasing).  Tells a
+ * test whether a frame has crossings that ask for a level the texture's mip chain does not have. */
+static f32 *g_lod_out;
+ORACLE_API void oracle_set_lod_out(f32 *buf) { g_lod_out = buf; }
 
 /* ---- camera uniforms as uploaded at render.py:3886-3892 ----------------- */
 typedef struct {
@@ -757,6 +762,7 @@ ORACLE_API int64_t oracle_ray_march(const oracle_camera *cam, const oracle_march
             v3 escape_dir = v3_make(0, 0, 0);
             v3 accum_disk = v3_make(0, 0, 0);
             float disk_alpha_total = 0.0f;
+            float lod_asked = -1.0f;     /* oracle_set_lod_out */
             int32_t step_count = 0;
             int32_t executed = 0;
             float affine = 0.0f;
@@ -877,6 +883,7 @@ ORACLE_API int64_t oracle_ray_march(const oracle_camera *cam, const oracle_march
                             float grad_sq = fmaxf(grad_sq_x, grad_sq_y);
                             float lod_diff = logf(fmaxf(grad_sq, 1.0f)) / logf(2.0f) * p->aa_strength;
                             lod_diff = fminf(fmaxf(lod_diff, 0.0f), 3.0f);
+                            if (lod_diff > lod_asked) lod_asked = lod_diff;
                             disk_rgba = sample_disk_mip(&sc, hit_x, hit_y, r_inner, r_outer, t_offset, lod_diff);
                         }
                         v3 disk_col = v3_make(disk_rgba.x, disk_rgba.y, disk_rgba.z);
@@ -901,6 +908,7 @@ ORACLE_API int64_t oracle_ray_march(const oracle_camera *cam, const oracle_march
             bg_color = v3_scale(1.0f - disk_alpha_total, bg_color);
 
             size_t o = ((size_t)i * height + j) * 3;
+            if (g_lod_out) g_lod_out[(size_t)i * height + j] = (f32)lod_asked;
             if (g_escape_out) {
                 g_escape_out[o + 0] = escaped ? (double)escape_dir.x : 0.0;
                 g_escape_out[o + 1] = escaped ? (double)escape_dir.y : 0.0;

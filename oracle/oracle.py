@@ -81,6 +81,8 @@ def load(fast=False) -> C.CDLL:
     lib.oracle_set_volume.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I32]
     lib.oracle_set_escape_out.restype = None
     lib.oracle_set_escape_out.argtypes = [C.c_void_p]
+    lib.oracle_set_lod_out.restype = None
+    lib.oracle_set_lod_out.argtypes = [C.c_void_p]
     for fn, at in (("oracle_probe_g_factor", [D, I64, D]), ("oracle_probe_tint", [D, I64, D]),
                    ("oracle_probe_disk_mip", [F, I32, I32, I32, D, I64, D]),
                    ("oracle_probe_skybox", [F, I32, I32, D, I64, D])):
@@ -115,6 +117,16 @@ def build_mips_padded(disk_tex: np.ndarray, levels: int = NUM_MIP_EXTRA_LEVELS +
     mips = np.zeros((levels, n_r, n_phi, 4), dtype=np.float32)
     lib.oracle_build_mips(_fp(mips), _fp(base), n_r, n_phi, levels)
     return mips
+
+
+def mip_level_count(n_r: int, n_phi: int, levels: int = NUM_MIP_EXTRA_LEVELS + 1) -> int:
+    """Length of the chain generate_disk_mipmaps builds (render.py:1113-1125): a level is halved only while both of
+    its sides are at least 2, `levels` at the most.  TaichiRenderer keeps it as num_mip_levels (render.py:2240) and
+    _sample_disk_mip clamps the level to it (render.py:2613); the padded levels beyond it stay zero and are never read."""
+    n, h, w = 1, int(n_r), int(n_phi)
+    while n < levels and h >= 2 and w >= 2:
+        h, w, n = h // 2, w // 2, n + 1
+    return n
 
 
 def eval_noise(coords: np.ndarray, mode: str = "simplex", octaves: int = 4, persistence: float = 0.5,
@@ -241,7 +253,7 @@ class OracleRenderer:
         self.disk_tex = np.ascontiguousarray(disk_tex, dtype=np.float32)
         self.dtex_h, self.dtex_w = self.disk_tex.shape[:2]
         self.mips = build_mips_padded(self.disk_tex, fast=self.fast)
-        self.num_mip_levels = self.mips.shape[0]
+        self.num_mip_levels = mip_level_count(self.dtex_h, self.dtex_w, self.mips.shape[0])
 
     def camera_uniforms(self, cam_pos, fov):
         p, right, up, fwd, pw, ph = build_camera(np.array(cam_pos, dtype=np.float64), fov, self.width, self.height)
@@ -282,6 +294,17 @@ class OracleRenderer:
             self.march(cam_pos, fov, skip_differentials=True, want_steps=False)
         finally:
             self.lib.oracle_set_escape_out(None)
+        return buf
+
+    def asked_lods(self, cam_pos, fov, frame=0):
+        """(W, H) float32: the largest lod (clamped to [0, 3] as at render.py:2989, before _sample_disk_mip clamps the level
+        to the mip chain) that a disk crossing of the pixel's ray asks for; -1 without a crossing or without anti-aliasing."""
+        buf = np.full((self.width, self.height), -1.0, dtype=np.float32)
+        self.lib.oracle_set_lod_out(buf.ctypes.data_as(C.c_void_p))
+        try:
+            self.march(cam_pos, fov, frame=frame, want_steps=False)
+        finally:
+            self.lib.oracle_set_lod_out(None)
         return buf
 
     def bloom(self, disk_layer):

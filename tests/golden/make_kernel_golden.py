@@ -63,8 +63,18 @@ MARCH_SCENES = {
     "fine_rot": dict(width=48, height=27, cam_pos=[4, 3, 1.5], fov=75, frame=7, tex=(32, 128), kw=dict(
         step_size=0.05, r_max=10.0, r_disk_inner=2.0, r_disk_outer=8.0, disk_tilt=5.0, anti_alias="disabled",
         disk_rotation_speed=0.1)),
+    # the far_aa view through a texture whose mip chain stops early: 4x12 -> 2x6 -> 1x3 is three levels
+    # (generate_disk_mipmaps, render.py:1118), so _sample_disk_mip clamps the lod 3 crossings to level 2;
+    # a sky that is neither a power of two nor 1:2
+    "few_levels": dict(width=32, height=18, cam_pos=[-20, 0, 2], fov=60, frame=0, tex=(4, 12), sky=(37, 101), kw=dict(
+        step_size=0.1, r_max=10.0, r_disk_inner=2.0, r_disk_outer=15.0, disk_tilt=20.0, anti_alias="lod_radius",
+        aa_strength=1.5)),
+    # the same view, the smallest 1:3 texture with four levels (8x24 ... 1x3): lod 3 has its own level; a 2x2 sky
+    "four_levels": dict(width=32, height=18, cam_pos=[-20, 0, 2], fov=60, frame=0, tex=(8, 24), sky=(2, 2), kw=dict(
+        step_size=0.1, r_max=10.0, r_disk_inner=2.0, r_disk_outer=15.0, disk_tilt=20.0, anti_alias="lod_radius",
+        aa_strength=1.5)),
 }
-SKY_SHAPE = (64, 128)
+SKY_SHAPE = (64, 128)   # a scene's "sky" entry overrides it
 N_UNIT = 192  # sampled ti.func calls kept per scene
 
 
@@ -80,10 +90,10 @@ def _setup(mode):
     return ti_shim, ref
 
 
-def _inputs(tex_shape):
+def _inputs(tex_shape, sky_shape=SKY_SHAPE):
     import bhr_amd  # noqa: F401
     from bhr_amd import scenes
-    return scenes.analytic_skybox(*SKY_SHAPE), scenes.noisy_disk(*tex_shape)
+    return scenes.analytic_skybox(*sky_shape), scenes.noisy_disk(*tex_shape)
 
 
 def _sha(a):
@@ -103,7 +113,7 @@ def run_march(task):
     ti, ref = _setup(mode)
     s = MARCH_SCENES[name]
     W, H = s["width"], s["height"]
-    sky, tex = _inputs(s["tex"])
+    sky, tex = _inputs(s["tex"], s.get("sky", SKY_SHAPE))
     r = ref.TaichiRenderer(W, H, sky, tex, **s["kw"])
 
     steps = np.zeros((W, H), dtype=np.int64)
@@ -259,7 +269,7 @@ def main():
             s = MARCH_SCENES[name]
             meta = dict(width=s["width"], height=s["height"], cam_pos=np.array(s["cam_pos"], dtype=np.float64),
                         fov=float(s["fov"]), frame=s["frame"], tex_shape=np.array(s["tex"]),
-                        sky_shape=np.array(SKY_SHAPE))
+                        sky_shape=np.array(s.get("sky", SKY_SHAPE)))
             np.savez_compressed(os.path.join(a.out, f"march_ref_{name}.npz"), **meta, **d)
         if fb:
             d = {}

@@ -27,7 +27,7 @@ import pytest
 from bhr_amd import scenes
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-MARCH = ["default", "e2e", "tilt_aa", "far_aa", "inside", "polar", "fine_rot"]
+MARCH = ["default", "e2e", "tilt_aa", "far_aa", "inside", "polar", "fine_rot", "few_levels", "four_levels"]
 # the reference-constructor arguments of make_kernel_golden.MARCH_SCENES (kept beside the fixtures' metadata)
 KW = {
     "default": dict(step_size=0.1, r_max=10.0, r_disk_inner=2.0, r_disk_outer=15.0, disk_tilt=0.0, anti_alias="disabled"),
@@ -40,6 +40,12 @@ KW = {
     "polar": dict(step_size=0.1, r_max=10.0, r_disk_inner=2.0, r_disk_outer=6.0, disk_tilt=0.0, anti_alias="lod_radius"),
     "fine_rot": dict(step_size=0.05, r_max=10.0, r_disk_inner=2.0, r_disk_outer=8.0, disk_tilt=5.0,
                      anti_alias="disabled", disk_rotation_speed=0.1),
+    # far_aa's arguments; a 4x12 texture (three mip levels: lod 3 is clamped to level 2) under a 37x101 sky, and an
+    # 8x24 texture (four levels) under a 2x2 sky
+    "few_levels": dict(step_size=0.1, r_max=10.0, r_disk_inner=2.0, r_disk_outer=15.0, disk_tilt=20.0,
+                       anti_alias="lod_radius", aa_strength=1.5),
+    "four_levels": dict(step_size=0.1, r_max=10.0, r_disk_inner=2.0, r_disk_outer=15.0, disk_tilt=20.0,
+                        anti_alias="lod_radius", aa_strength=1.5),
 }
 FLARE = {"tilt_aa"}
 
@@ -122,14 +128,15 @@ def test_g_factor_on_the_reference_s_own_calls(name, mode, oracle):
     assert ref.max() > 0.05  # the sample is not all dark
 
 
-@pytest.mark.parametrize("name", ["tilt_aa", "far_aa", "polar"])
+@pytest.mark.parametrize("name", ["tilt_aa", "far_aa", "polar", "few_levels", "four_levels"])
 @pytest.mark.parametrize("mode", ["f32", "f64"])
 def test_lod_sampler_on_the_reference_s_own_calls(name, mode, oracle):
     """_sample_disk_mip (2600-2637) with the LOD values the reference's march computed (2961-2990)."""
     g, _, tex = load_scene(name)
     calls = g[f"{mode}_mip_calls"].astype(np.float64)
     assert len(calls) > 50
-    mips = oracle.build_mips_padded(tex)
+    # the levels the reference's chain has (num_mip_levels, render.py:2240): the sampler clamps the level to them
+    mips = oracle.build_mips_padded(tex)[:oracle.mip_level_count(*tex.shape[:2])]
     out = oracle.probe_disk_mip(mips, calls[:, :6], fast=("f64" if mode == "f64" else False))
     # atan2f (glibc) vs the correctly rounded angle, times n_phi = 512 texels of a noisy texture
     assert np.abs(out - calls[:, 6:10]).max() <= 2e-5
@@ -139,6 +146,22 @@ def test_lod_values_cover_every_sampled_level():
     lods = np.concatenate([np.load(os.path.join(GOLD, f"march_ref_{n}.npz"))["f64_mip_calls"][:, 5]
                            for n in ("tilt_aa", "far_aa", "polar")])
     assert set(np.floor(lods).astype(int)) == {0, 1, 2, 3}, sorted(set(np.floor(lods).astype(int)))
+
+
+def test_few_levels_fixture_asks_for_a_level_its_chain_lacks(oracle):
+    """The 4x12 texture of `few_levels` has three levels and the reference's march asks for lod 3 there: its recorded
+    _sample_disk_mip calls carry the level clamp (render.py:2613).  `four_levels` (8x24) has the level."""
+    from bhr_amd import textures
+    few, four = (np.load(os.path.join(GOLD, f"march_ref_{n}.npz")) for n in ("few_levels", "four_levels"))
+    assert oracle.mip_level_count(*few["tex_shape"]) == 3 and oracle.mip_level_count(*four["tex_shape"]) == 4
+    for g in (few, four):
+        assert set(np.floor(g["f64_mip_calls"][:, 5]).astype(int)) == {0, 1, 2, 3}
+    # the count is the length of the chain the NumPy twin of the device mips builds, also where it floor-halves an odd side
+    for shape in ((2, 6), (4, 12), (8, 24), (16, 48), (2, 64), (64, 4), (37, 101), (36, 100), (5, 7), (3, 3), (1, 8), (128, 512)):
+        chain = textures.generate_disk_mipmaps(np.zeros(shape + (4,), np.float32))
+        assert oracle.mip_level_count(*shape) == len(chain), shape
+        o = oracle.OracleRenderer(8, 8, scenes.analytic_skybox(2, 2), np.zeros(shape + (4,), np.float32))
+        assert o.num_mip_levels == len(chain) and o.mips.shape[0] == 5
 
 
 @pytest.mark.parametrize("mode", ["f32", "f64"])
