@@ -79,6 +79,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--dither", type=str, default="none", choices=["none", "blue"],
                    help="8-bit quantisation: none = truncation as the reference (default); blue = a 64x64 blue-noise threshold is "
                         "added before the floor, so that smooth dark gradients come out as fine noise instead of bands")
+    p.add_argument("--shutter", type=float, default=0.0, metavar="S",
+                   help="--video: motion blur -- the share of the frame time the shutter is open, 0..1 (default: 0, an "
+                        "instantaneous exposure); every frame is the mean of --shutter_samples marches over the exposure")
+    p.add_argument("--shutter_samples", type=int, default=8, metavar="N",
+                   help="--shutter: marches per frame, 1..64 (default: 8)")
     p.add_argument("--ignore_taichi_cache", action="store_true", help="accepted for compatibility; no effect")
     p.add_argument("--video", action="store_true", help="render frames and assemble a video")
     p.add_argument("--interactive", action="store_true", help="not available in this build (needs ti.GUI)")
@@ -91,7 +96,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                    choices=["baseline", "parametric", "keyframes"], help="[deprecated] ignored")
     p.add_argument("--disk_rotation_speed", type=float, default=0.1, help="disk rotation speed (default: 0.1)")
     p.add_argument("--keyframes_count", type=int, default=10, help="[deprecated] ignored")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.shutter > 0 and not args.video:
+        p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    return args
 
 
 def validate_args(args) -> None:
@@ -137,6 +145,10 @@ def validate_args(args) -> None:
         raise ValueError("--bit_depth 16 does not combine with --video_codec mjpeg: JPEG frames are 8-bit")
     if getattr(args, "bit_depth", 8) == 16 and not args.video and not args.output.lower().endswith(".png"):
         raise ValueError(f"--bit_depth 16 writes PNG files, got {args.output!r}")
+    if not (0.0 <= getattr(args, "shutter", 0.0) <= 1.0):
+        raise ValueError(f"shutter must be between 0 and 1, got {args.shutter}")
+    if not (1 <= getattr(args, "shutter_samples", 8) <= 64):
+        raise ValueError(f"shutter_samples must be between 1 and 64, got {args.shutter_samples}")
     if getattr(args, "interactive", False):
         raise ValueError("--interactive needs the Taichi GUI and is not part of this build")
 
@@ -172,7 +184,7 @@ def main(argv=None) -> int:
                              orbit_degrees=args.orbit_degrees, rank=rank, world=world, video_stream=args.video_stream,
                              png_level=(drivers.DEVICE if args.png_encoder == "device" else drivers.VIDEO_LEVEL),
                              video_codec=args.video_codec, video_quality=args.video_quality, bit_depth=args.bit_depth,
-                             dither=args.dither)
+                             dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent

@@ -99,6 +99,7 @@ static void read_options(bhr_options *o) {
     o->group_threads = num("BHR_GROUP_THREADS", -1);
     { const char *e = getenv("BHR_GROUP_SCHEDULE"); o->group_schedule = e && e[0] ? (e[0] == 's' ? 0 : 1) : -1; }
     o->png16_menu = num("BHR_PNG16_MENU", 1) != 0;
+    o->shutter_timing = num("BHR_SHUTTER_TIMING", 0) != 0;
 }
 
 int32_t alloc_slot(bhr_ctx *ctx, int k) {
@@ -154,7 +155,7 @@ int32_t ensure_bloom_buffers(bhr_ctx *ctx, int k, bool split) {
 void free_slot(bhr_ctx *ctx, int k) {
     bhr_frame_slot &f = ctx->slots[k];
     void *bufs[] = {f.d_bg, f.d_disk, f.d_blur, f.d_final, f.d_final_u8, f.d_final_u16, f.d_hblur_base, f.d_pa, f.d_pb, f.d_sum, f.d_queue,
-                    f.d_glow_hw, f.d_glow_wh, f.d_flare_c0, f.d_flare_c12, f.d_flare_sums, f.d_ada_list, f.d_ada_mask, f.d_ada_counts};
+                    f.d_glow_hw, f.d_glow_wh, f.d_flare_c0, f.d_flare_c12, f.d_flare_sums, f.d_ada_list, f.d_ada_mask, f.d_ada_counts, f.d_acc_bg, f.d_acc_disk};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (f.done) (void)hipEventDestroy(f.done);
@@ -493,6 +494,7 @@ void bhr_destroy(bhr_ctx *ctx) {
     for (int k = 0; k < BHR_MAX_FRAME_SLOTS; ++k) free_slot(ctx, k);
     bhr_png_dev_free(ctx);
     bhr_jpeg_dev_free(ctx);
+    bhr_shutter_free(ctx);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);
     bhr_pipe_free(ctx);
@@ -714,19 +716,11 @@ int32_t bhr_eval_noise(bhr_ctx *ctx, const float *coords, int64_t n, int32_t mod
 // the tail and the post-passes of frame n.  The scene is only read; everything that writes it or reads a frame goes
 // through bhr_enter, which orders the scene stream behind both slots.
 namespace {
-int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring) {
+// The post-pass of the frame on slot k behind its march (a shutter frame's: behind the last accumulation and the pack):
+// bloom H -> bloom V + combine (-> lens flare), and the frame's end events.
+int32_t post_on_slot(bhr_ctx *ctx, uint32_t flags, int k, int ring) {
     bhr_frame_slot &f = ctx->slots[k];
     const int with_bloom = (flags & BHR_SKIP_BLOOM) ? 0 : 1;
-    BHR_TRY(bhr_frame_begin(ctx, flags));
-    // an adaptively supersampled frame: the k = 1 march, then detect + refinement inside the same march bracket
-    const bool adaptive = ctx->ada_k > 1;
-    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss};
-    ctx->ada_frame = adaptive;
-    BHR_TRY(bhr_launch_march(ctx, call));              // records the ring slot's march events
-    if (adaptive) BHR_TRY(bhr_launch_adaptive(ctx, call));
-    // the march's end is the timing ring's event (recorded by the launcher): an event of its own between the march and the
-    // H pass is another ~5 us barrier packet in the frame's stream (kernel-trace gaps: 10 us with two records, 0 with none)
-    f.march_done = ctx->ring_ev[ring * 3 + 1];
     if (with_bloom) BHR_TRY(bhr_launch_bloom_h(ctx, nullptr, 0));
     // the V kernel clears the counter cell BHR_MAX_FRAME_SLOTS frames ahead: no frame that may be in flight on another
     // slot's stream is counting into it (the next frames' marches may already be running)
@@ -750,6 +744,77 @@ int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     }
     BHR_HIP(hipEventRecord(ctx->ring_ev[ring * 3 + 2], f.stream));
     BHR_HIP(hipEventRecord(f.done, f.stream));
+    return BHR_OK;
+}
+
+int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring) {
+    bhr_frame_slot &f = ctx->slots[k];
+    BHR_TRY(bhr_frame_begin(ctx, flags));
+    // an adaptively supersampled frame: the k = 1 march, then detect + refinement inside the same march bracket
+    const bool adaptive = ctx->ada_k > 1;
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss};
+    ctx->ada_frame = adaptive;
+    BHR_TRY(bhr_launch_march(ctx, call));              // records the ring slot's march events
+    if (adaptive) BHR_TRY(bhr_launch_adaptive(ctx, call));
+    // the march's end is the timing ring's event (recorded by the launcher): an event of its own between the march and the
+    // H pass is another ~5 us barrier packet in the frame's stream (kernel-trace gaps: 10 us with two records, 0 with none)
+    f.march_done = ctx->ring_ev[ring * 3 + 1];
+    return post_on_slot(ctx, flags, k, ring);
+}
+
+// A shutter frame on slot k (bhr_render_shutter): n skip-bloom marches into the slot's layers, each followed by its
+// accumulation launch (shutter.hip), then the post-pass on the resolved layers as bhr_bloom runs it.  All on the slot's
+// stream; a two-stream hybrid sample forks onto the slot's second stream and joins before its accumulation, and the next
+// sample's fork waits for that accumulation.  The samples count into the frame's one ring cell and share its events: the
+// march bracket runs from the first sample's start to behind the last accumulation.
+int32_t shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, int n, uint32_t flags, int k, int ring) {
+    bhr_frame_slot &f = ctx->slots[k];
+    BHR_TRY(bhr_frame_begin(ctx, flags));              // the frame's post-pass and its buffers, before anything is launched
+    const bool adaptive = ctx->ada_k > 1;
+    ctx->ada_frame = adaptive;
+    for (int j = 0; j < n; ++j) {
+        // skip-bloom marches: they leave the split post-pass's packed operands alone
+        const bhr_march_call call = {&cams[j], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, ctx->ss,
+                                     /* keep_start */ j > 0};
+        BHR_TRY(bhr_launch_march(ctx, call));
+        if (adaptive) BHR_TRY(bhr_launch_adaptive(ctx, call));
+        if (n > 1) BHR_TRY(bhr_launch_shutter_accumulate(ctx, j, n));
+    }
+    BHR_HIP(hipEventRecord(ctx->ring_ev[ring * 3 + 1], f.stream));
+    ctx->march_end_recorded = 1;
+    ctx->counters.rays *= (uint64_t)n;
+    f.march_done = ctx->ring_ev[ring * 3 + 1];
+    if (f.frame_split) BHR_TRY(bhr_launch_bloom_pack(ctx));            // the resolved disk layer -> the H pass's operands, bg + disk
+    return post_on_slot(ctx, flags, k, ring);
+}
+
+// A frame on the context's next frame slot: orders the slot's stream behind the scene stream, points the launchers at the
+// slot, runs `body(slot, ring slot)` and keeps the books (slot rotation, timing ring).  exclusive: slot 0, behind every
+// frame in flight (launches that use per-context scratch).
+extern "C++" template <class Body>
+int32_t frame_on_next_slot(bhr_ctx *ctx, uint32_t flags, bool exclusive, Body body) {
+    ctx->stream = ctx->scene_stream;
+    if (exclusive) BHR_TRY(bhr_enter(ctx));
+    const int k = (ctx->n_slots > 1 && !exclusive) ? ctx->next_slot : 0;
+    BHR_TRY(alloc_slot(ctx, k));
+    bhr_frame_slot &f = ctx->slots[k];
+    if (!(flags & BHR_SKIP_BLOOM)) BHR_TRY(bhr_bloom_prepare(ctx));   // one-off tables, on the scene stream
+    if (f.stream != ctx->scene_stream) {
+        BHR_HIP(hipEventRecord(ctx->scene_ev, ctx->scene_stream));    // everything the scene stream has been given so far
+        BHR_HIP(hipStreamWaitEvent(f.stream, ctx->scene_ev, 0));
+    }
+    const int ring = (int)(ctx->ring_head % BHR_TIMING_RING);
+    ctx->active_slot = k;
+    ctx->stream = f.stream;
+    const int32_t rc = body(k, ring);
+    ctx->stream = ctx->scene_stream;
+    f.in_flight = 1;
+    BHR_TRY(rc);
+    if (ctx->n_slots > 1 && !exclusive) ctx->next_slot = (k + 1) % ctx->n_slots;
+    ctx->last_slot = ring;
+    ctx->ring_head += 1;
+    ctx->last_flags = (int32_t)flags;
+    ctx->timing_valid = 1;
     return BHR_OK;
 }
 }  // namespace
@@ -865,31 +930,22 @@ int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (ctx->n_slots > 1 && ctx->opt.calibrate_streams && !ctx->streams_calibrated && !ctx->calibrating &&
         !(flags & (BHR_PERSISTENT | BHR_ROW_COSTS)) && ++ctx->two_slot_frames > 8)
         BHR_TRY(calibrate_slot_streams(ctx, cam, flags));
-    ctx->stream = ctx->scene_stream;
     // launches that use per-context scratch (work queue of the persistent schedule, row-cost profile) stay on one slot
     const bool exclusive = (flags & (BHR_PERSISTENT | BHR_ROW_COSTS)) != 0;
-    if (exclusive) BHR_TRY(bhr_enter(ctx));
-    const int k = (ctx->n_slots > 1 && !exclusive) ? ctx->next_slot : 0;
-    BHR_TRY(alloc_slot(ctx, k));
-    bhr_frame_slot &f = ctx->slots[k];
-    if (!(flags & BHR_SKIP_BLOOM)) BHR_TRY(bhr_bloom_prepare(ctx));   // one-off tables, on the scene stream
-    if (f.stream != ctx->scene_stream) {
-        BHR_HIP(hipEventRecord(ctx->scene_ev, ctx->scene_stream));    // everything the scene stream has been given so far
-        BHR_HIP(hipStreamWaitEvent(f.stream, ctx->scene_ev, 0));
-    }
-    const int ring = (int)(ctx->ring_head % BHR_TIMING_RING);
-    ctx->active_slot = k;
-    ctx->stream = f.stream;
-    const int32_t rc = render_on_slot(ctx, cam, flags, k, ring);
-    ctx->stream = ctx->scene_stream;
-    f.in_flight = 1;
-    BHR_TRY(rc);
-    if (ctx->n_slots > 1 && !exclusive) ctx->next_slot = (k + 1) % ctx->n_slots;
-    ctx->last_slot = ring;
-    ctx->ring_head += 1;
-    ctx->last_flags = (int32_t)flags;
-    ctx->timing_valid = 1;
-    return BHR_OK;
+    return frame_on_next_slot(ctx, flags, exclusive, [&](int k, int ring) { return render_on_slot(ctx, cam, flags, k, ring); });
+}
+
+// One frame as the mean of n marches (include/bhr.h).  One frame of one frame slot: the next frame takes the other slot.
+// It neither triggers nor counts towards the calibration of slot 1's stream (the frames that does times are bhr_render's).
+int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags) {
+    if (!ctx || !cams) return bhr_fail(BHR_ERR_INVALID, "bhr_render_shutter: null argument");
+    if (n < 1 || n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "bhr_render_shutter: %d samples (1 .. %d)", n, BHR_SHUTTER_MAX_SAMPLES);
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_render_shutter: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
+    if (flags & (BHR_PERSISTENT | BHR_ROW_COSTS))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_render_shutter: BHR_PERSISTENT and BHR_ROW_COSTS are not available for shutter frames");
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring) { return shutter_on_slot(ctx, cams, n, flags, k, ring); });
 }
 
 int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out) {
@@ -960,6 +1016,15 @@ int32_t bhr_debug_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes, in
         for (int c = 0; c < 6; ++c) geom[2 + c] = ctx->calib_fps[c];
         return BHR_OK;
     }
+    if (which == 5) {                                   // option "shutter_timing": geom[0] = bracketed accumulation launches of the last shutter frame, [1] = their time in ns
+        if (!geom) return bhr_fail(BHR_ERR_INVALID, "bhr_debug_read: shutter timing needs geom");
+        BHR_HIP(hipStreamSynchronize(ctx->stream));
+        double ms = 0.0;
+        for (int j = 0; j < ctx->shutter_ev_n; ++j) ms += (double)ev_ms(ctx->shutter_ev[2 * j], ctx->shutter_ev[2 * j + 1]);
+        geom[0] = ctx->shutter_ev_n;
+        geom[1] = (int32_t)(ms * 1e6 + 0.5);
+        return BHR_OK;
+    }
     if (which == 3) {                                   // geom[0..9]: do pairs of the context's streams share a hardware queue (-1: no such stream)
         if (!geom) return bhr_fail(BHR_ERR_INVALID, "bhr_debug_read: stream map needs geom");
         hipStream_t st[5] = {ctx->scene_stream, ctx->slots[0].stream, ctx->n_slots > 1 ? ctx->slots[1].stream : nullptr, ctx->slots[0].aux_stream, ctx->slots[1].aux_stream};
@@ -1006,6 +1071,7 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     else if (n == "mip_lds") o.mip_lds = v != 0;
     else if (n == "group_threads") o.group_threads = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "group_schedule") o.group_schedule = v < 0 ? -1 : (v ? 1 : 0);
+    else if (n == "shutter_timing") o.shutter_timing = v != 0;
     else if (n == "png16_menu") {   // the tables are rebuilt at the next encode; no encode may be running on the old ones
         BHR_TRY(bhr_enter(ctx));
         BHR_HIP(hipStreamSynchronize(ctx->scene_stream));

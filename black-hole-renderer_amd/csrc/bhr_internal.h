@@ -31,6 +31,7 @@
 // the largest disk value the split-f16 post-pass carries: two f16 halves of x 2^14 (bloom.hip); a written DISK layer with a
 // larger one goes through the exact f32 kernels (bhr_write_layer, bhr_bloom)
 #define BHR_SPLIT_DISK_MAX 3.99f
+#define BHR_SHUTTER_MAX_SAMPLES 64   // samples of a shutter frame (bhr_render_shutter)
 #define BHR_STEP_LANES 128
 #define BHR_STEP_STRIDE 32          // in u64 words
 #define BHR_STEP_CELL (BHR_STEP_LANES * BHR_STEP_STRIDE)
@@ -133,6 +134,7 @@ struct bhr_march_call {
     bool time_untimed;       // an untimed launch records its march-end event too (BHR_GROUP_TIME_MARCH); off, the tile's stream carries no event between march and H pass
     bool defer_end;          // the caller records the march-end event (adaptive frames: the refinement follows the base march)
     int32_t ss;              // supersampling factor of the frame being marched
+    bool keep_start;         // a later sample of a shutter frame (bhr_render_shutter): the march-start event stays the first sample's
 };
 
 // The march kernels by what they do; each compilation of march.hip returns its own instantiation of a name (or null) from
@@ -192,6 +194,7 @@ struct bhr_options {
     int32_t group_threads;      // BHR_GROUP_THREADS: -1 by device layout (default), 0 / 1 one submitting thread / one per tile
     int32_t group_schedule;     // BHR_GROUP_SCHEDULE: -1 by flags (default), 0 serial, 1 pipelined
     int32_t png16_menu;         // BHR_PNG16_MENU: 1 (default) the 16-bit device PNG codes from its own menu, 0 from the 8-bit one (A/B runs)
+    int32_t shutter_timing;     // BHR_SHUTTER_TIMING: 1 a shutter frame brackets each accumulation launch with HIP events (bhr_debug_read, which = 5); default 0
 };
 
 // geometry of a context's split-f16 bloom buffers (bloom.hip)
@@ -240,6 +243,8 @@ struct bhr_frame_slot {
     int32_t *d_ada_list;
     unsigned char *d_ada_mask;
     unsigned int *d_ada_counts;
+    // shutter frames (shutter.hip), on first use: the running sums of the samples' BG and DISK layers, (rows, W, 3) f32 each
+    float *d_acc_bg, *d_acc_disk;
     // second march stream: the strict tiles of a two-stream hybrid march run on it beside the fast ones instead of ahead of
     // them (bhr_aux_fork / _join, which creates the streams of all slots on first use)
     hipStream_t aux_stream;
@@ -339,6 +344,9 @@ struct bhr_ctx {
     float *d_gather;           // (H, W, 3): full frame gathered from the tiles of a group render (BHR_GATHER_PEER), on tile 0
     void *png_dev;             // device PNG encoder state (png_device.hip), created on first use
     void *jpeg_dev;            // device JPEG encoder state (jpeg_device.hip), created on first use
+    // option "shutter_timing": a start / end event per accumulation launch of the last shutter frame (shutter.hip), on first use
+    hipEvent_t shutter_ev[2 * BHR_SHUTTER_MAX_SAMPLES];
+    int32_t shutter_ev_n;      // accumulation launches of the last shutter frame that were bracketed
     void *pop_host;            // pinned staging of bhr_accumulate_population (lifecycle.hip)
     float *h_pinned;           // staging for readbacks
     size_t h_pinned_bytes;
@@ -475,6 +483,11 @@ int32_t bhr_launch_quantize_dither(bhr_ctx *ctx);   // d_final -> d_final_u8, bl
 // jpeg_device.hip: (rows, W, 3) u8 at d_rgb -> JFIF file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
 int32_t bhr_launch_jpeg_encode(bhr_ctx *ctx, int32_t quality, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
 void bhr_jpeg_dev_free(bhr_ctx *ctx);
+// shutter.hip: sample j of the n > 1 samples of a shutter frame has been marched into the active slot's d_bg / d_disk; on
+// ctx->stream: j = 0 starts the slot's running sums with it, 0 < j < n - 1 adds it, j = n - 1 adds it and stores the mean
+// (sum * (1.0f / n)) back into d_bg / d_disk.  The sums are allocated here on first use.
+int32_t bhr_launch_shutter_accumulate(bhr_ctx *ctx, int32_t j, int32_t n);
+void bhr_shutter_free(bhr_ctx *ctx);                                 // the timing events
 void bhr_population_free(bhr_ctx *ctx);                              // lifecycle.hip
 int32_t bhr_launch_build_mips(bhr_ctx *ctx);
 int32_t bhr_launch_background(bhr_ctx *ctx, float t);

@@ -322,7 +322,7 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     if (slot < 0 && first_part) BHR_HIP(hipMemsetAsync(a.ray_steps, 0, sizeof(unsigned long long) * BHR_STEP_CELL, stream));
     if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(bhr_slot(ctx).d_queue, 0, sizeof(unsigned int), stream));
     // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
-    if (first_part) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, slot), stream));
+    if (first_part && !call.keep_start) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, slot), stream));
     const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags));
     if (!k.fn && !(part && part->n <= 0 && part->repair != 2))
         return bhr_fail(BHR_ERR_STATE, "bhr_render: no march kernel for this launch (supersampling %d, flags %u)", call.ss, flags);

@@ -245,8 +245,25 @@ def assemble_video(temp_dir: str, n_frames: int, fps: int, output_path: str, cod
     return True
 
 
+SHUTTER_MAX_SAMPLES = 64
+
+
+def shutter_times(frame, shutter: float, n: int) -> List[float]:
+    """The n fractional frame numbers at which frame ``frame`` is sampled under a shutter open for ``shutter`` of a frame
+    time: u_j = frame + shutter * ((j + 0.5) / n - 0.5), the midpoints of n equal parts of the exposure, in binary64.  They
+    are centred on the frame (n = 1 is the frame itself) and span shutter * (n - 1) / n."""
+    return [float(frame) + float(shutter) * ((j + 0.5) / n - 0.5) for j in range(n)]
+
+
+def check_shutter(shutter, shutter_samples) -> None:
+    if isinstance(shutter, bool) or not isinstance(shutter, (int, float)) or not (0.0 <= shutter <= 1.0):
+        raise ValueError(f"shutter must be between 0 and 1 (the share of the frame time the shutter is open), got {shutter!r}")
+    if isinstance(shutter_samples, bool) or not isinstance(shutter_samples, int) or not (1 <= shutter_samples <= SHUTTER_MAX_SAMPLES):
+        raise ValueError(f"shutter_samples must be an integer between 1 and {SHUTTER_MAX_SAMPLES}, got {shutter_samples!r}")
+
+
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
-                    bit_depth=8, dither="none") -> dict:
+                    bit_depth=8, dither="none", shutter=0.0, shutter_samples=8) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -258,6 +275,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(bit_depth=bit_depth)
     if dither != "none":
         params.update(dither=dither)
+    if shutter > 0:
+        params.update(shutter=shutter, shutter_samples=shutter_samples)
     return params
 
 
@@ -292,7 +311,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  assemble: bool = True, png_level: int = DEVICE, sink_slots: int = 0, sink_workers: int = 0,
                  video_stream: str = "auto", stats: Optional[dict] = None, supersample: Optional[int] = None,
                  supersample_threshold: Optional[float] = None, video_codec: str = "auto", video_quality: int = 90,
-                 bit_depth: int = 8, dither: str = "none", **_deprecated_kwargs) -> None:
+                 bit_depth: int = 8, dither: str = "none", shutter: float = 0.0, shutter_samples: int = 8,
+                 **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -320,7 +340,17 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     host); the yuv420p stream stays 8-bit, and the PNG-in-MP4 fallback muxes the files as it muxes any PNG.  ``dither="blue"``:
     every 8-bit consumer of the loop -- PNG or JPEG frames, the yuv420p stream -- gets the blue-noise dithered rows
     (HipRenderer.set_dither; the renderer's mode is restored on return).  The progress record carries the two only when
-    they are not the defaults, as it does the codec: a resume with other values starts over."""
+    they are not the defaults, as it does the codec: a resume with other values starts over.
+
+    ``shutter`` (0..1, the share of the frame time the shutter is open) above 0: motion blur.  Frame f is the mean of
+    ``shutter_samples`` (1..64) marches (HipRenderer.render_shutter_async) at the fractional frame numbers u_j of
+    shutter_times(f, shutter, shutter_samples): sample j is marched from orbit_position(static_cam_pos, u_j, ...) (the static
+    position without ``orbit``) with the disk rolled by t_offset = (u_j - f) * disk_rotation_speed, the Keplerian roll of the
+    texture within the exposure.  The texture itself is the frame's, composed once at t = f * dt: the populations and the
+    noise are NOT sampled within the exposure.  With ``shutter == 0`` the loop calls render_async exactly as it always has,
+    whatever ``shutter_samples`` is; the progress record carries the two values only when ``shutter > 0``, and a resume with
+    other values starts over."""
+    check_shutter(shutter, shutter_samples)
     if video_codec not in VIDEO_CODECS:
         raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
     check_depth_and_dither(bit_depth, dither, video_codec)
@@ -336,7 +366,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     temp_dir = _frames_dir(output_path)
     submitted: List[int] = []
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
-    params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither)
+    params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither,
+                             shutter, shutter_samples)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -432,7 +463,12 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             continue
         cam_pos = orbit_position(static_cam_pos, frame, n_frames, orbit_degrees) if orbit else static_cam_pos
         t0 = time.time()
-        renderer.render_async(cam_pos, fov, frame=0)   # lens flare, when enabled, is applied on the device
+        if shutter > 0:
+            times = shutter_times(frame, shutter, shutter_samples)
+            positions = [orbit_position(static_cam_pos, u, n_frames, orbit_degrees) if orbit else static_cam_pos for u in times]
+            renderer.render_shutter_async(positions, fov, [(u - frame) * disk_rotation_speed for u in times])
+        else:
+            renderer.render_async(cam_pos, fov, frame=0)   # lens flare, when enabled, is applied on the device
         sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))
         if stream is not None:
             try:

@@ -387,8 +387,9 @@ class HipRenderer:
         self._dv2 = (cp, m_sh, m_hs, t_peak)
 
     # ------------------------------------------------------------------ rendering
-    def camera_uniforms(self, cam_pos, fov: float, frame: int = 0) -> _lib.Camera:
-        """f64 camera -> the f32 uniforms of render.py:3880-3897."""
+    def camera_uniforms(self, cam_pos, fov: float, frame: int = 0, t_offset: Optional[float] = None) -> _lib.Camera:
+        """f64 camera -> the f32 uniforms of render.py:3880-3897.  ``t_offset``: the disk's roll given directly (a sample of a
+        shutter frame) instead of ``frame * disk_rotation_speed``."""
         eye, right, up, fwd, pw, ph = build_camera(np.array(cam_pos, dtype=np.float64), fov, self.width,
                                                    self.height)
         cam = _lib.Camera()
@@ -398,7 +399,7 @@ class HipRenderer:
         cam.forward[:] = list(fwd.astype(np.float32))
         cam.pixel_width, cam.pixel_height = float(pw), float(ph)
         cam.r_escape = float(max(self.r_max, float(np.linalg.norm(eye)) * 2))
-        cam.t_offset = float(frame) * self.disk_rotation_speed
+        cam.t_offset = float(frame) * self.disk_rotation_speed if t_offset is None else float(t_offset)
         return cam
 
     @staticmethod
@@ -416,6 +417,28 @@ class HipRenderer:
         if self.lens_flare if lens_flare is None else lens_flare:
             flags |= _lib.LENS_FLARE          # device twin of _apply_lens_flare (render.py:3920-4028)
         _lib.check(self._lib.bhr_render(self._ctx, C.byref(cam), flags))
+
+    def render_shutter_async(self, cam_positions, fov: float, t_offsets, skip_differentials: bool = False,
+                             skip_bloom: bool = False, math=None, lens_flare=None) -> None:
+        """Motion blur: one frame as the mean of ``len(cam_positions)`` marches (bhr_render_shutter; include/bhr.h states the
+        frame).  Sample j is marched from ``cam_positions[j]`` with the disk rolled by ``t_offsets[j]``; the BG and DISK layers
+        are the f32 means of the samples', the post-pass runs once on them.  1..64 samples; whole-frame contexts only."""
+        cam_positions, t_offsets = list(cam_positions), list(t_offsets)
+        if len(cam_positions) != len(t_offsets):
+            raise ValueError(f"{len(cam_positions)} camera positions for {len(t_offsets)} t_offsets")
+        cams = (_lib.Camera * max(len(cam_positions), 1))()
+        for j, (pos, t) in enumerate(zip(cam_positions, t_offsets)):
+            cams[j] = self.camera_uniforms(pos, fov, t_offset=t)
+        flags = self._flags(skip_differentials, skip_bloom, False, math)
+        if self.lens_flare if lens_flare is None else lens_flare:
+            flags |= _lib.LENS_FLARE
+        _lib.check(self._lib.bhr_render_shutter(self._ctx, cams, len(cam_positions), flags))
+
+    def render_shutter(self, cam_positions, fov: float, t_offsets, skip_differentials: bool = False,
+                       skip_bloom: bool = False, math=None, lens_flare=None) -> np.ndarray:
+        """render_shutter_async, then the frame: (rows, width, 3) float32 in [0, 1], as render returns it."""
+        self.render_shutter_async(cam_positions, fov, t_offsets, skip_differentials, skip_bloom, math, lens_flare)
+        return self.read_layer(_lib.LAYER_FINAL)
 
     def sync(self) -> None:
         _lib.check(self._lib.bhr_sync(self._ctx))
@@ -577,6 +600,13 @@ class HipRenderer:
         geom = (C.c_int32 * 10)()
         _lib.check(self._lib.bhr_debug_read(self._ctx, 4, None, 0, geom))
         return {"done": bool(geom[0]), "kept": int(geom[1]), "candidates_fps": [int(geom[2 + c]) for c in range(6)]}
+
+    def shutter_timing(self) -> dict:
+        """The accumulation launches of the last shutter frame rendered under option "shutter_timing" 1 (bhr_debug_read, which
+        = 5): how many were bracketed with HIP events and the sum of their times in ms.  Synchronises."""
+        geom = (C.c_int32 * 10)()
+        _lib.check(self._lib.bhr_debug_read(self._ctx, 5, None, 0, geom))
+        return {"launches": int(geom[0]), "ms": int(geom[1]) * 1e-6}
 
     def hybrid_launch_order(self) -> np.ndarray:
         """The partitioned launch order of the last math="hybrid" march: tile indices, the strict tiles first

@@ -235,6 +235,25 @@ BHR_API int32_t bhr_eval_noise(bhr_ctx *ctx, const float *coords, int64_t n, int
  * updates never race a march.  BHR_FRAME_SLOTS=1 in the environment of bhr_create: one frame at a time.  (Every BHR_*
  * environment switch of the library is read once, by bhr_create.) */
 BHR_API int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
+/* Motion blur: one frame as the mean of n marches over a shutter.  cams[0 .. n - 1] (1 <= n <= 64) are the samples' cameras,
+ * each with its own position, basis and t_offset (the samplers roll the disk by phi + t_offset * Omega(r), so the Keplerian
+ * roll within the exposure is the camera's t_offset).  For each layer L in {BG, DISK}:
+ *   L_j  is, bit for bit, what bhr_render(ctx, &cams[j], flags | BHR_SKIP_BLOOM) stores for that layer -- under the context's
+ *        arithmetic, disk source, anti-aliasing, supersampling or adaptive supersampling, hybrid lists and guards;
+ *   acc  = L_0, then acc = acc + L_j for j = 1 .. n - 1 in that order, one f32 addition per channel;
+ *   L    = acc * (1.0f / (float)n): the reciprocal rounded to f32 once, the product once, no FMA contraction anywhere.
+ * For n = 1 this is L_0 itself.  BLUR and FINAL are what bhr_bloom computes from the resolved BG and DISK under the frame's
+ * arithmetic (BHR_SKIP_BLOOM in flags suppresses them); BHR_LENS_FLARE then adds what bhr_lens_flare adds.  The resolved
+ * DISK stays in [0, 1], so the split-f16 post-pass applies whenever it would for a marched frame.  bhr_set_outputs,
+ * bhr_read_final_u8 / _u16, the dither, the PNG and JPEG sinks and the y4m stream work on the frame as on any other.
+ * The n marches, the accumulation (csrc/shutter.hip) and the post-pass are ONE frame of ONE frame slot, all on that slot's
+ * stream: the next bhr_render or bhr_render_shutter takes the other slot, as after a bhr_render.  bhr_counters: rays and
+ * ray_steps are the sums over the n marches (under adaptive supersampling rays counts the refinement of the last sample
+ * only); the frame has one entry in the timing ring, its march bracket from the first sample's start to behind the last
+ * accumulation.  Asynchronous.
+ * BHR_ERR_INVALID, with nothing launched and the context as it was: ctx or cams NULL, n < 1 or n > 64, a row-block
+ * context, BHR_PERSISTENT or BHR_ROW_COSTS in flags. */
+BHR_API int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags);
 /* image_field/disk_layer_field/blur_field .to_numpy() and the final image,
  * for the context's rows: (row1-row0, width, 3) f32.  Synchronises. */
 BHR_API int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out);
@@ -320,12 +339,16 @@ BHR_API int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]);
  *   "group_schedule"  BHR_GROUP_SCHEDULE  -1 by flags, else pipelined where a halo copy can hide (exact-f32 post-pass on distinct
  *                                         devices) and serial otherwise; 0 serial, 1 pipelined (explicit flags still win)
  *   "png16_menu"      BHR_PNG16_MENU      1 (default) the 16-bit device PNG encoder codes from its own menu, 0 from the 8-bit one (A/B runs)
+ *   "shutter_timing"  BHR_SHUTTER_TIMING  1 a shutter frame brackets each of its accumulation launches with a pair of HIP events
+ *                                         (bhr_debug_read, which = 5; ~5 us per event in the frame's stream); default 0
  * (bhr_create only: BHR_FRAME_SLOTS.) */
 BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
 /* Diagnostics (tests): the split-f16 post-pass's packed intermediates of the last frame as raw bytes -- which = 0 the H pass's
  * input (csrc/bloom.hip: pa), 1 its output / the V pass's input (pb) -- and the layout's geometry: geom[10] = {NT, n_tx, WP, YB,
  * GP, g0, t_first, n_ty, pbr, GR}; which = 2 the launch order of the last math-hybrid march as int32 tile indices, strict tiles
  * first (geom[0] = tiles in it; bhr_hybrid_info tells how many are strict).  out == NULL or bytes == 0: geometry only.
+ * which = 5 (option "shutter_timing"): geom[0] = accumulation launches of the last shutter frame, geom[1] = their summed
+ * HIP-event time in nanoseconds.
  * Synchronises. */
 BHR_API int32_t bhr_debug_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes, int32_t *geom);
 /* TaichiRenderer._apply_lens_flare(final, disk) (render.py:3925-4028) on the device, standalone:
