@@ -16,9 +16,11 @@ BHR_ERR_INVALID, BHR_ERR_NO_DEVICE, BHR_ERR_HIP, BHR_ERR_STATE, BHR_ERR_NOMEM = 
 SKIP_DIFFERENTIALS, SKIP_BLOOM, PERSISTENT, FORCE_FAST, FORCE_STRICT, LENS_FLARE, ROW_COSTS, GATHER_PEER = 1, 2, 4, 8, 16, 32, 64, 128
 FORCE_HYBRID, GATHER_U8, GROUP_SERIAL, GROUP_PIPELINED, GROUP_TIME_MARCH, GROUP_ASYNC = 256, 512, 1024, 2048, 4096, 8192
 MATH_FAST, MATH_STRICT, MATH_HYBRID = 0, 1, 2
-LAYER_FINAL, LAYER_BG, LAYER_DISK, LAYER_BLUR = 0, 1, 2, 3
+LAYER_FINAL, LAYER_BG, LAYER_DISK, LAYER_BLUR, LAYER_HDR = 0, 1, 2, 3, 4
 OUTPUT_F32, OUTPUT_BLUR, OUTPUT_U8 = 1, 2, 4
 DITHER_NONE, DITHER_BLUE = 0, 1
+GRADE_CLIP, GRADE_REINHARD, GRADE_ACES = 0, 1, 2
+TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
 
 # every symbol include/bhr.h declares (tests check the .so exports exactly these)
 SYMBOLS = (
@@ -26,7 +28,7 @@ SYMBOLS = (
     "bhr_set_skybox", "bhr_skybox_add_glow", "bhr_skybox_build", "bhr_get_skybox", "bhr_set_disk_texture", "bhr_get_disk_texture", "bhr_get_disk_mip", "bhr_num_mip_levels",
     "bhr_bg_init", "bhr_generate_background", "bhr_set_entity_staging", "bhr_set_comp", "bhr_read_comp",
     "bhr_fill_comp_slice", "bhr_set_compose_stats", "bhr_compose_texture", "bhr_eval_noise", "bhr_render", "bhr_render_shutter",
-    "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_read_final_u16", "bhr_set_dither", "bhr_dither_matrix", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
+    "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_read_final_u16", "bhr_set_dither", "bhr_dither_matrix", "bhr_set_grade", "bhr_grade_frame", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
     "bhr_stats_prepare", "bhr_stats_select", "bhr_stats_row_statistics",
     "bhr_png_bound16", "bhr_png_encode16", "bhr_png_write16", "bhr_png16_device_bound", "bhr_png16_device_max_width", "bhr_png16_encode_device", "bhr_sink_create_png16",
     "bhr_png_bound", "bhr_png_encode", "bhr_png_write", "bhr_png_device_bound", "bhr_png_device_max_width", "bhr_png_encode_device", "bhr_png_device_menu",
@@ -56,6 +58,11 @@ class Counters(C.Structure):
                 ("march_vgprs", C.c_int32), ("march_lds_bytes", C.c_int32), ("frames_timed", C.c_int32),
                 ("march_ms_sum", C.c_float), ("bloom_ms_sum", C.c_float), ("ray_steps_sum", C.c_uint64),
                 ("march_busy_ms", C.c_float), ("span_ms", C.c_float)]
+
+
+class Grade(C.Structure):
+    _fields_ = [("op", C.c_int32), ("transfer", C.c_int32), ("exposure_stops", C.c_float), ("white", C.c_float),
+                ("keep_hdr", C.c_int32)]
 
 
 TILE_SHM_WORDS = 8
@@ -131,6 +138,8 @@ def load() -> C.CDLL:
     lib.bhr_read_final_u16.argtypes = [P, C.POINTER(C.c_uint16)]
     lib.bhr_set_dither.argtypes = [P, I32]
     lib.bhr_dither_matrix.argtypes = [C.POINTER(C.c_uint16)]
+    lib.bhr_set_grade.argtypes = [P, C.POINTER(Grade)]
+    lib.bhr_grade_frame.argtypes = [P]
     lib.bhr_get_counters.argtypes = [P, C.POINTER(Counters)]
     lib.bhr_timing_reset.argtypes = [P]
     lib.bhr_timing_dump.argtypes = [P, F, I32]

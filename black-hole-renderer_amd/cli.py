@@ -84,6 +84,19 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "instantaneous exposure); every frame is the mean of --shutter_samples marches over the exposure")
     p.add_argument("--shutter_samples", type=int, default=8, metavar="N",
                    help="--shutter: marches per frame, 1..64 (default: 8)")
+    p.add_argument("--tonemap", type=str, default=None, choices=["clip", "reinhard", "aces"],
+                   help="grade the frame in place of the hard clip at 1 (default: off): clip = exposure and transfer only; "
+                        "reinhard = extended Reinhard roll-off, --white maps to 1; aces = Narkowicz's ACES filmic fit")
+    p.add_argument("--exposure", type=float, default=None, metavar="STOPS",
+                   help="--tonemap: exposure in stops, -16..16, the frame is scaled by 2^STOPS ahead of the operator (default: 0)")
+    p.add_argument("--white", type=float, default=None, metavar="W",
+                   help="--tonemap reinhard: the scene value that maps to 1, in (0, 65504] (default: 2.5)")
+    p.add_argument("--transfer", type=str, default=None, choices=["linear", "srgb"],
+                   help="--tonemap: display transfer function: linear = the values as they are, as the reference writes them "
+                        "(default); srgb = the sRGB encoding curve")
+    p.add_argument("--hdr_output", type=str, default=None, metavar="PATH",
+                   help="still images: also write the unclipped scene-linear frame, before exposure, as PATH (.pfm: exact f32; "
+                        ".hdr: Radiance RGBE)")
     p.add_argument("--ignore_taichi_cache", action="store_true", help="accepted for compatibility; no effect")
     p.add_argument("--video", action="store_true", help="render frames and assemble a video")
     p.add_argument("--interactive", action="store_true", help="not available in this build (needs ti.GUI)")
@@ -99,7 +112,21 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    # --exposure, --white, --transfer and --hdr_output without --tonemap mean --tonemap clip
+    if args.tonemap is None and any(v is not None for v in (args.exposure, args.white, args.transfer, args.hdr_output)):
+        args.tonemap = "clip"
+    if args.tonemap is not None:
+        args.exposure = 0.0 if args.exposure is None else args.exposure
+        args.white = 2.5 if args.white is None else args.white
+        args.transfer = "linear" if args.transfer is None else args.transfer
     return args
+
+
+def grade_from_args(args):
+    """The grade of a command line as drivers.render_image / render_video take it: None without --tonemap."""
+    if getattr(args, "tonemap", None) is None:
+        return None
+    return dict(tonemap=args.tonemap, exposure=args.exposure, white=args.white, transfer=args.transfer)
 
 
 def validate_args(args) -> None:
@@ -149,6 +176,19 @@ def validate_args(args) -> None:
         raise ValueError(f"shutter must be between 0 and 1, got {args.shutter}")
     if not (1 <= getattr(args, "shutter_samples", 8) <= 64):
         raise ValueError(f"shutter_samples must be between 1 and 64, got {args.shutter_samples}")
+    if getattr(args, "tonemap", None) is not None:
+        if not (math.isfinite(args.exposure) and -16.0 <= args.exposure <= 16.0):
+            raise ValueError(f"exposure must be between -16 and 16 stops, got {args.exposure}")
+        if not (math.isfinite(args.white) and 0.0 < args.white <= 65504.0):
+            raise ValueError(f"white must be greater than 0 and at most 65504, got {args.white}")
+        if getattr(args, "gpus", 1) > 1:
+            raise ValueError("--tonemap renders on one GPU: it does not combine with --gpus > 1")
+    hdr_output = getattr(args, "hdr_output", None)
+    if hdr_output is not None:
+        if args.video:
+            raise ValueError("--hdr_output writes still images: it does not combine with --video")
+        if not hdr_output.lower().endswith((".pfm", ".hdr")):
+            raise ValueError(f"--hdr_output writes .pfm or .hdr files, got {hdr_output!r}")
     if getattr(args, "interactive", False):
         raise ValueError("--interactive needs the Taichi GUI and is not part of this build")
 
@@ -184,7 +224,8 @@ def main(argv=None) -> int:
                              orbit_degrees=args.orbit_degrees, rank=rank, world=world, video_stream=args.video_stream,
                              png_level=(drivers.DEVICE if args.png_encoder == "device" else drivers.VIDEO_LEVEL),
                              video_codec=args.video_codec, video_quality=args.video_quality, bit_depth=args.bit_depth,
-                             dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples)
+                             dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples,
+                             grade=grade_from_args(args))
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -207,6 +248,7 @@ def main(argv=None) -> int:
         r_disk_outer=args.disk_outer_radius, disk_tilt=args.disk_tilt, lens_flare=args.lens_flare,
         anti_alias=args.anti_alias, aa_strength=args.aa_strength, disk_rotation_speed=args.disk_rotation_speed,
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
-        supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither)
+        supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
+        grade=grade_from_args(args), hdr_path=args.hdr_output)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

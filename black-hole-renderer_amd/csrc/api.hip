@@ -100,6 +100,7 @@ static void read_options(bhr_options *o) {
     { const char *e = getenv("BHR_GROUP_SCHEDULE"); o->group_schedule = e && e[0] ? (e[0] == 's' ? 0 : 1) : -1; }
     o->png16_menu = num("BHR_PNG16_MENU", 1) != 0;
     o->shutter_timing = num("BHR_SHUTTER_TIMING", 0) != 0;
+    o->grade_timing = num("BHR_GRADE_TIMING", 0) != 0;
 }
 
 int32_t alloc_slot(bhr_ctx *ctx, int k) {
@@ -155,7 +156,7 @@ int32_t ensure_bloom_buffers(bhr_ctx *ctx, int k, bool split) {
 void free_slot(bhr_ctx *ctx, int k) {
     bhr_frame_slot &f = ctx->slots[k];
     void *bufs[] = {f.d_bg, f.d_disk, f.d_blur, f.d_final, f.d_final_u8, f.d_final_u16, f.d_hblur_base, f.d_pa, f.d_pb, f.d_sum, f.d_queue,
-                    f.d_glow_hw, f.d_glow_wh, f.d_flare_c0, f.d_flare_c12, f.d_flare_sums, f.d_ada_list, f.d_ada_mask, f.d_ada_counts, f.d_acc_bg, f.d_acc_disk};
+                    f.d_glow_hw, f.d_glow_wh, f.d_flare_c0, f.d_flare_c12, f.d_flare_sums, f.d_ada_list, f.d_ada_mask, f.d_ada_counts, f.d_acc_bg, f.d_acc_disk, f.d_hdr};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (f.done) (void)hipEventDestroy(f.done);
@@ -495,6 +496,7 @@ void bhr_destroy(bhr_ctx *ctx) {
     bhr_png_dev_free(ctx);
     bhr_jpeg_dev_free(ctx);
     bhr_shutter_free(ctx);
+    bhr_grade_free(ctx);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);
     bhr_pipe_free(ctx);
@@ -730,8 +732,28 @@ int32_t post_on_slot(bhr_ctx *ctx, uint32_t flags, int k, int ring) {
     uint32_t want = ctx->out_want;
     if (flags & BHR_LENS_FLARE) want = (want | BHR_OUT_F32) & ~BHR_OUT_U8;
     if (ctx->dither) want = (want | BHR_OUT_F32) & ~BHR_OUT_U8;      // dithered rows: the same route (quantize.hip)
+    // a graded frame (bhr_set_grade): the V pass stores BLUR only -- zeros for a BHR_SKIP_BLOOM frame -- and the grade kernel
+    // writes FINAL, the authority for everything made on demand, and the undithered u8 rows where they are wanted (grade.hip)
+    const bool graded = ctx->grade_on != 0;
+    if (graded) want = BHR_OUT_BLUR;
     BHR_TRY(bhr_frame_post(ctx, with_bloom, want, zero_cell));
-    if (flags & BHR_LENS_FLARE) {
+    if (graded) {
+        const bool keep = ctx->grade.keep_hdr != 0, rows_u8 = (ctx->out_want & BHR_OUT_U8) && !ctx->dither;
+        if (flags & BHR_LENS_FLARE) {
+            if (ctx->rows != ctx->cfg.height)
+                return bhr_fail(BHR_ERR_INVALID, "bhr_render: the lens flare needs whole-frame sums; use bhr_group_render for row blocks");
+            // the flare sits in front of the sensor response: s -> the HDR plane, + flare without the upper clip, then the grade
+            BHR_TRY(bhr_launch_grade_sum(ctx));
+            BHR_TRY(bhr_launch_flare_glow(ctx, true));
+            BHR_TRY(bhr_launch_flare_sums(ctx));
+            BHR_TRY(bhr_launch_flare_apply(ctx, nullptr, true));
+            BHR_TRY(bhr_launch_grade(ctx, true, true, rows_u8));
+        } else {
+            BHR_TRY(bhr_launch_grade(ctx, false, keep, rows_u8));
+        }
+        f.have |= BHR_OUT_F32 | (keep ? BHR_OUT_HDR : 0u) | (rows_u8 ? BHR_OUT_U8 : 0u);
+        if (ctx->dither && (ctx->out_want & BHR_OUT_U8)) BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_U8));
+    } else if (flags & BHR_LENS_FLARE) {
         if (ctx->rows != ctx->cfg.height)
             return bhr_fail(BHR_ERR_INVALID, "bhr_render: the lens flare needs whole-frame sums; use bhr_group_render for row blocks");
         // every slot has its own flare scratch (glow, sums): the frames' flare passes overlap like the rest
@@ -958,6 +980,11 @@ int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out) {
         case BHR_LAYER_BG: src = f.d_bg; break;
         case BHR_LAYER_DISK: src = f.d_disk; break;
         case BHR_LAYER_BLUR: src = f.d_blur; BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_BLUR)); break;
+        case BHR_LAYER_HDR:
+            if (!(f.have & BHR_OUT_HDR) || !f.d_hdr)
+                return bhr_fail(BHR_ERR_STATE, "bhr_read_layer: the frame kept no HDR plane (bhr_set_grade with keep_hdr, then render or bhr_grade_frame)");
+            src = f.d_hdr;
+            break;
         default: return bhr_fail(BHR_ERR_INVALID, "bhr_read_layer: unknown layer %d", layer);
     }
     return download(ctx, out, src, (size_t)ctx->rows * ctx->cfg.width * 3 * sizeof(float));
@@ -966,6 +993,7 @@ int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out) {
 int32_t bhr_write_layer(bhr_ctx *ctx, int32_t layer, const float *in) {
     if (!ctx || !in) return bhr_fail(BHR_ERR_INVALID, "bhr_write_layer: bad argument");
     BHR_TRY(use_device(ctx));
+    if (layer == BHR_LAYER_HDR) return bhr_fail(BHR_ERR_INVALID, "bhr_write_layer: BHR_LAYER_HDR is read only");
     float *dst = nullptr;
     bhr_frame_slot &f = bhr_slot(ctx);
     const size_t n = (size_t)ctx->rows * ctx->cfg.width * 3;
@@ -1025,6 +1053,15 @@ int32_t bhr_debug_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes, in
         geom[1] = (int32_t)(ms * 1e6 + 0.5);
         return BHR_OK;
     }
+    if (which == 6) {                                   // option "grade_timing": geom[0] = bracketed launches of the last graded frame's grade stage, [1] = their time in ns
+        if (!geom) return bhr_fail(BHR_ERR_INVALID, "bhr_debug_read: grade timing needs geom");
+        BHR_HIP(hipStreamSynchronize(ctx->stream));
+        double ms = 0.0;
+        for (int j = 0; j < ctx->grade_ev_n; ++j) ms += (double)ev_ms(ctx->grade_ev[2 * j], ctx->grade_ev[2 * j + 1]);
+        geom[0] = ctx->grade_ev_n;
+        geom[1] = (int32_t)(ms * 1e6 + 0.5);
+        return BHR_OK;
+    }
     if (which == 3) {                                   // geom[0..9]: do pairs of the context's streams share a hardware queue (-1: no such stream)
         if (!geom) return bhr_fail(BHR_ERR_INVALID, "bhr_debug_read: stream map needs geom");
         hipStream_t st[5] = {ctx->scene_stream, ctx->slots[0].stream, ctx->n_slots > 1 ? ctx->slots[1].stream : nullptr, ctx->slots[0].aux_stream, ctx->slots[1].aux_stream};
@@ -1072,6 +1109,7 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     else if (n == "group_threads") o.group_threads = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "group_schedule") o.group_schedule = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "shutter_timing") o.shutter_timing = v != 0;
+    else if (n == "grade_timing") o.grade_timing = v != 0;
     else if (n == "png16_menu") {   // the tables are rebuilt at the next encode; no encode may be running on the old ones
         BHR_TRY(bhr_enter(ctx));
         BHR_HIP(hipStreamSynchronize(ctx->scene_stream));

@@ -177,6 +177,8 @@ struct BhrDetectArgs {
 #define BHR_OUT_U8 4u     // the frame quantised as save_image does (render.py:423); blue-noise dithered while bhr_set_dither(1)
 // internal only (no bhr_set_outputs bit): the 16-bit rows, always made on demand from the f32 frame (quantize.hip)
 #define BHR_OUT_U16 8u
+// internal only: the HDR plane h of a graded frame that keeps it (grade.hip; bhr_read_layer(BHR_LAYER_HDR)); never asked of bhr_ensure_outputs
+#define BHR_OUT_HDR 16u
 
 // The library's environment switches, read ONCE by bhr_create (nothing on the bhr_render path calls getenv).
 struct bhr_options {
@@ -194,6 +196,7 @@ struct bhr_options {
     int32_t group_threads;      // BHR_GROUP_THREADS: -1 by device layout (default), 0 / 1 one submitting thread / one per tile
     int32_t group_schedule;     // BHR_GROUP_SCHEDULE: -1 by flags (default), 0 serial, 1 pipelined
     int32_t png16_menu;         // BHR_PNG16_MENU: 1 (default) the 16-bit device PNG codes from its own menu, 0 from the 8-bit one (A/B runs)
+    int32_t grade_timing;       // BHR_GRADE_TIMING: 1 a graded frame brackets each launch of its grade stage with HIP events (bhr_debug_read, which = 6); default 0
     int32_t shutter_timing;     // BHR_SHUTTER_TIMING: 1 a shutter frame brackets each accumulation launch with HIP events (bhr_debug_read, which = 5); default 0
 };
 
@@ -227,6 +230,7 @@ struct bhr_frame_slot {
     int32_t disk_wide;         // the DISK layer is a caller's (bhr_write_layer) with a value above BHR_SPLIT_DISK_MAX; a march clears it
     uint8_t *d_final_u8;       // (rows, W, 3)
     uint16_t *d_final_u16;     // (rows, W, 3) 16-bit rows, native endian (bhr_read_final_u16, the 16-bit PNG paths); on first use
+    float *d_hdr;              // (rows, W, 3) the HDR plane of a graded frame (grade.hip): h where the frame keeps it, the flare's target; on first use
     uint32_t have;             // BHR_OUT_* layers of the slot's last frame that are in memory (the V pass stores what was asked for; the rest on demand)
     // the post-pass of the slot's frame, set by bhr_frame_begin: frame_split 0 exact f32 kernels (strict), 1 split-f16
     // matrix-core kernels (fast / hybrid); bhr_ensure_outputs re-runs its V pass
@@ -319,6 +323,15 @@ struct bhr_ctx {
     // takes the route of a flared frame: the V pass keeps f32, the rows are quantised afterwards
     int32_t dither;
     uint16_t *d_dither;        // the 64 x 64 rank matrix on the device, on first use
+    // bhr_set_grade: grade_on = 1 while a grade is set; the frames rendered then get FINAL (and their undithered u8 rows) from
+    // the grade kernel behind a V pass that stores BLUR only (grade.hip).  gain and iw2 are the host's two derived factors
+    int32_t grade_on;
+    bhr_grade grade;
+    float grade_gain, grade_iw2;
+    // option "grade_timing": a start / end event per launch of the last graded frame's grade stage (grade.hip: at most the sum
+    // kernel of a flared frame and the grade kernel), on first use
+    hipEvent_t grade_ev[4];
+    int32_t grade_ev_n;
     uint32_t out_want;         // BHR_OUT_* the frames of this context store (bhr_set_outputs; default: the f32 frame)
     bhr_options opt;           // the BHR_* environment switches, read once by bhr_create
     float *d_wsum_h;           // (3, W) in-bounds weight sums, then (3, W) the split H pass's multiplier 2^-10 / sum
@@ -470,7 +483,8 @@ int32_t bhr_aux_fork(bhr_ctx *ctx);
 int32_t bhr_aux_join(bhr_ctx *ctx);
 int32_t bhr_launch_flare_glow(bhr_ctx *ctx, bool whole_frame);       // flare.hip
 int32_t bhr_launch_flare_sums(bhr_ctx *ctx);
-int32_t bhr_launch_flare_apply(bhr_ctx *ctx, const double *sums);    // sums == nullptr: device-resident totals
+// sums == nullptr: device-resident totals; hdr: onto the slot's HDR plane without the upper clip (a graded frame) instead of FINAL
+int32_t bhr_launch_flare_apply(bhr_ctx *ctx, const double *sums, bool hdr = false);
 int32_t bhr_launch_quantize(bhr_ctx *ctx);                           // api.hip: the frame's u8 rows, on the stream (from the V pass, or FINAL -> u8)
 // png_device.hip: (rows, W, 3) u8 at d_rgb -> PNG file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
 int32_t bhr_launch_png_encode(bhr_ctx *ctx, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
@@ -480,6 +494,10 @@ void bhr_png_dev_free(bhr_ctx *ctx);
 // quantize.hip: the two quantisers that read the f32 FINAL frame, on ctx->stream (bhr_ensure_outputs calls them)
 int32_t bhr_launch_quantize_u16(bhr_ctx *ctx);      // d_final -> d_final_u16 (allocated here on first use)
 int32_t bhr_launch_quantize_dither(bhr_ctx *ctx);   // d_final -> d_final_u8, blue-noise dithered
+// grade.hip, on ctx->stream: FINAL of the active slot under the context's grade, from its BG / DISK / BLUR layers or (from_hdr)
+// from its HDR plane, which is then clamped in place; store_hdr: also the plane h; store_u8: also the undithered u8 rows
+int32_t bhr_launch_grade(bhr_ctx *ctx, bool from_hdr, bool store_hdr, bool store_u8);
+int32_t bhr_launch_grade_sum(bhr_ctx *ctx);         // (d_bg + d_disk) + d_blur -> d_hdr (allocated here on first use)
 // jpeg_device.hip: (rows, W, 3) u8 at d_rgb -> JFIF file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
 int32_t bhr_launch_jpeg_encode(bhr_ctx *ctx, int32_t quality, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
 void bhr_jpeg_dev_free(bhr_ctx *ctx);
@@ -488,6 +506,7 @@ void bhr_jpeg_dev_free(bhr_ctx *ctx);
 // (sum * (1.0f / n)) back into d_bg / d_disk.  The sums are allocated here on first use.
 int32_t bhr_launch_shutter_accumulate(bhr_ctx *ctx, int32_t j, int32_t n);
 void bhr_shutter_free(bhr_ctx *ctx);                                 // the timing events
+void bhr_grade_free(bhr_ctx *ctx);                                   // grade.hip: the timing events
 void bhr_population_free(bhr_ctx *ctx);                              // lifecycle.hip
 int32_t bhr_launch_build_mips(bhr_ctx *ctx);
 int32_t bhr_launch_background(bhr_ctx *ctx, float t);

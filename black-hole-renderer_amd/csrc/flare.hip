@@ -151,6 +151,8 @@ __device__ __forceinline__ double np_mod(double a, double m) {
     return r;
 }
 
+// HDR: the target is the HDR plane of a graded frame (grade.hip), and the sum keeps its headroom -- no upper clip
+template <bool HDR>
 __global__ __launch_bounds__(256) void flare_apply_kernel(float *__restrict__ fin, int W, int H, int row0, int rows,
                                                           const double *__restrict__ d_sums, FlareSums host_sums, int use_host) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -244,7 +246,7 @@ __global__ __launch_bounds__(256) void flare_apply_kernel(float *__restrict__ fi
         }
     }
     float *q = fin + p * 3;
-    for (int c = 0; c < 3; ++c) q[c] = fminf(fmaxf(q[c] + fl[c], 0.0f), 1.0f);
+    for (int c = 0; c < 3; ++c) q[c] = HDR ? fmaxf(q[c] + fl[c], 0.0f) : fminf(fmaxf(q[c] + fl[c], 0.0f), 1.0f);
 }
 
 // The pairwise recursion of one chunk of n elements as leaves + an in-order list of adds; the value of
@@ -330,14 +332,18 @@ int32_t bhr_launch_flare_sums(bhr_ctx *ctx) {
 }
 
 // sums == nullptr: use this context's own device-resident sums (whole-frame context, no host sync).
-int32_t bhr_launch_flare_apply(bhr_ctx *ctx, const double *sums) {
+int32_t bhr_launch_flare_apply(bhr_ctx *ctx, const double *sums, bool hdr) {
     if (int32_t rc = ensure_buffers(ctx, false)) return rc;
     FlareSums hs{0.0, 0.0, 0.0};
     if (sums) hs = FlareSums{sums[0], sums[1], sums[2]};
     const long long n = (long long)ctx->rows * ctx->cfg.width;
     const bhr_frame_slot &f = bhr_slot(ctx);
-    hipLaunchKernelGGL(flare_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, f.d_final, ctx->cfg.width,
-                       ctx->cfg.height, ctx->cfg.row0, ctx->rows, f.d_flare_sums, hs, sums ? 1 : 0);
+    if (hdr && !f.d_hdr) return bhr_fail(BHR_ERR_STATE, "flare: the frame slot has no HDR plane");
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (hdr) hipLaunchKernelGGL(flare_apply_kernel<true>, grid, block, 0, ctx->stream, f.d_hdr, ctx->cfg.width, ctx->cfg.height, ctx->cfg.row0, ctx->rows,
+                                f.d_flare_sums, hs, sums ? 1 : 0);
+    else hipLaunchKernelGGL(flare_apply_kernel<false>, grid, block, 0, ctx->stream, f.d_final, ctx->cfg.width, ctx->cfg.height, ctx->cfg.row0, ctx->rows,
+                            f.d_flare_sums, hs, sums ? 1 : 0);
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }

@@ -484,6 +484,9 @@ int32_t bhr_group_render_subset(bhr_ctx **ctxs, int32_t n, const bhr_camera *cam
     for (int k = 0; k < n; ++k) {
         if (!ctxs[k]) return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: null ctx %d", k);
         if (ctxs[k]->ss > 1 || ctxs[k]->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d is supersampled (row blocks render one sample per pixel)", k);
+        if (ctxs[k]->grade_on)
+            return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d has a grade set (bhr_set_grade) and a group render stores its rows from inside the V pass; "
+                            "switch the grade off", k);
         if (ctxs[k]->dither && (flags & BHR_GATHER_U8))
             return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d dithers (bhr_set_dither) and BHR_GATHER_U8 stores the undithered rows from inside the "
                             "V pass; gather the f32 frame, or switch dither off", k);
@@ -541,6 +544,7 @@ int32_t bhr_group_sync(bhr_ctx **ctxs, int32_t n) {
 int32_t bhr_tile_export(bhr_ctx *ctx, uint32_t gather_flags, bhr_tile_handles *out) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_export: bad argument");
     if (ctx->ss > 1 || ctx->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_export: the context is supersampled (row blocks render one sample per pixel)");
+    if (ctx->grade_on) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_export: the context has a grade set (bhr_set_grade) and a tile stores its rows from inside the V pass; switch the grade off");
     BHR_TRY(bhr_enter(ctx));
     BHR_TRY(bhr_activate_slot(ctx, 0));                                      // tile renders use slot 0, whatever bhr_render left active
     BHR_TRY(bhr_frame_begin(ctx, 0));                                        // the context's arithmetic picks the post-pass, allocates its planes
@@ -721,6 +725,8 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
 int32_t bhr_tile_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: bad argument");
     if (ctx->ss > 1 || ctx->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the context is supersampled (row blocks render one sample per pixel)");
+    if (ctx->grade_on)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the context has a grade set (bhr_set_grade) and a tile stores its rows from inside the V pass; switch the grade off");
     if (ctx->dither)
         return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the context dithers (bhr_set_dither) and a tile stores its u8 rows from inside the V pass; switch dither off");
     TilePipe *p = (TilePipe *)ctx->pipe;

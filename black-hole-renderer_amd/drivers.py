@@ -22,7 +22,7 @@ import numpy as np
 from .camera import orbit_position
 from .lifecycle import make_factories
 from .output import Y4MStream, FrameSink, VIDEO_LEVEL, DEVICE, DITHERS, png_write, quantize, quantize16
-from .renderer import HipRenderer, R_DISK_INNER_DEFAULT, R_DISK_OUTER_DEFAULT
+from .renderer import HipRenderer, R_DISK_INNER_DEFAULT, R_DISK_OUTER_DEFAULT, check_grade
 from .skybox import load_or_generate_skybox
 from .textures import compute_disk_texture_resolution, load_disk_texture
 
@@ -56,6 +56,48 @@ def save_image(image: np.ndarray, path: str, bit_depth: int = 8, dither: str = "
     else:
         from PIL import Image
         Image.fromarray(quantize(image, dither=dither)).save(path)
+    print(f"Saved: {path}")
+
+
+HDR_FORMATS = (".pfm", ".hdr")
+
+
+def check_hdr_path(path: str) -> None:
+    if not str(path).lower().endswith(HDR_FORMATS):
+        raise ValueError(f"the HDR master is written as .pfm or .hdr, got {path!r}")
+
+
+def rgbe_encode(image: np.ndarray) -> np.ndarray:
+    """(H, W, 3) float -> (H, W, 4) uint8 Radiance RGBE: the shared exponent is frexp's of the largest channel, the mantissas
+    are truncated (m * 256 / 2^e), a pixel whose largest channel is below 1e-32 is four zeros."""
+    x = np.clip(np.nan_to_num(np.asarray(image, dtype=np.float32), nan=0.0, posinf=np.float32(65504.0)), 0.0, None)
+    big = x.max(axis=-1)
+    _, e = np.frexp(big)
+    live = big >= 1e-32
+    scale = np.where(live, np.ldexp(np.float32(1.0), 8 - np.where(live, e, 0)), np.float32(0.0)).astype(np.float32)
+    out = np.empty(x.shape[:2] + (4,), dtype=np.uint8)
+    out[..., :3] = np.minimum(np.floor(x * scale[..., None]), 255).astype(np.uint8)
+    out[..., 3] = np.where(live, e + 128, 0).astype(np.uint8)
+    return out
+
+
+def save_hdr(image: np.ndarray, path: str) -> None:
+    """The scene-linear float frame (HipRenderer.read_hdr) as a file, encoded on the host.  ``.pfm``: the f32 values as they
+    are, little-endian, rows bottom-up (header "PF", "W H", "-1.0").  ``.hdr``: Radiance RGBE, flat (no run-length coding),
+    rows top-down, header "#?RADIANCE" / "FORMAT=32-bit_rle_rgbe" (rgbe_encode)."""
+    check_hdr_path(path)
+    image = np.asarray(image)
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError(f"save_hdr takes an (H, W, 3) image, got {image.shape}")
+    h, w = image.shape[:2]
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "wb") as f:
+        if path.lower().endswith(".pfm"):
+            f.write(f"PF\n{w} {h}\n-1.0\n".encode("ascii"))
+            f.write(np.ascontiguousarray(image[::-1], dtype="<f4").tobytes())
+        else:
+            f.write(f"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y {h} +X {w}\n".encode("ascii"))
+            f.write(rgbe_encode(image).tobytes())
     print(f"Saved: {path}")
 
 
@@ -142,14 +184,24 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  force_regenerate_disk_texture: bool = False, ignore_taichi_cache: bool = False,
                  gpus: int = 1, disk_model: str = "texture", math: Optional[str] = None,
                  supersample: int = 1, supersample_threshold: Optional[float] = None, bit_depth: int = 8,
-                 dither: str = "none") -> np.ndarray:
+                 dither: str = "none", grade: Optional[dict] = None, hdr_path: Optional[str] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
     pixel (one device only); ``supersample_threshold``: adaptive -- only for the pixels whose k = 1 neighbours differ by more
     than it (HipRenderer.set_supersample; None: every pixel).  ``bit_depth`` / ``dither`` are checked here and applied by
-    save_image to the frame this returns (the f32 frame does not depend on them)."""
+    save_image to the frame this returns (the f32 frame does not depend on them).  ``grade``: None, or a dict of
+    HipRenderer.set_grade's arguments (tonemap, exposure, white, transfer) -- the frame this returns is the graded one (one
+    device only).  ``hdr_path``: also writes the frame's scene-linear plane there (save_hdr; needs a grade, implies keep_hdr)."""
     check_depth_and_dither(bit_depth, dither)
+    grade = check_grade(grade)
+    if hdr_path is not None:
+        check_hdr_path(hdr_path)
+        if grade is None:
+            raise ValueError("hdr_path needs a grade: the HDR plane is written by the grading stage (tonemap 'clip' keeps the picture as it is)")
+        grade["keep_hdr"] = True
+    if gpus > 1 and grade is not None:
+        raise ValueError("a grade renders on one GPU: row-block tiles store their rows from inside the V pass")
     if gpus > 1 and supersample != 1:
         raise ValueError("supersample > 1 renders on one GPU: row-block tiles march one ray per pixel")
     if gpus > 1:
@@ -171,7 +223,11 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         advance_lifecycle_frame(renderer, factories, t=0.0, dt=0.0, recompute_stats=True)
     t0 = time.time()
     print(f"HIP: {width}x{height}, cam_pos={list(cam_pos)}, fov={fov}°, step_size={step_size}")
+    if grade is not None:
+        renderer.set_grade(**grade)
     img = renderer.render(cam_pos, fov, frame=0)
+    if hdr_path is not None:
+        save_hdr(renderer.read_hdr(), hdr_path)
     c = renderer.counters()
     dt = time.time() - t0
     print(f"Done in {dt:.3f}s  (march {c['march_ms']:.2f} ms, bloom {c['bloom_ms']:.2f} ms, "
@@ -263,7 +319,7 @@ def check_shutter(shutter, shutter_samples) -> None:
 
 
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
-                    bit_depth=8, dither="none", shutter=0.0, shutter_samples=8) -> dict:
+                    bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -277,6 +333,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(dither=dither)
     if shutter > 0:
         params.update(shutter=shutter, shutter_samples=shutter_samples)
+    if grade is not None:
+        params.update(tonemap=grade["tonemap"], exposure=grade["exposure"], white=grade["white"], transfer=grade["transfer"])
     return params
 
 
@@ -312,7 +370,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  video_stream: str = "auto", stats: Optional[dict] = None, supersample: Optional[int] = None,
                  supersample_threshold: Optional[float] = None, video_codec: str = "auto", video_quality: int = 90,
                  bit_depth: int = 8, dither: str = "none", shutter: float = 0.0, shutter_samples: int = 8,
-                 **_deprecated_kwargs) -> None:
+                 grade: Optional[dict] = None, **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -349,8 +407,16 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     texture within the exposure.  The texture itself is the frame's, composed once at t = f * dt: the populations and the
     noise are NOT sampled within the exposure.  With ``shutter == 0`` the loop calls render_async exactly as it always has,
     whatever ``shutter_samples`` is; the progress record carries the two values only when ``shutter > 0``, and a resume with
-    other values starts over."""
+    other values starts over.
+
+    ``grade``: None (the frames are as the renderer is set), or a dict of HipRenderer.set_grade's arguments (tonemap, exposure,
+    white, transfer): every consumer of the loop -- PNG (8 and 16 bit) or JPEG frames, the dither, the yuv420p stream -- gets the
+    graded frame; the renderer's own grade is restored on return.  The progress record carries the four values only when a
+    grade is given, and a resume with other values starts over.  The frames keep no HDR plane."""
     check_shutter(shutter, shutter_samples)
+    grade = check_grade(grade)
+    if grade is not None:
+        grade["keep_hdr"] = False
     if video_codec not in VIDEO_CODECS:
         raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
     check_depth_and_dither(bit_depth, dither, video_codec)
@@ -367,7 +433,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     submitted: List[int] = []
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
     params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither,
-                             shutter, shutter_samples)
+                             shutter, shutter_samples, grade)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -428,6 +494,9 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     dither_before = renderer.dither
     if dither != dither_before:
         renderer.set_dither(dither)
+    grade_before = renderer.grade
+    if grade is not None:
+        renderer.set_grade(**grade)
     if video_stream not in ("auto", "y4m", "off"):
         raise ValueError(f"video_stream must be 'auto', 'y4m' or 'off', got {video_stream!r}")
     stream = encoder = None
@@ -493,6 +562,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         renderer.set_outputs(outputs_before)
     if dither != dither_before:
         renderer.set_dither(dither_before)
+    if grade is not None:
+        renderer.set_grade(**(grade_before or {}))
     if stats is not None:
         stats.update(setup_s=t_loop0 - total_t0, loop_s=time.time() - t_loop0, frames=rendered)
     streamed = False

@@ -36,6 +36,34 @@ class _FieldView:
 SUPERSAMPLE_FACTORS = (1, 2, 4, 8)
 
 
+TONEMAPS = ("clip", "reinhard", "aces")
+TRANSFERS = ("linear", "srgb")
+
+
+def check_grade(grade) -> Optional[dict]:
+    """A grade as set_grade takes it -- None, or a dict with any of tonemap, exposure, white, transfer, keep_hdr -- checked and
+    completed with the defaults: None or dict(tonemap, exposure, white, transfer, keep_hdr).  Raises ValueError."""
+    if grade is None or grade.get("tonemap") is None:
+        if grade and any(k != "tonemap" for k in grade):
+            raise ValueError("a grade needs a tonemap: 'clip', 'reinhard' or 'aces'")
+        return None
+    unknown = set(grade) - {"tonemap", "exposure", "white", "transfer", "keep_hdr"}
+    if unknown:
+        raise ValueError(f"grade: unknown field(s) {sorted(unknown)}")
+    tonemap, transfer = grade["tonemap"], grade.get("transfer", "linear")
+    if tonemap not in TONEMAPS:
+        raise ValueError(f"tonemap must be one of {TONEMAPS} or None, got {tonemap!r}")
+    if transfer not in TRANSFERS:
+        raise ValueError(f"transfer must be one of {TRANSFERS}, got {transfer!r}")
+    exposure, white = float(grade.get("exposure", 0.0)), float(grade.get("white", 2.5))
+    if not (np.isfinite(exposure) and -16.0 <= exposure <= 16.0):
+        raise ValueError(f"exposure must be a finite number of stops in [-16, 16], got {exposure!r}")
+    if not (np.isfinite(white) and 0.0 < white <= 65504.0):
+        raise ValueError(f"white must be finite and in (0, 65504], got {white!r}")
+    return dict(tonemap=tonemap, exposure=float(np.float32(exposure)), white=float(np.float32(white)), transfer=transfer,
+                keep_hdr=bool(grade.get("keep_hdr", False)))
+
+
 def _check_supersample(k) -> None:
     if isinstance(k, bool) or k not in SUPERSAMPLE_FACTORS:
         raise ValueError(f"supersample must be one of {SUPERSAMPLE_FACTORS}, got {k!r}")
@@ -565,6 +593,39 @@ class HipRenderer:
         """"none" or "blue": the mode last chosen with set_dither."""
         return getattr(self, "_dither", "none")
 
+    def set_grade(self, tonemap=None, exposure: float = 0.0, white: float = 2.5, transfer: str = "linear",
+                  keep_hdr: bool = False) -> None:
+        """The grading stage of the frames rendered from now on (bhr_set_grade; include/bhr.h states the formulas).
+        ``tonemap``: None (default: off, the frame is clip(bg + disk + blur, 0, 1) as ever), "clip", "reinhard" or "aces";
+        ``exposure`` in stops (-16 .. 16); ``white``: the value "reinhard" maps to 1 (2.5: bg <= 0.5, disk <= 1, blur <= 1);
+        ``transfer``: "linear" or "srgb"; ``keep_hdr``: the frame keeps its scene-linear plane for read_hdr().  Every consumer
+        of the frame -- read_layer, read_final_u8 / _u16, the dither, the PNG and JPEG encoders, the sinks, the y4m stream --
+        follows."""
+        if tonemap is None:
+            _lib.check(self._lib.bhr_set_grade(self._ctx, None))
+            self._grade = None
+            return
+        grade = check_grade(dict(tonemap=tonemap, exposure=exposure, white=white, transfer=transfer, keep_hdr=keep_hdr))
+        g = _lib.Grade(TONEMAPS.index(grade["tonemap"]), TRANSFERS.index(grade["transfer"]), grade["exposure"], grade["white"],
+                       int(grade["keep_hdr"]))
+        _lib.check(self._lib.bhr_set_grade(self._ctx, C.byref(g)))
+        self._grade = grade
+
+    @property
+    def grade(self) -> Optional[dict]:
+        """The grade last chosen with set_grade: None (off) or dict(tonemap, exposure, white, transfer, keep_hdr)."""
+        g = getattr(self, "_grade", None)
+        return None if g is None else dict(g)
+
+    def grade_frame(self) -> None:
+        """FINAL <- grade((BG + DISK) + BLUR) on the layers in the context, without flare (bhr_grade_frame)."""
+        _lib.check(self._lib.bhr_grade_frame(self._ctx))
+
+    def read_hdr(self) -> np.ndarray:
+        """The scene-linear plane of the last frame rendered or graded under set_grade(..., keep_hdr=True): (rows, width, 3)
+        float32 in [0, 65504], before exposure, with the lens flare if the frame had one."""
+        return self.read_layer(_lib.LAYER_HDR)
+
     def render(self, cam_pos: List[float], fov: float, frame: int = 0,
                skip_differentials: bool = False, skip_bloom: bool = False) -> np.ndarray:
         """One frame -> (rows, width, 3) float32 in [0, 1]  (render.py:3865-3923)."""
@@ -606,6 +667,13 @@ class HipRenderer:
         = 5): how many were bracketed with HIP events and the sum of their times in ms.  Synchronises."""
         geom = (C.c_int32 * 10)()
         _lib.check(self._lib.bhr_debug_read(self._ctx, 5, None, 0, geom))
+        return {"launches": int(geom[0]), "ms": int(geom[1]) * 1e-6}
+
+    def grade_timing(self) -> dict:
+        """The launches of the last graded frame's grade stage under option "grade_timing" 1 (bhr_debug_read, which = 6): how
+        many were bracketed with HIP events and the sum of their times in ms.  Synchronises."""
+        geom = (C.c_int32 * 10)()
+        _lib.check(self._lib.bhr_debug_read(self._ctx, 6, None, 0, geom))
         return {"launches": int(geom[0]), "ms": int(geom[1]) * 1e-6}
 
     def hybrid_launch_order(self) -> np.ndarray:

@@ -132,7 +132,8 @@ typedef enum {
     BHR_LAYER_FINAL = 0,  /* clip(bg + disk + blur, 0, 1)           render.py:3918 */
     BHR_LAYER_BG = 1,     /* image_field  = skybox * (1 - alpha)    render.py:3017 */
     BHR_LAYER_DISK = 2,   /* disk_layer_field = clamp(accum, 0, 1)  render.py:3018 */
-    BHR_LAYER_BLUR = 3    /* blur_field after the V pass            render.py:3108 */
+    BHR_LAYER_BLUR = 3,   /* blur_field after the V pass            render.py:3108 */
+    BHR_LAYER_HDR = 4     /* the scene-linear plane h of a graded frame (bhr_set_grade, keep_hdr); read only */
 } bhr_layer;
 
 typedef struct {
@@ -341,6 +342,8 @@ BHR_API int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]);
  *   "png16_menu"      BHR_PNG16_MENU      1 (default) the 16-bit device PNG encoder codes from its own menu, 0 from the 8-bit one (A/B runs)
  *   "shutter_timing"  BHR_SHUTTER_TIMING  1 a shutter frame brackets each of its accumulation launches with a pair of HIP events
  *                                         (bhr_debug_read, which = 5; ~5 us per event in the frame's stream); default 0
+ *   "grade_timing"    BHR_GRADE_TIMING    1 a graded frame (bhr_set_grade) brackets each launch of its grade stage with a pair of HIP
+ *                                         events (bhr_debug_read, which = 6); default 0
  * (bhr_create only: BHR_FRAME_SLOTS.) */
 BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
 /* Diagnostics (tests): the split-f16 post-pass's packed intermediates of the last frame as raw bytes -- which = 0 the H pass's
@@ -348,7 +351,8 @@ BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
  * GP, g0, t_first, n_ty, pbr, GR}; which = 2 the launch order of the last math-hybrid march as int32 tile indices, strict tiles
  * first (geom[0] = tiles in it; bhr_hybrid_info tells how many are strict).  out == NULL or bytes == 0: geometry only.
  * which = 5 (option "shutter_timing"): geom[0] = accumulation launches of the last shutter frame, geom[1] = their summed
- * HIP-event time in nanoseconds.
+ * HIP-event time in nanoseconds.  which = 6 (option "grade_timing"): the same for the launches of the last graded frame's
+ * grade stage (csrc/grade.hip: one, or two for a flared frame).
  * Synchronises. */
 BHR_API int32_t bhr_debug_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes, int32_t *geom);
 /* TaichiRenderer._apply_lens_flare(final, disk) (render.py:3925-4028) on the device, standalone:
@@ -389,6 +393,43 @@ BHR_API int32_t bhr_set_dither(bhr_ctx *ctx, int32_t mode);
 /* The rank matrix M, row-major (out[64 y + x] = M[y][x]): every value of 0 .. 4095 once; void-and-cluster on a torus with a
  * Gaussian energy, generated by tools/make_blue_noise.py and compiled in.  Host only, needs no GPU. */
 BHR_API int32_t bhr_dither_matrix(uint16_t out[4096]);
+/* Grading: exposure, a highlight roll-off and a display transfer function in place of the combine's hard clip, between the
+ * combine and the quantisers.  Per value, all in f32, every operation rounded once:
+ *   x = (bg + disk) + blur                  the combine's own order; blur = 0 for a BHR_SKIP_BLOOM frame
+ *   h = fminf(fmaxf(x, 0), 65504)           the HDR value: NaN -> 0 as in the quantisers, +inf -> 65504
+ *   v = h * gain                            gain = (float)exp2((double)exposure_stops)
+ *   BHR_GRADE_CLIP      y = fminf(v, 1)
+ *   BHR_GRADE_REINHARD  y = fminf((v * (1 + v * iw2)) / (1 + v), 1)          iw2 = (float)(1 / ((double)white * white)): v = white -> 1
+ *   BHR_GRADE_ACES      y = fminf(fmaxf((v * (2.51f * v + 0.03f)) / (v * (2.43f * v + 0.59f) + 0.14f), 0), 1)
+ *   BHR_TRANSFER_LINEAR FINAL = y
+ *   BHR_TRANSFER_SRGB   FINAL = y <= 0.0031308f ? 12.92f * y : 1.055f * powf(y, 1.0f / 2.4f) - 0.055f
+ * bhr_set_grade(ctx, NULL) switches the stage off (the default): an ungraded frame launches the kernels it always has.
+ * {BHR_GRADE_CLIP, 0 stops, BHR_TRANSFER_LINEAR} is not a synonym for off: it runs the stage, and gives the ungraded frame bit
+ * for bit.  While a grade is set a frame of bhr_render / bhr_render_shutter takes the route of a flared or dithered frame: its
+ * V pass stores BLUR only, one kernel (csrc/grade.hip) writes FINAL -- and the frame's u8 rows where bhr_set_outputs asked for
+ * them and dither is off -- and FINAL is the authority for everything made on demand: bhr_read_final_u8 / _u16, the dither,
+ * the PNG and JPEG paths, the sinks and the y4m stream.  With BHR_LENS_FLARE the flare sits in front of the sensor response:
+ * x is fmaxf(((bg + disk) + blur) + flare, 0), the flare's term added without the upper clip.  keep_hdr != 0: the frame keeps
+ * its plane h (scene-linear, before exposure, with the flare if it had one), one more (rows, W, 3) f32 buffer of the frame slot
+ * from the first use on, read with bhr_read_layer(BHR_LAYER_HDR) -- BHR_ERR_STATE for a frame that did not keep it;
+ * bhr_write_layer refuses the layer.
+ * bhr_set_grade drains the frames in flight and applies to the frames rendered afterwards; frames in memory keep the outputs
+ * they were rendered with.  BHR_ERR_INVALID, with the context as it was: op not in {0, 1, 2}, transfer not in {0, 1},
+ * exposure_stops non-finite or outside [-16, 16], white non-finite or outside (0, 65504].  The stand-alone bhr_bloom and
+ * bhr_lens_flare stay the reference's functions and ignore the grade.  bhr_group_render*, bhr_tile_export and bhr_tile_render
+ * store rows from inside their V passes into peer memory: while a grade is set they return BHR_ERR_INVALID.  bhr_render on a
+ * row-block context works (without flare, as ever). */
+#define BHR_GRADE_CLIP 0
+#define BHR_GRADE_REINHARD 1
+#define BHR_GRADE_ACES 2
+#define BHR_TRANSFER_LINEAR 0
+#define BHR_TRANSFER_SRGB 1
+typedef struct { int32_t op, transfer; float exposure_stops, white; int32_t keep_hdr; } bhr_grade;
+BHR_API int32_t bhr_set_grade(bhr_ctx *ctx, const bhr_grade *g);   /* NULL: off (the default) */
+/* Stand-alone, like bhr_bloom: FINAL <- grade((BG + DISK) + BLUR) of the layers in the active frame slot, without flare; the
+ * plane h is kept if keep_hdr is set.  Invalidates the u8 and u16 rows.  Asynchronous.  BHR_ERR_STATE while no grade is set.
+ * Works on row-block contexts too: the stage is per value. */
+BHR_API int32_t bhr_grade_frame(bhr_ctx *ctx);
 BHR_API int32_t bhr_get_counters(bhr_ctx *ctx, bhr_counters *out);
 /* Last BHR_MATH_HYBRID march of this context: out_tiles = {tiles marched strict, tiles of the row block},
  * out_band = {lo, hi}: the strict band [b_c - lo, b_c + hi] of impact parameters, in r_s. */
