@@ -97,6 +97,15 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--hdr_output", type=str, default=None, metavar="PATH",
                    help="still images: also write the unclipped scene-linear frame, before exposure, as PATH (.pfm: exact f32; "
                         ".hdr: Radiance RGBE)")
+    p.add_argument("--ray_map", action="store_true",
+                   help="--video with a camera that stands still: march the view once, before the loop, and shade every frame "
+                        "from that ray map under the frame's texture instead of marching it again.  The frames are the strict "
+                        "arithmetic's whatever --math says.  Not with --orbit, --shutter, --supersample > 1, --disk_model v2 / "
+                        "v2_volume or --gpus > 1")
+    p.add_argument("--passes", type=str, default=None, metavar="PATH.npz",
+                   help="still images: also write the view's geometry passes (per pixel: steps, ray fate, escape direction, disk "
+                        "crossings and hit points, from a ray map of the view) and the frame's bg / disk / blur layers as a "
+                        "compressed .npz; the image itself is unchanged.  One GPU, --supersample 1, --disk_model texture")
     p.add_argument("--ignore_taichi_cache", action="store_true", help="accepted for compatibility; no effect")
     p.add_argument("--video", action="store_true", help="render frames and assemble a video")
     p.add_argument("--interactive", action="store_true", help="not available in this build (needs ti.GUI)")
@@ -112,6 +121,26 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    if args.ray_map:
+        if not args.video:
+            p.error("--ray_map needs --video: a still image is marched once anyway (--passes writes its ray map's passes)")
+        if args.orbit:
+            p.error("--ray_map does not combine with --orbit: a ray map is one view")
+        if args.shutter > 0:
+            p.error("--ray_map does not combine with --shutter: shutter frames are marched")
+        if args.supersample != 1:
+            p.error("--ray_map does not combine with --supersample other than 1: a ray map holds one ray per pixel")
+        if args.disk_model != "texture":
+            p.error("--ray_map does not combine with --disk_model other than texture: a ray map shades the disk texture")
+        if args.gpus != 1:
+            p.error("--ray_map does not combine with --gpus other than 1: a ray map lives on one GPU")
+    if args.passes is not None:
+        if args.video:
+            p.error("--passes writes the passes of a still image: it does not combine with --video")
+        if not args.passes.lower().endswith(".npz"):
+            p.error(f"--passes writes a .npz file, got {args.passes!r}")
+        if args.gpus != 1 or args.supersample != 1 or args.disk_model != "texture":
+            p.error("--passes needs one GPU, --supersample 1 and --disk_model texture: the passes come from a ray map")
     # --exposure, --white, --transfer and --hdr_output without --tonemap mean --tonemap clip
     if args.tonemap is None and any(v is not None for v in (args.exposure, args.white, args.transfer, args.hdr_output)):
         args.tonemap = "clip"
@@ -225,7 +254,7 @@ def main(argv=None) -> int:
                              png_level=(drivers.DEVICE if args.png_encoder == "device" else drivers.VIDEO_LEVEL),
                              video_codec=args.video_codec, video_quality=args.video_quality, bit_depth=args.bit_depth,
                              dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples,
-                             grade=grade_from_args(args))
+                             grade=grade_from_args(args), ray_map=args.ray_map)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -249,6 +278,6 @@ def main(argv=None) -> int:
         anti_alias=args.anti_alias, aa_strength=args.aa_strength, disk_rotation_speed=args.disk_rotation_speed,
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
-        grade=grade_from_args(args), hdr_path=args.hdr_output)
+        grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

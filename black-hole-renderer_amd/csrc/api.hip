@@ -446,6 +446,7 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) return bail(bhr_fail(BHR_ERR_HIP, "hipStreamCreate failed"));
     ctx->scene_stream = ctx->stream;
     read_options(&ctx->opt);
+    { const char *e = getenv("BHR_RAYMAP_SLOTS"); ctx->raymap_slots = e && e[0] ? atoi(e) : 4; }   // outside 1 .. 8: bhr_raymap_build refuses
     ctx->n_slots = ctx->opt.frame_slots;                 // 2 (default): frames alternate between two slots / streams
     ctx->split_ok = bhr_split_nt(ctx->bloom_R) <= 12;    // the split-f16 bloom's table: radius <= 176 (widths to 8849)
     ctx->out_want = BHR_OUT_F32;
@@ -497,6 +498,7 @@ void bhr_destroy(bhr_ctx *ctx) {
     bhr_jpeg_dev_free(ctx);
     bhr_shutter_free(ctx);
     bhr_grade_free(ctx);
+    bhr_raymap_release(ctx);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);
     bhr_pipe_free(ctx);
@@ -810,6 +812,22 @@ int32_t shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, int n, uint32_t fl
     return post_on_slot(ctx, flags, k, ring);
 }
 
+// A frame from the context's ray map on slot k (bhr_raymap_render): the shade kernel over the stored records, then the strict
+// fix kernel over the map's overflow list (its count is the device's: a grid for the list's capacity, as the hybrid march
+// launches it), inside one march bracket, then the post-pass as behind any march.  The ring cell counts the re-march only.
+int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring) {
+    bhr_frame_slot &f = ctx->slots[k];
+    const bhr_raymap &rm = *ctx->raymap;
+    BHR_TRY(bhr_frame_begin(ctx, flags));
+    ctx->ada_frame = 0;
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ false, /* ss */ 1};
+    BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0));
+    const bhr_march_part part = {nullptr, 0, /* first */ 0, /* last */ 1, BHR_MATH_STRICT, /* repair */ 2, rm.a.over_count, rm.a.over_list, rm.over_cap};
+    BHR_TRY(bhr_launch_march(ctx, call, &part));       // records the ring slot's march-end event
+    f.march_done = ctx->ring_ev[ring * 3 + 1];
+    return post_on_slot(ctx, flags, k, ring);
+}
+
 // A frame on the context's next frame slot: orders the slot's stream behind the scene stream, points the launchers at the
 // slot, runs `body(slot, ring slot)` and keeps the books (slot rotation, timing ring).  exclusive: slot 0, behind every
 // frame in flight (launches that use per-context scratch).
@@ -970,6 +988,17 @@ int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint
     return frame_on_next_slot(ctx, flags, false, [&](int k, int ring) { return shutter_on_slot(ctx, cams, n, flags, k, ring); });
 }
 
+// A frame from the ray map (include/bhr.h): the build camera with the caller's t_offset, the strict arithmetic, the build's
+// choice of differentials.  Like bhr_render_shutter it neither triggers nor counts towards the calibration of slot 1's stream.
+int32_t bhr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
+    BHR_TRY(bhr_raymap_check_render(ctx, t_offset, flags));
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    bhr_camera cam = ctx->raymap->cam;
+    cam.t_offset = t_offset;
+    const uint32_t fl = flags | BHR_FORCE_STRICT | (ctx->raymap->diff ? 0u : BHR_SKIP_DIFFERENTIALS);
+    return frame_on_next_slot(ctx, fl, false, [&](int k, int ring) { return raymap_on_slot(ctx, &cam, fl, k, ring); });
+}
+
 int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_read_layer: bad argument");
     BHR_TRY(use_device(ctx));
@@ -1110,6 +1139,10 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     else if (n == "group_schedule") o.group_schedule = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "shutter_timing") o.shutter_timing = v != 0;
     else if (n == "grade_timing") o.grade_timing = v != 0;
+    else if (n == "raymap_slots") {   // read by the next bhr_raymap_build; the map in memory keeps its own
+        if (!(value >= 1.0 && value <= 8.0)) return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: raymap_slots %g (1 .. 8)", value);
+        ctx->raymap_slots = v;
+    }
     else if (n == "png16_menu") {   // the tables are rebuilt at the next encode; no encode may be running on the old ones
         BHR_TRY(bhr_enter(ctx));
         BHR_HIP(hipStreamSynchronize(ctx->scene_stream));

@@ -1,0 +1,209 @@
+// api_raymap.hip -- the ray map's entry points (include/bhr.h): build, read, info, free, and the refusals of
+// bhr_raymap_render (the frame itself is launched from api.hip, next to bhr_render: it takes a frame slot like any other).
+// The kernels are raymap.hip's, their launchers march_launch.hip's.
+#include <math.h>
+#include <string.h>
+
+#include <vector>
+
+#include "bhr_internal.h"
+
+namespace {
+
+void free_planes(bhr_raymap *rm) {
+    BhrRayMapArgs &a = rm->a;
+    void *bufs[] = {a.steps, a.status, a.dir, a.crossings, a.hits, a.over_count, a.over_list, a.stats};
+    for (void *b : bufs)
+        if (b) (void)hipFree(b);
+    memset(&a, 0, sizeof(a));
+    rm->built = 0;
+    rm->alloc_slots = rm->alloc_comps = 0;
+    rm->over_cap = 0;
+    rm->device_bytes = 0;
+}
+
+template <typename T>
+int32_t plane_alloc(bhr_raymap *rm, T **p, size_t count) {
+    *p = nullptr;
+    const hipError_t e = hipMalloc((void **)p, count * sizeof(T));
+    if (e != hipSuccess) {
+        *p = nullptr;
+        (void)hipGetLastError();
+        return bhr_fail(BHR_ERR_NOMEM, "bhr_raymap_build: hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
+    }
+    rm->device_bytes += (int64_t)(count * sizeof(T));
+    return BHR_OK;
+}
+
+// every stream that may still read the map
+int32_t drain(bhr_ctx *ctx) {
+    for (auto &f : ctx->slots) {
+        if (f.stream) BHR_HIP(hipStreamSynchronize(f.stream));
+        if (f.aux_stream) BHR_HIP(hipStreamSynchronize(f.aux_stream));
+    }
+    BHR_HIP(hipStreamSynchronize(ctx->scene_stream));
+    return BHR_OK;
+}
+
+int32_t fetch(bhr_ctx *ctx, void *dst, const void *d_src, size_t bytes) {
+    BHR_HIP(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BHR_HIP(hipStreamSynchronize(ctx->stream));
+    return BHR_OK;
+}
+
+// what a context has to be for a map: whole frame, one ray per pixel, the texture source
+int32_t check_context(const bhr_ctx *ctx, const char *who, int32_t code) {
+    if (ctx->ss > 1 || ctx->ada_k > 1)
+        return bhr_fail(code, "%s: supersampling is on (factor %d); a ray map holds one ray per pixel", who, ctx->ss > 1 ? ctx->ss : ctx->ada_k);
+    if (ctx->disk_source != BHR_DISK_TEXTURE)
+        return bhr_fail(code, "%s: the disk source is Disk V2 (%d); a ray map shades the disk texture", who, ctx->disk_source);
+    return BHR_OK;
+}
+
+}  // namespace
+
+void bhr_raymap_release(bhr_ctx *ctx) {
+    if (!ctx->raymap) return;
+    free_planes(ctx->raymap);
+    delete ctx->raymap;
+    ctx->raymap = nullptr;
+}
+
+int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: null ctx");
+    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", flags);
+    if (!isfinite(t_offset)) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: t_offset is not finite");
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
+    if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no ray map has been built (bhr_raymap_build)");
+    return check_context(ctx, "bhr_raymap_render", BHR_ERR_STATE);
+}
+
+extern "C" {
+
+int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
+    if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: null argument");
+    if (flags & ~(uint32_t)BHR_SKIP_DIFFERENTIALS) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: flags %u (BHR_SKIP_DIFFERENTIALS only)", flags);
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
+    BHR_TRY(check_context(ctx, "bhr_raymap_build", BHR_ERR_INVALID));
+    const int32_t K = ctx->raymap_slots;
+    if (K < 1 || K > 8) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: raymap_slots %d (1 .. 8)", K);
+    const bool diff = bhr_want_diff(ctx, flags);
+    const int32_t comps = diff ? 9 : 5;
+    const size_t plane = (size_t)ctx->rows * ctx->cfg.width;
+
+    BHR_TRY(bhr_enter(ctx));           // behind the frames in flight: they may be reading the map this build rewrites
+    if (!ctx->raymap) {
+        ctx->raymap = new bhr_raymap();
+        memset(ctx->raymap, 0, sizeof(bhr_raymap));
+    }
+    bhr_raymap *rm = ctx->raymap;
+    rm->built = 0;
+    if (rm->a.hits && (rm->alloc_slots != K || rm->alloc_comps != comps)) {
+        BHR_TRY(drain(ctx));
+        free_planes(rm);
+    }
+    if (!rm->a.hits) {
+        BhrRayMapArgs &a = rm->a;
+        // the fix kernel's grid is sized in blocks of 256 entries of the list's capacity
+        const size_t over_cap = (plane + 255) / 256 * 256;
+        int32_t rc = BHR_OK;
+        if ((rc = plane_alloc(rm, &a.steps, plane)) || (rc = plane_alloc(rm, &a.status, plane)) || (rc = plane_alloc(rm, &a.dir, 3 * plane)) ||
+            (rc = plane_alloc(rm, &a.crossings, plane)) || (rc = plane_alloc(rm, &a.hits, (size_t)K * comps * plane)) ||
+            (rc = plane_alloc(rm, &a.over_count, 16)) || (rc = plane_alloc(rm, &a.over_list, over_cap)) ||
+            (rc = plane_alloc(rm, &a.stats, 8 + BHR_STEP_CELL))) {
+            free_planes(rm);           // a later build starts clean; the context is as it was
+            return rc;
+        }
+        a.slots = K;
+        a.comps = comps;
+        a.plane = (int64_t)plane;
+        rm->alloc_slots = K;
+        rm->alloc_comps = comps;
+        rm->over_cap = (int32_t)over_cap;
+    }
+    const BhrRayMapArgs &a = rm->a;
+    // records beyond a pixel's crossings stay zero
+    BHR_HIP(hipMemsetAsync(a.hits, 0, (size_t)K * comps * plane * sizeof(float), ctx->stream));
+    BHR_HIP(hipMemsetAsync(a.over_count, 0, 16 * sizeof(unsigned int), ctx->stream));
+    BHR_HIP(hipMemsetAsync(a.stats, 0, (8 + BHR_STEP_CELL) * sizeof(unsigned long long), ctx->stream));
+    BHR_TRY(bhr_launch_raymap_build(ctx, cam, flags, a));
+    std::vector<unsigned long long> stats(8 + BHR_STEP_CELL);
+    unsigned int over = 0;
+    BHR_TRY(fetch(ctx, stats.data(), a.stats, stats.size() * sizeof(unsigned long long)));
+    BHR_TRY(fetch(ctx, &over, a.over_count, sizeof(over)));
+    unsigned long long steps = 0;
+    for (int k = 0; k < BHR_STEP_LANES; ++k) steps += stats[8 + (size_t)k * BHR_STEP_STRIDE];
+    rm->ray_steps = steps;
+    rm->crossings_stored = stats[0];
+    rm->overflow_pixels = over;
+    rm->diff = diff ? 1 : 0;
+    rm->slots = K;
+    rm->cam = *cam;
+    rm->built = 1;
+    return BHR_OK;
+}
+
+int32_t bhr_raymap_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes) {
+    if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: bad argument");
+    if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_read: no ray map has been built (bhr_raymap_build)");
+    const bhr_raymap *rm = ctx->raymap;
+    const BhrRayMapArgs &a = rm->a;
+    const size_t plane = (size_t)a.plane;
+    size_t want = 0;
+    switch (which) {
+    case BHR_RAYMAP_STEPS: case BHR_RAYMAP_STATUS: case BHR_RAYMAP_CROSSINGS: want = plane * 4; break;
+    case BHR_RAYMAP_ESCAPE_DIR: want = plane * 12; break;
+    case BHR_RAYMAP_HITS: want = (size_t)a.slots * a.comps * plane * 4; break;
+    default: return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: unknown plane %d", which);
+    }
+    if (bytes != (int64_t)want) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: plane %d has %zu bytes, caller gave %lld", which, want, (long long)bytes);
+    BHR_TRY(bhr_enter(ctx));
+    if (which == BHR_RAYMAP_STEPS) return fetch(ctx, out, a.steps, want);
+    if (which == BHR_RAYMAP_STATUS) return fetch(ctx, out, a.status, want);
+    if (which == BHR_RAYMAP_CROSSINGS) return fetch(ctx, out, a.crossings, want);
+    // the device planes are [component][pixel]; the caller gets [pixel][component]
+    const int nc = which == BHR_RAYMAP_ESCAPE_DIR ? 3 : a.comps, ns = which == BHR_RAYMAP_ESCAPE_DIR ? 1 : a.slots;
+    std::vector<float> tmp((size_t)nc * plane);
+    float *o = (float *)out;
+    for (int s = 0; s < ns; ++s) {
+        const float *src = which == BHR_RAYMAP_ESCAPE_DIR ? a.dir : a.hits + (size_t)s * nc * plane;
+        BHR_TRY(fetch(ctx, tmp.data(), src, tmp.size() * sizeof(float)));
+        float *os = o + (size_t)s * plane * nc;
+        for (int c = 0; c < nc; ++c)
+            for (size_t p = 0; p < plane; ++p) os[p * nc + c] = tmp[(size_t)c * plane + p];
+    }
+    return BHR_OK;
+}
+
+int32_t bhr_raymap_get_info(bhr_ctx *ctx, bhr_raymap_info *out) {
+    if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_get_info: bad argument");
+    memset(out, 0, sizeof(*out));
+    const bhr_raymap *rm = ctx->raymap;
+    if (!rm) return BHR_OK;
+    out->built = rm->built;
+    out->device_bytes = rm->device_bytes;
+    if (!rm->built) return BHR_OK;
+    out->diff = rm->diff;
+    out->slots = rm->slots;
+    out->width = ctx->cfg.width;
+    out->rows = ctx->rows;
+    out->crossings_stored = (int64_t)rm->crossings_stored;
+    out->overflow_pixels = (int64_t)rm->overflow_pixels;
+    out->ray_steps = rm->ray_steps;
+    out->cam = rm->cam;
+    return BHR_OK;
+}
+
+int32_t bhr_raymap_free(bhr_ctx *ctx) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_free: null ctx");
+    if (!ctx->raymap) return BHR_OK;
+    BHR_TRY(bhr_enter(ctx));
+    BHR_TRY(drain(ctx));               // the frames in flight read the map
+    bhr_raymap_release(ctx);
+    return BHR_OK;
+}
+
+}  // extern "C"

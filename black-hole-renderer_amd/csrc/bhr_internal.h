@@ -155,6 +155,24 @@ enum bhr_march_kernel {
     BHR_MK_LIST_DV2,      // march_list_kernel<diff, 1>: analytic Disk V2                                        fast, strict
     BHR_MK_LIST_VOLUME,   // march_list_kernel<false, 2>: finite-thickness Disk V2                               fast, strict
     BHR_MK_DETECT,        // adaptive_detect_kernel: lists the output pixels whose neighbours differ             strict
+    // the ray map (raymap.hip)
+    BHR_MK_RAYMAP_BUILD,  // raymap_build_kernel<diff>: marches a view and records what the march finds          raymap
+    BHR_MK_RAYMAP_SHADE,  // raymap_shade_kernel<diff>: a frame from the records and the current scene           raymap
+};
+
+// The ray map as its two kernels see it (raymap.hip): second kernel argument, behind the march's own block.  Planar: every
+// plane is (rows, W) with the pixel index j W + i, so a wave's 8x8 tile reads and writes 32-byte runs of each.
+struct BhrRayMapArgs {
+    int32_t *steps;              // executed steps of the pixel's ray
+    int32_t *status;             // 0 captured, 1 escaped (samples the sky), 2 ran out of iterations
+    float *dir;                  // 3 planes: normalized(escape direction), zeros unless status 1
+    int32_t *crossings;          // annulus crossings of the ray, counting past the slots
+    float *hits;                 // slots x comps planes, [slot][component]: hit_x, hit_y, to_cam xyz (, dxx, dxy, dyx, dyy)
+    unsigned int *over_count;    // pixels with more crossings than slots ...
+    int32_t *over_list;          // ... and their indices (the fix kernel's list format)
+    unsigned long long *stats;   // [0] crossings stored
+    int32_t slots, comps;
+    int64_t plane;               // rows W
 };
 
 // Kernel argument block of adaptive_detect_kernel (march.hip).
@@ -198,6 +216,19 @@ struct bhr_options {
     int32_t png16_menu;         // BHR_PNG16_MENU: 1 (default) the 16-bit device PNG codes from its own menu, 0 from the 8-bit one (A/B runs)
     int32_t grade_timing;       // BHR_GRADE_TIMING: 1 a graded frame brackets each launch of its grade stage with HIP events (bhr_debug_read, which = 6); default 0
     int32_t shutter_timing;     // BHR_SHUTTER_TIMING: 1 a shutter frame brackets each accumulation launch with HIP events (bhr_debug_read, which = 5); default 0
+};
+
+// The context's ray map (api_raymap.hip): what the strict march of one whole-frame view finds before it shades anything.
+// Read-only shared state while frames are in flight, like the scene; allocated at the first build, reused by builds of the
+// same shape, released by bhr_raymap_free / bhr_destroy.
+struct bhr_raymap {
+    BhrRayMapArgs a;             // the device planes
+    int32_t built, diff, slots;
+    int32_t alloc_slots, alloc_comps;   // shape of the allocation
+    int32_t over_cap;            // capacity of the overflow list: the pixel count rounded up to whole blocks of the fix kernel
+    int64_t device_bytes;
+    bhr_camera cam;              // the view it was built for
+    uint64_t ray_steps, crossings_stored, overflow_pixels;
 };
 
 // geometry of a context's split-f16 bloom buffers (bloom.hip)
@@ -368,6 +399,10 @@ struct bhr_ctx {
     int32_t last_flags;
     int32_t timing_valid;
     int32_t march_end_recorded;
+
+    // the ray map (api_raymap.hip), behind everything the frames of bhr_render touch
+    bhr_raymap *raymap;        // null until the first bhr_raymap_build
+    int32_t raymap_slots;      // option "raymap_slots" / BHR_RAYMAP_SLOTS: crossings a map keeps per pixel (1..8, default 4), read by bhr_raymap_build
 };
 
 // The active frame slot: the one bhr_activate_slot / bhr_render last pointed the launchers at.
@@ -445,6 +480,7 @@ int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t 
 const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);       // march.o (ss: the supersampled twin)
 const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.o
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.o
+const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_raymap.o
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.o
 int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss);                               // march_launch.hip: builds d_/h_tile_order of the frame marched with factor ss
 int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_march_call &call);             // hybrid.hip
@@ -506,6 +542,14 @@ void bhr_jpeg_dev_free(bhr_ctx *ctx);
 // (sum * (1.0f / n)) back into d_bg / d_disk.  The sums are allocated here on first use.
 int32_t bhr_launch_shutter_accumulate(bhr_ctx *ctx, int32_t j, int32_t n);
 void bhr_shutter_free(bhr_ctx *ctx);                                 // the timing events
+// march_launch.hip: the ray map's two launches on ctx->stream.  build: marches `cam` and fills the map (counting its steps
+// into the context's scalar cell); shade: the map's pixels under the scene as it is and cam's t_offset into the active slot's
+// layers -- the pixels on the overflow list are left to the fix kernel (bhr_launch_march with a repair == 2 part over that list)
+int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m);
+int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff);
+// api_raymap.hip: the refusals of bhr_raymap_render (nothing launched); the map's flags for the march launcher; release
+int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
+void bhr_raymap_release(bhr_ctx *ctx);
 void bhr_grade_free(bhr_ctx *ctx);                                   // grade.hip: the timing events
 void bhr_population_free(bhr_ctx *ctx);                              // lifecycle.hip
 int32_t bhr_launch_build_mips(bhr_ctx *ctx);

@@ -36,6 +36,9 @@
 //                       texture kernels and the fix kernel of a hybrid march.
 // Each compilation instantiates only the kernels it launches and hands them to the one host launcher
 // (march_launch.hip) through a table: bhr_march_kernel_fast / _strict / _strict_ilp at the end of this file.
+//   march_raymap.o      the strict source a fourth time (-DBHR_MARCH_RAYMAP=1, the ILP object's flags): nothing but the ray
+//                       map's build and shade kernels (raymap.hip, made of this file's device functions), so that the three
+//                       objects above hold exactly the kernels they always have.
 #include "bhr_internal.h"
 #include "disk_v2_device.h"
 
@@ -44,6 +47,9 @@
 #endif
 #ifndef BHR_MARCH_ILP
 #define BHR_MARCH_ILP 0
+#endif
+#ifndef BHR_MARCH_RAYMAP
+#define BHR_MARCH_RAYMAP 0
 #endif
 #ifndef BHR_WAVE_STAMPS_BUILD
 #define BHR_WAVE_STAMPS_BUILD 0
@@ -789,6 +795,31 @@ struct Ray {
             shade_hit<DIFF, SRC>(a, sh, h.hit_x, h.hit_y, h.to_cam, h.dxx, h.dxy, h.dyx, h.dyy);
         }
     }
+    // The ray map's build (raymap.hip) in flush_one's place: the oldest parked crossing goes, exactly as parked, into the next
+    // map slot of the lane's pixel `at` instead of being shaded; n_rec counts the pixel's crossings past the slots.
+    __device__ __forceinline__ void record_one(const BhrRayMapArgs &m, size_t at, int &n_rec) {
+        if (n_pend > 0) {
+            const Pending<DIFF> h = park_load<DIFF>(0);
+            if (n_pend == 2) park_store<DIFF>(0, park_load<DIFF>(1));
+            n_pend -= 1;
+            if (n_rec < m.slots) {
+                const size_t p = (size_t)m.plane;
+                float *q = m.hits + (size_t)n_rec * m.comps * p + at;
+                q[0] = h.hit_x;
+                q[p] = h.hit_y;
+                q[2 * p] = h.to_cam.x;
+                q[3 * p] = h.to_cam.y;
+                q[4 * p] = h.to_cam.z;
+                if (DIFF) {
+                    q[5 * p] = h.dxx;
+                    q[6 * p] = h.dxy;
+                    q[7 * p] = h.dyx;
+                    q[8 * p] = h.dyy;
+                }
+            }
+            n_rec += 1;
+        }
+    }
     __device__ __forceinline__ void finish(const BhrMarchArgs &a) { write_pixel(a, pix % a.width, pix / a.width, escaped(), d, sh); }
     __device__ __forceinline__ void finish_at(const BhrMarchArgs &a, int i, int j) { write_pixel(a, i, j, escaped(), d, sh); }
     __device__ __forceinline__ void values(const BhrMarchArgs &a, float bk[3], float dk[3]) const { pixel_values(a, escaped(), d, sh, bk, dk); }
@@ -1292,7 +1323,10 @@ __global__ __launch_bounds__(256) void march_list_kernel(BhrMarchArgs a) {
     march_tile_body<DIFF, SRC, false, false, true, true>(a, wave, n);
 }
 
-#if BHR_MARCH_ILP
+#if BHR_MARCH_RAYMAP
+// the ray map's build and shade kernels: made of this file's device functions, the only kernels of this compilation
+#include "raymap.hip"
+#elif BHR_MARCH_ILP
 // Second half of the hybrid march's fast list: the pixels march_tile_guard_kernel put on the fix list, 64 per wave whatever
 // tile they came from, marched with the strict Ray -- bit-identical to math_mode 1.  Launched with a grid for the list's
 // capacity; waves beyond the count the device holds exit at once.
@@ -1526,7 +1560,16 @@ __global__ void selftest_kernel(unsigned long long *out, unsigned int div_rounds
 
 // ---- the kernels of this compilation, by the launcher's names (march_launch.hip); null: not in this object ----------
 // ss: the supersampled twin (a.ss > 1; the schedules refused with supersampling have none)
-#if BHR_MARCH_ILP
+#if BHR_MARCH_RAYMAP
+const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss) {
+    (void)ss;
+    switch (k) {
+    case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_kernel<true> : (const void *)raymap_build_kernel<false>;
+    case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_kernel<true> : (const void *)raymap_shade_kernel<false>;
+    default: return nullptr;
+    }
+}
+#elif BHR_MARCH_ILP
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss) {
     switch (k) {
     case BHR_MK_TILE_ILP:

@@ -423,3 +423,48 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
     ctx->ada_last_math = math;
     return BHR_OK;
 }
+
+// ---- the ray map (raymap.hip; api_raymap.hip owns the map) -------------------------------------------------------------------
+// Both kernels take the march's argument block of the k = 1 strict frame and the map as a second argument.
+int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m) {
+    const hipStream_t stream = ctx->stream;
+    const bhr_march_call call = {cam, flags | BHR_FORCE_STRICT, stream, /* slot */ -1, false, false, /* ss */ 1, false};
+    // the build marches but stores no layer: what march_args notes in the active frame slot for a march stays as it was
+    bhr_frame_slot &f = bhr_slot(ctx);
+    const int32_t disk_wide = f.disk_wide, sum_valid = f.sum_valid;
+    BhrMarchArgs a;
+    march_args(ctx, call, nullptr, 1, false, a);
+    f.disk_wide = disk_wide;
+    f.sum_valid = sum_valid;
+    if ((int64_t)a.width * a.rows != m.plane) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: the map has %lld pixels, the frame %lld", (long long)m.plane, (long long)a.width * a.rows);
+    BHR_TRY(ensure_tile_order(ctx, 1, a.tiles_x, a.n_tiles));
+    a.tile_order = ctx->d_tile_order;
+    a.ray_steps = m.stats + 8;                                 // a counter cell of the map's own, behind its totals
+    const bool diff = bhr_want_diff(ctx, flags);
+    if (m.comps != (diff ? 9 : 5)) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: %d components per record for differentials %d", m.comps, (int)diff);
+    const void *fn = bhr_march_kernel_raymap(BHR_MK_RAYMAP_BUILD, diff, 0);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: no build kernel in this library");
+    BhrRayMapArgs mm = m;
+    void *args[] = {&a, &mm};
+    (void)hipLaunchKernel(fn, dim3((a.n_list + 3) / 4), dim3(256), args, 0, stream);
+    BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}
+
+int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff) {
+    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no skybox set (bhr_set_skybox)");
+    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no disk texture set (bhr_set_disk_texture)");
+    BhrMarchArgs a;
+    march_args(ctx, call, nullptr, 1, false, a);
+    if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5))
+        return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: the map does not fit the frame");
+    const void *fn = bhr_march_kernel_raymap(BHR_MK_RAYMAP_SHADE, diff, 0);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no shade kernel in this library");
+    // the frame's march bracket opens here; the overflow launch behind this one (bhr_launch_march, last part) closes it
+    BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
+    BhrRayMapArgs mm = m;
+    void *args[] = {&a, &mm};
+    (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
+    BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}

@@ -1,0 +1,127 @@
+// raymap.hip -- the ray map's two kernels.  Device code only: march.hip includes this file inside its own namespace in a
+// strict compilation of its own (march_raymap.o: -DBHR_MARCH_STRICT=1 -DBHR_MARCH_RAYMAP=1 -ffp-contract=off, no fast-math,
+// the ILP-first scheduler), because the kernels are made of that file's device functions -- Ray<DIFF, 0>, Pending,
+// shade_hit, sample_skybox, store_pixel -- and the objects of the existing kernels stay what they were.
+//
+// A ray's path depends on the camera and the geometry of bhr_config only, not on the skybox, the disk texture or t_offset.
+// raymap_build_kernel marches a whole-frame view once with the strict Ray and, where the tile kernel shades a parked crossing
+// (flush_one), records it instead (Ray::record_one): per pixel up to `slots` Pending records, front to back, and a header --
+// executed steps, status, normalized escape direction, number of annulus crossings.  raymap_shade_kernel turns the records
+// and the scene as it stands into the frame's BG and DISK values: shade_hit on every record in order from the Shade that
+// Ray::init leaves, then the march's own pixel values and store.  These are the same device functions on the same values as
+// the strict march runs, in an object without contraction or re-association, so the frame is the strict frame bit for bit.
+// A pixel with more crossings than slots is on the overflow list; the shade kernel leaves it alone and march_fix_kernel
+// (march_strict_ilp.o) re-marches it in the same frame.
+#ifndef BHR_RAYMAP_HIP
+#define BHR_RAYMAP_HIP
+
+// One 8x8 tile per wave, tiles in the march's launch order (longest rays first).
+template <bool DIFF>
+__global__ __launch_bounds__(256) void raymap_build_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
+    const int slot = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (slot >= a.n_list) return;
+    const int lane = threadIdx.x & 63;
+    const int tile = a.tile_order ? a.tile_order[slot] : slot;
+    const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
+    const int i = tx * 8 + (lane & 7);
+    const int j = ty * 8 + (lane >> 3);
+    const bool valid = tile < a.n_tiles && i < a.width && j < a.rows;
+
+    Ray<DIFF, 0> ray;
+    ray.init(a, valid ? i : 0, valid ? j : 0);
+    if (!valid) ray.done = 4;
+    const size_t pix = valid ? (size_t)j * a.width + i : 0;
+    int cnt = 0, n_rec = 0;       // executed steps; crossings found so far (recorded while below m.slots)
+    // the tile body's march loop: a lane leaves when its ray terminates; when some lane has filled both its parking slots
+    // the wave records the older crossing of every lane that has one, and the second slot moves up
+    while (ray.done == 0) {
+        ray.step(a);
+        cnt += 1;
+        if (ray.full) {
+            ray.record_one(m, pix, n_rec);
+            ray.full = false;
+        }
+    }
+    ray.step_count = cnt;
+    if (cnt > 0) ray.settle(a);
+    else ray.done = 3;               // no step taken (max_iter <= 0, or no ray)
+    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
+    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
+
+    if (valid) {
+        const bool esc = ray.escaped();
+        m.steps[pix] = cnt;
+        m.status[pix] = esc ? 1 : (ray.done == 2 ? 0 : 2);
+        // the direction pixel_values hands sample_skybox
+        const V3 dn = esc ? normalized(ray.d) : mk(0.0f, 0.0f, 0.0f);
+        m.dir[pix] = dn.x;
+        m.dir[(size_t)m.plane + pix] = dn.y;
+        m.dir[2 * (size_t)m.plane + pix] = dn.z;
+        m.crossings[pix] = n_rec;
+    }
+    // more crossings than slots: the pixel keeps its first m.slots records and goes on the overflow list (wave-aggregated
+    // append, as the guard kernel's; every pixel is appended at most once and the list has room for all of them)
+    const bool over = valid && n_rec > m.slots;
+    const unsigned long long om = __ballot(over);
+    if (om) {
+        const int first = __ffsll((long long)om) - 1;
+        unsigned int base = 0;
+        if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(om));
+        base = __shfl(base, first, BHR_WAVE);
+        if (over) m.over_list[base + (unsigned int)__popcll(om & ((1ull << lane) - 1ull))] = (int32_t)pix;
+    }
+    const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
+    const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
+    if (lane == 0) {
+        atomicAdd(m.stats, stored);
+        atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
+    }
+}
+
+// render.py:3008-3018 as pixel_values has it, from the direction the build kernel stored already normalized
+__device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool escaped, V3 dir, const Shade &sh, float bk[3], float dk[3]) {
+    V3 bg = mk(0, 0, 0);
+    if (escaped) bg = sample_skybox(a.sc, dir);
+    float k = 1.0f - sh.alpha_total;
+    bk[0] = __fmul_rn(bg.x, k);
+    bk[1] = __fmul_rn(bg.y, k);
+    bk[2] = __fmul_rn(bg.z, k);
+    dk[0] = fminf(fmaxf(sh.accum.x, 0.0f), 1.0f);
+    dk[1] = fminf(fmaxf(sh.accum.y, 0.0f), 1.0f);
+    dk[2] = fminf(fmaxf(sh.accum.z, 0.0f), 1.0f);
+}
+
+// One lane per pixel, an 8x8 tile per wave as in the march (texture locality, and store_pixel's packed layout is per tile);
+// tiles in row-major order: every lane does about the same work.
+template <bool DIFF>
+__global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
+    const int tile = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (tile >= a.n_tiles) return;
+    const int lane = threadIdx.x & 63;
+    const int i = (tile % a.tiles_x) * 8 + (lane & 7);
+    const int j = (tile / a.tiles_x) * 8 + (lane >> 3);
+    if (!(i < a.width && j < a.rows)) return;
+    const size_t pix = (size_t)j * a.width + i;
+    const int count = m.crossings[pix];
+    if (count > m.slots) return;     // on the overflow list: the fix kernel marches and stores it
+    Shade sh;                        // as Ray::init leaves it
+    sh.accum = mk(0, 0, 0);
+    sh.alpha_total = 0.0f;
+    sh.unsure = 0;
+    for (int c = 0; c < count; ++c) {
+        const float *q = m.hits + (size_t)c * m.comps * (size_t)m.plane + pix;
+        const size_t p = (size_t)m.plane;
+        const float hx = q[0], hy = q[p];
+        const V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
+        float dxx = 0.0f, dxy = 0.0f, dyx = 0.0f, dyy = 0.0f;
+        if (DIFF) { dxx = q[5 * p]; dxy = q[6 * p]; dyx = q[7 * p]; dyy = q[8 * p]; }
+        shade_hit<DIFF, 0>(a, sh, hx, hy, to_cam, dxx, dxy, dyx, dyy);
+    }
+    const bool esc = m.status[pix] == 1;
+    const V3 dir = mk(m.dir[pix], m.dir[(size_t)m.plane + pix], m.dir[2 * (size_t)m.plane + pix]);
+    float bk[3], dk[3];
+    raymap_pixel_values(a, esc, dir, sh, bk, dk);
+    store_pixel(a, i, j, a.width, bk, dk);
+}
+
+#endif  // BHR_RAYMAP_HIP

@@ -21,7 +21,7 @@ import numpy as np
 
 from .camera import orbit_position
 from .lifecycle import make_factories
-from .output import Y4MStream, FrameSink, VIDEO_LEVEL, DEVICE, DITHERS, png_write, quantize, quantize16
+from .output import Y4MStream, FrameSink, VIDEO_LEVEL, DEVICE, DITHERS, png_write, quantize, quantize16, write_passes
 from .renderer import HipRenderer, R_DISK_INNER_DEFAULT, R_DISK_OUTER_DEFAULT, check_grade
 from .skybox import load_or_generate_skybox
 from .textures import compute_disk_texture_resolution, load_disk_texture
@@ -184,7 +184,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  force_regenerate_disk_texture: bool = False, ignore_taichi_cache: bool = False,
                  gpus: int = 1, disk_model: str = "texture", math: Optional[str] = None,
                  supersample: int = 1, supersample_threshold: Optional[float] = None, bit_depth: int = 8,
-                 dither: str = "none", grade: Optional[dict] = None, hdr_path: Optional[str] = None) -> np.ndarray:
+                 dither: str = "none", grade: Optional[dict] = None, hdr_path: Optional[str] = None,
+                 passes_path: Optional[str] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -192,8 +193,12 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     than it (HipRenderer.set_supersample; None: every pixel).  ``bit_depth`` / ``dither`` are checked here and applied by
     save_image to the frame this returns (the f32 frame does not depend on them).  ``grade``: None, or a dict of
     HipRenderer.set_grade's arguments (tonemap, exposure, white, transfer) -- the frame this returns is the graded one (one
-    device only).  ``hdr_path``: also writes the frame's scene-linear plane there (save_hdr; needs a grade, implies keep_hdr)."""
+    device only).  ``hdr_path``: also writes the frame's scene-linear plane there (save_hdr; needs a grade, implies keep_hdr).
+    ``passes_path``: also builds the view's ray map and writes its geometry passes and the frame's bg / disk / blur layers
+    there as a compressed .npz (output.write_passes); the image itself is rendered as without it (one device, one ray per
+    pixel, the texture disk source)."""
     check_depth_and_dither(bit_depth, dither)
+    check_passes(passes_path, gpus, supersample, disk_model)
     grade = check_grade(grade)
     if hdr_path is not None:
         check_hdr_path(hdr_path)
@@ -229,11 +234,52 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     if hdr_path is not None:
         save_hdr(renderer.read_hdr(), hdr_path)
     c = renderer.counters()
+    if passes_path is not None:
+        from . import _lib
+        layers = {"bg": renderer.read_layer(_lib.LAYER_BG), "disk": renderer.read_layer(_lib.LAYER_DISK),
+                  "blur": renderer.read_layer(_lib.LAYER_BLUR)}
+        renderer.build_ray_map(cam_pos, fov)
+        write_passes(passes_path, renderer.ray_map_passes(), layers)
+        info = renderer.ray_map_info()
+        print(f"Saved: {passes_path} (ray map: {info['slots']} slots, {info['crossings_stored']} crossings, "
+              f"{info['overflow_pixels']} overflow pixels)")
     dt = time.time() - t0
     print(f"Done in {dt:.3f}s  (march {c['march_ms']:.2f} ms, bloom {c['bloom_ms']:.2f} ms, "
           f"{c['ray_steps'] / 1e6:.1f} Mray-steps, {c['ray_steps'] / max(c['march_ms'], 1e-6) / 1e3:.0f} Mray-steps/s)")
     renderer.close()
     return img
+
+
+def check_passes(passes_path, gpus: int = 1, supersample: int = 1, disk_model: str = "texture") -> None:
+    """What a still image with geometry passes takes: a .npz path, one device, one ray per pixel, the texture source."""
+    if passes_path is None:
+        return
+    if not str(passes_path).lower().endswith(".npz"):
+        raise ValueError(f"the passes are written as a .npz file, got {passes_path!r}")
+    if gpus != 1:
+        raise ValueError("the passes come from a ray map, which lives on one GPU: --passes does not combine with --gpus > 1")
+    if supersample != 1:
+        raise ValueError("a ray map holds one ray per pixel: --passes does not combine with --supersample > 1")
+    if disk_model != "texture":
+        raise ValueError("a ray map shades the disk texture: --passes does not combine with --disk_model v2 / v2_volume")
+
+
+def check_ray_map(ray_map: bool, orbit: bool = False, shutter: float = 0.0, supersample=1, disk_model: str = "texture",
+                  gpus: int = 1, world: int = 1) -> None:
+    """What a video from a ray map takes: a camera that stands still, an instantaneous exposure, one ray per pixel, the
+    texture disk source, one GPU.  Raises ValueError before any device work."""
+    if not ray_map:
+        return
+    if orbit:
+        raise ValueError("a ray map is one view: --ray_map does not combine with --orbit")
+    if shutter > 0:
+        raise ValueError("shutter frames are marched: --ray_map does not combine with --shutter")
+    if supersample not in (None, 1):
+        raise ValueError("a ray map holds one ray per pixel: --ray_map does not combine with --supersample > 1")
+    if disk_model != "texture":
+        raise ValueError("a ray map shades the disk texture: --ray_map does not combine with --disk_model v2 / v2_volume")
+    if gpus != 1 or world != 1:
+        raise ValueError("a ray map lives on one GPU: --ray_map does not combine with --gpus > 1 or several ranks")
 
 
 def _lib_max_png_width(bit_depth: int = 8) -> int:
@@ -319,7 +365,7 @@ def check_shutter(shutter, shutter_samples) -> None:
 
 
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
-                    bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None) -> dict:
+                    bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -335,6 +381,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(shutter=shutter, shutter_samples=shutter_samples)
     if grade is not None:
         params.update(tonemap=grade["tonemap"], exposure=grade["exposure"], white=grade["white"], transfer=grade["transfer"])
+    if ray_map:
+        params.update(ray_map=True)
     return params
 
 
@@ -370,7 +418,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  video_stream: str = "auto", stats: Optional[dict] = None, supersample: Optional[int] = None,
                  supersample_threshold: Optional[float] = None, video_codec: str = "auto", video_quality: int = 90,
                  bit_depth: int = 8, dither: str = "none", shutter: float = 0.0, shutter_samples: int = 8,
-                 grade: Optional[dict] = None, **_deprecated_kwargs) -> None:
+                 grade: Optional[dict] = None, ray_map: bool = False, **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -412,11 +460,21 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     ``grade``: None (the frames are as the renderer is set), or a dict of HipRenderer.set_grade's arguments (tonemap, exposure,
     white, transfer): every consumer of the loop -- PNG (8 and 16 bit) or JPEG frames, the dither, the yuv420p stream -- gets the
     graded frame; the renderer's own grade is restored on return.  The progress record carries the four values only when a
-    grade is given, and a resume with other values starts over.  The frames keep no HDR plane."""
+    grade is given, and a resume with other values starts over.  The frames keep no HDR plane.
+
+    ``ray_map=True`` (a camera that stands still): the view is marched ONCE, before the loop (HipRenderer.build_ray_map), and
+    every frame is shaded from that map under the frame's texture (render_from_ray_map_async) instead of being marched again.
+    The frames are the STRICT arithmetic's whatever the renderer's ``math``: byte for byte those of a math="strict" run
+    without the flag.  Refused with ValueError, before any device work, together with ``orbit``, ``shutter > 0``, a
+    supersampling factor other than 1, a Disk V2 source or several ranks.  The progress record carries ``ray_map`` when it
+    is set, and a resume with the other setting starts over."""
     check_shutter(shutter, shutter_samples)
     grade = check_grade(grade)
     if grade is not None:
         grade["keep_hdr"] = False
+    if ray_map:
+        check_ray_map(ray_map, orbit, shutter, renderer.supersample if supersample is None else supersample,
+                      "texture" if getattr(renderer, "_dv2", None) is None else "v2", 1, world)
     if video_codec not in VIDEO_CODECS:
         raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
     check_depth_and_dither(bit_depth, dither, video_codec)
@@ -433,7 +491,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     submitted: List[int] = []
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
     params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither,
-                             shutter, shutter_samples, grade)
+                             shutter, shutter_samples, grade, ray_map)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -520,6 +578,10 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     factories = init_lifecycle_system(renderer, n_r, n_phi, seed=42)
     dt = disk_rotation_speed
     print(f"  lifecycle system ready (n_r={n_r}, n_phi={n_phi}), rank {rank}/{world}")
+    if ray_map:
+        renderer.build_ray_map(static_cam_pos, fov)     # the one march of the video
+        info = renderer.ray_map_info()
+        print(f"  ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
     t_loop0 = time.time()                               # ``stats`` (bench.py): the one-off set-up apart from the frame loop
 
     for frame in range(n_frames):
@@ -536,6 +598,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             times = shutter_times(frame, shutter, shutter_samples)
             positions = [orbit_position(static_cam_pos, u, n_frames, orbit_degrees) if orbit else static_cam_pos for u in times]
             renderer.render_shutter_async(positions, fov, [(u - frame) * disk_rotation_speed for u in times])
+        elif ray_map:
+            renderer.render_from_ray_map_async(frame=0)    # the same frame from the map: shade, no march
         else:
             renderer.render_async(cam_pos, fov, frame=0)   # lens flare, when enabled, is applied on the device
         sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))
@@ -558,6 +622,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
 
     frames_written, bytes_written = sink.drain()
     sink.close()
+    if ray_map:
+        renderer.free_ray_map()
     if mjpeg:
         renderer.set_outputs(outputs_before)
     if dither != dither_before:

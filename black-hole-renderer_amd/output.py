@@ -309,3 +309,58 @@ class Y4MStream:
             self.close()
         except Exception:
             pass
+
+
+# ---- geometry passes of a ray map (HipRenderer.ray_map_passes) -----------------------------------------------------------
+PASS_DTYPES = {"steps": np.int32, "status": np.int32, "crossings": np.int32, "escape_dir": np.float32, "hits": np.float32,
+               "hit_r": np.float32, "hit_phi": np.float32}
+PASS_LAYERS = ("bg", "disk", "blur")
+
+
+def hit_polar(hits: np.ndarray, crossings: np.ndarray):
+    """Radius and azimuth of every pixel's FIRST disk crossing in the disk's own plane, from the map's records: with
+    (hx, hy) = hits[0, ..., 0:2] in float32, ``hit_r = sqrt(hx * hx + hy * hy)`` (the march's annulus test, operation for
+    operation) and ``hit_phi = arctan2(hy, hx)`` in (-pi, pi]; NaN where ``crossings == 0``.  Returns (hit_r, hit_phi), each
+    (H, W) float32."""
+    hits = np.asarray(hits, dtype=np.float32)
+    crossings = np.asarray(crossings)
+    if hits.ndim != 4 or hits.shape[3] not in (5, 9) or hits.shape[1:3] != crossings.shape:
+        raise ValueError(f"hits must be (K, H, W, 5 | 9) and crossings (H, W), got {hits.shape} and {crossings.shape}")
+    hx, hy = hits[0, ..., 0], hits[0, ..., 1]
+    r = np.sqrt(hx * hx + hy * hy, dtype=np.float32)
+    phi = np.arctan2(hy, hx, dtype=np.float32)
+    none = crossings <= 0
+    return np.where(none, np.float32(np.nan), r).astype(np.float32), np.where(none, np.float32(np.nan), phi).astype(np.float32)
+
+
+def write_passes(path: str, passes: dict, layers: dict = None) -> None:
+    """The geometry passes of a ray map (HipRenderer.ray_map_passes) and, with ``layers``, the frame's ``bg`` / ``disk`` /
+    ``blur`` layers ((H, W, 3) float32 each) as one compressed ``.npz``: the integer passes as int32, everything else as
+    float32, under the keys they came with.  A host function; needs no device."""
+    if not str(path).lower().endswith(".npz"):
+        raise ValueError(f"the passes are written as a .npz file, got {path!r}")
+    missing = [k for k in ("steps", "status", "escape_dir", "crossings", "hits") if k not in passes]
+    if missing:
+        raise ValueError(f"passes lack {missing}")
+    unknown = sorted(set(passes) - set(PASS_DTYPES))
+    if unknown:
+        raise ValueError(f"unknown passes {unknown}")
+    shape = np.asarray(passes["steps"]).shape
+    if len(shape) != 2:
+        raise ValueError(f"steps must be (H, W), got {shape}")
+    out = {}
+    for name, a in passes.items():
+        a = np.ascontiguousarray(a, dtype=PASS_DTYPES[name])
+        want = {"escape_dir": shape + (3,), "hits": a.shape[:1] + shape + a.shape[3:]}.get(name, shape)
+        if a.shape != want or (name == "hits" and (a.ndim != 4 or a.shape[3] not in (5, 9))):
+            raise ValueError(f"pass {name!r} has shape {a.shape} in a {shape} frame")
+        out[name] = a
+    for name, a in (layers or {}).items():
+        if name not in PASS_LAYERS:
+            raise ValueError(f"layers are {PASS_LAYERS}, got {name!r}")
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape + (3,):
+            raise ValueError(f"layer {name!r} has shape {a.shape} in a {shape} frame")
+        out[name] = a
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    np.savez_compressed(path, **out)

@@ -468,6 +468,61 @@ class HipRenderer:
         self.render_shutter_async(cam_positions, fov, t_offsets, skip_differentials, skip_bloom, math, lens_flare)
         return self.read_layer(_lib.LAYER_FINAL)
 
+    # ------------------------------------------------------------------ ray map
+    def build_ray_map(self, cam_pos, fov: float, skip_differentials: bool = False) -> None:
+        """March the view once with the strict arithmetic and keep what the march finds before it shades anything
+        (bhr_raymap_build; include/bhr.h states the map).  The slot count is option "raymap_slots" (1..8, default 4).
+        Whole-frame contexts with one ray per pixel and the texture disk source only.  Synchronises."""
+        cam = self.camera_uniforms(cam_pos, fov, 0)
+        _lib.check(self._lib.bhr_raymap_build(self._ctx, C.byref(cam), _lib.SKIP_DIFFERENTIALS if skip_differentials else 0))
+
+    def render_from_ray_map_async(self, frame: int = 0, t_offset: Optional[float] = None, skip_bloom: bool = False,
+                                  lens_flare=None) -> None:
+        """One frame from the ray map under the scene as it is now (bhr_raymap_render): bit for bit the frame
+        render_async(cam_pos, fov, frame, math="strict") of the build's view leaves, without marching it again.  The disk is
+        rolled by ``t_offset``, or by ``frame * disk_rotation_speed``; the lens flare as render_async decides it."""
+        t = float(frame) * self.disk_rotation_speed if t_offset is None else float(t_offset)
+        flags = _lib.SKIP_BLOOM if skip_bloom else 0
+        if self.lens_flare if lens_flare is None else lens_flare:
+            flags |= _lib.LENS_FLARE
+        _lib.check(self._lib.bhr_raymap_render(self._ctx, t, flags))
+
+    def ray_map_info(self) -> dict:
+        """The context's ray map (bhr_raymap_get_info): built, diff, slots, width, rows, crossings_stored, overflow_pixels,
+        device_bytes, ray_steps of the build, and the build camera's pos / r_escape."""
+        info = _lib.RayMapInfo()
+        _lib.check(self._lib.bhr_raymap_get_info(self._ctx, C.byref(info)))
+        out = {name: int(getattr(info, name)) for name in ("built", "diff", "slots", "width", "rows", "crossings_stored",
+                                                           "overflow_pixels", "device_bytes", "ray_steps")}
+        out["cam_pos"] = [float(v) for v in info.cam.pos]
+        out["r_escape"] = float(info.cam.r_escape)
+        return out
+
+    def ray_map_passes(self) -> dict:
+        """The map's planes as NumPy arrays in (H, W[, ...]) order: ``steps``, ``status`` (0 captured, 1 escaped, 2 out of
+        iterations), ``escape_dir`` (H, W, 3), ``crossings``, ``hits`` (K, H, W, 5 | 9: hit_x, hit_y, to_cam xyz[, dxx, dxy, dyx,
+        dyy]) and, computed on the host from the first record (output.hit_polar), ``hit_r`` and ``hit_phi`` of the first
+        crossing, NaN where there is none."""
+        from .output import hit_polar
+        info = self.ray_map_info()
+        if not info["built"]:
+            raise AssertionError("no ray map has been built (build_ray_map)")
+        h, w, k, nc = info["rows"], info["width"], info["slots"], 9 if info["diff"] else 5
+
+        def read(which, shape, dtype):
+            out = np.empty(shape, dtype=dtype)
+            _lib.check(self._lib.bhr_raymap_read(self._ctx, which, out.ctypes.data, out.nbytes))
+            return out
+        passes = {"steps": read(_lib.RAYMAP_STEPS, (h, w), np.int32), "status": read(_lib.RAYMAP_STATUS, (h, w), np.int32),
+                  "escape_dir": read(_lib.RAYMAP_ESCAPE_DIR, (h, w, 3), np.float32),
+                  "crossings": read(_lib.RAYMAP_CROSSINGS, (h, w), np.int32), "hits": read(_lib.RAYMAP_HITS, (k, h, w, nc), np.float32)}
+        passes["hit_r"], passes["hit_phi"] = hit_polar(passes["hits"], passes["crossings"])
+        return passes
+
+    def free_ray_map(self) -> None:
+        """Release the ray map's device memory (bhr_raymap_free); close() does it too."""
+        _lib.check(self._lib.bhr_raymap_free(self._ctx))
+
     def sync(self) -> None:
         _lib.check(self._lib.bhr_sync(self._ctx))
 

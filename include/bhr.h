@@ -255,6 +255,60 @@ BHR_API int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
  * BHR_ERR_INVALID, with nothing launched and the context as it was: ctx or cams NULL, n < 1 or n > 64, a row-block
  * context, BHR_PERSISTENT or BHR_ROW_COSTS in flags. */
 BHR_API int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags);
+/* Ray map: march a view once, re-shade it for every frame, read the geometry passes.  A ray's path depends on the camera
+ * and the geometry of bhr_config only (step size, escape radius, disk radii, tilt, differentials or not) -- not on the skybox,
+ * the disk texture or t_offset.  bhr_raymap_build marches the whole-frame view `cam` once with the STRICT arithmetic (whatever
+ * the context's math_mode) and keeps, per pixel, what the march finds before it shades anything:
+ *   STEPS      executed while-loop iterations (i32)
+ *   STATUS     0 captured (r < r_s), 1 escaped: the pixel samples the sky (beyond r_escape or past the affine limit), 2 ran out
+ *              of iterations (i32)
+ *   ESCAPE_DIR the normalized direction handed to the skybox lookup, zeros unless STATUS is 1 (f32 x 3)
+ *   CROSSINGS  annulus crossings of the ray, counting past the slots (i32)
+ *   HITS       the first K crossings front to back, exactly as the march parks them: hit_x, hit_y, to_cam[3] and, with
+ *              differentials, dxx, dxy, dyx, dyy (f32 x 5 or 9); records beyond min(CROSSINGS, K) are zero
+ * K = option "raymap_slots" at the time of the build (1..8, default 4).  A pixel with more than K crossings is also put on an
+ * overflow list.  flags: BHR_SKIP_DIFFERENTIALS or 0.  Synchronises; ordered behind the frames in flight.  Device memory: 24
+ * bytes per pixel plus K x 20 (K x 36 with differentials) plus 4 for the overflow list; allocated at the first build, reused by
+ * later builds of the same K and record size, released by bhr_raymap_free or bhr_destroy.
+ * bhr_raymap_render(ctx, t, flags) is a frame: bit for bit the frame bhr_render(ctx, &cam_t, flags | BHR_FORCE_STRICT |
+ * <the build's BHR_SKIP_DIFFERENTIALS>) leaves, cam_t the build camera with t_offset = t, under the scene as it is at the time
+ * of the call -- BG, DISK, BLUR, FINAL and everything made from them on demand (u8 and u16 rows, dither, grade, HDR plane, lens
+ * flare, PNG and JPEG sinks, the y4m stream).  One kernel shades the stored records with the march's own device functions
+ * (csrc/raymap.hip); the strict fix kernel re-marches the pixels of the overflow list in the same frame.  flags:
+ * BHR_SKIP_BLOOM, BHR_LENS_FLARE.  The frame takes the next frame slot like any other and has one entry in the timing ring, its
+ * march bracket the shade and overflow launches; bhr_counters: rays = W H, ray_steps the steps of the overflow re-march only
+ * (bhr_raymap_info.ray_steps has the build's, equal to a strict bhr_render's).  It neither counts towards nor runs the
+ * calibration of slot 1's stream.  Asynchronous.  The map is read-only shared state like the scene: scene updates
+ * (bhr_set_skybox, bhr_set_disk_texture, bhr_compose_texture, the lifecycle calls) do not invalidate it.
+ * bhr_raymap_read copies one plane to the host, (rows, W[, 3]) and HITS as (K, rows, W, 5 | 9); bytes must be the plane's size.
+ * bhr_raymap_get_info never fails for want of a map: built = 0 then.  bhr_raymap_free is ordered behind the frames in flight.
+ * Refusals, with nothing launched and the context as it was --
+ *   BHR_ERR_STATE:   render or read before a build (or after bhr_raymap_free); render while supersampling, adaptive
+ *                    supersampling or a Disk V2 source is on (the map stays; switch back and it renders again);
+ *   BHR_ERR_INVALID: build or render on a row-block context; build with supersampling or adaptive supersampling on or with a
+ *                    Disk V2 source (surface or volume); any other flag bit; a non-finite t_offset; "raymap_slots" outside 1..8
+ *                    (refused by bhr_set_option; a BHR_RAYMAP_SLOTS outside it by the build); an unknown plane or a wrong size;
+ *   BHR_ERR_NOMEM:   a failed allocation: everything the call allocated is freed again and the context stays usable. */
+#define BHR_RAYMAP_STEPS 0
+#define BHR_RAYMAP_STATUS 1
+#define BHR_RAYMAP_ESCAPE_DIR 2
+#define BHR_RAYMAP_CROSSINGS 3
+#define BHR_RAYMAP_HITS 4
+typedef struct {
+    int32_t built, diff, slots;         /* a map exists; it holds the differential records; K */
+    int32_t width, rows;
+    int32_t reserved;
+    int64_t crossings_stored;           /* sum over the pixels of min(CROSSINGS, K) */
+    int64_t overflow_pixels;            /* pixels with CROSSINGS > K */
+    int64_t device_bytes;
+    uint64_t ray_steps;                 /* of the build: those of a strict bhr_render of the view */
+    bhr_camera cam;                     /* the view the map was built for */
+} bhr_raymap_info;
+BHR_API int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
+BHR_API int32_t bhr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
+BHR_API int32_t bhr_raymap_read(bhr_ctx *ctx, int32_t plane, void *out, int64_t bytes);
+BHR_API int32_t bhr_raymap_get_info(bhr_ctx *ctx, bhr_raymap_info *out);
+BHR_API int32_t bhr_raymap_free(bhr_ctx *ctx);
 /* image_field/disk_layer_field/blur_field .to_numpy() and the final image,
  * for the context's rows: (row1-row0, width, 3) f32.  Synchronises. */
 BHR_API int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out);
@@ -344,6 +398,7 @@ BHR_API int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]);
  *                                         (bhr_debug_read, which = 5; ~5 us per event in the frame's stream); default 0
  *   "grade_timing"    BHR_GRADE_TIMING    1 a graded frame (bhr_set_grade) brackets each launch of its grade stage with a pair of HIP
  *                                         events (bhr_debug_read, which = 6); default 0
+ *   "raymap_slots"    BHR_RAYMAP_SLOTS    crossings a ray map keeps per pixel (1..8, default 4); read by bhr_raymap_build
  * (bhr_create only: BHR_FRAME_SLOTS.) */
 BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
 /* Diagnostics (tests): the split-f16 post-pass's packed intermediates of the last frame as raw bytes -- which = 0 the H pass's
