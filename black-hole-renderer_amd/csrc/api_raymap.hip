@@ -1,6 +1,6 @@
 // api_raymap.hip -- the ray map's entry points (include/bhr.h): build, read, info, free, and the refusals of
 // bhr_raymap_render (the frame itself is launched from api.hip, next to bhr_render: it takes a frame slot like any other).
-// The kernels are raymap.hip's, their launchers march_launch.hip's.
+// The kernels are march_raymap.hip's, their launchers march_launch.hip's.
 #include <math.h>
 #include <string.h>
 

@@ -36,7 +36,7 @@
 #define BHR_STEP_STRIDE 32          // in u64 words
 #define BHR_STEP_CELL (BHR_STEP_LANES * BHR_STEP_STRIDE)
 
-// hybrid march: guard bands around the algorithm's switches; a lane inside one is re-marched strict (march.hip: march_tile_guard_kernel)
+// hybrid march: guard bands around the algorithm's switches; a lane inside one is re-marched strict (march.hip: march_tile_guard_kernel; march_strict_ilp.hip: march_fix_kernel)
 #ifndef BHR_LOD_GUARD
 #define BHR_LOD_GUARD 1e-2f         // |lod - level boundary|: the fast differentials are good to ~1e-5 in lod at the BASELINE views, but a camera
                                     // 15-50 r_s away behind a long lens carries them through hundreds of steps -- fuzzed 512x320 views flipped
@@ -137,8 +137,9 @@ struct bhr_march_call {
     bool keep_start;         // a later sample of a shutter frame (bhr_render_shutter): the march-start event stays the first sample's
 };
 
-// The march kernels by what they do; each compilation of march.hip returns its own instantiation of a name (or null) from
-// bhr_march_kernel_fast / _strict / _strict_ilp.  diff: the instantiation that integrates the ray differentials.
+// The march kernels by what they do; each march object returns its own instantiation of a name (or null) from
+// bhr_march_kernel_fast / _strict / _strict_ilp / _raymap (march.hip, march_strict.hip, march_strict_ilp.hip,
+// march_raymap.hip).  diff: the instantiation that integrates the ray differentials.
 enum bhr_march_kernel {
     BHR_MK_VOLUME,        // march_tile_kernel<false, 2>: finite-thickness Disk V2 (never differentials)          fast, strict
     BHR_MK_DV2,           // march_tile_kernel<diff, 1>: analytic Disk V2                                        fast, strict
@@ -155,12 +156,12 @@ enum bhr_march_kernel {
     BHR_MK_LIST_DV2,      // march_list_kernel<diff, 1>: analytic Disk V2                                        fast, strict
     BHR_MK_LIST_VOLUME,   // march_list_kernel<false, 2>: finite-thickness Disk V2                               fast, strict
     BHR_MK_DETECT,        // adaptive_detect_kernel: lists the output pixels whose neighbours differ             strict
-    // the ray map (raymap.hip)
+    // the ray map (march_raymap.hip)
     BHR_MK_RAYMAP_BUILD,  // raymap_build_kernel<diff>: marches a view and records what the march finds          raymap
     BHR_MK_RAYMAP_SHADE,  // raymap_shade_kernel<diff>: a frame from the records and the current scene           raymap
 };
 
-// The ray map as its two kernels see it (raymap.hip): second kernel argument, behind the march's own block.  Planar: every
+// The ray map as its two kernels see it (march_raymap.hip): second kernel argument, behind the march's own block.  Planar: every
 // plane is (rows, W) with the pixel index j W + i, so a wave's 8x8 tile reads and writes 32-byte runs of each.
 struct BhrRayMapArgs {
     int32_t *steps;              // executed steps of the pixel's ray
@@ -175,7 +176,7 @@ struct BhrRayMapArgs {
     int64_t plane;               // rows W
 };
 
-// Kernel argument block of adaptive_detect_kernel (march.hip).
+// Kernel argument block of adaptive_detect_kernel (march_strict.hip).
 struct BhrDetectArgs {
     const float *bg, *disk;      // the k = 1 frame: (height, width, 3)
     int32_t width, height;
@@ -477,11 +478,11 @@ int32_t bhr_leave_frame(bhr_ctx *ctx);
 int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags);                          // march_launch.hip: BHR_MATH_* of a frame
 int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part = nullptr);   // march_launch.hip: every march launch
 int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds); // march_launch.hip: registers / LDS of the frame kernel
-const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);       // march.o (ss: the supersampled twin)
-const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.o
-const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.o
-const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_raymap.o
-int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.o
+const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);       // march.hip -> march.o (ss: the supersampled twin)
+const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.hip -> march_strict.o
+const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.hip -> march_strict_ilp.o
+const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_raymap.hip -> march_raymap.o
+int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
 int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss);                               // march_launch.hip: builds d_/h_tile_order of the frame marched with factor ss
 int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_march_call &call);             // hybrid.hip
 // march_launch.hip: detect + refinement (ctx->ada_k) of an adaptively supersampled frame, behind its base march `call` on the same stream; records the march-end event

@@ -1,5 +1,5 @@
 // disk_v2_device.h -- binary64 device functions of the Disk V2 model, shared by the field evaluator
-// (disk_v2.hip) and the march kernel's analytic disk source (march.hip).  See disk_v2.hip for the
+// (disk_v2.hip) and the march kernel's analytic disk source (march_device.h).  See disk_v2.hip for the
 // reference citations.
 #pragma once
 #include <float.h>

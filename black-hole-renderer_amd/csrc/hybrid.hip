@@ -604,7 +604,7 @@ int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_march_call &call) {
     // The fast list's kernel carries guards: a lane that comes within a guard band of one of the algorithm's switches -- the
     // truncated mip level, a disk crossing in or next to the terminating step, a step that ends on the disk plane, the
     // disk's edges -- appends its pixel to a fix list instead of writing it, and a third launch marches the listed pixels
-    // with the strict arithmetic (march.hip: march_tile_guard_kernel / march_fix_kernel).  ~0.1 % of the pixels.
+    // with the strict arithmetic (march.hip: march_tile_guard_kernel, march_strict_ilp.hip: march_fix_kernel).  ~0.1 % of the pixels.
     // Default: on for anti-aliased views -- the mip-level switch alone flips ~300 pixels of a 4k frame (5e-4 RMSE) -- and for
     // TILTED disks: the plane function z - y tan(tilt) of a point on the plane is then a difference of O(1) numbers, it
     // rounds to exactly 0 for ~1e-6 of the crossings, and the reference's `f_old f_new < 0` never registers those (12 pixels

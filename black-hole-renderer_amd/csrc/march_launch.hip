@@ -1,7 +1,8 @@
 // march_launch.hip -- the host half of the ray march: every march launch goes through bhr_launch_march.
 //
-// march.hip is device code compiled three times (csrc/Makefile: fast, strict, strict with the ILP-first scheduler); each
-// object hands its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp).  This file resolves the
+// The march's device code is four objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
+// with the ILP-first scheduler, march_raymap.hip; the layout: march_device.h); each object hands its kernels over through a
+// table (bhr_march_kernel_fast / _strict / _strict_ilp / _raymap).  This file resolves the
 // arithmetic, builds the kernel arguments, keeps the tile order, the ray-step counters and the timing events, and picks
 // the kernel of a launch (march_kernel).  What a launch works from is in its arguments -- the caller's bhr_march_call
 // (camera, flags, stream, timing slot, end-event policy, supersampling factor) and, for one list of a hybrid march, a
@@ -398,7 +399,7 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
         a.tile_order = f.d_ada_list + (size_t)which * cap;
         a.n_list = cap;
         a.fix_count = f.d_ada_counts + which;
-        a.fix_list = (int32_t *)f.d_ada_mask;                           // LIST kernels read it as the mask (march.hip: list_refined)
+        a.fix_list = (int32_t *)f.d_ada_mask;                           // LIST kernels read it as the mask (march_tile.h: list_refined)
         a.fix_cap = 0;
         if (a.n_tiles != cap) return bhr_fail(BHR_ERR_STATE, "adaptive supersampling: %d fine tiles, lists for %d", a.n_tiles, cap);
         const auto own = fast ? bhr_march_kernel_fast : bhr_march_kernel_strict;
@@ -424,7 +425,7 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
     return BHR_OK;
 }
 
-// ---- the ray map (raymap.hip; api_raymap.hip owns the map) -------------------------------------------------------------------
+// ---- the ray map (march_raymap.hip; api_raymap.hip owns the map) ------------------------------------------------------------------
 // Both kernels take the march's argument block of the k = 1 strict frame and the map as a second argument.
 int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m) {
     const hipStream_t stream = ctx->stream;

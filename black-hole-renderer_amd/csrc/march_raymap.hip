@@ -1,7 +1,6 @@
-// raymap.hip -- the ray map's two kernels.  Device code only: march.hip includes this file inside its own namespace in a
-// strict compilation of its own (march_raymap.o: -DBHR_MARCH_STRICT=1 -DBHR_MARCH_RAYMAP=1 -ffp-contract=off, no fast-math,
-// the ILP-first scheduler), because the kernels are made of that file's device functions -- Ray<DIFF, 0>, Pending,
-// shade_hit, sample_skybox, store_pixel -- and the objects of the existing kernels stay what they were.
+// march_raymap.hip -> march_raymap.o: the ray map's two kernels, and nothing else, in a strict object of their own
+// (-ffp-contract=off, no fast-math, the ILP-first scheduler).  They are made of the strict march's device functions --
+// Ray<DIFF, 0>, Pending, shade_hit, sample_skybox, store_pixel (ray_strict.h, march_device.h).
 //
 // A ray's path depends on the camera and the geometry of bhr_config only, not on the skybox, the disk texture or t_offset.
 // raymap_build_kernel marches a whole-frame view once with the strict Ray and, where the tile kernel shades a parked crossing
@@ -12,13 +11,14 @@
 // the strict march runs, in an object without contraction or re-association, so the frame is the strict frame bit for bit.
 // A pixel with more crossings than slots is on the overflow list; the shade kernel leaves it alone and march_fix_kernel
 // (march_strict_ilp.o) re-marches it in the same frame.
-#ifndef BHR_RAYMAP_HIP
-#define BHR_RAYMAP_HIP
+#include "ray_strict.h"
+
+namespace {
 
 // One 8x8 tile per wave, tiles in the march's launch order (longest rays first).
 template <bool DIFF>
 __global__ __launch_bounds__(256) void raymap_build_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
-    const int slot = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int slot = wave_slot();
     if (slot >= a.n_list) return;
     const int lane = threadIdx.x & 63;
     const int tile = a.tile_order ? a.tile_order[slot] : slot;
@@ -95,7 +95,7 @@ __device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool 
 // tiles in row-major order: every lane does about the same work.
 template <bool DIFF>
 __global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
-    const int tile = blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tile = wave_slot();
     if (tile >= a.n_tiles) return;
     const int lane = threadIdx.x & 63;
     const int i = (tile % a.tiles_x) * 8 + (lane & 7);
@@ -124,4 +124,14 @@ __global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRa
     store_pixel(a, i, j, a.width, bk, dk);
 }
 
-#endif  // BHR_RAYMAP_HIP
+}  // namespace
+
+// ---- the kernels of this object, by the launcher's names (march_launch.hip); null: not in this object ----------
+const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss) {
+    (void)ss;
+    switch (k) {
+    case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_kernel<true> : (const void *)raymap_build_kernel<false>;
+    case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_kernel<true> : (const void *)raymap_shade_kernel<false>;
+    default: return nullptr;
+    }
+}

@@ -291,7 +291,7 @@ def reference_norms(params: DiskV2Params, structure_params: DiskV2StructureParam
 
 def disk_rgba(r, phi, cparams: _CParams, norm_shear: float, norm_hotspot: float, t_peak: float,
               color_temp: float = 6000.0, ctx=None) -> np.ndarray:
-    """Host twin of csrc/march.hip: disk_v2_rgba (fields from the device, colour mapping in NumPy):
+    """Host twin of csrc/march_device.h: disk_v2_rgba (fields from the device, colour mapping in NumPy):
     (..., 4) float32.  Used to bake textures and to test the in-kernel source."""
     from .skybox import blackbody_rgb
     F = evaluate(F_TOTAL, cparams, r, phi=phi, norm_shear=norm_shear, norm_hotspot=norm_hotspot, ctx=ctx)

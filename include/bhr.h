@@ -274,7 +274,7 @@ BHR_API int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t
  * <the build's BHR_SKIP_DIFFERENTIALS>) leaves, cam_t the build camera with t_offset = t, under the scene as it is at the time
  * of the call -- BG, DISK, BLUR, FINAL and everything made from them on demand (u8 and u16 rows, dither, grade, HDR plane, lens
  * flare, PNG and JPEG sinks, the y4m stream).  One kernel shades the stored records with the march's own device functions
- * (csrc/raymap.hip); the strict fix kernel re-marches the pixels of the overflow list in the same frame.  flags:
+ * (csrc/march_raymap.hip); the strict fix kernel re-marches the pixels of the overflow list in the same frame.  flags:
  * BHR_SKIP_BLOOM, BHR_LENS_FLARE.  The frame takes the next frame slot like any other and has one entry in the timing ring, its
  * march bracket the shade and overflow launches; bhr_counters: rays = W H, ray_steps the steps of the overflow re-march only
  * (bhr_raymap_info.ray_steps has the build's, equal to a strict bhr_render's).  It neither counts towards nor runs the

@@ -57,7 +57,7 @@ BHR_API int32_t bhr_disk_v2_eval(bhr_ctx *ctx, const bhr_disk_v2_params *params,
 
 /* Disk source of the march kernel: BHR_DISK_TEXTURE (default) samples the disk texture / mip stack;
  * BHR_DISK_V2 evaluates the Disk V2 model per hit in binary64 (temperature -> black-body colour,
- * density -> opacity; csrc/march.hip: disk_v2_rgba).  norm_shear / norm_hotspot are the maxima of the raw
+ * density -> opacity; csrc/march_device.h: disk_v2_rgba).  norm_shear / norm_hotspot are the maxima of the raw
  * structure sums on a reference grid (bhr_disk_v2_eval(..., max_out)), t_peak the maximum of T_mid(r). */
 #define BHR_DISK_TEXTURE 0
 #define BHR_DISK_V2 1
@@ -66,7 +66,7 @@ BHR_API int32_t bhr_disk_v2_eval(bhr_ctx *ctx, const bhr_disk_v2_params *params,
  * that passes through the volume |zeta| <= H(r), r_in <= r <= r_out of the tilted disk frame is cut into
  * `substeps` pieces; a piece at density rho, with direction cosine mu to the disk normal, has opacity
  * 1 - exp(-absorption * rho * (1 + grazing_gain * (1 - mu)) * ds) and the black-body colour of T(r, zeta) F
- * under the g-factor; pieces composite front to back like surface crossings (csrc/march.hip:
+ * under the g-factor; pieces composite front to back like surface crossings (csrc/march_device.h:
  * volume_segment); a ray stops sampling once its accumulated opacity reaches 0.9999.
  * Options are set with bhr_set_disk_volume_options before bhr_set_disk_source. */
 #define BHR_DISK_V2_VOLUME 2

@@ -627,7 +627,7 @@ ORACLE_API void oracle_set_volume(const oracle_dv2_params *p, double norm_shear,
 }
 
 /* black-body colour of the normalised temperature t in [0, 1]: the compose kernel's mapping
- * (render.py:3243-3257) as csrc/march.hip disk_v2_color applies it */
+ * (render.py:3243-3257) as csrc/march_device.h disk_v2_color applies it */
 static v3 dv2_color(float tf)
 {
     const float t_factor = (DISK_COLOR_TEMPERATURE - 4500.0f) / (6500.0f - 2700.0f);

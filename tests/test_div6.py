@@ -1,4 +1,4 @@
-"""The strict march divides by 6 with a 2-operation sequence, q = RN(x c_hi + RN(x c_lo)) (csrc/march.hip: div6).
+"""The strict march divides by 6 with a 2-operation sequence, q = RN(x c_hi + RN(x c_lo)) (csrc/march_device.h: div6).
 It must equal IEEE x / 6.0f for every f32 significand; checked exhaustively on the CPU with the
 same fmaf sequence (one binade covers all significands, a few exponents cover the rest of the
 range incl. negatives)."""

@@ -221,7 +221,7 @@ def test_exact_arithmetic_selftest(hip_lib):
 
 @pytest.mark.parametrize("cam,fov", [([8.0, 0.0, 0.0], 60), ([60.0, 0.0, 5.0], 30), ([1.6, 0.0, 0.2], 100), ([0.0, 0.0, 9.0], 70)])
 def test_fast_march_in_the_rays_own_clock_radial_and_extreme_rays(cam, fov, hip_lib):
-    """The fast march rescales every ray's affine parameter by tau = (1.5 L2)^(-1/2) (csrc/march.hip, "the ray's own clock").
+    """The fast march rescales every ray's affine parameter by tau = (1.5 L2)^(-1/2) (csrc/ray_fast.h, "the ray's own clock").
     Odd frame sizes put a pixel exactly on the optical axis: for a camera looking at the hole that ray is radial, L2 = 0, and
     tau comes from the clamp; far cameras have large L2 (small tau), cameras inside the photon sphere the opposite.  The frame
     must be finite everywhere, the axis pixel must end as strict's does, step totals and layers must agree with the strict

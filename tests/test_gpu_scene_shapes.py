@@ -1,4 +1,4 @@
-"""The march's texture and sky samplers (csrc/march.hip: sample_disk_level, sample_skybox, the level pick in shade_hit) at
+"""The march's texture and sky samplers (csrc/march_device.h: sample_disk_level, sample_skybox, the level pick in shade_hit) at
 the shapes the rest of the suite never marches through: disk textures with fewer than the five stored mip levels, odd
 sides, a single row, three texels across; skies that are neither a power of two nor 1:2, down to one texel.
 
