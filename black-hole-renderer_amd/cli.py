@@ -102,6 +102,13 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "from that ray map under the frame's texture instead of marching it again.  The frames are the strict "
                         "arithmetic's whatever --math says.  Not with --orbit, --shutter, --supersample > 1, --disk_model v2 / "
                         "v2_volume or --gpus > 1")
+    p.add_argument("--orbit_map", action="store_true",
+                   help="--video --orbit with --disk_tilt 0: march frame 0's view once and shade every frame of the orbit from "
+                        "that one ray map, turned about z to the frame's camera (the orbit is a symmetry of the hole, the untilted "
+                        "disk and the escape sphere).  Frame 0 is the strict arithmetic's frame; a later frame is the strict march "
+                        "of the symmetric rays, not byte-identical to the marched frame of that view: as far from it as two strict "
+                        "marches of symmetric views are from each other.  Not with --ray_map, --shutter, --supersample > 1, "
+                        "--disk_model v2 / v2_volume or --gpus > 1")
     p.add_argument("--passes", type=str, default=None, metavar="PATH.npz",
                    help="still images: also write the view's geometry passes (per pixel: steps, ray fate, escape direction, disk "
                         "crossings and hit points, from a ray map of the view) and the frame's bg / disk / blur layers as a "
@@ -121,6 +128,23 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    if args.orbit_map:
+        if not args.video:
+            p.error("--orbit_map needs --video: it is the ray map of an orbit video")
+        if not args.orbit:
+            p.error("--orbit_map needs --orbit: a camera that stands still takes --ray_map")
+        if args.ray_map:
+            p.error("--orbit_map does not combine with --ray_map: that is the map of a camera that stands still")
+        if args.disk_tilt != 0:
+            p.error("--orbit_map needs --disk_tilt 0: the orbit is a symmetry of an untilted disk only")
+        if args.shutter > 0:
+            p.error("--orbit_map does not combine with --shutter: shutter frames are marched")
+        if args.supersample != 1:
+            p.error("--orbit_map does not combine with --supersample other than 1: a ray map holds one ray per pixel")
+        if args.disk_model != "texture":
+            p.error("--orbit_map does not combine with --disk_model other than texture: a ray map shades the disk texture")
+        if args.gpus != 1:
+            p.error("--orbit_map does not combine with --gpus other than 1: a ray map lives on one GPU")
     if args.ray_map:
         if not args.video:
             p.error("--ray_map needs --video: a still image is marched once anyway (--passes writes its ray map's passes)")
@@ -254,7 +278,7 @@ def main(argv=None) -> int:
                              png_level=(drivers.DEVICE if args.png_encoder == "device" else drivers.VIDEO_LEVEL),
                              video_codec=args.video_codec, video_quality=args.video_quality, bit_depth=args.bit_depth,
                              dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples,
-                             grade=grade_from_args(args), ray_map=args.ray_map)
+                             grade=grade_from_args(args), ray_map=args.ray_map, orbit_map=args.orbit_map)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent

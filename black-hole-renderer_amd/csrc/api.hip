@@ -815,13 +815,15 @@ int32_t shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, int n, uint32_t fl
 // A frame from the context's ray map on slot k (bhr_raymap_render): the shade kernel over the stored records, then the strict
 // fix kernel over the map's overflow list (its count is the device's: a grid for the list's capacity, as the hybrid march
 // launches it), inside one march bracket, then the post-pass as behind any march.  The ring cell counts the re-march only.
-int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring) {
+// rot_c, rot_s: the turn of `cam` from the build camera (bhr_raymap_render_view; 1, 0 for bhr_raymap_render).  The fix kernel
+// marches the overflow pixels from `cam`, the frame's own camera.
+int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, float rot_c = 1.0f, float rot_s = 0.0f) {
     bhr_frame_slot &f = ctx->slots[k];
     const bhr_raymap &rm = *ctx->raymap;
     BHR_TRY(bhr_frame_begin(ctx, flags));
     ctx->ada_frame = 0;
     const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ false, /* ss */ 1};
-    BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0));
+    BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, rot_c, rot_s));
     const bhr_march_part part = {nullptr, 0, /* first */ 0, /* last */ 1, BHR_MATH_STRICT, /* repair */ 2, rm.a.over_count, rm.a.over_list, rm.over_cap};
     BHR_TRY(bhr_launch_march(ctx, call, &part));       // records the ring slot's march-end event
     f.march_done = ctx->ring_ev[ring * 3 + 1];
@@ -997,6 +999,17 @@ int32_t bhr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
     cam.t_offset = t_offset;
     const uint32_t fl = flags | BHR_FORCE_STRICT | (ctx->raymap->diff ? 0u : BHR_SKIP_DIFFERENTIALS);
     return frame_on_next_slot(ctx, fl, false, [&](int k, int ring) { return raymap_on_slot(ctx, &cam, fl, k, ring); });
+}
+
+// A frame from the ray map seen from the build camera turned about z (include/bhr.h): bhr_raymap_render's frame in every other
+// respect -- slot, timing ring, counters, post-pass and consumers.
+int32_t bhr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
+    float rot_c = 1.0f, rot_s = 0.0f;
+    BHR_TRY(bhr_raymap_check_render_view(ctx, cam, flags, &rot_c, &rot_s));
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    const bhr_camera view = *cam;
+    const uint32_t fl = flags | BHR_FORCE_STRICT | (ctx->raymap->diff ? 0u : BHR_SKIP_DIFFERENTIALS);
+    return frame_on_next_slot(ctx, fl, false, [&](int k, int ring) { return raymap_on_slot(ctx, &view, fl, k, ring, rot_c, rot_s); });
 }
 
 int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out) {

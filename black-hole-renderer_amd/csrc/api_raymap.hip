@@ -1,5 +1,6 @@
 // api_raymap.hip -- the ray map's entry points (include/bhr.h): build, read, info, free, and the refusals of
-// bhr_raymap_render (the frame itself is launched from api.hip, next to bhr_render: it takes a frame slot like any other).
+// bhr_raymap_render and bhr_raymap_render_view (the frames themselves are launched from api.hip, next to bhr_render: they take
+// a frame slot like any other).
 // The kernels are march_raymap.hip's, their launchers march_launch.hip's.
 #include <math.h>
 #include <string.h>
@@ -78,6 +79,51 @@ int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
         return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
     if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no ray map has been built (bhr_raymap_build)");
     return check_context(ctx, "bhr_raymap_render", BHR_ERR_STATE);
+}
+
+// bhr_raymap_render_view's refusals, in binary64 and before anything is launched: the disk is not tilted, and `cam` is the
+// build camera turned rigidly about z -- same height, pitch and escape radius, same distance from the axis, and right / up /
+// forward the build's turned by the angle between the two positions in the xy plane.  On the axis build_camera takes a
+// fallback basis that does not turn with the position: refused.
+int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, float *rot_c, float *rot_s) {
+    const char *who = "bhr_raymap_render_view";
+    if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
+        return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
+    if (!isfinite(cam->t_offset)) return bhr_fail(BHR_ERR_INVALID, "%s: t_offset is not finite", who);
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "%s: needs a whole-frame context (rows %d of %d)", who, ctx->rows, ctx->cfg.height);
+    if (ctx->cfg.disk_tilt_deg != 0.0f)
+        return bhr_fail(BHR_ERR_INVALID, "%s: the disk is tilted by %g degrees; a turn about z is a symmetry of an untilted disk only", who,
+                        (double)ctx->cfg.disk_tilt_deg);
+    if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no ray map has been built (bhr_raymap_build)", who);
+    BHR_TRY(check_context(ctx, who, BHR_ERR_STATE));
+    const bhr_camera &b = ctx->raymap->cam;
+    if (!(cam->pos[2] == b.pos[2] && cam->pixel_width == b.pixel_width && cam->pixel_height == b.pixel_height && cam->r_escape == b.r_escape))
+        return bhr_fail(BHR_ERR_INVALID, "%s: the camera's height, pixel pitch or escape radius (%g, %g x %g, %g) is not the build's (%g, %g x %g, %g)", who,
+                        (double)cam->pos[2], (double)cam->pixel_width, (double)cam->pixel_height, (double)cam->r_escape, (double)b.pos[2],
+                        (double)b.pixel_width, (double)b.pixel_height, (double)b.r_escape);
+    const double bx = b.pos[0], by = b.pos[1], cx = cam->pos[0], cy = cam->pos[1];
+    const double rb = sqrt(bx * bx + by * by), rc = sqrt(cx * cx + cy * cy);
+    if (!(rb >= 1e-6 && rc >= 1e-6))
+        return bhr_fail(BHR_ERR_INVALID, "%s: a camera on the z axis (distance %g, the build's %g) has no turn about it", who, rc, rb);
+    if (!(fabs(rc - rb) <= 1e-5 * rb))
+        return bhr_fail(BHR_ERR_INVALID, "%s: the camera is %.9g from the z axis, the build's %.9g: not a turn of it", who, rc, rb);
+    const double angle = atan2(bx * cy - by * cx, bx * cx + by * cy);
+    const double c = cos(angle), s = sin(angle);
+    const float *have[3] = {cam->right, cam->up, cam->forward};
+    const float *from[3] = {b.right, b.up, b.forward};
+    const char *names[3] = {"right", "up", "forward"};
+    for (int v = 0; v < 3; ++v) {
+        const double want[3] = {c * from[v][0] - s * from[v][1], s * from[v][0] + c * from[v][1], (double)from[v][2]};
+        for (int k = 0; k < 3; ++k)
+            if (!(fabs((double)have[v][k] - want[k]) <= 1e-5))
+                return bhr_fail(BHR_ERR_INVALID, "%s: the camera's %s[%d] is %.9g, the build's turned by %.9g rad has %.9g: not a turn of it", who, names[v],
+                                k, (double)have[v][k], angle, want[k]);
+    }
+    *rot_c = (float)c;
+    *rot_s = (float)s;
+    return BHR_OK;
 }
 
 extern "C" {

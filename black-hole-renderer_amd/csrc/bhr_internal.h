@@ -158,7 +158,8 @@ enum bhr_march_kernel {
     BHR_MK_DETECT,        // adaptive_detect_kernel: lists the output pixels whose neighbours differ             strict
     // the ray map (march_raymap.hip)
     BHR_MK_RAYMAP_BUILD,  // raymap_build_kernel<diff>: marches a view and records what the march finds          raymap
-    BHR_MK_RAYMAP_SHADE,  // raymap_shade_kernel<diff>: a frame from the records and the current scene           raymap
+    BHR_MK_RAYMAP_SHADE,  // raymap_shade_kernel<diff, false>: a frame from the records and the current scene    raymap
+    BHR_MK_RAYMAP_SHADE_ROT,  // raymap_shade_kernel<diff, true>: the same with the records turned about z       raymap
 };
 
 // The ray map as its two kernels see it (march_raymap.hip): second kernel argument, behind the march's own block.  Planar: every
@@ -174,6 +175,7 @@ struct BhrRayMapArgs {
     unsigned long long *stats;   // [0] crossings stored
     int32_t slots, comps;
     int64_t plane;               // rows W
+    float rot_c, rot_s;          // the rotated shade kernel only: cosine and sine of the turn about z (bhr_raymap_render_view)
 };
 
 // Kernel argument block of adaptive_detect_kernel (march_strict.hip).
@@ -547,9 +549,12 @@ void bhr_shutter_free(bhr_ctx *ctx);                                 // the timi
 // into the context's scalar cell); shade: the map's pixels under the scene as it is and cam's t_offset into the active slot's
 // layers -- the pixels on the overflow list are left to the fix kernel (bhr_launch_march with a repair == 2 part over that list)
 int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m);
-int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff);
+// rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
+int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f);
 // api_raymap.hip: the refusals of bhr_raymap_render (nothing launched); the map's flags for the march launcher; release
 int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
+// ... and of bhr_raymap_render_view, which also gives the cosine and sine of cam's turn from the build camera (binary64, rounded once)
+int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, float *rot_c, float *rot_s);
 void bhr_raymap_release(bhr_ctx *ctx);
 void bhr_grade_free(bhr_ctx *ctx);                                   // grade.hip: the timing events
 void bhr_population_free(bhr_ctx *ctx);                              // lifecycle.hip

@@ -426,7 +426,7 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
 }
 
 // ---- the ray map (march_raymap.hip; api_raymap.hip owns the map) ------------------------------------------------------------------
-// Both kernels take the march's argument block of the k = 1 strict frame and the map as a second argument.
+// The kernels take the march's argument block of the k = 1 strict frame and the map as a second argument.
 int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m) {
     const hipStream_t stream = ctx->stream;
     const bhr_march_call call = {cam, flags | BHR_FORCE_STRICT, stream, /* slot */ -1, false, false, /* ss */ 1, false};
@@ -452,18 +452,23 @@ int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     return BHR_OK;
 }
 
-int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff) {
+// rot_c, rot_s: the turn about z of call.cam from the map's build camera (bhr_raymap_render_view); 1, 0 is no turn and takes the
+// kernel without one, whose frame is the strict frame bit for bit.
+int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c, float rot_s) {
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no skybox set (bhr_set_skybox)");
     if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no disk texture set (bhr_set_disk_texture)");
     BhrMarchArgs a;
     march_args(ctx, call, nullptr, 1, false, a);
     if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5))
         return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: the map does not fit the frame");
-    const void *fn = bhr_march_kernel_raymap(BHR_MK_RAYMAP_SHADE, diff, 0);
+    const bool turned = !(rot_c == 1.0f && rot_s == 0.0f);
+    const void *fn = bhr_march_kernel_raymap(turned ? BHR_MK_RAYMAP_SHADE_ROT : BHR_MK_RAYMAP_SHADE, diff, 0);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no shade kernel in this library");
     // the frame's march bracket opens here; the overflow launch behind this one (bhr_launch_march, last part) closes it
     BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
     BhrRayMapArgs mm = m;
+    mm.rot_c = rot_c;
+    mm.rot_s = rot_s;
     void *args[] = {&a, &mm};
     (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
     BHR_HIP(hipGetLastError());

@@ -1,4 +1,5 @@
-// march_raymap.hip -> march_raymap.o: the ray map's two kernels, and nothing else, in a strict object of their own
+// march_raymap.hip -> march_raymap.o: the ray map's kernels (build, shade, shade turned about z), and nothing else, in a strict
+// object of their own
 // (-ffp-contract=off, no fast-math, the ILP-first scheduler).  They are made of the strict march's device functions --
 // Ray<DIFF, 0>, Pending, shade_hit, sample_skybox, store_pixel (ray_strict.h, march_device.h).
 //
@@ -11,6 +12,14 @@
 // the strict march runs, in an object without contraction or re-association, so the frame is the strict frame bit for bit.
 // A pixel with more crossings than slots is on the overflow list; the shade kernel leaves it alone and march_fix_kernel
 // (march_strict_ilp.o) re-marches it in the same frame.
+//
+// raymap_shade_kernel<DIFF, true> shades the map seen from the build camera turned rigidly about the z axis
+// (bhr_raymap_render_view; an orbit frame).  With a disk that is not tilted that turn is a symmetry of everything a ray's path
+// depends on -- the hole, the disk plane z = 0, its two radii, the escape sphere -- so the rays of the turned view are the
+// stored rays turned: the kernel turns the xy parts of hit point, to_cam, the hit differentials and the escape direction by
+// (c, s) = (m.rot_c, m.rot_s) and shades them with the same device functions.  Two products and a sum per component (no
+// contraction in this object).  Such a frame is the strict march of the BUILD view's rays, not bit for bit the strict frame of
+// the turned view; the launcher takes <DIFF, false> for c = 1, s = 0.
 #include "ray_strict.h"
 
 namespace {
@@ -91,9 +100,17 @@ __device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool 
     dk[2] = fminf(fmaxf(sh.accum.z, 0.0f), 1.0f);
 }
 
+// x' = c x - s y, y' = s x + c y
+__device__ __forceinline__ void turn_xy(float c, float s, float &x, float &y) {
+    const float xr = c * x - s * y, yr = s * x + c * y;
+    x = xr;
+    y = yr;
+}
+
 // One lane per pixel, an 8x8 tile per wave as in the march (texture locality, and store_pixel's packed layout is per tile);
 // tiles in row-major order: every lane does about the same work.
-template <bool DIFF>
+// ROT: the records are turned about z by (m.rot_c, m.rot_s) before they are shaded (the head of this file).
+template <bool DIFF, bool ROT>
 __global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
     const int tile = wave_slot();
     if (tile >= a.n_tiles) return;
@@ -108,17 +125,31 @@ __global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRa
     sh.accum = mk(0, 0, 0);
     sh.alpha_total = 0.0f;
     sh.unsure = 0;
+    // The turn's cosine and sine stay scalar operands.  A VALU instruction with an SGPR operand issues at half rate,
+    // but there are 8 (16 with differentials) such products per crossing beside the ~700 instructions of shade_hit, and 4 for
+    // the sky; copied into two vector registers once, the plain kernel goes from 79 to 81 VGPRs and loses a wave per SIMD
+    // (6 -> 5), as scalars both instantiations keep the registers of the kernels without a turn (79 / 76 VGPRs, 6 waves).
+    const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;
     for (int c = 0; c < count; ++c) {
         const float *q = m.hits + (size_t)c * m.comps * (size_t)m.plane + pix;
         const size_t p = (size_t)m.plane;
-        const float hx = q[0], hy = q[p];
-        const V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
+        float hx = q[0], hy = q[p];
+        V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
         float dxx = 0.0f, dxy = 0.0f, dyx = 0.0f, dyy = 0.0f;
         if (DIFF) { dxx = q[5 * p]; dxy = q[6 * p]; dyx = q[7 * p]; dyy = q[8 * p]; }
+        if (ROT) {
+            turn_xy(rc, rs, hx, hy);
+            turn_xy(rc, rs, to_cam.x, to_cam.y);
+            if (DIFF) {
+                turn_xy(rc, rs, dxx, dxy);           // d(hit x, hit y) / d(pixel x)
+                turn_xy(rc, rs, dyx, dyy);           // d(hit x, hit y) / d(pixel y)
+            }
+        }
         shade_hit<DIFF, 0>(a, sh, hx, hy, to_cam, dxx, dxy, dyx, dyy);
     }
     const bool esc = m.status[pix] == 1;
-    const V3 dir = mk(m.dir[pix], m.dir[(size_t)m.plane + pix], m.dir[2 * (size_t)m.plane + pix]);
+    V3 dir = mk(m.dir[pix], m.dir[(size_t)m.plane + pix], m.dir[2 * (size_t)m.plane + pix]);
+    if (ROT) turn_xy(rc, rs, dir.x, dir.y);
     float bk[3], dk[3];
     raymap_pixel_values(a, esc, dir, sh, bk, dk);
     store_pixel(a, i, j, a.width, bk, dk);
@@ -131,7 +162,8 @@ const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss
     (void)ss;
     switch (k) {
     case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_kernel<true> : (const void *)raymap_build_kernel<false>;
-    case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_kernel<true> : (const void *)raymap_shade_kernel<false>;
+    case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_kernel<true, false> : (const void *)raymap_shade_kernel<false, false>;
+    case BHR_MK_RAYMAP_SHADE_ROT: return diff ? (const void *)raymap_shade_kernel<true, true> : (const void *)raymap_shade_kernel<false, true>;
     default: return nullptr;
     }
 }

@@ -282,6 +282,31 @@ def check_ray_map(ray_map: bool, orbit: bool = False, shutter: float = 0.0, supe
         raise ValueError("a ray map lives on one GPU: --ray_map does not combine with --gpus > 1 or several ranks")
 
 
+def check_orbit_map(orbit_map: bool, video: bool = True, orbit: bool = True, ray_map: bool = False, disk_tilt: float = 0.0,
+                    shutter: float = 0.0, supersample=1, disk_model: str = "texture", gpus: int = 1, world: int = 1) -> None:
+    """What an orbit video from ONE ray map takes: --video --orbit, a disk that is not tilted (the orbit's turn about z is then
+    a symmetry of everything a ray's path depends on), an instantaneous exposure, one ray per pixel, the texture disk source,
+    one GPU -- and not --ray_map, which is the map of a camera that stands still.  Raises ValueError before any device work."""
+    if not orbit_map:
+        return
+    if not video:
+        raise ValueError("--orbit_map needs --video: it is the ray map of an orbit video")
+    if not orbit:
+        raise ValueError("--orbit_map needs --orbit: a camera that stands still takes --ray_map")
+    if ray_map:
+        raise ValueError("--orbit_map does not combine with --ray_map: that is the map of a camera that stands still")
+    if disk_tilt != 0:
+        raise ValueError("the orbit is a symmetry of an untilted disk only: --orbit_map needs --disk_tilt 0")
+    if shutter > 0:
+        raise ValueError("shutter frames are marched: --orbit_map does not combine with --shutter")
+    if supersample not in (None, 1):
+        raise ValueError("a ray map holds one ray per pixel: --orbit_map does not combine with --supersample > 1")
+    if disk_model != "texture":
+        raise ValueError("a ray map shades the disk texture: --orbit_map does not combine with --disk_model v2 / v2_volume")
+    if gpus != 1 or world != 1:
+        raise ValueError("a ray map lives on one GPU: --orbit_map does not combine with --gpus > 1 or several ranks")
+
+
 def _lib_max_png_width(bit_depth: int = 8) -> int:
     from . import _lib
     lib = _lib.load()
@@ -365,7 +390,7 @@ def check_shutter(shutter, shutter_samples) -> None:
 
 
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
-                    bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False) -> dict:
+                    bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -383,6 +408,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(tonemap=grade["tonemap"], exposure=grade["exposure"], white=grade["white"], transfer=grade["transfer"])
     if ray_map:
         params.update(ray_map=True)
+    if orbit_map:
+        params.update(orbit_map=True)
     return params
 
 
@@ -418,7 +445,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  video_stream: str = "auto", stats: Optional[dict] = None, supersample: Optional[int] = None,
                  supersample_threshold: Optional[float] = None, video_codec: str = "auto", video_quality: int = 90,
                  bit_depth: int = 8, dither: str = "none", shutter: float = 0.0, shutter_samples: int = 8,
-                 grade: Optional[dict] = None, ray_map: bool = False, **_deprecated_kwargs) -> None:
+                 grade: Optional[dict] = None, ray_map: bool = False, orbit_map: bool = False, **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -467,11 +494,25 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     The frames are the STRICT arithmetic's whatever the renderer's ``math``: byte for byte those of a math="strict" run
     without the flag.  Refused with ValueError, before any device work, together with ``orbit``, ``shutter > 0``, a
     supersampling factor other than 1, a Disk V2 source or several ranks.  The progress record carries ``ray_map`` when it
-    is set, and a resume with the other setting starts over."""
+    is set, and a resume with the other setting starts over.
+
+    ``orbit_map=True`` (with ``orbit``, a disk that is not tilted): ONE ray map serves the whole orbit.  The orbit turns the
+    camera rigidly about z, which is a symmetry of the hole, the untilted disk and the escape sphere, so the rays of frame f are
+    the rays of frame 0 turned by the orbit angle.  The map is built once for orbit_position(static_cam_pos, 0, ...) and frame f
+    is shaded from it turned to orbit_position(static_cam_pos, f, ...) (render_from_ray_map_async(cam_pos=...)).  Frame 0 is
+    byte for byte the math="strict" frame; a later frame is the strict march of the SYMMETRIC rays, not byte-identical to the
+    marched frame of its view: as far from it as two strict marches of symmetric views are from each other (f32 rounding of
+    the march, per-channel RMSE of a few 1e-5).  Refused with ValueError, before any device work, without ``orbit``, together
+    with ``ray_map``, ``shutter > 0``, a tilted disk, a supersampling factor other than 1, a Disk V2 source or several ranks.
+    The progress record carries ``orbit_map`` when it is set, and a resume with the other setting starts over."""
     check_shutter(shutter, shutter_samples)
     grade = check_grade(grade)
     if grade is not None:
         grade["keep_hdr"] = False
+    if orbit_map:
+        check_orbit_map(orbit_map, True, orbit, ray_map, renderer.disk_tilt, shutter,
+                        renderer.supersample if supersample is None else supersample,
+                        "texture" if getattr(renderer, "_dv2", None) is None else "v2", 1, world)
     if ray_map:
         check_ray_map(ray_map, orbit, shutter, renderer.supersample if supersample is None else supersample,
                       "texture" if getattr(renderer, "_dv2", None) is None else "v2", 1, world)
@@ -491,7 +532,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     submitted: List[int] = []
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
     params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither,
-                             shutter, shutter_samples, grade, ray_map)
+                             shutter, shutter_samples, grade, ray_map, orbit_map)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -582,6 +623,11 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         renderer.build_ray_map(static_cam_pos, fov)     # the one march of the video
         info = renderer.ray_map_info()
         print(f"  ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
+    if orbit_map:
+        # the orbit's radius is |pov|, not the pov's xy norm: frame 0 of the orbit, not the pov itself
+        renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees), fov)     # the one march of the video
+        info = renderer.ray_map_info()
+        print(f"  orbit ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
     t_loop0 = time.time()                               # ``stats`` (bench.py): the one-off set-up apart from the frame loop
 
     for frame in range(n_frames):
@@ -600,6 +646,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             renderer.render_shutter_async(positions, fov, [(u - frame) * disk_rotation_speed for u in times])
         elif ray_map:
             renderer.render_from_ray_map_async(frame=0)    # the same frame from the map: shade, no march
+        elif orbit_map:
+            renderer.render_from_ray_map_async(frame=0, cam_pos=cam_pos, fov=fov)    # the map turned to the frame's camera
         else:
             renderer.render_async(cam_pos, fov, frame=0)   # lens flare, when enabled, is applied on the device
         sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))
@@ -622,7 +670,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
 
     frames_written, bytes_written = sink.drain()
     sink.close()
-    if ray_map:
+    if ray_map or orbit_map:
         renderer.free_ray_map()
     if mjpeg:
         renderer.set_outputs(outputs_before)

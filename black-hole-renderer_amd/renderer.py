@@ -477,14 +477,26 @@ class HipRenderer:
         _lib.check(self._lib.bhr_raymap_build(self._ctx, C.byref(cam), _lib.SKIP_DIFFERENTIALS if skip_differentials else 0))
 
     def render_from_ray_map_async(self, frame: int = 0, t_offset: Optional[float] = None, skip_bloom: bool = False,
-                                  lens_flare=None) -> None:
+                                  lens_flare=None, cam_pos=None, fov: Optional[float] = None) -> None:
         """One frame from the ray map under the scene as it is now (bhr_raymap_render): bit for bit the frame
         render_async(cam_pos, fov, frame, math="strict") of the build's view leaves, without marching it again.  The disk is
-        rolled by ``t_offset``, or by ``frame * disk_rotation_speed``; the lens flare as render_async decides it."""
+        rolled by ``t_offset``, or by ``frame * disk_rotation_speed``; the lens flare as render_async decides it.
+
+        With ``cam_pos`` (and ``fov``): the frame seen from that camera, which has to be the build's turned about the z axis
+        (a position of camera.orbit_position) over a disk that is not tilted (bhr_raymap_render_view).  The stored rays are turned
+        with the camera: the frame is the strict march of the build view's rays, NOT bit-identical to
+        render_async(cam_pos, ...) -- as far from it as two strict marches of symmetric views are from each other; at the
+        build's own position it is the frame described above, bit for bit."""
         t = float(frame) * self.disk_rotation_speed if t_offset is None else float(t_offset)
         flags = _lib.SKIP_BLOOM if skip_bloom else 0
         if self.lens_flare if lens_flare is None else lens_flare:
             flags |= _lib.LENS_FLARE
+        if cam_pos is not None:
+            if fov is None:
+                raise ValueError("render_from_ray_map_async: cam_pos needs fov")
+            cam = self.camera_uniforms(cam_pos, fov, frame, t_offset)
+            _lib.check(self._lib.bhr_raymap_render_view(self._ctx, C.byref(cam), flags))
+            return
         _lib.check(self._lib.bhr_raymap_render(self._ctx, t, flags))
 
     def ray_map_info(self) -> dict:

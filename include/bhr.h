@@ -288,7 +288,29 @@ BHR_API int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t
  *   BHR_ERR_INVALID: build or render on a row-block context; build with supersampling or adaptive supersampling on or with a
  *                    Disk V2 source (surface or volume); any other flag bit; a non-finite t_offset; "raymap_slots" outside 1..8
  *                    (refused by bhr_set_option; a BHR_RAYMAP_SLOTS outside it by the build); an unknown plane or a wrong size;
- *   BHR_ERR_NOMEM:   a failed allocation: everything the call allocated is freed again and the context stays usable. */
+ *   BHR_ERR_NOMEM:   a failed allocation: everything the call allocated is freed again and the context stays usable.
+ *
+ * bhr_raymap_render_view(ctx, cam, flags): a frame from the map seen from `cam`, the build camera turned rigidly about the z
+ * axis (the cameras of an orbit: camera.orbit_position), with t_offset = cam->t_offset.  It needs a disk that is not tilted
+ * (bhr_config.disk_tilt_deg == 0): the turn is then a symmetry of everything a ray's path depends on -- the hole, the disk
+ * plane, the two disk radii, the escape sphere -- and in exact arithmetic the ray of pixel (i, j) of `cam` is the ray of pixel
+ * (i, j) of the build camera turned by the same angle.  The shade kernel turns the xy parts of the stored hit points, to_cam
+ * vectors, hit differentials and escape directions by that angle (its cosine and sine computed in binary64 and rounded once)
+ * and shades them as bhr_raymap_render does; the pixels of the overflow list are marched from `cam` by the strict fix kernel
+ * and are the strict frame's bit for bit.  Such a frame is the strict march of the build view's rays, not bit-identical to
+ * bhr_render of `cam`: it is as far from it as two strict marches of symmetric views are from each other (the f32 rounding of
+ * the march; per-channel RMSE of a few 1e-5 for a camera 6 r_s out, single chaotic pixels near the photon ring up to some 1e-2
+ * for a camera 2.6 r_s out).  With `cam` the build camera itself (angle 0) the frame is bhr_raymap_render's bit for bit.  In
+ * every other respect it is a frame like bhr_raymap_render's: frame slot, timing-ring entry, counters, post-pass, sinks, grade,
+ * dither and lens flare; flags BHR_SKIP_BLOOM, BHR_LENS_FLARE.  Asynchronous.
+ * Checked in binary64 before anything is launched: pos[2], pixel_width, pixel_height and r_escape equal the build camera's; the
+ * distance of pos from the z axis is at least 1e-6 (on the axis the camera basis does not turn with the position) and equals
+ * the build's within 1e-5 relative; right, up and forward each equal the build's turned by the angle between the two positions
+ * in the xy plane, within 1e-5 absolute.
+ * Refusals, with nothing launched and the context as it was --
+ *   BHR_ERR_INVALID: ctx or cam NULL; a tilted disk; a camera that is no such turn of the build's; any other flag bit; a
+ *                    non-finite t_offset; a row-block context;
+ *   BHR_ERR_STATE:   everything bhr_raymap_render refuses with it. */
 #define BHR_RAYMAP_STEPS 0
 #define BHR_RAYMAP_STATUS 1
 #define BHR_RAYMAP_ESCAPE_DIR 2
@@ -306,6 +328,7 @@ typedef struct {
 } bhr_raymap_info;
 BHR_API int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
 BHR_API int32_t bhr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
+BHR_API int32_t bhr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
 BHR_API int32_t bhr_raymap_read(bhr_ctx *ctx, int32_t plane, void *out, int64_t bytes);
 BHR_API int32_t bhr_raymap_get_info(bhr_ctx *ctx, bhr_raymap_info *out);
 BHR_API int32_t bhr_raymap_free(bhr_ctx *ctx);
