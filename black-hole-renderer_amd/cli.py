@@ -109,6 +109,14 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "of the symmetric rays, not byte-identical to the marched frame of that view: as far from it as two strict "
                         "marches of symmetric views are from each other.  Not with --ray_map, --shutter, --supersample > 1, "
                         "--disk_model v2 / v2_volume or --gpus > 1")
+    p.add_argument("--shutter_map", action="store_true",
+                   help="--video --shutter S: motion blur from ONE ray map.  The view is marched once (frame 0's under --orbit) and "
+                        "every sample of every exposure is shaded from that map -- the disk's roll and, under --orbit, the camera's "
+                        "turn about z are what a ray map leaves free -- and averaged on the device; no sample is marched.  The bg "
+                        "and disk layers are the strict arithmetic's whatever --math says (the bloom follows --math): with a camera "
+                        "that stands still and --math strict the frames are byte-identical to the marched --shutter frames, under "
+                        "--orbit they are the means of --orbit_map frames.  Not with --ray_map, "
+                        "--orbit_map, --orbit together with --disk_tilt, --supersample > 1, --disk_model v2 / v2_volume or --gpus > 1")
     p.add_argument("--passes", type=str, default=None, metavar="PATH.npz",
                    help="still images: also write the view's geometry passes (per pixel: steps, ray fate, escape direction, disk "
                         "crossings and hit points, from a ray map of the view) and the frame's bg / disk / blur layers as a "
@@ -128,6 +136,23 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    if args.shutter_map:
+        if not args.video:
+            p.error("--shutter_map needs --video: it is the ray map of a motion-blurred video")
+        if not args.shutter > 0:
+            p.error("--shutter_map needs --shutter > 0: an instantaneous exposure takes --ray_map or --orbit_map")
+        if args.ray_map:
+            p.error("--shutter_map does not combine with --ray_map: that is the map of an instantaneous exposure")
+        if args.orbit_map:
+            p.error("--shutter_map does not combine with --orbit_map: that is the map of an instantaneous exposure")
+        if args.orbit and args.disk_tilt != 0:
+            p.error("--shutter_map with --orbit needs --disk_tilt 0: the orbit is a symmetry of an untilted disk only")
+        if args.supersample != 1:
+            p.error("--shutter_map does not combine with --supersample other than 1: a ray map holds one ray per pixel")
+        if args.disk_model != "texture":
+            p.error("--shutter_map does not combine with --disk_model other than texture: a ray map shades the disk texture")
+        if args.gpus != 1:
+            p.error("--shutter_map does not combine with --gpus other than 1: a ray map lives on one GPU")
     if args.orbit_map:
         if not args.video:
             p.error("--orbit_map needs --video: it is the ray map of an orbit video")
@@ -278,7 +303,8 @@ def main(argv=None) -> int:
                              png_level=(drivers.DEVICE if args.png_encoder == "device" else drivers.VIDEO_LEVEL),
                              video_codec=args.video_codec, video_quality=args.video_quality, bit_depth=args.bit_depth,
                              dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples,
-                             grade=grade_from_args(args), ray_map=args.ray_map, orbit_map=args.orbit_map)
+                             grade=grade_from_args(args), ray_map=args.ray_map, orbit_map=args.orbit_map,
+                             shutter_map=args.shutter_map)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent

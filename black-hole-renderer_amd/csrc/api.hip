@@ -100,6 +100,7 @@ static void read_options(bhr_options *o) {
     { const char *e = getenv("BHR_GROUP_SCHEDULE"); o->group_schedule = e && e[0] ? (e[0] == 's' ? 0 : 1) : -1; }
     o->png16_menu = num("BHR_PNG16_MENU", 1) != 0;
     o->shutter_timing = num("BHR_SHUTTER_TIMING", 0) != 0;
+    o->raymap_shutter_fused = num("BHR_RAYMAP_SHUTTER_FUSED", 1) != 0;
     o->grade_timing = num("BHR_GRADE_TIMING", 0) != 0;
 }
 
@@ -830,6 +831,42 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     return post_on_slot(ctx, flags, k, ring);
 }
 
+// A shutter frame from the context's ray map on slot k (bhr_raymap_render_shutter): the mean of n frames from the map, then the
+// post-pass on the resolved layers as behind shutter_on_slot's last accumulation.  Two routes to the same bits.  Fused (a map
+// without overflow pixels, option "raymap_shutter_fused" not 0, n > 1): one launch shades every pixel under all n samples and
+// stores the mean.  Unfused: shutter_on_slot with a map frame in place of each march -- the shade launch and the strict fix
+// launch over the overflow list as raymap_on_slot issues them, as a skip-bloom call, then the accumulation launch; a later
+// sample keeps the frame's march-start event and the march-end event is recorded once behind the last accumulation.
+int32_t raymap_shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, const BhrShutterArgs &smp, bool turned, uint32_t flags, int k, int ring) {
+    bhr_frame_slot &f = ctx->slots[k];
+    const bhr_raymap &rm = *ctx->raymap;
+    const int n = smp.n;
+    // the layers are the strict arithmetic's; the post-pass on the resolved layers is the one bhr_bloom would run on them in this
+    // context -- the context's arithmetic decides its kernels (exact f32 under strict, split f16 under fast / hybrid)
+    BHR_TRY(bhr_frame_begin(ctx, flags & ~(uint32_t)BHR_FORCE_STRICT));
+    ctx->ada_frame = 0;
+    ctx->shutter_ev_n = 0;            // option "shutter_timing": the fused route has no accumulation launch to bracket
+    if (n > 1 && rm.overflow_pixels == 0 && ctx->opt.raymap_shutter_fused) {
+        const bhr_march_call call = {&cams[0], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ 1};
+        BHR_TRY(bhr_launch_raymap_shade_shutter(ctx, call, rm.a, rm.diff != 0, smp, turned));
+    } else {
+        for (int j = 0; j < n; ++j) {
+            const bhr_march_call call = {&cams[j], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ 1,
+                                         /* keep_start */ j > 0};
+            BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, smp.smp[j].c, smp.smp[j].s));
+            const bhr_march_part part = {nullptr, 0, /* first */ 0, /* last */ 1, BHR_MATH_STRICT, /* repair */ 2, rm.a.over_count, rm.a.over_list, rm.over_cap};
+            BHR_TRY(bhr_launch_march(ctx, call, &part));
+            if (n > 1) BHR_TRY(bhr_launch_shutter_accumulate(ctx, j, n));
+        }
+    }
+    BHR_HIP(hipEventRecord(ctx->ring_ev[ring * 3 + 1], f.stream));
+    ctx->march_end_recorded = 1;
+    ctx->counters.rays *= (uint64_t)n;
+    f.march_done = ctx->ring_ev[ring * 3 + 1];
+    if (f.frame_split) BHR_TRY(bhr_launch_bloom_pack(ctx));            // the resolved disk layer -> the H pass's operands, bg + disk
+    return post_on_slot(ctx, flags, k, ring);
+}
+
 // A frame on the context's next frame slot: orders the slot's stream behind the scene stream, points the launchers at the
 // slot, runs `body(slot, ring slot)` and keeps the books (slot rotation, timing ring).  exclusive: slot 0, behind every
 // frame in flight (launches that use per-context scratch).
@@ -1012,6 +1049,17 @@ int32_t bhr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fla
     return frame_on_next_slot(ctx, fl, false, [&](int k, int ring) { return raymap_on_slot(ctx, &view, fl, k, ring, rot_c, rot_s); });
 }
 
+// Motion blur from the ray map (include/bhr.h): one frame as the mean of n frames from the map, no march.  A frame like
+// bhr_raymap_render's in slot, timing ring and calibration; the strict arithmetic, the build's choice of differentials.
+int32_t bhr_raymap_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags) {
+    BhrShutterArgs smp;
+    bool turned = false;
+    BHR_TRY(bhr_raymap_check_render_shutter(ctx, cams, n, flags, &smp, &turned));
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    const uint32_t fl = flags | BHR_FORCE_STRICT | (ctx->raymap->diff ? 0u : BHR_SKIP_DIFFERENTIALS);
+    return frame_on_next_slot(ctx, fl, false, [&](int k, int ring) { return raymap_shutter_on_slot(ctx, cams, smp, turned, fl, k, ring); });
+}
+
 int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_read_layer: bad argument");
     BHR_TRY(use_device(ctx));
@@ -1151,6 +1199,7 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     else if (n == "group_threads") o.group_threads = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "group_schedule") o.group_schedule = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "shutter_timing") o.shutter_timing = v != 0;
+    else if (n == "raymap_shutter_fused") o.raymap_shutter_fused = v != 0;
     else if (n == "grade_timing") o.grade_timing = v != 0;
     else if (n == "raymap_slots") {   // read by the next bhr_raymap_build; the map in memory keeps its own
         if (!(value >= 1.0 && value <= 8.0)) return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: raymap_slots %g (1 .. 8)", value);

@@ -1,8 +1,9 @@
 // api_raymap.hip -- the ray map's entry points (include/bhr.h): build, read, info, free, and the refusals of
-// bhr_raymap_render and bhr_raymap_render_view (the frames themselves are launched from api.hip, next to bhr_render: they take
+// bhr_raymap_render, bhr_raymap_render_view and bhr_raymap_render_shutter (the frames themselves are launched from api.hip, next to bhr_render: they take
 // a frame slot like any other).
 // The kernels are march_raymap.hip's, their launchers march_launch.hip's.
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <vector>
@@ -61,44 +62,11 @@ int32_t check_context(const bhr_ctx *ctx, const char *who, int32_t code) {
     return BHR_OK;
 }
 
-}  // namespace
-
-void bhr_raymap_release(bhr_ctx *ctx) {
-    if (!ctx->raymap) return;
-    free_planes(ctx->raymap);
-    delete ctx->raymap;
-    ctx->raymap = nullptr;
-}
-
-int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
-    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: null ctx");
-    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
-        return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", flags);
-    if (!isfinite(t_offset)) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: t_offset is not finite");
-    if (ctx->rows != ctx->cfg.height)
-        return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
-    if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no ray map has been built (bhr_raymap_build)");
-    return check_context(ctx, "bhr_raymap_render", BHR_ERR_STATE);
-}
-
-// bhr_raymap_render_view's refusals, in binary64 and before anything is launched: the disk is not tilted, and `cam` is the
-// build camera turned rigidly about z -- same height, pitch and escape radius, same distance from the axis, and right / up /
-// forward the build's turned by the angle between the two positions in the xy plane.  On the axis build_camera takes a
-// fallback basis that does not turn with the position: refused.
-int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, float *rot_c, float *rot_s) {
-    const char *who = "bhr_raymap_render_view";
-    if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
-    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
-        return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
-    if (!isfinite(cam->t_offset)) return bhr_fail(BHR_ERR_INVALID, "%s: t_offset is not finite", who);
-    if (ctx->rows != ctx->cfg.height)
-        return bhr_fail(BHR_ERR_INVALID, "%s: needs a whole-frame context (rows %d of %d)", who, ctx->rows, ctx->cfg.height);
-    if (ctx->cfg.disk_tilt_deg != 0.0f)
-        return bhr_fail(BHR_ERR_INVALID, "%s: the disk is tilted by %g degrees; a turn about z is a symmetry of an untilted disk only", who,
-                        (double)ctx->cfg.disk_tilt_deg);
-    if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no ray map has been built (bhr_raymap_build)", who);
-    BHR_TRY(check_context(ctx, who, BHR_ERR_STATE));
-    const bhr_camera &b = ctx->raymap->cam;
+// Shared by bhr_raymap_render_view and bhr_raymap_render_shutter, in binary64: is `cam` the build camera `b` turned rigidly
+// about z -- same height, pitch and escape radius, same distance from the axis, and right / up / forward the build's turned by
+// the angle between the two positions in the xy plane?  On the axis build_camera takes a fallback basis that does not turn with
+// the position: refused.  Gives the turn's cosine and sine, rounded once.
+int32_t turn_of_build(const bhr_camera &b, const bhr_camera *cam, const char *who, float *rot_c, float *rot_s) {
     if (!(cam->pos[2] == b.pos[2] && cam->pixel_width == b.pixel_width && cam->pixel_height == b.pixel_height && cam->r_escape == b.r_escape))
         return bhr_fail(BHR_ERR_INVALID, "%s: the camera's height, pixel pitch or escape radius (%g, %g x %g, %g) is not the build's (%g, %g x %g, %g)", who,
                         (double)cam->pos[2], (double)cam->pixel_width, (double)cam->pixel_height, (double)cam->r_escape, (double)b.pos[2],
@@ -123,6 +91,85 @@ int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32
     }
     *rot_c = (float)c;
     *rot_s = (float)s;
+    return BHR_OK;
+}
+
+}  // namespace
+
+void bhr_raymap_release(bhr_ctx *ctx) {
+    if (!ctx->raymap) return;
+    free_planes(ctx->raymap);
+    delete ctx->raymap;
+    ctx->raymap = nullptr;
+}
+
+int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: null ctx");
+    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", flags);
+    if (!isfinite(t_offset)) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: t_offset is not finite");
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
+    if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no ray map has been built (bhr_raymap_build)");
+    return check_context(ctx, "bhr_raymap_render", BHR_ERR_STATE);
+}
+
+// bhr_raymap_render_view's refusals, before anything is launched: the disk is not tilted, and `cam` is the build camera turned
+// rigidly about z (turn_of_build).
+int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, float *rot_c, float *rot_s) {
+    const char *who = "bhr_raymap_render_view";
+    if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
+        return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
+    if (!isfinite(cam->t_offset)) return bhr_fail(BHR_ERR_INVALID, "%s: t_offset is not finite", who);
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "%s: needs a whole-frame context (rows %d of %d)", who, ctx->rows, ctx->cfg.height);
+    if (ctx->cfg.disk_tilt_deg != 0.0f)
+        return bhr_fail(BHR_ERR_INVALID, "%s: the disk is tilted by %g degrees; a turn about z is a symmetry of an untilted disk only", who,
+                        (double)ctx->cfg.disk_tilt_deg);
+    if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no ray map has been built (bhr_raymap_build)", who);
+    BHR_TRY(check_context(ctx, who, BHR_ERR_STATE));
+    return turn_of_build(ctx->raymap->cam, cam, who, rot_c, rot_s);
+}
+
+// bhr_raymap_render_shutter's refusals (include/bhr.h), before anything is launched.  A sample with the build camera's pose,
+// field for field, is the still camera -- on any disk, turn (1, 0); any other has to pass bhr_raymap_render_view's checks.
+int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned) {
+    const char *who = "bhr_raymap_render_shutter";
+    if (!ctx || !cams) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    if (n < 1 || n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "%s: %d samples (1 .. %d)", who, n, BHR_SHUTTER_MAX_SAMPLES);
+    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
+        return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
+    for (int j = 0; j < n; ++j)
+        if (!isfinite(cams[j].t_offset)) return bhr_fail(BHR_ERR_INVALID, "%s: sample %d: t_offset is not finite", who, j);
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "%s: needs a whole-frame context (rows %d of %d)", who, ctx->rows, ctx->cfg.height);
+    if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no ray map has been built (bhr_raymap_build)", who);
+    BHR_TRY(check_context(ctx, who, BHR_ERR_STATE));
+    const bhr_camera &b = ctx->raymap->cam;
+    memset(smp, 0, sizeof(*smp));
+    *turned = false;
+    for (int j = 0; j < n; ++j) {
+        const bhr_camera &c = cams[j];
+        BhrShutterSample &o = smp->smp[j];
+        o.t = c.t_offset;
+        o.c = 1.0f;
+        o.s = 0.0f;
+        for (int k = 0; k < 3; ++k) o.cp[k] = c.pos[k];
+        bool still = c.pixel_width == b.pixel_width && c.pixel_height == b.pixel_height && c.r_escape == b.r_escape;
+        for (int k = 0; k < 3; ++k)
+            still = still && c.pos[k] == b.pos[k] && c.right[k] == b.right[k] && c.up[k] == b.up[k] && c.forward[k] == b.forward[k];
+        if (still) continue;
+        char sample[64];
+        snprintf(sample, sizeof(sample), "%s: sample %d", who, j);
+        if (ctx->cfg.disk_tilt_deg != 0.0f)
+            return bhr_fail(BHR_ERR_INVALID, "%s: the disk is tilted by %g degrees and the camera is not the build's; a turn about z is a symmetry of an untilted disk only",
+                            sample, (double)ctx->cfg.disk_tilt_deg);
+        BHR_TRY(turn_of_build(b, &c, sample, &o.c, &o.s));
+        *turned = *turned || !(o.c == 1.0f && o.s == 0.0f);
+    }
+    smp->n = n;
+    smp->inv = 1.0f / (float)n;
     return BHR_OK;
 }
 

@@ -160,6 +160,8 @@ enum bhr_march_kernel {
     BHR_MK_RAYMAP_BUILD,  // raymap_build_kernel<diff>: marches a view and records what the march finds          raymap
     BHR_MK_RAYMAP_SHADE,  // raymap_shade_kernel<diff, false>: a frame from the records and the current scene    raymap
     BHR_MK_RAYMAP_SHADE_ROT,  // raymap_shade_kernel<diff, true>: the same with the records turned about z       raymap
+    BHR_MK_RAYMAP_SHUTTER,      // raymap_shade_shutter_kernel<diff, false>: the mean of n such frames, one launch   raymap
+    BHR_MK_RAYMAP_SHUTTER_ROT,  // raymap_shade_shutter_kernel<diff, true>: each sample turned about z by its own angle  raymap
 };
 
 // The ray map as its two kernels see it (march_raymap.hip): second kernel argument, behind the march's own block.  Planar: every
@@ -177,6 +179,20 @@ struct BhrRayMapArgs {
     int64_t plane;               // rows W
     float rot_c, rot_s;          // the rotated shade kernel only: cosine and sine of the turn about z (bhr_raymap_render_view)
 };
+
+// The samples of a shutter frame from the map (bhr_raymap_render_shutter): third argument of raymap_shade_shutter_kernel, behind
+// the map.  By value: the kernel indexes the table with its wave-uniform loop counter, so t, c and s come out of scalar loads.
+struct BhrShutterSample {
+    float t, c, s;               // the sample's t_offset; cosine and sine of its turn about z from the build camera (1, 0: none)
+    float cp[3];                 // its camera position: the g-factor takes the observer's radius from it (march_device.h: apply_g_factor)
+};
+struct BhrShutterArgs {
+    BhrShutterSample smp[BHR_SHUTTER_MAX_SAMPLES];
+    int32_t n;                   // samples, 1 .. BHR_SHUTTER_MAX_SAMPLES
+    float inv;                   // 1.0f / (float)n, rounded once on the host
+};
+static_assert(sizeof(BhrMarchArgs) + sizeof(BhrRayMapArgs) + sizeof(BhrShutterArgs) + 256 < 4096,
+              "raymap_shade_shutter_kernel: explicit and hidden kernel arguments stay under 4096 bytes");
 
 // Kernel argument block of adaptive_detect_kernel (march_strict.hip).
 struct BhrDetectArgs {
@@ -218,6 +234,7 @@ struct bhr_options {
     int32_t group_schedule;     // BHR_GROUP_SCHEDULE: -1 by flags (default), 0 serial, 1 pipelined
     int32_t png16_menu;         // BHR_PNG16_MENU: 1 (default) the 16-bit device PNG codes from its own menu, 0 from the 8-bit one (A/B runs)
     int32_t grade_timing;       // BHR_GRADE_TIMING: 1 a graded frame brackets each launch of its grade stage with HIP events (bhr_debug_read, which = 6); default 0
+    int32_t raymap_shutter_fused;   // BHR_RAYMAP_SHUTTER_FUSED: 1 (default) a shutter frame from a map without overflow pixels is one launch, 0 sample by sample (A/B runs, tests)
     int32_t shutter_timing;     // BHR_SHUTTER_TIMING: 1 a shutter frame brackets each accumulation launch with HIP events (bhr_debug_read, which = 5); default 0
 };
 
@@ -551,10 +568,16 @@ void bhr_shutter_free(bhr_ctx *ctx);                                 // the timi
 int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m);
 // rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
 int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f);
+// all samples of a shutter frame from the map in one launch (raymap_shade_shutter_kernel): the mean of the n frames the launch
+// above would store for (smp[j].t, smp[j].c, smp[j].s), into the active slot's BG / DISK; no packed bloom operands.  Opens the
+// frame's march bracket; the caller closes it.  turned: some sample has a turn other than (1, 0).
+int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrShutterArgs &smp, bool turned);
 // api_raymap.hip: the refusals of bhr_raymap_render (nothing launched); the map's flags for the march launcher; release
 int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
 // ... and of bhr_raymap_render_view, which also gives the cosine and sine of cam's turn from the build camera (binary64, rounded once)
 int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, float *rot_c, float *rot_s);
+// ... and of bhr_raymap_render_shutter, which fills smp (t, c, s per sample, n, 1 / n) and tells whether any sample is turned
+int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned);
 void bhr_raymap_release(bhr_ctx *ctx);
 void bhr_grade_free(bhr_ctx *ctx);                                   // grade.hip: the timing events
 void bhr_population_free(bhr_ctx *ctx);                              // lifecycle.hip

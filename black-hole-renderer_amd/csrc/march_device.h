@@ -238,10 +238,13 @@ __device__ __forceinline__ float4 sample_disk_level(const BhrScene &sc, float hi
 }
 
 // ---- _apply_g_factor (render.py:2439-2516) ----------------------------------
-__device__ __forceinline__ V3 apply_g_factor(const BhrMarchArgs &a, V3 base_color, V3 hit_pos, float hit_r,
+// f: the block the frame's camera position (the observer's radius) is read from -- `a` itself in every march; a shutter frame
+// from the ray map shades one set of records under several cameras and hands over each sample's (march_raymap.hip).  ONLY f.cp
+// may be read through f: that caller sets nothing else in it (see shade_hit).
+__device__ __forceinline__ V3 apply_g_factor(const BhrMarchArgs &a, const BhrMarchArgs &f, V3 base_color, V3 hit_pos, float hit_r,
                                              V3 ray_dir_to_cam) {
     const float rs_f = BHR_RS;
-    V3 cam_pos = ld3(a.cp);
+    V3 cam_pos = ld3(f.cp);
     // |cam| is the same for every hit, so the compiler hoists it out of the march loop and keeps it in a VGPR for the
     // whole march (the strict AA kernel spilled it at 128 VGPRs).  Shading runs a handful of times per ray: recompute.
     asm volatile("" : "+v"(cam_pos.x));
@@ -300,6 +303,9 @@ __device__ __forceinline__ V3 apply_g_factor(const BhrMarchArgs &a, V3 base_colo
     out.y = fminf(fmaxf(out.y, 0.0f), 10.0f);
     out.z = fminf(fmaxf(out.z, 0.0f), 10.0f);
     return out;
+}
+__device__ __forceinline__ V3 apply_g_factor(const BhrMarchArgs &a, V3 base_color, V3 hit_pos, float hit_r, V3 ray_dir_to_cam) {
+    return apply_g_factor(a, a, base_color, hit_pos, hit_r, ray_dir_to_cam);
 }
 
 // Analytic disk source (bhr_set_disk_source, BHR_DISK_V2): emission colour and opacity straight from
@@ -400,9 +406,20 @@ __device__ __forceinline__ Pending<DIFF> park_pop(int &n_pend) {
     n_pend -= 1;
     return h;
 }
+// f: the block the two fields that are a FRAME's own are read from, t_offset and cp (the disk's roll, the observer) -- `a` itself
+// in every march (the overload below).  A shutter frame from the ray map shades one set of records as several frames: it hands
+// over a block that holds each sample's two fields and leaves the kernel's argument block, with the mip tables the lanes index,
+// where it is (march_raymap.hip).
+// ONLY f.t_offset and f.cp may be read through f, here and in apply_g_factor: raymap_shade_shutter_kernel sets those four floats
+// and leaves the rest of its block uninitialised; any other field (f.r_inner, f.sc ...) would be garbage in that kernel alone.
+// f is a BhrMarchArgs and not a two-field type of its own on purpose: read through the same struct type, the two fields keep
+// the access metadata they had as a.t_offset / a.cp, and every existing march kernel compiles to the bytes it had (passing
+// them as a float reference and a pointer was tried: the scalar loads of the strict kernels merged differently and their
+// .text moved).  That identity is the compiler's doing, not a guarantee: after ANY edit to shade_hit, apply_g_factor or their
+// callers re-run tools/code_object_diff.py against the parent build (profiles/raymap_shutter_code_objects.txt is the last run).
 template <bool DIFF, int SRC>
-__device__ __forceinline__ void shade_hit(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam,
-                                          float hdx_x, float hdx_y, float hdy_x, float hdy_y) {
+__device__ __forceinline__ void shade_hit(const BhrMarchArgs &a, const BhrMarchArgs &f, Shade &sh, float hit_x, float hit_y,
+                                          V3 to_cam, float hdx_x, float hdx_y, float hdy_x, float hdy_y) {
     float hit_r = sqrtf(hit_x * hit_x + hit_y * hit_y);
     if (!(a.r_outer >= hit_r && hit_r >= a.r_inner)) return;
     float hit_z = hit_y * a.tan_t;
@@ -438,11 +455,11 @@ __device__ __forceinline__ void shade_hit(const BhrMarchArgs &a, Shade &sh, floa
     // SRC == 1 is a separate kernel instantiation: the binary64 model code (and its registers) never
     // touches the texture kernels
     float4 rgba = SRC == 1 ? disk_v2_rgba(a, hit_x, hit_y)
-                  : SRC == 3 ? sample_disk_level(a.sc, hit_x, hit_y, a.r_inner, a.r_outer, a.t_offset, lod_i, g_mip_lds, a.mip_lds_from)
-                             : sample_disk_level(a.sc, hit_x, hit_y, a.r_inner, a.r_outer, a.t_offset, lod_i);
+                  : SRC == 3 ? sample_disk_level(a.sc, hit_x, hit_y, a.r_inner, a.r_outer, f.t_offset, lod_i, g_mip_lds, a.mip_lds_from)
+                             : sample_disk_level(a.sc, hit_x, hit_y, a.r_inner, a.r_outer, f.t_offset, lod_i);
     float base_alpha = fminf(rgba.w, 0.999f);
     float disk_alpha = 1.0f - powf(1.0f - base_alpha, BHR_DISK_ALPHA_GAIN);
-    V3 col = apply_g_factor(a, mk(rgba.x, rgba.y, rgba.z), mk(hit_x, hit_y, hit_z), hit_r, to_cam);
+    V3 col = apply_g_factor(a, f, mk(rgba.x, rgba.y, rgba.z), mk(hit_x, hit_y, hit_z), hit_r, to_cam);
     float front = 1.0f - sh.alpha_total;
 #if BHR_RAY_STRICT
     sh.accum = mk(sh.accum.x + col.x * disk_alpha * front, sh.accum.y + col.y * disk_alpha * front,
@@ -452,6 +469,11 @@ __device__ __forceinline__ void shade_hit(const BhrMarchArgs &a, Shade &sh, floa
     sh.accum = mk(fmaf(col.x, wgt, sh.accum.x), fmaf(col.y, wgt, sh.accum.y), fmaf(col.z, wgt, sh.accum.z));
 #endif
     sh.alpha_total = 1.0f - front * (1.0f - disk_alpha);
+}
+template <bool DIFF, int SRC>
+__device__ __forceinline__ void shade_hit(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam,
+                                          float hdx_x, float hdx_y, float hdy_x, float hdy_y) {
+    shade_hit<DIFF, SRC>(a, a, sh, hit_x, hit_y, to_cam, hdx_x, hdx_y, hdy_x, hdy_y);
 }
 
 // Finite-thickness Disk V2 (docs/design_ad_v2.md 4.2-4.3, Phase 3 -- specified there, not implemented in

@@ -465,12 +465,40 @@ int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const 
     const void *fn = bhr_march_kernel_raymap(turned ? BHR_MK_RAYMAP_SHADE_ROT : BHR_MK_RAYMAP_SHADE, diff, 0);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no shade kernel in this library");
     // the frame's march bracket opens here; the overflow launch behind this one (bhr_launch_march, last part) closes it
-    BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
+    // (a later sample of a shutter frame from the map keeps the first sample's)
+    if (!call.keep_start) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
     BhrRayMapArgs mm = m;
     mm.rot_c = rot_c;
     mm.rot_s = rot_s;
     void *args[] = {&a, &mm};
     (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
     BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}
+
+// All samples of a shutter frame from the map in one launch (bhr_raymap_render_shutter's fused route): the shade kernel's grid,
+// the march's argument block of call.cam -- the two fields of it that a shade kernel reads of a camera, t_offset and the
+// position, are taken from the samples' table inside the kernel instead -- the map, and that table by value.  The caller closes
+// the march bracket.
+int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrShutterArgs &smp, bool turned) {
+    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: no skybox set (bhr_set_skybox)");
+    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: no disk texture set (bhr_set_disk_texture)");
+    if (smp.n < 1 || smp.n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render_shutter: %d samples (1 .. %d)", smp.n, BHR_SHUTTER_MAX_SAMPLES);
+    BhrMarchArgs a;
+    march_args(ctx, call, nullptr, 1, false, a);
+    if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5))
+        return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: the map does not fit the frame");
+    if (a.diskp) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: the fused launch takes a skip-bloom call (it stores no packed bloom operands)");
+    const void *fn = bhr_march_kernel_raymap(turned ? BHR_MK_RAYMAP_SHUTTER_ROT : BHR_MK_RAYMAP_SHUTTER, diff, 0);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: no shutter shade kernel in this library");
+    BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
+    BhrRayMapArgs mm = m;
+    BhrShutterArgs ss = smp;
+    void *args[] = {&a, &mm, &ss};
+    (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
+    BHR_HIP(hipGetLastError());
+    // no march launch follows: the frame's counter cell (cleared ahead of time, nothing counts into it) and its rays
+    ctx->last_steps_ptr = a.ray_steps;
+    ctx->counters.rays = (uint64_t)a.width * a.rows;
     return BHR_OK;
 }

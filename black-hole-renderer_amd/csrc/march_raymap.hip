@@ -1,5 +1,5 @@
-// march_raymap.hip -> march_raymap.o: the ray map's kernels (build, shade, shade turned about z), and nothing else, in a strict
-// object of their own
+// march_raymap.hip -> march_raymap.o: the ray map's kernels (build, shade, shade turned about z, shade all samples of a shutter
+// frame), and nothing else, in a strict object of their own
 // (-ffp-contract=off, no fast-math, the ILP-first scheduler).  They are made of the strict march's device functions --
 // Ray<DIFF, 0>, Pending, shade_hit, sample_skybox, store_pixel (ray_strict.h, march_device.h).
 //
@@ -20,6 +20,11 @@
 // (c, s) = (m.rot_c, m.rot_s) and shades them with the same device functions.  Two products and a sum per component (no
 // contraction in this object).  Such a frame is the strict march of the BUILD view's rays, not bit for bit the strict frame of
 // the turned view; the launcher takes <DIFF, false> for c = 1, s = 0.
+//
+// raymap_shade_shutter_kernel<DIFF, ROT> is a shutter frame from the map in one launch (bhr_raymap_render_shutter): per pixel,
+// the values raymap_shade_kernel<DIFF, ROT> would store under each sample's (t_offset, c, s), summed on the chip (in LDS, a word per lane and channel) in the order
+// of bhr_render_shutter's mean and multiplied by 1 / n.  It is in this object because the object's flags are what make
+// shade_hit, sample_skybox and turn_xy give the same bits wherever they are inlined.
 #include "ray_strict.h"
 
 namespace {
@@ -155,6 +160,106 @@ __global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRa
     store_pixel(a, i, j, a.width, bk, dk);
 }
 
+// A shutter frame from the map: the mean of the n frames raymap_shade_kernel<DIFF, ROT> stores under the samples
+// (t, c, s, cp) = sh.smp[j], j = 0 .. n - 1 (bhr_raymap_render_shutter; include/bhr.h states the mean).  Same mapping, same grid.
+// The sample loop is the outer one and wave-uniform: sh.smp[j] is indexed by a scalar, so t, c, s and cp come out of scalar
+// loads and stay scalar operands (what keeps the kernel above at its registers).
+// Of the march's argument block the shade path reads two things that are a sample's own: t_offset, and the camera position
+// (the g-factor's observer radius |cp|, which can differ in the last bit between the f32 positions of an orbit).  shade_hit
+// reads both from a second block, which here holds nothing but the sample's two fields out of the table -- scalars; the rest of
+// it is never read and never exists.  A whole private copy of the kernel's block with the fields replaced costs the
+// anti-aliased kernel 472 bytes of scratch per lane, because the mip tables inside it are indexed by the lane's level.
+// A pixel's records, its fate and its escape direction are read again for every sample -- 5 or 9 floats per crossing, the same
+// 32-byte runs per tile row each time, so they come from the cache after the first sample -- instead of being held: up to
+// 8 x 9 registers per lane would take the kernel from 6 waves per SIMD to 3, and the direction alone held across the samples
+// spills two registers of the plain kernel at 6 waves.
+// The six running sums are the only state that lives across samples.  They are kept in LDS, a word per lane and channel
+// (conflict free, as the march's parking slots): touched once per sample beside the ~700 instructions of a shade_hit, and in
+// registers they are what takes the kernel from 6 waves per SIMD to 5 (91 .. 96 VGPRs; 75 .. 80 with them in LDS, under the
+// occupancy hint below, without scratch).  No layer goes through memory between the samples.
+// ROT with c = 1, s = 0 (a sample at the build camera among turned ones) is an exact turn.
+// A pixel on the overflow list is left alone, as above: the launcher takes this kernel for maps without one only.
+__shared__ float g_shutter_acc[6][256];
+template <bool DIFF, bool ROT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void raymap_shade_shutter_kernel(BhrMarchArgs a, BhrRayMapArgs m, BhrShutterArgs sh) {
+    const int tile = wave_slot();
+    if (tile >= a.n_tiles) return;
+    const int lane = threadIdx.x & 63;
+    const int i = (tile % a.tiles_x) * 8 + (lane & 7);
+    const int j = (tile / a.tiles_x) * 8 + (lane >> 3);
+    if (!(i < a.width && j < a.rows)) return;
+    const size_t pix = (size_t)j * a.width + i;
+    const size_t p = (size_t)m.plane;
+    const int count = m.crossings[pix];
+    if (count > m.slots) return;
+    const int t = threadIdx.x;
+    for (int smp = 0; smp < sh.n; ++smp) {
+        // the two fields of the argument block that are a frame's own; shade_hit and apply_g_factor read NOTHING else through
+        // their second block (march_device.h says so at both), and the rest of this one is never set
+        BhrMarchArgs fs;
+        fs.t_offset = sh.smp[smp].t;
+        fs.cp[0] = sh.smp[smp].cp[0];
+        fs.cp[1] = sh.smp[smp].cp[1];
+        fs.cp[2] = sh.smp[smp].cp[2];
+        const float rc = ROT ? sh.smp[smp].c : 1.0f, rs = ROT ? sh.smp[smp].s : 0.0f;
+        Shade shd;                           // as Ray::init leaves it
+        shd.accum = mk(0, 0, 0);
+        shd.alpha_total = 0.0f;
+        shd.unsure = 0;
+        for (int c = 0; c < count; ++c) {
+            const float *q = m.hits + (size_t)c * m.comps * p + pix;
+            float hx = q[0], hy = q[p];
+            V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
+            float dxx = 0.0f, dxy = 0.0f, dyx = 0.0f, dyy = 0.0f;
+            if (DIFF) { dxx = q[5 * p]; dxy = q[6 * p]; dyx = q[7 * p]; dyy = q[8 * p]; }
+            if (ROT) {
+                turn_xy(rc, rs, hx, hy);
+                turn_xy(rc, rs, to_cam.x, to_cam.y);
+                if (DIFF) {
+                    turn_xy(rc, rs, dxx, dxy);
+                    turn_xy(rc, rs, dyx, dyy);
+                }
+            }
+            shade_hit<DIFF, 0>(a, fs, shd, hx, hy, to_cam, dxx, dxy, dyx, dyy);
+        }
+        const bool esc = m.status[pix] == 1;
+        V3 dir = mk(m.dir[pix], m.dir[p + pix], m.dir[2 * p + pix]);
+        if (ROT) turn_xy(rc, rs, dir.x, dir.y);
+        float bk[3], dk[3];
+        raymap_pixel_values(a, esc, dir, shd, bk, dk);
+        {
+#pragma clang fp contract(off)
+            // acc = L_0, then acc = acc + L_j: one f32 addition per channel (smp is wave-uniform)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                g_shutter_acc[k][t] = smp == 0 ? bk[k] : g_shutter_acc[k][t] + bk[k];
+                g_shutter_acc[3 + k][t] = smp == 0 ? dk[k] : g_shutter_acc[3 + k][t] + dk[k];
+            }
+        }
+    }
+    float acc_b[3], acc_d[3];
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            acc_b[k] = g_shutter_acc[k][t];
+            acc_d[k] = g_shutter_acc[3 + k][t];
+            if (sh.n > 1) {
+                acc_b[k] = acc_b[k] * sh.inv;
+                acc_d[k] = acc_d[k] * sh.inv;
+            }
+        }
+    }
+    // six plain stores: the pack kernel makes the split post-pass's operands from the resolved layer, as behind every shutter frame
+    const size_t o = ((size_t)j * a.width + i) * 3;
+    a.bg[o + 0] = acc_b[0];
+    a.bg[o + 1] = acc_b[1];
+    a.bg[o + 2] = acc_b[2];
+    a.disk[o + 0] = acc_d[0];
+    a.disk[o + 1] = acc_d[1];
+    a.disk[o + 2] = acc_d[2];
+}
+
 }  // namespace
 
 // ---- the kernels of this object, by the launcher's names (march_launch.hip); null: not in this object ----------
@@ -164,6 +269,10 @@ const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss
     case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_kernel<true> : (const void *)raymap_build_kernel<false>;
     case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_kernel<true, false> : (const void *)raymap_shade_kernel<false, false>;
     case BHR_MK_RAYMAP_SHADE_ROT: return diff ? (const void *)raymap_shade_kernel<true, true> : (const void *)raymap_shade_kernel<false, true>;
+    case BHR_MK_RAYMAP_SHUTTER:
+        return diff ? (const void *)raymap_shade_shutter_kernel<true, false> : (const void *)raymap_shade_shutter_kernel<false, false>;
+    case BHR_MK_RAYMAP_SHUTTER_ROT:
+        return diff ? (const void *)raymap_shade_shutter_kernel<true, true> : (const void *)raymap_shade_shutter_kernel<false, true>;
     default: return nullptr;
     }
 }

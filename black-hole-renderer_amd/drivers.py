@@ -307,6 +307,29 @@ def check_orbit_map(orbit_map: bool, video: bool = True, orbit: bool = True, ray
         raise ValueError("a ray map lives on one GPU: --orbit_map does not combine with --gpus > 1 or several ranks")
 
 
+def check_shutter_map(shutter_map: bool, shutter: float = 0.5, orbit: bool = False, ray_map: bool = False, orbit_map: bool = False,
+                      disk_tilt: float = 0.0, supersample=1, disk_model: str = "texture", gpus: int = 1, world: int = 1) -> None:
+    """What a motion-blurred video from ONE ray map takes: an open shutter, one ray per pixel, the texture disk source, one GPU,
+    and under --orbit a disk that is not tilted (a camera that stands still takes any disk) -- and neither --ray_map nor
+    --orbit_map, which are the maps of instantaneous exposures.  Raises ValueError before any device work."""
+    if not shutter_map:
+        return
+    if not shutter > 0:
+        raise ValueError("--shutter_map needs --shutter > 0: an instantaneous exposure takes --ray_map or --orbit_map")
+    if ray_map:
+        raise ValueError("--shutter_map does not combine with --ray_map: that is the map of an instantaneous exposure")
+    if orbit_map:
+        raise ValueError("--shutter_map does not combine with --orbit_map: that is the map of an instantaneous exposure")
+    if orbit and disk_tilt != 0:
+        raise ValueError("the orbit is a symmetry of an untilted disk only: --shutter_map with --orbit needs --disk_tilt 0")
+    if supersample not in (None, 1):
+        raise ValueError("a ray map holds one ray per pixel: --shutter_map does not combine with --supersample > 1")
+    if disk_model != "texture":
+        raise ValueError("a ray map shades the disk texture: --shutter_map does not combine with --disk_model v2 / v2_volume")
+    if gpus != 1 or world != 1:
+        raise ValueError("a ray map lives on one GPU: --shutter_map does not combine with --gpus > 1 or several ranks")
+
+
 def _lib_max_png_width(bit_depth: int = 8) -> int:
     from . import _lib
     lib = _lib.load()
@@ -390,7 +413,8 @@ def check_shutter(shutter, shutter_samples) -> None:
 
 
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
-                    bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False) -> dict:
+                    bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
+                    shutter_map=False) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -410,6 +434,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(ray_map=True)
     if orbit_map:
         params.update(orbit_map=True)
+    if shutter_map:
+        params.update(shutter_map=True)
     return params
 
 
@@ -445,7 +471,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  video_stream: str = "auto", stats: Optional[dict] = None, supersample: Optional[int] = None,
                  supersample_threshold: Optional[float] = None, video_codec: str = "auto", video_quality: int = 90,
                  bit_depth: int = 8, dither: str = "none", shutter: float = 0.0, shutter_samples: int = 8,
-                 grade: Optional[dict] = None, ray_map: bool = False, orbit_map: bool = False, **_deprecated_kwargs) -> None:
+                 grade: Optional[dict] = None, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False,
+                 **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -504,11 +531,26 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     marched frame of its view: as far from it as two strict marches of symmetric views are from each other (f32 rounding of
     the march, per-channel RMSE of a few 1e-5).  Refused with ValueError, before any device work, without ``orbit``, together
     with ``ray_map``, ``shutter > 0``, a tilted disk, a supersampling factor other than 1, a Disk V2 source or several ranks.
-    The progress record carries ``orbit_map`` when it is set, and a resume with the other setting starts over."""
+    The progress record carries ``orbit_map`` when it is set, and a resume with the other setting starts over.
+
+    ``shutter_map=True`` (with ``shutter > 0``): motion blur from ONE ray map.  What differs between the samples of an exposure
+    -- the disk's roll, and under ``orbit`` the camera's turn about z -- is what a map leaves free, so no sample is marched: the
+    map is built once (for orbit_position(static_cam_pos, 0, ...) under ``orbit``, else for ``static_cam_pos``) and every frame is
+    render_shutter_from_ray_map_async of exactly the sample times, positions and t_offsets the marched shutter loop hands
+    render_shutter_async.  The bg and disk layers are the STRICT arithmetic's whatever the renderer's ``math``, the post-pass is
+    the renderer's own (exact f32 under math="strict", split f16 under fast / hybrid).  With a camera that stands still and
+    math="strict" the frames are byte for byte those of the shutter video without the flag; under ``orbit`` they are the means
+    of orbit-map frames (see above).  Refused with ValueError, before any device work, with ``shutter == 0``, together with ``ray_map`` or
+    ``orbit_map``, with ``orbit`` over a tilted disk, a supersampling factor other than 1, a Disk V2 source or several ranks.
+    The progress record carries ``shutter_map`` when it is set, and a resume with the other setting starts over."""
     check_shutter(shutter, shutter_samples)
     grade = check_grade(grade)
     if grade is not None:
         grade["keep_hdr"] = False
+    if shutter_map:
+        check_shutter_map(shutter_map, shutter, orbit, ray_map, orbit_map, renderer.disk_tilt,
+                          renderer.supersample if supersample is None else supersample,
+                          "texture" if getattr(renderer, "_dv2", None) is None else "v2", 1, world)
     if orbit_map:
         check_orbit_map(orbit_map, True, orbit, ray_map, renderer.disk_tilt, shutter,
                         renderer.supersample if supersample is None else supersample,
@@ -532,7 +574,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     submitted: List[int] = []
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
     params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither,
-                             shutter, shutter_samples, grade, ray_map, orbit_map)
+                             shutter, shutter_samples, grade, ray_map, orbit_map, shutter_map)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -628,6 +670,10 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees), fov)     # the one march of the video
         info = renderer.ray_map_info()
         print(f"  orbit ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
+    if shutter_map:
+        renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov)   # the one march of the video
+        info = renderer.ray_map_info()
+        print(f"  shutter ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
     t_loop0 = time.time()                               # ``stats`` (bench.py): the one-off set-up apart from the frame loop
 
     for frame in range(n_frames):
@@ -643,7 +689,11 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         if shutter > 0:
             times = shutter_times(frame, shutter, shutter_samples)
             positions = [orbit_position(static_cam_pos, u, n_frames, orbit_degrees) if orbit else static_cam_pos for u in times]
-            renderer.render_shutter_async(positions, fov, [(u - frame) * disk_rotation_speed for u in times])
+            t_offsets = [(u - frame) * disk_rotation_speed for u in times]
+            if shutter_map:                                # the same samples from the map: shade, no march
+                renderer.render_shutter_from_ray_map_async(t_offsets, positions if orbit else None, fov)
+            else:
+                renderer.render_shutter_async(positions, fov, t_offsets)
         elif ray_map:
             renderer.render_from_ray_map_async(frame=0)    # the same frame from the map: shade, no march
         elif orbit_map:
@@ -670,7 +720,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
 
     frames_written, bytes_written = sink.drain()
     sink.close()
-    if ray_map or orbit_map:
+    if ray_map or orbit_map or shutter_map:
         renderer.free_ray_map()
     if mjpeg:
         renderer.set_outputs(outputs_before)

@@ -499,6 +499,38 @@ class HipRenderer:
             return
         _lib.check(self._lib.bhr_raymap_render(self._ctx, t, flags))
 
+    def render_shutter_from_ray_map_async(self, t_offsets, cam_positions=None, fov: Optional[float] = None, skip_bloom: bool = False,
+                                          lens_flare=None) -> None:
+        """Motion blur from the ray map: one frame as the mean of ``len(t_offsets)`` frames from the map, without a march
+        (bhr_raymap_render_shutter; include/bhr.h states the frame).  Sample j is the map's frame with the disk rolled by
+        ``t_offsets[j]``, seen from ``cam_positions[j]`` -- each the build's position or a turn of it about the z axis over a disk
+        that is not tilted, as render_from_ray_map_async(cam_pos=) takes them -- or, with ``cam_positions=None``, from the build
+        view itself (a camera that stands still, on any disk).  The BG and DISK layers are the f32 means of the samples' in
+        render_shutter_async's order and the strict arithmetic's whatever the renderer's ``math``; the post-pass runs once on them, with
+        the kernels bloom_only() would take in this context (exact f32 under math="strict", split f16 under fast / hybrid).
+        1..64 samples."""
+        t_offsets = list(t_offsets)
+        if cam_positions is not None:
+            cam_positions = list(cam_positions)
+            if len(cam_positions) != len(t_offsets):
+                raise ValueError(f"{len(cam_positions)} camera positions for {len(t_offsets)} t_offsets")
+            if fov is None:
+                raise ValueError("render_shutter_from_ray_map_async: cam_positions needs fov")
+        cams = (_lib.Camera * max(len(t_offsets), 1))()
+        if cam_positions is None:
+            info = _lib.RayMapInfo()       # without a map its camera is zeros, and the call below says that there is none
+            _lib.check(self._lib.bhr_raymap_get_info(self._ctx, C.byref(info)))
+            for j, t in enumerate(t_offsets):
+                cams[j] = info.cam
+                cams[j].t_offset = float(t)
+        else:
+            for j, (pos, t) in enumerate(zip(cam_positions, t_offsets)):
+                cams[j] = self.camera_uniforms(pos, fov, t_offset=t)
+        flags = _lib.SKIP_BLOOM if skip_bloom else 0
+        if self.lens_flare if lens_flare is None else lens_flare:
+            flags |= _lib.LENS_FLARE
+        _lib.check(self._lib.bhr_raymap_render_shutter(self._ctx, cams, len(t_offsets), flags))
+
     def ray_map_info(self) -> dict:
         """The context's ray map (bhr_raymap_get_info): built, diff, slots, width, rows, crossings_stored, overflow_pixels,
         device_bytes, ray_steps of the build, and the build camera's pos / r_escape."""

@@ -310,6 +310,40 @@ BHR_API int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t
  * Refusals, with nothing launched and the context as it was --
  *   BHR_ERR_INVALID: ctx or cam NULL; a tilted disk; a camera that is no such turn of the build's; any other flag bit; a
  *                    non-finite t_offset; a row-block context;
+ *   BHR_ERR_STATE:   everything bhr_raymap_render refuses with it.
+ *
+ * bhr_raymap_render_shutter(ctx, cams, n, flags): motion blur from the map -- one frame as the mean of n frames from the map,
+ * with no march at all.  cams[0 .. n - 1] (1 <= n <= 64) are the samples' cameras, each with its own t_offset.  What differs
+ * between the samples of one exposure is what the map leaves free: the disk's roll (t_offset, an argument of the samplers)
+ * and the orbit camera's turn about z (the turn bhr_raymap_render_view applies to the stored records).  A sample is accepted
+ *   - if its pose equals the build camera's field for field (everything but t_offset), on any disk, tilted or not: the still
+ *     camera, whose turn is (1, 0);
+ *   - else if it passes exactly the checks of bhr_raymap_render_view: the disk is not tilted and the camera is a turn of the
+ *     build camera about z within the tolerances above, checked in binary64; its cosine and sine are computed as there.
+ * For each layer L in {BG, DISK}:
+ *   L_j  is, bit for bit, what bhr_raymap_render_view(ctx, &cams[j], BHR_SKIP_BLOOM) stores for that layer for a turned
+ *        camera, and what bhr_raymap_render(ctx, cams[j].t_offset, BHR_SKIP_BLOOM) stores for a camera with the build pose;
+ *   acc  = L_0, then acc = acc + L_j for j = 1 .. n - 1 in that order, one f32 addition per channel;
+ *   L    = acc * (1.0f / (float)n): the reciprocal rounded to f32 once, the product once, no FMA contraction anywhere
+ * -- bhr_render_shutter's mean, word for word (tests/shutter_ref.py restates it).  For n = 1 this is L_0 itself.  BG and DISK
+ * are the STRICT arithmetic's whatever the context's math_mode.  BLUR and FINAL are what bhr_bloom computes from the resolved
+ * BG and DISK in this context -- its kernels follow the context's arithmetic as bhr_bloom's do: the exact f32 post-pass in a
+ * strict context (the frame is then the strict frame throughout), the split-f16 one in a fast or hybrid context (BHR_SKIP_BLOOM
+ * in flags suppresses them); BHR_LENS_FLARE then adds what bhr_lens_flare adds.  u8 / u16 rows, dither, grade, HDR plane, the
+ * sinks and the y4m stream work on the frame as on any other.
+ * Two routes give these bits.  A map without overflow pixels takes ONE launch (csrc/march_raymap.hip:
+ * raymap_shade_shutter_kernel) that shades a pixel's records under all n (t_offset, cos, sin, camera position) and keeps the
+ * running sums on the chip: no layer goes through memory between the samples.  A map with overflow pixels -- or any map
+ * while option "raymap_shutter_fused" is 0 -- runs, per sample, the shade launch and the strict fix launch over the overflow
+ * list as bhr_raymap_render[_view] issues them, then bhr_render_shutter's accumulation launch (csrc/shutter.hip).
+ * The frame takes the next frame slot like bhr_raymap_render and runs on that slot's stream; one timing-ring entry, its march
+ * bracket from the first shade launch to behind the last launch that writes BG / DISK; it neither counts towards nor runs the
+ * calibration of slot 1's stream.  bhr_counters: rays = n W H, ray_steps the sum of the overflow re-marches' steps (0 for a
+ * map without overflow pixels).  Asynchronous.
+ * Refusals, with nothing launched and the context as it was --
+ *   BHR_ERR_INVALID: ctx or cams NULL; n < 1 or n > 64; a flag bit other than BHR_SKIP_BLOOM / BHR_LENS_FLARE; a non-finite
+ *                    t_offset in any sample; a row-block context; a sample that is neither the build pose nor an admissible
+ *                    turn (a turned camera over a tilted disk included) -- the message names the sample index;
  *   BHR_ERR_STATE:   everything bhr_raymap_render refuses with it. */
 #define BHR_RAYMAP_STEPS 0
 #define BHR_RAYMAP_STATUS 1
@@ -329,6 +363,7 @@ typedef struct {
 BHR_API int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
 BHR_API int32_t bhr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
 BHR_API int32_t bhr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
+BHR_API int32_t bhr_raymap_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags);
 BHR_API int32_t bhr_raymap_read(bhr_ctx *ctx, int32_t plane, void *out, int64_t bytes);
 BHR_API int32_t bhr_raymap_get_info(bhr_ctx *ctx, bhr_raymap_info *out);
 BHR_API int32_t bhr_raymap_free(bhr_ctx *ctx);
@@ -422,6 +457,8 @@ BHR_API int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]);
  *   "grade_timing"    BHR_GRADE_TIMING    1 a graded frame (bhr_set_grade) brackets each launch of its grade stage with a pair of HIP
  *                                         events (bhr_debug_read, which = 6); default 0
  *   "raymap_slots"    BHR_RAYMAP_SLOTS    crossings a ray map keeps per pixel (1..8, default 4); read by bhr_raymap_build
+ *   "raymap_shutter_fused" BHR_RAYMAP_SHUTTER_FUSED 1 (default) bhr_raymap_render_shutter shades all samples of a map without overflow
+ *                                         pixels in one launch, 0 sample by sample with the accumulation launches (the same bits; A/B runs)
  * (bhr_create only: BHR_FRAME_SLOTS.) */
 BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
 /* Diagnostics (tests): the split-f16 post-pass's packed intermediates of the last frame as raw bytes -- which = 0 the H pass's
@@ -429,7 +466,8 @@ BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
  * GP, g0, t_first, n_ty, pbr, GR}; which = 2 the launch order of the last math-hybrid march as int32 tile indices, strict tiles
  * first (geom[0] = tiles in it; bhr_hybrid_info tells how many are strict).  out == NULL or bytes == 0: geometry only.
  * which = 5 (option "shutter_timing"): geom[0] = accumulation launches of the last shutter frame, geom[1] = their summed
- * HIP-event time in nanoseconds.  which = 6 (option "grade_timing"): the same for the launches of the last graded frame's
+ * HIP-event time in nanoseconds (bhr_render_shutter: n for n > 1; bhr_raymap_render_shutter: n on its sample-by-sample route,
+ * 0 on its fused route, which has no accumulation launch).  which = 6 (option "grade_timing"): the same for the launches of the last graded frame's
  * grade stage (csrc/grade.hip: one, or two for a flared frame).
  * Synchronises. */
 BHR_API int32_t bhr_debug_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes, int32_t *geom);
