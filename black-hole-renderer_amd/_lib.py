@@ -69,7 +69,7 @@ class Grade(C.Structure):
 
 class RayMapInfo(C.Structure):
     _fields_ = [("built", C.c_int32), ("diff", C.c_int32), ("slots", C.c_int32), ("width", C.c_int32), ("rows", C.c_int32),
-                ("reserved", C.c_int32), ("crossings_stored", C.c_int64), ("overflow_pixels", C.c_int64),
+                ("supersample", C.c_int32), ("crossings_stored", C.c_int64), ("overflow_pixels", C.c_int64),
                 ("device_bytes", C.c_int64), ("ray_steps", C.c_uint64), ("cam", Camera)]
 
 

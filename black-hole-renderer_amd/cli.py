@@ -100,15 +100,15 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--ray_map", action="store_true",
                    help="--video with a camera that stands still: march the view once, before the loop, and shade every frame "
                         "from that ray map under the frame's texture instead of marching it again.  The frames are the strict "
-                        "arithmetic's whatever --math says.  Not with --orbit, --shutter, --supersample > 1, --disk_model v2 / "
-                        "v2_volume or --gpus > 1")
+                        "arithmetic's whatever --math says.  Not with --orbit, --shutter, --supersample > 1 (a supersampled map takes "
+                        "--map_supersample), --disk_model v2 / v2_volume or --gpus > 1")
     p.add_argument("--orbit_map", action="store_true",
                    help="--video --orbit with --disk_tilt 0: march frame 0's view once and shade every frame of the orbit from "
                         "that one ray map, turned about z to the frame's camera (the orbit is a symmetry of the hole, the untilted "
                         "disk and the escape sphere).  Frame 0 is the strict arithmetic's frame; a later frame is the strict march "
                         "of the symmetric rays, not byte-identical to the marched frame of that view: as far from it as two strict "
-                        "marches of symmetric views are from each other.  Not with --ray_map, --shutter, --supersample > 1, "
-                        "--disk_model v2 / v2_volume or --gpus > 1")
+                        "marches of symmetric views are from each other.  Not with --ray_map, --shutter, --supersample > 1 (a supersampled "
+                        "map takes --map_supersample), --disk_model v2 / v2_volume or --gpus > 1")
     p.add_argument("--shutter_map", action="store_true",
                    help="--video --shutter S: motion blur from ONE ray map.  The view is marched once (frame 0's under --orbit) and "
                         "every sample of every exposure is shaded from that map -- the disk's roll and, under --orbit, the camera's "
@@ -116,7 +116,13 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "and disk layers are the strict arithmetic's whatever --math says (the bloom follows --math): with a camera "
                         "that stands still and --math strict the frames are byte-identical to the marched --shutter frames, under "
                         "--orbit they are the means of --orbit_map frames.  Not with --ray_map, "
-                        "--orbit_map, --orbit together with --disk_tilt, --supersample > 1, --disk_model v2 / v2_volume or --gpus > 1")
+                        "--orbit_map, --orbit together with --disk_tilt, --supersample > 1 (a supersampled map takes --map_supersample), "
+                        "--disk_model v2 / v2_volume or --gpus > 1")
+    p.add_argument("--map_supersample", type=int, default=1, choices=[1, 2, 4, 8], metavar="K",
+                   help="--ray_map, --orbit_map or --shutter_map: the map's own supersampling factor, 1, 2, 4 or 8 (default 1).  The "
+                        "one march of the video marches K x K rays per pixel and keeps their records; every frame shades all of them "
+                        "and resolves each pixel with --supersample's box filter, so the frames are those of --supersample K under "
+                        "--math strict without a march per frame.  Needs one of the three map flags; --supersample itself stays 1")
     p.add_argument("--passes", type=str, default=None, metavar="PATH.npz",
                    help="still images: also write the view's geometry passes (per pixel: steps, ray fate, escape direction, disk "
                         "crossings and hit points, from a ray map of the view) and the frame's bg / disk / blur layers as a "
@@ -136,6 +142,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    if args.map_supersample > 1 and not (args.ray_map or args.orbit_map or args.shutter_map):
+        p.error("--map_supersample needs --ray_map, --orbit_map or --shutter_map: it is a ray map's factor (marched frames take --supersample)")
     if args.shutter_map:
         if not args.video:
             p.error("--shutter_map needs --video: it is the ray map of a motion-blurred video")
@@ -304,7 +312,7 @@ def main(argv=None) -> int:
                              video_codec=args.video_codec, video_quality=args.video_quality, bit_depth=args.bit_depth,
                              dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples,
                              grade=grade_from_args(args), ray_map=args.ray_map, orbit_map=args.orbit_map,
-                             shutter_map=args.shutter_map)
+                             shutter_map=args.shutter_map, map_supersample=args.map_supersample)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent

@@ -448,6 +448,7 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
     ctx->scene_stream = ctx->stream;
     read_options(&ctx->opt);
     { const char *e = getenv("BHR_RAYMAP_SLOTS"); ctx->raymap_slots = e && e[0] ? atoi(e) : 4; }   // outside 1 .. 8: bhr_raymap_build refuses
+    { const char *e = getenv("BHR_RAYMAP_SUPERSAMPLE"); ctx->raymap_ss = e && e[0] ? atoi(e) : 1; }   // not 1, 2, 4 or 8: bhr_raymap_build refuses
     ctx->n_slots = ctx->opt.frame_slots;                 // 2 (default): frames alternate between two slots / streams
     ctx->split_ok = bhr_split_nt(ctx->bloom_R) <= 12;    // the split-f16 bloom's table: radius <= 176 (widths to 8849)
     ctx->out_want = BHR_OUT_F32;
@@ -813,6 +814,11 @@ int32_t shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, int n, uint32_t fl
     return post_on_slot(ctx, flags, k, ring);
 }
 
+// The fix launch of a map frame: the strict fix kernel over the map's overflow list (a grid for the list's capacity).
+bhr_march_part raymap_fix_part(const bhr_raymap &rm) {
+    return {nullptr, 0, /* first */ 0, /* last */ 1, BHR_MATH_STRICT, /* repair */ 2, rm.a.over_count, rm.a.over_list, rm.over_cap};
+}
+
 // A frame from the context's ray map on slot k (bhr_raymap_render): the shade kernel over the stored records, then the strict
 // fix kernel over the map's overflow list (its count is the device's: a grid for the list's capacity, as the hybrid march
 // launches it), inside one march bracket, then the post-pass as behind any march.  The ring cell counts the re-march only.
@@ -823,9 +829,11 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     const bhr_raymap &rm = *ctx->raymap;
     BHR_TRY(bhr_frame_begin(ctx, flags));
     ctx->ada_frame = 0;
-    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ false, /* ss */ 1};
+    // a supersampled map: the call carries the map's factor, so both launches work on the fine frame and the fix launch takes
+    // march_fix_ss_kernel, which resolves the overflow list's whole groups
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ false, /* ss */ rm.ss};
     BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, rot_c, rot_s));
-    const bhr_march_part part = {nullptr, 0, /* first */ 0, /* last */ 1, BHR_MATH_STRICT, /* repair */ 2, rm.a.over_count, rm.a.over_list, rm.over_cap};
+    const bhr_march_part part = raymap_fix_part(rm);
     BHR_TRY(bhr_launch_march(ctx, call, &part));       // records the ring slot's march-end event
     f.march_done = ctx->ring_ev[ring * 3 + 1];
     return post_on_slot(ctx, flags, k, ring);
@@ -846,15 +854,16 @@ int32_t raymap_shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, const BhrSh
     BHR_TRY(bhr_frame_begin(ctx, flags & ~(uint32_t)BHR_FORCE_STRICT));
     ctx->ada_frame = 0;
     ctx->shutter_ev_n = 0;            // option "shutter_timing": the fused route has no accumulation launch to bracket
-    if (n > 1 && rm.overflow_pixels == 0 && ctx->opt.raymap_shutter_fused) {
+    // (a supersampled map always goes sample by sample: there is no fused supersampled kernel, whatever "raymap_shutter_fused" says)
+    if (n > 1 && rm.overflow_pixels == 0 && ctx->opt.raymap_shutter_fused && rm.ss == 1) {
         const bhr_march_call call = {&cams[0], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ 1};
         BHR_TRY(bhr_launch_raymap_shade_shutter(ctx, call, rm.a, rm.diff != 0, smp, turned));
     } else {
         for (int j = 0; j < n; ++j) {
-            const bhr_march_call call = {&cams[j], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ 1,
+            const bhr_march_call call = {&cams[j], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ rm.ss,
                                          /* keep_start */ j > 0};
             BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, smp.smp[j].c, smp.smp[j].s));
-            const bhr_march_part part = {nullptr, 0, /* first */ 0, /* last */ 1, BHR_MATH_STRICT, /* repair */ 2, rm.a.over_count, rm.a.over_list, rm.over_cap};
+            const bhr_march_part part = raymap_fix_part(rm);
             BHR_TRY(bhr_launch_march(ctx, call, &part));
             if (n > 1) BHR_TRY(bhr_launch_shutter_accumulate(ctx, j, n));
         }
@@ -1204,6 +1213,11 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     else if (n == "raymap_slots") {   // read by the next bhr_raymap_build; the map in memory keeps its own
         if (!(value >= 1.0 && value <= 8.0)) return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: raymap_slots %g (1 .. 8)", value);
         ctx->raymap_slots = v;
+    }
+    else if (n == "raymap_supersample") {   // the next map's own factor; the context's bhr_set_supersample stays at 1 for every map call
+        if (!(value == 1.0 || value == 2.0 || value == 4.0 || value == 8.0))
+            return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: raymap_supersample %g (1, 2, 4 or 8)", value);
+        ctx->raymap_ss = v;
     }
     else if (n == "png16_menu") {   // the tables are rebuilt at the next encode; no encode may be running on the old ones
         BHR_TRY(bhr_enter(ctx));

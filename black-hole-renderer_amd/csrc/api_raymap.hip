@@ -3,6 +3,7 @@
 // a frame slot like any other).
 // The kernels are march_raymap.hip's, their launchers march_launch.hip's.
 #include <math.h>
+#include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -19,7 +20,7 @@ void free_planes(bhr_raymap *rm) {
         if (b) (void)hipFree(b);
     memset(&a, 0, sizeof(a));
     rm->built = 0;
-    rm->alloc_slots = rm->alloc_comps = 0;
+    rm->alloc_slots = rm->alloc_comps = rm->alloc_ss = 0;
     rm->over_cap = 0;
     rm->device_bytes = 0;
 }
@@ -53,7 +54,8 @@ int32_t fetch(bhr_ctx *ctx, void *dst, const void *d_src, size_t bytes) {
     return BHR_OK;
 }
 
-// what a context has to be for a map: whole frame, one ray per pixel, the texture source
+// what a context has to be for a map: whole frame, one ray per pixel, the texture source (a supersampled map has a factor of
+// its own, option "raymap_supersample"; the context's stays off)
 int32_t check_context(const bhr_ctx *ctx, const char *who, int32_t code) {
     if (ctx->ss > 1 || ctx->ada_k > 1)
         return bhr_fail(code, "%s: supersampling is on (factor %d); a ray map holds one ray per pixel", who, ctx->ss > 1 ? ctx->ss : ctx->ada_k);
@@ -183,9 +185,14 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     BHR_TRY(check_context(ctx, "bhr_raymap_build", BHR_ERR_INVALID));
     const int32_t K = ctx->raymap_slots;
     if (K < 1 || K > 8) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: raymap_slots %d (1 .. 8)", K);
+    // the map's own factor: the map of the fine frame, k rows x k W (the context's own supersampling stays off, check_context)
+    const int32_t ss = ctx->raymap_ss;
+    if (ss != 1 && ss != 2 && ss != 4 && ss != 8) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: raymap_supersample %d (1, 2, 4 or 8)", ss);
+    if ((int64_t)ss * ss * ctx->cfg.width * ctx->cfg.height >= ((int64_t)1 << 31))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: %d x %d rays of a %dx%d frame exceed 2^31", ss, ss, ctx->cfg.width, ctx->cfg.height);
     const bool diff = bhr_want_diff(ctx, flags);
     const int32_t comps = diff ? 9 : 5;
-    const size_t plane = (size_t)ctx->rows * ctx->cfg.width;
+    const size_t plane = (size_t)ctx->rows * ctx->cfg.width * (size_t)(ss * ss);
 
     BHR_TRY(bhr_enter(ctx));           // behind the frames in flight: they may be reading the map this build rewrites
     if (!ctx->raymap) {
@@ -194,14 +201,17 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     }
     bhr_raymap *rm = ctx->raymap;
     rm->built = 0;
-    if (rm->a.hits && (rm->alloc_slots != K || rm->alloc_comps != comps)) {
+    if (rm->a.hits && (rm->alloc_slots != K || rm->alloc_comps != comps || rm->alloc_ss != ss)) {
         BHR_TRY(drain(ctx));
         free_planes(rm);
     }
     if (!rm->a.hits) {
         BhrRayMapArgs &a = rm->a;
-        // the fix kernel's grid is sized in blocks of 256 entries of the list's capacity
+        // the fix kernel's grid is sized in blocks of 256 entries of the list's capacity; a supersampled map lists whole k x k
+        // groups, k^2-aligned (k^2 divides 256)
         const size_t over_cap = (plane + 255) / 256 * 256;
+        if (over_cap % 256 != 0 || over_cap % (size_t)(ss * ss) != 0 || over_cap > (size_t)INT32_MAX)
+            return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: an overflow list of %zu entries for factor %d", over_cap, ss);
         int32_t rc = BHR_OK;
         if ((rc = plane_alloc(rm, &a.steps, plane)) || (rc = plane_alloc(rm, &a.status, plane)) || (rc = plane_alloc(rm, &a.dir, 3 * plane)) ||
             (rc = plane_alloc(rm, &a.crossings, plane)) || (rc = plane_alloc(rm, &a.hits, (size_t)K * comps * plane)) ||
@@ -215,6 +225,7 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
         a.plane = (int64_t)plane;
         rm->alloc_slots = K;
         rm->alloc_comps = comps;
+        rm->alloc_ss = ss;
         rm->over_cap = (int32_t)over_cap;
     }
     const BhrRayMapArgs &a = rm->a;
@@ -222,7 +233,7 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     BHR_HIP(hipMemsetAsync(a.hits, 0, (size_t)K * comps * plane * sizeof(float), ctx->stream));
     BHR_HIP(hipMemsetAsync(a.over_count, 0, 16 * sizeof(unsigned int), ctx->stream));
     BHR_HIP(hipMemsetAsync(a.stats, 0, (8 + BHR_STEP_CELL) * sizeof(unsigned long long), ctx->stream));
-    BHR_TRY(bhr_launch_raymap_build(ctx, cam, flags, a));
+    BHR_TRY(bhr_launch_raymap_build(ctx, cam, flags, a, ss));
     std::vector<unsigned long long> stats(8 + BHR_STEP_CELL);
     unsigned int over = 0;
     BHR_TRY(fetch(ctx, stats.data(), a.stats, stats.size() * sizeof(unsigned long long)));
@@ -234,6 +245,7 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     rm->overflow_pixels = over;
     rm->diff = diff ? 1 : 0;
     rm->slots = K;
+    rm->ss = ss;
     rm->cam = *cam;
     rm->built = 1;
     return BHR_OK;
@@ -283,6 +295,7 @@ int32_t bhr_raymap_get_info(bhr_ctx *ctx, bhr_raymap_info *out) {
     out->slots = rm->slots;
     out->width = ctx->cfg.width;
     out->rows = ctx->rows;
+    out->supersample = rm->ss;
     out->crossings_stored = (int64_t)rm->crossings_stored;
     out->overflow_pixels = (int64_t)rm->overflow_pixels;
     out->ray_steps = rm->ray_steps;

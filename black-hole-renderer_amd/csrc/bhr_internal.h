@@ -162,10 +162,12 @@ enum bhr_march_kernel {
     BHR_MK_RAYMAP_SHADE_ROT,  // raymap_shade_kernel<diff, true>: the same with the records turned about z       raymap
     BHR_MK_RAYMAP_SHUTTER,      // raymap_shade_shutter_kernel<diff, false>: the mean of n such frames, one launch   raymap
     BHR_MK_RAYMAP_SHUTTER_ROT,  // raymap_shade_shutter_kernel<diff, true>: each sample turned about z by its own angle  raymap
+    // (ss: BUILD, SHADE and SHADE_ROT have twins for a supersampled map, raymap_build_ss_kernel / raymap_shade_ss_kernel; the shutter kernels have none)
 };
 
 // The ray map as its two kernels see it (march_raymap.hip): second kernel argument, behind the march's own block.  Planar: every
-// plane is (rows, W) with the pixel index j W + i, so a wave's 8x8 tile reads and writes 32-byte runs of each.
+// plane is (rows, W) with the pixel index j W + i, so a wave's 8x8 tile reads and writes 32-byte runs of each.  A supersampled
+// map (factor k) is the map of the fine frame: (k rows, k W), fine pixel indices; the kernels take k from the march's block.
 struct BhrRayMapArgs {
     int32_t *steps;              // executed steps of the pixel's ray
     int32_t *status;             // 0 captured, 1 escaped (samples the sky), 2 ran out of iterations
@@ -244,8 +246,9 @@ struct bhr_options {
 struct bhr_raymap {
     BhrRayMapArgs a;             // the device planes
     int32_t built, diff, slots;
-    int32_t alloc_slots, alloc_comps;   // shape of the allocation
-    int32_t over_cap;            // capacity of the overflow list: the pixel count rounded up to whole blocks of the fix kernel
+    int32_t ss;                  // the map's own supersampling factor (option "raymap_supersample" at the build): planes of the fine frame
+    int32_t alloc_slots, alloc_comps, alloc_ss;   // shape of the allocation
+    int32_t over_cap;            // capacity of the overflow list: the (fine) pixel count rounded up to whole blocks of the fix kernel
     int64_t device_bytes;
     bhr_camera cam;              // the view it was built for
     uint64_t ray_steps, crossings_stored, overflow_pixels;
@@ -423,6 +426,7 @@ struct bhr_ctx {
     // the ray map (api_raymap.hip), behind everything the frames of bhr_render touch
     bhr_raymap *raymap;        // null until the first bhr_raymap_build
     int32_t raymap_slots;      // option "raymap_slots" / BHR_RAYMAP_SLOTS: crossings a map keeps per pixel (1..8, default 4), read by bhr_raymap_build
+    int32_t raymap_ss;         // option "raymap_supersample" / BHR_RAYMAP_SUPERSAMPLE: the next map's own factor (1, 2, 4, 8; default 1), read by bhr_raymap_build
 };
 
 // The active frame slot: the one bhr_activate_slot / bhr_render last pointed the launchers at.
@@ -565,7 +569,8 @@ void bhr_shutter_free(bhr_ctx *ctx);                                 // the timi
 // march_launch.hip: the ray map's two launches on ctx->stream.  build: marches `cam` and fills the map (counting its steps
 // into the context's scalar cell); shade: the map's pixels under the scene as it is and cam's t_offset into the active slot's
 // layers -- the pixels on the overflow list are left to the fix kernel (bhr_launch_march with a repair == 2 part over that list)
-int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m);
+// ss: the map's factor -- the build marches the fine frame bhr_fine(ctx, ss) of `cam`
+int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss);
 // rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
 int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f);
 // all samples of a shutter frame from the map in one launch (raymap_shade_shutter_kernel): the mean of the n frames the launch

@@ -426,24 +426,31 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
 }
 
 // ---- the ray map (march_raymap.hip; api_raymap.hip owns the map) ------------------------------------------------------------------
-// The kernels take the march's argument block of the k = 1 strict frame and the map as a second argument.
-int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m) {
+// The kernels take the march's argument block of the strict frame and the map as a second argument.  A supersampled map (its
+// own factor ss, option "raymap_supersample"; the context's factor stays 1) takes the block of the fine frame, as a marched
+// supersampled frame does, and the kernels' supersampled twins.
+int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss) {
     const hipStream_t stream = ctx->stream;
-    const bhr_march_call call = {cam, flags | BHR_FORCE_STRICT, stream, /* slot */ -1, false, false, /* ss */ 1, false};
+    const bhr_march_call call = {cam, flags | BHR_FORCE_STRICT, stream, /* slot */ -1, false, false, ss, false};
     // the build marches but stores no layer: what march_args notes in the active frame slot for a march stays as it was
     bhr_frame_slot &f = bhr_slot(ctx);
     const int32_t disk_wide = f.disk_wide, sum_valid = f.sum_valid;
     BhrMarchArgs a;
-    march_args(ctx, call, nullptr, 1, false, a);
+    march_args(ctx, call, nullptr, ss, false, a);
     f.disk_wide = disk_wide;
     f.sum_valid = sum_valid;
     if ((int64_t)a.width * a.rows != m.plane) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: the map has %lld pixels, the frame %lld", (long long)m.plane, (long long)a.width * a.rows);
-    BHR_TRY(ensure_tile_order(ctx, 1, a.tiles_x, a.n_tiles));
-    a.tile_order = ctx->d_tile_order;
+    if (ss == 1) {
+        BHR_TRY(ensure_tile_order(ctx, 1, a.tiles_x, a.n_tiles));
+        a.tile_order = ctx->d_tile_order;
+    }
+    // ss > 1: the fine tiles in plain order (tile_order null).  The context's tile order is keyed by the marched frame's factor,
+    // and asking for the fine frame's would drop the order, the hybrid lists and the fix lists bhr_render's frames march over;
+    // a build is a one-off, its ragged tail does not matter.
     a.ray_steps = m.stats + 8;                                 // a counter cell of the map's own, behind its totals
     const bool diff = bhr_want_diff(ctx, flags);
     if (m.comps != (diff ? 9 : 5)) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: %d components per record for differentials %d", m.comps, (int)diff);
-    const void *fn = bhr_march_kernel_raymap(BHR_MK_RAYMAP_BUILD, diff, 0);
+    const void *fn = bhr_march_kernel_raymap(BHR_MK_RAYMAP_BUILD, diff, ss > 1);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: no build kernel in this library");
     BhrRayMapArgs mm = m;
     void *args[] = {&a, &mm};
@@ -457,12 +464,13 @@ int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
 int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c, float rot_s) {
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no skybox set (bhr_set_skybox)");
     if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no disk texture set (bhr_set_disk_texture)");
+    // call.ss: the map's factor -- the block of the fine frame (k W x k rows, k^2 W rows == the map's plane), a wave per fine tile
     BhrMarchArgs a;
-    march_args(ctx, call, nullptr, 1, false, a);
+    march_args(ctx, call, nullptr, call.ss, false, a);
     if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5))
         return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: the map does not fit the frame");
     const bool turned = !(rot_c == 1.0f && rot_s == 0.0f);
-    const void *fn = bhr_march_kernel_raymap(turned ? BHR_MK_RAYMAP_SHADE_ROT : BHR_MK_RAYMAP_SHADE, diff, 0);
+    const void *fn = bhr_march_kernel_raymap(turned ? BHR_MK_RAYMAP_SHADE_ROT : BHR_MK_RAYMAP_SHADE, diff, call.ss > 1);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no shade kernel in this library");
     // the frame's march bracket opens here; the overflow launch behind this one (bhr_launch_march, last part) closes it
     // (a later sample of a shutter frame from the map keeps the first sample's)
@@ -484,6 +492,7 @@ int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: no skybox set (bhr_set_skybox)");
     if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: no disk texture set (bhr_set_disk_texture)");
     if (smp.n < 1 || smp.n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render_shutter: %d samples (1 .. %d)", smp.n, BHR_SHUTTER_MAX_SAMPLES);
+    if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: the fused launch has no supersampled kernel (factor %d)", call.ss);
     BhrMarchArgs a;
     march_args(ctx, call, nullptr, 1, false, a);
     if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5))

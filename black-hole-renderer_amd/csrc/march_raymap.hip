@@ -260,11 +260,162 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void r
     a.disk[o + 2] = acc_d[2];
 }
 
+// ---- supersampled maps (option "raymap_supersample", a.ss = k > 1) -------------------------------------------------------
+// The map of the fine frame (k W x k rows, bhr_fine_camera): instantiations of their own, the k = 1 kernels above stay as they are.
+//
+// The build over the fine argument block (a.width / rows / pw / ph fine, out_width / out_rows the frame's): the loop above, fine
+// planes, tiles in plain order.  A k x k group with ANY ray over the slots goes on the overflow list whole, in the format
+// march_tile_body writes for march_fix_ss_kernel (march_tile.h): k^2 consecutive entries in sub-sample order (sy k + sx),
+// k^2-aligned, groups in the order of their (0, 0) lanes -- the fix kernel resolves a group from 64 / k^2 of them per wave.
+// k W and k rows are multiples of k (and 8 is one of k), so a group lies in one tile, inside the frame or outside it, whole.
+template <bool DIFF>
+__global__ __launch_bounds__(256) void raymap_build_ss_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
+    const int slot = wave_slot();
+    if (slot >= a.n_list) return;    // wave-uniform: the lanes of a wave stay together down to the butterfly
+    const int lane = threadIdx.x & 63;
+    const int tile = a.tile_order ? a.tile_order[slot] : slot;
+    const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
+    const int i = tx * 8 + (lane & 7);
+    const int j = ty * 8 + (lane >> 3);
+    const bool valid = tile < a.n_tiles && i < a.width && j < a.rows;
+
+    Ray<DIFF, 0> ray;
+    ray.init(a, valid ? i : 0, valid ? j : 0);
+    if (!valid) ray.done = 4;
+    const size_t pix = valid ? (size_t)j * a.width + i : 0;
+    int cnt = 0, n_rec = 0;
+    while (ray.done == 0) {
+        ray.step(a);
+        cnt += 1;
+        if (ray.full) {
+            ray.record_one(m, pix, n_rec);
+            ray.full = false;
+        }
+    }
+    ray.step_count = cnt;
+    if (cnt > 0) ray.settle(a);
+    else ray.done = 3;
+    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
+    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
+
+    if (valid) {
+        const bool esc = ray.escaped();
+        m.steps[pix] = cnt;
+        m.status[pix] = esc ? 1 : (ray.done == 2 ? 0 : 2);
+        const V3 dn = esc ? normalized(ray.d) : mk(0.0f, 0.0f, 0.0f);
+        m.dir[pix] = dn.x;
+        m.dir[(size_t)m.plane + pix] = dn.y;
+        m.dir[2 * (size_t)m.plane + pix] = dn.z;
+        m.crossings[pix] = n_rec;
+    }
+    // the group's flag: the guard kernel's butterfly (every lane of the wave is here)
+    int u = valid && n_rec > m.slots ? 1 : 0;
+    for (int x = 1; x < a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+    for (int x = 8; x < 8 * a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+    const bool over = valid && u != 0;
+    const unsigned long long om = __ballot(over);
+    if (om) {
+        const int first = __ffsll((long long)om) - 1;
+        const int km = a.ss - 1, sx = lane & km, sy = (lane >> 3) & km;
+        const unsigned long long lead = __ballot(over && sx == 0 && sy == 0);
+        unsigned int base = 0;
+        if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(lead) << (2 * a.ss_log2));
+        base = __shfl(base, first, BHR_WAVE);
+        const int l0 = lane - sx - 8 * sy;
+        const unsigned int at = base + ((unsigned int)__popcll(lead & ((1ull << l0) - 1ull)) << (2 * a.ss_log2)) + (unsigned int)((sy << a.ss_log2) + sx);
+        // (every group is appended at most once and the list has room for the whole fine plane)
+        if (over) m.over_list[at] = (int32_t)pix;
+    }
+    const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
+    const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
+    if (lane == 0) {
+        atomicAdd(m.stats, stored);
+        atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
+    }
+}
+
+// What resolve_store (march_device.h) asks of a ray: the six values it leaves.  Here they come out of the lane's records.
+struct RayMapValues {
+    float v[6];
+    __device__ __forceinline__ void values(const BhrMarchArgs &, float bk[3], float dk[3]) const {
+        bk[0] = v[0]; bk[1] = v[1]; bk[2] = v[2];
+        dk[0] = v[3]; dk[1] = v[4]; dk[2] = v[5];
+    }
+};
+
+// A frame from a supersampled map: one 8x8 tile of the FINE frame per wave, every lane shades its own fine record list exactly
+// as raymap_shade_kernel does (same device functions, same order, same turn), and the k x k groups are resolved in the wave by
+// resolve_store -- the marched supersampled kernels' butterfly and product, so the output pixel is theirs bit for bit; the lane
+// at sub-sample (0, 0) stores it at (i >> log2 k, j >> log2 k) of the output frame.
+// Two things the k = 1 kernel does are NOT done here:
+//  * no lane returns early (beyond the frame, or on the overflow list): __shfl_xor reads whatever a lane that has left last held
+//    in the register.  A lane without a ray shades no record and contributes zeros; its whole group is beyond the frame and is
+//    not stored.
+//  * overflow is a group's property: a group with any ray over the slots is on the overflow list whole (the build above) and is
+//    not stored here at all -- march_fix_ss_kernel marches and resolves it, so that pixel is the strict supersampled march itself.
+//    Its lanes shade nothing.
+template <bool DIFF, bool ROT>
+__global__ __launch_bounds__(256) void raymap_shade_ss_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
+    const int tile = wave_slot();
+    if (tile >= a.n_tiles) return;   // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const int i = (tile % a.tiles_x) * 8 + (lane & 7);
+    const int j = (tile / a.tiles_x) * 8 + (lane >> 3);
+    const bool valid = i < a.width && j < a.rows;
+    const size_t pix = valid ? (size_t)j * a.width + i : 0;
+    const int crossings = valid ? m.crossings[pix] : 0;
+    int u = crossings > m.slots ? 1 : 0;
+    for (int x = 1; x < a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+    for (int x = 8; x < 8 * a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+    const bool have = valid && u == 0;
+    const int count = have ? crossings : 0;
+    Shade sh;                        // as Ray::init leaves it
+    sh.accum = mk(0, 0, 0);
+    sh.alpha_total = 0.0f;
+    sh.unsure = 0;
+    const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;   // scalar operands, as above
+    for (int c = 0; c < count; ++c) {
+        const float *q = m.hits + (size_t)c * m.comps * (size_t)m.plane + pix;
+        const size_t p = (size_t)m.plane;
+        float hx = q[0], hy = q[p];
+        V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
+        float dxx = 0.0f, dxy = 0.0f, dyx = 0.0f, dyy = 0.0f;
+        if (DIFF) { dxx = q[5 * p]; dxy = q[6 * p]; dyx = q[7 * p]; dyy = q[8 * p]; }
+        if (ROT) {
+            turn_xy(rc, rs, hx, hy);
+            turn_xy(rc, rs, to_cam.x, to_cam.y);
+            if (DIFF) {
+                turn_xy(rc, rs, dxx, dxy);
+                turn_xy(rc, rs, dyx, dyy);
+            }
+        }
+        shade_hit<DIFF, 0>(a, sh, hx, hy, to_cam, dxx, dxy, dyx, dyy);
+    }
+    RayMapValues val = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
+    if (have) {
+        const bool esc = m.status[pix] == 1;
+        V3 dir = mk(m.dir[pix], m.dir[(size_t)m.plane + pix], m.dir[2 * (size_t)m.plane + pix]);
+        if (ROT) turn_xy(rc, rs, dir.x, dir.y);
+        raymap_pixel_values(a, esc, dir, sh, val.v, val.v + 3);
+    }
+    // every lane of the wave, whatever it holds
+    resolve_store(a, val, have, have, i, j, 8);
+}
+
 }  // namespace
 
 // ---- the kernels of this object, by the launcher's names (march_launch.hip); null: not in this object ----------
+// ss: the kernels of a supersampled map (a.ss > 1); its shutter frames go sample by sample through the shade kernels, there is
+// no fused supersampled shutter kernel
 const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss) {
-    (void)ss;
+    if (ss) {
+        switch (k) {
+        case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_ss_kernel<true> : (const void *)raymap_build_ss_kernel<false>;
+        case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_ss_kernel<true, false> : (const void *)raymap_shade_ss_kernel<false, false>;
+        case BHR_MK_RAYMAP_SHADE_ROT: return diff ? (const void *)raymap_shade_ss_kernel<true, true> : (const void *)raymap_shade_ss_kernel<false, true>;
+        default: return nullptr;
+        }
+    }
     switch (k) {
     case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_kernel<true> : (const void *)raymap_build_kernel<false>;
     case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_kernel<true, false> : (const void *)raymap_shade_kernel<false, false>;

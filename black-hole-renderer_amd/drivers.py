@@ -412,9 +412,20 @@ def check_shutter(shutter, shutter_samples) -> None:
         raise ValueError(f"shutter_samples must be an integer between 1 and {SHUTTER_MAX_SAMPLES}, got {shutter_samples!r}")
 
 
+def check_map_supersample(k, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False) -> None:
+    """--map_supersample k / render_video(map_supersample=k): the ray map's own supersampling factor (k x k records per
+    pixel, resolved in the shade).  1, 2, 4 or 8, and above 1 only with one of the three maps.  Raises ValueError before any
+    device work."""
+    if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4, 8):
+        raise ValueError(f"map_supersample must be 1, 2, 4 or 8, got {k!r}")
+    if k > 1 and not (ray_map or orbit_map or shutter_map):
+        raise ValueError("--map_supersample is a ray map's factor: it needs --ray_map, --orbit_map or --shutter_map "
+                         "(marched frames take --supersample)")
+
+
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
-                    shutter_map=False) -> dict:
+                    shutter_map=False, map_supersample=1) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -436,6 +447,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(orbit_map=True)
     if shutter_map:
         params.update(shutter_map=True)
+    if map_supersample > 1:
+        params.update(map_supersample=map_supersample)
     return params
 
 
@@ -472,7 +485,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  supersample_threshold: Optional[float] = None, video_codec: str = "auto", video_quality: int = 90,
                  bit_depth: int = 8, dither: str = "none", shutter: float = 0.0, shutter_samples: int = 8,
                  grade: Optional[dict] = None, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False,
-                 **_deprecated_kwargs) -> None:
+                 map_supersample: int = 1, **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -542,7 +555,14 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     math="strict" the frames are byte for byte those of the shutter video without the flag; under ``orbit`` they are the means
     of orbit-map frames (see above).  Refused with ValueError, before any device work, with ``shutter == 0``, together with ``ray_map`` or
     ``orbit_map``, with ``orbit`` over a tilted disk, a supersampling factor other than 1, a Disk V2 source or several ranks.
-    The progress record carries ``shutter_map`` when it is set, and a resume with the other setting starts over."""
+    The progress record carries ``shutter_map`` when it is set, and a resume with the other setting starts over.
+
+    ``map_supersample`` = k in {1, 2, 4, 8}: the factor of the one map the three modes above build
+    (HipRenderer.build_ray_map(supersample=k)) -- k x k records per pixel, every frame from the map resolved with
+    set_supersample's filter; ``supersample`` itself stays 1 with a map.  Refused with ValueError, before any device work, for
+    another value or for k > 1 without one of the three maps (check_map_supersample).  The progress record carries
+    ``map_supersample`` when it is above 1, and a resume with another factor starts over."""
+    check_map_supersample(map_supersample, ray_map, orbit_map, shutter_map)
     check_shutter(shutter, shutter_samples)
     grade = check_grade(grade)
     if grade is not None:
@@ -574,7 +594,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     submitted: List[int] = []
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
     params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither,
-                             shutter, shutter_samples, grade, ray_map, orbit_map, shutter_map)
+                             shutter, shutter_samples, grade, ray_map, orbit_map, shutter_map, map_supersample)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -662,16 +682,17 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     dt = disk_rotation_speed
     print(f"  lifecycle system ready (n_r={n_r}, n_phi={n_phi}), rank {rank}/{world}")
     if ray_map:
-        renderer.build_ray_map(static_cam_pos, fov)     # the one march of the video
+        renderer.build_ray_map(static_cam_pos, fov, supersample=map_supersample)     # the one march of the video
         info = renderer.ray_map_info()
         print(f"  ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
     if orbit_map:
         # the orbit's radius is |pov|, not the pov's xy norm: frame 0 of the orbit, not the pov itself
-        renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees), fov)     # the one march of the video
+        renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees), fov, supersample=map_supersample)     # the one march of the video
         info = renderer.ray_map_info()
         print(f"  orbit ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
     if shutter_map:
-        renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov)   # the one march of the video
+        renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov,
+                               supersample=map_supersample)   # the one march of the video
         info = renderer.ray_map_info()
         print(f"  shutter ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
     t_loop0 = time.time()                               # ``stats`` (bench.py): the one-off set-up apart from the frame loop

@@ -469,10 +469,17 @@ class HipRenderer:
         return self.read_layer(_lib.LAYER_FINAL)
 
     # ------------------------------------------------------------------ ray map
-    def build_ray_map(self, cam_pos, fov: float, skip_differentials: bool = False) -> None:
+    def build_ray_map(self, cam_pos, fov: float, skip_differentials: bool = False, supersample: int = 1) -> None:
         """March the view once with the strict arithmetic and keep what the march finds before it shades anything
         (bhr_raymap_build; include/bhr.h states the map).  The slot count is option "raymap_slots" (1..8, default 4).
-        Whole-frame contexts with one ray per pixel and the texture disk source only.  Synchronises."""
+        Whole-frame contexts with one ray per pixel and the texture disk source only.  Synchronises.
+
+        ``supersample`` = k in {1, 2, 4, 8} is the map's own factor (option "raymap_supersample"; the renderer's
+        ``set_supersample`` stays at 1): the map of the fine frame, k x k records per pixel, which every frame from the map
+        resolves with set_supersample's filter -- bit for bit the strict frame of a renderer with ``set_supersample(k)``."""
+        if supersample not in (1, 2, 4, 8):
+            raise ValueError(f"build_ray_map: supersample {supersample!r} (1, 2, 4 or 8)")
+        self.set_option("raymap_supersample", supersample)
         cam = self.camera_uniforms(cam_pos, fov, 0)
         _lib.check(self._lib.bhr_raymap_build(self._ctx, C.byref(cam), _lib.SKIP_DIFFERENTIALS if skip_differentials else 0))
 
@@ -532,18 +539,20 @@ class HipRenderer:
         _lib.check(self._lib.bhr_raymap_render_shutter(self._ctx, cams, len(t_offsets), flags))
 
     def ray_map_info(self) -> dict:
-        """The context's ray map (bhr_raymap_get_info): built, diff, slots, width, rows, crossings_stored, overflow_pixels,
-        device_bytes, ray_steps of the build, and the build camera's pos / r_escape."""
+        """The context's ray map (bhr_raymap_get_info): built, diff, slots, width, rows (the output frame's), supersample (the
+        map's own factor), crossings_stored, overflow_pixels, device_bytes, ray_steps of the build (fine rays), and the build
+        camera's pos / r_escape."""
         info = _lib.RayMapInfo()
         _lib.check(self._lib.bhr_raymap_get_info(self._ctx, C.byref(info)))
-        out = {name: int(getattr(info, name)) for name in ("built", "diff", "slots", "width", "rows", "crossings_stored",
+        out = {name: int(getattr(info, name)) for name in ("built", "diff", "slots", "width", "rows", "supersample", "crossings_stored",
                                                            "overflow_pixels", "device_bytes", "ray_steps")}
         out["cam_pos"] = [float(v) for v in info.cam.pos]
         out["r_escape"] = float(info.cam.r_escape)
         return out
 
     def ray_map_passes(self) -> dict:
-        """The map's planes as NumPy arrays in (H, W[, ...]) order: ``steps``, ``status`` (0 captured, 1 escaped, 2 out of
+        """The map's planes as NumPy arrays in (H, W[, ...]) order -- of the fine frame, (k H, k W[, ...]), for a map with
+        supersample k: ``steps``, ``status`` (0 captured, 1 escaped, 2 out of
         iterations), ``escape_dir`` (H, W, 3), ``crossings``, ``hits`` (K, H, W, 5 | 9: hit_x, hit_y, to_cam xyz[, dxx, dxy, dyx,
         dyy]) and, computed on the host from the first record (output.hit_polar), ``hit_r`` and ``hit_phi`` of the first
         crossing, NaN where there is none."""
@@ -551,7 +560,8 @@ class HipRenderer:
         info = self.ray_map_info()
         if not info["built"]:
             raise AssertionError("no ray map has been built (build_ray_map)")
-        h, w, k, nc = info["rows"], info["width"], info["slots"], 9 if info["diff"] else 5
+        ss = max(info["supersample"], 1)
+        h, w, k, nc = info["rows"] * ss, info["width"] * ss, info["slots"], 9 if info["diff"] else 5
 
         def read(which, shape, dtype):
             out = np.empty(shape, dtype=dtype)

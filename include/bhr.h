@@ -282,12 +282,31 @@ BHR_API int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t
  * (bhr_set_skybox, bhr_set_disk_texture, bhr_compose_texture, the lifecycle calls) do not invalidate it.
  * bhr_raymap_read copies one plane to the host, (rows, W[, 3]) and HITS as (K, rows, W, 5 | 9); bytes must be the plane's size.
  * bhr_raymap_get_info never fails for want of a map: built = 0 then.  bhr_raymap_free is ordered behind the frames in flight.
+ * Supersampled maps.  Option "raymap_supersample" (1, 2, 4 or 8; default 1) is the map's OWN factor k, read by
+ * bhr_raymap_build as "raymap_slots" is; the map in memory keeps the factor it was built with, and a build with another one
+ * reallocates.  The context's bhr_set_supersample / bhr_set_adaptive_supersample stay at 1 for every map call and are refused
+ * as below.  With k > 1 the map is the map of the fine frame: built by the strict march of bhr_set_supersample's fine camera
+ * (pixel pitch / k) of `cam`, every plane k rows x k W, the overflow list in fine pixel indices -- a k x k group with any ray
+ * over K is listed whole.  bhr_raymap_info: width and rows stay the output frame's, supersample = k, crossings_stored,
+ * overflow_pixels (a multiple of k^2) and ray_steps count fine rays, ray_steps equal to that of a strict bhr_render of the
+ * view with bhr_set_supersample(k).  bhr_raymap_read hands out the fine planes, (k rows, k W[, 3]) and (K, k rows, k W, 5 | 9).
+ * Device memory: k^2 x (24 + K x 20 | 36 + 4) bytes per output pixel.
+ * The frame: BG and DISK of bhr_raymap_render(ctx, t, flags) are bit for bit those of bhr_render(ctx', &cam_t, flags |
+ * BHR_FORCE_STRICT | <the build's BHR_SKIP_DIFFERENTIALS>), ctx' a context of the same configuration with
+ * bhr_set_supersample(ctx', k), and so is everything made from them.  The shade kernel shades each fine record list and resolves
+ * the k x k groups in the wave with bhr_set_supersample's filter (pairwise tree, times 1 / k^2); the groups of the overflow
+ * list are marched and resolved by the strict supersampled fix kernel.  bhr_counters: rays = k^2 W H.
+ * bhr_raymap_render_view and bhr_raymap_render_shutter take such a map with their checks and meanings unchanged (the camera is
+ * compared with the build camera as passed, at the output pitch): their frames are that k x k filter of the fine frames they
+ * are defined by below; a shutter frame resolves each sample first, then takes the mean, always sample by sample.
  * Refusals, with nothing launched and the context as it was --
  *   BHR_ERR_STATE:   render or read before a build (or after bhr_raymap_free); render while supersampling, adaptive
  *                    supersampling or a Disk V2 source is on (the map stays; switch back and it renders again);
  *   BHR_ERR_INVALID: build or render on a row-block context; build with supersampling or adaptive supersampling on or with a
  *                    Disk V2 source (surface or volume); any other flag bit; a non-finite t_offset; "raymap_slots" outside 1..8
- *                    (refused by bhr_set_option; a BHR_RAYMAP_SLOTS outside it by the build); an unknown plane or a wrong size;
+ *                    (refused by bhr_set_option; a BHR_RAYMAP_SLOTS outside it by the build); "raymap_supersample" not 1, 2, 4
+ *                    or 8 (likewise; BHR_RAYMAP_SUPERSAMPLE by the build), or a build with k^2 W H >= 2^31; an unknown plane or
+ *                    a wrong size;
  *   BHR_ERR_NOMEM:   a failed allocation: everything the call allocated is freed again and the context stays usable.
  *
  * bhr_raymap_render_view(ctx, cam, flags): a frame from the map seen from `cam`, the build camera turned rigidly about the z
@@ -352,10 +371,10 @@ BHR_API int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t
 #define BHR_RAYMAP_HITS 4
 typedef struct {
     int32_t built, diff, slots;         /* a map exists; it holds the differential records; K */
-    int32_t width, rows;
-    int32_t reserved;
-    int64_t crossings_stored;           /* sum over the pixels of min(CROSSINGS, K) */
-    int64_t overflow_pixels;            /* pixels with CROSSINGS > K */
+    int32_t width, rows;                /* of the output frame, whatever the factor */
+    int32_t supersample;                /* the map's own factor k (option "raymap_supersample"): the planes are k rows x k W */
+    int64_t crossings_stored;           /* sum over the (fine) pixels of min(CROSSINGS, K) */
+    int64_t overflow_pixels;            /* (fine) pixels on the overflow list: CROSSINGS > K; with k > 1 whole k x k groups */
     int64_t device_bytes;
     uint64_t ray_steps;                 /* of the build: those of a strict bhr_render of the view */
     bhr_camera cam;                     /* the view the map was built for */
@@ -457,6 +476,8 @@ BHR_API int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]);
  *   "grade_timing"    BHR_GRADE_TIMING    1 a graded frame (bhr_set_grade) brackets each launch of its grade stage with a pair of HIP
  *                                         events (bhr_debug_read, which = 6); default 0
  *   "raymap_slots"    BHR_RAYMAP_SLOTS    crossings a ray map keeps per pixel (1..8, default 4); read by bhr_raymap_build
+ *   "raymap_supersample" BHR_RAYMAP_SUPERSAMPLE the next ray map's own supersampling factor (1, 2, 4 or 8, default 1): k x k records per
+ *                                         pixel, resolved in the shade; read by bhr_raymap_build; anything else: BHR_ERR_INVALID
  *   "raymap_shutter_fused" BHR_RAYMAP_SHUTTER_FUSED 1 (default) bhr_raymap_render_shutter shades all samples of a map without overflow
  *                                         pixels in one launch, 0 sample by sample with the accumulation launches (the same bits; A/B runs)
  * (bhr_create only: BHR_FRAME_SLOTS.) */
