@@ -491,7 +491,14 @@ __device__ __forceinline__ void volume_segment(const BhrMarchArgs &a, Shade &sh,
     const double ct = (double)a.cos_t, st = (double)a.sin_t;
     const double z0 = (double)f0 * ct, z1 = (double)f1 * ct;           // heights above the disk plane
     const bool near_plane = z0 * z1 < 0.0 || fmin(fabs(z0), fabs(z1)) <= a.vol_h_max;
-    if (!(near_plane && (double)fmaxf(r0, r1) >= P.r_in && (double)fminf(r0, r1) <= a.vol_r_max)) return;
+    // Bounding slab.  A chord that does not cross the plane is nearest to it at an end, and farthest from the origin at an
+    // end, so those two tests read the ends alone.  It is NEAREST to the origin in between: two ends beyond vol_r_max can
+    // have the volume's rim between them (a chord of length l tangent at radius r dips l^2 / 8r inside its ends: 0.03 at
+    // step_size 0.5 and r = 10, twice the 0.015 by which vol_r_max exceeds r_out for the default disk).  No point of the
+    // chord is farther than half its length from the nearer end; 0.51 covers the f32 rounding of r0, r1 and the length
+    const float cx = p1.x - p0.x, cy = p1.y - p0.y, cz = p1.z - p0.z;
+    const float reach = 0.51f * sqrtf(cx * cx + cy * cy + cz * cz);
+    if (!(near_plane && (double)fmaxf(r0, r1) >= P.r_in && (double)(fminf(r0, r1) - reach) <= a.vol_r_max)) return;
     if (sh.alpha_total >= BHR_VOLUME_OPAQUE) return;     // what lies behind contributes < 1e-4 of its colour
     const double ex = (double)p1.x - (double)p0.x, ey = (double)p1.y - (double)p0.y, ez = (double)p1.z - (double)p0.z;
     const double len = sqrt(ex * ex + ey * ey + ez * ez);

@@ -638,6 +638,57 @@ static v3 dv2_color(float tf)
     return v3_make(clampf(c.x * lum, 0.0f, 1.0f), clampf(c.y * lum, 0.0f, 1.0f), clampf(c.z * lum, 0.0f, 1.0f));
 }
 
+/* ---- analytic Disk V2 surface source (include/bhr_disk_v2.h: BHR_DISK_V2).  At a plane crossing the RGBA comes from the
+ * model's mid-plane fields instead of the texture, by the mapping documented above disk_v2_color / disk_v2_rgba in
+ * csrc/march_device.h: the pattern is advected with the model's own Omega(r), phi_adv = phi + t_offset Omega(r) -- the
+ * sign of _sample_disk's texture roll (render.py:2575-2577), so that both sources turn the same way; temperature
+ * t = clamp(T_mid F / T_peak) goes through the compose kernel's black-body mapping (dv2_color), opacity is
+ * clamp(rho_mid F).  Model in binary64, colour in f32.  oracle_set_disk_v2_surface(NULL, ...) switches back. */
+typedef struct {
+    oracle_dv2_params p;
+    double norm_shear, norm_hotspot, t_peak;
+    int32_t on;
+} surface_t;
+static surface_t g_surf;
+
+ORACLE_API void oracle_set_disk_v2_surface(const oracle_dv2_params *p, double norm_shear, double norm_hotspot, double t_peak)
+{
+    g_surf.on = p != NULL;
+    if (!p) return;
+    g_surf.p = *p;
+    g_surf.norm_shear = norm_shear; g_surf.norm_hotspot = norm_hotspot; g_surf.t_peak = t_peak;
+}
+
+static v4 dv2_surface_rgba(const oracle_dv2_params *P, double norm_shear, double norm_hotspot, double t_peak,
+                           double x, double y, double t_offset)
+{
+    const double r = sqrt(x * x + y * y);
+    const double phi = atan2(y, x) + t_offset * dv2_omega(r, P);
+    const double F = dv2_structure(r, phi, P, norm_shear, norm_hotspot);
+    const double t = fmin(fmax(dv2_t_mid(r, P) * F / t_peak, 0.0), 1.0);
+    const double rho = fmin(fmax(dv2_rho_mid(r, P) * F, 0.0), 1.0);
+    const v3 c = dv2_color((float)t);
+    v4 o = {c.x, c.y, c.z, (float)rho};
+    return o;
+}
+
+/* the mapping at given hit points: rows of xy are (hit_x, hit_y), rows of out4 (r, g, b, alpha) */
+ORACLE_API void oracle_probe_dv2_rgba(const oracle_dv2_params *p, double norm_shear, double norm_hotspot, double t_peak,
+                                      const double *xy, int64_t n, double t_offset, double *out4)
+{
+    for (int64_t k = 0; k < n; ++k) {
+        v4 o = dv2_surface_rgba(p, norm_shear, norm_hotspot, t_peak, xy[2 * k], xy[2 * k + 1], t_offset);
+        out4[4 * k] = o.x; out4[4 * k + 1] = o.y; out4[4 * k + 2] = o.z; out4[4 * k + 3] = o.w;
+    }
+}
+
+/* Test hook: when set, every disk crossing that passes the radial gate appends a row (i, j, hit_x, hit_y, r, g, b, alpha)
+ * -- pixel, crossing point, the RGBA its source gave -- until `cap` rows are stored; *g_hits_n counts all of them. */
+static double *g_hits_out;
+static int64_t g_hits_cap, g_hits_n;
+ORACLE_API void oracle_set_hits_out(double *buf, int64_t cap) { g_hits_out = buf; g_hits_cap = cap; g_hits_n = 0; }
+ORACLE_API int64_t oracle_hits_recorded(void) { return g_hits_n; }
+
 /* one RK4 step's chord through the volume; *accum / *alpha_total are composited front to back */
 static void volume_segment(v3 p0, v3 p1, v3 dir0, float tilt_rad, float t_offset, v3 cam_pos, float r_inner, float r_outer,
                            v3 *accum, float *alpha_total)
@@ -866,7 +917,10 @@ ORACLE_API int64_t oracle_ray_march(const oracle_camera *cam, const oracle_march
                         v3 hit_pos_vec = v3_make(hit_x, hit_y, hit_z);
                         v3 ray_to_cam = v3_make(-dir_.x, -dir_.y, -dir_.z);
                         v4 disk_rgba;
-                        if (p->anti_alias_mode == 0 || skip_diff == 1) {
+                        if (g_surf.on) {
+                            disk_rgba = dv2_surface_rgba(&g_surf.p, g_surf.norm_shear, g_surf.norm_hotspot, g_surf.t_peak,
+                                                         (double)hit_x, (double)hit_y, (double)t_offset);
+                        } else if (p->anti_alias_mode == 0 || skip_diff == 1) {
                             disk_rgba = sample_disk(&sc, hit_x, hit_y, r_inner, r_outer, t_offset);
                         } else {
                             float hit_r_cyl = sqrtf(hit_x * hit_x + hit_y * hit_y + 1e-6f);
@@ -885,6 +939,18 @@ ORACLE_API int64_t oracle_ray_march(const oracle_camera *cam, const oracle_march
                             lod_diff = fminf(fmaxf(lod_diff, 0.0f), 3.0f);
                             if (lod_diff > lod_asked) lod_asked = lod_diff;
                             disk_rgba = sample_disk_mip(&sc, hit_x, hit_y, r_inner, r_outer, t_offset, lod_diff);
+                        }
+                        if (g_hits_out) {
+                            int64_t k;
+#ifdef _OPENMP
+#pragma omp atomic capture
+#endif
+                            k = g_hits_n++;
+                            if (k < g_hits_cap) {
+                                double *h = g_hits_out + 8 * k;
+                                h[0] = i; h[1] = j; h[2] = hit_x; h[3] = hit_y;
+                                h[4] = disk_rgba.x; h[5] = disk_rgba.y; h[6] = disk_rgba.z; h[7] = disk_rgba.w;
+                            }
                         }
                         v3 disk_col = v3_make(disk_rgba.x, disk_rgba.y, disk_rgba.z);
                         float base_alpha = fminf(disk_rgba.w, 0.999f);

@@ -79,6 +79,14 @@ def load(fast=False) -> C.CDLL:
     lib.oracle_dv2_eval.argtypes = [C.c_void_p, I32, D, D, D, I64, C.c_double, C.c_double, D]
     lib.oracle_set_volume.restype = None
     lib.oracle_set_volume.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, I32]
+    lib.oracle_set_disk_v2_surface.restype = None
+    lib.oracle_set_disk_v2_surface.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
+    lib.oracle_probe_dv2_rgba.restype = None
+    lib.oracle_probe_dv2_rgba.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, D, I64, C.c_double, D]
+    lib.oracle_set_hits_out.restype = None
+    lib.oracle_set_hits_out.argtypes = [C.c_void_p, I64]
+    lib.oracle_hits_recorded.restype = I64
+    lib.oracle_hits_recorded.argtypes = []
     lib.oracle_set_escape_out.restype = None
     lib.oracle_set_escape_out.argtypes = [C.c_void_p]
     lib.oracle_set_lod_out.restype = None
@@ -222,6 +230,16 @@ def probe_skybox(skybox, dirs, fast=False):
     return out
 
 
+def probe_dv2_rgba(cparams, norms, t_peak, xy, t_offset=0.0, fast=False):
+    """The Disk V2 surface source's mapping (bhr_oracle.c: dv2_surface_rgba) at hit points ``xy`` (n, 2) of the disk
+    plane -> (n, 4) r, g, b, alpha.  ``norms``: (norm_shear, norm_hotspot)."""
+    a = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+    out = np.empty((a.shape[0], 4), dtype=np.float64)
+    load(fast).oracle_probe_dv2_rgba(C.byref(cparams), float(norms[0]), float(norms[1]), float(t_peak), _dp(a), a.shape[0],
+                                     float(t_offset), _dp(out))
+    return out
+
+
 class OracleRenderer:
     """CPU twin of TaichiRenderer's render path (render.py:2199-2266, 3865-3923)."""
 
@@ -231,6 +249,26 @@ class OracleRenderer:
         (None: back to the textured thin disk).  Mirrors bhr_set_disk_source(BHR_DISK_V2_VOLUME)."""
         self.lib.oracle_set_volume(C.byref(cparams) if cparams is not None else None, norm_shear, norm_hotspot, t_peak,
                                    absorption, grazing_gain, substeps)
+
+    def set_disk_v2_surface(self, cparams=None, norm_shear=1.0, norm_hotspot=1.0, t_peak=1.0):
+        """Analytic Disk V2 surface source for the following march() calls of THIS build of the library (None: back to
+        the texture).  Mirrors bhr_set_disk_source(BHR_DISK_V2); a volume set with set_volume() takes precedence."""
+        self.lib.oracle_set_disk_v2_surface(C.byref(cparams) if cparams is not None else None, norm_shear, norm_hotspot,
+                                            t_peak)
+
+    def crossings(self, cam_pos, fov, frame=0, skip_differentials=False, cap=1 << 20):
+        """One march() with the crossing hook on: (image, disk_layer, rows) with one row (i, j, hit_x, hit_y, r, g, b,
+        alpha) per disk crossing that passed the radial gate, sorted by pixel (the order within a pixel is not kept)."""
+        buf = np.zeros((cap, 8), dtype=np.float64)
+        self.lib.oracle_set_hits_out(buf.ctypes.data_as(C.c_void_p), cap)
+        try:
+            img, disk = self.march(cam_pos, fov, frame=frame, skip_differentials=skip_differentials, want_steps=False)
+            n = int(self.lib.oracle_hits_recorded())
+        finally:
+            self.lib.oracle_set_hits_out(None, 0)
+        assert n <= cap, "crossing buffer too small"
+        rows = buf[:n]
+        return img, disk, rows[np.lexsort((rows[:, 1], rows[:, 0]))]
 
     def __init__(self, width, height, skybox, disk_tex, step_size=0.1, r_max=10.0, r_disk_inner=2.0,
                  r_disk_outer=15.0, disk_tilt=0.0, anti_alias="disabled", aa_strength=1.0,

@@ -44,6 +44,53 @@ class _Field:
         self.arr = np.array(a)
 
 
+def disk_v2_tables(dv, P, sp, r, rg, phi):
+    """The reference package's fields on r x (zf H(r)) and its modulations on rg x phi, as plain arrays."""
+    Hh = dv.disk_half_thickness(r, P)
+    zf = np.array([0.0, 0.25, -0.25, 1.0, -1.0, 1.1])
+    rr = np.repeat(r[:, None], len(zf), axis=1)
+    zz = zf[None, :] * np.asarray(Hh)[:, None]
+    d2 = dict(r=r, zf=zf, H=Hh, smooth=dv.geometry.smoothstep(0.0, 1.0, np.linspace(-0.5, 1.5, 41)),
+              mask_r=dv.disk_radial_mask(r, P), W_r=dv.disk_radial_weight(r, P),
+              W_z=dv.disk_vertical_weight(rr, zz, P), mask_vol=dv.disk_volume_mask(rr, zz, P),
+              omega=dv.angular_velocity_field(r, P), rho_mid=dv.midplane_density_field(r, P),
+              T_mid=dv.midplane_temperature_field(r, P), rho=dv.density_field(rr, zz, P),
+              T=dv.temperature_field(rr, zz, P))
+    rg2, pg2 = np.meshgrid(rg, phi, indexing="ij")
+    d2["F_mode"] = dv.weak_mode_modulation(rg2, pg2, P, sp)
+    for seed in (7, 42, 123):
+        d2[f"F_shear_{seed}"] = dv.shear_modulation(rg2, pg2, P, sp, seed=seed)
+        d2[f"F_hotspot_{seed}"] = dv.hotspot_modulation(rg2, pg2, P, sp, seed=seed)
+        d2[f"F_total_{seed}"] = dv.structure_modulation(rg2, pg2, P, sp, seed=seed)
+    d2["rg"], d2["phig"] = rg, phi
+    return d2
+
+
+def write_disk_v2_tables():
+    """disk_v2 analytic model (numpy only, imported as shipped): disk_v2.npz for the default parameters, disk_v2_alt.npz
+    for the second set of tests/disk_v2_sets.py -- radii from 0.5 r_in to 1.2 r_out with r_in and r_out among the points,
+    angles over [-40, 40]."""
+    if REF not in sys.path:
+        sys.path.insert(0, REF)
+    sys.path.insert(0, os.path.dirname(OUT))
+    import disk_v2 as dv
+    import disk_v2_sets as sets
+    P = dv.DiskV2Params()
+    d2 = disk_v2_tables(dv, P, None, np.linspace(1.5, 11.0, 64), np.linspace(1.5, 11.0, 48),
+                        np.linspace(0, 2 * np.pi, 96, endpoint=False))
+    d2["scalar_probe"] = np.array([dv.disk_half_thickness(3.0, P), dv.disk_radial_weight(2.0, P),
+                                   dv.disk_radial_weight(10.0, P), dv.angular_velocity_field(2.0, P),
+                                   dv.midplane_temperature_field(2.0, P), dv.density_field(4.0, 0.0, P)],
+                                  dtype=np.float64)
+    np.savez_compressed(os.path.join(OUT, "disk_v2.npz"), **d2)
+    P = dv.DiskV2Params(**sets.ALT["params"])
+    sp = dv.DiskV2StructureParams(**sets.ALT["structure"])
+    lo, hi = 0.5 * P.r_in, 1.2 * P.r_out
+    grid = lambda n: np.sort(np.concatenate([np.linspace(lo, hi, n - 2), [P.r_in, P.r_out]]))
+    d2 = disk_v2_tables(dv, P, sp, grid(64), grid(48), np.linspace(-40.0, 40.0, 96))
+    np.savez_compressed(os.path.join(OUT, "disk_v2_alt.npz"), **d2)
+
+
 def main():
     ref = import_reference()
     g = {}
@@ -192,38 +239,14 @@ def main():
             orb.append([n_frames, deg, fr, radius * np.cos(a), radius * np.sin(a), static[2]])
     np.savez(os.path.join(OUT, "orbit.npz"), rows=np.array(orb, dtype=np.float64))
 
-    # ---- disk_v2 analytic model (numpy only, imported as shipped) -----------------------
-    import disk_v2 as dv
-    P = dv.DiskV2Params()
-    r = np.linspace(1.5, 11.0, 64)
-    Hh = dv.disk_half_thickness(r, P)
-    zf = np.array([0.0, 0.25, -0.25, 1.0, -1.0, 1.1])
-    rr = np.repeat(r[:, None], len(zf), axis=1)
-    zz = zf[None, :] * np.asarray(Hh)[:, None]
-    d2 = dict(r=r, zf=zf, H=Hh, smooth=dv.geometry.smoothstep(0.0, 1.0, np.linspace(-0.5, 1.5, 41)),
-              mask_r=dv.disk_radial_mask(r, P), W_r=dv.disk_radial_weight(r, P),
-              W_z=dv.disk_vertical_weight(rr, zz, P), mask_vol=dv.disk_volume_mask(rr, zz, P),
-              omega=dv.angular_velocity_field(r, P), rho_mid=dv.midplane_density_field(r, P),
-              T_mid=dv.midplane_temperature_field(r, P), rho=dv.density_field(rr, zz, P),
-              T=dv.temperature_field(rr, zz, P),
-              scalar_probe=np.array([dv.disk_half_thickness(3.0, P), dv.disk_radial_weight(2.0, P),
-                                     dv.disk_radial_weight(10.0, P), dv.angular_velocity_field(2.0, P),
-                                     dv.midplane_temperature_field(2.0, P), dv.density_field(4.0, 0.0, P)],
-                                    dtype=np.float64))
-    phi = np.linspace(0, 2 * np.pi, 96, endpoint=False)
-    rg = np.linspace(1.5, 11.0, 48)
-    rg2, pg2 = np.meshgrid(rg, phi, indexing="ij")
-    d2["F_mode"] = dv.weak_mode_modulation(rg2, pg2, P)
-    for seed in (7, 42, 123):
-        d2[f"F_shear_{seed}"] = dv.shear_modulation(rg2, pg2, P, seed=seed)
-        d2[f"F_hotspot_{seed}"] = dv.hotspot_modulation(rg2, pg2, P, seed=seed)
-        d2[f"F_total_{seed}"] = dv.structure_modulation(rg2, pg2, P, seed=seed)
-    d2["rg"], d2["phig"] = rg, phi
-    np.savez_compressed(os.path.join(OUT, "disk_v2.npz"), **d2)
+    write_disk_v2_tables()
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)))
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["disk_v2"]:          # only the Disk V2 tables
+        write_disk_v2_tables()
+    else:
+        main()

@@ -36,7 +36,9 @@ def _frame(W, H, cam, fov, math, k=1, threshold=None, source=None, frozen_kw=())
     sky, tex = _scene()
     r = HipRenderer(W, H, sky, tex, math=math, supersample=k, supersample_threshold=threshold, **dict(frozen_kw))
     if source:
-        r.use_disk_v2(volume=source == "v2_volume")
+        from bhr_amd.disk_v2 import DiskV2Params
+        r.use_disk_v2(DiskV2Params(), volume=source == "v2_volume")     # (params=None would switch BACK to the texture)
+        assert r._dv2 is not None
     r.render_async(cam, fov, skip_bloom=True)
     out = dict(bg=r.read_layer(_lib.LAYER_BG), disk=r.read_layer(_lib.LAYER_DISK), c=r.counters())
     if threshold is not None and k > 1:

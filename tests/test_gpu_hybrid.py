@@ -185,6 +185,50 @@ def test_hybrid_strict_tiles_are_the_strict_frame_at_the_default_band(view, hip_
     r.close()
 
 
+@pytest.mark.parametrize("source", ["v2", "v2_volume"])
+def test_hybrid_with_a_disk_v2_source_is_the_strict_march(source, hip_lib):
+    """Hybrid does not split a frame whose disk comes from the Disk V2 model: include/bhr.h has it resolve to strict for
+    those sources (bhr_resolve_math: the model's kernels have no fast / strict list pair; bench.py and the CLI rely on
+    it).  No error is documented or returned, so the property the texture has on its strict tiles -- the pixels ARE the
+    strict march's -- must hold on every tile: BG and DISK of a math="hybrid" frame are the FORCE_STRICT frame bit for
+    bit, with the same ray steps, and no hybrid march is on record.  With adaptive supersampling on top the refinement
+    runs the model's LIST kernels (march_launch.hip: BHR_MK_LIST_DV2 / _VOLUME) under the same resolution.  The view is
+    one the texture splits into both tile kinds."""
+    from bhr_amd import HipRenderer, _lib, scenes
+    from bhr_amd.disk_v2 import DiskV2Params
+    from test_reference_kernels import E2E_KW
+    W, H, cam, fov = 320, 180, [6.0, 0.0, 0.5], 60.0
+    sky, tex = scenes.analytic_skybox(), scenes.noisy_disk()
+    kw = dict(E2E_KW, r_disk_outer=10.0)                                        # the model's radii
+    for extra in (dict(), dict(supersample=2, supersample_threshold=0.25)):
+        r = HipRenderer(W, H, sky, tex, math="hybrid", **dict(kw, **extra))
+        if not extra:
+            r.render_async(cam, fov, skip_bloom=True)
+            info = r.hybrid_info()
+            assert 0 < info["strict_tiles"] < info["tiles"], info            # the texture: both kinds of tiles
+        r.use_disk_v2(DiskV2Params(), volume=source == "v2_volume")
+        frames = {}
+        for math in ("hybrid", "strict"):
+            r.render_async(cam, fov, frame=25, skip_bloom=True, math=math)
+            frames[math] = (r.read_layer(_lib.LAYER_BG), r.read_layer(_lib.LAYER_DISK), r.counters()["ray_steps"],
+                            r.adaptive_info() if extra else None)
+        assert frames["strict"][1].max() > 0.3 and (frames["strict"][1].sum(axis=2) > 0).mean() > 0.1
+        np.testing.assert_array_equal(frames["hybrid"][0], frames["strict"][0])
+        np.testing.assert_array_equal(frames["hybrid"][1], frames["strict"][1])
+        assert frames["hybrid"][2:] == frames["strict"][2:]
+        if extra:
+            assert 0 < frames["hybrid"][3]["refined"] < W * H
+            assert frames["hybrid"][3]["strict"] == frames["hybrid"][3]["refined"]      # every refined pixel marched strict
+        fresh = HipRenderer(W, H, sky, tex, math="hybrid", **dict(kw, **extra))
+        fresh.use_disk_v2(DiskV2Params(), volume=source == "v2_volume")
+        fresh.render_async(cam, fov, frame=25, skip_bloom=True)
+        np.testing.assert_array_equal(fresh.read_layer(_lib.LAYER_DISK), frames["strict"][1])
+        with pytest.raises(AssertionError):                                             # BHR_ERR_STATE: no hybrid march has run
+            fresh.hybrid_info()
+        fresh.close()
+        r.close()
+
+
 def test_hybrid_in_row_blocks(hip_lib):
     """Hybrid tiles in a group render (pipelined: band lists x strict / fast lists = four launches per tile) against one
     hybrid context: the classification is per 8x8 tile of the image, so the pixels are the same ones."""

@@ -59,6 +59,72 @@ def test_volume_matches_oracle_strict(view, oracle, hip_lib):
     hip.close()
 
 
+# ---- where the bounding-slab cull of volume_segment (csrc/march_device.h) can bite --------------------------------
+# The kernel skips a chord whose two ends lie outside a slab derived in bhr_set_disk_source (|zeta| <= max H, r_in <= |p|,
+# |p| <= sqrt(r_out^2 + max H^2)); the oracle samples every chord.  96 x 54 frames (the last 8-row tile is partial)
+# unless a case names its own size.
+THICK = dict(h0=0.25, beta_h=0.3)            # flares outwards: H(r_out) = 4.05 is the maximum
+INWARD = dict(h0=0.25, beta_h=-1.5)          # H(r) = h0 r_in (r / r_in)^-0.5: H(r_in) = 0.5 is the maximum, H(r_out) = 0.22
+CAM0, CAM60 = dict(cam=[9.0, 0.0, 0.6], fov=70, tilt=0.0), dict(cam=[7.0, 2.0, 2.5], fov=80, tilt=60.0)
+ABOVE0 = dict(cam=[8.0, 0.0, 6.0], fov=70, tilt=0.0)   # the thick disk from outside its flare: CAM0 sits inside it (H(9) = 3.5)
+CULL_CASES = {
+    "thick_tilt0": dict(params=THICK, **ABOVE0),
+    "thick_tilt60": dict(params=THICK, **CAM60),
+    "inward_tilt0": dict(params=INWARD, **CAM0),
+    "inward_tilt60": dict(params=INWARD, **CAM60),
+    "camera_inside_slab": dict(params=THICK, cam=[6.0, 0.0, 0.02], fov=70, tilt=0.0),     # the first chord starts in the volume
+    "camera_on_axis": dict(params=THICK, cam=[0.0, 0.0, 9.0], fov=90, tilt=0.0),          # down the pole
+    "sharp_edge_on": dict(params=dict(edge_softness=0.0), cam=[12.0, 0.0, 0.05], fov=70, tilt=0.0),   # density up to r_out
+    "substeps1": dict(params=THICK, substeps=1, **ABOVE0),
+    "substeps16": dict(params=THICK, substeps=16, **ABOVE0),
+    "absorption50": dict(params=THICK, absorption=50.0, **ABOVE0),                          # rays stop at BHR_VOLUME_OPAQUE
+    # One row of 16384 rays in the disk plane, 2e-4 apart, at step_size 0.5: chords 1.6 long near r_out, so that among the
+    # ~80 rays tangent within 0.016 below r_out some have a chord whose two ends lie beyond the slab's outer radius
+    # (10.0146) while its middle, where the single sample is taken, lies inside r_out -- in the sharp-edged disk, where the
+    # density there is 0.2.  The cull of the parent commit read the ends alone and dropped those samples (70 pixels, up to
+    # 1.9e-2; found with the cull restated inside the oracle); volume_segment now allows for half the chord.
+    "coarse_step_tangent": dict(params=dict(edge_softness=0.0), cam=[12.2, 0.0, 0.0], fov=float(np.degrees(2 * np.arctan(1e-4))),
+                                tilt=0.0, size=(16384, 1), step=0.5, substeps=1, absorption=1.0),   # Ca = 1: the hot inner disk shows through
+}
+# Measured (MI355X), largest per-channel RMSE / max |difference|:   BG                   DISK
+#   thick_tilt0          2.5e-07 / 6.1e-06   3.4e-08 / 2.4e-07     thick_tilt60         1.1e-07 / 2.0e-06   3.3e-08 / 1.5e-07
+#   inward_tilt0         5.0e-07 / 6.1e-06   2.3e-08 / 1.8e-07     inward_tilt60        5.7e-07 / 5.8e-06   2.2e-08 / 2.4e-07
+#   camera_inside_slab   3.5e-09 / 9.8e-08   3.7e-08 / 2.4e-07     camera_on_axis       2.9e-07 / 5.3e-06   2.9e-08 / 2.4e-07
+#   sharp_edge_on        6.3e-07 / 6.1e-06   7.9e-09 / 1.8e-07     substeps1            2.5e-07 / 6.1e-06   3.6e-08 / 2.4e-07
+#   substeps16           2.5e-07 / 6.1e-06   3.4e-08 / 2.4e-07     absorption50         2.1e-07 / 6.1e-06   2.8e-08 / 1.8e-07
+#   coarse_step_tangent  7.8e-08 / 2.8e-06   1.3e-08 / 1.2e-07     (the parent commit's cull: see the mutation note in the case)
+
+
+@pytest.mark.parametrize("case", list(CULL_CASES))
+def test_volume_cull_matches_oracle_strict(case, oracle, hip_lib):
+    from bhr_amd import HipRenderer, _lib, disk_v2 as dv
+    c = CULL_CASES[case]
+    P = dv.DiskV2Params(**c["params"])
+    vol = dict(substeps=c.get("substeps", 3), absorption=c.get("absorption", 4.0), grazing_gain=1.0)
+    sky, tex = scenes.analytic_skybox(), scenes.noisy_disk()
+    kw = dict(step_size=c.get("step", 0.1), r_disk_inner=P.r_in, r_disk_outer=P.r_out, disk_tilt=c["tilt"])
+    CULL_W, CULL_H = c.get("size", (96, 54))
+    hip = HipRenderer(CULL_W, CULL_H, sky, tex, math="strict", **kw)
+    hip.use_disk_v2(P, seed=42, volume=True, **vol)
+    cp, m_s, m_h, t_peak = hip._dv2
+    ora = oracle.OracleRenderer(CULL_W, CULL_H, sky, tex, **kw)
+    ora.set_volume(cp, m_s, m_h, t_peak, vol["absorption"], vol["grazing_gain"], vol["substeps"])
+    try:
+        hip.render_async(c["cam"], c["fov"], frame=25, skip_bloom=True)
+        bg, disk = hip.read_layer(_lib.LAYER_BG), hip.read_layer(_lib.LAYER_DISK)
+        rbg, rdisk = (x.transpose(1, 0, 2) for x in ora.march(c["cam"], c["fov"], frame=25))
+    finally:
+        ora.set_volume(None)
+    assert rdisk.max() > 0.3 and (rdisk.sum(axis=2) > 0).mean() > 0.1          # the disk is really in view
+    for name, a, b in (("bg", bg, rbg), ("disk", disk, rdisk)):
+        e, m = _rmse(a, b), float(np.abs(a - b).max())
+        print(f"\n[{case} {name}] RMSE {e.max():.3g} max {m:.3g}")
+        assert (e <= 1e-5).all(), f"{case}/{name}: RMSE {e}"
+        assert m <= 2e-4, f"{case}/{name}: max {m} at {np.unravel_index(np.abs(a - b).argmax(), a.shape)}"
+    assert hip.counters()["ray_steps"] == ora.last_total_steps
+    hip.close()
+
+
 def test_volume_fast_math_against_binary64(oracle, hip_lib):
     from bhr_amd import _lib
     v = VIEWS["edge_on"]

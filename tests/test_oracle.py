@@ -195,12 +195,13 @@ def test_differentials_do_not_change_aa_off_pixels(oracle):
 
 
 # ---- Disk V2 restatement in the oracle, pinned by the reference package's own tables ----------------
-def test_oracle_disk_v2_fields_match_reference_tables(oracle):
+def _check_oracle_disk_v2_tables(oracle, which):
     import bhr_amd  # noqa: F401
     from bhr_amd import disk_v2 as dv
-    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "disk_v2.npz"))
-    P = dv.DiskV2Params()
-    cp = dv.pack_params(P)
+    import disk_v2_sets as sets
+    gold = np.load(os.path.join(G, sets.SETS[which]["fixture"]))
+    P, sp = sets.make(which)
+    cp = dv.pack_params(P, sp)
     tol = dict(rtol=2e-14, atol=1e-15)
     r, zf = gold["r"], gold["zf"]
     rr = np.repeat(r[:, None], len(zf), axis=1)
@@ -220,8 +221,7 @@ def test_oracle_disk_v2_fields_match_reference_tables(oracle):
     np.testing.assert_allclose(ev(dv.F_MODE, rg, None, pg), gold["F_mode"], rtol=1e-13, atol=1e-14)
     for seed in (7, 42, 123):
         # the reference normalises each signed sum by its maximum over the evaluated array
-        cs = dv.pack_params(P, None, shear_seed=seed, hotspot_seed=seed)
-        sp = dv.DiskV2StructureParams()
+        cs = dv.pack_params(P, sp, shear_seed=seed, hotspot_seed=seed)
         raw_s = oracle.dv2_eval(cs, dv.F_SHEAR, rg, None, pg)
         raw_h = oracle.dv2_eval(cs, dv.F_HOTSPOT, rg, None, pg)
         wr = oracle.dv2_eval(cs, dv.F_W_R, rg) > 0
@@ -229,11 +229,184 @@ def test_oracle_disk_v2_fields_match_reference_tables(oracle):
         f_h = np.where(wr, 1.0 + sp.hotspot_strength * raw_h / np.abs(raw_h).max(), 1.0)
         np.testing.assert_allclose(f_s, gold[f"F_shear_{seed}"], rtol=1e-12, atol=1e-13)
         np.testing.assert_allclose(f_h, gold[f"F_hotspot_{seed}"], rtol=1e-12, atol=1e-13)
-        ct = dv.pack_params(P, None, shear_seed=seed, hotspot_seed=seed + 1)      # structure_modulation: seed, seed + 1
+        ct = dv.pack_params(P, sp, shear_seed=seed, hotspot_seed=seed + 1)      # structure_modulation: seed, seed + 1
         m_s = np.abs(oracle.dv2_eval(ct, dv.F_SHEAR, rg, None, pg)).max()
         m_h = np.abs(oracle.dv2_eval(ct, dv.F_HOTSPOT, rg, None, pg)).max()
         np.testing.assert_allclose(oracle.dv2_eval(ct, dv.F_TOTAL, rg, None, pg, norm_shear=m_s, norm_hotspot=m_h),
                                    gold[f"F_total_{seed}"], rtol=1e-12, atol=1e-13)
+
+
+def test_oracle_disk_v2_fields_match_reference_tables(oracle):
+    _check_oracle_disk_v2_tables(oracle, "default")
+
+
+def test_oracle_disk_v2_fields_match_reference_tables_alt(oracle):
+    """The same tables from the reference package at the second parameter set (tests/disk_v2_sets.py): 32 shear
+    components and hotspots, radii 0.5 r_in .. 1.2 r_out with both radii among the points, angles over [-40, 40]."""
+    _check_oracle_disk_v2_tables(oracle, "alt")
+
+
+# ---- the Disk V2 surface source of the oracle ----------------------------------------------------------
+def _np_tint(temp):
+    """_color_temp_to_tint (render.py:2407-2437) in NumPy float32, one IEEE operation per statement of the reference."""
+    f = np.float32
+    t = (temp / f(100.0)).astype(f)
+    hot = np.maximum(t - f(60.0), f(0.0001))
+    r = np.where(t > f(66.0), np.clip(f(1.292936) * np.power(hot, f(-0.1332047592)), f(0), f(1)), f(1.0))
+    g = np.where(t <= f(66.0), np.clip(f(0.390082) * np.log(np.maximum(t, f(0.0001))) - f(0.631841), f(0), f(1)),
+                 np.clip(f(1.129891) * np.power(hot, f(-0.0755148492)), f(0), f(1)))
+    b_log = np.clip(f(0.543207) * np.log(np.maximum(t - f(10.0), f(0.0001))) - f(1.19625), f(0), f(1))
+    b = np.where(t < f(66.0), np.where(t <= f(19.0), f(0.0), b_log), f(1.0))
+    return np.stack([r, g, b], axis=-1).astype(f), t
+
+
+def _np_dv2_color(tf):
+    """The mapping above disk_v2_color in csrc/march_device.h (the compose kernel's, render.py:3243-3257) in float32:
+    T_K = T_min + t (T_max - T_min), rgb = tint(T_K) sqrt(t) with blue <= red, clamped to [0, 1]."""
+    f = np.float32
+    tf = tf.astype(f)
+    t_factor = (f(6000.0) - f(4500.0)) / (f(6500.0) - f(2700.0))
+    T_min, T_max = f(2000.0) + t_factor * f(1000.0), f(9000.0) + t_factor * f(3000.0)
+    c, tk = _np_tint(T_min + tf * (T_max - T_min))
+    c[..., 2] = np.minimum(c[..., 2], c[..., 0])
+    lum = np.clip(np.sqrt(tf), f(0), f(1))
+    return np.clip(c * lum[..., None], f(0), f(1)), tk
+
+
+# The longest path of the mapping from t to a channel: T_K = T_min + t * dT (2 operations), / 100, - 10 (or - 60), log (or
+# pow), * coefficient, - offset, sqrt(t), * lum: 9 operations, each at most 1 ulp of its own result away from the NumPy
+# restatement of the same operation (the basic ones are IEEE and agree exactly; libm's logf / powf against NumPy's need
+# the ulp).  What follows tk is below 8 in magnitude (log(tk) <= log(102) = 4.6), so its ulp is at most 2^-21, and is
+# carried to the channel with a gain of at most 1 (coefficients < 1.3 on slopes < 1, lum <= 1): 6 x 2^-21.  The three
+# operations that make tk <= 128 (ulp 2^-17) reach the channel through the steepest slope of the mapping,
+# 0.543207 / (tk - 10) <= 0.04 at tk >= 23.9: 3 x 2^-17 x 0.04.
+_COLOUR_BAR = 6 * 2.0 ** -21 + 3 * 2.0 ** -17 * 0.04          # 3.8e-6
+# alpha = (float)clamp(rho_mid F): the binary64 product, rounded once (half an ulp of a value <= 1).  The angle the test
+# hands to dv2_eval is NumPy's arctan2 + t Omega, libm's in the oracle: one ulp of an angle <= 600 (1.1e-13) through raw
+# sums whose slope in phi is below 32 terms x 10: 4e-11.
+_ALPHA_BAR = 2.0 ** -25 + 4e-11
+
+
+def _dv2_hit_points(P):
+    """Hit points of the disk plane for the probe: r at both radii exactly and one ulp either side of each (on the x
+    axis, where sqrt(x^2 + 0) is exact), and a polar fan over the disk and beyond both edges."""
+    edge = [np.nextafter(P.r_in, 0), P.r_in, np.nextafter(P.r_in, 99), np.nextafter(P.r_out, 0), P.r_out,
+            np.nextafter(P.r_out, 99)]
+    pts = [(s * r, 0.0) for r in edge for s in (1.0, -1.0)]
+    rr = np.concatenate([np.linspace(0.4 * P.r_in, 1.2 * P.r_out, 181), np.geomspace(P.r_in, 1.2 * P.r_in, 120)])
+    for k, r in enumerate(rr):
+        a = 2.399963 * k                                           # golden-angle fan
+        pts.append((r * np.cos(a), r * np.sin(a)))
+    return np.array(pts, dtype=np.float64), len(edge) * 2
+
+
+@pytest.mark.parametrize("which", ["default", "alt", "sharp"])
+@pytest.mark.parametrize("t_offset", [0.0, 2.5, 400.0])
+def test_probe_dv2_rgba_is_the_documented_mapping(oracle, which, t_offset):
+    """probe_dv2_rgba against a NumPy composition of the fields the reference tables pin (OMEGA, T_MID, RHO_MID, F_TOTAL)
+    and the float32 restatement of the colour mapping above."""
+    import bhr_amd  # noqa: F401
+    from bhr_amd import disk_v2 as dv
+    import disk_v2_sets as sets
+    P, sp = sets.make(which)
+    cp = dv.pack_params(P, sp, shear_seed=42, hotspot_seed=43)
+    rg, pg = np.meshgrid(np.linspace(P.r_in, P.r_out, 64), np.linspace(0, 2 * np.pi, 128, endpoint=False), indexing="ij")
+    m_s = np.abs(oracle.dv2_eval(cp, dv.F_SHEAR, rg, None, pg)).max()
+    m_h = np.abs(oracle.dv2_eval(cp, dv.F_HOTSPOT, rg, None, pg)).max()
+    t_peak = oracle.dv2_eval(cp, dv.F_T_MID, np.linspace(P.r_in, P.r_out, 512)).max()
+    xy, n_edge = _dv2_hit_points(P)
+    got = oracle.probe_dv2_rgba(cp, (m_s, m_h), t_peak, xy, t_offset)
+
+    r = np.sqrt(xy[:, 0] ** 2 + xy[:, 1] ** 2)
+    assert (r[:n_edge:2] == r[1:n_edge:2]).all() and P.r_in in r and P.r_out in r
+    phi = np.arctan2(xy[:, 1], xy[:, 0]) + t_offset * oracle.dv2_eval(cp, dv.F_OMEGA, r)
+    F = oracle.dv2_eval(cp, dv.F_TOTAL, r, None, phi, norm_shear=m_s, norm_hotspot=m_h)
+    t = np.clip(oracle.dv2_eval(cp, dv.F_T_MID, r) * F / t_peak, 0.0, 1.0)
+    rho = np.clip(oracle.dv2_eval(cp, dv.F_RHO_MID, r) * F, 0.0, 1.0)
+    rgb, tk = _np_dv2_color(t)
+    # both branches of the tint at tk = 66 are taken; tk <= 19 cannot be: t = 0 gives T_min = 2394.7 K, tk = 23.9
+    assert (tk > 66).sum() > 10 and ((tk < 66) & (t > 0)).sum() > 10 and tk.min() > 19
+    assert t.max() > 0.9 and rho.max() > 0.5 and (t[r <= P.r_in] == 0).all() and (rho[r >= P.r_out] == 0).all()
+    assert np.abs(got[:, :3] - rgb).max() <= _COLOUR_BAR, np.abs(got[:, :3] - rgb).max()
+    assert np.abs(got[:, 3] - rho).max() <= _ALPHA_BAR, np.abs(got[:, 3] - rho).max()
+    assert (got[:, 3] == got[:, 3].astype(np.float32)).all()       # alpha is a binary32 value
+    # the binary64 build runs the colour mapping in binary64: the same bar, now against the rounding-free value
+    exact = oracle.probe_dv2_rgba(cp, (m_s, m_h), t_peak, xy, t_offset, fast="f64")
+    assert np.abs(got[:, :3] - exact[:, :3]).max() <= _COLOUR_BAR
+    np.testing.assert_allclose(exact[:, 3], rho, rtol=0, atol=4e-11)
+
+
+def test_tint_branches_the_mapping_cannot_reach(oracle):
+    """tk = 19 (blue switches off) lies below every temperature disk_v2_color asks for, so it is held to the NumPy
+    restatement directly: both sides of 1900 K and of 6600 K, to 1 ulp per operation (4 at most: / 100, - 10, log, *, -)."""
+    temps = np.array([1000.0, 1899.0, 1900.0, np.nextafter(np.float32(1900.0), np.float32(1e9)), 1901.0, 2400.0, 6599.0,
+                      6600.0, np.nextafter(np.float32(6600.0), np.float32(1e9)), 6601.0, 10184.0], dtype=np.float32)
+    want, _ = _np_tint(temps)
+    got = oracle.probe_tint(temps)
+    assert np.abs(got - want).max() <= 5 * 2.0 ** -21
+    assert (got[:3, 2] == 0).all() and got[5, 2] > 0.2 and (got[9:, 2] == 1).all() and (got[:8, 0] == 1).all()
+
+
+def _surface_oracle(oracle, which, flat=False, fast=False, **kw):
+    import bhr_amd  # noqa: F401
+    from bhr_amd import disk_v2 as dv, scenes
+    import disk_v2_sets as sets
+    P, sp = sets.make(which)
+    if flat:
+        sp = dv.DiskV2StructureParams(mode1_strength=0.0, mode2_strength=0.0, shear_strength=0.0, hotspot_strength=0.0)
+    cp = dv.pack_params(P, sp, shear_seed=42, hotspot_seed=43)
+    rg, pg = np.meshgrid(np.linspace(P.r_in, P.r_out, 64), np.linspace(0, 2 * np.pi, 128, endpoint=False), indexing="ij")
+    norms = (np.abs(oracle.dv2_eval(cp, dv.F_SHEAR, rg, None, pg)).max(), np.abs(oracle.dv2_eval(cp, dv.F_HOTSPOT, rg, None, pg)).max())
+    t_peak = oracle.dv2_eval(cp, dv.F_T_MID, np.linspace(P.r_in, P.r_out, 512)).max()
+    args = dict(step_size=0.1, r_disk_inner=P.r_in, r_disk_outer=P.r_out, disk_tilt=20.0)
+    args.update(kw)
+    ora = oracle.OracleRenderer(48, 27, scenes.analytic_skybox(32, 64), np.zeros((8, 16, 4), np.float32), fast=fast, **args)
+    return ora, cp, norms, t_peak
+
+
+@pytest.mark.parametrize("which,gate", [("default", None), ("alt", None), ("default", (3.5, 6.0))])
+def test_surface_frame_shades_its_crossings_with_the_probe(oracle, which, gate):
+    """A frame in surface mode: at every crossing the march's loop records (oracle_set_hits_out), the RGBA it composites
+    is bit for bit the probe's at that point and that frame's t_offset; crossings are gated by the RENDERER's radii
+    (the model gates its fields by its own); pixels without a crossing carry no disk, and switching the source off
+    restores the textured frame."""
+    kw = {} if gate is None else dict(r_disk_inner=gate[0], r_disk_outer=gate[1])
+    ora, cp, norms, t_peak = _surface_oracle(oracle, which, **kw)
+    cam, fov = [7.0, 2.0, 2.5], 80
+    textured = ora.march(cam, fov, frame=25)
+    ora.set_disk_v2_surface(cp, norms[0], norms[1], t_peak)
+    try:
+        for frame, diff in ((0, False), (25, True)):
+            img, disk, rows = ora.crossings(cam, fov, frame=frame, skip_differentials=diff)
+            assert len(rows) > 300 and disk.max() > 0.3
+            want = oracle.probe_dv2_rgba(cp, norms, t_peak, rows[:, 2:4], frame * ora.disk_rotation_speed)
+            np.testing.assert_array_equal(rows[:, 4:], want)
+            hit_r = np.sqrt(rows[:, 2].astype(np.float32) ** 2 + rows[:, 3].astype(np.float32) ** 2)
+            assert hit_r.min() >= np.float32(ora.r_disk_inner) and hit_r.max() <= np.float32(ora.r_disk_outer)
+            crossed = np.zeros(disk.shape[:2], bool)
+            crossed[rows[:, 0].astype(int), rows[:, 1].astype(int)] = True
+            assert not disk[~crossed].any() and (disk[crossed].sum(axis=1) > 0).mean() > 0.9
+            np.testing.assert_array_equal(ora.march(cam, fov, frame=frame, skip_differentials=diff)[1], disk)   # the hook is passive
+    finally:
+        ora.set_disk_v2_surface(None)
+    for a, b in zip(textured, ora.march(cam, fov, frame=25)):
+        np.testing.assert_array_equal(a, b)
+
+
+def test_surface_advection_needs_structure(oracle):
+    """phi_adv = phi + t Omega(r): with every structure strength 0 the frame is the same at frame 0 and frame 40, with
+    the default structure it is not -- in both builds of the oracle."""
+    for fast in (False, "f64"):
+        frames = {}
+        for flat in (True, False):
+            ora, cp, norms, t_peak = _surface_oracle(oracle, "default", flat=flat, fast=fast)
+            ora.set_disk_v2_surface(cp, 1.0 if flat else norms[0], 1.0 if flat else norms[1], t_peak)
+            try:
+                frames[flat] = [ora.march([7.0, 2.0, 2.5], 80, frame=f)[1] for f in (0, 40)]
+            finally:
+                ora.set_disk_v2_surface(None)
+        np.testing.assert_array_equal(frames[True][0], frames[True][1])
+        assert frames[True][0].max() > 0.3 and np.abs(frames[False][0] - frames[False][1]).mean() > 1e-3
 
 
 # ---- the restated integrator against an independent one -------------------------------------------------
