@@ -788,6 +788,18 @@ int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     return post_on_slot(ctx, flags, k, ring);
 }
 
+// The end of a shutter frame of n samples on slot k, marched or from the ray map: closes the march bracket behind the last
+// sample -- the samples count into the frame's one ring cell and share its events -- then the post-pass on the resolved layers.
+int32_t shutter_close_on_slot(bhr_ctx *ctx, int n, uint32_t flags, int k, int ring) {
+    bhr_frame_slot &f = ctx->slots[k];
+    BHR_HIP(hipEventRecord(ctx->ring_ev[ring * 3 + 1], f.stream));
+    ctx->march_end_recorded = 1;
+    ctx->counters.rays *= (uint64_t)n;
+    f.march_done = ctx->ring_ev[ring * 3 + 1];
+    if (f.frame_split) BHR_TRY(bhr_launch_bloom_pack(ctx));            // the resolved disk layer -> the H pass's operands, bg + disk
+    return post_on_slot(ctx, flags, k, ring);
+}
+
 // A shutter frame on slot k (bhr_render_shutter): n skip-bloom marches into the slot's layers, each followed by its
 // accumulation launch (shutter.hip), then the post-pass on the resolved layers as bhr_bloom runs it.  All on the slot's
 // stream; a two-stream hybrid sample forks onto the slot's second stream and joins before its accumulation, and the next
@@ -806,17 +818,20 @@ int32_t shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, int n, uint32_t fl
         if (adaptive) BHR_TRY(bhr_launch_adaptive(ctx, call));
         if (n > 1) BHR_TRY(bhr_launch_shutter_accumulate(ctx, j, n));
     }
-    BHR_HIP(hipEventRecord(ctx->ring_ev[ring * 3 + 1], f.stream));
-    ctx->march_end_recorded = 1;
-    ctx->counters.rays *= (uint64_t)n;
-    f.march_done = ctx->ring_ev[ring * 3 + 1];
-    if (f.frame_split) BHR_TRY(bhr_launch_bloom_pack(ctx));            // the resolved disk layer -> the H pass's operands, bg + disk
-    return post_on_slot(ctx, flags, k, ring);
+    return shutter_close_on_slot(ctx, n, flags, k, ring);
 }
 
 // The fix launch of a map frame: the strict fix kernel over the map's overflow list (a grid for the list's capacity).
 bhr_march_part raymap_fix_part(const bhr_raymap &rm) {
     return {nullptr, 0, /* first */ 0, /* last */ 1, BHR_MATH_STRICT, /* repair */ 2, rm.a.over_count, rm.a.over_list, rm.over_cap};
+}
+
+// The launches of one frame from the map `rm` under `call`: the shade kernel over the stored records, turned by (c, s), then the
+// strict fix kernel over the overflow list (which, unless the call defers it, records the ring slot's march-end event).
+int32_t raymap_frame_launches(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm, float c, float s) {
+    BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, c, s));
+    const bhr_march_part part = raymap_fix_part(rm);
+    return bhr_launch_march(ctx, call, &part);
 }
 
 // A frame from the context's ray map on slot k (bhr_raymap_render): the shade kernel over the stored records, then the strict
@@ -832,9 +847,7 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     // a supersampled map: the call carries the map's factor, so both launches work on the fine frame and the fix launch takes
     // march_fix_ss_kernel, which resolves the overflow list's whole groups
     const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ false, /* ss */ rm.ss};
-    BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, rot_c, rot_s));
-    const bhr_march_part part = raymap_fix_part(rm);
-    BHR_TRY(bhr_launch_march(ctx, call, &part));       // records the ring slot's march-end event
+    BHR_TRY(raymap_frame_launches(ctx, call, rm, rot_c, rot_s));
     f.march_done = ctx->ring_ev[ring * 3 + 1];
     return post_on_slot(ctx, flags, k, ring);
 }
@@ -862,18 +875,11 @@ int32_t raymap_shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, const BhrSh
         for (int j = 0; j < n; ++j) {
             const bhr_march_call call = {&cams[j], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ rm.ss,
                                          /* keep_start */ j > 0};
-            BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, smp.smp[j].c, smp.smp[j].s));
-            const bhr_march_part part = raymap_fix_part(rm);
-            BHR_TRY(bhr_launch_march(ctx, call, &part));
+            BHR_TRY(raymap_frame_launches(ctx, call, rm, smp.smp[j].c, smp.smp[j].s));
             if (n > 1) BHR_TRY(bhr_launch_shutter_accumulate(ctx, j, n));
         }
     }
-    BHR_HIP(hipEventRecord(ctx->ring_ev[ring * 3 + 1], f.stream));
-    ctx->march_end_recorded = 1;
-    ctx->counters.rays *= (uint64_t)n;
-    f.march_done = ctx->ring_ev[ring * 3 + 1];
-    if (f.frame_split) BHR_TRY(bhr_launch_bloom_pack(ctx));            // the resolved disk layer -> the H pass's operands, bg + disk
-    return post_on_slot(ctx, flags, k, ring);
+    return shutter_close_on_slot(ctx, n, flags, k, ring);
 }
 
 // A frame on the context's next frame slot: orders the slot's stream behind the scene stream, points the launchers at the
@@ -1038,12 +1044,17 @@ int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint
 
 // A frame from the ray map (include/bhr.h): the build camera with the caller's t_offset, the strict arithmetic, the build's
 // choice of differentials.  Like bhr_render_shutter it neither triggers nor counts towards the calibration of slot 1's stream.
+// The flag word of a frame from the map: the strict arithmetic, the build's choice of differentials.
+uint32_t raymap_frame_flags(const bhr_ctx *ctx, uint32_t flags) {
+    return flags | BHR_FORCE_STRICT | (ctx->raymap->diff ? 0u : BHR_SKIP_DIFFERENTIALS);
+}
+
 int32_t bhr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
     BHR_TRY(bhr_raymap_check_render(ctx, t_offset, flags));
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     bhr_camera cam = ctx->raymap->cam;
     cam.t_offset = t_offset;
-    const uint32_t fl = flags | BHR_FORCE_STRICT | (ctx->raymap->diff ? 0u : BHR_SKIP_DIFFERENTIALS);
+    const uint32_t fl = raymap_frame_flags(ctx, flags);
     return frame_on_next_slot(ctx, fl, false, [&](int k, int ring) { return raymap_on_slot(ctx, &cam, fl, k, ring); });
 }
 
@@ -1054,7 +1065,7 @@ int32_t bhr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fla
     BHR_TRY(bhr_raymap_check_render_view(ctx, cam, flags, &rot_c, &rot_s));
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     const bhr_camera view = *cam;
-    const uint32_t fl = flags | BHR_FORCE_STRICT | (ctx->raymap->diff ? 0u : BHR_SKIP_DIFFERENTIALS);
+    const uint32_t fl = raymap_frame_flags(ctx, flags);
     return frame_on_next_slot(ctx, fl, false, [&](int k, int ring) { return raymap_on_slot(ctx, &view, fl, k, ring, rot_c, rot_s); });
 }
 
@@ -1065,7 +1076,7 @@ int32_t bhr_raymap_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t 
     bool turned = false;
     BHR_TRY(bhr_raymap_check_render_shutter(ctx, cams, n, flags, &smp, &turned));
     BHR_HIP(hipSetDevice(ctx->cfg.device));
-    const uint32_t fl = flags | BHR_FORCE_STRICT | (ctx->raymap->diff ? 0u : BHR_SKIP_DIFFERENTIALS);
+    const uint32_t fl = raymap_frame_flags(ctx, flags);
     return frame_on_next_slot(ctx, fl, false, [&](int k, int ring) { return raymap_shutter_on_slot(ctx, cams, smp, turned, fl, k, ring); });
 }
 

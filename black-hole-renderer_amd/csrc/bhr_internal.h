@@ -162,7 +162,7 @@ enum bhr_march_kernel {
     BHR_MK_RAYMAP_SHADE_ROT,  // raymap_shade_kernel<diff, true>: the same with the records turned about z       raymap
     BHR_MK_RAYMAP_SHUTTER,      // raymap_shade_shutter_kernel<diff, false>: the mean of n such frames, one launch   raymap
     BHR_MK_RAYMAP_SHUTTER_ROT,  // raymap_shade_shutter_kernel<diff, true>: each sample turned about z by its own angle  raymap
-    // (ss: BUILD, SHADE and SHADE_ROT have twins for a supersampled map, raymap_build_ss_kernel / raymap_shade_ss_kernel; the shutter kernels have none)
+    // (ss: BUILD, SHADE and SHADE_ROT have twins for a supersampled map, raymap_build_kernel<DIFF, true> / raymap_shade_ss_kernel; the shutter kernels have none)
 };
 
 // The ray map as its two kernels see it (march_raymap.hip): second kernel argument, behind the march's own block.  Planar: every

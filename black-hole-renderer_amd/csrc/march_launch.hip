@@ -459,16 +459,22 @@ int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     return BHR_OK;
 }
 
+// What both shade launchers begin with: a scene to shade, the argument block `a` of call's frame at factor ss, and a map that
+// fits it.  api: the public call a refusal names.
+static int32_t raymap_shade_args(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, int32_t ss, const char *api, BhrMarchArgs &a) {
+    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "%s: no skybox set (bhr_set_skybox)", api);
+    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "%s: no disk texture set (bhr_set_disk_texture)", api);
+    march_args(ctx, call, nullptr, ss, false, a);
+    if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5)) return bhr_fail(BHR_ERR_STATE, "%s: the map does not fit the frame", api);
+    return BHR_OK;
+}
+
 // rot_c, rot_s: the turn about z of call.cam from the map's build camera (bhr_raymap_render_view); 1, 0 is no turn and takes the
 // kernel without one, whose frame is the strict frame bit for bit.
 int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c, float rot_s) {
-    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no skybox set (bhr_set_skybox)");
-    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no disk texture set (bhr_set_disk_texture)");
     // call.ss: the map's factor -- the block of the fine frame (k W x k rows, k^2 W rows == the map's plane), a wave per fine tile
     BhrMarchArgs a;
-    march_args(ctx, call, nullptr, call.ss, false, a);
-    if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5))
-        return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: the map does not fit the frame");
+    BHR_TRY(raymap_shade_args(ctx, call, m, diff, call.ss, "bhr_raymap_render", a));
     const bool turned = !(rot_c == 1.0f && rot_s == 0.0f);
     const void *fn = bhr_march_kernel_raymap(turned ? BHR_MK_RAYMAP_SHADE_ROT : BHR_MK_RAYMAP_SHADE, diff, call.ss > 1);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no shade kernel in this library");
@@ -489,14 +495,10 @@ int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const 
 // position, are taken from the samples' table inside the kernel instead -- the map, and that table by value.  The caller closes
 // the march bracket.
 int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrShutterArgs &smp, bool turned) {
-    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: no skybox set (bhr_set_skybox)");
-    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: no disk texture set (bhr_set_disk_texture)");
+    BhrMarchArgs a;
+    BHR_TRY(raymap_shade_args(ctx, call, m, diff, 1, "bhr_raymap_render_shutter", a));
     if (smp.n < 1 || smp.n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render_shutter: %d samples (1 .. %d)", smp.n, BHR_SHUTTER_MAX_SAMPLES);
     if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: the fused launch has no supersampled kernel (factor %d)", call.ss);
-    BhrMarchArgs a;
-    march_args(ctx, call, nullptr, 1, false, a);
-    if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5))
-        return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: the map does not fit the frame");
     if (a.diskp) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: the fused launch takes a skip-bloom call (it stores no packed bloom operands)");
     const void *fn = bhr_march_kernel_raymap(turned ? BHR_MK_RAYMAP_SHUTTER_ROT : BHR_MK_RAYMAP_SHUTTER, diff, 0);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: no shutter shade kernel in this library");

@@ -1,7 +1,14 @@
 // march_raymap.hip -> march_raymap.o: the ray map's kernels (build, shade, shade turned about z, shade all samples of a shutter
-// frame), and nothing else, in a strict object of their own
+// frame, and the build and shade kernels of a supersampled map), and nothing else, in a strict object of their own
 // (-ffp-contract=off, no fast-math, the ILP-first scheduler).  They are made of the strict march's device functions --
 // Ray<DIFF, 0>, Pending, shade_hit, sample_skybox, store_pixel (ray_strict.h, march_device.h).
+//
+// The layout: three pieces of device code, each written once.
+//   raymap_build_kernel<DIFF, SS>     the march that records; SS: the build of a supersampled map
+//   raymap_shade_records<DIFF, ROT>   a lane's records -> its Shade       the three shade kernels
+//   raymap_values<ROT>                Shade, fate, direction -> values    the three shade kernels
+// A shade kernel is its pixel mapping, those two calls and its own way to store: store_pixel (raymap_shade_kernel), the mean
+// over the samples (raymap_shade_shutter_kernel), resolve_store over the k x k groups (raymap_shade_ss_kernel).
 //
 // A ray's path depends on the camera and the geometry of bhr_config only, not on the skybox, the disk texture or t_offset.
 // raymap_build_kernel marches a whole-frame view once with the strict Ray and, where the tile kernel shades a parked crossing
@@ -29,11 +36,18 @@
 
 namespace {
 
+// ---- the build ----------------------------------------------------------------------------------------------------------------
 // One 8x8 tile per wave, tiles in the march's launch order (longest rays first).
-template <bool DIFF>
+// SS: the map of the fine frame of a supersampled map (option "raymap_supersample", a.ss = k > 1; k W x k rows, bhr_fine_camera)
+// -- the fine argument block (a.width / rows / pw / ph fine, out_width / out_rows the frame's), fine planes, tiles in plain
+// order.  The march, the records and the header are the same; what differs is what goes on the overflow list.
+// One kernel template and not a shared body under two kernels: inlined from a function of its own, the body comes out with
+// commuted operands in seven instructions of the two DIFF kernels; as a template parameter, SS leaves all four instantiations
+// the instructions of the two kernels they were (tools/code_object_diff.py, profiles/raymap_refactor_code_objects.txt).
+template <bool DIFF, bool SS>
 __global__ __launch_bounds__(256) void raymap_build_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
     const int slot = wave_slot();
-    if (slot >= a.n_list) return;
+    if (slot >= a.n_list) return;    // wave-uniform: the lanes of a wave stay together down to the butterfly
     const int lane = threadIdx.x & 63;
     const int tile = a.tile_order ? a.tile_order[slot] : slot;
     const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
@@ -73,16 +87,41 @@ __global__ __launch_bounds__(256) void raymap_build_kernel(BhrMarchArgs a, BhrRa
         m.dir[2 * (size_t)m.plane + pix] = dn.z;
         m.crossings[pix] = n_rec;
     }
-    // more crossings than slots: the pixel keeps its first m.slots records and goes on the overflow list (wave-aggregated
-    // append, as the guard kernel's; every pixel is appended at most once and the list has room for all of them)
-    const bool over = valid && n_rec > m.slots;
-    const unsigned long long om = __ballot(over);
-    if (om) {
-        const int first = __ffsll((long long)om) - 1;
-        unsigned int base = 0;
-        if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(om));
-        base = __shfl(base, first, BHR_WAVE);
-        if (over) m.over_list[base + (unsigned int)__popcll(om & ((1ull << lane) - 1ull))] = (int32_t)pix;
+    if (SS) {
+        // A k x k group with ANY ray over the slots goes on the overflow list whole, in the format march_tile_body writes for
+        // march_fix_ss_kernel (march_tile.h): k^2 consecutive entries in sub-sample order (sy k + sx), k^2-aligned, groups in the
+        // order of their (0, 0) lanes -- the fix kernel resolves a group from 64 / k^2 of them per wave.  k W and k rows are
+        // multiples of k (and 8 is one of k), so a group lies in one tile, inside the frame or outside it, whole.
+        // the group's flag: the guard kernel's butterfly (every lane of the wave is here: no early return before it)
+        int u = valid && n_rec > m.slots ? 1 : 0;
+        for (int x = 1; x < a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+        for (int x = 8; x < 8 * a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+        const bool over = valid && u != 0;
+        const unsigned long long om = __ballot(over);
+        if (om) {
+            const int first = __ffsll((long long)om) - 1;
+            const int km = a.ss - 1, sx = lane & km, sy = (lane >> 3) & km;
+            const unsigned long long lead = __ballot(over && sx == 0 && sy == 0);
+            unsigned int base = 0;
+            if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(lead) << (2 * a.ss_log2));
+            base = __shfl(base, first, BHR_WAVE);
+            const int l0 = lane - sx - 8 * sy;
+            const unsigned int at = base + ((unsigned int)__popcll(lead & ((1ull << l0) - 1ull)) << (2 * a.ss_log2)) + (unsigned int)((sy << a.ss_log2) + sx);
+            // (every group is appended at most once and the list has room for the whole fine plane)
+            if (over) m.over_list[at] = (int32_t)pix;
+        }
+    } else {
+        // more crossings than slots: the pixel keeps its first m.slots records and goes on the overflow list (wave-aggregated
+        // append, as the guard kernel's; every pixel is appended at most once and the list has room for all of them)
+        const bool over = valid && n_rec > m.slots;
+        const unsigned long long om = __ballot(over);
+        if (om) {
+            const int first = __ffsll((long long)om) - 1;
+            unsigned int base = 0;
+            if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(om));
+            base = __shfl(base, first, BHR_WAVE);
+            if (over) m.over_list[base + (unsigned int)__popcll(om & ((1ull << lane) - 1ull))] = (int32_t)pix;
+        }
     }
     const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
     const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
@@ -92,19 +131,7 @@ __global__ __launch_bounds__(256) void raymap_build_kernel(BhrMarchArgs a, BhrRa
     }
 }
 
-// render.py:3008-3018 as pixel_values has it, from the direction the build kernel stored already normalized
-__device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool escaped, V3 dir, const Shade &sh, float bk[3], float dk[3]) {
-    V3 bg = mk(0, 0, 0);
-    if (escaped) bg = sample_skybox(a.sc, dir);
-    float k = 1.0f - sh.alpha_total;
-    bk[0] = __fmul_rn(bg.x, k);
-    bk[1] = __fmul_rn(bg.y, k);
-    bk[2] = __fmul_rn(bg.z, k);
-    dk[0] = fminf(fmaxf(sh.accum.x, 0.0f), 1.0f);
-    dk[1] = fminf(fmaxf(sh.accum.y, 0.0f), 1.0f);
-    dk[2] = fminf(fmaxf(sh.accum.z, 0.0f), 1.0f);
-}
-
+// ---- the shade: the two steps every shade kernel is made of ----------------------------------------------------------------------
 // x' = c x - s y, y' = s x + c y
 __device__ __forceinline__ void turn_xy(float c, float s, float &x, float &y) {
     const float xr = c * x - s * y, yr = s * x + c * y;
@@ -112,29 +139,21 @@ __device__ __forceinline__ void turn_xy(float c, float s, float &x, float &y) {
     y = yr;
 }
 
-// One lane per pixel, an 8x8 tile per wave as in the march (texture locality, and store_pixel's packed layout is per tile);
-// tiles in row-major order: every lane does about the same work.
-// ROT: the records are turned about z by (m.rot_c, m.rot_s) before they are shaded (the head of this file).
+// The lane's first `count` records of pixel `pix`, front to back, through shade_hit from the Shade that Ray::init leaves.
+// ROT: each record is turned about z by (rc, rs) before it is shaded (the head of this file).
+// f: the block shade_hit reads a frame's own two fields from -- `a` itself for a frame under one camera (what shade_hit's
+// convenience overload passes), a sample's for the shutter kernel.  ONLY f.t_offset and f.cp may be read through f, here as in
+// shade_hit and apply_g_factor (march_device.h says so at both): the shutter kernel sets nothing else in it.
+// The map is taken by value on purpose: so the four raymap_shade_kernel instantiations compile to the instructions they had with
+// the loop written out in them; with the map by reference two instructions of the DIFF ones move
+// (tools/code_object_diff.py against the parent build; profiles/raymap_refactor_code_objects.txt is the last run).
 template <bool DIFF, bool ROT>
-__global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
-    const int tile = wave_slot();
-    if (tile >= a.n_tiles) return;
-    const int lane = threadIdx.x & 63;
-    const int i = (tile % a.tiles_x) * 8 + (lane & 7);
-    const int j = (tile / a.tiles_x) * 8 + (lane >> 3);
-    if (!(i < a.width && j < a.rows)) return;
-    const size_t pix = (size_t)j * a.width + i;
-    const int count = m.crossings[pix];
-    if (count > m.slots) return;     // on the overflow list: the fix kernel marches and stores it
+__device__ __forceinline__ Shade raymap_shade_records(const BhrMarchArgs &a, const BhrMarchArgs &f, const BhrRayMapArgs m, size_t pix, int count,
+                                                       float rc, float rs) {
     Shade sh;                        // as Ray::init leaves it
     sh.accum = mk(0, 0, 0);
     sh.alpha_total = 0.0f;
     sh.unsure = 0;
-    // The turn's cosine and sine stay scalar operands.  A VALU instruction with an SGPR operand issues at half rate (DESIGN 4),
-    // but there are 8 (16 with differentials) such products per crossing beside the ~700 instructions of shade_hit, and 4 for
-    // the sky; copied into two vector registers once, the plain kernel goes from 79 to 81 VGPRs and loses a wave per SIMD
-    // (6 -> 5), as scalars both instantiations keep the registers of the kernels without a turn (79 / 76 VGPRs, 6 waves).
-    const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;
     for (int c = 0; c < count; ++c) {
         const float *q = m.hits + (size_t)c * m.comps * (size_t)m.plane + pix;
         const size_t p = (size_t)m.plane;
@@ -150,13 +169,58 @@ __global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRa
                 turn_xy(rc, rs, dyx, dyy);           // d(hit x, hit y) / d(pixel y)
             }
         }
-        shade_hit<DIFF, 0>(a, sh, hx, hy, to_cam, dxx, dxy, dyx, dyy);
+        shade_hit<DIFF, 0>(a, f, sh, hx, hy, to_cam, dxx, dxy, dyx, dyy);
     }
+    return sh;
+}
+
+// render.py:3008-3018 as pixel_values has it, from the direction the build kernel stored already normalized
+__device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool escaped, V3 dir, const Shade &sh, float bk[3], float dk[3]) {
+    V3 bg = mk(0, 0, 0);
+    if (escaped) bg = sample_skybox(a.sc, dir);
+    float k = 1.0f - sh.alpha_total;
+    bk[0] = __fmul_rn(bg.x, k);
+    bk[1] = __fmul_rn(bg.y, k);
+    bk[2] = __fmul_rn(bg.z, k);
+    dk[0] = fminf(fmaxf(sh.accum.x, 0.0f), 1.0f);
+    dk[1] = fminf(fmaxf(sh.accum.y, 0.0f), 1.0f);
+    dk[2] = fminf(fmaxf(sh.accum.z, 0.0f), 1.0f);
+}
+
+// The pixel's BG and DISK values from its shaded records: the ray's fate and its stored escape direction (turned as the
+// records were), then the march's own pixel values.
+template <bool ROT>
+__device__ __forceinline__ void raymap_values(const BhrMarchArgs &a, const BhrRayMapArgs &m, size_t pix, const Shade &sh, float rc, float rs,
+                                              float bk[3], float dk[3]) {
     const bool esc = m.status[pix] == 1;
     V3 dir = mk(m.dir[pix], m.dir[(size_t)m.plane + pix], m.dir[2 * (size_t)m.plane + pix]);
     if (ROT) turn_xy(rc, rs, dir.x, dir.y);
-    float bk[3], dk[3];
     raymap_pixel_values(a, esc, dir, sh, bk, dk);
+}
+
+// ---- the shade kernels --------------------------------------------------------------------------------------------------------
+// One lane per pixel, an 8x8 tile per wave as in the march (texture locality, and store_pixel's packed layout is per tile);
+// tiles in row-major order: every lane does about the same work.
+// ROT: the records are turned about z by (m.rot_c, m.rot_s) before they are shaded (the head of this file).
+template <bool DIFF, bool ROT>
+__global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
+    const int tile = wave_slot();
+    if (tile >= a.n_tiles) return;
+    const int lane = threadIdx.x & 63;
+    const int i = (tile % a.tiles_x) * 8 + (lane & 7);
+    const int j = (tile / a.tiles_x) * 8 + (lane >> 3);
+    if (!(i < a.width && j < a.rows)) return;
+    const size_t pix = (size_t)j * a.width + i;
+    const int count = m.crossings[pix];
+    if (count > m.slots) return;     // on the overflow list: the fix kernel marches and stores it
+    // The turn's cosine and sine stay scalar operands.  A VALU instruction with an SGPR operand issues at half rate (DESIGN 4),
+    // but there are 8 (16 with differentials) such products per crossing beside the ~700 instructions of shade_hit, and 4 for
+    // the sky; copied into two vector registers once, the plain kernel goes from 79 to 81 VGPRs and loses a wave per SIMD
+    // (6 -> 5), as scalars both instantiations keep the registers of the kernels without a turn (79 / 76 VGPRs, 6 waves).
+    const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;
+    const Shade sh = raymap_shade_records<DIFF, ROT>(a, a, m, pix, count, rc, rs);
+    float bk[3], dk[3];
+    raymap_values<ROT>(a, m, pix, sh, rc, rs, bk, dk);
     store_pixel(a, i, j, a.width, bk, dk);
 }
 
@@ -189,44 +253,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void r
     const int j = (tile / a.tiles_x) * 8 + (lane >> 3);
     if (!(i < a.width && j < a.rows)) return;
     const size_t pix = (size_t)j * a.width + i;
-    const size_t p = (size_t)m.plane;
     const int count = m.crossings[pix];
     if (count > m.slots) return;
     const int t = threadIdx.x;
     for (int smp = 0; smp < sh.n; ++smp) {
-        // the two fields of the argument block that are a frame's own; shade_hit and apply_g_factor read NOTHING else through
-        // their second block (march_device.h says so at both), and the rest of this one is never set
+        // the two fields of the argument block that are a frame's own; the rest of this block is never set
         BhrMarchArgs fs;
         fs.t_offset = sh.smp[smp].t;
         fs.cp[0] = sh.smp[smp].cp[0];
         fs.cp[1] = sh.smp[smp].cp[1];
         fs.cp[2] = sh.smp[smp].cp[2];
         const float rc = ROT ? sh.smp[smp].c : 1.0f, rs = ROT ? sh.smp[smp].s : 0.0f;
-        Shade shd;                           // as Ray::init leaves it
-        shd.accum = mk(0, 0, 0);
-        shd.alpha_total = 0.0f;
-        shd.unsure = 0;
-        for (int c = 0; c < count; ++c) {
-            const float *q = m.hits + (size_t)c * m.comps * p + pix;
-            float hx = q[0], hy = q[p];
-            V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
-            float dxx = 0.0f, dxy = 0.0f, dyx = 0.0f, dyy = 0.0f;
-            if (DIFF) { dxx = q[5 * p]; dxy = q[6 * p]; dyx = q[7 * p]; dyy = q[8 * p]; }
-            if (ROT) {
-                turn_xy(rc, rs, hx, hy);
-                turn_xy(rc, rs, to_cam.x, to_cam.y);
-                if (DIFF) {
-                    turn_xy(rc, rs, dxx, dxy);
-                    turn_xy(rc, rs, dyx, dyy);
-                }
-            }
-            shade_hit<DIFF, 0>(a, fs, shd, hx, hy, to_cam, dxx, dxy, dyx, dyy);
-        }
-        const bool esc = m.status[pix] == 1;
-        V3 dir = mk(m.dir[pix], m.dir[p + pix], m.dir[2 * p + pix]);
-        if (ROT) turn_xy(rc, rs, dir.x, dir.y);
+        const Shade shd = raymap_shade_records<DIFF, ROT>(a, fs, m, pix, count, rc, rs);
         float bk[3], dk[3];
-        raymap_pixel_values(a, esc, dir, shd, bk, dk);
+        raymap_values<ROT>(a, m, pix, shd, rc, rs, bk, dk);
         {
 #pragma clang fp contract(off)
             // acc = L_0, then acc = acc + L_j: one f32 addition per channel (smp is wave-uniform)
@@ -258,80 +298,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void r
     a.disk[o + 0] = acc_d[0];
     a.disk[o + 1] = acc_d[1];
     a.disk[o + 2] = acc_d[2];
-}
-
-// ---- supersampled maps (option "raymap_supersample", a.ss = k > 1) -------------------------------------------------------
-// The map of the fine frame (k W x k rows, bhr_fine_camera): instantiations of their own, the k = 1 kernels above stay as they are.
-//
-// The build over the fine argument block (a.width / rows / pw / ph fine, out_width / out_rows the frame's): the loop above, fine
-// planes, tiles in plain order.  A k x k group with ANY ray over the slots goes on the overflow list whole, in the format
-// march_tile_body writes for march_fix_ss_kernel (march_tile.h): k^2 consecutive entries in sub-sample order (sy k + sx),
-// k^2-aligned, groups in the order of their (0, 0) lanes -- the fix kernel resolves a group from 64 / k^2 of them per wave.
-// k W and k rows are multiples of k (and 8 is one of k), so a group lies in one tile, inside the frame or outside it, whole.
-template <bool DIFF>
-__global__ __launch_bounds__(256) void raymap_build_ss_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
-    const int slot = wave_slot();
-    if (slot >= a.n_list) return;    // wave-uniform: the lanes of a wave stay together down to the butterfly
-    const int lane = threadIdx.x & 63;
-    const int tile = a.tile_order ? a.tile_order[slot] : slot;
-    const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
-    const int i = tx * 8 + (lane & 7);
-    const int j = ty * 8 + (lane >> 3);
-    const bool valid = tile < a.n_tiles && i < a.width && j < a.rows;
-
-    Ray<DIFF, 0> ray;
-    ray.init(a, valid ? i : 0, valid ? j : 0);
-    if (!valid) ray.done = 4;
-    const size_t pix = valid ? (size_t)j * a.width + i : 0;
-    int cnt = 0, n_rec = 0;
-    while (ray.done == 0) {
-        ray.step(a);
-        cnt += 1;
-        if (ray.full) {
-            ray.record_one(m, pix, n_rec);
-            ray.full = false;
-        }
-    }
-    ray.step_count = cnt;
-    if (cnt > 0) ray.settle(a);
-    else ray.done = 3;
-    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
-    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
-
-    if (valid) {
-        const bool esc = ray.escaped();
-        m.steps[pix] = cnt;
-        m.status[pix] = esc ? 1 : (ray.done == 2 ? 0 : 2);
-        const V3 dn = esc ? normalized(ray.d) : mk(0.0f, 0.0f, 0.0f);
-        m.dir[pix] = dn.x;
-        m.dir[(size_t)m.plane + pix] = dn.y;
-        m.dir[2 * (size_t)m.plane + pix] = dn.z;
-        m.crossings[pix] = n_rec;
-    }
-    // the group's flag: the guard kernel's butterfly (every lane of the wave is here)
-    int u = valid && n_rec > m.slots ? 1 : 0;
-    for (int x = 1; x < a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
-    for (int x = 8; x < 8 * a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
-    const bool over = valid && u != 0;
-    const unsigned long long om = __ballot(over);
-    if (om) {
-        const int first = __ffsll((long long)om) - 1;
-        const int km = a.ss - 1, sx = lane & km, sy = (lane >> 3) & km;
-        const unsigned long long lead = __ballot(over && sx == 0 && sy == 0);
-        unsigned int base = 0;
-        if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(lead) << (2 * a.ss_log2));
-        base = __shfl(base, first, BHR_WAVE);
-        const int l0 = lane - sx - 8 * sy;
-        const unsigned int at = base + ((unsigned int)__popcll(lead & ((1ull << l0) - 1ull)) << (2 * a.ss_log2)) + (unsigned int)((sy << a.ss_log2) + sx);
-        // (every group is appended at most once and the list has room for the whole fine plane)
-        if (over) m.over_list[at] = (int32_t)pix;
-    }
-    const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
-    const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
-    if (lane == 0) {
-        atomicAdd(m.stats, stored);
-        atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
-    }
 }
 
 // What resolve_store (march_device.h) asks of a ray: the six values it leaves.  Here they come out of the lane's records.
@@ -368,36 +334,10 @@ __global__ __launch_bounds__(256) void raymap_shade_ss_kernel(BhrMarchArgs a, Bh
     for (int x = 1; x < a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
     for (int x = 8; x < 8 * a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
     const bool have = valid && u == 0;
-    const int count = have ? crossings : 0;
-    Shade sh;                        // as Ray::init leaves it
-    sh.accum = mk(0, 0, 0);
-    sh.alpha_total = 0.0f;
-    sh.unsure = 0;
-    const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;   // scalar operands, as above
-    for (int c = 0; c < count; ++c) {
-        const float *q = m.hits + (size_t)c * m.comps * (size_t)m.plane + pix;
-        const size_t p = (size_t)m.plane;
-        float hx = q[0], hy = q[p];
-        V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
-        float dxx = 0.0f, dxy = 0.0f, dyx = 0.0f, dyy = 0.0f;
-        if (DIFF) { dxx = q[5 * p]; dxy = q[6 * p]; dyx = q[7 * p]; dyy = q[8 * p]; }
-        if (ROT) {
-            turn_xy(rc, rs, hx, hy);
-            turn_xy(rc, rs, to_cam.x, to_cam.y);
-            if (DIFF) {
-                turn_xy(rc, rs, dxx, dxy);
-                turn_xy(rc, rs, dyx, dyy);
-            }
-        }
-        shade_hit<DIFF, 0>(a, sh, hx, hy, to_cam, dxx, dxy, dyx, dyy);
-    }
+    const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;   // scalar operands, as in raymap_shade_kernel
+    const Shade sh = raymap_shade_records<DIFF, ROT>(a, a, m, pix, have ? crossings : 0, rc, rs);
     RayMapValues val = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
-    if (have) {
-        const bool esc = m.status[pix] == 1;
-        V3 dir = mk(m.dir[pix], m.dir[(size_t)m.plane + pix], m.dir[2 * (size_t)m.plane + pix]);
-        if (ROT) turn_xy(rc, rs, dir.x, dir.y);
-        raymap_pixel_values(a, esc, dir, sh, val.v, val.v + 3);
-    }
+    if (have) raymap_values<ROT>(a, m, pix, sh, rc, rs, val.v, val.v + 3);
     // every lane of the wave, whatever it holds
     resolve_store(a, val, have, have, i, j, 8);
 }
@@ -410,14 +350,14 @@ __global__ __launch_bounds__(256) void raymap_shade_ss_kernel(BhrMarchArgs a, Bh
 const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss) {
     if (ss) {
         switch (k) {
-        case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_ss_kernel<true> : (const void *)raymap_build_ss_kernel<false>;
+        case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_kernel<true, true> : (const void *)raymap_build_kernel<false, true>;
         case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_ss_kernel<true, false> : (const void *)raymap_shade_ss_kernel<false, false>;
         case BHR_MK_RAYMAP_SHADE_ROT: return diff ? (const void *)raymap_shade_ss_kernel<true, true> : (const void *)raymap_shade_ss_kernel<false, true>;
         default: return nullptr;
         }
     }
     switch (k) {
-    case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_kernel<true> : (const void *)raymap_build_kernel<false>;
+    case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_kernel<true, false> : (const void *)raymap_build_kernel<false, false>;
     case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_kernel<true, false> : (const void *)raymap_shade_kernel<false, false>;
     case BHR_MK_RAYMAP_SHADE_ROT: return diff ? (const void *)raymap_shade_kernel<true, true> : (const void *)raymap_shade_kernel<false, true>;
     case BHR_MK_RAYMAP_SHUTTER:

@@ -6,8 +6,16 @@ usage: tools/code_object_diff.py OLD_OBJ_DIR NEW_OBJ_DIR     (two copies of blac
 Every *.o of either directory that carries a gfx950 code object is unbundled with llvm-objdump --offloading (as
 tools/kernel_resources.sh does) and three things are compared: the raw bytes of .text, the raw bytes of .rodata, and the text
 of llvm-readelf --notes (kernel names, registers, LDS, argument layouts).  One line per object: name, .text size, kernel
-count, `same` or `DIFFERENT`.  Exit status 1 on any difference or if an object is on one side only."""
+count, `same` or `DIFFERENT`.  Exit status 1 on any difference or if an object is on one side only.
+
+Under an object that differs, two lines per kernel symbol of either side (paired by name): VGPRs, SGPRs, private segment and
+group segment bytes from the notes and the instruction count `n` from llvm-objdump -d, each as `old` or `old -> new`, and
+whether the instruction text is the same.  Instruction text is mnemonic and operands only: addresses, encodings and the
+branch-target labels (symbol + offset, which move with the kernel's place in .text) are dropped; a branch keeps its relative
+offset.  A kernel on one side only is listed as such, with the other side's one-sided kernels of the same text, if any."""
+import difflib
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -43,7 +51,54 @@ def describe(obj, work):
         return None
     notes = subprocess.check_output([tool("llvm-readelf"), "--notes", co], text=True)
     kernels = sum(1 for line in notes.splitlines() if line.strip().startswith(".symbol:"))
-    return {"text": section(co, ".text"), "rodata": section(co, ".rodata"), "notes": notes, "kernels": kernels}
+    return {"text": section(co, ".text"), "rodata": section(co, ".rodata"), "notes": notes, "kernels": kernels, "co": co}
+
+
+NOTE_FIELDS = (("vgpr", "vgpr_count"), ("sgpr", "sgpr_count"), ("private", "private_segment_fixed_size"), ("lds", "group_segment_fixed_size"))
+
+
+def per_kernel(d):
+    """{kernel symbol: resources from the notes + "insts": its instruction text, a list}"""
+    col = lambda key: re.findall(r"^\s*-?\s*\." + key + r":\s*(\S+)", d["notes"], re.M)   # once per kernel, in the kernels' order
+    names = [s[:-3] if s.endswith(".kd") else s for s in col("symbol")]
+    out = {n: {"insts": []} for n in names}
+    for short, key in NOTE_FIELDS:
+        for n, v in zip(names, col(key)):
+            out[n][short] = int(v)
+    cur = None
+    for line in subprocess.check_output([tool("llvm-objdump"), "-d", d["co"]], text=True).splitlines():
+        label = re.match(r"^[0-9a-fA-F]+ <(.+)>:$", line)
+        if label:
+            cur = out.get(label.group(1))
+        elif cur is not None and line.startswith(("\t", " ")) and line.strip():
+            cur["insts"].append(" ".join(line.split("//")[0].split()))
+    for k in out.values():   # the padding behind a kernel's last instruction is not its code
+        while k["insts"] and k["insts"][-1].split()[0] in ("s_code_end", "s_nop"):
+            k["insts"].pop()
+    return out
+
+
+def kernel_breakdown(a, b):
+    ka, kb = per_kernel(a), per_kernel(b)
+    for k in list(ka.values()) + list(kb.values()):
+        k["n"] = len(k["insts"])
+    keys = ("vgpr", "sgpr", "private", "lds", "n")
+    for sym in sorted(set(ka) | set(kb)):
+        if sym in ka and sym in kb:
+            x, y = ka[sym], kb[sym]
+            cols = " ".join(f"{k} {x[k]}" + ("" if x[k] == y[k] else f" -> {y[k]}") for k in keys)
+            if x["insts"] == y["insts"]:
+                text = "text same"
+            else:   # how many instructions of either side are outside a longest common run of lines
+                kept = sum(m.size for m in difflib.SequenceMatcher(None, x["insts"], y["insts"], autojunk=False).get_matching_blocks())
+                text = f"text DIFFERENT ({x['n'] - kept} old, {y['n'] - kept} new instructions unmatched)"
+        else:       # on one side only; a renamed kernel shows as a kernel of the other side only with the same text
+            here, there, side, other = (ka, kb, "OLD", "NEW") if sym in ka else (kb, ka, "NEW", "OLD")
+            x = here[sym]
+            cols = " ".join(f"{k} {x[k]}" for k in keys)
+            twins = [t for t in sorted(there) if t not in here and there[t]["insts"] == x["insts"]]
+            text = f"only in {side}" + "".join(f"; text same as {other}'s {t}" for t in twins)
+        print(f"    {sym}\n        {cols}  {text}")
 
 
 def main(argv):
@@ -76,6 +131,8 @@ def main(argv):
             bad += bool(diffs)
             verdict = "same" if not diffs else "DIFFERENT (" + ", ".join(diffs) + ")"
             print(f"{name:24s} {len(b['text']):10d} {b['kernels']:3d}  {verdict}")
+            if diffs:
+                kernel_breakdown(a, b)
     print(f"{'all the same' if not bad else str(bad) + ' object(s) differ'}: .text, .rodata and notes of every gfx950 code object")
     return 1 if bad else 0
 
