@@ -21,6 +21,7 @@ OUTPUT_F32, OUTPUT_BLUR, OUTPUT_U8 = 1, 2, 4
 DITHER_NONE, DITHER_BLUE = 0, 1
 GRADE_CLIP, GRADE_REINHARD, GRADE_ACES = 0, 1, 2
 TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
+HDR_PQ, HDR_HLG = 1, 2
 RAYMAP_STEPS, RAYMAP_STATUS, RAYMAP_ESCAPE_DIR, RAYMAP_CROSSINGS, RAYMAP_HITS = 0, 1, 2, 3, 4
 
 # every symbol include/bhr.h declares (tests check the .so exports exactly these)
@@ -37,6 +38,7 @@ SYMBOLS = (
     "bhr_jpeg_device_bound", "bhr_jpeg_restart_interval", "bhr_jpeg_tables", "bhr_jpeg_encode_device", "bhr_sink_create_jpeg",
     "bhr_sink_create", "bhr_sink_submit", "bhr_sink_drain",
     "bhr_sink_destroy", "bhr_y4m_open", "bhr_y4m_submit", "bhr_y4m_drain", "bhr_y4m_close",
+    "bhr_y4m_open_hdr", "bhr_y4m_light_levels",
 )
 
 
@@ -65,6 +67,10 @@ class Counters(C.Structure):
 class Grade(C.Structure):
     _fields_ = [("op", C.c_int32), ("transfer", C.c_int32), ("exposure_stops", C.c_float), ("white", C.c_float),
                 ("keep_hdr", C.c_int32)]
+
+
+class HdrStream(C.Structure):
+    _fields_ = [("transfer", C.c_int32), ("exposure_stops", C.c_float), ("white_nits", C.c_float), ("reserved", C.c_int32)]
 
 
 class RayMapInfo(C.Structure):
@@ -202,6 +208,8 @@ def load() -> C.CDLL:
     lib.bhr_y4m_submit.argtypes = [P]
     lib.bhr_y4m_drain.argtypes = [P, C.POINTER(I64), C.POINTER(I64)]
     lib.bhr_y4m_close.argtypes = [P]
+    lib.bhr_y4m_open_hdr.argtypes = [P, C.c_char_p, I32, I32, I32, C.POINTER(HdrStream), C.POINTER(P)]
+    lib.bhr_y4m_light_levels.argtypes = [P, C.POINTER(C.c_double)]
     for name in SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("bhr_last_error", "bhr_destroy", "bhr_sink_destroy", "bhr_png_bound", "bhr_png_device_bound", "bhr_jpeg_device_bound", "bhr_y4m_close",

@@ -75,7 +75,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--video_quality", type=int, default=90, help="--video_codec mjpeg: JPEG quality 1..100 (default: 90)")
     p.add_argument("--bit_depth", type=int, default=8, choices=[8, 16],
                    help="bits per sample of the PNG output: 8 (default), or 16 -- (uint16)(clip(x, 0, 1) * 65535), still images and "
-                        "--video frames alike (the yuv420p stream stays 8-bit); not with --dither blue or --video_codec mjpeg")
+                        "--video frames alike (the yuv420p stream stays 8-bit; --video_hdr is the 10-bit stream); not with --dither blue or --video_codec mjpeg")
     p.add_argument("--dither", type=str, default="none", choices=["none", "blue"],
                    help="8-bit quantisation: none = truncation as the reference (default); blue = a 64x64 blue-noise threshold is "
                         "added before the floor, so that smooth dark gradients come out as fine noise instead of bands")
@@ -97,6 +97,17 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--hdr_output", type=str, default=None, metavar="PATH",
                    help="still images: also write the unclipped scene-linear frame, before exposure, as PATH (.pfm: exact f32; "
                         ".hdr: Radiance RGBE)")
+    p.add_argument("--video_hdr", type=str, default=None, choices=["pq", "hlg"],
+                   help="--video: the video stream is HDR -- 10-bit BT.2020 frames under the PQ (SMPTE ST 2084) or HLG (BT.2100) "
+                        "transfer, made on the device from every frame's unclipped scene-linear plane and piped into ffmpeg "
+                        "(libx265) when it is on PATH, else written as <output stem>.y4m; <output stem>.hdr10.json records the "
+                        "colour description and the content light levels.  The frame files stay the SDR frames they would be "
+                        "without it.  One rank; not with --resume on a run that has frames, --video_codec mjpeg or --video_stream off")
+    p.add_argument("--hdr_white", type=float, default=None, metavar="NITS",
+                   help="--video_hdr pq: the display level of scene value 1.0 in nits, in (0, 10000] (default: 203, the reference "
+                        "white of BT.2408)")
+    p.add_argument("--hdr_exposure", type=float, default=None, metavar="STOPS",
+                   help="--video_hdr: exposure of the HDR stream in stops, -16..16 (default: 0); the SDR frames take --exposure")
     p.add_argument("--ray_map", action="store_true",
                    help="--video with a camera that stands still: march the view once, before the loop, and shade every frame "
                         "from that ray map under the frame's texture instead of marching it again.  The frames are the strict "
@@ -191,6 +202,22 @@ def parse_args(argv=None) -> argparse.Namespace:
             p.error("--ray_map does not combine with --disk_model other than texture: a ray map shades the disk texture")
         if args.gpus != 1:
             p.error("--ray_map does not combine with --gpus other than 1: a ray map lives on one GPU")
+    if args.video_hdr is None:
+        if args.hdr_white is not None:
+            p.error("--hdr_white needs --video_hdr pq: it is the display level of the PQ stream's scene value 1.0")
+        if args.hdr_exposure is not None:
+            p.error("--hdr_exposure needs --video_hdr: it is the exposure of the HDR stream")
+    else:
+        if not args.video:
+            p.error("--video_hdr needs --video: it is the HDR stream of a video (still images take --hdr_output)")
+        if args.video_hdr == "hlg" and args.hdr_white is not None:
+            p.error("--hdr_white is PQ's: HLG is scene-referred and places scene value 1.0 at its 75 % reference white")
+        if args.video_codec == "mjpeg":
+            p.error("--video_hdr does not combine with --video_codec mjpeg: that mode writes no stream")
+        if args.video_stream == "off":
+            p.error("--video_hdr is a video stream: it does not combine with --video_stream off")
+    args.hdr_white = 203.0 if args.hdr_white is None else args.hdr_white
+    args.hdr_exposure = 0.0 if args.hdr_exposure is None else args.hdr_exposure
     if args.passes is not None:
         if args.video:
             p.error("--passes writes the passes of a still image: it does not combine with --video")
@@ -269,6 +296,13 @@ def validate_args(args) -> None:
             raise ValueError(f"white must be greater than 0 and at most 65504, got {args.white}")
         if getattr(args, "gpus", 1) > 1:
             raise ValueError("--tonemap renders on one GPU: it does not combine with --gpus > 1")
+    if getattr(args, "video_hdr", None) is not None:
+        if not (math.isfinite(args.hdr_exposure) and -16.0 <= args.hdr_exposure <= 16.0):
+            raise ValueError(f"hdr_exposure must be between -16 and 16 stops, got {args.hdr_exposure}")
+        if args.video_hdr == "pq" and not (math.isfinite(args.hdr_white) and 0.0 < args.hdr_white <= 10000.0):
+            raise ValueError(f"hdr_white must be greater than 0 and at most 10000 nits, got {args.hdr_white}")
+        if getattr(args, "gpus", 1) > 1:
+            raise ValueError("--video_hdr renders on one GPU: it does not combine with --gpus > 1")
     hdr_output = getattr(args, "hdr_output", None)
     if hdr_output is not None:
         if args.video:
@@ -312,7 +346,8 @@ def main(argv=None) -> int:
                              video_codec=args.video_codec, video_quality=args.video_quality, bit_depth=args.bit_depth,
                              dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples,
                              grade=grade_from_args(args), ray_map=args.ray_map, orbit_map=args.orbit_map,
-                             shutter_map=args.shutter_map, map_supersample=args.map_supersample)
+                             shutter_map=args.shutter_map, map_supersample=args.map_supersample, video_hdr=args.video_hdr,
+                             hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent

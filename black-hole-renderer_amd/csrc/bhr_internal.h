@@ -558,6 +558,10 @@ int32_t bhr_launch_quantize_dither(bhr_ctx *ctx);   // d_final -> d_final_u8, bl
 // from its HDR plane, which is then clamped in place; store_hdr: also the plane h; store_u8: also the undithered u8 rows
 int32_t bhr_launch_grade(bhr_ctx *ctx, bool from_hdr, bool store_hdr, bool store_u8);
 int32_t bhr_launch_grade_sum(bhr_ctx *ctx);         // (d_bg + d_disk) + d_blur -> d_hdr (allocated here on first use)
+// hdr_stream.hip, on ctx->stream: the active slot's HDR plane -> planar u16 Y | Cb | Cr (3 W rows bytes) at d_out under
+// `transfer` (BHR_HDR_PQ / _HLG), and the frame's light levels into d_levels = {u32 bits of the largest f32 nits, u32 0, f64 sum
+// of nits}, 16 bytes on an 8-byte boundary that the launch clears first (HLG leaves them 0).  scale: white_nits / 10000 (PQ)
+int32_t bhr_launch_hdr_yuv420p10(bhr_ctx *ctx, int32_t transfer, float gain, float scale, float white_nits, uint16_t *d_out, void *d_levels);
 // jpeg_device.hip: (rows, W, 3) u8 at d_rgb -> JFIF file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
 int32_t bhr_launch_jpeg_encode(bhr_ctx *ctx, int32_t quality, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
 void bhr_jpeg_dev_free(bhr_ctx *ctx);

@@ -10,8 +10,11 @@
 #include <signal.h>
 #include <zlib.h>
 
+#include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <mutex>
@@ -363,7 +366,7 @@ struct bhr_y4m {
     FILE *f = nullptr;
     // every ring slot owns its device planes: the conversion rides the stream of the frame slot that rendered the frame
     // (bhr_enter_frame), so two frames in flight convert side by side and the scene stream stays free
-    struct Slot { uint8_t *host = nullptr; uint8_t *dev = nullptr; hipEvent_t ev = nullptr; };
+    struct Slot { uint8_t *host = nullptr; uint8_t *dev = nullptr; hipEvent_t ev = nullptr; hipEvent_t k0 = nullptr, k1 = nullptr; };
     std::vector<Slot> slots;
     std::deque<int> free_slots, jobs;      // jobs in submission order: ONE writer keeps the frame order
     int in_flight = 0;
@@ -374,6 +377,14 @@ struct bhr_y4m {
     int32_t err = BHR_OK;
     std::string err_text;
     int64_t frames = 0, bytes = 0;
+    // an HDR stream (bhr_y4m_open_hdr; transfer 0: the 8-bit stream): frame_bytes = 3 W H, and behind them, on the next 16-byte
+    // boundary, every ring slot carries the 16 bytes of its frame's light levels (hdr_stream.hip), copied with the frame
+    int transfer = 0;
+    float gain = 1.0f, scale = 0.0f, white_nits = 0.0f;
+    size_t levels_at = 0;                  // offset of the light levels in a slot's buffers
+    double max_cll = 0.0, max_fall = 0.0;  // over the frames written
+    bool timing = false;                   // BHR_HDR_TIMING=1: the conversion kernel of every frame is bracketed by HIP events
+    double kernel_ms = 0.0;
 
     void work() {
         (void)hipSetDevice(ctx->cfg.device);
@@ -401,6 +412,20 @@ struct bhr_y4m {
                 std::lock_guard<std::mutex> lk(mu);
                 if (rc != BHR_OK && err == BHR_OK) { err = rc; err_text = bhr_last_error(); }
                 if (rc == BHR_OK) { frames += 1; bytes += 6 + (int64_t)frame_bytes; }
+                if (rc == BHR_OK && transfer == BHR_HDR_PQ) {
+                    uint32_t top_bits;
+                    float top;
+                    double sum;
+                    memcpy(&top_bits, slots[slot].host + levels_at, 4);
+                    memcpy(&top, &top_bits, 4);
+                    memcpy(&sum, slots[slot].host + levels_at + 8, 8);
+                    max_cll = std::max(max_cll, (double)top);
+                    max_fall = std::max(max_fall, sum / ((double)w * h));
+                }
+                if (rc == BHR_OK && timing) {
+                    float ms = 0.0f;
+                    if (hipEventElapsedTime(&ms, slots[slot].k0, slots[slot].k1) == hipSuccess) kernel_ms += ms;
+                }
                 free_slots.push_back(slot);
                 in_flight -= 1;
             }
@@ -410,9 +435,9 @@ struct bhr_y4m {
     }
 };
 
-extern "C" {
-
-int32_t bhr_y4m_open(bhr_ctx *ctx, const char *path, int32_t fps_num, int32_t fps_den, int32_t n_slots, bhr_y4m **out) {
+// Both kinds of stream: hdr null -- the 8-bit yuv420p stream -- or a checked HDR configuration.
+static int32_t y4m_open(bhr_ctx *ctx, const char *path, int32_t fps_num, int32_t fps_den, int32_t n_slots, const bhr_hdr_stream *hdr,
+                        bhr_y4m **out) {
     if (!ctx || !path || !out || fps_num <= 0 || fps_den <= 0 || n_slots < 1 || n_slots > 256)
         return bhr_fail(BHR_ERR_INVALID, "bhr_y4m_open: bad argument");
     *out = nullptr;
@@ -424,16 +449,30 @@ int32_t bhr_y4m_open(bhr_ctx *ctx, const char *path, int32_t fps_num, int32_t fp
     s->w = ctx->cfg.width;
     s->h = ctx->rows;
     s->frame_bytes = (size_t)s->w * s->h * 3 / 2;
+    size_t slot_bytes = s->frame_bytes;
+    if (hdr) {
+        s->transfer = hdr->transfer;
+        s->gain = (float)exp2((double)hdr->exposure_stops);
+        s->white_nits = hdr->transfer == BHR_HDR_PQ ? hdr->white_nits : 0.0f;
+        s->scale = s->white_nits / 10000.0f;
+        s->frame_bytes = (size_t)s->w * s->h * 3;                     // u16 samples
+        s->levels_at = (s->frame_bytes + 15) & ~(size_t)15;
+        slot_bytes = s->levels_at + 16;
+        const char *t = getenv("BHR_HDR_TIMING");
+        s->timing = t && atoi(t) != 0;
+    }
     s->f = fopen(path, "wb");
     if (!s->f) { delete s; return bhr_fail(BHR_ERR_INVALID, "bhr_y4m_open: cannot open %s for writing", path); }
     setvbuf(s->f, nullptr, _IOFBF, 1 << 22);
-    fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n", s->w, s->h, fps_num, fps_den);
+    fprintf(s->f, "YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 %s XCOLORRANGE=LIMITED\n", s->w, s->h, fps_num, fps_den, hdr ? "C420p10" : "C420jpeg");
     hipError_t e = hipSuccess;
     s->slots.resize(n_slots);
     for (int k = 0; k < n_slots && e == hipSuccess; ++k) {
-        e = hipHostMalloc((void **)&s->slots[k].host, s->frame_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&s->slots[k].dev, s->frame_bytes);
+        e = hipHostMalloc((void **)&s->slots[k].host, slot_bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **)&s->slots[k].dev, slot_bytes);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s->slots[k].ev, hipEventDisableTiming);
+        if (e == hipSuccess && s->timing) e = hipEventCreate(&s->slots[k].k0);
+        if (e == hipSuccess && s->timing) e = hipEventCreate(&s->slots[k].k1);
         s->free_slots.push_back(k);
     }
     s->writer = std::thread(&bhr_y4m::work, s);
@@ -442,6 +481,34 @@ int32_t bhr_y4m_open(bhr_ctx *ctx, const char *path, int32_t fps_num, int32_t fp
         return bhr_fail(BHR_ERR_HIP, "bhr_y4m_open: %s", hipGetErrorString(e));
     }
     *out = s;
+    return BHR_OK;
+}
+
+extern "C" {
+
+int32_t bhr_y4m_open(bhr_ctx *ctx, const char *path, int32_t fps_num, int32_t fps_den, int32_t n_slots, bhr_y4m **out) {
+    return y4m_open(ctx, path, fps_num, fps_den, n_slots, nullptr, out);
+}
+
+int32_t bhr_y4m_open_hdr(bhr_ctx *ctx, const char *path, int32_t fps_num, int32_t fps_den, int32_t n_slots, const bhr_hdr_stream *cfg,
+                         bhr_y4m **out) {
+    if (out) *out = nullptr;
+    if (!cfg) return bhr_fail(BHR_ERR_INVALID, "bhr_y4m_open_hdr: null configuration");
+    if (cfg->transfer != BHR_HDR_PQ && cfg->transfer != BHR_HDR_HLG)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_y4m_open_hdr: transfer %d (1 pq, 2 hlg)", cfg->transfer);
+    if (!(cfg->exposure_stops >= -16.0f && cfg->exposure_stops <= 16.0f))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_y4m_open_hdr: exposure of %g stops (finite, -16 .. 16)", (double)cfg->exposure_stops);
+    if (cfg->transfer == BHR_HDR_PQ && !(cfg->white_nits > 0.0f && cfg->white_nits <= 10000.0f))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_y4m_open_hdr: white of %g nits (finite, in (0, 10000])", (double)cfg->white_nits);
+    if (cfg->reserved != 0) return bhr_fail(BHR_ERR_INVALID, "bhr_y4m_open_hdr: reserved must be 0, got %d", cfg->reserved);
+    return y4m_open(ctx, path, fps_num, fps_den, n_slots, cfg, out);
+}
+
+int32_t bhr_y4m_light_levels(bhr_y4m *s, double out[2]) {
+    if (!s || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_y4m_light_levels: bad argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    out[0] = s->max_cll;
+    out[1] = s->max_fall;
     return BHR_OK;
 }
 
@@ -459,9 +526,21 @@ int32_t bhr_y4m_submit(bhr_y4m *s) {
     bhr_ctx *ctx = s->ctx;
     int32_t rc = bhr_enter_frame(ctx);       // the stream that rendered the last frame (behind its post-passes)
     hipError_t e = hipSuccess;
-    // the conversion reads the f32 frame (a context that keeps only u8 rows gets it on demand); with dither on, the dithered u8 rows
-    if (rc == BHR_OK) rc = bhr_ensure_outputs(ctx, ctx->dither ? BHR_OUT_U8 : BHR_OUT_F32);
-    if (rc == BHR_OK) {
+    if (rc == BHR_OK && s->transfer) {
+        // an HDR stream converts the slot's HDR plane (hdr_stream.hip): BHR_ERR_STATE for a frame that kept none
+        bhr_y4m::Slot &sl = s->slots[slot];
+        if (s->timing) e = hipEventRecord(sl.k0, ctx->stream);
+        if (e == hipSuccess) rc = bhr_launch_hdr_yuv420p10(ctx, s->transfer, s->gain, s->scale, s->white_nits, (uint16_t *)sl.dev, sl.dev + s->levels_at);
+        if (rc == BHR_OK && e == hipSuccess && s->timing) e = hipEventRecord(sl.k1, ctx->stream);
+        if (rc == BHR_OK && e == hipSuccess) e = hipMemcpyAsync(sl.host, sl.dev, s->levels_at + 16, hipMemcpyDeviceToHost, ctx->stream);
+        if (rc == BHR_OK && e == hipSuccess) e = hipEventRecord(sl.ev, ctx->stream);
+        const int32_t rc_leave = bhr_leave_frame(ctx);
+        if (rc == BHR_OK) rc = rc_leave;
+    } else if (rc == BHR_OK) {
+        // the conversion reads the f32 frame (a context that keeps only u8 rows gets it on demand); with dither on, the dithered u8 rows
+        rc = bhr_ensure_outputs(ctx, ctx->dither ? BHR_OUT_U8 : BHR_OUT_F32);
+    }
+    if (rc == BHR_OK && !s->transfer) {
         dim3 block(32, 8), grid(((s->w >> 1) + 31) / 32, ((s->h >> 1) + 7) / 8);
         if (ctx->dither)
             hipLaunchKernelGGL(u8_to_yuv420_kernel, grid, block, 0, ctx->stream, bhr_slot(ctx).d_final_u8, s->slots[slot].dev, s->w, s->h);
@@ -516,8 +595,13 @@ void bhr_y4m_close(bhr_y4m *s) {
     (void)hipSetDevice(s->ctx->cfg.device);
     (void)bhr_enter(s->ctx);                             // joins the frame slots' streams: a slot's planes may still be a copy's source
     (void)hipStreamSynchronize(s->ctx->scene_stream);
+    if (s->timing && s->frames > 0)
+        fprintf(stderr, "bhr hdr stream: %lld frames of %dx%d, conversion kernel %.2f us per frame\n", (long long)s->frames, s->w, s->h,
+                1e3 * s->kernel_ms / (double)s->frames);
     for (auto &sl : s->slots) {
         if (sl.ev) (void)hipEventDestroy(sl.ev);
+        if (sl.k0) (void)hipEventDestroy(sl.k0);
+        if (sl.k1) (void)hipEventDestroy(sl.k1);
         if (sl.host) (void)hipHostFree(sl.host);
         if (sl.dev) (void)hipFree(sl.dev);
     }

@@ -423,9 +423,53 @@ def check_map_supersample(k, ray_map: bool = False, orbit_map: bool = False, shu
                          "(marched frames take --supersample)")
 
 
+VIDEO_HDRS = ("pq", "hlg")
+HDR_COLOR_TRC = {"pq": "smpte2084", "hlg": "arib-std-b67"}     # ffmpeg's names of the two transfers
+
+
+def check_video_hdr(video_hdr, hdr_white=203.0, hdr_exposure=0.0, width: int = 2, height: int = 2, world: int = 1,
+                    video_codec: str = "auto", video_stream: str = "auto"):
+    """What an HDR video stream takes (render_video(video_hdr=...)): "pq" or "hlg", a white level in (0, 10000] nits (PQ) and an
+    exposure of -16 .. 16 stops, even frame sizes, one rank, PNG frames (not video_codec="mjpeg") and a stream to write
+    (not video_stream="off").  Returns None without ``video_hdr``, else the ``hdr`` dict of output.Y4MStream.  Raises ValueError
+    before any device work."""
+    if video_hdr is None:
+        return None
+    if video_hdr not in VIDEO_HDRS:
+        raise ValueError(f"video_hdr must be one of {VIDEO_HDRS}, got {video_hdr!r}")
+    from .output import check_hdr
+    hdr = check_hdr(dict(transfer=video_hdr, exposure=hdr_exposure, white_nits=hdr_white))
+    if world > 1:
+        raise ValueError("the HDR stream is written by one rank in frame order: --video_hdr does not combine with several ranks")
+    if video_codec == "mjpeg":
+        raise ValueError("--video_hdr does not combine with --video_codec mjpeg: that mode writes no stream")
+    if video_stream == "off":
+        raise ValueError("--video_hdr is a video stream: it does not combine with --video_stream off")
+    if width % 2 or height % 2:
+        raise ValueError(f"the HDR stream is 4:2:0 and needs even frame sizes, got {width}x{height}")
+    return hdr
+
+
+def hdr_ffmpeg_args(video_hdr: str, output_path: str) -> List[str]:
+    """The command that encodes the HDR stream from its standard input: HEVC Main 10 with the stream's colour description
+    (BT.2020 primaries, PQ or HLG transfer, BT.2020 non-constant-luminance matrix, limited range) signalled in the file."""
+    if video_hdr not in VIDEO_HDRS:
+        raise ValueError(f"video_hdr must be one of {VIDEO_HDRS}, got {video_hdr!r}")
+    return ["ffmpeg", "-y", "-loglevel", "error", "-f", "yuv4mpegpipe", "-i", "-", "-c:v", "libx265", "-pix_fmt", "yuv420p10le",
+            "-color_primaries", "bt2020", "-color_trc", HDR_COLOR_TRC[video_hdr], "-colorspace", "bt2020nc", "-color_range", "tv",
+            output_path]
+
+
+def hdr_sidecar(hdr: dict, max_cll: float, max_fall: float, frames: int) -> dict:
+    """The record written beside an HDR stream (``<output stem>.hdr10.json``): what a remux step needs to signal the stream's
+    colour description and, for PQ, its content light levels, which are known only once the last frame is written."""
+    return {"transfer": hdr["transfer"], "white_nits": hdr["white_nits"], "exposure": hdr["exposure"], "primaries": "bt2020",
+            "matrix": "bt2020nc", "range": "limited", "max_cll": max_cll, "max_fall": max_fall, "frames": frames}
+
+
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
-                    shutter_map=False, map_supersample=1) -> dict:
+                    shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -449,6 +493,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(shutter_map=True)
     if map_supersample > 1:
         params.update(map_supersample=map_supersample)
+    if video_hdr is not None:
+        params.update(video_hdr=video_hdr, hdr_white=hdr_white, hdr_exposure=hdr_exposure)
     return params
 
 
@@ -485,7 +531,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  supersample_threshold: Optional[float] = None, video_codec: str = "auto", video_quality: int = 90,
                  bit_depth: int = 8, dither: str = "none", shutter: float = 0.0, shutter_samples: int = 8,
                  grade: Optional[dict] = None, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False,
-                 map_supersample: int = 1, **_deprecated_kwargs) -> None:
+                 map_supersample: int = 1, video_hdr: Optional[str] = None, hdr_white: float = 203.0, hdr_exposure: float = 0.0,
+                 **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -510,7 +557,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     mode the renderer's outputs selection is restored on return ("auto" leaves it at "u8", as it always has).
 
     ``bit_depth=16``: the frame files are 16-bit PNGs (bhr_sink_create_png16; on the device up to its width limit, else on the
-    host); the yuv420p stream stays 8-bit, and the PNG-in-MP4 fallback muxes the files as it muxes any PNG.  ``dither="blue"``:
+    host); the yuv420p stream stays 8-bit (``video_hdr`` is the 10-bit stream), and the PNG-in-MP4 fallback muxes the files as it muxes any PNG.  ``dither="blue"``:
     every 8-bit consumer of the loop -- PNG or JPEG frames, the yuv420p stream -- gets the blue-noise dithered rows
     (HipRenderer.set_dither; the renderer's mode is restored on return).  The progress record carries the two only when
     they are not the defaults, as it does the codec: a resume with other values starts over.
@@ -561,9 +608,25 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     (HipRenderer.build_ray_map(supersample=k)) -- k x k records per pixel, every frame from the map resolved with
     set_supersample's filter; ``supersample`` itself stays 1 with a map.  Refused with ValueError, before any device work, for
     another value or for k > 1 without one of the three maps (check_map_supersample).  The progress record carries
-    ``map_supersample`` when it is above 1, and a resume with another factor starts over."""
+    ``map_supersample`` when it is above 1, and a resume with another factor starts over.
+
+    ``video_hdr`` = "pq" or "hlg": the loop's stream is the HDR one (output.Y4MStream(hdr=...); include/bhr_output.h states the
+    formulas): 10-bit BT.2020 frames under that transfer, made on the device from every frame's unclipped scene-linear plane --
+    ``hdr_exposure`` stops applied, and under PQ scene value 1.0 shown at ``hdr_white`` nits -- while the frame files stay what
+    they would be without it: the SDR frames and the HDR stream come out of one render of each frame, whatever produces it
+    (marched, shutter, ray_map, orbit_map, shutter_map).  The renderer's grade is the caller's with keep_hdr, and without a
+    caller's grade {clip, 0 stops, linear, keep_hdr}, which gives the ungraded frame bit for bit; it is restored on return.
+    ``video_stream="auto"`` with an ``ffmpeg`` on PATH pipes the stream into hdr_ffmpeg_args(video_hdr, output_path) (libx265);
+    without one, or with "y4m", the stream is ``<output stem>.y4m`` and the MP4 is assembled from the SDR frames as before.
+    After the loop ``<output stem>.hdr10.json`` (hdr_sidecar) records the stream's colour description, its MaxCLL and MaxFALL
+    -- known only then -- and its frame count.  Refused with ValueError, before any device work: several ranks, a resume that
+    finds completed frames (a stream cannot be resumed), ``video_codec="mjpeg"``, ``video_stream="off"``, odd frame sizes.  The
+    progress record carries ``video_hdr``, ``hdr_white`` and ``hdr_exposure`` only when ``video_hdr`` is set."""
     check_map_supersample(map_supersample, ray_map, orbit_map, shutter_map)
     check_shutter(shutter, shutter_samples)
+    if video_stream not in ("auto", "y4m", "off"):
+        raise ValueError(f"video_stream must be 'auto', 'y4m' or 'off', got {video_stream!r}")
+    hdr = check_video_hdr(video_hdr, hdr_white, hdr_exposure, width, height, world, video_codec, video_stream)
     grade = check_grade(grade)
     if grade is not None:
         grade["keep_hdr"] = False
@@ -594,7 +657,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     submitted: List[int] = []
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
     params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither,
-                             shutter, shutter_samples, grade, ray_map, orbit_map, shutter_map, map_supersample)
+                             shutter, shutter_samples, grade, ray_map, orbit_map, shutter_map, map_supersample,
+                             video_hdr, hdr_white, hdr_exposure)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -635,6 +699,9 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                 done |= set(r.get("completed", []))
             completed = {f for f in done if os.path.isfile(os.path.join(temp_dir, f"frame_{f:04d}{ext}"))}
             print(f"Resuming: {len(completed)}/{n_frames} frames already rendered")
+    if hdr is not None and completed:
+        raise ValueError(f"--video_hdr does not resume: {len(completed)} frames are already rendered and a stream cannot be taken "
+                         "up in the middle; render without --resume")
 
     total_t0 = time.time()
     rendered = 0
@@ -656,27 +723,30 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     if dither != dither_before:
         renderer.set_dither(dither)
     grade_before = renderer.grade
+    if hdr is not None:
+        # the HDR stream reads the frame's scene-linear plane: the caller's grade, or the one that is the ungraded frame, keeps it
+        grade = dict(grade or check_grade(dict(tonemap="clip", exposure=0.0, transfer="linear")), keep_hdr=True)
     if grade is not None:
         renderer.set_grade(**grade)
-    if video_stream not in ("auto", "y4m", "off"):
-        raise ValueError(f"video_stream must be 'auto', 'y4m' or 'off', got {video_stream!r}")
     stream = encoder = None
     streamable = world == 1 and not completed and width % 2 == 0 and height % 2 == 0 and not mjpeg
-    if streamable and video_stream == "y4m":
-        stream = Y4MStream(renderer, os.path.splitext(output_path)[0] + ".y4m", fps)
-    elif streamable and video_stream == "auto" and assemble and shutil.which("ffmpeg"):
+    if streamable and video_stream == "auto" and assemble and shutil.which("ffmpeg"):
         import subprocess
-        encoder = subprocess.Popen(["ffmpeg", "-y", "-loglevel", "error", "-f", "yuv4mpegpipe", "-i", "-", "-c:v", "libx264",
+        encoder = subprocess.Popen(hdr_ffmpeg_args(video_hdr, output_path) if hdr is not None else
+                                   ["ffmpeg", "-y", "-loglevel", "error", "-f", "yuv4mpegpipe", "-i", "-", "-c:v", "libx264",
                                     "-pix_fmt", "yuv420p", output_path], stdin=subprocess.PIPE)
-        stream = Y4MStream(renderer, f"/proc/self/fd/{encoder.stdin.fileno()}", fps)
+        stream = Y4MStream(renderer, f"/proc/self/fd/{encoder.stdin.fileno()}", fps, hdr=hdr)
+    elif streamable and (video_stream == "y4m" or hdr is not None):
+        stream = Y4MStream(renderer, os.path.splitext(output_path)[0] + ".y4m", fps, hdr=hdr)
 
     # the loop's consumers read the quantised rows (PNG sink) and, with a yuv420p stream, the f32 frame: the V pass of every
     # frame stores exactly those (12 bytes per pixel less to write without a stream, 24 with the blur layer nobody reads)
     # (16-bit frames and dithered rows are quantised from the f32 frame by kernels of their own: the frame keeps f32)
+    # (the HDR stream reads the frame's HDR plane, which the grade stage stores: the frame's own stores are as without a stream)
     if bit_depth == 16:
         renderer.set_outputs("f32")
     else:
-        renderer.set_outputs("u8" if stream is None else "f32+u8")
+        renderer.set_outputs("u8" if stream is None or hdr is not None else "f32+u8")
     n_r, n_phi = renderer.dtex_h, renderer.dtex_w
     factories = init_lifecycle_system(renderer, n_r, n_phi, seed=42)
     dt = disk_rotation_speed
@@ -757,6 +827,12 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             n_streamed, _ = stream.drain()
         except Exception as e:
             stream, encoder = _drop_stream(stream, encoder, e), None
+    if stream is not None and hdr is not None:
+        max_cll, max_fall = stream.light_levels()
+        sidecar = os.path.splitext(output_path)[0] + ".hdr10.json"
+        with open(sidecar, "w") as f:
+            json.dump(hdr_sidecar(hdr, max_cll, max_fall, n_streamed), f)
+        print(f"HDR stream: {video_hdr}, MaxCLL {max_cll:.1f} nits, MaxFALL {max_fall:.1f} nits ({sidecar})")
     if stream is not None:
         stream.close()
         if encoder is not None:

@@ -250,36 +250,81 @@ def rgb_to_yuv420(rgb_u8: np.ndarray):
 
 
 def read_y4m(path: str):
-    """Minimal YUV4MPEG2 reader (4:2:0): -> (header dict, list of (Y, Cb, Cr) uint8 planes)."""
+    """Minimal YUV4MPEG2 reader (4:2:0): -> (header dict, list of (Y, Cb, Cr) uint8 planes).  A ``C420p10`` file (the HDR
+    stream) gives uint16 planes, from little-endian samples."""
     with open(path, "rb") as f:
         head = f.readline().decode("ascii").split()
         assert head[0] == "YUV4MPEG2", head
         tags = {t[0]: t[1:] for t in head[1:]}
         w, h = int(tags["W"]), int(tags["H"])
+        deep = tags.get("C") == "420p10"
+        dtype, nbytes = (np.dtype("<u2"), w * h * 3) if deep else (np.dtype(np.uint8), w * h * 3 // 2)
         frames = []
         while True:
             line = f.readline()
             if not line:
                 break
             assert line.startswith(b"FRAME"), line[:20]
-            buf = np.frombuffer(f.read(w * h * 3 // 2), dtype=np.uint8)
-            assert buf.size == w * h * 3 // 2, "truncated frame"
+            raw = f.read(nbytes)
+            assert len(raw) == nbytes, "truncated frame"
+            buf = np.frombuffer(raw, dtype=dtype)
+            if deep:
+                buf = buf.astype(np.uint16)
             frames.append((buf[:w * h].reshape(h, w), buf[w * h:w * h * 5 // 4].reshape(h // 2, w // 2),
                            buf[w * h * 5 // 4:].reshape(h // 2, w // 2)))
     return {"width": w, "height": h, "fps": tags["F"], "chroma": [t for t in head[1:] if t.startswith("C")][0],
             "tags": head[1:]}, frames
 
 
+HDR_TRANSFERS = ("pq", "hlg")
+HDR_WHITE_NITS = 203.0      # BT.2408's reference white: the display level of scene value 1.0 under PQ
+
+
+def check_hdr(hdr):
+    """The ``hdr`` of a Y4MStream -- None, or a dict with ``transfer`` ("pq" | "hlg") and any of ``exposure`` (stops, -16 .. 16)
+    and ``white_nits`` (PQ: the display level of scene value 1.0, in (0, 10000]) -- checked and completed with the defaults:
+    None or dict(transfer, exposure, white_nits).  Raises ValueError; needs no device."""
+    if hdr is None:
+        return None
+    if not isinstance(hdr, dict):
+        raise ValueError(f"hdr must be None or a dict, got {hdr!r}")
+    unknown = set(hdr) - {"transfer", "exposure", "white_nits"}
+    if unknown:
+        raise ValueError(f"unknown hdr settings {sorted(unknown)}")
+    transfer = hdr.get("transfer")
+    if transfer not in HDR_TRANSFERS:
+        raise ValueError(f"hdr transfer must be one of {HDR_TRANSFERS}, got {transfer!r}")
+    exposure, white = hdr.get("exposure", 0.0), hdr.get("white_nits", HDR_WHITE_NITS)
+    for name, v in (("exposure", exposure), ("white_nits", white)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"hdr {name} must be a number, got {v!r}")
+    if not (np.isfinite(exposure) and -16.0 <= exposure <= 16.0):
+        raise ValueError(f"hdr exposure must be between -16 and 16 stops, got {exposure!r}")
+    if transfer == "pq" and not (np.isfinite(white) and 0.0 < white <= 10000.0):
+        raise ValueError(f"hdr white_nits must be greater than 0 and at most 10000, got {white!r}")
+    return dict(transfer=transfer, exposure=float(exposure), white_nits=float(white))
+
+
 class Y4MStream:
     """Device frames -> one YUV4MPEG2 (yuv420p) stream, in submission order, without a PNG detour
-    (replaces the PNG -> imread -> libx264 assembly of render.py:4497-4503; include/bhr_output.h)."""
+    (replaces the PNG -> imread -> libx264 assembly of render.py:4497-4503; include/bhr_output.h).
 
-    def __init__(self, renderer, path: str, fps: int, slots: int = 8):
+    ``hdr`` = dict(transfer="pq" | "hlg", exposure=0.0, white_nits=203.0): the HDR stream instead (bhr_y4m_open_hdr): 10-bit
+    BT.2020 frames (``C420p10``) made from the scene-linear HDR plane of every submitted frame, which must have kept it
+    (set_grade(..., keep_hdr=True)); ``light_levels()`` gives its MaxCLL and MaxFALL."""
+
+    def __init__(self, renderer, path: str, fps: int, slots: int = 8, hdr=None):
+        self.hdr = check_hdr(hdr)
         self._lib = _lib.load()
         self._s = C.c_void_p()
         self._renderer = renderer
         os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-        _lib.check(self._lib.bhr_y4m_open(renderer._ctx, os.fsencode(path), int(fps), 1, slots, C.byref(self._s)))
+        if self.hdr is None:
+            _lib.check(self._lib.bhr_y4m_open(renderer._ctx, os.fsencode(path), int(fps), 1, slots, C.byref(self._s)))
+        else:
+            cfg = _lib.HdrStream(_lib.HDR_PQ if self.hdr["transfer"] == "pq" else _lib.HDR_HLG, self.hdr["exposure"],
+                                 self.hdr["white_nits"], 0)
+            _lib.check(self._lib.bhr_y4m_open_hdr(renderer._ctx, os.fsencode(path), int(fps), 1, slots, C.byref(cfg), C.byref(self._s)))
         import weakref
         if not hasattr(renderer, "_sinks"):
             renderer._sinks = []
@@ -292,6 +337,14 @@ class Y4MStream:
         frames, nbytes = C.c_int64(0), C.c_int64(0)
         _lib.check(self._lib.bhr_y4m_drain(self._s, C.byref(frames), C.byref(nbytes)))
         return frames.value, nbytes.value
+
+    def light_levels(self):
+        """(MaxCLL, MaxFALL) in nits of the frames written so far (call it after drain()): the largest pixel and the largest
+        frame mean of min(white_nits * max(R, G, B), 10000) over the linear BT.2020 values.  (0.0, 0.0) for an HLG stream,
+        which carries no such metadata, and for an 8-bit stream."""
+        out = (C.c_double * 2)()
+        _lib.check(self._lib.bhr_y4m_light_levels(self._s, out))
+        return float(out[0]), float(out[1])
 
     def close(self) -> None:
         if self._s:

@@ -549,7 +549,7 @@ BHR_API int32_t bhr_dither_matrix(uint16_t out[4096]);
  * x is fmaxf(((bg + disk) + blur) + flare, 0), the flare's term added without the upper clip.  keep_hdr != 0: the frame keeps
  * its plane h (scene-linear, before exposure, with the flare if it had one), one more (rows, W, 3) f32 buffer of the frame slot
  * from the first use on, read with bhr_read_layer(BHR_LAYER_HDR) -- BHR_ERR_STATE for a frame that did not keep it;
- * bhr_write_layer refuses the layer.
+ * bhr_write_layer refuses the layer.  The plane is also what the HDR video stream converts (bhr_output.h: bhr_y4m_open_hdr).
  * bhr_set_grade drains the frames in flight and applies to the frames rendered afterwards; frames in memory keep the outputs
  * they were rendered with.  BHR_ERR_INVALID, with the context as it was: op not in {0, 1, 2}, transfer not in {0, 1},
  * exposure_stops non-finite or outside [-16, 16], white non-finite or outside (0, 65504].  The stand-alone bhr_bloom and

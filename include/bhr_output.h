@@ -137,6 +137,41 @@ BHR_API int32_t bhr_y4m_drain(bhr_y4m *stream, int64_t *frames_written, int64_t 
 /* Drains, closes the file and frees the stream. */
 BHR_API void bhr_y4m_close(bhr_y4m *stream);
 
+/* HDR video stream (csrc/hdr_stream.hip): 10-bit BT.2020 Y'CbCr 4:2:0 with a PQ (SMPTE ST 2084) or HLG (BT.2100) transfer,
+ * made from the frame's scene-linear HDR plane h (bhr_set_grade with keep_hdr: BT.709 primaries, 0 <= h <= 65504, unclipped,
+ * with the flare if the frame had one) -- a consumer of that plane beside the grade stage, so the SDR frame files and this
+ * stream come out of one render of each frame.  bhr_y4m_open_hdr opens a stream that bhr_y4m_submit, _drain and _close serve
+ * like the 8-bit one; its header line is "YUV4MPEG2 W.. H.. F<num>:<den> Ip A1:1 C420p10 XCOLORRANGE=LIMITED" and a frame is
+ * "FRAME\n" + planar little-endian uint16 Y (W H) | Cb (W H / 4) | Cr: 3 W H bytes, what `ffmpeg -f yuv4mpegpipe` reads as
+ * yuv420p10le and x265 takes as it is (-color_primaries bt2020 -color_trc smpte2084 | arib-std-b67 -colorspace bt2020nc).
+ * Per pixel, all in f32, every operation rounded once (no contraction):
+ *   v       = h * gain                                    gain = (float)exp2((double)exposure_stops)
+ *   (R,G,B) = M . v, each row ((m0 r + m1 g) + m2 b)      BT.709 -> BT.2020 (BT.2087):
+ *                                                         0.6274 0.3293 0.0433 / 0.0691 0.9195 0.0114 / 0.0164 0.0880 0.8956
+ *   BHR_HDR_PQ   Y  = fminf(X * (white_nits / 10000), 1)  scene value 1.0 is white_nits on the display
+ *                E' = ((c1 + c2 Y^m1) / (1 + c3 Y^m1))^m2,  every power x^e evaluated as exp2f(e * log2f(x))
+ *                m1 = 2610/16384, m2 = 2523/4096*128, c1 = 3424/4096, c2 = 2413/4096*32, c3 = 2392/4096*32
+ *   BHR_HDR_HLG  E  = fminf(X * 0.265, 1)                 scene value 1.0 is the 75 % reference white (BT.2408)
+ *                E' = E <= 1/12 ? sqrtf(3 E) : a logf(12 E - b) + c     a = 0.17883277, b = 0.28466892, c = 0.55991073
+ *   Y'  = (0.2627 R' + 0.6780 G') + 0.0593 B'             BT.2020 non-constant luminance
+ *   DY  = clamp((int)floorf(876 Y' + 64.5f), 64, 940)
+ * Chroma, one pair per 2x2 block, centre sited as in the 8-bit stream: the mean R'G'B' of the four pixels, summed as
+ * ((a + b) + (c + d)) * 0.25f with a, b the upper and c, d the lower row, its own Y' as above, Cb = (B' - Y') / 1.8814,
+ * Cr = (R' - Y') / 1.4746, DC = clamp((int)floorf(896 C + 512.5f), 64, 960).
+ * Dither (bhr_set_dither) does not apply: the stream is quantised from floats, never from the context's u8 rows.
+ * Light levels (PQ only; HLG carries no such metadata and reports 0, 0): per pixel nits = fminf(white_nits * max(R, G, B), 10000);
+ * the stream keeps MaxCLL, the largest pixel over all frames written, and MaxFALL, the largest frame mean (the frame's sum is
+ * kept in binary64).  bhr_y4m_light_levels: out = {MaxCLL, MaxFALL} of the frames written so far; call it after a drain.
+ * bhr_y4m_submit on an HDR stream: BHR_ERR_STATE when the frame in the active slot kept no HDR plane.  bhr_y4m_open_hdr:
+ * BHR_ERR_INVALID for a transfer other than the two, exposure_stops non-finite or outside [-16, 16], for PQ white_nits
+ * non-finite or outside (0, 10000] (HLG ignores the field), reserved != 0, and what bhr_y4m_open refuses (odd sizes). */
+#define BHR_HDR_PQ 1
+#define BHR_HDR_HLG 2
+typedef struct { int32_t transfer; float exposure_stops; float white_nits; int32_t reserved; } bhr_hdr_stream;
+BHR_API int32_t bhr_y4m_open_hdr(bhr_ctx *ctx, const char *path, int32_t fps_num, int32_t fps_den, int32_t slots,
+                                 const bhr_hdr_stream *cfg, bhr_y4m **out);
+BHR_API int32_t bhr_y4m_light_levels(bhr_y4m *stream, double out[2]);
+
 #ifdef __cplusplus
 }
 #endif
