@@ -10,6 +10,7 @@ from __future__ import annotations
 import argparse
 import math
 import os
+from typing import Optional
 
 from .renderer import R_DISK_INNER_DEFAULT, R_DISK_OUTER_DEFAULT
 
@@ -63,6 +64,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--supersample_threshold", type=float, default=None,
                    help="adaptive supersampling: the k x k rays of --supersample only for the pixels whose largest difference to an "
                         "edge neighbour in the one-ray frame exceeds this value (omitted: every pixel)")
+    p.add_argument("--spin", type=float, default=0.0, metavar="A",
+                   help="spin of the hole, the dimensionless a/M with |A| <= 0.998 (default: 0, a Schwarzschild hole).  Positive: the "
+                        "hole turns with the disk's orbital motion; negative: a retrograde disk.  The spin axis is the disk normal.  "
+                        "Marched in Kerr-Schild form by a kernel of its own, whatever --math says.  Not with --disk_tilt, "
+                        "--anti_alias lod_radius, --disk_model v2 / v2_volume, --supersample_threshold, --shutter, the ray-map "
+                        "flags, --passes or --gpus > 1; plain --supersample works")
     p.add_argument("--video_stream", type=str, default="auto", choices=["auto", "y4m", "off"],
                    help="--video: also hand the frames to the encoder as a yuv420p stream converted on the device "
                         "(auto: pipe into ffmpeg when it is on PATH; y4m: write <output stem>.y4m; off: PNG frames only)")
@@ -153,6 +160,24 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    if args.spin != 0:
+        from .kerr import SPIN_MAX
+        if not abs(args.spin) <= SPIN_MAX:
+            p.error(f"--spin is a/M with |a/M| <= {SPIN_MAX}, got {args.spin}")
+        if args.disk_tilt != 0:
+            p.error("--spin does not combine with --disk_tilt other than 0: the spin axis is the disk normal")
+        if args.anti_alias != "disabled":
+            p.error("--spin does not combine with --anti_alias lod_radius: ray differentials around a spinning hole need Kerr's variational equations")
+        if args.disk_model != "texture":
+            p.error("--spin does not combine with --disk_model other than texture: the Kerr march shades the disk texture")
+        if args.supersample_threshold is not None:
+            p.error("--spin does not combine with --supersample_threshold: the Kerr march has no refinement kernels (plain --supersample works)")
+        if args.ray_map or args.orbit_map or args.shutter_map or args.passes is not None:
+            p.error("--spin does not combine with --ray_map, --orbit_map, --shutter_map or --passes: a ray map holds Schwarzschild rays")
+        if args.shutter > 0:
+            p.error("--spin does not combine with --shutter: shutter frames march Schwarzschild rays")
+        if args.gpus != 1:
+            p.error("--spin does not combine with --gpus other than 1: row-block tiles march Schwarzschild rays")
     if args.map_supersample > 1 and not (args.ray_map or args.orbit_map or args.shutter_map):
         p.error("--map_supersample needs --ray_map, --orbit_map or --shutter_map: it is a ray map's factor (marched frames take --supersample)")
     if args.shutter_map:
@@ -242,6 +267,20 @@ def grade_from_args(args):
     return dict(tonemap=args.tonemap, exposure=args.exposure, white=args.white, transfer=args.transfer)
 
 
+def spin_note(args) -> Optional[str]:
+    """A note for a disk that reaches inside the innermost stable orbit of its own sense of rotation; None otherwise."""
+    from . import kerr
+    spin = getattr(args, "spin", 0.0)
+    if spin == 0:
+        return None
+    isco = kerr.disk_isco(spin)
+    if args.disk_inner_radius >= isco:
+        return None
+    sense = "prograde" if spin > 0 else "retrograde"
+    return (f"Note: --ar1 {args.disk_inner_radius:g} lies inside the {sense} ISCO at {isco:.4f} r_s for spin {spin:g}: "
+            "matter there plunges, the disk model's circular orbits are a picture only")
+
+
 def validate_args(args) -> None:
     """Same checks and messages as render.py:4586-4616, plus the backend restrictions."""
     if not (0 < args.fov < 180):
@@ -320,6 +359,10 @@ def main(argv=None) -> int:
 
     width, height = RESOLUTIONS[args.resolution]
     fov = args.fov % 180
+    note = spin_note(args)
+    if note:
+        print(note)
+    spin_kw = {"spin": args.spin} if args.spin != 0 else {}      # without a spin the drivers are called as ever
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))
@@ -336,7 +379,7 @@ def main(argv=None) -> int:
             width, height, args.pov, fov, args.step_size, args.texture, args.n_stars, 2048, 1024, args.r_max, None,
             args.disk_inner_radius, args.disk_outer_radius, args.disk_tilt, args.lens_flare, args.anti_alias,
             args.aa_strength, args.disk_rotation_speed, device_index=local_rank, math=args.math, supersample=args.supersample,
-            supersample_threshold=args.supersample_threshold)
+            supersample_threshold=args.supersample_threshold, **spin_kw)
         print(f"Rendering video: {args.n_frames} frames at {width}x{height} (rank {rank}/{world})")
         drivers.render_video(renderer, width, height, n_frames=args.n_frames, fps=args.fps,
                              output_path=args.output, fov=fov, static_cam_pos=args.pov, orbit=args.orbit,
@@ -371,6 +414,6 @@ def main(argv=None) -> int:
         anti_alias=args.anti_alias, aa_strength=args.aa_strength, disk_rotation_speed=args.disk_rotation_speed,
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
-        grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes)
+        grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

@@ -1018,6 +1018,7 @@ static int32_t calibrate_slot_streams(bhr_ctx *ctx, const bhr_camera *cam, uint3
 
 int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_render: null argument");
+    BHR_TRY(bhr_kerr_check(ctx, flags, "bhr_render"));
     if ((ctx->ss > 1 || ctx->ada_k > 1) && (flags & (BHR_PERSISTENT | BHR_ROW_COSTS)))
         return bhr_fail(BHR_ERR_INVALID, "bhr_render: BHR_PERSISTENT and BHR_ROW_COSTS are not available with supersampling (factor %d)", ctx->ss > 1 ? ctx->ss : ctx->ada_k);
     BHR_HIP(hipSetDevice(ctx->cfg.device));
@@ -1033,6 +1034,7 @@ int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
 // It neither triggers nor counts towards the calibration of slot 1's stream (the frames that does times are bhr_render's).
 int32_t bhr_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags) {
     if (!ctx || !cams) return bhr_fail(BHR_ERR_INVALID, "bhr_render_shutter: null argument");
+    BHR_TRY(bhr_kerr_refuse(ctx, "bhr_render_shutter", "shutter frames march Schwarzschild rays"));
     if (n < 1 || n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "bhr_render_shutter: %d samples (1 .. %d)", n, BHR_SHUTTER_MAX_SAMPLES);
     if (ctx->rows != ctx->cfg.height)
         return bhr_fail(BHR_ERR_INVALID, "bhr_render_shutter: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
@@ -1237,6 +1239,66 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
         bhr_png_dev_free(ctx);
     }
     else return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: unknown option '%s'", name);
+    return BHR_OK;
+}
+
+// ---- the spinning hole (bhr_set_spin; csrc/ray_kerr.h, march_kerr.hip) ----------------------------------------------------------
+// What has no Kerr form in this version; every refusal names the combination.
+extern "C++" {
+int32_t bhr_kerr_refuse(const bhr_ctx *ctx, const char *who, const char *what) {
+    if (!ctx || !ctx->kerr_on) return BHR_OK;
+    return bhr_fail(BHR_ERR_INVALID, "%s: a spin is set (bhr_set_spin, a / M = %g) and %s", who, (double)ctx->kerr_spin, what);
+}
+static int32_t kerr_state_check(const bhr_ctx *ctx, uint32_t flags, const char *who, double spin) {
+    if (ctx->cfg.disk_tilt_deg != 0.0f)
+        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with a disk tilted by %g degrees: the spin axis is the disk normal, tilt must be 0", who, spin, (double)ctx->cfg.disk_tilt_deg);
+    if (ctx->cfg.anti_alias != 0)
+        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with anti_alias = 1: ray differentials around a spinning hole need Kerr's variational equations", who, spin);
+    if (ctx->disk_source != BHR_DISK_TEXTURE)
+        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with a Disk V2 source (%d): the Kerr march shades the disk texture", who, spin, ctx->disk_source);
+    if (ctx->ada_k > 1)
+        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with adaptive supersampling (factor %d): the Kerr march has no refinement kernels; use bhr_set_supersample", who, spin, ctx->ada_k);
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g on a row-block context (rows %d of %d): group and tile renders march Schwarzschild rays", who, spin, ctx->rows, ctx->cfg.height);
+    if (flags & BHR_PERSISTENT)
+        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with BHR_PERSISTENT: the Kerr march has the tile schedule only", who, spin);
+    if (flags & BHR_ROW_COSTS)
+        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with BHR_ROW_COSTS: the Kerr march fills no row-cost profile", who, spin);
+    return BHR_OK;
+}
+int32_t bhr_kerr_check(const bhr_ctx *ctx, uint32_t flags, const char *who) {
+    if (!ctx || !ctx->kerr_on) return BHR_OK;
+    return kerr_state_check(ctx, flags, who, (double)ctx->kerr_spin);
+}
+}  // extern "C++"
+
+int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: null ctx");
+    if (!(fabsf(a_over_m) <= 0.998f)) return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin a / M = %g (|a / M| <= 0.998)", (double)a_over_m);
+    const int32_t on = (a_over_m != 0.0f || force_kerr) ? 1 : 0;
+    if (on) BHR_TRY(kerr_state_check(ctx, 0, "bhr_set_spin", (double)a_over_m));
+    if (on == ctx->kerr_on && a_over_m == ctx->kerr_spin) return BHR_OK;
+    BHR_TRY(bhr_enter(ctx));            // behind the frames in flight, like every other change of what a frame is
+    ctx->kerr_on = on;
+    ctx->kerr_spin = on ? a_over_m : 0.0f;
+    // the counters name the kernel that marches a frame
+    int32_t v = 0, l = 0;
+    BHR_TRY(bhr_march_resources(on ? -1 : ctx->cfg.math_mode, on ? 0 : ctx->cfg.anti_alias, &v, &l));
+    ctx->counters.march_vgprs = v;
+    ctx->counters.march_lds_bytes = l;
+    return BHR_OK;
+}
+
+// {VGPRs, LDS bytes, scratch bytes per lane} of the Kerr march kernel (ss: its supersampled twin).  No context: host + hipFuncGetAttributes.
+int32_t bhr_kerr_resources(int32_t ss, int32_t out[3]) {
+    if (!out) return bhr_fail(BHR_ERR_INVALID, "bhr_kerr_resources: null argument");
+    const void *f = bhr_march_kernel_kerr(BHR_MK_TILE, 0, ss ? 1 : 0);
+    if (!f) return bhr_fail(BHR_ERR_STATE, "bhr_kerr_resources: no Kerr march kernel in this library");
+    hipFuncAttributes at;
+    BHR_HIP(hipFuncGetAttributes(&at, f));
+    out[0] = at.numRegs;
+    out[1] = (int32_t)at.sharedSizeBytes;
+    out[2] = (int32_t)at.localSizeBytes;
     return BHR_OK;
 }
 

@@ -107,6 +107,7 @@ void bhr_raymap_release(bhr_ctx *ctx) {
 
 int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
     if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: null ctx");
+    BHR_TRY(bhr_kerr_refuse(ctx, "bhr_raymap_render", "a ray map holds Schwarzschild rays"));
     if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
         return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", flags);
     if (!isfinite(t_offset)) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: t_offset is not finite");
@@ -121,6 +122,7 @@ int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
 int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, float *rot_c, float *rot_s) {
     const char *who = "bhr_raymap_render_view";
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    BHR_TRY(bhr_kerr_refuse(ctx, who, "a ray map holds Schwarzschild rays"));
     if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
         return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
     if (!isfinite(cam->t_offset)) return bhr_fail(BHR_ERR_INVALID, "%s: t_offset is not finite", who);
@@ -139,6 +141,7 @@ int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32
 int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned) {
     const char *who = "bhr_raymap_render_shutter";
     if (!ctx || !cams) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    BHR_TRY(bhr_kerr_refuse(ctx, who, "a ray map holds Schwarzschild rays"));
     if (n < 1 || n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "%s: %d samples (1 .. %d)", who, n, BHR_SHUTTER_MAX_SAMPLES);
     if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
         return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
@@ -179,6 +182,7 @@ extern "C" {
 
 int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: null argument");
+    BHR_TRY(bhr_kerr_refuse(ctx, "bhr_raymap_build", "a ray map holds Schwarzschild rays"));
     if (flags & ~(uint32_t)BHR_SKIP_DIFFERENTIALS) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: flags %u (BHR_SKIP_DIFFERENTIALS only)", flags);
     if (ctx->rows != ctx->cfg.height)
         return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);

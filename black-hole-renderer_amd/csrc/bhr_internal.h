@@ -111,6 +111,14 @@ struct BhrMarchArgs {
     float ss_inv;            // 1 / k^2
     int32_t out_width, out_rows;   // the output frame's row block: the store pitch and rows of bg / disk / sum
 };
+// The argument block of the Kerr object's kernels (march_kerr.hip): the march's block with the spinning hole's two numbers at
+// its end -- a = A M in r_s, and the horizon radius r_plus = (1 + sqrt(1 - A^2)) / 2 a ray is captured at (0 and 1 without a
+// spin).  A block of its own, because BhrMarchArgs is the whole explicit argument of every other march kernel: one more
+// field in it moves their hidden arguments, and with them the code of all of them (tools/code_object_diff.py).  The launcher
+// builds this block for every launch; the other kernels read its first sizeof(BhrMarchArgs) bytes.
+struct BhrKerrMarchArgs : BhrMarchArgs {
+    float kerr_a, kerr_rplus;
+};
 
 // A partial march launch: the tiles of `d_list` only.  bhr_launch_march_hybrid builds one for each of its launches (strict
 // list, fast list, fix list and the empty parts that bracket them) and passes it to bhr_launch_march (null: the whole block).
@@ -427,6 +435,10 @@ struct bhr_ctx {
     bhr_raymap *raymap;        // null until the first bhr_raymap_build
     int32_t raymap_slots;      // option "raymap_slots" / BHR_RAYMAP_SLOTS: crossings a map keeps per pixel (1..8, default 4), read by bhr_raymap_build
     int32_t raymap_ss;         // option "raymap_supersample" / BHR_RAYMAP_SUPERSAMPLE: the next map's own factor (1, 2, 4, 8; default 1), read by bhr_raymap_build
+
+    // bhr_set_spin: kerr_on = the march is the Kerr object's (a spin other than 0, or force_kerr); kerr_spin = A = a / M
+    int32_t kerr_on;
+    float kerr_spin;
 };
 
 // The active frame slot: the one bhr_activate_slot / bhr_render last pointed the launchers at.
@@ -505,6 +517,12 @@ const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);
 const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.hip -> march_strict.o
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.hip -> march_strict_ilp.o
 const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_raymap.hip -> march_raymap.o
+const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE, diff 0 only)
+// api.hip: what a context with a spin set (kerr_on) refuses, as BHR_ERR_INVALID naming the combination -- the context's own
+// state (tilt, anti-aliasing, Disk V2, adaptive supersampling) and `flags` of the call; `who`: the entry point.  BHR_OK without a spin.
+int32_t bhr_kerr_check(const bhr_ctx *ctx, uint32_t flags, const char *who);
+// api.hip: a call that has no Kerr form at all (ray maps, shutter frames, group and tile renders): BHR_ERR_INVALID with a spin set
+int32_t bhr_kerr_refuse(const bhr_ctx *ctx, const char *who, const char *what);
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
 int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss);                               // march_launch.hip: builds d_/h_tile_order of the frame marched with factor ss
 int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_march_call &call);             // hybrid.hip

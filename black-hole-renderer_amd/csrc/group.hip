@@ -483,6 +483,7 @@ int32_t bhr_group_render_subset(bhr_ctx **ctxs, int32_t n, const bhr_camera *cam
     int expect = 0;
     for (int k = 0; k < n; ++k) {
         if (!ctxs[k]) return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: null ctx %d", k);
+        BHR_TRY(bhr_kerr_refuse(ctxs[k], "bhr_group_render", "group and tile renders march Schwarzschild rays"));
         if (ctxs[k]->ss > 1 || ctxs[k]->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d is supersampled (row blocks render one sample per pixel)", k);
         if (ctxs[k]->grade_on)
             return bhr_fail(BHR_ERR_INVALID, "bhr_group_render: tile %d has a grade set (bhr_set_grade) and a group render stores its rows from inside the V pass; "
@@ -543,6 +544,7 @@ int32_t bhr_group_sync(bhr_ctx **ctxs, int32_t n) {
 // publishing `done`; a rank returns when all have (nobody stores into a neighbour's planes while they are still read).
 int32_t bhr_tile_export(bhr_ctx *ctx, uint32_t gather_flags, bhr_tile_handles *out) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_export: bad argument");
+    BHR_TRY(bhr_kerr_refuse(ctx, "bhr_tile_export", "group and tile renders march Schwarzschild rays"));
     if (ctx->ss > 1 || ctx->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_export: the context is supersampled (row blocks render one sample per pixel)");
     if (ctx->grade_on) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_export: the context has a grade set (bhr_set_grade) and a tile stores its rows from inside the V pass; switch the grade off");
     BHR_TRY(bhr_enter(ctx));
@@ -724,6 +726,7 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
 
 int32_t bhr_tile_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: bad argument");
+    BHR_TRY(bhr_kerr_refuse(ctx, "bhr_tile_render", "group and tile renders march Schwarzschild rays"));
     if (ctx->ss > 1 || ctx->ada_k > 1) return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the context is supersampled (row blocks render one sample per pixel)");
     if (ctx->grade_on)
         return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the context has a grade set (bhr_set_grade) and a tile stores its rows from inside the V pass; switch the grade off");

@@ -25,12 +25,14 @@
 // v_rsq/v_rcp/v_sqrt instead of IEEE sqrt + divide inside the RK4 stages, FMA contraction, and the
 // re-use of |new_pos| as the next step's |pos| (same value in the reference).
 //
-// The march's device source is five headers and four translation units, one per object (csrc/Makefile):
+// The march's device source is six headers and five translation units, one per object (csrc/Makefile):
 //   march_device.h      this file: vectors, exact-rounding sequences, samplers, shading, parking slots, pixel stores
 //   ray_strict.h        Ray<DIFF, SRC>, strict: every operation of the RK4 loop in the reference's order with IEEE sqrt and
 //                       divide, so that positions, step counts and hit points are bit-identical to a strict f32 evaluation
 //                       of render.py:2854-3006 (selected with bhr_config.math_mode = 1)
 //   ray_fast.h          Ray<DIFF, SRC>, fast: v_rsq/v_rcp/v_sqrt, FMA contraction, in-plane state, the ray's own clock
+//   ray_kerr.h          Ray<false, 0>, Kerr: a spinning hole in Kerr-Schild coordinates, RK4 on (x, p), its own sampler and g-factor
+//                       (bhr_set_spin); the Schwarzschild Rays above know nothing of it
 //   march_tile.h        the tile schedule: march_tile_body, its plain, supersampled and list kernels
 //   march_persistent.h  the persistent schedule
 //   march.hip            -> march.o             ray_fast.h, both schedules; fast-math
@@ -38,9 +40,10 @@
 //   march_strict_ilp.hip -> march_strict_ilp.o  ray_strict.h, tile schedule: the strict texture kernels and the fix kernel of
 //                                               a hybrid march; the strict flags and the ILP-first machine scheduler
 //   march_raymap.hip     -> march_raymap.o      ray_strict.h: the ray map's build and shade kernels; the ILP object's flags
+//   march_kerr.hip       -> march_kerr.o        ray_kerr.h, tile schedule, plain and supersampled; -ffp-contract=on, no fast-math
 // A translation unit includes the one Ray header it marches with (which includes this file), then the schedules it uses,
 // defines the kernels that are its own and ends with their table, by which the one host launcher (march_launch.hip) finds
-// them: bhr_march_kernel_fast / _strict / _strict_ilp / _raymap.
+// them: bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr.
 #pragma once
 #include "bhr_internal.h"
 #include "disk_v2_device.h"
@@ -48,7 +51,7 @@
 // The two places where shared code differs by arithmetic (BHR_BILERP, the accumulation in shade_hit) are keyed on
 // BHR_RAY_STRICT, which the Ray header sets before it includes this file; never on a command line.
 #ifndef BHR_RAY_STRICT
-#error "include ray_strict.h or ray_fast.h, not march_device.h"
+#error "include ray_strict.h, ray_fast.h or ray_kerr.h, not march_device.h"
 #endif
 #ifndef BHR_WAVE_STAMPS_BUILD
 #define BHR_WAVE_STAMPS_BUILD 0

@@ -1,8 +1,8 @@
 // march_launch.hip -- the host half of the ray march: every march launch goes through bhr_launch_march.
 //
-// The march's device code is four objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
-// with the ILP-first scheduler, march_raymap.hip; the layout: march_device.h); each object hands its kernels over through a
-// table (bhr_march_kernel_fast / _strict / _strict_ilp / _raymap).  This file resolves the
+// The march's device code is five objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
+// with the ILP-first scheduler, march_raymap.hip, march_kerr.hip; the layout: march_device.h); each object hands its kernels over
+// through a table (bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr).  This file resolves the
 // arithmetic, builds the kernel arguments, keeps the tile order, the ray-step counters and the timing events, and picks
 // the kernel of a launch (march_kernel).  What a launch works from is in its arguments -- the caller's bhr_march_call
 // (camera, flags, stream, timing slot, end-event policy, supersampling factor) and, for one list of a hybrid march, a
@@ -67,6 +67,7 @@ float fast_sqrt(float s) {
 // The kernel of a launch and its grid (fn null: the part only records its bracket events).
 //
 //   arithmetic     request                                              kernel (object)
+//   any            a spin is set (bhr_set_spin), whole block            march_kerr_kernel / march_kerr_ss_kernel (kerr)
 //   any            hybrid part with n <= 0, not the fix list            none
 //   strict         hybrid fix list (part->repair == 2)                  march_fix_kernel<diff> (strict_ilp)
 //   fast / strict  Disk V2 volume source                                march_tile_kernel<false, 2> (own object)
@@ -99,6 +100,11 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
     const bool persistent = (flags & BHR_PERSISTENT) != 0;
     const int ss = a.ss > 1;                                   // the supersampled twins (bhr_render refuses the schedules they lack)
     const auto own = math == BHR_MATH_FAST ? bhr_march_kernel_fast : bhr_march_kernel_strict;
+    // the spinning hole: one arithmetic, one schedule, no lists (what has no Kerr form was refused before anything was launched)
+    if (ctx->kerr_on) {
+        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = bhr_march_kernel_kerr(BHR_MK_TILE, diff, ss);
+        return k;
+    }
     if (part && part->n <= 0 && part->repair != 2) return k;
     if (part && part->repair == 2) {
         k.fn = bhr_march_kernel_strict_ilp(BHR_MK_FIX, diff, ss);
@@ -164,9 +170,11 @@ int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss) {
 }
 
 // registers / LDS of the kernel that marches a whole texture frame: the fast object's under fast arithmetic, the ILP
-// object's under strict and hybrid (bhr_create reports them)
+// object's under strict and hybrid (bhr_create reports them); math -1: the Kerr object's (bhr_set_spin)
 int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds) {
-    const void *f = math == BHR_MATH_FAST ? bhr_march_kernel_fast(BHR_MK_TILE, diff, 0) : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff, 0);
+    const void *f = math < 0                 ? bhr_march_kernel_kerr(BHR_MK_TILE, 0, 0)
+                    : math == BHR_MATH_FAST ? bhr_march_kernel_fast(BHR_MK_TILE, diff, 0)
+                                            : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff, 0);
     hipFuncAttributes at;
     BHR_HIP(hipFuncGetAttributes(&at, f));
     *vgprs = at.numRegs;
@@ -279,14 +287,21 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     const hipStream_t stream = call.stream;
     // a partial launch (part: one list of a hybrid march) marches the tiles of a caller-made list under the arithmetic the
     // caller chose; the first part records the start event and clears an untimed counter, the last part records the end event
-    const int math = part ? part->math : bhr_resolve_math(ctx, flags);
+    // with a spin set the context's math mode does not select the march: one launch of the Kerr object, its argument block the
+    // strict one's (the post-pass has followed the math mode, bhr_frame_begin)
+    const int math = part ? part->math : ctx->kerr_on ? BHR_MATH_STRICT : bhr_resolve_math(ctx, flags);
     if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, call);
     const bool fast = math == BHR_MATH_FAST;
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
     if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_render: no disk texture set (bhr_set_disk_texture)");
 
-    BhrMarchArgs a;
+    BhrKerrMarchArgs a;                 // the march's block, and behind it what the Kerr object's kernels alone read
     march_args(ctx, call, part, call.ss, fast, a);
+    {   // the spinning hole: a = A M with M = r_s / 2 and the horizon's radius, in binary64, each rounded once
+        const double A = ctx->kerr_on ? (double)ctx->kerr_spin : 0.0;
+        a.kerr_a = (float)(0.5 * A);
+        a.kerr_rplus = (float)(0.5 * (1.0 + sqrt(1.0 - A * A)));
+    }
     const bhr_fine_frame fr = bhr_fine(ctx, call.ss);
     const int slot = call.slot;
     const bool first_part = !part || part->first, last_part = !part || part->last;

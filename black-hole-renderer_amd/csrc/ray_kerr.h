@@ -1,0 +1,300 @@
+// ray_kerr.h -- the Kerr Ray of the march (march_kerr.o; see march_device.h): a spinning hole in Kerr-Schild coordinates.
+//
+// Units r_s = 1, M = 1/2; a = A M is the spin parameter (kerr(a).kerr_a), the spin axis is z = the normal of the untilted disk.
+// With rho2 = x.x, w = rho2 - a^2 and S = sqrt(w^2 + 4 a^2 z^2):
+//   r^2 = (w + S) / 2               (the Kerr-Schild radius; S = 2 r^2 - w = r^2 + a^2 cos^2 theta, so r^4 + a^2 z^2 = r^2 S)
+//   f   = r_s r^3 / (r^4 + a^2 z^2) = r / S
+//   l   = ((r x + a y) / Q, (r y - a x) / Q, z / r),   Q = r^2 + a^2
+//   H   = (p.p - 1) / 2 - f (1 + l.p)^2 / 2            (p_t = -1)
+//   dx/dl = p - f u l,   u = 1 + l.p
+//   dp/dl = -grad_x H = (u^2 / 2) grad f + f u grad (l.p)
+//   grad r = (r^2 x + a^2 z e_z) / (r S),   grad S = (2 w x + 4 a^2 z e_z) / S,   grad f = (grad r - f grad S) / S
+//   grad (l.p) = ((r p_x - a p_y) / Q, (a p_x + r p_y) / Q, p_z / r) + (d(l.p)/dr) grad r
+//   d(l.p)/dr  = (x p_x + y p_y) / Q - 2 r N / Q^2 - z p_z / r^2,   N = r (x p_x + y p_y) + a (y p_x - x p_y)
+// tests/kerr_ref.py states the same model in NumPy (rhs()) and checks the gradients against central differences of H.
+//
+// The state is (x, p), six components, RK4 with the reference's adaptive step on the Kerr-Schild radius.  What is conserved
+// along a ray (E = 1, L_z) is not carried.  The traced ray is the future-directed photon that leaves the camera with its
+// coordinate velocity along the pixel direction; by time reversal and a -> -a that is the image of a hole that turns with
+// this project's disk (v_hat = r_hat x n, clockwise seen from +z) for A > 0.  DESIGN.md "Kerr" has the conventions.
+//
+// No ray differentials (they would need the variational equations of this system) and one disk source, the texture at
+// level 0: Ray<false, 0> is the only instantiation.
+#pragma once
+#define BHR_RAY_STRICT 1   // the shared samplers in the reference's evaluation order (march_device.h: BHR_BILERP)
+#include "march_device.h"
+
+namespace {
+
+// The kernels of this object take the march's block with the hole's numbers behind it (bhr_internal.h: BhrKerrMarchArgs) and hand
+// it to the shared schedule as the BhrMarchArgs it is; the Kerr code reads the tail through this.
+__device__ __forceinline__ const BhrKerrMarchArgs &kerr(const BhrMarchArgs &a) { return static_cast<const BhrKerrMarchArgs &>(a); }
+
+// v_rsq of x and v_rcp of y back to back (march_device.h: rsq2 / rcp2 say why)
+__device__ __forceinline__ void rsq_rcp(float x, float y, float &rs, float &rc) {
+    asm("v_rsq_f32 %0, %2\n\tv_rcp_f32 %1, %3\n\ts_nop 0" : "=&v"(rs), "=&v"(rc) : "v"(x), "v"(y));
+}
+// sqrt(x) and 1 / sqrt(x) from the seed y = v_rsq(x): one Newton step each from the one residual e = 1 - x y^2
+__device__ __forceinline__ void sqrt_both(float x, float y, float &s, float &inv) {
+    const float s0 = x * y;
+    const float e = fmaf(-s0, y, 1.0f);
+    s = fmaf(0.5f * s0, e, s0);
+    inv = fmaf(0.5f * y, e, y);
+}
+
+// The Kerr-Schild geometry at a point: what the right-hand side and the termination test share.
+struct KerrGeom {
+    float w, S, iS, r2;
+};
+__device__ __forceinline__ KerrGeom kerr_geom(float a2, V3 x) {
+    KerrGeom g;
+    g.w = dot(x, x) - a2;
+    const float S2 = fmaf(g.w, g.w, 4.0f * a2 * (x.z * x.z));
+    sqrt_both(S2, q_rsq(S2), g.S, g.iS);
+    g.r2 = 0.5f * (g.w + g.S);
+    return g;
+}
+// dx/dl and dp/dl at (x, p)
+__device__ __forceinline__ void kerr_rhs(float a, float a2, V3 x, V3 p, V3 &v, V3 &dp, float &r_out) {
+    const KerrGeom g = kerr_geom(a2, x);
+    const float Q = g.r2 + a2;
+    float y_r, y_q;
+    rsq_rcp(g.r2, Q, y_r, y_q);
+    float r, ir;
+    sqrt_both(g.r2, y_r, r, ir);
+    const float iQ = rcp_rn_s(Q, y_q);
+    r_out = r;
+    const float f = r * g.iS;
+    const V3 l = mk((r * x.x + a * x.y) * iQ, (r * x.y - a * x.x) * iQ, x.z * ir);
+    const float u = 1.0f + dot(l, p);
+    const float fu = f * u;
+    v = mk(p.x - fu * l.x, p.y - fu * l.y, p.z - fu * l.z);
+    const float gg = ir * g.iS;
+    const V3 gr = mk(g.r2 * x.x * gg, g.r2 * x.y * gg, Q * x.z * gg);
+    const float w2 = 2.0f * g.w;
+    const V3 gf = mk((gr.x - f * (w2 * x.x * g.iS)) * g.iS, (gr.y - f * (w2 * x.y * g.iS)) * g.iS,
+                     (gr.z - f * ((w2 + 4.0f * a2) * x.z * g.iS)) * g.iS);
+    const float sxy = x.x * p.x + x.y * p.y;
+    const float N = r * sxy + a * (x.y * p.x - x.x * p.y);
+    const float dr = sxy * iQ - 2.0f * r * N * iQ * iQ - x.z * p.z * ir * ir;
+    const V3 gl = mk((r * p.x - a * p.y) * iQ + dr * gr.x, (a * p.x + r * p.y) * iQ + dr * gr.y, p.z * ir + dr * gr.z);
+    const float c1 = 0.5f * u * u;
+    dp = mk(c1 * gf.x + fu * gl.x, c1 * gf.y + fu * gl.y, c1 * gf.z + fu * gl.z);
+}
+__device__ __forceinline__ float kerr_radius(float a2, V3 x) {
+    const KerrGeom g = kerr_geom(a2, x);
+    return sqrt_rn(g.r2);
+}
+
+// Kerr's orbital frequency sqrt(M) / (r^1.5 + a sqrt(M)) with the reference's guard: sqrt(0.5 / (r^3 + 1e-6)) at a = 0
+__device__ __forceinline__ float kerr_omega(float r_safe, float a) {
+    const float sm = 0.70710678118654752f;   // sqrt(M)
+    return sm / (sqrtf(r_safe * r_safe * r_safe + 1e-6f) + a * sm);
+}
+
+// _sample_disk (render.py:2568-2600) at level 0 with the Boyer-Lindquist hit radius and Kerr's Omega in the roll
+// (march_device.h: sample_disk_level is the Schwarzschild sampler and stays as it is)
+__device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, float hit_x, float hit_y, float hit_r) {
+    const BhrScene &sc = a.sc;
+    float phi = atan2f(hit_y, hit_x);
+    const float r_safe = fmaxf(hit_r, 1e-3f);
+    phi = phi + a.t_offset * kerr_omega(r_safe, kerr(a).kerr_a);
+    while (phi < 0) phi += BHR_TWO_PI_F;
+    while (phi >= BHR_TWO_PI_F) phi -= BHR_TWO_PI_F;
+    const float u = phi / BHR_TWO_PI_F * (float)sc.n_phi;
+    const float v = (hit_r - a.r_inner) / (a.r_outer - a.r_inner) * (float)sc.n_r;
+    const int u0 = (int)floorf(u), v0 = (int)floorf(v);
+    const float fu = u - (float)u0, fv = v - (float)v0;
+    const int u0_w = pymod(u0, sc.n_phi), u1_w = pymod(u0 + 1, sc.n_phi);
+    const int v0_h = min(max(v0, 0), sc.n_r - 1), v1_h = min(max(v0 + 1, 0), sc.n_r - 1);
+    const float4 *t = sc.mips + sc.mip_off[0];
+    const int stride = sc.mip_w[0];
+    const float4 c00 = t[(size_t)v0_h * stride + u0_w], c10 = t[(size_t)v0_h * stride + u1_w];
+    const float4 c01 = t[(size_t)v1_h * stride + u0_w], c11 = t[(size_t)v1_h * stride + u1_w];
+    return make_float4(BHR_BILERP(c00.x, c10.x, c01.x, c11.x), BHR_BILERP(c00.y, c10.y, c01.y, c11.y),
+                       BHR_BILERP(c00.z, c10.z, c01.z, c11.z), BHR_BILERP(c00.w, c10.w, c01.w, c11.w));
+}
+
+// _apply_g_factor (render.py:2439-2516) for the untilted disk, unchanged but for the orbital frequency (Kerr's) and the
+// emitter's radius, which is the Boyer-Lindquist hit radius the frequency is a function of.  The exact Kerr g-factor
+// u^t (1 - Omega L_z) with frame dragging is left out.
+__device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color, float hit_x, float hit_y, float hit_r, V3 to_cam) {
+    const float rs_f = BHR_RS;
+    V3 cam_pos = ld3(a.cp);
+    asm volatile("" : "+v"(cam_pos.x));          // recomputed per hit, not kept across the march loop (march_device.h: apply_g_factor)
+    const float r_obs = sqrtf(dot(cam_pos, cam_pos));
+    const float r_em = hit_r;
+    const float r_safe = fmaxf(r_em, rs_f + 1e-3f);
+    const float omega = kerr_omega(r_safe, kerr(a).kerr_a);
+    const float lorentz = sqrtf(fmaxf(1.0f - rs_f / r_safe, 1e-6f));
+    const float beta = fminf(r_safe * omega / fmaxf(lorentz, 1e-6f), 0.99f);
+    const float gamma = 1.0f / sqrtf(fmaxf(1.0f - beta * beta, 1e-6f));
+    const float inv = 1.0f / sqrtf(hit_x * hit_x + hit_y * hit_y);
+    const float rx = inv * hit_x, ry = inv * hit_y;
+    float vx = ry, vy = -rx;                     // v_hat = r_hat x n, n = (0, 0, 1)
+    const float v_norm = sqrtf(vx * vx + vy * vy);
+    if (v_norm > 1e-6f) { vx = vx / v_norm; vy = vy / v_norm; } else { vx = 0.0f; vy = 1.0f; }
+    const float ti = 1.0f / sqrtf(dot(to_cam, to_cam));
+    const float cos_theta = vx * (ti * to_cam.x) + vy * (ti * to_cam.y);
+    const float denom = fmaxf(1.0f - beta * cos_theta, 1e-3f);
+    const float g_doppler = 1.0f / (gamma * denom);
+    const float grav_num = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_obs, rs_f + 1e-3f), 1e-6f));
+    const float grav_den = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_em, rs_f + 1e-3f), 1e-6f));
+    const float g = fminf(g_doppler * (grav_num / grav_den), BHR_G_FACTOR_CAP);
+    const float intensity = fmaxf(powf(g, BHR_G_LUMINOSITY_POWER), 0.0f);
+    float brightness = BHR_G_BRIGHTNESS_GAIN * intensity / (1.0f + intensity / BHR_G_FACTOR_CAP);
+    const float radial_span = fmaxf(a.r_outer - a.r_inner, 1e-3f);
+    const float radial_t = fminf(fmaxf((fmaxf(hit_r, a.r_inner) - a.r_inner) / radial_span, 0.0f), 1.0f);
+    const float radial_profile = powf(1.0f - radial_t, BHR_DISK_RADIAL_BRIGHTNESS_POWER);
+    brightness *= BHR_DISK_RADIAL_BRIGHTNESS_MIN + (BHR_DISK_RADIAL_BRIGHTNESS_MAX - BHR_DISK_RADIAL_BRIGHTNESS_MIN) * radial_profile;
+    const float wien_arg = 1.0f - 1.0f / fmaxf(g, 0.1f);
+    float r_scale = expf(2.21f * wien_arg);
+    const float g_scale = expf(2.72f * wien_arg);
+    float b_scale = expf(3.13f * wien_arg);
+    r_scale = fminf(r_scale / g_scale, 3.0f);
+    b_scale = fminf(b_scale / g_scale, 3.0f);
+    const V3 tint = disk_tint();
+    V3 out = mk(base_color.x * r_scale * tint.x * brightness, base_color.y * tint.y * brightness, base_color.z * b_scale * tint.z * brightness);
+    out.x = fminf(fmaxf(out.x, 0.0f), 10.0f);
+    out.y = fminf(fmaxf(out.y, 0.0f), 10.0f);
+    out.z = fminf(fmaxf(out.z, 0.0f), 10.0f);
+    return out;
+}
+
+// one disk crossing, shaded and composited front to back (render.py:2951-3002 without the mip levels)
+__device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam) {
+    const float hit_r = sqrtf(hit_x * hit_x + hit_y * hit_y - kerr(a).kerr_a * kerr(a).kerr_a);
+    if (!(a.r_outer >= hit_r && hit_r >= a.r_inner)) return;
+    const float4 rgba = kerr_sample_disk(a, hit_x, hit_y, hit_r);
+    const float base_alpha = fminf(rgba.w, 0.999f);
+    const float disk_alpha = 1.0f - powf(1.0f - base_alpha, BHR_DISK_ALPHA_GAIN);
+    const V3 col = kerr_g_factor(a, mk(rgba.x, rgba.y, rgba.z), hit_x, hit_y, hit_r, to_cam);
+    const float front = 1.0f - sh.alpha_total;
+    const float wgt = disk_alpha * front;
+    sh.accum = mk(sh.accum.x + col.x * wgt, sh.accum.y + col.y * wgt, sh.accum.z + col.z * wgt);
+    sh.alpha_total = 1.0f - front * (1.0f - disk_alpha);
+}
+
+template <bool DIFF, int SRC = 0>
+struct Ray {
+    static_assert(!DIFF && SRC == 0, "the Kerr march has no ray differentials and one disk source, the texture");
+    V3 x, p;
+    float r;       // Kerr-Schild radius of x
+    float affine;
+    Shade sh;
+    int n_pend;    // parked disk crossings (0..2), in the lane's LDS slots, oldest first
+    int step_count;
+    int done;      // 0 running, 2 captured or escaped (escaped() tells), 3 ran out of iterations, 4 empty lane
+    bool full;     // wave-uniform: some live lane has both its parking slots occupied
+
+    // The camera: the momentum of the future-directed photon whose coordinate velocity is parallel to the pixel direction d,
+    //   s = 1 / sqrt(1 - f (1 - (l.d)^2)),   Lam = (1 + s l.d) / (1 - f),   p = s d + f Lam l
+    // (then 1 + l.p = Lam and dx/dl = s d; H = 0).  Outside the loop: IEEE operations.
+    __device__ __forceinline__ void init(const BhrMarchArgs &a, int i, int j_local) {
+        V3 unused_x, unused_y;
+        const V3 d = pixel_ray<false>(a, i, j_local, unused_x, unused_y);
+        x = ld3(a.cp);
+        const float ka = kerr(a).kerr_a, a2 = ka * ka;
+        const float w = dot(x, x) - a2;
+        const float S = sqrtf(w * w + 4.0f * a2 * (x.z * x.z));
+        const float r2 = 0.5f * (w + S);
+        r = sqrtf(r2);
+        const float f = r / S, Q = r2 + a2;
+        const V3 l = mk((r * x.x + ka * x.y) / Q, (r * x.y - ka * x.x) / Q, x.z / r);
+        const float c = dot(l, d);
+        const float s = 1.0f / sqrtf(1.0f - f * (1.0f - c * c));
+        const float fl = f * ((1.0f + s * c) / (1.0f - f));
+        p = mk(s * d.x + fl * l.x, s * d.y + fl * l.y, s * d.z + fl * l.z);
+        affine = 0.0f;
+        sh.accum = mk(0, 0, 0);
+        sh.alpha_total = 0.0f;
+        sh.unsure = 0;
+        n_pend = 0;
+        full = false;
+        step_count = 0;
+        done = a.max_iter <= 0 ? 3 : 0;
+    }
+
+    // One RK4 step on (x, p).  The state is committed unconditionally, as in the strict Ray: a lane whose ray has ended
+    // leaves the loop and reads only what settle() and values() need.
+    __device__ __forceinline__ bool step(const BhrMarchArgs &a) {
+        const float ka = kerr(a).kerr_a, a2 = ka * ka;
+        // h = h_base dt_fac, the reference's step rule (render.py:2865-2868) on the Kerr-Schild radius; r_cap = r_s = 1
+        float r_safe;
+        asm("v_max_f32 %0, %1, %2" : "=v"(r_safe) : "v"(r), "v"(BHR_RS + 1e-3f));
+        float y_s, y_q;
+        rsq_rcp(r_safe, r_safe, y_s, y_q);
+        const float far_scale = __builtin_fminf(sqrt_rn_s(r_safe, y_s), 10.0f);
+        const float q = rcp_rn_s(r_safe, y_q);
+        const float near_damp = rcp_rn(fmaf(2.0f, q * q * q, 1.0f));
+        const float h = a.h_base * __builtin_amdgcn_fmed3f(far_scale * near_damp, 0.2f, 10.0f);
+        const float hh = 0.5f * h;
+
+        V3 v1, d1, v, d, sv, sd;
+        float rr;
+        kerr_rhs(ka, a2, x, p, v1, d1, rr);
+        kerr_rhs(ka, a2, fma3(hh, v1, x), fma3(hh, d1, p), v, d, rr);
+        sv = fma3(2.0f, v, v1);
+        sd = fma3(2.0f, d, d1);
+        kerr_rhs(ka, a2, fma3(hh, v, x), fma3(hh, d, p), v, d, rr);
+        sv = fma3(2.0f, v, sv);
+        sd = fma3(2.0f, d, sd);
+        kerr_rhs(ka, a2, fma3(h, v, x), fma3(h, d, p), v, d, rr);
+        const float h6 = h * (1.0f / 6.0f);
+        const V3 nx = fma3(h6, sv + v, x);
+        const V3 np = fma3(h6, sd + d, p);
+        const float rn = kerr_radius(a2, nx);
+
+        const float aff = affine + h;
+        // the ray goes on iff r_plus <= r <= r_escape and the affine parameter is within its limit
+        const bool ended = __builtin_amdgcn_fmed3f(rn, kerr(a).kerr_rplus, a.r_esc) != rn || aff > a.max_affine;
+        const bool crossing = x.z * nx.z < 0;              // the disk plane is z = 0 (no tilt with a spin)
+        if (__builtin_amdgcn_ballot_w64(crossing) != 0ull) {
+            if (!ended && crossing) {
+                const float t_frac = x.z / (x.z - nx.z + 1e-8f);
+                const float hx = x.x + t_frac * (nx.x - x.x);
+                const float hy = x.y + t_frac * (nx.y - x.y);
+                const float hit_r = sqrtf(hx * hx + hy * hy - a2);          // the Boyer-Lindquist radius in the plane
+                if (a.r_outer >= hit_r && hit_r >= a.r_inner) {
+                    Pending<false> hit;
+                    hit.hit_x = hx;
+                    hit.hit_y = hy;
+                    hit.to_cam = mk(-v1.x, -v1.y, -v1.z);                   // against dx/dl at the START of the step
+                    park_store<false>(n_pend, hit);                         // a free slot is guaranteed (march_tile_body flushes at 2)
+                    n_pend += 1;
+                }
+            }
+            full = __builtin_amdgcn_ballot_w64(n_pend == 2) != 0ull;
+        }
+        affine = aff;
+        x = nx;
+        p = np;
+        r = rn;
+        step_count += 1;               // the lane's own count: max_iter ends the loop by it (march_tile_body keeps its twin for the totals)
+        done = ended ? 2 : (step_count >= a.max_iter ? 3 : 0);
+        return true;
+    }
+
+    __device__ __forceinline__ void settle(const BhrMarchArgs &a) {
+        done = (__builtin_amdgcn_fmed3f(r, kerr(a).kerr_rplus, a.r_esc) != r || affine > a.max_affine) ? 2 : 3;
+    }
+    __device__ __forceinline__ bool escaped(const BhrMarchArgs &a) const { return done == 2 && !(r < kerr(a).kerr_rplus); }
+
+    __device__ __forceinline__ void flush_one(const BhrMarchArgs &a) {
+        if (n_pend > 0) {
+            const Pending<false> h = park_pop<false>(n_pend);
+            kerr_shade_hit(a, sh, h.hit_x, h.hit_y, h.to_cam);
+        }
+    }
+    // the escape direction is the direction of dx/dl at the last state
+    __device__ __forceinline__ V3 velocity(const BhrMarchArgs &a) const {
+        V3 v, d;
+        float rr;
+        kerr_rhs(kerr(a).kerr_a, kerr(a).kerr_a * kerr(a).kerr_a, x, p, v, d, rr);
+        return v;
+    }
+    __device__ __forceinline__ void finish_at(const BhrMarchArgs &a, int i, int j) { write_pixel(a, i, j, escaped(a), velocity(a), sh); }
+    __device__ __forceinline__ void values(const BhrMarchArgs &a, float bk[3], float dk[3]) const { pixel_values(a, escaped(a), velocity(a), sh, bk, dk); }
+};
+
+}  // namespace

@@ -1,0 +1,46 @@
+"""Radii of the Kerr metric in this project's units (r_s = 1, M = 1/2) and the checks of ``--spin`` / ``HipRenderer.set_spin``.
+
+The spin is A = a / M, |A| <= 0.998; positive turns with the disk's orbital motion.  No device is needed for any of this.
+"""
+import math
+
+M = 0.5
+SPIN_MAX = 0.998
+
+
+def check_spin(a_over_m) -> float:
+    a = float(a_over_m)
+    if not abs(a) <= SPIN_MAX:           # NaN included
+        raise ValueError(f"spin a/M must lie in [-{SPIN_MAX}, {SPIN_MAX}], got {a_over_m!r}")
+    return a
+
+
+def r_plus(a_over_m: float) -> float:
+    """Radius of the outer horizon, (1 + sqrt(1 - A^2)) / 2: 1 = r_s at A = 0."""
+    return 0.5 * (1.0 + math.sqrt(1.0 - a_over_m * a_over_m))
+
+
+def r_isco(a_over_m: float, prograde: bool) -> float:
+    """Innermost stable circular orbit (Bardeen, Press, Teukolsky 1972); prograde: the orbit turns with the hole."""
+    A = abs(a_over_m)
+    z1 = 1.0 + (1.0 - A * A) ** (1.0 / 3.0) * ((1.0 + A) ** (1.0 / 3.0) + (1.0 - A) ** (1.0 / 3.0))
+    z2 = math.sqrt(3.0 * A * A + z1 * z1)
+    root = math.sqrt(max((3.0 - z1) * (3.0 + z1 + 2.0 * z2), 0.0))
+    return M * (3.0 + z2 - root if prograde else 3.0 + z2 + root)
+
+
+def r_photon(a_over_m: float, prograde: bool) -> float:
+    """Equatorial circular photon orbit, 2 M (1 + cos(2/3 acos(-+A)))."""
+    A = abs(a_over_m)
+    return 2.0 * M * (1.0 + math.cos(2.0 / 3.0 * math.acos(-A if prograde else A)))
+
+
+def kerr_info(a_over_m: float) -> dict:
+    A = check_spin(a_over_m)
+    return dict(a=A * M, r_plus=r_plus(A), r_isco_prograde=r_isco(A, True), r_isco_retrograde=r_isco(A, False),
+                r_photon_pro=r_photon(A, True), r_photon_retro=r_photon(A, False))
+
+
+def disk_isco(a_over_m: float) -> float:
+    """The ISCO of the disk's own sense of rotation: prograde for A >= 0, retrograde for a disk that turns against the hole."""
+    return r_isco(a_over_m, a_over_m >= 0)

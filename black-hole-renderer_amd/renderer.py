@@ -92,7 +92,7 @@ class HipRenderer:
                  disk_rotation_speed=0.1, ignore_taichi_cache=False,
                  device_index: int = 0, rows: Optional[Sequence[int]] = None, math: str = "strict",
                  frame_slots: Optional[int] = None, outputs: Optional[str] = None, options: Optional[dict] = None,
-                 supersample: int = 1, supersample_threshold: Optional[float] = None):
+                 supersample: int = 1, supersample_threshold: Optional[float] = None, spin: float = 0.0):
         # supersample=k: k x k rays per pixel, box-filtered inside the march (bhr_set_supersample; include/bhr.h states the filter)
         # supersample_threshold=T: adaptive -- k x k rays only for the pixels whose k = 1 neighbours differ by more than T
         # (bhr_set_adaptive_supersample); None: every pixel
@@ -158,6 +158,15 @@ class HipRenderer:
         if supersample != 1 or supersample_threshold is not None:
             try:
                 self.set_supersample(supersample, supersample_threshold)
+            except Exception:
+                self.close()
+                raise
+
+        # spin=A: a spinning (Kerr) hole, A = a / M (set_spin)
+        self._spin, self._force_kerr = 0.0, False
+        if spin != 0.0:
+            try:
+                self.set_spin(spin)
             except Exception:
                 self.close()
                 raise
@@ -618,6 +627,32 @@ class HipRenderer:
             _lib.check(self._lib.bhr_set_adaptive_supersample(self._ctx, int(k), float(threshold)))
         self._supersample = int(k)
         self._supersample_threshold = None if threshold is None or int(k) == 1 else float(np.float32(threshold))
+
+    def set_spin(self, a: float, force_kerr: bool = False) -> None:
+        """A spinning (Kerr) hole for the frames rendered from now on (bhr_set_spin; include/bhr.h states the model): a is the
+        dimensionless a / M, |a| <= 0.998, positive with the disk's orbital motion; 0 is the Schwarzschild hole.  force_kerr
+        runs the Kerr kernel at spin 0 too (tests).  Refused (ValueError naming the combination) with a tilted disk,
+        anti-aliasing, a Disk V2 source, adaptive supersampling or a row-block context."""
+        from . import kerr
+        a = kerr.check_spin(a)
+        _lib.check(self._lib.bhr_set_spin(self._ctx, a, 1 if force_kerr else 0))
+        self._spin, self._force_kerr = a, bool(force_kerr)
+
+    @property
+    def spin(self) -> float:
+        return self._spin
+
+    def kerr_info(self) -> dict:
+        """Radii of the hole of the current spin, in r_s: a, r_plus, r_isco_prograde, r_isco_retrograde, r_photon_pro,
+        r_photon_retro (prograde: turning with the hole)."""
+        from . import kerr
+        return kerr.kerr_info(self._spin)
+
+    def kerr_resources(self, supersampled: bool = False) -> dict:
+        """Registers per lane, LDS and scratch bytes of the Kerr march kernel (bhr_kerr_resources)."""
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_kerr_resources(1 if supersampled else 0, out))
+        return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
 
     def adaptive_info(self) -> dict:
         """The last adaptively supersampled frame: pixels refined, how many of them were marched strict, pixels of the frame

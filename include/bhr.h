@@ -453,6 +453,26 @@ BHR_API int32_t bhr_set_adaptive_supersample(bhr_ctx *ctx, int32_t k, float thre
 /* out = {refined pixels |R| of the last adaptive frame, those of them marched with the strict arithmetic, pixels of the
  * frame}.  Synchronises.  BHR_ERR_STATE before the first frame rendered under bhr_set_adaptive_supersample(k > 1). */
 BHR_API int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]);
+/* A spinning (Kerr) hole.  a_over_m = A = a / M, |A| <= 0.998; 0 (the default) is the Schwarzschild hole every other entry
+ * point describes.  The spin axis is the normal of the untilted disk (+z); A > 0 turns with the disk's orbital motion
+ * (v_hat = r_hat x n), A < 0 against it.  With A != 0 -- or with force_kerr != 0 at any A, which tests use to run the Kerr
+ * kernel at spin 0 -- the frames of bhr_render are marched by the Kerr object (csrc/march_kerr.hip): RK4 on the six-component
+ * state (x, p) of the Hamiltonian H = (p.p - 1) / 2 - f (1 + l.p)^2 / 2 in Kerr-Schild coordinates, the reference's step rule
+ * on the Kerr-Schild radius, capture at r < r_plus = (1 + sqrt(1 - A^2)) / 2, the disk crossing gated on the Boyer-Lindquist
+ * radius sqrt(hx^2 + hy^2 - a^2) and shaded with the reference's g-factor model with Kerr's orbital frequency
+ * sqrt(M) / (r^1.5 + a sqrt(M)) (DESIGN.md "Kerr" states the model; tests/kerr_ref.py is its CPU reference).  bhr_config.math_mode
+ * then no longer selects the march (there is one Kerr arithmetic); the post-pass follows it as before.  Plain supersampling
+ * (bhr_set_supersample), lens flare, grading, every output path and sink work as for any frame.  A = 0 with force_kerr = 0
+ * launches exactly the kernels a context that never called this launches.  Ordered behind the frames in flight.
+ * BHR_ERR_INVALID, each with a message that names the combination: |A| > 0.998 or NaN; with a spin set (A != 0 or forced), by
+ * this call or by the call that meets it -- a tilted disk, anti_alias = 1, a Disk V2 source, adaptive supersampling, a
+ * row-block context (bhr_group_render*, bhr_tile_export, bhr_tile_render), bhr_render with BHR_PERSISTENT or BHR_ROW_COSTS,
+ * bhr_render_shutter, bhr_raymap_build and the three bhr_raymap_render* calls. */
+BHR_API int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr);
+/* out = {VGPRs per lane, LDS bytes per block, scratch (private segment) bytes per lane} of the Kerr march kernel
+ * (supersampled != 0: of its supersampled twin), from hipFuncGetAttributes.  After a frame marched with a spin set,
+ * bhr_counters.march_vgprs / march_lds_bytes are that kernel's too. */
+BHR_API int32_t bhr_kerr_resources(int32_t supersampled, int32_t out[3]);
 /* The library's switches.  Each has an environment variable that bhr_create reads ONCE (no entry point calls getenv
  * afterwards) and can be changed per context later with this call -- what tests and A/B tools use:
  *   "bloom_split"     BHR_BLOOM_SPLIT     -1 post-pass by arithmetic (exact f32 under strict, split f16 under fast / hybrid), 0 / 1 force
