@@ -22,6 +22,7 @@ DITHER_NONE, DITHER_BLUE = 0, 1
 GRADE_CLIP, GRADE_REINHARD, GRADE_ACES = 0, 1, 2
 TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
 HDR_PQ, HDR_HLG = 1, 2
+REDSHIFT_MODEL, REDSHIFT_EXACT = 0, 1
 RAYMAP_STEPS, RAYMAP_STATUS, RAYMAP_ESCAPE_DIR, RAYMAP_CROSSINGS, RAYMAP_HITS = 0, 1, 2, 3, 4
 
 # every symbol include/bhr.h declares (tests check the .so exports exactly these)
@@ -30,7 +31,7 @@ SYMBOLS = (
     "bhr_set_skybox", "bhr_skybox_add_glow", "bhr_skybox_build", "bhr_get_skybox", "bhr_set_disk_texture", "bhr_get_disk_texture", "bhr_get_disk_mip", "bhr_num_mip_levels",
     "bhr_bg_init", "bhr_generate_background", "bhr_set_entity_staging", "bhr_set_comp", "bhr_read_comp",
     "bhr_fill_comp_slice", "bhr_set_compose_stats", "bhr_compose_texture", "bhr_eval_noise", "bhr_render", "bhr_render_shutter",
-    "bhr_set_spin", "bhr_kerr_resources",
+    "bhr_set_spin", "bhr_kerr_resources", "bhr_set_redshift", "bhr_kerr_redshift_resources",
     "bhr_raymap_build", "bhr_raymap_render", "bhr_raymap_render_view", "bhr_raymap_render_shutter", "bhr_raymap_read", "bhr_raymap_get_info", "bhr_raymap_free",
     "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_read_final_u16", "bhr_set_dither", "bhr_dither_matrix", "bhr_set_grade", "bhr_grade_frame", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
     "bhr_stats_prepare", "bhr_stats_select", "bhr_stats_row_statistics",
@@ -154,6 +155,8 @@ def load() -> C.CDLL:
     lib.bhr_adaptive_info.argtypes = [P, C.POINTER(C.c_int64)]
     lib.bhr_set_spin.argtypes = [P, C.c_float, I32]
     lib.bhr_kerr_resources.argtypes = [I32, C.POINTER(C.c_int32)]
+    lib.bhr_set_redshift.argtypes = [P, I32]
+    lib.bhr_kerr_redshift_resources.argtypes = [I32, I32, C.POINTER(C.c_int32)]
     lib.bhr_set_option.argtypes = [P, C.c_char_p, C.c_double]
     lib.bhr_debug_read.argtypes = [P, I32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
     lib.bhr_lens_flare.argtypes = [P]

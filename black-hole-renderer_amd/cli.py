@@ -70,6 +70,12 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "Marched in Kerr-Schild form by a kernel of its own, whatever --math says.  Not with --disk_tilt, "
                         "--anti_alias lod_radius, --disk_model v2 / v2_volume, --supersample_threshold, --shutter, the ray-map "
                         "flags, --passes or --gpus > 1; plain --supersample works")
+    p.add_argument("--redshift", type=str, default="model", choices=["model", "exact"],
+                   help="redshift of the disk around the hole of --spin.  model (default): the reference's g-factor model with "
+                        "Kerr's orbital frequency.  exact: the g-factor of the Kerr metric -- frame dragging, the Doppler term from "
+                        "the photon's own angular momentum, and gas that plunges inside the ISCO with the ISCO orbit's energy and "
+                        "angular momentum.  It is the Kerr kernel's: with --spin 0 the Schwarzschild hole is marched by it too, "
+                        "and what --spin does not combine with, --redshift exact does not either")
     p.add_argument("--video_stream", type=str, default="auto", choices=["auto", "y4m", "off"],
                    help="--video: also hand the frames to the encoder as a yuv420p stream converted on the device "
                         "(auto: pipe into ffmpeg when it is on PATH; y4m: write <output stem>.y4m; off: PNG frames only)")
@@ -160,24 +166,26 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
-    if args.spin != 0:
+    if args.spin != 0 or args.redshift == "exact":
         from .kerr import SPIN_MAX
+        # the Kerr march: asked for by a spin, or by the exact redshift at spin 0
+        who = "--spin" if args.spin != 0 else "--redshift exact (the Kerr march, as with --spin)"
         if not abs(args.spin) <= SPIN_MAX:
             p.error(f"--spin is a/M with |a/M| <= {SPIN_MAX}, got {args.spin}")
         if args.disk_tilt != 0:
-            p.error("--spin does not combine with --disk_tilt other than 0: the spin axis is the disk normal")
+            p.error(f"{who} does not combine with --disk_tilt other than 0: the spin axis is the disk normal")
         if args.anti_alias != "disabled":
-            p.error("--spin does not combine with --anti_alias lod_radius: ray differentials around a spinning hole need Kerr's variational equations")
+            p.error(f"{who} does not combine with --anti_alias lod_radius: ray differentials around a spinning hole need Kerr's variational equations")
         if args.disk_model != "texture":
-            p.error("--spin does not combine with --disk_model other than texture: the Kerr march shades the disk texture")
+            p.error(f"{who} does not combine with --disk_model other than texture: the Kerr march shades the disk texture")
         if args.supersample_threshold is not None:
-            p.error("--spin does not combine with --supersample_threshold: the Kerr march has no refinement kernels (plain --supersample works)")
+            p.error(f"{who} does not combine with --supersample_threshold: the Kerr march has no refinement kernels (plain --supersample works)")
         if args.ray_map or args.orbit_map or args.shutter_map or args.passes is not None:
-            p.error("--spin does not combine with --ray_map, --orbit_map, --shutter_map or --passes: a ray map holds Schwarzschild rays")
+            p.error(f"{who} does not combine with --ray_map, --orbit_map, --shutter_map or --passes: a ray map holds Schwarzschild rays")
         if args.shutter > 0:
-            p.error("--spin does not combine with --shutter: shutter frames march Schwarzschild rays")
+            p.error(f"{who} does not combine with --shutter: shutter frames march Schwarzschild rays")
         if args.gpus != 1:
-            p.error("--spin does not combine with --gpus other than 1: row-block tiles march Schwarzschild rays")
+            p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march Schwarzschild rays")
     if args.map_supersample > 1 and not (args.ray_map or args.orbit_map or args.shutter_map):
         p.error("--map_supersample needs --ray_map, --orbit_map or --shutter_map: it is a ray map's factor (marched frames take --supersample)")
     if args.shutter_map:
@@ -271,11 +279,15 @@ def spin_note(args) -> Optional[str]:
     """A note for a disk that reaches inside the innermost stable orbit of its own sense of rotation; None otherwise."""
     from . import kerr
     spin = getattr(args, "spin", 0.0)
-    if spin == 0:
+    exact = getattr(args, "redshift", "model") == "exact"
+    if spin == 0 and not exact:
         return None
     isco = kerr.disk_isco(spin)
     if args.disk_inner_radius >= isco:
         return None
+    if exact:
+        return (f"Note: --ar1 {args.disk_inner_radius:g} lies inside the ISCO at {isco:.4f} r_s for spin {spin:g}: --redshift exact "
+                "shades the matter there as gas that plunges with the ISCO orbit's energy and angular momentum")
     sense = "prograde" if spin > 0 else "retrograde"
     return (f"Note: --ar1 {args.disk_inner_radius:g} lies inside the {sense} ISCO at {isco:.4f} r_s for spin {spin:g}: "
             "matter there plunges, the disk model's circular orbits are a picture only")
@@ -363,6 +375,8 @@ def main(argv=None) -> int:
     if note:
         print(note)
     spin_kw = {"spin": args.spin} if args.spin != 0 else {}      # without a spin the drivers are called as ever
+    if args.redshift != "model":
+        spin_kw["redshift"] = args.redshift
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))

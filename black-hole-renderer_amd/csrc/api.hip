@@ -1277,29 +1277,56 @@ int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr) {
     if (!(fabsf(a_over_m) <= 0.998f)) return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin a / M = %g (|a / M| <= 0.998)", (double)a_over_m);
     const int32_t on = (a_over_m != 0.0f || force_kerr) ? 1 : 0;
     if (on) BHR_TRY(kerr_state_check(ctx, 0, "bhr_set_spin", (double)a_over_m));
+    if (!on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin 0 without force_kerr while the exact redshift is set (bhr_set_redshift): it is a Kerr kernel's; set BHR_REDSHIFT_MODEL first");
     if (on == ctx->kerr_on && a_over_m == ctx->kerr_spin) return BHR_OK;
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight, like every other change of what a frame is
     ctx->kerr_on = on;
     ctx->kerr_spin = on ? a_over_m : 0.0f;
     // the counters name the kernel that marches a frame
     int32_t v = 0, l = 0;
-    BHR_TRY(bhr_march_resources(on ? -1 : ctx->cfg.math_mode, on ? 0 : ctx->cfg.anti_alias, &v, &l));
+    BHR_TRY(bhr_march_resources(on ? (ctx->kerr_redshift == BHR_REDSHIFT_EXACT ? -2 : -1) : ctx->cfg.math_mode, on ? 0 : ctx->cfg.anti_alias, &v, &l));
     ctx->counters.march_vgprs = v;
     ctx->counters.march_lds_bytes = l;
     return BHR_OK;
 }
 
+int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_redshift: null ctx");
+    if (mode != BHR_REDSHIFT_MODEL && mode != BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_set_redshift: unknown mode %d (BHR_REDSHIFT_MODEL = 0, BHR_REDSHIFT_EXACT = 1)", mode);
+    if (mode == BHR_REDSHIFT_EXACT && !ctx->kerr_on)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_set_redshift: the exact redshift without the Kerr march: set a spin, or force_kerr at spin 0, first (bhr_set_spin)");
+    if (mode == ctx->kerr_redshift) return BHR_OK;
+    BHR_TRY(bhr_enter(ctx));            // behind the frames in flight
+    ctx->kerr_redshift = mode;
+    if (ctx->kerr_on) {                 // the counters name the kernel that marches a frame
+        int32_t v = 0, l = 0;
+        BHR_TRY(bhr_march_resources(mode == BHR_REDSHIFT_EXACT ? -2 : -1, 0, &v, &l));
+        ctx->counters.march_vgprs = v;
+        ctx->counters.march_lds_bytes = l;
+    }
+    return BHR_OK;
+}
+
 // {VGPRs, LDS bytes, scratch bytes per lane} of the Kerr march kernel (ss: its supersampled twin).  No context: host + hipFuncGetAttributes.
-int32_t bhr_kerr_resources(int32_t ss, int32_t out[3]) {
-    if (!out) return bhr_fail(BHR_ERR_INVALID, "bhr_kerr_resources: null argument");
-    const void *f = bhr_march_kernel_kerr(BHR_MK_TILE, 0, ss ? 1 : 0);
-    if (!f) return bhr_fail(BHR_ERR_STATE, "bhr_kerr_resources: no Kerr march kernel in this library");
+static int32_t kerr_kernel_resources(const char *who, bhr_march_kernel k, int32_t ss, int32_t out[3]) {
+    if (!out) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    const void *f = bhr_march_kernel_kerr(k, 0, ss ? 1 : 0);
+    if (!f) return bhr_fail(BHR_ERR_STATE, "%s: no Kerr march kernel in this library", who);
     hipFuncAttributes at;
     BHR_HIP(hipFuncGetAttributes(&at, f));
     out[0] = at.numRegs;
     out[1] = (int32_t)at.sharedSizeBytes;
     out[2] = (int32_t)at.localSizeBytes;
     return BHR_OK;
+}
+int32_t bhr_kerr_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_kerr_resources", BHR_MK_TILE, ss, out); }
+// ... of the kernels of a redshift mode (bhr_set_redshift)
+int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t ss, int32_t out[3]) {
+    if (mode != BHR_REDSHIFT_MODEL && mode != BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_kerr_redshift_resources: unknown mode %d (BHR_REDSHIFT_MODEL = 0, BHR_REDSHIFT_EXACT = 1)", mode);
+    return kerr_kernel_resources("bhr_kerr_redshift_resources", mode == BHR_REDSHIFT_EXACT ? BHR_MK_KERR_EXACT : BHR_MK_TILE, ss, out);
 }
 
 // Both supersampling settings: `ss` rays per pixel everywhere (ada_k = 0), or one ray per pixel and ada_k x ada_k where the

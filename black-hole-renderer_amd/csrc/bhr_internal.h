@@ -119,6 +119,13 @@ struct BhrMarchArgs {
 struct BhrKerrMarchArgs : BhrMarchArgs {
     float kerr_a, kerr_rplus;
 };
+// The argument block of the Kerr object's exact-redshift kernels (bhr_set_redshift, BHR_REDSHIFT_EXACT): the Kerr block with
+// the ISCO of the disk's sense of rotation behind it -- its radius and the energy -u_t and angular momentum u_phi of its
+// orbit, which the gas inside it keeps (ray_kerr.h: kerr_g_exact).  Again a block of its own, for the reason above: the two
+// model kernels take BhrKerrMarchArgs by value and stay what they were.
+struct BhrKerrExactMarchArgs : BhrKerrMarchArgs {
+    float isco_r, isco_e, isco_l;
+};
 
 // A partial march launch: the tiles of `d_list` only.  bhr_launch_march_hybrid builds one for each of its launches (strict
 // list, fast list, fix list and the empty parts that bracket them) and passes it to bhr_launch_march (null: the whole block).
@@ -170,6 +177,8 @@ enum bhr_march_kernel {
     BHR_MK_RAYMAP_SHADE_ROT,  // raymap_shade_kernel<diff, true>: the same with the records turned about z       raymap
     BHR_MK_RAYMAP_SHUTTER,      // raymap_shade_shutter_kernel<diff, false>: the mean of n such frames, one launch   raymap
     BHR_MK_RAYMAP_SHUTTER_ROT,  // raymap_shade_shutter_kernel<diff, true>: each sample turned about z by its own angle  raymap
+    // the Kerr object's exact-redshift kernels (march_kerr.hip; the model ones are its BHR_MK_TILE)
+    BHR_MK_KERR_EXACT,    // march_kerr_exact_kernel / march_kerr_exact_ss_kernel                                   kerr
     // (ss: BUILD, SHADE and SHADE_ROT have twins for a supersampled map, raymap_build_kernel<DIFF, true> / raymap_shade_ss_kernel; the shutter kernels have none)
 };
 
@@ -439,6 +448,7 @@ struct bhr_ctx {
     // bhr_set_spin: kerr_on = the march is the Kerr object's (a spin other than 0, or force_kerr); kerr_spin = A = a / M
     int32_t kerr_on;
     float kerr_spin;
+    int32_t kerr_redshift;     // bhr_set_redshift: BHR_REDSHIFT_MODEL (0) or BHR_REDSHIFT_EXACT, which needs kerr_on
 };
 
 // The active frame slot: the one bhr_activate_slot / bhr_render last pointed the launchers at.
@@ -517,7 +527,7 @@ const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);
 const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.hip -> march_strict.o
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.hip -> march_strict_ilp.o
 const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_raymap.hip -> march_raymap.o
-const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE, diff 0 only)
+const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
 // api.hip: what a context with a spin set (kerr_on) refuses, as BHR_ERR_INVALID naming the combination -- the context's own
 // state (tilt, anti-aliasing, Disk V2, adaptive supersampling) and `flags` of the call; `who`: the entry point.  BHR_OK without a spin.
 int32_t bhr_kerr_check(const bhr_ctx *ctx, uint32_t flags, const char *who);

@@ -1,5 +1,5 @@
 // march_kerr.hip -> march_kerr.o: the march around a spinning hole (ray_kerr.h) in the tile schedule, one ray per pixel and
-// the supersampled twin.  Built with FMA contraction and without fast-math (csrc/Makefile says why).
+// the supersampled twin, each with the model redshift and with the exact one (bhr_set_redshift).  Built with FMA contraction and without fast-math (csrc/Makefile says why).
 #include "ray_kerr.h"
 #include "march_tile.h"
 
@@ -12,12 +12,22 @@ __global__ __launch_bounds__(256) void march_kerr_kernel(BhrKerrMarchArgs a) {
 __global__ __launch_bounds__(256) void march_kerr_ss_kernel(BhrKerrMarchArgs a) {
     march_tile_body<false, 0, false, false, true>(a, wave_slot());
 }
+// the same two over the Kerr Ray of the exact redshift, with the ISCO's numbers behind the Kerr block
+__global__ __launch_bounds__(256) void march_kerr_exact_kernel(BhrKerrExactMarchArgs a) {
+    march_tile_body<false, KERR_EXACT, false, false>(a, wave_slot());
+}
+__global__ __launch_bounds__(256) void march_kerr_exact_ss_kernel(BhrKerrExactMarchArgs a) {
+    march_tile_body<false, KERR_EXACT, false, false, true>(a, wave_slot());
+}
 
 }  // namespace
 
 // ---- the kernels of this object, by the launcher's names (march_launch.hip); null: not in this object ----------
-// The Kerr march has the texture source and no differentials: BHR_MK_TILE with diff = 0 is all there is.
+// The Kerr march has the texture source and no differentials: BHR_MK_TILE (the model redshift) and BHR_MK_KERR_EXACT with
+// diff = 0 are all there is.
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss) {
-    if (k != BHR_MK_TILE || diff) return nullptr;
-    return ss ? (const void *)march_kerr_ss_kernel : (const void *)march_kerr_kernel;
+    if (diff) return nullptr;
+    if (k == BHR_MK_TILE) return ss ? (const void *)march_kerr_ss_kernel : (const void *)march_kerr_kernel;
+    if (k == BHR_MK_KERR_EXACT) return ss ? (const void *)march_kerr_exact_ss_kernel : (const void *)march_kerr_exact_kernel;
+    return nullptr;
 }

@@ -68,6 +68,7 @@ float fast_sqrt(float s) {
 //
 //   arithmetic     request                                              kernel (object)
 //   any            a spin is set (bhr_set_spin), whole block            march_kerr_kernel / march_kerr_ss_kernel (kerr)
+//   any            ... and the exact redshift (bhr_set_redshift)         march_kerr_exact_kernel / march_kerr_exact_ss_kernel (kerr)
 //   any            hybrid part with n <= 0, not the fix list            none
 //   strict         hybrid fix list (part->repair == 2)                  march_fix_kernel<diff> (strict_ilp)
 //   fast / strict  Disk V2 volume source                                march_tile_kernel<false, 2> (own object)
@@ -102,7 +103,8 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
     const auto own = math == BHR_MATH_FAST ? bhr_march_kernel_fast : bhr_march_kernel_strict;
     // the spinning hole: one arithmetic, one schedule, no lists (what has no Kerr form was refused before anything was launched)
     if (ctx->kerr_on) {
-        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = bhr_march_kernel_kerr(BHR_MK_TILE, diff, ss);
+        if (!part && !persistent && !a.row_steps && !a.dv2)
+            k.fn = bhr_march_kernel_kerr(ctx->kerr_redshift == BHR_REDSHIFT_EXACT ? BHR_MK_KERR_EXACT : BHR_MK_TILE, diff, ss);
         return k;
     }
     if (part && part->n <= 0 && part->repair != 2) return k;
@@ -170,9 +172,10 @@ int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss) {
 }
 
 // registers / LDS of the kernel that marches a whole texture frame: the fast object's under fast arithmetic, the ILP
-// object's under strict and hybrid (bhr_create reports them); math -1: the Kerr object's (bhr_set_spin)
+// object's under strict and hybrid (bhr_create reports them); math -1: the Kerr object's (bhr_set_spin), -2: its
+// exact-redshift kernel's (bhr_set_redshift)
 int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds) {
-    const void *f = math < 0                 ? bhr_march_kernel_kerr(BHR_MK_TILE, 0, 0)
+    const void *f = math < 0                 ? bhr_march_kernel_kerr(math == -2 ? BHR_MK_KERR_EXACT : BHR_MK_TILE, 0, 0)
                     : math == BHR_MATH_FAST ? bhr_march_kernel_fast(BHR_MK_TILE, diff, 0)
                                             : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff, 0);
     hipFuncAttributes at;
@@ -295,12 +298,27 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
     if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_render: no disk texture set (bhr_set_disk_texture)");
 
-    BhrKerrMarchArgs a;                 // the march's block, and behind it what the Kerr object's kernels alone read
+    BhrKerrExactMarchArgs a;            // the march's block, and behind it what the Kerr object's kernels alone read
     march_args(ctx, call, part, call.ss, fast, a);
     {   // the spinning hole: a = A M with M = r_s / 2 and the horizon's radius, in binary64, each rounded once
         const double A = ctx->kerr_on ? (double)ctx->kerr_spin : 0.0;
         a.kerr_a = (float)(0.5 * A);
         a.kerr_rplus = (float)(0.5 * (1.0 + sqrt(1.0 - A * A)));
+        // ... and, for the exact-redshift kernels alone, the ISCO of the disk's sense of rotation (prograde for A >= 0) with the
+        // energy and angular momentum of its orbit (Bardeen, Press, Teukolsky 1972; M = 1/2, signed a, an orbit in the +phi sense)
+        a.isco_r = a.isco_e = a.isco_l = 0.0f;
+        if (ctx->kerr_on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT) {
+            const double M = 0.5, sa = 0.5 * A, q = fabs(A);
+            const double z1 = 1.0 + cbrt(1.0 - q * q) * (cbrt(1.0 + q) + cbrt(1.0 - q));
+            const double z2 = sqrt(3.0 * q * q + z1 * z1);
+            const double root = sqrt(std::max((3.0 - z1) * (3.0 + z1 + 2.0 * z2), 0.0));
+            const double r = M * (A >= 0.0 ? 3.0 + z2 - root : 3.0 + z2 + root);
+            const double sm = sqrt(M), sr = sqrt(r);
+            const double den = pow(r, 0.75) * sqrt(r * sr - 3.0 * M * sr + 2.0 * sa * sm);
+            a.isco_r = (float)r;
+            a.isco_e = (float)((r * sr - 2.0 * M * sr + sa * sm) / den);
+            a.isco_l = (float)(sm * (r * r - 2.0 * sa * sm * sr + sa * sa) / den);
+        }
     }
     const bhr_fine_frame fr = bhr_fine(ctx, call.ss);
     const int slot = call.slot;

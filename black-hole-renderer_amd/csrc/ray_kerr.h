@@ -19,7 +19,10 @@
 // this project's disk (v_hat = r_hat x n, clockwise seen from +z) for A > 0.  DESIGN.md "Kerr" has the conventions.
 //
 // No ray differentials (they would need the variational equations of this system) and one disk source, the texture at
-// level 0: Ray<false, 0> is the only instantiation.
+// level 0.  The Ray's second parameter, the disk source everywhere else, selects the disk's redshift here: Ray<false, 0> has
+// the reference's g-factor model with Kerr's orbital frequency, Ray<false, KERR_EXACT> the g-factor of the Kerr metric
+// (kerr_g_exact below; bhr_set_redshift).  The march is one and the same; the two differ in what a crossing parks and in
+// how its shade makes g.
 #pragma once
 #define BHR_RAY_STRICT 1   // the shared samplers in the reference's evaluation order (march_device.h: BHR_BILERP)
 #include "march_device.h"
@@ -29,6 +32,9 @@ namespace {
 // The kernels of this object take the march's block with the hole's numbers behind it (bhr_internal.h: BhrKerrMarchArgs) and hand
 // it to the shared schedule as the BhrMarchArgs it is; the Kerr code reads the tail through this.
 __device__ __forceinline__ const BhrKerrMarchArgs &kerr(const BhrMarchArgs &a) { return static_cast<const BhrKerrMarchArgs &>(a); }
+// ... and the exact-redshift kernels' block with the ISCO's numbers behind that (BhrKerrExactMarchArgs); theirs alone
+__device__ __forceinline__ const BhrKerrExactMarchArgs &kerr_exact(const BhrMarchArgs &a) { return static_cast<const BhrKerrExactMarchArgs &>(a); }
+constexpr int KERR_EXACT = 1;   // Ray<false, KERR_EXACT>: the exact redshift
 
 // v_rsq of x and v_rcp of y back to back (march_device.h: rsq2 / rcp2 say why)
 __device__ __forceinline__ void rsq_rcp(float x, float y, float &rs, float &rc) {
@@ -115,32 +121,91 @@ __device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, float 
                        BHR_BILERP(c00.z, c10.z, c01.z, c11.z), BHR_BILERP(c00.w, c10.w, c01.w, c11.w));
 }
 
+// The g-factor of the Kerr metric for a crossing at Boyer-Lindquist radius r of the plane, g = nu_obs / nu_em with both
+// frequencies -p.u on the traced photon (p_t = -1), capped like the model's.  ph: the photon's momentum at the hit (hx, hy, 0)
+// (Ray<false, KERR_EXACT>::step parks its x and y), of which three numbers enter: L_z = hx p_y - hy p_x, P = p.e_rho =
+// (hx p_x + hy p_y) / rho and U = 1 + l.p = 1 + (r P - a L_z / rho) / rho, with rho^2 = hx^2 + hy^2 = r^2 + a^2.
+//   observer  static at the camera: nu_obs = 1 / sqrt(1 - f), f = r / S there
+//   emitter   r >= r_isco (of the disk's sense): the circular geodesic of Kerr's Omega,
+//               nu_em = (1 - Omega L_z) / sqrt(1 - Omega^2 (r^2 + a^2) - (1 - a Omega)^2 / r)
+//             the radicand clamped at 1e-6 like the reference's other guards (inside the photon orbit of the disk's sense there
+//             is no circular orbit and the clamp would leave the gas dark; r_isco lies outside it at every spin)
+//             r < r_isco: the gas keeps the ISCO orbit's E = -u_t and L = u_phi (from the host, binary64) and falls: its
+//             covariant velocity is (-E, (L / rho) e_phi + w e_rho), rho^2 = r^2 + a^2, with w the inward root of
+//             g^{mu nu} u_mu u_nu = -1,  qa w^2 + qb w + qc = 0:
+//               c0 = E - a L / rho^2,  qa = 1 - r / rho^2,  qb = -2 c0 / rho,  qc = 1 - E^2 + L^2 / rho^2 - c0^2 / r
+//               w = (-qb - sqrt(qb^2 - 4 qa qc)) / (2 qa),  S = l^mu u_mu = c0 + r w / rho
+//               nu_em = E - L L_z / rho^2 - w P + U S / r
+//             The discriminant is 4 (u^rho)^2 and, with the ISCO's E and L, the radial potential has its triple root at
+//             r_isco: qb^2 - 4 qa qc = 4 (1 - E^2) (r_isco - r)^3 / (r rho^2), which is what is evaluated -- the literal
+//             difference vanishes at r_isco and its square root there is the square root of the rounding (3e-4 in f32).
+// tests/kerr_redshift_ref.py states the same in NumPy; tests/test_kerr_redshift_ref.py checks it against the 4 x 4 metric.
+__device__ __forceinline__ float kerr_g_exact(const BhrMarchArgs &a, float hx, float hy, float r, V3 ph) {
+    const BhrKerrExactMarchArgs &k = kerr_exact(a);
+    const float ka = k.kerr_a, a2 = ka * ka;
+    V3 c = ld3(a.cp);
+    asm volatile("" : "+v"(c.x));                // recomputed per hit, as the model's camera radius is
+    const float cw = dot(c, c) - a2;
+    const float cS = sqrtf(cw * cw + 4.0f * a2 * (c.z * c.z));
+    const float nu_obs = 1.0f / sqrtf(1.0f - sqrtf(0.5f * (cw + cS)) / cS);
+    const float rho2 = r * r + a2;
+    const float irho = 1.0f / sqrtf(hx * hx + hy * hy);
+    const float lz = hx * ph.y - hy * ph.x;
+    const float P = (hx * ph.x + hy * ph.y) * irho;
+    const float U = 1.0f + (r * P - ka * lz * irho) * irho;
+    float nu_em;
+    if (r >= k.isco_r) {
+        const float om = kerr_omega(r, ka);
+        const float q = 1.0f - ka * om;
+        nu_em = (1.0f - om * lz) / sqrtf(fmaxf(1.0f - om * om * rho2 - q * q / r, 1e-6f));
+    } else {
+        const float E = k.isco_e, L = k.isco_l;
+        const float rho = sqrtf(rho2);
+        const float c0 = E - ka * L / rho2;
+        const float qa = 1.0f - r / rho2;
+        const float qb = -2.0f * c0 / rho;
+        const float dr = fmaxf(k.isco_r - r, 0.0f);
+        const float disc = 4.0f * ((1.0f - E) * (1.0f + E)) * (dr * dr * dr) / (r * rho2);
+        const float w = (-qb - sqrtf(disc)) / (2.0f * qa);
+        const float S = c0 + r * w / rho;
+        nu_em = E - L * lz / rho2 - w * P + U * S / r;
+    }
+    return fminf(nu_obs / fmaxf(nu_em, 1e-3f), BHR_G_FACTOR_CAP);
+}
+
 // _apply_g_factor (render.py:2439-2516) for the untilted disk, unchanged but for the orbital frequency (Kerr's) and the
 // emitter's radius, which is the Boyer-Lindquist hit radius the frequency is a function of.  The exact Kerr g-factor
-// u^t (1 - Omega L_z) with frame dragging is left out.
+// u^t (1 - Omega L_z) with frame dragging is kerr_g_exact above.  RS = KERR_EXACT: to_cam is the photon's momentum at the hit instead and
+// g is kerr_g_exact's; everything downstream of g is the same code.
+template <int RS>
 __device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color, float hit_x, float hit_y, float hit_r, V3 to_cam) {
     const float rs_f = BHR_RS;
-    V3 cam_pos = ld3(a.cp);
-    asm volatile("" : "+v"(cam_pos.x));          // recomputed per hit, not kept across the march loop (march_device.h: apply_g_factor)
-    const float r_obs = sqrtf(dot(cam_pos, cam_pos));
-    const float r_em = hit_r;
-    const float r_safe = fmaxf(r_em, rs_f + 1e-3f);
-    const float omega = kerr_omega(r_safe, kerr(a).kerr_a);
-    const float lorentz = sqrtf(fmaxf(1.0f - rs_f / r_safe, 1e-6f));
-    const float beta = fminf(r_safe * omega / fmaxf(lorentz, 1e-6f), 0.99f);
-    const float gamma = 1.0f / sqrtf(fmaxf(1.0f - beta * beta, 1e-6f));
-    const float inv = 1.0f / sqrtf(hit_x * hit_x + hit_y * hit_y);
-    const float rx = inv * hit_x, ry = inv * hit_y;
-    float vx = ry, vy = -rx;                     // v_hat = r_hat x n, n = (0, 0, 1)
-    const float v_norm = sqrtf(vx * vx + vy * vy);
-    if (v_norm > 1e-6f) { vx = vx / v_norm; vy = vy / v_norm; } else { vx = 0.0f; vy = 1.0f; }
-    const float ti = 1.0f / sqrtf(dot(to_cam, to_cam));
-    const float cos_theta = vx * (ti * to_cam.x) + vy * (ti * to_cam.y);
-    const float denom = fmaxf(1.0f - beta * cos_theta, 1e-3f);
-    const float g_doppler = 1.0f / (gamma * denom);
-    const float grav_num = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_obs, rs_f + 1e-3f), 1e-6f));
-    const float grav_den = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_em, rs_f + 1e-3f), 1e-6f));
-    const float g = fminf(g_doppler * (grav_num / grav_den), BHR_G_FACTOR_CAP);
+    float g;
+    if (RS == KERR_EXACT) {
+        g = kerr_g_exact(a, hit_x, hit_y, hit_r, to_cam);
+    } else {
+        V3 cam_pos = ld3(a.cp);
+        asm volatile("" : "+v"(cam_pos.x));          // recomputed per hit, not kept across the march loop (march_device.h: apply_g_factor)
+        const float r_obs = sqrtf(dot(cam_pos, cam_pos));
+        const float r_em = hit_r;
+        const float r_safe = fmaxf(r_em, rs_f + 1e-3f);
+        const float omega = kerr_omega(r_safe, kerr(a).kerr_a);
+        const float lorentz = sqrtf(fmaxf(1.0f - rs_f / r_safe, 1e-6f));
+        const float beta = fminf(r_safe * omega / fmaxf(lorentz, 1e-6f), 0.99f);
+        const float gamma = 1.0f / sqrtf(fmaxf(1.0f - beta * beta, 1e-6f));
+        const float inv = 1.0f / sqrtf(hit_x * hit_x + hit_y * hit_y);
+        const float rx = inv * hit_x, ry = inv * hit_y;
+        float vx = ry, vy = -rx;                     // v_hat = r_hat x n, n = (0, 0, 1)
+        const float v_norm = sqrtf(vx * vx + vy * vy);
+        if (v_norm > 1e-6f) { vx = vx / v_norm; vy = vy / v_norm; } else { vx = 0.0f; vy = 1.0f; }
+        const float ti = 1.0f / sqrtf(dot(to_cam, to_cam));
+        const float cos_theta = vx * (ti * to_cam.x) + vy * (ti * to_cam.y);
+        const float denom = fmaxf(1.0f - beta * cos_theta, 1e-3f);
+        const float g_doppler = 1.0f / (gamma * denom);
+        const float grav_num = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_obs, rs_f + 1e-3f), 1e-6f));
+        const float grav_den = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_em, rs_f + 1e-3f), 1e-6f));
+        g = fminf(g_doppler * (grav_num / grav_den), BHR_G_FACTOR_CAP);
+    }
     const float intensity = fmaxf(powf(g, BHR_G_LUMINOSITY_POWER), 0.0f);
     float brightness = BHR_G_BRIGHTNESS_GAIN * intensity / (1.0f + intensity / BHR_G_FACTOR_CAP);
     const float radial_span = fmaxf(a.r_outer - a.r_inner, 1e-3f);
@@ -162,13 +227,14 @@ __device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color
 }
 
 // one disk crossing, shaded and composited front to back (render.py:2951-3002 without the mip levels)
+template <int RS>
 __device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam) {
     const float hit_r = sqrtf(hit_x * hit_x + hit_y * hit_y - kerr(a).kerr_a * kerr(a).kerr_a);
     if (!(a.r_outer >= hit_r && hit_r >= a.r_inner)) return;
     const float4 rgba = kerr_sample_disk(a, hit_x, hit_y, hit_r);
     const float base_alpha = fminf(rgba.w, 0.999f);
     const float disk_alpha = 1.0f - powf(1.0f - base_alpha, BHR_DISK_ALPHA_GAIN);
-    const V3 col = kerr_g_factor(a, mk(rgba.x, rgba.y, rgba.z), hit_x, hit_y, hit_r, to_cam);
+    const V3 col = kerr_g_factor<RS>(a, mk(rgba.x, rgba.y, rgba.z), hit_x, hit_y, hit_r, to_cam);
     const float front = 1.0f - sh.alpha_total;
     const float wgt = disk_alpha * front;
     sh.accum = mk(sh.accum.x + col.x * wgt, sh.accum.y + col.y * wgt, sh.accum.z + col.z * wgt);
@@ -177,7 +243,7 @@ __device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh,
 
 template <bool DIFF, int SRC = 0>
 struct Ray {
-    static_assert(!DIFF && SRC == 0, "the Kerr march has no ray differentials and one disk source, the texture");
+    static_assert(!DIFF && (SRC == 0 || SRC == KERR_EXACT), "the Kerr march has no ray differentials; its second parameter is the redshift, model or exact");
     V3 x, p;
     float r;       // Kerr-Schild radius of x
     float affine;
@@ -259,7 +325,14 @@ struct Ray {
                     Pending<false> hit;
                     hit.hit_x = hx;
                     hit.hit_y = hy;
-                    hit.to_cam = mk(-v1.x, -v1.y, -v1.z);                   // against dx/dl at the START of the step
+                    if (SRC == KERR_EXACT) {
+                        // the photon at the hit: its momentum interpolated like the hit point (second order in the step), in
+                        // the slot's floats of to_cam.  Its x and y are all the shade needs in the plane (kerr_g_exact makes
+                        // L_z, P and U of them: no divide or square root here, inside the march loop)
+                        hit.to_cam = mk(p.x + t_frac * (np.x - p.x), p.y + t_frac * (np.y - p.y), 0.0f);
+                    } else {
+                        hit.to_cam = mk(-v1.x, -v1.y, -v1.z);               // against dx/dl at the START of the step
+                    }
                     park_store<false>(n_pend, hit);                         // a free slot is guaranteed (march_tile_body flushes at 2)
                     n_pend += 1;
                 }
@@ -283,7 +356,7 @@ struct Ray {
     __device__ __forceinline__ void flush_one(const BhrMarchArgs &a) {
         if (n_pend > 0) {
             const Pending<false> h = park_pop<false>(n_pend);
-            kerr_shade_hit(a, sh, h.hit_x, h.hit_y, h.to_cam);
+            kerr_shade_hit<SRC>(a, sh, h.hit_x, h.hit_y, h.to_cam);
         }
     }
     // the escape direction is the direction of dx/dl at the last state

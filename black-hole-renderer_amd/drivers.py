@@ -145,7 +145,7 @@ def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, 
                   tex_h=1024, r_max=10.0, disk_texture_path=None, r_disk_inner=R_DISK_INNER_DEFAULT,
                   r_disk_outer=R_DISK_OUTER_DEFAULT, disk_tilt=0.0, lens_flare=False, anti_alias="disabled",
                   aa_strength=1.0, disk_rotation_speed=0.1, device_index=0, rows=None, frame_slots=None, math=None,
-                  supersample=1, supersample_threshold=None, spin=0.0):
+                  supersample=1, supersample_threshold=None, spin=0.0, redshift="model"):
     """Renderer with a placeholder (or file) disk texture, as the reference's entry points build it
     (render.py:4044-4064, 4627-4644).  Returns (renderer, use_lifecycle, n_r, n_phi)."""
     # procedural sky: the host draws its random tables, the device rasterises them (nebula resize, star blobs in
@@ -169,7 +169,8 @@ def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, 
                            lens_flare=lens_flare, anti_alias=anti_alias, aa_strength=aa_strength,
                            disk_rotation_speed=disk_rotation_speed, device_index=device_index, rows=rows,
                            frame_slots=frame_slots, supersample=supersample, supersample_threshold=supersample_threshold,
-                           **({} if math is None else {"math": math}), **({"spin": spin} if spin != 0 else {}))
+                           **({} if math is None else {"math": math}), **({"spin": spin} if spin != 0 else {}),
+                           **({"redshift": redshift} if redshift != "model" else {}))
     if procedural_sky:
         renderer.build_procedural_skybox(seed=42, n_stars=n_stars)
     return renderer, use_lifecycle, n_r, n_phi
@@ -185,7 +186,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  gpus: int = 1, disk_model: str = "texture", math: Optional[str] = None,
                  supersample: int = 1, supersample_threshold: Optional[float] = None, bit_depth: int = 8,
                  dither: str = "none", grade: Optional[dict] = None, hdr_path: Optional[str] = None,
-                 passes_path: Optional[str] = None, spin: float = 0.0) -> np.ndarray:
+                 passes_path: Optional[str] = None, spin: float = 0.0, redshift: str = "model") -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -197,7 +198,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     ``passes_path``: also builds the view's ray map and writes its geometry passes and the frame's bg / disk / blur layers
     there as a compressed .npz (output.write_passes); the image itself is rendered as without it (one device, one ray per
     pixel, the texture disk source).  ``spin``: a / M of a spinning hole (HipRenderer.set_spin; one device, the texture source,
-    no tilt, no anti-aliasing, no passes)."""
+    no tilt, no anti-aliasing, no passes).  ``redshift``: "model" or "exact", the disk's g-factor of the Kerr metric
+    (HipRenderer.set_redshift; the Kerr march at any spin, with a spin's restrictions)."""
     check_depth_and_dither(bit_depth, dither)
     check_passes(passes_path, gpus, supersample, disk_model)
     grade = check_grade(grade)
@@ -210,7 +212,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         raise ValueError("a grade renders on one GPU: row-block tiles store their rows from inside the V pass")
     if gpus > 1 and supersample != 1:
         raise ValueError("supersample > 1 renders on one GPU: row-block tiles march one ray per pixel")
-    if spin != 0 and (gpus > 1 or passes_path is not None or disk_model != "texture"):
+    if (spin != 0 or redshift != "model") and (gpus > 1 or passes_path is not None or disk_model != "texture"):
         raise ValueError("a spin renders on one GPU with the texture disk source and writes no passes: row-block tiles, ray maps "
                          "and Disk V2 are Schwarzschild's")
     if gpus > 1:
@@ -224,7 +226,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     renderer, use_lifecycle, n_r, n_phi = make_renderer(
         width, height, cam_pos, fov, step_size, skybox_path, n_stars, tex_w, tex_h, r_max, disk_texture_path,
         r_disk_inner, r_disk_outer, disk_tilt, lens_flare, anti_alias, aa_strength, disk_rotation_speed, math=math,
-        supersample=supersample, supersample_threshold=supersample_threshold, spin=spin)
+        supersample=supersample, supersample_threshold=supersample_threshold, spin=spin,
+        **({"redshift": redshift} if redshift != "model" else {}))
     if use_analytic_disk(renderer, disk_model):
         pass
     elif use_lifecycle:

@@ -6,6 +6,13 @@ import math
 
 M = 0.5
 SPIN_MAX = 0.998
+REDSHIFTS = ("model", "exact")
+
+
+def check_redshift(mode) -> str:
+    if mode not in REDSHIFTS:
+        raise ValueError(f"redshift must be 'model' or 'exact', got {mode!r}")
+    return mode
 
 
 def check_spin(a_over_m) -> float:
@@ -44,3 +51,11 @@ def kerr_info(a_over_m: float) -> dict:
 def disk_isco(a_over_m: float) -> float:
     """The ISCO of the disk's own sense of rotation: prograde for A >= 0, retrograde for a disk that turns against the hole."""
     return r_isco(a_over_m, a_over_m >= 0)
+
+
+def disk_isco_orbit(a_over_m: float) -> tuple:
+    """(r_isco, E, L) of the disk's sense: the radius and the energy -u_t and angular momentum u_phi of its circular orbit,
+    which the gas inside it keeps under the exact redshift (the library computes the same in binary64 for its kernels)."""
+    r, a, sm = disk_isco(a_over_m), a_over_m * M, math.sqrt(M)
+    den = r ** 0.75 * math.sqrt(r ** 1.5 - 3.0 * M * math.sqrt(r) + 2.0 * a * sm)
+    return r, (r ** 1.5 - 2.0 * M * math.sqrt(r) + a * sm) / den, sm * (r * r - 2.0 * a * sm * math.sqrt(r) + a * a) / den

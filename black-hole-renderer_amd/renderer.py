@@ -92,7 +92,8 @@ class HipRenderer:
                  disk_rotation_speed=0.1, ignore_taichi_cache=False,
                  device_index: int = 0, rows: Optional[Sequence[int]] = None, math: str = "strict",
                  frame_slots: Optional[int] = None, outputs: Optional[str] = None, options: Optional[dict] = None,
-                 supersample: int = 1, supersample_threshold: Optional[float] = None, spin: float = 0.0):
+                 supersample: int = 1, supersample_threshold: Optional[float] = None, spin: float = 0.0,
+                 redshift: str = "model"):
         # supersample=k: k x k rays per pixel, box-filtered inside the march (bhr_set_supersample; include/bhr.h states the filter)
         # supersample_threshold=T: adaptive -- k x k rays only for the pixels whose k = 1 neighbours differ by more than T
         # (bhr_set_adaptive_supersample); None: every pixel
@@ -163,10 +164,15 @@ class HipRenderer:
                 raise
 
         # spin=A: a spinning (Kerr) hole, A = a / M (set_spin)
+        # redshift="exact": the disk's g-factor of the Kerr metric instead of the reference's model (set_redshift)
         self._spin, self._force_kerr = 0.0, False
-        if spin != 0.0:
+        self._redshift, self._redshift_forced = "model", False
+        if spin != 0.0 or redshift != "model":
             try:
-                self.set_spin(spin)
+                if spin != 0.0:
+                    self.set_spin(spin)
+                if redshift != "model":
+                    self.set_redshift(redshift)
             except Exception:
                 self.close()
                 raise
@@ -637,10 +643,34 @@ class HipRenderer:
         a = kerr.check_spin(a)
         _lib.check(self._lib.bhr_set_spin(self._ctx, a, 1 if force_kerr else 0))
         self._spin, self._force_kerr = a, bool(force_kerr)
+        self._redshift_forced = False
 
     @property
     def spin(self) -> float:
         return self._spin
+
+    def set_redshift(self, mode: str) -> None:
+        """The redshift of the disk for the frames rendered from now on (bhr_set_redshift; include/bhr.h states both): "model",
+        the reference's g-factor model with Kerr's orbital frequency, or "exact", the g-factor of the Kerr metric -- frame
+        dragging, the photon's own angular momentum, and gas that plunges inside the ISCO.  "exact" is a Kerr kernel's: at
+        spin 0 it turns the forced Kerr march on itself (and "model" turns that off again), so a Schwarzschild hole gets the
+        exact redshift too, and what a spin refuses (set_spin) is refused."""
+        from . import kerr
+        mode = kerr.check_redshift(mode)
+        if mode == "exact":
+            if self._spin == 0.0 and not self._force_kerr:
+                self.set_spin(0.0, force_kerr=True)
+                self._redshift_forced = True
+            _lib.check(self._lib.bhr_set_redshift(self._ctx, _lib.REDSHIFT_EXACT))
+        else:
+            _lib.check(self._lib.bhr_set_redshift(self._ctx, _lib.REDSHIFT_MODEL))
+            if self._redshift_forced:
+                self.set_spin(0.0)
+        self._redshift = mode
+
+    @property
+    def redshift(self) -> str:
+        return self._redshift
 
     def kerr_info(self) -> dict:
         """Radii of the hole of the current spin, in r_s: a, r_plus, r_isco_prograde, r_isco_retrograde, r_photon_pro,
@@ -648,10 +678,15 @@ class HipRenderer:
         from . import kerr
         return kerr.kerr_info(self._spin)
 
-    def kerr_resources(self, supersampled: bool = False) -> dict:
-        """Registers per lane, LDS and scratch bytes of the Kerr march kernel (bhr_kerr_resources)."""
+    def kerr_resources(self, supersampled: bool = False, redshift: str = "model") -> dict:
+        """Registers per lane, LDS and scratch bytes of the Kerr march kernel of a redshift mode (bhr_kerr_resources,
+        bhr_kerr_redshift_resources)."""
+        from . import kerr
         out = (C.c_int32 * 3)()
-        _lib.check(self._lib.bhr_kerr_resources(1 if supersampled else 0, out))
+        if kerr.check_redshift(redshift) == "model":
+            _lib.check(self._lib.bhr_kerr_resources(1 if supersampled else 0, out))
+        else:
+            _lib.check(self._lib.bhr_kerr_redshift_resources(_lib.REDSHIFT_EXACT, 1 if supersampled else 0, out))
         return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
 
     def adaptive_info(self) -> dict:

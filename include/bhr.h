@@ -473,6 +473,24 @@ BHR_API int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr);
  * (supersampled != 0: of its supersampled twin), from hipFuncGetAttributes.  After a frame marched with a spin set,
  * bhr_counters.march_vgprs / march_lds_bytes are that kernel's too. */
 BHR_API int32_t bhr_kerr_resources(int32_t supersampled, int32_t out[3]);
+/* The redshift of the disk around a spinning hole.  BHR_REDSHIFT_MODEL (the default) is the reference's g-factor model with
+ * Kerr's orbital frequency, as above.  BHR_REDSHIFT_EXACT is the g-factor of the Kerr metric, g = nu_obs / nu_em with both
+ * frequencies -p.u on the traced photon: a static observer at the camera; gas on the circular geodesic of Kerr's Omega at
+ * r >= r_isco of the disk's sense of rotation (frame dragging included, the Doppler term from the photon's own L_z); and
+ * inside the ISCO gas that keeps the ISCO orbit's energy and angular momentum and falls inward, down to the horizon.  (Inside
+ * the photon orbit of the disk's sense no circular orbit exists; the guard of the circular branch would make the gas dark
+ * there, but that branch is taken at r >= r_isco only, which lies outside the photon orbit at every spin.)  The photon's momentum at a crossing is interpolated like the hit
+ * point (second order in the step).  Everything behind g -- intensity, radial profile, Wien tint, the sampler and its roll -- is
+ * the model's (DESIGN.md "Kerr"; tests/kerr_redshift_ref.py is the CPU reference).  The march is the same: BG, the step count
+ * and the crossings do not change, two kernels of the Kerr object of their own shade the disk.
+ * EXACT needs the Kerr march: BHR_ERR_INVALID naming the combination without a spin or force_kerr (bhr_set_spin), for an
+ * unknown mode, and from a bhr_set_spin that would switch the Kerr march off while EXACT is set.  A context that never calls
+ * this launches what it always launched.  Ordered behind the frames in flight. */
+#define BHR_REDSHIFT_MODEL 0
+#define BHR_REDSHIFT_EXACT 1
+BHR_API int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode);
+/* bhr_kerr_resources for the kernels of a redshift mode (BHR_REDSHIFT_MODEL: the same numbers). */
+BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, int32_t out[3]);
 /* The library's switches.  Each has an environment variable that bhr_create reads ONCE (no entry point calls getenv
  * afterwards) and can be changed per context later with this call -- what tests and A/B tools use:
  *   "bloom_split"     BHR_BLOOM_SPLIT     -1 post-pass by arithmetic (exact f32 under strict, split f16 under fast / hybrid), 0 / 1 force
