@@ -186,6 +186,10 @@ def parse_args(argv=None) -> argparse.Namespace:
             p.error(f"{who} does not combine with --shutter: shutter frames march Schwarzschild rays")
         if args.gpus != 1:
             p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march Schwarzschild rays")
+        from .kerr import camera_f, camera_outside_static_limit
+        if not camera_outside_static_limit(args.pov, args.spin):
+            p.error(f"{who} needs --pov outside the static limit of the hole: at {args.pov} f = r / S = {camera_f(args.pov, args.spin)[0]:.4g} "
+                    f"(f < 1 is needed: r > 1 in the disk plane), no static observer and no photon along every pixel direction there")
     if args.map_supersample > 1 and not (args.ray_map or args.orbit_map or args.shutter_map):
         p.error("--map_supersample needs --ray_map, --orbit_map or --shutter_map: it is a ray map's factor (marched frames take --supersample)")
     if args.shutter_map:

@@ -1016,9 +1016,12 @@ static int32_t calibrate_slot_streams(bhr_ctx *ctx, const bhr_camera *cam, uint3
     return rc;
 }
 
+static int32_t kerr_camera_check(const bhr_ctx *ctx, const bhr_camera *cam, const char *who);   // with the other Kerr checks, below
+
 int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_render: null argument");
     BHR_TRY(bhr_kerr_check(ctx, flags, "bhr_render"));
+    BHR_TRY(kerr_camera_check(ctx, cam, "bhr_render"));
     if ((ctx->ss > 1 || ctx->ada_k > 1) && (flags & (BHR_PERSISTENT | BHR_ROW_COSTS)))
         return bhr_fail(BHR_ERR_INVALID, "bhr_render: BHR_PERSISTENT and BHR_ROW_COSTS are not available with supersampling (factor %d)", ctx->ss > 1 ? ctx->ss : ctx->ada_k);
     BHR_HIP(hipSetDevice(ctx->cfg.device));
@@ -1271,6 +1274,24 @@ int32_t bhr_kerr_check(const bhr_ctx *ctx, uint32_t flags, const char *who) {
     return kerr_state_check(ctx, flags, who, (double)ctx->kerr_spin);
 }
 }  // extern "C++"
+
+// The camera of a Kerr frame stands outside the static limit f = r / S = 1 (and so outside the horizon): the photon that
+// leaves it along a pixel direction d has p = s d + f Lam l with s = 1 / sqrt(1 - f (1 - (l.d)^2)) and Lam = (1 + s l.d) / (1 - f)
+// (ray_kerr.h: Ray::init), real for every d only where f < 1, and the exact redshift's observer is static.  Evaluated in
+// binary64 on the Kerr-Schild radius of the position; refused before anything is launched.
+static int32_t kerr_camera_check(const bhr_ctx *ctx, const bhr_camera *cam, const char *who) {
+    if (!ctx || !ctx->kerr_on) return BHR_OK;
+    const double A = (double)ctx->kerr_spin, a2 = 0.25 * A * A;
+    const double x = cam->pos[0], y = cam->pos[1], z = cam->pos[2];
+    const double w = (x * x + y * y + z * z) - a2;
+    const double S = sqrt(w * w + 4.0 * a2 * z * z);
+    const double r = sqrt(0.5 * (w + S)), r_plus = 0.5 * (1.0 + sqrt(1.0 - A * A));
+    const double f = S > 0.0 ? r / S : INFINITY;
+    if (!(f < 1.0 && r >= r_plus))
+        return bhr_fail(BHR_ERR_INVALID, "%s: the camera at (%g, %g, %g) lies inside the static limit of the hole of spin %g (f = r / S = %g with the Kerr-Schild radius r = %g; "
+                        "f < 1 is needed, and r >= r_plus = %g): no photon leaves it along every pixel direction", who, x, y, z, A, f, r, r_plus);
+    return BHR_OK;
+}
 
 int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr) {
     if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: null ctx");

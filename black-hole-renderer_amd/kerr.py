@@ -42,6 +42,23 @@ def r_photon(a_over_m: float, prograde: bool) -> float:
     return 2.0 * M * (1.0 + math.cos(2.0 / 3.0 * math.acos(-A if prograde else A)))
 
 
+def camera_f(cam_pos, a_over_m: float) -> tuple:
+    """(f, r) at a camera position: f = r / S of the Kerr-Schild form and the Kerr-Schild radius r.  f = 1 is the static limit."""
+    x, y, z = (float(v) for v in cam_pos)
+    a2 = (a_over_m * M) ** 2
+    w = (x * x + y * y + z * z) - a2
+    S = math.sqrt(w * w + 4.0 * a2 * z * z)
+    r = math.sqrt(0.5 * (w + S))
+    return (r / S if S > 0 else math.inf), r
+
+
+def camera_outside_static_limit(cam_pos, a_over_m: float) -> bool:
+    """The domain of the Kerr march's camera (include/bhr.h: bhr_set_spin): f < 1 and outside the horizon.  An orbit about the
+    spin axis keeps both numbers, so a video's first camera decides for all its frames."""
+    f, r = camera_f(cam_pos, a_over_m)
+    return f < 1.0 and r >= r_plus(a_over_m)
+
+
 def kerr_info(a_over_m: float) -> dict:
     A = check_spin(a_over_m)
     return dict(a=A * M, r_plus=r_plus(A), r_isco_prograde=r_isco(A, True), r_isco_retrograde=r_isco(A, False),

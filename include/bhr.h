@@ -467,7 +467,13 @@ BHR_API int32_t bhr_adaptive_info(bhr_ctx *ctx, int64_t out[3]);
  * BHR_ERR_INVALID, each with a message that names the combination: |A| > 0.998 or NaN; with a spin set (A != 0 or forced), by
  * this call or by the call that meets it -- a tilted disk, anti_alias = 1, a Disk V2 source, adaptive supersampling, a
  * row-block context (bhr_group_render*, bhr_tile_export, bhr_tile_render), bhr_render with BHR_PERSISTENT or BHR_ROW_COSTS,
- * bhr_render_shutter, bhr_raymap_build and the three bhr_raymap_render* calls. */
+ * bhr_render_shutter, bhr_raymap_build and the three bhr_raymap_render* calls.
+ * The camera of a frame marched with a spin set stands outside the static limit: with w = pos.pos - a^2,
+ * S = sqrt(w^2 + 4 a^2 z^2) and the Kerr-Schild radius r = sqrt((w + S) / 2) of bhr_camera.pos, f = r / S < 1 (in the plane that is
+ * r > r_s = 1 at every spin; on the axis the limit meets the horizon), and r >= r_plus.  Inside it no static observer exists and
+ * the photon along a pixel direction d, p = s d + f Lam l with s = 1 / sqrt(1 - f (1 - (l.d)^2)), is not real for every d.
+ * bhr_render evaluates f in binary64 and returns BHR_ERR_INVALID naming the static limit before anything is launched; the
+ * context is untouched and renders the next camera as ever. */
 BHR_API int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr);
 /* out = {VGPRs per lane, LDS bytes per block, scratch (private segment) bytes per lane} of the Kerr march kernel
  * (supersampled != 0: of its supersampled twin), from hipFuncGetAttributes.  After a frame marched with a spin set,

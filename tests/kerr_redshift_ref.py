@@ -212,6 +212,7 @@ def render(cam, A, sky, tex, h_base=0.1, r_inner=2.0, r_outer=15.0, t_offset=0.0
     """kerr_ref.render's frame dict under the exact redshift, and first_g (H, W): the g-factor of a ray's first crossing
     (NaN without one)."""
     t = np.dtype(dtype).type
+    K.check_camera(cam["pos"], A)
     W, H = cam["width"], cam["height"]
     d = K.pixel_rays(cam, dtype).reshape(-1, 3)
     m = march(cam["pos"].astype(dtype), d, A, h_base, cam["r_escape"], r_inner, r_outer, dtype)

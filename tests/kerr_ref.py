@@ -149,6 +149,26 @@ def initial_momentum(x, d, a):
     return s[..., None] * d + (f * lam)[..., None] * l
 
 
+def camera_f(cam_pos, A):
+    """(f, r) of a camera position in binary64: f = r / S and the Kerr-Schild radius r."""
+    x = np.asarray(cam_pos).astype(np.float64)
+    a2 = (float(A) * M) ** 2
+    w = float((x * x).sum()) - a2
+    S = float(np.sqrt(w * w + 4.0 * a2 * float(x[2]) ** 2))
+    r = float(np.sqrt(0.5 * (w + S)))
+    return (r / S if S > 0 else np.inf), r
+
+
+def check_camera(cam_pos, A):
+    """The domain of the camera (include/bhr.h: bhr_set_spin): outside the static limit f = 1, where initial_momentum's
+    s = 1 / sqrt(1 - f (1 - c^2)) is real for every direction and a static observer exists, and outside the horizon.  The
+    library refuses a render from anywhere else before it launches, and so does this reference."""
+    f, r = camera_f(cam_pos, A)
+    if not (f < 1.0 and r >= r_plus(float(A))):
+        raise ValueError(f"camera at {tuple(float(v) for v in cam_pos)} lies inside the static limit of the hole of spin {A:g} "
+                         f"(f = r / S = {f:g} >= 1 or r = {r:g} inside the horizon at {r_plus(float(A)):g})")
+
+
 def dt_fac(r):
     """The reference's step factor (render.py:2865-2868) on the Kerr-Schild radius: r_cap = r_s = 1, max_fac 10."""
     t = r.dtype.type
@@ -389,8 +409,10 @@ def g_factor(base, hx, hy, hit_r, to_cam, a, cam_pos, r_inner, r_outer):
 
 def render(cam, A, sky, tex, h_base=0.1, r_inner=2.0, r_outer=15.0, t_offset=0.0, dtype=np.float64):
     """One frame of the camera `cam` (build_camera): dict with bg, disk, final = clip(bg + disk) as (H, W, 3) in `dtype`,
-    fate, n_hits, steps as (H, W), esc_dir and first_hit (H, W, 3 / 2; NaN without one)."""
+    fate, n_hits, steps as (H, W), esc_dir and first_hit (H, W, 3 / 2; NaN without one).  ValueError for a camera inside the
+    static limit (check_camera), as the library's."""
     t = np.dtype(dtype).type
+    check_camera(cam["pos"], A)
     W, H = cam["width"], cam["height"]
     d = pixel_rays(cam, dtype).reshape(-1, 3)
     x0 = cam["pos"].astype(dtype)

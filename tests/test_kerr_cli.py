@@ -64,3 +64,14 @@ def test_isco_note():
     info = kerr.kerr_info(0.9)
     assert info["r_isco_prograde"] < 3.0 < info["r_isco_retrograde"] and info["r_photon_pro"] < 1.5 < info["r_photon_retro"]
     assert info["a"] == pytest.approx(0.45)
+
+
+@pytest.mark.parametrize("line", [["--spin", "0.998", "--pov", "1.08", "0", "0.05"], ["--spin", "0.998", "--pov", "0.7", "0", "0.02"],
+                                  ["--redshift", "exact", "--pov", "0.9", "0", "0.1"], ["--spin", "0.5", "--video", "--orbit", "--pov", "0.95", "0", "0"]])
+def test_a_camera_inside_the_static_limit_is_an_argparse_error(line, capsys):
+    with pytest.raises(SystemExit) as e:
+        cli.parse_args(line)
+    assert e.value.code == 2 and "static limit" in capsys.readouterr().err
+    cli.parse_args([a for a in line if a not in ("--spin", "0.998", "0.5", "--redshift", "exact")])   # without the Kerr march it parses
+    assert cli.parse_args(["--spin", "0.998", "--pov", "1.3", "0.2", "0.1"]).pov == [1.3, 0.2, 0.1]
+
