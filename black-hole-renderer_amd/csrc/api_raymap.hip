@@ -1,5 +1,5 @@
 // api_raymap.hip -- the ray map's entry points (include/bhr.h): build, read, info, free, and the refusals of
-// bhr_raymap_render, bhr_raymap_render_view and bhr_raymap_render_shutter (the frames themselves are launched from api.hip, next to bhr_render: they take
+// bhr_raymap_render, bhr_raymap_render_view and bhr_raymap_render_shutter (the frames themselves are launched from render.hip, next to bhr_render: they take
 // a frame slot like any other).
 // The kernels are march_raymap.hip's, their launchers march_launch.hip's.
 #include <math.h>
@@ -187,10 +187,10 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (ctx->rows != ctx->cfg.height)
         return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
     BHR_TRY(check_context(ctx, "bhr_raymap_build", BHR_ERR_INVALID));
-    const int32_t K = ctx->raymap_slots;
+    const int32_t K = ctx->opt.raymap_slots;
     if (K < 1 || K > 8) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: raymap_slots %d (1 .. 8)", K);
     // the map's own factor: the map of the fine frame, k rows x k W (the context's own supersampling stays off, check_context)
-    const int32_t ss = ctx->raymap_ss;
+    const int32_t ss = ctx->opt.raymap_ss;
     if (ss != 1 && ss != 2 && ss != 4 && ss != 8) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: raymap_supersample %d (1, 2, 4 or 8)", ss);
     if ((int64_t)ss * ss * ctx->cfg.width * ctx->cfg.height >= ((int64_t)1 << 31))
         return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: %d x %d rays of a %dx%d frame exceed 2^31", ss, ss, ctx->cfg.width, ctx->cfg.height);

@@ -246,7 +246,7 @@ struct bhr_options {
     int32_t hybrid_band_set;
     double hybrid_pad;          // share of its own span of b a small tile is padded by in the strict-band test (BHR_HYBRID_PAD, default 0.5; hybrid.hip: tile_pad)
     int32_t hybrid_streams;     // BHR_HYBRID_STREAMS: 1 both lists of a hybrid march on one stream, 2 on two, -1 (default) 1 where two frame slots overlap frames, else 2
-    int32_t calibrate_streams;  // BHR_CALIBRATE_STREAMS: 1 (default) a two-slot context picks slot 1's stream by timing candidates (api.hip)
+    int32_t calibrate_streams;  // BHR_CALIBRATE_STREAMS: 1 (default) a two-slot context picks slot 1's stream by timing candidates (calibrate.hip)
     int32_t hybrid_classify;    // BHR_HYBRID_CLASSIFY: 1 (default) the tiles are classified and the launch order partitioned on the device, 0 on the host
     int32_t mip_lds;            // BHR_MIP_LDS=1: anti-aliased fast frames stage the coarse mip levels in LDS
     int32_t group_threads;      // BHR_GROUP_THREADS: -1 by device layout (default), 0 / 1 one submitting thread / one per tile
@@ -255,6 +255,8 @@ struct bhr_options {
     int32_t grade_timing;       // BHR_GRADE_TIMING: 1 a graded frame brackets each launch of its grade stage with HIP events (bhr_debug_read, which = 6); default 0
     int32_t raymap_shutter_fused;   // BHR_RAYMAP_SHUTTER_FUSED: 1 (default) a shutter frame from a map without overflow pixels is one launch, 0 sample by sample (A/B runs, tests)
     int32_t shutter_timing;     // BHR_SHUTTER_TIMING: 1 a shutter frame brackets each accumulation launch with HIP events (bhr_debug_read, which = 5); default 0
+    int32_t raymap_slots;       // BHR_RAYMAP_SLOTS / option "raymap_slots": crossings a map keeps per pixel (1..8, default 4), read by bhr_raymap_build, which refuses anything else
+    int32_t raymap_ss;          // BHR_RAYMAP_SUPERSAMPLE / option "raymap_supersample": the next map's own factor (1, 2, 4, 8; default 1), read by bhr_raymap_build likewise
 };
 
 // The context's ray map (api_raymap.hip): what the strict march of one whole-frame view finds before it shades anything.
@@ -330,6 +332,18 @@ struct bhr_frame_slot {
     int32_t in_flight;      // rendered since the last join
 };
 
+// What bhr_get_counters and bhr_get_row_costs* report about "the last frame": the last frame call that launched everything it
+// meant to.  Written whole, in two kinds of place: frame_on_next_slot (render.hip) once a frame's body has returned BHR_OK, and
+// the group / tile renders (group.hip: record_tile_frame).  No launcher writes it; a frame that fails leaves the one before.
+struct bhr_last_frame {
+    int32_t valid;         // a frame has been launched since bhr_create
+    int32_t ring;          // its timing-ring slot (events, counter cell: bhr_steps_cell); -1: the context's scalar ones (group / tile renders)
+    int32_t march_timed;   // its march-end event was recorded (a group render without BHR_GROUP_TIME_MARCH: not)
+    uint32_t flags;
+    uint64_t rays;         // launched by the frame's marches: the fine frame's pixels times its shutter samples (an adaptive frame's refinement is added when read)
+    int32_t adaptive;      // an adaptively supersampled frame: its refinement's counts are in slot ada_info_slot
+};
+
 struct bhr_ctx {
     bhr_config cfg;
     int32_t rows;
@@ -338,7 +352,7 @@ struct bhr_ctx {
     bhr_frame_slot slots[BHR_MAX_FRAME_SLOTS];   // the per-frame state; the context keeps no copy of it
     int32_t n_slots, next_slot;
     int32_t active_slot;                // the slot the launchers work on (bhr_slot): always a valid, allocated one (bhr_activate_slot)
-    int32_t two_slot_frames, streams_calibrated, calibrating;   // calibrate_slot_streams (api.hip)
+    int32_t two_slot_frames, streams_calibrated, calibrating;   // bhr_calibrate_slot_streams (calibrate.hip)
     int32_t calib_choice, calib_fps[8];
     hipStream_t calib_idle[8];
     int32_t n_calib_idle;
@@ -350,8 +364,6 @@ struct bhr_ctx {
     unsigned long long *d_steps_ring;   // one ray-step counter cell (BHR_STEP_CELL words) per ring slot
     unsigned long long *d_steps_fold;   // folded cells (BHR_TIMING_RING words)
     int64_t ring_head;                  // frames recorded since reset
-    unsigned long long *last_steps_ptr; // counter the last march accumulated into
-    int32_t last_slot;                  // ring slot of the last completed bhr_render, -1 after a group render
 
     // scene
     float *d_skybox;
@@ -418,9 +430,12 @@ struct bhr_ctx {
     // ada_threshold are marched again with ada_k x ada_k rays (march_launch.hip: bhr_launch_adaptive).  ada_k = 0: off.
     int32_t ada_k;
     float ada_threshold;
-    int32_t ada_last_slot;     // frame slot of the last adaptive frame (-1: none since the setting changed), and
-    int32_t ada_last_math;     // the arithmetic bhr_resolve_math gave it
-    int32_t ada_frame;         // the last bhr_render was an adaptive frame (bhr_get_counters adds the refinement's rays)
+    // bhr_adaptive_info's subject, beside the last-frame record because it outlives it: written with the record of an adaptive
+    // frame, kept across frames of other kinds, reset only by a change of the sampling (settings.hip: set_sampling).  (Today
+    // every frame of a context with ada_k > 1 is adaptive and the other kinds are refused there, so "kept across" cannot be
+    // observed: the two fields behave like fields of the record that set_sampling clears.)
+    int32_t ada_info_slot;     // frame slot of the last adaptive frame (-1: none since the setting changed), and
+    int32_t ada_info_math;     // the arithmetic bhr_resolve_math gave it
     void *hybrid;              // hybrid.hip: tile classification cache
     void *pipe;                // group.hip: streams, events and band lists of the pipelined row-block path
     uint8_t *d_gather_u8;      // (H, W, 3) u8: quantised frame gathered from the tiles (BHR_GATHER_U8), on tile 0
@@ -436,14 +451,10 @@ struct bhr_ctx {
     size_t h_pinned_bytes;
 
     bhr_counters counters;
-    int32_t last_flags;
-    int32_t timing_valid;
-    int32_t march_end_recorded;
+    bhr_last_frame last;       // the last frame launched whole; counters.rays / ray_steps / *_ms are filled from it when read
 
     // the ray map (api_raymap.hip), behind everything the frames of bhr_render touch
     bhr_raymap *raymap;        // null until the first bhr_raymap_build
-    int32_t raymap_slots;      // option "raymap_slots" / BHR_RAYMAP_SLOTS: crossings a map keeps per pixel (1..8, default 4), read by bhr_raymap_build
-    int32_t raymap_ss;         // option "raymap_supersample" / BHR_RAYMAP_SUPERSAMPLE: the next map's own factor (1, 2, 4, 8; default 1), read by bhr_raymap_build
 
     // bhr_set_spin: kerr_on = the march is the Kerr object's (a spin other than 0, or force_kerr); kerr_spin = A = a / M
     int32_t kerr_on;
@@ -475,6 +486,8 @@ inline int32_t bhr_log2(int32_t k) { return k == 8 ? 3 : k == 4 ? 2 : k == 2 ? 1
 // The march events of a call: timed launches (bhr_render) use their ring slot's, the others the context's scalar ones.
 inline hipEvent_t bhr_march_start_event(const bhr_ctx *ctx, int32_t slot) { return slot >= 0 ? ctx->ring_ev[slot * 3 + 0] : ctx->ev[0]; }
 inline hipEvent_t bhr_march_end_event(const bhr_ctx *ctx, int32_t slot) { return slot >= 0 ? ctx->ring_ev[slot * 3 + 1] : ctx->ev[1]; }
+// ... and the ray-step counter cell they count into: the ring slot's, or the context's scalar one
+inline unsigned long long *bhr_steps_cell(const bhr_ctx *ctx, int32_t slot) { return slot >= 0 ? ctx->d_steps_ring + (size_t)slot * BHR_STEP_CELL : ctx->d_ray_steps; }
 // anti_alias "disabled": the reference still integrates the differentials (skip_diff = 0 on
 // the CLI path) but never reads them (render.py:2957-2959) => skipping them is pixel-identical.
 inline bool bhr_want_diff(const bhr_ctx *ctx, uint32_t flags) { return ctx->cfg.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS); }
@@ -487,7 +500,9 @@ struct bhr_mirror {
     int32_t pbr, gr;
 };
 
-// error plumbing (api.hip)
+// ================ internal functions, by the source that defines them ================================================================
+
+// ---- context.hip: error plumbing, the context's synchronisation and copies --------------------------------------------------------
 int32_t bhr_fail(int32_t code, const char *fmt, ...);
 #define BHR_HIP(call)                                                                       \
     do {                                                                                    \
@@ -503,6 +518,28 @@ int32_t bhr_fail(int32_t code, const char *fmt, ...);
         if (rc__ != BHR_OK) return rc__; \
     } while (0)
 
+// `count` elements of device memory at *p (null for none, and on failure: BHR_ERR_NOMEM)
+template <typename T>
+int32_t bhr_dev_alloc(T **p, size_t count) {
+    *p = nullptr;
+    if (count == 0) return BHR_OK;
+    hipError_t e = hipMalloc((void **)p, count * sizeof(T));
+    if (e != hipSuccess) {
+        *p = nullptr;
+        return bhr_fail(BHR_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
+    }
+    return BHR_OK;
+}
+int32_t bhr_ensure_pinned(bhr_ctx *ctx, size_t bytes);                     // the pinned staging buffer holds at least `bytes`
+// caller memory <-> device memory on ctx->stream, which both synchronise (the download through the pinned staging buffer)
+int32_t bhr_download(bhr_ctx *ctx, void *dst, const void *d_src, size_t bytes);
+int32_t bhr_upload(bhr_ctx *ctx, void *d_dst, const void *src, size_t bytes);
+int32_t bhr_poll_sync(bhr_ctx *ctx, hipStream_t stream);                   // waits for `stream`, polling an event for the first 200 ms
+
+// ---- frame_slot.hip: the frame slots, their streams and post-pass -----------------------------------------------------------------
+int32_t bhr_alloc_slot(bhr_ctx *ctx, int k);                               // slot k's stream, event and layers, once
+void bhr_free_slot(bhr_ctx *ctx, int k);
+int32_t bhr_activate_slot(bhr_ctx *ctx, int32_t k);                        // points the launchers at frame slot k (allocating it)
 // Every API entry point except bhr_render: selects the device and orders the scene stream behind the frames in
 // flight, so that scene writes, read-backs and stand-alone passes see (and never race with) a finished frame.
 int32_t bhr_enter(bhr_ctx *ctx);
@@ -518,31 +555,76 @@ int32_t bhr_enter_components(bhr_ctx *ctx);
 int32_t bhr_enter_scene_write(bhr_ctx *ctx);
 int32_t bhr_enter_frame(bhr_ctx *ctx);
 int32_t bhr_leave_frame(bhr_ctx *ctx);
+// fork: the aux stream waits for everything ctx->stream has been given so far; join: ctx->stream waits for the aux stream
+int32_t bhr_aux_fork(bhr_ctx *ctx);
+int32_t bhr_aux_join(bhr_ctx *ctx);
+// decides the frame's arithmetic / post-pass kernels (exact: the exact f32 ones whatever the arithmetic) and makes sure their
+// buffers exist (before the march is launched)
+int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags, bool exact = false);
+// the whole-block V pass of a frame into the context's own buffers, recording what it stored
+int32_t bhr_frame_post(bhr_ctx *ctx, int32_t with_bloom, uint32_t want, unsigned long long *zero_cell);
+// the lens flare of the active slot's frame from device-resident sums: glow -> sums -> apply (hdr: as bhr_launch_flare_apply)
+int32_t bhr_frame_flare(bhr_ctx *ctx, bool hdr);
+// makes the BHR_OUT_* layers in `need` of the active slot's last frame exist (re-runs its V pass for what is missing)
+int32_t bhr_ensure_outputs(bhr_ctx *ctx, uint32_t need);
 
-// launchers (each lives next to its kernels)
-int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags);                          // march_launch.hip: BHR_MATH_* of a frame
-int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part = nullptr);   // march_launch.hip: every march launch
-int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds); // march_launch.hip: registers / LDS of the frame kernel
+// ---- scene.hip ------------------------------------------------------------------------------------------------------------------------
+void bhr_free_scene(bhr_ctx *ctx);                                         // the mip stack
+void bhr_free_bg(bhr_ctx *ctx);                                            // the background layer's planes
+
+// ---- calibrate.hip ----------------------------------------------------------------------------------------------------------------------
+int32_t bhr_streams_share_queue(hipStream_t a, hipStream_t b, int32_t *share);   // probe (two one-lane kernels, <= 4 ms)
+// picks slot 1's stream by timing candidates on frames of (cam, flags) through bhr_render; once per two-slot context
+int32_t bhr_calibrate_slot_streams(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
+
+// ---- settings.hip: the refusals of a context with a spin set (kerr_on); BHR_OK without one ------------------------------------------
+// BHR_ERR_INVALID naming the combination -- the context's own state (tilt, anti-aliasing, Disk V2, adaptive supersampling) and
+// `flags` of the call; `who`: the entry point
+int32_t bhr_kerr_check(const bhr_ctx *ctx, uint32_t flags, const char *who);
+// a call that has no Kerr form at all (ray maps, shutter frames, group and tile renders): BHR_ERR_INVALID with a spin set
+int32_t bhr_kerr_refuse(const bhr_ctx *ctx, const char *who, const char *what);
+// a camera inside the static limit: BHR_ERR_INVALID, before anything is launched
+int32_t bhr_kerr_camera_check(const bhr_ctx *ctx, const bhr_camera *cam, const char *who);
+
+// ---- counters.hip -------------------------------------------------------------------------------------------------------------------
+float bhr_ev_ms(hipEvent_t a, hipEvent_t b);                               // milliseconds between two recorded events, -1 where there are none
+// sum of the lanes of each of `n` counter cells -> host_out[n], on ctx->stream (synchronises)
+int32_t bhr_fold_cells(bhr_ctx *ctx, const unsigned long long *cells, int n, unsigned long long *host_out);
+
+// ---- march_launch.hip and the march objects (each table lives next to its kernels) ----------------------------------------------------
+int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags);                          // BHR_MATH_* of a frame
+int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part = nullptr);   // every march launch
+int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds); // registers / LDS of the frame kernel
+int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss);                               // builds d_/h_tile_order of the frame marched with factor ss
+// detect + refinement (ctx->ada_k) of an adaptively supersampled frame, behind its base march `call` on the same stream; records the march-end event
+int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call);
+// the ray map's launches on ctx->stream.  build: marches `cam` and fills the map (counting its steps into a cell of the map's
+// own); shade: the map's pixels under the scene as it is and cam's t_offset into the active slot's
+// layers -- the pixels on the overflow list are left to the fix kernel (bhr_launch_march with a repair == 2 part over that list)
+// ss: the map's factor -- the build marches the fine frame bhr_fine(ctx, ss) of `cam`
+int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss);
+// rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
+int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f);
+// all samples of a shutter frame from the map in one launch (raymap_shade_shutter_kernel): the mean of the n frames the launch
+// above would store for (smp[j].t, smp[j].c, smp[j].s), into the active slot's BG / DISK; no packed bloom operands.  Opens the
+// frame's march bracket; the caller closes it.  turned: some sample has a turn other than (1, 0).
+int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrShutterArgs &smp, bool turned);
 const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);       // march.hip -> march.o (ss: the supersampled twin)
 const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.hip -> march_strict.o
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.hip -> march_strict_ilp.o
 const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_raymap.hip -> march_raymap.o
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
-// api.hip: what a context with a spin set (kerr_on) refuses, as BHR_ERR_INVALID naming the combination -- the context's own
-// state (tilt, anti-aliasing, Disk V2, adaptive supersampling) and `flags` of the call; `who`: the entry point.  BHR_OK without a spin.
-int32_t bhr_kerr_check(const bhr_ctx *ctx, uint32_t flags, const char *who);
-// api.hip: a call that has no Kerr form at all (ray maps, shutter frames, group and tile renders): BHR_ERR_INVALID with a spin set
-int32_t bhr_kerr_refuse(const bhr_ctx *ctx, const char *who, const char *what);
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
-int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss);                               // march_launch.hip: builds d_/h_tile_order of the frame marched with factor ss
-int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_march_call &call);             // hybrid.hip
-// march_launch.hip: detect + refinement (ctx->ada_k) of an adaptively supersampled frame, behind its base march `call` on the same stream; records the march-end event
-int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call);
-// hybrid.hip: strict flag per 8x8 tile of the frame k times finer than the context's (the rule a bhr_set_supersample(k) hybrid
+
+// ---- hybrid.hip -------------------------------------------------------------------------------------------------------------------------
+int32_t bhr_launch_march_hybrid(bhr_ctx *ctx, const bhr_march_call &call);
+// strict flag per 8x8 tile of the frame k times finer than the context's (the rule a bhr_set_supersample(k) hybrid
 // frame classifies its tiles by), in a buffer of the active frame slot, made on ctx->stream and cached on the view key
 int32_t bhr_hybrid_fine_flags(bhr_ctx *ctx, const bhr_camera *cam, int32_t k, const uint8_t **d_flags, int32_t *tiles_x);
 void bhr_hybrid_free(bhr_ctx *ctx);
-int32_t bhr_hybrid_active_list(bhr_ctx *ctx, const int32_t **list, int32_t *n);   // hybrid.o: the active slot's partitioned launch order (tests)
+int32_t bhr_hybrid_active_list(bhr_ctx *ctx, const int32_t **list, int32_t *n);   // the active slot's partitioned launch order (tests)
+
+// ---- bloom.hip ------------------------------------------------------------------------------------------------------------------------
 int32_t bhr_bloom_prepare(bhr_ctx *ctx);
 int32_t bhr_split_nt(int32_t R);
 void bhr_split_geometry(const bhr_ctx *ctx, bhr_split_geom *g);
@@ -555,69 +637,61 @@ int32_t bhr_launch_bloom_h(bhr_ctx *ctx, const bhr_mirror *mirrors, int32_t n_mi
 int32_t bhr_launch_bloom_v_rows(bhr_ctx *ctx, int32_t with_bloom, int32_t r0, int32_t r1, uint32_t want, uint8_t *gather_u8, float *gather_f32,
                                 unsigned long long *zero_cell);
 int32_t bhr_bloom_v_tile_rows(bhr_ctx *ctx);                               // output rows per V-pass block
-int32_t bhr_activate_slot(bhr_ctx *ctx, int32_t k);                        // api.hip: points the launchers at frame slot k (allocating it)
-// api.hip: decides the frame's arithmetic / post-pass kernels (exact: the exact f32 ones whatever the arithmetic) and makes
-// sure their buffers exist (before the march is launched)
-int32_t bhr_frame_begin(bhr_ctx *ctx, uint32_t flags, bool exact = false);
-// api.hip: the whole-block V pass of a frame into the context's own buffers, recording what it stored
-int32_t bhr_frame_post(bhr_ctx *ctx, int32_t with_bloom, uint32_t want, unsigned long long *zero_cell);
-// api.hip: makes the BHR_OUT_* layers in `need` of the active slot's last frame exist (re-runs its V pass for what is missing)
-int32_t bhr_ensure_outputs(bhr_ctx *ctx, uint32_t need);
-void bhr_pipe_free(bhr_ctx *ctx);                                          // group.hip
-int32_t bhr_ensure_pinned(bhr_ctx *ctx, size_t bytes);                     // api.hip
-// fork: the aux stream waits for everything ctx->stream has been given so far; join: ctx->stream waits for the aux stream
-int32_t bhr_streams_share_queue(hipStream_t a, hipStream_t b, int32_t *share);   // api.o: probe (two one-lane kernels, <= 4 ms)
-int32_t bhr_aux_fork(bhr_ctx *ctx);
-int32_t bhr_aux_join(bhr_ctx *ctx);
-int32_t bhr_launch_flare_glow(bhr_ctx *ctx, bool whole_frame);       // flare.hip
+
+// ---- group.hip --------------------------------------------------------------------------------------------------------------------------
+void bhr_pipe_free(bhr_ctx *ctx);
+
+// ---- flare.hip ------------------------------------------------------------------------------------------------------------------------
+int32_t bhr_launch_flare_glow(bhr_ctx *ctx, bool whole_frame);
 int32_t bhr_launch_flare_sums(bhr_ctx *ctx);
 // sums == nullptr: device-resident totals; hdr: onto the slot's HDR plane without the upper clip (a graded frame) instead of FINAL
 int32_t bhr_launch_flare_apply(bhr_ctx *ctx, const double *sums, bool hdr = false);
-int32_t bhr_launch_quantize(bhr_ctx *ctx);                           // api.hip: the frame's u8 rows, on the stream (from the V pass, or FINAL -> u8)
-// png_device.hip: (rows, W, 3) u8 at d_rgb -> PNG file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
+
+// ---- png_device.hip, jpeg_device.hip ------------------------------------------------------------------------------------------------------
+// (rows, W, 3) u8 at d_rgb -> PNG file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
 int32_t bhr_launch_png_encode(bhr_ctx *ctx, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
 // the same for the (rows, W, 3) u16 rows at d_rgb16 (native endian): a 16-bit PNG, samples big-endian in the file
 int32_t bhr_launch_png16_encode(bhr_ctx *ctx, const uint16_t *d_rgb16, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
 void bhr_png_dev_free(bhr_ctx *ctx);
-// quantize.hip: the two quantisers that read the f32 FINAL frame, on ctx->stream (bhr_ensure_outputs calls them)
+// (rows, W, 3) u8 at d_rgb -> JFIF file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
+int32_t bhr_launch_jpeg_encode(bhr_ctx *ctx, int32_t quality, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
+void bhr_jpeg_dev_free(bhr_ctx *ctx);
+
+// ---- quantize.hip: the two quantisers that read the f32 FINAL frame, on ctx->stream (bhr_ensure_outputs calls them) ------------------
 int32_t bhr_launch_quantize_u16(bhr_ctx *ctx);      // d_final -> d_final_u16 (allocated here on first use)
 int32_t bhr_launch_quantize_dither(bhr_ctx *ctx);   // d_final -> d_final_u8, blue-noise dithered
-// grade.hip, on ctx->stream: FINAL of the active slot under the context's grade, from its BG / DISK / BLUR layers or (from_hdr)
+
+// ---- grade.hip, on ctx->stream ------------------------------------------------------------------------------------------------------------
+// FINAL of the active slot under the context's grade, from its BG / DISK / BLUR layers or (from_hdr)
 // from its HDR plane, which is then clamped in place; store_hdr: also the plane h; store_u8: also the undithered u8 rows
 int32_t bhr_launch_grade(bhr_ctx *ctx, bool from_hdr, bool store_hdr, bool store_u8);
 int32_t bhr_launch_grade_sum(bhr_ctx *ctx);         // (d_bg + d_disk) + d_blur -> d_hdr (allocated here on first use)
-// hdr_stream.hip, on ctx->stream: the active slot's HDR plane -> planar u16 Y | Cb | Cr (3 W rows bytes) at d_out under
+void bhr_grade_free(bhr_ctx *ctx);                  // the timing events
+
+// ---- hdr_stream.hip, on ctx->stream ---------------------------------------------------------------------------------------------------
+// the active slot's HDR plane -> planar u16 Y | Cb | Cr (3 W rows bytes) at d_out under
 // `transfer` (BHR_HDR_PQ / _HLG), and the frame's light levels into d_levels = {u32 bits of the largest f32 nits, u32 0, f64 sum
 // of nits}, 16 bytes on an 8-byte boundary that the launch clears first (HLG leaves them 0).  scale: white_nits / 10000 (PQ)
 int32_t bhr_launch_hdr_yuv420p10(bhr_ctx *ctx, int32_t transfer, float gain, float scale, float white_nits, uint16_t *d_out, void *d_levels);
-// jpeg_device.hip: (rows, W, 3) u8 at d_rgb -> JFIF file bytes at d_out on ctx->stream; d_meta (4 words) = {length, error, ..}
-int32_t bhr_launch_jpeg_encode(bhr_ctx *ctx, int32_t quality, const uint8_t *d_rgb, uint8_t *d_out, int64_t cap, uint32_t *d_meta);
-void bhr_jpeg_dev_free(bhr_ctx *ctx);
-// shutter.hip: sample j of the n > 1 samples of a shutter frame has been marched into the active slot's d_bg / d_disk; on
+
+// ---- shutter.hip ----------------------------------------------------------------------------------------------------------------------
+// sample j of the n > 1 samples of a shutter frame has been marched into the active slot's d_bg / d_disk; on
 // ctx->stream: j = 0 starts the slot's running sums with it, 0 < j < n - 1 adds it, j = n - 1 adds it and stores the mean
 // (sum * (1.0f / n)) back into d_bg / d_disk.  The sums are allocated here on first use.
 int32_t bhr_launch_shutter_accumulate(bhr_ctx *ctx, int32_t j, int32_t n);
 void bhr_shutter_free(bhr_ctx *ctx);                                 // the timing events
-// march_launch.hip: the ray map's two launches on ctx->stream.  build: marches `cam` and fills the map (counting its steps
-// into the context's scalar cell); shade: the map's pixels under the scene as it is and cam's t_offset into the active slot's
-// layers -- the pixels on the overflow list are left to the fix kernel (bhr_launch_march with a repair == 2 part over that list)
-// ss: the map's factor -- the build marches the fine frame bhr_fine(ctx, ss) of `cam`
-int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss);
-// rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
-int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f);
-// all samples of a shutter frame from the map in one launch (raymap_shade_shutter_kernel): the mean of the n frames the launch
-// above would store for (smp[j].t, smp[j].c, smp[j].s), into the active slot's BG / DISK; no packed bloom operands.  Opens the
-// frame's march bracket; the caller closes it.  turned: some sample has a turn other than (1, 0).
-int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrShutterArgs &smp, bool turned);
-// api_raymap.hip: the refusals of bhr_raymap_render (nothing launched); the map's flags for the march launcher; release
+
+// ---- api_raymap.hip -------------------------------------------------------------------------------------------------------------------
+// the refusals of bhr_raymap_render (nothing launched)
 int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
 // ... and of bhr_raymap_render_view, which also gives the cosine and sine of cam's turn from the build camera (binary64, rounded once)
 int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, float *rot_c, float *rot_s);
 // ... and of bhr_raymap_render_shutter, which fills smp (t, c, s per sample, n, 1 / n) and tells whether any sample is turned
 int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned);
 void bhr_raymap_release(bhr_ctx *ctx);
-void bhr_grade_free(bhr_ctx *ctx);                                   // grade.hip: the timing events
-void bhr_population_free(bhr_ctx *ctx);                              // lifecycle.hip
+
+// ---- lifecycle.hip, texture.hip, disk_v2.hip ------------------------------------------------------------------------------------------
+void bhr_population_free(bhr_ctx *ctx);
 int32_t bhr_launch_build_mips(bhr_ctx *ctx);
 int32_t bhr_launch_background(bhr_ctx *ctx, float t);
 int32_t bhr_launch_compose(bhr_ctx *ctx, float t_offset, int32_t enable_rt, float color_temp);

@@ -10,7 +10,7 @@
 //   linear    FINAL = y
 //   srgb      FINAL = y <= 0.0031308f ? 12.92f * y : 1.055f * powf(y, 1.0f / 2.4f) - 0.055f
 // The kernel stores FINAL, the plane h where the frame keeps it, and -- where the frame's consumers want undithered u8 rows --
-// those rows as well, by api.hip's quantize_u8_kernel's expression of FINAL.  tests/grade_ref.py restates all of it in NumPy.
+// those rows as well, by frame_slot.hip's quantize_u8_kernel's expression of FINAL.  tests/grade_ref.py restates all of it in NumPy.
 // Streaming, like shutter.hip: every lane moves 16 bytes per f32 access (4 bytes of u8 rows), consecutive lanes consecutive
 // float4s, grid-stride over at most 2048 blocks, the count's remainder mod 4 by scalar accesses; no LDS, no scratch.
 #include <algorithm>
@@ -44,7 +44,7 @@ __device__ __forceinline__ float grade_value(float x, float gain, float iw2, flo
     return y;
 }
 
-// quantize_u8_kernel's expression (api.hip), bit for bit
+// quantize_u8_kernel's expression (frame_slot.hip), bit for bit
 __device__ __forceinline__ uint32_t grade_q8(float f) { return (uint32_t)(uint8_t)(int)(fminf(fmaxf(f, 0.0f), 1.0f) * 255.0f); }
 
 __device__ __forceinline__ float grade_sum(float bg, float disk, float blur) {

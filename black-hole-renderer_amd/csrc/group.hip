@@ -265,6 +265,11 @@ int32_t finish(bhr_ctx **ctxs, int n, const int32_t *live, float *out_host) {
 bhr_march_call tile_march(bhr_ctx *c, const bhr_camera *cam, uint32_t flags) {
     return {cam, flags, c->stream, /* slot */ -1, /* time_untimed */ (flags & BHR_GROUP_TIME_MARCH) != 0, /* defer_end */ false, c->ss};
 }
+// ... and the last-frame record of the tile once everything of its frame is launched: what tile_march's call counts and times
+void record_tile_frame(bhr_ctx *c, uint32_t flags) {
+    const bhr_fine_frame fr = bhr_fine(c, c->ss);
+    c->last = {1, /* ring */ -1, /* march_timed */ (flags & BHR_GROUP_TIME_MARCH) != 0, flags, (uint64_t)fr.width * fr.rows, /* adaptive */ 0};
+}
 
 // the planes of the other tiles that hold rows of tile k: its H pass writes them there itself (mirrors: BHR_MAX_MIRRORS entries)
 int32_t set_mirrors(bhr_ctx **ctxs, int n, int k, bhr_mirror *mirrors, int32_t *n_mirrors) {
@@ -309,7 +314,6 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
         bhr_ctx *c = ctxs[k];
         BHR_TRY(bhr_enter(c));
         BHR_TRY(bhr_activate_slot(c, 0));
-        c->last_slot = -1;
         BHR_TRY(ensure_pipe(c));
         BHR_TRY(bhr_frame_begin(c, flags, !all_peer));
     }
@@ -402,8 +406,7 @@ int32_t render_tiles(bhr_ctx **ctxs, int n, const bhr_camera *cam, uint32_t flag
                     BHR_TRY(bhr_launch_bloom_v_rows(c, with_bloom, chunks[ci].r0, chunks[ci].r1, want, direct ? head->d_gather_u8 : nullptr,
                                                     direct ? head->d_gather : nullptr, nullptr));
             bhr_slot(c).have = direct ? 0u : want;           // what sits in the tile's OWN buffers
-            c->last_flags = (int32_t)flags;
-            c->timing_valid = 1;
+            record_tile_frame(c, flags);
         }
     if (flare) BHR_TRY(flare_pass(ctxs, n, live));
     if (gather)
@@ -666,7 +669,6 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
     volatile uint64_t *mine = p->shm + (size_t)rank * BHR_TILE_SHM_WORDS;
     BHR_TRY(bhr_enter(ctx));
     BHR_TRY(bhr_activate_slot(ctx, 0));
-    ctx->last_slot = -1;
     BHR_TRY(bhr_frame_begin(ctx, flags));
     if (with_bloom && bhr_slot(ctx).frame_split != p->split)
         return bhr_fail(BHR_ERR_INVALID, "bhr_tile_render: the flags select the other post-pass arithmetic than the one the tiles were connected for");
@@ -713,8 +715,7 @@ int32_t tile_render_linked(bhr_ctx *ctx, TilePipe *p, const bhr_camera *cam, uin
         if (chunks[ci].needs_halo) BHR_TRY(v_chunk(ci));
     BHR_HIP(hipEventRecord(ctx->ev[2], ctx->stream));
     bhr_slot(ctx).have = direct ? 0u : want;
-    ctx->last_flags = (int32_t)flags;
-    ctx->timing_valid = 1;
+    record_tile_frame(ctx, flags);
     BHR_HIP(hipStreamSynchronize(ctx->stream));
     // end of frame: my rows have landed and nobody reads my halo rows any more once every rank has said `done`
     __atomic_store_n(mine + 1, frame, __ATOMIC_RELEASE);

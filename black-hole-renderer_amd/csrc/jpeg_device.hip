@@ -531,7 +531,7 @@ int32_t bhr_jpeg_encode_device(bhr_ctx *ctx, int32_t quality, uint8_t *out, int6
         BHR_TRY(dev_alloc(&d->d_out, (size_t)bound));
         d->out_cap = bound;
     }
-    BHR_TRY(bhr_launch_quantize(ctx));
+    BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_U8));
     BHR_TRY(bhr_launch_jpeg_encode(ctx, quality, bhr_slot(ctx).d_final_u8, d->d_out, bound, d->d_meta));
     uint32_t meta[4] = {0, 0, 0, 0};
     BHR_HIP(hipMemcpyAsync(meta, d->d_meta, sizeof(meta), hipMemcpyDeviceToHost, ctx->stream));

@@ -155,7 +155,7 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
 
 // The arithmetic of a march: the context's math_mode unless the call forces one.  Hybrid is launches over complementary tile
 // lists (hybrid.hip); the schedules and disk sources that have no list form run strict.  bhr_frame_begin picks the frame's
-// post-pass kernels from the same decision (api.hip).
+// post-pass kernels from the same decision (frame_slot.hip).
 int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags) {
     int32_t mode = ctx->cfg.math_mode;
     if (flags & BHR_FORCE_FAST) mode = BHR_MATH_FAST;
@@ -187,7 +187,8 @@ int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t 
 
 // The kernel argument block of a march of the frame bhr_fine(ctx, ss) under the fast or the strict arithmetic: everything but
 // the launch's own list, row-cost and diagnostic pointers.  ss: the call's factor for the base march, ada_k for the refinement.
-static void march_args(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part, int32_t ss, bool fast, BhrMarchArgs &a) {
+// Reads the context and the active frame slot, writes neither (layers_stored notes what a launch that stores layers changes).
+static void march_args(const bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part, int32_t ss, bool fast, BhrMarchArgs &a) {
     const bhr_config &c = ctx->cfg;
     const bhr_camera *cam = call.cam;
     for (int k = 0; k < 3; ++k) {
@@ -244,10 +245,9 @@ static void march_args(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march
     a.sc.n_phi = ctx->n_phi;
     a.sc.mip_last = 0;
     for (int l = 1; l < BHR_NUM_MIP_LEVELS && ctx->mip_h[l] > 0 && ctx->mip_w[l] > 0; ++l) a.sc.mip_last = l;
-    bhr_frame_slot &f = bhr_slot(ctx);
+    const bhr_frame_slot &f = bhr_slot(ctx);
     a.bg = f.d_bg;
     a.disk = f.d_disk;
-    f.disk_wide = 0;          // the march's disk layer lies in [0, 1]
     a.diskp = nullptr;
     a.dp_yb = a.dp_gp = a.dp_g0 = 0;
     a.sum = nullptr;
@@ -259,10 +259,9 @@ static void march_args(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march
         a.dp_gp = g.GP;
         a.dp_g0 = g.g0;
         a.sum = f.d_sum;
-        f.sum_valid = 1;
     }
     // timed launches (bhr_render) count into their ring slot; group launches into the scalar
-    a.ray_steps = call.slot >= 0 ? ctx->d_steps_ring + (size_t)call.slot * BHR_STEP_CELL : ctx->d_ray_steps;
+    a.ray_steps = bhr_steps_cell(ctx, call.slot);
     a.queue = f.d_queue;
     a.dv2 = ctx->disk_source != BHR_DISK_TEXTURE ? ctx->d_dv2_params : nullptr;
     a.vol_absorption = ctx->vol_opts[0];
@@ -285,6 +284,14 @@ static void march_args(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march
     a.tile_order = nullptr;
 }
 
+// What a launch that stores the active slot's BG / DISK layers under the block `a` leaves in the slot: the march, with the list
+// refinement behind it, the map shade and the fused shutter shade (the map build stores no layer).
+static void layers_stored(bhr_ctx *ctx, const BhrMarchArgs &a) {
+    bhr_frame_slot &f = bhr_slot(ctx);
+    f.disk_wide = 0;                  // a marched disk layer lies in [0, 1]
+    if (a.sum) f.sum_valid = 1;       // the split-f16 post-pass's bg + disk plane comes with the layers
+}
+
 int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part) {
     const uint32_t flags = call.flags;
     const hipStream_t stream = call.stream;
@@ -300,6 +307,7 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
 
     BhrKerrExactMarchArgs a;            // the march's block, and behind it what the Kerr object's kernels alone read
     march_args(ctx, call, part, call.ss, fast, a);
+    layers_stored(ctx, a);
     {   // the spinning hole: a = A M with M = r_s / 2 and the horizon's radius, in binary64, each rounded once
         const double A = ctx->kerr_on ? (double)ctx->kerr_spin : 0.0;
         a.kerr_a = (float)(0.5 * A);
@@ -320,7 +328,6 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
             a.isco_l = (float)(sm * (r * r - 2.0 * sa * sm * sr + sa * sa) / den);
         }
     }
-    const bhr_fine_frame fr = bhr_fine(ctx, call.ss);
     const int slot = call.slot;
     const bool first_part = !part || part->first, last_part = !part || part->last;
     if (flags & BHR_ROW_COSTS) {
@@ -370,7 +377,6 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     // the H pass of a tile whose whole tail is ~0.12 ms
     const bool timed = slot >= 0 || call.time_untimed;
     if (last_part && !call.defer_end && timed) BHR_HIP(hipEventRecord(bhr_march_end_event(ctx, slot), stream));
-    if (last_part) ctx->march_end_recorded = timed;
     if (d_stamps) {
         std::vector<unsigned long long> h((size_t)a.n_tiles * 4);
         BHR_HIP(hipMemcpyAsync(h.data(), d_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
@@ -378,8 +384,6 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
         (void)hipFree(d_stamps);
         if (FILE *f = fopen(stamp_path, "wb")) { fwrite(h.data(), sizeof(unsigned long long), h.size(), f); fclose(f); }
     }
-    ctx->last_steps_ptr = a.ray_steps;
-    ctx->counters.rays = (uint64_t)fr.width * fr.rows;
     return BHR_OK;
 }
 
@@ -453,8 +457,6 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
         BHR_TRY(refine(math == BHR_MATH_FAST, 0));
     }
     if (call.slot >= 0 || call.time_untimed) BHR_HIP(hipEventRecord(bhr_march_end_event(ctx, call.slot), stream));
-    ctx->ada_last_slot = ctx->active_slot;
-    ctx->ada_last_math = math;
     return BHR_OK;
 }
 
@@ -465,13 +467,8 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
 int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss) {
     const hipStream_t stream = ctx->stream;
     const bhr_march_call call = {cam, flags | BHR_FORCE_STRICT, stream, /* slot */ -1, false, false, ss, false};
-    // the build marches but stores no layer: what march_args notes in the active frame slot for a march stays as it was
-    bhr_frame_slot &f = bhr_slot(ctx);
-    const int32_t disk_wide = f.disk_wide, sum_valid = f.sum_valid;
     BhrMarchArgs a;
     march_args(ctx, call, nullptr, ss, false, a);
-    f.disk_wide = disk_wide;
-    f.sum_valid = sum_valid;
     if ((int64_t)a.width * a.rows != m.plane) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: the map has %lld pixels, the frame %lld", (long long)m.plane, (long long)a.width * a.rows);
     if (ss == 1) {
         BHR_TRY(ensure_tile_order(ctx, 1, a.tiles_x, a.n_tiles));
@@ -498,6 +495,7 @@ static int32_t raymap_shade_args(bhr_ctx *ctx, const bhr_march_call &call, const
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "%s: no skybox set (bhr_set_skybox)", api);
     if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "%s: no disk texture set (bhr_set_disk_texture)", api);
     march_args(ctx, call, nullptr, ss, false, a);
+    layers_stored(ctx, a);
     if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5)) return bhr_fail(BHR_ERR_STATE, "%s: the map does not fit the frame", api);
     return BHR_OK;
 }
@@ -541,8 +539,5 @@ int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call
     void *args[] = {&a, &mm, &ss};
     (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
     BHR_HIP(hipGetLastError());
-    // no march launch follows: the frame's counter cell (cleared ahead of time, nothing counts into it) and its rays
-    ctx->last_steps_ptr = a.ray_steps;
-    ctx->counters.rays = (uint64_t)a.width * a.rows;
     return BHR_OK;
 }

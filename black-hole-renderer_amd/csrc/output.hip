@@ -729,7 +729,7 @@ int32_t bhr_sink_submit(bhr_sink *s, const char *path) {
     hipError_t e = hipSuccess;
     int32_t rc = bhr_enter_frame(ctx);      // quantise, encode and copy ride the stream that rendered the frame
     const bool deep = s->bit_depth == 16;
-    if (rc == BHR_OK) rc = deep ? bhr_ensure_outputs(ctx, BHR_OUT_U16) : bhr_launch_quantize(ctx);
+    if (rc == BHR_OK) rc = bhr_ensure_outputs(ctx, deep ? BHR_OUT_U16 : BHR_OUT_U8);
     if (rc == BHR_OK && s->on_device) {
         bhr_sink::Slot &sl = s->slots[slot];
         rc = deep ? bhr_launch_png16_encode(ctx, bhr_slot(ctx).d_final_u16, sl.dev, (int64_t)s->host_bytes, sl.d_meta) :

@@ -823,7 +823,7 @@ static int32_t encode_device(bhr_ctx *ctx, int deep, uint8_t *out, int64_t cap, 
         BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_U16));
         BHR_TRY(bhr_launch_png16_encode(ctx, bhr_slot(ctx).d_final_u16, d->d_out, bound, d->d_meta));
     } else {
-        BHR_TRY(bhr_launch_quantize(ctx));
+        BHR_TRY(bhr_ensure_outputs(ctx, BHR_OUT_U8));
         BHR_TRY(bhr_launch_png_encode(ctx, bhr_slot(ctx).d_final_u8, d->d_out, bound, d->d_meta));
     }
     uint32_t meta[4] = {0, 0, 0, 0};

@@ -1,5 +1,5 @@
 // quantize.hip -- the two quantisers of the f32 FINAL frame that are kernels of their own (include/bhr.h: bhr_read_final_u16,
-// bhr_set_dither), beside save_image's truncation, which the V pass fuses into its store (bloom.hip) and api.hip's
+// bhr_set_dither), beside save_image's truncation, which the V pass fuses into its store (bloom.hip) and frame_slot.hip's
 // quantize_u8_kernel repeats for a flared frame.  Both are reached through bhr_ensure_outputs.
 //
 //   16 bit:   q16 = (uint16)(int)(clip(x, 0, 1) * 65535.0f)              the same truncation, 65536 levels

@@ -1,4 +1,4 @@
-// shutter.hip -- the accumulation of a shutter frame (bhr_render_shutter, api.hip).
+// shutter.hip -- the accumulation of a shutter frame (bhr_render_shutter, render.hip).
 //
 // A shutter frame is the mean of n marches: every sample is marched into the frame slot's own d_bg / d_disk by the march
 // kernels as they are, and one launch of the kernel below follows each march on the slot's stream:

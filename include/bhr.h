@@ -507,7 +507,7 @@ BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, 
  *   "hybrid_streams"  BHR_HYBRID_STREAMS  -1 (default) the two lists of a hybrid march on one stream where two frame slots overlap
  *                                         frames and on two where a frame runs alone; 1 / 2 force
  *   "calibrate_streams" BHR_CALIBRATE_STREAMS 1 (default) a context with two frame slots times six candidate streams for slot 1 on
- *                                         its ninth frame and keeps the fastest (~0.15 s once; csrc/api.hip: calibrate_slot_streams)
+ *                                         its ninth frame and keeps the fastest (~0.15 s once; csrc/calibrate.hip)
  *   "hybrid_classify" BHR_HYBRID_CLASSIFY 1 (default) a view change classifies the tiles and partitions the launch order on the
  *                                         device (~0.05 ms whatever the size), 0 on the submitting thread (the same lists)
  *   "mip_lds"         BHR_MIP_LDS         1 anti-aliased fast frames stage the coarse mip levels in LDS

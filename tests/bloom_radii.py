@@ -1,4 +1,4 @@
-"""The radius classes of the split-f16 post-pass (csrc/bloom.hip): R = int(0.02 W) (render.py:3914, api.hip), weight
+"""The radius classes of the split-f16 post-pass (csrc/bloom.hip): R = int(0.02 W) (render.py:3914, context.hip), weight
 table count NT = (R + 15) // 16 + 1 (bhr_split_nt), split kernels up to NT = 12, i.e. W <= 8849 (split_ok).  The frame
 shapes tests/test_gpu_bloom_radii.py runs and the synthetic layers it blurs."""
 import numpy as np

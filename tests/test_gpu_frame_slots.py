@@ -1,4 +1,4 @@
-"""Two frames in flight per context (bhr_frame_slot, csrc/api.hip): successive bhr_render calls alternate between
+"""Two frames in flight per context (bhr_frame_slot, csrc/frame_slot.hip and render.hip): successive bhr_render calls alternate between
 two slots / streams that share the scene.  Overlap must never change a pixel: every frame of a two-slot context is
 bit-identical to the same frame from a one-slot context, with scene updates, read-backs and stand-alone passes in
 between; the per-frame counters stay exact."""
@@ -138,7 +138,7 @@ def test_march_busy_time_is_the_union_of_the_march_intervals(slots, hip_lib):
 
 def test_slot_stream_calibration_is_invisible_in_the_frames(hip_lib):
     """A two-slot context times six candidate streams for slot 1 once eight two-slot frames have been asked for
-    (csrc/api.hip: calibrate_slot_streams) -- ~500 extra renders of the ninth frame's view.  Nothing of it may show:
+    (csrc/calibrate.hip: bhr_calibrate_slot_streams) -- ~500 extra renders of the ninth frame's view.  Nothing of it may show:
     every frame before, at and after the calibration equals the one-slot context's, the ray-step and frame counters count
     the caller's frames only, the report names the stream kept; option calibrate_streams 0 never calibrates."""
     from bhr_amd import _lib

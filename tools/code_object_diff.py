@@ -12,7 +12,10 @@ Under an object that differs, two lines per kernel symbol of either side (paired
 group segment bytes from the notes and the instruction count `n` from llvm-objdump -d, each as `old` or `old -> new`, and
 whether the instruction text is the same.  Instruction text is mnemonic and operands only: addresses, encodings and the
 branch-target labels (symbol + offset, which move with the kernel's place in .text) are dropped; a branch keeps its relative
-offset.  A kernel on one side only is listed as such, with the other side's one-sided kernels of the same text, if any."""
+offset.  A kernel on one side only is listed as such, with the other side's one-sided kernels of the same text, if any.
+
+Behind the objects, the kernels of the code objects that are on one side only (a source split or renamed): each OLD one with its
+resources and the NEW ones of the same instruction text and resources -- where it moved to -- or `no twin`."""
 import difflib
 import os
 import re
@@ -73,7 +76,7 @@ def per_kernel(d):
         elif cur is not None and line.startswith(("\t", " ")) and line.strip():
             cur["insts"].append(" ".join(line.split("//")[0].split()))
     for k in out.values():   # the padding behind a kernel's last instruction is not its code
-        while k["insts"] and k["insts"][-1].split()[0] in ("s_code_end", "s_nop"):
+        while k["insts"] and k["insts"][-1].split()[0] in ("s_code_end", "s_nop", "..."):   # "...": objdump's mark for a run of zero bytes
             k["insts"].pop()
     return out
 
@@ -101,6 +104,18 @@ def kernel_breakdown(a, b):
         print(f"    {sym}\n        {cols}  {text}")
 
 
+def moved_kernels(old_only, new_only):
+    """old_only, new_only: {object name: describe()} of the code objects on one side only."""
+    keys = ("vgpr", "sgpr", "private", "lds")
+    new = [(name, sym, k) for name, d in sorted(new_only.items()) for sym, k in sorted(per_kernel(d).items())]
+    print("kernels of the code objects on one side only:")
+    for name, d in sorted(old_only.items()):
+        for sym, x in sorted(per_kernel(d).items()):
+            cols = " ".join(f"{k} {x[k]}" for k in keys) + f" n {len(x['insts'])}"
+            twins = [f"{n}: {s}" for n, s, y in new if y["insts"] == x["insts"] and all(y[k] == x[k] for k in keys)]
+            print(f"    OLD {name}: {sym}\n        {cols}  " + ("; ".join("same text and resources as NEW " + t for t in twins) or "no twin in NEW"))
+
+
 def main(argv):
     if len(argv) != 3:
         sys.stderr.write(__doc__)
@@ -109,6 +124,7 @@ def main(argv):
     objs = lambda d: {f for f in os.listdir(d) if f.endswith(".o")}
     old, new = objs(old_dir), objs(new_dir)
     bad = 0
+    old_only, new_only = {}, {}
     with tempfile.TemporaryDirectory() as tmp:
         for name in sorted(old | new):
             a = describe(os.path.join(old_dir, name), os.path.join(tmp, "old", name)) if name in old else None
@@ -123,6 +139,7 @@ def main(argv):
                 bad += 1
                 have = a or b
                 side = "OLD" if b is None else "NEW"
+                (old_only if b is None else new_only)[name] = have
                 print(f"{name:24s} {len(have['text']):10d} {have['kernels']:3d}  DIFFERENT (code object only in {side})")
                 continue
             diffs = [k for k in ("text", "rodata", "notes") if a[k] != b[k]]
@@ -133,6 +150,8 @@ def main(argv):
             print(f"{name:24s} {len(b['text']):10d} {b['kernels']:3d}  {verdict}")
             if diffs:
                 kernel_breakdown(a, b)
+        if old_only and new_only:
+            moved_kernels(old_only, new_only)
     print(f"{'all the same' if not bad else str(bad) + ' object(s) differ'}: .text, .rodata and notes of every gfx950 code object")
     return 1 if bad else 0
 
