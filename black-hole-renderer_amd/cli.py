@@ -3,7 +3,8 @@
 Additions: ``--device hip`` (the default and only backend; ``gpu`` is accepted as an alias, ``cpu`` is
 refused -- this build has no CPU path), ``-r 8k``, ``--gpus N`` (row-block tiling of a still image
 inside one process; for ``--video`` launch one process per GPU with torchrun and frames are sharded
-round-robin by RANK / WORLD_SIZE), ``--disk_model`` (the analytic Disk V2 sources of the march kernel).
+round-robin by RANK / WORLD_SIZE), ``--disk_model`` (the analytic Disk V2 sources of the march kernel), ``--observer`` /
+``--observer_velocity`` (a camera that moves: aberration and Doppler shift).
 """
 from __future__ import annotations
 
@@ -76,6 +77,23 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "the photon's own angular momentum, and gas that plunges inside the ISCO with the ISCO orbit's energy and "
                         "angular momentum.  It is the Kerr kernel's: with --spin 0 the Schwarzschild hole is marched by it too, "
                         "and what --spin does not combine with, --redshift exact does not either")
+    p.add_argument("--observer", type=str, default=None, choices=["static", "circular", "infall"],
+                   help="a camera that moves: aberration squeezes the sky and the shadow towards the direction of motion, the "
+                        "Doppler factor brightens and blue-shifts what lies ahead.  static: at rest (the default picture, marched by the "
+                        "observer kernel); circular: on the circular geodesic through the camera position, in the disk's sense "
+                        "(half the speed of light at r = 3; outside 1.5 r_s and off the z axis); infall: in radial free fall from "
+                        "rest at infinity.  A still evaluates the velocity at --pov, --video at every frame's own camera position.  "
+                        "Marched by a strict kernel of its own whatever --math says.  Not with --spin, --redshift exact, --anti_alias "
+                        "lod_radius, --disk_model v2 / v2_volume, --supersample_threshold, --gpus > 1, --shutter, the ray-map flags or --passes")
+    p.add_argument("--observer_velocity", type=float, nargs=3, default=None, metavar=("BX", "BY", "BZ"),
+                   help="the moving camera's velocity given directly, in units of c as the static observer at the camera measures "
+                        "it, |beta| <= 0.995; instead of --observer")
+    p.add_argument("--observer_sky", type=str, default=None, choices=["shift", "plain"],
+                   help="--observer / --observer_velocity: shift (default) = the sky takes the Doppler factor too (brightness and "
+                        "colour, values above 1 go to the HDR plane); plain = the sky is aberrated only")
+    p.add_argument("--infall_to", type=float, default=None, metavar="R",
+                   help="--observer infall --video: the camera falls radially from |pov| to R >= 1.05 along --pov, the frames "
+                        "uniform in its proper time; not with --orbit")
     p.add_argument("--video_stream", type=str, default="auto", choices=["auto", "y4m", "off"],
                    help="--video: also hand the frames to the encoder as a yuv420p stream converted on the device "
                         "(auto: pipe into ffmpeg when it is on PATH; y4m: write <output stem>.y4m; off: PNG frames only)")
@@ -190,6 +208,53 @@ def parse_args(argv=None) -> argparse.Namespace:
         if not camera_outside_static_limit(args.pov, args.spin):
             p.error(f"{who} needs --pov outside the static limit of the hole: at {args.pov} f = r / S = {camera_f(args.pov, args.spin)[0]:.4g} "
                     f"(f < 1 is needed: r > 1 in the disk plane), no static observer and no photon along every pixel direction there")
+    moving = args.observer is not None or args.observer_velocity is not None
+    if moving or args.observer_sky is not None or args.infall_to is not None:
+        from . import observer as obs
+        from .camera import orbit_position
+        who = "--observer" if args.observer is not None else "--observer_velocity" if args.observer_velocity is not None else \
+            "--observer_sky" if args.observer_sky is not None else "--infall_to"
+        if args.observer is not None and args.observer_velocity is not None:
+            p.error("--observer names a velocity and --observer_velocity gives one: take one of the two")
+        if not moving:
+            p.error(f"{who} needs --observer or --observer_velocity: it belongs to a camera that moves")
+        if args.spin != 0:
+            p.error(f"{who} does not combine with --spin: the observer march is Schwarzschild's")
+        if args.redshift == "exact":
+            p.error(f"{who} does not combine with --redshift exact: its observer is static")
+        if args.anti_alias != "disabled":
+            p.error(f"{who} does not combine with --anti_alias lod_radius: the differential seeds under aberration are not implemented")
+        if args.disk_model != "texture":
+            p.error(f"{who} does not combine with --disk_model other than texture: the observer march shades the disk texture")
+        if args.supersample_threshold is not None:
+            p.error(f"{who} does not combine with --supersample_threshold: the observer march has no refinement kernels (plain --supersample works)")
+        if args.gpus != 1:
+            p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march the camera that stands still")
+        if args.shutter > 0:
+            p.error(f"{who} does not combine with --shutter: shutter frames march the camera that stands still")
+        if args.ray_map or args.orbit_map or args.shutter_map or args.passes is not None:
+            p.error(f"{who} does not combine with --ray_map, --orbit_map, --shutter_map or --passes: a ray map holds the rays of the camera that stands still")
+        if args.infall_to is not None:
+            if args.observer != "infall":
+                p.error("--infall_to needs --observer infall: it is the path of the falling camera")
+            if not args.video:
+                p.error("--infall_to needs --video: a still image stays at --pov")
+            if args.orbit:
+                p.error("--infall_to does not combine with --orbit: the camera falls radially")
+        try:
+            if args.observer_velocity is not None:
+                obs.check_beta(args.observer_velocity)
+            if args.infall_to is not None:
+                obs.check_infall_to(args.pov, args.infall_to)
+            # the named velocity where the camera will stand: --pov, frame 0 of an orbit (which keeps r and the height), and
+            # the end of a fall, where it is largest
+            if args.observer is not None:
+                obs.velocity(args.observer, orbit_position(args.pov, 0, max(args.n_frames, 1), args.orbit_degrees) if args.video and args.orbit else args.pov)
+                if args.infall_to is not None:
+                    obs.velocity(args.observer, obs.frame_plan(2, args.pov, "infall", infall_to=args.infall_to)[-1][0])
+        except ValueError as e:
+            p.error(f"{who}: {e}")
+    args.observer_sky = "shift" if args.observer_sky is None else args.observer_sky
     if args.map_supersample > 1 and not (args.ray_map or args.orbit_map or args.shutter_map):
         p.error("--map_supersample needs --ray_map, --orbit_map or --shutter_map: it is a ray map's factor (marched frames take --supersample)")
     if args.shutter_map:
@@ -277,6 +342,16 @@ def grade_from_args(args):
     if getattr(args, "tonemap", None) is None:
         return None
     return dict(tonemap=args.tonemap, exposure=args.exposure, white=args.white, transfer=args.transfer)
+
+
+def observer_beta(args):
+    """The velocity of a still image's camera: --observer_velocity, or --observer evaluated at --pov; None without either."""
+    from . import observer
+    if getattr(args, "observer_velocity", None) is not None:
+        return observer.check_beta(args.observer_velocity)
+    if getattr(args, "observer", None) is not None:
+        return tuple(float(v) for v in observer.velocity(args.observer, args.pov))
+    return None
 
 
 def spin_note(args) -> Optional[str]:
@@ -381,6 +456,9 @@ def main(argv=None) -> int:
     spin_kw = {"spin": args.spin} if args.spin != 0 else {}      # without a spin the drivers are called as ever
     if args.redshift != "model":
         spin_kw["redshift"] = args.redshift
+    # likewise the moving observer: without one the drivers are called as ever
+    moving = args.observer is not None or args.observer_velocity is not None
+    sky = args.observer_sky == "shift"
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))
@@ -408,7 +486,9 @@ def main(argv=None) -> int:
                              dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples,
                              grade=grade_from_args(args), ray_map=args.ray_map, orbit_map=args.orbit_map,
                              shutter_map=args.shutter_map, map_supersample=args.map_supersample, video_hdr=args.video_hdr,
-                             hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure)
+                             hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure,
+                             **(dict(observer=args.observer, observer_velocity=args.observer_velocity, observer_sky=sky,
+                                     infall_to=args.infall_to) if moving else {}))
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -432,6 +512,7 @@ def main(argv=None) -> int:
         anti_alias=args.anti_alias, aa_strength=args.aa_strength, disk_rotation_speed=args.disk_rotation_speed,
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
-        grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw)
+        grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw,
+        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}))
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

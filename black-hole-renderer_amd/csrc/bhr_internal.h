@@ -126,6 +126,14 @@ struct BhrKerrMarchArgs : BhrMarchArgs {
 struct BhrKerrExactMarchArgs : BhrKerrMarchArgs {
     float isco_r, isco_e, isco_l;
 };
+// The argument block of the observer object's kernels (march_observer.hip; bhr_render_observer): the march's block with the
+// moving camera behind it -- its velocity, gamma and gamma^2 / (gamma + 1) (binary64 on the host, each rounded once) and
+// whether the sky sample takes the Doppler factor.  A block of its own for the Kerr block's reason: BhrMarchArgs does not grow.
+struct BhrObserverMarchArgs : BhrMarchArgs {
+    float obs_beta[3];
+    float obs_gamma, obs_g2;
+    int32_t obs_sky_shift;
+};
 
 // A partial march launch: the tiles of `d_list` only.  bhr_launch_march_hybrid builds one for each of its launches (strict
 // list, fast list, fix list and the empty parts that bracket them) and passes it to bhr_launch_march (null: the whole block).
@@ -150,6 +158,7 @@ struct bhr_march_call {
     bool defer_end;          // the caller records the march-end event (adaptive frames: the refinement follows the base march)
     int32_t ss;              // supersampling factor of the frame being marched
     bool keep_start;         // a later sample of a shutter frame (bhr_render_shutter): the march-start event stays the first sample's
+    const bhr_observer *observer = nullptr;   // bhr_render_observer: the frame is marched by the observer object for this moving camera
 };
 
 // The march kernels by what they do; each march object returns its own instantiation of a name (or null) from
@@ -613,6 +622,7 @@ const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);
 const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.hip -> march_strict.o
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.hip -> march_strict_ilp.o
 const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_raymap.hip -> march_raymap.o
+const void *bhr_march_kernel_observer(bhr_march_kernel k, int32_t diff, int32_t ss);   // march_observer.hip -> march_observer.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
 

@@ -25,12 +25,14 @@
 // v_rsq/v_rcp/v_sqrt instead of IEEE sqrt + divide inside the RK4 stages, FMA contraction, and the
 // re-use of |new_pos| as the next step's |pos| (same value in the reference).
 //
-// The march's device source is six headers and five translation units, one per object (csrc/Makefile):
+// The march's device source is seven headers and six translation units, one per object (csrc/Makefile):
 //   march_device.h      this file: vectors, exact-rounding sequences, samplers, shading, parking slots, pixel stores
 //   ray_strict.h        Ray<DIFF, SRC>, strict: every operation of the RK4 loop in the reference's order with IEEE sqrt and
 //                       divide, so that positions, step counts and hit points are bit-identical to a strict f32 evaluation
 //                       of render.py:2854-3006 (selected with bhr_config.math_mode = 1)
 //   ray_fast.h          Ray<DIFF, SRC>, fast: v_rsq/v_rcp/v_sqrt, FMA contraction, in-plane state, the ray's own clock
+//   ray_observer.h      Ray<false, 0>, observer: the strict Ray launched along the aberrated pixel direction of a moving camera, its
+//                       Doppler factor in the disk's g and on the sky (bhr_render_observer)
 //   ray_kerr.h          Ray<false, 0>, Kerr: a spinning hole in Kerr-Schild coordinates, RK4 on (x, p), its own sampler and g-factor
 //                       (bhr_set_spin); the Schwarzschild Rays above know nothing of it
 //   march_tile.h        the tile schedule: march_tile_body, its plain, supersampled and list kernels
@@ -41,9 +43,10 @@
 //                                               a hybrid march; the strict flags and the ILP-first machine scheduler
 //   march_raymap.hip     -> march_raymap.o      ray_strict.h: the ray map's build and shade kernels; the ILP object's flags
 //   march_kerr.hip       -> march_kerr.o        ray_kerr.h, tile schedule, plain and supersampled; -ffp-contract=on, no fast-math
+//   march_observer.hip   -> march_observer.o    ray_observer.h, tile schedule, plain and supersampled; the strict flags
 // A translation unit includes the one Ray header it marches with (which includes this file), then the schedules it uses,
 // defines the kernels that are its own and ends with their table, by which the one host launcher (march_launch.hip) finds
-// them: bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr.
+// them: bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr / _observer.
 #pragma once
 #include "bhr_internal.h"
 #include "disk_v2_device.h"
@@ -244,8 +247,10 @@ __device__ __forceinline__ float4 sample_disk_level(const BhrScene &sc, float hi
 // f: the block the frame's camera position (the observer's radius) is read from -- `a` itself in every march; a shutter frame
 // from the ray map shades one set of records under several cameras and hands over each sample's (march_raymap.hip).  ONLY f.cp
 // may be read through f: that caller sets nothing else in it (see shade_hit).
+// obs_d: nu_observed / nu_static of a moving observer for this ray (ray_observer.h), a factor of g ahead of the cap; the
+// literal 1 of every other caller folds away.
 __device__ __forceinline__ V3 apply_g_factor(const BhrMarchArgs &a, const BhrMarchArgs &f, V3 base_color, V3 hit_pos, float hit_r,
-                                             V3 ray_dir_to_cam) {
+                                             V3 ray_dir_to_cam, float obs_d = 1.0f) {
     const float rs_f = BHR_RS;
     V3 cam_pos = ld3(f.cp);
     // |cam| is the same for every hit, so the compiler hoists it out of the march loop and keeps it in a VGPR for the
@@ -278,7 +283,7 @@ __device__ __forceinline__ V3 apply_g_factor(const BhrMarchArgs &a, const BhrMar
     float grav_den = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_em, rs_f + 1e-3f), 1e-6f));
     float g_grav = grav_num / grav_den;
 
-    float g = fminf(g_doppler * g_grav, BHR_G_FACTOR_CAP);
+    float g = fminf(g_doppler * g_grav * obs_d, BHR_G_FACTOR_CAP);
     float intensity = fmaxf(powf(g, BHR_G_LUMINOSITY_POWER), 0.0f);
     float brightness = BHR_G_BRIGHTNESS_GAIN * intensity / (1.0f + intensity / BHR_G_FACTOR_CAP);
 
@@ -422,7 +427,7 @@ __device__ __forceinline__ Pending<DIFF> park_pop(int &n_pend) {
 // callers re-run tools/code_object_diff.py against the parent build (profiles/raymap_shutter_code_objects.txt is the last run).
 template <bool DIFF, int SRC>
 __device__ __forceinline__ void shade_hit(const BhrMarchArgs &a, const BhrMarchArgs &f, Shade &sh, float hit_x, float hit_y,
-                                          V3 to_cam, float hdx_x, float hdx_y, float hdy_x, float hdy_y) {
+                                          V3 to_cam, float hdx_x, float hdx_y, float hdy_x, float hdy_y, float obs_d = 1.0f) {
     float hit_r = sqrtf(hit_x * hit_x + hit_y * hit_y);
     if (!(a.r_outer >= hit_r && hit_r >= a.r_inner)) return;
     float hit_z = hit_y * a.tan_t;
@@ -462,7 +467,7 @@ __device__ __forceinline__ void shade_hit(const BhrMarchArgs &a, const BhrMarchA
                              : sample_disk_level(a.sc, hit_x, hit_y, a.r_inner, a.r_outer, f.t_offset, lod_i);
     float base_alpha = fminf(rgba.w, 0.999f);
     float disk_alpha = 1.0f - powf(1.0f - base_alpha, BHR_DISK_ALPHA_GAIN);
-    V3 col = apply_g_factor(a, f, mk(rgba.x, rgba.y, rgba.z), mk(hit_x, hit_y, hit_z), hit_r, to_cam);
+    V3 col = apply_g_factor(a, f, mk(rgba.x, rgba.y, rgba.z), mk(hit_x, hit_y, hit_z), hit_r, to_cam, obs_d);
     float front = 1.0f - sh.alpha_total;
 #if BHR_RAY_STRICT
     sh.accum = mk(sh.accum.x + col.x * disk_alpha * front, sh.accum.y + col.y * disk_alpha * front,

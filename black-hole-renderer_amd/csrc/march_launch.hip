@@ -1,8 +1,8 @@
 // march_launch.hip -- the host half of the ray march: every march launch goes through bhr_launch_march.
 //
-// The march's device code is five objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
-// with the ILP-first scheduler, march_raymap.hip, march_kerr.hip; the layout: march_device.h); each object hands its kernels over
-// through a table (bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr).  This file resolves the
+// The march's device code is six objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
+// with the ILP-first scheduler, march_raymap.hip, march_kerr.hip, march_observer.hip; the layout: march_device.h); each object hands
+// its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr / _observer).  This file resolves the
 // arithmetic, builds the kernel arguments, keeps the tile order, the ray-step counters and the timing events, and picks
 // the kernel of a launch (march_kernel).  What a launch works from is in its arguments -- the caller's bhr_march_call
 // (camera, flags, stream, timing slot, end-event policy, supersampling factor) and, for one list of a hybrid march, a
@@ -67,6 +67,7 @@ float fast_sqrt(float s) {
 // The kernel of a launch and its grid (fn null: the part only records its bracket events).
 //
 //   arithmetic     request                                              kernel (object)
+//   any            a moving observer (bhr_render_observer)              march_observer_kernel / march_observer_ss_kernel (observer)
 //   any            a spin is set (bhr_set_spin), whole block            march_kerr_kernel / march_kerr_ss_kernel (kerr)
 //   any            ... and the exact redshift (bhr_set_redshift)         march_kerr_exact_kernel / march_kerr_exact_ss_kernel (kerr)
 //   any            hybrid part with n <= 0, not the fix list            none
@@ -95,12 +96,17 @@ struct MarchKernel {
     dim3 grid;
     size_t lds = 0;
 };
-MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *part, int math, uint32_t flags, bool diff) {
+MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *part, int math, uint32_t flags, bool diff, bool observer) {
     MarchKernel k;
     k.grid = dim3((a.n_list + 3) / 4);
     const bool persistent = (flags & BHR_PERSISTENT) != 0;
     const int ss = a.ss > 1;                                   // the supersampled twins (bhr_render refuses the schedules they lack)
     const auto own = math == BHR_MATH_FAST ? bhr_march_kernel_fast : bhr_march_kernel_strict;
+    // the moving observer (bhr_render_observer): the observer object's march, on the same terms as the spinning hole's below
+    if (observer) {
+        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = bhr_march_kernel_observer(BHR_MK_TILE, diff, ss);
+        return k;
+    }
     // the spinning hole: one arithmetic, one schedule, no lists (what has no Kerr form was refused before anything was launched)
     if (ctx->kerr_on) {
         if (!part && !persistent && !a.row_steps && !a.dv2)
@@ -299,7 +305,8 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     // caller chose; the first part records the start event and clears an untimed counter, the last part records the end event
     // with a spin set the context's math mode does not select the march: one launch of the Kerr object, its argument block the
     // strict one's (the post-pass has followed the math mode, bhr_frame_begin)
-    const int math = part ? part->math : ctx->kerr_on ? BHR_MATH_STRICT : bhr_resolve_math(ctx, flags);
+    // (likewise the frame of a moving observer, bhr_render_observer: one launch of the observer object)
+    const int math = part ? part->math : (ctx->kerr_on || call.observer) ? BHR_MATH_STRICT : bhr_resolve_math(ctx, flags);
     if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, call);
     const bool fast = math == BHR_MATH_FAST;
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
@@ -364,12 +371,25 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(bhr_slot(ctx).d_queue, 0, sizeof(unsigned int), stream));
     // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
     if (first_part && !call.keep_start) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, slot), stream));
-    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags));
+    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags), call.observer != nullptr);
     if (!k.fn && !(part && part->n <= 0 && part->repair != 2))
         return bhr_fail(BHR_ERR_STATE, "bhr_render: no march kernel for this launch (supersampling %d, flags %u)", call.ss, flags);
     if (k.fn) {
         int refill_below = 40;                                 // persistent schedule: refill a wave below 40 live lanes
         void *args[] = {&a, &refill_below};                    // (the second argument is the persistent kernel's alone)
+        // the moving observer: the finished march block with the camera's velocity behind it, gamma and gamma^2 / (gamma + 1)
+        // in binary64, each rounded once (the observer object's kernels take this block; nobody else reads it)
+        BhrObserverMarchArgs oa;
+        if (call.observer) {
+            static_cast<BhrMarchArgs &>(oa) = a;
+            const float *b = call.observer->beta;
+            const double gamma = 1.0 / sqrt(1.0 - ((double)b[0] * b[0] + (double)b[1] * b[1] + (double)b[2] * b[2]));
+            for (int c = 0; c < 3; ++c) oa.obs_beta[c] = b[c];
+            oa.obs_gamma = (float)gamma;
+            oa.obs_g2 = (float)(gamma * gamma / (gamma + 1.0));
+            oa.obs_sky_shift = call.observer->sky_shift ? 1 : 0;
+            args[0] = &oa;
+        }
         (void)hipLaunchKernel(k.fn, k.grid, dim3(256), args, k.lds, stream);
     }
     BHR_HIP(hipGetLastError());

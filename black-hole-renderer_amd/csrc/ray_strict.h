@@ -1,4 +1,5 @@
-// ray_strict.h -- the strict Ray of the march (march_strict.o, march_strict_ilp.o, march_raymap.o; see march_device.h).
+// ray_strict.h -- the strict Ray of the march (march_strict.o, march_strict_ilp.o, march_raymap.o, and under ray_observer.h
+// march_observer.o; see march_device.h).
 #pragma once
 #define BHR_RAY_STRICT 1
 #include "march_device.h"
@@ -9,7 +10,7 @@ namespace {
 // strict build: render.py:2854-3006 operation by operation, 3-D state
 // =============================================================================
 template <bool DIFF, int SRC = 0>
-struct Ray {
+struct StrictRay {
     V3 p, d;
     float m15L2;   // -1.5 * L2
     float r;       // |p|
@@ -25,7 +26,10 @@ struct Ray {
     V3 dpx, ddx, dpy, ddy;   // ray differentials (DIFF only)
 
     __device__ __forceinline__ void init(const BhrMarchArgs &a, int i, int j_local) {
-        V3 ray_dir = pixel_ray<DIFF>(a, i, j_local, ddx, ddy);
+        init_along(a, pixel_ray<DIFF>(a, i, j_local, ddx, ddy), i, j_local);
+    }
+    // the ray of pixel (i, j_local) leaves the camera along ray_dir (ray_observer.h: a moving observer's is not the pixel's own)
+    __device__ __forceinline__ void init_along(const BhrMarchArgs &a, V3 ray_dir, int i, int j_local) {
         p = ld3(a.cp);
         d = ray_dir;
         V3 Lv = cross(d, p);
@@ -227,5 +231,12 @@ struct Ray {
     __device__ __forceinline__ void finish_at(const BhrMarchArgs &a, int i, int j) { write_pixel(a, i, j, escaped(), d, sh); }
     __device__ __forceinline__ void values(const BhrMarchArgs &a, float bk[3], float dk[3]) const { pixel_values(a, escaped(), d, sh, bk, dk); }
 };
+
+// The Ray the schedules march (march_tile.h, march_persistent.h): the strict one itself, unless the Ray header that included
+// this file derives its own from it (ray_observer.h).
+#ifndef BHR_RAY_OBSERVER
+template <bool DIFF, int SRC = 0>
+using Ray = StrictRay<DIFF, SRC>;
+#endif
 
 }  // namespace

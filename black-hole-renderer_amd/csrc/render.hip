@@ -3,6 +3,8 @@
 // frame slots (bhr_frame_slot): frame n + 1 is launched on the other slot's stream into its own buffers and overlaps
 // the tail and the post-passes of frame n.  The scene is only read; everything that writes it or reads a frame goes
 // through bhr_enter, which orders the scene stream behind both slots.
+#include <math.h>
+
 #include "bhr_internal.h"
 
 namespace {
@@ -59,12 +61,13 @@ int32_t post_on_slot(bhr_ctx *ctx, uint32_t flags, int k, int ring) {
     return BHR_OK;
 }
 
-int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm) {
+// obs: the frame of a moving observer (bhr_render_observer), marched by the observer object; null: bhr_render's
+int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, const bhr_observer *obs = nullptr) {
     bhr_frame_slot &f = ctx->slots[k];
     BHR_TRY(bhr_frame_begin(ctx, flags));
     // an adaptively supersampled frame: the k = 1 march, then detect + refinement inside the same march bracket
     const bool adaptive = ctx->ada_k > 1;
-    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss};
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss, /* keep_start */ false, obs};
     *fm = {call.ss, 1, adaptive};
     BHR_TRY(bhr_launch_march(ctx, call));              // records the ring slot's march events
     if (adaptive) BHR_TRY(bhr_launch_adaptive(ctx, call));
@@ -225,6 +228,33 @@ int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     // launches that use per-context scratch (work queue of the persistent schedule, row-cost profile) stay on one slot
     const bool exclusive = (flags & (BHR_PERSISTENT | BHR_ROW_COSTS)) != 0;
     return frame_on_next_slot(ctx, flags, exclusive, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm); });
+}
+
+// One frame as a moving camera sees it (include/bhr.h).  Everything that can refuse does so before the frame takes a slot; like
+// bhr_render_shutter the frame neither triggers nor counts towards the calibration of slot 1's stream.
+int32_t bhr_render_observer(bhr_ctx *ctx, const bhr_camera *cam, const bhr_observer *obs, uint32_t flags) {
+    const char *who = "bhr_render_observer";
+    if (!ctx || !cam || !obs) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    const double b2 = (double)obs->beta[0] * obs->beta[0] + (double)obs->beta[1] * obs->beta[1] + (double)obs->beta[2] * obs->beta[2];
+    if (!(b2 <= 0.995 * 0.995))       // a NaN fails the comparison too
+        return bhr_fail(BHR_ERR_INVALID, "%s: observer velocity (%g, %g, %g): |beta| = %g, at most 0.995 and no NaN", who, (double)obs->beta[0],
+                        (double)obs->beta[1], (double)obs->beta[2], sqrt(b2));
+    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
+        return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
+    if (ctx->cfg.anti_alias != 0)
+        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with anti_alias = 1: the differential seeds under aberration are not implemented", who);
+    if (ctx->disk_source != BHR_DISK_TEXTURE)
+        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with a Disk V2 source (%d): the observer march shades the disk texture", who, ctx->disk_source);
+    if (ctx->ada_k > 1)
+        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with adaptive supersampling (factor %d): the observer march has no refinement kernels; use bhr_set_supersample", who, ctx->ada_k);
+    if (ctx->kerr_on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with the exact redshift (bhr_set_redshift): its observer is static", who);
+    if (ctx->kerr_on)
+        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with a spin set (bhr_set_spin, a / M = %g): the observer march is Schwarzschild's", who, (double)ctx->kerr_spin);
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer on a row-block context (rows %d of %d): needs a whole-frame context", who, ctx->rows, ctx->cfg.height);
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, obs); });
 }
 
 // One frame as the mean of n marches (include/bhr.h).  One frame of one frame slot: the next frame takes the other slot.

@@ -186,7 +186,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  gpus: int = 1, disk_model: str = "texture", math: Optional[str] = None,
                  supersample: int = 1, supersample_threshold: Optional[float] = None, bit_depth: int = 8,
                  dither: str = "none", grade: Optional[dict] = None, hdr_path: Optional[str] = None,
-                 passes_path: Optional[str] = None, spin: float = 0.0, redshift: str = "model") -> np.ndarray:
+                 passes_path: Optional[str] = None, spin: float = 0.0, redshift: str = "model",
+                 observer=None, observer_sky: bool = True) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -199,8 +200,13 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     there as a compressed .npz (output.write_passes); the image itself is rendered as without it (one device, one ray per
     pixel, the texture disk source).  ``spin``: a / M of a spinning hole (HipRenderer.set_spin; one device, the texture source,
     no tilt, no anti-aliasing, no passes).  ``redshift``: "model" or "exact", the disk's g-factor of the Kerr metric
-    (HipRenderer.set_redshift; the Kerr march at any spin, with a spin's restrictions)."""
+    (HipRenderer.set_redshift; the Kerr march at any spin, with a spin's restrictions).  ``observer``: the velocity beta of a
+    camera that moves through ``cam_pos`` (HipRenderer.render_async; bhr_amd.observer.velocity names some), ``observer_sky``:
+    whether the sky takes its Doppler factor; one device, the texture source, no anti-aliasing, no spin, no adaptive
+    supersampling, no passes."""
     check_depth_and_dither(bit_depth, dither)
+    check_observer(observer, anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus,
+                   spin=spin, redshift=redshift, passes=passes_path is not None)
     check_passes(passes_path, gpus, supersample, disk_model)
     grade = check_grade(grade)
     if hdr_path is not None:
@@ -237,7 +243,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     print(f"HIP: {width}x{height}, cam_pos={list(cam_pos)}, fov={fov}°, step_size={step_size}")
     if grade is not None:
         renderer.set_grade(**grade)
-    img = renderer.render(cam_pos, fov, frame=0)
+    img = renderer.render(cam_pos, fov, frame=0, **({} if observer is None else {"observer": observer, "observer_sky": observer_sky}))
     if hdr_path is not None:
         save_hdr(renderer.read_hdr(), hdr_path)
     c = renderer.counters()
@@ -255,6 +261,34 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
           f"{c['ray_steps'] / 1e6:.1f} Mray-steps, {c['ray_steps'] / max(c['march_ms'], 1e-6) / 1e3:.0f} Mray-steps/s)")
     renderer.close()
     return img
+
+
+def check_observer(observer, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None, gpus: int = 1,
+                   world: int = 1, spin: float = 0.0, redshift: str = "model", passes: bool = False, shutter: float = 0.0,
+                   maps: bool = False) -> None:
+    """What a frame of a moving observer takes: a velocity within |beta| <= 0.995, one device, the texture disk source, the
+    Schwarzschild hole with the model redshift, marched frames without anti-aliasing, adaptive supersampling, shutter or ray
+    map.  Raises ValueError before any device work; None: the camera stands still and nothing is checked."""
+    if observer is None:
+        return
+    from .observer import check_beta
+    check_beta(observer)
+    if anti_alias not in ("disabled", 0, False, None):
+        raise ValueError("a moving observer does not combine with anti_alias: the differential seeds under aberration are not implemented")
+    if disk_model != "texture":
+        raise ValueError("a moving observer does not combine with disk_model v2 / v2_volume: the observer march shades the disk texture")
+    if supersample_threshold is not None:
+        raise ValueError("a moving observer does not combine with supersample_threshold: the observer march has no refinement kernels (plain supersample works)")
+    if gpus != 1:
+        raise ValueError("a moving observer renders on one GPU: row-block tiles march the camera that stands still")
+    if spin != 0 or redshift != "model":
+        raise ValueError("a moving observer does not combine with a spin or the exact redshift: the observer march is Schwarzschild's, the exact redshift's observer static")
+    if passes:
+        raise ValueError("a moving observer writes no passes: a ray map holds the rays of the camera that stands still")
+    if shutter > 0:
+        raise ValueError("a moving observer does not combine with shutter: shutter frames march the camera that stands still")
+    if maps:
+        raise ValueError("a moving observer does not combine with ray_map, orbit_map or shutter_map: a ray map holds the rays of the camera that stands still")
 
 
 def check_passes(passes_path, gpus: int = 1, supersample: int = 1, disk_model: str = "texture") -> None:
@@ -476,7 +510,7 @@ def hdr_sidecar(hdr: dict, max_cll: float, max_fall: float, frames: int) -> dict
 
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
-                    shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0) -> dict:
+                    shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -502,6 +536,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(map_supersample=map_supersample)
     if video_hdr is not None:
         params.update(video_hdr=video_hdr, hdr_white=hdr_white, hdr_exposure=hdr_exposure)
+    if observer is not None:
+        params.update(observer=observer)
     return params
 
 
@@ -539,7 +575,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  bit_depth: int = 8, dither: str = "none", shutter: float = 0.0, shutter_samples: int = 8,
                  grade: Optional[dict] = None, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False,
                  map_supersample: int = 1, video_hdr: Optional[str] = None, hdr_white: float = 203.0, hdr_exposure: float = 0.0,
-                 **_deprecated_kwargs) -> None:
+                 observer: Optional[str] = None, observer_velocity=None, observer_sky: bool = True,
+                 infall_to: Optional[float] = None, **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -628,7 +665,28 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     After the loop ``<output stem>.hdr10.json`` (hdr_sidecar) records the stream's colour description, its MaxCLL and MaxFALL
     -- known only then -- and its frame count.  Refused with ValueError, before any device work: several ranks, a resume that
     finds completed frames (a stream cannot be resumed), ``video_codec="mjpeg"``, ``video_stream="off"``, odd frame sizes.  The
-    progress record carries ``video_hdr``, ``hdr_white`` and ``hdr_exposure`` only when ``video_hdr`` is set."""
+    progress record carries ``video_hdr``, ``hdr_white`` and ``hdr_exposure`` only when ``video_hdr`` is set.
+
+    ``observer`` ("static", "circular" or "infall": bhr_amd.observer.velocity) or ``observer_velocity`` (a fixed beta): the
+    camera moves.  Every frame is render_async(..., observer=beta_f, observer_sky=...) with the named velocity evaluated at
+    that frame's own camera position (bhr_amd.observer.frame_plan), so an ``orbit`` with "circular" is the view from the
+    orbiting camera.  ``infall_to`` = R (with "infall", without ``orbit``) moves the camera radially from |static_cam_pos| to R
+    along static_cam_pos, uniformly in the falling observer's proper time.  Refused with ValueError, before any device work, with
+    both given, ``shutter > 0``, a ray map, anti-aliasing, a Disk V2 source, adaptive supersampling or a spin.  The progress
+    record carries the observer's settings when one is given, and a resume with others starts over."""
+    moving = observer is not None or observer_velocity is not None
+    plan = None
+    if moving or infall_to is not None:
+        from . import observer as obs_mod
+        if observer is not None and observer_velocity is not None:
+            raise ValueError("observer names a velocity and observer_velocity gives one: take one of the two")
+        if infall_to is not None and observer != "infall":
+            raise ValueError("infall_to is the path of observer='infall'")
+        thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
+        check_observer((0.0, 0.0, 0.0), anti_alias=renderer.anti_alias, disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2",
+                       supersample_threshold=thr, spin=renderer.spin, redshift=renderer.redshift, shutter=shutter,
+                       maps=ray_map or orbit_map or shutter_map)
+        plan = obs_mod.frame_plan(n_frames, static_cam_pos, observer, observer_velocity, orbit, orbit_degrees, infall_to)
     check_map_supersample(map_supersample, ray_map, orbit_map, shutter_map)
     check_shutter(shutter, shutter_samples)
     if video_stream not in ("auto", "y4m", "off"):
@@ -665,7 +723,9 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
     params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither,
                              shutter, shutter_samples, grade, ray_map, orbit_map, shutter_map, map_supersample,
-                             video_hdr, hdr_white, hdr_exposure)
+                             video_hdr, hdr_white, hdr_exposure,
+                             observer=None if plan is None else {"kind": observer, "velocity": None if observer_velocity is None else list(observer_velocity),
+                                                                 "sky": bool(observer_sky), "infall_to": infall_to})
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -783,6 +843,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         if not mine:
             continue
         cam_pos = orbit_position(static_cam_pos, frame, n_frames, orbit_degrees) if orbit else static_cam_pos
+        if plan is not None:
+            cam_pos, beta = plan[frame]                    # the moving observer: the frame's position and its velocity there
         t0 = time.time()
         if shutter > 0:
             times = shutter_times(frame, shutter, shutter_samples)
@@ -796,6 +858,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             renderer.render_from_ray_map_async(frame=0)    # the same frame from the map: shade, no march
         elif orbit_map:
             renderer.render_from_ray_map_async(frame=0, cam_pos=cam_pos, fov=fov)    # the map turned to the frame's camera
+        elif plan is not None:
+            renderer.render_async(cam_pos, fov, frame=0, observer=beta, observer_sky=observer_sky)
         else:
             renderer.render_async(cam_pos, fov, frame=0)   # lens flare, when enabled, is applied on the device
         sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))

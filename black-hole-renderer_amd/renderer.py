@@ -452,13 +452,27 @@ class HipRenderer:
                 | {None: 0, "fast": _lib.FORCE_FAST, "strict": _lib.FORCE_STRICT, "hybrid": _lib.FORCE_HYBRID}[math])
 
     def render_async(self, cam_pos, fov: float, frame: int = 0, skip_differentials: bool = False,
-                     skip_bloom: bool = False, compaction: bool = False, math=None, lens_flare=None) -> None:
+                     skip_bloom: bool = False, compaction: bool = False, math=None, lens_flare=None,
+                     observer=None, observer_sky: bool = True) -> None:
         """Launch march + bloom + combine; the frame stays in HBM (counterpart of render_to_field,
-        render.py:3819-3863, without the GUI flip)."""
+        render.py:3819-3863, without the GUI flip).
+
+        ``observer``: a velocity (beta_x, beta_y, beta_z) in units of c, |beta| <= 0.995 -- the frame as a camera sees it that
+        moves through ``cam_pos`` with it (bhr_render_observer; include/bhr.h states the model, bhr_amd.observer names
+        velocities): aberration, the Doppler factor in the disk's g and, with ``observer_sky``, on the sky.  Marched by the
+        observer kernel whatever ``math`` the renderer has (``math=`` here is refused), (0, 0, 0) included, which is the
+        strict frame.  The velocity belongs to this call alone.  None (the default): the camera stands still, as ever."""
         cam = self.camera_uniforms(cam_pos, fov, frame)
         flags = self._flags(skip_differentials, skip_bloom, compaction, math)
         if self.lens_flare if lens_flare is None else lens_flare:
             flags |= _lib.LENS_FLARE          # device twin of _apply_lens_flare (render.py:3920-4028)
+        if observer is not None:
+            from . import observer as obs_mod
+            obs = _lib.Observer()
+            obs.beta[:] = obs_mod.check_beta(observer)
+            obs.sky_shift = 1 if observer_sky else 0
+            _lib.check(self._lib.bhr_render_observer(self._ctx, C.byref(cam), C.byref(obs), flags))
+            return
         _lib.check(self._lib.bhr_render(self._ctx, C.byref(cam), flags))
 
     def render_shutter_async(self, cam_positions, fov: float, t_offsets, skip_differentials: bool = False,
@@ -689,6 +703,12 @@ class HipRenderer:
             _lib.check(self._lib.bhr_kerr_redshift_resources(_lib.REDSHIFT_EXACT, 1 if supersampled else 0, out))
         return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
 
+    def observer_resources(self, supersampled: bool = False) -> dict:
+        """Registers per lane, LDS and scratch bytes of the observer march kernel (bhr_observer_resources)."""
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_observer_resources(1 if supersampled else 0, out))
+        return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
+
     def adaptive_info(self) -> dict:
         """The last adaptively supersampled frame: pixels refined, how many of them were marched strict, pixels of the frame
         (bhr_adaptive_info; synchronises)."""
@@ -806,12 +826,13 @@ class HipRenderer:
         return self.read_layer(_lib.LAYER_HDR)
 
     def render(self, cam_pos: List[float], fov: float, frame: int = 0,
-               skip_differentials: bool = False, skip_bloom: bool = False) -> np.ndarray:
-        """One frame -> (rows, width, 3) float32 in [0, 1]  (render.py:3865-3923)."""
+               skip_differentials: bool = False, skip_bloom: bool = False, observer=None, observer_sky: bool = True) -> np.ndarray:
+        """One frame -> (rows, width, 3) float32 in [0, 1]  (render.py:3865-3923).  ``observer``, ``observer_sky``: a moving
+        camera, as render_async takes it."""
         if self.lens_flare and self.rows != self.height:
             raise ValueError("lens flare needs whole-frame sums; render row blocks through "
                              "bhr_amd.multigpu.group_render(..., lens_flare=True)")
-        self.render_async(cam_pos, fov, frame, skip_differentials, skip_bloom)
+        self.render_async(cam_pos, fov, frame, skip_differentials, skip_bloom, observer=observer, observer_sky=observer_sky)
         return self.read_layer(_lib.LAYER_FINAL)
 
     def selftest(self) -> dict:

@@ -497,6 +497,32 @@ BHR_API int32_t bhr_kerr_resources(int32_t supersampled, int32_t out[3]);
 BHR_API int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode);
 /* bhr_kerr_resources for the kernels of a redshift mode (BHR_REDSHIFT_MODEL: the same numbers). */
 BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, int32_t out[3]);
+/* A moving observer: one frame as a camera sees it that moves through bhr_camera.pos with velocity beta (a 3-vector in units of
+ * c, |beta| <= 0.995) as the static observer there measures it.  That observer's local frame is identified with the coordinate
+ * axes, as the camera that stands still identifies it; the camera basis is the moving camera's own.  With n' the pixel's
+ * direction in that basis, gamma = 1 / sqrt(1 - beta.beta) and D = 1 / (gamma (1 - beta.n')) = nu_observed / nu_static, the ray
+ * is traced along n = (n' + (gamma^2 / (gamma + 1)) (beta.n') beta - gamma beta) D (aberration) by the strict Schwarzschild
+ * march; the disk's g-factor is g_doppler g_grav D ahead of its cap (brightness law and Wien shift), and with sky_shift != 0
+ * the sky sample c becomes c (r_s I, I, b_s I) with Ds = clamp(D, 0.1, 1.5), I = Ds^1.5, w = 1 - 1 / Ds,
+ * r_s = min(e^(2.21 w) / e^(2.72 w), 3), b_s = min(e^(3.13 w) / e^(2.72 w), 3), ahead of the product with 1 - alpha: BG may
+ * exceed 1, FINAL clips as ever, the HDR plane carries the headroom.  sky_shift = 0: the sky is aberrated only.  (DESIGN.md
+ * "Observer" states the model; tests/observer_ref.py is its CPU reference.)
+ * The frame is bhr_render's in every other respect -- next frame slot, one timing-ring entry, counters, post-pass, lens flare,
+ * grade, HDR plane, rows, dither, sinks and streams; asynchronous -- and is marched by the observer object
+ * (csrc/march_observer.hip) whatever bhr_config.math_mode is, beta = 0 included, where BG, DISK and ray_steps are the strict
+ * march's bit for bit; the post-pass follows the context's arithmetic.  The velocity travels with the call: frames in flight
+ * may differ in it.  Works with a tilted disk and bhr_set_supersample.  flags: BHR_SKIP_BLOOM, BHR_LENS_FLARE.
+ * BHR_ERR_INVALID with a message that names the combination, nothing launched and the context untouched: a null argument, a NaN
+ * in beta or |beta| > 0.995, any other flag bit, anti_alias = 1, a Disk V2 source, adaptive supersampling, a spin or the forced
+ * Kerr march (bhr_set_spin) or the exact redshift, a row-block context. */
+typedef struct {
+    float beta[3];
+    int32_t sky_shift;
+} bhr_observer;
+BHR_API int32_t bhr_render_observer(bhr_ctx *ctx, const bhr_camera *cam, const bhr_observer *obs, uint32_t flags);
+/* out = {VGPRs per lane, LDS bytes per block, scratch bytes per lane} of the observer march kernel (supersampled != 0: of its
+ * supersampled twin), from hipFuncGetAttributes.  No context. */
+BHR_API int32_t bhr_observer_resources(int32_t supersampled, int32_t out[3]);
 /* The library's switches.  Each has an environment variable that bhr_create reads ONCE (no entry point calls getenv
  * afterwards) and can be changed per context later with this call -- what tests and A/B tools use:
  *   "bloom_split"     BHR_BLOOM_SPLIT     -1 post-pass by arithmetic (exact f32 under strict, split f16 under fast / hybrid), 0 / 1 force
