@@ -24,6 +24,7 @@ TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
 HDR_PQ, HDR_HLG = 1, 2
 REDSHIFT_MODEL, REDSHIFT_EXACT = 0, 1
 RAYMAP_STEPS, RAYMAP_STATUS, RAYMAP_ESCAPE_DIR, RAYMAP_CROSSINGS, RAYMAP_HITS = 0, 1, 2, 3, 4
+RAYMAP_STARS = 5
 
 # every symbol include/bhr.h declares (tests check the .so exports exactly these)
 SYMBOLS = (
@@ -34,6 +35,7 @@ SYMBOLS = (
     "bhr_set_spin", "bhr_kerr_resources", "bhr_set_redshift", "bhr_kerr_redshift_resources",
     "bhr_render_observer", "bhr_observer_resources",
     "bhr_raymap_build", "bhr_raymap_render", "bhr_raymap_render_view", "bhr_raymap_render_shutter", "bhr_raymap_read", "bhr_raymap_get_info", "bhr_raymap_free",
+    "bhr_set_stars", "bhr_get_stars_info", "bhr_stars_resources",
     "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_read_final_u16", "bhr_set_dither", "bhr_dither_matrix", "bhr_set_grade", "bhr_grade_frame", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
     "bhr_stats_prepare", "bhr_stats_select", "bhr_stats_row_statistics",
     "bhr_png_bound16", "bhr_png_encode16", "bhr_png_write16", "bhr_png16_device_bound", "bhr_png16_device_max_width", "bhr_png16_encode_device", "bhr_sink_create_png16",
@@ -85,6 +87,21 @@ class RayMapInfo(C.Structure):
     _fields_ = [("built", C.c_int32), ("diff", C.c_int32), ("slots", C.c_int32), ("width", C.c_int32), ("rows", C.c_int32),
                 ("supersample", C.c_int32), ("crossings_stored", C.c_int64), ("overflow_pixels", C.c_int64),
                 ("device_bytes", C.c_int64), ("ray_steps", C.c_uint64), ("cam", Camera)]
+
+
+class Star(C.Structure):
+    """bhr_star: a unit direction on the celestial sphere and an RGB flux (sky value x steradian)."""
+    _fields_ = [("dir", C.c_float * 3), ("flux", C.c_float * 3)]
+
+
+class StarParams(C.Structure):
+    _fields_ = [("max_magnification", C.c_float), ("max_span_deg", C.c_float)]
+
+
+class StarsInfo(C.Structure):
+    _fields_ = [("n", C.c_int32), ("bins_theta", C.c_int32), ("bins_phi", C.c_int32), ("reserved", C.c_int32),
+                ("params", StarParams), ("device_bytes", C.c_int64), ("images", C.c_int64), ("capped", C.c_int64),
+                ("skipped_span", C.c_int64)]
 
 
 TILE_SHM_WORDS = 8
@@ -149,6 +166,9 @@ def load() -> C.CDLL:
     lib.bhr_raymap_read.argtypes = [P, I32, C.c_void_p, C.c_int64]
     lib.bhr_raymap_get_info.argtypes = [P, C.POINTER(RayMapInfo)]
     lib.bhr_raymap_free.argtypes = [P]
+    lib.bhr_set_stars.argtypes = [P, C.c_void_p, I32, C.POINTER(StarParams)]
+    lib.bhr_get_stars_info.argtypes = [P, C.POINTER(StarsInfo)]
+    lib.bhr_stars_resources.argtypes = [I32, C.POINTER(C.c_int32)]
     lib.bhr_read_layer.argtypes = [P, I32, F]
     lib.bhr_read_gathered.argtypes = [P, F]
     PI32 = C.POINTER(C.c_int32)

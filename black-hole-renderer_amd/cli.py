@@ -4,7 +4,8 @@ Additions: ``--device hip`` (the default and only backend; ``gpu`` is accepted a
 refused -- this build has no CPU path), ``-r 8k``, ``--gpus N`` (row-block tiling of a still image
 inside one process; for ``--video`` launch one process per GPU with torchrun and frames are sharded
 round-robin by RANK / WORLD_SIZE), ``--disk_model`` (the analytic Disk V2 sources of the march kernel), ``--observer`` /
-``--observer_velocity`` (a camera that moves: aberration and Doppler shift).
+``--observer_velocity`` (a camera that moves: aberration and Doppler shift), ``--stars point`` (the procedural sky's stars as a
+catalogue of lensed points rendered through a ray map).
 """
 from __future__ import annotations
 
@@ -169,6 +170,20 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="still images: also write the view's geometry passes (per pixel: steps, ray fate, escape direction, disk "
                         "crossings and hit points, from a ray map of the view) and the frame's bg / disk / blur layers as a "
                         "compressed .npz; the image itself is unchanged.  One GPU, --supersample 1, --disk_model texture")
+    p.add_argument("--stars", type=str, default="texture", choices=["texture", "point"],
+                   help="how the procedural sky's stars are drawn.  texture (default): baked into the sky texture as Gaussian blobs, "
+                        "as the reference does -- a texture lookup conserves surface brightness, so near the hole a star is smeared "
+                        "into a dim arc.  point: a star catalogue rendered through a ray map of the view -- every image of a star "
+                        "stays a point and its flux is multiplied by the lensing magnification (the Einstein-ring sparkle); the sky "
+                        "texture keeps the nebula and the glow.  The frame is shaded from the map with the strict arithmetic, "
+                        "whatever --math says.  --video needs --ray_map or --orbit_map beside it.  Not with --texture, --shutter_map, "
+                        "--map_supersample > 1, --supersample > 1, --gpus > 1, --disk_model v2 / v2_volume, --spin, --redshift exact "
+                        "or a moving observer")
+    p.add_argument("--star_gain", type=float, default=2.0, metavar="G",
+                   help="--stars point: an unlensed star of table brightness b deposits G b in total, whatever the resolution "
+                        "(default: 2.0, an aesthetic choice)")
+    p.add_argument("--star_max_magnification", type=float, default=32.0, metavar="M",
+                   help="--stars point: cap of a star image's magnification on the critical curve, 1 .. 1e6 (default: 32)")
     p.add_argument("--ignore_taichi_cache", action="store_true", help="accepted for compatibility; no effect")
     p.add_argument("--video", action="store_true", help="render frames and assemble a video")
     p.add_argument("--interactive", action="store_true", help="not available in this build (needs ti.GUI)")
@@ -254,6 +269,7 @@ def parse_args(argv=None) -> argparse.Namespace:
                     obs.velocity(args.observer, obs.frame_plan(2, args.pov, "infall", infall_to=args.infall_to)[-1][0])
         except ValueError as e:
             p.error(f"{who}: {e}")
+    observer_flags = moving or args.observer_sky is not None or args.infall_to is not None
     args.observer_sky = "shift" if args.observer_sky is None else args.observer_sky
     if args.map_supersample > 1 and not (args.ray_map or args.orbit_map or args.shutter_map):
         p.error("--map_supersample needs --ray_map, --orbit_map or --shutter_map: it is a ray map's factor (marched frames take --supersample)")
@@ -327,6 +343,31 @@ def parse_args(argv=None) -> argparse.Namespace:
             p.error(f"--passes writes a .npz file, got {args.passes!r}")
         if args.gpus != 1 or args.supersample != 1 or args.disk_model != "texture":
             p.error("--passes needs one GPU, --supersample 1 and --disk_model texture: the passes come from a ray map")
+    # point stars, behind every refusal above: a line that was refused without --stars point is refused with the same words
+    if args.stars == "point":
+        if args.texture is not None:
+            p.error("--stars point does not combine with --texture: a sky image has no catalogue")
+        if args.spin != 0 or args.redshift == "exact":
+            p.error("--stars point does not combine with --spin or --redshift exact: a ray map holds Schwarzschild rays")
+        if observer_flags:
+            p.error("--stars point does not combine with --observer, --observer_velocity, --observer_sky or --infall_to: a ray map holds "
+                    "the rays of the camera that stands still")
+        if args.video and not (args.ray_map or args.orbit_map or args.shutter_map):
+            p.error("--stars point with --video needs --ray_map or --orbit_map: point stars are rendered through a ray map")
+        if args.shutter_map:
+            p.error("--stars point does not combine with --shutter_map: shutter frames from the map have no point stars")
+        if args.map_supersample > 1:
+            p.error("--stars point does not combine with --map_supersample other than 1: point stars need a map with one ray per pixel")
+        if args.supersample != 1:
+            p.error("--stars point does not combine with --supersample other than 1: point stars need a map with one ray per pixel")
+        if args.gpus != 1:
+            p.error("--stars point does not combine with --gpus other than 1: a ray map lives on one GPU")
+        if args.disk_model != "texture":
+            p.error("--stars point does not combine with --disk_model other than texture: a ray map shades the disk texture")
+        if not (args.star_gain > 0 and math.isfinite(args.star_gain)):
+            p.error(f"--star_gain must be greater than 0, got {args.star_gain}")
+        if not 1.0 <= args.star_max_magnification <= 1e6:
+            p.error(f"--star_max_magnification must be between 1 and 1e6, got {args.star_max_magnification}")
     # --exposure, --white, --transfer and --hdr_output without --tonemap mean --tonemap clip
     if args.tonemap is None and any(v is not None for v in (args.exposure, args.white, args.transfer, args.hdr_output)):
         args.tonemap = "clip"
@@ -342,6 +383,13 @@ def grade_from_args(args):
     if getattr(args, "tonemap", None) is None:
         return None
     return dict(tonemap=args.tonemap, exposure=args.exposure, white=args.white, transfer=args.transfer)
+
+
+def stars_from_args(args):
+    """The point stars of a command line as drivers.render_image / render_video take them: None without --stars point."""
+    if getattr(args, "stars", "texture") != "point":
+        return None
+    return dict(gain=args.star_gain, max_magnification=args.star_max_magnification)
 
 
 def observer_beta(args):
@@ -459,6 +507,8 @@ def main(argv=None) -> int:
     # likewise the moving observer: without one the drivers are called as ever
     moving = args.observer is not None or args.observer_velocity is not None
     sky = args.observer_sky == "shift"
+    # ... and the point stars
+    stars_kw = {"stars": stars_from_args(args)} if args.stars == "point" else {}
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))
@@ -475,7 +525,7 @@ def main(argv=None) -> int:
             width, height, args.pov, fov, args.step_size, args.texture, args.n_stars, 2048, 1024, args.r_max, None,
             args.disk_inner_radius, args.disk_outer_radius, args.disk_tilt, args.lens_flare, args.anti_alias,
             args.aa_strength, args.disk_rotation_speed, device_index=local_rank, math=args.math, supersample=args.supersample,
-            supersample_threshold=args.supersample_threshold, **spin_kw)
+            supersample_threshold=args.supersample_threshold, **spin_kw, **stars_kw)
         print(f"Rendering video: {args.n_frames} frames at {width}x{height} (rank {rank}/{world})")
         drivers.render_video(renderer, width, height, n_frames=args.n_frames, fps=args.fps,
                              output_path=args.output, fov=fov, static_cam_pos=args.pov, orbit=args.orbit,
@@ -486,7 +536,7 @@ def main(argv=None) -> int:
                              dither=args.dither, shutter=args.shutter, shutter_samples=args.shutter_samples,
                              grade=grade_from_args(args), ray_map=args.ray_map, orbit_map=args.orbit_map,
                              shutter_map=args.shutter_map, map_supersample=args.map_supersample, video_hdr=args.video_hdr,
-                             hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure,
+                             hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure, **stars_kw,
                              **(dict(observer=args.observer, observer_velocity=args.observer_velocity, observer_sky=sky,
                                      infall_to=args.infall_to) if moving else {}))
         if world > 1:
@@ -512,7 +562,7 @@ def main(argv=None) -> int:
         anti_alias=args.anti_alias, aa_strength=args.aa_strength, disk_rotation_speed=args.disk_rotation_speed,
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
-        grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw,
+        grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw, **stars_kw,
         **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}))
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

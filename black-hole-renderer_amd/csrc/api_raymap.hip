@@ -96,6 +96,14 @@ int32_t turn_of_build(const bhr_camera &b, const bhr_camera *cam, const char *wh
     return BHR_OK;
 }
 
+// point stars (bhr_set_stars): a supersampled map's shade kernels have no STARS variant
+int32_t check_stars(const bhr_ctx *ctx, const char *who) {
+    if (bhr_have_stars(ctx) && ctx->raymap->ss > 1)
+        return bhr_fail(BHR_ERR_STATE, "%s: a star catalogue is set (bhr_set_stars, %d stars) and the map is supersampled (factor %d); point stars need a map with one ray per pixel",
+                        who, ctx->stars->n, ctx->raymap->ss);
+    return BHR_OK;
+}
+
 }  // namespace
 
 void bhr_raymap_release(bhr_ctx *ctx) {
@@ -103,6 +111,7 @@ void bhr_raymap_release(bhr_ctx *ctx) {
     free_planes(ctx->raymap);
     delete ctx->raymap;
     ctx->raymap = nullptr;
+    bhr_stars_invalidate(ctx);
 }
 
 int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
@@ -114,7 +123,8 @@ int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
     if (ctx->rows != ctx->cfg.height)
         return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
     if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no ray map has been built (bhr_raymap_build)");
-    return check_context(ctx, "bhr_raymap_render", BHR_ERR_STATE);
+    BHR_TRY(check_context(ctx, "bhr_raymap_render", BHR_ERR_STATE));
+    return check_stars(ctx, "bhr_raymap_render");
 }
 
 // bhr_raymap_render_view's refusals, before anything is launched: the disk is not tilted, and `cam` is the build camera turned
@@ -133,7 +143,8 @@ int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32
                         (double)ctx->cfg.disk_tilt_deg);
     if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no ray map has been built (bhr_raymap_build)", who);
     BHR_TRY(check_context(ctx, who, BHR_ERR_STATE));
-    return turn_of_build(ctx->raymap->cam, cam, who, rot_c, rot_s);
+    BHR_TRY(turn_of_build(ctx->raymap->cam, cam, who, rot_c, rot_s));
+    return check_stars(ctx, who);
 }
 
 // bhr_raymap_render_shutter's refusals (include/bhr.h), before anything is launched.  A sample with the build camera's pose,
@@ -175,6 +186,10 @@ int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, in
     }
     smp->n = n;
     smp->inv = 1.0f / (float)n;
+    // point stars: the fused and the supersampled shade kernels have no STARS variant
+    if (bhr_have_stars(ctx))
+        return bhr_fail(BHR_ERR_STATE, "%s: a star catalogue is set (bhr_set_stars, %d stars); shutter frames from the map have no point stars -- remove it (n = 0) first", who,
+                        ctx->stars->n);
     return BHR_OK;
 }
 
@@ -205,6 +220,7 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     }
     bhr_raymap *rm = ctx->raymap;
     rm->built = 0;
+    bhr_stars_invalidate(ctx);         // the star plane of the build view belongs to the map this build rewrites
     if (rm->a.hits && (rm->alloc_slots != K || rm->alloc_comps != comps || rm->alloc_ss != ss)) {
         BHR_TRY(drain(ctx));
         free_planes(rm);
@@ -262,6 +278,16 @@ int32_t bhr_raymap_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes) {
     const BhrRayMapArgs &a = rm->a;
     const size_t plane = (size_t)a.plane;
     size_t want = 0;
+    if (which == BHR_RAYMAP_STARS) {
+        // the build view's star plane (include/bhr.h "point stars"), gathered now if the map or the catalogue changed since
+        if (!bhr_have_stars(ctx)) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_read: no star catalogue has been set (bhr_set_stars)");
+        BHR_TRY(check_stars(ctx, "bhr_raymap_read"));
+        want = plane * 12;
+        if (bytes != (int64_t)want) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: plane %d has %zu bytes, caller gave %lld", which, want, (long long)bytes);
+        BHR_TRY(bhr_stars_ensure_plane(ctx));
+        BHR_TRY(bhr_enter(ctx));
+        return fetch(ctx, out, ctx->stars->d_plane, want);
+    }
     switch (which) {
     case BHR_RAYMAP_STEPS: case BHR_RAYMAP_STATUS: case BHR_RAYMAP_CROSSINGS: want = plane * 4; break;
     case BHR_RAYMAP_ESCAPE_DIR: want = plane * 12; break;

@@ -188,6 +188,9 @@ enum bhr_march_kernel {
     BHR_MK_RAYMAP_SHUTTER_ROT,  // raymap_shade_shutter_kernel<diff, true>: each sample turned about z by its own angle  raymap
     // the Kerr object's exact-redshift kernels (march_kerr.hip; the model ones are its BHR_MK_TILE)
     BHR_MK_KERR_EXACT,    // march_kerr_exact_kernel / march_kerr_exact_ss_kernel                                   kerr
+    // point stars (bhr_set_stars): the shade kernels that add the star plane to the sky sample; no supersampled twins
+    BHR_MK_RAYMAP_SHADE_STARS,      // raymap_shade_kernel<diff, false, true>                                     raymap
+    BHR_MK_RAYMAP_SHADE_STARS_ROT,  // raymap_shade_kernel<diff, true, true>                                      raymap
     // (ss: BUILD, SHADE and SHADE_ROT have twins for a supersampled map, raymap_build_kernel<DIFF, true> / raymap_shade_ss_kernel; the shutter kernels have none)
 };
 
@@ -206,6 +209,27 @@ struct BhrRayMapArgs {
     int32_t slots, comps;
     int64_t plane;               // rows W
     float rot_c, rot_s;          // the rotated shade kernel only: cosine and sine of the turn about z (bhr_raymap_render_view)
+};
+
+// The map as the STARS shade kernels see it: the map's block with the frame's star plane behind it.  A block of its own for the
+// Kerr block's reason: BhrRayMapArgs is an argument of every other map kernel and does not grow.
+struct BhrRayMapStarArgs : BhrRayMapArgs {
+    const float *stars;          // (rows, W, 3): the star plane S of the frame's view (stars.hip)
+};
+
+// Second argument of stars_gather_kernel (stars.hip), behind the march's block of the view (its camera fields and frame shape):
+// the map's two planes it reads, the turn of the view, the binned catalogue and the plane it fills.
+struct BhrStarsArgs {
+    const int32_t *status;       // the map's STATUS plane
+    const float *dir;            // ... and its three direction planes
+    int64_t plane;               // rows W
+    float rot_c, rot_s;          // the turned kernel only: cosine and sine of the view's turn about z
+    const float *rec;            // n star records of 6 floats (direction, flux), sorted by bin
+    const int32_t *off;          // bins_theta bins_phi + 1 offsets into them
+    int32_t bins_theta, bins_phi;
+    float cos_span, max_mag;     // cos(max_span) (binary64, rounded once), max_magnification
+    float *out;                  // S: (rows, W, 3)
+    unsigned int *counts;        // images, capped, skipped_span (cleared ahead of the launch)
 };
 
 // The samples of a shutter frame from the map (bhr_raymap_render_shutter): third argument of raymap_shade_shutter_kernel, behind
@@ -282,6 +306,19 @@ struct bhr_raymap {
     uint64_t ray_steps, crossings_stored, overflow_pixels;
 };
 
+// The context's star catalogue (api_stars.hip): read-only shared state while frames are in flight, like the map.
+struct bhr_stars {
+    int32_t n, bins_theta, bins_phi;
+    bhr_star_params params;
+    float cos_span;              // cos(max_span_deg), binary64 rounded once
+    float *d_rec;                // n x 6
+    int32_t *d_off;              // bins + 1
+    float *d_plane;              // the build view's plane (rows, W, 3) and, behind it, its gather's three counts
+    int32_t plane_valid;         // ... holds the plane of the map and catalogue as they are
+    const unsigned int *last_counts;   // the counts of the last gather launched (in d_plane's tail or a frame slot's)
+    int64_t device_bytes;
+};
+
 // geometry of a context's split-f16 bloom buffers (bloom.hip)
 struct bhr_split_geom {
     int32_t NT;            // 16-tap chunks either side of a tile: ceil(R / 16) + 1
@@ -331,6 +368,8 @@ struct bhr_frame_slot {
     unsigned int *d_ada_counts;
     // shutter frames (shutter.hip), on first use: the running sums of the samples' BG and DISK layers, (rows, W, 3) f32 each
     float *d_acc_bg, *d_acc_disk;
+    // point stars (api_stars.hip), on first use: the star plane of a turned view's frame, (rows, W, 3) f32, and behind it its gather's counts
+    float *d_star_plane;
     // second march stream: the strict tiles of a two-stream hybrid march run on it beside the fast ones instead of ahead of
     // them (bhr_aux_fork / _join, which creates the streams of all slots on first use)
     hipStream_t aux_stream;
@@ -469,6 +508,9 @@ struct bhr_ctx {
     int32_t kerr_on;
     float kerr_spin;
     int32_t kerr_redshift;     // bhr_set_redshift: BHR_REDSHIFT_MODEL (0) or BHR_REDSHIFT_EXACT, which needs kerr_on
+
+    // point stars (api_stars.hip)
+    bhr_stars *stars;          // null until a catalogue is set (bhr_set_stars)
 };
 
 // The active frame slot: the one bhr_activate_slot / bhr_render last pointed the launchers at.
@@ -613,7 +655,13 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call);
 // ss: the map's factor -- the build marches the fine frame bhr_fine(ctx, ss) of `cam`
 int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss);
 // rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
-int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f);
+// stars: the star plane of the frame's view (bhr_set_stars), added to the sky sample by the STARS kernels; null: the kernels without
+int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f,
+                                const float *stars = nullptr);
+// the star plane of the map seen from `cam`, the build camera turned by (rot_c, rot_s), into `out` (rows W 3 floats and three
+// counts behind them, which the launch clears first) on `stream` (stars.hip: stars_gather_kernel)
+int32_t bhr_launch_stars_gather(bhr_ctx *ctx, const bhr_camera *cam, const BhrRayMapArgs &m, float rot_c, float rot_s, float *out, hipStream_t stream);
+const void *bhr_stars_kernel(int32_t rot);                                             // stars.hip -> stars.o
 // all samples of a shutter frame from the map in one launch (raymap_shade_shutter_kernel): the mean of the n frames the launch
 // above would store for (smp[j].t, smp[j].c, smp[j].s), into the active slot's BG / DISK; no packed bloom operands.  Opens the
 // frame's march bracket; the caller closes it.  turned: some sample has a turn other than (1, 0).
@@ -699,6 +747,16 @@ int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32
 // ... and of bhr_raymap_render_shutter, which fills smp (t, c, s per sample, n, 1 / n) and tells whether any sample is turned
 int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned);
 void bhr_raymap_release(bhr_ctx *ctx);
+
+// ---- api_stars.hip ----------------------------------------------------------------------------------------------------------------------
+inline bool bhr_have_stars(const bhr_ctx *ctx) { return ctx->stars && ctx->stars->n > 0; }
+size_t bhr_star_plane_floats(const bhr_ctx *ctx);                          // rows W 3 and the counts' words behind them
+// the build view's plane exists and is current (gathers it on the scene stream, behind the frames in flight, if not)
+int32_t bhr_stars_ensure_plane(bhr_ctx *ctx);
+// the star plane of the active slot's frame from the map turned by (c, s) on ctx->stream: the cached one for no turn, else gathered into the slot's own
+int32_t bhr_stars_frame_plane(bhr_ctx *ctx, const bhr_camera *cam, float c, float s, const float **plane);
+void bhr_stars_invalidate(bhr_ctx *ctx);                                   // the map changed: the cached plane is stale
+void bhr_stars_release(bhr_ctx *ctx);
 
 // ---- lifecycle.hip, texture.hip, disk_v2.hip ------------------------------------------------------------------------------------------
 void bhr_population_free(bhr_ctx *ctx);

@@ -522,21 +522,59 @@ static int32_t raymap_shade_args(bhr_ctx *ctx, const bhr_march_call &call, const
 
 // rot_c, rot_s: the turn about z of call.cam from the map's build camera (bhr_raymap_render_view); 1, 0 is no turn and takes the
 // kernel without one, whose frame is the strict frame bit for bit.
-int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c, float rot_s) {
+int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c, float rot_s, const float *stars) {
     // call.ss: the map's factor -- the block of the fine frame (k W x k rows, k^2 W rows == the map's plane), a wave per fine tile
     BhrMarchArgs a;
     BHR_TRY(raymap_shade_args(ctx, call, m, diff, call.ss, "bhr_raymap_render", a));
     const bool turned = !(rot_c == 1.0f && rot_s == 0.0f);
-    const void *fn = bhr_march_kernel_raymap(turned ? BHR_MK_RAYMAP_SHADE_ROT : BHR_MK_RAYMAP_SHADE, diff, call.ss > 1);
+    // stars: the STARS kernels, which have no supersampled twins (the table then returns none)
+    const bhr_march_kernel name = stars ? (turned ? BHR_MK_RAYMAP_SHADE_STARS_ROT : BHR_MK_RAYMAP_SHADE_STARS) : (turned ? BHR_MK_RAYMAP_SHADE_ROT : BHR_MK_RAYMAP_SHADE);
+    const void *fn = bhr_march_kernel_raymap(name, diff, call.ss > 1);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no shade kernel in this library");
     // the frame's march bracket opens here; the overflow launch behind this one (bhr_launch_march, last part) closes it
     // (a later sample of a shutter frame from the map keeps the first sample's)
     if (!call.keep_start) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
-    BhrRayMapArgs mm = m;
+    BhrRayMapStarArgs mm;              // the kernels without stars read its first sizeof(BhrRayMapArgs) bytes
+    static_cast<BhrRayMapArgs &>(mm) = m;
     mm.rot_c = rot_c;
     mm.rot_s = rot_s;
+    mm.stars = stars;
     void *args[] = {&a, &mm};
     (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
+    BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}
+
+// The star plane of the map `m` seen from `cam` -- the build camera turned about z by (rot_c, rot_s) -- into `out`: rows W 3
+// floats, and behind them the gather's three counts, cleared here ahead of the launch (stars.hip).  The march's block carries
+// the view's camera and the frame's shape; the kernel reads nothing else of it.
+int32_t bhr_launch_stars_gather(bhr_ctx *ctx, const bhr_camera *cam, const BhrRayMapArgs &m, float rot_c, float rot_s, float *out, hipStream_t stream) {
+    const bhr_stars *st = ctx->stars;
+    if (!st || st->n <= 0) return bhr_fail(BHR_ERR_STATE, "star gather: no star catalogue (bhr_set_stars)");
+    const bhr_march_call call = {cam, BHR_FORCE_STRICT | BHR_SKIP_BLOOM, stream, /* slot */ -1, false, false, 1, false};
+    BhrMarchArgs a;
+    march_args(ctx, call, nullptr, 1, false, a);
+    if ((int64_t)a.width * a.rows != m.plane) return bhr_fail(BHR_ERR_STATE, "star gather: the map has %lld pixels, the frame %lld", (long long)m.plane, (long long)a.width * a.rows);
+    const bool turned = !(rot_c == 1.0f && rot_s == 0.0f);
+    const void *fn = bhr_stars_kernel(turned ? 1 : 0);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "star gather: no gather kernel in this library");
+    BhrStarsArgs s;
+    s.status = m.status;
+    s.dir = m.dir;
+    s.plane = m.plane;
+    s.rot_c = rot_c;
+    s.rot_s = rot_s;
+    s.rec = st->d_rec;
+    s.off = st->d_off;
+    s.bins_theta = st->bins_theta;
+    s.bins_phi = st->bins_phi;
+    s.cos_span = st->cos_span;
+    s.max_mag = st->params.max_magnification;
+    s.out = out;
+    s.counts = (unsigned int *)(out + (size_t)a.width * a.rows * 3);
+    BHR_HIP(hipMemsetAsync(s.counts, 0, 4 * sizeof(unsigned int), stream));
+    void *args[] = {&a, &s};
+    (void)hipLaunchKernel(fn, dim3((a.width + 14) / 15, (a.rows + 14) / 15), dim3(256), args, 0, stream);
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }

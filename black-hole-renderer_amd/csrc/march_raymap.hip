@@ -28,10 +28,17 @@
 // contraction in this object).  Such a frame is the strict march of the BUILD view's rays, not bit for bit the strict frame of
 // the turned view; the launcher takes <DIFF, false> for c = 1, s = 0.
 //
+// raymap_shade_kernel<DIFF, ROT, true> (STARS) is the frame of a context with a star catalogue (bhr_set_stars; include/bhr.h "point
+// stars"): the view's star plane, gathered by stars.hip's kernel ahead of this launch, joins the sky sample ahead of the march's
+// own product.  The map's block then has the plane's pointer behind it (BhrRayMapStarArgs); the kernels without stars keep their
+// block, their instructions and their registers (profiles/stars_code_objects.txt).
+//
 // raymap_shade_shutter_kernel<DIFF, ROT> is a shutter frame from the map in one launch (bhr_raymap_render_shutter): per pixel,
 // the values raymap_shade_kernel<DIFF, ROT> would store under each sample's (t_offset, c, s), summed on the chip (in LDS, a word per lane and channel) in the order
 // of bhr_render_shutter's mean and multiplied by 1 / n.  It is in this object because the object's flags are what make
 // shade_hit, sample_skybox and turn_xy give the same bits wherever they are inlined.
+#include <type_traits>
+
 #include "ray_strict.h"
 
 namespace {
@@ -175,9 +182,13 @@ __device__ __forceinline__ Shade raymap_shade_records(const BhrMarchArgs &a, con
 }
 
 // render.py:3008-3018 as pixel_values has it, from the direction the build kernel stored already normalized
-__device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool escaped, V3 dir, const Shade &sh, float bk[3], float dk[3]) {
+// star: the pixel's value of the star plane (stars.hip; include/bhr.h "point stars"), added to the sky sample ahead of the product --
+// of a captured ray's pixel too, which has images from the triangles of its neighbours; null: no catalogue, no addition
+__device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool escaped, V3 dir, const Shade &sh, float bk[3], float dk[3],
+                                                    const float *star = nullptr) {
     V3 bg = mk(0, 0, 0);
     if (escaped) bg = sample_skybox(a.sc, dir);
+    if (star) bg = bg + mk(star[0], star[1], star[2]);
     float k = 1.0f - sh.alpha_total;
     bk[0] = __fmul_rn(bg.x, k);
     bk[1] = __fmul_rn(bg.y, k);
@@ -191,19 +202,22 @@ __device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool 
 // records were), then the march's own pixel values.
 template <bool ROT>
 __device__ __forceinline__ void raymap_values(const BhrMarchArgs &a, const BhrRayMapArgs &m, size_t pix, const Shade &sh, float rc, float rs,
-                                              float bk[3], float dk[3]) {
+                                              float bk[3], float dk[3], const float *star = nullptr) {
     const bool esc = m.status[pix] == 1;
     V3 dir = mk(m.dir[pix], m.dir[(size_t)m.plane + pix], m.dir[2 * (size_t)m.plane + pix]);
     if (ROT) turn_xy(rc, rs, dir.x, dir.y);
-    raymap_pixel_values(a, esc, dir, sh, bk, dk);
+    raymap_pixel_values(a, esc, dir, sh, bk, dk, star);
 }
 
 // ---- the shade kernels --------------------------------------------------------------------------------------------------------
 // One lane per pixel, an 8x8 tile per wave as in the march (texture locality, and store_pixel's packed layout is per tile);
 // tiles in row-major order: every lane does about the same work.
 // ROT: the records are turned about z by (m.rot_c, m.rot_s) before they are shaded (the head of this file).
-template <bool DIFF, bool ROT>
-__global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRayMapArgs m) {
+// STARS: the frame of a context with a star catalogue (bhr_set_stars) -- the map's block has the view's star plane behind it
+// (BhrRayMapStarArgs), whose value at the pixel joins the sky sample.  A pixel on the overflow list gets none: the fix kernel
+// stores it.
+template <bool DIFF, bool ROT, bool STARS = false>
+__global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, std::conditional_t<STARS, BhrRayMapStarArgs, BhrRayMapArgs> m) {
     const int tile = wave_slot();
     if (tile >= a.n_tiles) return;
     const int lane = threadIdx.x & 63;
@@ -220,7 +234,8 @@ __global__ __launch_bounds__(256) void raymap_shade_kernel(BhrMarchArgs a, BhrRa
     const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;
     const Shade sh = raymap_shade_records<DIFF, ROT>(a, a, m, pix, count, rc, rs);
     float bk[3], dk[3];
-    raymap_values<ROT>(a, m, pix, sh, rc, rs, bk, dk);
+    if constexpr (STARS) raymap_values<ROT>(a, m, pix, sh, rc, rs, bk, dk, m.stars + pix * 3);
+    else raymap_values<ROT>(a, m, pix, sh, rc, rs, bk, dk);
     store_pixel(a, i, j, a.width, bk, dk);
 }
 
@@ -360,6 +375,10 @@ const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss
     case BHR_MK_RAYMAP_BUILD: return diff ? (const void *)raymap_build_kernel<true, false> : (const void *)raymap_build_kernel<false, false>;
     case BHR_MK_RAYMAP_SHADE: return diff ? (const void *)raymap_shade_kernel<true, false> : (const void *)raymap_shade_kernel<false, false>;
     case BHR_MK_RAYMAP_SHADE_ROT: return diff ? (const void *)raymap_shade_kernel<true, true> : (const void *)raymap_shade_kernel<false, true>;
+    case BHR_MK_RAYMAP_SHADE_STARS:
+        return diff ? (const void *)raymap_shade_kernel<true, false, true> : (const void *)raymap_shade_kernel<false, false, true>;
+    case BHR_MK_RAYMAP_SHADE_STARS_ROT:
+        return diff ? (const void *)raymap_shade_kernel<true, true, true> : (const void *)raymap_shade_kernel<false, true, true>;
     case BHR_MK_RAYMAP_SHUTTER:
         return diff ? (const void *)raymap_shade_shutter_kernel<true, false> : (const void *)raymap_shade_shutter_kernel<false, false>;
     case BHR_MK_RAYMAP_SHUTTER_ROT:

@@ -115,8 +115,13 @@ bhr_march_part raymap_fix_part(const bhr_raymap &rm) {
 
 // The launches of one frame from the map `rm` under `call`: the shade kernel over the stored records, turned by (c, s), then the
 // strict fix kernel over the overflow list (which, unless the call defers it, records the ring slot's march-end event).
+// With a star catalogue set (bhr_set_stars) the view's star plane comes first -- the cached one of the build view, or the gather
+// of the turned view into the slot's own plane, on the frame's stream ahead of its march bracket -- and the shade kernel is the
+// STARS one.
 int32_t raymap_frame_launches(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm, float c, float s) {
-    BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, c, s));
+    const float *stars = nullptr;
+    if (bhr_have_stars(ctx)) BHR_TRY(bhr_stars_frame_plane(ctx, call.cam, c, s, &stars));
+    BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, c, s, stars));
     const bhr_march_part part = raymap_fix_part(rm);
     return bhr_launch_march(ctx, call, &part);
 }
@@ -278,6 +283,7 @@ int32_t bhr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     bhr_camera cam = ctx->raymap->cam;
     cam.t_offset = t_offset;
+    if (bhr_have_stars(ctx)) BHR_TRY(bhr_stars_ensure_plane(ctx));   // the build view's star plane, once per (map, catalogue)
     const uint32_t fl = raymap_frame_flags(ctx, flags);
     return frame_on_next_slot(ctx, fl, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, &cam, fl, k, ring, fm); });
 }
@@ -289,6 +295,7 @@ int32_t bhr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fla
     BHR_TRY(bhr_raymap_check_render_view(ctx, cam, flags, &rot_c, &rot_s));
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     const bhr_camera view = *cam;
+    if (bhr_have_stars(ctx) && rot_c == 1.0f && rot_s == 0.0f) BHR_TRY(bhr_stars_ensure_plane(ctx));   // angle 0: bhr_raymap_render's plane
     const uint32_t fl = raymap_frame_flags(ctx, flags);
     return frame_on_next_slot(ctx, fl, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, &view, fl, k, ring, fm, rot_c, rot_s); });
 }

@@ -145,9 +145,13 @@ def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, 
                   tex_h=1024, r_max=10.0, disk_texture_path=None, r_disk_inner=R_DISK_INNER_DEFAULT,
                   r_disk_outer=R_DISK_OUTER_DEFAULT, disk_tilt=0.0, lens_flare=False, anti_alias="disabled",
                   aa_strength=1.0, disk_rotation_speed=0.1, device_index=0, rows=None, frame_slots=None, math=None,
-                  supersample=1, supersample_threshold=None, spin=0.0, redshift="model"):
+                  supersample=1, supersample_threshold=None, spin=0.0, redshift="model", stars=None):
     """Renderer with a placeholder (or file) disk texture, as the reference's entry points build it
-    (render.py:4044-4064, 4627-4644).  Returns (renderer, use_lifecycle, n_r, n_phi)."""
+    (render.py:4044-4064, 4627-4644).  Returns (renderer, use_lifecycle, n_r, n_phi).
+    ``stars``: None, or the point stars of check_stars -- the procedural sky is then built WITHOUT its baked star blobs and its
+    ``n_stars`` stars become the renderer's catalogue (HipRenderer.set_stars), with the solid angle of a pixel of the view
+    (cam_pos, fov) in their flux, so that the look does not depend on the resolution."""
+    stars = check_stars(stars, skybox_path=skybox_path, supersample=supersample, spin=spin, redshift=redshift)
     # procedural sky: the host draws its random tables, the device rasterises them (nebula resize, star blobs in
     # NumPy's accumulation order, Milky-Way glow; skyglow.hip); an image file is loaded as it is
     procedural_sky = not (skybox_path and os.path.isfile(skybox_path))
@@ -171,9 +175,49 @@ def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, 
                            frame_slots=frame_slots, supersample=supersample, supersample_threshold=supersample_threshold,
                            **({} if math is None else {"math": math}), **({"spin": spin} if spin != 0 else {}),
                            **({"redshift": redshift} if redshift != "model" else {}))
-    if procedural_sky:
+    if procedural_sky and stars is not None:
+        from .skybox import sky_tables
+        from .stars import catalog_from_tables
+        renderer.build_procedural_skybox(seed=42, n_stars=n_stars, starless=True)
+        cam = renderer.camera_uniforms(cam_pos, fov, 0)
+        dirs, flux = catalog_from_tables(sky_tables(tex_w, tex_h, 42, n_stars), stars["gain"], float(cam.pixel_width) * float(cam.pixel_height))
+        renderer.set_stars(dirs, flux, max_magnification=stars["max_magnification"])
+    elif procedural_sky:
         renderer.build_procedural_skybox(seed=42, n_stars=n_stars)
     return renderer, use_lifecycle, n_r, n_phi
+
+
+def check_stars(stars, skybox_path=None, supersample=1, spin: float = 0.0, redshift: str = "model", gpus: int = 1,
+                disk_model: str = "texture", observer=None):
+    """--stars point / stars=dict(gain=, max_magnification=): the procedural sky's stars as a catalogue of lensed points rendered
+    through a ray map.  -> the dict with its defaults filled in, or None.  Raises ValueError, naming the combination, for what
+    point stars do not take: a sky image (it has no catalogue), supersampling, several GPUs, Disk V2, a spin or the exact
+    redshift, a moving observer."""
+    if stars is None:
+        return None
+    from .stars import DEFAULT_MAX_MAGNIFICATION, DEFAULT_STAR_GAIN
+    out = {"gain": DEFAULT_STAR_GAIN, "max_magnification": DEFAULT_MAX_MAGNIFICATION}
+    unknown = set(stars) - set(out)
+    if unknown:
+        raise ValueError(f"stars takes gain and max_magnification, got {sorted(unknown)}")
+    out.update(stars)
+    if not (out["gain"] > 0 and np.isfinite(out["gain"])):
+        raise ValueError(f"star gain must be greater than 0, got {out['gain']}")
+    if not 1.0 <= out["max_magnification"] <= 1e6:
+        raise ValueError(f"star max_magnification must be between 1 and 1e6, got {out['max_magnification']}")
+    if skybox_path is not None:
+        raise ValueError("point stars do not combine with a sky texture: a sky image has no catalogue")
+    if supersample not in (None, 1):
+        raise ValueError("point stars do not combine with supersample > 1: they need a ray map with one ray per pixel")
+    if gpus != 1:
+        raise ValueError("point stars render on one GPU: a ray map lives on one GPU")
+    if disk_model != "texture":
+        raise ValueError("point stars do not combine with disk_model v2 / v2_volume: a ray map shades the disk texture")
+    if spin != 0 or redshift != "model":
+        raise ValueError("point stars do not combine with a spin or the exact redshift: a ray map holds Schwarzschild rays")
+    if observer is not None:
+        raise ValueError("point stars do not combine with a moving observer: a ray map holds the rays of the camera that stands still")
+    return out
 
 
 def render_image(width: int, height: int, cam_pos: List[float], fov: float, step_size: float,
@@ -187,7 +231,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  supersample: int = 1, supersample_threshold: Optional[float] = None, bit_depth: int = 8,
                  dither: str = "none", grade: Optional[dict] = None, hdr_path: Optional[str] = None,
                  passes_path: Optional[str] = None, spin: float = 0.0, redshift: str = "model",
-                 observer=None, observer_sky: bool = True) -> np.ndarray:
+                 observer=None, observer_sky: bool = True, stars: Optional[dict] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -203,8 +247,12 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     (HipRenderer.set_redshift; the Kerr march at any spin, with a spin's restrictions).  ``observer``: the velocity beta of a
     camera that moves through ``cam_pos`` (HipRenderer.render_async; bhr_amd.observer.velocity names some), ``observer_sky``:
     whether the sky takes its Doppler factor; one device, the texture source, no anti-aliasing, no spin, no adaptive
-    supersampling, no passes."""
+    supersampling, no passes.  ``stars``: None, or dict(gain=, max_magnification=) -- point stars (check_stars): the sky is built
+    without its baked stars, the view's ray map is built and the frame is shaded from it with the star catalogue, by the strict
+    arithmetic whatever ``math`` says."""
     check_depth_and_dither(bit_depth, dither)
+    stars = check_stars(stars, skybox_path=skybox_path, supersample=supersample, spin=spin, redshift=redshift, gpus=gpus,
+                        disk_model=disk_model, observer=observer)
     check_observer(observer, anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus,
                    spin=spin, redshift=redshift, passes=passes_path is not None)
     check_passes(passes_path, gpus, supersample, disk_model)
@@ -233,7 +281,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         width, height, cam_pos, fov, step_size, skybox_path, n_stars, tex_w, tex_h, r_max, disk_texture_path,
         r_disk_inner, r_disk_outer, disk_tilt, lens_flare, anti_alias, aa_strength, disk_rotation_speed, math=math,
         supersample=supersample, supersample_threshold=supersample_threshold, spin=spin,
-        **({"redshift": redshift} if redshift != "model" else {}))
+        **({"redshift": redshift} if redshift != "model" else {}), **({} if stars is None else {"stars": stars}))
     if use_analytic_disk(renderer, disk_model):
         pass
     elif use_lifecycle:
@@ -243,7 +291,16 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     print(f"HIP: {width}x{height}, cam_pos={list(cam_pos)}, fov={fov}°, step_size={step_size}")
     if grade is not None:
         renderer.set_grade(**grade)
-    img = renderer.render(cam_pos, fov, frame=0, **({} if observer is None else {"observer": observer, "observer_sky": observer_sky}))
+    if stars is not None:
+        from . import _lib
+        renderer.build_ray_map(cam_pos, fov)
+        renderer.render_from_ray_map_async(frame=0)
+        img = renderer.read_layer(_lib.LAYER_FINAL)
+        si = renderer.stars_info()
+        print(f"Point stars: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
+              f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
+    else:
+        img = renderer.render(cam_pos, fov, frame=0, **({} if observer is None else {"observer": observer, "observer_sky": observer_sky}))
     if hdr_path is not None:
         save_hdr(renderer.read_hdr(), hdr_path)
     c = renderer.counters()
@@ -510,7 +567,8 @@ def hdr_sidecar(hdr: dict, max_cll: float, max_fall: float, frames: int) -> dict
 
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
-                    shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None) -> dict:
+                    shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None,
+                    stars=None) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -538,6 +596,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(video_hdr=video_hdr, hdr_white=hdr_white, hdr_exposure=hdr_exposure)
     if observer is not None:
         params.update(observer=observer)
+    if stars is not None:
+        params.update(stars=dict(stars))
     return params
 
 
@@ -576,7 +636,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  grade: Optional[dict] = None, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False,
                  map_supersample: int = 1, video_hdr: Optional[str] = None, hdr_white: float = 203.0, hdr_exposure: float = 0.0,
                  observer: Optional[str] = None, observer_velocity=None, observer_sky: bool = True,
-                 infall_to: Optional[float] = None, **_deprecated_kwargs) -> None:
+                 infall_to: Optional[float] = None, stars: Optional[dict] = None, **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -706,6 +766,21 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     if ray_map:
         check_ray_map(ray_map, orbit, shutter, renderer.supersample if supersample is None else supersample,
                       "texture" if getattr(renderer, "_dv2", None) is None else "v2", 1, world)
+    # point stars: the renderer carries the catalogue (make_renderer(stars=)); the frames that show it are the map's
+    if stars is not None:
+        stars = check_stars(stars, supersample=renderer.supersample if supersample is None else supersample, spin=renderer.spin,
+                            redshift=renderer.redshift, disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2",
+                            observer=None if plan is None else observer or observer_velocity)
+        if shutter_map:
+            raise ValueError("point stars do not combine with shutter_map: shutter frames from the map have no point stars")
+        if not (ray_map or orbit_map):
+            raise ValueError("point stars in a video need ray_map or orbit_map: they are rendered through a ray map")
+        if map_supersample != 1:
+            raise ValueError("point stars do not combine with map_supersample > 1: they need a ray map with one ray per pixel")
+        if world != 1:
+            raise ValueError("point stars render on one GPU: a ray map lives on one GPU")
+        if renderer.stars_info()["n"] == 0:
+            raise ValueError("point stars: the renderer has no star catalogue (make_renderer(stars=...) sets it)")
     if video_codec not in VIDEO_CODECS:
         raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
     check_depth_and_dither(bit_depth, dither, video_codec)
@@ -725,7 +800,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                              shutter, shutter_samples, grade, ray_map, orbit_map, shutter_map, map_supersample,
                              video_hdr, hdr_white, hdr_exposure,
                              observer=None if plan is None else {"kind": observer, "velocity": None if observer_velocity is None else list(observer_velocity),
-                                                                 "sky": bool(observer_sky), "infall_to": infall_to})
+                                                                 "sky": bool(observer_sky), "infall_to": infall_to},
+                             **({} if stars is None else {"stars": stars}))
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never

@@ -219,13 +219,17 @@ class HipRenderer:
         constructor must be generate_skybox(..., glow=False)."""
         _lib.check(self._lib.bhr_skybox_add_glow(self._ctx))
 
-    def build_procedural_skybox(self, seed: int = 42, n_stars: int = 6000) -> None:
+    def build_procedural_skybox(self, seed: int = 42, n_stars: int = 6000, starless: bool = False) -> None:
         """generate_skybox(tex_w, tex_h, seed, n_stars) (render.py:153-341) into this renderer's skybox, on the
         device: the host draws the random tables (skybox.sky_tables), bhr_skybox_build rasterises them bit-identically
         to NumPy / Pillow, bhr_skybox_add_glow adds the Milky-Way glow and clips.  The skybox given to the constructor
-        only fixes the size."""
+        only fixes the size.  ``starless``: the same sky without its baked star blobs (stars.starless_tables) -- the nebula
+        and the glow of a sky whose stars are drawn as points (set_stars)."""
         from .skybox import STAR_PATCH_R, pillow_bilinear_coeffs, sky_tables
         t = sky_tables(self.tex_w, self.tex_h, seed, n_stars)
+        if starless:
+            from .stars import starless_tables
+            t = starless_tables(t)
         ch, cw = t["coarse_u8"].shape[:2]
         kh, bh = pillow_bilinear_coeffs(cw, self.tex_w)
         kv, bv = pillow_bilinear_coeffs(ch, self.tex_h)
@@ -605,6 +609,49 @@ class HipRenderer:
     def free_ray_map(self) -> None:
         """Release the ray map's device memory (bhr_raymap_free); close() does it too."""
         _lib.check(self._lib.bhr_raymap_free(self._ctx))
+
+    # ------------------------------------------------------------------ point stars
+    def set_stars(self, dirs, flux, max_magnification: float = 32.0, max_span_deg: float = 10.0) -> None:
+        """Set the star catalogue the frames from the ray map render as lensed points (bhr_set_stars; include/bhr.h states the
+        model, bhr_amd.stars makes catalogues): ``dirs`` (n, 3) unit vectors in the sky's convention, ``flux`` (n, 3) RGB in
+        sky value x steradian.  n = 0 removes it.  A triangle of the map whose magnification exceeds ``max_magnification`` is
+        capped at it; one whose escape directions are more than ``max_span_deg`` apart contributes nothing.  Marched frames
+        (render_async and its kin) ignore the catalogue; shutter frames from the map and supersampled maps refuse it.
+        Synchronises."""
+        from . import stars as stars_mod
+        d, f = stars_mod.check_catalog(dirs, flux)
+        rec = np.ascontiguousarray(np.concatenate([d, f], axis=1), dtype=np.float32)      # bhr_star: dir[3], flux[3]
+        par = _lib.StarParams(float(max_magnification), float(max_span_deg))
+        _lib.check(self._lib.bhr_set_stars(self._ctx, rec.ctypes.data if len(rec) else None, len(rec), C.byref(par)))
+
+    def clear_stars(self) -> None:
+        """Remove the star catalogue (bhr_set_stars with n = 0): every frame is again what it is without one."""
+        _lib.check(self._lib.bhr_set_stars(self._ctx, None, 0, None))
+
+    def stars_info(self) -> dict:
+        """The catalogue (bhr_get_stars_info): n (0: none), bins_theta, bins_phi, max_magnification, max_span_deg, device_bytes,
+        and of the last gather launched: images (deposits), capped and skipped_span (triangles)."""
+        info = _lib.StarsInfo()
+        _lib.check(self._lib.bhr_get_stars_info(self._ctx, C.byref(info)))
+        out = {name: int(getattr(info, name)) for name in ("n", "bins_theta", "bins_phi", "device_bytes", "images", "capped", "skipped_span")}
+        out["max_magnification"] = float(info.params.max_magnification)
+        out["max_span_deg"] = float(info.params.max_span_deg)
+        return out
+
+    def read_star_plane(self) -> np.ndarray:
+        """The star plane of the ray map's build view, (rows, width, 3) float32 (bhr_raymap_read, BHR_RAYMAP_STARS): the sum of
+        all star images' deposits, which a frame from the map adds to its sky sample.  Gathered now if the map or the catalogue
+        changed since the last time."""
+        out = np.empty((self.rows, self.width, 3), dtype=np.float32)
+        _lib.check(self._lib.bhr_raymap_read(self._ctx, _lib.RAYMAP_STARS, out.ctypes.data, out.nbytes))
+        return out
+
+    def stars_resources(self, turned: bool = False) -> dict:
+        """Registers, LDS bytes and scratch bytes of the star gather kernel (bhr_stars_resources); ``turned``: the one of a
+        turned view."""
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_stars_resources(1 if turned else 0, out))
+        return {"vgprs": int(out[0]), "lds_bytes": int(out[1]), "scratch_bytes": int(out[2])}
 
     def sync(self) -> None:
         _lib.check(self._lib.bhr_sync(self._ctx))

@@ -386,6 +386,69 @@ BHR_API int32_t bhr_raymap_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, 
 BHR_API int32_t bhr_raymap_read(bhr_ctx *ctx, int32_t plane, void *out, int64_t bytes);
 BHR_API int32_t bhr_raymap_get_info(bhr_ctx *ctx, bhr_raymap_info *out);
 BHR_API int32_t bhr_raymap_free(bhr_ctx *ctx);
+/* ---- point stars: a star catalogue rendered through the ray map (csrc/stars.hip, csrc/api_stars.hip; DESIGN 4 "Point stars") ----
+ * The sky texture conserves surface brightness: near the hole a baked star is smeared into a dim arc.  A real star is
+ * unresolved -- its images stay points and their flux is multiplied by the lensing magnification.  With a catalogue set, a frame
+ * from the ray map adds those images to the sky.
+ * A star is a unit direction u on the celestial sphere in the sky's own convention (theta = acos(u.z), phi = atan2(u.y, u.x), as
+ * sample_skybox takes a direction) and an RGB flux Phi in units of sky value x steradian: a patch of sky of solid angle Omega
+ * that contains the star has the mean radiance Phi / Omega.
+ * Cells and triangles.  Cell (i, j), 0 <= i < W - 1, 0 <= j < rows - 1, has the pixel centres (i, j), (i+1, j), (i, j+1),
+ * (i+1, j+1) as corners P00, P10, P01, P11 and is cut into T0 = (P00, P10, P01) and T1 = (P11, P01, P10).  For a triangle with
+ * corner pixels a, b, c: e_a, e_b, e_c are the map's stored escape directions (for a turned view turned about z exactly as the
+ * shade kernel turns them), n_a, n_b, n_c the normalized camera-side pixel directions.  A triangle is USED when all three rays
+ * escaped (status 1) and min(e_a.e_b, e_b.e_c, e_c.e_a) >= cos(max_span); otherwise it contributes nothing (the huge sky patches
+ * of high-order images and of cells that straddle the shadow or a fold, whose magnification is of the order
+ * (pixel angle / span)^2).
+ * Solid angles (Van Oosterom and Strackee, the triple product on differences so that it does not cancel):
+ *   Omega(a, b, c) = 2 atan2(|a . ((b - a) x (c - a))|, 1 + a.b + b.c + c.a),  Omega_sky = Omega(e_a, e_b, e_c),
+ *   Omega_cam = Omega(n_a, n_b, n_c).
+ * Inside test and weights: with s_c = u . (e_a x e_b), s_a = u . (e_b x e_c), s_b = u . (e_c x e_a) (evaluated as
+ * u . ((e_a - u) x (e_b - u)) and so on, the same determinants without the cancellation) the star is inside when all three are
+ * >= 0, or all three are <= 0 (a parity-flipped image: real, and kept), and u . (e_a + e_b + e_c) > 0.  The barycentric weights
+ * are w_x = s_x / (s_a + s_b + s_c); a zero sum contributes nothing.  The image lies at the weighted mean of the three corner
+ * positions, so inside the cell.
+ * Deposit: D = Phi / (2 Omega_cam) * min(Omega_cam / Omega_sky, max_magnification) -- the triangle's mean radiance over half a
+ * pixel's area, capped on the critical curve -- spread over the cell's four corner pixels with the bilinear (tent) weights of
+ * the image position.  A pixel receives star light from its four adjacent cells only; without a hole Omega_sky = Omega_cam and
+ * every star in the frame deposits Phi / (2 Omega_cam) in total.
+ * The star plane S, (rows, W, 3) f32, is the sum of all deposits: per cell and corner one running f32 sum, T0's stars then T1's,
+ * each in the catalogue's binned order; a pixel adds its four cells in the order (j-1, i-1), (j-1, i), (j, i-1), (j, i).  No
+ * floating-point atomics: two gathers of the same map and catalogue give the same bits.
+ * The frame: BG = fl((sky_sample + S) * (1 - alpha_total)) per channel -- the plane is added to the sky sample ahead of the
+ * march's own product; DISK is untouched.  BG may exceed 1; FINAL clips as ever, the HDR plane and the grade carry the rest.  A
+ * pixel on the map's overflow list is stored by the strict fix kernel as without a catalogue and receives NO star light.
+ * bhr_set_stars copies the catalogue (directions normalized in binary64 and rounded once), sorts it into an equirectangular grid
+ * of bins and uploads it; n = 0 removes it; p = NULL means max_magnification 32 and max_span_deg 10.  It synchronises.
+ *   BHR_ERR_INVALID, the context unchanged: ctx NULL (or stars NULL with n > 0); n < 0 or n > 2^22; a direction that is
+ *     non-finite or whose norm is not within 1e-3 of 1; a negative or non-finite flux; max_magnification outside [1, 1e6];
+ *     max_span_deg outside (0, 60]; a row-block context.
+ *   BHR_ERR_NOMEM: with everything freed -- the context then has no catalogue.
+ * With a catalogue set, bhr_raymap_render and bhr_raymap_render_view launch the gather kernel and the shade kernel that adds the
+ * plane.  The plane of the un-turned build view is computed once per (map, catalogue) and reused; the plane of a turned view is
+ * computed per frame into storage of the frame slot.  A view at angle 0 uses the cached plane and is bhr_raymap_render's frame
+ * bit for bit.  Refused with BHR_ERR_STATE naming the stars, nothing launched, map and catalogue kept:
+ * bhr_raymap_render_shutter, and any render from (or plane read of) a map with supersample > 1.  Without a catalogue every call is exactly what it
+ * is without this section.  bhr_render, bhr_render_shutter, bhr_render_observer and the Kerr march IGNORE the catalogue.
+ * bhr_raymap_read(ctx, BHR_RAYMAP_STARS, out, rows * W * 12) returns the build view's plane, computing it if needed;
+ * BHR_ERR_STATE without a map or without a catalogue.
+ * bhr_get_stars_info: the catalogue (n = 0: none) and the counts of the last gather launched -- images: deposits (star, used
+ * triangle); capped: used triangles whose magnification exceeded the cap; skipped_span: triangles of three escaped rays dropped
+ * by the span rule.  bhr_stars_resources: VGPRs, LDS bytes and scratch bytes of the gather kernel (rot: the turned one). */
+#define BHR_RAYMAP_STARS 5
+typedef struct { float dir[3]; float flux[3]; } bhr_star;
+typedef struct { float max_magnification; float max_span_deg; } bhr_star_params;
+typedef struct {
+    int32_t n;                          /* stars in the catalogue; 0: none */
+    int32_t bins_theta, bins_phi;       /* the grid of bins */
+    int32_t reserved;
+    bhr_star_params params;
+    int64_t device_bytes;
+    int64_t images, capped, skipped_span;   /* of the last gather */
+} bhr_stars_info;
+BHR_API int32_t bhr_set_stars(bhr_ctx *ctx, const bhr_star *stars, int32_t n, const bhr_star_params *p);
+BHR_API int32_t bhr_get_stars_info(bhr_ctx *ctx, bhr_stars_info *out);
+BHR_API int32_t bhr_stars_resources(int32_t rot, int32_t out[3]);
 /* image_field/disk_layer_field/blur_field .to_numpy() and the final image,
  * for the context's rows: (row1-row0, width, 3) f32.  Synchronises. */
 BHR_API int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out);
