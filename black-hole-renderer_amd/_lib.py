@@ -34,6 +34,7 @@ SYMBOLS = (
     "bhr_fill_comp_slice", "bhr_set_compose_stats", "bhr_compose_texture", "bhr_eval_noise", "bhr_render", "bhr_render_shutter",
     "bhr_set_spin", "bhr_kerr_resources", "bhr_set_redshift", "bhr_kerr_redshift_resources",
     "bhr_render_observer", "bhr_observer_resources",
+    "bhr_render_projected", "bhr_projected_resources",
     "bhr_raymap_build", "bhr_raymap_render", "bhr_raymap_render_view", "bhr_raymap_render_shutter", "bhr_raymap_read", "bhr_raymap_get_info", "bhr_raymap_free",
     "bhr_set_stars", "bhr_get_stars_info", "bhr_stars_resources",
     "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_read_final_u16", "bhr_set_dither", "bhr_dither_matrix", "bhr_set_grade", "bhr_grade_frame", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
@@ -58,6 +59,14 @@ class Config(C.Structure):
 class Observer(C.Structure):
     """bhr_observer: the velocity of a moving camera (bhr_render_observer) and whether the sky takes its Doppler factor."""
     _fields_ = [("beta", C.c_float * 3), ("sky_shift", C.c_int32)]
+
+
+PROJ_EQUIRECT, PROJ_FISHEYE = 1, 2
+
+
+class Projection(C.Structure):
+    """bhr_projection: an equirectangular or fisheye camera (bhr_render_projected) and its field of view in degrees."""
+    _fields_ = [("kind", C.c_int32), ("fov_h_deg", C.c_float), ("fov_v_deg", C.c_float), ("reserved", C.c_int32)]
 
 
 class Camera(C.Structure):
@@ -185,6 +194,8 @@ def load() -> C.CDLL:
     lib.bhr_kerr_redshift_resources.argtypes = [I32, I32, C.POINTER(C.c_int32)]
     lib.bhr_render_observer.argtypes = [P, C.POINTER(Camera), C.POINTER(Observer), C.c_uint32]
     lib.bhr_observer_resources.argtypes = [I32, C.POINTER(C.c_int32)]
+    lib.bhr_render_projected.argtypes = [P, C.POINTER(Camera), C.POINTER(Projection), C.POINTER(Observer), C.c_uint32]
+    lib.bhr_projected_resources.argtypes = [I32, C.POINTER(C.c_int32)]
     lib.bhr_set_option.argtypes = [P, C.c_char_p, C.c_double]
     lib.bhr_debug_read.argtypes = [P, I32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
     lib.bhr_lens_flare.argtypes = [P]

@@ -5,7 +5,8 @@ refused -- this build has no CPU path), ``-r 8k``, ``--gpus N`` (row-block tilin
 inside one process; for ``--video`` launch one process per GPU with torchrun and frames are sharded
 round-robin by RANK / WORLD_SIZE), ``--disk_model`` (the analytic Disk V2 sources of the march kernel), ``--observer`` /
 ``--observer_velocity`` (a camera that moves: aberration and Doppler shift), ``--stars point`` (the procedural sky's stars as a
-catalogue of lensed points rendered through a ray map).
+catalogue of lensed points rendered through a ray map), ``--projection`` / ``--projection_fov`` (equirectangular 360-degree
+frames and fisheye dome masters instead of the pinhole camera).
 """
 from __future__ import annotations
 
@@ -24,7 +25,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     p = argparse.ArgumentParser(description="Schwarzschild black-hole ray tracer (MI355X / HIP)")
     p.add_argument("--pov", type=float, nargs=3, default=[6, 0, 0.5], metavar=("X", "Y", "Z"),
                    help="camera position (default: 6 0 0.5)")
-    p.add_argument("--fov", type=float, default=90, help="field of view 0-180 deg (default: 90)")
+    p.add_argument("--fov", type=float, default=None, help="field of view 0-180 deg (default: 90)")
     p.add_argument("--resolution", "-r", type=str, default="fhd", choices=list(RESOLUTIONS),
                    help="8k/4k/fhd/hd/sd (default: fhd)")
     p.add_argument("--texture", "-t", type=str, default=None, help="skybox texture path")
@@ -95,6 +96,22 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--infall_to", type=float, default=None, metavar="R",
                    help="--observer infall --video: the camera falls radially from |pov| to R >= 1.05 along --pov, the frames "
                         "uniform in its proper time; not with --orbit")
+    p.add_argument("--projection", type=str, default="perspective", choices=["perspective", "equirect", "fisheye"],
+                   help="the camera's projection.  perspective (default): the pinhole camera of --fov.  equirect: the equirectangular "
+                        "panorama, 360 x 180 degrees by default -- the whole sky, the second image of what lies behind the camera "
+                        "included; the frame is the resolution's width x width / 2 (fhd: 1920 x 960).  fisheye: the equidistant "
+                        "fisheye, 180 degrees by default -- a dome master; the frame is height x height (fhd: 1080 x 1080), blank "
+                        "outside the image circle.  Both look along the camera's forward axis (at the hole), are marched by a strict "
+                        "kernel of their own whatever --math says, and work with --supersample, --disk_tilt, --lens_flare, the grade, "
+                        "HDR, --video [--orbit] and --observer.  A full-sphere equirect --video that this program muxes itself "
+                        "(--video_codec mjpeg, or PNG frames in MP4 where no H.264 encoder exists) carries the Spherical Video V1 "
+                        "metadata that makes players open it as a 360-degree video; the ffmpeg and pyav routes write none.  The "
+                        "bloom does not wrap at the +-180 degree seam.  Not with --fov, --spin, --redshift exact, --anti_alias "
+                        "lod_radius, --disk_model v2 / v2_volume, --supersample_threshold, --gpus > 1, --shutter, the ray-map flags, "
+                        "--passes or --stars point")
+    p.add_argument("--projection_fov", type=float, nargs="+", default=None, metavar=("A", "B"),
+                   help="--projection equirect: the horizontal and vertical span in degrees, A in (0, 360] and B in (0, 180] (default: "
+                        "360 180); --projection fisheye: the full angle of the image circle, A in (0, 360] (default: 180)")
     p.add_argument("--video_stream", type=str, default="auto", choices=["auto", "y4m", "off"],
                    help="--video: also hand the frames to the encoder as a yuv420p stream converted on the device "
                         "(auto: pipe into ffmpeg when it is on PATH; y4m: write <output stem>.y4m; off: PNG frames only)")
@@ -197,6 +214,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--disk_rotation_speed", type=float, default=0.1, help="disk rotation speed (default: 0.1)")
     p.add_argument("--keyframes_count", type=int, default=10, help="[deprecated] ignored")
     args = p.parse_args(argv)
+    fov_given = args.fov is not None                # --projection refuses an explicit --fov; the default is 90 as ever
+    args.fov = 90 if args.fov is None else args.fov
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
     if args.spin != 0 or args.redshift == "exact":
@@ -368,6 +387,39 @@ def parse_args(argv=None) -> argparse.Namespace:
             p.error(f"--star_gain must be greater than 0, got {args.star_gain}")
         if not 1.0 <= args.star_max_magnification <= 1e6:
             p.error(f"--star_max_magnification must be between 1 and 1e6, got {args.star_max_magnification}")
+    # a projection, behind every refusal above: a line that was refused without --projection is refused with the same words
+    if args.projection == "perspective":
+        if args.projection_fov is not None:
+            p.error("--projection_fov needs --projection equirect or fisheye: it is the field of view of that camera (the pinhole takes --fov)")
+    else:
+        who = f"--projection {args.projection}"
+        if fov_given:
+            p.error(f"{who} does not combine with --fov: that is the pinhole camera's field of view (--projection_fov is this one's)")
+        if args.spin != 0:
+            p.error(f"{who} does not combine with --spin: the projected march is Schwarzschild's")
+        if args.redshift == "exact":
+            p.error(f"{who} does not combine with --redshift exact: that is the Kerr march's")
+        if args.anti_alias != "disabled":
+            p.error(f"{who} does not combine with --anti_alias lod_radius: the projected march has no ray differentials")
+        if args.disk_model != "texture":
+            p.error(f"{who} does not combine with --disk_model other than texture: the projected march shades the disk texture")
+        if args.supersample_threshold is not None:
+            p.error(f"{who} does not combine with --supersample_threshold: the projected march has no refinement kernels (plain --supersample works)")
+        if args.gpus != 1:
+            p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march the pinhole camera")
+        if args.shutter > 0:
+            p.error(f"{who} does not combine with --shutter: shutter frames march the pinhole camera")
+        for flag, on in (("--ray_map", args.ray_map), ("--orbit_map", args.orbit_map), ("--shutter_map", args.shutter_map),
+                         ("--passes", args.passes is not None)):
+            if on:
+                p.error(f"{who} does not combine with {flag}: a ray map holds the rays of the pinhole camera")
+        if args.stars == "point":
+            p.error(f"{who} does not combine with --stars point: point stars are rendered through a ray map of the pinhole camera")
+        try:
+            from .projection import check
+            check(args.projection, args.projection_fov)
+        except ValueError as e:
+            p.error(f"{who} --projection_fov: {e}")
     # --exposure, --white, --transfer and --hdr_output without --tonemap mean --tonemap clip
     if args.tonemap is None and any(v is not None for v in (args.exposure, args.white, args.transfer, args.hdr_output)):
         args.tonemap = "clip"
@@ -390,6 +442,14 @@ def stars_from_args(args):
     if getattr(args, "stars", "texture") != "point":
         return None
     return dict(gain=args.star_gain, max_magnification=args.star_max_magnification)
+
+
+def projection_from_args(args) -> dict:
+    """The projection of a command line as drivers.render_image / render_video take it: {} with the pinhole camera."""
+    if getattr(args, "projection", "perspective") == "perspective":
+        return {}
+    fov = getattr(args, "projection_fov", None)
+    return dict(projection=args.projection, projection_fov=None if fov is None else tuple(fov))
 
 
 def observer_beta(args):
@@ -509,11 +569,18 @@ def main(argv=None) -> int:
     sky = args.observer_sky == "shift"
     # ... and the point stars
     stars_kw = {"stars": stars_from_args(args)} if args.stars == "point" else {}
+    # ... and a projection, whose frame size follows from the resolution (bhr_amd.projection.frame_size)
+    proj_kw = projection_from_args(args)
+    if proj_kw:
+        from .projection import frame_size
+        width, height = frame_size(args.projection, width, height)
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))
         world = int(os.environ.get("WORLD_SIZE", "1"))
         local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+        if proj_kw:                                 # several ranks are refused before a device is touched
+            drivers.check_projection(world=world, **proj_kw)
         if "BHR_FORCE_DEVICE" in os.environ:        # rehearsal: several ranks sharing one card
             local_rank = int(os.environ["BHR_FORCE_DEVICE"])
         elif world > 1:                             # a launcher that shows every rank only its own GPU: ordinal 0
@@ -538,7 +605,7 @@ def main(argv=None) -> int:
                              shutter_map=args.shutter_map, map_supersample=args.map_supersample, video_hdr=args.video_hdr,
                              hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure, **stars_kw,
                              **(dict(observer=args.observer, observer_velocity=args.observer_velocity, observer_sky=sky,
-                                     infall_to=args.infall_to) if moving else {}))
+                                     infall_to=args.infall_to) if moving else {}), **proj_kw)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -563,6 +630,6 @@ def main(argv=None) -> int:
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
         grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw, **stars_kw,
-        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}))
+        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

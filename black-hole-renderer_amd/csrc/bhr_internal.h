@@ -134,6 +134,13 @@ struct BhrObserverMarchArgs : BhrMarchArgs {
     float obs_gamma, obs_g2;
     int32_t obs_sky_shift;
 };
+// The argument block of the projected object's kernels (march_projected.hip; bhr_render_projected): the observer's block with the
+// projection behind it -- its kind (BHR_PROJ_*) and its spans in radians, binary64 on the host rounded once: the equirectangular
+// frame's horizontal and vertical span, the fisheye's HALF angle in span_h (ray_projected.h).
+struct BhrProjectedMarchArgs : BhrObserverMarchArgs {
+    int32_t proj_kind;
+    float span_h, span_v;
+};
 
 // A partial march launch: the tiles of `d_list` only.  bhr_launch_march_hybrid builds one for each of its launches (strict
 // list, fast list, fix list and the empty parts that bracket them) and passes it to bhr_launch_march (null: the whole block).
@@ -159,6 +166,7 @@ struct bhr_march_call {
     int32_t ss;              // supersampling factor of the frame being marched
     bool keep_start;         // a later sample of a shutter frame (bhr_render_shutter): the march-start event stays the first sample's
     const bhr_observer *observer = nullptr;   // bhr_render_observer: the frame is marched by the observer object for this moving camera
+    const bhr_projection *projection = nullptr;   // bhr_render_projected (observer is set too): the projected object marches it under this projection
 };
 
 // The march kernels by what they do; each march object returns its own instantiation of a name (or null) from
@@ -671,6 +679,7 @@ const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.hip -> march_strict_ilp.o
 const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_raymap.hip -> march_raymap.o
 const void *bhr_march_kernel_observer(bhr_march_kernel k, int32_t diff, int32_t ss);   // march_observer.hip -> march_observer.o (BHR_MK_TILE, diff 0 only)
+const void *bhr_march_kernel_projected(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_projected.hip -> march_projected.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
 

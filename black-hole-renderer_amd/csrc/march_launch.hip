@@ -1,8 +1,9 @@
 // march_launch.hip -- the host half of the ray march: every march launch goes through bhr_launch_march.
 //
-// The march's device code is six objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
-// with the ILP-first scheduler, march_raymap.hip, march_kerr.hip, march_observer.hip; the layout: march_device.h); each object hands
-// its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr / _observer).  This file resolves the
+// The march's device code is seven objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
+// with the ILP-first scheduler, march_raymap.hip, march_kerr.hip, march_observer.hip, march_projected.hip; the layout: march_device.h);
+// each object hands its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr / _observer /
+// _projected).  This file resolves the
 // arithmetic, builds the kernel arguments, keeps the tile order, the ray-step counters and the timing events, and picks
 // the kernel of a launch (march_kernel).  What a launch works from is in its arguments -- the caller's bhr_march_call
 // (camera, flags, stream, timing slot, end-event policy, supersampling factor) and, for one list of a hybrid march, a
@@ -67,6 +68,7 @@ float fast_sqrt(float s) {
 // The kernel of a launch and its grid (fn null: the part only records its bracket events).
 //
 //   arithmetic     request                                              kernel (object)
+//   any            a projection (bhr_render_projected)                  march_projected_kernel / march_projected_ss_kernel (projected)
 //   any            a moving observer (bhr_render_observer)              march_observer_kernel / march_observer_ss_kernel (observer)
 //   any            a spin is set (bhr_set_spin), whole block            march_kerr_kernel / march_kerr_ss_kernel (kerr)
 //   any            ... and the exact redshift (bhr_set_redshift)         march_kerr_exact_kernel / march_kerr_exact_ss_kernel (kerr)
@@ -96,7 +98,7 @@ struct MarchKernel {
     dim3 grid;
     size_t lds = 0;
 };
-MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *part, int math, uint32_t flags, bool diff, bool observer) {
+MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *part, int math, uint32_t flags, bool diff, bool observer, bool projected) {
     MarchKernel k;
     k.grid = dim3((a.n_list + 3) / 4);
     const bool persistent = (flags & BHR_PERSISTENT) != 0;
@@ -104,7 +106,8 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
     const auto own = math == BHR_MATH_FAST ? bhr_march_kernel_fast : bhr_march_kernel_strict;
     // the moving observer (bhr_render_observer): the observer object's march, on the same terms as the spinning hole's below
     if (observer) {
-        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = bhr_march_kernel_observer(BHR_MK_TILE, diff, ss);
+        // (a projection, bhr_render_projected, is an observer's frame marched by the projected object)
+        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = (projected ? bhr_march_kernel_projected : bhr_march_kernel_observer)(BHR_MK_TILE, diff, ss);
         return k;
     }
     // the spinning hole: one arithmetic, one schedule, no lists (what has no Kerr form was refused before anything was launched)
@@ -371,7 +374,7 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(bhr_slot(ctx).d_queue, 0, sizeof(unsigned int), stream));
     // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
     if (first_part && !call.keep_start) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, slot), stream));
-    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags), call.observer != nullptr);
+    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags), call.observer != nullptr, call.projection != nullptr);
     if (!k.fn && !(part && part->n <= 0 && part->repair != 2))
         return bhr_fail(BHR_ERR_STATE, "bhr_render: no march kernel for this launch (supersampling %d, flags %u)", call.ss, flags);
     if (k.fn) {
@@ -379,7 +382,9 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
         void *args[] = {&a, &refill_below};                    // (the second argument is the persistent kernel's alone)
         // the moving observer: the finished march block with the camera's velocity behind it, gamma and gamma^2 / (gamma + 1)
         // in binary64, each rounded once (the observer object's kernels take this block; nobody else reads it)
-        BhrObserverMarchArgs oa;
+        // (a projection: its kind and its spans in radians behind that, binary64 rounded once; the projected object's kernels take
+        // the longer block)
+        BhrProjectedMarchArgs oa;
         if (call.observer) {
             static_cast<BhrMarchArgs &>(oa) = a;
             const float *b = call.observer->beta;
@@ -388,6 +393,14 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
             oa.obs_gamma = (float)gamma;
             oa.obs_g2 = (float)(gamma * gamma / (gamma + 1.0));
             oa.obs_sky_shift = call.observer->sky_shift ? 1 : 0;
+            oa.proj_kind = 0;
+            oa.span_h = oa.span_v = 0.0f;
+            if (const bhr_projection *pr = call.projection) {
+                const double rad = 3.14159265358979323846 / 180.0;
+                oa.proj_kind = pr->kind;
+                oa.span_h = pr->kind == BHR_PROJ_FISHEYE ? (float)((double)pr->fov_h_deg * rad / 2.0) : (float)((double)pr->fov_h_deg * rad);
+                oa.span_v = pr->kind == BHR_PROJ_FISHEYE ? 0.0f : (float)((double)pr->fov_v_deg * rad);
+            }
             args[0] = &oa;
         }
         (void)hipLaunchKernel(k.fn, k.grid, dim3(256), args, k.lds, stream);

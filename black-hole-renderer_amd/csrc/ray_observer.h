@@ -1,4 +1,5 @@
-// ray_observer.h -- the observer Ray of the march (march_observer.o; see march_device.h): the strict Ray seen by a camera that moves.
+// ray_observer.h -- the observer Ray of the march (march_observer.o, and under ray_projected.h march_projected.o; see
+// march_device.h): the strict Ray seen by a camera that moves.
 //
 // The camera moves with velocity beta (units of c) as the static observer at its position measures it; that observer's local
 // frame is identified with the coordinate axes, as pixel_ray does for the camera that stands still (DESIGN.md "Observer").  A
@@ -37,15 +38,19 @@ __device__ __forceinline__ V3 observer_sky(V3 c, float D) {
 }
 
 template <bool DIFF, int SRC = 0>
-struct Ray : StrictRay<DIFF, SRC> {
+struct ObserverRay : StrictRay<DIFF, SRC> {
     static_assert(!DIFF && SRC == 0, "the observer march has no ray differentials and the texture source only");
     typedef StrictRay<DIFF, SRC> Base;
     float dopp;    // D of the lane's ray
 
     __device__ __forceinline__ void init(const BhrMarchArgs &a, int i, int j_local) {
-        const BhrObserverMarchArgs &o = observer(a);
         V3 unused_x, unused_y;
-        const V3 np = pixel_ray<false>(a, i, j_local, unused_x, unused_y);
+        init_aberrated(a, pixel_ray<false>(a, i, j_local, unused_x, unused_y), i, j_local);
+    }
+    // the ray of pixel (i, j_local), whose direction in the moving camera's frame is np (ray_projected.h: a projection's is not
+    // pixel_ray's)
+    __device__ __forceinline__ void init_aberrated(const BhrMarchArgs &a, const V3 np, int i, int j_local) {
+        const BhrObserverMarchArgs &o = observer(a);
         const V3 b = ld3(o.obs_beta);
         const float bn = dot(b, np);
         dopp = 1.0f / (o.obs_gamma * (1.0f - bn));
@@ -82,5 +87,12 @@ struct Ray : StrictRay<DIFF, SRC> {
         store_pixel(a, i, j, a.width, bk, dk);
     }
 };
+
+// The Ray the schedules march: the observer's itself, unless the Ray header that included this file derives its own from it
+// (ray_projected.h).
+#ifndef BHR_RAY_PROJECTED
+template <bool DIFF, int SRC = 0>
+using Ray = ObserverRay<DIFF, SRC>;
+#endif
 
 }  // namespace

@@ -62,12 +62,14 @@ int32_t post_on_slot(bhr_ctx *ctx, uint32_t flags, int k, int ring) {
 }
 
 // obs: the frame of a moving observer (bhr_render_observer), marched by the observer object; null: bhr_render's
-int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, const bhr_observer *obs = nullptr) {
+// proj (with obs): that frame under a projection (bhr_render_projected), marched by the projected object
+int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, const bhr_observer *obs = nullptr,
+                       const bhr_projection *proj = nullptr) {
     bhr_frame_slot &f = ctx->slots[k];
     BHR_TRY(bhr_frame_begin(ctx, flags));
     // an adaptively supersampled frame: the k = 1 march, then detect + refinement inside the same march bracket
     const bool adaptive = ctx->ada_k > 1;
-    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss, /* keep_start */ false, obs};
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss, /* keep_start */ false, obs, proj};
     *fm = {call.ss, 1, adaptive};
     BHR_TRY(bhr_launch_march(ctx, call));              // records the ring slot's march events
     if (adaptive) BHR_TRY(bhr_launch_adaptive(ctx, call));
@@ -235,11 +237,9 @@ int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     return frame_on_next_slot(ctx, flags, exclusive, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm); });
 }
 
-// One frame as a moving camera sees it (include/bhr.h).  Everything that can refuse does so before the frame takes a slot; like
-// bhr_render_shutter the frame neither triggers nor counts towards the calibration of slot 1's stream.
-int32_t bhr_render_observer(bhr_ctx *ctx, const bhr_camera *cam, const bhr_observer *obs, uint32_t flags) {
-    const char *who = "bhr_render_observer";
-    if (!ctx || !cam || !obs) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+// What bhr_render_observer and bhr_render_projected refuse alike, for `what` ("a moving observer", "a projection"): the velocity,
+// the flags and the state of the context that the observer march has no form for.
+static int32_t observer_frame_check(const bhr_ctx *ctx, const bhr_observer *obs, uint32_t flags, const char *who, const char *what) {
     const double b2 = (double)obs->beta[0] * obs->beta[0] + (double)obs->beta[1] * obs->beta[1] + (double)obs->beta[2] * obs->beta[2];
     if (!(b2 <= 0.995 * 0.995))       // a NaN fails the comparison too
         return bhr_fail(BHR_ERR_INVALID, "%s: observer velocity (%g, %g, %g): |beta| = %g, at most 0.995 and no NaN", who, (double)obs->beta[0],
@@ -247,19 +247,47 @@ int32_t bhr_render_observer(bhr_ctx *ctx, const bhr_camera *cam, const bhr_obser
     if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
         return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
     if (ctx->cfg.anti_alias != 0)
-        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with anti_alias = 1: the differential seeds under aberration are not implemented", who);
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with anti_alias = 1: the differential seeds under aberration are not implemented", who, what);
     if (ctx->disk_source != BHR_DISK_TEXTURE)
-        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with a Disk V2 source (%d): the observer march shades the disk texture", who, ctx->disk_source);
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with a Disk V2 source (%d): the observer march shades the disk texture", who, what, ctx->disk_source);
     if (ctx->ada_k > 1)
-        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with adaptive supersampling (factor %d): the observer march has no refinement kernels; use bhr_set_supersample", who, ctx->ada_k);
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with adaptive supersampling (factor %d): the observer march has no refinement kernels; use bhr_set_supersample", who, what, ctx->ada_k);
     if (ctx->kerr_on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
-        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with the exact redshift (bhr_set_redshift): its observer is static", who);
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with the exact redshift (bhr_set_redshift): its observer is static", who, what);
     if (ctx->kerr_on)
-        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer with a spin set (bhr_set_spin, a / M = %g): the observer march is Schwarzschild's", who, (double)ctx->kerr_spin);
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with a spin set (bhr_set_spin, a / M = %g): the observer march is Schwarzschild's", who, what, (double)ctx->kerr_spin);
     if (ctx->rows != ctx->cfg.height)
-        return bhr_fail(BHR_ERR_INVALID, "%s: a moving observer on a row-block context (rows %d of %d): needs a whole-frame context", who, ctx->rows, ctx->cfg.height);
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s on a row-block context (rows %d of %d): needs a whole-frame context", who, what, ctx->rows, ctx->cfg.height);
+    return BHR_OK;
+}
+
+// One frame as a moving camera sees it (include/bhr.h).  Everything that can refuse does so before the frame takes a slot; like
+// bhr_render_shutter the frame neither triggers nor counts towards the calibration of slot 1's stream.
+int32_t bhr_render_observer(bhr_ctx *ctx, const bhr_camera *cam, const bhr_observer *obs, uint32_t flags) {
+    const char *who = "bhr_render_observer";
+    if (!ctx || !cam || !obs) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    BHR_TRY(observer_frame_check(ctx, obs, flags, who, "a moving observer"));
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, obs); });
+}
+
+// One frame under an equirectangular or fisheye projection, from a camera that may move (include/bhr.h): bhr_render_observer's
+// frame marched by the projected object.  obs null: the camera stands still, which is the observer at rest with a plain sky.
+int32_t bhr_render_projected(bhr_ctx *ctx, const bhr_camera *cam, const bhr_projection *proj, const bhr_observer *obs, uint32_t flags) {
+    const char *who = "bhr_render_projected";
+    if (!ctx || !cam || !proj) return bhr_fail(BHR_ERR_INVALID, "%s: null argument (ctx, cam and proj are needed)", who);
+    if (proj->kind != BHR_PROJ_EQUIRECT && proj->kind != BHR_PROJ_FISHEYE)
+        return bhr_fail(BHR_ERR_INVALID, "%s: projection kind %d (BHR_PROJ_EQUIRECT or BHR_PROJ_FISHEYE)", who, proj->kind);
+    const bool eq = proj->kind == BHR_PROJ_EQUIRECT;
+    if (!(proj->fov_h_deg > 0.0f && proj->fov_h_deg <= 360.0f))       // a NaN fails the comparison too
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s projection with fov_h_deg = %g: in (0, 360] and no NaN", who, eq ? "equirectangular" : "fisheye", (double)proj->fov_h_deg);
+    if (eq && !(proj->fov_v_deg > 0.0f && proj->fov_v_deg <= 180.0f))
+        return bhr_fail(BHR_ERR_INVALID, "%s: equirectangular projection with fov_v_deg = %g: in (0, 180] and no NaN", who, (double)proj->fov_v_deg);
+    static const bhr_observer at_rest = {{0.0f, 0.0f, 0.0f}, 0};
+    const bhr_observer o = obs ? *obs : at_rest;
+    BHR_TRY(observer_frame_check(ctx, &o, flags, who, "a projection"));
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, &o, proj); });
 }
 
 // One frame as the mean of n marches (include/bhr.h).  One frame of one frame slot: the next frame takes the other slot.

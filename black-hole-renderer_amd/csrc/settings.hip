@@ -26,9 +26,10 @@ int32_t kerr_state_check(const bhr_ctx *ctx, uint32_t flags, const char *who, do
 
 // {VGPRs, LDS bytes, scratch bytes per lane} of a march kernel of the Kerr object, or of the observer object (ss: its supersampled
 // twin).  No context: host + hipFuncGetAttributes.
-int32_t kerr_kernel_resources(const char *who, bhr_march_kernel k, int32_t ss, int32_t out[3], bool observer = false) {
+int32_t kerr_kernel_resources(const char *who, bhr_march_kernel k, int32_t ss, int32_t out[3], int observer = 0) {
     if (!out) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
-    const void *f = observer ? bhr_march_kernel_observer(k, 0, ss ? 1 : 0) : bhr_march_kernel_kerr(k, 0, ss ? 1 : 0);
+    const void *f = observer == 2 ? bhr_march_kernel_projected(k, 0, ss ? 1 : 0)   // 1: the observer object, 2: the projected object
+                    : observer  ? bhr_march_kernel_observer(k, 0, ss ? 1 : 0) : bhr_march_kernel_kerr(k, 0, ss ? 1 : 0);
     if (!f) return bhr_fail(BHR_ERR_STATE, "%s: no such march kernel in this library", who);
     hipFuncAttributes at;
     BHR_HIP(hipFuncGetAttributes(&at, f));
@@ -137,7 +138,8 @@ int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode) {
     return BHR_OK;
 }
 
-int32_t bhr_observer_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_observer_resources", BHR_MK_TILE, ss, out, true); }
+int32_t bhr_observer_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_observer_resources", BHR_MK_TILE, ss, out, 1); }
+int32_t bhr_projected_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_projected_resources", BHR_MK_TILE, ss, out, 2); }
 
 int32_t bhr_kerr_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_kerr_resources", BHR_MK_TILE, ss, out); }
 // ... of the kernels of a redshift mode (bhr_set_redshift)

@@ -231,7 +231,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  supersample: int = 1, supersample_threshold: Optional[float] = None, bit_depth: int = 8,
                  dither: str = "none", grade: Optional[dict] = None, hdr_path: Optional[str] = None,
                  passes_path: Optional[str] = None, spin: float = 0.0, redshift: str = "model",
-                 observer=None, observer_sky: bool = True, stars: Optional[dict] = None) -> np.ndarray:
+                 observer=None, observer_sky: bool = True, stars: Optional[dict] = None,
+                 projection: Optional[str] = None, projection_fov=None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -249,8 +250,13 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     whether the sky takes its Doppler factor; one device, the texture source, no anti-aliasing, no spin, no adaptive
     supersampling, no passes.  ``stars``: None, or dict(gain=, max_magnification=) -- point stars (check_stars): the sky is built
     without its baked stars, the view's ray map is built and the frame is shaded from it with the star catalogue, by the strict
-    arithmetic whatever ``math`` says."""
+    arithmetic whatever ``math`` says.  ``projection``: "equirect" or "fisheye" with ``projection_fov`` in degrees
+    (HipRenderer.render_async; bhr_amd.projection): the width x height frame through that camera instead of the pinhole, ``fov``
+    unused (bhr_amd.projection.frame_size is the command line's size rule); combines with ``observer`` and takes what it takes
+    (check_projection)."""
     check_depth_and_dither(bit_depth, dither)
+    check_projection(projection, projection_fov, anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold,
+                     gpus=gpus, spin=spin, redshift=redshift, passes=passes_path is not None, stars=stars is not None)
     stars = check_stars(stars, skybox_path=skybox_path, supersample=supersample, spin=spin, redshift=redshift, gpus=gpus,
                         disk_model=disk_model, observer=observer)
     check_observer(observer, anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus,
@@ -300,7 +306,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         print(f"Point stars: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
               f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
     else:
-        img = renderer.render(cam_pos, fov, frame=0, **({} if observer is None else {"observer": observer, "observer_sky": observer_sky}))
+        img = renderer.render(cam_pos, fov, frame=0, **({} if observer is None else {"observer": observer, "observer_sky": observer_sky}),
+                              **({} if projection is None else {"projection": projection, "projection_fov": projection_fov}))
     if hdr_path is not None:
         save_hdr(renderer.read_hdr(), hdr_path)
     c = renderer.counters()
@@ -346,6 +353,40 @@ def check_observer(observer, anti_alias="disabled", disk_model: str = "texture",
         raise ValueError("a moving observer does not combine with shutter: shutter frames march the camera that stands still")
     if maps:
         raise ValueError("a moving observer does not combine with ray_map, orbit_map or shutter_map: a ray map holds the rays of the camera that stands still")
+
+
+def check_projection(projection, projection_fov=None, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None,
+                     gpus: int = 1, world: int = 1, spin: float = 0.0, redshift: str = "model", passes: bool = False, shutter: float = 0.0,
+                     maps: bool = False, stars: bool = False):
+    """What a frame under a projection takes (bhr_amd.projection.check: "equirect" or "fisheye" and its angles): one device, the
+    texture disk source, the Schwarzschild hole with the model redshift, marched frames without anti-aliasing, adaptive
+    supersampling, shutter, ray map or point stars -- the observer march's terms.  Raises ValueError, naming the combination,
+    before any device work; -> (kind, fov_h, fov_v), or None without a projection (``projection_fov`` alone is an error)."""
+    if projection is None:
+        if projection_fov is not None:
+            raise ValueError("projection_fov needs a projection: it is the field of view of an equirect or fisheye camera")
+        return None
+    from .projection import check
+    out = check(projection, projection_fov)
+    if spin != 0 or redshift != "model":
+        raise ValueError("a projection does not combine with a spin or the exact redshift: the projected march is Schwarzschild's, with the model redshift")
+    if anti_alias not in ("disabled", 0, False, None):
+        raise ValueError("a projection does not combine with anti_alias: the projected march has no ray differentials")
+    if disk_model != "texture":
+        raise ValueError("a projection does not combine with disk_model v2 / v2_volume: the projected march shades the disk texture")
+    if supersample_threshold is not None:
+        raise ValueError("a projection does not combine with supersample_threshold: the projected march has no refinement kernels (plain supersample works)")
+    if gpus != 1 or world != 1:
+        raise ValueError("a projection renders on one GPU: row-block tiles and frame-sharded ranks march the pinhole camera")
+    if shutter > 0:
+        raise ValueError("a projection does not combine with shutter: shutter frames march the pinhole camera")
+    if maps:
+        raise ValueError("a projection does not combine with ray_map, orbit_map or shutter_map: a ray map holds the rays of the pinhole camera")
+    if passes:
+        raise ValueError("a projection writes no passes: a ray map holds the rays of the pinhole camera")
+    if stars:
+        raise ValueError("a projection does not combine with point stars: they are rendered through a ray map of the pinhole camera")
+    return out
 
 
 def check_passes(passes_path, gpus: int = 1, supersample: int = 1, disk_model: str = "texture") -> None:
@@ -442,14 +483,17 @@ def _frames_dir(output_path: str) -> str:
 VIDEO_CODECS = ("auto", "mjpeg")
 
 
-def assemble_video(temp_dir: str, n_frames: int, fps: int, output_path: str, codec: str = "auto") -> bool:
+def assemble_video(temp_dir: str, n_frames: int, fps: int, output_path: str, codec: str = "auto", spherical: bool = False) -> bool:
     """Frames -> MP4.  ``codec="mjpeg"``: the frame_%04d.jpg files of render_video(video_codec="mjpeg") become the samples
     of a Motion-JPEG track as they are (mp4.write_jpeg_mp4, object type 0x6C); nothing is re-coded and no external
     encoder is looked for.  ``codec="auto"``:
     PNG frames -> MP4 (render.py:4497-4503: libx264 through imageio's pyav plugin).  In order of preference: imageio +
     pyav as the reference; an ``ffmpeg`` binary on PATH (same codec, same pixel format); failing both, the frames
     themselves muxed into an MP4 as PNG-coded samples (mp4.write_png_mp4: lossless, plays in ffmpeg / mpv / VLC, and is one
-    ffmpeg call away from the H.264 file).  Returns False only when a frame is missing."""
+    ffmpeg call away from the H.264 file).  Returns False only when a frame is missing.  ``spherical``: the frames are
+    full-sphere equirectangular panoramas -- where this module's own muxer writes the file (Motion-JPEG, PNG-in-MP4) the video
+    track gets the Spherical Video V1 box and players open it as a 360-degree video; the pyav and ffmpeg routes write no such
+    metadata."""
     if codec not in VIDEO_CODECS:
         raise ValueError(f"codec must be one of {VIDEO_CODECS}, got {codec!r}")
     ext = ".jpg" if codec == "mjpeg" else ".png"
@@ -461,7 +505,7 @@ def assemble_video(temp_dir: str, n_frames: int, fps: int, output_path: str, cod
     if codec == "mjpeg":
         from .mp4 import jpeg_size, write_jpeg_mp4
         w, h = jpeg_size(frames[0])
-        nbytes = write_jpeg_mp4(frames, fps, output_path, w, h)
+        nbytes = write_jpeg_mp4(frames, fps, output_path, w, h, **({"spherical": True} if spherical else {}))
         print(f"Video saved: {output_path} ({n_frames} JPEG-coded frames, {nbytes / 1e6:.0f} MB, Motion-JPEG in MP4)")
         return True
     try:
@@ -487,7 +531,7 @@ def assemble_video(temp_dir: str, n_frames: int, fps: int, output_path: str, cod
         print(f"ffmpeg failed ({rc}) on the PNG frames; writing them into the MP4 as they are")
     from .mp4 import png_size, write_png_mp4
     w, h = png_size(frames[0])
-    nbytes = write_png_mp4(frames, fps, output_path, w, h)
+    nbytes = write_png_mp4(frames, fps, output_path, w, h, **({"spherical": True} if spherical else {}))
     print(f"Video saved: {output_path} ({n_frames} PNG-coded frames, {nbytes / 1e6:.0f} MB, lossless; no H.264 encoder in this "
           f"environment -- re-code with: ffmpeg -i {output_path} -c:v libx264 -crf 18 -pix_fmt yuv420p out.mp4)")
     return True
@@ -568,7 +612,7 @@ def hdr_sidecar(hdr: dict, max_cll: float, max_fall: float, frames: int) -> dict
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
                     shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None,
-                    stars=None) -> dict:
+                    stars=None, projection=None) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -598,6 +642,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(observer=observer)
     if stars is not None:
         params.update(stars=dict(stars))
+    if projection is not None:
+        params.update(projection=projection)
     return params
 
 
@@ -636,7 +682,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  grade: Optional[dict] = None, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False,
                  map_supersample: int = 1, video_hdr: Optional[str] = None, hdr_white: float = 203.0, hdr_exposure: float = 0.0,
                  observer: Optional[str] = None, observer_velocity=None, observer_sky: bool = True,
-                 infall_to: Optional[float] = None, stars: Optional[dict] = None, **_deprecated_kwargs) -> None:
+                 infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
+                 **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -733,7 +780,13 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     orbiting camera.  ``infall_to`` = R (with "infall", without ``orbit``) moves the camera radially from |static_cam_pos| to R
     along static_cam_pos, uniformly in the falling observer's proper time.  Refused with ValueError, before any device work, with
     both given, ``shutter > 0``, a ray map, anti-aliasing, a Disk V2 source, adaptive supersampling or a spin.  The progress
-    record carries the observer's settings when one is given, and a resume with others starts over."""
+    record carries the observer's settings when one is given, and a resume with others starts over.
+
+    ``projection`` ("equirect" or "fisheye") with ``projection_fov``: every frame is render_async(..., projection=...) -- the
+    width x height frames through that camera instead of the pinhole, ``fov`` unused -- from the moving camera when an observer
+    is given as well.  Refused with ValueError, before any device work, with what check_projection names.  The progress record
+    carries the projection when one is given, and a resume under another starts over.  A full-sphere equirect video muxed by
+    this package (Motion-JPEG, PNG-in-MP4) carries the Spherical Video V1 box (assemble_video)."""
     moving = observer is not None or observer_velocity is not None
     plan = None
     if moving or infall_to is not None:
@@ -747,6 +800,13 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                        supersample_threshold=thr, spin=renderer.spin, redshift=renderer.redshift, shutter=shutter,
                        maps=ray_map or orbit_map or shutter_map)
         plan = obs_mod.frame_plan(n_frames, static_cam_pos, observer, observer_velocity, orbit, orbit_degrees, infall_to)
+    proj = None
+    if projection is not None or projection_fov is not None:
+        thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
+        proj = check_projection(projection, projection_fov, anti_alias=renderer.anti_alias,
+                                disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2", supersample_threshold=thr,
+                                world=world, spin=renderer.spin, redshift=renderer.redshift, shutter=shutter,
+                                maps=ray_map or orbit_map or shutter_map, stars=stars is not None)
     check_map_supersample(map_supersample, ray_map, orbit_map, shutter_map)
     check_shutter(shutter, shutter_samples)
     if video_stream not in ("auto", "y4m", "off"):
@@ -801,7 +861,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                              video_hdr, hdr_white, hdr_exposure,
                              observer=None if plan is None else {"kind": observer, "velocity": None if observer_velocity is None else list(observer_velocity),
                                                                  "sky": bool(observer_sky), "infall_to": infall_to},
-                             **({} if stars is None else {"stars": stars}))
+                             **({} if stars is None else {"stars": stars}),
+                             **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}))
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -934,6 +995,9 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             renderer.render_from_ray_map_async(frame=0)    # the same frame from the map: shade, no march
         elif orbit_map:
             renderer.render_from_ray_map_async(frame=0, cam_pos=cam_pos, fov=fov)    # the map turned to the frame's camera
+        elif proj is not None:                             # the frame through the projection, from the moving camera if there is one
+            renderer.render_async(cam_pos, fov, frame=0, projection=projection, projection_fov=projection_fov,
+                                  **({} if plan is None else {"observer": beta, "observer_sky": observer_sky}))
         elif plan is not None:
             renderer.render_async(cam_pos, fov, frame=0, observer=beta, observer_sky=observer_sky)
         else:
@@ -1003,4 +1067,6 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         print(f"Warning: only {len(completed)}/{n_frames} frames completed. Run again to resume.")
         return
     if not streamed:
-        assemble_video(temp_dir, n_frames, fps, output_path, codec=video_codec)
+        from .projection import full_sphere
+        assemble_video(temp_dir, n_frames, fps, output_path, codec=video_codec,
+                       **({"spherical": True} if proj is not None and full_sphere(projection, projection_fov) else {}))

@@ -12,6 +12,10 @@ this was developed: what the tests verify is the box structure and that every sa
 
 Only what such a file needs: ftyp, moov (mvhd, one trak: tkhd, mdia: mdhd, hdlr, minf: vmhd, dinf/dref, stbl: stsd
 [mp4v + esds], stts, stsc, stsz, co64), mdat with a 64-bit size.  ``read_samples`` walks the same boxes back (tests).
+
+``spherical=True`` (a full-sphere equirectangular video, drivers.assemble_video) adds the Spherical Video V1 ``uuid`` box to
+the video ``trak``: what makes players and upload sites open the file as a 360-degree video.  Without it the files are byte
+for byte what they were.
 """
 import os
 import struct
@@ -37,11 +41,18 @@ def _descr(tag: int, payload: bytes) -> bytes:
     return bytes([tag, 0x80 | (n >> 21) & 0x7F, 0x80 | (n >> 14) & 0x7F, 0x80 | (n >> 7) & 0x7F, n & 0x7F]) + payload
 
 
+# Spherical Video V1 (the spatial-media RFC): a 'uuid' box in the video trak whose payload is this RDF/XML
+SPHERICAL_UUID = bytes.fromhex("ffcc8263f8554a938814587a02521fdd")
+SPHERICAL_XML = (b'<?xml version="1.0"?><rdf:SphericalVideo xmlns:rdf="http://www.w3.org/1999/02/22-rdf-syntax-ns#" '
+                 b'xmlns:GSpherical="http://ns.google.com/videos/1.0/spherical/"><GSpherical:Spherical>true</GSpherical:Spherical>'
+                 b'<GSpherical:Stitched>true</GSpherical:Stitched><GSpherical:StitchingSoftware>bhr</GSpherical:StitchingSoftware>'
+                 b'<GSpherical:ProjectionType>equirectangular</GSpherical:ProjectionType></rdf:SphericalVideo>')
+
 MATRIX = struct.pack(">9i", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000)
 
 
 def _moov(width: int, height: int, fps: int, sizes: Sequence[int], first_offset: int, object_type: int = PNG_OBJECT_TYPE,
-          name: bytes = b"PNG frames (bhr)") -> bytes:
+          name: bytes = b"PNG frames (bhr)", spherical: bool = False) -> bytes:
     n = len(sizes)
     timescale, duration = int(fps), n                       # one tick per frame
     mvhd = _full(b"mvhd", 0, 0, struct.pack(">IIII", 0, 0, timescale, duration) + struct.pack(">IH", 0x10000, 0x0100) +
@@ -71,11 +82,12 @@ def _moov(width: int, height: int, fps: int, sizes: Sequence[int], first_offset:
     stbl = _box(b"stbl", stsd + stts + stsc + stsz + co64)
     minf = _box(b"minf", vmhd + dinf + stbl)
     mdia = _box(b"mdia", mdhd + hdlr + minf)
-    return _box(b"moov", mvhd + _box(b"trak", tkhd + mdia))
+    sv1 = _box(b"uuid", SPHERICAL_UUID + SPHERICAL_XML) if spherical else b""
+    return _box(b"moov", mvhd + _box(b"trak", tkhd + mdia + sv1))
 
 
 def _write_mp4(who: str, kind: str, magic: bytes, object_type: int, name: bytes, frame_paths: Sequence[str], fps: int,
-               output_path: str, width: int, height: int) -> int:
+               output_path: str, width: int, height: int, spherical: bool = False) -> int:
     """One sample per frame file in an 'mp4v' track of the given object type; every file must begin with ``magic``."""
     sizes = [os.path.getsize(p) for p in frame_paths]
     if not sizes:
@@ -83,9 +95,9 @@ def _write_mp4(who: str, kind: str, magic: bytes, object_type: int, name: bytes,
     if any(s >= 1 << 32 for s in sizes):
         raise ValueError(f"{who}: a frame of 4 GiB or more does not fit a sample size")
     ftyp = _box(b"ftyp", b"isom" + struct.pack(">I", 0x200) + b"isomiso2mp41")
-    moov_len = len(_moov(width, height, fps, sizes, 0, object_type, name))
+    moov_len = len(_moov(width, height, fps, sizes, 0, object_type, name, spherical))
     first = len(ftyp) + moov_len + 16                        # mdat header with a 64-bit size
-    moov = _moov(width, height, fps, sizes, first, object_type, name)
+    moov = _moov(width, height, fps, sizes, first, object_type, name, spherical)
     assert len(moov) == moov_len
     total = sum(sizes)
     tmp = output_path + ".part"
@@ -110,18 +122,19 @@ def _write_mp4(who: str, kind: str, magic: bytes, object_type: int, name: bytes,
     return first + total
 
 
-def write_png_mp4(frame_paths: Sequence[str], fps: int, output_path: str, width: int, height: int) -> int:
+def write_png_mp4(frame_paths: Sequence[str], fps: int, output_path: str, width: int, height: int, spherical: bool = False) -> int:
     """Muxes the PNG files (in order, one sample each) into ``output_path``; returns the bytes written.  The sample
-    table comes first (players start without reading the whole file), the frames are streamed through, never held."""
+    table comes first (players start without reading the whole file), the frames are streamed through, never held.
+    ``spherical``: the frames are full-sphere equirectangular panoramas -- the track gets the Spherical Video V1 box."""
     return _write_mp4("write_png_mp4", "PNG", PNG_MAGIC, PNG_OBJECT_TYPE, b"PNG frames (bhr)", frame_paths, fps, output_path,
-                      width, height)
+                      width, height, spherical)
 
 
-def write_jpeg_mp4(frame_paths: Sequence[str], fps: int, output_path: str, width: int, height: int) -> int:
+def write_jpeg_mp4(frame_paths: Sequence[str], fps: int, output_path: str, width: int, height: int, spherical: bool = False) -> int:
     """Muxes baseline JPEG files (in order, one sample each) into ``output_path`` as Motion-JPEG (object type 0x6C);
-    returns the bytes written.  Same layout as write_png_mp4."""
+    returns the bytes written.  Same layout as write_png_mp4, ``spherical`` included."""
     return _write_mp4("write_jpeg_mp4", "JPEG", JPEG_MAGIC, JPEG_OBJECT_TYPE, b"Motion JPEG (bhr)", frame_paths, fps, output_path,
-                      width, height)
+                      width, height, spherical)
 
 
 def jpeg_size(path: str) -> Tuple[int, int]:

@@ -457,7 +457,7 @@ class HipRenderer:
 
     def render_async(self, cam_pos, fov: float, frame: int = 0, skip_differentials: bool = False,
                      skip_bloom: bool = False, compaction: bool = False, math=None, lens_flare=None,
-                     observer=None, observer_sky: bool = True) -> None:
+                     observer=None, observer_sky: bool = True, projection=None, projection_fov=None) -> None:
         """Launch march + bloom + combine; the frame stays in HBM (counterpart of render_to_field,
         render.py:3819-3863, without the GUI flip).
 
@@ -465,7 +465,17 @@ class HipRenderer:
         moves through ``cam_pos`` with it (bhr_render_observer; include/bhr.h states the model, bhr_amd.observer names
         velocities): aberration, the Doppler factor in the disk's g and, with ``observer_sky``, on the sky.  Marched by the
         observer kernel whatever ``math`` the renderer has (``math=`` here is refused), (0, 0, 0) included, which is the
-        strict frame.  The velocity belongs to this call alone.  None (the default): the camera stands still, as ever."""
+        strict frame.  The velocity belongs to this call alone.  None (the default): the camera stands still, as ever.
+
+        ``projection``: "equirect" or "fisheye" -- the frame through an equirectangular panorama or an equidistant fisheye
+        instead of the pinhole (bhr_render_projected; include/bhr.h states the model, bhr_amd.projection the arguments).
+        ``projection_fov``: (h, v) degrees for equirect, (full_angle,) for fisheye; None: (360, 180) and (180,).  ``fov`` is then
+        unused.  Combines with ``observer``; without one the camera stands still.  Marched by the projected kernel whatever
+        ``math`` the renderer has (``math=`` here is refused).  None (the default): the pinhole camera, as ever."""
+        if projection is not None:
+            from . import projection as proj_mod
+            kind, fov_h, fov_v = proj_mod.check(projection, projection_fov)
+            fov = 90.0                        # the camera's basis and position are used, its image plane is not
         cam = self.camera_uniforms(cam_pos, fov, frame)
         flags = self._flags(skip_differentials, skip_bloom, compaction, math)
         if self.lens_flare if lens_flare is None else lens_flare:
@@ -475,6 +485,11 @@ class HipRenderer:
             obs = _lib.Observer()
             obs.beta[:] = obs_mod.check_beta(observer)
             obs.sky_shift = 1 if observer_sky else 0
+        if projection is not None:
+            proj = _lib.Projection(_lib.PROJ_EQUIRECT if kind == "equirect" else _lib.PROJ_FISHEYE, fov_h, fov_v, 0)
+            _lib.check(self._lib.bhr_render_projected(self._ctx, C.byref(cam), C.byref(proj), None if observer is None else C.byref(obs), flags))
+            return
+        if observer is not None:
             _lib.check(self._lib.bhr_render_observer(self._ctx, C.byref(cam), C.byref(obs), flags))
             return
         _lib.check(self._lib.bhr_render(self._ctx, C.byref(cam), flags))
@@ -756,6 +771,12 @@ class HipRenderer:
         _lib.check(self._lib.bhr_observer_resources(1 if supersampled else 0, out))
         return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
 
+    def projected_resources(self, supersampled: bool = False) -> dict:
+        """Registers per lane, LDS and scratch bytes of the projected march kernel (bhr_projected_resources)."""
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_projected_resources(1 if supersampled else 0, out))
+        return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
+
     def adaptive_info(self) -> dict:
         """The last adaptively supersampled frame: pixels refined, how many of them were marched strict, pixels of the frame
         (bhr_adaptive_info; synchronises)."""
@@ -873,13 +894,15 @@ class HipRenderer:
         return self.read_layer(_lib.LAYER_HDR)
 
     def render(self, cam_pos: List[float], fov: float, frame: int = 0,
-               skip_differentials: bool = False, skip_bloom: bool = False, observer=None, observer_sky: bool = True) -> np.ndarray:
+               skip_differentials: bool = False, skip_bloom: bool = False, observer=None, observer_sky: bool = True,
+               projection=None, projection_fov=None) -> np.ndarray:
         """One frame -> (rows, width, 3) float32 in [0, 1]  (render.py:3865-3923).  ``observer``, ``observer_sky``: a moving
-        camera, as render_async takes it."""
+        camera, ``projection``, ``projection_fov``: an equirect or fisheye camera, as render_async takes them."""
         if self.lens_flare and self.rows != self.height:
             raise ValueError("lens flare needs whole-frame sums; render row blocks through "
                              "bhr_amd.multigpu.group_render(..., lens_flare=True)")
-        self.render_async(cam_pos, fov, frame, skip_differentials, skip_bloom, observer=observer, observer_sky=observer_sky)
+        self.render_async(cam_pos, fov, frame, skip_differentials, skip_bloom, observer=observer, observer_sky=observer_sky,
+                          **({} if projection is None else {"projection": projection, "projection_fov": projection_fov}))
         return self.read_layer(_lib.LAYER_FINAL)
 
     def selftest(self) -> dict:

@@ -586,6 +586,52 @@ BHR_API int32_t bhr_render_observer(bhr_ctx *ctx, const bhr_camera *cam, const b
 /* out = {VGPRs per lane, LDS bytes per block, scratch bytes per lane} of the observer march kernel (supersampled != 0: of its
  * supersampled twin), from hipFuncGetAttributes.  No context. */
 BHR_API int32_t bhr_observer_resources(int32_t supersampled, int32_t out[3]);
+/* Projections: one frame through an equirectangular (360 degree panorama) or an equidistant fisheye (dome master) camera instead
+ * of the pinhole.  The frame is bhr_render_observer's frame in every respect but the pixel's direction n' -- next frame slot,
+ * one timing-ring entry, counters, post-pass following the context's arithmetic, lens flare, grade, HDR plane, u8 / u16 rows,
+ * dither, sinks, streams; asynchronous; a tilted disk and bhr_set_supersample work; the texture source only, no ray
+ * differentials -- and is marched by the projected object (csrc/march_projected.hip).  Of cam, pos, right, up, forward,
+ * r_escape and t_offset are used; pixel_width and pixel_height are ignored.
+ * F, R, U are cam's forward, right and up, Wf x Hf the grid the march walks (k W x k H under bhr_set_supersample(k)), (i, j) the
+ * fine pixel; everything is f32, every operation rounded once, the two spans made in binary64 and rounded once:
+ *   BHR_PROJ_EQUIRECT   fov_h_deg in (0, 360], fov_v_deg in (0, 180]; 360 x 180 is the full sphere
+ *       lon = (((float)i + 0.5f) / (float)Wf - 0.5f) * span_h        span_h = (float)radians(fov_h_deg)
+ *       lat = (0.5f - ((float)j + 0.5f) / (float)Hf) * span_v        span_v = (float)radians(fov_v_deg)
+ *       a = cosf(lat) * cosf(lon);  b = cosf(lat) * sinf(lon);  c = sinf(lat)
+ *       n'_k = (a * F_k + b * R_k) + c * U_k
+ *     longitude grows towards right, row 0 is the top, the image centre looks along forward.
+ *   BHR_PROJ_FISHEYE    equidistant; fov_h_deg in (0, 360] is the full angle of the image circle, which is inscribed in the
+ *                       shorter side; fov_v_deg is ignored
+ *       s = 2.0f / (float)min(Wf, Hf)
+ *       x = (((float)i + 0.5f) - (float)Wf / 2) * s;   y = ((float)Hf / 2 - ((float)j + 0.5f)) * s
+ *       rho = sqrtf(x * x + y * y);   inside = rho <= 1.0f
+ *       theta = rho * half                                            half = (float)(radians(fov_h_deg) / 2)
+ *       inv = rho > 0 ? 1.0f / rho : 0.0f
+ *       a = cosf(theta);  b = sinf(theta) * (x * inv);  c = sinf(theta) * (y * inv);   n'_k as above
+ *     a pixel that is not inside takes no step and its BG and DISK are exactly 0; under supersampling it enters the box filter
+ *     as zeros, which anti-aliases the rim.  bhr_counters.rays is k^2 W H for either projection, ray_steps the steps taken.
+ * sinf / cosf are the device library's accurate functions, evaluated once per ray (their bits are not pinned); n' is unit to a
+ * few ulps and not renormalised.  With obs != NULL, n' is the n' of bhr_render_observer: aberration, D in the disk's g, the sky
+ * under sky_shift exactly as stated there.  obs == NULL: the camera stands still, the frame bit for bit that of
+ * obs = {{0, 0, 0}, 0}.  flags: BHR_SKIP_BLOOM, BHR_LENS_FLARE.  A star catalogue is ignored, as bhr_render ignores it.  The
+ * bloom is an image-space pass and does not wrap at the +-180 degree seam.  (DESIGN.md "Projections"; tests/projection_ref.py is
+ * the CPU reference.)
+ * BHR_ERR_INVALID with a message that names the combination, nothing launched and the context untouched: a null ctx, cam or
+ * proj, an unknown kind, a NaN or out-of-range field of view, any other flag bit, everything bhr_render_observer refuses for
+ * its obs, anti_alias = 1, a Disk V2 source, adaptive supersampling, a spin or the forced Kerr march or the exact redshift, a
+ * row-block context. */
+#define BHR_PROJ_EQUIRECT 1
+#define BHR_PROJ_FISHEYE  2
+typedef struct {
+    int32_t kind;
+    float fov_h_deg, fov_v_deg;
+    int32_t reserved;
+} bhr_projection;
+BHR_API int32_t bhr_render_projected(bhr_ctx *ctx, const bhr_camera *cam, const bhr_projection *proj,
+                                     const bhr_observer *obs /* NULL: the camera stands still */, uint32_t flags);
+/* out = {VGPRs per lane, LDS bytes per block, scratch bytes per lane} of the projected march kernel (supersampled != 0: of its
+ * supersampled twin), from hipFuncGetAttributes.  No context. */
+BHR_API int32_t bhr_projected_resources(int32_t supersampled, int32_t out[3]);
 /* The library's switches.  Each has an environment variable that bhr_create reads ONCE (no entry point calls getenv
  * afterwards) and can be changed per context later with this call -- what tests and A/B tools use:
  *   "bloom_split"     BHR_BLOOM_SPLIT     -1 post-pass by arithmetic (exact f32 under strict, split f16 under fast / hybrid), 0 / 1 force
