@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE -- NumPy restatement of the reference's lens flare (render.py:3925-4028),
-pinned bit for bit by tests/golden/misc.npz (generated from the reference's _apply_lens_flare).
-The product path is the device kernel in csrc/flare.hip; only tests/ may import this module.
+pinned bit for bit by tests/golden/misc.npz and tests/golden/flare_cases.npz (generated from the
+reference's _apply_lens_flare; tests/test_flare_ref.py).  The product path is the device kernel in csrc/flare.hip; only tests/ may import this module.
 
 
 The reference works on (W, H, 3) arrays; frames here are (H, W, 3).  The effect is evaluated
@@ -17,20 +17,27 @@ _HEX_TINT = np.array([0.6, 0.7, 1.0])
 _STREAK_TINT = np.array([1.0, 0.95, 0.9])
 
 
-def _flare_wh(final: np.ndarray, disk: np.ndarray) -> np.ndarray:
-    """final, disk: (W, H, 3).  Returns clip(final + flare, 0, 1)."""
-    w, h, _ = final.shape
+def _flare_term_wh(disk: np.ndarray, probe: dict = None):
+    """disk: (W, H, 3).  The f32 flare plane (W, H, 3) before it is added and clipped, None where the disk layer's total is
+    under the threshold.  probe: a dict that receives what the tests' premises look at and the result does not show -- each
+    shape's own alpha plane ("ghost0" .. "ghost7", "ring0" .. "ring2", "hex", "streaks": how many of the four wedges a pixel
+    is in), the streaks' "delta" per axis, "total", "ratio" (total / (0.3 w h), as compared with 1.0) and "src"."""
+    w, h, _ = disk.shape
     scale = min(w, h) / 360.0                      # sizes are quoted for a 360-line frame
 
     glow = np.max(disk, axis=2)                    # per-pixel disk brightness, (W, H)
     total = np.sum(glow)
+    if probe is not None:
+        probe["total"] = total
     if total < 0.01:
-        return final
+        return None
     xs, ys = np.mgrid[0:w, 0:h]
     src_x = np.sum(xs * glow) / total              # brightness centroid of the disk layer
     src_y = np.sum(ys * glow) / total
     mid_x, mid_y = w / 2, h / 2
     strength = min(total / (w * h * 0.3), 1.0) * 1.5
+    if probe is not None:
+        probe["ratio"], probe["src"] = total / (w * h * 0.3), (src_x, src_y)
 
     def along_axis(t):
         """Point at fraction t on the line source -> screen centre."""
@@ -48,6 +55,8 @@ def _flare_wh(final: np.ndarray, disk: np.ndarray) -> np.ndarray:
         alpha[inside] = (1 - dist[inside] / radius) ** 2 * (1 - g * 0.08) * strength
         for c in range(3):
             flare[:, :, c] += alpha * _GHOST_TINT[c]
+        if probe is not None:
+            probe[f"ghost{g}"] = alpha
 
     # three diffraction rings with slightly different tints
     for k in range(3):
@@ -59,6 +68,8 @@ def _flare_wh(final: np.ndarray, disk: np.ndarray) -> np.ndarray:
         alpha = np.clip(1 - off / ring_w, 0, 1) ** 2 * 0.5 * strength * (1 - k * 0.25)
         for c in range(3):
             flare[:, :, c] += alpha * _RING_TINTS[k][c]
+        if probe is not None:
+            probe[f"ring{k}"] = alpha
 
     # hexagonal aperture ring half way
     hx, hy = along_axis(0.5)
@@ -71,6 +82,8 @@ def _flare_wh(final: np.ndarray, disk: np.ndarray) -> np.ndarray:
     alpha = np.clip(1 - off / (15 * scale), 0, 1) ** 2 * facet * 0.3 * strength
     for c in range(3):
         flare[:, :, c] += alpha * _HEX_TINT[c]
+    if probe is not None:
+        probe["hex"] = alpha
 
     # four streaks through the source
     reach = min(w, h) * 0.4
@@ -78,14 +91,33 @@ def _flare_wh(final: np.ndarray, disk: np.ndarray) -> np.ndarray:
     dx, dy = xs - src_x, ys - src_y
     dist = np.sqrt(dx ** 2 + dy ** 2)
     angle = np.arctan2(dy, dx)
+    if probe is not None:
+        probe["streaks"], probe["delta"] = np.zeros((w, h), dtype=np.int64), []
     for axis in [0, np.pi / 2, np.pi, 3 * np.pi / 2]:
         delta = np.abs(np.mod(angle - axis + np.pi, 2 * np.pi) - np.pi)
         on = delta < 0.05
         falloff = np.exp(-dist / reach)
         for c in range(3):
             flare[:, :, c] += np.where(on, falloff * gain * _STREAK_TINT[c], 0)
+        if probe is not None:
+            probe["streaks"] += on
+            probe["delta"].append(delta)
+    return flare
 
+
+def _flare_wh(final: np.ndarray, disk: np.ndarray) -> np.ndarray:
+    """final, disk: (W, H, 3).  Returns clip(final + flare, 0, 1)."""
+    flare = _flare_term_wh(disk)
+    if flare is None:
+        return final
     return np.clip(final + flare, 0, 1)
+
+
+def flare_term(disk_hw3: np.ndarray, probe: dict = None):
+    """(H, W, 3) disk layer -> the (H, W, 3) f32 flare plane before it is added to the frame and clipped, or None where the
+    layer's total is under the threshold and the frame stays untouched.  probe: see _flare_term_wh; its planes are (W, H)."""
+    flare = _flare_term_wh(np.ascontiguousarray(disk_hw3.transpose(1, 0, 2)), probe)
+    return None if flare is None else np.ascontiguousarray(flare.transpose(1, 0, 2))
 
 
 def apply_lens_flare(final_hw3: np.ndarray, disk_hw3: np.ndarray) -> np.ndarray:
