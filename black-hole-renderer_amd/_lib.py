@@ -33,7 +33,7 @@ SYMBOLS = (
     "bhr_bg_init", "bhr_generate_background", "bhr_set_entity_staging", "bhr_set_comp", "bhr_read_comp",
     "bhr_fill_comp_slice", "bhr_set_compose_stats", "bhr_compose_texture", "bhr_eval_noise", "bhr_render", "bhr_render_shutter",
     "bhr_set_spin", "bhr_kerr_resources", "bhr_set_redshift", "bhr_kerr_redshift_resources",
-    "bhr_render_observer", "bhr_observer_resources",
+    "bhr_render_observer", "bhr_observer_resources", "bhr_render_delayed", "bhr_delayed_resources",
     "bhr_render_projected", "bhr_projected_resources",
     "bhr_raymap_build", "bhr_raymap_render", "bhr_raymap_render_view", "bhr_raymap_render_shutter", "bhr_raymap_read", "bhr_raymap_get_info", "bhr_raymap_free",
     "bhr_set_stars", "bhr_get_stars_info", "bhr_stars_resources",
@@ -67,6 +67,11 @@ PROJ_EQUIRECT, PROJ_FISHEYE = 1, 2
 class Projection(C.Structure):
     """bhr_projection: an equirectangular or fisheye camera (bhr_render_projected) and its field of view in degrees."""
     _fields_ = [("kind", C.c_int32), ("fov_h_deg", C.c_float), ("fov_v_deg", C.c_float), ("reserved", C.c_int32)]
+
+
+class LightDelay(C.Structure):
+    """bhr_light_delay: the scale of the light delay of a frame (bhr_render_delayed); reserved is 0."""
+    _fields_ = [("scale", C.c_float), ("reserved", C.c_int32)]
 
 
 class Camera(C.Structure):
@@ -194,6 +199,8 @@ def load() -> C.CDLL:
     lib.bhr_kerr_redshift_resources.argtypes = [I32, I32, C.POINTER(C.c_int32)]
     lib.bhr_render_observer.argtypes = [P, C.POINTER(Camera), C.POINTER(Observer), C.c_uint32]
     lib.bhr_observer_resources.argtypes = [I32, C.POINTER(C.c_int32)]
+    lib.bhr_render_delayed.argtypes = [P, C.POINTER(Camera), C.POINTER(LightDelay), C.c_uint32]
+    lib.bhr_delayed_resources.argtypes = [I32, C.POINTER(C.c_int32)]
     lib.bhr_render_projected.argtypes = [P, C.POINTER(Camera), C.POINTER(Projection), C.POINTER(Observer), C.c_uint32]
     lib.bhr_projected_resources.argtypes = [I32, C.POINTER(C.c_int32)]
     lib.bhr_set_option.argtypes = [P, C.c_char_p, C.c_double]

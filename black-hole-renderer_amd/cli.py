@@ -5,7 +5,8 @@ refused -- this build has no CPU path), ``-r 8k``, ``--gpus N`` (row-block tilin
 inside one process; for ``--video`` launch one process per GPU with torchrun and frames are sharded
 round-robin by RANK / WORLD_SIZE), ``--disk_model`` (the analytic Disk V2 sources of the march kernel), ``--observer`` /
 ``--observer_velocity`` (a camera that moves: aberration and Doppler shift), ``--stars point`` (the procedural sky's stars as a
-catalogue of lensed points rendered through a ray map), ``--projection`` / ``--projection_fov`` (equirectangular 360-degree
+catalogue of lensed points rendered through a ray map), ``--light_delay`` (every disk crossing shaded at the
+time its light left the gas), ``--projection`` / ``--projection_fov`` (equirectangular 360-degree
 frames and fisheye dome masters instead of the pinhole camera).
 """
 from __future__ import annotations
@@ -112,6 +113,15 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--projection_fov", type=float, nargs="+", default=None, metavar=("A", "B"),
                    help="--projection equirect: the horizontal and vertical span in degrees, A in (0, 360] and B in (0, 180] (default: "
                         "360 180); --projection fisheye: the full angle of the image circle, A in (0, 360] (default: 180)")
+    p.add_argument("--light_delay", type=float, nargs="?", const=1.0, default=argparse.SUPPRESS, metavar="SCALE",
+                   help="light delay: every disk crossing is shaded at the time its light left the gas, so the far side of the disk "
+                        "and the secondary image show the gas earlier than the near side does (tens of r_s / c: radians of orbital "
+                        "phase near the inner edge).  SCALE in [0, 16] multiplies the delay: 1 (the default when the flag is given "
+                        "bare) is physical, larger values exaggerate it, 0 is the undelayed frame.  Marched by a strict kernel of "
+                        "its own whatever --math says; works with --supersample, --disk_tilt, --lens_flare, the grade, HDR and "
+                        "--video [--orbit].  Not with --anti_alias lod_radius, --disk_model v2 / v2_volume, "
+                        "--supersample_threshold, --gpus > 1, --spin, --redshift exact, the observer flags, --projection, --passes, "
+                        "--shutter, the ray-map flags or --stars point")
     p.add_argument("--video_stream", type=str, default="auto", choices=["auto", "y4m", "off"],
                    help="--video: also hand the frames to the encoder as a yuv420p stream converted on the device "
                         "(auto: pipe into ffmpeg when it is on PATH; y4m: write <output stem>.y4m; off: PNG frames only)")
@@ -420,6 +430,38 @@ def parse_args(argv=None) -> argparse.Namespace:
             check(args.projection, args.projection_fov)
         except ValueError as e:
             p.error(f"{who} --projection_fov: {e}")
+    # light delay, behind every refusal above: a line that was refused without --light_delay is refused with the same words.  The
+    # option has no default in the namespace: it is there only when the flag was given
+    delay = getattr(args, "light_delay", None)
+    if delay is not None:
+        who = "--light_delay"
+        if not 0.0 <= delay <= 16.0:               # a NaN fails the comparison too
+            p.error(f"{who} is a scale in [0, 16], got {delay}")
+        if args.anti_alias != "disabled":
+            p.error(f"{who} does not combine with --anti_alias lod_radius: the delayed march has no ray differentials")
+        if args.disk_model != "texture":
+            p.error(f"{who} does not combine with --disk_model other than texture: the delayed march shades the disk texture")
+        if args.supersample_threshold is not None:
+            p.error(f"{who} does not combine with --supersample_threshold: the delayed march has no refinement kernels (plain --supersample works)")
+        if args.gpus != 1:
+            p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march without the light's travel time")
+        if args.spin != 0:
+            p.error(f"{who} does not combine with --spin: the delayed march is Schwarzschild's")
+        if args.redshift == "exact":
+            p.error(f"{who} does not combine with --redshift exact: that is the Kerr march's")
+        if observer_flags:
+            p.error(f"{who} does not combine with --observer, --observer_velocity, --observer_sky or --infall_to: the delayed march is "
+                    "the camera's that stands still")
+        if args.projection != "perspective":
+            p.error(f"{who} does not combine with --projection {args.projection}: the delayed march is the pinhole camera's")
+        if args.shutter > 0:
+            p.error(f"{who} does not combine with --shutter: shutter frames march without the light's travel time")
+        for flag, on in (("--ray_map", args.ray_map), ("--orbit_map", args.orbit_map), ("--shutter_map", args.shutter_map),
+                         ("--passes", args.passes is not None)):
+            if on:
+                p.error(f"{who} does not combine with {flag}: a ray map's records hold no travel time")
+        if args.stars == "point":
+            p.error(f"{who} does not combine with --stars point: point stars are rendered through a ray map, whose records hold no travel time")
     # --exposure, --white, --transfer and --hdr_output without --tonemap mean --tonemap clip
     if args.tonemap is None and any(v is not None for v in (args.exposure, args.white, args.transfer, args.hdr_output)):
         args.tonemap = "clip"
@@ -450,6 +492,12 @@ def projection_from_args(args) -> dict:
         return {}
     fov = getattr(args, "projection_fov", None)
     return dict(projection=args.projection, projection_fov=None if fov is None else tuple(fov))
+
+
+def light_delay_from_args(args) -> dict:
+    """The light delay of a command line as drivers.render_image / render_video take it: {} without --light_delay."""
+    delay = getattr(args, "light_delay", None)
+    return {} if delay is None else dict(light_delay=float(delay))
 
 
 def observer_beta(args):
@@ -574,6 +622,8 @@ def main(argv=None) -> int:
     if proj_kw:
         from .projection import frame_size
         width, height = frame_size(args.projection, width, height)
+    # ... and the light delay
+    delay_kw = light_delay_from_args(args)
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))
@@ -581,6 +631,8 @@ def main(argv=None) -> int:
         local_rank = int(os.environ.get("LOCAL_RANK", "0"))
         if proj_kw:                                 # several ranks are refused before a device is touched
             drivers.check_projection(world=world, **proj_kw)
+        if delay_kw:
+            drivers.check_light_delay(delay_kw["light_delay"], world=world)
         if "BHR_FORCE_DEVICE" in os.environ:        # rehearsal: several ranks sharing one card
             local_rank = int(os.environ["BHR_FORCE_DEVICE"])
         elif world > 1:                             # a launcher that shows every rank only its own GPU: ordinal 0
@@ -605,7 +657,7 @@ def main(argv=None) -> int:
                              shutter_map=args.shutter_map, map_supersample=args.map_supersample, video_hdr=args.video_hdr,
                              hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure, **stars_kw,
                              **(dict(observer=args.observer, observer_velocity=args.observer_velocity, observer_sky=sky,
-                                     infall_to=args.infall_to) if moving else {}), **proj_kw)
+                                     infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -630,6 +682,6 @@ def main(argv=None) -> int:
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
         grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw, **stars_kw,
-        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw)
+        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

@@ -141,6 +141,11 @@ struct BhrProjectedMarchArgs : BhrObserverMarchArgs {
     int32_t proj_kind;
     float span_h, span_v;
 };
+// The argument block of the delay object's kernels (march_delay.hip; bhr_render_delayed): the march's block with the scale of
+// the light delay behind it (ray_delay.h: t_eff = t_offset - delay_scale * T_hit).  A block of its own, as the observer's is.
+struct BhrDelayMarchArgs : BhrMarchArgs {
+    float delay_scale;
+};
 
 // A partial march launch: the tiles of `d_list` only.  bhr_launch_march_hybrid builds one for each of its launches (strict
 // list, fast list, fix list and the empty parts that bracket them) and passes it to bhr_launch_march (null: the whole block).
@@ -167,6 +172,7 @@ struct bhr_march_call {
     bool keep_start;         // a later sample of a shutter frame (bhr_render_shutter): the march-start event stays the first sample's
     const bhr_observer *observer = nullptr;   // bhr_render_observer: the frame is marched by the observer object for this moving camera
     const bhr_projection *projection = nullptr;   // bhr_render_projected (observer is set too): the projected object marches it under this projection
+    const bhr_light_delay *delay = nullptr;   // bhr_render_delayed: the frame is marched by the delay object under this scale
 };
 
 // The march kernels by what they do; each march object returns its own instantiation of a name (or null) from
@@ -680,6 +686,7 @@ const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_
 const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_raymap.hip -> march_raymap.o
 const void *bhr_march_kernel_observer(bhr_march_kernel k, int32_t diff, int32_t ss);   // march_observer.hip -> march_observer.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_projected(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_projected.hip -> march_projected.o (BHR_MK_TILE, diff 0 only)
+const void *bhr_march_kernel_delay(bhr_march_kernel k, int32_t diff, int32_t ss);      // march_delay.hip -> march_delay.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
 

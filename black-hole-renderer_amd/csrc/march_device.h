@@ -25,7 +25,7 @@
 // v_rsq/v_rcp/v_sqrt instead of IEEE sqrt + divide inside the RK4 stages, FMA contraction, and the
 // re-use of |new_pos| as the next step's |pos| (same value in the reference).
 //
-// The march's device source is eight headers and seven translation units, one per object (csrc/Makefile):
+// The march's device source is nine headers and eight translation units, one per object (csrc/Makefile):
 //   march_device.h      this file: vectors, exact-rounding sequences, samplers, shading, parking slots, pixel stores
 //   ray_strict.h        Ray<DIFF, SRC>, strict: every operation of the RK4 loop in the reference's order with IEEE sqrt and
 //                       divide, so that positions, step counts and hit points are bit-identical to a strict f32 evaluation
@@ -35,6 +35,8 @@
 //                       Doppler factor in the disk's g and on the sky (bhr_render_observer)
 //   ray_projected.h     Ray<false, 0>, projected: the observer Ray launched along an equirectangular or fisheye pixel direction
 //                       (bhr_render_projected)
+//   ray_delay.h         Ray<false, 0>, delayed: the strict Ray with the light's coordinate time beside it, every disk crossing shaded at
+//                       its emission time (bhr_render_delayed)
 //   ray_kerr.h          Ray<false, 0>, Kerr: a spinning hole in Kerr-Schild coordinates, RK4 on (x, p), its own sampler and g-factor
 //                       (bhr_set_spin); the Schwarzschild Rays above know nothing of it
 //   march_tile.h        the tile schedule: march_tile_body, its plain, supersampled and list kernels
@@ -47,9 +49,10 @@
 //   march_kerr.hip       -> march_kerr.o        ray_kerr.h, tile schedule, plain and supersampled; -ffp-contract=on, no fast-math
 //   march_observer.hip   -> march_observer.o    ray_observer.h, tile schedule, plain and supersampled; the strict flags
 //   march_projected.hip  -> march_projected.o   ray_projected.h, tile schedule, plain and supersampled; the strict flags
+//   march_delay.hip      -> march_delay.o       ray_delay.h, tile schedule, plain and supersampled; the strict flags
 // A translation unit includes the one Ray header it marches with (which includes this file), then the schedules it uses,
 // defines the kernels that are its own and ends with their table, by which the one host launcher (march_launch.hip) finds
-// them: bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr / _observer / _projected.
+// them: bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr / _observer / _projected / _delay.
 #pragma once
 #include "bhr_internal.h"
 #include "disk_v2_device.h"

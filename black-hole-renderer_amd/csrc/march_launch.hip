@@ -1,9 +1,9 @@
 // march_launch.hip -- the host half of the ray march: every march launch goes through bhr_launch_march.
 //
-// The march's device code is seven objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
-// with the ILP-first scheduler, march_raymap.hip, march_kerr.hip, march_observer.hip, march_projected.hip; the layout: march_device.h);
+// The march's device code is eight objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
+// with the ILP-first scheduler, march_raymap.hip, march_kerr.hip, march_observer.hip, march_projected.hip, march_delay.hip; the layout: march_device.h);
 // each object hands its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr / _observer /
-// _projected).  This file resolves the
+// _projected / _delay).  This file resolves the
 // arithmetic, builds the kernel arguments, keeps the tile order, the ray-step counters and the timing events, and picks
 // the kernel of a launch (march_kernel).  What a launch works from is in its arguments -- the caller's bhr_march_call
 // (camera, flags, stream, timing slot, end-event policy, supersampling factor) and, for one list of a hybrid march, a
@@ -70,6 +70,7 @@ float fast_sqrt(float s) {
 //   arithmetic     request                                              kernel (object)
 //   any            a projection (bhr_render_projected)                  march_projected_kernel / march_projected_ss_kernel (projected)
 //   any            a moving observer (bhr_render_observer)              march_observer_kernel / march_observer_ss_kernel (observer)
+//   any            light delay (bhr_render_delayed)                     march_delay_kernel / march_delay_ss_kernel (delay)
 //   any            a spin is set (bhr_set_spin), whole block            march_kerr_kernel / march_kerr_ss_kernel (kerr)
 //   any            ... and the exact redshift (bhr_set_redshift)         march_kerr_exact_kernel / march_kerr_exact_ss_kernel (kerr)
 //   any            hybrid part with n <= 0, not the fix list            none
@@ -98,7 +99,7 @@ struct MarchKernel {
     dim3 grid;
     size_t lds = 0;
 };
-MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *part, int math, uint32_t flags, bool diff, bool observer, bool projected) {
+MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *part, int math, uint32_t flags, bool diff, bool observer, bool projected, bool delayed) {
     MarchKernel k;
     k.grid = dim3((a.n_list + 3) / 4);
     const bool persistent = (flags & BHR_PERSISTENT) != 0;
@@ -108,6 +109,11 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
     if (observer) {
         // (a projection, bhr_render_projected, is an observer's frame marched by the projected object)
         if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = (projected ? bhr_march_kernel_projected : bhr_march_kernel_observer)(BHR_MK_TILE, diff, ss);
+        return k;
+    }
+    // light delay (bhr_render_delayed): the delay object's march, on the same terms
+    if (delayed) {
+        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = bhr_march_kernel_delay(BHR_MK_TILE, diff, ss);
         return k;
     }
     // the spinning hole: one arithmetic, one schedule, no lists (what has no Kerr form was refused before anything was launched)
@@ -308,8 +314,9 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     // caller chose; the first part records the start event and clears an untimed counter, the last part records the end event
     // with a spin set the context's math mode does not select the march: one launch of the Kerr object, its argument block the
     // strict one's (the post-pass has followed the math mode, bhr_frame_begin)
-    // (likewise the frame of a moving observer, bhr_render_observer: one launch of the observer object)
-    const int math = part ? part->math : (ctx->kerr_on || call.observer) ? BHR_MATH_STRICT : bhr_resolve_math(ctx, flags);
+    // (likewise the frame of a moving observer, bhr_render_observer: one launch of the observer object; and a frame with light
+    // delay, bhr_render_delayed: one launch of the delay object)
+    const int math = part ? part->math : (ctx->kerr_on || call.observer || call.delay) ? BHR_MATH_STRICT : bhr_resolve_math(ctx, flags);
     if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, call);
     const bool fast = math == BHR_MATH_FAST;
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
@@ -374,7 +381,7 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(bhr_slot(ctx).d_queue, 0, sizeof(unsigned int), stream));
     // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
     if (first_part && !call.keep_start) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, slot), stream));
-    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags), call.observer != nullptr, call.projection != nullptr);
+    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags), call.observer != nullptr, call.projection != nullptr, call.delay != nullptr);
     if (!k.fn && !(part && part->n <= 0 && part->repair != 2))
         return bhr_fail(BHR_ERR_STATE, "bhr_render: no march kernel for this launch (supersampling %d, flags %u)", call.ss, flags);
     if (k.fn) {
@@ -402,6 +409,13 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
                 oa.span_v = pr->kind == BHR_PROJ_FISHEYE ? 0.0f : (float)((double)pr->fov_v_deg * rad);
             }
             args[0] = &oa;
+        }
+        // light delay: the finished march block with the call's scale behind it (the delay object's kernels take this block)
+        BhrDelayMarchArgs da;
+        if (call.delay) {
+            static_cast<BhrMarchArgs &>(da) = a;
+            da.delay_scale = call.delay->scale;
+            args[0] = &da;
         }
         (void)hipLaunchKernel(k.fn, k.grid, dim3(256), args, k.lds, stream);
     }

@@ -1,5 +1,5 @@
-// ray_strict.h -- the strict Ray of the march (march_strict.o, march_strict_ilp.o, march_raymap.o, and under ray_observer.h
-// march_observer.o; see march_device.h).
+// ray_strict.h -- the strict Ray of the march (march_strict.o, march_strict_ilp.o, march_raymap.o, under ray_observer.h
+// march_observer.o and under ray_delay.h march_delay.o; see march_device.h).
 #pragma once
 #define BHR_RAY_STRICT 1
 #include "march_device.h"
@@ -233,7 +233,7 @@ struct StrictRay {
 };
 
 // The Ray the schedules march (march_tile.h, march_persistent.h): the strict one itself, unless the Ray header that included
-// this file derives its own from it (ray_observer.h).
+// this file derives its own from it (ray_observer.h, ray_delay.h).
 #ifndef BHR_RAY_OBSERVER
 template <bool DIFF, int SRC = 0>
 using Ray = StrictRay<DIFF, SRC>;

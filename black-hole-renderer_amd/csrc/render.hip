@@ -63,13 +63,14 @@ int32_t post_on_slot(bhr_ctx *ctx, uint32_t flags, int k, int ring) {
 
 // obs: the frame of a moving observer (bhr_render_observer), marched by the observer object; null: bhr_render's
 // proj (with obs): that frame under a projection (bhr_render_projected), marched by the projected object
+// delay (without either): the frame with light delay (bhr_render_delayed), marched by the delay object
 int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, const bhr_observer *obs = nullptr,
-                       const bhr_projection *proj = nullptr) {
+                       const bhr_projection *proj = nullptr, const bhr_light_delay *delay = nullptr) {
     bhr_frame_slot &f = ctx->slots[k];
     BHR_TRY(bhr_frame_begin(ctx, flags));
     // an adaptively supersampled frame: the k = 1 march, then detect + refinement inside the same march bracket
     const bool adaptive = ctx->ada_k > 1;
-    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss, /* keep_start */ false, obs, proj};
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss, /* keep_start */ false, obs, proj, delay};
     *fm = {call.ss, 1, adaptive};
     BHR_TRY(bhr_launch_march(ctx, call));              // records the ring slot's march events
     if (adaptive) BHR_TRY(bhr_launch_adaptive(ctx, call));
@@ -288,6 +289,33 @@ int32_t bhr_render_projected(bhr_ctx *ctx, const bhr_camera *cam, const bhr_proj
     BHR_TRY(observer_frame_check(ctx, &o, flags, who, "a projection"));
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, &o, proj); });
+}
+
+// One frame with every disk crossing shaded at its emission time (include/bhr.h): bhr_render's frame marched by the delay object.
+// Everything that can refuse does so before the frame takes a slot; like bhr_render_observer the frame neither triggers nor
+// counts towards the calibration of slot 1's stream.
+int32_t bhr_render_delayed(bhr_ctx *ctx, const bhr_camera *cam, const bhr_light_delay *d, uint32_t flags) {
+    const char *who = "bhr_render_delayed";
+    if (!ctx || !cam || !d) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    if (!(d->scale >= 0.0f && d->scale <= 16.0f))       // a NaN fails the comparison too
+        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with scale = %g: in [0, 16] and no NaN", who, (double)d->scale);
+    if (d->reserved != 0) return bhr_fail(BHR_ERR_INVALID, "%s: light delay with reserved = %d: must be 0", who, d->reserved);
+    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
+        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
+    if (ctx->cfg.anti_alias != 0)
+        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with anti_alias = 1: the delayed march has no ray differentials", who);
+    if (ctx->disk_source != BHR_DISK_TEXTURE)
+        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with a Disk V2 source (%d): the delayed march shades the disk texture", who, ctx->disk_source);
+    if (ctx->ada_k > 1)
+        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with adaptive supersampling (factor %d): the delayed march has no refinement kernels; use bhr_set_supersample", who, ctx->ada_k);
+    if (ctx->kerr_on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with the exact redshift (bhr_set_redshift): the delayed march is Schwarzschild's", who);
+    if (ctx->kerr_on)
+        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with a spin set or the Kerr march forced (bhr_set_spin, a / M = %g): the delayed march is Schwarzschild's", who, (double)ctx->kerr_spin);
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "%s: light delay on a row-block context (rows %d of %d): needs a whole-frame context", who, ctx->rows, ctx->cfg.height);
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, nullptr, nullptr, d); });
 }
 
 // One frame as the mean of n marches (include/bhr.h).  One frame of one frame slot: the next frame takes the other slot.

@@ -28,7 +28,8 @@ int32_t kerr_state_check(const bhr_ctx *ctx, uint32_t flags, const char *who, do
 // twin).  No context: host + hipFuncGetAttributes.
 int32_t kerr_kernel_resources(const char *who, bhr_march_kernel k, int32_t ss, int32_t out[3], int observer = 0) {
     if (!out) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
-    const void *f = observer == 2 ? bhr_march_kernel_projected(k, 0, ss ? 1 : 0)   // 1: the observer object, 2: the projected object
+    const void *f = observer == 3 ? bhr_march_kernel_delay(k, 0, ss ? 1 : 0)       // 3: the delay object
+                    : observer == 2 ? bhr_march_kernel_projected(k, 0, ss ? 1 : 0)   // 1: the observer object, 2: the projected object
                     : observer  ? bhr_march_kernel_observer(k, 0, ss ? 1 : 0) : bhr_march_kernel_kerr(k, 0, ss ? 1 : 0);
     if (!f) return bhr_fail(BHR_ERR_STATE, "%s: no such march kernel in this library", who);
     hipFuncAttributes at;
@@ -140,6 +141,7 @@ int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode) {
 
 int32_t bhr_observer_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_observer_resources", BHR_MK_TILE, ss, out, 1); }
 int32_t bhr_projected_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_projected_resources", BHR_MK_TILE, ss, out, 2); }
+int32_t bhr_delayed_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_delayed_resources", BHR_MK_TILE, ss, out, 3); }
 
 int32_t bhr_kerr_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_kerr_resources", BHR_MK_TILE, ss, out); }
 // ... of the kernels of a redshift mode (bhr_set_redshift)

@@ -232,7 +232,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  dither: str = "none", grade: Optional[dict] = None, hdr_path: Optional[str] = None,
                  passes_path: Optional[str] = None, spin: float = 0.0, redshift: str = "model",
                  observer=None, observer_sky: bool = True, stars: Optional[dict] = None,
-                 projection: Optional[str] = None, projection_fov=None) -> np.ndarray:
+                 projection: Optional[str] = None, projection_fov=None, light_delay=None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -253,8 +253,13 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     arithmetic whatever ``math`` says.  ``projection``: "equirect" or "fisheye" with ``projection_fov`` in degrees
     (HipRenderer.render_async; bhr_amd.projection): the width x height frame through that camera instead of the pinhole, ``fov``
     unused (bhr_amd.projection.frame_size is the command line's size rule); combines with ``observer`` and takes what it takes
-    (check_projection)."""
+    (check_projection).  ``light_delay``: a scale in [0, 16] -- every disk crossing shaded at the time its light left the gas
+    (HipRenderer.render_async; 1 is physical); one device, the texture source, the strict Schwarzschild march of the pinhole
+    camera that stands still (check_light_delay)."""
     check_depth_and_dither(bit_depth, dither)
+    check_light_delay(light_delay, anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus,
+                      spin=spin, redshift=redshift, observer=observer is not None, projection=projection is not None,
+                      passes=passes_path is not None, stars=stars is not None)
     check_projection(projection, projection_fov, anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold,
                      gpus=gpus, spin=spin, redshift=redshift, passes=passes_path is not None, stars=stars is not None)
     stars = check_stars(stars, skybox_path=skybox_path, supersample=supersample, spin=spin, redshift=redshift, gpus=gpus,
@@ -307,7 +312,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
               f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
     else:
         img = renderer.render(cam_pos, fov, frame=0, **({} if observer is None else {"observer": observer, "observer_sky": observer_sky}),
-                              **({} if projection is None else {"projection": projection, "projection_fov": projection_fov}))
+                              **({} if projection is None else {"projection": projection, "projection_fov": projection_fov}),
+                              **({} if light_delay is None else {"light_delay": light_delay}))
     if hdr_path is not None:
         save_hdr(renderer.read_hdr(), hdr_path)
     c = renderer.counters()
@@ -386,6 +392,48 @@ def check_projection(projection, projection_fov=None, anti_alias="disabled", dis
         raise ValueError("a projection writes no passes: a ray map holds the rays of the pinhole camera")
     if stars:
         raise ValueError("a projection does not combine with point stars: they are rendered through a ray map of the pinhole camera")
+    return out
+
+
+def check_light_delay(scale, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None, gpus: int = 1,
+                      world: int = 1, spin: float = 0.0, redshift: str = "model", observer: bool = False, projection: bool = False,
+                      passes: bool = False, shutter: float = 0.0, maps: bool = False, stars: bool = False):
+    """What a frame with light delay takes: a scale in [0, 16], one device and one rank, the texture disk source, the
+    Schwarzschild hole with the model redshift, the pinhole camera that stands still, marched frames without anti-aliasing,
+    adaptive supersampling, shutter, ray map or point stars.  Raises ValueError, naming the combination, before any device work;
+    -> the scale as a float, or None without one (nothing is checked)."""
+    if scale is None:
+        return None
+    try:
+        out = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"light_delay is a scale in [0, 16], got {scale!r}") from None
+    if not 0.0 <= out <= 16.0:            # a NaN fails the comparison too
+        raise ValueError(f"light_delay is a scale in [0, 16], got {scale!r}")
+    if anti_alias not in ("disabled", 0, False, None):
+        raise ValueError("light_delay does not combine with anti_alias: the delayed march has no ray differentials")
+    if disk_model != "texture":
+        raise ValueError("light_delay does not combine with disk_model v2 / v2_volume: the delayed march shades the disk texture")
+    if supersample_threshold is not None:
+        raise ValueError("light_delay does not combine with supersample_threshold: the delayed march has no refinement kernels (plain supersample works)")
+    if gpus != 1:
+        raise ValueError("light_delay renders on one GPU: row-block tiles march without the light's travel time")
+    if world != 1:
+        raise ValueError("light_delay renders on one rank: frame-sharded ranks march without the light's travel time")
+    if spin != 0 or redshift != "model":
+        raise ValueError("light_delay does not combine with a spin or the exact redshift: the delayed march is Schwarzschild's, with the model redshift")
+    if observer:
+        raise ValueError("light_delay does not combine with a moving observer: the delayed march is the camera's that stands still")
+    if projection:
+        raise ValueError("light_delay does not combine with a projection: the delayed march is the pinhole camera's")
+    if passes:
+        raise ValueError("light_delay writes no passes: a ray map's records hold no travel time")
+    if shutter > 0:
+        raise ValueError("light_delay does not combine with shutter: shutter frames march without the light's travel time")
+    if maps:
+        raise ValueError("light_delay does not combine with ray_map, orbit_map or shutter_map: a ray map's records hold no travel time")
+    if stars:
+        raise ValueError("light_delay does not combine with point stars: they are rendered through a ray map, whose records hold no travel time")
     return out
 
 
@@ -612,7 +660,7 @@ def hdr_sidecar(hdr: dict, max_cll: float, max_fall: float, frames: int) -> dict
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
                     shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None,
-                    stars=None, projection=None) -> dict:
+                    stars=None, projection=None, light_delay=None) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -644,6 +692,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(stars=dict(stars))
     if projection is not None:
         params.update(projection=projection)
+    if light_delay is not None:
+        params.update(light_delay=light_delay)
     return params
 
 
@@ -683,7 +733,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  map_supersample: int = 1, video_hdr: Optional[str] = None, hdr_white: float = 203.0, hdr_exposure: float = 0.0,
                  observer: Optional[str] = None, observer_velocity=None, observer_sky: bool = True,
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
-                 **_deprecated_kwargs) -> None:
+                 light_delay=None, **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -786,7 +836,12 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     width x height frames through that camera instead of the pinhole, ``fov`` unused -- from the moving camera when an observer
     is given as well.  Refused with ValueError, before any device work, with what check_projection names.  The progress record
     carries the projection when one is given, and a resume under another starts over.  A full-sphere equirect video muxed by
-    this package (Motion-JPEG, PNG-in-MP4) carries the Spherical Video V1 box (assemble_video)."""
+    this package (Motion-JPEG, PNG-in-MP4) carries the Spherical Video V1 box (assemble_video).
+
+    ``light_delay`` (a scale in [0, 16]): every frame is render_async(..., light_delay=scale) with the frame's own camera
+    position and t_offset, with and without ``orbit`` -- each disk crossing shaded at the time its light left the gas.  Refused
+    with ValueError, before any device work, with what check_light_delay names.  The progress record carries the scale when one
+    is given, and a resume under another starts over."""
     moving = observer is not None or observer_velocity is not None
     plan = None
     if moving or infall_to is not None:
@@ -807,6 +862,13 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                                 disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2", supersample_threshold=thr,
                                 world=world, spin=renderer.spin, redshift=renderer.redshift, shutter=shutter,
                                 maps=ray_map or orbit_map or shutter_map, stars=stars is not None)
+    if light_delay is not None:
+        thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
+        light_delay = check_light_delay(light_delay, anti_alias=renderer.anti_alias,
+                                        disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2", supersample_threshold=thr,
+                                        world=world, spin=renderer.spin, redshift=renderer.redshift, observer=moving or infall_to is not None,
+                                        projection=projection is not None or projection_fov is not None, shutter=shutter,
+                                        maps=ray_map or orbit_map or shutter_map, stars=stars is not None)
     check_map_supersample(map_supersample, ray_map, orbit_map, shutter_map)
     check_shutter(shutter, shutter_samples)
     if video_stream not in ("auto", "y4m", "off"):
@@ -862,7 +924,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                              observer=None if plan is None else {"kind": observer, "velocity": None if observer_velocity is None else list(observer_velocity),
                                                                  "sky": bool(observer_sky), "infall_to": infall_to},
                              **({} if stars is None else {"stars": stars}),
-                             **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}))
+                             **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}),
+                             **({} if light_delay is None else {"light_delay": light_delay}))
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -1000,6 +1063,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                                   **({} if plan is None else {"observer": beta, "observer_sky": observer_sky}))
         elif plan is not None:
             renderer.render_async(cam_pos, fov, frame=0, observer=beta, observer_sky=observer_sky)
+        elif light_delay is not None:                      # every crossing at its emission time
+            renderer.render_async(cam_pos, fov, frame=0, light_delay=light_delay)
         else:
             renderer.render_async(cam_pos, fov, frame=0)   # lens flare, when enabled, is applied on the device
         sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))

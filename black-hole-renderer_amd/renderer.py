@@ -457,7 +457,7 @@ class HipRenderer:
 
     def render_async(self, cam_pos, fov: float, frame: int = 0, skip_differentials: bool = False,
                      skip_bloom: bool = False, compaction: bool = False, math=None, lens_flare=None,
-                     observer=None, observer_sky: bool = True, projection=None, projection_fov=None) -> None:
+                     observer=None, observer_sky: bool = True, projection=None, projection_fov=None, light_delay=None) -> None:
         """Launch march + bloom + combine; the frame stays in HBM (counterpart of render_to_field,
         render.py:3819-3863, without the GUI flip).
 
@@ -471,7 +471,20 @@ class HipRenderer:
         instead of the pinhole (bhr_render_projected; include/bhr.h states the model, bhr_amd.projection the arguments).
         ``projection_fov``: (h, v) degrees for equirect, (full_angle,) for fisheye; None: (360, 180) and (180,).  ``fov`` is then
         unused.  Combines with ``observer``; without one the camera stands still.  Marched by the projected kernel whatever
-        ``math`` the renderer has (``math=`` here is refused).  None (the default): the pinhole camera, as ever."""
+        ``math`` the renderer has (``math=`` here is refused).  None (the default): the pinhole camera, as ever.
+
+        ``light_delay``: a scale in [0, 16] -- every disk crossing is shaded at the time its light left the gas, the texture's
+        roll under t_offset - scale * T with T the coordinate time along the ray (bhr_render_delayed; include/bhr.h states the
+        model).  1 is physical, larger values exaggerate, 0 is the strict frame.  Marched by the delayed kernel whatever ``math``
+        the renderer has; refused together with ``observer``, ``projection`` or ``math=``.  The scale belongs to this call
+        alone.  None (the default): the whole disk at the frame's one instant, as ever."""
+        if light_delay is not None:
+            if observer is not None or projection is not None or math is not None:
+                raise ValueError("light_delay does not combine with observer, projection or math=: the delayed march is the strict "
+                                 "Schwarzschild march of the pinhole camera that stands still")
+            scale = float(light_delay)
+            if not 0.0 <= scale <= 16.0:          # a NaN fails the comparison too
+                raise ValueError(f"light_delay = {light_delay!r}: a scale in [0, 16]")
         if projection is not None:
             from . import projection as proj_mod
             kind, fov_h, fov_v = proj_mod.check(projection, projection_fov)
@@ -485,6 +498,10 @@ class HipRenderer:
             obs = _lib.Observer()
             obs.beta[:] = obs_mod.check_beta(observer)
             obs.sky_shift = 1 if observer_sky else 0
+        if light_delay is not None:
+            d = _lib.LightDelay(scale, 0)
+            _lib.check(self._lib.bhr_render_delayed(self._ctx, C.byref(cam), C.byref(d), flags))
+            return
         if projection is not None:
             proj = _lib.Projection(_lib.PROJ_EQUIRECT if kind == "equirect" else _lib.PROJ_FISHEYE, fov_h, fov_v, 0)
             _lib.check(self._lib.bhr_render_projected(self._ctx, C.byref(cam), C.byref(proj), None if observer is None else C.byref(obs), flags))
@@ -765,6 +782,12 @@ class HipRenderer:
             _lib.check(self._lib.bhr_kerr_redshift_resources(_lib.REDSHIFT_EXACT, 1 if supersampled else 0, out))
         return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
 
+    def delayed_resources(self, supersampled: bool = False) -> dict:
+        """Registers per lane, LDS and scratch bytes of the delayed march kernel (bhr_delayed_resources)."""
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_delayed_resources(1 if supersampled else 0, out))
+        return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
+
     def observer_resources(self, supersampled: bool = False) -> dict:
         """Registers per lane, LDS and scratch bytes of the observer march kernel (bhr_observer_resources)."""
         out = (C.c_int32 * 3)()
@@ -895,14 +918,16 @@ class HipRenderer:
 
     def render(self, cam_pos: List[float], fov: float, frame: int = 0,
                skip_differentials: bool = False, skip_bloom: bool = False, observer=None, observer_sky: bool = True,
-               projection=None, projection_fov=None) -> np.ndarray:
+               projection=None, projection_fov=None, light_delay=None) -> np.ndarray:
         """One frame -> (rows, width, 3) float32 in [0, 1]  (render.py:3865-3923).  ``observer``, ``observer_sky``: a moving
-        camera, ``projection``, ``projection_fov``: an equirect or fisheye camera, as render_async takes them."""
+        camera, ``projection``, ``projection_fov``: an equirect or fisheye camera, ``light_delay``: the scale of the light
+        delay, as render_async takes them."""
         if self.lens_flare and self.rows != self.height:
             raise ValueError("lens flare needs whole-frame sums; render row blocks through "
                              "bhr_amd.multigpu.group_render(..., lens_flare=True)")
         self.render_async(cam_pos, fov, frame, skip_differentials, skip_bloom, observer=observer, observer_sky=observer_sky,
-                          **({} if projection is None else {"projection": projection, "projection_fov": projection_fov}))
+                          **({} if projection is None else {"projection": projection, "projection_fov": projection_fov}),
+                          **({} if light_delay is None else {"light_delay": light_delay}))
         return self.read_layer(_lib.LAYER_FINAL)
 
     def selftest(self) -> dict:

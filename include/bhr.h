@@ -632,6 +632,40 @@ BHR_API int32_t bhr_render_projected(bhr_ctx *ctx, const bhr_camera *cam, const 
 /* out = {VGPRs per lane, LDS bytes per block, scratch bytes per lane} of the projected march kernel (supersampled != 0: of its
  * supersampled twin), from hipFuncGetAttributes.  No context. */
 BHR_API int32_t bhr_projected_resources(int32_t supersampled, int32_t out[3]);
+/* Light delay: one frame in which every disk crossing is shaded at the coordinate time its light LEFT the gas, not at the frame's
+ * one instant.  Units r_s = 1, c = 1: t_offset is coordinate time in r_s / c.  The strict Schwarzschild march integrates
+ * x'' = -1.5 L^2 x / r^5 with |d| = 1 at the camera; along that parameter l a null geodesic has energy
+ * E = sqrt(1 - L^2 / r_cam^3) (L^2 = |d x p|^2 at launch) and dt/dl = E w(r), w(r) = r / (r - 1) with r clamped to
+ * max(r, 1 + 1e-3) as the march clamps it.  The march accumulates, f32, every operation rounded once, no contraction, sqrt and
+ * quotients correctly rounded:
+ *   launch     E = sqrt(1 - L2 / (r2p * r)),  w = wr(r),  T = 0                  wr(r): rs = max(r, 1 + 1e-3); rs / (rs - 1)
+ *   step       from (p, d, r) to (np, nd, rn) under the step's own h:
+ *              m_k = 0.5 * (p_k + np_k) + (0.125 * h) * (d_k - nd_k)             the Hermite midpoint
+ *              rm = sqrt((m.x m.x + m.y m.y) + m.z m.z)
+ *              dT = (E * (h / 6)) * ((w + 4 * wr(rm)) + wr(rn))                  Simpson's rule, fourth order like the RK4
+ *   crossing   T_hit = T + t_frac * dT, t_frac the step's own hit fraction f_old / (f_old - f_new + 1e-8)
+ *   commit     T = T + dT,  w = wr(rn)
+ *   shade      the crossing is shaded exactly as bhr_render shades it, but under t_eff = t_offset - scale * T_hit
+ *              (one product, one difference): the texture's Keplerian roll is phi + t_eff Omega(r).
+ * Redshift, brightness, alpha, the sky, step counts and termination do not see T.  scale = 1 is physical, larger values
+ * exaggerate the delay for teaching, and scale = 0 gives BG, DISK and ray_steps of the strict march bit for bit (T_hit is finite
+ * for every crossing).  The texture stays the frame's: its population and noise do not evolve within the delay.  (DESIGN.md
+ * "Light delay"; tests/delay_ref.py is the CPU reference.)
+ * The frame is bhr_render's in every other respect -- next frame slot, one timing-ring entry, counters, post-pass following the
+ * context's arithmetic, lens flare, grade, HDR plane, u8 / u16 rows, dither, sinks and streams; asynchronous -- and is marched
+ * by the delay object (csrc/march_delay.hip) whatever bhr_config.math_mode is.  The scale travels with the call: frames in flight
+ * may differ in it.  Works with a tilted disk and bhr_set_supersample.  flags: BHR_SKIP_BLOOM, BHR_LENS_FLARE.
+ * BHR_ERR_INVALID with a message that names the combination, nothing launched and the context untouched: a null argument, a NaN,
+ * negative or > 16 scale, reserved != 0, any other flag bit, anti_alias = 1, a Disk V2 source, adaptive supersampling, a spin or
+ * the forced Kerr march (bhr_set_spin) or the exact redshift, a row-block context. */
+typedef struct {
+    float scale;
+    int32_t reserved;
+} bhr_light_delay;
+BHR_API int32_t bhr_render_delayed(bhr_ctx *ctx, const bhr_camera *cam, const bhr_light_delay *d, uint32_t flags);
+/* out = {VGPRs per lane, LDS bytes per block, scratch bytes per lane} of the delayed march kernel (supersampled != 0: of its
+ * supersampled twin), from hipFuncGetAttributes.  No context. */
+BHR_API int32_t bhr_delayed_resources(int32_t supersampled, int32_t out[3]);
 /* The library's switches.  Each has an environment variable that bhr_create reads ONCE (no entry point calls getenv
  * afterwards) and can be changed per context later with this call -- what tests and A/B tools use:
  *   "bloom_split"     BHR_BLOOM_SPLIT     -1 post-pass by arithmetic (exact f32 under strict, split f16 under fast / hybrid), 0 / 1 force
