@@ -111,40 +111,27 @@ struct BhrMarchArgs {
     float ss_inv;            // 1 / k^2
     int32_t out_width, out_rows;   // the output frame's row block: the store pitch and rows of bg / disk / sum
 };
-// The argument block of the Kerr object's kernels (march_kerr.hip): the march's block with the spinning hole's two numbers at
-// its end -- a = A M in r_s, and the horizon radius r_plus = (1 + sqrt(1 - A^2)) / 2 a ray is captured at (0 and 1 without a
-// spin).  A block of its own, because BhrMarchArgs is the whole explicit argument of every other march kernel: one more
-// field in it moves their hidden arguments, and with them the code of all of them (tools/code_object_diff.py).  The launcher
-// builds this block for every launch; the other kernels read its first sizeof(BhrMarchArgs) bytes.
-struct BhrKerrMarchArgs : BhrMarchArgs {
-    float kerr_a, kerr_rplus;
+// The argument blocks of the march variants' kernels (bhr_march_variant): each the march's block with the variant's own words
+// behind it, binary64 on the host rounded once, filled for a launch of that variant alone (march_launch.hip: variant_args).  Blocks
+// of their own, because BhrMarchArgs is the whole explicit argument of every other march kernel: one more field in it moves
+// their hidden arguments, and with them the code of all of them (tools/code_object_diff.py).
+struct BhrKerrMarchArgs : BhrMarchArgs {          // march_kerr.hip
+    float kerr_a, kerr_rplus;                     // a = A M in r_s; the horizon radius r_plus = (1 + sqrt(1 - A^2)) / 2 a ray is captured at
 };
-// The argument block of the Kerr object's exact-redshift kernels (bhr_set_redshift, BHR_REDSHIFT_EXACT): the Kerr block with
-// the ISCO of the disk's sense of rotation behind it -- its radius and the energy -u_t and angular momentum u_phi of its
-// orbit, which the gas inside it keeps (ray_kerr.h: kerr_g_exact).  Again a block of its own, for the reason above: the two
-// model kernels take BhrKerrMarchArgs by value and stay what they were.
-struct BhrKerrExactMarchArgs : BhrKerrMarchArgs {
-    float isco_r, isco_e, isco_l;
+struct BhrKerrExactMarchArgs : BhrKerrMarchArgs { // ... its exact-redshift kernels (the model ones keep the block above)
+    float isco_r, isco_e, isco_l;                 // the ISCO of the disk's sense of rotation: its radius, and the energy -u_t and angular
+};                                                // momentum u_phi of its orbit, which the gas inside it keeps (ray_kerr.h: kerr_g_exact)
+struct BhrObserverMarchArgs : BhrMarchArgs {      // march_observer.hip
+    float obs_beta[3];                            // the moving camera's velocity,
+    float obs_gamma, obs_g2;                      // gamma and gamma^2 / (gamma + 1),
+    int32_t obs_sky_shift;                        // and whether the sky sample takes the Doppler factor
 };
-// The argument block of the observer object's kernels (march_observer.hip; bhr_render_observer): the march's block with the
-// moving camera behind it -- its velocity, gamma and gamma^2 / (gamma + 1) (binary64 on the host, each rounded once) and
-// whether the sky sample takes the Doppler factor.  A block of its own for the Kerr block's reason: BhrMarchArgs does not grow.
-struct BhrObserverMarchArgs : BhrMarchArgs {
-    float obs_beta[3];
-    float obs_gamma, obs_g2;
-    int32_t obs_sky_shift;
+struct BhrProjectedMarchArgs : BhrObserverMarchArgs {   // march_projected.hip
+    int32_t proj_kind;                            // BHR_PROJ_*
+    float span_h, span_v;                         // radians: the equirectangular frame's spans; the fisheye's HALF angle in span_h (ray_projected.h)
 };
-// The argument block of the projected object's kernels (march_projected.hip; bhr_render_projected): the observer's block with the
-// projection behind it -- its kind (BHR_PROJ_*) and its spans in radians, binary64 on the host rounded once: the equirectangular
-// frame's horizontal and vertical span, the fisheye's HALF angle in span_h (ray_projected.h).
-struct BhrProjectedMarchArgs : BhrObserverMarchArgs {
-    int32_t proj_kind;
-    float span_h, span_v;
-};
-// The argument block of the delay object's kernels (march_delay.hip; bhr_render_delayed): the march's block with the scale of
-// the light delay behind it (ray_delay.h: t_eff = t_offset - delay_scale * T_hit).  A block of its own, as the observer's is.
-struct BhrDelayMarchArgs : BhrMarchArgs {
-    float delay_scale;
+struct BhrDelayMarchArgs : BhrMarchArgs {         // march_delay.hip
+    float delay_scale;                            // ray_delay.h: t_eff = t_offset - delay_scale * T_hit
 };
 
 // A partial march launch: the tiles of `d_list` only.  bhr_launch_march_hybrid builds one for each of its launches (strict
@@ -160,6 +147,19 @@ struct bhr_march_part {
     int32_t fix_cap;
 };
 
+// The marches that are not the Schwarzschild pinhole march of a camera at rest: each one object over a ray_*.h (march_device.h)
+// with the tile schedule, the texture source, no differentials, and a row of what the host knows of it (bhr_variant_row).
+enum bhr_march_variant { BHR_MV_NONE, BHR_MV_KERR, BHR_MV_KERR_EXACT, BHR_MV_OBSERVER, BHR_MV_PROJECTED, BHR_MV_DELAYED, BHR_MV_COUNT };
+
+// What a frame's entry point (render.hip) asks of the march: the variant and its payload -- a projection comes with an observer
+// (at rest if the caller gave none), light delay with neither, none of them with a spin (bhr_variant_frame_check refuses it).
+struct bhr_variant_request {
+    bhr_march_variant variant = BHR_MV_NONE;
+    const bhr_observer *observer = nullptr;       // BHR_MV_OBSERVER, BHR_MV_PROJECTED: the camera's velocity
+    const bhr_projection *projection = nullptr;   // BHR_MV_PROJECTED
+    const bhr_light_delay *delay = nullptr;       // BHR_MV_DELAYED: the scale
+};
+
 // One march call, built by the caller: what bhr_launch_march, bhr_launch_march_hybrid and bhr_launch_adaptive work from.
 struct bhr_march_call {
     const bhr_camera *cam;
@@ -170,9 +170,7 @@ struct bhr_march_call {
     bool defer_end;          // the caller records the march-end event (adaptive frames: the refinement follows the base march)
     int32_t ss;              // supersampling factor of the frame being marched
     bool keep_start;         // a later sample of a shutter frame (bhr_render_shutter): the march-start event stays the first sample's
-    const bhr_observer *observer = nullptr;   // bhr_render_observer: the frame is marched by the observer object for this moving camera
-    const bhr_projection *projection = nullptr;   // bhr_render_projected (observer is set too): the projected object marches it under this projection
-    const bhr_light_delay *delay = nullptr;   // bhr_render_delayed: the frame is marched by the delay object under this scale
+    bhr_variant_request req;    // the variant whose object marches the frame, resolved by the frame's entry point (none: the rest of this file's marches)
 };
 
 // The march kernels by what they do; each march object returns its own instantiation of a name (or null) from
@@ -206,6 +204,19 @@ enum bhr_march_kernel {
     BHR_MK_RAYMAP_SHADE_STARS,      // raymap_shade_kernel<diff, false, true>                                     raymap
     BHR_MK_RAYMAP_SHADE_STARS_ROT,  // raymap_shade_kernel<diff, true, true>                                      raymap
     // (ss: BUILD, SHADE and SHADE_ROT have twins for a supersampled map, raymap_build_kernel<DIFF, true> / raymap_shade_ss_kernel; the shutter kernels have none)
+};
+
+// The row of a march variant (settings.hip: bhr_variant_row_of): its kernels, and the terms and words of its refusals.
+struct bhr_variant_row {
+    const void *(*kernels)(bhr_march_kernel, int32_t diff, int32_t ss);   // the object's kernel table (diff 0 only) ...
+    bhr_march_kernel name;       // ... and the name its frame kernel is asked for under
+    const char *noun;            // what a refusal calls the request (a format of the spin: the Kerr rows print it)
+    const char *march;           // "the <march> march shades the disk texture", "... has no refinement kernels", "... is Schwarzschild's"
+    const char *no_diff;         // why it takes no anti-aliasing
+    const char *no_exact;        // why it takes no exact redshift (the Kerr rows: null)
+    const char *no_rows;         // why it takes no row-block context
+    uint32_t flags_ok;           // the flags of a call it accepts
+    bool kerr;                   // the spinning hole's: refuses a tilted disk; the others refuse a spin and the exact redshift
 };
 
 // The ray map as its two kernels see it (march_raymap.hip): second kernel argument, behind the march's own block.  Planar: every
@@ -642,10 +653,15 @@ int32_t bhr_streams_share_queue(hipStream_t a, hipStream_t b, int32_t *share);  
 // picks slot 1's stream by timing candidates on frames of (cam, flags) through bhr_render; once per two-slot context
 int32_t bhr_calibrate_slot_streams(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
 
-// ---- settings.hip: the refusals of a context with a spin set (kerr_on); BHR_OK without one ------------------------------------------
-// BHR_ERR_INVALID naming the combination -- the context's own state (tilt, anti-aliasing, Disk V2, adaptive supersampling) and
-// `flags` of the call; `who`: the entry point
-int32_t bhr_kerr_check(const bhr_ctx *ctx, uint32_t flags, const char *who);
+// ---- settings.hip: the march variants' table and their refusals -----------------------------------------------------------------------
+const bhr_variant_row &bhr_variant_row_of(bhr_march_variant v);   // the table
+// the variant of a frame: what its entry point asks for, else what the context is set to (a spin, the exact redshift) -- the
+// one place that reads kerr_on for it; everything else switches on the result
+bhr_march_variant bhr_variant_of(const bhr_ctx *ctx, bhr_march_variant asked = BHR_MV_NONE);
+int32_t bhr_note_frame_kernel(bhr_ctx *ctx);                               // its registers / LDS into the counters (bhr_create, bhr_set_spin, bhr_set_redshift)
+// what a frame of variant v does not combine with: BHR_ERR_INVALID naming it -- `flags` of the call, the context's state (tilt,
+// anti-aliasing, Disk V2, adaptive supersampling, spin and redshift, row block).  spin: a / M as printed (bhr_set_spin: the candidate)
+int32_t bhr_variant_frame_check(const bhr_ctx *ctx, bhr_march_variant v, uint32_t flags, const char *who, double spin);
 // a call that has no Kerr form at all (ray maps, shutter frames, group and tile renders): BHR_ERR_INVALID with a spin set
 int32_t bhr_kerr_refuse(const bhr_ctx *ctx, const char *who, const char *what);
 // a camera inside the static limit: BHR_ERR_INVALID, before anything is launched
@@ -659,7 +675,8 @@ int32_t bhr_fold_cells(bhr_ctx *ctx, const unsigned long long *cells, int n, uns
 // ---- march_launch.hip and the march objects (each table lives next to its kernels) ----------------------------------------------------
 int32_t bhr_resolve_math(const bhr_ctx *ctx, uint32_t flags);                          // BHR_MATH_* of a frame
 int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part = nullptr);   // every march launch
-int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds); // registers / LDS of the frame kernel
+// {VGPRs, LDS, scratch bytes} of the kernel that marches a whole texture frame: variant v's, or without one the arithmetic's
+int32_t bhr_march_resources(const char *who, bhr_march_variant v, int32_t math, int32_t diff, int32_t ss, int32_t out[3]);
 int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss);                               // builds d_/h_tile_order of the frame marched with factor ss
 // detect + refinement (ctx->ada_k) of an adaptively supersampled frame, behind its base march `call` on the same stream; records the march-end event
 int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call);

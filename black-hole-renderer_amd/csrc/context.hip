@@ -161,13 +161,9 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
     if (hipMemsetAsync(ctx->d_ray_steps, 0, sizeof(unsigned long long) * BHR_STEP_CELL, ctx->stream) != hipSuccess ||
         hipMemsetAsync(ctx->d_steps_ring, 0, sizeof(unsigned long long) * BHR_TIMING_RING * BHR_STEP_CELL, ctx->stream) != hipSuccess)
         return bail(bhr_fail(BHR_ERR_HIP, "hipMemsetAsync failed"));
-    int32_t v = 0, l = 0;
     if (cfg->math_mode != BHR_MATH_FAST && cfg->math_mode != BHR_MATH_STRICT && cfg->math_mode != BHR_MATH_HYBRID)
         return bail(bhr_fail(BHR_ERR_INVALID, "bhr_create: math_mode %d", cfg->math_mode));
-    if (bhr_march_resources(cfg->math_mode, cfg->anti_alias != 0, &v, &l) == BHR_OK) {
-        ctx->counters.march_vgprs = v;
-        ctx->counters.march_lds_bytes = l;
-    }
+    (void)bhr_note_frame_kernel(ctx);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail(bhr_fail(BHR_ERR_HIP, "stream sync failed"));
     *out = ctx;
     return BHR_OK;

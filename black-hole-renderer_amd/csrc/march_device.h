@@ -25,20 +25,12 @@
 // v_rsq/v_rcp/v_sqrt instead of IEEE sqrt + divide inside the RK4 stages, FMA contraction, and the
 // re-use of |new_pos| as the next step's |pos| (same value in the reference).
 //
-// The march's device source is nine headers and eight translation units, one per object (csrc/Makefile):
+// The march's device source is a header per Ray and per schedule and a translation unit per object (csrc/Makefile):
 //   march_device.h      this file: vectors, exact-rounding sequences, samplers, shading, parking slots, pixel stores
 //   ray_strict.h        Ray<DIFF, SRC>, strict: every operation of the RK4 loop in the reference's order with IEEE sqrt and
 //                       divide, so that positions, step counts and hit points are bit-identical to a strict f32 evaluation
 //                       of render.py:2854-3006 (selected with bhr_config.math_mode = 1)
 //   ray_fast.h          Ray<DIFF, SRC>, fast: v_rsq/v_rcp/v_sqrt, FMA contraction, in-plane state, the ray's own clock
-//   ray_observer.h      Ray<false, 0>, observer: the strict Ray launched along the aberrated pixel direction of a moving camera, its
-//                       Doppler factor in the disk's g and on the sky (bhr_render_observer)
-//   ray_projected.h     Ray<false, 0>, projected: the observer Ray launched along an equirectangular or fisheye pixel direction
-//                       (bhr_render_projected)
-//   ray_delay.h         Ray<false, 0>, delayed: the strict Ray with the light's coordinate time beside it, every disk crossing shaded at
-//                       its emission time (bhr_render_delayed)
-//   ray_kerr.h          Ray<false, 0>, Kerr: a spinning hole in Kerr-Schild coordinates, RK4 on (x, p), its own sampler and g-factor
-//                       (bhr_set_spin); the Schwarzschild Rays above know nothing of it
 //   march_tile.h        the tile schedule: march_tile_body, its plain, supersampled and list kernels
 //   march_persistent.h  the persistent schedule
 //   march.hip            -> march.o             ray_fast.h, both schedules; fast-math
@@ -46,13 +38,18 @@
 //   march_strict_ilp.hip -> march_strict_ilp.o  ray_strict.h, tile schedule: the strict texture kernels and the fix kernel of
 //                                               a hybrid march; the strict flags and the ILP-first machine scheduler
 //   march_raymap.hip     -> march_raymap.o      ray_strict.h: the ray map's build and shade kernels; the ILP object's flags
-//   march_kerr.hip       -> march_kerr.o        ray_kerr.h, tile schedule, plain and supersampled; -ffp-contract=on, no fast-math
-//   march_observer.hip   -> march_observer.o    ray_observer.h, tile schedule, plain and supersampled; the strict flags
-//   march_projected.hip  -> march_projected.o   ray_projected.h, tile schedule, plain and supersampled; the strict flags
-//   march_delay.hip      -> march_delay.o       ray_delay.h, tile schedule, plain and supersampled; the strict flags
+// and per march variant (bhr_internal.h: bhr_march_variant, with a row of what the host knows of it) a ray_<v>.h with a
+// Ray<false, 0> of its own and a march_<v>.hip -> march_<v>.o with the tile schedule's plain and supersampled kernel:
+//   kerr       a spinning hole in Kerr-Schild coordinates, RK4 on (x, p), its own sampler and g-factor, model or exact
+//              (bhr_set_spin, bhr_set_redshift); the Schwarzschild Rays know nothing of it; -ffp-contract=on, no fast-math
+//   observer   the strict Ray launched along the aberrated pixel direction of a moving camera, its Doppler factor in the
+//              disk's g and on the sky (bhr_render_observer); the strict flags, as the next two
+//   projected  the observer Ray launched along an equirectangular or fisheye pixel direction (bhr_render_projected)
+//   delay      the strict Ray with the light's coordinate time beside it, every disk crossing shaded at its emission time
+//              (bhr_render_delayed)
 // A translation unit includes the one Ray header it marches with (which includes this file), then the schedules it uses,
 // defines the kernels that are its own and ends with their table, by which the one host launcher (march_launch.hip) finds
-// them: bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr / _observer / _projected / _delay.
+// them: bhr_march_kernel_fast / _strict / _strict_ilp / _raymap, and bhr_march_kernel_<v> through the variant's row.
 #pragma once
 #include "bhr_internal.h"
 #include "disk_v2_device.h"

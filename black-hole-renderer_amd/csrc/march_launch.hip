@@ -1,13 +1,13 @@
 // march_launch.hip -- the host half of the ray march: every march launch goes through bhr_launch_march.
 //
-// The march's device code is eight objects, each from a source of its own (march.hip fast, march_strict.hip, march_strict_ilp.hip
-// with the ILP-first scheduler, march_raymap.hip, march_kerr.hip, march_observer.hip, march_projected.hip, march_delay.hip; the layout: march_device.h);
-// each object hands its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp / _raymap / _kerr / _observer /
-// _projected / _delay).  This file resolves the
-// arithmetic, builds the kernel arguments, keeps the tile order, the ray-step counters and the timing events, and picks
-// the kernel of a launch (march_kernel).  What a launch works from is in its arguments -- the caller's bhr_march_call
-// (camera, flags, stream, timing slot, end-event policy, supersampling factor) and, for one list of a hybrid march, a
-// bhr_march_part -- never in fields a caller left in the context.
+// The march's device code is one object per source (the layout: march_device.h): march.hip fast, march_strict.hip,
+// march_strict_ilp.hip with the ILP-first scheduler, march_raymap.hip, and one per march variant (bhr_variant_row_of: its row
+// names the object).  Each object hands its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp /
+// _raymap, and the variant rows').  This file resolves the arithmetic, builds the kernel arguments -- a variant's block with
+// its own words behind the march's (variant_args) -- keeps the tile order, the ray-step counters and the timing events, and
+// picks the kernel of a launch (march_kernel).  What a launch works from is in its arguments -- the caller's bhr_march_call
+// (camera, flags, stream, timing slot, end-event policy, supersampling factor, variant request) and, for one list of a hybrid
+// march, a bhr_march_part -- never in fields a caller left in the context.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -68,11 +68,7 @@ float fast_sqrt(float s) {
 // The kernel of a launch and its grid (fn null: the part only records its bracket events).
 //
 //   arithmetic     request                                              kernel (object)
-//   any            a projection (bhr_render_projected)                  march_projected_kernel / march_projected_ss_kernel (projected)
-//   any            a moving observer (bhr_render_observer)              march_observer_kernel / march_observer_ss_kernel (observer)
-//   any            light delay (bhr_render_delayed)                     march_delay_kernel / march_delay_ss_kernel (delay)
-//   any            a spin is set (bhr_set_spin), whole block            march_kerr_kernel / march_kerr_ss_kernel (kerr)
-//   any            ... and the exact redshift (bhr_set_redshift)         march_kerr_exact_kernel / march_kerr_exact_ss_kernel (kerr)
+//   any            a march variant v (call.req.variant), whole block    its row's kernel: kernels(name, 0, ss) of bhr_variant_row_of(v)
 //   any            hybrid part with n <= 0, not the fix list            none
 //   strict         hybrid fix list (part->repair == 2)                  march_fix_kernel<diff> (strict_ilp)
 //   fast / strict  Disk V2 volume source                                march_tile_kernel<false, 2> (own object)
@@ -99,27 +95,16 @@ struct MarchKernel {
     dim3 grid;
     size_t lds = 0;
 };
-MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *part, int math, uint32_t flags, bool diff, bool observer, bool projected, bool delayed) {
+MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *part, int math, uint32_t flags, bool diff, bhr_march_variant v) {
     MarchKernel k;
     k.grid = dim3((a.n_list + 3) / 4);
     const bool persistent = (flags & BHR_PERSISTENT) != 0;
     const int ss = a.ss > 1;                                   // the supersampled twins (bhr_render refuses the schedules they lack)
     const auto own = math == BHR_MATH_FAST ? bhr_march_kernel_fast : bhr_march_kernel_strict;
-    // the moving observer (bhr_render_observer): the observer object's march, on the same terms as the spinning hole's below
-    if (observer) {
-        // (a projection, bhr_render_projected, is an observer's frame marched by the projected object)
-        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = (projected ? bhr_march_kernel_projected : bhr_march_kernel_observer)(BHR_MK_TILE, diff, ss);
-        return k;
-    }
-    // light delay (bhr_render_delayed): the delay object's march, on the same terms
-    if (delayed) {
-        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = bhr_march_kernel_delay(BHR_MK_TILE, diff, ss);
-        return k;
-    }
-    // the spinning hole: one arithmetic, one schedule, no lists (what has no Kerr form was refused before anything was launched)
-    if (ctx->kerr_on) {
-        if (!part && !persistent && !a.row_steps && !a.dv2)
-            k.fn = bhr_march_kernel_kerr(ctx->kerr_redshift == BHR_REDSHIFT_EXACT ? BHR_MK_KERR_EXACT : BHR_MK_TILE, diff, ss);
+    // a variant: one arithmetic, one schedule, no lists (what it has no form for was refused before anything was launched)
+    if (v != BHR_MV_NONE) {
+        const bhr_variant_row &r = bhr_variant_row_of(v);
+        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = r.kernels(r.name, diff, ss);
         return k;
     }
     if (part && part->n <= 0 && part->repair != 2) return k;
@@ -186,17 +171,20 @@ int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss) {
     return ensure_tile_order(ctx, ss, tiles_x, tiles_x * ((fr.rows + 7) / 8));
 }
 
-// registers / LDS of the kernel that marches a whole texture frame: the fast object's under fast arithmetic, the ILP
-// object's under strict and hybrid (bhr_create reports them); math -1: the Kerr object's (bhr_set_spin), -2: its
-// exact-redshift kernel's (bhr_set_redshift)
-int32_t bhr_march_resources(int32_t math, int32_t diff, int32_t *vgprs, int32_t *lds) {
-    const void *f = math < 0                 ? bhr_march_kernel_kerr(math == -2 ? BHR_MK_KERR_EXACT : BHR_MK_TILE, 0, 0)
-                    : math == BHR_MATH_FAST ? bhr_march_kernel_fast(BHR_MK_TILE, diff, 0)
-                                            : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff, 0);
+// {VGPRs, LDS bytes, scratch bytes per lane} of the kernel that marches a whole texture frame (ss: its supersampled twin): variant
+// v's own, else the fast object's under fast arithmetic, the ILP object's under strict and hybrid.  No context: host + hipFuncGetAttributes.
+int32_t bhr_march_resources(const char *who, bhr_march_variant v, int32_t math, int32_t diff, int32_t ss, int32_t out[3]) {
+    if (!out) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    const bhr_variant_row &r = bhr_variant_row_of(v);
+    const void *f = v != BHR_MV_NONE         ? r.kernels(r.name, 0, ss ? 1 : 0)
+                    : math == BHR_MATH_FAST ? bhr_march_kernel_fast(BHR_MK_TILE, diff, ss ? 1 : 0)
+                                            : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff, ss ? 1 : 0);
+    if (!f) return bhr_fail(BHR_ERR_STATE, "%s: no such march kernel in this library", who);
     hipFuncAttributes at;
     BHR_HIP(hipFuncGetAttributes(&at, f));
-    *vgprs = at.numRegs;
-    *lds = (int32_t)at.sharedSizeBytes;
+    out[0] = at.numRegs;
+    out[1] = (int32_t)at.sharedSizeBytes;
+    out[2] = (int32_t)at.localSizeBytes;
     return BHR_OK;
 }
 
@@ -307,32 +295,27 @@ static void layers_stored(bhr_ctx *ctx, const BhrMarchArgs &a) {
     if (a.sum) f.sum_valid = 1;       // the split-f16 post-pass's bg + disk plane comes with the layers
 }
 
-int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part) {
-    const uint32_t flags = call.flags;
-    const hipStream_t stream = call.stream;
-    // a partial launch (part: one list of a hybrid march) marches the tiles of a caller-made list under the arithmetic the
-    // caller chose; the first part records the start event and clears an untimed counter, the last part records the end event
-    // with a spin set the context's math mode does not select the march: one launch of the Kerr object, its argument block the
-    // strict one's (the post-pass has followed the math mode, bhr_frame_begin)
-    // (likewise the frame of a moving observer, bhr_render_observer: one launch of the observer object; and a frame with light
-    // delay, bhr_render_delayed: one launch of the delay object)
-    const int math = part ? part->math : (ctx->kerr_on || call.observer || call.delay) ? BHR_MATH_STRICT : bhr_resolve_math(ctx, flags);
-    if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, call);
-    const bool fast = math == BHR_MATH_FAST;
-    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
-    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_render: no disk texture set (bhr_set_disk_texture)");
-
-    BhrKerrExactMarchArgs a;            // the march's block, and behind it what the Kerr object's kernels alone read
-    march_args(ctx, call, part, call.ss, fast, a);
-    layers_stored(ctx, a);
-    {   // the spinning hole: a = A M with M = r_s / 2 and the horizon's radius, in binary64, each rounded once
-        const double A = ctx->kerr_on ? (double)ctx->kerr_spin : 0.0;
-        a.kerr_a = (float)(0.5 * A);
-        a.kerr_rplus = (float)(0.5 * (1.0 + sqrt(1.0 - A * A)));
+// The first kernel argument of a launch: the finished march block `a` itself, or for a variant `a` copied into the variant's own
+// block in `b` with its words behind it -- binary64, each rounded once (the variant's kernels take this block; nobody else reads it).
+union VariantArgs {
+    BhrKerrExactMarchArgs kerr;       // the model kernels read its first sizeof(BhrKerrMarchArgs) bytes
+    BhrProjectedMarchArgs observer;   // the observer's kernels its first sizeof(BhrObserverMarchArgs)
+    BhrDelayMarchArgs delay;
+};
+static void *variant_args(const bhr_ctx *ctx, const bhr_variant_request &req, BhrMarchArgs &a, VariantArgs &b) {
+    switch (req.variant) {
+    case BHR_MV_KERR:
+    case BHR_MV_KERR_EXACT: {
+        BhrKerrExactMarchArgs &k = b.kerr;
+        static_cast<BhrMarchArgs &>(k) = a;
+        // the spinning hole: a = A M with M = r_s / 2 and the horizon's radius
+        const double A = (double)ctx->kerr_spin;
+        k.kerr_a = (float)(0.5 * A);
+        k.kerr_rplus = (float)(0.5 * (1.0 + sqrt(1.0 - A * A)));
         // ... and, for the exact-redshift kernels alone, the ISCO of the disk's sense of rotation (prograde for A >= 0) with the
         // energy and angular momentum of its orbit (Bardeen, Press, Teukolsky 1972; M = 1/2, signed a, an orbit in the +phi sense)
-        a.isco_r = a.isco_e = a.isco_l = 0.0f;
-        if (ctx->kerr_on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT) {
+        k.isco_r = k.isco_e = k.isco_l = 0.0f;
+        if (req.variant == BHR_MV_KERR_EXACT) {
             const double M = 0.5, sa = 0.5 * A, q = fabs(A);
             const double z1 = 1.0 + cbrt(1.0 - q * q) * (cbrt(1.0 + q) + cbrt(1.0 - q));
             const double z2 = sqrt(3.0 * q * q + z1 * z1);
@@ -340,11 +323,61 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
             const double r = M * (A >= 0.0 ? 3.0 + z2 - root : 3.0 + z2 + root);
             const double sm = sqrt(M), sr = sqrt(r);
             const double den = pow(r, 0.75) * sqrt(r * sr - 3.0 * M * sr + 2.0 * sa * sm);
-            a.isco_r = (float)r;
-            a.isco_e = (float)((r * sr - 2.0 * M * sr + sa * sm) / den);
-            a.isco_l = (float)(sm * (r * r - 2.0 * sa * sm * sr + sa * sa) / den);
+            k.isco_r = (float)r;
+            k.isco_e = (float)((r * sr - 2.0 * M * sr + sa * sm) / den);
+            k.isco_l = (float)(sm * (r * r - 2.0 * sa * sm * sr + sa * sa) / den);
         }
+        return &k;
     }
+    case BHR_MV_OBSERVER:
+    case BHR_MV_PROJECTED: {
+        BhrProjectedMarchArgs &o = b.observer;
+        static_cast<BhrMarchArgs &>(o) = a;
+        // the camera's velocity, gamma and gamma^2 / (gamma + 1)
+        const float *beta = req.observer->beta;
+        const double gamma = 1.0 / sqrt(1.0 - ((double)beta[0] * beta[0] + (double)beta[1] * beta[1] + (double)beta[2] * beta[2]));
+        for (int c = 0; c < 3; ++c) o.obs_beta[c] = beta[c];
+        o.obs_gamma = (float)gamma;
+        o.obs_g2 = (float)(gamma * gamma / (gamma + 1.0));
+        o.obs_sky_shift = req.observer->sky_shift ? 1 : 0;
+        // a projection: its kind and its spans in radians behind that
+        o.proj_kind = 0;
+        o.span_h = o.span_v = 0.0f;
+        if (req.variant == BHR_MV_PROJECTED) {
+            const bhr_projection *pr = req.projection;
+            const double rad = 3.14159265358979323846 / 180.0;
+            o.proj_kind = pr->kind;
+            o.span_h = pr->kind == BHR_PROJ_FISHEYE ? (float)((double)pr->fov_h_deg * rad / 2.0) : (float)((double)pr->fov_h_deg * rad);
+            o.span_v = pr->kind == BHR_PROJ_FISHEYE ? 0.0f : (float)((double)pr->fov_v_deg * rad);
+        }
+        return &o;
+    }
+    case BHR_MV_DELAYED:
+        static_cast<BhrMarchArgs &>(b.delay) = a;
+        b.delay.delay_scale = req.delay->scale;
+        return &b.delay;
+    default:
+        return &a;
+    }
+}
+
+int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_march_part *part) {
+    const uint32_t flags = call.flags;
+    const hipStream_t stream = call.stream;
+    const bhr_march_variant variant = call.req.variant;
+    // a partial launch (part: one list of a hybrid march) marches the tiles of a caller-made list under the arithmetic the
+    // caller chose; the first part records the start event and clears an untimed counter, the last part records the end event
+    // a variant's frame is not selected by the context's math mode: one launch of the variant's object, its argument block the
+    // strict one's (the post-pass has followed the math mode, bhr_frame_begin)
+    const int math = part ? part->math : variant != BHR_MV_NONE ? BHR_MATH_STRICT : bhr_resolve_math(ctx, flags);
+    if (math == BHR_MATH_HYBRID) return bhr_launch_march_hybrid(ctx, call);
+    const bool fast = math == BHR_MATH_FAST;
+    if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "bhr_render: no skybox set (bhr_set_skybox)");
+    if (!ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "bhr_render: no disk texture set (bhr_set_disk_texture)");
+
+    BhrMarchArgs a;
+    march_args(ctx, call, part, call.ss, fast, a);
+    layers_stored(ctx, a);
     const int slot = call.slot;
     const bool first_part = !part || part->first, last_part = !part || part->last;
     if (flags & BHR_ROW_COSTS) {
@@ -381,42 +414,13 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(bhr_slot(ctx).d_queue, 0, sizeof(unsigned int), stream));
     // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
     if (first_part && !call.keep_start) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, slot), stream));
-    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags), call.observer != nullptr, call.projection != nullptr, call.delay != nullptr);
+    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags), variant);
     if (!k.fn && !(part && part->n <= 0 && part->repair != 2))
         return bhr_fail(BHR_ERR_STATE, "bhr_render: no march kernel for this launch (supersampling %d, flags %u)", call.ss, flags);
     if (k.fn) {
         int refill_below = 40;                                 // persistent schedule: refill a wave below 40 live lanes
-        void *args[] = {&a, &refill_below};                    // (the second argument is the persistent kernel's alone)
-        // the moving observer: the finished march block with the camera's velocity behind it, gamma and gamma^2 / (gamma + 1)
-        // in binary64, each rounded once (the observer object's kernels take this block; nobody else reads it)
-        // (a projection: its kind and its spans in radians behind that, binary64 rounded once; the projected object's kernels take
-        // the longer block)
-        BhrProjectedMarchArgs oa;
-        if (call.observer) {
-            static_cast<BhrMarchArgs &>(oa) = a;
-            const float *b = call.observer->beta;
-            const double gamma = 1.0 / sqrt(1.0 - ((double)b[0] * b[0] + (double)b[1] * b[1] + (double)b[2] * b[2]));
-            for (int c = 0; c < 3; ++c) oa.obs_beta[c] = b[c];
-            oa.obs_gamma = (float)gamma;
-            oa.obs_g2 = (float)(gamma * gamma / (gamma + 1.0));
-            oa.obs_sky_shift = call.observer->sky_shift ? 1 : 0;
-            oa.proj_kind = 0;
-            oa.span_h = oa.span_v = 0.0f;
-            if (const bhr_projection *pr = call.projection) {
-                const double rad = 3.14159265358979323846 / 180.0;
-                oa.proj_kind = pr->kind;
-                oa.span_h = pr->kind == BHR_PROJ_FISHEYE ? (float)((double)pr->fov_h_deg * rad / 2.0) : (float)((double)pr->fov_h_deg * rad);
-                oa.span_v = pr->kind == BHR_PROJ_FISHEYE ? 0.0f : (float)((double)pr->fov_v_deg * rad);
-            }
-            args[0] = &oa;
-        }
-        // light delay: the finished march block with the call's scale behind it (the delay object's kernels take this block)
-        BhrDelayMarchArgs da;
-        if (call.delay) {
-            static_cast<BhrMarchArgs &>(da) = a;
-            da.delay_scale = call.delay->scale;
-            args[0] = &da;
-        }
+        VariantArgs va;
+        void *args[] = {variant_args(ctx, call.req, a, va), &refill_below};   // (the second argument is the persistent kernel's alone)
         (void)hipLaunchKernel(k.fn, k.grid, dim3(256), args, k.lds, stream);
     }
     BHR_HIP(hipGetLastError());

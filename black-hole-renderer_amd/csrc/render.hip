@@ -1,4 +1,5 @@
-// render.hip -- the five kinds of frame on a frame slot, and the one place that rotates the slots and keeps the last frame's record.
+// render.hip -- the kinds of frame on a frame slot (marched, under any march variant; shutter; from the ray map, its view and
+// its shutter), and the one place that rotates the slots and keeps the last frame's record.
 // One frame: march -> bloom H -> bloom V + combine (-> lens flare).  Frames alternate between the context's two
 // frame slots (bhr_frame_slot): frame n + 1 is launched on the other slot's stream into its own buffers and overlaps
 // the tail and the post-passes of frame n.  The scene is only read; everything that writes it or reads a frame goes
@@ -61,16 +62,14 @@ int32_t post_on_slot(bhr_ctx *ctx, uint32_t flags, int k, int ring) {
     return BHR_OK;
 }
 
-// obs: the frame of a moving observer (bhr_render_observer), marched by the observer object; null: bhr_render's
-// proj (with obs): that frame under a projection (bhr_render_projected), marched by the projected object
-// delay (without either): the frame with light delay (bhr_render_delayed), marched by the delay object
-int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, const bhr_observer *obs = nullptr,
-                       const bhr_projection *proj = nullptr, const bhr_light_delay *delay = nullptr) {
+// One marched frame on slot k.  req: the march variant of the frame with its payload, resolved by the entry point (none: the
+// context's arithmetic picks the march).
+int32_t render_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, const bhr_variant_request &req) {
     bhr_frame_slot &f = ctx->slots[k];
     BHR_TRY(bhr_frame_begin(ctx, flags));
     // an adaptively supersampled frame: the k = 1 march, then detect + refinement inside the same march bracket
     const bool adaptive = ctx->ada_k > 1;
-    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss, /* keep_start */ false, obs, proj, delay};
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ adaptive, ctx->ss, /* keep_start */ false, req};
     *fm = {call.ss, 1, adaptive};
     BHR_TRY(bhr_launch_march(ctx, call));              // records the ring slot's march events
     if (adaptive) BHR_TRY(bhr_launch_adaptive(ctx, call));
@@ -225,7 +224,8 @@ extern "C" {
 
 int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "bhr_render: null argument");
-    BHR_TRY(bhr_kerr_check(ctx, flags, "bhr_render"));
+    const bhr_variant_request req = {bhr_variant_of(ctx)};          // a spin, the exact redshift: the context's own variant
+    BHR_TRY(bhr_variant_frame_check(ctx, req.variant, flags, "bhr_render", (double)ctx->kerr_spin));
     BHR_TRY(bhr_kerr_camera_check(ctx, cam, "bhr_render"));
     if ((ctx->ss > 1 || ctx->ada_k > 1) && (flags & (BHR_PERSISTENT | BHR_ROW_COSTS)))
         return bhr_fail(BHR_ERR_INVALID, "bhr_render: BHR_PERSISTENT and BHR_ROW_COSTS are not available with supersampling (factor %d)", ctx->ss > 1 ? ctx->ss : ctx->ada_k);
@@ -235,41 +235,34 @@ int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
         BHR_TRY(bhr_calibrate_slot_streams(ctx, cam, flags));
     // launches that use per-context scratch (work queue of the persistent schedule, row-cost profile) stay on one slot
     const bool exclusive = (flags & (BHR_PERSISTENT | BHR_ROW_COSTS)) != 0;
-    return frame_on_next_slot(ctx, flags, exclusive, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm); });
+    return frame_on_next_slot(ctx, flags, exclusive, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, req); });
 }
 
-// What bhr_render_observer and bhr_render_projected refuse alike, for `what` ("a moving observer", "a projection"): the velocity,
-// the flags and the state of the context that the observer march has no form for.
-static int32_t observer_frame_check(const bhr_ctx *ctx, const bhr_observer *obs, uint32_t flags, const char *who, const char *what) {
+// The frame of a request that names its variant (bhr_render_observer, bhr_render_projected, bhr_render_delayed), behind the
+// entry point's checks of its own payload: the variant's refusals (bhr_variant_frame_check), then the frame.  Everything that
+// can refuse does so before the frame takes a slot; like bhr_render_shutter the frame neither triggers nor counts towards the
+// calibration of slot 1's stream.
+static int32_t variant_frame(bhr_ctx *ctx, const bhr_camera *cam, const bhr_variant_request &req, uint32_t flags, const char *who) {
+    BHR_TRY(bhr_variant_frame_check(ctx, req.variant, flags, who, (double)ctx->kerr_spin));
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, req); });
+}
+
+// The velocity of a moving camera, as bhr_render_observer and bhr_render_projected take it.
+static int32_t observer_beta_check(const bhr_observer *obs, const char *who) {
     const double b2 = (double)obs->beta[0] * obs->beta[0] + (double)obs->beta[1] * obs->beta[1] + (double)obs->beta[2] * obs->beta[2];
     if (!(b2 <= 0.995 * 0.995))       // a NaN fails the comparison too
         return bhr_fail(BHR_ERR_INVALID, "%s: observer velocity (%g, %g, %g): |beta| = %g, at most 0.995 and no NaN", who, (double)obs->beta[0],
                         (double)obs->beta[1], (double)obs->beta[2], sqrt(b2));
-    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
-        return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
-    if (ctx->cfg.anti_alias != 0)
-        return bhr_fail(BHR_ERR_INVALID, "%s: %s with anti_alias = 1: the differential seeds under aberration are not implemented", who, what);
-    if (ctx->disk_source != BHR_DISK_TEXTURE)
-        return bhr_fail(BHR_ERR_INVALID, "%s: %s with a Disk V2 source (%d): the observer march shades the disk texture", who, what, ctx->disk_source);
-    if (ctx->ada_k > 1)
-        return bhr_fail(BHR_ERR_INVALID, "%s: %s with adaptive supersampling (factor %d): the observer march has no refinement kernels; use bhr_set_supersample", who, what, ctx->ada_k);
-    if (ctx->kerr_on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
-        return bhr_fail(BHR_ERR_INVALID, "%s: %s with the exact redshift (bhr_set_redshift): its observer is static", who, what);
-    if (ctx->kerr_on)
-        return bhr_fail(BHR_ERR_INVALID, "%s: %s with a spin set (bhr_set_spin, a / M = %g): the observer march is Schwarzschild's", who, what, (double)ctx->kerr_spin);
-    if (ctx->rows != ctx->cfg.height)
-        return bhr_fail(BHR_ERR_INVALID, "%s: %s on a row-block context (rows %d of %d): needs a whole-frame context", who, what, ctx->rows, ctx->cfg.height);
     return BHR_OK;
 }
 
-// One frame as a moving camera sees it (include/bhr.h).  Everything that can refuse does so before the frame takes a slot; like
-// bhr_render_shutter the frame neither triggers nor counts towards the calibration of slot 1's stream.
+// One frame as a moving camera sees it (include/bhr.h).
 int32_t bhr_render_observer(bhr_ctx *ctx, const bhr_camera *cam, const bhr_observer *obs, uint32_t flags) {
     const char *who = "bhr_render_observer";
     if (!ctx || !cam || !obs) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
-    BHR_TRY(observer_frame_check(ctx, obs, flags, who, "a moving observer"));
-    BHR_HIP(hipSetDevice(ctx->cfg.device));
-    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, obs); });
+    BHR_TRY(observer_beta_check(obs, who));
+    return variant_frame(ctx, cam, {BHR_MV_OBSERVER, obs}, flags, who);
 }
 
 // One frame under an equirectangular or fisheye projection, from a camera that may move (include/bhr.h): bhr_render_observer's
@@ -286,36 +279,18 @@ int32_t bhr_render_projected(bhr_ctx *ctx, const bhr_camera *cam, const bhr_proj
         return bhr_fail(BHR_ERR_INVALID, "%s: equirectangular projection with fov_v_deg = %g: in (0, 180] and no NaN", who, (double)proj->fov_v_deg);
     static const bhr_observer at_rest = {{0.0f, 0.0f, 0.0f}, 0};
     const bhr_observer o = obs ? *obs : at_rest;
-    BHR_TRY(observer_frame_check(ctx, &o, flags, who, "a projection"));
-    BHR_HIP(hipSetDevice(ctx->cfg.device));
-    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, &o, proj); });
+    BHR_TRY(observer_beta_check(&o, who));
+    return variant_frame(ctx, cam, {BHR_MV_PROJECTED, &o, proj}, flags, who);
 }
 
 // One frame with every disk crossing shaded at its emission time (include/bhr.h): bhr_render's frame marched by the delay object.
-// Everything that can refuse does so before the frame takes a slot; like bhr_render_observer the frame neither triggers nor
-// counts towards the calibration of slot 1's stream.
 int32_t bhr_render_delayed(bhr_ctx *ctx, const bhr_camera *cam, const bhr_light_delay *d, uint32_t flags) {
     const char *who = "bhr_render_delayed";
     if (!ctx || !cam || !d) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
     if (!(d->scale >= 0.0f && d->scale <= 16.0f))       // a NaN fails the comparison too
         return bhr_fail(BHR_ERR_INVALID, "%s: light delay with scale = %g: in [0, 16] and no NaN", who, (double)d->scale);
     if (d->reserved != 0) return bhr_fail(BHR_ERR_INVALID, "%s: light delay with reserved = %d: must be 0", who, d->reserved);
-    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
-        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
-    if (ctx->cfg.anti_alias != 0)
-        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with anti_alias = 1: the delayed march has no ray differentials", who);
-    if (ctx->disk_source != BHR_DISK_TEXTURE)
-        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with a Disk V2 source (%d): the delayed march shades the disk texture", who, ctx->disk_source);
-    if (ctx->ada_k > 1)
-        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with adaptive supersampling (factor %d): the delayed march has no refinement kernels; use bhr_set_supersample", who, ctx->ada_k);
-    if (ctx->kerr_on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
-        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with the exact redshift (bhr_set_redshift): the delayed march is Schwarzschild's", who);
-    if (ctx->kerr_on)
-        return bhr_fail(BHR_ERR_INVALID, "%s: light delay with a spin set or the Kerr march forced (bhr_set_spin, a / M = %g): the delayed march is Schwarzschild's", who, (double)ctx->kerr_spin);
-    if (ctx->rows != ctx->cfg.height)
-        return bhr_fail(BHR_ERR_INVALID, "%s: light delay on a row-block context (rows %d of %d): needs a whole-frame context", who, ctx->rows, ctx->cfg.height);
-    BHR_HIP(hipSetDevice(ctx->cfg.device));
-    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, nullptr, nullptr, d); });
+    return variant_frame(ctx, cam, {BHR_MV_DELAYED, nullptr, nullptr, d}, flags, who);
 }
 
 // One frame as the mean of n marches (include/bhr.h).  One frame of one frame slot: the next frame takes the other slot.

@@ -1,44 +1,12 @@
-// settings.hip -- what changes the kind of frame a context renders: the spinning hole with its refusals, and the sampling.
+// settings.hip -- what changes the kind of frame a context renders: the march variants' table with their refusals, the spinning
+// hole, and the sampling.
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include "bhr_internal.h"
 
 namespace {
-
-int32_t kerr_state_check(const bhr_ctx *ctx, uint32_t flags, const char *who, double spin) {
-    if (ctx->cfg.disk_tilt_deg != 0.0f)
-        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with a disk tilted by %g degrees: the spin axis is the disk normal, tilt must be 0", who, spin, (double)ctx->cfg.disk_tilt_deg);
-    if (ctx->cfg.anti_alias != 0)
-        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with anti_alias = 1: ray differentials around a spinning hole need Kerr's variational equations", who, spin);
-    if (ctx->disk_source != BHR_DISK_TEXTURE)
-        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with a Disk V2 source (%d): the Kerr march shades the disk texture", who, spin, ctx->disk_source);
-    if (ctx->ada_k > 1)
-        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with adaptive supersampling (factor %d): the Kerr march has no refinement kernels; use bhr_set_supersample", who, spin, ctx->ada_k);
-    if (ctx->rows != ctx->cfg.height)
-        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g on a row-block context (rows %d of %d): group and tile renders march Schwarzschild rays", who, spin, ctx->rows, ctx->cfg.height);
-    if (flags & BHR_PERSISTENT)
-        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with BHR_PERSISTENT: the Kerr march has the tile schedule only", who, spin);
-    if (flags & BHR_ROW_COSTS)
-        return bhr_fail(BHR_ERR_INVALID, "%s: spin %g with BHR_ROW_COSTS: the Kerr march fills no row-cost profile", who, spin);
-    return BHR_OK;
-}
-
-// {VGPRs, LDS bytes, scratch bytes per lane} of a march kernel of the Kerr object, or of the observer object (ss: its supersampled
-// twin).  No context: host + hipFuncGetAttributes.
-int32_t kerr_kernel_resources(const char *who, bhr_march_kernel k, int32_t ss, int32_t out[3], int observer = 0) {
-    if (!out) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
-    const void *f = observer == 3 ? bhr_march_kernel_delay(k, 0, ss ? 1 : 0)       // 3: the delay object
-                    : observer == 2 ? bhr_march_kernel_projected(k, 0, ss ? 1 : 0)   // 1: the observer object, 2: the projected object
-                    : observer  ? bhr_march_kernel_observer(k, 0, ss ? 1 : 0) : bhr_march_kernel_kerr(k, 0, ss ? 1 : 0);
-    if (!f) return bhr_fail(BHR_ERR_STATE, "%s: no such march kernel in this library", who);
-    hipFuncAttributes at;
-    BHR_HIP(hipFuncGetAttributes(&at, f));
-    out[0] = at.numRegs;
-    out[1] = (int32_t)at.sharedSizeBytes;
-    out[2] = (int32_t)at.localSizeBytes;
-    return BHR_OK;
-}
 
 // Both supersampling settings: `ss` rays per pixel everywhere (ada_k = 0), or one ray per pixel and ada_k x ada_k where the
 // neighbours differ by more than T.
@@ -70,16 +38,71 @@ int32_t set_sampling(bhr_ctx *ctx, const char *who, int32_t k, int32_t adaptive,
 
 }  // namespace
 
+// ---- the march variants (bhr_internal.h: bhr_march_variant) -----------------------------------------------------------------------
+const bhr_variant_row &bhr_variant_row_of(bhr_march_variant v) {
+    constexpr uint32_t kerr_flags = ~(uint32_t)(BHR_PERSISTENT | BHR_ROW_COSTS), rest_flags = BHR_SKIP_BLOOM | BHR_LENS_FLARE;
+    constexpr const char *kerr_diff = "ray differentials around a spinning hole need Kerr's variational equations";
+    constexpr const char *kerr_rows = "group and tile renders march Schwarzschild rays", *rest_rows = "needs a whole-frame context";
+    constexpr const char *obs_diff = "the differential seeds under aberration are not implemented", *obs_exact = "its observer is static";
+    // (a projection's frame is an observer's, at rest if need be, marched by the projected object: the observer's words)
+    static const bhr_variant_row rows[BHR_MV_COUNT] = {
+        {},                            // BHR_MV_NONE: the marches march_kernel picks by arithmetic, schedule and disk source
+        {bhr_march_kernel_kerr, BHR_MK_TILE, "spin %g", "Kerr", kerr_diff, nullptr, kerr_rows, kerr_flags, true},
+        {bhr_march_kernel_kerr, BHR_MK_KERR_EXACT, "spin %g", "Kerr", kerr_diff, nullptr, kerr_rows, kerr_flags, true},
+        {bhr_march_kernel_observer, BHR_MK_TILE, "a moving observer", "observer", obs_diff, obs_exact, rest_rows, rest_flags, false},
+        {bhr_march_kernel_projected, BHR_MK_TILE, "a projection", "observer", obs_diff, obs_exact, rest_rows, rest_flags, false},
+        {bhr_march_kernel_delay, BHR_MK_TILE, "light delay", "delayed", "the delayed march has no ray differentials", "the delayed march is Schwarzschild's",
+         rest_rows, rest_flags, false},
+    };
+    return rows[v];
+}
+
+// The counters name the kernel that marches a frame: the context's variant's, else its arithmetic's.
+int32_t bhr_note_frame_kernel(bhr_ctx *ctx) {
+    int32_t res[3];
+    BHR_TRY(bhr_march_resources("bhr_note_frame_kernel", bhr_variant_of(ctx), ctx->cfg.math_mode, ctx->cfg.anti_alias != 0, 0, res));
+    ctx->counters.march_vgprs = res[0];
+    ctx->counters.march_lds_bytes = res[1];
+    return BHR_OK;
+}
+
+bhr_march_variant bhr_variant_of(const bhr_ctx *ctx, bhr_march_variant asked) {
+    if (asked != BHR_MV_NONE || !ctx->kerr_on) return asked;
+    return ctx->kerr_redshift == BHR_REDSHIFT_EXACT ? BHR_MV_KERR_EXACT : BHR_MV_KERR;
+}
+
+// The flags first, then the context's state; every refusal names the combination.
+int32_t bhr_variant_frame_check(const bhr_ctx *ctx, bhr_march_variant v, uint32_t flags, const char *who, double spin) {
+    if (v == BHR_MV_NONE) return BHR_OK;
+    const bhr_variant_row &r = bhr_variant_row_of(v);
+    char what[48];
+    snprintf(what, sizeof(what), r.noun, spin);
+    if (const uint32_t bad = flags & ~r.flags_ok) {
+        if (!r.kerr) return bhr_fail(BHR_ERR_INVALID, "%s: %s with flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, what, flags);
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with %s", who, what,
+                        (bad & BHR_PERSISTENT) ? "BHR_PERSISTENT: the Kerr march has the tile schedule only" : "BHR_ROW_COSTS: the Kerr march fills no row-cost profile");
+    }
+    if (r.kerr && ctx->cfg.disk_tilt_deg != 0.0f)
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with a disk tilted by %g degrees: the spin axis is the disk normal, tilt must be 0", who, what, (double)ctx->cfg.disk_tilt_deg);
+    if (ctx->cfg.anti_alias != 0) return bhr_fail(BHR_ERR_INVALID, "%s: %s with anti_alias = 1: %s", who, what, r.no_diff);
+    if (ctx->disk_source != BHR_DISK_TEXTURE)
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with a Disk V2 source (%d): the %s march shades the disk texture", who, what, ctx->disk_source, r.march);
+    if (ctx->ada_k > 1)
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with adaptive supersampling (factor %d): the %s march has no refinement kernels; use bhr_set_supersample", who, what, ctx->ada_k, r.march);
+    if (!r.kerr && ctx->kerr_on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with the exact redshift (bhr_set_redshift): %s", who, what, r.no_exact);
+    if (!r.kerr && ctx->kerr_on)
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s with a spin set or the Kerr march forced (bhr_set_spin, a / M = %g): the %s march is Schwarzschild's", who, what, spin, r.march);
+    if (ctx->rows != ctx->cfg.height)
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s on a row-block context (rows %d of %d): %s", who, what, ctx->rows, ctx->cfg.height, r.no_rows);
+    return BHR_OK;
+}
+
 // ---- the spinning hole (bhr_set_spin; csrc/ray_kerr.h, march_kerr.hip) ----------------------------------------------------------
-// What has no Kerr form in this version; every refusal names the combination.
+// A call that has no Kerr form at all in this version; the refusal names the combination.
 int32_t bhr_kerr_refuse(const bhr_ctx *ctx, const char *who, const char *what) {
     if (!ctx || !ctx->kerr_on) return BHR_OK;
     return bhr_fail(BHR_ERR_INVALID, "%s: a spin is set (bhr_set_spin, a / M = %g) and %s", who, (double)ctx->kerr_spin, what);
-}
-
-int32_t bhr_kerr_check(const bhr_ctx *ctx, uint32_t flags, const char *who) {
-    if (!ctx || !ctx->kerr_on) return BHR_OK;
-    return kerr_state_check(ctx, flags, who, (double)ctx->kerr_spin);
 }
 
 // The camera of a Kerr frame stands outside the static limit f = r / S = 1 (and so outside the horizon): the photon that
@@ -106,19 +129,14 @@ int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr) {
     if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: null ctx");
     if (!(fabsf(a_over_m) <= 0.998f)) return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin a / M = %g (|a / M| <= 0.998)", (double)a_over_m);
     const int32_t on = (a_over_m != 0.0f || force_kerr) ? 1 : 0;
-    if (on) BHR_TRY(kerr_state_check(ctx, 0, "bhr_set_spin", (double)a_over_m));
+    if (on) BHR_TRY(bhr_variant_frame_check(ctx, BHR_MV_KERR, 0, "bhr_set_spin", (double)a_over_m));
     if (!on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
         return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin 0 without force_kerr while the exact redshift is set (bhr_set_redshift): it is a Kerr kernel's; set BHR_REDSHIFT_MODEL first");
     if (on == ctx->kerr_on && a_over_m == ctx->kerr_spin) return BHR_OK;
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight, like every other change of what a frame is
     ctx->kerr_on = on;
     ctx->kerr_spin = on ? a_over_m : 0.0f;
-    // the counters name the kernel that marches a frame
-    int32_t v = 0, l = 0;
-    BHR_TRY(bhr_march_resources(on ? (ctx->kerr_redshift == BHR_REDSHIFT_EXACT ? -2 : -1) : ctx->cfg.math_mode, on ? 0 : ctx->cfg.anti_alias, &v, &l));
-    ctx->counters.march_vgprs = v;
-    ctx->counters.march_lds_bytes = l;
-    return BHR_OK;
+    return bhr_note_frame_kernel(ctx);
 }
 
 int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode) {
@@ -130,25 +148,19 @@ int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode) {
     if (mode == ctx->kerr_redshift) return BHR_OK;
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight
     ctx->kerr_redshift = mode;
-    if (ctx->kerr_on) {                 // the counters name the kernel that marches a frame
-        int32_t v = 0, l = 0;
-        BHR_TRY(bhr_march_resources(mode == BHR_REDSHIFT_EXACT ? -2 : -1, 0, &v, &l));
-        ctx->counters.march_vgprs = v;
-        ctx->counters.march_lds_bytes = l;
-    }
-    return BHR_OK;
+    return bhr_note_frame_kernel(ctx);
 }
 
-int32_t bhr_observer_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_observer_resources", BHR_MK_TILE, ss, out, 1); }
-int32_t bhr_projected_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_projected_resources", BHR_MK_TILE, ss, out, 2); }
-int32_t bhr_delayed_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_delayed_resources", BHR_MK_TILE, ss, out, 3); }
+int32_t bhr_observer_resources(int32_t ss, int32_t out[3]) { return bhr_march_resources("bhr_observer_resources", BHR_MV_OBSERVER, 0, 0, ss, out); }
+int32_t bhr_projected_resources(int32_t ss, int32_t out[3]) { return bhr_march_resources("bhr_projected_resources", BHR_MV_PROJECTED, 0, 0, ss, out); }
+int32_t bhr_delayed_resources(int32_t ss, int32_t out[3]) { return bhr_march_resources("bhr_delayed_resources", BHR_MV_DELAYED, 0, 0, ss, out); }
 
-int32_t bhr_kerr_resources(int32_t ss, int32_t out[3]) { return kerr_kernel_resources("bhr_kerr_resources", BHR_MK_TILE, ss, out); }
+int32_t bhr_kerr_resources(int32_t ss, int32_t out[3]) { return bhr_march_resources("bhr_kerr_resources", BHR_MV_KERR, 0, 0, ss, out); }
 // ... of the kernels of a redshift mode (bhr_set_redshift)
 int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t ss, int32_t out[3]) {
     if (mode != BHR_REDSHIFT_MODEL && mode != BHR_REDSHIFT_EXACT)
         return bhr_fail(BHR_ERR_INVALID, "bhr_kerr_redshift_resources: unknown mode %d (BHR_REDSHIFT_MODEL = 0, BHR_REDSHIFT_EXACT = 1)", mode);
-    return kerr_kernel_resources("bhr_kerr_redshift_resources", mode == BHR_REDSHIFT_EXACT ? BHR_MK_KERR_EXACT : BHR_MK_TILE, ss, out);
+    return bhr_march_resources("bhr_kerr_redshift_resources", mode == BHR_REDSHIFT_EXACT ? BHR_MV_KERR_EXACT : BHR_MV_KERR, 0, 0, ss, out);
 }
 
 int32_t bhr_set_supersample(bhr_ctx *ctx, int32_t k) {

@@ -257,15 +257,13 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     (HipRenderer.render_async; 1 is physical); one device, the texture source, the strict Schwarzschild march of the pinhole
     camera that stands still (check_light_delay)."""
     check_depth_and_dither(bit_depth, dither)
-    check_light_delay(light_delay, anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus,
-                      spin=spin, redshift=redshift, observer=observer is not None, projection=projection is not None,
-                      passes=passes_path is not None, stars=stars is not None)
-    check_projection(projection, projection_fov, anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold,
-                     gpus=gpus, spin=spin, redshift=redshift, passes=passes_path is not None, stars=stars is not None)
+    facts = dict(anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus, spin=spin,
+                 redshift=redshift, passes=passes_path is not None)      # what the three variant checks take alike
+    check_light_delay(light_delay, observer=observer is not None, projection=projection is not None, stars=stars is not None, **facts)
+    check_projection(projection, projection_fov, stars=stars is not None, **facts)
     stars = check_stars(stars, skybox_path=skybox_path, supersample=supersample, spin=spin, redshift=redshift, gpus=gpus,
                         disk_model=disk_model, observer=observer)
-    check_observer(observer, anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus,
-                   spin=spin, redshift=redshift, passes=passes_path is not None)
+    check_observer(observer, **facts)
     check_passes(passes_path, gpus, supersample, disk_model)
     grade = check_grade(grade)
     if hdr_path is not None:
@@ -311,9 +309,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         print(f"Point stars: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
               f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
     else:
-        img = renderer.render(cam_pos, fov, frame=0, **({} if observer is None else {"observer": observer, "observer_sky": observer_sky}),
-                              **({} if projection is None else {"projection": projection, "projection_fov": projection_fov}),
-                              **({} if light_delay is None else {"light_delay": light_delay}))
+        img = renderer.render(cam_pos, fov, frame=0, observer=observer, observer_sky=observer_sky, projection=projection,
+                              projection_fov=projection_fov, light_delay=light_delay)
     if hdr_path is not None:
         save_hdr(renderer.read_hdr(), hdr_path)
     c = renderer.counters()
@@ -333,6 +330,49 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     return img
 
 
+# What a frame marched by a variant of the march -- a moving observer, a projection, light delay -- does not take.
+# _VARIANT_REFUSALS: every condition some variant refuses -- its name, whether the check's keywords ``f`` violate it, and the
+# refusal behind the variant's noun, with the variant's own words in braces.  _VARIANTS: per variant those words and the
+# conditions it refuses (an observer takes any ``world``: frame-sharded observer videos are legal).
+_VARIANT_REFUSALS = (
+    ("anti_alias", lambda f: f["anti_alias"] not in ("disabled", 0, False, None), "does not combine with anti_alias: {no_diff}"),
+    ("disk_model", lambda f: f["disk_model"] != "texture", "does not combine with disk_model v2 / v2_volume: the {march} march shades the disk texture"),
+    ("supersample_threshold", lambda f: f["supersample_threshold"] is not None,
+     "does not combine with supersample_threshold: the {march} march has no refinement kernels (plain supersample works)"),
+    ("gpus_or_world", lambda f: f["gpus"] != 1 or f["world"] != 1, "renders on one GPU: row-block tiles and frame-sharded ranks march {cam}"),
+    ("gpus", lambda f: f["gpus"] != 1, "renders on one GPU: row-block tiles march {cam}"),
+    ("world", lambda f: f["world"] != 1, "renders on one rank: frame-sharded ranks march {cam}"),
+    ("spin", lambda f: f["spin"] != 0 or f["redshift"] != "model",
+     "does not combine with a spin or the exact redshift: the {march} march is Schwarzschild's, {no_exact}"),
+    ("observer", lambda f: f["observer"], "does not combine with a moving observer: the {march} march is the camera's that stands still"),
+    ("projection", lambda f: f["projection"], "does not combine with a projection: the {march} march is the pinhole camera's"),
+    ("passes", lambda f: f["passes"], "writes no passes: {map}"),
+    ("shutter", lambda f: f["shutter"] > 0, "does not combine with shutter: shutter frames march {cam}"),
+    ("maps", lambda f: f["maps"], "does not combine with ray_map, orbit_map or shutter_map: {map}"),
+    ("stars", lambda f: f["stars"], "does not combine with point stars: they are rendered through a ray map{of_map}"),
+)
+_VARIANTS = {
+    "observer": dict(noun="a moving observer", march="observer", cam="the camera that stands still",
+                     no_diff="the differential seeds under aberration are not implemented", no_exact="the exact redshift's observer static",
+                     map="a ray map holds the rays of the camera that stands still",
+                     refuses="anti_alias disk_model supersample_threshold gpus spin passes shutter maps"),
+    "projection": dict(noun="a projection", march="projected", cam="the pinhole camera", no_diff="the projected march has no ray differentials",
+                       no_exact="with the model redshift", map="a ray map holds the rays of the pinhole camera", of_map=" of the pinhole camera",
+                       refuses="anti_alias disk_model supersample_threshold gpus_or_world spin passes shutter maps stars"),
+    "light_delay": dict(noun="light_delay", march="delayed", cam="without the light's travel time", no_diff="the delayed march has no ray differentials",
+                        no_exact="with the model redshift", map="a ray map's records hold no travel time", of_map=", whose records hold no travel time",
+                        refuses="anti_alias disk_model supersample_threshold gpus world spin observer projection passes shutter maps stars"),
+}
+
+
+def _check_variant(variant: str, f: dict) -> None:
+    """Raises ValueError for the first of the variant's refusals that the keywords ``f`` of its check violate."""
+    words = _VARIANTS[variant]
+    for condition, violated, refusal in _VARIANT_REFUSALS:
+        if condition in words["refuses"].split() and violated(f):
+            raise ValueError(f"{words['noun']} {refusal.format(**words)}")
+
+
 def check_observer(observer, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None, gpus: int = 1,
                    world: int = 1, spin: float = 0.0, redshift: str = "model", passes: bool = False, shutter: float = 0.0,
                    maps: bool = False) -> None:
@@ -343,22 +383,7 @@ def check_observer(observer, anti_alias="disabled", disk_model: str = "texture",
         return
     from .observer import check_beta
     check_beta(observer)
-    if anti_alias not in ("disabled", 0, False, None):
-        raise ValueError("a moving observer does not combine with anti_alias: the differential seeds under aberration are not implemented")
-    if disk_model != "texture":
-        raise ValueError("a moving observer does not combine with disk_model v2 / v2_volume: the observer march shades the disk texture")
-    if supersample_threshold is not None:
-        raise ValueError("a moving observer does not combine with supersample_threshold: the observer march has no refinement kernels (plain supersample works)")
-    if gpus != 1:
-        raise ValueError("a moving observer renders on one GPU: row-block tiles march the camera that stands still")
-    if spin != 0 or redshift != "model":
-        raise ValueError("a moving observer does not combine with a spin or the exact redshift: the observer march is Schwarzschild's, the exact redshift's observer static")
-    if passes:
-        raise ValueError("a moving observer writes no passes: a ray map holds the rays of the camera that stands still")
-    if shutter > 0:
-        raise ValueError("a moving observer does not combine with shutter: shutter frames march the camera that stands still")
-    if maps:
-        raise ValueError("a moving observer does not combine with ray_map, orbit_map or shutter_map: a ray map holds the rays of the camera that stands still")
+    _check_variant("observer", locals())
 
 
 def check_projection(projection, projection_fov=None, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None,
@@ -374,24 +399,7 @@ def check_projection(projection, projection_fov=None, anti_alias="disabled", dis
         return None
     from .projection import check
     out = check(projection, projection_fov)
-    if spin != 0 or redshift != "model":
-        raise ValueError("a projection does not combine with a spin or the exact redshift: the projected march is Schwarzschild's, with the model redshift")
-    if anti_alias not in ("disabled", 0, False, None):
-        raise ValueError("a projection does not combine with anti_alias: the projected march has no ray differentials")
-    if disk_model != "texture":
-        raise ValueError("a projection does not combine with disk_model v2 / v2_volume: the projected march shades the disk texture")
-    if supersample_threshold is not None:
-        raise ValueError("a projection does not combine with supersample_threshold: the projected march has no refinement kernels (plain supersample works)")
-    if gpus != 1 or world != 1:
-        raise ValueError("a projection renders on one GPU: row-block tiles and frame-sharded ranks march the pinhole camera")
-    if shutter > 0:
-        raise ValueError("a projection does not combine with shutter: shutter frames march the pinhole camera")
-    if maps:
-        raise ValueError("a projection does not combine with ray_map, orbit_map or shutter_map: a ray map holds the rays of the pinhole camera")
-    if passes:
-        raise ValueError("a projection writes no passes: a ray map holds the rays of the pinhole camera")
-    if stars:
-        raise ValueError("a projection does not combine with point stars: they are rendered through a ray map of the pinhole camera")
+    _check_variant("projection", locals())
     return out
 
 
@@ -410,30 +418,7 @@ def check_light_delay(scale, anti_alias="disabled", disk_model: str = "texture",
         raise ValueError(f"light_delay is a scale in [0, 16], got {scale!r}") from None
     if not 0.0 <= out <= 16.0:            # a NaN fails the comparison too
         raise ValueError(f"light_delay is a scale in [0, 16], got {scale!r}")
-    if anti_alias not in ("disabled", 0, False, None):
-        raise ValueError("light_delay does not combine with anti_alias: the delayed march has no ray differentials")
-    if disk_model != "texture":
-        raise ValueError("light_delay does not combine with disk_model v2 / v2_volume: the delayed march shades the disk texture")
-    if supersample_threshold is not None:
-        raise ValueError("light_delay does not combine with supersample_threshold: the delayed march has no refinement kernels (plain supersample works)")
-    if gpus != 1:
-        raise ValueError("light_delay renders on one GPU: row-block tiles march without the light's travel time")
-    if world != 1:
-        raise ValueError("light_delay renders on one rank: frame-sharded ranks march without the light's travel time")
-    if spin != 0 or redshift != "model":
-        raise ValueError("light_delay does not combine with a spin or the exact redshift: the delayed march is Schwarzschild's, with the model redshift")
-    if observer:
-        raise ValueError("light_delay does not combine with a moving observer: the delayed march is the camera's that stands still")
-    if projection:
-        raise ValueError("light_delay does not combine with a projection: the delayed march is the pinhole camera's")
-    if passes:
-        raise ValueError("light_delay writes no passes: a ray map's records hold no travel time")
-    if shutter > 0:
-        raise ValueError("light_delay does not combine with shutter: shutter frames march without the light's travel time")
-    if maps:
-        raise ValueError("light_delay does not combine with ray_map, orbit_map or shutter_map: a ray map's records hold no travel time")
-    if stars:
-        raise ValueError("light_delay does not combine with point stars: they are rendered through a ray map, whose records hold no travel time")
+    _check_variant("light_delay", locals())
     return out
 
 
@@ -842,33 +827,28 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     position and t_offset, with and without ``orbit`` -- each disk crossing shaded at the time its light left the gas.  Refused
     with ValueError, before any device work, with what check_light_delay names.  The progress record carries the scale when one
     is given, and a resume under another starts over."""
-    moving = observer is not None or observer_velocity is not None
+    moving = observer is not None or observer_velocity is not None or infall_to is not None
+    projected = projection is not None or projection_fov is not None
+    disk_model = "texture" if getattr(renderer, "_dv2", None) is None else "v2"
+    if moving or projected or light_delay is not None:
+        # what the three variant checks take from the renderer and the call
+        thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
+        facts = dict(anti_alias=renderer.anti_alias, disk_model=disk_model, supersample_threshold=thr, spin=renderer.spin, redshift=renderer.redshift,
+                     shutter=shutter, maps=ray_map or orbit_map or shutter_map)
     plan = None
-    if moving or infall_to is not None:
+    if moving:
         from . import observer as obs_mod
         if observer is not None and observer_velocity is not None:
             raise ValueError("observer names a velocity and observer_velocity gives one: take one of the two")
         if infall_to is not None and observer != "infall":
             raise ValueError("infall_to is the path of observer='infall'")
-        thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
-        check_observer((0.0, 0.0, 0.0), anti_alias=renderer.anti_alias, disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2",
-                       supersample_threshold=thr, spin=renderer.spin, redshift=renderer.redshift, shutter=shutter,
-                       maps=ray_map or orbit_map or shutter_map)
+        check_observer((0.0, 0.0, 0.0), **facts)
         plan = obs_mod.frame_plan(n_frames, static_cam_pos, observer, observer_velocity, orbit, orbit_degrees, infall_to)
     proj = None
-    if projection is not None or projection_fov is not None:
-        thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
-        proj = check_projection(projection, projection_fov, anti_alias=renderer.anti_alias,
-                                disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2", supersample_threshold=thr,
-                                world=world, spin=renderer.spin, redshift=renderer.redshift, shutter=shutter,
-                                maps=ray_map or orbit_map or shutter_map, stars=stars is not None)
+    if projected:
+        proj = check_projection(projection, projection_fov, world=world, stars=stars is not None, **facts)
     if light_delay is not None:
-        thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
-        light_delay = check_light_delay(light_delay, anti_alias=renderer.anti_alias,
-                                        disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2", supersample_threshold=thr,
-                                        world=world, spin=renderer.spin, redshift=renderer.redshift, observer=moving or infall_to is not None,
-                                        projection=projection is not None or projection_fov is not None, shutter=shutter,
-                                        maps=ray_map or orbit_map or shutter_map, stars=stars is not None)
+        light_delay = check_light_delay(light_delay, world=world, observer=moving, projection=projected, stars=stars is not None, **facts)
     check_map_supersample(map_supersample, ray_map, orbit_map, shutter_map)
     check_shutter(shutter, shutter_samples)
     if video_stream not in ("auto", "y4m", "off"):
@@ -879,20 +859,16 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         grade["keep_hdr"] = False
     if shutter_map:
         check_shutter_map(shutter_map, shutter, orbit, ray_map, orbit_map, renderer.disk_tilt,
-                          renderer.supersample if supersample is None else supersample,
-                          "texture" if getattr(renderer, "_dv2", None) is None else "v2", 1, world)
+                          renderer.supersample if supersample is None else supersample, disk_model, 1, world)
     if orbit_map:
         check_orbit_map(orbit_map, True, orbit, ray_map, renderer.disk_tilt, shutter,
-                        renderer.supersample if supersample is None else supersample,
-                        "texture" if getattr(renderer, "_dv2", None) is None else "v2", 1, world)
+                        renderer.supersample if supersample is None else supersample, disk_model, 1, world)
     if ray_map:
-        check_ray_map(ray_map, orbit, shutter, renderer.supersample if supersample is None else supersample,
-                      "texture" if getattr(renderer, "_dv2", None) is None else "v2", 1, world)
+        check_ray_map(ray_map, orbit, shutter, renderer.supersample if supersample is None else supersample, disk_model, 1, world)
     # point stars: the renderer carries the catalogue (make_renderer(stars=)); the frames that show it are the map's
     if stars is not None:
         stars = check_stars(stars, supersample=renderer.supersample if supersample is None else supersample, spin=renderer.spin,
-                            redshift=renderer.redshift, disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2",
-                            observer=None if plan is None else observer or observer_velocity)
+                            redshift=renderer.redshift, disk_model=disk_model, observer=None if plan is None else observer or observer_velocity)
         if shutter_map:
             raise ValueError("point stars do not combine with shutter_map: shutter frames from the map have no point stars")
         if not (ray_map or orbit_map):
@@ -1058,15 +1034,9 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             renderer.render_from_ray_map_async(frame=0)    # the same frame from the map: shade, no march
         elif orbit_map:
             renderer.render_from_ray_map_async(frame=0, cam_pos=cam_pos, fov=fov)    # the map turned to the frame's camera
-        elif proj is not None:                             # the frame through the projection, from the moving camera if there is one
-            renderer.render_async(cam_pos, fov, frame=0, projection=projection, projection_fov=projection_fov,
-                                  **({} if plan is None else {"observer": beta, "observer_sky": observer_sky}))
-        elif plan is not None:
-            renderer.render_async(cam_pos, fov, frame=0, observer=beta, observer_sky=observer_sky)
-        elif light_delay is not None:                      # every crossing at its emission time
-            renderer.render_async(cam_pos, fov, frame=0, light_delay=light_delay)
-        else:
-            renderer.render_async(cam_pos, fov, frame=0)   # lens flare, when enabled, is applied on the device
+        else:                                              # marched: the frame of the moving camera, through the projection, with light delay
+            renderer.render_async(cam_pos, fov, frame=0, observer=None if plan is None else beta, observer_sky=observer_sky,
+                                  projection=projection, projection_fov=projection_fov, light_delay=light_delay)   # (lens flare: on the device)
         sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))
         if stream is not None:
             try:

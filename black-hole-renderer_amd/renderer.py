@@ -926,8 +926,7 @@ class HipRenderer:
             raise ValueError("lens flare needs whole-frame sums; render row blocks through "
                              "bhr_amd.multigpu.group_render(..., lens_flare=True)")
         self.render_async(cam_pos, fov, frame, skip_differentials, skip_bloom, observer=observer, observer_sky=observer_sky,
-                          **({} if projection is None else {"projection": projection, "projection_fov": projection_fov}),
-                          **({} if light_delay is None else {"light_delay": light_delay}))
+                          projection=projection, projection_fov=projection_fov, light_delay=light_delay)
         return self.read_layer(_lib.LAYER_FINAL)
 
     def selftest(self) -> dict:
