@@ -7,7 +7,7 @@ round-robin by RANK / WORLD_SIZE), ``--disk_model`` (the analytic Disk V2 source
 ``--observer_velocity`` (a camera that moves: aberration and Doppler shift), ``--stars point`` (the procedural sky's stars as a
 catalogue of lensed points rendered through a ray map), ``--light_delay`` (every disk crossing shaded at the
 time its light left the gas), ``--projection`` / ``--projection_fov`` (equirectangular 360-degree
-frames and fisheye dome masters instead of the pinhole camera).
+frames and fisheye dome masters instead of the pinhole camera), ``--polarization`` (Stokes Q / U maps of the disk through a ray map).
 """
 from __future__ import annotations
 
@@ -122,6 +122,22 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "--video [--orbit].  Not with --anti_alias lod_radius, --disk_model v2 / v2_volume, "
                         "--supersample_threshold, --gpus > 1, --spin, --redshift exact, the observer flags, --projection, --passes, "
                         "--shutter, the ray-map flags or --stars point")
+    p.add_argument("--polarization", type=str, nargs="+", default=argparse.SUPPRESS, metavar="FIELD",
+                   help="polarisation: Stokes Q / U maps of the disk's synchrotron light, computed through a ray map of the view by a "
+                        "pass behind the shade.  FIELD is the magnetic field in the gas frame: toroidal, radial, vertical, or three "
+                        "numbers BR BPHI BZ.  A still image writes --stokes_output (planes, cell grid, field, fraction, convention, "
+                        "camera) and --polarization_ticks (the frame with a tick per cell); --video --ray_map collects one cell grid "
+                        "per frame into one .npz.  The angle is counted from image-right towards image-up.  Not with --spin, "
+                        "--redshift exact, the observer flags, --projection, --light_delay, --orbit_map, --shutter_map, --shutter, "
+                        "--map_supersample > 1, --supersample > 1, --disk_model v2 / v2_volume, --gpus > 1, or a video without --ray_map")
+    p.add_argument("--polarization_fraction", type=float, default=argparse.SUPPRESS, metavar="PI0",
+                   help="--polarization: the degree of polarisation of light emitted across the field, in [0, 1] (default: 0.7)")
+    p.add_argument("--polarization_cell", type=int, default=argparse.SUPPRESS, metavar="C",
+                   help="--polarization: the side of a cell of the tick grid in pixels, 8, 16 or 32 (default: 16)")
+    p.add_argument("--stokes_output", type=str, default=argparse.SUPPRESS, metavar="PATH.npz",
+                   help="--polarization: where the Stokes .npz goes (a video's default: <output stem>.stokes.npz)")
+    p.add_argument("--polarization_ticks", type=str, default=argparse.SUPPRESS, metavar="PATH.png",
+                   help="--polarization, still images: the frame with the polarisation ticks drawn over it")
     p.add_argument("--video_stream", type=str, default="auto", choices=["auto", "y4m", "off"],
                    help="--video: also hand the frames to the encoder as a yuv420p stream converted on the device "
                         "(auto: pipe into ffmpeg when it is on PATH; y4m: write <output stem>.y4m; off: PNG frames only)")
@@ -462,6 +478,52 @@ def parse_args(argv=None) -> argparse.Namespace:
                 p.error(f"{who} does not combine with {flag}: a ray map's records hold no travel time")
         if args.stars == "point":
             p.error(f"{who} does not combine with --stars point: point stars are rendered through a ray map, whose records hold no travel time")
+    # polarisation, behind every refusal above, light delay's included: a line that was refused without --polarization is refused
+    # with the same words.  Its five options have no default in the namespace: they are there only when the flag was given
+    pol = getattr(args, "polarization", None)
+    for flag in ("polarization_fraction", "polarization_cell", "stokes_output", "polarization_ticks"):
+        if pol is None and getattr(args, flag, None) is not None:
+            p.error(f"--{flag} needs --polarization: it belongs to the Stokes maps")
+    if pol is not None:
+        who = "--polarization"
+        from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check, parse_field
+        try:
+            check(parse_field(pol), getattr(args, "polarization_fraction", DEFAULT_FRACTION), getattr(args, "polarization_cell", DEFAULT_CELL))
+        except ValueError as e:
+            p.error(f"{who}: {e}")
+        if args.spin != 0:
+            p.error(f"{who} does not combine with --spin: the transport rule is Schwarzschild's and a ray map holds Schwarzschild rays")
+        if args.redshift == "exact":
+            p.error(f"{who} does not combine with --redshift exact: that is the Kerr march's")
+        if observer_flags:
+            p.error(f"{who} does not combine with --observer, --observer_velocity, --observer_sky or --infall_to: a ray map holds the rays "
+                    "of the camera that stands still")
+        if args.projection != "perspective":
+            p.error(f"{who} does not combine with --projection {args.projection}: a ray map holds the rays of the pinhole camera")
+        if delay is not None:
+            p.error(f"{who} does not combine with --light_delay: a ray map's records hold no travel time")
+        if args.orbit_map:
+            p.error(f"{who} does not combine with --orbit_map: the Stokes planes are the build view's, turned views have none")
+        if args.shutter_map:
+            p.error(f"{who} does not combine with --shutter_map: shutter frames from the map have no Stokes planes")
+        if args.shutter > 0:
+            p.error(f"{who} does not combine with --shutter: shutter frames are marched, the Stokes planes come from a ray map")
+        if args.map_supersample != 1:
+            p.error(f"{who} does not combine with --map_supersample other than 1: the Stokes planes need a map with one ray per pixel")
+        if args.supersample != 1:
+            p.error(f"{who} does not combine with --supersample other than 1: the Stokes planes need a map with one ray per pixel")
+        if args.disk_model != "texture":
+            p.error(f"{who} does not combine with --disk_model other than texture: a ray map shades the disk texture")
+        if args.gpus != 1:
+            p.error(f"{who} does not combine with --gpus other than 1: a ray map lives on one GPU")
+        if args.video and not args.ray_map:
+            p.error(f"{who} with --video needs --ray_map: the Stokes planes come from the ray map of a camera that stands still")
+        if args.video and getattr(args, "polarization_ticks", None) is not None:
+            p.error("--polarization_ticks is a still image's overlay: it does not combine with --video (the cell grids go to --stokes_output)")
+        if not getattr(args, "stokes_output", "x.npz").lower().endswith(".npz"):
+            p.error(f"--stokes_output writes a .npz file, got {args.stokes_output!r}")
+        if not getattr(args, "polarization_ticks", "x.png").lower().endswith(".png"):
+            p.error(f"--polarization_ticks writes a .png file, got {args.polarization_ticks!r}")
     # --exposure, --white, --transfer and --hdr_output without --tonemap mean --tonemap clip
     if args.tonemap is None and any(v is not None for v in (args.exposure, args.white, args.transfer, args.hdr_output)):
         args.tonemap = "clip"
@@ -498,6 +560,21 @@ def light_delay_from_args(args) -> dict:
     """The light delay of a command line as drivers.render_image / render_video take it: {} without --light_delay."""
     delay = getattr(args, "light_delay", None)
     return {} if delay is None else dict(light_delay=float(delay))
+
+
+def polarization_from_args(args) -> dict:
+    """The polarisation of a command line as drivers.render_image / render_video take it: {} without --polarization."""
+    pol = getattr(args, "polarization", None)
+    if pol is None:
+        return {}
+    from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, parse_field
+    out = dict(polarization=dict(field=parse_field(pol), fraction=float(getattr(args, "polarization_fraction", DEFAULT_FRACTION)),
+                                 cell=int(getattr(args, "polarization_cell", DEFAULT_CELL))))
+    if getattr(args, "stokes_output", None) is not None:
+        out["stokes_path"] = args.stokes_output
+    if getattr(args, "polarization_ticks", None) is not None and not getattr(args, "video", False):
+        out["ticks_path"] = args.polarization_ticks
+    return out
 
 
 def observer_beta(args):
@@ -624,6 +701,8 @@ def main(argv=None) -> int:
         width, height = frame_size(args.projection, width, height)
     # ... and the light delay
     delay_kw = light_delay_from_args(args)
+    # ... and the polarisation
+    pol_kw = polarization_from_args(args)
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))
@@ -633,6 +712,8 @@ def main(argv=None) -> int:
             drivers.check_projection(world=world, **proj_kw)
         if delay_kw:
             drivers.check_light_delay(delay_kw["light_delay"], world=world)
+        if pol_kw:
+            drivers.check_polarization(pol_kw["polarization"], video=True, ray_map=args.ray_map, world=world)
         if "BHR_FORCE_DEVICE" in os.environ:        # rehearsal: several ranks sharing one card
             local_rank = int(os.environ["BHR_FORCE_DEVICE"])
         elif world > 1:                             # a launcher that shows every rank only its own GPU: ordinal 0
@@ -657,7 +738,7 @@ def main(argv=None) -> int:
                              shutter_map=args.shutter_map, map_supersample=args.map_supersample, video_hdr=args.video_hdr,
                              hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure, **stars_kw,
                              **(dict(observer=args.observer, observer_velocity=args.observer_velocity, observer_sky=sky,
-                                     infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw)
+                                     infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw, **pol_kw)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -682,6 +763,6 @@ def main(argv=None) -> int:
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
         grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw, **stars_kw,
-        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw)
+        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw, **pol_kw)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

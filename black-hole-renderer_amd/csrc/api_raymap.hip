@@ -104,6 +104,12 @@ int32_t check_stars(const bhr_ctx *ctx, const char *who) {
     return BHR_OK;
 }
 
+// polarisation (bhr_set_polarization): the Stokes kernel walks the build view's records of a map with one ray per pixel
+int32_t check_polar(const bhr_ctx *ctx, const char *who, const char *what) {
+    if (bhr_have_polar(ctx)) return bhr_fail(BHR_ERR_STATE, "%s: a polarisation is set (bhr_set_polarization) and %s -- switch it off (NULL) first", who, what);
+    return BHR_OK;
+}
+
 }  // namespace
 
 void bhr_raymap_release(bhr_ctx *ctx) {
@@ -112,6 +118,7 @@ void bhr_raymap_release(bhr_ctx *ctx) {
     delete ctx->raymap;
     ctx->raymap = nullptr;
     bhr_stars_invalidate(ctx);
+    bhr_polar_invalidate(ctx);
 }
 
 int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
@@ -124,7 +131,9 @@ int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
         return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: needs a whole-frame context (rows %d of %d)", ctx->rows, ctx->cfg.height);
     if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no ray map has been built (bhr_raymap_build)");
     BHR_TRY(check_context(ctx, "bhr_raymap_render", BHR_ERR_STATE));
-    return check_stars(ctx, "bhr_raymap_render");
+    BHR_TRY(check_stars(ctx, "bhr_raymap_render"));
+    if (ctx->raymap->ss > 1) BHR_TRY(check_polar(ctx, "bhr_raymap_render", "the map is supersampled; the Stokes planes need a map with one ray per pixel"));
+    return BHR_OK;
 }
 
 // bhr_raymap_render_view's refusals, before anything is launched: the disk is not tilted, and `cam` is the build camera turned
@@ -144,7 +153,8 @@ int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32
     if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no ray map has been built (bhr_raymap_build)", who);
     BHR_TRY(check_context(ctx, who, BHR_ERR_STATE));
     BHR_TRY(turn_of_build(ctx->raymap->cam, cam, who, rot_c, rot_s));
-    return check_stars(ctx, who);
+    BHR_TRY(check_stars(ctx, who));
+    return check_polar(ctx, who, "the Stokes planes are the build view's; turned views have none");
 }
 
 // bhr_raymap_render_shutter's refusals (include/bhr.h), before anything is launched.  A sample with the build camera's pose,
@@ -190,7 +200,7 @@ int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, in
     if (bhr_have_stars(ctx))
         return bhr_fail(BHR_ERR_STATE, "%s: a star catalogue is set (bhr_set_stars, %d stars); shutter frames from the map have no point stars -- remove it (n = 0) first", who,
                         ctx->stars->n);
-    return BHR_OK;
+    return check_polar(ctx, who, "shutter frames from the map have no Stokes planes");
 }
 
 extern "C" {
@@ -221,6 +231,7 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     bhr_raymap *rm = ctx->raymap;
     rm->built = 0;
     bhr_stars_invalidate(ctx);         // the star plane of the build view belongs to the map this build rewrites
+    bhr_polar_invalidate(ctx);         // ... and so do the Stokes planes of its last frame
     if (rm->a.hits && (rm->alloc_slots != K || rm->alloc_comps != comps || rm->alloc_ss != ss)) {
         BHR_TRY(drain(ctx));
         free_planes(rm);

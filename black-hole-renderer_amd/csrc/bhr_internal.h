@@ -242,6 +242,17 @@ struct BhrRayMapStarArgs : BhrRayMapArgs {
     const float *stars;          // (rows, W, 3): the star plane S of the frame's view (stars.hip)
 };
 
+// Third argument of raymap_stokes_kernel (march_polar.hip), behind the march's block of the map's view and the map: the frame's
+// polarisation -- wave-uniform, so scalars -- and the three planes it fills.  Also the argument of stokes_cells_kernel.
+struct BhrStokesArgs {
+    float b[3];                  // the field in the gas frame (b_r, b_phi, b_z), normalized on the host in binary64 and rounded once
+    float frac;                  // Pi_0
+    float *out;                  // I | Q | U: three planes of rows W floats
+    float *cells;                // (gh, gw, 3): the means over cell x cell pixels
+    int32_t cell, gw, gh;
+    int32_t width, rows;
+};
+
 // Second argument of stars_gather_kernel (stars.hip), behind the march's block of the view (its camera fields and frame shape):
 // the map's two planes it reads, the turn of the view, the binned catalogue and the plane it fills.
 struct BhrStarsArgs {
@@ -395,12 +406,19 @@ struct bhr_frame_slot {
     float *d_acc_bg, *d_acc_disk;
     // point stars (api_stars.hip), on first use: the star plane of a turned view's frame, (rows, W, 3) f32, and behind it its gather's counts
     float *d_star_plane;
+    // polarisation (api_polar.hip), on first use: the Stokes planes I | Q | U of the slot's last map frame, rows W floats each, and
+    // the grid of their cell means (sized for the smallest cell); stokes_cell: the cell size of that frame, 0: the slot has none
+    float *d_stokes, *d_stokes_cells;
+    int32_t stokes_cell;
     // second march stream: the strict tiles of a two-stream hybrid march run on it beside the fast ones instead of ahead of
     // them (bhr_aux_fork / _join, which creates the streams of all slots on first use)
     hipStream_t aux_stream;
     hipEvent_t aux_fork, aux_done;
     hipEvent_t done;        // end of the slot's last bhr_render (and of frame work queued behind it: bhr_leave_frame)
-    hipEvent_t march_done;  // end of its last march: the last reader of the scene (bhr_enter_scene_write); borrowed from the timing ring
+    // the last reader of the scene in the slot's last frame (bhr_enter_scene_write): the end of its last march, borrowed from the
+    // timing ring -- or, for a map frame with a polarisation set, stokes_done: its Stokes pass samples the disk texture behind the march
+    hipEvent_t march_done;
+    hipEvent_t stokes_done; // the slot's own, on first use (api_polar.hip): behind the Stokes pass of its last map frame
     int32_t allocated;
     int32_t in_flight;      // rendered since the last join
 };
@@ -536,6 +554,12 @@ struct bhr_ctx {
 
     // point stars (api_stars.hip)
     bhr_stars *stars;          // null until a catalogue is set (bhr_set_stars)
+
+    // polarisation (api_polar.hip): polar_on = a polarisation is set (bhr_set_polarization); stokes_slot = the frame slot that holds
+    // the Stokes planes of the last map frame rendered since (-1: none)
+    int32_t polar_on;
+    bhr_polarization polar;
+    int32_t stokes_slot;
 };
 
 // The active frame slot: the one bhr_activate_slot / bhr_render last pointed the launchers at.
@@ -790,6 +814,17 @@ int32_t bhr_stars_ensure_plane(bhr_ctx *ctx);
 int32_t bhr_stars_frame_plane(bhr_ctx *ctx, const bhr_camera *cam, float c, float s, const float **plane);
 void bhr_stars_invalidate(bhr_ctx *ctx);                                   // the map changed: the cached plane is stale
 void bhr_stars_release(bhr_ctx *ctx);
+
+// ---- api_polar.hip, march_polar.hip -----------------------------------------------------------------------------------------------------
+inline bool bhr_have_polar(const bhr_ctx *ctx) { return ctx->polar_on != 0; }
+// the Stokes pass of the active slot's map frame on ctx->stream, behind its shade launch: the planes and the cell grid into the
+// slot's own storage (allocated here on first use); records the slot's stokes_done behind it and makes it the slot's march_done
+int32_t bhr_polar_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm);
+void bhr_polar_invalidate(bhr_ctx *ctx);                                   // the map or the setting changed: no frame's planes to read
+// march_launch.hip: the two launches of that pass under the march's block of call's view
+int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrStokesArgs &s);
+const void *bhr_stokes_kernel(int32_t diff);                               // march_polar.hip -> march_polar.o
+const void *bhr_stokes_cells_kernel(void);
 
 // ---- lifecycle.hip, texture.hip, disk_v2.hip ------------------------------------------------------------------------------------------
 void bhr_population_free(bhr_ctx *ctx);

@@ -132,6 +132,7 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
     ctx->mip_lds_from = -1;
     ctx->ss = 1;
     ctx->ada_info_slot = -1;
+    ctx->stokes_slot = -1;
 
     auto bail = [&](int32_t rc) { bhr_destroy(ctx); return rc; };
     if (hipSetDevice(cfg->device) != hipSuccess) return bail(bhr_fail(BHR_ERR_HIP, "hipSetDevice(%d) failed", cfg->device));

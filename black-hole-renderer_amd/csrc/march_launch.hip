@@ -610,6 +610,32 @@ int32_t bhr_launch_stars_gather(bhr_ctx *ctx, const bhr_camera *cam, const BhrRa
     return BHR_OK;
 }
 
+// The Stokes pass of a map frame (march_polar.hip; api_polar.hip owns the planes): the Stokes kernel on the shade kernel's grid
+// under the march's block of call's frame -- the block the shade launch of the same frame was given, so shade_hit sees the values
+// it saw there -- then the cell means, one block per cell.  Stores no layer: the slot's BG / DISK and what is noted of them stay.
+int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrStokesArgs &s) {
+    if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "polarisation: the Stokes kernel has no supersampled twin (factor %d)", call.ss);
+    BhrMarchArgs a;
+    march_args(ctx, call, nullptr, 1, false, a);
+    if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5) || s.width != a.width || s.rows != a.rows)
+        return bhr_fail(BHR_ERR_STATE, "polarisation: the map does not fit the frame");
+    if (s.cell < 1 || s.gw != (a.width + s.cell - 1) / s.cell || s.gh != (a.rows + s.cell - 1) / s.cell || !s.out || !s.cells)
+        return bhr_fail(BHR_ERR_STATE, "polarisation: a cell grid of %d x %d cells of %d pixels for a %d x %d frame", s.gw, s.gh, s.cell, a.width, a.rows);
+    const void *fn = bhr_stokes_kernel(diff ? 1 : 0), *fc = bhr_stokes_cells_kernel();
+    if (!fn || !fc) return bhr_fail(BHR_ERR_STATE, "polarisation: no Stokes kernel in this library");
+    BhrRayMapArgs mm = m;
+    BhrStokesArgs ss = s;
+    void *args[] = {&a, &mm, &ss};
+    (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
+    BHR_HIP(hipGetLastError());
+    void *cargs[] = {&ss};
+    // whole waves, no more than the cell has pixels for: one wave for the 8 x 8 cell, four for 16 x 16 and 32 x 32
+    const unsigned cell_threads = s.cell * s.cell >= 256 ? 256u : 64u;
+    (void)hipLaunchKernel(fc, dim3(s.gw * s.gh), dim3(cell_threads), cargs, 0, call.stream);
+    BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}
+
 // All samples of a shutter frame from the map in one launch (bhr_raymap_render_shutter's fused route): the shade kernel's grid,
 // the march's argument block of call.cam -- the two fields of it that a shade kernel reads of a camera, t_offset and the
 // position, are taken from the samples' table inside the kernel instead -- the map, and that table by value.  The caller closes

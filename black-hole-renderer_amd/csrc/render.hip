@@ -143,6 +143,13 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     *fm = {rm.ss, 1, false};
     BHR_TRY(raymap_frame_launches(ctx, call, rm, rot_c, rot_s));
     f.march_done = ctx->ring_ev[ring * 3 + 1];
+    // a polarisation is set (bhr_set_polarization): the Stokes pass over the same records into the slot's own planes, behind the
+    // frame's march bracket and ahead of its post-pass -- the frame's end event covers it, so a read waits for it like for the rest.
+    // It reads the scene (shade_hit samples the disk texture), so it replaces f.march_done by an event of the slot's own behind it.
+    if (bhr_have_polar(ctx)) {
+        BHR_TRY(bhr_polar_frame(ctx, call, rm));
+        ctx->stokes_slot = k;
+    }
     return post_on_slot(ctx, flags, k, ring);
 }
 

@@ -232,7 +232,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  dither: str = "none", grade: Optional[dict] = None, hdr_path: Optional[str] = None,
                  passes_path: Optional[str] = None, spin: float = 0.0, redshift: str = "model",
                  observer=None, observer_sky: bool = True, stars: Optional[dict] = None,
-                 projection: Optional[str] = None, projection_fov=None, light_delay=None) -> np.ndarray:
+                 projection: Optional[str] = None, projection_fov=None, light_delay=None, polarization: Optional[dict] = None,
+                 stokes_path: Optional[str] = None, ticks_path: Optional[str] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -255,7 +256,11 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     unused (bhr_amd.projection.frame_size is the command line's size rule); combines with ``observer`` and takes what it takes
     (check_projection).  ``light_delay``: a scale in [0, 16] -- every disk crossing shaded at the time its light left the gas
     (HipRenderer.render_async; 1 is physical); one device, the texture source, the strict Schwarzschild march of the pinhole
-    camera that stands still (check_light_delay)."""
+    camera that stands still (check_light_delay).  ``polarization``: None, or dict(field=, fraction=, cell=) -- Stokes Q / U maps
+    of the disk (check_polarization): the view's ray map is built and the frame is shaded from it, the way ``stars`` does it, by the
+    strict arithmetic whatever ``math`` says, with the Stokes pass behind the shade; ``stokes_path`` then takes the planes, the cell
+    grid, the field, Pi_0, the convention and the camera as a compressed .npz (bhr_amd.polarization.write_stokes) and ``ticks_path``
+    the frame with a polarisation tick per cell drawn over it (draw_ticks) as a PNG."""
     check_depth_and_dither(bit_depth, dither)
     facts = dict(anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus, spin=spin,
                  redshift=redshift, passes=passes_path is not None)      # what the three variant checks take alike
@@ -265,6 +270,9 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                         disk_model=disk_model, observer=observer)
     check_observer(observer, **facts)
     check_passes(passes_path, gpus, supersample, disk_model)
+    polarization = check_polarization(polarization, supersample=supersample, disk_model=disk_model, gpus=gpus, spin=spin, redshift=redshift,
+                                      observer=observer is not None, projection=projection is not None, light_delay=light_delay is not None,
+                                      stokes_path=stokes_path, ticks_path=ticks_path)
     grade = check_grade(grade)
     if hdr_path is not None:
         check_hdr_path(hdr_path)
@@ -300,17 +308,34 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     print(f"HIP: {width}x{height}, cam_pos={list(cam_pos)}, fov={fov}°, step_size={step_size}")
     if grade is not None:
         renderer.set_grade(**grade)
-    if stars is not None:
+    if polarization is not None:
+        renderer.set_polarization(**polarization)          # ahead of the frame: its Stokes pass rides behind the shade launch
+    if stars is not None or polarization is not None:
         from . import _lib
         renderer.build_ray_map(cam_pos, fov)
         renderer.render_from_ray_map_async(frame=0)
         img = renderer.read_layer(_lib.LAYER_FINAL)
-        si = renderer.stars_info()
-        print(f"Point stars: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
-              f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
     else:
         img = renderer.render(cam_pos, fov, frame=0, observer=observer, observer_sky=observer_sky, projection=projection,
                               projection_fov=projection_fov, light_delay=light_delay)
+    if stars is not None:
+        si = renderer.stars_info()
+        print(f"Point stars: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
+              f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
+    if polarization is not None:
+        from . import polarization as pol_mod
+        planes, cells = renderer.stokes(), renderer.stokes_cells()
+        deg, _ = pol_mod.degree_and_angle(cells[..., 0], cells[..., 1], cells[..., 2])
+        print(f"Polarization: field {polarization['field']}, fraction {polarization['fraction']:g}, {cells.shape[1]} x {cells.shape[0]} cells of "
+              f"{polarization['cell']} pixels, largest cell degree {float(deg.max()) if deg.size else 0.0:.3f}")
+        if stokes_path is not None:
+            pol_mod.write_stokes(stokes_path, cells, polarization["cell"], polarization["field"], polarization["fraction"],
+                                 camera=dict(cam_pos=list(cam_pos), fov=fov), stokes=planes)
+            print(f"Saved: {stokes_path}")
+        if ticks_path is not None:
+            from .output import png_write, quantize
+            png_write(ticks_path, pol_mod.draw_ticks(quantize(img), cells, polarization["cell"]))
+            print(f"Saved: {ticks_path}")
     if hdr_path is not None:
         save_hdr(renderer.read_hdr(), hdr_path)
     c = renderer.counters()
@@ -434,6 +459,58 @@ def check_passes(passes_path, gpus: int = 1, supersample: int = 1, disk_model: s
         raise ValueError("a ray map holds one ray per pixel: --passes does not combine with --supersample > 1")
     if disk_model != "texture":
         raise ValueError("a ray map shades the disk texture: --passes does not combine with --disk_model v2 / v2_volume")
+
+
+def check_polarization(polarization, video: bool = False, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False,
+                       shutter: float = 0.0, supersample=1, map_supersample: int = 1, disk_model: str = "texture", gpus: int = 1,
+                       world: int = 1, spin: float = 0.0, redshift: str = "model", observer: bool = False, projection: bool = False,
+                       light_delay: bool = False, stokes_path=None, ticks_path=None):
+    """polarization=dict(field=, fraction=, cell=) (bhr_amd.polarization.check: a preset or three numbers, Pi_0 in [0, 1], a cell
+    of 8, 16 or 32 pixels): Stokes Q / U maps of the disk, computed through a ray map of the view.  -> the dict with its defaults
+    filled in, or None without one (``stokes_path`` / ``ticks_path`` alone are an error).  Raises ValueError, naming the
+    combination, before any device work, for what polarization does not take: a spin or the exact redshift (the transport rule is
+    Schwarzschild's), a moving observer, a projection, light delay, the orbit and shutter maps, shutter, supersampling of the frame
+    or of the map, Disk V2, several GPUs or ranks, a video without ray_map, and outputs that are not .npz / .png."""
+    if polarization is None:
+        if stokes_path is not None or ticks_path is not None:
+            raise ValueError("stokes_output and polarization_ticks need a polarization: they are its outputs")
+        return None
+    from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check
+    unknown = set(polarization) - {"field", "fraction", "cell"}
+    if unknown or "field" not in polarization:
+        raise ValueError(f"polarization takes field, fraction and cell, got {sorted(polarization)}")
+    out = check(polarization["field"], polarization.get("fraction", DEFAULT_FRACTION), polarization.get("cell", DEFAULT_CELL))
+    if spin != 0 or redshift != "model":
+        raise ValueError("polarization does not combine with a spin or the exact redshift: the transport rule is Schwarzschild's and a ray map holds Schwarzschild rays")
+    if observer:
+        raise ValueError("polarization does not combine with a moving observer: a ray map holds the rays of the camera that stands still")
+    if projection:
+        raise ValueError("polarization does not combine with a projection: a ray map holds the rays of the pinhole camera")
+    if light_delay:
+        raise ValueError("polarization does not combine with light_delay: a ray map's records hold no travel time")
+    if orbit_map:
+        raise ValueError("polarization does not combine with orbit_map: the Stokes planes are the build view's, turned views have none")
+    if shutter_map:
+        raise ValueError("polarization does not combine with shutter_map: shutter frames from the map have no Stokes planes")
+    if shutter > 0:
+        raise ValueError("polarization does not combine with shutter: shutter frames are marched, the Stokes planes come from a ray map")
+    if map_supersample != 1:
+        raise ValueError("polarization does not combine with map_supersample > 1: the Stokes planes need a map with one ray per pixel")
+    if supersample not in (None, 1):
+        raise ValueError("polarization does not combine with supersample > 1: the Stokes planes need a map with one ray per pixel")
+    if disk_model != "texture":
+        raise ValueError("polarization does not combine with disk_model v2 / v2_volume: a ray map shades the disk texture")
+    if gpus != 1 or world != 1:
+        raise ValueError("polarization renders on one GPU: a ray map lives on one GPU")
+    if video and not ray_map:
+        raise ValueError("polarization in a video needs ray_map: the Stokes planes come from the ray map of a camera that stands still")
+    if video and ticks_path is not None:
+        raise ValueError("polarization_ticks is a still image's overlay: a video writes its cell grids to stokes_output")
+    if stokes_path is not None and not str(stokes_path).lower().endswith(".npz"):
+        raise ValueError(f"stokes_output is written as a .npz file, got {stokes_path!r}")
+    if ticks_path is not None and not str(ticks_path).lower().endswith(".png"):
+        raise ValueError(f"polarization_ticks is written as a .png file, got {ticks_path!r}")
+    return out
 
 
 def check_ray_map(ray_map: bool, orbit: bool = False, shutter: float = 0.0, supersample=1, disk_model: str = "texture",
@@ -645,7 +722,7 @@ def hdr_sidecar(hdr: dict, max_cll: float, max_fall: float, frames: int) -> dict
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
                     shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None,
-                    stars=None, projection=None, light_delay=None) -> dict:
+                    stars=None, projection=None, light_delay=None, polarization=None) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -679,6 +756,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(projection=projection)
     if light_delay is not None:
         params.update(light_delay=light_delay)
+    if polarization is not None:
+        params.update(polarization={"field": list(polarization["field"]), "fraction": polarization["fraction"], "cell": polarization["cell"]})
     return params
 
 
@@ -718,7 +797,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  map_supersample: int = 1, video_hdr: Optional[str] = None, hdr_white: float = 203.0, hdr_exposure: float = 0.0,
                  observer: Optional[str] = None, observer_velocity=None, observer_sky: bool = True,
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
-                 light_delay=None, **_deprecated_kwargs) -> None:
+                 light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -826,7 +905,14 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     ``light_delay`` (a scale in [0, 16]): every frame is render_async(..., light_delay=scale) with the frame's own camera
     position and t_offset, with and without ``orbit`` -- each disk crossing shaded at the time its light left the gas.  Refused
     with ValueError, before any device work, with what check_light_delay names.  The progress record carries the scale when one
-    is given, and a resume under another starts over."""
+    is given, and a resume under another starts over.
+
+    ``polarization`` (dict(field=, fraction=, cell=); needs ``ray_map=True``): every frame from the map is followed by the Stokes
+    pass (HipRenderer.set_polarization), and the frames' cell grids -- never the full planes -- are collected into ONE compressed
+    .npz at ``stokes_path`` (default ``<output stem>.stokes.npz``) with ``cells`` of shape (n_frames, gh, gw, 3).  Refused with
+    ValueError, before any device work, with what check_polarization names, and with a resume that finds frames already rendered
+    (their grids are gone).  The renderer's polarisation is switched off on return.  The progress record names the polarisation
+    only when it is set."""
     moving = observer is not None or observer_velocity is not None or infall_to is not None
     projected = projection is not None or projection_fov is not None
     disk_model = "texture" if getattr(renderer, "_dv2", None) is None else "v2"
@@ -851,6 +937,12 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         light_delay = check_light_delay(light_delay, world=world, observer=moving, projection=projected, stars=stars is not None, **facts)
     check_map_supersample(map_supersample, ray_map, orbit_map, shutter_map)
     check_shutter(shutter, shutter_samples)
+    if polarization is not None or stokes_path is not None:     # (without one the renderer is not asked anything, as ever)
+        polarization = check_polarization(polarization, video=True, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map, shutter=shutter,
+                                          supersample=renderer.supersample if supersample is None else supersample,
+                                          map_supersample=map_supersample, disk_model=disk_model, world=world, spin=renderer.spin,
+                                          redshift=renderer.redshift, observer=moving, projection=projected, light_delay=light_delay is not None,
+                                          stokes_path=stokes_path)
     if video_stream not in ("auto", "y4m", "off"):
         raise ValueError(f"video_stream must be 'auto', 'y4m' or 'off', got {video_stream!r}")
     hdr = check_video_hdr(video_hdr, hdr_white, hdr_exposure, width, height, world, video_codec, video_stream)
@@ -901,7 +993,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                                                                  "sky": bool(observer_sky), "infall_to": infall_to},
                              **({} if stars is None else {"stars": stars}),
                              **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}),
-                             **({} if light_delay is None else {"light_delay": light_delay}))
+                             **({} if light_delay is None else {"light_delay": light_delay}),
+                             **({} if polarization is None else {"polarization": polarization}))
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -945,6 +1038,10 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     if hdr is not None and completed:
         raise ValueError(f"--video_hdr does not resume: {len(completed)} frames are already rendered and a stream cannot be taken "
                          "up in the middle; render without --resume")
+
+    if polarization is not None and completed:
+        raise ValueError(f"polarization does not resume: {len(completed)} frames are already rendered and their cell grids are gone; "
+                         "render without --resume")
 
     total_t0 = time.time()
     rendered = 0
@@ -998,6 +1095,9 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         renderer.build_ray_map(static_cam_pos, fov, supersample=map_supersample)     # the one march of the video
         info = renderer.ray_map_info()
         print(f"  ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
+    stokes_grids = {}
+    if polarization is not None:
+        renderer.set_polarization(**polarization)
     if orbit_map:
         # the orbit's radius is |pov|, not the pov's xy norm: frame 0 of the orbit, not the pov itself
         renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees), fov, supersample=map_supersample)     # the one march of the video
@@ -1010,53 +1110,68 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         print(f"  shutter ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
     t_loop0 = time.time()                               # ``stats`` (bench.py): the one-off set-up apart from the frame loop
 
-    for frame in range(n_frames):
-        t = frame * dt
-        mine = frame % world == rank and frame not in completed
-        # the factories advance on every frame index on every rank; statistics are a function of the
-        # frame index (every 60th), texture composition only happens for frames rendered here
-        advance_lifecycle_frame(renderer, factories, t, dt, recompute_stats=(frame % 60 == 0), compose=mine)
-        if not mine:
-            continue
-        cam_pos = orbit_position(static_cam_pos, frame, n_frames, orbit_degrees) if orbit else static_cam_pos
-        if plan is not None:
-            cam_pos, beta = plan[frame]                    # the moving observer: the frame's position and its velocity there
-        t0 = time.time()
-        if shutter > 0:
-            times = shutter_times(frame, shutter, shutter_samples)
-            positions = [orbit_position(static_cam_pos, u, n_frames, orbit_degrees) if orbit else static_cam_pos for u in times]
-            t_offsets = [(u - frame) * disk_rotation_speed for u in times]
-            if shutter_map:                                # the same samples from the map: shade, no march
-                renderer.render_shutter_from_ray_map_async(t_offsets, positions if orbit else None, fov)
-            else:
-                renderer.render_shutter_async(positions, fov, t_offsets)
-        elif ray_map:
-            renderer.render_from_ray_map_async(frame=0)    # the same frame from the map: shade, no march
-        elif orbit_map:
-            renderer.render_from_ray_map_async(frame=0, cam_pos=cam_pos, fov=fov)    # the map turned to the frame's camera
-        else:                                              # marched: the frame of the moving camera, through the projection, with light delay
-            renderer.render_async(cam_pos, fov, frame=0, observer=None if plan is None else beta, observer_sky=observer_sky,
-                                  projection=projection, projection_fov=projection_fov, light_delay=light_delay)   # (lens flare: on the device)
-        sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))
-        if stream is not None:
-            try:
-                stream.submit()
-            except Exception as e:                      # the encoder went away (EPIPE): the PNG frames carry on
-                stream, encoder = _drop_stream(stream, encoder, e), None
-        elapsed = time.time() - t0
-        rendered += 1
-        submitted.append(frame)
-        if rendered % 50 == 0 or frame >= n_frames - world:
-            sink.drain()                                # progress.json only lists frames that are on disk
-            completed.update(submitted)
-            submitted.clear()
-            with open(progress_file, "w") as f:
-                json.dump({"params": params, "completed": sorted(completed)}, f)
-        if rendered % 100 == 0 or frame == n_frames - 1:
-            print(f"  frame {frame}/{n_frames} {elapsed * 1e3:.1f} ms, done {len(completed)}")
+    try:                                                # (a polarisation set above does not outlive a frame loop that raises)
+        for frame in range(n_frames):
+            t = frame * dt
+            mine = frame % world == rank and frame not in completed
+            # the factories advance on every frame index on every rank; statistics are a function of the
+            # frame index (every 60th), texture composition only happens for frames rendered here
+            advance_lifecycle_frame(renderer, factories, t, dt, recompute_stats=(frame % 60 == 0), compose=mine)
+            if not mine:
+                continue
+            cam_pos = orbit_position(static_cam_pos, frame, n_frames, orbit_degrees) if orbit else static_cam_pos
+            if plan is not None:
+                cam_pos, beta = plan[frame]                    # the moving observer: the frame's position and its velocity there
+            t0 = time.time()
+            if shutter > 0:
+                times = shutter_times(frame, shutter, shutter_samples)
+                positions = [orbit_position(static_cam_pos, u, n_frames, orbit_degrees) if orbit else static_cam_pos for u in times]
+                t_offsets = [(u - frame) * disk_rotation_speed for u in times]
+                if shutter_map:                                # the same samples from the map: shade, no march
+                    renderer.render_shutter_from_ray_map_async(t_offsets, positions if orbit else None, fov)
+                else:
+                    renderer.render_shutter_async(positions, fov, t_offsets)
+            elif ray_map:
+                renderer.render_from_ray_map_async(frame=0)    # the same frame from the map: shade, no march
+                if polarization is not None:
+                    stokes_grids[frame] = renderer.stokes_cells()      # the frame's cell grid (synchronises: a few kB per frame)
+            elif orbit_map:
+                renderer.render_from_ray_map_async(frame=0, cam_pos=cam_pos, fov=fov)    # the map turned to the frame's camera
+            else:                                              # marched: the frame of the moving camera, through the projection, with light delay
+                renderer.render_async(cam_pos, fov, frame=0, observer=None if plan is None else beta, observer_sky=observer_sky,
+                                      projection=projection, projection_fov=projection_fov, light_delay=light_delay)   # (lens flare: on the device)
+            sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))
+            if stream is not None:
+                try:
+                    stream.submit()
+                except Exception as e:                      # the encoder went away (EPIPE): the PNG frames carry on
+                    stream, encoder = _drop_stream(stream, encoder, e), None
+            elapsed = time.time() - t0
+            rendered += 1
+            submitted.append(frame)
+            if rendered % 50 == 0 or frame >= n_frames - world:
+                sink.drain()                                # progress.json only lists frames that are on disk
+                completed.update(submitted)
+                submitted.clear()
+                with open(progress_file, "w") as f:
+                    json.dump({"params": params, "completed": sorted(completed)}, f)
+            if rendered % 100 == 0 or frame == n_frames - 1:
+                print(f"  frame {frame}/{n_frames} {elapsed * 1e3:.1f} ms, done {len(completed)}")
+    finally:
+        if polarization is not None:
+            renderer.set_polarization(None)
 
     frames_written, bytes_written = sink.drain()
     sink.close()
+    if polarization is not None:
+        from .polarization import write_stokes
+        path = stokes_path if stokes_path is not None else os.path.splitext(output_path)[0] + ".stokes.npz"
+        # one GPU and no resume (check_polarization, above): every frame was rendered here, so every grid is here
+        if len(stokes_grids) != n_frames:
+            raise RuntimeError(f"polarization: {len(stokes_grids)} cell grids for {n_frames} frames; {path} is not written")
+        write_stokes(path, np.stack([stokes_grids[f] for f in range(n_frames)]), polarization["cell"], polarization["field"],
+                     polarization["fraction"], camera=dict(cam_pos=list(static_cam_pos), fov=fov))
+        print(f"Saved: {path} ({n_frames} cell grids of {polarization['cell']}-pixel cells)")
     if ray_map or orbit_map or shutter_map:
         renderer.free_ray_map()
     if mjpeg:

@@ -685,6 +685,48 @@ class HipRenderer:
         _lib.check(self._lib.bhr_stars_resources(1 if turned else 0, out))
         return {"vgprs": int(out[0]), "lds_bytes": int(out[1]), "scratch_bytes": int(out[2])}
 
+    # ------------------------------------------------------------------ polarisation
+    def set_polarization(self, field="toroidal", fraction: float = 0.7, cell: int = 16) -> None:
+        """Set the polarisation the frames from the ray map compute Stokes planes under (bhr_set_polarization; include/bhr.h
+        states the model, bhr_amd.polarization the presets): ``field`` a preset name or (b_r, b_phi, b_z) in the gas frame,
+        ``fraction`` Pi_0 in [0, 1], ``cell`` the side of a cell of the grid (8, 16 or 32); ``field=None`` switches it off.  The
+        frames themselves are what they are without it.  Turned views, shutter frames from the map and supersampled maps are
+        refused while it is set; a spin, Disk V2 and row-block renderers refuse the setter.  Synchronises."""
+        if field is None:
+            _lib.check(self._lib.bhr_set_polarization(self._ctx, None))
+            return
+        from . import polarization as pol_mod
+        b = pol_mod.field_vector(field)
+        par = _lib.Polarization(b[0], b[1], b[2], float(fraction), int(cell))
+        _lib.check(self._lib.bhr_set_polarization(self._ctx, C.byref(par)))
+
+    def clear_polarization(self) -> None:
+        """Switch the polarisation off (bhr_set_polarization with NULL)."""
+        self.set_polarization(None)
+
+    def stokes(self) -> np.ndarray:
+        """Stokes I, Q, U of the last frame from the ray map, (3, rows, width) float32 (bhr_read_stokes).  chi = atan2(U, Q) / 2 is
+        counted from image-right towards image-up.  Synchronises."""
+        out = np.empty((3, self.rows, self.width), dtype=np.float32)
+        for k in range(3):
+            _lib.check(self._lib.bhr_read_stokes(self._ctx, k, _lib.fptr(out[k])))
+        return out
+
+    def stokes_cells(self) -> np.ndarray:
+        """The means of I, Q, U of that frame over the cells of the grid, (gh, gw, 3) float32 (bhr_read_stokes_cells)."""
+        dims = (C.c_int32 * 2)()
+        _lib.check(self._lib.bhr_read_stokes_cells(self._ctx, None, dims))
+        out = np.empty((int(dims[0]), int(dims[1]), 3), dtype=np.float32)
+        _lib.check(self._lib.bhr_read_stokes_cells(self._ctx, _lib.fptr(out), dims))
+        return out
+
+    def stokes_resources(self, diff: bool = False) -> dict:
+        """Registers, LDS bytes and scratch bytes of the Stokes kernel (bhr_stokes_resources); ``diff``: the one of a map with
+        differentials."""
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_stokes_resources(1 if diff else 0, out))
+        return {"vgprs": int(out[0]), "lds_bytes": int(out[1]), "scratch_bytes": int(out[2])}
+
     def sync(self) -> None:
         _lib.check(self._lib.bhr_sync(self._ctx))
 

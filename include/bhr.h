@@ -449,6 +449,53 @@ typedef struct {
 BHR_API int32_t bhr_set_stars(bhr_ctx *ctx, const bhr_star *stars, int32_t n, const bhr_star_params *p);
 BHR_API int32_t bhr_get_stars_info(bhr_ctx *ctx, bhr_stars_info *out);
 BHR_API int32_t bhr_stars_resources(int32_t rot, int32_t out[3]);
+/* ---- polarisation: Stokes I, Q, U of the disk through the ray map (csrc/march_polar.hip, csrc/api_polar.hip; DESIGN 4 "Polarisation") ----
+ * With a polarisation set, a frame of bhr_raymap_render is followed on its own frame slot and stream by one more pass over the
+ * map's records, which stores three f32 planes (rows, W) and a grid of cell means; the frame's layers and rows are what they are
+ * without it.  Units r_s = 1, F(r) = 1 - 1 / r.  For a pixel: C the camera position, D the unit direction its ray is launched
+ * along, (R, U, Fwd) the camera's basis; the photon arrives travelling along -D.  N = normalize(C x D) is the unit normal of the
+ * ray's plane, which is parallel-transported along a Schwarzschild ray, so the angle psi between the polarisation vector and N,
+ * measured about the photon direction, is the same at the gas and at the camera (Connors, Piran and Stark 1980).  A ray with
+ * |C x D| < 1e-6 |C| is radial and adds nothing to Q and U.  Per stored crossing k, front to back:
+ *   P = (hit_x, hit_y, hit_y tan_t), r_hat = P / |P|, r = max(|P|, 1 + 1e-3), w = to_cam;
+ *   K = normalize(K0 - (K0 . N) N), K0 = (w . r_hat) / sqrt(F(r)) r_hat + (w - (w . r_hat) r_hat): the photon's direction in the
+ *     static observer's orthonormal frame, in the ray's plane;
+ *   the gas: v_hat = normalize(r_hat x n), n = (0, -sin_t, cos_t) the disk normal (the g-factor's v_hat, with its fallback),
+ *     beta = min(r Omega / sqrt(F), 0.99), Omega = sqrt(0.5 / r^3), gamma = 1 / sqrt(1 - beta^2);
+ *   in the gas frame: n' = [K + ((gamma - 1)(K . v_hat) - gamma beta) v_hat] / (gamma (1 - beta K . v_hat));
+ *   the field: B' = normalize(b_r r_hat + b_phi v_hat + b_z n), e' = n' x B', s2 = |e'|^2, e_hat = e' / sqrt(s2) -- the electric
+ *     vector of synchrotron light is perpendicular to the projected field; the polarised weight is p_k = fraction s2, which goes
+ *     to 0 continuously where the photon runs along the field (s2 = 0 adds nothing);
+ *   back in the static frame: f = e_hat + (gamma - 1)(e_hat . v_hat) v_hat - gamma beta (e_hat . v_hat) K, a unit vector
+ *     perpendicular to K; cos psi = f . N, sin psi = f . (N x K);
+ *   at the camera: f_c = cos psi N + sin psi (N x (-D)); the sky-plane axes are e_x = normalize(R - (R . D) D) and e_y = D x e_x
+ *     with its sign flipped if e_y . U < 0; x = f_c . e_x, y = f_c . e_y, cos 2chi = (x^2 - y^2) / (x^2 + y^2),
+ *     sin 2chi = 2 x y / (x^2 + y^2): chi is counted from image-right towards image-up;
+ *   c_k = the Rec. 709 luma (0.2126, 0.7152, 0.0722) of what the crossing added to the disk accumulator (after minus before).
+ * I = sum c_k, Q = sum p_k c_k cos 2chi_k, U = sum p_k c_k sin 2chi_k, each one f32 running sum in record order.  A crossing
+ * outside [r_disk_inner, r_disk_outer] adds nothing; a pixel on the map's overflow list (more crossings than slots) has
+ * I = Q = U = 0.  The cell grid: means of I, Q and U over cell x cell pixel cells, ceil(rows / cell) x ceil(W / cell) of them,
+ * edge cells over the pixels they have; summed in a fixed order without floating-point atomics, so two runs give the same bits.
+ * bhr_set_polarization: p NULL switches it off (the default).  It synchronises.  BHR_ERR_INVALID, the context unchanged: a field
+ *   that is zero or not finite; fraction outside [0, 1]; cell other than 8, 16 or 32; reserved words other than 0; a row-block
+ *   (group or tile) context; a spin set (bhr_set_spin); a Disk V2 source.
+ * With a polarisation set, refused with BHR_ERR_STATE naming it and nothing launched: bhr_raymap_render_shutter,
+ *   bhr_raymap_render_view, and bhr_raymap_render from a map with supersample > 1.
+ * bhr_read_stokes: plane 0, 1, 2 = I, Q, U of the last frame of bhr_raymap_render, rows * W floats; bhr_read_stokes_cells: its
+ *   cell grid, dims[0] x dims[1] x 3 floats (I, Q, U means; at most ceil(rows / 8) ceil(W / 8) 3) and the grid's rows and columns
+ *   in dims; out NULL returns dims only.  BHR_ERR_STATE where no such frame has been rendered since the polarisation was set or
+ *   the map was built.  Both synchronise.
+ * bhr_stokes_resources: VGPRs, LDS bytes and scratch bytes of the Stokes kernel (diff: the one of a map with differentials). */
+typedef struct {
+    float b_r, b_phi, b_z;              /* the field in the gas frame: radial, along the orbit, along the disk normal */
+    float fraction;                     /* Pi_0: the degree of polarisation of light emitted across the field, 0 .. 1 */
+    int32_t cell;                       /* pixels per side of a cell of the grid: 8, 16 or 32 */
+    int32_t reserved[3];                /* 0 */
+} bhr_polarization;
+BHR_API int32_t bhr_set_polarization(bhr_ctx *ctx, const bhr_polarization *p);
+BHR_API int32_t bhr_read_stokes(bhr_ctx *ctx, int32_t plane, float *out);
+BHR_API int32_t bhr_read_stokes_cells(bhr_ctx *ctx, float *out, int32_t dims[2]);
+BHR_API int32_t bhr_stokes_resources(int32_t diff, int32_t out[3]);
 /* image_field/disk_layer_field/blur_field .to_numpy() and the final image,
  * for the context's rows: (row1-row0, width, 3) f32.  Synchronises. */
 BHR_API int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out);
