@@ -36,6 +36,7 @@ SYMBOLS = (
     "bhr_render_observer", "bhr_observer_resources", "bhr_render_delayed", "bhr_delayed_resources",
     "bhr_render_projected", "bhr_projected_resources",
     "bhr_raymap_build", "bhr_raymap_render", "bhr_raymap_render_view", "bhr_raymap_render_shutter", "bhr_raymap_read", "bhr_raymap_get_info", "bhr_raymap_free",
+    "bhr_kerr_raymap_build", "bhr_kerr_raymap_render", "bhr_kerr_raymap_render_view", "bhr_kerr_raymap_read", "bhr_kerr_raymap_info", "bhr_kerr_raymap_free",
     "bhr_set_stars", "bhr_get_stars_info", "bhr_stars_resources",
     "bhr_set_polarization", "bhr_read_stokes", "bhr_read_stokes_cells", "bhr_stokes_resources",
     "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_read_final_u16", "bhr_set_dither", "bhr_dither_matrix", "bhr_set_grade", "bhr_grade_frame", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
@@ -102,6 +103,13 @@ class RayMapInfo(C.Structure):
     _fields_ = [("built", C.c_int32), ("diff", C.c_int32), ("slots", C.c_int32), ("width", C.c_int32), ("rows", C.c_int32),
                 ("supersample", C.c_int32), ("crossings_stored", C.c_int64), ("overflow_pixels", C.c_int64),
                 ("device_bytes", C.c_int64), ("ray_steps", C.c_uint64), ("cam", Camera)]
+
+
+class KerrRayMapDesc(C.Structure):
+    """bhr_kerr_raymap_desc: the Kerr ray map of a context with the spin and the redshift mode it was built under."""
+    _fields_ = [("built", C.c_int32), ("slots", C.c_int32), ("width", C.c_int32), ("rows", C.c_int32), ("redshift", C.c_int32),
+                ("spin", C.c_float), ("crossings_stored", C.c_int64), ("overflow_pixels", C.c_int64), ("device_bytes", C.c_int64),
+                ("ray_steps", C.c_uint64), ("cam", Camera)]
 
 
 class Star(C.Structure):
@@ -187,6 +195,12 @@ def load() -> C.CDLL:
     lib.bhr_raymap_read.argtypes = [P, I32, C.c_void_p, C.c_int64]
     lib.bhr_raymap_get_info.argtypes = [P, C.POINTER(RayMapInfo)]
     lib.bhr_raymap_free.argtypes = [P]
+    lib.bhr_kerr_raymap_build.argtypes = [P, C.POINTER(Camera), C.c_uint32]
+    lib.bhr_kerr_raymap_render.argtypes = [P, C.c_float, C.c_uint32]
+    lib.bhr_kerr_raymap_render_view.argtypes = [P, C.POINTER(Camera), C.c_uint32]
+    lib.bhr_kerr_raymap_read.argtypes = [P, I32, C.c_void_p, C.c_int64]
+    lib.bhr_kerr_raymap_info.argtypes = [P, C.POINTER(KerrRayMapDesc)]
+    lib.bhr_kerr_raymap_free.argtypes = [P]
     lib.bhr_set_stars.argtypes = [P, C.c_void_p, I32, C.POINTER(StarParams)]
     lib.bhr_get_stars_info.argtypes = [P, C.POINTER(StarsInfo)]
     lib.bhr_stars_resources.argtypes = [I32, C.POINTER(C.c_int32)]

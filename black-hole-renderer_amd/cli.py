@@ -204,6 +204,15 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "--orbit they are the means of --orbit_map frames.  Not with --ray_map, "
                         "--orbit_map, --orbit together with --disk_tilt, --supersample > 1 (a supersampled map takes --map_supersample), "
                         "--disk_model v2 / v2_volume or --gpus > 1")
+    p.add_argument("--spin_map", action="store_true", default=argparse.SUPPRESS,
+                   help="--video with --spin or --redshift exact: march the spinning hole's view once with the Kerr march and shade "
+                        "every frame from that one Kerr ray map instead of marching it again.  A camera that stands still: the "
+                        "frames are byte-identical to the marched ones.  With --orbit: frame 0's view is marched and every frame is "
+                        "shaded from the map turned about z, the spin axis, to the frame's camera (an exact symmetry of a Kerr ray's "
+                        "path); frame 0 is the marched frame, a later frame the Kerr march of the symmetric rays.  --lens_flare, the "
+                        "grade, --video_codec mjpeg, --video_hdr, --bit_depth 16 and --dither work as ever.  Not with --shutter, "
+                        "--supersample > 1, --map_supersample > 1, --gpus > 1, --ray_map, --orbit_map, --shutter_map, the observer "
+                        "flags, --projection, --light_delay, --stars point or --polarization")
     p.add_argument("--map_supersample", type=int, default=1, choices=[1, 2, 4, 8], metavar="K",
                    help="--ray_map, --orbit_map or --shutter_map: the map's own supersampling factor, 1, 2, 4 or 8 (default 1).  The "
                         "one march of the video marches K x K rays per pixel and keeps their records; every frame shades all of them "
@@ -244,6 +253,32 @@ def parse_args(argv=None) -> argparse.Namespace:
     args.fov = 90 if args.fov is None else args.fov
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    if hasattr(args, "spin_map"):     # (the namespace of a line without the flag is what it was: no key)
+        # the Kerr ray map of a video (drivers.check_spin_map has the same refusals): ahead of a spin's own, so that each names --spin_map
+        if args.spin == 0 and args.redshift == "model":
+            p.error("--spin_map needs --spin or --redshift exact: it is the ray map of the Kerr march; a hole that does not spin takes "
+                    "--ray_map or --orbit_map")
+        if not args.video:
+            p.error("--spin_map needs --video: it is the ray map of a video")
+        if args.shutter > 0:
+            p.error("--spin_map does not combine with --shutter: shutter frames are marched")
+        if args.supersample != 1:
+            p.error("--spin_map does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
+        if args.map_supersample != 1:
+            p.error("--spin_map does not combine with --map_supersample other than 1: a Kerr ray map has no supersampled form")
+        if args.gpus != 1:
+            p.error("--spin_map does not combine with --gpus other than 1: a ray map lives on one GPU")
+        for flag, on in (("--ray_map", args.ray_map), ("--orbit_map", args.orbit_map), ("--shutter_map", args.shutter_map)):
+            if on:
+                p.error(f"--spin_map does not combine with {flag}: that is a map of Schwarzschild rays")
+        for flag, on in (("--observer", args.observer is not None), ("--observer_velocity", args.observer_velocity is not None),
+                         ("--observer_sky", args.observer_sky is not None), ("--infall_to", args.infall_to is not None),
+                         ("--projection", args.projection != "perspective" or args.projection_fov is not None),
+                         ("--light_delay", hasattr(args, "light_delay")), ("--stars point", args.stars == "point"),
+                         ("--polarization", any(hasattr(args, n) for n in ("polarization", "polarization_fraction", "polarization_cell",
+                                                                           "stokes_output", "polarization_ticks")))):
+            if on:
+                p.error(f"--spin_map does not combine with {flag}: it is a Schwarzschild march's or the Schwarzschild ray map's")
     if args.spin != 0 or args.redshift == "exact":
         from .kerr import SPIN_MAX
         # the Kerr march: asked for by a spin, or by the exact redshift at spin 0
@@ -738,7 +773,8 @@ def main(argv=None) -> int:
                              shutter_map=args.shutter_map, map_supersample=args.map_supersample, video_hdr=args.video_hdr,
                              hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure, **stars_kw,
                              **(dict(observer=args.observer, observer_velocity=args.observer_velocity, observer_sky=sky,
-                                     infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw, **pol_kw)
+                                     infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw, **pol_kw,
+                             **({"spin_map": True} if hasattr(args, "spin_map") else {}))
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent

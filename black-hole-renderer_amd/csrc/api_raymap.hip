@@ -13,26 +13,15 @@
 
 namespace {
 
-void free_planes(bhr_raymap *rm) {
-    BhrRayMapArgs &a = rm->a;
-    void *bufs[] = {a.steps, a.status, a.dir, a.crossings, a.hits, a.over_count, a.over_list, a.stats};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    memset(&a, 0, sizeof(a));
-    rm->built = 0;
-    rm->alloc_slots = rm->alloc_comps = rm->alloc_ss = 0;
-    rm->over_cap = 0;
-    rm->device_bytes = 0;
-}
-
+// one plane of a map object
 template <typename T>
-int32_t plane_alloc(bhr_raymap *rm, T **p, size_t count) {
+int32_t plane_alloc(bhr_raymap *rm, const char *who, T **p, size_t count) {
     *p = nullptr;
     const hipError_t e = hipMalloc((void **)p, count * sizeof(T));
     if (e != hipSuccess) {
         *p = nullptr;
         (void)hipGetLastError();
-        return bhr_fail(BHR_ERR_NOMEM, "bhr_raymap_build: hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
+        return bhr_fail(BHR_ERR_NOMEM, "%s: hipMalloc(%zu bytes) failed: %s", who, count * sizeof(T), hipGetErrorString(e));
     }
     rm->device_bytes += (int64_t)(count * sizeof(T));
     return BHR_OK;
@@ -64,11 +53,14 @@ int32_t check_context(const bhr_ctx *ctx, const char *who, int32_t code) {
     return BHR_OK;
 }
 
-// Shared by bhr_raymap_render_view and bhr_raymap_render_shutter, in binary64: is `cam` the build camera `b` turned rigidly
+}  // namespace
+
+// Shared by bhr_raymap_render_view, bhr_raymap_render_shutter and the Kerr ray map's view frames (api_kerr_raymap.hip), in
+// binary64: is `cam` the build camera `b` turned rigidly
 // about z -- same height, pitch and escape radius, same distance from the axis, and right / up / forward the build's turned by
 // the angle between the two positions in the xy plane?  On the axis build_camera takes a fallback basis that does not turn with
 // the position: refused.  Gives the turn's cosine and sine, rounded once.
-int32_t turn_of_build(const bhr_camera &b, const bhr_camera *cam, const char *who, float *rot_c, float *rot_s) {
+int32_t bhr_raymap_turn_of_build(const bhr_camera &b, const bhr_camera *cam, const char *who, float *rot_c, float *rot_s) {
     if (!(cam->pos[2] == b.pos[2] && cam->pixel_width == b.pixel_width && cam->pixel_height == b.pixel_height && cam->r_escape == b.r_escape))
         return bhr_fail(BHR_ERR_INVALID, "%s: the camera's height, pixel pitch or escape radius (%g, %g x %g, %g) is not the build's (%g, %g x %g, %g)", who,
                         (double)cam->pos[2], (double)cam->pixel_width, (double)cam->pixel_height, (double)cam->r_escape, (double)b.pos[2],
@@ -96,6 +88,8 @@ int32_t turn_of_build(const bhr_camera &b, const bhr_camera *cam, const char *wh
     return BHR_OK;
 }
 
+namespace {
+
 // point stars (bhr_set_stars): a supersampled map's shade kernels have no STARS variant
 int32_t check_stars(const bhr_ctx *ctx, const char *who) {
     if (bhr_have_stars(ctx) && ctx->raymap->ss > 1)
@@ -112,9 +106,46 @@ int32_t check_polar(const bhr_ctx *ctx, const char *who, const char *what) {
 
 }  // namespace
 
+void bhr_raymap_free_planes(bhr_raymap *rm) {
+    BhrRayMapArgs &a = rm->a;
+    void *bufs[] = {a.steps, a.status, a.dir, a.crossings, a.hits, a.over_count, a.over_list, a.stats};
+    for (void *b : bufs)
+        if (b) (void)hipFree(b);
+    memset(&a, 0, sizeof(a));
+    rm->built = 0;
+    rm->alloc_slots = rm->alloc_comps = rm->alloc_ss = 0;
+    rm->over_cap = 0;
+    rm->device_bytes = 0;
+}
+
+int32_t bhr_raymap_alloc_planes(bhr_raymap *rm, const char *who, int32_t K, int32_t comps, size_t plane, int32_t ss) {
+    BhrRayMapArgs &a = rm->a;
+    // the fix kernel's grid is sized in blocks of 256 entries of the list's capacity; a supersampled map lists whole k x k
+    // groups, k^2-aligned (k^2 divides 256)
+    const size_t over_cap = (plane + 255) / 256 * 256;
+    if (over_cap % 256 != 0 || over_cap % (size_t)(ss * ss) != 0 || over_cap > (size_t)INT32_MAX)
+        return bhr_fail(BHR_ERR_STATE, "%s: an overflow list of %zu entries for factor %d", who, over_cap, ss);
+    int32_t rc = BHR_OK;
+    if ((rc = plane_alloc(rm, who, &a.steps, plane)) || (rc = plane_alloc(rm, who, &a.status, plane)) || (rc = plane_alloc(rm, who, &a.dir, 3 * plane)) ||
+        (rc = plane_alloc(rm, who, &a.crossings, plane)) || (rc = plane_alloc(rm, who, &a.hits, (size_t)K * comps * plane)) ||
+        (rc = plane_alloc(rm, who, &a.over_count, 16)) || (rc = plane_alloc(rm, who, &a.over_list, over_cap)) ||
+        (rc = plane_alloc(rm, who, &a.stats, 8 + BHR_STEP_CELL))) {
+        bhr_raymap_free_planes(rm);    // a later build starts clean; the context is as it was
+        return rc;
+    }
+    a.slots = K;
+    a.comps = comps;
+    a.plane = (int64_t)plane;
+    rm->alloc_slots = K;
+    rm->alloc_comps = comps;
+    rm->alloc_ss = ss;
+    rm->over_cap = (int32_t)over_cap;
+    return BHR_OK;
+}
+
 void bhr_raymap_release(bhr_ctx *ctx) {
     if (!ctx->raymap) return;
-    free_planes(ctx->raymap);
+    bhr_raymap_free_planes(ctx->raymap);
     delete ctx->raymap;
     ctx->raymap = nullptr;
     bhr_stars_invalidate(ctx);
@@ -137,7 +168,7 @@ int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
 }
 
 // bhr_raymap_render_view's refusals, before anything is launched: the disk is not tilted, and `cam` is the build camera turned
-// rigidly about z (turn_of_build).
+// rigidly about z (bhr_raymap_turn_of_build).
 int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, float *rot_c, float *rot_s) {
     const char *who = "bhr_raymap_render_view";
     if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
@@ -152,7 +183,7 @@ int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32
                         (double)ctx->cfg.disk_tilt_deg);
     if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no ray map has been built (bhr_raymap_build)", who);
     BHR_TRY(check_context(ctx, who, BHR_ERR_STATE));
-    BHR_TRY(turn_of_build(ctx->raymap->cam, cam, who, rot_c, rot_s));
+    BHR_TRY(bhr_raymap_turn_of_build(ctx->raymap->cam, cam, who, rot_c, rot_s));
     BHR_TRY(check_stars(ctx, who));
     return check_polar(ctx, who, "the Stokes planes are the build view's; turned views have none");
 }
@@ -191,7 +222,7 @@ int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, in
         if (ctx->cfg.disk_tilt_deg != 0.0f)
             return bhr_fail(BHR_ERR_INVALID, "%s: the disk is tilted by %g degrees and the camera is not the build's; a turn about z is a symmetry of an untilted disk only",
                             sample, (double)ctx->cfg.disk_tilt_deg);
-        BHR_TRY(turn_of_build(b, &c, sample, &o.c, &o.s));
+        BHR_TRY(bhr_raymap_turn_of_build(b, &c, sample, &o.c, &o.s));
         *turned = *turned || !(o.c == 1.0f && o.s == 0.0f);
     }
     smp->n = n;
@@ -234,31 +265,9 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     bhr_polar_invalidate(ctx);         // ... and so do the Stokes planes of its last frame
     if (rm->a.hits && (rm->alloc_slots != K || rm->alloc_comps != comps || rm->alloc_ss != ss)) {
         BHR_TRY(drain(ctx));
-        free_planes(rm);
+        bhr_raymap_free_planes(rm);
     }
-    if (!rm->a.hits) {
-        BhrRayMapArgs &a = rm->a;
-        // the fix kernel's grid is sized in blocks of 256 entries of the list's capacity; a supersampled map lists whole k x k
-        // groups, k^2-aligned (k^2 divides 256)
-        const size_t over_cap = (plane + 255) / 256 * 256;
-        if (over_cap % 256 != 0 || over_cap % (size_t)(ss * ss) != 0 || over_cap > (size_t)INT32_MAX)
-            return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: an overflow list of %zu entries for factor %d", over_cap, ss);
-        int32_t rc = BHR_OK;
-        if ((rc = plane_alloc(rm, &a.steps, plane)) || (rc = plane_alloc(rm, &a.status, plane)) || (rc = plane_alloc(rm, &a.dir, 3 * plane)) ||
-            (rc = plane_alloc(rm, &a.crossings, plane)) || (rc = plane_alloc(rm, &a.hits, (size_t)K * comps * plane)) ||
-            (rc = plane_alloc(rm, &a.over_count, 16)) || (rc = plane_alloc(rm, &a.over_list, over_cap)) ||
-            (rc = plane_alloc(rm, &a.stats, 8 + BHR_STEP_CELL))) {
-            free_planes(rm);           // a later build starts clean; the context is as it was
-            return rc;
-        }
-        a.slots = K;
-        a.comps = comps;
-        a.plane = (int64_t)plane;
-        rm->alloc_slots = K;
-        rm->alloc_comps = comps;
-        rm->alloc_ss = ss;
-        rm->over_cap = (int32_t)over_cap;
-    }
+    if (!rm->a.hits) BHR_TRY(bhr_raymap_alloc_planes(rm, "bhr_raymap_build", K, comps, plane, ss));
     const BhrRayMapArgs &a = rm->a;
     // records beyond a pixel's crossings stay zero
     BHR_HIP(hipMemsetAsync(a.hits, 0, (size_t)K * comps * plane * sizeof(float), ctx->stream));

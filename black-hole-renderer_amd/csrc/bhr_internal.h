@@ -204,6 +204,11 @@ enum bhr_march_kernel {
     BHR_MK_RAYMAP_SHADE_STARS,      // raymap_shade_kernel<diff, false, true>                                     raymap
     BHR_MK_RAYMAP_SHADE_STARS_ROT,  // raymap_shade_kernel<diff, true, true>                                      raymap
     // (ss: BUILD, SHADE and SHADE_ROT have twins for a supersampled map, raymap_build_kernel<DIFF, true> / raymap_shade_ss_kernel; the shutter kernels have none)
+    // the Kerr ray map (march_kerr_raymap.hip), each with the model and with the exact redshift; no differentials, no supersampled twins
+    BHR_MK_KERR_RAYMAP_BUILD,      // kerr_raymap_build_kernel<RS>: marches a view with the Kerr Ray and records what it finds    kerr_raymap
+    BHR_MK_KERR_RAYMAP_SHADE,      // kerr_raymap_shade_kernel<RS, false>: a frame from the records and the current scene          kerr_raymap
+    BHR_MK_KERR_RAYMAP_SHADE_ROT,  // kerr_raymap_shade_kernel<RS, true>: the same with the records turned about z                 kerr_raymap
+    BHR_MK_KERR_RAYMAP_FIX,        // kerr_raymap_fix_kernel<RS>: the map's overflow list, marched with the Kerr Ray               kerr_raymap
 };
 
 // The row of a march variant (settings.hip: bhr_variant_row_of): its kernels, and the terms and words of its refusals.
@@ -552,6 +557,12 @@ struct bhr_ctx {
     float kerr_spin;
     int32_t kerr_redshift;     // bhr_set_redshift: BHR_REDSHIFT_MODEL (0) or BHR_REDSHIFT_EXACT, which needs kerr_on
 
+    // the Kerr ray map (api_kerr_raymap.hip): a map object of its own -- nothing of `raymap` above is shared, stars and polarisation
+    // never see it -- with the spin and the redshift mode it was built under, which a frame from it needs the context to have still
+    bhr_raymap *kerr_raymap;   // null until the first bhr_kerr_raymap_build
+    float kerr_map_spin;
+    int32_t kerr_map_redshift;
+
     // point stars (api_stars.hip)
     bhr_stars *stars;          // null until a catalogue is set (bhr_set_stars)
 
@@ -729,6 +740,13 @@ const void *bhr_march_kernel_observer(bhr_march_kernel k, int32_t diff, int32_t 
 const void *bhr_march_kernel_projected(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_projected.hip -> march_projected.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_delay(bhr_march_kernel k, int32_t diff, int32_t ss);      // march_delay.hip -> march_delay.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
+const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact);           // march_kerr_raymap.hip -> march_kerr_raymap.o (exact: the exact redshift's)
+// the Kerr ray map's launches (march_kerr_raymap.hip), under the Kerr block of variant v (BHR_MV_KERR or BHR_MV_KERR_EXACT).
+// build: on ctx->stream, marches `cam` with the Kerr Ray and fills the map.  shade: call.req.variant's kernel over the map into
+// the active slot's layers, turned by (rot_c, rot_s); opens the frame's march bracket -- the overflow launch behind it
+// (bhr_launch_march with the same call and a repair == 2 part over the map's list: kerr_raymap_fix_kernel) closes it
+int32_t bhr_launch_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, bhr_march_variant v, const BhrRayMapArgs &m);
+int32_t bhr_launch_kerr_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, float rot_c, float rot_s);
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
 
 // ---- hybrid.hip -------------------------------------------------------------------------------------------------------------------------
@@ -804,6 +822,17 @@ int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32
 // ... and of bhr_raymap_render_shutter, which fills smp (t, c, s per sample, n, 1 / n) and tells whether any sample is turned
 int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned);
 void bhr_raymap_release(bhr_ctx *ctx);
+// a map object's device planes, for both maps of a context: K slots of `comps` floats over `plane` pixels with an overflow list
+// for factor ss (who: the build a refusal names; a failed allocation leaves the object empty), and their release
+int32_t bhr_raymap_alloc_planes(bhr_raymap *rm, const char *who, int32_t K, int32_t comps, size_t plane, int32_t ss);
+void bhr_raymap_free_planes(bhr_raymap *rm);
+// is `cam` the build camera `b` turned rigidly about z?  Gives the turn's cosine and sine (binary64, rounded once)
+int32_t bhr_raymap_turn_of_build(const bhr_camera &b, const bhr_camera *cam, const char *who, float *rot_c, float *rot_s);
+
+// ---- api_kerr_raymap.hip ------------------------------------------------------------------------------------------------------------------
+// the refusals of bhr_kerr_raymap_render and bhr_kerr_raymap_render_view (nothing launched); cam null: the build camera, no turn
+int32_t bhr_kerr_raymap_check_render(bhr_ctx *ctx, const char *who, const bhr_camera *cam, float t_offset, uint32_t flags, float *rot_c, float *rot_s);
+void bhr_kerr_raymap_release(bhr_ctx *ctx);
 
 // ---- api_stars.hip ----------------------------------------------------------------------------------------------------------------------
 inline bool bhr_have_stars(const bhr_ctx *ctx) { return ctx->stars && ctx->stars->n > 0; }

@@ -187,6 +187,7 @@ void bhr_destroy(bhr_ctx *ctx) {
     bhr_shutter_free(ctx);
     bhr_grade_free(ctx);
     bhr_raymap_release(ctx);
+    bhr_kerr_raymap_release(ctx);
     bhr_stars_release(ctx);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);

@@ -42,6 +42,8 @@
 // Ray<false, 0> of its own and a march_<v>.hip -> march_<v>.o with the tile schedule's plain and supersampled kernel:
 //   kerr       a spinning hole in Kerr-Schild coordinates, RK4 on (x, p), its own sampler and g-factor, model or exact
 //              (bhr_set_spin, bhr_set_redshift); the Schwarzschild Rays know nothing of it; -ffp-contract=on, no fast-math
+//              (and march_kerr_raymap.hip -> march_kerr_raymap.o over the same Ray: the Kerr ray map's build, shade and
+//              overflow kernels, with the Kerr object's flags; its table is bhr_march_kernel_kerr_raymap)
 //   observer   the strict Ray launched along the aberrated pixel direction of a moving camera, its Doppler factor in the
 //              disk's g and on the sky (bhr_render_observer); the strict flags, as the next two
 //   projected  the observer Ray launched along an equirectangular or fisheye pixel direction (bhr_render_projected)

@@ -1,0 +1,213 @@
+// march_kerr_raymap.hip -> march_kerr_raymap.o: the Kerr ray map's kernels (build, shade, shade turned about z, and the march of
+// the overflow list), each with the model redshift and with the exact one, and nothing else.  Built with exactly the flags of
+// march_kerr.o (csrc/Makefile says why): the kernels are made of the Kerr march's device functions -- Ray<false, RS>, Pending,
+// kerr_shade_hit, sample_skybox, store_pixel (ray_kerr.h, march_device.h) -- and under those flags a function gives the same
+// bits wherever it is inlined.
+//
+// A Kerr ray's path depends on the camera, the geometry of bhr_config and the spin, not on the skybox, the disk texture or
+// t_offset.  kerr_raymap_build_kernel marches a whole-frame view once with the Kerr Ray and, where the tile kernel shades a
+// parked crossing (flush_one), records it instead (Ray::record_one): per pixel up to `slots` Pending<false> records, front to
+// back, and a header -- executed steps, status, normalized escape direction, number of annulus crossings.  For the exact
+// redshift the three to_cam floats of a record are the photon's momentum (p_x, p_y, 0) at the hit, which is what its step
+// parks.  kerr_raymap_shade_kernel turns the records and the scene as it stands into the frame's BG and DISK values:
+// kerr_shade_hit on every record in order from the Shade that Ray::init leaves, then the march's own pixel values and store --
+// the frame march_kerr_kernel / march_kerr_exact_kernel leaves, bit for bit.  A pixel with more crossings than slots is on the
+// overflow list; the shade kernel leaves it alone and kerr_raymap_fix_kernel marches it in the same frame.
+//
+// kerr_raymap_shade_kernel<RS, true> shades the map seen from the build camera turned rigidly about the z axis
+// (bhr_kerr_raymap_render_view; an orbit frame).  The spin axis is z and the disk of a spinning hole is not tilted, so that turn
+// is a symmetry of everything a Kerr ray's path depends on: the rays of the turned view are the stored rays turned.  The kernel
+// turns the xy parts of hit point, to_cam (a direction or a momentum: a vector either way) and escape direction by
+// (c, s) = (m.rot_c, m.rot_s).  Such a frame is the Kerr march of the BUILD view's rays, not bit for bit the marched frame of
+// the turned view; the launcher takes <RS, false> for c = 1, s = 0.
+//
+// No differentials (the Kerr Ray has none) and no supersampled form.
+#include <type_traits>
+
+#include "ray_kerr.h"
+
+namespace {
+
+// the block of a redshift's kernels: the Kerr block, with the ISCO's numbers behind it for the exact one
+template <int RS>
+using KerrBlock = std::conditional_t<RS == KERR_EXACT, BhrKerrExactMarchArgs, BhrKerrMarchArgs>;
+
+// ---- the build ----------------------------------------------------------------------------------------------------------------
+// raymap_build_kernel<false, false>'s body (march_raymap.hip) over the Kerr Ray: one 8x8 tile per wave, tiles in the march's
+// launch order (longest rays first).
+template <int RS>
+__global__ __launch_bounds__(256) void kerr_raymap_build_kernel(KerrBlock<RS> a, BhrRayMapArgs m) {
+    const int slot = wave_slot();
+    if (slot >= a.n_list) return;    // wave-uniform: the lanes of a wave stay together down to the ballots
+    const int lane = threadIdx.x & 63;
+    const int tile = a.tile_order ? a.tile_order[slot] : slot;
+    const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
+    const int i = tx * 8 + (lane & 7);
+    const int j = ty * 8 + (lane >> 3);
+    const bool valid = tile < a.n_tiles && i < a.width && j < a.rows;
+
+    Ray<false, RS> ray;
+    ray.init(a, valid ? i : 0, valid ? j : 0);
+    if (!valid) ray.done = 4;
+    const size_t pix = valid ? (size_t)j * a.width + i : 0;
+    int cnt = 0, n_rec = 0;       // executed steps; crossings found so far (recorded while below m.slots)
+    // the tile body's march loop: a lane leaves when its ray terminates; when some lane has filled both its parking slots
+    // the wave records the older crossing of every lane that has one, and the second slot moves up
+    while (ray.done == 0) {
+        ray.step(a);
+        cnt += 1;
+        if (ray.full) {
+            ray.record_one(m, pix, n_rec);
+            ray.full = false;
+        }
+    }
+    ray.step_count = cnt;
+    if (cnt > 0) ray.settle(a);
+    else ray.done = 3;               // no step taken (max_iter <= 0, or no ray)
+    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
+    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
+
+    if (valid) {
+        const bool esc = ray.escaped(a);
+        m.steps[pix] = cnt;
+        m.status[pix] = esc ? 1 : (ray.done == 2 ? 0 : 2);
+        // the direction pixel_values hands sample_skybox
+        V3 dn = mk(0.0f, 0.0f, 0.0f);
+        if (esc) dn = normalized(ray.velocity(a));
+        m.dir[pix] = dn.x;
+        m.dir[(size_t)m.plane + pix] = dn.y;
+        m.dir[2 * (size_t)m.plane + pix] = dn.z;
+        m.crossings[pix] = n_rec;
+    }
+    // more crossings than slots: the pixel keeps its first m.slots records and goes on the overflow list (wave-aggregated
+    // append; every pixel is appended at most once and the list has room for all of them)
+    const bool over = valid && n_rec > m.slots;
+    const unsigned long long om = __ballot(over);
+    if (om) {
+        const int first = __ffsll((long long)om) - 1;
+        unsigned int base = 0;
+        if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(om));
+        base = __shfl(base, first, BHR_WAVE);
+        if (over) m.over_list[base + (unsigned int)__popcll(om & ((1ull << lane) - 1ull))] = (int32_t)pix;
+    }
+    const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
+    const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
+    if (lane == 0) {
+        atomicAdd(m.stats, stored);
+        atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
+    }
+}
+
+// ---- the shade ----------------------------------------------------------------------------------------------------------------
+// x' = c x - s y, y' = s x + c y: two products and a sum per component, as march_raymap.hip's turn_xy rounds them (this object
+// contracts within an expression; the turn is kept out of that)
+__device__ __forceinline__ void turn_xy(float c, float s, float &x, float &y) {
+#pragma clang fp contract(off)
+    const float xr = c * x - s * y, yr = s * x + c * y;
+    x = xr;
+    y = yr;
+}
+
+// render.py:3008-3018 as pixel_values has it, from the direction the build kernel stored already normalized
+// (march_raymap.hip: raymap_pixel_values, without the star plane)
+__device__ __forceinline__ void kerr_raymap_pixel_values(const BhrMarchArgs &a, bool escaped, V3 dir, const Shade &sh, float bk[3], float dk[3]) {
+    V3 bg = mk(0, 0, 0);
+    if (escaped) bg = sample_skybox(a.sc, dir);
+    float k = 1.0f - sh.alpha_total;
+    bk[0] = __fmul_rn(bg.x, k);
+    bk[1] = __fmul_rn(bg.y, k);
+    bk[2] = __fmul_rn(bg.z, k);
+    dk[0] = fminf(fmaxf(sh.accum.x, 0.0f), 1.0f);
+    dk[1] = fminf(fmaxf(sh.accum.y, 0.0f), 1.0f);
+    dk[2] = fminf(fmaxf(sh.accum.z, 0.0f), 1.0f);
+}
+
+// One lane per pixel, an 8x8 tile per wave as in the march (texture locality, and store_pixel's packed layout is per tile);
+// tiles in row-major order: every lane does about the same work.
+// ROT: the records are turned about z by (m.rot_c, m.rot_s) before they are shaded (the head of this file).
+template <int RS, bool ROT>
+__global__ __launch_bounds__(256) void kerr_raymap_shade_kernel(KerrBlock<RS> a, BhrRayMapArgs m) {
+    const int tile = wave_slot();
+    if (tile >= a.n_tiles) return;
+    const int lane = threadIdx.x & 63;
+    const int i = (tile % a.tiles_x) * 8 + (lane & 7);
+    const int j = (tile / a.tiles_x) * 8 + (lane >> 3);
+    if (!(i < a.width && j < a.rows)) return;
+    const size_t pix = (size_t)j * a.width + i;
+    const int count = m.crossings[pix];
+    if (count > m.slots) return;     // on the overflow list: the fix kernel marches and stores it
+    // the turn's cosine and sine stay scalar operands (march_raymap.hip: raymap_shade_kernel says why)
+    const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;
+    Shade sh;                        // as Ray::init leaves it
+    sh.accum = mk(0, 0, 0);
+    sh.alpha_total = 0.0f;
+    sh.unsure = 0;
+    const size_t p = (size_t)m.plane;
+    for (int c = 0; c < count; ++c) {
+        const float *q = m.hits + (size_t)c * m.comps * p + pix;
+        float hx = q[0], hy = q[p];
+        V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
+        if (ROT) {
+            turn_xy(rc, rs, hx, hy);
+            turn_xy(rc, rs, to_cam.x, to_cam.y);
+        }
+        kerr_shade_hit<RS>(a, sh, hx, hy, to_cam);
+    }
+    const bool esc = m.status[pix] == 1;
+    V3 dir = mk(m.dir[pix], m.dir[p + pix], m.dir[2 * p + pix]);
+    if (ROT) turn_xy(rc, rs, dir.x, dir.y);
+    float bk[3], dk[3];
+    kerr_raymap_pixel_values(a, esc, dir, sh, bk, dk);
+    store_pixel(a, i, j, a.width, bk, dk);
+}
+
+// ---- the overflow list --------------------------------------------------------------------------------------------------------
+// march_fix_kernel's body (march_strict_ilp.hip) over the Kerr Ray: the pixels of the map's overflow list, 64 per wave whatever
+// tile they came from, marched from the frame's own camera and stored through the march's own values and store -- the marched
+// Kerr frame's pixels.  Launched with a grid for the list's capacity; waves beyond the count the device holds exit at once.
+template <int RS>
+__global__ __launch_bounds__(256) void kerr_raymap_fix_kernel(KerrBlock<RS> a) {
+    const int wave = wave_slot();
+    unsigned int n = *a.fix_count;
+    if (n > (unsigned int)a.fix_cap) n = (unsigned int)a.fix_cap;
+    if ((unsigned int)wave * 64u >= n) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned int k = (unsigned int)wave * 64u + (unsigned int)lane;
+    const bool valid = k < n;
+    const int pix = valid ? a.fix_list[k] : 0;
+    Ray<false, RS> ray;
+    ray.init(a, pix % a.width, pix / a.width);
+    if (!valid) ray.done = 4;
+    int cnt = 0;
+    while (ray.done == 0) {
+        ray.step(a);
+        cnt += 1;
+        if (ray.full) { ray.flush_one(a); ray.full = false; }
+    }
+    ray.step_count = cnt;
+    if (cnt > 0) ray.settle(a);
+    else ray.done = 3;
+    if (__ballot(ray.n_pend > 0)) ray.flush_one(a);
+    if (__ballot(ray.n_pend > 0)) ray.flush_one(a);
+    if (valid) {
+        float bk[3], dk[3];
+        ray.values(a, bk, dk);
+        store_pixel(a, pix % a.width, pix / a.width, a.width, bk, dk);
+    }
+    const unsigned long long tot = wave_sum_u32((unsigned int)ray.step_count);
+    if (lane == 0) atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
+}
+
+}  // namespace
+
+// ---- the kernels of this object, by the launcher's names (march_launch.hip); null: not in this object ----------
+// exact: the kernels of the exact redshift (they take BhrKerrExactMarchArgs)
+const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact) {
+    switch (k) {
+    case BHR_MK_KERR_RAYMAP_BUILD: return exact ? (const void *)kerr_raymap_build_kernel<KERR_EXACT> : (const void *)kerr_raymap_build_kernel<0>;
+    case BHR_MK_KERR_RAYMAP_SHADE: return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, false> : (const void *)kerr_raymap_shade_kernel<0, false>;
+    case BHR_MK_KERR_RAYMAP_SHADE_ROT: return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, true> : (const void *)kerr_raymap_shade_kernel<0, true>;
+    case BHR_MK_KERR_RAYMAP_FIX: return exact ? (const void *)kerr_raymap_fix_kernel<KERR_EXACT> : (const void *)kerr_raymap_fix_kernel<0>;
+    default: return nullptr;
+    }
+}

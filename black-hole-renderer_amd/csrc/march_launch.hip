@@ -1,7 +1,7 @@
 // march_launch.hip -- the host half of the ray march: every march launch goes through bhr_launch_march.
 //
 // The march's device code is one object per source (the layout: march_device.h): march.hip fast, march_strict.hip,
-// march_strict_ilp.hip with the ILP-first scheduler, march_raymap.hip, and one per march variant (bhr_variant_row_of: its row
+// march_strict_ilp.hip with the ILP-first scheduler, march_raymap.hip, march_kerr_raymap.hip, and one per march variant (bhr_variant_row_of: its row
 // names the object).  Each object hands its kernels over through a table (bhr_march_kernel_fast / _strict / _strict_ilp /
 // _raymap, and the variant rows').  This file resolves the arithmetic, builds the kernel arguments -- a variant's block with
 // its own words behind the march's (variant_args) -- keeps the tile order, the ray-step counters and the timing events, and
@@ -69,6 +69,7 @@ float fast_sqrt(float s) {
 //
 //   arithmetic     request                                              kernel (object)
 //   any            a march variant v (call.req.variant), whole block    its row's kernel: kernels(name, 0, ss) of bhr_variant_row_of(v)
+//   any            a Kerr variant, fix list (part->repair == 2)         kerr_raymap_fix_kernel<RS> (kerr_raymap)
 //   any            hybrid part with n <= 0, not the fix list            none
 //   strict         hybrid fix list (part->repair == 2)                  march_fix_kernel<diff> (strict_ilp)
 //   fast / strict  Disk V2 volume source                                march_tile_kernel<false, 2> (own object)
@@ -104,6 +105,12 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
     // a variant: one arithmetic, one schedule, no lists (what it has no form for was refused before anything was launched)
     if (v != BHR_MV_NONE) {
         const bhr_variant_row &r = bhr_variant_row_of(v);
+        // the overflow list of a frame from the Kerr ray map (part->repair == 2 under a Kerr variant): kerr_raymap_fix_kernel
+        if (part && part->repair == 2 && r.kerr) {
+            k.fn = bhr_march_kernel_kerr_raymap(BHR_MK_KERR_RAYMAP_FIX, v == BHR_MV_KERR_EXACT);
+            k.grid = dim3((a.fix_cap / 64 + 3) / 4);
+            return k;
+        }
         if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = r.kernels(r.name, diff, ss);
         return k;
     }
@@ -571,6 +578,47 @@ int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const 
     mm.rot_s = rot_s;
     mm.stars = stars;
     void *args[] = {&a, &mm};
+    (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
+    BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}
+
+// ---- the Kerr ray map (march_kerr_raymap.hip; api_kerr_raymap.hip owns the map) ---------------------------------------------------
+// The kernels take the Kerr block of the redshift (variant_args) and the map as a second argument; one ray per pixel, no
+// differentials: 5 components per record.
+int32_t bhr_launch_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, bhr_march_variant v, const BhrRayMapArgs &m) {
+    const hipStream_t stream = ctx->stream;
+    const bhr_march_call call = {cam, BHR_FORCE_STRICT | BHR_SKIP_DIFFERENTIALS, stream, /* slot */ -1, false, false, 1, false, {v}};
+    BhrMarchArgs a;
+    march_args(ctx, call, nullptr, 1, false, a);
+    if ((int64_t)a.width * a.rows != m.plane || m.comps != 5)
+        return bhr_fail(BHR_ERR_STATE, "bhr_kerr_raymap_build: the map has %lld pixels of %d components, the frame %lld of 5", (long long)m.plane, m.comps, (long long)a.width * a.rows);
+    BHR_TRY(ensure_tile_order(ctx, 1, a.tiles_x, a.n_tiles));
+    a.tile_order = ctx->d_tile_order;
+    a.ray_steps = m.stats + 8;                                 // a counter cell of the map's own, behind its totals
+    const void *fn = bhr_march_kernel_kerr_raymap(BHR_MK_KERR_RAYMAP_BUILD, v == BHR_MV_KERR_EXACT);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_kerr_raymap_build: no build kernel in this library");
+    VariantArgs va;
+    BhrRayMapArgs mm = m;
+    void *args[] = {variant_args(ctx, call.req, a, va), &mm};
+    (void)hipLaunchKernel(fn, dim3((a.n_list + 3) / 4), dim3(256), args, 0, stream);
+    BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}
+
+int32_t bhr_launch_kerr_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, float rot_c, float rot_s) {
+    BhrMarchArgs a;
+    BHR_TRY(raymap_shade_args(ctx, call, m, false, 1, "bhr_kerr_raymap_render", a));
+    const bool turned = !(rot_c == 1.0f && rot_s == 0.0f);
+    const void *fn = bhr_march_kernel_kerr_raymap(turned ? BHR_MK_KERR_RAYMAP_SHADE_ROT : BHR_MK_KERR_RAYMAP_SHADE, call.req.variant == BHR_MV_KERR_EXACT);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_kerr_raymap_render: no shade kernel in this library");
+    // the frame's march bracket opens here; the overflow launch behind this one (bhr_launch_march, last part) closes it
+    BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
+    VariantArgs va;
+    BhrRayMapArgs mm = m;
+    mm.rot_c = rot_c;
+    mm.rot_s = rot_s;
+    void *args[] = {variant_args(ctx, call.req, a, va), &mm};
     (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
     BHR_HIP(hipGetLastError());
     return BHR_OK;

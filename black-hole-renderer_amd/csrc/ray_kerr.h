@@ -359,6 +359,24 @@ struct Ray {
             kerr_shade_hit<SRC>(a, sh, h.hit_x, h.hit_y, h.to_cam);
         }
     }
+    // The Kerr ray map's build (march_kerr_raymap.hip): where flush_one shades the oldest parked crossing, this stores it as the
+    // map's record n_rec of pixel `at`, front to back, and counts on past the slots.  For KERR_EXACT the three to_cam floats are
+    // the photon's momentum (p_x, p_y, 0) the step parked.
+    __device__ __forceinline__ void record_one(const BhrRayMapArgs &m, size_t at, int &n_rec) {
+        if (n_pend > 0) {
+            const Pending<false> h = park_pop<false>(n_pend);
+            if (n_rec < m.slots) {
+                const size_t p = (size_t)m.plane;
+                float *q = m.hits + (size_t)n_rec * m.comps * p + at;
+                q[0] = h.hit_x;
+                q[p] = h.hit_y;
+                q[2 * p] = h.to_cam.x;
+                q[3 * p] = h.to_cam.y;
+                q[4 * p] = h.to_cam.z;
+            }
+            n_rec += 1;
+        }
+    }
     // the escape direction is the direction of dx/dl at the last state
     __device__ __forceinline__ V3 velocity(const BhrMarchArgs &a) const {
         V3 v, d;

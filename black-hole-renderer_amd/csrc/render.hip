@@ -153,6 +153,24 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int 
     return post_on_slot(ctx, flags, k, ring);
 }
 
+// A frame from the context's Kerr ray map on slot k (bhr_kerr_raymap_render, bhr_kerr_raymap_render_view): the Kerr shade kernel
+// over the stored records, turned by (rot_c, rot_s), then kerr_raymap_fix_kernel over the map's overflow list as the last part of
+// a partial march under the context's Kerr variant -- it marches those pixels from `cam`, the frame's own camera -- inside one
+// march bracket, then the post-pass as behind a marched Kerr frame.  The ring cell counts the re-march only.
+int32_t kerr_raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, float rot_c, float rot_s) {
+    bhr_frame_slot &f = ctx->slots[k];
+    const bhr_raymap &rm = *ctx->kerr_raymap;
+    BHR_TRY(bhr_frame_begin(ctx, flags));
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ false, /* ss */ 1, /* keep_start */ false,
+                                 {bhr_variant_of(ctx)}};
+    *fm = {1, 1, false};
+    BHR_TRY(bhr_launch_kerr_raymap_shade(ctx, call, rm.a, rot_c, rot_s));
+    const bhr_march_part part = raymap_fix_part(rm);
+    BHR_TRY(bhr_launch_march(ctx, call, &part));
+    f.march_done = ctx->ring_ev[ring * 3 + 1];
+    return post_on_slot(ctx, flags, k, ring);
+}
+
 // A shutter frame from the context's ray map on slot k (bhr_raymap_render_shutter): the mean of n frames from the map, then the
 // post-pass on the resolved layers as behind shutter_on_slot's last accumulation.  Two routes to the same bits.  Fused (a map
 // without overflow pixels, option "raymap_shutter_fused" not 0, n > 1): one launch shades every pixel under all n samples and
@@ -336,6 +354,28 @@ int32_t bhr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fla
     if (bhr_have_stars(ctx) && rot_c == 1.0f && rot_s == 0.0f) BHR_TRY(bhr_stars_ensure_plane(ctx));   // angle 0: bhr_raymap_render's plane
     const uint32_t fl = raymap_frame_flags(ctx, flags);
     return frame_on_next_slot(ctx, fl, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, &view, fl, k, ring, fm, rot_c, rot_s); });
+}
+
+// A frame from the Kerr ray map (include/bhr.h): the build camera with the caller's t_offset, under the flags as they are -- the
+// post-pass is the one behind a marched Kerr frame of this context.  Like bhr_raymap_render it neither triggers nor counts
+// towards the calibration of slot 1's stream.
+int32_t bhr_kerr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
+    float rot_c = 1.0f, rot_s = 0.0f;
+    BHR_TRY(bhr_kerr_raymap_check_render(ctx, "bhr_kerr_raymap_render", nullptr, t_offset, flags, &rot_c, &rot_s));
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    bhr_camera cam = ctx->kerr_raymap->cam;
+    cam.t_offset = t_offset;
+    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return kerr_raymap_on_slot(ctx, &cam, flags, k, ring, fm, 1.0f, 0.0f); });
+}
+
+// ... seen from the build camera turned about z (include/bhr.h): bhr_kerr_raymap_render's frame in every other respect.
+int32_t bhr_kerr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
+    float rot_c = 1.0f, rot_s = 0.0f;
+    if (!cam) return bhr_fail(BHR_ERR_INVALID, "bhr_kerr_raymap_render_view: null argument");
+    BHR_TRY(bhr_kerr_raymap_check_render(ctx, "bhr_kerr_raymap_render_view", cam, cam->t_offset, flags, &rot_c, &rot_s));
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    const bhr_camera view = *cam;
+    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return kerr_raymap_on_slot(ctx, &view, flags, k, ring, fm, rot_c, rot_s); });
 }
 
 // Motion blur from the ray map (include/bhr.h): one frame as the mean of n frames from the map, no march.  A frame like

@@ -579,6 +579,41 @@ def check_shutter_map(shutter_map: bool, shutter: float = 0.5, orbit: bool = Fal
         raise ValueError("a ray map lives on one GPU: --shutter_map does not combine with --gpus > 1 or several ranks")
 
 
+def check_spin_map(spin_map: bool, spin: float = 0.0, redshift: str = "model", video: bool = True, shutter: float = 0.0, supersample=1,
+                   map_supersample=1, gpus: int = 1, world: int = 1, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False,
+                   observer: bool = False, projection: bool = False, light_delay: bool = False, stars: bool = False,
+                   polarization: bool = False) -> None:
+    """--spin_map is the Kerr ray map of a video (render_video): one march of a spinning hole's view, every frame shaded from it
+    -- under --orbit turned about the spin axis to the frame's camera.  It needs a spin or the exact redshift (the Kerr march),
+    a video, an instantaneous exposure, one ray per pixel and one GPU, and none of the Schwarzschild maps or of what a spin
+    refuses anyway.  Raises ValueError naming --spin_map and the other flag, before any device work."""
+    if not spin_map:
+        return
+    if spin == 0 and redshift == "model":
+        raise ValueError("--spin_map needs --spin or --redshift exact: it is the ray map of the Kerr march; a hole that does not spin "
+                         "takes --ray_map or --orbit_map")
+    if not video:
+        raise ValueError("--spin_map needs --video: it is the ray map of a video")
+    if shutter > 0:
+        raise ValueError("shutter frames are marched: --spin_map does not combine with --shutter")
+    if supersample != 1:
+        raise ValueError("a Kerr ray map holds one ray per pixel: --spin_map does not combine with --supersample > 1")
+    if map_supersample != 1:
+        raise ValueError("a Kerr ray map has no supersampled form: --spin_map does not combine with --map_supersample > 1")
+    if gpus != 1 or world != 1:
+        raise ValueError("a ray map lives on one GPU: --spin_map does not combine with --gpus > 1 or several ranks")
+    for on, flag in ((ray_map, "--ray_map"), (orbit_map, "--orbit_map"), (shutter_map, "--shutter_map")):
+        if on:
+            raise ValueError(f"--spin_map does not combine with {flag}: that is a map of Schwarzschild rays")
+    for on, flag, why in ((observer, "--observer", "the observer march is Schwarzschild's"),
+                          (projection, "--projection", "the projected march is Schwarzschild's"),
+                          (light_delay, "--light_delay", "the delayed march is Schwarzschild's"),
+                          (stars, "--stars point", "point stars are rendered through the map of Schwarzschild rays"),
+                          (polarization, "--polarization", "the transport rule is Schwarzschild's")):
+        if on:
+            raise ValueError(f"--spin_map does not combine with {flag}: {why}")
+
+
 def _lib_max_png_width(bit_depth: int = 8) -> int:
     from . import _lib
     lib = _lib.load()
@@ -722,7 +757,7 @@ def hdr_sidecar(hdr: dict, max_cll: float, max_fall: float, frames: int) -> dict
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
                     shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None,
-                    stars=None, projection=None, light_delay=None, polarization=None) -> dict:
+                    stars=None, projection=None, light_delay=None, polarization=None, spin_map=False) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -744,6 +779,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(orbit_map=True)
     if shutter_map:
         params.update(shutter_map=True)
+    if spin_map:
+        params.update(spin_map=True)
     if map_supersample > 1:
         params.update(map_supersample=map_supersample)
     if video_hdr is not None:
@@ -797,7 +834,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  map_supersample: int = 1, video_hdr: Optional[str] = None, hdr_white: float = 203.0, hdr_exposure: float = 0.0,
                  observer: Optional[str] = None, observer_velocity=None, observer_sky: bool = True,
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
-                 light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, **_deprecated_kwargs) -> None:
+                 light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, spin_map: bool = False,
+                 **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
@@ -858,6 +896,15 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     with ``ray_map``, ``shutter > 0``, a tilted disk, a supersampling factor other than 1, a Disk V2 source or several ranks.
     The progress record carries ``orbit_map`` when it is set, and a resume with the other setting starts over.
 
+    ``spin_map=True`` (a renderer with a spin or the exact redshift): ONE Kerr ray map serves the whole video
+    (HipRenderer.build_kerr_ray_map).  A camera that stands still: its view is marched once, before the loop, and every frame is
+    shaded from the map (render_from_kerr_ray_map_async), bit for bit the marched frame.  With ``orbit``: the spin axis is z, so
+    the orbit is an exact symmetry of everything a Kerr ray's path depends on; frame 0's view is marched once and every frame is
+    shaded from the map turned to the frame's camera -- frame 0 is the marched frame, the others are as far from theirs as two
+    Kerr marches of symmetric views are from each other.  The map is freed at the end.  Refused with ValueError, before any
+    device work, with what check_spin_map names.  The progress record carries ``spin_map`` when it is set, and a resume with the
+    other setting starts over.
+
     ``shutter_map=True`` (with ``shutter > 0``): motion blur from ONE ray map.  What differs between the samples of an exposure
     -- the disk's roll, and under ``orbit`` the camera's turn about z -- is what a map leaves free, so no sample is marched: the
     map is built once (for orbit_position(static_cam_pos, 0, ...) under ``orbit``, else for ``static_cam_pos``) and every frame is
@@ -916,6 +963,10 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     moving = observer is not None or observer_velocity is not None or infall_to is not None
     projected = projection is not None or projection_fov is not None
     disk_model = "texture" if getattr(renderer, "_dv2", None) is None else "v2"
+    if spin_map:                                                # (without it the renderer is not asked anything, as ever)
+        check_spin_map(spin_map, renderer.spin, renderer.redshift, True, shutter, renderer.supersample if supersample is None else supersample,
+                       map_supersample, 1, world, ray_map, orbit_map, shutter_map, moving, projected, light_delay is not None,
+                       stars is not None, polarization is not None or stokes_path is not None)
     if moving or projected or light_delay is not None:
         # what the three variant checks take from the renderer and the call
         thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
@@ -994,7 +1045,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                              **({} if stars is None else {"stars": stars}),
                              **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}),
                              **({} if light_delay is None else {"light_delay": light_delay}),
-                             **({} if polarization is None else {"polarization": polarization}))
+                             **({} if polarization is None else {"polarization": polarization}), spin_map=spin_map)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -1108,6 +1159,12 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                                supersample=map_supersample)   # the one march of the video
         info = renderer.ray_map_info()
         print(f"  shutter ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
+    if spin_map:
+        # a camera that stands still: its view; an orbit: frame 0's, which every frame's camera is a turn of about the spin axis
+        renderer.build_kerr_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov)   # the one march of the video
+        info = renderer.kerr_ray_map_info()
+        print(f"  Kerr ray map built (spin {info['spin']:g}, {info['redshift']} redshift): {info['slots']} slots, {info['overflow_pixels']} overflow pixels, "
+              f"{info['device_bytes'] / 1e6:.0f} MB")
     t_loop0 = time.time()                               # ``stats`` (bench.py): the one-off set-up apart from the frame loop
 
     try:                                                # (a polarisation set above does not outlive a frame loop that raises)
@@ -1137,6 +1194,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                     stokes_grids[frame] = renderer.stokes_cells()      # the frame's cell grid (synchronises: a few kB per frame)
             elif orbit_map:
                 renderer.render_from_ray_map_async(frame=0, cam_pos=cam_pos, fov=fov)    # the map turned to the frame's camera
+            elif spin_map:                                     # the Kerr map: shade, no march; an orbit frame turned to its camera
+                renderer.render_from_kerr_ray_map_async(frame=0, cam_pos=cam_pos if orbit else None)
             else:                                              # marched: the frame of the moving camera, through the projection, with light delay
                 renderer.render_async(cam_pos, fov, frame=0, observer=None if plan is None else beta, observer_sky=observer_sky,
                                       projection=projection, projection_fov=projection_fov, light_delay=light_delay)   # (lens flare: on the device)
@@ -1174,6 +1233,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         print(f"Saved: {path} ({n_frames} cell grids of {polarization['cell']}-pixel cells)")
     if ray_map or orbit_map or shutter_map:
         renderer.free_ray_map()
+    if spin_map:
+        renderer.free_kerr_ray_map()
     if mjpeg:
         renderer.set_outputs(outputs_before)
     if dither != dither_before:

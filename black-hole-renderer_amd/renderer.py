@@ -642,6 +642,76 @@ class HipRenderer:
         """Release the ray map's device memory (bhr_raymap_free); close() does it too."""
         _lib.check(self._lib.bhr_raymap_free(self._ctx))
 
+    # ------------------------------------------------------------------ Kerr ray map
+    def build_kerr_ray_map(self, cam_pos, fov: float) -> None:
+        """March the view once with the Kerr march of the renderer's spin and redshift mode and keep what the march finds
+        before it shades anything (bhr_kerr_raymap_build; include/bhr.h states the map).  A map of its own beside build_ray_map's,
+        which stays the call for a hole that does not spin.  The slot count is option "raymap_slots" (1..8, default 4); one ray
+        per pixel, whole-frame renderers only.  Synchronises."""
+        cam = self.camera_uniforms(cam_pos, fov, 0)
+        _lib.check(self._lib.bhr_kerr_raymap_build(self._ctx, C.byref(cam), 0))
+        self._kerr_map_fov = float(fov)
+
+    def render_from_kerr_ray_map_async(self, frame: int = 0, t_offset: Optional[float] = None, cam_pos=None, skip_bloom: bool = False,
+                                       lens_flare=None) -> None:
+        """One frame from the Kerr ray map under the scene as it is now (bhr_kerr_raymap_render): bit for bit the frame
+        render_async(cam_pos, fov, frame) of the build's view leaves, without marching it again.  The disk is rolled by
+        ``t_offset``, or by ``frame * disk_rotation_speed``; the lens flare as render_async decides it.  The renderer's spin and
+        redshift mode have to be the build's still.
+
+        With ``cam_pos``: the frame seen from that camera under the build's field of view, which has to be the build's turned about
+        the z axis, the spin axis (a position of camera.orbit_position; bhr_kerr_raymap_render_view).  The stored rays are turned with the camera:
+        the frame is the Kerr march of the build view's rays, NOT bit-identical to render_async(cam_pos, ...); at the build's own
+        position it is the frame described above, bit for bit."""
+        t = float(frame) * self.disk_rotation_speed if t_offset is None else float(t_offset)
+        flags = _lib.SKIP_BLOOM if skip_bloom else 0
+        if self.lens_flare if lens_flare is None else lens_flare:
+            flags |= _lib.LENS_FLARE
+        if cam_pos is not None:
+            fov = getattr(self, "_kerr_map_fov", None)
+            if fov is None:
+                raise AssertionError("no Kerr ray map has been built (build_kerr_ray_map)")
+            cam = self.camera_uniforms(cam_pos, fov, frame, t_offset)
+            _lib.check(self._lib.bhr_kerr_raymap_render_view(self._ctx, C.byref(cam), flags))
+            return
+        _lib.check(self._lib.bhr_kerr_raymap_render(self._ctx, t, flags))
+
+    def kerr_ray_map_info(self) -> dict:
+        """The renderer's Kerr ray map (bhr_kerr_raymap_info): built, slots, width, rows, ray_steps of the build,
+        crossings_stored, overflow_pixels, device_bytes, the spin and the redshift ("model" / "exact") it was built under, and
+        the build camera's pos / r_escape."""
+        info = _lib.KerrRayMapDesc()
+        _lib.check(self._lib.bhr_kerr_raymap_info(self._ctx, C.byref(info)))
+        out = {name: int(getattr(info, name)) for name in ("built", "slots", "width", "rows", "crossings_stored", "overflow_pixels",
+                                                           "device_bytes", "ray_steps")}
+        out["spin"] = float(info.spin)
+        out["redshift"] = "exact" if info.redshift == _lib.REDSHIFT_EXACT else "model"
+        out["cam_pos"] = [float(v) for v in info.cam.pos]
+        out["r_escape"] = float(info.cam.r_escape)
+        return out
+
+    def kerr_ray_map_passes(self) -> dict:
+        """The Kerr map's planes as NumPy arrays in (H, W[, ...]) order: ``steps``, ``status`` (0 captured, 1 escaped, 2 out of
+        iterations), ``escape_dir`` (H, W, 3), ``crossings`` and ``hits`` (K, H, W, 5: hit_x, hit_y, and to_cam xyz under the
+        model redshift or the photon's momentum (p_x, p_y, 0) under the exact one)."""
+        info = self.kerr_ray_map_info()
+        if not info["built"]:
+            raise AssertionError("no Kerr ray map has been built (build_kerr_ray_map)")
+        h, w, k = info["rows"], info["width"], info["slots"]
+
+        def read(which, shape, dtype):
+            out = np.empty(shape, dtype=dtype)
+            _lib.check(self._lib.bhr_kerr_raymap_read(self._ctx, which, out.ctypes.data, out.nbytes))
+            return out
+        return {"steps": read(_lib.RAYMAP_STEPS, (h, w), np.int32), "status": read(_lib.RAYMAP_STATUS, (h, w), np.int32),
+                "escape_dir": read(_lib.RAYMAP_ESCAPE_DIR, (h, w, 3), np.float32),
+                "crossings": read(_lib.RAYMAP_CROSSINGS, (h, w), np.int32), "hits": read(_lib.RAYMAP_HITS, (k, h, w, 5), np.float32)}
+
+    def free_kerr_ray_map(self) -> None:
+        """Release the Kerr ray map's device memory (bhr_kerr_raymap_free); close() does it too."""
+        _lib.check(self._lib.bhr_kerr_raymap_free(self._ctx))
+        self._kerr_map_fov = None
+
     # ------------------------------------------------------------------ point stars
     def set_stars(self, dirs, flux, max_magnification: float = 32.0, max_span_deg: float = 10.0) -> None:
         """Set the star catalogue the frames from the ray map render as lensed points (bhr_set_stars; include/bhr.h states the

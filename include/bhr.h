@@ -607,6 +607,57 @@ BHR_API int32_t bhr_kerr_resources(int32_t supersampled, int32_t out[3]);
 BHR_API int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode);
 /* bhr_kerr_resources for the kernels of a redshift mode (BHR_REDSHIFT_MODEL: the same numbers). */
 BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, int32_t out[3]);
+/* The Kerr ray map: the ray map (bhr_raymap_build above) of a spinning hole, an object of its own beside it.  A Kerr ray's path
+ * depends on the camera, the geometry of bhr_config and the spin, not on the skybox, the disk texture or t_offset.
+ * bhr_kerr_raymap_build(ctx, cam, 0) marches the whole-frame view `cam` once with the Kerr march of the context's redshift
+ * mode and keeps per pixel what bhr_raymap_build keeps: the executed steps, the status (0 captured, 1 escaped, 2 out of
+ * iterations), the normalized escape direction (zeros unless escaped), the number of annulus crossings, and the first K of
+ * them front to back as 5 floats each -- hit_x, hit_y, and to_cam xyz under BHR_REDSHIFT_MODEL or the photon's momentum
+ * (p_x, p_y, 0) at the hit under BHR_REDSHIFT_EXACT.  K = option "raymap_slots" (1..8).  A pixel with more crossings is put on
+ * an overflow list.  Synchronises; ordered behind the frames in flight; the planes are reused by later builds of the same K.
+ * The build records the spin, the redshift mode and the camera.
+ * bhr_kerr_raymap_render(ctx, t, flags) is a frame: BG, DISK, and with them FINAL and the u8 rows, are bit for bit those of
+ * bhr_render(ctx, &cam_t, flags) with cam_t the build camera at t_offset = t, under the scene as it is at the call.  The
+ * records are shaded by csrc/march_kerr_raymap.hip's shade kernel, the pixels of the overflow list are marched by its fix
+ * kernel in the same frame.  flags: BHR_SKIP_BLOOM | BHR_LENS_FLARE.  The frame takes the next frame slot, has one
+ * timing-ring entry whose march bracket spans the two launches, and goes through the post-pass, grade, sinks and reads like
+ * any frame; its ray-step count is that of the overflow pixels (bhr_kerr_raymap_desc.ray_steps has the build's, equal to a
+ * marched frame's).  It neither counts towards nor runs the stream calibration.
+ * bhr_kerr_raymap_render_view(ctx, cam, flags): the frame seen from `cam`, which must be the build camera turned rigidly about
+ * the z axis (the checks of bhr_raymap_render_view).  The spin axis is z and the disk of a spinning hole is not tilted, so the
+ * turn is an exact symmetry of everything a Kerr ray's path depends on: the stored records are turned with the camera (two
+ * products and a sum per component) and shaded; overflow pixels are marched from `cam`.  Such a frame is the Kerr march of the
+ * build view's rays, not bit for bit bhr_render's frame of `cam`; with `cam` the build camera it is bhr_kerr_raymap_render's
+ * bit for bit.
+ * bhr_kerr_raymap_read hands out BHR_RAYMAP_STEPS / _STATUS / _ESCAPE_DIR / _CROSSINGS as (rows, W[, 3]) and _HITS as
+ * (K, rows, W, 5); bhr_kerr_raymap_info never fails for want of a map (built = 0 then); bhr_kerr_raymap_free is ordered behind
+ * the frames in flight, and bhr_destroy releases the map.  The Schwarzschild map of the context, point stars and the
+ * polarisation neither see nor are changed by any of these calls.
+ * Not available: shutter frames from this map, a supersampled map, several devices.
+ *   BHR_ERR_STATE:   build without the Kerr march (no spin, not forced, no exact redshift): bhr_raymap_build is the call for a
+ *                    hole that does not spin; render or read before a build (or after bhr_kerr_raymap_free); render while the
+ *                    context's spin or redshift mode is no longer the build's (the message names both).
+ *   BHR_ERR_INVALID: a row-block context; everything the Kerr march refuses (a tilted disk, anti_alias = 1, a Disk V2 source,
+ *                    adaptive supersampling); bhr_set_supersample(k > 1); "raymap_supersample" other than 1 or "raymap_slots"
+ *                    outside 1..8 at a build; a build camera inside the static limit; any build flag; any other render flag;
+ *                    a non-finite t_offset; a view camera that is not a turn of the build's about z; an unknown plane or a
+ *                    wrong byte count.  Nothing is launched and the context renders as before. */
+typedef struct {
+    int32_t built, slots, width, rows;
+    int32_t redshift;                   /* BHR_REDSHIFT_* the map was built under */
+    float spin;                         /* a / M the map was built for */
+    int64_t crossings_stored;
+    int64_t overflow_pixels;
+    int64_t device_bytes;
+    uint64_t ray_steps;                 /* of the build: a marched Kerr frame's */
+    bhr_camera cam;                     /* the build camera */
+} bhr_kerr_raymap_desc;
+BHR_API int32_t bhr_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
+BHR_API int32_t bhr_kerr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
+BHR_API int32_t bhr_kerr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
+BHR_API int32_t bhr_kerr_raymap_read(bhr_ctx *ctx, int32_t plane, void *out, int64_t bytes);
+BHR_API int32_t bhr_kerr_raymap_info(bhr_ctx *ctx, bhr_kerr_raymap_desc *out);
+BHR_API int32_t bhr_kerr_raymap_free(bhr_ctx *ctx);
 /* A moving observer: one frame as a camera sees it that moves through bhr_camera.pos with velocity beta (a 3-vector in units of
  * c, |beta| <= 0.995) as the static observer there measures it.  That observer's local frame is identified with the coordinate
  * axes, as the camera that stands still identifies it; the camera basis is the moving camera's own.  With n' the pixel's
