@@ -1,7 +1,9 @@
-// api_raymap.hip -- the ray map's entry points (include/bhr.h): build, read, info, free, and the refusals of
-// bhr_raymap_render, bhr_raymap_render_view and bhr_raymap_render_shutter (the frames themselves are launched from render.hip, next to bhr_render: they take
-// a frame slot like any other).
-// The kernels are march_raymap.hip's, their launchers march_launch.hip's.
+// api_raymap.hip -- the owner of a context's ray maps, and the Schwarzschild map's entry points (include/bhr.h).
+// The owner: what a map of either kind (bhr_raymap, bhr_internal.h) needs done the same way -- its planes, the tail of a build,
+// the plane reader, free -- once, taking the map; api_kerr_raymap.hip keeps the Kerr map's refusals and entry points over it.
+// The entry points: build, read, info, free, and the refusals of bhr_raymap_render, bhr_raymap_render_view and
+// bhr_raymap_render_shutter (the frames themselves are launched from render.hip, next to bhr_render: they take a frame slot
+// like any other).  The kernels are march_raymap.hip's and march_kerr_raymap.hip's, their launchers march_launch.hip's.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -104,9 +106,7 @@ int32_t check_polar(const bhr_ctx *ctx, const char *who, const char *what) {
     return BHR_OK;
 }
 
-}  // namespace
-
-void bhr_raymap_free_planes(bhr_raymap *rm) {
+void free_planes(bhr_raymap *rm) {
     BhrRayMapArgs &a = rm->a;
     void *bufs[] = {a.steps, a.status, a.dir, a.crossings, a.hits, a.over_count, a.over_list, a.stats};
     for (void *b : bufs)
@@ -118,7 +118,8 @@ void bhr_raymap_free_planes(bhr_raymap *rm) {
     rm->device_bytes = 0;
 }
 
-int32_t bhr_raymap_alloc_planes(bhr_raymap *rm, const char *who, int32_t K, int32_t comps, size_t plane, int32_t ss) {
+// K slots of `comps` floats over `plane` pixels with an overflow list for factor ss; a failed allocation leaves the object empty
+int32_t alloc_planes(bhr_raymap *rm, const char *who, int32_t K, int32_t comps, size_t plane, int32_t ss) {
     BhrRayMapArgs &a = rm->a;
     // the fix kernel's grid is sized in blocks of 256 entries of the list's capacity; a supersampled map lists whole k x k
     // groups, k^2-aligned (k^2 divides 256)
@@ -130,7 +131,7 @@ int32_t bhr_raymap_alloc_planes(bhr_raymap *rm, const char *who, int32_t K, int3
         (rc = plane_alloc(rm, who, &a.crossings, plane)) || (rc = plane_alloc(rm, who, &a.hits, (size_t)K * comps * plane)) ||
         (rc = plane_alloc(rm, who, &a.over_count, 16)) || (rc = plane_alloc(rm, who, &a.over_list, over_cap)) ||
         (rc = plane_alloc(rm, who, &a.stats, 8 + BHR_STEP_CELL))) {
-        bhr_raymap_free_planes(rm);    // a later build starts clean; the context is as it was
+        free_planes(rm);               // a later build starts clean; the context is as it was
         return rc;
     }
     a.slots = K;
@@ -143,14 +144,110 @@ int32_t bhr_raymap_alloc_planes(bhr_raymap *rm, const char *who, int32_t K, int3
     return BHR_OK;
 }
 
-void bhr_raymap_release(bhr_ctx *ctx) {
-    if (!ctx->raymap) return;
-    bhr_raymap_free_planes(ctx->raymap);
-    delete ctx->raymap;
-    ctx->raymap = nullptr;
+// the star plane of the build view and the Stokes planes of the last frame belong to the Schwarzschild map: stale when it changes
+void invalidate_consumers(bhr_ctx *ctx, const bhr_raymap *rm) {
+    if (rm->kind != BHR_RAYMAP_SCHWARZSCHILD) return;
     bhr_stars_invalidate(ctx);
     bhr_polar_invalidate(ctx);
 }
+
+}  // namespace
+
+// ---- what the two maps of a context share (bhr_internal.h) ----------------------------------------------------------------------------
+
+void bhr_raymap_release(bhr_ctx *ctx, bhr_raymap **map) {
+    bhr_raymap *rm = *map;
+    if (!rm) return;
+    free_planes(rm);
+    *map = nullptr;
+    invalidate_consumers(ctx, rm);
+    delete rm;
+}
+
+int32_t bhr_raymap_free_map(bhr_ctx *ctx, bhr_raymap **map) {
+    if (!*map) return BHR_OK;
+    BHR_TRY(bhr_enter(ctx));
+    BHR_TRY(drain(ctx));               // the frames in flight read the map
+    bhr_raymap_release(ctx, map);
+    return BHR_OK;
+}
+
+int32_t bhr_raymap_build_into(bhr_ctx *ctx, bhr_raymap **map, const char *who, const bhr_camera *cam, uint32_t flags, bhr_march_variant v, int32_t K, int32_t ss) {
+    const bool diff = bhr_want_diff(ctx, flags);
+    const int32_t comps = diff ? 9 : 5;
+    const size_t plane = (size_t)ctx->rows * ctx->cfg.width * (size_t)(ss * ss);
+
+    BHR_TRY(bhr_enter(ctx));           // behind the frames in flight: they may be reading the map this build rewrites
+    if (!*map) {
+        *map = new bhr_raymap();
+        memset(*map, 0, sizeof(bhr_raymap));
+        (*map)->kind = v == BHR_MV_NONE ? BHR_RAYMAP_SCHWARZSCHILD : BHR_RAYMAP_KERR;
+    }
+    bhr_raymap *rm = *map;
+    rm->built = 0;
+    invalidate_consumers(ctx, rm);
+    if (rm->a.hits && (rm->alloc_slots != K || rm->alloc_comps != comps || rm->alloc_ss != ss)) {
+        BHR_TRY(drain(ctx));
+        free_planes(rm);
+    }
+    if (!rm->a.hits) BHR_TRY(alloc_planes(rm, who, K, comps, plane, ss));
+    const BhrRayMapArgs &a = rm->a;
+    // records beyond a pixel's crossings stay zero
+    BHR_HIP(hipMemsetAsync(a.hits, 0, (size_t)K * comps * plane * sizeof(float), ctx->stream));
+    BHR_HIP(hipMemsetAsync(a.over_count, 0, 16 * sizeof(unsigned int), ctx->stream));
+    BHR_HIP(hipMemsetAsync(a.stats, 0, (8 + BHR_STEP_CELL) * sizeof(unsigned long long), ctx->stream));
+    BHR_TRY(bhr_launch_raymap_build(ctx, cam, flags, a, ss, v));
+    std::vector<unsigned long long> stats(8 + BHR_STEP_CELL);
+    unsigned int over = 0;
+    BHR_TRY(fetch(ctx, stats.data(), a.stats, stats.size() * sizeof(unsigned long long)));
+    BHR_TRY(fetch(ctx, &over, a.over_count, sizeof(over)));
+    unsigned long long steps = 0;
+    for (int k = 0; k < BHR_STEP_LANES; ++k) steps += stats[8 + (size_t)k * BHR_STEP_STRIDE];
+    rm->ray_steps = steps;
+    rm->crossings_stored = stats[0];
+    rm->overflow_pixels = over;
+    rm->diff = diff ? 1 : 0;
+    rm->slots = K;
+    rm->ss = ss;
+    rm->cam = *cam;
+    if (rm->kind == BHR_RAYMAP_KERR) {
+        rm->kerr_spin = ctx->kerr_spin;
+        rm->kerr_redshift = ctx->kerr_redshift;
+    }
+    rm->built = 1;
+    return BHR_OK;
+}
+
+int32_t bhr_raymap_read_plane(bhr_ctx *ctx, const bhr_raymap *rm, const char *who, int32_t which, void *out, int64_t bytes) {
+    const BhrRayMapArgs &a = rm->a;
+    const size_t plane = (size_t)a.plane;
+    size_t want = 0;
+    switch (which) {
+    case BHR_RAYMAP_STEPS: case BHR_RAYMAP_STATUS: case BHR_RAYMAP_CROSSINGS: want = plane * 4; break;
+    case BHR_RAYMAP_ESCAPE_DIR: want = plane * 12; break;
+    case BHR_RAYMAP_HITS: want = (size_t)a.slots * a.comps * plane * 4; break;
+    default: return bhr_fail(BHR_ERR_INVALID, "%s: unknown plane %d", who, which);
+    }
+    if (bytes != (int64_t)want) return bhr_fail(BHR_ERR_INVALID, "%s: plane %d has %zu bytes, caller gave %lld", who, which, want, (long long)bytes);
+    BHR_TRY(bhr_enter(ctx));
+    if (which == BHR_RAYMAP_STEPS) return fetch(ctx, out, a.steps, want);
+    if (which == BHR_RAYMAP_STATUS) return fetch(ctx, out, a.status, want);
+    if (which == BHR_RAYMAP_CROSSINGS) return fetch(ctx, out, a.crossings, want);
+    // the device planes are [component][pixel]; the caller gets [pixel][component]
+    const int nc = which == BHR_RAYMAP_ESCAPE_DIR ? 3 : a.comps, ns = which == BHR_RAYMAP_ESCAPE_DIR ? 1 : a.slots;
+    std::vector<float> tmp((size_t)nc * plane);
+    float *o = (float *)out;
+    for (int s = 0; s < ns; ++s) {
+        const float *src = which == BHR_RAYMAP_ESCAPE_DIR ? a.dir : a.hits + (size_t)s * nc * plane;
+        BHR_TRY(fetch(ctx, tmp.data(), src, tmp.size() * sizeof(float)));
+        float *os = o + (size_t)s * plane * nc;
+        for (int c = 0; c < nc; ++c)
+            for (size_t p = 0; p < plane; ++p) os[p * nc + c] = tmp[(size_t)c * plane + p];
+    }
+    return BHR_OK;
+}
+
+// ---- the Schwarzschild map's own -------------------------------------------------------------------------------------------------------
 
 int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
     if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render: null ctx");
@@ -250,116 +347,36 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     if (ss != 1 && ss != 2 && ss != 4 && ss != 8) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: raymap_supersample %d (1, 2, 4 or 8)", ss);
     if ((int64_t)ss * ss * ctx->cfg.width * ctx->cfg.height >= ((int64_t)1 << 31))
         return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_build: %d x %d rays of a %dx%d frame exceed 2^31", ss, ss, ctx->cfg.width, ctx->cfg.height);
-    const bool diff = bhr_want_diff(ctx, flags);
-    const int32_t comps = diff ? 9 : 5;
-    const size_t plane = (size_t)ctx->rows * ctx->cfg.width * (size_t)(ss * ss);
-
-    BHR_TRY(bhr_enter(ctx));           // behind the frames in flight: they may be reading the map this build rewrites
-    if (!ctx->raymap) {
-        ctx->raymap = new bhr_raymap();
-        memset(ctx->raymap, 0, sizeof(bhr_raymap));
-    }
-    bhr_raymap *rm = ctx->raymap;
-    rm->built = 0;
-    bhr_stars_invalidate(ctx);         // the star plane of the build view belongs to the map this build rewrites
-    bhr_polar_invalidate(ctx);         // ... and so do the Stokes planes of its last frame
-    if (rm->a.hits && (rm->alloc_slots != K || rm->alloc_comps != comps || rm->alloc_ss != ss)) {
-        BHR_TRY(drain(ctx));
-        bhr_raymap_free_planes(rm);
-    }
-    if (!rm->a.hits) BHR_TRY(bhr_raymap_alloc_planes(rm, "bhr_raymap_build", K, comps, plane, ss));
-    const BhrRayMapArgs &a = rm->a;
-    // records beyond a pixel's crossings stay zero
-    BHR_HIP(hipMemsetAsync(a.hits, 0, (size_t)K * comps * plane * sizeof(float), ctx->stream));
-    BHR_HIP(hipMemsetAsync(a.over_count, 0, 16 * sizeof(unsigned int), ctx->stream));
-    BHR_HIP(hipMemsetAsync(a.stats, 0, (8 + BHR_STEP_CELL) * sizeof(unsigned long long), ctx->stream));
-    BHR_TRY(bhr_launch_raymap_build(ctx, cam, flags, a, ss));
-    std::vector<unsigned long long> stats(8 + BHR_STEP_CELL);
-    unsigned int over = 0;
-    BHR_TRY(fetch(ctx, stats.data(), a.stats, stats.size() * sizeof(unsigned long long)));
-    BHR_TRY(fetch(ctx, &over, a.over_count, sizeof(over)));
-    unsigned long long steps = 0;
-    for (int k = 0; k < BHR_STEP_LANES; ++k) steps += stats[8 + (size_t)k * BHR_STEP_STRIDE];
-    rm->ray_steps = steps;
-    rm->crossings_stored = stats[0];
-    rm->overflow_pixels = over;
-    rm->diff = diff ? 1 : 0;
-    rm->slots = K;
-    rm->ss = ss;
-    rm->cam = *cam;
-    rm->built = 1;
-    return BHR_OK;
+    return bhr_raymap_build_into(ctx, &ctx->raymap, "bhr_raymap_build", cam, flags, BHR_MV_NONE, K, ss);
 }
 
 int32_t bhr_raymap_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: bad argument");
     if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_read: no ray map has been built (bhr_raymap_build)");
-    const bhr_raymap *rm = ctx->raymap;
-    const BhrRayMapArgs &a = rm->a;
-    const size_t plane = (size_t)a.plane;
-    size_t want = 0;
     if (which == BHR_RAYMAP_STARS) {
         // the build view's star plane (include/bhr.h "point stars"), gathered now if the map or the catalogue changed since
         if (!bhr_have_stars(ctx)) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_read: no star catalogue has been set (bhr_set_stars)");
         BHR_TRY(check_stars(ctx, "bhr_raymap_read"));
-        want = plane * 12;
+        const size_t want = (size_t)ctx->raymap->a.plane * 12;
         if (bytes != (int64_t)want) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: plane %d has %zu bytes, caller gave %lld", which, want, (long long)bytes);
         BHR_TRY(bhr_stars_ensure_plane(ctx));
         BHR_TRY(bhr_enter(ctx));
         return fetch(ctx, out, ctx->stars->d_plane, want);
     }
-    switch (which) {
-    case BHR_RAYMAP_STEPS: case BHR_RAYMAP_STATUS: case BHR_RAYMAP_CROSSINGS: want = plane * 4; break;
-    case BHR_RAYMAP_ESCAPE_DIR: want = plane * 12; break;
-    case BHR_RAYMAP_HITS: want = (size_t)a.slots * a.comps * plane * 4; break;
-    default: return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: unknown plane %d", which);
-    }
-    if (bytes != (int64_t)want) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: plane %d has %zu bytes, caller gave %lld", which, want, (long long)bytes);
-    BHR_TRY(bhr_enter(ctx));
-    if (which == BHR_RAYMAP_STEPS) return fetch(ctx, out, a.steps, want);
-    if (which == BHR_RAYMAP_STATUS) return fetch(ctx, out, a.status, want);
-    if (which == BHR_RAYMAP_CROSSINGS) return fetch(ctx, out, a.crossings, want);
-    // the device planes are [component][pixel]; the caller gets [pixel][component]
-    const int nc = which == BHR_RAYMAP_ESCAPE_DIR ? 3 : a.comps, ns = which == BHR_RAYMAP_ESCAPE_DIR ? 1 : a.slots;
-    std::vector<float> tmp((size_t)nc * plane);
-    float *o = (float *)out;
-    for (int s = 0; s < ns; ++s) {
-        const float *src = which == BHR_RAYMAP_ESCAPE_DIR ? a.dir : a.hits + (size_t)s * nc * plane;
-        BHR_TRY(fetch(ctx, tmp.data(), src, tmp.size() * sizeof(float)));
-        float *os = o + (size_t)s * plane * nc;
-        for (int c = 0; c < nc; ++c)
-            for (size_t p = 0; p < plane; ++p) os[p * nc + c] = tmp[(size_t)c * plane + p];
-    }
-    return BHR_OK;
+    return bhr_raymap_read_plane(ctx, ctx->raymap, "bhr_raymap_read", which, out, bytes);
 }
 
 int32_t bhr_raymap_get_info(bhr_ctx *ctx, bhr_raymap_info *out) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_get_info: bad argument");
-    memset(out, 0, sizeof(*out));
-    const bhr_raymap *rm = ctx->raymap;
-    if (!rm) return BHR_OK;
-    out->built = rm->built;
-    out->device_bytes = rm->device_bytes;
-    if (!rm->built) return BHR_OK;
-    out->diff = rm->diff;
-    out->slots = rm->slots;
-    out->width = ctx->cfg.width;
-    out->rows = ctx->rows;
-    out->supersample = rm->ss;
-    out->crossings_stored = (int64_t)rm->crossings_stored;
-    out->overflow_pixels = (int64_t)rm->overflow_pixels;
-    out->ray_steps = rm->ray_steps;
-    out->cam = rm->cam;
+    if (!bhr_raymap_fill_info(ctx, ctx->raymap, out)) return BHR_OK;
+    out->diff = ctx->raymap->diff;
+    out->supersample = ctx->raymap->ss;
     return BHR_OK;
 }
 
 int32_t bhr_raymap_free(bhr_ctx *ctx) {
     if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_free: null ctx");
-    if (!ctx->raymap) return BHR_OK;
-    BHR_TRY(bhr_enter(ctx));
-    BHR_TRY(drain(ctx));               // the frames in flight read the map
-    bhr_raymap_release(ctx);
-    return BHR_OK;
+    return bhr_raymap_free_map(ctx, &ctx->raymap);
 }
 
 }  // extern "C"

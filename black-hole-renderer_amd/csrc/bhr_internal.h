@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/bhr.h"
 #include "../../include/bhr_disk_v2.h"
@@ -335,9 +336,14 @@ struct bhr_options {
 
 // The context's ray map (api_raymap.hip): what the strict march of one whole-frame view finds before it shades anything.
 // Read-only shared state while frames are in flight, like the scene; allocated at the first build, reused by builds of the
-// same shape, released by bhr_raymap_free / bhr_destroy.
+// same shape, released by bhr_raymap_free / bhr_destroy.  A context owns up to two, ctx->raymap and ctx->kerr_raymap, one of each
+// kind; everything that builds, reads, shades and frees a map takes the map and asks it what it is.
+enum bhr_raymap_kind { BHR_RAYMAP_SCHWARZSCHILD, BHR_RAYMAP_KERR };
 struct bhr_raymap {
     BhrRayMapArgs a;             // the device planes
+    int32_t kind;                // bhr_raymap_kind: whose rays the records hold; stars and polarisation are the Schwarzschild kind's
+    float kerr_spin;             // a Kerr map: the spin and the redshift mode of its build, which a frame from it needs the
+    int32_t kerr_redshift;       // context to have still
     int32_t built, diff, slots;
     int32_t ss;                  // the map's own supersampling factor (option "raymap_supersample" at the build): planes of the fine frame
     int32_t alloc_slots, alloc_comps, alloc_ss;   // shape of the allocation
@@ -558,10 +564,8 @@ struct bhr_ctx {
     int32_t kerr_redshift;     // bhr_set_redshift: BHR_REDSHIFT_MODEL (0) or BHR_REDSHIFT_EXACT, which needs kerr_on
 
     // the Kerr ray map (api_kerr_raymap.hip): a map object of its own -- nothing of `raymap` above is shared, stars and polarisation
-    // never see it -- with the spin and the redshift mode it was built under, which a frame from it needs the context to have still
+    // never see it; it carries the spin and the redshift mode it was built under
     bhr_raymap *kerr_raymap;   // null until the first bhr_kerr_raymap_build
-    float kerr_map_spin;
-    int32_t kerr_map_redshift;
 
     // point stars (api_stars.hip)
     bhr_stars *stars;          // null until a catalogue is set (bhr_set_stars)
@@ -719,7 +723,9 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call);
 // own); shade: the map's pixels under the scene as it is and cam's t_offset into the active slot's
 // layers -- the pixels on the overflow list are left to the fix kernel (bhr_launch_march with a repair == 2 part over that list)
 // ss: the map's factor -- the build marches the fine frame bhr_fine(ctx, ss) of `cam`
-int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss);
+// v, call.req.variant: none takes march_raymap.hip's kernels under the march's block, BHR_MV_KERR / BHR_MV_KERR_EXACT
+// march_kerr_raymap.hip's under the Kerr block (one ray per pixel, 5 components, no stars)
+int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss, bhr_march_variant v = BHR_MV_NONE);
 // rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
 // stars: the star plane of the frame's view (bhr_set_stars), added to the sky sample by the STARS kernels; null: the kernels without
 int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f,
@@ -741,12 +747,6 @@ const void *bhr_march_kernel_projected(bhr_march_kernel k, int32_t diff, int32_t
 const void *bhr_march_kernel_delay(bhr_march_kernel k, int32_t diff, int32_t ss);      // march_delay.hip -> march_delay.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
 const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact);           // march_kerr_raymap.hip -> march_kerr_raymap.o (exact: the exact redshift's)
-// the Kerr ray map's launches (march_kerr_raymap.hip), under the Kerr block of variant v (BHR_MV_KERR or BHR_MV_KERR_EXACT).
-// build: on ctx->stream, marches `cam` with the Kerr Ray and fills the map.  shade: call.req.variant's kernel over the map into
-// the active slot's layers, turned by (rot_c, rot_s); opens the frame's march bracket -- the overflow launch behind it
-// (bhr_launch_march with the same call and a repair == 2 part over the map's list: kerr_raymap_fix_kernel) closes it
-int32_t bhr_launch_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, bhr_march_variant v, const BhrRayMapArgs &m);
-int32_t bhr_launch_kerr_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, float rot_c, float rot_s);
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
 
 // ---- hybrid.hip -------------------------------------------------------------------------------------------------------------------------
@@ -821,18 +821,39 @@ int32_t bhr_raymap_check_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
 int32_t bhr_raymap_check_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, float *rot_c, float *rot_s);
 // ... and of bhr_raymap_render_shutter, which fills smp (t, c, s per sample, n, 1 / n) and tells whether any sample is turned
 int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned);
-void bhr_raymap_release(bhr_ctx *ctx);
-// a map object's device planes, for both maps of a context: K slots of `comps` floats over `plane` pixels with an overflow list
-// for factor ss (who: the build a refusal names; a failed allocation leaves the object empty), and their release
-int32_t bhr_raymap_alloc_planes(bhr_raymap *rm, const char *who, int32_t K, int32_t comps, size_t plane, int32_t ss);
-void bhr_raymap_free_planes(bhr_raymap *rm);
+// What both maps of a context share, each taking the map or the context's pointer to it (&ctx->raymap or &ctx->kerr_raymap) and
+// the public call `who` that a refusal names.
+// The tail of a build, behind the entry point's own refusals: enters behind the frames in flight, creates the map or re-allocates
+// it on a shape change, clears it, marches `cam` into it (bhr_launch_raymap_build under `flags` and variant `v`, which also says
+// the map's kind) and fills its fields.  K: slots per pixel; ss: the map's own factor.
+int32_t bhr_raymap_build_into(bhr_ctx *ctx, bhr_raymap **map, const char *who, const bhr_camera *cam, uint32_t flags, bhr_march_variant v, int32_t K, int32_t ss);
+// one plane of a built map (BHR_RAYMAP_STEPS .. _HITS) to the host, [pixel][component]
+int32_t bhr_raymap_read_plane(bhr_ctx *ctx, const bhr_raymap *rm, const char *who, int32_t which, void *out, int64_t bytes);
+int32_t bhr_raymap_free_map(bhr_ctx *ctx, bhr_raymap **map);                    // behind every stream that may still read it
+void bhr_raymap_release(bhr_ctx *ctx, bhr_raymap **map);                        // ... without waiting (bhr_destroy)
+// the fields the two info structs of include/bhr.h share, `out` zeroed first; false: no built map, nothing more to say
+template <class Info>
+bool bhr_raymap_fill_info(const bhr_ctx *ctx, const bhr_raymap *rm, Info *out) {
+    memset(out, 0, sizeof(*out));
+    if (!rm) return false;
+    out->built = rm->built;
+    out->device_bytes = rm->device_bytes;
+    if (!rm->built) return false;
+    out->slots = rm->slots;
+    out->width = ctx->cfg.width;
+    out->rows = ctx->rows;
+    out->crossings_stored = (int64_t)rm->crossings_stored;
+    out->overflow_pixels = (int64_t)rm->overflow_pixels;
+    out->ray_steps = rm->ray_steps;
+    out->cam = rm->cam;
+    return true;
+}
 // is `cam` the build camera `b` turned rigidly about z?  Gives the turn's cosine and sine (binary64, rounded once)
 int32_t bhr_raymap_turn_of_build(const bhr_camera &b, const bhr_camera *cam, const char *who, float *rot_c, float *rot_s);
 
 // ---- api_kerr_raymap.hip ------------------------------------------------------------------------------------------------------------------
 // the refusals of bhr_kerr_raymap_render and bhr_kerr_raymap_render_view (nothing launched); cam null: the build camera, no turn
 int32_t bhr_kerr_raymap_check_render(bhr_ctx *ctx, const char *who, const bhr_camera *cam, float t_offset, uint32_t flags, float *rot_c, float *rot_s);
-void bhr_kerr_raymap_release(bhr_ctx *ctx);
 
 // ---- api_stars.hip ----------------------------------------------------------------------------------------------------------------------
 inline bool bhr_have_stars(const bhr_ctx *ctx) { return ctx->stars && ctx->stars->n > 0; }

@@ -186,8 +186,8 @@ void bhr_destroy(bhr_ctx *ctx) {
     bhr_jpeg_dev_free(ctx);
     bhr_shutter_free(ctx);
     bhr_grade_free(ctx);
-    bhr_raymap_release(ctx);
-    bhr_kerr_raymap_release(ctx);
+    bhr_raymap_release(ctx, &ctx->raymap);
+    bhr_raymap_release(ctx, &ctx->kerr_raymap);
     bhr_stars_release(ctx);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);

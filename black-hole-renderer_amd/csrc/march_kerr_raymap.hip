@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "ray_kerr.h"
+#include "raymap_device.h"
 
 namespace {
 
@@ -33,8 +34,8 @@ template <int RS>
 using KerrBlock = std::conditional_t<RS == KERR_EXACT, BhrKerrExactMarchArgs, BhrKerrMarchArgs>;
 
 // ---- the build ----------------------------------------------------------------------------------------------------------------
-// raymap_build_kernel<false, false>'s body (march_raymap.hip) over the Kerr Ray: one 8x8 tile per wave, tiles in the march's
-// launch order (longest rays first).
+// raymap_build_kernel<false, false>'s march (march_raymap.hip) over the Kerr Ray: one 8x8 tile per wave, tiles in the march's
+// launch order (longest rays first); the overflow list is appended to by the function both builds call (raymap_device.h).
 template <int RS>
 __global__ __launch_bounds__(256) void kerr_raymap_build_kernel(KerrBlock<RS> a, BhrRayMapArgs m) {
     const int slot = wave_slot();
@@ -79,17 +80,7 @@ __global__ __launch_bounds__(256) void kerr_raymap_build_kernel(KerrBlock<RS> a,
         m.dir[2 * (size_t)m.plane + pix] = dn.z;
         m.crossings[pix] = n_rec;
     }
-    // more crossings than slots: the pixel keeps its first m.slots records and goes on the overflow list (wave-aggregated
-    // append; every pixel is appended at most once and the list has room for all of them)
-    const bool over = valid && n_rec > m.slots;
-    const unsigned long long om = __ballot(over);
-    if (om) {
-        const int first = __ffsll((long long)om) - 1;
-        unsigned int base = 0;
-        if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(om));
-        base = __shfl(base, first, BHR_WAVE);
-        if (over) m.over_list[base + (unsigned int)__popcll(om & ((1ull << lane) - 1ull))] = (int32_t)pix;
-    }
+    raymap_append_overflow(m, valid && n_rec > m.slots, lane, pix);
     const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
     const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
     if (lane == 0) {
@@ -99,29 +90,7 @@ __global__ __launch_bounds__(256) void kerr_raymap_build_kernel(KerrBlock<RS> a,
 }
 
 // ---- the shade ----------------------------------------------------------------------------------------------------------------
-// x' = c x - s y, y' = s x + c y: two products and a sum per component, as march_raymap.hip's turn_xy rounds them (this object
-// contracts within an expression; the turn is kept out of that)
-__device__ __forceinline__ void turn_xy(float c, float s, float &x, float &y) {
-#pragma clang fp contract(off)
-    const float xr = c * x - s * y, yr = s * x + c * y;
-    x = xr;
-    y = yr;
-}
-
-// render.py:3008-3018 as pixel_values has it, from the direction the build kernel stored already normalized
-// (march_raymap.hip: raymap_pixel_values, without the star plane)
-__device__ __forceinline__ void kerr_raymap_pixel_values(const BhrMarchArgs &a, bool escaped, V3 dir, const Shade &sh, float bk[3], float dk[3]) {
-    V3 bg = mk(0, 0, 0);
-    if (escaped) bg = sample_skybox(a.sc, dir);
-    float k = 1.0f - sh.alpha_total;
-    bk[0] = __fmul_rn(bg.x, k);
-    bk[1] = __fmul_rn(bg.y, k);
-    bk[2] = __fmul_rn(bg.z, k);
-    dk[0] = fminf(fmaxf(sh.accum.x, 0.0f), 1.0f);
-    dk[1] = fminf(fmaxf(sh.accum.y, 0.0f), 1.0f);
-    dk[2] = fminf(fmaxf(sh.accum.z, 0.0f), 1.0f);
-}
-
+// (turn_xy and raymap_pixel_values, without a star plane: raymap_device.h)
 // One lane per pixel, an 8x8 tile per wave as in the march (texture locality, and store_pixel's packed layout is per tile);
 // tiles in row-major order: every lane does about the same work.
 // ROT: the records are turned about z by (m.rot_c, m.rot_s) before they are shaded (the head of this file).
@@ -157,7 +126,7 @@ __global__ __launch_bounds__(256) void kerr_raymap_shade_kernel(KerrBlock<RS> a,
     V3 dir = mk(m.dir[pix], m.dir[p + pix], m.dir[2 * p + pix]);
     if (ROT) turn_xy(rc, rs, dir.x, dir.y);
     float bk[3], dk[3];
-    kerr_raymap_pixel_values(a, esc, dir, sh, bk, dk);
+    raymap_pixel_values(a, esc, dir, sh, bk, dk);
     store_pixel(a, i, j, a.width, bk, dk);
 }
 

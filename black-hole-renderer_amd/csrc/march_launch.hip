@@ -518,16 +518,22 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
     return BHR_OK;
 }
 
-// ---- the ray map (march_raymap.hip; api_raymap.hip owns the map) ------------------------------------------------------------------
+// ---- the ray maps (march_raymap.hip, march_kerr_raymap.hip; api_raymap.hip owns the maps) ------------------------------------------
 // The kernels take the march's argument block of the strict frame and the map as a second argument.  A supersampled map (its
 // own factor ss, option "raymap_supersample"; the context's factor stays 1) takes the block of the fine frame, as a marched
-// supersampled frame does, and the kernels' supersampled twins.
-int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss) {
+// supersampled frame does, and the kernels' supersampled twins.  Under a Kerr variant the kernels are the Kerr map's, which take
+// the Kerr block of the redshift (variant_args) in the march block's place: one ray per pixel, no differentials, no stars.
+static const void *raymap_kernel(bhr_march_variant v, bhr_march_kernel plain, bhr_march_kernel kerr, bool diff, int32_t ss) {
+    return v == BHR_MV_NONE ? bhr_march_kernel_raymap(plain, diff, ss > 1) : bhr_march_kernel_kerr_raymap(kerr, v == BHR_MV_KERR_EXACT);
+}
+
+int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss, bhr_march_variant v) {
+    const char *api = v == BHR_MV_NONE ? "bhr_raymap_build" : "bhr_kerr_raymap_build";
     const hipStream_t stream = ctx->stream;
-    const bhr_march_call call = {cam, flags | BHR_FORCE_STRICT, stream, /* slot */ -1, false, false, ss, false};
+    const bhr_march_call call = {cam, flags | BHR_FORCE_STRICT, stream, /* slot */ -1, false, false, ss, false, {v}};
     BhrMarchArgs a;
     march_args(ctx, call, nullptr, ss, false, a);
-    if ((int64_t)a.width * a.rows != m.plane) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: the map has %lld pixels, the frame %lld", (long long)m.plane, (long long)a.width * a.rows);
+    if ((int64_t)a.width * a.rows != m.plane) return bhr_fail(BHR_ERR_STATE, "%s: the map has %lld pixels, the frame %lld", api, (long long)m.plane, (long long)a.width * a.rows);
     if (ss == 1) {
         BHR_TRY(ensure_tile_order(ctx, 1, a.tiles_x, a.n_tiles));
         a.tile_order = ctx->d_tile_order;
@@ -537,17 +543,18 @@ int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     // a build is a one-off, its ragged tail does not matter.
     a.ray_steps = m.stats + 8;                                 // a counter cell of the map's own, behind its totals
     const bool diff = bhr_want_diff(ctx, flags);
-    if (m.comps != (diff ? 9 : 5)) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: %d components per record for differentials %d", m.comps, (int)diff);
-    const void *fn = bhr_march_kernel_raymap(BHR_MK_RAYMAP_BUILD, diff, ss > 1);
-    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_build: no build kernel in this library");
+    if (m.comps != (diff ? 9 : 5)) return bhr_fail(BHR_ERR_STATE, "%s: %d components per record for differentials %d", api, m.comps, (int)diff);
+    const void *fn = raymap_kernel(v, BHR_MK_RAYMAP_BUILD, BHR_MK_KERR_RAYMAP_BUILD, diff, ss);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "%s: no build kernel in this library", api);
+    VariantArgs va;
     BhrRayMapArgs mm = m;
-    void *args[] = {&a, &mm};
+    void *args[] = {variant_args(ctx, call.req, a, va), &mm};
     (void)hipLaunchKernel(fn, dim3((a.n_list + 3) / 4), dim3(256), args, 0, stream);
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }
 
-// What both shade launchers begin with: a scene to shade, the argument block `a` of call's frame at factor ss, and a map that
+// What the shade launchers begin with: a scene to shade, the argument block `a` of call's frame at factor ss, and a map that
 // fits it.  api: the public call a refusal names.
 static int32_t raymap_shade_args(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, int32_t ss, const char *api, BhrMarchArgs &a) {
     if (!ctx->d_skybox) return bhr_fail(BHR_ERR_STATE, "%s: no skybox set (bhr_set_skybox)", api);
@@ -559,65 +566,26 @@ static int32_t raymap_shade_args(bhr_ctx *ctx, const bhr_march_call &call, const
 }
 
 // rot_c, rot_s: the turn about z of call.cam from the map's build camera (bhr_raymap_render_view); 1, 0 is no turn and takes the
-// kernel without one, whose frame is the strict frame bit for bit.
+// kernel without one, whose frame is the marched frame bit for bit.
 int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c, float rot_s, const float *stars) {
+    const char *api = call.req.variant == BHR_MV_NONE ? "bhr_raymap_render" : "bhr_kerr_raymap_render";
     // call.ss: the map's factor -- the block of the fine frame (k W x k rows, k^2 W rows == the map's plane), a wave per fine tile
     BhrMarchArgs a;
-    BHR_TRY(raymap_shade_args(ctx, call, m, diff, call.ss, "bhr_raymap_render", a));
+    BHR_TRY(raymap_shade_args(ctx, call, m, diff, call.ss, api, a));
     const bool turned = !(rot_c == 1.0f && rot_s == 0.0f);
     // stars: the STARS kernels, which have no supersampled twins (the table then returns none)
     const bhr_march_kernel name = stars ? (turned ? BHR_MK_RAYMAP_SHADE_STARS_ROT : BHR_MK_RAYMAP_SHADE_STARS) : (turned ? BHR_MK_RAYMAP_SHADE_ROT : BHR_MK_RAYMAP_SHADE);
-    const void *fn = bhr_march_kernel_raymap(name, diff, call.ss > 1);
-    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render: no shade kernel in this library");
+    const void *fn = raymap_kernel(call.req.variant, name, turned ? BHR_MK_KERR_RAYMAP_SHADE_ROT : BHR_MK_KERR_RAYMAP_SHADE, diff, call.ss);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "%s: no shade kernel in this library", api);
     // the frame's march bracket opens here; the overflow launch behind this one (bhr_launch_march, last part) closes it
     // (a later sample of a shutter frame from the map keeps the first sample's)
     if (!call.keep_start) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
+    VariantArgs va;
     BhrRayMapStarArgs mm;              // the kernels without stars read its first sizeof(BhrRayMapArgs) bytes
     static_cast<BhrRayMapArgs &>(mm) = m;
     mm.rot_c = rot_c;
     mm.rot_s = rot_s;
     mm.stars = stars;
-    void *args[] = {&a, &mm};
-    (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
-    BHR_HIP(hipGetLastError());
-    return BHR_OK;
-}
-
-// ---- the Kerr ray map (march_kerr_raymap.hip; api_kerr_raymap.hip owns the map) ---------------------------------------------------
-// The kernels take the Kerr block of the redshift (variant_args) and the map as a second argument; one ray per pixel, no
-// differentials: 5 components per record.
-int32_t bhr_launch_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, bhr_march_variant v, const BhrRayMapArgs &m) {
-    const hipStream_t stream = ctx->stream;
-    const bhr_march_call call = {cam, BHR_FORCE_STRICT | BHR_SKIP_DIFFERENTIALS, stream, /* slot */ -1, false, false, 1, false, {v}};
-    BhrMarchArgs a;
-    march_args(ctx, call, nullptr, 1, false, a);
-    if ((int64_t)a.width * a.rows != m.plane || m.comps != 5)
-        return bhr_fail(BHR_ERR_STATE, "bhr_kerr_raymap_build: the map has %lld pixels of %d components, the frame %lld of 5", (long long)m.plane, m.comps, (long long)a.width * a.rows);
-    BHR_TRY(ensure_tile_order(ctx, 1, a.tiles_x, a.n_tiles));
-    a.tile_order = ctx->d_tile_order;
-    a.ray_steps = m.stats + 8;                                 // a counter cell of the map's own, behind its totals
-    const void *fn = bhr_march_kernel_kerr_raymap(BHR_MK_KERR_RAYMAP_BUILD, v == BHR_MV_KERR_EXACT);
-    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_kerr_raymap_build: no build kernel in this library");
-    VariantArgs va;
-    BhrRayMapArgs mm = m;
-    void *args[] = {variant_args(ctx, call.req, a, va), &mm};
-    (void)hipLaunchKernel(fn, dim3((a.n_list + 3) / 4), dim3(256), args, 0, stream);
-    BHR_HIP(hipGetLastError());
-    return BHR_OK;
-}
-
-int32_t bhr_launch_kerr_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, float rot_c, float rot_s) {
-    BhrMarchArgs a;
-    BHR_TRY(raymap_shade_args(ctx, call, m, false, 1, "bhr_kerr_raymap_render", a));
-    const bool turned = !(rot_c == 1.0f && rot_s == 0.0f);
-    const void *fn = bhr_march_kernel_kerr_raymap(turned ? BHR_MK_KERR_RAYMAP_SHADE_ROT : BHR_MK_KERR_RAYMAP_SHADE, call.req.variant == BHR_MV_KERR_EXACT);
-    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_kerr_raymap_render: no shade kernel in this library");
-    // the frame's march bracket opens here; the overflow launch behind this one (bhr_launch_march, last part) closes it
-    BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
-    VariantArgs va;
-    BhrRayMapArgs mm = m;
-    mm.rot_c = rot_c;
-    mm.rot_s = rot_s;
     void *args[] = {variant_args(ctx, call.req, a, va), &mm};
     (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
     BHR_HIP(hipGetLastError());

@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "ray_strict.h"
+#include "raymap_device.h"
 
 namespace {
 
@@ -118,17 +119,7 @@ __global__ __launch_bounds__(256) void raymap_build_kernel(BhrMarchArgs a, BhrRa
             if (over) m.over_list[at] = (int32_t)pix;
         }
     } else {
-        // more crossings than slots: the pixel keeps its first m.slots records and goes on the overflow list (wave-aggregated
-        // append, as the guard kernel's; every pixel is appended at most once and the list has room for all of them)
-        const bool over = valid && n_rec > m.slots;
-        const unsigned long long om = __ballot(over);
-        if (om) {
-            const int first = __ffsll((long long)om) - 1;
-            unsigned int base = 0;
-            if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(om));
-            base = __shfl(base, first, BHR_WAVE);
-            if (over) m.over_list[base + (unsigned int)__popcll(om & ((1ull << lane) - 1ull))] = (int32_t)pix;
-        }
+        raymap_append_overflow(m, valid && n_rec > m.slots, lane, pix);
     }
     const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
     const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
@@ -138,14 +129,7 @@ __global__ __launch_bounds__(256) void raymap_build_kernel(BhrMarchArgs a, BhrRa
     }
 }
 
-// ---- the shade: the two steps every shade kernel is made of ----------------------------------------------------------------------
-// x' = c x - s y, y' = s x + c y
-__device__ __forceinline__ void turn_xy(float c, float s, float &x, float &y) {
-    const float xr = c * x - s * y, yr = s * x + c * y;
-    x = xr;
-    y = yr;
-}
-
+// ---- the shade: the two steps every shade kernel is made of (turn_xy and raymap_pixel_values: raymap_device.h) ---------------------
 // The lane's first `count` records of pixel `pix`, front to back, through shade_hit from the Shade that Ray::init leaves.
 // ROT: each record is turned about z by (rc, rs) before it is shaded (the head of this file).
 // f: the block shade_hit reads a frame's own two fields from -- `a` itself for a frame under one camera (what shade_hit's
@@ -179,23 +163,6 @@ __device__ __forceinline__ Shade raymap_shade_records(const BhrMarchArgs &a, con
         shade_hit<DIFF, 0>(a, f, sh, hx, hy, to_cam, dxx, dxy, dyx, dyy);
     }
     return sh;
-}
-
-// render.py:3008-3018 as pixel_values has it, from the direction the build kernel stored already normalized
-// star: the pixel's value of the star plane (stars.hip; include/bhr.h "point stars"), added to the sky sample ahead of the product --
-// of a captured ray's pixel too, which has images from the triangles of its neighbours; null: no catalogue, no addition
-__device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool escaped, V3 dir, const Shade &sh, float bk[3], float dk[3],
-                                                    const float *star = nullptr) {
-    V3 bg = mk(0, 0, 0);
-    if (escaped) bg = sample_skybox(a.sc, dir);
-    if (star) bg = bg + mk(star[0], star[1], star[2]);
-    float k = 1.0f - sh.alpha_total;
-    bk[0] = __fmul_rn(bg.x, k);
-    bk[1] = __fmul_rn(bg.y, k);
-    bk[2] = __fmul_rn(bg.z, k);
-    dk[0] = fminf(fmaxf(sh.accum.x, 0.0f), 1.0f);
-    dk[1] = fminf(fmaxf(sh.accum.y, 0.0f), 1.0f);
-    dk[2] = fminf(fmaxf(sh.accum.z, 0.0f), 1.0f);
 }
 
 // The pixel's BG and DISK values from its shaded records: the ray's fate and its stored escape direction (turned as the

@@ -1,0 +1,51 @@
+// raymap_device.h -- the device code the two ray maps' kernels state once (march_raymap.hip, march_kerr_raymap.hip): what a
+// build kernel appends to the overflow list, and what a shade kernel does besides shading the records -- the turn about z, the
+// pixel's values.  Included behind the object's one ray_*.h (V3, Shade, sample_skybox and the
+// argument blocks are march_device.h's); every function is inlined, under the including object's own flags.
+// The march that records and the loops over the records stay with each object: they are made of its Ray and its shade_hit.
+#pragma once
+
+// x' = c x - s y, y' = s x + c y: two products and a sum per component.  Kept out of contraction by the pragma -- the Kerr
+// object contracts within an expression, the strict object not at all, where the pragma does nothing -- so both maps turn a
+// record to the same bits.
+__device__ __forceinline__ void turn_xy(float c, float s, float &x, float &y) {
+#pragma clang fp contract(off)
+    const float xr = c * x - s * y, yr = s * x + c * y;
+    x = xr;
+    y = yr;
+}
+
+// render.py:3008-3018 as pixel_values has it, from the direction the build kernel stored already normalized
+// star: the pixel's value of the star plane (stars.hip; include/bhr.h "point stars"), added to the sky sample ahead of the product --
+// of a captured ray's pixel too, which has images from the triangles of its neighbours; null: no catalogue, no addition
+__device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool escaped, V3 dir, const Shade &sh, float bk[3], float dk[3],
+                                                    const float *star = nullptr) {
+    V3 bg = mk(0, 0, 0);
+    if (escaped) bg = sample_skybox(a.sc, dir);
+    if (star) bg = bg + mk(star[0], star[1], star[2]);
+    float k = 1.0f - sh.alpha_total;
+    bk[0] = __fmul_rn(bg.x, k);
+    bk[1] = __fmul_rn(bg.y, k);
+    bk[2] = __fmul_rn(bg.z, k);
+    dk[0] = fminf(fmaxf(sh.accum.x, 0.0f), 1.0f);
+    dk[1] = fminf(fmaxf(sh.accum.y, 0.0f), 1.0f);
+    dk[2] = fminf(fmaxf(sh.accum.z, 0.0f), 1.0f);
+}
+
+// The header store is NOT here: each build kernel keeps its six stores.  Called through a function -- with the direction as a
+// value, or evaluated between the stores as the kernels have it -- they come out in another order in raymap_build_kernel<true, *>
+// (20 instructions of each; with the direction as a value, in all six build kernels): tools/code_object_diff.py.
+
+// One ray per pixel, more crossings than slots: the pixel keeps its first m.slots records and goes on the overflow list
+// (wave-aggregated append, as the guard kernel's; every pixel is appended at most once and the list has room for all of them).
+// Every lane of the wave calls it.
+__device__ __forceinline__ void raymap_append_overflow(const BhrRayMapArgs &m, bool over, int lane, size_t pix) {
+    const unsigned long long om = __ballot(over);
+    if (om) {
+        const int first = __ffsll((long long)om) - 1;
+        unsigned int base = 0;
+        if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(om));
+        base = __shfl(base, first, BHR_WAVE);
+        if (over) m.over_list[base + (unsigned int)__popcll(om & ((1ull << lane) - 1ull))] = (int32_t)pix;
+    }
+}

@@ -1,5 +1,5 @@
-// render.hip -- the kinds of frame on a frame slot (marched, under any march variant; shutter; from the ray map, its view and
-// its shutter), and the one place that rotates the slots and keeps the last frame's record.
+// render.hip -- the kinds of frame on a frame slot (marched, under any march variant; shutter; from a ray map of either kind,
+// its view and the Schwarzschild map's shutter), and the one place that rotates the slots and keeps the last frame's record.
 // One frame: march -> bloom H -> bloom V + combine (-> lens flare).  Frames alternate between the context's two
 // frame slots (bhr_frame_slot): frame n + 1 is launched on the other slot's stream into its own buffers and overlaps
 // the tail and the post-passes of frame n.  The scene is only read; everything that writes it or reads a frame goes
@@ -119,55 +119,40 @@ bhr_march_part raymap_fix_part(const bhr_raymap &rm) {
 // strict fix kernel over the overflow list (which, unless the call defers it, records the ring slot's march-end event).
 // With a star catalogue set (bhr_set_stars) the view's star plane comes first -- the cached one of the build view, or the gather
 // of the turned view into the slot's own plane, on the frame's stream ahead of its march bracket -- and the shade kernel is the
-// STARS one.
+// STARS one.  Stars are the Schwarzschild kind's: a Kerr map's frame does not ask for the catalogue.
+// Under call's Kerr variant both launches take the Kerr map's kernels (march_launch.hip).
 int32_t raymap_frame_launches(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm, float c, float s) {
     const float *stars = nullptr;
-    if (bhr_have_stars(ctx)) BHR_TRY(bhr_stars_frame_plane(ctx, call.cam, c, s, &stars));
+    if (rm.kind == BHR_RAYMAP_SCHWARZSCHILD && bhr_have_stars(ctx)) BHR_TRY(bhr_stars_frame_plane(ctx, call.cam, c, s, &stars));
     BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, c, s, stars));
     const bhr_march_part part = raymap_fix_part(rm);
     return bhr_launch_march(ctx, call, &part);
 }
 
-// A frame from the context's ray map on slot k (bhr_raymap_render): the shade kernel over the stored records, then the strict
-// fix kernel over the map's overflow list (its count is the device's: a grid for the list's capacity, as the hybrid march
+// A frame from the map `rm` on slot k (bhr_raymap_render, bhr_kerr_raymap_render): the shade kernel over the stored records, then
+// the fix kernel over the map's overflow list (its count is the device's: a grid for the list's capacity, as the hybrid march
 // launches it), inside one march bracket, then the post-pass as behind any march.  The ring cell counts the re-march only.
-// rot_c, rot_s: the turn of `cam` from the build camera (bhr_raymap_render_view; 1, 0 for bhr_raymap_render).  The fix kernel
-// marches the overflow pixels from `cam`, the frame's own camera.
-int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, float rot_c = 1.0f, float rot_s = 0.0f) {
+// rot_c, rot_s: the turn of `cam` from the build camera (the _render_view calls; 1, 0 for the build view).  The fix kernel
+// marches the overflow pixels from `cam`, the frame's own camera.  A Kerr map's frame runs under the context's Kerr variant.
+int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_raymap &rm, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, float rot_c = 1.0f, float rot_s = 0.0f) {
     bhr_frame_slot &f = ctx->slots[k];
-    const bhr_raymap &rm = *ctx->raymap;
+    const bool kerr = rm.kind == BHR_RAYMAP_KERR;
     BHR_TRY(bhr_frame_begin(ctx, flags));
     // a supersampled map: the call carries the map's factor, so both launches work on the fine frame and the fix launch takes
     // march_fix_ss_kernel, which resolves the overflow list's whole groups
-    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ false, /* ss */ rm.ss};
+    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ false, /* ss */ rm.ss, /* keep_start */ false,
+                                 {kerr ? bhr_variant_of(ctx) : BHR_MV_NONE}};
     *fm = {rm.ss, 1, false};
     BHR_TRY(raymap_frame_launches(ctx, call, rm, rot_c, rot_s));
     f.march_done = ctx->ring_ev[ring * 3 + 1];
     // a polarisation is set (bhr_set_polarization): the Stokes pass over the same records into the slot's own planes, behind the
     // frame's march bracket and ahead of its post-pass -- the frame's end event covers it, so a read waits for it like for the rest.
     // It reads the scene (shade_hit samples the disk texture), so it replaces f.march_done by an event of the slot's own behind it.
-    if (bhr_have_polar(ctx)) {
+    // The Schwarzschild kind's alone, like the stars.
+    if (!kerr && bhr_have_polar(ctx)) {
         BHR_TRY(bhr_polar_frame(ctx, call, rm));
         ctx->stokes_slot = k;
     }
-    return post_on_slot(ctx, flags, k, ring);
-}
-
-// A frame from the context's Kerr ray map on slot k (bhr_kerr_raymap_render, bhr_kerr_raymap_render_view): the Kerr shade kernel
-// over the stored records, turned by (rot_c, rot_s), then kerr_raymap_fix_kernel over the map's overflow list as the last part of
-// a partial march under the context's Kerr variant -- it marches those pixels from `cam`, the frame's own camera -- inside one
-// march bracket, then the post-pass as behind a marched Kerr frame.  The ring cell counts the re-march only.
-int32_t kerr_raymap_on_slot(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, int k, int ring, frame_marches *fm, float rot_c, float rot_s) {
-    bhr_frame_slot &f = ctx->slots[k];
-    const bhr_raymap &rm = *ctx->kerr_raymap;
-    BHR_TRY(bhr_frame_begin(ctx, flags));
-    const bhr_march_call call = {cam, flags, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ false, /* ss */ 1, /* keep_start */ false,
-                                 {bhr_variant_of(ctx)}};
-    *fm = {1, 1, false};
-    BHR_TRY(bhr_launch_kerr_raymap_shade(ctx, call, rm.a, rot_c, rot_s));
-    const bhr_march_part part = raymap_fix_part(rm);
-    BHR_TRY(bhr_launch_march(ctx, call, &part));
-    f.march_done = ctx->ring_ev[ring * 3 + 1];
     return post_on_slot(ctx, flags, k, ring);
 }
 
@@ -341,7 +326,7 @@ int32_t bhr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
     cam.t_offset = t_offset;
     if (bhr_have_stars(ctx)) BHR_TRY(bhr_stars_ensure_plane(ctx));   // the build view's star plane, once per (map, catalogue)
     const uint32_t fl = raymap_frame_flags(ctx, flags);
-    return frame_on_next_slot(ctx, fl, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, &cam, fl, k, ring, fm); });
+    return frame_on_next_slot(ctx, fl, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, *ctx->raymap, &cam, fl, k, ring, fm); });
 }
 
 // A frame from the ray map seen from the build camera turned about z (include/bhr.h): bhr_raymap_render's frame in every other
@@ -353,7 +338,7 @@ int32_t bhr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fla
     const bhr_camera view = *cam;
     if (bhr_have_stars(ctx) && rot_c == 1.0f && rot_s == 0.0f) BHR_TRY(bhr_stars_ensure_plane(ctx));   // angle 0: bhr_raymap_render's plane
     const uint32_t fl = raymap_frame_flags(ctx, flags);
-    return frame_on_next_slot(ctx, fl, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, &view, fl, k, ring, fm, rot_c, rot_s); });
+    return frame_on_next_slot(ctx, fl, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, *ctx->raymap, &view, fl, k, ring, fm, rot_c, rot_s); });
 }
 
 // A frame from the Kerr ray map (include/bhr.h): the build camera with the caller's t_offset, under the flags as they are -- the
@@ -365,7 +350,7 @@ int32_t bhr_kerr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     bhr_camera cam = ctx->kerr_raymap->cam;
     cam.t_offset = t_offset;
-    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return kerr_raymap_on_slot(ctx, &cam, flags, k, ring, fm, 1.0f, 0.0f); });
+    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, *ctx->kerr_raymap, &cam, flags, k, ring, fm); });
 }
 
 // ... seen from the build camera turned about z (include/bhr.h): bhr_kerr_raymap_render's frame in every other respect.
@@ -375,7 +360,7 @@ int32_t bhr_kerr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_
     BHR_TRY(bhr_kerr_raymap_check_render(ctx, "bhr_kerr_raymap_render_view", cam, cam->t_offset, flags, &rot_c, &rot_s));
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     const bhr_camera view = *cam;
-    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return kerr_raymap_on_slot(ctx, &view, flags, k, ring, fm, rot_c, rot_s); });
+    return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, *ctx->kerr_raymap, &view, flags, k, ring, fm, rot_c, rot_s); });
 }
 
 // Motion blur from the ray map (include/bhr.h): one frame as the mean of n frames from the map, no march.  A frame like

@@ -261,15 +261,15 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     strict arithmetic whatever ``math`` says, with the Stokes pass behind the shade; ``stokes_path`` then takes the planes, the cell
     grid, the field, Pi_0, the convention and the camera as a compressed .npz (bhr_amd.polarization.write_stokes) and ``ticks_path``
     the frame with a polarisation tick per cell drawn over it (draw_ticks) as a PNG."""
-    check_depth_and_dither(bit_depth, dither)
+    check_depth_and_dither(bit_depth, dither=dither)
     facts = dict(anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus, spin=spin,
                  redshift=redshift, passes=passes_path is not None)      # what the three variant checks take alike
     check_light_delay(light_delay, observer=observer is not None, projection=projection is not None, stars=stars is not None, **facts)
-    check_projection(projection, projection_fov, stars=stars is not None, **facts)
+    check_projection(projection, projection_fov=projection_fov, stars=stars is not None, **facts)
     stars = check_stars(stars, skybox_path=skybox_path, supersample=supersample, spin=spin, redshift=redshift, gpus=gpus,
                         disk_model=disk_model, observer=observer)
     check_observer(observer, **facts)
-    check_passes(passes_path, gpus, supersample, disk_model)
+    check_passes(passes_path, gpus=gpus, supersample=supersample, disk_model=disk_model)
     polarization = check_polarization(polarization, supersample=supersample, disk_model=disk_model, gpus=gpus, spin=spin, redshift=redshift,
                                       observer=observer is not None, projection=projection is not None, light_delay=light_delay is not None,
                                       stokes_path=stokes_path, ticks_path=ticks_path)
@@ -513,22 +513,61 @@ def check_polarization(polarization, video: bool = False, ray_map: bool = False,
     return out
 
 
+# What a video from ONE ray map does not take.  _MAP_REFUSALS: every condition some map mode refuses -- whether the check's
+# keywords ``f`` violate it, and the refusal, with the mode's own words in braces.  _MAPS: per mode those words and the
+# conditions it refuses, in the order it names them (the first one violated is the one raised).
+_MAP_REFUSALS = {
+    "no_spin": (lambda f: f["spin"] == 0 and f["redshift"] == "model",
+                "{flag} needs --spin or --redshift exact: it is the ray map of the Kerr march; a hole that does not spin takes --ray_map or --orbit_map"),
+    "no_video": (lambda f: not f["video"], "{flag} needs --video: it is the ray map of {video}"),
+    "no_orbit": (lambda f: not f["orbit"], "{flag} needs --orbit: a camera that stands still takes --ray_map"),
+    "no_shutter": (lambda f: not f["shutter"] > 0, "{flag} needs --shutter > 0: an instantaneous exposure takes --ray_map or --orbit_map"),
+    "orbit": (lambda f: f["orbit"], "a ray map is one view: {flag} does not combine with --orbit"),
+    "ray_map": (lambda f: f["ray_map"], "{flag} does not combine with --ray_map: that is {other_map}"),
+    "orbit_map": (lambda f: f["orbit_map"], "{flag} does not combine with --orbit_map: that is {other_map}"),
+    "shutter_map": (lambda f: f["shutter_map"], "{flag} does not combine with --shutter_map: that is {other_map}"),
+    "disk_tilt": (lambda f: f["disk_tilt"] != 0, "the orbit is a symmetry of an untilted disk only: {flag} needs --disk_tilt 0"),
+    "orbit_disk_tilt": (lambda f: f["orbit"] and f["disk_tilt"] != 0,
+                        "the orbit is a symmetry of an untilted disk only: {flag} with --orbit needs --disk_tilt 0"),
+    "shutter": (lambda f: f["shutter"] > 0, "shutter frames are marched: {flag} does not combine with --shutter"),
+    "supersample": (lambda f: f["supersample"] not in (None, 1), "{a_map} holds one ray per pixel: {flag} does not combine with --supersample > 1"),
+    "supersample_unset": (lambda f: f["supersample"] != 1, "{a_map} holds one ray per pixel: {flag} does not combine with --supersample > 1"),
+    "map_supersample": (lambda f: f["map_supersample"] != 1, "{a_map} has no supersampled form: {flag} does not combine with --map_supersample > 1"),
+    "disk_model": (lambda f: f["disk_model"] != "texture", "a ray map shades the disk texture: {flag} does not combine with --disk_model v2 / v2_volume"),
+    "gpus": (lambda f: f["gpus"] != 1 or f["world"] != 1, "a ray map lives on one GPU: {flag} does not combine with --gpus > 1 or several ranks"),
+    "observer": (lambda f: f["observer"], "{flag} does not combine with --observer: the observer march is Schwarzschild's"),
+    "projection": (lambda f: f["projection"], "{flag} does not combine with --projection: the projected march is Schwarzschild's"),
+    "light_delay": (lambda f: f["light_delay"], "{flag} does not combine with --light_delay: the delayed march is Schwarzschild's"),
+    "stars": (lambda f: f["stars"], "{flag} does not combine with --stars point: point stars are rendered through the map of Schwarzschild rays"),
+    "polarization": (lambda f: f["polarization"], "{flag} does not combine with --polarization: the transport rule is Schwarzschild's"),
+}
+_MAPS = {
+    "ray_map": dict(flag="--ray_map", a_map="a ray map", refuses="orbit shutter supersample disk_model gpus"),
+    "orbit_map": dict(flag="--orbit_map", a_map="a ray map", video="an orbit video", other_map="the map of a camera that stands still",
+                      refuses="no_video no_orbit ray_map disk_tilt shutter supersample disk_model gpus"),
+    "shutter_map": dict(flag="--shutter_map", a_map="a ray map", other_map="the map of an instantaneous exposure",
+                        refuses="no_shutter ray_map orbit_map orbit_disk_tilt supersample disk_model gpus"),
+    "spin_map": dict(flag="--spin_map", a_map="a Kerr ray map", video="a video", other_map="a map of Schwarzschild rays",
+                     refuses="no_spin no_video shutter supersample_unset map_supersample gpus ray_map orbit_map shutter_map "
+                             "observer projection light_delay stars polarization"),
+}
+
+
+def _check_map(mode: str, f: dict) -> None:
+    """Raises ValueError for the first of the mode's refusals that the keywords ``f`` of its check violate."""
+    words = _MAPS[mode]
+    for condition in words["refuses"].split():
+        violated, refusal = _MAP_REFUSALS[condition]
+        if violated(f):
+            raise ValueError(refusal.format(**words))
+
+
 def check_ray_map(ray_map: bool, orbit: bool = False, shutter: float = 0.0, supersample=1, disk_model: str = "texture",
                   gpus: int = 1, world: int = 1) -> None:
     """What a video from a ray map takes: a camera that stands still, an instantaneous exposure, one ray per pixel, the
     texture disk source, one GPU.  Raises ValueError before any device work."""
-    if not ray_map:
-        return
-    if orbit:
-        raise ValueError("a ray map is one view: --ray_map does not combine with --orbit")
-    if shutter > 0:
-        raise ValueError("shutter frames are marched: --ray_map does not combine with --shutter")
-    if supersample not in (None, 1):
-        raise ValueError("a ray map holds one ray per pixel: --ray_map does not combine with --supersample > 1")
-    if disk_model != "texture":
-        raise ValueError("a ray map shades the disk texture: --ray_map does not combine with --disk_model v2 / v2_volume")
-    if gpus != 1 or world != 1:
-        raise ValueError("a ray map lives on one GPU: --ray_map does not combine with --gpus > 1 or several ranks")
+    if ray_map:
+        _check_map("ray_map", locals())
 
 
 def check_orbit_map(orbit_map: bool, video: bool = True, orbit: bool = True, ray_map: bool = False, disk_tilt: float = 0.0,
@@ -536,24 +575,8 @@ def check_orbit_map(orbit_map: bool, video: bool = True, orbit: bool = True, ray
     """What an orbit video from ONE ray map takes: --video --orbit, a disk that is not tilted (the orbit's turn about z is then
     a symmetry of everything a ray's path depends on), an instantaneous exposure, one ray per pixel, the texture disk source,
     one GPU -- and not --ray_map, which is the map of a camera that stands still.  Raises ValueError before any device work."""
-    if not orbit_map:
-        return
-    if not video:
-        raise ValueError("--orbit_map needs --video: it is the ray map of an orbit video")
-    if not orbit:
-        raise ValueError("--orbit_map needs --orbit: a camera that stands still takes --ray_map")
-    if ray_map:
-        raise ValueError("--orbit_map does not combine with --ray_map: that is the map of a camera that stands still")
-    if disk_tilt != 0:
-        raise ValueError("the orbit is a symmetry of an untilted disk only: --orbit_map needs --disk_tilt 0")
-    if shutter > 0:
-        raise ValueError("shutter frames are marched: --orbit_map does not combine with --shutter")
-    if supersample not in (None, 1):
-        raise ValueError("a ray map holds one ray per pixel: --orbit_map does not combine with --supersample > 1")
-    if disk_model != "texture":
-        raise ValueError("a ray map shades the disk texture: --orbit_map does not combine with --disk_model v2 / v2_volume")
-    if gpus != 1 or world != 1:
-        raise ValueError("a ray map lives on one GPU: --orbit_map does not combine with --gpus > 1 or several ranks")
+    if orbit_map:
+        _check_map("orbit_map", locals())
 
 
 def check_shutter_map(shutter_map: bool, shutter: float = 0.5, orbit: bool = False, ray_map: bool = False, orbit_map: bool = False,
@@ -561,22 +584,8 @@ def check_shutter_map(shutter_map: bool, shutter: float = 0.5, orbit: bool = Fal
     """What a motion-blurred video from ONE ray map takes: an open shutter, one ray per pixel, the texture disk source, one GPU,
     and under --orbit a disk that is not tilted (a camera that stands still takes any disk) -- and neither --ray_map nor
     --orbit_map, which are the maps of instantaneous exposures.  Raises ValueError before any device work."""
-    if not shutter_map:
-        return
-    if not shutter > 0:
-        raise ValueError("--shutter_map needs --shutter > 0: an instantaneous exposure takes --ray_map or --orbit_map")
-    if ray_map:
-        raise ValueError("--shutter_map does not combine with --ray_map: that is the map of an instantaneous exposure")
-    if orbit_map:
-        raise ValueError("--shutter_map does not combine with --orbit_map: that is the map of an instantaneous exposure")
-    if orbit and disk_tilt != 0:
-        raise ValueError("the orbit is a symmetry of an untilted disk only: --shutter_map with --orbit needs --disk_tilt 0")
-    if supersample not in (None, 1):
-        raise ValueError("a ray map holds one ray per pixel: --shutter_map does not combine with --supersample > 1")
-    if disk_model != "texture":
-        raise ValueError("a ray map shades the disk texture: --shutter_map does not combine with --disk_model v2 / v2_volume")
-    if gpus != 1 or world != 1:
-        raise ValueError("a ray map lives on one GPU: --shutter_map does not combine with --gpus > 1 or several ranks")
+    if shutter_map:
+        _check_map("shutter_map", locals())
 
 
 def check_spin_map(spin_map: bool, spin: float = 0.0, redshift: str = "model", video: bool = True, shutter: float = 0.0, supersample=1,
@@ -587,31 +596,41 @@ def check_spin_map(spin_map: bool, spin: float = 0.0, redshift: str = "model", v
     -- under --orbit turned about the spin axis to the frame's camera.  It needs a spin or the exact redshift (the Kerr march),
     a video, an instantaneous exposure, one ray per pixel and one GPU, and none of the Schwarzschild maps or of what a spin
     refuses anyway.  Raises ValueError naming --spin_map and the other flag, before any device work."""
-    if not spin_map:
-        return
-    if spin == 0 and redshift == "model":
-        raise ValueError("--spin_map needs --spin or --redshift exact: it is the ray map of the Kerr march; a hole that does not spin "
-                         "takes --ray_map or --orbit_map")
-    if not video:
-        raise ValueError("--spin_map needs --video: it is the ray map of a video")
-    if shutter > 0:
-        raise ValueError("shutter frames are marched: --spin_map does not combine with --shutter")
-    if supersample != 1:
-        raise ValueError("a Kerr ray map holds one ray per pixel: --spin_map does not combine with --supersample > 1")
-    if map_supersample != 1:
-        raise ValueError("a Kerr ray map has no supersampled form: --spin_map does not combine with --map_supersample > 1")
-    if gpus != 1 or world != 1:
-        raise ValueError("a ray map lives on one GPU: --spin_map does not combine with --gpus > 1 or several ranks")
-    for on, flag in ((ray_map, "--ray_map"), (orbit_map, "--orbit_map"), (shutter_map, "--shutter_map")):
-        if on:
-            raise ValueError(f"--spin_map does not combine with {flag}: that is a map of Schwarzschild rays")
-    for on, flag, why in ((observer, "--observer", "the observer march is Schwarzschild's"),
-                          (projection, "--projection", "the projected march is Schwarzschild's"),
-                          (light_delay, "--light_delay", "the delayed march is Schwarzschild's"),
-                          (stars, "--stars point", "point stars are rendered through the map of Schwarzschild rays"),
-                          (polarization, "--polarization", "the transport rule is Schwarzschild's")):
-        if on:
-            raise ValueError(f"--spin_map does not combine with {flag}: {why}")
+    if spin_map:
+        _check_map("spin_map", locals())
+
+
+# A video's map as render_video drives it: per mode the build of its one map, with the line it prints, the frame from it and the
+# free.  fr: the frame's camera and, under a shutter, its samples.  (The build view needs no entry: frame 0 of the orbit under
+# ``orbit``, else the camera that stands still -- ray_map has no orbit and orbit_map always one, by their checks.)
+def _build_map(label: str):
+    def build(renderer, cam_pos, fov, map_supersample):
+        renderer.build_ray_map(cam_pos, fov, supersample=map_supersample)
+        info = renderer.ray_map_info()
+        print(f"  {label} built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
+    return build
+
+
+def _build_kerr_map(renderer, cam_pos, fov, map_supersample):
+    renderer.build_kerr_ray_map(cam_pos, fov)
+    info = renderer.kerr_ray_map_info()
+    print(f"  Kerr ray map built (spin {info['spin']:g}, {info['redshift']} redshift): {info['slots']} slots, {info['overflow_pixels']} overflow pixels, "
+          f"{info['device_bytes'] / 1e6:.0f} MB")
+
+
+_MAP_MODES = {
+    # the same frame from the map: shade, no march
+    "ray_map": dict(build=_build_map("ray map"), free="free_ray_map", frame=lambda r, fr: r.render_from_ray_map_async(frame=0)),
+    # the map turned to the frame's camera
+    "orbit_map": dict(build=_build_map("orbit ray map"), free="free_ray_map",
+                      frame=lambda r, fr: r.render_from_ray_map_async(frame=0, cam_pos=fr["cam_pos"], fov=fr["fov"])),
+    # the marched shutter loop's samples from the map
+    "shutter_map": dict(build=_build_map("shutter ray map"), free="free_ray_map",
+                        frame=lambda r, fr: r.render_shutter_from_ray_map_async(fr["t_offsets"], fr["positions"] if fr["orbit"] else None, fr["fov"])),
+    # the Kerr map; an orbit frame turned to its camera
+    "spin_map": dict(build=_build_kerr_map, free="free_kerr_ray_map",
+                     frame=lambda r, fr: r.render_from_kerr_ray_map_async(frame=0, cam_pos=fr["cam_pos"] if fr["orbit"] else None)),
+}
 
 
 def _lib_max_png_width(bit_depth: int = 8) -> int:
@@ -964,9 +983,11 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     projected = projection is not None or projection_fov is not None
     disk_model = "texture" if getattr(renderer, "_dv2", None) is None else "v2"
     if spin_map:                                                # (without it the renderer is not asked anything, as ever)
-        check_spin_map(spin_map, renderer.spin, renderer.redshift, True, shutter, renderer.supersample if supersample is None else supersample,
-                       map_supersample, 1, world, ray_map, orbit_map, shutter_map, moving, projected, light_delay is not None,
-                       stars is not None, polarization is not None or stokes_path is not None)
+        check_spin_map(spin_map, spin=renderer.spin, redshift=renderer.redshift, video=True, shutter=shutter,
+                       supersample=renderer.supersample if supersample is None else supersample, map_supersample=map_supersample, world=world,
+                       ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map, observer=moving, projection=projected,
+                       light_delay=light_delay is not None, stars=stars is not None,
+                       polarization=polarization is not None or stokes_path is not None)
     if moving or projected or light_delay is not None:
         # what the three variant checks take from the renderer and the call
         thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
@@ -983,11 +1004,11 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         plan = obs_mod.frame_plan(n_frames, static_cam_pos, observer, observer_velocity, orbit, orbit_degrees, infall_to)
     proj = None
     if projected:
-        proj = check_projection(projection, projection_fov, world=world, stars=stars is not None, **facts)
+        proj = check_projection(projection, projection_fov=projection_fov, world=world, stars=stars is not None, **facts)
     if light_delay is not None:
         light_delay = check_light_delay(light_delay, world=world, observer=moving, projection=projected, stars=stars is not None, **facts)
-    check_map_supersample(map_supersample, ray_map, orbit_map, shutter_map)
-    check_shutter(shutter, shutter_samples)
+    check_map_supersample(map_supersample, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map)
+    check_shutter(shutter, shutter_samples=shutter_samples)
     if polarization is not None or stokes_path is not None:     # (without one the renderer is not asked anything, as ever)
         polarization = check_polarization(polarization, video=True, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map, shutter=shutter,
                                           supersample=renderer.supersample if supersample is None else supersample,
@@ -996,18 +1017,22 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                                           stokes_path=stokes_path)
     if video_stream not in ("auto", "y4m", "off"):
         raise ValueError(f"video_stream must be 'auto', 'y4m' or 'off', got {video_stream!r}")
-    hdr = check_video_hdr(video_hdr, hdr_white, hdr_exposure, width, height, world, video_codec, video_stream)
+    hdr = check_video_hdr(video_hdr, hdr_white=hdr_white, hdr_exposure=hdr_exposure, width=width, height=height, world=world,
+                          video_codec=video_codec, video_stream=video_stream)
     grade = check_grade(grade)
     if grade is not None:
         grade["keep_hdr"] = False
     if shutter_map:
-        check_shutter_map(shutter_map, shutter, orbit, ray_map, orbit_map, renderer.disk_tilt,
-                          renderer.supersample if supersample is None else supersample, disk_model, 1, world)
+        check_shutter_map(shutter_map, shutter=shutter, orbit=orbit, ray_map=ray_map, orbit_map=orbit_map, disk_tilt=renderer.disk_tilt,
+                          supersample=renderer.supersample if supersample is None else supersample, disk_model=disk_model, world=world)
     if orbit_map:
-        check_orbit_map(orbit_map, True, orbit, ray_map, renderer.disk_tilt, shutter,
-                        renderer.supersample if supersample is None else supersample, disk_model, 1, world)
+        check_orbit_map(orbit_map, video=True, orbit=orbit, ray_map=ray_map, disk_tilt=renderer.disk_tilt, shutter=shutter,
+                        supersample=renderer.supersample if supersample is None else supersample, disk_model=disk_model, world=world)
     if ray_map:
-        check_ray_map(ray_map, orbit, shutter, renderer.supersample if supersample is None else supersample, disk_model, 1, world)
+        check_ray_map(ray_map, orbit=orbit, shutter=shutter, supersample=renderer.supersample if supersample is None else supersample,
+                      disk_model=disk_model, world=world)
+    # the checks have refused every combination of two: the video's one map, or none
+    mode = next((m for m, on in (("ray_map", ray_map), ("orbit_map", orbit_map), ("shutter_map", shutter_map), ("spin_map", spin_map)) if on), None)
     # point stars: the renderer carries the catalogue (make_renderer(stars=)); the frames that show it are the map's
     if stars is not None:
         stars = check_stars(stars, supersample=renderer.supersample if supersample is None else supersample, spin=renderer.spin,
@@ -1024,7 +1049,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             raise ValueError("point stars: the renderer has no star catalogue (make_renderer(stars=...) sets it)")
     if video_codec not in VIDEO_CODECS:
         raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
-    check_depth_and_dither(bit_depth, dither, video_codec)
+    check_depth_and_dither(bit_depth, dither=dither, video_codec=video_codec)
     mjpeg = video_codec == "mjpeg"
     if mjpeg and not (isinstance(video_quality, int) and 1 <= video_quality <= 100):
         raise ValueError(f"video_quality must be an integer between 1 and 100, got {video_quality!r}")
@@ -1142,105 +1167,84 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     factories = init_lifecycle_system(renderer, n_r, n_phi, seed=42)
     dt = disk_rotation_speed
     print(f"  lifecycle system ready (n_r={n_r}, n_phi={n_phi}), rank {rank}/{world}")
-    if ray_map:
-        renderer.build_ray_map(static_cam_pos, fov, supersample=map_supersample)     # the one march of the video
-        info = renderer.ray_map_info()
-        print(f"  ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
+    if mode is not None:
+        # the one march of the video.  A camera that stands still: its view; an orbit: frame 0's (the orbit's radius is |pov|, not
+        # the pov's xy norm: not the pov itself), which every frame's camera is a turn of about z
+        _MAP_MODES[mode]["build"](renderer, orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov, map_supersample)
     stokes_grids = {}
     if polarization is not None:
         renderer.set_polarization(**polarization)
-    if orbit_map:
-        # the orbit's radius is |pov|, not the pov's xy norm: frame 0 of the orbit, not the pov itself
-        renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees), fov, supersample=map_supersample)     # the one march of the video
-        info = renderer.ray_map_info()
-        print(f"  orbit ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
-    if shutter_map:
-        renderer.build_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov,
-                               supersample=map_supersample)   # the one march of the video
-        info = renderer.ray_map_info()
-        print(f"  shutter ray map built: {info['slots']} slots, {info['overflow_pixels']} overflow pixels, {info['device_bytes'] / 1e6:.0f} MB")
-    if spin_map:
-        # a camera that stands still: its view; an orbit: frame 0's, which every frame's camera is a turn of about the spin axis
-        renderer.build_kerr_ray_map(orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov)   # the one march of the video
-        info = renderer.kerr_ray_map_info()
-        print(f"  Kerr ray map built (spin {info['spin']:g}, {info['redshift']} redshift): {info['slots']} slots, {info['overflow_pixels']} overflow pixels, "
-              f"{info['device_bytes'] / 1e6:.0f} MB")
     t_loop0 = time.time()                               # ``stats`` (bench.py): the one-off set-up apart from the frame loop
 
-    try:                                                # (a polarisation set above does not outlive a frame loop that raises)
-        for frame in range(n_frames):
-            t = frame * dt
-            mine = frame % world == rank and frame not in completed
-            # the factories advance on every frame index on every rank; statistics are a function of the
-            # frame index (every 60th), texture composition only happens for frames rendered here
-            advance_lifecycle_frame(renderer, factories, t, dt, recompute_stats=(frame % 60 == 0), compose=mine)
-            if not mine:
-                continue
-            cam_pos = orbit_position(static_cam_pos, frame, n_frames, orbit_degrees) if orbit else static_cam_pos
-            if plan is not None:
-                cam_pos, beta = plan[frame]                    # the moving observer: the frame's position and its velocity there
-            t0 = time.time()
-            if shutter > 0:
-                times = shutter_times(frame, shutter, shutter_samples)
-                positions = [orbit_position(static_cam_pos, u, n_frames, orbit_degrees) if orbit else static_cam_pos for u in times]
-                t_offsets = [(u - frame) * disk_rotation_speed for u in times]
-                if shutter_map:                                # the same samples from the map: shade, no march
-                    renderer.render_shutter_from_ray_map_async(t_offsets, positions if orbit else None, fov)
-                else:
-                    renderer.render_shutter_async(positions, fov, t_offsets)
-            elif ray_map:
-                renderer.render_from_ray_map_async(frame=0)    # the same frame from the map: shade, no march
-                if polarization is not None:
-                    stokes_grids[frame] = renderer.stokes_cells()      # the frame's cell grid (synchronises: a few kB per frame)
-            elif orbit_map:
-                renderer.render_from_ray_map_async(frame=0, cam_pos=cam_pos, fov=fov)    # the map turned to the frame's camera
-            elif spin_map:                                     # the Kerr map: shade, no march; an orbit frame turned to its camera
-                renderer.render_from_kerr_ray_map_async(frame=0, cam_pos=cam_pos if orbit else None)
-            else:                                              # marched: the frame of the moving camera, through the projection, with light delay
-                renderer.render_async(cam_pos, fov, frame=0, observer=None if plan is None else beta, observer_sky=observer_sky,
-                                      projection=projection, projection_fov=projection_fov, light_delay=light_delay)   # (lens flare: on the device)
-            sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))
-            if stream is not None:
-                try:
-                    stream.submit()
-                except Exception as e:                      # the encoder went away (EPIPE): the PNG frames carry on
-                    stream, encoder = _drop_stream(stream, encoder, e), None
-            elapsed = time.time() - t0
-            rendered += 1
-            submitted.append(frame)
-            if rendered % 50 == 0 or frame >= n_frames - world:
-                sink.drain()                                # progress.json only lists frames that are on disk
-                completed.update(submitted)
-                submitted.clear()
-                with open(progress_file, "w") as f:
-                    json.dump({"params": params, "completed": sorted(completed)}, f)
-            if rendered % 100 == 0 or frame == n_frames - 1:
-                print(f"  frame {frame}/{n_frames} {elapsed * 1e3:.1f} ms, done {len(completed)}")
-    finally:
+    # (the map, a polarisation set above and the renderer's outputs, dither and grade do not outlive a frame loop that raises)
+    try:
+        try:
+            for frame in range(n_frames):
+                t = frame * dt
+                mine = frame % world == rank and frame not in completed
+                # the factories advance on every frame index on every rank; statistics are a function of the
+                # frame index (every 60th), texture composition only happens for frames rendered here
+                advance_lifecycle_frame(renderer, factories, t, dt, recompute_stats=(frame % 60 == 0), compose=mine)
+                if not mine:
+                    continue
+                cam_pos = orbit_position(static_cam_pos, frame, n_frames, orbit_degrees) if orbit else static_cam_pos
+                if plan is not None:
+                    cam_pos, beta = plan[frame]                    # the moving observer: the frame's position and its velocity there
+                t0 = time.time()
+                fr = dict(cam_pos=cam_pos, fov=fov, orbit=orbit)
+                if shutter > 0:
+                    times = shutter_times(frame, shutter, shutter_samples)
+                    fr["positions"] = [orbit_position(static_cam_pos, u, n_frames, orbit_degrees) if orbit else static_cam_pos for u in times]
+                    fr["t_offsets"] = [(u - frame) * disk_rotation_speed for u in times]
+                if mode is not None:                               # from the video's map: shade, no march
+                    _MAP_MODES[mode]["frame"](renderer, fr)
+                    if polarization is not None:                   # (ray_map only: check_polarization)
+                        stokes_grids[frame] = renderer.stokes_cells()      # the frame's cell grid (synchronises: a few kB per frame)
+                elif shutter > 0:
+                    renderer.render_shutter_async(fr["positions"], fov, fr["t_offsets"])
+                else:                                              # marched: the frame of the moving camera, through the projection, with light delay
+                    renderer.render_async(cam_pos, fov, frame=0, observer=None if plan is None else beta, observer_sky=observer_sky,
+                                          projection=projection, projection_fov=projection_fov, light_delay=light_delay)   # (lens flare: on the device)
+                sink.submit(os.path.join(temp_dir, f"frame_{frame:04d}{ext}"))
+                if stream is not None:
+                    try:
+                        stream.submit()
+                    except Exception as e:                      # the encoder went away (EPIPE): the PNG frames carry on
+                        stream, encoder = _drop_stream(stream, encoder, e), None
+                elapsed = time.time() - t0
+                rendered += 1
+                submitted.append(frame)
+                if rendered % 50 == 0 or frame >= n_frames - world:
+                    sink.drain()                                # progress.json only lists frames that are on disk
+                    completed.update(submitted)
+                    submitted.clear()
+                    with open(progress_file, "w") as f:
+                        json.dump({"params": params, "completed": sorted(completed)}, f)
+                if rendered % 100 == 0 or frame == n_frames - 1:
+                    print(f"  frame {frame}/{n_frames} {elapsed * 1e3:.1f} ms, done {len(completed)}")
+        finally:
+            if polarization is not None:
+                renderer.set_polarization(None)
+        frames_written, bytes_written = sink.drain()
+        sink.close()
         if polarization is not None:
-            renderer.set_polarization(None)
-
-    frames_written, bytes_written = sink.drain()
-    sink.close()
-    if polarization is not None:
-        from .polarization import write_stokes
-        path = stokes_path if stokes_path is not None else os.path.splitext(output_path)[0] + ".stokes.npz"
-        # one GPU and no resume (check_polarization, above): every frame was rendered here, so every grid is here
-        if len(stokes_grids) != n_frames:
-            raise RuntimeError(f"polarization: {len(stokes_grids)} cell grids for {n_frames} frames; {path} is not written")
-        write_stokes(path, np.stack([stokes_grids[f] for f in range(n_frames)]), polarization["cell"], polarization["field"],
-                     polarization["fraction"], camera=dict(cam_pos=list(static_cam_pos), fov=fov))
-        print(f"Saved: {path} ({n_frames} cell grids of {polarization['cell']}-pixel cells)")
-    if ray_map or orbit_map or shutter_map:
-        renderer.free_ray_map()
-    if spin_map:
-        renderer.free_kerr_ray_map()
-    if mjpeg:
-        renderer.set_outputs(outputs_before)
-    if dither != dither_before:
-        renderer.set_dither(dither_before)
-    if grade is not None:
-        renderer.set_grade(**(grade_before or {}))
+            from .polarization import write_stokes
+            path = stokes_path if stokes_path is not None else os.path.splitext(output_path)[0] + ".stokes.npz"
+            # one GPU and no resume (check_polarization, above): every frame was rendered here, so every grid is here
+            if len(stokes_grids) != n_frames:
+                raise RuntimeError(f"polarization: {len(stokes_grids)} cell grids for {n_frames} frames; {path} is not written")
+            write_stokes(path, np.stack([stokes_grids[f] for f in range(n_frames)]), polarization["cell"], polarization["field"],
+                         polarization["fraction"], camera=dict(cam_pos=list(static_cam_pos), fov=fov))
+            print(f"Saved: {path} ({n_frames} cell grids of {polarization['cell']}-pixel cells)")
+    finally:
+        if mode is not None:
+            getattr(renderer, _MAP_MODES[mode]["free"])()
+        if mjpeg:
+            renderer.set_outputs(outputs_before)
+        if dither != dither_before:
+            renderer.set_dither(dither_before)
+        if grade is not None:
+            renderer.set_grade(**(grade_before or {}))
     if stats is not None:
         stats.update(setup_s=t_loop0 - total_t0, loop_s=time.time() - t_loop0, frames=rendered)
     streamed = False

@@ -534,6 +534,29 @@ class HipRenderer:
         return self.read_layer(_lib.LAYER_FINAL)
 
     # ------------------------------------------------------------------ ray map
+    def _map_frame_flags(self, skip_bloom: bool, lens_flare) -> int:
+        """The flag word of a frame from either map: the lens flare as render_async decides it."""
+        flare = self.lens_flare if lens_flare is None else lens_flare
+        return (_lib.SKIP_BLOOM if skip_bloom else 0) | (_lib.LENS_FLARE if flare else 0)
+
+    def _map_planes(self, read_fn, h: int, w: int, k: int, nc: int) -> dict:
+        """A map's planes through its read entry point, (h, w) pixels with k records of nc floats each."""
+        def read(which, shape, dtype):
+            out = np.empty(shape, dtype=dtype)
+            _lib.check(read_fn(self._ctx, which, out.ctypes.data, out.nbytes))
+            return out
+        return {"steps": read(_lib.RAYMAP_STEPS, (h, w), np.int32), "status": read(_lib.RAYMAP_STATUS, (h, w), np.int32),
+                "escape_dir": read(_lib.RAYMAP_ESCAPE_DIR, (h, w, 3), np.float32),
+                "crossings": read(_lib.RAYMAP_CROSSINGS, (h, w), np.int32), "hits": read(_lib.RAYMAP_HITS, (k, h, w, nc), np.float32)}
+
+    @staticmethod
+    def _map_info(info, names) -> dict:
+        """The integer fields `names` of a map's info struct, and the build camera's pos / r_escape."""
+        out = {name: int(getattr(info, name)) for name in names}
+        out["cam_pos"] = [float(v) for v in info.cam.pos]
+        out["r_escape"] = float(info.cam.r_escape)
+        return out
+
     def build_ray_map(self, cam_pos, fov: float, skip_differentials: bool = False, supersample: int = 1) -> None:
         """March the view once with the strict arithmetic and keep what the march finds before it shades anything
         (bhr_raymap_build; include/bhr.h states the map).  The slot count is option "raymap_slots" (1..8, default 4).
@@ -560,9 +583,7 @@ class HipRenderer:
         render_async(cam_pos, ...) -- as far from it as two strict marches of symmetric views are from each other; at the
         build's own position it is the frame described above, bit for bit."""
         t = float(frame) * self.disk_rotation_speed if t_offset is None else float(t_offset)
-        flags = _lib.SKIP_BLOOM if skip_bloom else 0
-        if self.lens_flare if lens_flare is None else lens_flare:
-            flags |= _lib.LENS_FLARE
+        flags = self._map_frame_flags(skip_bloom, lens_flare)
         if cam_pos is not None:
             if fov is None:
                 raise ValueError("render_from_ray_map_async: cam_pos needs fov")
@@ -598,9 +619,7 @@ class HipRenderer:
         else:
             for j, (pos, t) in enumerate(zip(cam_positions, t_offsets)):
                 cams[j] = self.camera_uniforms(pos, fov, t_offset=t)
-        flags = _lib.SKIP_BLOOM if skip_bloom else 0
-        if self.lens_flare if lens_flare is None else lens_flare:
-            flags |= _lib.LENS_FLARE
+        flags = self._map_frame_flags(skip_bloom, lens_flare)
         _lib.check(self._lib.bhr_raymap_render_shutter(self._ctx, cams, len(t_offsets), flags))
 
     def ray_map_info(self) -> dict:
@@ -609,11 +628,8 @@ class HipRenderer:
         camera's pos / r_escape."""
         info = _lib.RayMapInfo()
         _lib.check(self._lib.bhr_raymap_get_info(self._ctx, C.byref(info)))
-        out = {name: int(getattr(info, name)) for name in ("built", "diff", "slots", "width", "rows", "supersample", "crossings_stored",
-                                                           "overflow_pixels", "device_bytes", "ray_steps")}
-        out["cam_pos"] = [float(v) for v in info.cam.pos]
-        out["r_escape"] = float(info.cam.r_escape)
-        return out
+        return self._map_info(info, ("built", "diff", "slots", "width", "rows", "supersample", "crossings_stored", "overflow_pixels",
+                                     "device_bytes", "ray_steps"))
 
     def ray_map_passes(self) -> dict:
         """The map's planes as NumPy arrays in (H, W[, ...]) order -- of the fine frame, (k H, k W[, ...]), for a map with
@@ -626,15 +642,7 @@ class HipRenderer:
         if not info["built"]:
             raise AssertionError("no ray map has been built (build_ray_map)")
         ss = max(info["supersample"], 1)
-        h, w, k, nc = info["rows"] * ss, info["width"] * ss, info["slots"], 9 if info["diff"] else 5
-
-        def read(which, shape, dtype):
-            out = np.empty(shape, dtype=dtype)
-            _lib.check(self._lib.bhr_raymap_read(self._ctx, which, out.ctypes.data, out.nbytes))
-            return out
-        passes = {"steps": read(_lib.RAYMAP_STEPS, (h, w), np.int32), "status": read(_lib.RAYMAP_STATUS, (h, w), np.int32),
-                  "escape_dir": read(_lib.RAYMAP_ESCAPE_DIR, (h, w, 3), np.float32),
-                  "crossings": read(_lib.RAYMAP_CROSSINGS, (h, w), np.int32), "hits": read(_lib.RAYMAP_HITS, (k, h, w, nc), np.float32)}
+        passes = self._map_planes(self._lib.bhr_raymap_read, info["rows"] * ss, info["width"] * ss, info["slots"], 9 if info["diff"] else 5)
         passes["hit_r"], passes["hit_phi"] = hit_polar(passes["hits"], passes["crossings"])
         return passes
 
@@ -664,9 +672,7 @@ class HipRenderer:
         the frame is the Kerr march of the build view's rays, NOT bit-identical to render_async(cam_pos, ...); at the build's own
         position it is the frame described above, bit for bit."""
         t = float(frame) * self.disk_rotation_speed if t_offset is None else float(t_offset)
-        flags = _lib.SKIP_BLOOM if skip_bloom else 0
-        if self.lens_flare if lens_flare is None else lens_flare:
-            flags |= _lib.LENS_FLARE
+        flags = self._map_frame_flags(skip_bloom, lens_flare)
         if cam_pos is not None:
             fov = getattr(self, "_kerr_map_fov", None)
             if fov is None:
@@ -682,12 +688,9 @@ class HipRenderer:
         the build camera's pos / r_escape."""
         info = _lib.KerrRayMapDesc()
         _lib.check(self._lib.bhr_kerr_raymap_info(self._ctx, C.byref(info)))
-        out = {name: int(getattr(info, name)) for name in ("built", "slots", "width", "rows", "crossings_stored", "overflow_pixels",
-                                                           "device_bytes", "ray_steps")}
+        out = self._map_info(info, ("built", "slots", "width", "rows", "crossings_stored", "overflow_pixels", "device_bytes", "ray_steps"))
         out["spin"] = float(info.spin)
         out["redshift"] = "exact" if info.redshift == _lib.REDSHIFT_EXACT else "model"
-        out["cam_pos"] = [float(v) for v in info.cam.pos]
-        out["r_escape"] = float(info.cam.r_escape)
         return out
 
     def kerr_ray_map_passes(self) -> dict:
@@ -697,15 +700,7 @@ class HipRenderer:
         info = self.kerr_ray_map_info()
         if not info["built"]:
             raise AssertionError("no Kerr ray map has been built (build_kerr_ray_map)")
-        h, w, k = info["rows"], info["width"], info["slots"]
-
-        def read(which, shape, dtype):
-            out = np.empty(shape, dtype=dtype)
-            _lib.check(self._lib.bhr_kerr_raymap_read(self._ctx, which, out.ctypes.data, out.nbytes))
-            return out
-        return {"steps": read(_lib.RAYMAP_STEPS, (h, w), np.int32), "status": read(_lib.RAYMAP_STATUS, (h, w), np.int32),
-                "escape_dir": read(_lib.RAYMAP_ESCAPE_DIR, (h, w, 3), np.float32),
-                "crossings": read(_lib.RAYMAP_CROSSINGS, (h, w), np.int32), "hits": read(_lib.RAYMAP_HITS, (k, h, w, 5), np.float32)}
+        return self._map_planes(self._lib.bhr_kerr_raymap_read, info["rows"], info["width"], info["slots"], 5)
 
     def free_kerr_ray_map(self) -> None:
         """Release the Kerr ray map's device memory (bhr_kerr_raymap_free); close() does it too."""

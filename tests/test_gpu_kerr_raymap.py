@@ -352,3 +352,57 @@ def test_video(orbit, tmp_path, hip_lib, capsys):
     assert "starting over" in capsys.readouterr().out and "spin_map" not in rec2["params"]
     assert again == marched
     r.close()
+
+
+# ---- 7. both maps through one context -------------------------------------------------------------------------------------------------
+def test_both_maps_through_one_context(hip_lib):
+    """A context holds a Schwarzschild map and a Kerr map side by side, and building, rebuilding or freeing one leaves the other
+    as it was: its info field for field, its frames bit for bit.  The smallest ragged frame with no side a multiple of 8; with one
+    slot per pixel both maps have pixels on the overflow list and pixels off it, so the fix launch of both kinds runs."""
+    w, h = min((s for s in KC.RAGGED_SIZES if s[0] % 8 and s[1] % 8), key=lambda s: s[0] * s[1], default=(61, 37))
+    view, fov = list(KC.VIEWS[0]), KC.FOV
+    r = _mk(0.0, width=w, height=h)
+    # 1. the Schwarzschild map at spin 0, one slot
+    r.set_option("raymap_slots", 1)
+    r.build_ray_map(view, fov, skip_differentials=True)
+    r.render_from_ray_map_async(frame=3)
+    S = _read(r)
+    r.render_async(view, fov, frame=3, skip_differentials=True)
+    _assert_equal(S, _read(r), "the Schwarzschild map's frame")
+    schw = r.ray_map_info()
+    assert schw["built"] == 1 and schw["slots"] == 1 and 0 < schw["overflow_pixels"] < w * h, schw
+    # 2. the Kerr map beside it, under both redshifts
+    r.set_spin(0.6)
+    for redshift in ("model", "exact"):
+        r.set_redshift(redshift)
+        r.build_kerr_ray_map(view, fov)
+        r.render_from_kerr_ray_map_async()
+        K = _read(r)
+        r.render_async(view, fov)
+        _assert_equal(K, _read(r), f"the Kerr map's frame, {redshift} redshift")
+        kerr1 = r.kerr_ray_map_info()
+        assert kerr1["built"] == 1 and kerr1["slots"] == 1 and kerr1["redshift"] == redshift and 0 < kerr1["overflow_pixels"] < w * h, kerr1
+        # 3. the Schwarzschild map is as it was
+        assert r.ray_map_info() == schw
+    # 4. four slots: three more records of 5 floats per pixel, and nothing else
+    r.set_option("raymap_slots", 4)
+    r.build_kerr_ray_map(view, fov)
+    kerr4 = r.kerr_ray_map_info()
+    assert kerr4["slots"] == 4 and kerr4["device_bytes"] - kerr1["device_bytes"] == 3 * 5 * w * h * 4
+    r.render_from_kerr_ray_map_async()
+    _assert_equal(_read(r), K, "the Kerr map's frame, four slots")
+    assert r.ray_map_info() == schw
+    # 5. the Kerr map freed, the Schwarzschild map stays
+    r.free_kerr_ray_map()
+    gone = r.kerr_ray_map_info()
+    assert gone["built"] == 0 and gone["device_bytes"] == 0
+    assert r.ray_map_info() == schw
+    # 6. ... and still gives its frame once the spin is off
+    r.set_redshift("model")
+    r.set_spin(0.0)
+    r.render_from_ray_map_async(frame=3)
+    _assert_equal(_read(r), S, "the Schwarzschild map's frame behind the Kerr map's life")
+    # 7. both gone
+    r.free_ray_map()
+    assert r.ray_map_info()["built"] == 0 and r.kerr_ray_map_info()["built"] == 0
+    r.close()
