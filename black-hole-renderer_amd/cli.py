@@ -130,6 +130,13 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "per frame into one .npz.  The angle is counted from image-right towards image-up.  Not with --spin, "
                         "--redshift exact, the observer flags, --projection, --light_delay, --orbit_map, --shutter_map, --shutter, "
                         "--map_supersample > 1, --supersample > 1, --disk_model v2 / v2_volume, --gpus > 1, or a video without --ray_map")
+    p.add_argument("--spin_polarization", type=str, nargs="+", default=argparse.SUPPRESS, metavar="FIELD",
+                   help="--polarization for a spinning hole: the Stokes Q / U maps carried along each Kerr ray by the Walker-Penrose "
+                        "constant.  FIELD as for --polarization.  Needs --spin (or --redshift exact); a still image builds a Kerr ray "
+                        "map of the view and renders the frame from it; --video needs --spin_map and no --orbit.  Works with both "
+                        "--redshift modes, --lens_flare and the grade; --polarization_fraction, --polarization_cell, --stokes_output "
+                        "and --polarization_ticks serve it as they serve --polarization (the .npz also holds spin and redshift).  Not "
+                        "with --polarization, --supersample > 1 or anything --spin_map refuses")
     p.add_argument("--polarization_fraction", type=float, default=argparse.SUPPRESS, metavar="PI0",
                    help="--polarization: the degree of polarisation of light emitted across the field, in [0, 1] (default: 0.7)")
     p.add_argument("--polarization_cell", type=int, default=argparse.SUPPRESS, metavar="C",
@@ -275,8 +282,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                          ("--observer_sky", args.observer_sky is not None), ("--infall_to", args.infall_to is not None),
                          ("--projection", args.projection != "perspective" or args.projection_fov is not None),
                          ("--light_delay", hasattr(args, "light_delay")), ("--stars point", args.stars == "point"),
-                         ("--polarization", any(hasattr(args, n) for n in ("polarization", "polarization_fraction", "polarization_cell",
-                                                                           "stokes_output", "polarization_ticks")))):
+                         # (its four companions count as --polarization's unless --spin_polarization, which they serve too, is there)
+                         ("--polarization", hasattr(args, "polarization") or (not hasattr(args, "spin_polarization") and any(
+                             hasattr(args, n) for n in ("polarization_fraction", "polarization_cell", "stokes_output", "polarization_ticks"))))):
             if on:
                 p.error(f"--spin_map does not combine with {flag}: it is a Schwarzschild march's or the Schwarzschild ray map's")
     if args.spin != 0 or args.redshift == "exact":
@@ -516,8 +524,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     # polarisation, behind every refusal above, light delay's included: a line that was refused without --polarization is refused
     # with the same words.  Its five options have no default in the namespace: they are there only when the flag was given
     pol = getattr(args, "polarization", None)
+    spin_pol = getattr(args, "spin_polarization", None)
     for flag in ("polarization_fraction", "polarization_cell", "stokes_output", "polarization_ticks"):
-        if pol is None and getattr(args, flag, None) is not None:
+        if pol is None and spin_pol is None and getattr(args, flag, None) is not None:
             p.error(f"--{flag} needs --polarization: it belongs to the Stokes maps")
     if pol is not None:
         who = "--polarization"
@@ -553,6 +562,47 @@ def parse_args(argv=None) -> argparse.Namespace:
             p.error(f"{who} does not combine with --gpus other than 1: a ray map lives on one GPU")
         if args.video and not args.ray_map:
             p.error(f"{who} with --video needs --ray_map: the Stokes planes come from the ray map of a camera that stands still")
+        if args.video and getattr(args, "polarization_ticks", None) is not None:
+            p.error("--polarization_ticks is a still image's overlay: it does not combine with --video (the cell grids go to --stokes_output)")
+        if not getattr(args, "stokes_output", "x.npz").lower().endswith(".npz"):
+            p.error(f"--stokes_output writes a .npz file, got {args.stokes_output!r}")
+        if not getattr(args, "polarization_ticks", "x.png").lower().endswith(".png"):
+            p.error(f"--polarization_ticks writes a .png file, got {args.polarization_ticks!r}")
+    # the Kerr polarisation (drivers.check_kerr_polarization has the same refusals), behind --polarization's: each names --spin_polarization
+    if spin_pol is not None:
+        who = "--spin_polarization"
+        from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check, parse_field
+        try:
+            check(parse_field(spin_pol), getattr(args, "polarization_fraction", DEFAULT_FRACTION), getattr(args, "polarization_cell", DEFAULT_CELL))
+        except ValueError as e:
+            p.error(f"{who}: {e}")
+        if pol is not None:
+            p.error(f"{who} does not combine with --polarization: that is the hole that does not spin")
+        if args.spin == 0 and args.redshift == "model":
+            p.error(f"{who} needs --spin or --redshift exact: it is the polarisation of the Kerr march; a hole that does not spin takes --polarization")
+        if args.video and not hasattr(args, "spin_map"):
+            p.error(f"{who} with --video needs --spin_map: the Stokes planes come from the Kerr ray map")
+        if args.video and args.orbit:
+            p.error(f"{who} does not combine with --orbit: the Stokes planes are the build view's, turned views have none")
+        if args.shutter > 0:
+            p.error(f"{who} does not combine with --shutter: shutter frames are marched")
+        if args.supersample != 1 or args.supersample_threshold is not None:
+            p.error(f"{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
+        if args.map_supersample != 1:
+            p.error(f"{who} does not combine with --map_supersample other than 1: a Kerr ray map has no supersampled form")
+        if args.gpus != 1:
+            p.error(f"{who} does not combine with --gpus other than 1: a ray map lives on one GPU")
+        for flag, on in (("--ray_map", args.ray_map), ("--orbit_map", args.orbit_map), ("--shutter_map", args.shutter_map),
+                         ("--passes", args.passes is not None)):
+            if on:
+                p.error(f"{who} does not combine with {flag}: that is a map of Schwarzschild rays")
+        for flag, on in (("--observer, --observer_velocity, --observer_sky or --infall_to", bool(observer_flags)),
+                         ("--projection", args.projection != "perspective" or args.projection_fov is not None),
+                         ("--light_delay", hasattr(args, "light_delay")), ("--stars point", args.stars == "point")):
+            if on:
+                p.error(f"{who} does not combine with {flag}: it is a Schwarzschild march's or the Schwarzschild ray map's")
+        if args.disk_model != "texture":
+            p.error(f"{who} does not combine with --disk_model other than texture: a ray map shades the disk texture")
         if args.video and getattr(args, "polarization_ticks", None) is not None:
             p.error("--polarization_ticks is a still image's overlay: it does not combine with --video (the cell grids go to --stokes_output)")
         if not getattr(args, "stokes_output", "x.npz").lower().endswith(".npz"):
@@ -598,13 +648,17 @@ def light_delay_from_args(args) -> dict:
 
 
 def polarization_from_args(args) -> dict:
-    """The polarisation of a command line as drivers.render_image / render_video take it: {} without --polarization."""
+    """The polarisation of a command line as drivers.render_image / render_video take it: {} without --polarization or
+    --spin_polarization; the latter's goes under ``kerr_polarization``."""
     pol = getattr(args, "polarization", None)
+    key = "polarization"
+    if pol is None:
+        pol, key = getattr(args, "spin_polarization", None), "kerr_polarization"
     if pol is None:
         return {}
     from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, parse_field
-    out = dict(polarization=dict(field=parse_field(pol), fraction=float(getattr(args, "polarization_fraction", DEFAULT_FRACTION)),
-                                 cell=int(getattr(args, "polarization_cell", DEFAULT_CELL))))
+    out = {key: dict(field=parse_field(pol), fraction=float(getattr(args, "polarization_fraction", DEFAULT_FRACTION)),
+                                 cell=int(getattr(args, "polarization_cell", DEFAULT_CELL)))}
     if getattr(args, "stokes_output", None) is not None:
         out["stokes_path"] = args.stokes_output
     if getattr(args, "polarization_ticks", None) is not None and not getattr(args, "video", False):
@@ -747,8 +801,11 @@ def main(argv=None) -> int:
             drivers.check_projection(world=world, **proj_kw)
         if delay_kw:
             drivers.check_light_delay(delay_kw["light_delay"], world=world)
-        if pol_kw:
+        if "polarization" in pol_kw:
             drivers.check_polarization(pol_kw["polarization"], video=True, ray_map=args.ray_map, world=world)
+        if "kerr_polarization" in pol_kw:
+            drivers.check_kerr_polarization(pol_kw["kerr_polarization"], video=True, spin_map=hasattr(args, "spin_map"), orbit=args.orbit,
+                                            spin=args.spin, redshift=args.redshift, world=world)
         if "BHR_FORCE_DEVICE" in os.environ:        # rehearsal: several ranks sharing one card
             local_rank = int(os.environ["BHR_FORCE_DEVICE"])
         elif world > 1:                             # a launcher that shows every rank only its own GPU: ordinal 0

@@ -7,6 +7,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "bhr_internal.h"
 
 namespace {
@@ -39,6 +41,14 @@ int32_t bhr_kerr_raymap_check_render(bhr_ctx *ctx, const char *who, const bhr_ca
                         (double)ctx->kerr_spin, redshift_name(ctx->kerr_redshift));
     BHR_TRY(check_context(ctx, who));
     if (cam) BHR_TRY(bhr_raymap_turn_of_build(rm->cam, cam, who, rot_c, rot_s));
+    // a Kerr polarisation (bhr_set_kerr_polarization): the Stokes kernel walks the build view's records and needs the photon's
+    // momentum with each, which only a build under the polarisation keeps
+    if (bhr_have_kerr_polar(ctx)) {
+        if (cam && !(*rot_c == 1.0f && *rot_s == 0.0f))
+            return bhr_fail(BHR_ERR_STATE, "%s: a Kerr polarisation is set (bhr_set_kerr_polarization) and the Stokes planes are the build view's; turned views have none -- switch it off (NULL) first", who);
+        if (!rm->has_mom)
+            return bhr_fail(BHR_ERR_STATE, "%s: a Kerr polarisation is set (bhr_set_kerr_polarization) and the map was built without the photon momenta it needs; build it again (bhr_kerr_raymap_build)", who);
+    }
     return BHR_OK;
 }
 
@@ -66,6 +76,22 @@ int32_t bhr_kerr_raymap_read(bhr_ctx *ctx, int32_t which, void *out, int64_t byt
     const char *who = "bhr_kerr_raymap_read";
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "%s: bad argument", who);
     if (!ctx->kerr_raymap || !ctx->kerr_raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no Kerr ray map has been built (bhr_kerr_raymap_build)", who);
+    if (which == BHR_RAYMAP_MOMENTUM) {
+        // the momentum planes of a build under a Kerr polarisation: [slot][component][pixel] on the device, [slot][pixel][component] out
+        const bhr_raymap *rm = ctx->kerr_raymap;
+        if (!rm->has_mom) return bhr_fail(BHR_ERR_STATE, "%s: the map was built without the photon momenta (bhr_set_kerr_polarization, then bhr_kerr_raymap_build)", who);
+        const size_t plane = (size_t)rm->a.plane, want = (size_t)rm->a.slots * 3 * plane * sizeof(float);
+        if (bytes != (int64_t)want) return bhr_fail(BHR_ERR_INVALID, "%s: plane %d has %zu bytes, caller gave %lld", who, which, want, (long long)bytes);
+        BHR_TRY(bhr_enter(ctx));
+        std::vector<float> tmp((size_t)rm->a.slots * 3 * plane);
+        BHR_HIP(hipMemcpyAsync(tmp.data(), rm->mom, want, hipMemcpyDeviceToHost, ctx->stream));
+        BHR_HIP(hipStreamSynchronize(ctx->stream));
+        float *o = (float *)out;
+        for (size_t s = 0; s < (size_t)rm->a.slots; ++s)
+            for (size_t c = 0; c < 3; ++c)
+                for (size_t p = 0; p < plane; ++p) o[(s * plane + p) * 3 + c] = tmp[(s * 3 + c) * plane + p];
+        return BHR_OK;
+    }
     return bhr_raymap_read_plane(ctx, ctx->kerr_raymap, who, which, out, bytes);
 }
 

@@ -108,10 +108,12 @@ int32_t check_polar(const bhr_ctx *ctx, const char *who, const char *what) {
 
 void free_planes(bhr_raymap *rm) {
     BhrRayMapArgs &a = rm->a;
-    void *bufs[] = {a.steps, a.status, a.dir, a.crossings, a.hits, a.over_count, a.over_list, a.stats};
+    void *bufs[] = {a.steps, a.status, a.dir, a.crossings, a.hits, a.over_count, a.over_list, a.stats, rm->mom};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     memset(&a, 0, sizeof(a));
+    rm->mom = nullptr;
+    rm->has_mom = 0;
     rm->built = 0;
     rm->alloc_slots = rm->alloc_comps = rm->alloc_ss = 0;
     rm->over_cap = 0;
@@ -144,8 +146,10 @@ int32_t alloc_planes(bhr_raymap *rm, const char *who, int32_t K, int32_t comps, 
     return BHR_OK;
 }
 
-// the star plane of the build view and the Stokes planes of the last frame belong to the Schwarzschild map: stale when it changes
+// the star plane of the build view and the Stokes planes of the last frame belong to the Schwarzschild map: stale when it changes;
+// under a Kerr polarisation the Stokes planes are a Kerr map frame's: stale when that map changes
 void invalidate_consumers(bhr_ctx *ctx, const bhr_raymap *rm) {
+    if (rm->kind == BHR_RAYMAP_KERR && bhr_have_kerr_polar(ctx)) bhr_polar_invalidate(ctx);
     if (rm->kind != BHR_RAYMAP_SCHWARZSCHILD) return;
     bhr_stars_invalidate(ctx);
     bhr_polar_invalidate(ctx);
@@ -191,12 +195,24 @@ int32_t bhr_raymap_build_into(bhr_ctx *ctx, bhr_raymap **map, const char *who, c
         free_planes(rm);
     }
     if (!rm->a.hits) BHR_TRY(alloc_planes(rm, who, K, comps, plane, ss));
+    // a Kerr map built under a Kerr polarisation (bhr_set_kerr_polarization) keeps the photon's momentum per stored crossing in
+    // planes of its own; a build without one gives them back
+    const bool want_mom = rm->kind == BHR_RAYMAP_KERR && bhr_have_kerr_polar(ctx);
+    rm->has_mom = 0;
+    if (want_mom && !rm->mom) BHR_TRY(plane_alloc(rm, who, &rm->mom, (size_t)K * 3 * plane));
+    if (!want_mom && rm->mom) {
+        BHR_TRY(drain(ctx));
+        (void)hipFree(rm->mom);
+        rm->mom = nullptr;
+        rm->device_bytes -= (int64_t)((size_t)K * 3 * plane * sizeof(float));
+    }
     const BhrRayMapArgs &a = rm->a;
     // records beyond a pixel's crossings stay zero
     BHR_HIP(hipMemsetAsync(a.hits, 0, (size_t)K * comps * plane * sizeof(float), ctx->stream));
     BHR_HIP(hipMemsetAsync(a.over_count, 0, 16 * sizeof(unsigned int), ctx->stream));
     BHR_HIP(hipMemsetAsync(a.stats, 0, (8 + BHR_STEP_CELL) * sizeof(unsigned long long), ctx->stream));
-    BHR_TRY(bhr_launch_raymap_build(ctx, cam, flags, a, ss, v));
+    if (rm->mom) BHR_HIP(hipMemsetAsync(rm->mom, 0, (size_t)K * 3 * plane * sizeof(float), ctx->stream));
+    BHR_TRY(bhr_launch_raymap_build(ctx, cam, flags, a, ss, v, rm->mom));
     std::vector<unsigned long long> stats(8 + BHR_STEP_CELL);
     unsigned int over = 0;
     BHR_TRY(fetch(ctx, stats.data(), a.stats, stats.size() * sizeof(unsigned long long)));
@@ -214,6 +230,7 @@ int32_t bhr_raymap_build_into(bhr_ctx *ctx, bhr_raymap **map, const char *who, c
         rm->kerr_spin = ctx->kerr_spin;
         rm->kerr_redshift = ctx->kerr_redshift;
     }
+    rm->has_mom = rm->mom ? 1 : 0;
     rm->built = 1;
     return BHR_OK;
 }

@@ -210,6 +210,7 @@ enum bhr_march_kernel {
     BHR_MK_KERR_RAYMAP_SHADE,      // kerr_raymap_shade_kernel<RS, false>: a frame from the records and the current scene          kerr_raymap
     BHR_MK_KERR_RAYMAP_SHADE_ROT,  // kerr_raymap_shade_kernel<RS, true>: the same with the records turned about z                 kerr_raymap
     BHR_MK_KERR_RAYMAP_FIX,        // kerr_raymap_fix_kernel<RS>: the map's overflow list, marched with the Kerr Ray               kerr_raymap
+    BHR_MK_KERR_RAYMAP_BUILD_MOM,  // kerr_raymap_build_mom_kernel<RS>: the build that also keeps each crossing's photon momentum  kerr_raymap
 };
 
 // The row of a march variant (settings.hip: bhr_variant_row_of): its kernels, and the terms and words of its refusals.
@@ -246,6 +247,12 @@ struct BhrRayMapArgs {
 // Kerr block's reason: BhrRayMapArgs is an argument of every other map kernel and does not grow.
 struct BhrRayMapStarArgs : BhrRayMapArgs {
     const float *stars;          // (rows, W, 3): the star plane S of the frame's view (stars.hip)
+};
+
+// The Kerr map as its build under a Kerr polarisation and the Kerr Stokes kernel see it (bhr_set_kerr_polarization): the map's
+// block with the momentum planes behind it, for the star block's reason.
+struct BhrRayMapMomArgs : BhrRayMapArgs {
+    float *mom;                  // slots x 3 planes, [slot][component]: the photon's covariant momentum (p_x, p_y, p_z) at each stored crossing
 };
 
 // Third argument of raymap_stokes_kernel (march_polar.hip), behind the march's block of the map's view and the map: the frame's
@@ -351,6 +358,10 @@ struct bhr_raymap {
     int64_t device_bytes;
     bhr_camera cam;              // the view it was built for
     uint64_t ray_steps, crossings_stored, overflow_pixels;
+    // a Kerr map built while a Kerr polarisation was set: the photon's momentum at each stored crossing, slots x 3 planes of the
+    // map's own beside the hits (BhrRayMapMomArgs); has_mom: the last build filled them
+    float *mom;
+    int32_t has_mom;
 };
 
 // The context's star catalogue (api_stars.hip): read-only shared state while frames are in flight, like the map.
@@ -575,6 +586,10 @@ struct bhr_ctx {
     int32_t polar_on;
     bhr_polarization polar;
     int32_t stokes_slot;
+    // ... and the Kerr polarisation (bhr_set_kerr_polarization), a setting of its own beside it: the Stokes pass of the frames from
+    // the Kerr ray map, into the same slot planes
+    int32_t kerr_polar_on;
+    bhr_polarization kerr_polar;
 };
 
 // The active frame slot: the one bhr_activate_slot / bhr_render last pointed the launchers at.
@@ -725,7 +740,9 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call);
 // ss: the map's factor -- the build marches the fine frame bhr_fine(ctx, ss) of `cam`
 // v, call.req.variant: none takes march_raymap.hip's kernels under the march's block, BHR_MV_KERR / BHR_MV_KERR_EXACT
 // march_kerr_raymap.hip's under the Kerr block (one ray per pixel, 5 components, no stars)
-int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss, bhr_march_variant v = BHR_MV_NONE);
+// mom: a Kerr build's momentum planes (kerr_raymap_build_mom_kernel fills them beside the records); null: the plain build
+int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss, bhr_march_variant v = BHR_MV_NONE,
+                                float *mom = nullptr);
 // rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
 // stars: the star plane of the frame's view (bhr_set_stars), added to the sky sample by the STARS kernels; null: the kernels without
 int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f,
@@ -875,6 +892,12 @@ void bhr_polar_invalidate(bhr_ctx *ctx);                                   // th
 int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrStokesArgs &s);
 const void *bhr_stokes_kernel(int32_t diff);                               // march_polar.hip -> march_polar.o
 const void *bhr_stokes_cells_kernel(void);
+// the Kerr polarisation (bhr_set_kerr_polarization): the same pass for a frame from the Kerr ray map `rm`, which has to hold the
+// momentum planes; the kernel is march_kerr_polar.hip's under the Kerr block of call's variant, the cell means the kernel above
+inline bool bhr_have_kerr_polar(const bhr_ctx *ctx) { return ctx->kerr_polar_on != 0; }
+int32_t bhr_kerr_polar_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm);
+int32_t bhr_launch_kerr_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, float *mom, const BhrStokesArgs &s);
+const void *bhr_kerr_stokes_kernel(int32_t exact);                         // march_kerr_polar.hip -> march_kerr_polar.o
 
 // ---- lifecycle.hip, texture.hip, disk_v2.hip ------------------------------------------------------------------------------------------
 void bhr_population_free(bhr_ctx *ctx);

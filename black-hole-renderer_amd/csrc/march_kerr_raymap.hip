@@ -21,6 +21,9 @@
 // (c, s) = (m.rot_c, m.rot_s).  Such a frame is the Kerr march of the BUILD view's rays, not bit for bit the marched frame of
 // the turned view; the launcher takes <RS, false> for c = 1, s = 0.
 //
+// kerr_raymap_build_mom_kernel<RS> is the build while a Kerr polarisation is set (bhr_set_kerr_polarization; march_kerr_polar.hip
+// has the pass that reads what it keeps): the same march, and per stored crossing the photon's momentum (p_x, p_y, p_z) as well.
+//
 // No differentials (the Kerr Ray has none) and no supersampled form.
 #include <type_traits>
 
@@ -73,6 +76,61 @@ __global__ __launch_bounds__(256) void kerr_raymap_build_kernel(KerrBlock<RS> a,
         m.steps[pix] = cnt;
         m.status[pix] = esc ? 1 : (ray.done == 2 ? 0 : 2);
         // the direction pixel_values hands sample_skybox
+        V3 dn = mk(0.0f, 0.0f, 0.0f);
+        if (esc) dn = normalized(ray.velocity(a));
+        m.dir[pix] = dn.x;
+        m.dir[(size_t)m.plane + pix] = dn.y;
+        m.dir[2 * (size_t)m.plane + pix] = dn.z;
+        m.crossings[pix] = n_rec;
+    }
+    raymap_append_overflow(m, valid && n_rec > m.slots, lane, pix);
+    const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
+    const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
+    if (lane == 0) {
+        atomicAdd(m.stats, stored);
+        atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
+    }
+}
+
+// The build under a Kerr polarisation (bhr_set_kerr_polarization): the kernel above, line for line, over Ray<false, RS, true>,
+// which parks the photon's whole momentum with each crossing, and with record_mom in record_one's place, which stores it in the
+// map's momentum planes m.mom beside the record.  A kernel of its own and not a shared body: the kernel above keeps the code it
+// had (a body both call moved ~180 of its instructions; tools/code_object_diff.py).  Records, header, overflow list and
+// counters are the plain build's bit for bit -- the march is the same and the momentum rides in words the plain ray leaves alone.
+template <int RS>
+__global__ __launch_bounds__(256) void kerr_raymap_build_mom_kernel(KerrBlock<RS> a, BhrRayMapMomArgs m) {
+    const int slot = wave_slot();
+    if (slot >= a.n_list) return;
+    const int lane = threadIdx.x & 63;
+    const int tile = a.tile_order ? a.tile_order[slot] : slot;
+    const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
+    const int i = tx * 8 + (lane & 7);
+    const int j = ty * 8 + (lane >> 3);
+    const bool valid = tile < a.n_tiles && i < a.width && j < a.rows;
+
+    Ray<false, RS, true> ray;
+    ray.init(a, valid ? i : 0, valid ? j : 0);
+    if (!valid) ray.done = 4;
+    const size_t pix = valid ? (size_t)j * a.width + i : 0;
+    int cnt = 0, n_rec = 0;
+    while (ray.done == 0) {
+        ray.step(a);
+        cnt += 1;
+        if (ray.full) {
+            ray.record_mom(m, m.mom, pix, n_rec);
+            ray.full = false;
+        }
+    }
+    ray.step_count = cnt;
+    if (cnt > 0) ray.settle(a);
+    else ray.done = 3;
+    if (__ballot(ray.n_pend > 0)) ray.record_mom(m, m.mom, pix, n_rec);
+    if (__ballot(ray.n_pend > 0)) ray.record_mom(m, m.mom, pix, n_rec);
+
+    if (valid) {
+        const bool esc = ray.escaped(a);
+        m.steps[pix] = cnt;
+        m.status[pix] = esc ? 1 : (ray.done == 2 ? 0 : 2);
         V3 dn = mk(0.0f, 0.0f, 0.0f);
         if (esc) dn = normalized(ray.velocity(a));
         m.dir[pix] = dn.x;
@@ -176,6 +234,7 @@ const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact) {
     case BHR_MK_KERR_RAYMAP_BUILD: return exact ? (const void *)kerr_raymap_build_kernel<KERR_EXACT> : (const void *)kerr_raymap_build_kernel<0>;
     case BHR_MK_KERR_RAYMAP_SHADE: return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, false> : (const void *)kerr_raymap_shade_kernel<0, false>;
     case BHR_MK_KERR_RAYMAP_SHADE_ROT: return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, true> : (const void *)kerr_raymap_shade_kernel<0, true>;
+    case BHR_MK_KERR_RAYMAP_BUILD_MOM: return exact ? (const void *)kerr_raymap_build_mom_kernel<KERR_EXACT> : (const void *)kerr_raymap_build_mom_kernel<0>;
     case BHR_MK_KERR_RAYMAP_FIX: return exact ? (const void *)kerr_raymap_fix_kernel<KERR_EXACT> : (const void *)kerr_raymap_fix_kernel<0>;
     default: return nullptr;
     }

@@ -527,7 +527,7 @@ static const void *raymap_kernel(bhr_march_variant v, bhr_march_kernel plain, bh
     return v == BHR_MV_NONE ? bhr_march_kernel_raymap(plain, diff, ss > 1) : bhr_march_kernel_kerr_raymap(kerr, v == BHR_MV_KERR_EXACT);
 }
 
-int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss, bhr_march_variant v) {
+int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss, bhr_march_variant v, float *mom) {
     const char *api = v == BHR_MV_NONE ? "bhr_raymap_build" : "bhr_kerr_raymap_build";
     const hipStream_t stream = ctx->stream;
     const bhr_march_call call = {cam, flags | BHR_FORCE_STRICT, stream, /* slot */ -1, false, false, ss, false, {v}};
@@ -544,10 +544,13 @@ int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t fl
     a.ray_steps = m.stats + 8;                                 // a counter cell of the map's own, behind its totals
     const bool diff = bhr_want_diff(ctx, flags);
     if (m.comps != (diff ? 9 : 5)) return bhr_fail(BHR_ERR_STATE, "%s: %d components per record for differentials %d", api, m.comps, (int)diff);
-    const void *fn = raymap_kernel(v, BHR_MK_RAYMAP_BUILD, BHR_MK_KERR_RAYMAP_BUILD, diff, ss);
+    if (mom && v == BHR_MV_NONE) return bhr_fail(BHR_ERR_STATE, "%s: momentum planes are a Kerr build's", api);
+    const void *fn = raymap_kernel(v, BHR_MK_RAYMAP_BUILD, mom ? BHR_MK_KERR_RAYMAP_BUILD_MOM : BHR_MK_KERR_RAYMAP_BUILD, diff, ss);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "%s: no build kernel in this library", api);
     VariantArgs va;
-    BhrRayMapArgs mm = m;
+    BhrRayMapMomArgs mm;               // the plain builds read its first sizeof(BhrRayMapArgs) bytes
+    static_cast<BhrRayMapArgs &>(mm) = m;
+    mm.mom = mom;
     void *args[] = {variant_args(ctx, call.req, a, va), &mm};
     (void)hipLaunchKernel(fn, dim3((a.n_list + 3) / 4), dim3(256), args, 0, stream);
     BHR_HIP(hipGetLastError());
@@ -646,6 +649,36 @@ int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRay
     BHR_HIP(hipGetLastError());
     void *cargs[] = {&ss};
     // whole waves, no more than the cell has pixels for: one wave for the 8 x 8 cell, four for 16 x 16 and 32 x 32
+    const unsigned cell_threads = s.cell * s.cell >= 256 ? 256u : 64u;
+    (void)hipLaunchKernel(fc, dim3(s.gw * s.gh), dim3(cell_threads), cargs, 0, call.stream);
+    BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}
+
+// The Stokes pass of a frame from the Kerr ray map (march_kerr_polar.hip; api_polar.hip owns the planes): the Kerr Stokes kernel of
+// the frame's redshift on the Kerr shade kernel's grid under the Kerr block the shade launch of the same frame was given, then the
+// cell means as above.
+int32_t bhr_launch_kerr_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, float *mom, const BhrStokesArgs &s) {
+    const bhr_march_variant v = call.req.variant;
+    if (v != BHR_MV_KERR && v != BHR_MV_KERR_EXACT) return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: the frame is not a Kerr variant's");
+    if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: the Stokes kernel has no supersampled twin (factor %d)", call.ss);
+    BhrMarchArgs a;
+    march_args(ctx, call, nullptr, 1, false, a);
+    if ((int64_t)a.width * a.rows != m.plane || m.comps != 5 || s.width != a.width || s.rows != a.rows || !mom)
+        return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: the map does not fit the frame");
+    if (s.cell < 1 || s.gw != (a.width + s.cell - 1) / s.cell || s.gh != (a.rows + s.cell - 1) / s.cell || !s.out || !s.cells)
+        return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: a cell grid of %d x %d cells of %d pixels for a %d x %d frame", s.gw, s.gh, s.cell, a.width, a.rows);
+    const void *fn = bhr_kerr_stokes_kernel(v == BHR_MV_KERR_EXACT ? 1 : 0), *fc = bhr_stokes_cells_kernel();
+    if (!fn || !fc) return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: no Stokes kernel in this library");
+    VariantArgs va;
+    BhrRayMapMomArgs mm;
+    static_cast<BhrRayMapArgs &>(mm) = m;
+    mm.mom = mom;
+    BhrStokesArgs ss = s;
+    void *args[] = {variant_args(ctx, call.req, a, va), &mm, &ss};
+    (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
+    BHR_HIP(hipGetLastError());
+    void *cargs[] = {&ss};
     const unsigned cell_threads = s.cell * s.cell >= 256 ? 256u : 64u;
     (void)hipLaunchKernel(fc, dim3(s.gw * s.gh), dim3(cell_threads), cargs, 0, call.stream);
     BHR_HIP(hipGetLastError());

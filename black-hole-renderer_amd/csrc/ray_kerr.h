@@ -241,7 +241,10 @@ __device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh,
     sh.alpha_total = 1.0f - front * (1.0f - disk_alpha);
 }
 
-template <bool DIFF, int SRC = 0>
+// MOM (the Kerr ray map's build under a Kerr polarisation, march_kerr_raymap.hip): a crossing also parks the photon's whole
+// momentum (p_x, p_y, p_z) at the hit, interpolated like the hit point, in words 5..7 of the lane's parking slot -- the words a
+// ray with differentials would use, which the Kerr ray has none of -- and record_mom stores it beside the record.
+template <bool DIFF, int SRC = 0, bool MOM = false>
 struct Ray {
     static_assert(!DIFF && (SRC == 0 || SRC == KERR_EXACT), "the Kerr march has no ray differentials; its second parameter is the redshift, model or exact");
     V3 x, p;
@@ -334,6 +337,11 @@ struct Ray {
                         hit.to_cam = mk(-v1.x, -v1.y, -v1.z);               // against dx/dl at the START of the step
                     }
                     park_store<false>(n_pend, hit);                         // a free slot is guaranteed (march_tile_body flushes at 2)
+                    if (MOM) {
+                        g_park[n_pend][5][threadIdx.x] = p.x + t_frac * (np.x - p.x);
+                        g_park[n_pend][6][threadIdx.x] = p.y + t_frac * (np.y - p.y);
+                        g_park[n_pend][7][threadIdx.x] = p.z + t_frac * (np.z - p.z);
+                    }
                     n_pend += 1;
                 }
             }
@@ -375,6 +383,28 @@ struct Ray {
                 q[4 * p] = h.to_cam.z;
             }
             n_rec += 1;
+        }
+    }
+    // MOM: record_one with the parked momentum behind it -- into the map's momentum planes `mom`, [slot][component] like the
+    // hits -- and the second slot's three words moved up with its record
+    __device__ __forceinline__ void record_mom(const BhrRayMapArgs &m, float *mom, size_t at, int &n_rec) {
+        static_assert(MOM, "record_mom: the momentum is parked by Ray<false, RS, true> alone");
+        if (n_pend > 0) {
+            const int t = threadIdx.x;
+            const V3 ph = mk(g_park[0][5][t], g_park[0][6][t], g_park[0][7][t]);
+            if (n_pend == 2) {
+                g_park[0][5][t] = g_park[1][5][t];
+                g_park[0][6][t] = g_park[1][6][t];
+                g_park[0][7][t] = g_park[1][7][t];
+            }
+            if (n_rec < m.slots) {
+                const size_t p = (size_t)m.plane;
+                float *q = mom + (size_t)n_rec * 3 * p + at;
+                q[0] = ph.x;
+                q[p] = ph.y;
+                q[2 * p] = ph.z;
+            }
+            record_one(m, at, n_rec);
         }
     }
     // the escape direction is the direction of dx/dl at the last state

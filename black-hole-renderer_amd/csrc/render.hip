@@ -153,6 +153,11 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_raymap &rm, const bhr_camera *cam
         BHR_TRY(bhr_polar_frame(ctx, call, rm));
         ctx->stokes_slot = k;
     }
+    // ... and a Kerr map's frame under a Kerr polarisation (bhr_set_kerr_polarization) by the Kerr Stokes kernel, likewise
+    if (kerr && bhr_have_kerr_polar(ctx)) {
+        BHR_TRY(bhr_kerr_polar_frame(ctx, call, rm));
+        ctx->stokes_slot = k;
+    }
     return post_on_slot(ctx, flags, k, ring);
 }
 

@@ -136,6 +136,7 @@ int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr) {
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight, like every other change of what a frame is
     ctx->kerr_on = on;
     ctx->kerr_spin = on ? a_over_m : 0.0f;
+    if (bhr_have_kerr_polar(ctx)) bhr_polar_invalidate(ctx);   // the Stokes planes of a Kerr map frame are that spin's
     return bhr_note_frame_kernel(ctx);
 }
 
@@ -148,6 +149,7 @@ int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode) {
     if (mode == ctx->kerr_redshift) return BHR_OK;
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight
     ctx->kerr_redshift = mode;
+    if (bhr_have_kerr_polar(ctx)) bhr_polar_invalidate(ctx);   // ... and that mode's gas
     return bhr_note_frame_kernel(ctx);
 }
 

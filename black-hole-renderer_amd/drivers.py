@@ -233,7 +233,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  passes_path: Optional[str] = None, spin: float = 0.0, redshift: str = "model",
                  observer=None, observer_sky: bool = True, stars: Optional[dict] = None,
                  projection: Optional[str] = None, projection_fov=None, light_delay=None, polarization: Optional[dict] = None,
-                 stokes_path: Optional[str] = None, ticks_path: Optional[str] = None) -> np.ndarray:
+                 stokes_path: Optional[str] = None, ticks_path: Optional[str] = None, kerr_polarization: Optional[dict] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -270,9 +270,16 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                         disk_model=disk_model, observer=observer)
     check_observer(observer, **facts)
     check_passes(passes_path, gpus=gpus, supersample=supersample, disk_model=disk_model)
-    polarization = check_polarization(polarization, supersample=supersample, disk_model=disk_model, gpus=gpus, spin=spin, redshift=redshift,
-                                      observer=observer is not None, projection=projection is not None, light_delay=light_delay is not None,
-                                      stokes_path=stokes_path, ticks_path=ticks_path)
+    # ``kerr_polarization``: the same dict for a spinning hole (check_kerr_polarization): the view's KERR ray map is built with the
+    # photon momenta and the frame is shaded from it, the Kerr Stokes pass behind the shade; stokes_path and ticks_path serve it too
+    kerr_polarization = check_kerr_polarization(kerr_polarization, polarization=polarization is not None, spin=spin, redshift=redshift,
+                                                supersample=supersample, supersample_threshold=supersample_threshold, gpus=gpus, disk_model=disk_model,
+                                                observer=observer is not None, projection=projection is not None, light_delay=light_delay is not None,
+                                                stars=stars is not None, passes=passes_path is not None, stokes_path=stokes_path, ticks_path=ticks_path)
+    if kerr_polarization is None:
+        polarization = check_polarization(polarization, supersample=supersample, disk_model=disk_model, gpus=gpus, spin=spin, redshift=redshift,
+                                          observer=observer is not None, projection=projection is not None, light_delay=light_delay is not None,
+                                          stokes_path=stokes_path, ticks_path=ticks_path)
     grade = check_grade(grade)
     if hdr_path is not None:
         check_hdr_path(hdr_path)
@@ -310,7 +317,14 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         renderer.set_grade(**grade)
     if polarization is not None:
         renderer.set_polarization(**polarization)          # ahead of the frame: its Stokes pass rides behind the shade launch
-    if stars is not None or polarization is not None:
+    if kerr_polarization is not None:
+        from . import _lib
+        renderer.set_kerr_polarization(**kerr_polarization)   # ahead of the build: the map then keeps the photon momenta
+        renderer.build_kerr_ray_map(cam_pos, fov)
+        renderer.render_from_kerr_ray_map_async(frame=0)
+        img = renderer.read_layer(_lib.LAYER_FINAL)
+        polarization = kerr_polarization                       # the outputs below are the same
+    elif stars is not None or polarization is not None:
         from . import _lib
         renderer.build_ray_map(cam_pos, fov)
         renderer.render_from_ray_map_async(frame=0)
@@ -330,7 +344,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
               f"{polarization['cell']} pixels, largest cell degree {float(deg.max()) if deg.size else 0.0:.3f}")
         if stokes_path is not None:
             pol_mod.write_stokes(stokes_path, cells, polarization["cell"], polarization["field"], polarization["fraction"],
-                                 camera=dict(cam_pos=list(cam_pos), fov=fov), stokes=planes)
+                                 camera=dict(cam_pos=list(cam_pos), fov=fov), stokes=planes,
+                                 **({} if kerr_polarization is None else {"hole": dict(spin=spin, redshift=redshift)}))
             print(f"Saved: {stokes_path}")
         if ticks_path is not None:
             from .output import png_write, quantize
@@ -586,6 +601,57 @@ def check_shutter_map(shutter_map: bool, shutter: float = 0.5, orbit: bool = Fal
     --orbit_map, which are the maps of instantaneous exposures.  Raises ValueError before any device work."""
     if shutter_map:
         _check_map("shutter_map", locals())
+
+
+def check_kerr_polarization(kerr_polarization, polarization: bool = False, video: bool = False, spin_map: bool = False, orbit: bool = False,
+                            spin: float = 0.0, redshift: str = "model", shutter: float = 0.0, supersample=1, supersample_threshold=None,
+                            map_supersample=1, gpus: int = 1, world: int = 1, disk_model: str = "texture", ray_map: bool = False,
+                            orbit_map: bool = False, shutter_map: bool = False, observer: bool = False, projection: bool = False,
+                            light_delay: bool = False, stars: bool = False, passes: bool = False, stokes_path=None, ticks_path=None):
+    """kerr_polarization=dict(field=, fraction=, cell=): Stokes Q / U maps of the disk of a SPINNING hole, carried along each ray
+    by the Walker-Penrose constant (--spin_polarization; HipRenderer.set_kerr_polarization) -> the dict with its defaults filled
+    in, or None without one.  It needs a spin or the exact redshift (the Kerr march); a still builds a Kerr ray map of the view,
+    a video needs spin_map and a camera that stands still.  Raises ValueError naming --spin_polarization and the other flag,
+    before any device work, for what a Kerr ray map does not take (check_spin_map) and for supersample > 1."""
+    if kerr_polarization is None:
+        return None
+    who = "--spin_polarization"
+    from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check
+    unknown = set(kerr_polarization) - {"field", "fraction", "cell"}
+    if unknown or "field" not in kerr_polarization:
+        raise ValueError(f"{who} takes field, fraction and cell, got {sorted(kerr_polarization)}")
+    out = check(kerr_polarization["field"], kerr_polarization.get("fraction", DEFAULT_FRACTION), kerr_polarization.get("cell", DEFAULT_CELL))
+    if polarization:
+        raise ValueError(f"{who} does not combine with --polarization: that is the hole that does not spin")
+    if spin == 0 and redshift == "model":
+        raise ValueError(f"{who} needs --spin or --redshift exact: it is the polarisation of the Kerr march; a hole that does not spin takes --polarization")
+    if video and not spin_map:
+        raise ValueError(f"{who} with --video needs --spin_map: the Stokes planes come from the Kerr ray map")
+    if video and orbit:
+        raise ValueError(f"{who} does not combine with --orbit: the Stokes planes are the build view's, turned views have none")
+    if video and ticks_path is not None:
+        raise ValueError("polarization_ticks is a still image's overlay: a video writes its cell grids to stokes_output")
+    if shutter > 0:
+        raise ValueError(f"{who} does not combine with --shutter: shutter frames are marched")
+    if supersample != 1 or supersample_threshold is not None:
+        raise ValueError(f"{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
+    if map_supersample != 1:
+        raise ValueError(f"{who} does not combine with --map_supersample other than 1: a Kerr ray map has no supersampled form")
+    if gpus != 1 or world != 1:
+        raise ValueError(f"{who} does not combine with --gpus other than 1: a ray map lives on one GPU")
+    for flag, on in (("--ray_map", ray_map), ("--orbit_map", orbit_map), ("--shutter_map", shutter_map), ("--passes", passes)):
+        if on:
+            raise ValueError(f"{who} does not combine with {flag}: that is a map of Schwarzschild rays")
+    for flag, on in (("--observer", observer), ("--projection", projection), ("--light_delay", light_delay), ("--stars point", stars)):
+        if on:
+            raise ValueError(f"{who} does not combine with {flag}: it is a Schwarzschild march's or the Schwarzschild ray map's")
+    if disk_model != "texture":
+        raise ValueError(f"{who} does not combine with --disk_model other than texture: a ray map shades the disk texture")
+    if stokes_path is not None and not str(stokes_path).lower().endswith(".npz"):
+        raise ValueError(f"stokes_output is written as a .npz file, got {stokes_path!r}")
+    if ticks_path is not None and not str(ticks_path).lower().endswith(".png"):
+        raise ValueError(f"polarization_ticks is written as a .png file, got {ticks_path!r}")
+    return out
 
 
 def check_spin_map(spin_map: bool, spin: float = 0.0, redshift: str = "model", video: bool = True, shutter: float = 0.0, supersample=1,
@@ -854,6 +920,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  observer: Optional[str] = None, observer_velocity=None, observer_sky: bool = True,
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
                  light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, spin_map: bool = False,
+                 kerr_polarization: Optional[dict] = None,
                  **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
@@ -987,7 +1054,16 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                        supersample=renderer.supersample if supersample is None else supersample, map_supersample=map_supersample, world=world,
                        ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map, observer=moving, projection=projected,
                        light_delay=light_delay is not None, stars=stars is not None,
-                       polarization=polarization is not None or stokes_path is not None)
+                       polarization=polarization is not None or (stokes_path is not None and kerr_polarization is None))
+    # ``kerr_polarization`` (needs ``spin_map=True`` and no ``orbit``): polarization's outputs for a spinning hole -- set ahead of
+    # the map's build, which then keeps the photon momenta; every frame's cell grid is collected into the one .npz
+    if kerr_polarization is not None:                           # (without one the renderer is not asked anything, as ever)
+        kerr_polarization = check_kerr_polarization(kerr_polarization, polarization=polarization is not None, video=True, spin_map=spin_map,
+                                                    orbit=orbit, spin=renderer.spin, redshift=renderer.redshift, shutter=shutter,
+                                                    supersample=renderer.supersample if supersample is None else supersample,
+                                                    map_supersample=map_supersample, world=world, disk_model=disk_model, ray_map=ray_map,
+                                                    orbit_map=orbit_map, shutter_map=shutter_map, observer=moving, projection=projected,
+                                                    light_delay=light_delay is not None, stars=stars is not None, stokes_path=stokes_path)
     if moving or projected or light_delay is not None:
         # what the three variant checks take from the renderer and the call
         thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
@@ -1009,7 +1085,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         light_delay = check_light_delay(light_delay, world=world, observer=moving, projection=projected, stars=stars is not None, **facts)
     check_map_supersample(map_supersample, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map)
     check_shutter(shutter, shutter_samples=shutter_samples)
-    if polarization is not None or stokes_path is not None:     # (without one the renderer is not asked anything, as ever)
+    if kerr_polarization is None and (polarization is not None or stokes_path is not None):     # (without one the renderer is not asked anything, as ever)
         polarization = check_polarization(polarization, video=True, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map, shutter=shutter,
                                           supersample=renderer.supersample if supersample is None else supersample,
                                           map_supersample=map_supersample, disk_model=disk_model, world=world, spin=renderer.spin,
@@ -1115,7 +1191,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         raise ValueError(f"--video_hdr does not resume: {len(completed)} frames are already rendered and a stream cannot be taken "
                          "up in the middle; render without --resume")
 
-    if polarization is not None and completed:
+    if (polarization is not None or kerr_polarization is not None) and completed:
         raise ValueError(f"polarization does not resume: {len(completed)} frames are already rendered and their cell grids are gone; "
                          "render without --resume")
 
@@ -1167,6 +1243,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     factories = init_lifecycle_system(renderer, n_r, n_phi, seed=42)
     dt = disk_rotation_speed
     print(f"  lifecycle system ready (n_r={n_r}, n_phi={n_phi}), rank {rank}/{world}")
+    if kerr_polarization is not None:
+        renderer.set_kerr_polarization(**kerr_polarization)     # ahead of the build: the map then keeps the photon momenta
     if mode is not None:
         # the one march of the video.  A camera that stands still: its view; an orbit: frame 0's (the orbit's radius is |pov|, not
         # the pov's xy norm: not the pov itself), which every frame's camera is a turn of about z
@@ -1198,7 +1276,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                     fr["t_offsets"] = [(u - frame) * disk_rotation_speed for u in times]
                 if mode is not None:                               # from the video's map: shade, no march
                     _MAP_MODES[mode]["frame"](renderer, fr)
-                    if polarization is not None:                   # (ray_map only: check_polarization)
+                    if polarization is not None or kerr_polarization is not None:      # (ray_map, or spin_map under kerr_polarization)
                         stokes_grids[frame] = renderer.stokes_cells()      # the frame's cell grid (synchronises: a few kB per frame)
                 elif shutter > 0:
                     renderer.render_shutter_async(fr["positions"], fov, fr["t_offsets"])
@@ -1225,8 +1303,12 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         finally:
             if polarization is not None:
                 renderer.set_polarization(None)
+            if kerr_polarization is not None:
+                renderer.set_kerr_polarization(None)
         frames_written, bytes_written = sink.drain()
         sink.close()
+        hole = {} if kerr_polarization is None else {"hole": dict(spin=renderer.spin, redshift=renderer.redshift)}
+        polarization = polarization if kerr_polarization is None else kerr_polarization
         if polarization is not None:
             from .polarization import write_stokes
             path = stokes_path if stokes_path is not None else os.path.splitext(output_path)[0] + ".stokes.npz"
@@ -1234,7 +1316,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             if len(stokes_grids) != n_frames:
                 raise RuntimeError(f"polarization: {len(stokes_grids)} cell grids for {n_frames} frames; {path} is not written")
             write_stokes(path, np.stack([stokes_grids[f] for f in range(n_frames)]), polarization["cell"], polarization["field"],
-                         polarization["fraction"], camera=dict(cam_pos=list(static_cam_pos), fov=fov))
+                         polarization["fraction"], camera=dict(cam_pos=list(static_cam_pos), fov=fov), **hole)
             print(f"Saved: {path} ({n_frames} cell grids of {polarization['cell']}-pixel cells)")
     finally:
         if mode is not None:

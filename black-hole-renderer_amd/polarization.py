@@ -109,10 +109,11 @@ def draw_ticks(rgb_u8, cells, cell, color=(255, 255, 255), scale=0.9) -> np.ndar
     return out
 
 
-def write_stokes(path, cells, cell, field, fraction, camera=None, stokes=None) -> None:
+def write_stokes(path, cells, cell, field, fraction, camera=None, stokes=None, hole=None) -> None:
     """A compressed .npz: ``cells`` -- (gh, gw, 3) of a still or (n_frames, gh, gw, 3) of a video --, ``cell``, ``field``,
     ``fraction``, ``convention`` (CONVENTION), ``cam_pos`` / ``fov`` where ``camera`` = dict(cam_pos=, fov=) is given, and
-    where ``stokes`` (3, H, W) is given the planes ``I``, ``Q``, ``U`` (a still; a video carries the grids only)."""
+    where ``stokes`` (3, H, W) is given the planes ``I``, ``Q``, ``U`` (a still; a video carries the grids only); with ``hole`` =
+    dict(spin=, redshift=) -- the Kerr polarisation's files -- also ``spin`` (a / M) and ``redshift`` ("model" or "exact")."""
     if not str(path).lower().endswith(".npz"):
         raise ValueError(f"the Stokes output is written as a .npz file, got {path!r}")
     data = {"cells": np.asarray(cells, dtype=np.float32), "cell": np.int32(cell), "field": np.asarray(field_vector(field), dtype=np.float64),
@@ -120,6 +121,9 @@ def write_stokes(path, cells, cell, field, fraction, camera=None, stokes=None) -
     if camera is not None:
         data["cam_pos"] = np.asarray(camera["cam_pos"], dtype=np.float64)
         data["fov"] = np.float64(camera["fov"])
+    if hole is not None:
+        data["spin"] = np.float64(hole["spin"])
+        data["redshift"] = np.array(str(hole["redshift"]))
     if stokes is not None:
         s = np.asarray(stokes, dtype=np.float32)
         data["I"], data["Q"], data["U"] = s[0], s[1], s[2]

@@ -702,6 +702,16 @@ class HipRenderer:
             raise AssertionError("no Kerr ray map has been built (build_kerr_ray_map)")
         return self._map_planes(self._lib.bhr_kerr_raymap_read, info["rows"], info["width"], info["slots"], 5)
 
+    def kerr_ray_map_momentum(self) -> np.ndarray:
+        """The photon's covariant momentum (p_x, p_y, p_z) at each stored crossing of a Kerr map built under a Kerr polarisation,
+        (K, H, W, 3) float32 in record order (bhr_kerr_raymap_read, BHR_RAYMAP_MOMENTUM); refused for a map built without."""
+        info = self.kerr_ray_map_info()
+        if not info["built"]:
+            raise AssertionError("no Kerr ray map has been built (build_kerr_ray_map)")
+        out = np.empty((info["slots"], info["rows"], info["width"], 3), dtype=np.float32)
+        _lib.check(self._lib.bhr_kerr_raymap_read(self._ctx, _lib.RAYMAP_MOMENTUM, out.ctypes.data, out.nbytes))
+        return out
+
     def free_kerr_ray_map(self) -> None:
         """Release the Kerr ray map's device memory (bhr_kerr_raymap_free); close() does it too."""
         _lib.check(self._lib.bhr_kerr_raymap_free(self._ctx))
@@ -790,6 +800,33 @@ class HipRenderer:
         differentials."""
         out = (C.c_int32 * 3)()
         _lib.check(self._lib.bhr_stokes_resources(1 if diff else 0, out))
+        return {"vgprs": int(out[0]), "lds_bytes": int(out[1]), "scratch_bytes": int(out[2])}
+
+    def set_kerr_polarization(self, field="toroidal", fraction: float = 0.7, cell: int = 16) -> None:
+        """Set the polarisation the frames from the KERR ray map compute Stokes planes under (bhr_set_kerr_polarization;
+        include/bhr.h "Kerr polarisation" states the transport by the Walker-Penrose constant): the arguments of
+        set_polarization; ``field=None`` switches it off.  It needs a spin or the forced Kerr march (set_spin).  Set it BEFORE
+        build_kerr_ray_map: the build then keeps the photon's momentum per crossing, which a frame under it needs (a map built
+        without is refused, naming the rebuild).  Turned views are refused while it is set.  stokes() and stokes_cells() read the
+        planes of the last such frame.  Synchronises."""
+        if field is None:
+            _lib.check(self._lib.bhr_set_kerr_polarization(self._ctx, None))
+            return
+        from . import polarization as pol_mod
+        b = pol_mod.field_vector(field)
+        par = _lib.Polarization(b[0], b[1], b[2], float(fraction), int(cell))
+        _lib.check(self._lib.bhr_set_kerr_polarization(self._ctx, C.byref(par)))
+
+    def clear_kerr_polarization(self) -> None:
+        """Switch the Kerr polarisation off (bhr_set_kerr_polarization with NULL)."""
+        self.set_kerr_polarization(None)
+
+    def kerr_stokes_resources(self, redshift: str = "model") -> dict:
+        """Registers, LDS bytes and scratch bytes of the Kerr Stokes kernel of a redshift mode (bhr_kerr_stokes_resources)."""
+        if redshift not in ("model", "exact"):
+            raise ValueError(f"redshift mode {redshift!r}: 'model' or 'exact'")
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_kerr_stokes_resources(_lib.REDSHIFT_EXACT if redshift == "exact" else _lib.REDSHIFT_MODEL, out))
         return {"vgprs": int(out[0]), "lds_bytes": int(out[1]), "scratch_bytes": int(out[2])}
 
     def sync(self) -> None:

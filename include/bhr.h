@@ -496,6 +496,35 @@ BHR_API int32_t bhr_set_polarization(bhr_ctx *ctx, const bhr_polarization *p);
 BHR_API int32_t bhr_read_stokes(bhr_ctx *ctx, int32_t plane, float *out);
 BHR_API int32_t bhr_read_stokes_cells(bhr_ctx *ctx, float *out, int32_t dims[2]);
 BHR_API int32_t bhr_stokes_resources(int32_t diff, int32_t out[3]);
+/* ---- Kerr polarisation: the same planes for the frames of bhr_kerr_raymap_render (csrc/march_kerr_polar.hip; DESIGN 4 "Kerr polarisation") ----
+ * The struct, the planes, the cell grid, c_k, I, Q, U, the convention for chi and both reads are those above.  What differs is how
+ * a crossing's polarisation gets from the gas to the camera: by the Walker-Penrose constant, in the march's Kerr-Schild chart
+ * (units r_s = 1, M = 1/2, a = A M; g = eta + f l l, l_mu = (1, l); csrc/ray_kerr.h).  For the traced photon, covariant momentum
+ * (-1, p), contravariant k = (1 + f u, p - f u l), u = 1 + l . p, and a polarisation vector f parallel-transported along it,
+ *   kappa1 = k^t (x . f) - f^t (x . k) + a (k^x f^y - k^y f^x),   kappa2 = x . (k x f) - a (k^t f^z - k^z f^t)
+ * are conserved (bold spatial parts, Euclidean dot and cross).  Per stored crossing at (hx, hy, 0) with the photon's momentum p
+ * there (kept per record by a build under the polarisation):
+ *   r = sqrt(hx^2 + hy^2 - a^2), f = 1 / r, l = ((r hx + a hy) / Q, (r hy - a hx) / Q, 0), Q = hx^2 + hy^2;
+ *   the gas's 4-velocity u of the context's redshift mode -- model: speed beta = min(r_s Omega / sqrt(1 - 1 / r_s), 0.99), r_s =
+ *     max(r, 1 + 1e-3), Kerr's Omega, along the orbit as the static observer at the hit measures it; exact: the circular geodesic
+ *     outside the ISCO, the plunge with the ISCO's E and L inside it (the g-factor's gas in either mode);
+ *   the tetrad by Gram-Schmidt under g: u, e_phi from v_hat = r_hat x n (the sense of the disk), e_z = d_z, e_r from r_hat;
+ *   n'_(i) = (k . e_(i)) / (-k . u), normalized (the interpolated p is null to second order in its step only); B' = normalize(b_r, b_phi, b_z) in (e_r, e_phi, e_z); e' = n' x B', s2 = |e'|^2,
+ *     p_k = fraction s2; f_em = (e'_(i) / sqrt(s2)) e_(i); kappa_em = kappa(hit, k, f_em).
+ * At the camera C with the photon Ray::init launches along the pixel direction D (momentum p_c): e_x, e_y the sky-plane axes
+ * above, lifted to E_x = (p_c . e_x, e_x), E_y = (p_c . e_y, e_y); (alpha, beta) solves alpha kappa(E_x) + beta kappa(E_y) =
+ * kappa_em; cos 2chi = (alpha^2 - beta^2) / (alpha^2 + beta^2), sin 2chi = 2 alpha beta / (alpha^2 + beta^2).  A pixel whose
+ * 2 x 2 system is singular (the radial ray of a hole that does not spin) adds to I only.
+ * bhr_set_kerr_polarization: the validation of bhr_set_polarization's struct; BHR_ERR_STATE without the Kerr march (bhr_set_spin);
+ *   NULL switches it off; it synchronises.  A Kerr map built while it is set keeps the momenta (slots x 3 floats per pixel more);
+ *   bhr_kerr_raymap_render from a map built without them, and bhr_kerr_raymap_render_view with a turned camera, are BHR_ERR_STATE
+ *   while it is set.  A change of spin or redshift mode makes the planes unreadable until the next such frame.
+ * bhr_kerr_stokes_resources: VGPRs, LDS bytes and scratch bytes of the Kerr Stokes kernel of a redshift mode. */
+/* bhr_kerr_raymap_read(ctx, BHR_RAYMAP_MOMENTUM, out, slots * rows * W * 12): the momenta (p_x, p_y, p_z) of a map that keeps them,
+ * (slots, rows, W, 3) in record order, zeros behind a pixel's crossings; BHR_ERR_STATE for a map built without them. */
+#define BHR_RAYMAP_MOMENTUM 6
+BHR_API int32_t bhr_set_kerr_polarization(bhr_ctx *ctx, const bhr_polarization *p);
+BHR_API int32_t bhr_kerr_stokes_resources(int32_t redshift, int32_t out[3]);
 /* image_field/disk_layer_field/blur_field .to_numpy() and the final image,
  * for the context's rows: (row1-row0, width, 3) f32.  Synchronises. */
 BHR_API int32_t bhr_read_layer(bhr_ctx *ctx, int32_t layer, float *out);
