@@ -35,7 +35,7 @@ SYMBOLS = (
     "bhr_fill_comp_slice", "bhr_set_compose_stats", "bhr_compose_texture", "bhr_eval_noise", "bhr_render", "bhr_render_shutter",
     "bhr_set_spin", "bhr_kerr_resources", "bhr_set_redshift", "bhr_kerr_redshift_resources",
     "bhr_render_observer", "bhr_observer_resources", "bhr_render_delayed", "bhr_delayed_resources",
-    "bhr_render_projected", "bhr_projected_resources",
+    "bhr_render_projected", "bhr_projected_resources", "bhr_render_kerr_view", "bhr_kerr_view_resources",
     "bhr_raymap_build", "bhr_raymap_render", "bhr_raymap_render_view", "bhr_raymap_render_shutter", "bhr_raymap_read", "bhr_raymap_get_info", "bhr_raymap_free",
     "bhr_kerr_raymap_build", "bhr_kerr_raymap_render", "bhr_kerr_raymap_render_view", "bhr_kerr_raymap_read", "bhr_kerr_raymap_info", "bhr_kerr_raymap_free",
     "bhr_set_stars", "bhr_get_stars_info", "bhr_stars_resources",
@@ -232,6 +232,8 @@ def load() -> C.CDLL:
     lib.bhr_delayed_resources.argtypes = [I32, C.POINTER(C.c_int32)]
     lib.bhr_render_projected.argtypes = [P, C.POINTER(Camera), C.POINTER(Projection), C.POINTER(Observer), C.c_uint32]
     lib.bhr_projected_resources.argtypes = [I32, C.POINTER(C.c_int32)]
+    lib.bhr_render_kerr_view.argtypes = [P, C.POINTER(Camera), C.POINTER(Observer), C.POINTER(Projection), C.c_uint32]
+    lib.bhr_kerr_view_resources.argtypes = [I32, I32, C.POINTER(C.c_int32)]
     lib.bhr_set_option.argtypes = [P, C.c_char_p, C.c_double]
     lib.bhr_debug_read.argtypes = [P, I32, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
     lib.bhr_lens_flare.argtypes = [P]

@@ -7,7 +7,8 @@ round-robin by RANK / WORLD_SIZE), ``--disk_model`` (the analytic Disk V2 source
 ``--observer_velocity`` (a camera that moves: aberration and Doppler shift), ``--stars point`` (the procedural sky's stars as a
 catalogue of lensed points rendered through a ray map), ``--light_delay`` (every disk crossing shaded at the
 time its light left the gas), ``--projection`` / ``--projection_fov`` (equirectangular 360-degree
-frames and fisheye dome masters instead of the pinhole camera), ``--polarization`` (Stokes Q / U maps of the disk through a ray map).
+frames and fisheye dome masters instead of the pinhole camera), ``--polarization`` (Stokes Q / U maps of the disk through a ray map),
+``--spin_observer`` / ``--spin_projection`` and their companions (the moving and the panoramic camera of a spinning hole).
 """
 from __future__ import annotations
 
@@ -113,6 +114,26 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--projection_fov", type=float, nargs="+", default=None, metavar=("A", "B"),
                    help="--projection equirect: the horizontal and vertical span in degrees, A in (0, 360] and B in (0, 180] (default: "
                         "360 180); --projection fisheye: the full angle of the image circle, A in (0, 360] (default: 180)")
+    p.add_argument("--spin_observer", type=str, default=argparse.SUPPRESS, choices=["static", "circular", "zamo", "infall"], metavar="{static,circular,zamo}",
+                   help="--spin / --redshift exact: the camera of the spinning hole moves through --pov -- aberration, the Doppler "
+                        "factor in the disk's g and on the sky, in front of the Kerr march.  static: it hovers (the Kerr frame, "
+                        "marched by the Kerr camera's kernel); circular: on the equatorial circular geodesic in the disk's sense "
+                        "(--pov in the plane z = 0); zamo: the frame-dragged, zero-angular-momentum observer (anywhere outside the "
+                        "static limit).  In a --video the velocity is evaluated at every frame's own position, so --orbit with "
+                        "circular is the fly-around.  infall is not offered under a spin.  Works with --supersample, --lens_flare, "
+                        "the grade, --video [--orbit], --video_codec mjpeg and --video_hdr.  Not with --spin_map, "
+                        "--spin_polarization, --observer, --projection, --light_delay, --shutter, --gpus > 1, --passes or --stars point")
+    p.add_argument("--spin_observer_velocity", type=float, nargs=3, default=argparse.SUPPRESS, metavar=("BX", "BY", "BZ"),
+                   help="the spinning hole's camera velocity given directly, in units of c as the static observer at the camera "
+                        "measures it, |beta| <= 0.995; instead of --spin_observer")
+    p.add_argument("--spin_observer_sky", type=str, default=argparse.SUPPRESS, choices=["shift", "plain"],
+                   help="--spin_observer / --spin_observer_velocity: shift (default) = the sky takes the Doppler factor too; plain = "
+                        "the sky is aberrated only")
+    p.add_argument("--spin_projection", type=str, default=argparse.SUPPRESS, choices=["equirect", "fisheye"],
+                   help="--spin / --redshift exact: --projection's equirectangular or fisheye camera in front of the Kerr march; "
+                        "frame sizes follow --projection's rule; combines with --spin_observer")
+    p.add_argument("--spin_projection_fov", type=float, nargs="+", default=argparse.SUPPRESS, metavar=("A", "B"),
+                   help="--spin_projection: its field of view, as --projection_fov")
     p.add_argument("--light_delay", type=float, nargs="?", const=1.0, default=argparse.SUPPRESS, metavar="SCALE",
                    help="light delay: every disk crossing is shaded at the time its light left the gas, so the far side of the disk "
                         "and the secondary image show the gas earlier than the near side does (tens of r_s / c: radians of orbital "
@@ -287,6 +308,27 @@ def parse_args(argv=None) -> argparse.Namespace:
                              hasattr(args, n) for n in ("polarization_fraction", "polarization_cell", "stokes_output", "polarization_ticks"))))):
             if on:
                 p.error(f"--spin_map does not combine with {flag}: it is a Schwarzschild march's or the Schwarzschild ray map's")
+    view = kerr_view_from_args(args)
+    if view:
+        # the Kerr camera (drivers.check_kerr_view: the refusal table's row): ahead of a spin's own refusals, so that each names it
+        from . import drivers
+        from .camera import orbit_position
+        try:
+            checked = drivers.check_kerr_view(
+                view["kerr_view"], spin=args.spin, redshift=args.redshift, disk_tilt=args.disk_tilt, anti_alias=args.anti_alias,
+                disk_model=args.disk_model, supersample_threshold=args.supersample_threshold, gpus=args.gpus,
+                observer=any(v is not None for v in (args.observer, args.observer_velocity, args.observer_sky, args.infall_to)),
+                projection=args.projection != "perspective" or args.projection_fov is not None, light_delay=hasattr(args, "light_delay"),
+                passes=args.passes is not None, shutter=args.shutter, maps=args.ray_map or args.orbit_map or args.shutter_map,
+                stars=args.stars == "point", spin_map=hasattr(args, "spin_map") or hasattr(args, "spin_polarization"))
+            if fov_given and checked["projection"] is not None:
+                raise ValueError(f"--spin_projection {checked['projection']} does not combine with --fov: that is the pinhole camera's "
+                                 "field of view (--spin_projection_fov is this one's)")
+            # the named velocity where the camera will stand: --pov, or frame 0 of an orbit (which keeps r and the height)
+            drivers.kerr_view_beta(checked, orbit_position(args.pov, 0, max(args.n_frames, 1), args.orbit_degrees)
+                                   if args.video and args.orbit else args.pov, args.spin)
+        except ValueError as e:
+            p.error(str(e))
     if args.spin != 0 or args.redshift == "exact":
         from .kerr import SPIN_MAX
         # the Kerr march: asked for by a spin, or by the exact redshift at spin 0
@@ -641,6 +683,20 @@ def projection_from_args(args) -> dict:
     return dict(projection=args.projection, projection_fov=None if fov is None else tuple(fov))
 
 
+def kerr_view_from_args(args) -> dict:
+    """The Kerr camera of a command line as drivers.render_image / render_video take it: {} without --spin_observer,
+    --spin_observer_velocity, --spin_observer_sky, --spin_projection or --spin_projection_fov."""
+    keys = (("observer", "spin_observer"), ("velocity", "spin_observer_velocity"), ("sky", "spin_observer_sky"),
+            ("projection", "spin_projection"), ("projection_fov", "spin_projection_fov"))
+    if not any(hasattr(args, flag) for _, flag in keys):
+        return {}
+    view = {k: getattr(args, flag, None) for k, flag in keys}
+    for k in ("velocity", "projection_fov"):
+        if view[k] is not None:
+            view[k] = tuple(view[k])
+    return {"kerr_view": view}
+
+
 def light_delay_from_args(args) -> dict:
     """The light delay of a command line as drivers.render_image / render_video take it: {} without --light_delay."""
     delay = getattr(args, "light_delay", None)
@@ -788,6 +844,11 @@ def main(argv=None) -> int:
     if proj_kw:
         from .projection import frame_size
         width, height = frame_size(args.projection, width, height)
+    # ... and the Kerr camera, whose projection sizes the frame by the same rule
+    view_kw = kerr_view_from_args(args)
+    if view_kw and view_kw["kerr_view"]["projection"] is not None:
+        from .projection import frame_size
+        width, height = frame_size(view_kw["kerr_view"]["projection"], width, height)
     # ... and the light delay
     delay_kw = light_delay_from_args(args)
     # ... and the polarisation
@@ -830,7 +891,7 @@ def main(argv=None) -> int:
                              shutter_map=args.shutter_map, map_supersample=args.map_supersample, video_hdr=args.video_hdr,
                              hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure, **stars_kw,
                              **(dict(observer=args.observer, observer_velocity=args.observer_velocity, observer_sky=sky,
-                                     infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw, **pol_kw,
+                                     infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw,
                              **({"spin_map": True} if hasattr(args, "spin_map") else {}))
         if world > 1:
             from . import distributed as D
@@ -856,6 +917,6 @@ def main(argv=None) -> int:
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
         grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw, **stars_kw,
-        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw, **pol_kw)
+        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

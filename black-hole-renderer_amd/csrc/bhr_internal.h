@@ -122,6 +122,13 @@ struct BhrKerrMarchArgs : BhrMarchArgs {          // march_kerr.hip
 struct BhrKerrExactMarchArgs : BhrKerrMarchArgs { // ... its exact-redshift kernels (the model ones keep the block above)
     float isco_r, isco_e, isco_l;                 // the ISCO of the disk's sense of rotation: its radius, and the energy -u_t and angular
 };                                                // momentum u_phi of its orbit, which the gas inside it keeps (ray_kerr.h: kerr_g_exact)
+struct BhrKerrViewMarchArgs : BhrKerrExactMarchArgs {   // march_kerr_observer.hip: the Kerr camera (bhr_render_kerr_view), both redshifts
+    float obs_beta[3];                            // the moving camera's velocity,
+    float obs_gamma, obs_g2;                      // gamma and gamma^2 / (gamma + 1),
+    int32_t obs_sky_shift;                        // whether the sky sample takes the Doppler factor,
+    int32_t proj_kind;                            // 0: the pinhole, else BHR_PROJ_*
+    float span_h, span_v;                         // and the projection's spans as in BhrProjectedMarchArgs
+};
 struct BhrObserverMarchArgs : BhrMarchArgs {      // march_observer.hip
     float obs_beta[3];                            // the moving camera's velocity,
     float obs_gamma, obs_g2;                      // gamma and gamma^2 / (gamma + 1),
@@ -150,14 +157,17 @@ struct bhr_march_part {
 
 // The marches that are not the Schwarzschild pinhole march of a camera at rest: each one object over a ray_*.h (march_device.h)
 // with the tile schedule, the texture source, no differentials, and a row of what the host knows of it (bhr_variant_row).
-enum bhr_march_variant { BHR_MV_NONE, BHR_MV_KERR, BHR_MV_KERR_EXACT, BHR_MV_OBSERVER, BHR_MV_PROJECTED, BHR_MV_DELAYED, BHR_MV_COUNT };
+enum bhr_march_variant { BHR_MV_NONE, BHR_MV_KERR, BHR_MV_KERR_EXACT, BHR_MV_OBSERVER, BHR_MV_PROJECTED, BHR_MV_DELAYED, BHR_MV_KERR_VIEW, BHR_MV_KERR_VIEW_EXACT,
+                         BHR_MV_COUNT };
 
 // What a frame's entry point (render.hip) asks of the march: the variant and its payload -- a projection comes with an observer
 // (at rest if the caller gave none), light delay with neither, none of them with a spin (bhr_variant_frame_check refuses it).
+// The Kerr camera's two (BHR_MV_KERR_VIEW, _EXACT: bhr_render_kerr_view) need the spin or the forced Kerr march, come with an
+// observer (at rest if the caller gave none) and may come with a projection (null: the pinhole).
 struct bhr_variant_request {
     bhr_march_variant variant = BHR_MV_NONE;
-    const bhr_observer *observer = nullptr;       // BHR_MV_OBSERVER, BHR_MV_PROJECTED: the camera's velocity
-    const bhr_projection *projection = nullptr;   // BHR_MV_PROJECTED
+    const bhr_observer *observer = nullptr;       // BHR_MV_OBSERVER, BHR_MV_PROJECTED, BHR_MV_KERR_VIEW*: the camera's velocity
+    const bhr_projection *projection = nullptr;   // BHR_MV_PROJECTED; BHR_MV_KERR_VIEW*: or null
     const bhr_light_delay *delay = nullptr;       // BHR_MV_DELAYED: the scale
 };
 
@@ -763,6 +773,7 @@ const void *bhr_march_kernel_observer(bhr_march_kernel k, int32_t diff, int32_t 
 const void *bhr_march_kernel_projected(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_projected.hip -> march_projected.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_delay(bhr_march_kernel k, int32_t diff, int32_t ss);      // march_delay.hip -> march_delay.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
+const void *bhr_march_kernel_kerr_view(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_kerr_observer.hip -> march_kerr_observer.o (as bhr_march_kernel_kerr)
 const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact);           // march_kerr_raymap.hip -> march_kerr_raymap.o (exact: the exact redshift's)
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
 

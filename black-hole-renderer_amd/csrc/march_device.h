@@ -44,6 +44,9 @@
 //              (bhr_set_spin, bhr_set_redshift); the Schwarzschild Rays know nothing of it; -ffp-contract=on, no fast-math
 //              (and march_kerr_raymap.hip -> march_kerr_raymap.o over the same Ray: the Kerr ray map's build, shade and
 //              overflow kernels, with the Kerr object's flags; its table is bhr_march_kernel_kerr_raymap)
+//   kerr_observer  the Kerr Ray launched along the aberrated pinhole, equirectangular or fisheye direction of a camera that may
+//              move, its Doppler factor in the disk's g and on the sky (bhr_render_kerr_view); the Kerr object's flags;
+//              camera_device.h holds what it shares with the next two (the projections' directions, the sky's scaling)
 //   observer   the strict Ray launched along the aberrated pixel direction of a moving camera, its Doppler factor in the
 //              disk's g and on the sky (bhr_render_observer); the strict flags, as the next two
 //   projected  the observer Ray launched along an equirectangular or fisheye pixel direction (bhr_render_projected)

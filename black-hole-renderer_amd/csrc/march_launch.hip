@@ -305,15 +305,17 @@ static void layers_stored(bhr_ctx *ctx, const BhrMarchArgs &a) {
 // The first kernel argument of a launch: the finished march block `a` itself, or for a variant `a` copied into the variant's own
 // block in `b` with its words behind it -- binary64, each rounded once (the variant's kernels take this block; nobody else reads it).
 union VariantArgs {
-    BhrKerrExactMarchArgs kerr;       // the model kernels read its first sizeof(BhrKerrMarchArgs) bytes
+    BhrKerrViewMarchArgs kerr;        // the model kernels read its first sizeof(BhrKerrMarchArgs) bytes, the exact ones' sizeof(BhrKerrExactMarchArgs)
     BhrProjectedMarchArgs observer;   // the observer's kernels its first sizeof(BhrObserverMarchArgs)
     BhrDelayMarchArgs delay;
 };
 static void *variant_args(const bhr_ctx *ctx, const bhr_variant_request &req, BhrMarchArgs &a, VariantArgs &b) {
     switch (req.variant) {
     case BHR_MV_KERR:
-    case BHR_MV_KERR_EXACT: {
-        BhrKerrExactMarchArgs &k = b.kerr;
+    case BHR_MV_KERR_EXACT:
+    case BHR_MV_KERR_VIEW:
+    case BHR_MV_KERR_VIEW_EXACT: {
+        BhrKerrViewMarchArgs &k = b.kerr;
         static_cast<BhrMarchArgs &>(k) = a;
         // the spinning hole: a = A M with M = r_s / 2 and the horizon's radius
         const double A = (double)ctx->kerr_spin;
@@ -322,7 +324,7 @@ static void *variant_args(const bhr_ctx *ctx, const bhr_variant_request &req, Bh
         // ... and, for the exact-redshift kernels alone, the ISCO of the disk's sense of rotation (prograde for A >= 0) with the
         // energy and angular momentum of its orbit (Bardeen, Press, Teukolsky 1972; M = 1/2, signed a, an orbit in the +phi sense)
         k.isco_r = k.isco_e = k.isco_l = 0.0f;
-        if (req.variant == BHR_MV_KERR_EXACT) {
+        if (req.variant == BHR_MV_KERR_EXACT || req.variant == BHR_MV_KERR_VIEW_EXACT) {
             const double M = 0.5, sa = 0.5 * A, q = fabs(A);
             const double z1 = 1.0 + cbrt(1.0 - q * q) * (cbrt(1.0 + q) + cbrt(1.0 - q));
             const double z2 = sqrt(3.0 * q * q + z1 * z1);
@@ -333,6 +335,24 @@ static void *variant_args(const bhr_ctx *ctx, const bhr_variant_request &req, Bh
             k.isco_r = (float)r;
             k.isco_e = (float)((r * sr - 2.0 * M * sr + sa * sm) / den);
             k.isco_l = (float)(sm * (r * r - 2.0 * sa * sm * sr + sa * sa) / den);
+        }
+        // ... and, for the Kerr camera's kernels alone, the camera behind that: the observer's words, then the projection's
+        // (kind 0: the pinhole)
+        if (req.variant == BHR_MV_KERR_VIEW || req.variant == BHR_MV_KERR_VIEW_EXACT) {
+            const float *beta = req.observer->beta;
+            const double gamma = 1.0 / sqrt(1.0 - ((double)beta[0] * beta[0] + (double)beta[1] * beta[1] + (double)beta[2] * beta[2]));
+            for (int c = 0; c < 3; ++c) k.obs_beta[c] = beta[c];
+            k.obs_gamma = (float)gamma;
+            k.obs_g2 = (float)(gamma * gamma / (gamma + 1.0));
+            k.obs_sky_shift = req.observer->sky_shift ? 1 : 0;
+            k.proj_kind = 0;
+            k.span_h = k.span_v = 0.0f;
+            if (const bhr_projection *pr = req.projection) {
+                const double rad = 3.14159265358979323846 / 180.0;
+                k.proj_kind = pr->kind;
+                k.span_h = pr->kind == BHR_PROJ_FISHEYE ? (float)((double)pr->fov_h_deg * rad / 2.0) : (float)((double)pr->fov_h_deg * rad);
+                k.span_v = pr->kind == BHR_PROJ_FISHEYE ? 0.0f : (float)((double)pr->fov_v_deg * rad);
+            }
         }
         return &k;
     }

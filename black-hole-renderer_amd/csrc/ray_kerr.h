@@ -140,7 +140,8 @@ __device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, float 
 //             r_isco: qb^2 - 4 qa qc = 4 (1 - E^2) (r_isco - r)^3 / (r rho^2), which is what is evaluated -- the literal
 //             difference vanishes at r_isco and its square root there is the square root of the rounding (3e-4 in f32).
 // tests/kerr_redshift_ref.py states the same in NumPy; tests/test_kerr_redshift_ref.py checks it against the 4 x 4 metric.
-__device__ __forceinline__ float kerr_g_exact(const BhrMarchArgs &a, float hx, float hy, float r, V3 ph) {
+// obs_d: nu_moving / nu_static of the ray at a camera that moves (ray_kerr_observer.h), a factor of nu_obs; 1 at rest.
+__device__ __forceinline__ float kerr_g_exact(const BhrMarchArgs &a, float hx, float hy, float r, V3 ph, float obs_d = 1.0f) {
     const BhrKerrExactMarchArgs &k = kerr_exact(a);
     const float ka = k.kerr_a, a2 = ka * ka;
     V3 c = ld3(a.cp);
@@ -170,7 +171,7 @@ __device__ __forceinline__ float kerr_g_exact(const BhrMarchArgs &a, float hx, f
         const float S = c0 + r * w / rho;
         nu_em = E - L * lz / rho2 - w * P + U * S / r;
     }
-    return fminf(nu_obs / fmaxf(nu_em, 1e-3f), BHR_G_FACTOR_CAP);
+    return fminf(nu_obs * obs_d / fmaxf(nu_em, 1e-3f), BHR_G_FACTOR_CAP);
 }
 
 // _apply_g_factor (render.py:2439-2516) for the untilted disk, unchanged but for the orbital frequency (Kerr's) and the
@@ -178,11 +179,11 @@ __device__ __forceinline__ float kerr_g_exact(const BhrMarchArgs &a, float hx, f
 // u^t (1 - Omega L_z) with frame dragging is kerr_g_exact above.  RS = KERR_EXACT: to_cam is the photon's momentum at the hit instead and
 // g is kerr_g_exact's; everything downstream of g is the same code.
 template <int RS>
-__device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color, float hit_x, float hit_y, float hit_r, V3 to_cam) {
+__device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color, float hit_x, float hit_y, float hit_r, V3 to_cam, float obs_d = 1.0f) {
     const float rs_f = BHR_RS;
     float g;
     if (RS == KERR_EXACT) {
-        g = kerr_g_exact(a, hit_x, hit_y, hit_r, to_cam);
+        g = kerr_g_exact(a, hit_x, hit_y, hit_r, to_cam, obs_d);
     } else {
         V3 cam_pos = ld3(a.cp);
         asm volatile("" : "+v"(cam_pos.x));          // recomputed per hit, not kept across the march loop (march_device.h: apply_g_factor)
@@ -204,7 +205,7 @@ __device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color
         const float g_doppler = 1.0f / (gamma * denom);
         const float grav_num = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_obs, rs_f + 1e-3f), 1e-6f));
         const float grav_den = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_em, rs_f + 1e-3f), 1e-6f));
-        g = fminf(g_doppler * (grav_num / grav_den), BHR_G_FACTOR_CAP);
+        g = fminf(g_doppler * (grav_num / grav_den) * obs_d, BHR_G_FACTOR_CAP);
     }
     const float intensity = fmaxf(powf(g, BHR_G_LUMINOSITY_POWER), 0.0f);
     float brightness = BHR_G_BRIGHTNESS_GAIN * intensity / (1.0f + intensity / BHR_G_FACTOR_CAP);
@@ -226,15 +227,16 @@ __device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color
     return out;
 }
 
-// one disk crossing, shaded and composited front to back (render.py:2951-3002 without the mip levels)
+// one disk crossing, shaded and composited front to back (render.py:2951-3002 without the mip levels); obs_d: the moving
+// camera's factor of g ahead of its cap in both redshift modes (1: the camera at rest)
 template <int RS>
-__device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam) {
+__device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam, float obs_d = 1.0f) {
     const float hit_r = sqrtf(hit_x * hit_x + hit_y * hit_y - kerr(a).kerr_a * kerr(a).kerr_a);
     if (!(a.r_outer >= hit_r && hit_r >= a.r_inner)) return;
     const float4 rgba = kerr_sample_disk(a, hit_x, hit_y, hit_r);
     const float base_alpha = fminf(rgba.w, 0.999f);
     const float disk_alpha = 1.0f - powf(1.0f - base_alpha, BHR_DISK_ALPHA_GAIN);
-    const V3 col = kerr_g_factor<RS>(a, mk(rgba.x, rgba.y, rgba.z), hit_x, hit_y, hit_r, to_cam);
+    const V3 col = kerr_g_factor<RS>(a, mk(rgba.x, rgba.y, rgba.z), hit_x, hit_y, hit_r, to_cam, obs_d);
     const float front = 1.0f - sh.alpha_total;
     const float wgt = disk_alpha * front;
     sh.accum = mk(sh.accum.x + col.x * wgt, sh.accum.y + col.y * wgt, sh.accum.z + col.z * wgt);
@@ -245,7 +247,7 @@ __device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh,
 // momentum (p_x, p_y, p_z) at the hit, interpolated like the hit point, in words 5..7 of the lane's parking slot -- the words a
 // ray with differentials would use, which the Kerr ray has none of -- and record_mom stores it beside the record.
 template <bool DIFF, int SRC = 0, bool MOM = false>
-struct Ray {
+struct KerrRay {
     static_assert(!DIFF && (SRC == 0 || SRC == KERR_EXACT), "the Kerr march has no ray differentials; its second parameter is the redshift, model or exact");
     V3 x, p;
     float r;       // Kerr-Schild radius of x
@@ -261,7 +263,10 @@ struct Ray {
     // (then 1 + l.p = Lam and dx/dl = s d; H = 0).  Outside the loop: IEEE operations.
     __device__ __forceinline__ void init(const BhrMarchArgs &a, int i, int j_local) {
         V3 unused_x, unused_y;
-        const V3 d = pixel_ray<false>(a, i, j_local, unused_x, unused_y);
+        init_along(a, pixel_ray<false>(a, i, j_local, unused_x, unused_y));
+    }
+    // the photon leaves the camera along d (ray_kerr_observer.h: a moving or panoramic camera's is not the pinhole pixel's own)
+    __device__ __forceinline__ void init_along(const BhrMarchArgs &a, const V3 d) {
         x = ld3(a.cp);
         const float ka = kerr(a).kerr_a, a2 = ka * ka;
         const float w = dot(x, x) - a2;
@@ -417,5 +422,12 @@ struct Ray {
     __device__ __forceinline__ void finish_at(const BhrMarchArgs &a, int i, int j) { write_pixel(a, i, j, escaped(a), velocity(a), sh); }
     __device__ __forceinline__ void values(const BhrMarchArgs &a, float bk[3], float dk[3]) const { pixel_values(a, escaped(a), velocity(a), sh, bk, dk); }
 };
+
+// The Ray the schedules and the Kerr map's kernels march: the Kerr one itself, unless the Ray header that included this file
+// derives its own from it (ray_kerr_observer.h) -- the idiom of ray_strict.h.
+#ifndef BHR_RAY_KERR_OBSERVER
+template <bool DIFF, int SRC = 0, bool MOM = false>
+using Ray = KerrRay<DIFF, SRC, MOM>;
+#endif
 
 }  // namespace

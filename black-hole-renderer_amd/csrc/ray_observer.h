@@ -18,6 +18,7 @@
 #pragma once
 #define BHR_RAY_OBSERVER 1   // ray_strict.h: the schedules' Ray is the one below, derived from the strict one
 #include "ray_strict.h"
+#include "camera_device.h"
 
 namespace {
 
@@ -25,17 +26,7 @@ namespace {
 // it to the shared schedule as the BhrMarchArgs it is; the observer code reads the tail through this.
 __device__ __forceinline__ const BhrObserverMarchArgs &observer(const BhrMarchArgs &a) { return static_cast<const BhrObserverMarchArgs &>(a); }
 
-// The sky through the moving camera: the sample scaled by the disk's brightness power of D and its Wien ratios, without the
-// brightness law's soft knee.  D is clamped to [0.1, BHR_G_FACTOR_CAP] like g; the result may exceed 1.
-__device__ __forceinline__ V3 observer_sky(V3 c, float D) {
-    const float Ds = fminf(fmaxf(D, 0.1f), BHR_G_FACTOR_CAP);
-    const float I = powf(Ds, BHR_G_LUMINOSITY_POWER);
-    const float w = 1.0f - 1.0f / Ds;
-    const float g_scale = expf(2.72f * w);
-    const float r_s = fminf(expf(2.21f * w) / g_scale, 3.0f);
-    const float b_s = fminf(expf(3.13f * w) / g_scale, 3.0f);
-    return mk(c.x * (r_s * I), c.y * I, c.z * (b_s * I));
-}
+// (observer_sky, the sky sample through the moving camera, is camera_device.h's: the Kerr camera scales its sky alike)
 
 template <bool DIFF, int SRC = 0>
 struct ObserverRay : StrictRay<DIFF, SRC> {

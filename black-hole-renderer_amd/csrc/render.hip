@@ -253,7 +253,8 @@ int32_t bhr_render(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
     return frame_on_next_slot(ctx, flags, exclusive, [&](int k, int ring, frame_marches *fm) { return render_on_slot(ctx, cam, flags, k, ring, fm, req); });
 }
 
-// The frame of a request that names its variant (bhr_render_observer, bhr_render_projected, bhr_render_delayed), behind the
+// The frame of a request that names its variant (bhr_render_observer, bhr_render_projected, bhr_render_delayed,
+// bhr_render_kerr_view), behind the
 // entry point's checks of its own payload: the variant's refusals (bhr_variant_frame_check), then the frame.  Everything that
 // can refuse does so before the frame takes a slot; like bhr_render_shutter the frame neither triggers nor counts towards the
 // calibration of slot 1's stream.
@@ -272,6 +273,19 @@ static int32_t observer_beta_check(const bhr_observer *obs, const char *who) {
     return BHR_OK;
 }
 
+// The kind and the field of view of a panoramic camera, as bhr_render_projected and bhr_render_kerr_view take them.
+static int32_t projection_check(const bhr_projection *proj, const char *who) {
+    if (proj->kind != BHR_PROJ_EQUIRECT && proj->kind != BHR_PROJ_FISHEYE)
+        return bhr_fail(BHR_ERR_INVALID, "%s: projection kind %d (BHR_PROJ_EQUIRECT or BHR_PROJ_FISHEYE)", who, proj->kind);
+    const bool eq = proj->kind == BHR_PROJ_EQUIRECT;
+    if (!(proj->fov_h_deg > 0.0f && proj->fov_h_deg <= 360.0f))       // a NaN fails the comparison too
+        return bhr_fail(BHR_ERR_INVALID, "%s: %s projection with fov_h_deg = %g: in (0, 360] and no NaN", who, eq ? "equirectangular" : "fisheye", (double)proj->fov_h_deg);
+    if (eq && !(proj->fov_v_deg > 0.0f && proj->fov_v_deg <= 180.0f))
+        return bhr_fail(BHR_ERR_INVALID, "%s: equirectangular projection with fov_v_deg = %g: in (0, 180] and no NaN", who, (double)proj->fov_v_deg);
+    return BHR_OK;
+}
+static const bhr_observer observer_at_rest = {{0.0f, 0.0f, 0.0f}, 0};   // a call without a velocity: at rest, with a plain sky
+
 // One frame as a moving camera sees it (include/bhr.h).
 int32_t bhr_render_observer(bhr_ctx *ctx, const bhr_camera *cam, const bhr_observer *obs, uint32_t flags) {
     const char *who = "bhr_render_observer";
@@ -285,17 +299,25 @@ int32_t bhr_render_observer(bhr_ctx *ctx, const bhr_camera *cam, const bhr_obser
 int32_t bhr_render_projected(bhr_ctx *ctx, const bhr_camera *cam, const bhr_projection *proj, const bhr_observer *obs, uint32_t flags) {
     const char *who = "bhr_render_projected";
     if (!ctx || !cam || !proj) return bhr_fail(BHR_ERR_INVALID, "%s: null argument (ctx, cam and proj are needed)", who);
-    if (proj->kind != BHR_PROJ_EQUIRECT && proj->kind != BHR_PROJ_FISHEYE)
-        return bhr_fail(BHR_ERR_INVALID, "%s: projection kind %d (BHR_PROJ_EQUIRECT or BHR_PROJ_FISHEYE)", who, proj->kind);
-    const bool eq = proj->kind == BHR_PROJ_EQUIRECT;
-    if (!(proj->fov_h_deg > 0.0f && proj->fov_h_deg <= 360.0f))       // a NaN fails the comparison too
-        return bhr_fail(BHR_ERR_INVALID, "%s: %s projection with fov_h_deg = %g: in (0, 360] and no NaN", who, eq ? "equirectangular" : "fisheye", (double)proj->fov_h_deg);
-    if (eq && !(proj->fov_v_deg > 0.0f && proj->fov_v_deg <= 180.0f))
-        return bhr_fail(BHR_ERR_INVALID, "%s: equirectangular projection with fov_v_deg = %g: in (0, 180] and no NaN", who, (double)proj->fov_v_deg);
-    static const bhr_observer at_rest = {{0.0f, 0.0f, 0.0f}, 0};
-    const bhr_observer o = obs ? *obs : at_rest;
+    BHR_TRY(projection_check(proj, who));
+    const bhr_observer o = obs ? *obs : observer_at_rest;
     BHR_TRY(observer_beta_check(&o, who));
     return variant_frame(ctx, cam, {BHR_MV_PROJECTED, &o, proj}, flags, who);
+}
+
+// One frame of the spinning hole through the Kerr camera (include/bhr.h): bhr_render's Kerr frame marched by the Kerr camera's
+// object, under the context's redshift.  obs null: the camera hovers (the static observer); proj null: the pinhole.
+int32_t bhr_render_kerr_view(bhr_ctx *ctx, const bhr_camera *cam, const bhr_observer *obs, const bhr_projection *proj, uint32_t flags) {
+    const char *who = "bhr_render_kerr_view";
+    if (!ctx || !cam) return bhr_fail(BHR_ERR_INVALID, "%s: null argument (ctx and cam are needed)", who);
+    if (!ctx->kerr_on)
+        return bhr_fail(BHR_ERR_INVALID, "%s: a Kerr view without the Kerr march: set a spin, or force_kerr at spin 0, first (bhr_set_spin)", who);
+    if (proj) BHR_TRY(projection_check(proj, who));
+    const bhr_observer o = obs ? *obs : observer_at_rest;
+    BHR_TRY(observer_beta_check(&o, who));
+    const bhr_march_variant v = ctx->kerr_redshift == BHR_REDSHIFT_EXACT ? BHR_MV_KERR_VIEW_EXACT : BHR_MV_KERR_VIEW;
+    BHR_TRY(bhr_kerr_camera_check(ctx, cam, who));
+    return variant_frame(ctx, cam, {v, &o, proj}, flags, who);
 }
 
 // One frame with every disk crossing shaded at its emission time (include/bhr.h): bhr_render's frame marched by the delay object.

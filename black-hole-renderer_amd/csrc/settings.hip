@@ -53,6 +53,9 @@ const bhr_variant_row &bhr_variant_row_of(bhr_march_variant v) {
         {bhr_march_kernel_projected, BHR_MK_TILE, "a projection", "observer", obs_diff, obs_exact, rest_rows, rest_flags, false},
         {bhr_march_kernel_delay, BHR_MK_TILE, "light delay", "delayed", "the delayed march has no ray differentials", "the delayed march is Schwarzschild's",
          rest_rows, rest_flags, false},
+        // the Kerr camera (bhr_render_kerr_view): the Kerr rows' refusals with the observer's flags and whole-frame context
+        {bhr_march_kernel_kerr_view, BHR_MK_TILE, "a Kerr view at spin %g", "Kerr", kerr_diff, nullptr, rest_rows, rest_flags, true},
+        {bhr_march_kernel_kerr_view, BHR_MK_KERR_EXACT, "a Kerr view at spin %g", "Kerr", kerr_diff, nullptr, rest_rows, rest_flags, true},
     };
     return rows[v];
 }
@@ -78,7 +81,8 @@ int32_t bhr_variant_frame_check(const bhr_ctx *ctx, bhr_march_variant v, uint32_
     char what[48];
     snprintf(what, sizeof(what), r.noun, spin);
     if (const uint32_t bad = flags & ~r.flags_ok) {
-        if (!r.kerr) return bhr_fail(BHR_ERR_INVALID, "%s: %s with flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, what, flags);
+        // (the rows that take the two post-pass flags only say so; the Kerr march's own rows take all but the two they name)
+        if ((r.flags_ok | BHR_PERSISTENT | BHR_ROW_COSTS) != ~(uint32_t)0) return bhr_fail(BHR_ERR_INVALID, "%s: %s with flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, what, flags);
         return bhr_fail(BHR_ERR_INVALID, "%s: %s with %s", who, what,
                         (bad & BHR_PERSISTENT) ? "BHR_PERSISTENT: the Kerr march has the tile schedule only" : "BHR_ROW_COSTS: the Kerr march fills no row-cost profile");
     }
@@ -163,6 +167,13 @@ int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t ss, int32_t out[3]) {
     if (mode != BHR_REDSHIFT_MODEL && mode != BHR_REDSHIFT_EXACT)
         return bhr_fail(BHR_ERR_INVALID, "bhr_kerr_redshift_resources: unknown mode %d (BHR_REDSHIFT_MODEL = 0, BHR_REDSHIFT_EXACT = 1)", mode);
     return bhr_march_resources("bhr_kerr_redshift_resources", mode == BHR_REDSHIFT_EXACT ? BHR_MV_KERR_EXACT : BHR_MV_KERR, 0, 0, ss, out);
+}
+
+// ... of the Kerr camera's kernels (bhr_render_kerr_view), by redshift mode
+int32_t bhr_kerr_view_resources(int32_t mode, int32_t ss, int32_t out[3]) {
+    if (mode != BHR_REDSHIFT_MODEL && mode != BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_kerr_view_resources: unknown mode %d (BHR_REDSHIFT_MODEL = 0, BHR_REDSHIFT_EXACT = 1)", mode);
+    return bhr_march_resources("bhr_kerr_view_resources", mode == BHR_REDSHIFT_EXACT ? BHR_MV_KERR_VIEW_EXACT : BHR_MV_KERR_VIEW, 0, 0, ss, out);
 }
 
 int32_t bhr_set_supersample(bhr_ctx *ctx, int32_t k) {

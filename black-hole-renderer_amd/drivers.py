@@ -233,7 +233,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  passes_path: Optional[str] = None, spin: float = 0.0, redshift: str = "model",
                  observer=None, observer_sky: bool = True, stars: Optional[dict] = None,
                  projection: Optional[str] = None, projection_fov=None, light_delay=None, polarization: Optional[dict] = None,
-                 stokes_path: Optional[str] = None, ticks_path: Optional[str] = None, kerr_polarization: Optional[dict] = None) -> np.ndarray:
+                 stokes_path: Optional[str] = None, ticks_path: Optional[str] = None, kerr_polarization: Optional[dict] = None,
+                 kerr_view: Optional[dict] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -260,8 +261,16 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     of the disk (check_polarization): the view's ray map is built and the frame is shaded from it, the way ``stars`` does it, by the
     strict arithmetic whatever ``math`` says, with the Stokes pass behind the shade; ``stokes_path`` then takes the planes, the cell
     grid, the field, Pi_0, the convention and the camera as a compressed .npz (bhr_amd.polarization.write_stokes) and ``ticks_path``
-    the frame with a polarisation tick per cell drawn over it (draw_ticks) as a PNG."""
+    the frame with a polarisation tick per cell drawn over it (draw_ticks) as a PNG.  ``kerr_view``: None, or the Kerr camera of a
+    spinning hole (check_kerr_view: a named or fixed velocity, the sky's shift, an equirect or fisheye projection) -- the frame is
+    HipRenderer.render_async(kerr_observer=, kerr_projection=)'s."""
     check_depth_and_dither(bit_depth, dither=dither)
+    kerr_view = check_kerr_view(kerr_view, spin=spin, redshift=redshift, disk_tilt=disk_tilt, anti_alias=anti_alias, disk_model=disk_model,
+                                supersample_threshold=supersample_threshold, gpus=gpus, observer=observer is not None,
+                                projection=projection is not None, light_delay=light_delay is not None, passes=passes_path is not None,
+                                stars=stars is not None, spin_map=kerr_polarization is not None)
+    if kerr_view is not None:                                  # refused ahead of any device work, like the rest
+        kerr_view_beta(kerr_view, cam_pos, spin)
     facts = dict(anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus, spin=spin,
                  redshift=redshift, passes=passes_path is not None)      # what the three variant checks take alike
     check_light_delay(light_delay, observer=observer is not None, projection=projection is not None, stars=stars is not None, **facts)
@@ -329,6 +338,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         renderer.build_ray_map(cam_pos, fov)
         renderer.render_from_ray_map_async(frame=0)
         img = renderer.read_layer(_lib.LAYER_FINAL)
+    elif kerr_view is not None:
+        img = renderer.render(cam_pos, fov, frame=0, **_kerr_view_kw(kerr_view, kerr_view_beta(kerr_view, cam_pos, spin)))
     else:
         img = renderer.render(cam_pos, fov, frame=0, observer=observer, observer_sky=observer_sky, projection=projection,
                               projection_fov=projection_fov, light_delay=light_delay)
@@ -375,6 +386,12 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
 # refusal behind the variant's noun, with the variant's own words in braces.  _VARIANTS: per variant those words and the
 # conditions it refuses (an observer takes any ``world``: frame-sharded observer videos are legal).
 _VARIANT_REFUSALS = (
+    ("no_spin", lambda f: f["spin"] == 0 and f["redshift"] == "model",
+     "needs --spin or --redshift exact: it is the camera of the Kerr march; a hole that does not spin takes --observer and --projection"),
+    ("spin_map", lambda f: f["spin_map"], "does not combine with --spin_map or --spin_polarization: {map}"),
+    ("schwarzschild_marches", lambda f: f["observer"] or f["projection"] or f["light_delay"],
+     "does not combine with --observer, --projection or --light_delay: those marches are Schwarzschild's"),
+    ("disk_tilt", lambda f: f["disk_tilt"] != 0, "does not combine with disk_tilt other than 0: the spin axis is the disk normal"),
     ("anti_alias", lambda f: f["anti_alias"] not in ("disabled", 0, False, None), "does not combine with anti_alias: {no_diff}"),
     ("disk_model", lambda f: f["disk_model"] != "texture", "does not combine with disk_model v2 / v2_volume: the {march} march shades the disk texture"),
     ("supersample_threshold", lambda f: f["supersample_threshold"] is not None,
@@ -402,6 +419,11 @@ _VARIANTS = {
     "light_delay": dict(noun="light_delay", march="delayed", cam="without the light's travel time", no_diff="the delayed march has no ray differentials",
                         no_exact="with the model redshift", map="a ray map's records hold no travel time", of_map=", whose records hold no travel time",
                         refuses="anti_alias disk_model supersample_threshold gpus world spin observer projection passes shutter maps stars"),
+    # the Kerr camera (--spin_observer, --spin_projection and their companions; HipRenderer.render_async(kerr_observer=, kerr_projection=))
+    "kerr_view": dict(noun="--spin_observer / --spin_projection", march="Kerr", cam="Schwarzschild rays",
+                      no_diff="ray differentials around a spinning hole need Kerr's variational equations",
+                      map="a ray map holds the rays of the pinhole camera at rest", of_map=" of Schwarzschild rays",
+                      refuses="no_spin spin_map schwarzschild_marches disk_tilt anti_alias disk_model supersample_threshold gpus passes shutter maps stars"),
 }
 
 
@@ -460,6 +482,66 @@ def check_light_delay(scale, anti_alias="disabled", disk_model: str = "texture",
         raise ValueError(f"light_delay is a scale in [0, 16], got {scale!r}")
     _check_variant("light_delay", locals())
     return out
+
+
+def check_kerr_view(kerr_view, spin: float = 0.0, redshift: str = "model", disk_tilt: float = 0.0, anti_alias="disabled",
+                    disk_model: str = "texture", supersample_threshold=None, gpus: int = 1, observer: bool = False, projection: bool = False,
+                    light_delay: bool = False, passes: bool = False, shutter: float = 0.0, maps: bool = False, stars: bool = False,
+                    spin_map: bool = False):
+    """kerr_view=dict(observer=, velocity=, sky=, projection=, projection_fov=): the Kerr camera of a spinning hole (--spin_observer
+    and its companions) -> the dict with its defaults filled in, or None without one.  ``observer``: "static", "circular" or
+    "zamo" (bhr_amd.observer.kerr_velocity) or ``velocity``: a fixed beta, one of the two at most; ``sky``: "shift" (default) or
+    "plain"; ``projection``: "equirect" or "fisheye" with ``projection_fov`` (bhr_amd.projection.check).  It needs a spin or the
+    exact redshift and takes what the Kerr march takes, on one GPU, marched: no Kerr ray map or Kerr polarisation, none of the
+    Schwarzschild marches, no shutter, ray map, passes or point stars.  Raises ValueError, naming the combination, before any
+    device work."""
+    if kerr_view is None:
+        return None
+    from . import observer as obs_mod
+    unknown = set(kerr_view) - {"observer", "velocity", "sky", "projection", "projection_fov"}
+    if unknown:
+        raise ValueError(f"kerr_view takes observer, velocity, sky, projection and projection_fov, got {sorted(kerr_view)}")
+    out = dict(observer=kerr_view.get("observer"), velocity=kerr_view.get("velocity"), sky=kerr_view.get("sky"),
+               projection=kerr_view.get("projection"), projection_fov=kerr_view.get("projection_fov"))
+    if out["observer"] is not None and out["velocity"] is not None:
+        raise ValueError("--spin_observer names a velocity and --spin_observer_velocity gives one: take one of the two")
+    if out["observer"] == "infall":
+        raise ValueError("--spin_observer infall is not offered: the free fall from rest at infinity is not radial around a spinning hole "
+                         f"(one of {obs_mod.KERR_KINDS})")
+    if out["observer"] is not None and out["observer"] not in obs_mod.KERR_KINDS:
+        raise ValueError(f"--spin_observer must be one of {obs_mod.KERR_KINDS}, got {out['observer']!r}")
+    if out["sky"] is not None and out["observer"] is None and out["velocity"] is None:
+        raise ValueError("--spin_observer_sky needs --spin_observer or --spin_observer_velocity: it belongs to a camera that moves")
+    out["sky"] = obs_mod.check_sky("shift" if out["sky"] is None else out["sky"])
+    if out["velocity"] is not None:
+        out["velocity"] = obs_mod.check_beta(out["velocity"])
+    if out["projection"] is None and out["projection_fov"] is not None:
+        raise ValueError("--spin_projection_fov needs --spin_projection equirect or fisheye: it is the field of view of that camera")
+    if out["projection"] is not None:
+        from .projection import check
+        _, fov_h, fov_v = check(out["projection"], out["projection_fov"])
+        out["projection_fov"] = (fov_h, fov_v) if out["projection"] == "equirect" else (fov_h,)
+    if out["observer"] is None and out["velocity"] is None and out["projection"] is None:
+        raise ValueError("kerr_view needs an observer, a velocity or a projection")
+    _check_variant("kerr_view", locals())
+    return out
+
+
+def kerr_view_beta(kerr_view: dict, pos, spin: float):
+    """The velocity of the Kerr camera ``kerr_view`` (check_kerr_view's dict) at ``pos``: its fixed one, its named one evaluated
+    there, or None for a camera without either (a projection at rest)."""
+    from . import observer as obs_mod
+    if kerr_view["velocity"] is not None:
+        return tuple(kerr_view["velocity"])
+    if kerr_view["observer"] is not None:
+        return tuple(float(v) for v in obs_mod.kerr_velocity(kerr_view["observer"], pos, spin))
+    return None
+
+
+def _kerr_view_kw(kerr_view: dict, beta) -> dict:
+    """HipRenderer.render_async's keywords of one frame of the Kerr camera moving with ``beta`` (None: the call without a velocity)."""
+    return dict(kerr_observer=beta, kerr_observer_sky=kerr_view["sky"] == "shift", kerr_projection=kerr_view["projection"],
+                kerr_projection_fov=kerr_view["projection_fov"])
 
 
 def check_passes(passes_path, gpus: int = 1, supersample: int = 1, disk_model: str = "texture") -> None:
@@ -842,7 +924,7 @@ def hdr_sidecar(hdr: dict, max_cll: float, max_fall: float, frames: int) -> dict
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
                     shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None,
-                    stars=None, projection=None, light_delay=None, polarization=None, spin_map=False) -> dict:
+                    stars=None, projection=None, light_delay=None, polarization=None, spin_map=False, kerr_view=None) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -880,6 +962,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(light_delay=light_delay)
     if polarization is not None:
         params.update(polarization={"field": list(polarization["field"]), "fraction": polarization["fraction"], "cell": polarization["cell"]})
+    if kerr_view is not None:
+        params.update(kerr_view={k: (list(v) if isinstance(v, tuple) else v) for k, v in kerr_view.items()})
     return params
 
 
@@ -920,7 +1004,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  observer: Optional[str] = None, observer_velocity=None, observer_sky: bool = True,
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
                  light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, spin_map: bool = False,
-                 kerr_polarization: Optional[dict] = None,
+                 kerr_polarization: Optional[dict] = None, kerr_view: Optional[dict] = None,
                  **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
@@ -1045,7 +1129,26 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     .npz at ``stokes_path`` (default ``<output stem>.stokes.npz``) with ``cells`` of shape (n_frames, gh, gw, 3).  Refused with
     ValueError, before any device work, with what check_polarization names, and with a resume that finds frames already rendered
     (their grids are gone).  The renderer's polarisation is switched off on return.  The progress record names the polarisation
-    only when it is set."""
+    only when it is set.
+
+    ``kerr_view`` (check_kerr_view's dict; the renderer has a spin or the exact redshift set): every frame is
+    render_async(..., kerr_observer=beta_f, kerr_projection=...) -- the Kerr march through the Kerr camera, with the named velocity
+    evaluated at that frame's own camera position (bhr_amd.observer.kerr_frame_plan), so an ``orbit`` with "circular" is the
+    fly-around on the equatorial geodesic.  Refused with ValueError, before any device work, with what check_kerr_view names.  The
+    progress record carries the camera when one is given, and a resume under another starts over."""
+    kerr_plan = None
+    if kerr_view is not None:                                   # (without one the renderer is not asked anything, as ever)
+        from . import observer as obs_mod
+        kerr_view = check_kerr_view(kerr_view, spin=renderer.spin, redshift=renderer.redshift, disk_tilt=renderer.disk_tilt,
+                                    anti_alias=renderer.anti_alias, disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2",
+                                    supersample_threshold=supersample_threshold if supersample is not None or supersample_threshold is not None
+                                    else getattr(renderer, "supersample_threshold", None),
+                                    observer=observer is not None or observer_velocity is not None or infall_to is not None,
+                                    projection=projection is not None or projection_fov is not None, light_delay=light_delay is not None,
+                                    shutter=shutter, maps=ray_map or orbit_map or shutter_map, stars=stars is not None,
+                                    spin_map=spin_map or kerr_polarization is not None)
+        if kerr_view["observer"] is not None or kerr_view["velocity"] is not None:
+            kerr_plan = obs_mod.kerr_frame_plan(n_frames, static_cam_pos, renderer.spin, kerr_view["observer"], kerr_view["velocity"], orbit, orbit_degrees)
     moving = observer is not None or observer_velocity is not None or infall_to is not None
     projected = projection is not None or projection_fov is not None
     disk_model = "texture" if getattr(renderer, "_dv2", None) is None else "v2"
@@ -1146,7 +1249,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                              **({} if stars is None else {"stars": stars}),
                              **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}),
                              **({} if light_delay is None else {"light_delay": light_delay}),
-                             **({} if polarization is None else {"polarization": polarization}), spin_map=spin_map)
+                             **({} if polarization is None else {"polarization": polarization}), spin_map=spin_map, kerr_view=kerr_view)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -1280,6 +1383,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                         stokes_grids[frame] = renderer.stokes_cells()      # the frame's cell grid (synchronises: a few kB per frame)
                 elif shutter > 0:
                     renderer.render_shutter_async(fr["positions"], fov, fr["t_offsets"])
+                elif kerr_view is not None:                        # marched by the Kerr camera's object, at the frame's own velocity
+                    renderer.render_async(cam_pos, fov, frame=0, **_kerr_view_kw(kerr_view, None if kerr_plan is None else kerr_plan[frame][1]))
                 else:                                              # marched: the frame of the moving camera, through the projection, with light delay
                     renderer.render_async(cam_pos, fov, frame=0, observer=None if plan is None else beta, observer_sky=observer_sky,
                                           projection=projection, projection_fov=projection_fov, light_delay=light_delay)   # (lens flare: on the device)

@@ -65,6 +65,80 @@ def velocity(kind: str, pos) -> np.ndarray:
     return b
 
 
+KERR_KINDS = ("static", "circular", "zamo")
+
+
+def kerr_velocity(kind: str, pos, A: float) -> np.ndarray:
+    """beta of a named observer at camera position ``pos`` (Kerr-Schild coordinates) around a hole of spin A = a / M, as the static
+    observer there measures it (binary64; a = A / 2, M = 1/2).  From pos: w = |pos|^2 - a^2, S = sqrt(w^2 + 4 a^2 z^2),
+    r^2 = (w + S) / 2, Sigma = S, sin^2 theta = (x^2 + y^2) / (r^2 + a^2), and the metric's
+    g_tt = -(1 - r / Sigma), g_tphi = -a r sin^2 theta / Sigma, g_phiphi = (r^2 + a^2 + a^2 r sin^2 theta / Sigma) sin^2 theta.
+    A camera with angular velocity Omega (positive in the disk's sense, the hole's for A > 0) has
+    u^t = 1 / sqrt(-(g_tt + 2 g_tphi Omega + g_phiphi Omega^2)), gamma = u^t (-g_tt - g_tphi Omega) / sqrt(-g_tt),
+    beta = sign(Omega) sqrt(1 - 1 / gamma^2) along (y, -x, 0) / sqrt(x^2 + y^2), the disk's v_hat = r_hat x z_hat.
+    static    0
+    circular  Omega = sqrt(M) / (r^1.5 + a sqrt(M)), the equatorial circular geodesic in the disk's sense; the equatorial camera
+              only (|z| <= 1e-6 |pos|), refused where there is no such orbit or beta > 0.995; at A = 0 it is velocity("circular")
+    zamo      Omega = -g_tphi / g_phiphi, the zero-angular-momentum (frame-dragged) observer; anywhere outside the static limit,
+              0 on the axis
+    infall is not offered under a spin: its direction is not radial there."""
+    if kind == "infall":
+        raise ValueError("observer infall under a spin: the free fall from rest at infinity is not radial around a spinning hole; "
+                         f"one of {KERR_KINDS}")
+    if kind not in KERR_KINDS:
+        raise ValueError(f"observer under a spin must be one of {KERR_KINDS}, got {kind!r}")
+    A = float(A)
+    if not abs(A) <= 0.998:              # NaN included
+        raise ValueError(f"spin a / M = {A!r} (|a / M| <= 0.998)")
+    p = np.array([float(v) for v in pos], dtype=np.float64)
+    n = float(np.linalg.norm(p))
+    if not (n > 0.0 and math.isfinite(n)):
+        raise ValueError(f"observer {kind}: no camera position at {list(pos)}")
+    if kind == "static":
+        return np.zeros(3)
+    M, a = 0.5, 0.5 * A
+    x, y, z = p
+    w = n * n - a * a
+    S = math.sqrt(w * w + 4.0 * a * a * z * z)
+    r2 = 0.5 * (w + S)
+    r = math.sqrt(r2)
+    s2 = (x * x + y * y) / (r2 + a * a)
+    g_tt = -(1.0 - r / S)
+    g_tp = -a * r * s2 / S
+    g_pp = (r2 + a * a + a * a * r * s2 / S) * s2
+    if not g_tt < 0.0:
+        raise ValueError(f"observer {kind}: the camera at {list(pos)} lies inside the static limit of the hole of spin {A:g}")
+    if kind == "circular":
+        if abs(z) > 1e-6 * n:
+            raise ValueError(f"observer circular under a spin: the camera at {list(pos)} is off the equatorial plane, where no circular geodesic lies")
+        om = math.sqrt(M) / (r ** 1.5 + a * math.sqrt(M))
+    else:
+        if not g_pp > 0.0:               # on the axis: the frame-dragged observer is the static one
+            return np.zeros(3)
+        om = -g_tp / g_pp
+    rad = -(g_tt + 2.0 * g_tp * om + g_pp * om * om)
+    if not rad > 0.0:
+        raise ValueError(f"observer {kind}: no such orbit at r = {r:g} around the hole of spin {A:g} (inside its photon orbit)")
+    # sign(Omega) sqrt(1 - 1 / gamma^2) without its cancellation at small beta: 1 - 1 / gamma^2 is
+    # Omega^2 (g_tphi^2 - g_tt g_phiphi) / (g_tt + g_tphi Omega)^2 identically, which is 0 where Omega is
+    beta = om * math.sqrt(g_tp * g_tp - g_tt * g_pp) / (-g_tt - g_tp * om)
+    if abs(beta) > BETA_MAX:
+        raise ValueError(f"observer {kind}: beta = {beta:g} at r = {r:g} around the hole of spin {A:g}, at most {BETA_MAX}")
+    rho = math.sqrt(x * x + y * y)
+    return beta * np.array([y / rho, -x / rho, 0.0])
+
+
+def kerr_frame_plan(n_frames: int, pov, A: float, kind=None, beta=None, orbit: bool = False, orbit_degrees: float = 360.0) -> list:
+    """frame_plan for the spinning hole: [(camera position, beta)] with kerr_velocity(kind, position, A) at every frame's own
+    position, or the fixed ``beta``."""
+    from .camera import orbit_position
+    positions = [[float(v) for v in (orbit_position(pov, f, n_frames, orbit_degrees) if orbit else pov)] for f in range(n_frames)]
+    if beta is not None:
+        b = check_beta(beta)
+        return [(pos, b) for pos in positions]
+    return [(pos, tuple(float(v) for v in kerr_velocity(kind or "static", pos, A))) for pos in positions]
+
+
 def infall_radii(r0: float, r1: float, n: int) -> np.ndarray:
     """Radii of an n-frame radial fall from r0 to r1, uniform in the proper time of the observer who falls from rest at
     infinity (d tau = -sqrt(r) dr): r_k = (r0^1.5 + k / (n - 1) (r1^1.5 - r0^1.5))^(2/3); one frame stays at r0."""

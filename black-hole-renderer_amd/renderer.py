@@ -457,7 +457,8 @@ class HipRenderer:
 
     def render_async(self, cam_pos, fov: float, frame: int = 0, skip_differentials: bool = False,
                      skip_bloom: bool = False, compaction: bool = False, math=None, lens_flare=None,
-                     observer=None, observer_sky: bool = True, projection=None, projection_fov=None, light_delay=None) -> None:
+                     observer=None, observer_sky: bool = True, projection=None, projection_fov=None, light_delay=None,
+                     kerr_observer=None, kerr_observer_sky: bool = True, kerr_projection=None, kerr_projection_fov=None) -> None:
         """Launch march + bloom + combine; the frame stays in HBM (counterpart of render_to_field,
         render.py:3819-3863, without the GUI flip).
 
@@ -477,7 +478,23 @@ class HipRenderer:
         roll under t_offset - scale * T with T the coordinate time along the ray (bhr_render_delayed; include/bhr.h states the
         model).  1 is physical, larger values exaggerate, 0 is the strict frame.  Marched by the delayed kernel whatever ``math``
         the renderer has; refused together with ``observer``, ``projection`` or ``math=``.  The scale belongs to this call
-        alone.  None (the default): the whole disk at the frame's one instant, as ever."""
+        alone.  None (the default): the whole disk at the frame's one instant, as ever.
+
+        ``kerr_observer`` / ``kerr_projection``: the same camera model in front of the Kerr march of a renderer with a spin (or
+        the forced Kerr march) set (bhr_render_kerr_view; include/bhr.h states the model, bhr_amd.observer.kerr_velocity names
+        velocities).  ``kerr_observer``: a velocity as the static observer at ``cam_pos`` measures it, or "rest" for the call
+        without one; ``kerr_observer_sky``: the Doppler factor on the sky; ``kerr_projection`` and ``kerr_projection_fov``:
+        as ``projection`` and ``projection_fov``.  Either selects the Kerr camera; at rest under the pinhole the frame is the
+        Kerr frame of this method bit for bit.  Refused together with ``observer``, ``projection``, ``light_delay`` or ``math=``.
+        None (the default): the hovering pinhole camera, as ever."""
+        kerr_view = kerr_observer is not None or kerr_projection is not None or kerr_projection_fov is not None
+        if kerr_view:
+            if observer is not None or projection is not None or light_delay is not None or math is not None:
+                raise ValueError("kerr_observer / kerr_projection do not combine with observer, projection, light_delay or math=: "
+                                 "those marches are Schwarzschild's, the Kerr camera is the Kerr march's own")
+            if kerr_projection is None and kerr_projection_fov is not None:
+                raise ValueError("kerr_projection_fov without kerr_projection")
+            projection, projection_fov = kerr_projection, kerr_projection_fov     # checked and turned into a bhr_projection below
         if light_delay is not None:
             if observer is not None or projection is not None or math is not None:
                 raise ValueError("light_delay does not combine with observer, projection or math=: the delayed march is the strict "
@@ -498,6 +515,19 @@ class HipRenderer:
             obs = _lib.Observer()
             obs.beta[:] = obs_mod.check_beta(observer)
             obs.sky_shift = 1 if observer_sky else 0
+        if kerr_view:
+            from . import observer as obs_mod
+            kobs = None
+            if kerr_observer is not None and not (isinstance(kerr_observer, str) and kerr_observer == "rest"):
+                kobs = _lib.Observer()
+                kobs.beta[:] = obs_mod.check_beta(kerr_observer)
+                kobs.sky_shift = 1 if kerr_observer_sky else 0
+            proj = None
+            if kerr_projection is not None:
+                proj = _lib.Projection(_lib.PROJ_EQUIRECT if kind == "equirect" else _lib.PROJ_FISHEYE, fov_h, fov_v, 0)
+            _lib.check(self._lib.bhr_render_kerr_view(self._ctx, C.byref(cam), None if kobs is None else C.byref(kobs),
+                                                      None if proj is None else C.byref(proj), flags))
+            return
         if light_delay is not None:
             d = _lib.LightDelay(scale, 0)
             _lib.check(self._lib.bhr_render_delayed(self._ctx, C.byref(cam), C.byref(d), flags))
@@ -944,6 +974,12 @@ class HipRenderer:
         _lib.check(self._lib.bhr_projected_resources(1 if supersampled else 0, out))
         return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
 
+    def kerr_view_resources(self, exact: bool = False, supersampled: bool = False) -> dict:
+        """Registers per lane, LDS and scratch bytes of the Kerr camera's march kernel of a redshift mode (bhr_kerr_view_resources)."""
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_kerr_view_resources(_lib.REDSHIFT_EXACT if exact else _lib.REDSHIFT_MODEL, 1 if supersampled else 0, out))
+        return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
+
     def adaptive_info(self) -> dict:
         """The last adaptively supersampled frame: pixels refined, how many of them were marched strict, pixels of the frame
         (bhr_adaptive_info; synchronises)."""
@@ -1062,15 +1098,18 @@ class HipRenderer:
 
     def render(self, cam_pos: List[float], fov: float, frame: int = 0,
                skip_differentials: bool = False, skip_bloom: bool = False, observer=None, observer_sky: bool = True,
-               projection=None, projection_fov=None, light_delay=None) -> np.ndarray:
+               projection=None, projection_fov=None, light_delay=None, kerr_observer=None, kerr_observer_sky: bool = True,
+               kerr_projection=None, kerr_projection_fov=None) -> np.ndarray:
         """One frame -> (rows, width, 3) float32 in [0, 1]  (render.py:3865-3923).  ``observer``, ``observer_sky``: a moving
         camera, ``projection``, ``projection_fov``: an equirect or fisheye camera, ``light_delay``: the scale of the light
-        delay, as render_async takes them."""
+        delay, ``kerr_observer``, ``kerr_observer_sky``, ``kerr_projection``, ``kerr_projection_fov``: the Kerr camera, as
+        render_async takes them."""
         if self.lens_flare and self.rows != self.height:
             raise ValueError("lens flare needs whole-frame sums; render row blocks through "
                              "bhr_amd.multigpu.group_render(..., lens_flare=True)")
         self.render_async(cam_pos, fov, frame, skip_differentials, skip_bloom, observer=observer, observer_sky=observer_sky,
-                          projection=projection, projection_fov=projection_fov, light_delay=light_delay)
+                          projection=projection, projection_fov=projection_fov, light_delay=light_delay, kerr_observer=kerr_observer,
+                          kerr_observer_sky=kerr_observer_sky, kerr_projection=kerr_projection, kerr_projection_fov=kerr_projection_fov)
         return self.read_layer(_lib.LAYER_FINAL)
 
     def selftest(self) -> dict:

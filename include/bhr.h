@@ -759,6 +759,40 @@ BHR_API int32_t bhr_render_projected(bhr_ctx *ctx, const bhr_camera *cam, const 
 /* out = {VGPRs per lane, LDS bytes per block, scratch bytes per lane} of the projected march kernel (supersampled != 0: of its
  * supersampled twin), from hipFuncGetAttributes.  No context. */
 BHR_API int32_t bhr_projected_resources(int32_t supersampled, int32_t out[3]);
+/* The Kerr camera: one frame of the spinning hole (bhr_set_spin, or the Kerr march forced at spin 0) through a camera that may
+ * move and may be panoramic.  Units r_s = 1, M = 1/2, a = A / 2.  The Kerr march identifies the static observer's local frame at
+ * the camera with the Kerr-Schild coordinate axes: a pixel's direction is the photon's coordinate direction d, from which the
+ * march makes its momentum (s = 1 / sqrt(1 - f (1 - (l.d)^2)), Lam = (1 + s l.d) / (1 - f), p = s d + f Lam l).  This call keeps
+ * that convention and puts the camera model of bhr_render_observer and bhr_render_projected ahead of it:
+ *   n'   the pixel's direction in the camera's own frame: the pinhole's (proj == NULL: bhr_render's), or the equirectangular or
+ *        fisheye direction exactly as stated for bhr_render_projected (same formulas and spans; here a product and the sum behind
+ *        it may be one fused multiply-add); a fisheye pixel outside the image circle takes no step, its BG and DISK are exactly
+ *        0 and enter the box filter of a supersampled frame as zeros; bhr_counters.rays is k^2 W H
+ *   beta the velocity (units of c, |beta| <= 0.995) the static observer at bhr_camera.pos measures; obs == NULL: the camera
+ *        hovers, the frame bit for bit that of obs = {{0, 0, 0}, 0}
+ *   D  = 1 / (gamma (1 - beta.n'))                                       gamma = 1 / sqrt(1 - beta.beta)
+ *   n  = (n' + (gamma^2 / (gamma + 1)) (beta.n') beta - gamma beta) D    f32; gamma, gamma^2 / (gamma + 1) binary64 rounded once
+ * n is not renormalised and takes the place of d.  The RK4 loop, step rule, capture at r_plus, escape and crossings are the Kerr
+ * march's.  D is a factor of the disk's g ahead of its cap in both redshift modes (bhr_set_redshift):
+ *   model   g = min((g_doppler (grav_num / grav_den)) D, 1.5)
+ *   exact   g = min((nu_obs D) / max(nu_em, 1e-3), 1.5)                   the static observer's nu_obs turned into the moving one's
+ * and with sky_shift != 0 the sky sample is scaled as stated for bhr_render_observer (BG may exceed 1, FINAL clips).  With
+ * beta = 0 and proj == NULL, under either sky setting, BG, DISK, FINAL and ray_steps are bhr_render's Kerr frame bit for bit.
+ * The frame is bhr_render's in every other respect -- next frame slot, one timing-ring entry, counters, post-pass following
+ * math_mode, lens flare, grade, HDR plane, sinks; asynchronous -- and is marched by the Kerr camera's object
+ * (csrc/march_kerr_observer.hip) under the context's redshift mode.  The velocity and the projection travel with the call: frames
+ * in flight may differ in them.  Works with bhr_set_supersample.  flags: BHR_SKIP_BLOOM, BHR_LENS_FLARE.  (DESIGN.md "Kerr
+ * camera"; tests/kerr_observer_ref.py is the CPU reference; bhr_amd.observer.kerr_velocity has the circular orbit's and the
+ * zero-angular-momentum observer's velocity.)
+ * BHR_ERR_INVALID with a message that names the combination, nothing launched and the context untouched: a null ctx or cam; no
+ * spin and no forced Kerr march; a NaN in beta or |beta| > 0.995; an unknown projection kind or a field of view
+ * bhr_render_projected refuses; any other flag bit; everything bhr_set_spin refuses (a tilted disk, anti_alias = 1, a Disk V2
+ * source, adaptive supersampling, a row-block context); a camera inside the static limit. */
+BHR_API int32_t bhr_render_kerr_view(bhr_ctx *ctx, const bhr_camera *cam, const bhr_observer *obs /* NULL: at rest */,
+                                     const bhr_projection *proj /* NULL: pinhole */, uint32_t flags);
+/* out = {VGPRs per lane, LDS bytes per block, scratch bytes per lane} of the Kerr camera's march kernel of a redshift mode
+ * (BHR_REDSHIFT_*; supersampled != 0: of its supersampled twin), from hipFuncGetAttributes.  No context. */
+BHR_API int32_t bhr_kerr_view_resources(int32_t mode, int32_t supersampled, int32_t out[3]);
 /* Light delay: one frame in which every disk crossing is shaded at the coordinate time its light LEFT the gas, not at the frame's
  * one instant.  Units r_s = 1, c = 1: t_offset is coordinate time in r_s / c.  The strict Schwarzschild march integrates
  * x'' = -1.5 L^2 x / r^5 with |d| = 1 at the camera; along that parameter l a null geodesic has energy
