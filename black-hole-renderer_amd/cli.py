@@ -241,6 +241,13 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "grade, --video_codec mjpeg, --video_hdr, --bit_depth 16 and --dither work as ever.  Not with --shutter, "
                         "--supersample > 1, --map_supersample > 1, --gpus > 1, --ray_map, --orbit_map, --shutter_map, the observer "
                         "flags, --projection, --light_delay, --stars point or --polarization")
+    p.add_argument("--spin_map_supersample", type=int, default=argparse.SUPPRESS, choices=[1, 2, 4, 8], metavar="K",
+                   help="--spin_map: the Kerr ray map's own supersampling factor, 1, 2, 4 or 8 (default 1) -- the only anti-aliasing a "
+                        "spinning hole has.  The one march of the video marches K x K Kerr rays per pixel and keeps their records; "
+                        "every frame shades all of them and resolves each pixel with --supersample's box filter, so with a camera "
+                        "that stands still the frames are byte-identical to those of --spin A --supersample K without a march per "
+                        "frame.  Needs --spin_map and takes its restrictions (--supersample and --map_supersample stay 1); not with "
+                        "--spin_polarization")
     p.add_argument("--map_supersample", type=int, default=1, choices=[1, 2, 4, 8], metavar="K",
                    help="--ray_map, --orbit_map or --shutter_map: the map's own supersampling factor, 1, 2, 4 or 8 (default 1).  The "
                         "one march of the video marches K x K rays per pixel and keeps their records; every frame shades all of them "
@@ -281,6 +288,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     args.fov = 90 if args.fov is None else args.fov
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    if hasattr(args, "spin_map_supersample"):     # (no key without the flag, likewise)
+        if not hasattr(args, "spin_map"):
+            p.error("--spin_map_supersample needs --spin_map: it is the Kerr ray map's factor (marched frames take --supersample)")
+        if hasattr(args, "spin_polarization"):
+            p.error("--spin_map_supersample does not combine with --spin_polarization: the Stokes planes need a Kerr ray map with one ray per pixel")
     if hasattr(args, "spin_map"):     # (the namespace of a line without the flag is what it was: no key)
         # the Kerr ray map of a video (drivers.check_spin_map has the same refusals): ahead of a spin's own, so that each names --spin_map
         if args.spin == 0 and args.redshift == "model":
@@ -892,7 +904,8 @@ def main(argv=None) -> int:
                              hdr_white=args.hdr_white, hdr_exposure=args.hdr_exposure, **stars_kw,
                              **(dict(observer=args.observer, observer_velocity=args.observer_velocity, observer_sky=sky,
                                      infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw,
-                             **({"spin_map": True} if hasattr(args, "spin_map") else {}))
+                             **({"spin_map": True} if hasattr(args, "spin_map") else {}),
+                             **({"spin_map_supersample": args.spin_map_supersample} if hasattr(args, "spin_map_supersample") else {}))
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent

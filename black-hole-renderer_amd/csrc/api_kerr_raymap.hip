@@ -16,9 +16,12 @@ namespace {
 const char *redshift_name(int32_t mode) { return mode == BHR_REDSHIFT_EXACT ? "exact" : "model"; }
 
 // What the Kerr march refuses of a context (tilt, anti-aliasing, Disk V2, adaptive supersampling, row blocks), and supersampling:
-// the map holds one Kerr ray per pixel.
-int32_t check_context(const bhr_ctx *ctx, const char *who) {
+// the context marches one Kerr ray per pixel for every map call (a supersampled map has a factor of its own, option
+// "kerr_raymap_supersample" = map_ss, which the refusal names when it is on).
+int32_t check_context(const bhr_ctx *ctx, const char *who, int32_t map_ss = 1) {
     BHR_TRY(bhr_variant_frame_check(ctx, bhr_variant_of(ctx), 0, who, (double)ctx->kerr_spin));
+    if (ctx->ss > 1 && map_ss > 1)
+        return bhr_fail(BHR_ERR_INVALID, "%s: supersampling is on (factor %d); a Kerr ray map holds one ray per pixel -- kerr_raymap_supersample %d is the map's own factor, bhr_set_supersample stays at 1", who, ctx->ss, map_ss);
     if (ctx->ss > 1) return bhr_fail(BHR_ERR_INVALID, "%s: supersampling is on (factor %d); a Kerr ray map holds one ray per pixel", who, ctx->ss);
     return BHR_OK;
 }
@@ -62,14 +65,22 @@ int32_t bhr_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flag
     if (!ctx->kerr_on)
         return bhr_fail(BHR_ERR_STATE, "%s: no spin is set and the Kerr march is not forced (bhr_set_spin, bhr_set_redshift); bhr_raymap_build is the ray map of a hole that does not spin", who);
     if (flags) return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (none are defined)", who, flags);
-    BHR_TRY(check_context(ctx, who));
+    // the map's own factor: the map of the fine frame, k rows x k W (the context's own supersampling stays off, check_context)
+    const int32_t ss = ctx->opt.kerr_raymap_ss;
+    BHR_TRY(check_context(ctx, who, ss));
     const int32_t K = ctx->opt.raymap_slots;
     if (K < 1 || K > 8) return bhr_fail(BHR_ERR_INVALID, "%s: raymap_slots %d (1 .. 8)", who, K);
     if (ctx->opt.raymap_ss != 1)
         return bhr_fail(BHR_ERR_INVALID, "%s: raymap_supersample %d; a Kerr ray map has no supersampled form (1 only)", who, ctx->opt.raymap_ss);
+    if (ss != 1 && ss != 2 && ss != 4 && ss != 8) return bhr_fail(BHR_ERR_INVALID, "%s: kerr_raymap_supersample %d (1, 2, 4 or 8)", who, ss);
+    if ((int64_t)ss * ss * ctx->cfg.width * ctx->cfg.height >= ((int64_t)1 << 31))
+        return bhr_fail(BHR_ERR_INVALID, "%s: %d x %d rays of a %dx%d frame exceed 2^31", who, ss, ss, ctx->cfg.width, ctx->cfg.height);
+    // the momentum build and the Kerr Stokes kernel have no supersampled twin
+    if (ss > 1 && bhr_have_kerr_polar(ctx))
+        return bhr_fail(BHR_ERR_INVALID, "%s: kerr_raymap_supersample %d while a Kerr polarisation is set (bhr_set_kerr_polarization); the Stokes planes need a map with one ray per pixel -- set the factor to 1 or switch the polarisation off (NULL) first", who, ss);
     BHR_TRY(bhr_kerr_camera_check(ctx, cam, who));
-    // one Kerr ray per pixel, no differentials; the context's variant (BHR_MV_KERR or BHR_MV_KERR_EXACT) marches it
-    return bhr_raymap_build_into(ctx, &ctx->kerr_raymap, who, cam, BHR_SKIP_DIFFERENTIALS, bhr_variant_of(ctx), K, 1);
+    // k x k Kerr rays per pixel, no differentials; the context's variant (BHR_MV_KERR or BHR_MV_KERR_EXACT) marches them
+    return bhr_raymap_build_into(ctx, &ctx->kerr_raymap, who, cam, BHR_SKIP_DIFFERENTIALS, bhr_variant_of(ctx), K, ss);
 }
 
 int32_t bhr_kerr_raymap_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes) {
@@ -100,6 +111,14 @@ int32_t bhr_kerr_raymap_info(bhr_ctx *ctx, bhr_kerr_raymap_desc *out) {
     if (!bhr_raymap_fill_info(ctx, ctx->kerr_raymap, out)) return BHR_OK;
     out->redshift = ctx->kerr_raymap->kerr_redshift;
     out->spin = ctx->kerr_raymap->kerr_spin;
+    return BHR_OK;
+}
+
+// never fails for want of a map: 1 then
+int32_t bhr_kerr_raymap_get_supersample(bhr_ctx *ctx, int32_t *k) {
+    if (!ctx || !k) return bhr_fail(BHR_ERR_INVALID, "bhr_kerr_raymap_get_supersample: bad argument");
+    const bhr_raymap *rm = ctx->kerr_raymap;
+    *k = rm && rm->built ? rm->ss : 1;
     return BHR_OK;
 }
 

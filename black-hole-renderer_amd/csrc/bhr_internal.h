@@ -349,6 +349,7 @@ struct bhr_options {
     int32_t shutter_timing;     // BHR_SHUTTER_TIMING: 1 a shutter frame brackets each accumulation launch with HIP events (bhr_debug_read, which = 5); default 0
     int32_t raymap_slots;       // BHR_RAYMAP_SLOTS / option "raymap_slots": crossings a map keeps per pixel (1..8, default 4), read by bhr_raymap_build, which refuses anything else
     int32_t raymap_ss;          // BHR_RAYMAP_SUPERSAMPLE / option "raymap_supersample": the next map's own factor (1, 2, 4, 8; default 1), read by bhr_raymap_build likewise
+    int32_t kerr_raymap_ss;     // BHR_KERR_RAYMAP_SUPERSAMPLE / option "kerr_raymap_supersample": the next Kerr map's own factor (1, 2, 4, 8; default 1), read by bhr_kerr_raymap_build
 };
 
 // The context's ray map (api_raymap.hip): what the strict march of one whole-frame view finds before it shades anything.
@@ -362,7 +363,7 @@ struct bhr_raymap {
     float kerr_spin;             // a Kerr map: the spin and the redshift mode of its build, which a frame from it needs the
     int32_t kerr_redshift;       // context to have still
     int32_t built, diff, slots;
-    int32_t ss;                  // the map's own supersampling factor (option "raymap_supersample" at the build): planes of the fine frame
+    int32_t ss;                  // the map's own supersampling factor (option "raymap_supersample", a Kerr map's "kerr_raymap_supersample", at the build): planes of the fine frame
     int32_t alloc_slots, alloc_comps, alloc_ss;   // shape of the allocation
     int32_t over_cap;            // capacity of the overflow list: the (fine) pixel count rounded up to whole blocks of the fix kernel
     int64_t device_bytes;
@@ -774,7 +775,7 @@ const void *bhr_march_kernel_projected(bhr_march_kernel k, int32_t diff, int32_t
 const void *bhr_march_kernel_delay(bhr_march_kernel k, int32_t diff, int32_t ss);      // march_delay.hip -> march_delay.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
 const void *bhr_march_kernel_kerr_view(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_kerr_observer.hip -> march_kerr_observer.o (as bhr_march_kernel_kerr)
-const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact);           // march_kerr_raymap.hip -> march_kerr_raymap.o (exact: the exact redshift's)
+const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact, int32_t ss);   // march_kerr_raymap.hip -> march_kerr_raymap.o (exact: the exact redshift's; ss: a supersampled map's)
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o
 
 // ---- hybrid.hip -------------------------------------------------------------------------------------------------------------------------

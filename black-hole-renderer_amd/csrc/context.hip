@@ -46,6 +46,7 @@ void read_options(bhr_options *o) {
     o->grade_timing = num("BHR_GRADE_TIMING", 0) != 0;
     o->raymap_slots = num("BHR_RAYMAP_SLOTS", 4);        // outside 1 .. 8: bhr_raymap_build refuses
     o->raymap_ss = num("BHR_RAYMAP_SUPERSAMPLE", 1);     // not 1, 2, 4 or 8: bhr_raymap_build refuses
+    o->kerr_raymap_ss = num("BHR_KERR_RAYMAP_SUPERSAMPLE", 1);   // not 1, 2, 4 or 8: bhr_kerr_raymap_build refuses
 }
 
 }  // namespace
@@ -248,6 +249,11 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
         if (!(value == 1.0 || value == 2.0 || value == 4.0 || value == 8.0))
             return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: raymap_supersample %g (1, 2, 4 or 8)", value);
         o.raymap_ss = v;
+    }
+    else if (n == "kerr_raymap_supersample") {   // the next Kerr map's own factor, a name of its own: "raymap_supersample" stays the Schwarzschild map's
+        if (!(value == 1.0 || value == 2.0 || value == 4.0 || value == 8.0))
+            return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: kerr_raymap_supersample %g (1, 2, 4 or 8)", value);
+        o.kerr_raymap_ss = v;
     }
     else if (n == "png16_menu") {   // the tables are rebuilt at the next encode; no encode may be running on the old ones
         BHR_TRY(bhr_enter(ctx));

@@ -24,7 +24,15 @@
 // kerr_raymap_build_mom_kernel<RS> is the build while a Kerr polarisation is set (bhr_set_kerr_polarization; march_kerr_polar.hip
 // has the pass that reads what it keeps): the same march, and per stored crossing the photon's momentum (p_x, p_y, p_z) as well.
 //
-// No differentials (the Kerr Ray has none) and no supersampled form.
+// The supersampled map (option "kerr_raymap_supersample", a.ss = k > 1) is the map of the fine frame, k W x k rows seen through
+// bhr_fine_camera: kerr_raymap_build_ss_kernel, kerr_raymap_shade_ss_kernel and kerr_raymap_fix_ss_kernel take the fine argument
+// block (a.width / rows / pw / ph fine, out_width / out_rows the frame's) and are the three kernels above with the k x k groups
+// handled in the wave: a group with any ray over the slots goes on the overflow list whole, every other group is resolved by
+// resolve_store (march_device.h) from its lanes' shaded records, and the listed groups are marched and resolved by the fix
+// kernel -- the frame march_kerr_ss_kernel / march_kerr_exact_ss_kernel leaves, bit for bit.  They are kernels of their own
+// beside the k = 1 kernels, which keep their code (tools/code_object_diff.py).
+//
+// No differentials (the Kerr Ray has none); the momentum build has no supersampled form.
 #include <type_traits>
 
 #include "ray_kerr.h"
@@ -84,6 +92,79 @@ __global__ __launch_bounds__(256) void kerr_raymap_build_kernel(KerrBlock<RS> a,
         m.crossings[pix] = n_rec;
     }
     raymap_append_overflow(m, valid && n_rec > m.slots, lane, pix);
+    const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
+    const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
+    if (lane == 0) {
+        atomicAdd(m.stats, stored);
+        atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
+    }
+}
+
+// The build of a supersampled map: kerr_raymap_build_kernel's march, records and header over the fine block, the fine tiles in
+// plain order (a.tile_order null).  What differs is the overflow list, as in raymap_build_kernel<DIFF, true> (march_raymap.hip):
+// a k x k group with ANY ray over the slots is appended whole in the format the supersampled fix kernel reads -- k^2 consecutive
+// entries in sub-sample order (sy k + sx), k^2-aligned, groups in the order of their (0, 0) lanes.  k W and k rows are
+// multiples of k (and 8 is one of k), so a group lies in one tile, inside the frame or outside it, whole.
+// No lane returns before the butterfly: only the wave-uniform exit stays.
+template <int RS>
+__global__ __launch_bounds__(256) void kerr_raymap_build_ss_kernel(KerrBlock<RS> a, BhrRayMapArgs m) {
+    const int slot = wave_slot();
+    if (slot >= a.n_list) return;    // wave-uniform: the lanes of a wave stay together down to the butterfly
+    const int lane = threadIdx.x & 63;
+    const int tile = a.tile_order ? a.tile_order[slot] : slot;
+    const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
+    const int i = tx * 8 + (lane & 7);
+    const int j = ty * 8 + (lane >> 3);
+    const bool valid = tile < a.n_tiles && i < a.width && j < a.rows;
+
+    Ray<false, RS> ray;
+    ray.init(a, valid ? i : 0, valid ? j : 0);
+    if (!valid) ray.done = 4;
+    const size_t pix = valid ? (size_t)j * a.width + i : 0;
+    int cnt = 0, n_rec = 0;
+    while (ray.done == 0) {
+        ray.step(a);
+        cnt += 1;
+        if (ray.full) {
+            ray.record_one(m, pix, n_rec);
+            ray.full = false;
+        }
+    }
+    ray.step_count = cnt;
+    if (cnt > 0) ray.settle(a);
+    else ray.done = 3;
+    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
+    if (__ballot(ray.n_pend > 0)) ray.record_one(m, pix, n_rec);
+
+    if (valid) {
+        const bool esc = ray.escaped(a);
+        m.steps[pix] = cnt;
+        m.status[pix] = esc ? 1 : (ray.done == 2 ? 0 : 2);
+        V3 dn = mk(0.0f, 0.0f, 0.0f);
+        if (esc) dn = normalized(ray.velocity(a));
+        m.dir[pix] = dn.x;
+        m.dir[(size_t)m.plane + pix] = dn.y;
+        m.dir[2 * (size_t)m.plane + pix] = dn.z;
+        m.crossings[pix] = n_rec;
+    }
+    // the group's flag: ORed over the group by the butterfly (every lane of the wave is here)
+    int u = valid && n_rec > m.slots ? 1 : 0;
+    for (int x = 1; x < a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+    for (int x = 8; x < 8 * a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+    const bool over = valid && u != 0;
+    const unsigned long long om = __ballot(over);
+    if (om) {
+        const int first = __ffsll((long long)om) - 1;
+        const int km = a.ss - 1, sx = lane & km, sy = (lane >> 3) & km;
+        const unsigned long long lead = __ballot(over && sx == 0 && sy == 0);
+        unsigned int base = 0;
+        if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(lead) << (2 * a.ss_log2));
+        base = __shfl(base, first, BHR_WAVE);
+        const int l0 = lane - sx - 8 * sy;
+        const unsigned int at = base + ((unsigned int)__popcll(lead & ((1ull << l0) - 1ull)) << (2 * a.ss_log2)) + (unsigned int)((sy << a.ss_log2) + sx);
+        // (every group is appended at most once and the list has room for the whole fine plane)
+        if (over) m.over_list[at] = (int32_t)pix;
+    }
     const unsigned long long stored = wave_sum_u32((unsigned int)(valid ? min(n_rec, m.slots) : 0));
     const unsigned long long tot = wave_sum_u32((unsigned int)cnt);
     if (lane == 0) {
@@ -188,6 +269,70 @@ __global__ __launch_bounds__(256) void kerr_raymap_shade_kernel(KerrBlock<RS> a,
     store_pixel(a, i, j, a.width, bk, dk);
 }
 
+// What resolve_store (march_device.h) asks of a ray: the six values it leaves.  Here they come out of the lane's records.
+struct KerrRayMapValues {
+    float v[6];
+    __device__ __forceinline__ void values(const BhrMarchArgs &, float bk[3], float dk[3]) const {
+        bk[0] = v[0]; bk[1] = v[1]; bk[2] = v[2];
+        dk[0] = v[3]; dk[1] = v[4]; dk[2] = v[5];
+    }
+};
+
+// A frame from a supersampled map: one 8x8 tile of the FINE frame per wave, every lane shades its own fine record list exactly
+// as kerr_raymap_shade_kernel does (same device functions, same order, same turn), and the k x k groups are resolved in the wave
+// by resolve_store -- the marched Kerr supersampled kernels' butterfly and product, so the output pixel is theirs bit for bit;
+// the lane at sub-sample (0, 0) stores it at (i >> log2 k, j >> log2 k) of the output frame.
+// Two things the k = 1 kernel does are NOT done here:
+//  * no lane returns early (beyond the frame, or on the overflow list): __shfl_xor reads whatever a lane that has left last held
+//    in the register.  A lane without a ray shades no record and contributes zeros; its whole group is beyond the frame and is
+//    not stored.
+//  * overflow is a group's property: a group with any ray over the slots is on the overflow list whole (the build above) and is
+//    not stored here at all -- kerr_raymap_fix_ss_kernel marches and resolves it.  Its lanes shade nothing.
+// The occupancy hint is the k = 1 twin's waves per SIMD (63 / 71 VGPRs: 8 with the model redshift, 7 with the exact one).  The
+// six values across the butterfly are the only new live state; without the hint the model kernels take 66 VGPRs and lose a
+// wave, with it 64, and the exact ones 72 for 71 -- no scratch either way (tools/kernel_resources.sh kerr_raymap).
+template <int RS, bool ROT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RS == KERR_EXACT ? 7 : 8))) void kerr_raymap_shade_ss_kernel(KerrBlock<RS> a, BhrRayMapArgs m) {
+    const int tile = wave_slot();
+    if (tile >= a.n_tiles) return;   // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const int i = (tile % a.tiles_x) * 8 + (lane & 7);
+    const int j = (tile / a.tiles_x) * 8 + (lane >> 3);
+    const bool valid = i < a.width && j < a.rows;
+    const size_t pix = valid ? (size_t)j * a.width + i : 0;
+    const int crossings = valid ? m.crossings[pix] : 0;
+    int u = crossings > m.slots ? 1 : 0;
+    for (int x = 1; x < a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+    for (int x = 8; x < 8 * a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
+    const bool have = valid && u == 0;
+    const int count = have ? crossings : 0;
+    const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;   // scalar operands, as in kerr_raymap_shade_kernel
+    Shade sh;                        // as Ray::init leaves it
+    sh.accum = mk(0, 0, 0);
+    sh.alpha_total = 0.0f;
+    sh.unsure = 0;
+    const size_t p = (size_t)m.plane;
+    for (int c = 0; c < count; ++c) {
+        const float *q = m.hits + (size_t)c * m.comps * p + pix;
+        float hx = q[0], hy = q[p];
+        V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
+        if (ROT) {
+            turn_xy(rc, rs, hx, hy);
+            turn_xy(rc, rs, to_cam.x, to_cam.y);
+        }
+        kerr_shade_hit<RS>(a, sh, hx, hy, to_cam);
+    }
+    KerrRayMapValues val = {{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}};
+    if (have) {
+        const bool esc = m.status[pix] == 1;
+        V3 dir = mk(m.dir[pix], m.dir[p + pix], m.dir[2 * p + pix]);
+        if (ROT) turn_xy(rc, rs, dir.x, dir.y);
+        raymap_pixel_values(a, esc, dir, sh, val.v, val.v + 3);
+    }
+    // every lane of the wave, whatever it holds
+    resolve_store(a, val, have, have, i, j, 8);
+}
+
 // ---- the overflow list --------------------------------------------------------------------------------------------------------
 // march_fix_kernel's body (march_strict_ilp.hip) over the Kerr Ray: the pixels of the map's overflow list, 64 per wave whatever
 // tile they came from, marched from the frame's own camera and stored through the march's own values and store -- the marched
@@ -225,11 +370,53 @@ __global__ __launch_bounds__(256) void kerr_raymap_fix_kernel(KerrBlock<RS> a) {
     if (lane == 0) atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
 }
 
+// The overflow list of a supersampled map: whole k x k groups, k^2 consecutive entries in sub-sample order, k^2-aligned (the
+// build above), 64 / k^2 groups per wave.  kerr_raymap_fix_kernel's march, and the groups resolved like a tile's, with the
+// sub-sample rows k lanes apart -- the supersampled Kerr march of those pixels.
+template <int RS>
+__global__ __launch_bounds__(256) void kerr_raymap_fix_ss_kernel(KerrBlock<RS> a) {
+    const int wave = wave_slot();
+    unsigned int n = *a.fix_count;
+    if (n > (unsigned int)a.fix_cap) n = (unsigned int)a.fix_cap;
+    if ((unsigned int)wave * 64u >= n) return;    // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const unsigned int k = (unsigned int)wave * 64u + (unsigned int)lane;
+    const bool valid = k < n;
+    const int pix = valid ? a.fix_list[k] : 0;
+    Ray<false, RS> ray;
+    ray.init(a, pix % a.width, pix / a.width);
+    if (!valid) ray.done = 4;
+    int cnt = 0;
+    while (ray.done == 0) {
+        ray.step(a);
+        cnt += 1;
+        if (ray.full) { ray.flush_one(a); ray.full = false; }
+    }
+    ray.step_count = cnt;
+    if (cnt > 0) ray.settle(a);
+    else ray.done = 3;
+    if (__ballot(ray.n_pend > 0)) ray.flush_one(a);
+    if (__ballot(ray.n_pend > 0)) ray.flush_one(a);
+    resolve_store(a, ray, valid, valid, pix % a.width, pix / a.width, a.ss);
+    const unsigned long long tot = wave_sum_u32((unsigned int)ray.step_count);
+    if (lane == 0) atomicAdd(a.ray_steps + (size_t)(blockIdx.x & (BHR_STEP_LANES - 1)) * BHR_STEP_STRIDE, tot);
+}
+
 }  // namespace
 
 // ---- the kernels of this object, by the launcher's names (march_launch.hip); null: not in this object ----------
-// exact: the kernels of the exact redshift (they take BhrKerrExactMarchArgs)
-const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact) {
+// exact: the kernels of the exact redshift (they take BhrKerrExactMarchArgs); ss: the kernels of a supersampled map (a.ss > 1;
+// the momentum build has none)
+const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact, int32_t ss) {
+    if (ss) {
+        switch (k) {
+        case BHR_MK_KERR_RAYMAP_BUILD: return exact ? (const void *)kerr_raymap_build_ss_kernel<KERR_EXACT> : (const void *)kerr_raymap_build_ss_kernel<0>;
+        case BHR_MK_KERR_RAYMAP_SHADE: return exact ? (const void *)kerr_raymap_shade_ss_kernel<KERR_EXACT, false> : (const void *)kerr_raymap_shade_ss_kernel<0, false>;
+        case BHR_MK_KERR_RAYMAP_SHADE_ROT: return exact ? (const void *)kerr_raymap_shade_ss_kernel<KERR_EXACT, true> : (const void *)kerr_raymap_shade_ss_kernel<0, true>;
+        case BHR_MK_KERR_RAYMAP_FIX: return exact ? (const void *)kerr_raymap_fix_ss_kernel<KERR_EXACT> : (const void *)kerr_raymap_fix_ss_kernel<0>;
+        default: return nullptr;
+        }
+    }
     switch (k) {
     case BHR_MK_KERR_RAYMAP_BUILD: return exact ? (const void *)kerr_raymap_build_kernel<KERR_EXACT> : (const void *)kerr_raymap_build_kernel<0>;
     case BHR_MK_KERR_RAYMAP_SHADE: return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, false> : (const void *)kerr_raymap_shade_kernel<0, false>;

@@ -69,7 +69,7 @@ float fast_sqrt(float s) {
 //
 //   arithmetic     request                                              kernel (object)
 //   any            a march variant v (call.req.variant), whole block    its row's kernel: kernels(name, 0, ss) of bhr_variant_row_of(v)
-//   any            a Kerr variant, fix list (part->repair == 2)         kerr_raymap_fix_kernel<RS> (kerr_raymap)
+//   any            a Kerr variant, fix list (part->repair == 2)         kerr_raymap_fix_kernel<RS> / kerr_raymap_fix_ss_kernel<RS> (kerr_raymap)
 //   any            hybrid part with n <= 0, not the fix list            none
 //   strict         hybrid fix list (part->repair == 2)                  march_fix_kernel<diff> (strict_ilp)
 //   fast / strict  Disk V2 volume source                                march_tile_kernel<false, 2> (own object)
@@ -105,9 +105,10 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
     // a variant: one arithmetic, one schedule, no lists (what it has no form for was refused before anything was launched)
     if (v != BHR_MV_NONE) {
         const bhr_variant_row &r = bhr_variant_row_of(v);
-        // the overflow list of a frame from the Kerr ray map (part->repair == 2 under a Kerr variant): kerr_raymap_fix_kernel
+        // the overflow list of a frame from the Kerr ray map (part->repair == 2 under a Kerr variant): kerr_raymap_fix_kernel, or
+        // kerr_raymap_fix_ss_kernel over the whole groups of a supersampled map's list (the grid is sized for the fine capacity)
         if (part && part->repair == 2 && r.kerr) {
-            k.fn = bhr_march_kernel_kerr_raymap(BHR_MK_KERR_RAYMAP_FIX, v == BHR_MV_KERR_EXACT);
+            k.fn = bhr_march_kernel_kerr_raymap(BHR_MK_KERR_RAYMAP_FIX, v == BHR_MV_KERR_EXACT, ss);
             k.grid = dim3((a.fix_cap / 64 + 3) / 4);
             return k;
         }
@@ -540,11 +541,12 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
 
 // ---- the ray maps (march_raymap.hip, march_kerr_raymap.hip; api_raymap.hip owns the maps) ------------------------------------------
 // The kernels take the march's argument block of the strict frame and the map as a second argument.  A supersampled map (its
-// own factor ss, option "raymap_supersample"; the context's factor stays 1) takes the block of the fine frame, as a marched
-// supersampled frame does, and the kernels' supersampled twins.  Under a Kerr variant the kernels are the Kerr map's, which take
-// the Kerr block of the redshift (variant_args) in the march block's place: one ray per pixel, no differentials, no stars.
+// own factor ss, option "raymap_supersample" or a Kerr map's "kerr_raymap_supersample"; the context's factor stays 1) takes the
+// block of the fine frame, as a marched supersampled frame does, and the kernels' supersampled twins.  Under a Kerr variant the
+// kernels are the Kerr map's, which take the Kerr block of the redshift (variant_args) in the march block's place: no
+// differentials, no stars.
 static const void *raymap_kernel(bhr_march_variant v, bhr_march_kernel plain, bhr_march_kernel kerr, bool diff, int32_t ss) {
-    return v == BHR_MV_NONE ? bhr_march_kernel_raymap(plain, diff, ss > 1) : bhr_march_kernel_kerr_raymap(kerr, v == BHR_MV_KERR_EXACT);
+    return v == BHR_MV_NONE ? bhr_march_kernel_raymap(plain, diff, ss > 1) : bhr_march_kernel_kerr_raymap(kerr, v == BHR_MV_KERR_EXACT, ss > 1);
 }
 
 int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss, bhr_march_variant v, float *mom) {

@@ -760,9 +760,14 @@ def _build_map(label: str):
 
 
 def _build_kerr_map(renderer, cam_pos, fov, map_supersample):
-    renderer.build_kerr_ray_map(cam_pos, fov)
+    # (map_supersample: the Kerr map's own factor, render_video's spin_map_supersample)
+    if map_supersample == 1:
+        renderer.build_kerr_ray_map(cam_pos, fov)
+    else:
+        renderer.build_kerr_ray_map(cam_pos, fov, supersample=map_supersample)
     info = renderer.kerr_ray_map_info()
-    print(f"  Kerr ray map built (spin {info['spin']:g}, {info['redshift']} redshift): {info['slots']} slots, {info['overflow_pixels']} overflow pixels, "
+    factor = "" if map_supersample == 1 else f"{map_supersample} x {map_supersample} rays per pixel, "
+    print(f"  Kerr ray map built (spin {info['spin']:g}, {info['redshift']} redshift): {factor}{info['slots']} slots, {info['overflow_pixels']} overflow pixels, "
           f"{info['device_bytes'] / 1e6:.0f} MB")
 
 
@@ -877,6 +882,19 @@ def check_map_supersample(k, ray_map: bool = False, orbit_map: bool = False, shu
                          "(marched frames take --supersample)")
 
 
+def check_spin_map_supersample(k, spin_map: bool = False, spin_polarization: bool = False) -> None:
+    """--spin_map_supersample k / render_video(spin_map=True, spin_map_supersample=k): the Kerr ray map's own supersampling
+    factor (k x k records per pixel, resolved in the shade; HipRenderer.build_kerr_ray_map(supersample=k)).  1, 2, 4 or 8, above
+    1 only with --spin_map and not with --spin_polarization (the Stokes planes need a map with one ray per pixel).  Raises
+    ValueError naming both flags, before any device work."""
+    if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4, 8):
+        raise ValueError(f"spin_map_supersample must be 1, 2, 4 or 8, got {k!r}")
+    if k > 1 and not spin_map:
+        raise ValueError("--spin_map_supersample is the Kerr ray map's factor: it needs --spin_map (marched frames take --supersample)")
+    if k > 1 and spin_polarization:
+        raise ValueError("--spin_map_supersample does not combine with --spin_polarization: the Stokes planes need a Kerr ray map with one ray per pixel")
+
+
 VIDEO_HDRS = ("pq", "hlg")
 HDR_COLOR_TRC = {"pq": "smpte2084", "hlg": "arib-std-b67"}     # ffmpeg's names of the two transfers
 
@@ -924,7 +942,8 @@ def hdr_sidecar(hdr: dict, max_cll: float, max_fall: float, frames: int) -> dict
 def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec="auto", video_quality=90,
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
                     shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None,
-                    stars=None, projection=None, light_delay=None, polarization=None, spin_map=False, kerr_view=None) -> dict:
+                    stars=None, projection=None, light_delay=None, polarization=None, spin_map=False, kerr_view=None,
+                    spin_map_supersample=1) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -948,6 +967,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(shutter_map=True)
     if spin_map:
         params.update(spin_map=True)
+    if spin_map_supersample > 1:
+        params.update(spin_map_supersample=spin_map_supersample)
     if map_supersample > 1:
         params.update(map_supersample=map_supersample)
     if video_hdr is not None:
@@ -1004,7 +1025,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  observer: Optional[str] = None, observer_velocity=None, observer_sky: bool = True,
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
                  light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, spin_map: bool = False,
-                 kerr_polarization: Optional[dict] = None, kerr_view: Optional[dict] = None,
+                 kerr_polarization: Optional[dict] = None, kerr_view: Optional[dict] = None, spin_map_supersample: int = 1,
                  **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
@@ -1075,6 +1096,14 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     device work, with what check_spin_map names.  The progress record carries ``spin_map`` when it is set, and a resume with the
     other setting starts over.
 
+    ``spin_map_supersample`` = k in {1, 2, 4, 8} (with ``spin_map=True``): the Kerr map's own factor
+    (HipRenderer.build_kerr_ray_map(supersample=k)) -- k x k records per pixel, every frame from the map resolved with
+    set_supersample's filter; with a camera that stands still the frames are byte for byte those of the marched video of a
+    renderer with ``supersample=k``, and no march runs per frame.  ``supersample`` and ``map_supersample`` stay 1 with this map.
+    Refused with ValueError, before any device work, for another value, for k > 1 without ``spin_map`` and with
+    ``kerr_polarization`` (check_spin_map_supersample).  The progress record carries ``spin_map_supersample`` when it is above 1,
+    and a resume with another factor starts over.
+
     ``shutter_map=True`` (with ``shutter > 0``): motion blur from ONE ray map.  What differs between the samples of an exposure
     -- the disk's roll, and under ``orbit`` the camera's turn about z -- is what a map leaves free, so no sample is marched: the
     map is built once (for orbit_position(static_cam_pos, 0, ...) under ``orbit``, else for ``static_cam_pos``) and every frame is
@@ -1136,6 +1165,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     evaluated at that frame's own camera position (bhr_amd.observer.kerr_frame_plan), so an ``orbit`` with "circular" is the
     fly-around on the equatorial geodesic.  Refused with ValueError, before any device work, with what check_kerr_view names.  The
     progress record carries the camera when one is given, and a resume under another starts over."""
+    # the Kerr map's own factor: refused first, before the renderer is asked anything
+    check_spin_map_supersample(spin_map_supersample, spin_map=spin_map, spin_polarization=kerr_polarization is not None)
     kerr_plan = None
     if kerr_view is not None:                                   # (without one the renderer is not asked anything, as ever)
         from . import observer as obs_mod
@@ -1249,7 +1280,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                              **({} if stars is None else {"stars": stars}),
                              **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}),
                              **({} if light_delay is None else {"light_delay": light_delay}),
-                             **({} if polarization is None else {"polarization": polarization}), spin_map=spin_map, kerr_view=kerr_view)
+                             **({} if polarization is None else {"polarization": polarization}), spin_map=spin_map, kerr_view=kerr_view,
+                             spin_map_supersample=spin_map_supersample)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -1351,7 +1383,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     if mode is not None:
         # the one march of the video.  A camera that stands still: its view; an orbit: frame 0's (the orbit's radius is |pov|, not
         # the pov's xy norm: not the pov itself), which every frame's camera is a turn of about z
-        _MAP_MODES[mode]["build"](renderer, orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov, map_supersample)
+        _MAP_MODES[mode]["build"](renderer, orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov,
+                                  spin_map_supersample if mode == "spin_map" else map_supersample)
     stokes_grids = {}
     if polarization is not None:
         renderer.set_polarization(**polarization)

@@ -681,11 +681,18 @@ class HipRenderer:
         _lib.check(self._lib.bhr_raymap_free(self._ctx))
 
     # ------------------------------------------------------------------ Kerr ray map
-    def build_kerr_ray_map(self, cam_pos, fov: float) -> None:
+    def build_kerr_ray_map(self, cam_pos, fov: float, supersample: int = 1) -> None:
         """March the view once with the Kerr march of the renderer's spin and redshift mode and keep what the march finds
         before it shades anything (bhr_kerr_raymap_build; include/bhr.h states the map).  A map of its own beside build_ray_map's,
-        which stays the call for a hole that does not spin.  The slot count is option "raymap_slots" (1..8, default 4); one ray
-        per pixel, whole-frame renderers only.  Synchronises."""
+        which stays the call for a hole that does not spin.  The slot count is option "raymap_slots" (1..8, default 4);
+        whole-frame renderers only.  Synchronises.
+
+        ``supersample`` = k in {1, 2, 4, 8} is the map's own factor (option "kerr_raymap_supersample"; the renderer's
+        ``set_supersample`` stays at 1): the map of the fine frame, k x k records per pixel, which every frame from the map
+        resolves with set_supersample's filter -- bit for bit the marched Kerr frame of a renderer with ``set_supersample(k)``."""
+        if supersample not in (1, 2, 4, 8):
+            raise ValueError(f"build_kerr_ray_map: supersample {supersample!r} (1, 2, 4 or 8)")
+        self.set_option("kerr_raymap_supersample", supersample)
         cam = self.camera_uniforms(cam_pos, fov, 0)
         _lib.check(self._lib.bhr_kerr_raymap_build(self._ctx, C.byref(cam), 0))
         self._kerr_map_fov = float(fov)
@@ -713,24 +720,30 @@ class HipRenderer:
         _lib.check(self._lib.bhr_kerr_raymap_render(self._ctx, t, flags))
 
     def kerr_ray_map_info(self) -> dict:
-        """The renderer's Kerr ray map (bhr_kerr_raymap_info): built, slots, width, rows, ray_steps of the build,
-        crossings_stored, overflow_pixels, device_bytes, the spin and the redshift ("model" / "exact") it was built under, and
-        the build camera's pos / r_escape."""
+        """The renderer's Kerr ray map (bhr_kerr_raymap_info): built, slots, width, rows (the output frame's), supersample (the
+        map's own factor, bhr_kerr_raymap_get_supersample; 1 without a map), ray_steps of the build, crossings_stored,
+        overflow_pixels (fine rays), device_bytes, the spin and the redshift ("model" / "exact") it was built under, and the build
+        camera's pos / r_escape."""
         info = _lib.KerrRayMapDesc()
         _lib.check(self._lib.bhr_kerr_raymap_info(self._ctx, C.byref(info)))
         out = self._map_info(info, ("built", "slots", "width", "rows", "crossings_stored", "overflow_pixels", "device_bytes", "ray_steps"))
         out["spin"] = float(info.spin)
         out["redshift"] = "exact" if info.redshift == _lib.REDSHIFT_EXACT else "model"
+        k = C.c_int32(1)
+        _lib.check(self._lib.bhr_kerr_raymap_get_supersample(self._ctx, C.byref(k)))
+        out["supersample"] = int(k.value)
         return out
 
     def kerr_ray_map_passes(self) -> dict:
-        """The Kerr map's planes as NumPy arrays in (H, W[, ...]) order: ``steps``, ``status`` (0 captured, 1 escaped, 2 out of
+        """The Kerr map's planes as NumPy arrays in (H, W[, ...]) order -- of the fine frame, (k H, k W[, ...]), for a map with
+        supersample k: ``steps``, ``status`` (0 captured, 1 escaped, 2 out of
         iterations), ``escape_dir`` (H, W, 3), ``crossings`` and ``hits`` (K, H, W, 5: hit_x, hit_y, and to_cam xyz under the
         model redshift or the photon's momentum (p_x, p_y, 0) under the exact one)."""
         info = self.kerr_ray_map_info()
         if not info["built"]:
             raise AssertionError("no Kerr ray map has been built (build_kerr_ray_map)")
-        return self._map_planes(self._lib.bhr_kerr_raymap_read, info["rows"], info["width"], info["slots"], 5)
+        ss = max(info["supersample"], 1)
+        return self._map_planes(self._lib.bhr_kerr_raymap_read, info["rows"] * ss, info["width"] * ss, info["slots"], 5)
 
     def kerr_ray_map_momentum(self) -> np.ndarray:
         """The photon's covariant momentum (p_x, p_y, p_z) at each stored crossing of a Kerr map built under a Kerr polarisation,

@@ -662,13 +662,36 @@ BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, 
  * (K, rows, W, 5); bhr_kerr_raymap_info never fails for want of a map (built = 0 then); bhr_kerr_raymap_free is ordered behind
  * the frames in flight, and bhr_destroy releases the map.  The Schwarzschild map of the context, point stars and the
  * polarisation neither see nor are changed by any of these calls.
- * Not available: shutter frames from this map, a supersampled map, several devices.
+ * Supersampled Kerr maps.  Option "kerr_raymap_supersample" (1, 2, 4 or 8; default 1) is the Kerr map's OWN factor k, read by
+ * bhr_kerr_raymap_build as "raymap_slots" is; the map in memory keeps the factor it was built with, and a build with another
+ * one reallocates.  ("raymap_supersample" stays the Schwarzschild map's and is refused here unless 1.)  The context's
+ * bhr_set_supersample / bhr_set_adaptive_supersample stay at 1 for every map call.  With k > 1 the map is the map of the fine
+ * frame: built by the Kerr march of bhr_set_supersample's fine camera (pixel pitch / k) of `cam`, every plane k rows x k W, the
+ * overflow list in fine pixel indices -- a k x k group with any ray over K is listed whole.  bhr_kerr_raymap_info: width and rows
+ * stay the output frame's; crossings_stored, overflow_pixels (a multiple of k^2) and ray_steps count fine rays, ray_steps equal
+ * to that of a marched Kerr frame of the view with bhr_set_supersample(k).  bhr_kerr_raymap_desc keeps its layout;
+ * bhr_kerr_raymap_get_supersample(ctx, &k) reports the factor, never fails for want of a map and gives 1 when there is none.
+ * bhr_kerr_raymap_read hands out the fine planes, (k rows, k W[, 3]) and (K, k rows, k W, 5).  Device memory: k^2 x (24 + K x 20)
+ * bytes per output pixel.
+ * The frame: BG, DISK, FINAL and the u8 rows of bhr_kerr_raymap_render(ctx, t, flags) are bit for bit those of
+ * bhr_render(ctx', &cam_t, flags), ctx' a context of the same configuration, spin and redshift with bhr_set_supersample(ctx', k).
+ * The shade kernel shades each fine record list and resolves the k x k groups in the wave with bhr_set_supersample's filter
+ * (pairwise tree, times 1 / k^2); the groups of the overflow list are marched and resolved by the map's supersampled fix
+ * kernel.  No march runs per frame.  bhr_kerr_raymap_render_view takes such a map with its checks and meaning unchanged (the
+ * camera is compared with the build camera as passed, at the output pitch): its frame is the Kerr march of the build view's
+ * fine rays turned about z, resolved the same way.  Flags, frame slot, timing-ring entry, post-pass, grade, sinks and reads are
+ * those of a frame from a k = 1 map; no calibration.
+ * Not available: shutter frames from this map, point stars or a Kerr polarisation on a supersampled map, several devices.
  *   BHR_ERR_STATE:   build without the Kerr march (no spin, not forced, no exact redshift): bhr_raymap_build is the call for a
  *                    hole that does not spin; render or read before a build (or after bhr_kerr_raymap_free); render while the
  *                    context's spin or redshift mode is no longer the build's (the message names both).
  *   BHR_ERR_INVALID: a row-block context; everything the Kerr march refuses (a tilted disk, anti_alias = 1, a Disk V2 source,
  *                    adaptive supersampling); bhr_set_supersample(k > 1); "raymap_supersample" other than 1 or "raymap_slots"
- *                    outside 1..8 at a build; a build camera inside the static limit; any build flag; any other render flag;
+ *                    outside 1..8 at a build; "kerr_raymap_supersample" not 1, 2, 4 or 8 (refused by bhr_set_option; a
+ *                    BHR_KERR_RAYMAP_SUPERSAMPLE outside it by the build), a build with k^2 W H >= 2^31 (refused by arithmetic,
+ *                    before any allocation), or k > 1 while a Kerr polarisation is set (bhr_set_kerr_polarization: the momentum
+ *                    build and the Kerr Stokes kernel have no supersampled twin; the message names both);
+ *                    a build camera inside the static limit; any build flag; any other render flag;
  *                    a non-finite t_offset; a view camera that is not a turn of the build's about z; an unknown plane or a
  *                    wrong byte count.  Nothing is launched and the context renders as before. */
 typedef struct {
@@ -686,6 +709,7 @@ BHR_API int32_t bhr_kerr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t fl
 BHR_API int32_t bhr_kerr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
 BHR_API int32_t bhr_kerr_raymap_read(bhr_ctx *ctx, int32_t plane, void *out, int64_t bytes);
 BHR_API int32_t bhr_kerr_raymap_info(bhr_ctx *ctx, bhr_kerr_raymap_desc *out);
+BHR_API int32_t bhr_kerr_raymap_get_supersample(bhr_ctx *ctx, int32_t *k);
 BHR_API int32_t bhr_kerr_raymap_free(bhr_ctx *ctx);
 /* A moving observer: one frame as a camera sees it that moves through bhr_camera.pos with velocity beta (a 3-vector in units of
  * c, |beta| <= 0.995) as the static observer there measures it.  That observer's local frame is identified with the coordinate
@@ -852,6 +876,8 @@ BHR_API int32_t bhr_delayed_resources(int32_t supersampled, int32_t out[3]);
  *   "raymap_slots"    BHR_RAYMAP_SLOTS    crossings a ray map keeps per pixel (1..8, default 4); read by bhr_raymap_build
  *   "raymap_supersample" BHR_RAYMAP_SUPERSAMPLE the next ray map's own supersampling factor (1, 2, 4 or 8, default 1): k x k records per
  *                                         pixel, resolved in the shade; read by bhr_raymap_build; anything else: BHR_ERR_INVALID
+ *   "kerr_raymap_supersample" BHR_KERR_RAYMAP_SUPERSAMPLE the next Kerr ray map's own supersampling factor (1, 2, 4 or 8, default 1): k x k
+ *                                         records per pixel, resolved in the shade; read by bhr_kerr_raymap_build; anything else: BHR_ERR_INVALID
  *   "raymap_shutter_fused" BHR_RAYMAP_SHUTTER_FUSED 1 (default) bhr_raymap_render_shutter shades all samples of a map without overflow
  *                                         pixels in one launch, 0 sample by sample with the accumulation launches (the same bits; A/B runs)
  * (bhr_create only: BHR_FRAME_SLOTS.) */

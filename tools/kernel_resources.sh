@@ -1,7 +1,7 @@
 #!/bin/bash
 # Registers / spills / LDS of every kernel in the built objects, from the code-object metadata (no GPU needed).
 # usage: tools/kernel_resources.sh [object-name-filter]
-#   e.g. kerr_polar: the Kerr polarisation's Stokes kernels (march_kerr_polar.o); kerr_raymap: the Kerr map's, its momentum builds included
+#   e.g. kerr_polar: the Kerr polarisation's Stokes kernels (march_kerr_polar.o); kerr_raymap: the Kerr map's, its momentum builds and its supersampled kernels included
 set -e
 OBJ=/root/repo/black-hole-renderer_amd/lib/obj
 T=$(mktemp -d)
