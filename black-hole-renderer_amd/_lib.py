@@ -37,7 +37,7 @@ SYMBOLS = (
     "bhr_render_observer", "bhr_observer_resources", "bhr_render_delayed", "bhr_delayed_resources",
     "bhr_render_projected", "bhr_projected_resources", "bhr_render_kerr_view", "bhr_kerr_view_resources",
     "bhr_raymap_build", "bhr_raymap_render", "bhr_raymap_render_view", "bhr_raymap_render_shutter", "bhr_raymap_read", "bhr_raymap_get_info", "bhr_raymap_free",
-    "bhr_kerr_raymap_build", "bhr_kerr_raymap_render", "bhr_kerr_raymap_render_view", "bhr_kerr_raymap_read", "bhr_kerr_raymap_info", "bhr_kerr_raymap_get_supersample", "bhr_kerr_raymap_free",
+    "bhr_kerr_raymap_build", "bhr_kerr_raymap_render", "bhr_kerr_raymap_render_view", "bhr_kerr_raymap_render_shutter", "bhr_kerr_raymap_read", "bhr_kerr_raymap_info", "bhr_kerr_raymap_get_supersample", "bhr_kerr_raymap_free",
     "bhr_set_stars", "bhr_get_stars_info", "bhr_stars_resources",
     "bhr_set_polarization", "bhr_read_stokes", "bhr_read_stokes_cells", "bhr_stokes_resources",
     "bhr_set_kerr_polarization", "bhr_kerr_stokes_resources",
@@ -200,6 +200,7 @@ def load() -> C.CDLL:
     lib.bhr_kerr_raymap_build.argtypes = [P, C.POINTER(Camera), C.c_uint32]
     lib.bhr_kerr_raymap_render.argtypes = [P, C.c_float, C.c_uint32]
     lib.bhr_kerr_raymap_render_view.argtypes = [P, C.POINTER(Camera), C.c_uint32]
+    lib.bhr_kerr_raymap_render_shutter.argtypes = [P, C.POINTER(Camera), I32, C.c_uint32]
     lib.bhr_kerr_raymap_read.argtypes = [P, I32, C.c_void_p, C.c_int64]
     lib.bhr_kerr_raymap_info.argtypes = [P, C.POINTER(KerrRayMapDesc)]
     lib.bhr_kerr_raymap_get_supersample.argtypes = [P, C.POINTER(C.c_int32)]

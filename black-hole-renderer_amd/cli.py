@@ -73,8 +73,8 @@ def parse_args(argv=None) -> argparse.Namespace:
                    help="spin of the hole, the dimensionless a/M with |A| <= 0.998 (default: 0, a Schwarzschild hole).  Positive: the "
                         "hole turns with the disk's orbital motion; negative: a retrograde disk.  The spin axis is the disk normal.  "
                         "Marched in Kerr-Schild form by a kernel of its own, whatever --math says.  Not with --disk_tilt, "
-                        "--anti_alias lod_radius, --disk_model v2 / v2_volume, --supersample_threshold, --shutter, the ray-map "
-                        "flags, --passes or --gpus > 1; plain --supersample works")
+                        "--anti_alias lod_radius, --disk_model v2 / v2_volume, --supersample_threshold, --shutter (unless --spin_shutter_map), the "
+                        "ray-map flags, --passes or --gpus > 1; plain --supersample works")
     p.add_argument("--redshift", type=str, default="model", choices=["model", "exact"],
                    help="redshift of the disk around the hole of --spin.  model (default): the reference's g-factor model with "
                         "Kerr's orbital frequency.  exact: the g-factor of the Kerr metric -- frame dragging, the Doppler term from "
@@ -241,13 +241,21 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "grade, --video_codec mjpeg, --video_hdr, --bit_depth 16 and --dither work as ever.  Not with --shutter, "
                         "--supersample > 1, --map_supersample > 1, --gpus > 1, --ray_map, --orbit_map, --shutter_map, the observer "
                         "flags, --projection, --light_delay, --stars point or --polarization")
+    p.add_argument("--spin_shutter_map", action="store_true", default=argparse.SUPPRESS,
+                   help="--video --shutter S with --spin or --redshift exact: motion blur from ONE Kerr ray map.  The spinning hole's "
+                        "view is marched once (frame 0's under --orbit) and every sample of every exposure is shaded from that map -- "
+                        "the disk's roll and, under --orbit, the camera's turn about z, the spin axis, are what a Kerr ray map leaves "
+                        "free -- and averaged on the device; no sample is marched.  --spin_map_supersample K works beside it.  Not "
+                        "with --spin_map (the map of an instantaneous exposure), --ray_map, --orbit_map, --shutter_map, --supersample "
+                        "> 1, --map_supersample > 1, --spin_polarization, --spin_observer, --spin_projection, the observer flags, "
+                        "--projection, --light_delay, --stars point, --polarization or --gpus > 1")
     p.add_argument("--spin_map_supersample", type=int, default=argparse.SUPPRESS, choices=[1, 2, 4, 8], metavar="K",
                    help="--spin_map: the Kerr ray map's own supersampling factor, 1, 2, 4 or 8 (default 1) -- the only anti-aliasing a "
                         "spinning hole has.  The one march of the video marches K x K Kerr rays per pixel and keeps their records; "
                         "every frame shades all of them and resolves each pixel with --supersample's box filter, so with a camera "
                         "that stands still the frames are byte-identical to those of --spin A --supersample K without a march per "
-                        "frame.  Needs --spin_map and takes its restrictions (--supersample and --map_supersample stay 1); not with "
-                        "--spin_polarization")
+                        "frame.  Needs --spin_map or --spin_shutter_map (whose samples are then resolved one by one, ahead of the mean) and "
+                        "takes the map's restrictions (--supersample and --map_supersample stay 1); not with --spin_polarization")
     p.add_argument("--map_supersample", type=int, default=1, choices=[1, 2, 4, 8], metavar="K",
                    help="--ray_map, --orbit_map or --shutter_map: the map's own supersampling factor, 1, 2, 4 or 8 (default 1).  The "
                         "one march of the video marches K x K rays per pixel and keeps their records; every frame shades all of them "
@@ -288,8 +296,29 @@ def parse_args(argv=None) -> argparse.Namespace:
     args.fov = 90 if args.fov is None else args.fov
     if args.shutter > 0 and not args.video:
         p.error("--shutter needs --video: a still image is an instantaneous exposure")
+    if hasattr(args, "spin_shutter_map"):     # (no key without the flag, as for --spin_map)
+        # motion blur from the Kerr ray map (drivers.check_spin_shutter_map has these refusals): ahead of every other check, so that
+        # each names --spin_shutter_map
+        from . import drivers
+        view = kerr_view_from_args(args).get("kerr_view", {})
+        try:
+            drivers.check_spin_shutter_map(
+                True, spin=args.spin, redshift=args.redshift, video=args.video, shutter=args.shutter, spin_map=hasattr(args, "spin_map"),
+                ray_map=args.ray_map, orbit_map=args.orbit_map, shutter_map=args.shutter_map, supersample=args.supersample,
+                map_supersample=args.map_supersample, spin_polarization=hasattr(args, "spin_polarization"),
+                spin_observer=bool(view) and view.get("projection") is None and view.get("projection_fov") is None,
+                spin_projection=view.get("projection") is not None or view.get("projection_fov") is not None,
+                observer=any(v is not None for v in (args.observer, args.observer_velocity, args.observer_sky, args.infall_to)),
+                projection=args.projection != "perspective" or args.projection_fov is not None, light_delay=hasattr(args, "light_delay"),
+                stars=args.stars == "point",
+                # (its four companions count as --polarization's unless --spin_polarization, which they serve too, is there)
+                polarization=hasattr(args, "polarization") or (not hasattr(args, "spin_polarization") and any(
+                    hasattr(args, n) for n in ("polarization_fraction", "polarization_cell", "stokes_output", "polarization_ticks"))),
+                gpus=args.gpus)
+        except ValueError as e:
+            p.error(str(e))
     if hasattr(args, "spin_map_supersample"):     # (no key without the flag, likewise)
-        if not hasattr(args, "spin_map"):
+        if not (hasattr(args, "spin_map") or hasattr(args, "spin_shutter_map")):
             p.error("--spin_map_supersample needs --spin_map: it is the Kerr ray map's factor (marched frames take --supersample)")
         if hasattr(args, "spin_polarization"):
             p.error("--spin_map_supersample does not combine with --spin_polarization: the Stokes planes need a Kerr ray map with one ray per pixel")
@@ -357,7 +386,7 @@ def parse_args(argv=None) -> argparse.Namespace:
             p.error(f"{who} does not combine with --supersample_threshold: the Kerr march has no refinement kernels (plain --supersample works)")
         if args.ray_map or args.orbit_map or args.shutter_map or args.passes is not None:
             p.error(f"{who} does not combine with --ray_map, --orbit_map, --shutter_map or --passes: a ray map holds Schwarzschild rays")
-        if args.shutter > 0:
+        if args.shutter > 0 and not hasattr(args, "spin_shutter_map"):     # (with it the samples come from the Kerr ray map)
             p.error(f"{who} does not combine with --shutter: shutter frames march Schwarzschild rays")
         if args.gpus != 1:
             p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march Schwarzschild rays")
@@ -879,6 +908,8 @@ def main(argv=None) -> int:
         if "kerr_polarization" in pol_kw:
             drivers.check_kerr_polarization(pol_kw["kerr_polarization"], video=True, spin_map=hasattr(args, "spin_map"), orbit=args.orbit,
                                             spin=args.spin, redshift=args.redshift, world=world)
+        if hasattr(args, "spin_shutter_map"):
+            drivers.check_spin_shutter_map(True, spin=args.spin, redshift=args.redshift, shutter=args.shutter, world=world)
         if "BHR_FORCE_DEVICE" in os.environ:        # rehearsal: several ranks sharing one card
             local_rank = int(os.environ["BHR_FORCE_DEVICE"])
         elif world > 1:                             # a launcher that shows every rank only its own GPU: ordinal 0
@@ -905,6 +936,7 @@ def main(argv=None) -> int:
                              **(dict(observer=args.observer, observer_velocity=args.observer_velocity, observer_sky=sky,
                                      infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw,
                              **({"spin_map": True} if hasattr(args, "spin_map") else {}),
+                             **({"spin_shutter_map": True} if hasattr(args, "spin_shutter_map") else {}),
                              **({"spin_map_supersample": args.spin_map_supersample} if hasattr(args, "spin_map_supersample") else {}))
         if world > 1:
             from . import distributed as D

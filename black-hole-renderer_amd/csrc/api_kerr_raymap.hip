@@ -1,11 +1,13 @@
 // api_kerr_raymap.hip -- the Kerr ray map's entry points (include/bhr.h): build, read, info, free, and the refusals of
-// bhr_kerr_raymap_render and bhr_kerr_raymap_render_view (the frames themselves are launched from render.hip, next to
+// bhr_kerr_raymap_render, bhr_kerr_raymap_render_view and bhr_kerr_raymap_render_shutter (the frames themselves are launched from render.hip, next to
 // bhr_raymap_render: they take a frame slot like any other).  The map is a bhr_raymap object of its own, ctx->kerr_raymap, of
 // the Kerr kind; nothing of the Schwarzschild map's state is shared or touched.  This file holds what is Kerr's alone -- what
 // such a map asks of a context, of a build and of a frame; building, reading and freeing the object is api_raymap.hip's, for
 // both kinds.  The kernels are march_kerr_raymap.hip's, their launchers march_launch.hip's.
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <string.h>
 
 #include <vector>
 
@@ -52,6 +54,47 @@ int32_t bhr_kerr_raymap_check_render(bhr_ctx *ctx, const char *who, const bhr_ca
         if (!rm->has_mom)
             return bhr_fail(BHR_ERR_STATE, "%s: a Kerr polarisation is set (bhr_set_kerr_polarization) and the map was built without the photon momenta it needs; build it again (bhr_kerr_raymap_build)", who);
     }
+    return BHR_OK;
+}
+
+// bhr_kerr_raymap_render_shutter's refusals (include/bhr.h), before anything is launched: everything bhr_kerr_raymap_render
+// refuses, then the samples as bhr_raymap_check_render_shutter takes them -- a sample with the build camera's pose, field for
+// field, is the still camera, turn (1, 0); any other has to be a turn of the build camera about z (the spin axis: no tilt to ask
+// about, the Kerr march refuses one).
+int32_t bhr_kerr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned) {
+    const char *who = "bhr_kerr_raymap_render_shutter";
+    if (!ctx || !cams) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    if (n < 1 || n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "%s: %d samples (1 .. %d)", who, n, BHR_SHUTTER_MAX_SAMPLES);
+    if (flags & ~(uint32_t)(BHR_SKIP_BLOOM | BHR_LENS_FLARE))
+        return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
+    for (int j = 0; j < n; ++j)
+        if (!isfinite(cams[j].t_offset)) return bhr_fail(BHR_ERR_INVALID, "%s: sample %d: t_offset is not finite", who, j);
+    // the Kerr Stokes kernel walks one frame's records: a mean of frames has no Stokes planes (bhr_raymap_render_shutter likewise)
+    if (bhr_have_kerr_polar(ctx))
+        return bhr_fail(BHR_ERR_STATE, "%s: a Kerr polarisation is set (bhr_set_kerr_polarization) and shutter frames from the map have no Stokes planes -- switch it off (NULL) first", who);
+    float c1 = 1.0f, s0 = 0.0f;
+    BHR_TRY(bhr_kerr_raymap_check_render(ctx, who, nullptr, 0.0f, flags, &c1, &s0));
+    const bhr_camera &b = ctx->kerr_raymap->cam;
+    memset(smp, 0, sizeof(*smp));
+    *turned = false;
+    for (int j = 0; j < n; ++j) {
+        const bhr_camera &c = cams[j];
+        BhrShutterSample &o = smp->smp[j];
+        o.t = c.t_offset;
+        o.c = 1.0f;
+        o.s = 0.0f;
+        for (int k = 0; k < 3; ++k) o.cp[k] = c.pos[k];
+        bool still = c.pixel_width == b.pixel_width && c.pixel_height == b.pixel_height && c.r_escape == b.r_escape;
+        for (int k = 0; k < 3; ++k)
+            still = still && c.pos[k] == b.pos[k] && c.right[k] == b.right[k] && c.up[k] == b.up[k] && c.forward[k] == b.forward[k];
+        if (still) continue;
+        char sample[64];
+        snprintf(sample, sizeof(sample), "%s: sample %d", who, j);
+        BHR_TRY(bhr_raymap_turn_of_build(b, &c, sample, &o.c, &o.s));
+        *turned = *turned || !(o.c == 1.0f && o.s == 0.0f);
+    }
+    smp->n = n;
+    smp->inv = 1.0f / (float)n;
     return BHR_OK;
 }
 

@@ -221,6 +221,8 @@ enum bhr_march_kernel {
     BHR_MK_KERR_RAYMAP_SHADE_ROT,  // kerr_raymap_shade_kernel<RS, true>: the same with the records turned about z                 kerr_raymap
     BHR_MK_KERR_RAYMAP_FIX,        // kerr_raymap_fix_kernel<RS>: the map's overflow list, marched with the Kerr Ray               kerr_raymap
     BHR_MK_KERR_RAYMAP_BUILD_MOM,  // kerr_raymap_build_mom_kernel<RS>: the build that also keeps each crossing's photon momentum  kerr_raymap
+    BHR_MK_KERR_RAYMAP_SHUTTER,      // kerr_raymap_shade_shutter_kernel<RS, false>: the mean of n frames from the Kerr map, one launch  kerr_raymap
+    BHR_MK_KERR_RAYMAP_SHUTTER_ROT,  // kerr_raymap_shade_shutter_kernel<RS, true>: each sample turned about z by its own angle          kerr_raymap
 };
 
 // The row of a march variant (settings.hip: bhr_variant_row_of): its kernels, and the terms and words of its refusals.
@@ -304,6 +306,8 @@ struct BhrShutterArgs {
 };
 static_assert(sizeof(BhrMarchArgs) + sizeof(BhrRayMapArgs) + sizeof(BhrShutterArgs) + 256 < 4096,
               "raymap_shade_shutter_kernel: explicit and hidden kernel arguments stay under 4096 bytes");
+static_assert(sizeof(BhrKerrExactMarchArgs) + sizeof(BhrRayMapArgs) + sizeof(BhrShutterArgs) + 256 < 4096,
+              "kerr_raymap_shade_shutter_kernel: explicit and hidden kernel arguments stay under 4096 bytes");
 
 // Kernel argument block of adaptive_detect_kernel (march_strict.hip).
 struct BhrDetectArgs {
@@ -346,6 +350,7 @@ struct bhr_options {
     int32_t png16_menu;         // BHR_PNG16_MENU: 1 (default) the 16-bit device PNG codes from its own menu, 0 from the 8-bit one (A/B runs)
     int32_t grade_timing;       // BHR_GRADE_TIMING: 1 a graded frame brackets each launch of its grade stage with HIP events (bhr_debug_read, which = 6); default 0
     int32_t raymap_shutter_fused;   // BHR_RAYMAP_SHUTTER_FUSED: 1 (default) a shutter frame from a map without overflow pixels is one launch, 0 sample by sample (A/B runs, tests)
+    int32_t kerr_raymap_shutter_fused;   // BHR_KERR_RAYMAP_SHUTTER_FUSED: the same for a shutter frame from the Kerr map (k = 1, no overflow pixels); default 1
     int32_t shutter_timing;     // BHR_SHUTTER_TIMING: 1 a shutter frame brackets each accumulation launch with HIP events (bhr_debug_read, which = 5); default 0
     int32_t raymap_slots;       // BHR_RAYMAP_SLOTS / option "raymap_slots": crossings a map keeps per pixel (1..8, default 4), read by bhr_raymap_build, which refuses anything else
     int32_t raymap_ss;          // BHR_RAYMAP_SUPERSAMPLE / option "raymap_supersample": the next map's own factor (1, 2, 4, 8; default 1), read by bhr_raymap_build likewise
@@ -766,6 +771,8 @@ const void *bhr_stars_kernel(int32_t rot);                                      
 // above would store for (smp[j].t, smp[j].c, smp[j].s), into the active slot's BG / DISK; no packed bloom operands.  Opens the
 // frame's march bracket; the caller closes it.  turned: some sample has a turn other than (1, 0).
 int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrShutterArgs &smp, bool turned);
+// ... from the Kerr map (kerr_raymap_shade_shutter_kernel<RS, turned>), under call's Kerr variant and its Kerr block
+int32_t bhr_launch_kerr_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, const BhrShutterArgs &smp, bool turned);
 const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);       // march.hip -> march.o (ss: the supersampled twin)
 const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.hip -> march_strict.o
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.hip -> march_strict_ilp.o
@@ -883,6 +890,8 @@ int32_t bhr_raymap_turn_of_build(const bhr_camera &b, const bhr_camera *cam, con
 // ---- api_kerr_raymap.hip ------------------------------------------------------------------------------------------------------------------
 // the refusals of bhr_kerr_raymap_render and bhr_kerr_raymap_render_view (nothing launched); cam null: the build camera, no turn
 int32_t bhr_kerr_raymap_check_render(bhr_ctx *ctx, const char *who, const bhr_camera *cam, float t_offset, uint32_t flags, float *rot_c, float *rot_s);
+// ... and of bhr_kerr_raymap_render_shutter, which fills smp and tells whether any sample is turned (as bhr_raymap_check_render_shutter)
+int32_t bhr_kerr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned);
 
 // ---- api_stars.hip ----------------------------------------------------------------------------------------------------------------------
 inline bool bhr_have_stars(const bhr_ctx *ctx) { return ctx->stars && ctx->stars->n > 0; }

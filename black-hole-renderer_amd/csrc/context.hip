@@ -43,6 +43,7 @@ void read_options(bhr_options *o) {
     o->png16_menu = num("BHR_PNG16_MENU", 1) != 0;
     o->shutter_timing = num("BHR_SHUTTER_TIMING", 0) != 0;
     o->raymap_shutter_fused = num("BHR_RAYMAP_SHUTTER_FUSED", 1) != 0;
+    o->kerr_raymap_shutter_fused = num("BHR_KERR_RAYMAP_SHUTTER_FUSED", 1) != 0;
     o->grade_timing = num("BHR_GRADE_TIMING", 0) != 0;
     o->raymap_slots = num("BHR_RAYMAP_SLOTS", 4);        // outside 1 .. 8: bhr_raymap_build refuses
     o->raymap_ss = num("BHR_RAYMAP_SUPERSAMPLE", 1);     // not 1, 2, 4 or 8: bhr_raymap_build refuses
@@ -240,6 +241,7 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
     else if (n == "group_schedule") o.group_schedule = v < 0 ? -1 : (v ? 1 : 0);
     else if (n == "shutter_timing") o.shutter_timing = v != 0;
     else if (n == "raymap_shutter_fused") o.raymap_shutter_fused = v != 0;
+    else if (n == "kerr_raymap_shutter_fused") o.kerr_raymap_shutter_fused = v != 0;
     else if (n == "grade_timing") o.grade_timing = v != 0;
     else if (n == "raymap_slots") {   // read by the next bhr_raymap_build; the map in memory keeps its own
         if (!(value >= 1.0 && value <= 8.0)) return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: raymap_slots %g (1 .. 8)", value);

@@ -1,5 +1,5 @@
-// march_kerr_raymap.hip -> march_kerr_raymap.o: the Kerr ray map's kernels (build, shade, shade turned about z, and the march of
-// the overflow list), each with the model redshift and with the exact one, and nothing else.  Built with exactly the flags of
+// march_kerr_raymap.hip -> march_kerr_raymap.o: the Kerr ray map's kernels (build, shade, shade turned about z, the shade of a
+// whole shutter exposure, and the march of the overflow list), each with the model redshift and with the exact one, and nothing else.  Built with exactly the flags of
 // march_kerr.o (csrc/Makefile says why): the kernels are made of the Kerr march's device functions -- Ray<false, RS>, Pending,
 // kerr_shade_hit, sample_skybox, store_pixel (ray_kerr.h, march_device.h) -- and under those flags a function gives the same
 // bits wherever it is inlined.
@@ -32,7 +32,11 @@
 // kernel -- the frame march_kerr_ss_kernel / march_kerr_exact_ss_kernel leaves, bit for bit.  They are kernels of their own
 // beside the k = 1 kernels, which keep their code (tools/code_object_diff.py).
 //
-// No differentials (the Kerr Ray has none); the momentum build has no supersampled form.
+// kerr_raymap_shade_shutter_kernel<RS, ROT> is a shutter frame from the k = 1 map in one launch (bhr_kerr_raymap_render_shutter's
+// fused route): the mean of the n frames kerr_raymap_shade_kernel<RS, ROT> stores under n (t_offset, turn, camera position), the
+// running sums kept on the chip.  A kernel of its own beside the shade kernels, which keep their code.
+//
+// No differentials (the Kerr Ray has none); the momentum build and the shutter kernel have no supersampled form.
 #include <type_traits>
 
 #include "ray_kerr.h"
@@ -269,6 +273,104 @@ __global__ __launch_bounds__(256) void kerr_raymap_shade_kernel(KerrBlock<RS> a,
     store_pixel(a, i, j, a.width, bk, dk);
 }
 
+// A shutter frame from the Kerr map: the mean of the n frames kerr_raymap_shade_kernel<RS, ROT> stores under the samples
+// (t, c, s, cp) = sh.smp[j], j = 0 .. n - 1 (bhr_kerr_raymap_render_shutter; include/bhr.h states the mean) -- march_raymap.hip's
+// raymap_shade_shutter_kernel over the Kerr records.  Same mapping, same grid, same early exits as the k = 1 shade above.
+// The sample loop is the outer one and wave-uniform: sh.smp[j] is indexed by a scalar, so t, c, s and cp come out of scalar
+// loads and stay scalar operands.  Of the argument block the Kerr shade path reads three things that are a sample's own --
+// t_offset in kerr_sample_disk, cp in the model g-factor, cp in kerr_g_exact -- and kerr_shade_hit reads them from a second
+// block, a bare BhrMarchArgs that holds the sample's four floats out of the table and nothing else (ray_kerr.h: kerr_sample_disk
+// says why it is that type); the spin and the ISCO stay on the kernel's own block.
+// A pixel's records, fate and escape direction are read again for every sample (the same 32-byte runs per tile row each time)
+// instead of being held across them.  The six running sums are the only state that lives across samples; they are kept in LDS, a
+// word per lane and channel, conflict free: in registers they are live across the whole of kerr_shade_hit and cost the kernel a
+// wave per SIMD against its k = 1 twin (DESIGN 4 "Kerr shutter frames from the map" has both forms' registers).  No layer goes
+// through memory between the samples.
+// This object is compiled with -ffp-contract=on: the accumulation and the final product sit under `fp contract(off)`, or the last
+// product of a sample's value would be fused into the sum and the mean would no longer be the sum of the frames' stored values.
+// ROT with c = 1, s = 0 (a sample at the build camera among turned ones) is an exact turn.
+// A pixel on the overflow list is left alone, as above: the launcher takes this kernel for maps without one only.
+__shared__ float g_kerr_shutter_acc[6][256];
+template <int RS, bool ROT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RS == KERR_EXACT ? 7 : 8))) void kerr_raymap_shade_shutter_kernel(KerrBlock<RS> a, BhrRayMapArgs m,
+                                                                                                                                      BhrShutterArgs sh) {
+    const int tile = wave_slot();
+    if (tile >= a.n_tiles) return;
+    const int lane = threadIdx.x & 63;
+    const int i = (tile % a.tiles_x) * 8 + (lane & 7);
+    const int j = (tile / a.tiles_x) * 8 + (lane >> 3);
+    if (!(i < a.width && j < a.rows)) return;
+    int pix = j * a.width + i;           // below 2^31: the build refuses a plane that is not
+    const int count = m.crossings[pix];
+    if (count > m.slots) return;
+    // the lane's word of the sums: the wave's number in the block is a scalar and the lane is the low bits of (i, j), so no
+    // register is spent on threadIdx.x across kerr_shade_hit
+    const int t = __builtin_amdgcn_readfirstlane(threadIdx.x & 192) + (i & 7) + ((j & 7) << 3);
+    const size_t p = (size_t)m.plane;
+    for (int smp = 0; smp < sh.n; ++smp) {
+        // The pixel index is made opaque once per sample: the loads below are then not loop-invariant and stay inside the
+        // sample.  Left alone, the compiler hoists the pixel's fate and escape direction out of the sample loop and holds them
+        // across kerr_shade_hit -- 5 or 6 spilled registers (24 / 28 bytes of scratch) at the k = 1 twin's occupancy.
+        asm volatile("" : "+v"(pix));
+        // the fields of the argument block that are a frame's own; the rest of this block is never set
+        BhrMarchArgs fs;
+        fs.t_offset = sh.smp[smp].t;
+        fs.cp[0] = sh.smp[smp].cp[0];
+        fs.cp[1] = sh.smp[smp].cp[1];
+        fs.cp[2] = sh.smp[smp].cp[2];
+        const float rc = ROT ? sh.smp[smp].c : 1.0f, rs = ROT ? sh.smp[smp].s : 0.0f;
+        Shade shd;                       // as Ray::init leaves it
+        shd.accum = mk(0, 0, 0);
+        shd.alpha_total = 0.0f;
+        shd.unsure = 0;
+        for (int c = 0; c < count; ++c) {
+            const float *q = m.hits + (size_t)c * m.comps * p + pix;
+            float hx = q[0], hy = q[p];
+            V3 to_cam = mk(q[2 * p], q[3 * p], q[4 * p]);
+            if (ROT) {
+                turn_xy(rc, rs, hx, hy);
+                turn_xy(rc, rs, to_cam.x, to_cam.y);
+            }
+            kerr_shade_hit<RS>(a, fs, shd, hx, hy, to_cam);
+        }
+        const bool esc = m.status[pix] == 1;
+        V3 dir = mk(m.dir[pix], m.dir[p + pix], m.dir[2 * p + pix]);
+        if (ROT) turn_xy(rc, rs, dir.x, dir.y);
+        float bk[3], dk[3];
+        raymap_pixel_values(a, esc, dir, shd, bk, dk);
+        {
+#pragma clang fp contract(off)
+            // acc = L_0, then acc = acc + L_j: one f32 addition per channel (smp is wave-uniform)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                g_kerr_shutter_acc[k][t] = smp == 0 ? bk[k] : g_kerr_shutter_acc[k][t] + bk[k];
+                g_kerr_shutter_acc[3 + k][t] = smp == 0 ? dk[k] : g_kerr_shutter_acc[3 + k][t] + dk[k];
+            }
+        }
+    }
+    float acc_b[3], acc_d[3];
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            acc_b[k] = g_kerr_shutter_acc[k][t];
+            acc_d[k] = g_kerr_shutter_acc[3 + k][t];
+            if (sh.n > 1) {
+                acc_b[k] = acc_b[k] * sh.inv;
+                acc_d[k] = acc_d[k] * sh.inv;
+            }
+        }
+    }
+    // six plain stores: the pack kernel makes the split post-pass's operands from the resolved layer, as behind every shutter frame
+    const size_t o = ((size_t)j * a.width + i) * 3;
+    a.bg[o + 0] = acc_b[0];
+    a.bg[o + 1] = acc_b[1];
+    a.bg[o + 2] = acc_b[2];
+    a.disk[o + 0] = acc_d[0];
+    a.disk[o + 1] = acc_d[1];
+    a.disk[o + 2] = acc_d[2];
+}
+
 // What resolve_store (march_device.h) asks of a ray: the six values it leaves.  Here they come out of the lane's records.
 struct KerrRayMapValues {
     float v[6];
@@ -406,7 +508,7 @@ __global__ __launch_bounds__(256) void kerr_raymap_fix_ss_kernel(KerrBlock<RS> a
 
 // ---- the kernels of this object, by the launcher's names (march_launch.hip); null: not in this object ----------
 // exact: the kernels of the exact redshift (they take BhrKerrExactMarchArgs); ss: the kernels of a supersampled map (a.ss > 1;
-// the momentum build has none)
+// the momentum build has none, and neither have the shutter kernels: a supersampled map's shutter frames go sample by sample)
 const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact, int32_t ss) {
     if (ss) {
         switch (k) {
@@ -423,6 +525,10 @@ const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact, int3
     case BHR_MK_KERR_RAYMAP_SHADE_ROT: return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, true> : (const void *)kerr_raymap_shade_kernel<0, true>;
     case BHR_MK_KERR_RAYMAP_BUILD_MOM: return exact ? (const void *)kerr_raymap_build_mom_kernel<KERR_EXACT> : (const void *)kerr_raymap_build_mom_kernel<0>;
     case BHR_MK_KERR_RAYMAP_FIX: return exact ? (const void *)kerr_raymap_fix_kernel<KERR_EXACT> : (const void *)kerr_raymap_fix_kernel<0>;
+    case BHR_MK_KERR_RAYMAP_SHUTTER:
+        return exact ? (const void *)kerr_raymap_shade_shutter_kernel<KERR_EXACT, false> : (const void *)kerr_raymap_shade_shutter_kernel<0, false>;
+    case BHR_MK_KERR_RAYMAP_SHUTTER_ROT:
+        return exact ? (const void *)kerr_raymap_shade_shutter_kernel<KERR_EXACT, true> : (const void *)kerr_raymap_shade_shutter_kernel<0, true>;
     default: return nullptr;
     }
 }

@@ -727,3 +727,26 @@ int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call
     BHR_HIP(hipGetLastError());
     return BHR_OK;
 }
+
+// ... from the Kerr map (bhr_kerr_raymap_render_shutter's fused route): the Kerr shade kernel's grid, the Kerr block of call's
+// variant in the march block's place (variant_args: the spin, and the ISCO for the exact redshift), the map, the table.
+int32_t bhr_launch_kerr_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, const BhrShutterArgs &smp, bool turned) {
+    const char *api = "bhr_kerr_raymap_render_shutter";
+    const bhr_march_variant v = call.req.variant;
+    if (v != BHR_MV_KERR && v != BHR_MV_KERR_EXACT) return bhr_fail(BHR_ERR_STATE, "%s: the frame is not a Kerr variant's", api);
+    BhrMarchArgs a;
+    BHR_TRY(raymap_shade_args(ctx, call, m, false, 1, api, a));
+    if (smp.n < 1 || smp.n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "%s: %d samples (1 .. %d)", api, smp.n, BHR_SHUTTER_MAX_SAMPLES);
+    if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "%s: the fused launch has no supersampled kernel (factor %d)", api, call.ss);
+    if (a.diskp) return bhr_fail(BHR_ERR_STATE, "%s: the fused launch takes a skip-bloom call (it stores no packed bloom operands)", api);
+    const void *fn = bhr_march_kernel_kerr_raymap(turned ? BHR_MK_KERR_RAYMAP_SHUTTER_ROT : BHR_MK_KERR_RAYMAP_SHUTTER, v == BHR_MV_KERR_EXACT, 0);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "%s: no shutter shade kernel in this library", api);
+    BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
+    VariantArgs va;
+    BhrRayMapArgs mm = m;
+    BhrShutterArgs ss = smp;
+    void *args[] = {variant_args(ctx, call.req, a, va), &mm, &ss};
+    (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
+    BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}

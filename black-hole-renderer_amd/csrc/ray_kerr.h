@@ -100,11 +100,18 @@ __device__ __forceinline__ float kerr_omega(float r_safe, float a) {
 
 // _sample_disk (render.py:2568-2600) at level 0 with the Boyer-Lindquist hit radius and Kerr's Omega in the roll
 // (march_device.h: sample_disk_level is the Schwarzschild sampler and stays as it is)
-__device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, float hit_x, float hit_y, float hit_r) {
+// f: the block the fields that are a FRAME's own are read from -- t_offset here, cp in the g-factors below -- `a` itself in every
+// march and every map frame (the overloads without it).  A shutter frame from the Kerr map shades one set of records as several
+// frames and hands over a bare BhrMarchArgs that holds each sample's four floats and nothing else (march_kerr_raymap.hip):
+// ONLY f.t_offset and f.cp may be read through f, and kerr(a) / kerr_exact(a) stay on `a` -- f is not inside a Kerr block.
+// A BhrMarchArgs and not a type of its own for march_device.h's reason (shade_hit): read through the same struct type the
+// fields keep their access metadata and every existing Kerr kernel compiles to the bytes it had (tools/code_object_diff.py;
+// profiles/kerr_map_shutter_code_objects.txt is the last run).
+__device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, const BhrMarchArgs &f, float hit_x, float hit_y, float hit_r) {
     const BhrScene &sc = a.sc;
     float phi = atan2f(hit_y, hit_x);
     const float r_safe = fmaxf(hit_r, 1e-3f);
-    phi = phi + a.t_offset * kerr_omega(r_safe, kerr(a).kerr_a);
+    phi = phi + f.t_offset * kerr_omega(r_safe, kerr(a).kerr_a);
     while (phi < 0) phi += BHR_TWO_PI_F;
     while (phi >= BHR_TWO_PI_F) phi -= BHR_TWO_PI_F;
     const float u = phi / BHR_TWO_PI_F * (float)sc.n_phi;
@@ -119,6 +126,9 @@ __device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, float 
     const float4 c01 = t[(size_t)v1_h * stride + u0_w], c11 = t[(size_t)v1_h * stride + u1_w];
     return make_float4(BHR_BILERP(c00.x, c10.x, c01.x, c11.x), BHR_BILERP(c00.y, c10.y, c01.y, c11.y),
                        BHR_BILERP(c00.z, c10.z, c01.z, c11.z), BHR_BILERP(c00.w, c10.w, c01.w, c11.w));
+}
+__device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, float hit_x, float hit_y, float hit_r) {
+    return kerr_sample_disk(a, a, hit_x, hit_y, hit_r);
 }
 
 // The g-factor of the Kerr metric for a crossing at Boyer-Lindquist radius r of the plane, g = nu_obs / nu_em with both
@@ -141,10 +151,11 @@ __device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, float 
 //             difference vanishes at r_isco and its square root there is the square root of the rounding (3e-4 in f32).
 // tests/kerr_redshift_ref.py states the same in NumPy; tests/test_kerr_redshift_ref.py checks it against the 4 x 4 metric.
 // obs_d: nu_moving / nu_static of the ray at a camera that moves (ray_kerr_observer.h), a factor of nu_obs; 1 at rest.
-__device__ __forceinline__ float kerr_g_exact(const BhrMarchArgs &a, float hx, float hy, float r, V3 ph, float obs_d = 1.0f) {
+// f: the block the camera position is read from (kerr_sample_disk says what it is).
+__device__ __forceinline__ float kerr_g_exact(const BhrMarchArgs &a, const BhrMarchArgs &f, float hx, float hy, float r, V3 ph, float obs_d = 1.0f) {
     const BhrKerrExactMarchArgs &k = kerr_exact(a);
     const float ka = k.kerr_a, a2 = ka * ka;
-    V3 c = ld3(a.cp);
+    V3 c = ld3(f.cp);
     asm volatile("" : "+v"(c.x));                // recomputed per hit, as the model's camera radius is
     const float cw = dot(c, c) - a2;
     const float cS = sqrtf(cw * cw + 4.0f * a2 * (c.z * c.z));
@@ -173,19 +184,23 @@ __device__ __forceinline__ float kerr_g_exact(const BhrMarchArgs &a, float hx, f
     }
     return fminf(nu_obs * obs_d / fmaxf(nu_em, 1e-3f), BHR_G_FACTOR_CAP);
 }
+__device__ __forceinline__ float kerr_g_exact(const BhrMarchArgs &a, float hx, float hy, float r, V3 ph, float obs_d = 1.0f) {
+    return kerr_g_exact(a, a, hx, hy, r, ph, obs_d);
+}
 
 // _apply_g_factor (render.py:2439-2516) for the untilted disk, unchanged but for the orbital frequency (Kerr's) and the
 // emitter's radius, which is the Boyer-Lindquist hit radius the frequency is a function of.  The exact Kerr g-factor
 // u^t (1 - Omega L_z) with frame dragging is kerr_g_exact above.  RS = KERR_EXACT: to_cam is the photon's momentum at the hit instead and
 // g is kerr_g_exact's; everything downstream of g is the same code.
+// f: the block the camera position is read from (kerr_sample_disk says what it is).
 template <int RS>
-__device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color, float hit_x, float hit_y, float hit_r, V3 to_cam, float obs_d = 1.0f) {
+__device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, const BhrMarchArgs &f, V3 base_color, float hit_x, float hit_y, float hit_r, V3 to_cam, float obs_d = 1.0f) {
     const float rs_f = BHR_RS;
     float g;
     if (RS == KERR_EXACT) {
-        g = kerr_g_exact(a, hit_x, hit_y, hit_r, to_cam, obs_d);
+        g = kerr_g_exact(a, f, hit_x, hit_y, hit_r, to_cam, obs_d);
     } else {
-        V3 cam_pos = ld3(a.cp);
+        V3 cam_pos = ld3(f.cp);
         asm volatile("" : "+v"(cam_pos.x));          // recomputed per hit, not kept across the march loop (march_device.h: apply_g_factor)
         const float r_obs = sqrtf(dot(cam_pos, cam_pos));
         const float r_em = hit_r;
@@ -226,21 +241,30 @@ __device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color
     out.z = fminf(fmaxf(out.z, 0.0f), 10.0f);
     return out;
 }
+template <int RS>
+__device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color, float hit_x, float hit_y, float hit_r, V3 to_cam, float obs_d = 1.0f) {
+    return kerr_g_factor<RS>(a, a, base_color, hit_x, hit_y, hit_r, to_cam, obs_d);
+}
 
 // one disk crossing, shaded and composited front to back (render.py:2951-3002 without the mip levels); obs_d: the moving
-// camera's factor of g ahead of its cap in both redshift modes (1: the camera at rest)
+// camera's factor of g ahead of its cap in both redshift modes (1: the camera at rest); f: the block the frame's own fields
+// (t_offset, cp) are read from (kerr_sample_disk says what it is)
 template <int RS>
-__device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam, float obs_d = 1.0f) {
+__device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, const BhrMarchArgs &f, Shade &sh, float hit_x, float hit_y, V3 to_cam, float obs_d = 1.0f) {
     const float hit_r = sqrtf(hit_x * hit_x + hit_y * hit_y - kerr(a).kerr_a * kerr(a).kerr_a);
     if (!(a.r_outer >= hit_r && hit_r >= a.r_inner)) return;
-    const float4 rgba = kerr_sample_disk(a, hit_x, hit_y, hit_r);
+    const float4 rgba = kerr_sample_disk(a, f, hit_x, hit_y, hit_r);
     const float base_alpha = fminf(rgba.w, 0.999f);
     const float disk_alpha = 1.0f - powf(1.0f - base_alpha, BHR_DISK_ALPHA_GAIN);
-    const V3 col = kerr_g_factor<RS>(a, mk(rgba.x, rgba.y, rgba.z), hit_x, hit_y, hit_r, to_cam, obs_d);
+    const V3 col = kerr_g_factor<RS>(a, f, mk(rgba.x, rgba.y, rgba.z), hit_x, hit_y, hit_r, to_cam, obs_d);
     const float front = 1.0f - sh.alpha_total;
     const float wgt = disk_alpha * front;
     sh.accum = mk(sh.accum.x + col.x * wgt, sh.accum.y + col.y * wgt, sh.accum.z + col.z * wgt);
     sh.alpha_total = 1.0f - front * (1.0f - disk_alpha);
+}
+template <int RS>
+__device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam, float obs_d = 1.0f) {
+    kerr_shade_hit<RS>(a, a, sh, hit_x, hit_y, to_cam, obs_d);
 }
 
 // MOM (the Kerr ray map's build under a Kerr polarisation, march_kerr_raymap.hip): a crossing also parks the photon's whole

@@ -1,5 +1,5 @@
 // render.hip -- the kinds of frame on a frame slot (marched, under any march variant; shutter; from a ray map of either kind,
-// its view and the Schwarzschild map's shutter), and the one place that rotates the slots and keeps the last frame's record.
+// its view and its shutter), and the one place that rotates the slots and keeps the last frame's record.
 // One frame: march -> bloom H -> bloom V + combine (-> lens flare).  Frames alternate between the context's two
 // frame slots (bhr_frame_slot): frame n + 1 is launched on the other slot's stream into its own buffers and overlaps
 // the tail and the post-passes of frame n.  The scene is only read; everything that writes it or reads a frame goes
@@ -167,9 +167,15 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_raymap &rm, const bhr_camera *cam
 // stores the mean.  Unfused: shutter_on_slot with a map frame in place of each march -- the shade launch and the strict fix
 // launch over the overflow list as raymap_on_slot issues them, as a skip-bloom call, then the accumulation launch; a later
 // sample keeps the frame's march-start event and the march-end event is recorded once behind the last accumulation.
-int32_t raymap_shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, const BhrShutterArgs &smp, bool turned, uint32_t flags, int k, int ring, frame_marches *fm) {
+// The map `rm` is of either kind.  A Kerr map's frame (bhr_kerr_raymap_render_shutter) runs under the context's Kerr variant:
+// the unfused route's launches take the Kerr map's kernels, the fused launch is the Kerr map's own, and its option is
+// "kerr_raymap_shutter_fused".
+int32_t raymap_shutter_on_slot(bhr_ctx *ctx, const bhr_raymap &rm, const bhr_camera *cams, const BhrShutterArgs &smp, bool turned, uint32_t flags, int k, int ring,
+                               frame_marches *fm) {
     bhr_frame_slot &f = ctx->slots[k];
-    const bhr_raymap &rm = *ctx->raymap;
+    const bool kerr = rm.kind == BHR_RAYMAP_KERR;
+    const bhr_variant_request req = {kerr ? bhr_variant_of(ctx) : BHR_MV_NONE};
+    const bool fused = kerr ? ctx->opt.kerr_raymap_shutter_fused != 0 : ctx->opt.raymap_shutter_fused != 0;
     const int n = smp.n;
     // the layers are the strict arithmetic's; the post-pass on the resolved layers is the one bhr_bloom would run on them in this
     // context -- the context's arithmetic decides its kernels (exact f32 under strict, split f16 under fast / hybrid)
@@ -177,14 +183,16 @@ int32_t raymap_shutter_on_slot(bhr_ctx *ctx, const bhr_camera *cams, const BhrSh
     *fm = {rm.ss, n, false};
     ctx->shutter_ev_n = 0;            // option "shutter_timing": the fused route has no accumulation launch to bracket
     // (a supersampled map always goes sample by sample: there is no fused supersampled kernel, whatever "raymap_shutter_fused" says)
-    if (n > 1 && rm.overflow_pixels == 0 && ctx->opt.raymap_shutter_fused && rm.ss == 1) {
+    if (n > 1 && rm.overflow_pixels == 0 && fused && rm.ss == 1) {
         // no march launch follows the fused one: nothing counts into the frame's counter cell, which was cleared ahead of time
-        const bhr_march_call call = {&cams[0], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ 1};
-        BHR_TRY(bhr_launch_raymap_shade_shutter(ctx, call, rm.a, rm.diff != 0, smp, turned));
+        const bhr_march_call call = {&cams[0], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ 1,
+                                     /* keep_start */ false, req};
+        if (kerr) BHR_TRY(bhr_launch_kerr_raymap_shade_shutter(ctx, call, rm.a, smp, turned));
+        else BHR_TRY(bhr_launch_raymap_shade_shutter(ctx, call, rm.a, rm.diff != 0, smp, turned));
     } else {
         for (int j = 0; j < n; ++j) {
             const bhr_march_call call = {&cams[j], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ rm.ss,
-                                         /* keep_start */ j > 0};
+                                         /* keep_start */ j > 0, req};
             BHR_TRY(raymap_frame_launches(ctx, call, rm, smp.smp[j].c, smp.smp[j].s));
             if (n > 1) BHR_TRY(bhr_launch_shutter_accumulate(ctx, j, n));
         }
@@ -398,7 +406,18 @@ int32_t bhr_raymap_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t 
     BHR_TRY(bhr_raymap_check_render_shutter(ctx, cams, n, flags, &smp, &turned));
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     const uint32_t fl = raymap_frame_flags(ctx, flags);
-    return frame_on_next_slot(ctx, fl, false, [&](int k, int ring, frame_marches *fm) { return raymap_shutter_on_slot(ctx, cams, smp, turned, fl, k, ring, fm); });
+    return frame_on_next_slot(ctx, fl, false, [&](int k, int ring, frame_marches *fm) { return raymap_shutter_on_slot(ctx, *ctx->raymap, cams, smp, turned, fl, k, ring, fm); });
+}
+
+// Motion blur from the Kerr ray map (include/bhr.h): one frame as the mean of n frames from the Kerr map, no march.  A frame like
+// bhr_kerr_raymap_render's in slot, timing ring and calibration, under the flags as they are and the context's Kerr variant.
+int32_t bhr_kerr_raymap_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags) {
+    BhrShutterArgs smp;
+    bool turned = false;
+    BHR_TRY(bhr_kerr_raymap_check_render_shutter(ctx, cams, n, flags, &smp, &turned));
+    BHR_HIP(hipSetDevice(ctx->cfg.device));
+    return frame_on_next_slot(ctx, flags, false,
+                              [&](int k, int ring, frame_marches *fm) { return raymap_shutter_on_slot(ctx, *ctx->kerr_raymap, cams, smp, turned, flags, k, ring, fm); });
 }
 
 }  // extern "C"

@@ -615,14 +615,15 @@ def check_polarization(polarization, video: bool = False, ray_map: bool = False,
 # conditions it refuses, in the order it names them (the first one violated is the one raised).
 _MAP_REFUSALS = {
     "no_spin": (lambda f: f["spin"] == 0 and f["redshift"] == "model",
-                "{flag} needs --spin or --redshift exact: it is the ray map of the Kerr march; a hole that does not spin takes --ray_map or --orbit_map"),
+                "{flag} needs --spin or --redshift exact: it is the ray map of the Kerr march; a hole that does not spin takes {plain}"),
     "no_video": (lambda f: not f["video"], "{flag} needs --video: it is the ray map of {video}"),
     "no_orbit": (lambda f: not f["orbit"], "{flag} needs --orbit: a camera that stands still takes --ray_map"),
-    "no_shutter": (lambda f: not f["shutter"] > 0, "{flag} needs --shutter > 0: an instantaneous exposure takes --ray_map or --orbit_map"),
+    "no_shutter": (lambda f: not f["shutter"] > 0, "{flag} needs --shutter > 0: an instantaneous exposure takes {instant}"),
     "orbit": (lambda f: f["orbit"], "a ray map is one view: {flag} does not combine with --orbit"),
     "ray_map": (lambda f: f["ray_map"], "{flag} does not combine with --ray_map: that is {other_map}"),
     "orbit_map": (lambda f: f["orbit_map"], "{flag} does not combine with --orbit_map: that is {other_map}"),
     "shutter_map": (lambda f: f["shutter_map"], "{flag} does not combine with --shutter_map: that is {other_map}"),
+    "spin_map": (lambda f: f["spin_map"], "{flag} does not combine with --spin_map: that is the map of an instantaneous exposure"),
     "disk_tilt": (lambda f: f["disk_tilt"] != 0, "the orbit is a symmetry of an untilted disk only: {flag} needs --disk_tilt 0"),
     "orbit_disk_tilt": (lambda f: f["orbit"] and f["disk_tilt"] != 0,
                         "the orbit is a symmetry of an untilted disk only: {flag} with --orbit needs --disk_tilt 0"),
@@ -637,16 +638,24 @@ _MAP_REFUSALS = {
     "light_delay": (lambda f: f["light_delay"], "{flag} does not combine with --light_delay: the delayed march is Schwarzschild's"),
     "stars": (lambda f: f["stars"], "{flag} does not combine with --stars point: point stars are rendered through the map of Schwarzschild rays"),
     "polarization": (lambda f: f["polarization"], "{flag} does not combine with --polarization: the transport rule is Schwarzschild's"),
+    "spin_polarization": (lambda f: f["spin_polarization"],
+                          "{flag} does not combine with --spin_polarization: shutter frames from the Kerr map have no Stokes planes"),
+    "spin_observer": (lambda f: f["spin_observer"], "{flag} does not combine with --spin_observer: a Kerr ray map holds the rays of the camera at rest"),
+    "spin_projection": (lambda f: f["spin_projection"], "{flag} does not combine with --spin_projection: a Kerr ray map holds the rays of the pinhole camera"),
 }
 _MAPS = {
     "ray_map": dict(flag="--ray_map", a_map="a ray map", refuses="orbit shutter supersample disk_model gpus"),
     "orbit_map": dict(flag="--orbit_map", a_map="a ray map", video="an orbit video", other_map="the map of a camera that stands still",
                       refuses="no_video no_orbit ray_map disk_tilt shutter supersample disk_model gpus"),
-    "shutter_map": dict(flag="--shutter_map", a_map="a ray map", other_map="the map of an instantaneous exposure",
+    "shutter_map": dict(flag="--shutter_map", a_map="a ray map", other_map="the map of an instantaneous exposure", instant="--ray_map or --orbit_map",
                         refuses="no_shutter ray_map orbit_map orbit_disk_tilt supersample disk_model gpus"),
-    "spin_map": dict(flag="--spin_map", a_map="a Kerr ray map", video="a video", other_map="a map of Schwarzschild rays",
+    "spin_map": dict(flag="--spin_map", a_map="a Kerr ray map", video="a video", other_map="a map of Schwarzschild rays", plain="--ray_map or --orbit_map",
                      refuses="no_spin no_video shutter supersample_unset map_supersample gpus ray_map orbit_map shutter_map "
                              "observer projection light_delay stars polarization"),
+    "spin_shutter_map": dict(flag="--spin_shutter_map", a_map="a Kerr ray map", video="a motion-blurred video", other_map="a map of Schwarzschild rays",
+                             plain="--shutter_map", instant="--spin_map",
+                             refuses="no_spin no_video no_shutter spin_map ray_map orbit_map shutter_map supersample_unset map_supersample "
+                                     "spin_polarization spin_observer spin_projection observer projection light_delay stars polarization gpus"),
 }
 
 
@@ -748,6 +757,21 @@ def check_spin_map(spin_map: bool, spin: float = 0.0, redshift: str = "model", v
         _check_map("spin_map", locals())
 
 
+def check_spin_shutter_map(spin_shutter_map: bool, spin: float = 0.0, redshift: str = "model", video: bool = True, shutter: float = 0.5,
+                           spin_map: bool = False, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False, supersample=1,
+                           map_supersample=1, spin_polarization: bool = False, spin_observer: bool = False, spin_projection: bool = False,
+                           observer: bool = False, projection: bool = False, light_delay: bool = False, stars: bool = False,
+                           polarization: bool = False, gpus: int = 1, world: int = 1) -> None:
+    """--spin_shutter_map is motion blur from ONE Kerr ray map (render_video): a spinning hole's view marched once, every sample of
+    every exposure shaded from it -- the disk's roll and, under --orbit, the camera's turn about the spin axis are what the map
+    leaves free.  It needs a spin or the exact redshift (the Kerr march), a video, an open shutter, one ray per pixel of the
+    context (--spin_map_supersample is the map's own factor) and one GPU, and none of --spin_map (the map of an instantaneous
+    exposure), the Schwarzschild maps, the Kerr polarisation, the Kerr camera or what a spin refuses anyway.  Raises ValueError
+    naming --spin_shutter_map and the other flag, before any device work."""
+    if spin_shutter_map:
+        _check_map("spin_shutter_map", locals())
+
+
 # A video's map as render_video drives it: per mode the build of its one map, with the line it prints, the frame from it and the
 # free.  fr: the frame's camera and, under a shutter, its samples.  (The build view needs no entry: frame 0 of the orbit under
 # ``orbit``, else the camera that stands still -- ray_map has no orbit and orbit_map always one, by their checks.)
@@ -783,6 +807,9 @@ _MAP_MODES = {
     # the Kerr map; an orbit frame turned to its camera
     "spin_map": dict(build=_build_kerr_map, free="free_kerr_ray_map",
                      frame=lambda r, fr: r.render_from_kerr_ray_map_async(frame=0, cam_pos=fr["cam_pos"] if fr["orbit"] else None)),
+    # the marched shutter loop's samples from the Kerr map
+    "spin_shutter_map": dict(build=_build_kerr_map, free="free_kerr_ray_map",
+                             frame=lambda r, fr: r.render_shutter_from_kerr_ray_map_async(fr["t_offsets"], fr["positions"] if fr["orbit"] else None, fr["fov"])),
 }
 
 
@@ -882,14 +909,15 @@ def check_map_supersample(k, ray_map: bool = False, orbit_map: bool = False, shu
                          "(marched frames take --supersample)")
 
 
-def check_spin_map_supersample(k, spin_map: bool = False, spin_polarization: bool = False) -> None:
+def check_spin_map_supersample(k, spin_map: bool = False, spin_polarization: bool = False, spin_shutter_map: bool = False) -> None:
     """--spin_map_supersample k / render_video(spin_map=True, spin_map_supersample=k): the Kerr ray map's own supersampling
     factor (k x k records per pixel, resolved in the shade; HipRenderer.build_kerr_ray_map(supersample=k)).  1, 2, 4 or 8, above
-    1 only with --spin_map and not with --spin_polarization (the Stokes planes need a map with one ray per pixel).  Raises
-    ValueError naming both flags, before any device work."""
+    1 only with --spin_map or --spin_shutter_map (whose samples are then resolved one by one, ahead of the mean) and not with
+    --spin_polarization (the Stokes planes need a map with one ray per pixel).  Raises ValueError naming both flags, before any
+    device work."""
     if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4, 8):
         raise ValueError(f"spin_map_supersample must be 1, 2, 4 or 8, got {k!r}")
-    if k > 1 and not spin_map:
+    if k > 1 and not (spin_map or spin_shutter_map):
         raise ValueError("--spin_map_supersample is the Kerr ray map's factor: it needs --spin_map (marched frames take --supersample)")
     if k > 1 and spin_polarization:
         raise ValueError("--spin_map_supersample does not combine with --spin_polarization: the Stokes planes need a Kerr ray map with one ray per pixel")
@@ -943,7 +971,7 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
                     shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None,
                     stars=None, projection=None, light_delay=None, polarization=None, spin_map=False, kerr_view=None,
-                    spin_map_supersample=1) -> dict:
+                    spin_map_supersample=1, spin_shutter_map=False) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -967,6 +995,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(shutter_map=True)
     if spin_map:
         params.update(spin_map=True)
+    if spin_shutter_map:
+        params.update(spin_shutter_map=True)
     if spin_map_supersample > 1:
         params.update(spin_map_supersample=spin_map_supersample)
     if map_supersample > 1:
@@ -1026,6 +1056,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
                  light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, spin_map: bool = False,
                  kerr_polarization: Optional[dict] = None, kerr_view: Optional[dict] = None, spin_map_supersample: int = 1,
+                 spin_shutter_map: bool = False,
                  **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
@@ -1104,6 +1135,13 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     ``kerr_polarization`` (check_spin_map_supersample).  The progress record carries ``spin_map_supersample`` when it is above 1,
     and a resume with another factor starts over.
 
+    ``spin_shutter_map=True`` (a renderer with a spin or the exact redshift, ``shutter > 0``): motion blur from ONE Kerr ray map
+    -- ``shutter_map`` for the spinning hole.  The map is built once (frame 0's view under ``orbit``, else ``static_cam_pos``; with
+    ``spin_map_supersample`` = k its own factor) and every frame is render_shutter_from_kerr_ray_map_async of exactly the sample
+    times, positions and t_offsets the ``shutter_map`` loop hands render_shutter_from_ray_map_async; no sample is marched.  Refused
+    with ValueError, before any device work, with what check_spin_shutter_map names.  The progress record carries
+    ``spin_shutter_map`` when it is set, and a resume with the other setting starts over.
+
     ``shutter_map=True`` (with ``shutter > 0``): motion blur from ONE ray map.  What differs between the samples of an exposure
     -- the disk's roll, and under ``orbit`` the camera's turn about z -- is what a map leaves free, so no sample is marched: the
     map is built once (for orbit_position(static_cam_pos, 0, ...) under ``orbit``, else for ``static_cam_pos``) and every frame is
@@ -1166,7 +1204,22 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     fly-around on the equatorial geodesic.  Refused with ValueError, before any device work, with what check_kerr_view names.  The
     progress record carries the camera when one is given, and a resume under another starts over."""
     # the Kerr map's own factor: refused first, before the renderer is asked anything
-    check_spin_map_supersample(spin_map_supersample, spin_map=spin_map, spin_polarization=kerr_polarization is not None)
+    check_spin_map_supersample(spin_map_supersample, spin_map=spin_map, spin_polarization=kerr_polarization is not None,
+                               **({"spin_shutter_map": True} if spin_shutter_map else {}))
+    if spin_shutter_map:
+        # motion blur from the Kerr map: ahead of every other check, so that each refusal names it -- first what the call itself
+        # says, before the renderer is asked anything, then with the renderer's spin, redshift and supersampling
+        said = dict(video=True, shutter=shutter, spin_map=spin_map, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map,
+                    map_supersample=map_supersample, spin_polarization=kerr_polarization is not None,
+                    spin_observer=kerr_view is not None and kerr_view.get("projection") is None,
+                    spin_projection=kerr_view is not None and kerr_view.get("projection") is not None,
+                    observer=observer is not None or observer_velocity is not None or infall_to is not None,
+                    projection=projection is not None or projection_fov is not None, light_delay=light_delay is not None,
+                    stars=stars is not None, polarization=polarization is not None or (stokes_path is not None and kerr_polarization is None),
+                    world=world)
+        check_spin_shutter_map(True, spin=1.0, supersample=1 if supersample is None else supersample, **said)
+        check_spin_shutter_map(True, spin=renderer.spin, redshift=renderer.redshift,
+                               supersample=renderer.supersample if supersample is None else supersample, **said)
     kerr_plan = None
     if kerr_view is not None:                                   # (without one the renderer is not asked anything, as ever)
         from . import observer as obs_mod
@@ -1242,7 +1295,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         check_ray_map(ray_map, orbit=orbit, shutter=shutter, supersample=renderer.supersample if supersample is None else supersample,
                       disk_model=disk_model, world=world)
     # the checks have refused every combination of two: the video's one map, or none
-    mode = next((m for m, on in (("ray_map", ray_map), ("orbit_map", orbit_map), ("shutter_map", shutter_map), ("spin_map", spin_map)) if on), None)
+    mode = next((m for m, on in (("ray_map", ray_map), ("orbit_map", orbit_map), ("shutter_map", shutter_map), ("spin_map", spin_map),
+                                 ("spin_shutter_map", spin_shutter_map)) if on), None)
     # point stars: the renderer carries the catalogue (make_renderer(stars=)); the frames that show it are the map's
     if stars is not None:
         stars = check_stars(stars, supersample=renderer.supersample if supersample is None else supersample, spin=renderer.spin,
@@ -1281,7 +1335,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                              **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}),
                              **({} if light_delay is None else {"light_delay": light_delay}),
                              **({} if polarization is None else {"polarization": polarization}), spin_map=spin_map, kerr_view=kerr_view,
-                             spin_map_supersample=spin_map_supersample)
+                             spin_map_supersample=spin_map_supersample, **({"spin_shutter_map": True} if spin_shutter_map else {}))
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
@@ -1384,7 +1438,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         # the one march of the video.  A camera that stands still: its view; an orbit: frame 0's (the orbit's radius is |pov|, not
         # the pov's xy norm: not the pov itself), which every frame's camera is a turn of about z
         _MAP_MODES[mode]["build"](renderer, orbit_position(static_cam_pos, 0, n_frames, orbit_degrees) if orbit else static_cam_pos, fov,
-                                  spin_map_supersample if mode == "spin_map" else map_supersample)
+                                  spin_map_supersample if mode in ("spin_map", "spin_shutter_map") else map_supersample)
     stokes_grids = {}
     if polarization is not None:
         renderer.set_polarization(**polarization)

@@ -719,6 +719,38 @@ class HipRenderer:
             return
         _lib.check(self._lib.bhr_kerr_raymap_render(self._ctx, t, flags))
 
+    def render_shutter_from_kerr_ray_map_async(self, t_offsets, cam_positions=None, fov: Optional[float] = None, skip_bloom: bool = False,
+                                               lens_flare=None) -> None:
+        """Motion blur from the Kerr ray map: one frame as the mean of ``len(t_offsets)`` frames from the map, without a march
+        (bhr_kerr_raymap_render_shutter; include/bhr.h states the frame) -- render_shutter_from_ray_map_async for the spinning
+        hole.  Sample j is the map's frame with the disk rolled by ``t_offsets[j]``, seen from ``cam_positions[j]`` -- each the
+        build's position or a turn of it about the z axis, the spin axis, as render_from_kerr_ray_map_async(cam_pos=) takes them
+        -- or, with ``cam_positions=None``, from the build view itself (a camera that stands still; the build camera out of
+        bhr_kerr_raymap_info).  ``fov`` defaults to the build's.  The BG and DISK layers are the f32 means of the samples' in
+        render_shutter_async's order; the post-pass runs once on them, with the kernels bloom_only() would take in this context.
+        1..64 samples."""
+        t_offsets = list(t_offsets)
+        if cam_positions is not None:
+            cam_positions = list(cam_positions)
+            if len(cam_positions) != len(t_offsets):
+                raise ValueError(f"{len(cam_positions)} camera positions for {len(t_offsets)} t_offsets")
+            if fov is None:
+                fov = getattr(self, "_kerr_map_fov", None)
+            if fov is None:
+                raise AssertionError("no Kerr ray map has been built (build_kerr_ray_map)")
+        cams = (_lib.Camera * max(len(t_offsets), 1))()
+        if cam_positions is None:
+            info = _lib.KerrRayMapDesc()   # without a map its camera is zeros, and the call below says that there is none
+            _lib.check(self._lib.bhr_kerr_raymap_info(self._ctx, C.byref(info)))
+            for j, t in enumerate(t_offsets):
+                cams[j] = info.cam
+                cams[j].t_offset = float(t)
+        else:
+            for j, (pos, t) in enumerate(zip(cam_positions, t_offsets)):
+                cams[j] = self.camera_uniforms(pos, fov, t_offset=t)
+        flags = self._map_frame_flags(skip_bloom, lens_flare)
+        _lib.check(self._lib.bhr_kerr_raymap_render_shutter(self._ctx, cams, len(t_offsets), flags))
+
     def kerr_ray_map_info(self) -> dict:
         """The renderer's Kerr ray map (bhr_kerr_raymap_info): built, slots, width, rows (the output frame's), supersample (the
         map's own factor, bhr_kerr_raymap_get_supersample; 1 without a map), ray_steps of the build, crossings_stored,

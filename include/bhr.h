@@ -681,8 +681,39 @@ BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, 
  * camera is compared with the build camera as passed, at the output pitch): its frame is the Kerr march of the build view's
  * fine rays turned about z, resolved the same way.  Flags, frame slot, timing-ring entry, post-pass, grade, sinks and reads are
  * those of a frame from a k = 1 map; no calibration.
- * Not available: shutter frames from this map, point stars or a Kerr polarisation on a supersampled map, several devices.
- *   BHR_ERR_STATE:   build without the Kerr march (no spin, not forced, no exact redshift): bhr_raymap_build is the call for a
+ * bhr_kerr_raymap_render_shutter(ctx, cams, n, flags): motion blur from the Kerr map -- one frame as the mean of n frames from
+ * the map, with no march at all; bhr_raymap_render_shutter's contract with the Kerr names.  cams[0 .. n - 1] (1 <= n <= 64) are
+ * the samples' cameras, each with its own t_offset.  What differs between the samples of one exposure is what the Kerr map leaves
+ * free: the disk's roll (t_offset enters the disk sampler alone) and the orbit camera's turn about z, the spin axis, an exact
+ * symmetry (the turn bhr_kerr_raymap_render_view applies).  A sample is accepted
+ *   - if its pose equals the build camera's field for field (everything but t_offset): the still camera, whose turn is (1, 0);
+ *   - else if it passes bhr_raymap_turn_of_build's checks against the Kerr map's camera, exactly as bhr_kerr_raymap_render_view's
+ *     camera does (binary64; cosine and sine computed as there).
+ * For each layer L in {BG, DISK}:
+ *   L_j  is, bit for bit, what bhr_kerr_raymap_render_view(ctx, &cams[j], BHR_SKIP_BLOOM) stores for a turned camera and what
+ *        bhr_kerr_raymap_render(ctx, cams[j].t_offset, BHR_SKIP_BLOOM) stores for a camera with the build pose;
+ *   acc  = L_0, then acc = acc + L_j for j = 1 .. n - 1 in that order, one f32 addition per channel;
+ *   L    = acc * (1.0f / (float)n): the reciprocal rounded to f32 once, the product once, no FMA contraction anywhere
+ * -- bhr_render_shutter's mean, word for word (tests/shutter_ref.py restates it).  For n = 1 this is L_0 itself.  The post-pass is
+ * the one behind every shutter frame (the pack launch for a split-f16 frame, then the frame's post-pass): BLUR, FINAL and the
+ * u8 / u16 rows are what bhr_bloom computes from the resolved layers in this context (BHR_SKIP_BLOOM suppresses them),
+ * BHR_LENS_FLARE adds what bhr_lens_flare adds; dither, grade, HDR plane, the sinks and the y4m stream work on the frame as on any
+ * other.
+ * Two routes give these bits.  A k = 1 map without overflow pixels takes ONE launch when n > 1 (csrc/march_kerr_raymap.hip:
+ * kerr_raymap_shade_shutter_kernel) that shades a pixel's records under all n (t_offset, cos, sin, camera position) and keeps the
+ * running sums on the chip.  A supersampled map (each sample is resolved first, then the mean), a map with overflow pixels -- or
+ * any map while option "kerr_raymap_shutter_fused" is 0 -- runs, per sample, the shade launch and the fix launch over the overflow
+ * list as bhr_kerr_raymap_render[_view] issues them, then bhr_render_shutter's accumulation launch (csrc/shutter.hip).
+ * The frame takes the next frame slot and runs under the context's Kerr variant; one timing-ring entry, its march bracket from the
+ * first shade launch to behind the last launch that writes BG / DISK; it neither counts towards nor runs the stream calibration.
+ * bhr_counters: rays = n k^2 W H, ray_steps the sum of the overflow re-marches' steps (0 for a map without overflow pixels).
+ * Asynchronous.  Refusals, with nothing launched and the context as it was: everything bhr_kerr_raymap_render refuses; ctx or cams
+ * NULL, n < 1 or n > 64, a non-finite t_offset in any sample, a sample that is neither the build pose nor an admissible turn (the
+ * message names the sample index): BHR_ERR_INVALID; a Kerr polarisation being set (bhr_set_kerr_polarization: a mean of frames
+ * has no Stokes planes): BHR_ERR_STATE.  bhr_render_shutter keeps refusing a spin and bhr_raymap_render_shutter a Kerr context:
+ * this is the call for the combination.
+ * Not available: point stars or a Kerr polarisation on a supersampled map, several devices.
+ *   BHR_ERR_STATE:  build without the Kerr march (no spin, not forced, no exact redshift): bhr_raymap_build is the call for a
  *                    hole that does not spin; render or read before a build (or after bhr_kerr_raymap_free); render while the
  *                    context's spin or redshift mode is no longer the build's (the message names both).
  *   BHR_ERR_INVALID: a row-block context; everything the Kerr march refuses (a tilted disk, anti_alias = 1, a Disk V2 source,
@@ -707,6 +738,7 @@ typedef struct {
 BHR_API int32_t bhr_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
 BHR_API int32_t bhr_kerr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags);
 BHR_API int32_t bhr_kerr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags);
+BHR_API int32_t bhr_kerr_raymap_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags);
 BHR_API int32_t bhr_kerr_raymap_read(bhr_ctx *ctx, int32_t plane, void *out, int64_t bytes);
 BHR_API int32_t bhr_kerr_raymap_info(bhr_ctx *ctx, bhr_kerr_raymap_desc *out);
 BHR_API int32_t bhr_kerr_raymap_get_supersample(bhr_ctx *ctx, int32_t *k);
@@ -880,6 +912,8 @@ BHR_API int32_t bhr_delayed_resources(int32_t supersampled, int32_t out[3]);
  *                                         records per pixel, resolved in the shade; read by bhr_kerr_raymap_build; anything else: BHR_ERR_INVALID
  *   "raymap_shutter_fused" BHR_RAYMAP_SHUTTER_FUSED 1 (default) bhr_raymap_render_shutter shades all samples of a map without overflow
  *                                         pixels in one launch, 0 sample by sample with the accumulation launches (the same bits; A/B runs)
+ *   "kerr_raymap_shutter_fused" BHR_KERR_RAYMAP_SHUTTER_FUSED 1 (default) bhr_kerr_raymap_render_shutter shades all samples of a k = 1 Kerr
+ *                                         map without overflow pixels in one launch, 0 sample by sample likewise (the same bits; A/B runs)
  * (bhr_create only: BHR_FRAME_SLOTS.) */
 BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
 /* Diagnostics (tests): the split-f16 post-pass's packed intermediates of the last frame as raw bytes -- which = 0 the H pass's
