@@ -51,8 +51,9 @@ int32_t check_struct(const bhr_ctx *ctx, const char *who, const bhr_polarization
     return BHR_OK;
 }
 
-// The pass of either kind into the active slot's planes under `pol`; kerr: the Kerr map's kernel over its momentum planes.
-int32_t stokes_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm, const bhr_polarization &pol, bool kerr) {
+// The pass of either kind into the active slot's planes under `pol`; under call's Kerr variant the launcher takes the Kerr map's
+// kernel over its momentum planes.
+int32_t stokes_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm, const bhr_polarization &pol) {
     bhr_frame_slot &f = bhr_slot(ctx);
     // the slot is the sole owner of its planes; the grid is sized for the smallest cell, so a change of cell size keeps it
     if (!f.d_stokes) BHR_TRY(bhr_dev_alloc(&f.d_stokes, 3 * plane_floats(ctx)));
@@ -71,8 +72,7 @@ int32_t stokes_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap 
     s.gw = cells_along(s.width, s.cell);
     s.gh = cells_along(s.rows, s.cell);
     f.stokes_cell = 0;                 // until both launches are in the stream
-    if (kerr) BHR_TRY(bhr_launch_kerr_stokes(ctx, call, rm.a, rm.has_mom ? rm.mom : nullptr, s));
-    else BHR_TRY(bhr_launch_stokes(ctx, call, rm.a, rm.diff != 0, s));
+    BHR_TRY(bhr_launch_stokes(ctx, call, rm.a, rm.diff != 0, rm.has_mom ? rm.mom : nullptr, s));
     f.stokes_cell = pol.cell;
     // the Stokes kernel calls shade_hit, so it samples the disk texture and its mips behind the frame's march bracket: it is the
     // frame's last reader of the scene, and a scene write (bhr_enter_scene_write) has to wait for it, not for the march's end
@@ -89,8 +89,8 @@ void bhr_polar_invalidate(bhr_ctx *ctx) {
     for (auto &f : ctx->slots) f.stokes_cell = 0;
 }
 
-int32_t bhr_polar_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm) { return stokes_frame(ctx, call, rm, ctx->polar, false); }
-int32_t bhr_kerr_polar_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm) { return stokes_frame(ctx, call, rm, ctx->kerr_polar, true); }
+int32_t bhr_polar_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm) { return stokes_frame(ctx, call, rm, ctx->polar); }
+int32_t bhr_kerr_polar_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm) { return stokes_frame(ctx, call, rm, ctx->kerr_polar); }
 
 extern "C" {
 

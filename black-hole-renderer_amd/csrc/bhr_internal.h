@@ -215,12 +215,14 @@ enum bhr_march_kernel {
     BHR_MK_RAYMAP_SHADE_STARS,      // raymap_shade_kernel<diff, false, true>                                     raymap
     BHR_MK_RAYMAP_SHADE_STARS_ROT,  // raymap_shade_kernel<diff, true, true>                                      raymap
     // (ss: BUILD, SHADE and SHADE_ROT have twins for a supersampled map, raymap_build_kernel<DIFF, true> / raymap_shade_ss_kernel; the shutter kernels have none)
-    // the Kerr ray map (march_kerr_raymap.hip), each with the model and with the exact redshift; no differentials, no supersampled twins
-    BHR_MK_KERR_RAYMAP_BUILD,      // kerr_raymap_build_kernel<RS>: marches a view with the Kerr Ray and records what it finds    kerr_raymap
+    // the Kerr ray map (march_kerr_raymap.hip), each with the model and with the exact redshift; no differentials
+    // (ss: BUILD, SHADE, SHADE_ROT and FIX have twins for a supersampled map -- kerr_raymap_build_kernel<RS, KERR_BUILD_SS>,
+    // kerr_raymap_shade_ss_kernel<RS, ROT>, kerr_raymap_fix_kernel<RS, true>; the momentum build and the shutter kernels have none)
+    BHR_MK_KERR_RAYMAP_BUILD,      // kerr_raymap_build_kernel<RS, KERR_BUILD_PLAIN>: marches a view with the Kerr Ray and records what it finds  kerr_raymap
     BHR_MK_KERR_RAYMAP_SHADE,      // kerr_raymap_shade_kernel<RS, false>: a frame from the records and the current scene          kerr_raymap
     BHR_MK_KERR_RAYMAP_SHADE_ROT,  // kerr_raymap_shade_kernel<RS, true>: the same with the records turned about z                 kerr_raymap
-    BHR_MK_KERR_RAYMAP_FIX,        // kerr_raymap_fix_kernel<RS>: the map's overflow list, marched with the Kerr Ray               kerr_raymap
-    BHR_MK_KERR_RAYMAP_BUILD_MOM,  // kerr_raymap_build_mom_kernel<RS>: the build that also keeps each crossing's photon momentum  kerr_raymap
+    BHR_MK_KERR_RAYMAP_FIX,        // kerr_raymap_fix_kernel<RS, false>: the map's overflow list, marched with the Kerr Ray        kerr_raymap
+    BHR_MK_KERR_RAYMAP_BUILD_MOM,  // kerr_raymap_build_kernel<RS, KERR_BUILD_MOM>: the build that also keeps each crossing's photon momentum  kerr_raymap
     BHR_MK_KERR_RAYMAP_SHUTTER,      // kerr_raymap_shade_shutter_kernel<RS, false>: the mean of n frames from the Kerr map, one launch  kerr_raymap
     BHR_MK_KERR_RAYMAP_SHUTTER_ROT,  // kerr_raymap_shade_shutter_kernel<RS, true>: each sample turned about z by its own angle          kerr_raymap
 };
@@ -756,7 +758,7 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call);
 // ss: the map's factor -- the build marches the fine frame bhr_fine(ctx, ss) of `cam`
 // v, call.req.variant: none takes march_raymap.hip's kernels under the march's block, BHR_MV_KERR / BHR_MV_KERR_EXACT
 // march_kerr_raymap.hip's under the Kerr block (one ray per pixel, 5 components, no stars)
-// mom: a Kerr build's momentum planes (kerr_raymap_build_mom_kernel fills them beside the records); null: the plain build
+// mom: a Kerr build's momentum planes (kerr_raymap_build_kernel<RS, KERR_BUILD_MOM> fills them beside the records); null: the plain build
 int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss, bhr_march_variant v = BHR_MV_NONE,
                                 float *mom = nullptr);
 // rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
@@ -769,10 +771,9 @@ int32_t bhr_launch_stars_gather(bhr_ctx *ctx, const bhr_camera *cam, const BhrRa
 const void *bhr_stars_kernel(int32_t rot);                                             // stars.hip -> stars.o
 // all samples of a shutter frame from the map in one launch (raymap_shade_shutter_kernel): the mean of the n frames the launch
 // above would store for (smp[j].t, smp[j].c, smp[j].s), into the active slot's BG / DISK; no packed bloom operands.  Opens the
-// frame's march bracket; the caller closes it.  turned: some sample has a turn other than (1, 0).
+// frame's march bracket; the caller closes it.  turned: some sample has a turn other than (1, 0).  Under call's Kerr variant the
+// map is the Kerr map and the kernel kerr_raymap_shade_shutter_kernel<RS, turned> under the Kerr block (diff: false).
 int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrShutterArgs &smp, bool turned);
-// ... from the Kerr map (kerr_raymap_shade_shutter_kernel<RS, turned>), under call's Kerr variant and its Kerr block
-int32_t bhr_launch_kerr_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, const BhrShutterArgs &smp, bool turned);
 const void *bhr_march_kernel_fast(bhr_march_kernel k, int32_t diff, int32_t ss);       // march.hip -> march.o (ss: the supersampled twin)
 const void *bhr_march_kernel_strict(bhr_march_kernel k, int32_t diff, int32_t ss);     // march_strict.hip -> march_strict.o
 const void *bhr_march_kernel_strict_ilp(bhr_march_kernel k, int32_t diff, int32_t ss); // march_strict_ilp.hip -> march_strict_ilp.o
@@ -909,15 +910,15 @@ inline bool bhr_have_polar(const bhr_ctx *ctx) { return ctx->polar_on != 0; }
 // slot's own storage (allocated here on first use); records the slot's stokes_done behind it and makes it the slot's march_done
 int32_t bhr_polar_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm);
 void bhr_polar_invalidate(bhr_ctx *ctx);                                   // the map or the setting changed: no frame's planes to read
-// march_launch.hip: the two launches of that pass under the march's block of call's view
-int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrStokesArgs &s);
+// march_launch.hip: the two launches of that pass under the march's block of call's view -- or, under call's Kerr variant, the
+// Kerr Stokes kernel under the Kerr block over the Kerr map's momentum planes `mom` (diff: false), and the same cell means
+int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float *mom, const BhrStokesArgs &s);
 const void *bhr_stokes_kernel(int32_t diff);                               // march_polar.hip -> march_polar.o
 const void *bhr_stokes_cells_kernel(void);
 // the Kerr polarisation (bhr_set_kerr_polarization): the same pass for a frame from the Kerr ray map `rm`, which has to hold the
 // momentum planes; the kernel is march_kerr_polar.hip's under the Kerr block of call's variant, the cell means the kernel above
 inline bool bhr_have_kerr_polar(const bhr_ctx *ctx) { return ctx->kerr_polar_on != 0; }
 int32_t bhr_kerr_polar_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm);
-int32_t bhr_launch_kerr_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, float *mom, const BhrStokesArgs &s);
 const void *bhr_kerr_stokes_kernel(int32_t exact);                         // march_kerr_polar.hip -> march_kerr_polar.o
 
 // ---- lifecycle.hip, texture.hip, disk_v2.hip ------------------------------------------------------------------------------------------

@@ -69,7 +69,7 @@ float fast_sqrt(float s) {
 //
 //   arithmetic     request                                              kernel (object)
 //   any            a march variant v (call.req.variant), whole block    its row's kernel: kernels(name, 0, ss) of bhr_variant_row_of(v)
-//   any            a Kerr variant, fix list (part->repair == 2)         kerr_raymap_fix_kernel<RS> / kerr_raymap_fix_ss_kernel<RS> (kerr_raymap)
+//   any            a Kerr variant, fix list (part->repair == 2)         kerr_raymap_fix_kernel<RS, ss> (kerr_raymap)
 //   any            hybrid part with n <= 0, not the fix list            none
 //   strict         hybrid fix list (part->repair == 2)                  march_fix_kernel<diff> (strict_ilp)
 //   fast / strict  Disk V2 volume source                                march_tile_kernel<false, 2> (own object)
@@ -105,8 +105,8 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
     // a variant: one arithmetic, one schedule, no lists (what it has no form for was refused before anything was launched)
     if (v != BHR_MV_NONE) {
         const bhr_variant_row &r = bhr_variant_row_of(v);
-        // the overflow list of a frame from the Kerr ray map (part->repair == 2 under a Kerr variant): kerr_raymap_fix_kernel, or
-        // kerr_raymap_fix_ss_kernel over the whole groups of a supersampled map's list (the grid is sized for the fine capacity)
+        // the overflow list of a frame from the Kerr ray map (part->repair == 2 under a Kerr variant): kerr_raymap_fix_kernel, its
+        // SS form over the whole groups of a supersampled map's list (the grid is sized for the fine capacity)
         if (part && part->repair == 2 && r.kerr) {
             k.fn = bhr_march_kernel_kerr_raymap(BHR_MK_KERR_RAYMAP_FIX, v == BHR_MV_KERR_EXACT, ss);
             k.grid = dim3((a.fix_cap / 64 + 3) / 4);
@@ -651,22 +651,32 @@ int32_t bhr_launch_stars_gather(bhr_ctx *ctx, const bhr_camera *cam, const BhrRa
     return BHR_OK;
 }
 
-// The Stokes pass of a map frame (march_polar.hip; api_polar.hip owns the planes): the Stokes kernel on the shade kernel's grid
-// under the march's block of call's frame -- the block the shade launch of the same frame was given, so shade_hit sees the values
-// it saw there -- then the cell means, one block per cell.  Stores no layer: the slot's BG / DISK and what is noted of them stay.
-int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrStokesArgs &s) {
-    if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "polarisation: the Stokes kernel has no supersampled twin (factor %d)", call.ss);
+// The Stokes pass of a map frame (march_polar.hip, march_kerr_polar.hip; api_polar.hip owns the planes): the Stokes kernel on the
+// shade kernel's grid under the block the shade launch of the same frame was given -- the march's block of call's frame, so
+// shade_hit sees the values it saw there, or the Kerr block of call's Kerr variant -- then the cell means, one block per cell.
+// The Kerr kernel is its redshift's and reads the map's momentum planes `mom` behind the map.  Stores no layer: the slot's
+// BG / DISK and what is noted of them stay.
+int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float *mom, const BhrStokesArgs &s) {
+    const bhr_march_variant v = call.req.variant;
+    const bool kerr = v != BHR_MV_NONE;
+    const char *who = kerr ? "Kerr polarisation" : "polarisation";
+    if (kerr && v != BHR_MV_KERR && v != BHR_MV_KERR_EXACT) return bhr_fail(BHR_ERR_STATE, "%s: the frame is not a Kerr variant's", who);
+    if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "%s: the Stokes kernel has no supersampled twin (factor %d)", who, call.ss);
     BhrMarchArgs a;
     march_args(ctx, call, nullptr, 1, false, a);
-    if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5) || s.width != a.width || s.rows != a.rows)
-        return bhr_fail(BHR_ERR_STATE, "polarisation: the map does not fit the frame");
+    // the Kerr map: no differentials, and the momentum planes; the Schwarzschild map: none
+    if ((int64_t)a.width * a.rows != m.plane || m.comps != (diff ? 9 : 5) || s.width != a.width || s.rows != a.rows || (kerr ? diff || !mom : mom != nullptr))
+        return bhr_fail(BHR_ERR_STATE, "%s: the map does not fit the frame", who);
     if (s.cell < 1 || s.gw != (a.width + s.cell - 1) / s.cell || s.gh != (a.rows + s.cell - 1) / s.cell || !s.out || !s.cells)
-        return bhr_fail(BHR_ERR_STATE, "polarisation: a cell grid of %d x %d cells of %d pixels for a %d x %d frame", s.gw, s.gh, s.cell, a.width, a.rows);
-    const void *fn = bhr_stokes_kernel(diff ? 1 : 0), *fc = bhr_stokes_cells_kernel();
-    if (!fn || !fc) return bhr_fail(BHR_ERR_STATE, "polarisation: no Stokes kernel in this library");
-    BhrRayMapArgs mm = m;
+        return bhr_fail(BHR_ERR_STATE, "%s: a cell grid of %d x %d cells of %d pixels for a %d x %d frame", who, s.gw, s.gh, s.cell, a.width, a.rows);
+    const void *fn = kerr ? bhr_kerr_stokes_kernel(v == BHR_MV_KERR_EXACT ? 1 : 0) : bhr_stokes_kernel(diff ? 1 : 0), *fc = bhr_stokes_cells_kernel();
+    if (!fn || !fc) return bhr_fail(BHR_ERR_STATE, "%s: no Stokes kernel in this library", who);
+    VariantArgs va;
+    BhrRayMapMomArgs mm;               // the Schwarzschild kernel reads its first sizeof(BhrRayMapArgs) bytes
+    static_cast<BhrRayMapArgs &>(mm) = m;
+    mm.mom = mom;
     BhrStokesArgs ss = s;
-    void *args[] = {&a, &mm, &ss};
+    void *args[] = {variant_args(ctx, call.req, a, va), &mm, &ss};
     (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
     BHR_HIP(hipGetLastError());
     void *cargs[] = {&ss};
@@ -677,69 +687,21 @@ int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRay
     return BHR_OK;
 }
 
-// The Stokes pass of a frame from the Kerr ray map (march_kerr_polar.hip; api_polar.hip owns the planes): the Kerr Stokes kernel of
-// the frame's redshift on the Kerr shade kernel's grid under the Kerr block the shade launch of the same frame was given, then the
-// cell means as above.
-int32_t bhr_launch_kerr_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, float *mom, const BhrStokesArgs &s) {
-    const bhr_march_variant v = call.req.variant;
-    if (v != BHR_MV_KERR && v != BHR_MV_KERR_EXACT) return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: the frame is not a Kerr variant's");
-    if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: the Stokes kernel has no supersampled twin (factor %d)", call.ss);
-    BhrMarchArgs a;
-    march_args(ctx, call, nullptr, 1, false, a);
-    if ((int64_t)a.width * a.rows != m.plane || m.comps != 5 || s.width != a.width || s.rows != a.rows || !mom)
-        return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: the map does not fit the frame");
-    if (s.cell < 1 || s.gw != (a.width + s.cell - 1) / s.cell || s.gh != (a.rows + s.cell - 1) / s.cell || !s.out || !s.cells)
-        return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: a cell grid of %d x %d cells of %d pixels for a %d x %d frame", s.gw, s.gh, s.cell, a.width, a.rows);
-    const void *fn = bhr_kerr_stokes_kernel(v == BHR_MV_KERR_EXACT ? 1 : 0), *fc = bhr_stokes_cells_kernel();
-    if (!fn || !fc) return bhr_fail(BHR_ERR_STATE, "Kerr polarisation: no Stokes kernel in this library");
-    VariantArgs va;
-    BhrRayMapMomArgs mm;
-    static_cast<BhrRayMapArgs &>(mm) = m;
-    mm.mom = mom;
-    BhrStokesArgs ss = s;
-    void *args[] = {variant_args(ctx, call.req, a, va), &mm, &ss};
-    (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
-    BHR_HIP(hipGetLastError());
-    void *cargs[] = {&ss};
-    const unsigned cell_threads = s.cell * s.cell >= 256 ? 256u : 64u;
-    (void)hipLaunchKernel(fc, dim3(s.gw * s.gh), dim3(cell_threads), cargs, 0, call.stream);
-    BHR_HIP(hipGetLastError());
-    return BHR_OK;
-}
-
-// All samples of a shutter frame from the map in one launch (bhr_raymap_render_shutter's fused route): the shade kernel's grid,
-// the march's argument block of call.cam -- the two fields of it that a shade kernel reads of a camera, t_offset and the
-// position, are taken from the samples' table inside the kernel instead -- the map, and that table by value.  The caller closes
-// the march bracket.
+// All samples of a shutter frame from the map in one launch (the fused route of bhr_raymap_render_shutter and
+// bhr_kerr_raymap_render_shutter): the shade kernel's grid, the block of call.cam's frame -- the fields of it that a shade kernel
+// reads of a camera, t_offset and the position, are taken from the samples' table inside the kernel instead -- the map, and that
+// table by value.  Under a Kerr variant the kernel is the Kerr map's and the block the variant's Kerr block (variant_args: the
+// spin, and the ISCO for the exact redshift).  The caller closes the march bracket.
 int32_t bhr_launch_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, const BhrShutterArgs &smp, bool turned) {
-    BhrMarchArgs a;
-    BHR_TRY(raymap_shade_args(ctx, call, m, diff, 1, "bhr_raymap_render_shutter", a));
-    if (smp.n < 1 || smp.n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_render_shutter: %d samples (1 .. %d)", smp.n, BHR_SHUTTER_MAX_SAMPLES);
-    if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: the fused launch has no supersampled kernel (factor %d)", call.ss);
-    if (a.diskp) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: the fused launch takes a skip-bloom call (it stores no packed bloom operands)");
-    const void *fn = bhr_march_kernel_raymap(turned ? BHR_MK_RAYMAP_SHUTTER_ROT : BHR_MK_RAYMAP_SHUTTER, diff, 0);
-    if (!fn) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_render_shutter: no shutter shade kernel in this library");
-    BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
-    BhrRayMapArgs mm = m;
-    BhrShutterArgs ss = smp;
-    void *args[] = {&a, &mm, &ss};
-    (void)hipLaunchKernel(fn, dim3((a.n_tiles + 3) / 4), dim3(256), args, 0, call.stream);
-    BHR_HIP(hipGetLastError());
-    return BHR_OK;
-}
-
-// ... from the Kerr map (bhr_kerr_raymap_render_shutter's fused route): the Kerr shade kernel's grid, the Kerr block of call's
-// variant in the march block's place (variant_args: the spin, and the ISCO for the exact redshift), the map, the table.
-int32_t bhr_launch_kerr_raymap_shade_shutter(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, const BhrShutterArgs &smp, bool turned) {
-    const char *api = "bhr_kerr_raymap_render_shutter";
     const bhr_march_variant v = call.req.variant;
-    if (v != BHR_MV_KERR && v != BHR_MV_KERR_EXACT) return bhr_fail(BHR_ERR_STATE, "%s: the frame is not a Kerr variant's", api);
+    const char *api = v == BHR_MV_NONE ? "bhr_raymap_render_shutter" : "bhr_kerr_raymap_render_shutter";
+    if (v != BHR_MV_NONE && v != BHR_MV_KERR && v != BHR_MV_KERR_EXACT) return bhr_fail(BHR_ERR_STATE, "%s: the frame is not a Kerr variant's", api);
     BhrMarchArgs a;
-    BHR_TRY(raymap_shade_args(ctx, call, m, false, 1, api, a));
+    BHR_TRY(raymap_shade_args(ctx, call, m, diff, 1, api, a));
     if (smp.n < 1 || smp.n > BHR_SHUTTER_MAX_SAMPLES) return bhr_fail(BHR_ERR_INVALID, "%s: %d samples (1 .. %d)", api, smp.n, BHR_SHUTTER_MAX_SAMPLES);
     if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "%s: the fused launch has no supersampled kernel (factor %d)", api, call.ss);
     if (a.diskp) return bhr_fail(BHR_ERR_STATE, "%s: the fused launch takes a skip-bloom call (it stores no packed bloom operands)", api);
-    const void *fn = bhr_march_kernel_kerr_raymap(turned ? BHR_MK_KERR_RAYMAP_SHUTTER_ROT : BHR_MK_KERR_RAYMAP_SHUTTER, v == BHR_MV_KERR_EXACT, 0);
+    const void *fn = raymap_kernel(v, turned ? BHR_MK_RAYMAP_SHUTTER_ROT : BHR_MK_RAYMAP_SHUTTER, turned ? BHR_MK_KERR_RAYMAP_SHUTTER_ROT : BHR_MK_KERR_RAYMAP_SHUTTER, diff, 1);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "%s: no shutter shade kernel in this library", api);
     BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, call.slot), call.stream));
     VariantArgs va;

@@ -96,28 +96,7 @@ __global__ __launch_bounds__(256) void raymap_build_kernel(BhrMarchArgs a, BhrRa
         m.crossings[pix] = n_rec;
     }
     if (SS) {
-        // A k x k group with ANY ray over the slots goes on the overflow list whole, in the format march_tile_body writes for
-        // march_fix_ss_kernel (march_tile.h): k^2 consecutive entries in sub-sample order (sy k + sx), k^2-aligned, groups in the
-        // order of their (0, 0) lanes -- the fix kernel resolves a group from 64 / k^2 of them per wave.  k W and k rows are
-        // multiples of k (and 8 is one of k), so a group lies in one tile, inside the frame or outside it, whole.
-        // the group's flag: the guard kernel's butterfly (every lane of the wave is here: no early return before it)
-        int u = valid && n_rec > m.slots ? 1 : 0;
-        for (int x = 1; x < a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
-        for (int x = 8; x < 8 * a.ss; x <<= 1) u |= __shfl_xor(u, x, BHR_WAVE);
-        const bool over = valid && u != 0;
-        const unsigned long long om = __ballot(over);
-        if (om) {
-            const int first = __ffsll((long long)om) - 1;
-            const int km = a.ss - 1, sx = lane & km, sy = (lane >> 3) & km;
-            const unsigned long long lead = __ballot(over && sx == 0 && sy == 0);
-            unsigned int base = 0;
-            if (lane == first) base = atomicAdd(m.over_count, (unsigned int)__popcll(lead) << (2 * a.ss_log2));
-            base = __shfl(base, first, BHR_WAVE);
-            const int l0 = lane - sx - 8 * sy;
-            const unsigned int at = base + ((unsigned int)__popcll(lead & ((1ull << l0) - 1ull)) << (2 * a.ss_log2)) + (unsigned int)((sy << a.ss_log2) + sx);
-            // (every group is appended at most once and the list has room for the whole fine plane)
-            if (over) m.over_list[at] = (int32_t)pix;
-        }
+        raymap_append_overflow_groups(a, m, valid, n_rec > m.slots, lane, pix);   // whole k x k groups (raymap_device.h)
     } else {
         raymap_append_overflow(m, valid && n_rec > m.slots, lane, pix);
     }
@@ -281,15 +260,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void r
     a.disk[o + 1] = acc_d[1];
     a.disk[o + 2] = acc_d[2];
 }
-
-// What resolve_store (march_device.h) asks of a ray: the six values it leaves.  Here they come out of the lane's records.
-struct RayMapValues {
-    float v[6];
-    __device__ __forceinline__ void values(const BhrMarchArgs &, float bk[3], float dk[3]) const {
-        bk[0] = v[0]; bk[1] = v[1]; bk[2] = v[2];
-        dk[0] = v[3]; dk[1] = v[4]; dk[2] = v[5];
-    }
-};
 
 // A frame from a supersampled map: one 8x8 tile of the FINE frame per wave, every lane shades its own fine record list exactly
 // as raymap_shade_kernel does (same device functions, same order, same turn), and the k x k groups are resolved in the wave by

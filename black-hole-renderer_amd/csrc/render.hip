@@ -168,7 +168,7 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_raymap &rm, const bhr_camera *cam
 // launch over the overflow list as raymap_on_slot issues them, as a skip-bloom call, then the accumulation launch; a later
 // sample keeps the frame's march-start event and the march-end event is recorded once behind the last accumulation.
 // The map `rm` is of either kind.  A Kerr map's frame (bhr_kerr_raymap_render_shutter) runs under the context's Kerr variant:
-// the unfused route's launches take the Kerr map's kernels, the fused launch is the Kerr map's own, and its option is
+// both routes' launches take the Kerr map's kernels by the call's variant, and its option is
 // "kerr_raymap_shutter_fused".
 int32_t raymap_shutter_on_slot(bhr_ctx *ctx, const bhr_raymap &rm, const bhr_camera *cams, const BhrShutterArgs &smp, bool turned, uint32_t flags, int k, int ring,
                                frame_marches *fm) {
@@ -187,8 +187,7 @@ int32_t raymap_shutter_on_slot(bhr_ctx *ctx, const bhr_raymap &rm, const bhr_cam
         // no march launch follows the fused one: nothing counts into the frame's counter cell, which was cleared ahead of time
         const bhr_march_call call = {&cams[0], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ 1,
                                      /* keep_start */ false, req};
-        if (kerr) BHR_TRY(bhr_launch_kerr_raymap_shade_shutter(ctx, call, rm.a, smp, turned));
-        else BHR_TRY(bhr_launch_raymap_shade_shutter(ctx, call, rm.a, rm.diff != 0, smp, turned));
+        BHR_TRY(bhr_launch_raymap_shade_shutter(ctx, call, rm.a, rm.diff != 0, smp, turned));
     } else {
         for (int j = 0; j < n; ++j) {
             const bhr_march_call call = {&cams[j], flags | BHR_SKIP_BLOOM, f.stream, /* slot */ ring, /* time_untimed */ false, /* defer_end */ true, /* ss */ rm.ss,

@@ -406,3 +406,91 @@ def test_both_maps_through_one_context(hip_lib):
     r.free_ray_map()
     assert r.ray_map_info()["built"] == 0 and r.kerr_ray_map_info()["built"] == 0
     r.close()
+
+
+# ---- 8. the launchers both kinds share, alternating on one context ------------------------------------------------------------------------
+def test_shared_launchers_alternate_between_the_kinds(hip_lib):
+    """The fused shutter launch and the Stokes pass of both map kinds go through one launcher each, which takes the kind from the
+    frame's variant.  One context alternates between the kinds: Schwarzschild, Kerr under either redshift, Schwarzschild again.
+    Every fused shutter frame is bit for bit the frame of its own unfused route, and the first and last Schwarzschild frames are
+    equal; with a polarisation and a Kerr polarisation set, the Stokes planes of each kind are those of a context that only ever
+    held that kind.  27 x 19 (partial tiles on both sides), three samples, eight slots: no map has overflow pixels, so the
+    shutter frames take the fused launch -- counted under option "shutter_timing", which brackets the accumulation launches the
+    fused route has none of."""
+    from bhr_amd import drivers
+    w, h, n, fov = 27, 19, 3, KC.FOV
+    u = drivers.shutter_times(5, 0.5, n)
+    pos, toff = [_cam(t) for t in u], [(t - 5) * 0.1 for t in u]
+    layers = ("final", "bg", "disk")
+
+    def both_routes(r, render, option, tag):
+        got = {}
+        for fused, launches in ((1, 0), (0, n)):
+            r.set_option(option, fused)
+            render(toff, pos, fov)
+            got[fused] = _read(r, layers)
+            assert r.shutter_timing()["launches"] == launches, (tag, fused)
+        r.set_option(option, 1)
+        _assert_equal(got[1], got[0], f"{tag}: the fused launch against the sample-by-sample route")
+        assert (got[1]["disk"] > 0).any() and (got[1]["bg"] > 0).any(), f"{tag}: a blank frame"
+        return got[1]
+
+    r = _mk(0.0, width=w, height=h)
+    r.set_option("raymap_slots", 8)
+    r.set_option("shutter_timing", 1)
+    r.build_ray_map(_cam(0), fov)
+    assert r.ray_map_info()["overflow_pixels"] == 0
+    first = both_routes(r, r.render_shutter_from_ray_map_async, "raymap_shutter_fused", "Schwarzschild")
+    r.set_spin(0.6)
+    for redshift in ("model", "exact"):
+        r.set_redshift(redshift)
+        r.build_kerr_ray_map(_cam(0), fov)
+        assert r.kerr_ray_map_info()["overflow_pixels"] == 0
+        K = both_routes(r, r.render_shutter_from_kerr_ray_map_async, "kerr_raymap_shutter_fused", f"Kerr, {redshift} redshift")
+        assert (K["disk"] != first["disk"]).any()
+    r.set_redshift("model")
+    r.set_spin(0.0)
+    _assert_equal(both_routes(r, r.render_shutter_from_ray_map_async, "raymap_shutter_fused", "Schwarzschild again"), first,
+                  "the Schwarzschild shutter frame behind the Kerr ones")
+    r.close()
+
+    # the Stokes pass: the planes and the cell means of a map frame of either kind
+    view, t, field, kerr_field = list(KC.VIEWS[0]), 0.7, "toroidal", (0.3, 0.8, 0.5)
+
+    def planes(r, kerr):
+        (r.render_from_kerr_ray_map_async if kerr else r.render_from_ray_map_async)(t_offset=t, skip_bloom=True)
+        S, cells = r.stokes(), r.stokes_cells()
+        assert S[0].any() and S[1].any() and cells.any()
+        return S, cells
+
+    def same(got, want, tag):
+        assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), f"{tag}: the Stokes planes differ"
+
+    alone = {}
+    s = _mk(0.0, width=w, height=h)
+    s.set_polarization(field, 0.7, 8)
+    s.build_ray_map(view, fov)
+    alone["schwarzschild"] = planes(s, False)
+    s.close()
+    k = _mk(0.6, width=w, height=h)
+    k.set_kerr_polarization(kerr_field, 0.7, 8)
+    for redshift in ("model", "exact"):
+        k.set_redshift(redshift)
+        k.build_kerr_ray_map(view, fov)
+        alone[redshift] = planes(k, True)
+    k.close()
+
+    r = _mk(0.0, width=w, height=h)
+    r.set_polarization(field, 0.7, 8)
+    r.build_ray_map(view, fov)
+    same(planes(r, False), alone["schwarzschild"], "Schwarzschild")
+    r.set_spin(0.6)
+    r.set_kerr_polarization(kerr_field, 0.7, 8)
+    for redshift in ("model", "exact"):
+        r.set_redshift(redshift)
+        r.build_kerr_ray_map(view, fov)
+        same(planes(r, True), alone[redshift], f"Kerr, {redshift} redshift")
+    r.set_redshift("model")
+    r.set_spin(0.0)
+    same(planes(r, False), alone["schwarzschild"], "Schwarzschild behind the Kerr frames")
+    r.close()
