@@ -39,6 +39,7 @@ SYMBOLS = (
     "bhr_raymap_build", "bhr_raymap_render", "bhr_raymap_render_view", "bhr_raymap_render_shutter", "bhr_raymap_read", "bhr_raymap_get_info", "bhr_raymap_free",
     "bhr_kerr_raymap_build", "bhr_kerr_raymap_render", "bhr_kerr_raymap_render_view", "bhr_kerr_raymap_render_shutter", "bhr_kerr_raymap_read", "bhr_kerr_raymap_info", "bhr_kerr_raymap_get_supersample", "bhr_kerr_raymap_free",
     "bhr_set_stars", "bhr_get_stars_info", "bhr_stars_resources",
+    "bhr_set_kerr_stars", "bhr_get_kerr_stars_info", "bhr_kerr_stars_resources",
     "bhr_set_polarization", "bhr_read_stokes", "bhr_read_stokes_cells", "bhr_stokes_resources",
     "bhr_set_kerr_polarization", "bhr_kerr_stokes_resources",
     "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_read_final_u16", "bhr_set_dither", "bhr_dither_matrix", "bhr_set_grade", "bhr_grade_frame", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
@@ -208,6 +209,9 @@ def load() -> C.CDLL:
     lib.bhr_set_stars.argtypes = [P, C.c_void_p, I32, C.POINTER(StarParams)]
     lib.bhr_get_stars_info.argtypes = [P, C.POINTER(StarsInfo)]
     lib.bhr_stars_resources.argtypes = [I32, C.POINTER(C.c_int32)]
+    lib.bhr_set_kerr_stars.argtypes = [P, C.c_void_p, I32, C.POINTER(StarParams)]
+    lib.bhr_get_kerr_stars_info.argtypes = [P, C.POINTER(StarsInfo)]
+    lib.bhr_kerr_stars_resources.argtypes = [I32, I32, C.POINTER(C.c_int32)]
     lib.bhr_set_polarization.argtypes = [P, C.POINTER(Polarization)]
     lib.bhr_read_stokes.argtypes = [P, I32, F]
     lib.bhr_read_stokes_cells.argtypes = [P, F, C.POINTER(C.c_int32)]

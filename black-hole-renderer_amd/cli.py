@@ -8,7 +8,8 @@ round-robin by RANK / WORLD_SIZE), ``--disk_model`` (the analytic Disk V2 source
 catalogue of lensed points rendered through a ray map), ``--light_delay`` (every disk crossing shaded at the
 time its light left the gas), ``--projection`` / ``--projection_fov`` (equirectangular 360-degree
 frames and fisheye dome masters instead of the pinhole camera), ``--polarization`` (Stokes Q / U maps of the disk through a ray map),
-``--spin_observer`` / ``--spin_projection`` and their companions (the moving and the panoramic camera of a spinning hole).
+``--spin_observer`` / ``--spin_projection`` and their companions (the moving and the panoramic camera of a spinning hole),
+``--spin_stars point`` (the catalogue of lensed points through a Kerr ray map) and ``--spin_passes`` (a Kerr ray map's passes of a still).
 """
 from __future__ import annotations
 
@@ -279,6 +280,19 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "(default: 2.0, an aesthetic choice)")
     p.add_argument("--star_max_magnification", type=float, default=32.0, metavar="M",
                    help="--stars point: cap of a star image's magnification on the critical curve, 1 .. 1e6 (default: 32)")
+    p.add_argument("--spin_stars", type=str, default=argparse.SUPPRESS, choices=["point"],
+                   help="--spin or --redshift exact: point -- the procedural sky's stars as a catalogue rendered through a Kerr ray map "
+                        "of the view, --stars point for a spinning hole: every image of a star stays a point and its flux is "
+                        "multiplied by the lensing magnification, the sparkle along the asymmetric critical curve; the sky texture "
+                        "keeps the nebula and the glow.  Reads --star_gain and --star_max_magnification.  A still is shaded from "
+                        "the view's Kerr ray map; --video needs --spin_map beside it, and with --orbit every frame gathers the star "
+                        "images of its turned view.  Not with --texture, --stars point, --supersample > 1, --spin_map_supersample > "
+                        "1, --spin_shutter_map, --shutter, --spin_observer, --spin_projection, --spin_polarization or --gpus > 1")
+    p.add_argument("--spin_passes", type=str, default=argparse.SUPPRESS, metavar="PATH.npz",
+                   help="still images with --spin or --redshift exact: --passes for a spinning hole -- also build the Kerr ray map of "
+                        "the view and write its geometry passes, the frame's bg / disk / blur layers and the hole's spin and "
+                        "redshift mode as a compressed .npz; the image itself is unchanged.  Not with --supersample > 1, "
+                        "--spin_observer, --spin_projection, --gpus > 1 or --video")
     p.add_argument("--ignore_taichi_cache", action="store_true", help="accepted for compatibility; no effect")
     p.add_argument("--video", action="store_true", help="render frames and assemble a video")
     p.add_argument("--interactive", action="store_true", help="not available in this build (needs ti.GUI)")
@@ -692,6 +706,27 @@ def parse_args(argv=None) -> argparse.Namespace:
             p.error(f"--stokes_output writes a .npz file, got {args.stokes_output!r}")
         if not getattr(args, "polarization_ticks", "x.png").lower().endswith(".png"):
             p.error(f"--polarization_ticks writes a .png file, got {args.polarization_ticks!r}")
+    # the Kerr point stars and the Kerr passes (drivers.check_kerr_stars / check_kerr_passes have the same refusals), behind every
+    # refusal above: a line that was refused without them is refused with the same words.  Neither has a default in the namespace
+    if hasattr(args, "spin_stars") or hasattr(args, "spin_passes"):
+        from . import drivers
+        view = kerr_view_from_args(args).get("kerr_view", {})
+        spin_projection = view.get("projection") is not None or view.get("projection_fov") is not None
+        spin_observer = bool(view) and not spin_projection
+        try:
+            if hasattr(args, "spin_stars"):
+                drivers.check_kerr_stars(
+                    kerr_stars_from_args(args), spin=args.spin, redshift=args.redshift, skybox_path=args.texture, stars=args.stars == "point",
+                    supersample=args.supersample, spin_map_supersample=getattr(args, "spin_map_supersample", 1),
+                    spin_shutter_map=hasattr(args, "spin_shutter_map"), shutter=args.shutter, spin_observer=spin_observer,
+                    spin_projection=spin_projection, gpus=args.gpus, video=args.video, spin_map=hasattr(args, "spin_map"))
+                if spin_pol is not None:
+                    raise ValueError("--spin_stars does not combine with --spin_polarization on one command line: take one of the two")
+            if hasattr(args, "spin_passes"):
+                drivers.check_kerr_passes(args.spin_passes, spin=args.spin, redshift=args.redshift, supersample=args.supersample,
+                                          spin_observer=spin_observer, spin_projection=spin_projection, gpus=args.gpus, video=args.video)
+        except ValueError as e:
+            p.error(str(e))
     # --exposure, --white, --transfer and --hdr_output without --tonemap mean --tonemap clip
     if args.tonemap is None and any(v is not None for v in (args.exposure, args.white, args.transfer, args.hdr_output)):
         args.tonemap = "clip"
@@ -712,6 +747,13 @@ def grade_from_args(args):
 def stars_from_args(args):
     """The point stars of a command line as drivers.render_image / render_video take them: None without --stars point."""
     if getattr(args, "stars", "texture") != "point":
+        return None
+    return dict(gain=args.star_gain, max_magnification=args.star_max_magnification)
+
+
+def kerr_stars_from_args(args):
+    """The Kerr point stars of a command line as drivers.render_image / render_video take them: None without --spin_stars."""
+    if not hasattr(args, "spin_stars"):
         return None
     return dict(gain=args.star_gain, max_magnification=args.star_max_magnification)
 
@@ -880,6 +922,8 @@ def main(argv=None) -> int:
     sky = args.observer_sky == "shift"
     # ... and the point stars
     stars_kw = {"stars": stars_from_args(args)} if args.stars == "point" else {}
+    # ... and a spinning hole's
+    kerr_stars_kw = {"kerr_stars": kerr_stars_from_args(args)} if hasattr(args, "spin_stars") else {}
     # ... and a projection, whose frame size follows from the resolution (bhr_amd.projection.frame_size)
     proj_kw = projection_from_args(args)
     if proj_kw:
@@ -910,6 +954,9 @@ def main(argv=None) -> int:
                                             spin=args.spin, redshift=args.redshift, world=world)
         if hasattr(args, "spin_shutter_map"):
             drivers.check_spin_shutter_map(True, spin=args.spin, redshift=args.redshift, shutter=args.shutter, world=world)
+        if kerr_stars_kw:
+            drivers.check_kerr_stars(kerr_stars_kw["kerr_stars"], spin=args.spin, redshift=args.redshift, world=world, video=True,
+                                     spin_map=hasattr(args, "spin_map"))
         if "BHR_FORCE_DEVICE" in os.environ:        # rehearsal: several ranks sharing one card
             local_rank = int(os.environ["BHR_FORCE_DEVICE"])
         elif world > 1:                             # a launcher that shows every rank only its own GPU: ordinal 0
@@ -921,7 +968,7 @@ def main(argv=None) -> int:
             width, height, args.pov, fov, args.step_size, args.texture, args.n_stars, 2048, 1024, args.r_max, None,
             args.disk_inner_radius, args.disk_outer_radius, args.disk_tilt, args.lens_flare, args.anti_alias,
             args.aa_strength, args.disk_rotation_speed, device_index=local_rank, math=args.math, supersample=args.supersample,
-            supersample_threshold=args.supersample_threshold, **spin_kw, **stars_kw)
+            supersample_threshold=args.supersample_threshold, **spin_kw, **stars_kw, **kerr_stars_kw)
         print(f"Rendering video: {args.n_frames} frames at {width}x{height} (rank {rank}/{world})")
         drivers.render_video(renderer, width, height, n_frames=args.n_frames, fps=args.fps,
                              output_path=args.output, fov=fov, static_cam_pos=args.pov, orbit=args.orbit,
@@ -937,7 +984,8 @@ def main(argv=None) -> int:
                                      infall_to=args.infall_to) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw,
                              **({"spin_map": True} if hasattr(args, "spin_map") else {}),
                              **({"spin_shutter_map": True} if hasattr(args, "spin_shutter_map") else {}),
-                             **({"spin_map_supersample": args.spin_map_supersample} if hasattr(args, "spin_map_supersample") else {}))
+                             **({"spin_map_supersample": args.spin_map_supersample} if hasattr(args, "spin_map_supersample") else {}),
+                             **kerr_stars_kw)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -962,6 +1010,7 @@ def main(argv=None) -> int:
         gpus=args.gpus, disk_model=args.disk_model, math=args.math, supersample=args.supersample,
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
         grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw, **stars_kw,
-        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw)
+        **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw,
+        **kerr_stars_kw, **({"kerr_passes_path": args.spin_passes} if hasattr(args, "spin_passes") else {}))
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

@@ -54,7 +54,8 @@ int32_t bhr_kerr_raymap_check_render(bhr_ctx *ctx, const char *who, const bhr_ca
         if (!rm->has_mom)
             return bhr_fail(BHR_ERR_STATE, "%s: a Kerr polarisation is set (bhr_set_kerr_polarization) and the map was built without the photon momenta it needs; build it again (bhr_kerr_raymap_build)", who);
     }
-    return BHR_OK;
+    // Kerr point stars (bhr_set_kerr_stars): a supersampled Kerr map's shade kernels have no STARS variant
+    return bhr_stars_check_map(ctx, BHR_RAYMAP_KERR, who);
 }
 
 // bhr_kerr_raymap_render_shutter's refusals (include/bhr.h), before anything is launched: everything bhr_kerr_raymap_render
@@ -95,7 +96,8 @@ int32_t bhr_kerr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cam
     }
     smp->n = n;
     smp->inv = 1.0f / (float)n;
-    return BHR_OK;
+    // Kerr point stars: the fused and the supersampled shade kernels have no STARS variant
+    return bhr_stars_check_shutter(ctx, BHR_RAYMAP_KERR, who);
 }
 
 extern "C" {
@@ -130,6 +132,8 @@ int32_t bhr_kerr_raymap_read(bhr_ctx *ctx, int32_t which, void *out, int64_t byt
     const char *who = "bhr_kerr_raymap_read";
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "%s: bad argument", who);
     if (!ctx->kerr_raymap || !ctx->kerr_raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no Kerr ray map has been built (bhr_kerr_raymap_build)", who);
+    // the build view's star plane under the Kerr catalogue, gathered now if the map or the catalogue changed since
+    if (which == BHR_RAYMAP_STARS) return bhr_stars_read_plane(ctx, BHR_RAYMAP_KERR, who, out, bytes);
     if (which == BHR_RAYMAP_MOMENTUM) {
         // the momentum planes of a build under a Kerr polarisation: [slot][component][pixel] on the device, [slot][pixel][component] out
         const bhr_raymap *rm = ctx->kerr_raymap;

@@ -93,12 +93,7 @@ int32_t bhr_raymap_turn_of_build(const bhr_camera &b, const bhr_camera *cam, con
 namespace {
 
 // point stars (bhr_set_stars): a supersampled map's shade kernels have no STARS variant
-int32_t check_stars(const bhr_ctx *ctx, const char *who) {
-    if (bhr_have_stars(ctx) && ctx->raymap->ss > 1)
-        return bhr_fail(BHR_ERR_STATE, "%s: a star catalogue is set (bhr_set_stars, %d stars) and the map is supersampled (factor %d); point stars need a map with one ray per pixel",
-                        who, ctx->stars->n, ctx->raymap->ss);
-    return BHR_OK;
-}
+int32_t check_stars(const bhr_ctx *ctx, const char *who) { return bhr_stars_check_map(ctx, BHR_RAYMAP_SCHWARZSCHILD, who); }
 
 // polarisation (bhr_set_polarization): the Stokes kernel walks the build view's records of a map with one ray per pixel
 int32_t check_polar(const bhr_ctx *ctx, const char *who, const char *what) {
@@ -146,12 +141,12 @@ int32_t alloc_planes(bhr_raymap *rm, const char *who, int32_t K, int32_t comps, 
     return BHR_OK;
 }
 
-// the star plane of the build view and the Stokes planes of the last frame belong to the Schwarzschild map: stale when it changes;
-// under a Kerr polarisation the Stokes planes are a Kerr map frame's: stale when that map changes
+// the star plane of the build view under the map's own kind of catalogue is stale when the map changes; so are the Stokes planes
+// of the last frame: the Schwarzschild map's, or under a Kerr polarisation a Kerr map frame's
 void invalidate_consumers(bhr_ctx *ctx, const bhr_raymap *rm) {
+    bhr_stars_invalidate(ctx, rm->kind);
     if (rm->kind == BHR_RAYMAP_KERR && bhr_have_kerr_polar(ctx)) bhr_polar_invalidate(ctx);
     if (rm->kind != BHR_RAYMAP_SCHWARZSCHILD) return;
-    bhr_stars_invalidate(ctx);
     bhr_polar_invalidate(ctx);
 }
 
@@ -342,9 +337,7 @@ int32_t bhr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, in
     smp->n = n;
     smp->inv = 1.0f / (float)n;
     // point stars: the fused and the supersampled shade kernels have no STARS variant
-    if (bhr_have_stars(ctx))
-        return bhr_fail(BHR_ERR_STATE, "%s: a star catalogue is set (bhr_set_stars, %d stars); shutter frames from the map have no point stars -- remove it (n = 0) first", who,
-                        ctx->stars->n);
+    BHR_TRY(bhr_stars_check_shutter(ctx, BHR_RAYMAP_SCHWARZSCHILD, who));
     return check_polar(ctx, who, "shutter frames from the map have no Stokes planes");
 }
 
@@ -370,16 +363,8 @@ int32_t bhr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags) {
 int32_t bhr_raymap_read(bhr_ctx *ctx, int32_t which, void *out, int64_t bytes) {
     if (!ctx || !out) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: bad argument");
     if (!ctx->raymap || !ctx->raymap->built) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_read: no ray map has been built (bhr_raymap_build)");
-    if (which == BHR_RAYMAP_STARS) {
-        // the build view's star plane (include/bhr.h "point stars"), gathered now if the map or the catalogue changed since
-        if (!bhr_have_stars(ctx)) return bhr_fail(BHR_ERR_STATE, "bhr_raymap_read: no star catalogue has been set (bhr_set_stars)");
-        BHR_TRY(check_stars(ctx, "bhr_raymap_read"));
-        const size_t want = (size_t)ctx->raymap->a.plane * 12;
-        if (bytes != (int64_t)want) return bhr_fail(BHR_ERR_INVALID, "bhr_raymap_read: plane %d has %zu bytes, caller gave %lld", which, want, (long long)bytes);
-        BHR_TRY(bhr_stars_ensure_plane(ctx));
-        BHR_TRY(bhr_enter(ctx));
-        return fetch(ctx, out, ctx->stars->d_plane, want);
-    }
+    // the build view's star plane (include/bhr.h "point stars"), gathered now if the map or the catalogue changed since
+    if (which == BHR_RAYMAP_STARS) return bhr_stars_read_plane(ctx, BHR_RAYMAP_SCHWARZSCHILD, "bhr_raymap_read", out, bytes);
     return bhr_raymap_read_plane(ctx, ctx->raymap, "bhr_raymap_read", which, out, bytes);
 }
 

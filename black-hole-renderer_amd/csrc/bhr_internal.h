@@ -225,6 +225,9 @@ enum bhr_march_kernel {
     BHR_MK_KERR_RAYMAP_BUILD_MOM,  // kerr_raymap_build_kernel<RS, KERR_BUILD_MOM>: the build that also keeps each crossing's photon momentum  kerr_raymap
     BHR_MK_KERR_RAYMAP_SHUTTER,      // kerr_raymap_shade_shutter_kernel<RS, false>: the mean of n frames from the Kerr map, one launch  kerr_raymap
     BHR_MK_KERR_RAYMAP_SHUTTER_ROT,  // kerr_raymap_shade_shutter_kernel<RS, true>: each sample turned about z by its own angle          kerr_raymap
+    // Kerr point stars (bhr_set_kerr_stars): the Kerr shade kernels that add the star plane to the sky sample; no supersampled twins
+    BHR_MK_KERR_RAYMAP_SHADE_STARS,      // kerr_raymap_shade_kernel<RS, false, true>                                                    kerr_raymap
+    BHR_MK_KERR_RAYMAP_SHADE_STARS_ROT,  // kerr_raymap_shade_kernel<RS, true, true>                                                     kerr_raymap
 };
 
 // The row of a march variant (settings.hip: bhr_variant_row_of): its kernels, and the terms and words of its refusals.
@@ -366,7 +369,7 @@ struct bhr_options {
 enum bhr_raymap_kind { BHR_RAYMAP_SCHWARZSCHILD, BHR_RAYMAP_KERR };
 struct bhr_raymap {
     BhrRayMapArgs a;             // the device planes
-    int32_t kind;                // bhr_raymap_kind: whose rays the records hold; stars and polarisation are the Schwarzschild kind's
+    int32_t kind;                // bhr_raymap_kind: whose rays the records hold; each kind has a star catalogue and a polarisation of its own
     float kerr_spin;             // a Kerr map: the spin and the redshift mode of its build, which a frame from it needs the
     int32_t kerr_redshift;       // context to have still
     int32_t built, diff, slots;
@@ -382,7 +385,9 @@ struct bhr_raymap {
     int32_t has_mom;
 };
 
-// The context's star catalogue (api_stars.hip): read-only shared state while frames are in flight, like the map.
+// A star catalogue of the context (api_stars.hip): read-only shared state while frames are in flight, like the map.  A context
+// owns up to two, ctx->stars (bhr_set_stars) and ctx->kerr_stars (bhr_set_kerr_stars), one for each kind of map; everything that
+// sets, gathers and frees a catalogue takes the kind (bhr_raymap_kind) and serves that kind's map with that kind's catalogue.
 struct bhr_stars {
     int32_t n, bins_theta, bins_phi;
     bhr_star_params params;
@@ -592,12 +597,13 @@ struct bhr_ctx {
     float kerr_spin;
     int32_t kerr_redshift;     // bhr_set_redshift: BHR_REDSHIFT_MODEL (0) or BHR_REDSHIFT_EXACT, which needs kerr_on
 
-    // the Kerr ray map (api_kerr_raymap.hip): a map object of its own -- nothing of `raymap` above is shared, stars and polarisation
+    // the Kerr ray map (api_kerr_raymap.hip): a map object of its own -- nothing of `raymap` above is shared, its stars and polarisation
     // never see it; it carries the spin and the redshift mode it was built under
     bhr_raymap *kerr_raymap;   // null until the first bhr_kerr_raymap_build
 
     // point stars (api_stars.hip)
-    bhr_stars *stars;          // null until a catalogue is set (bhr_set_stars)
+    bhr_stars *stars;          // null until a catalogue is set (bhr_set_stars): the Schwarzschild map's
+    bhr_stars *kerr_stars;     // null until a catalogue is set (bhr_set_kerr_stars): the Kerr map's
 
     // polarisation (api_polar.hip): polar_on = a polarisation is set (bhr_set_polarization); stokes_slot = the frame slot that holds
     // the Stokes planes of the last map frame rendered since (-1: none)
@@ -757,17 +763,19 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call);
 // layers -- the pixels on the overflow list are left to the fix kernel (bhr_launch_march with a repair == 2 part over that list)
 // ss: the map's factor -- the build marches the fine frame bhr_fine(ctx, ss) of `cam`
 // v, call.req.variant: none takes march_raymap.hip's kernels under the march's block, BHR_MV_KERR / BHR_MV_KERR_EXACT
-// march_kerr_raymap.hip's under the Kerr block (one ray per pixel, 5 components, no stars)
+// march_kerr_raymap.hip's under the Kerr block (one ray per pixel, 5 components)
 // mom: a Kerr build's momentum planes (kerr_raymap_build_kernel<RS, KERR_BUILD_MOM> fills them beside the records); null: the plain build
 int32_t bhr_launch_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flags, const BhrRayMapArgs &m, int32_t ss, bhr_march_variant v = BHR_MV_NONE,
                                 float *mom = nullptr);
 // rot_c, rot_s: the stored records turned about z by that cosine and sine before they are shaded (1, 0: the kernel without a turn)
-// stars: the star plane of the frame's view (bhr_set_stars), added to the sky sample by the STARS kernels; null: the kernels without
+// stars: the star plane of the frame's view (bhr_set_stars, a Kerr map's bhr_set_kerr_stars), added to the sky sample by the STARS kernels; null: the kernels without
 int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, bool diff, float rot_c = 1.0f, float rot_s = 0.0f,
                                 const float *stars = nullptr);
-// the star plane of the map seen from `cam`, the build camera turned by (rot_c, rot_s), into `out` (rows W 3 floats and three
-// counts behind them, which the launch clears first) on `stream` (stars.hip: stars_gather_kernel)
-int32_t bhr_launch_stars_gather(bhr_ctx *ctx, const bhr_camera *cam, const BhrRayMapArgs &m, float rot_c, float rot_s, float *out, hipStream_t stream);
+// the star plane of the map `m` under the catalogue `st`, seen from `cam`, the build camera turned by (rot_c, rot_s), into `out`
+// (rows W 3 floats and three counts behind them, which the launch clears first) on `stream` (stars.hip: stars_gather_kernel).
+// The kernel reads the view's camera and the frame's shape out of the march's block -- the part a Kerr block begins with -- and
+// the map's status and direction planes, which both kinds of map store alike: either kind's map, with either catalogue.
+int32_t bhr_launch_stars_gather(bhr_ctx *ctx, const bhr_stars *st, const bhr_camera *cam, const BhrRayMapArgs &m, float rot_c, float rot_s, float *out, hipStream_t stream);
 const void *bhr_stars_kernel(int32_t rot);                                             // stars.hip -> stars.o
 // all samples of a shutter frame from the map in one launch (raymap_shade_shutter_kernel): the mean of the n frames the launch
 // above would store for (smp[j].t, smp[j].c, smp[j].s), into the active slot's BG / DISK; no packed bloom operands.  Opens the
@@ -895,14 +903,28 @@ int32_t bhr_kerr_raymap_check_render(bhr_ctx *ctx, const char *who, const bhr_ca
 int32_t bhr_kerr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cams, int32_t n, uint32_t flags, BhrShutterArgs *smp, bool *turned);
 
 // ---- api_stars.hip ----------------------------------------------------------------------------------------------------------------------
-inline bool bhr_have_stars(const bhr_ctx *ctx) { return ctx->stars && ctx->stars->n > 0; }
+// kind (bhr_raymap_kind): whose catalogue -- the Schwarzschild map's (bhr_set_stars) or the Kerr map's (bhr_set_kerr_stars); a
+// catalogue serves the map of its own kind and no other
+inline bhr_stars *&bhr_stars_of(bhr_ctx *ctx, int32_t kind) { return kind == BHR_RAYMAP_KERR ? ctx->kerr_stars : ctx->stars; }
+inline const bhr_stars *bhr_stars_of(const bhr_ctx *ctx, int32_t kind) { return kind == BHR_RAYMAP_KERR ? ctx->kerr_stars : ctx->stars; }
+inline const bhr_raymap *bhr_stars_map(const bhr_ctx *ctx, int32_t kind) { return kind == BHR_RAYMAP_KERR ? ctx->kerr_raymap : ctx->raymap; }
+inline bool bhr_have_stars(const bhr_ctx *ctx, int32_t kind = BHR_RAYMAP_SCHWARZSCHILD) {
+    const bhr_stars *st = bhr_stars_of(ctx, kind);
+    return st && st->n > 0;
+}
 size_t bhr_star_plane_floats(const bhr_ctx *ctx);                          // rows W 3 and the counts' words behind them
 // the build view's plane exists and is current (gathers it on the scene stream, behind the frames in flight, if not)
-int32_t bhr_stars_ensure_plane(bhr_ctx *ctx);
+int32_t bhr_stars_ensure_plane(bhr_ctx *ctx, int32_t kind = BHR_RAYMAP_SCHWARZSCHILD);
 // the star plane of the active slot's frame from the map turned by (c, s) on ctx->stream: the cached one for no turn, else gathered into the slot's own
-int32_t bhr_stars_frame_plane(bhr_ctx *ctx, const bhr_camera *cam, float c, float s, const float **plane);
-void bhr_stars_invalidate(bhr_ctx *ctx);                                   // the map changed: the cached plane is stale
-void bhr_stars_release(bhr_ctx *ctx);
+int32_t bhr_stars_frame_plane(bhr_ctx *ctx, int32_t kind, const bhr_camera *cam, float c, float s, const float **plane);
+void bhr_stars_invalidate(bhr_ctx *ctx, int32_t kind);                     // the kind's map changed: the cached plane is stale
+// what the entry points of the kind's (built) map refuse while its catalogue is set, BHR_ERR_STATE naming the stars: a render or a
+// plane read from a supersampled map; a shutter frame
+int32_t bhr_stars_check_map(const bhr_ctx *ctx, int32_t kind, const char *who);
+int32_t bhr_stars_check_shutter(const bhr_ctx *ctx, int32_t kind, const char *who);
+// BHR_RAYMAP_STARS of the kind's (built) map for `who` (bhr_raymap_read, bhr_kerr_raymap_read): the build view's plane, gathered now if stale
+int32_t bhr_stars_read_plane(bhr_ctx *ctx, int32_t kind, const char *who, void *out, int64_t bytes);
+void bhr_stars_release(bhr_ctx *ctx, int32_t kind);
 
 // ---- api_polar.hip, march_polar.hip -----------------------------------------------------------------------------------------------------
 inline bool bhr_have_polar(const bhr_ctx *ctx) { return ctx->polar_on != 0; }

@@ -190,7 +190,8 @@ void bhr_destroy(bhr_ctx *ctx) {
     bhr_grade_free(ctx);
     bhr_raymap_release(ctx, &ctx->raymap);
     bhr_raymap_release(ctx, &ctx->kerr_raymap);
-    bhr_stars_release(ctx);
+    bhr_stars_release(ctx, BHR_RAYMAP_SCHWARZSCHILD);
+    bhr_stars_release(ctx, BHR_RAYMAP_KERR);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);
     bhr_pipe_free(ctx);

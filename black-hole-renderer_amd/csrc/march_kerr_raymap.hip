@@ -174,22 +174,29 @@ __device__ __forceinline__ Shade kerr_raymap_shade_records(const BhrMarchArgs &a
 
 // The pixel's BG and DISK values from its shaded records: the ray's fate and its stored escape direction (turned as the
 // records were), then the march's own pixel values.
+// star: the pixel's value of the view's star plane (the STARS kernel), which joins the sky sample; null: none.
 template <bool ROT>
 __device__ __forceinline__ void kerr_raymap_values(const BhrMarchArgs &a, const BhrRayMapArgs &m, size_t pix, const Shade &sh, float rc, float rs,
-                                                   float bk[3], float dk[3]) {
+                                                   float bk[3], float dk[3], const float *star = nullptr) {
     const size_t p = (size_t)m.plane;
     const bool esc = m.status[pix] == 1;
     V3 dir = mk(m.dir[pix], m.dir[p + pix], m.dir[2 * p + pix]);
     if (ROT) turn_xy(rc, rs, dir.x, dir.y);
-    raymap_pixel_values(a, esc, dir, sh, bk, dk);
+    raymap_pixel_values(a, esc, dir, sh, bk, dk, star);
 }
 
 // ---- the shade kernels --------------------------------------------------------------------------------------------------------
 // One lane per pixel, an 8x8 tile per wave as in the march (texture locality, and store_pixel's packed layout is per tile);
 // tiles in row-major order: every lane does about the same work.
 // ROT: the records are turned about z by (m.rot_c, m.rot_s) before they are shaded (the head of this file).
-template <int RS, bool ROT>
-__global__ __launch_bounds__(256) void kerr_raymap_shade_kernel(KerrBlock<RS> a, BhrRayMapArgs m) {
+// STARS: the frame of a context with a Kerr star catalogue (bhr_set_kerr_stars) -- march_raymap.hip's raymap_shade_kernel<.., true>
+// over the Kerr records: the map's block has the view's star plane behind it (BhrRayMapStarArgs), gathered by stars.hip's kernel
+// over this map's status and direction planes ahead of the launch, and the plane's value at the pixel joins the sky sample in one
+// f32 addition ahead of the march's own product (raymap_device.h: raymap_pixel_values).  A pixel on the overflow list gets none:
+// the fix kernel stores it.  The kernels without stars keep their block, their instructions and their registers
+// (profiles/kerr_stars_code_objects.txt).  No supersampled, shutter or fix twin.
+template <int RS, bool ROT, bool STARS = false>
+__global__ __launch_bounds__(256) void kerr_raymap_shade_kernel(KerrBlock<RS> a, std::conditional_t<STARS, BhrRayMapStarArgs, BhrRayMapArgs> m) {
     const int tile = wave_slot();
     if (tile >= a.n_tiles) return;
     const int lane = threadIdx.x & 63;
@@ -203,7 +210,8 @@ __global__ __launch_bounds__(256) void kerr_raymap_shade_kernel(KerrBlock<RS> a,
     const float rc = ROT ? m.rot_c : 1.0f, rs = ROT ? m.rot_s : 0.0f;
     const Shade sh = kerr_raymap_shade_records<RS, ROT>(a, a, m, pix, count, rc, rs);
     float bk[3], dk[3];
-    kerr_raymap_values<ROT>(a, m, pix, sh, rc, rs, bk, dk);
+    if constexpr (STARS) kerr_raymap_values<ROT>(a, m, pix, sh, rc, rs, bk, dk, m.stars + pix * 3);
+    else kerr_raymap_values<ROT>(a, m, pix, sh, rc, rs, bk, dk);
     store_pixel(a, i, j, a.width, bk, dk);
 }
 
@@ -368,7 +376,8 @@ __global__ __launch_bounds__(256) void kerr_raymap_fix_kernel(KerrBlock<RS> a) {
 
 // ---- the kernels of this object, by the launcher's names (march_launch.hip); null: not in this object ----------
 // exact: the kernels of the exact redshift (they take BhrKerrExactMarchArgs); ss: the kernels of a supersampled map (a.ss > 1;
-// the momentum build has none, and neither have the shutter kernels: a supersampled map's shutter frames go sample by sample)
+// the momentum build has none, neither have the STARS shade kernels, and neither have the shutter kernels: a supersampled map's
+// shutter frames go sample by sample)
 const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact, int32_t ss) {
     if (ss) {
         switch (k) {
@@ -383,6 +392,10 @@ const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact, int3
     case BHR_MK_KERR_RAYMAP_BUILD: return exact ? (const void *)kerr_raymap_build_kernel<KERR_EXACT, KERR_BUILD_PLAIN> : (const void *)kerr_raymap_build_kernel<0, KERR_BUILD_PLAIN>;
     case BHR_MK_KERR_RAYMAP_SHADE: return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, false> : (const void *)kerr_raymap_shade_kernel<0, false>;
     case BHR_MK_KERR_RAYMAP_SHADE_ROT: return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, true> : (const void *)kerr_raymap_shade_kernel<0, true>;
+    case BHR_MK_KERR_RAYMAP_SHADE_STARS:
+        return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, false, true> : (const void *)kerr_raymap_shade_kernel<0, false, true>;
+    case BHR_MK_KERR_RAYMAP_SHADE_STARS_ROT:
+        return exact ? (const void *)kerr_raymap_shade_kernel<KERR_EXACT, true, true> : (const void *)kerr_raymap_shade_kernel<0, true, true>;
     case BHR_MK_KERR_RAYMAP_BUILD_MOM: return exact ? (const void *)kerr_raymap_build_kernel<KERR_EXACT, KERR_BUILD_MOM> : (const void *)kerr_raymap_build_kernel<0, KERR_BUILD_MOM>;
     case BHR_MK_KERR_RAYMAP_FIX: return exact ? (const void *)kerr_raymap_fix_kernel<KERR_EXACT, false> : (const void *)kerr_raymap_fix_kernel<0, false>;
     case BHR_MK_KERR_RAYMAP_SHUTTER:

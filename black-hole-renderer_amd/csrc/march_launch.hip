@@ -544,7 +544,7 @@ int32_t bhr_launch_adaptive(bhr_ctx *ctx, const bhr_march_call &call) {
 // own factor ss, option "raymap_supersample" or a Kerr map's "kerr_raymap_supersample"; the context's factor stays 1) takes the
 // block of the fine frame, as a marched supersampled frame does, and the kernels' supersampled twins.  Under a Kerr variant the
 // kernels are the Kerr map's, which take the Kerr block of the redshift (variant_args) in the march block's place: no
-// differentials, no stars.
+// differentials.
 static const void *raymap_kernel(bhr_march_variant v, bhr_march_kernel plain, bhr_march_kernel kerr, bool diff, int32_t ss) {
     return v == BHR_MV_NONE ? bhr_march_kernel_raymap(plain, diff, ss > 1) : bhr_march_kernel_kerr_raymap(kerr, v == BHR_MV_KERR_EXACT, ss > 1);
 }
@@ -598,9 +598,11 @@ int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const 
     BhrMarchArgs a;
     BHR_TRY(raymap_shade_args(ctx, call, m, diff, call.ss, api, a));
     const bool turned = !(rot_c == 1.0f && rot_s == 0.0f);
-    // stars: the STARS kernels, which have no supersampled twins (the table then returns none)
+    // stars: the STARS kernels of either map, which have no supersampled twins (the table then returns none)
     const bhr_march_kernel name = stars ? (turned ? BHR_MK_RAYMAP_SHADE_STARS_ROT : BHR_MK_RAYMAP_SHADE_STARS) : (turned ? BHR_MK_RAYMAP_SHADE_ROT : BHR_MK_RAYMAP_SHADE);
-    const void *fn = raymap_kernel(call.req.variant, name, turned ? BHR_MK_KERR_RAYMAP_SHADE_ROT : BHR_MK_KERR_RAYMAP_SHADE, diff, call.ss);
+    const bhr_march_kernel kerr_name =
+        stars ? (turned ? BHR_MK_KERR_RAYMAP_SHADE_STARS_ROT : BHR_MK_KERR_RAYMAP_SHADE_STARS) : (turned ? BHR_MK_KERR_RAYMAP_SHADE_ROT : BHR_MK_KERR_RAYMAP_SHADE);
+    const void *fn = raymap_kernel(call.req.variant, name, kerr_name, diff, call.ss);
     if (!fn) return bhr_fail(BHR_ERR_STATE, "%s: no shade kernel in this library", api);
     // the frame's march bracket opens here; the overflow launch behind this one (bhr_launch_march, last part) closes it
     // (a later sample of a shutter frame from the map keeps the first sample's)
@@ -617,12 +619,12 @@ int32_t bhr_launch_raymap_shade(bhr_ctx *ctx, const bhr_march_call &call, const 
     return BHR_OK;
 }
 
-// The star plane of the map `m` seen from `cam` -- the build camera turned about z by (rot_c, rot_s) -- into `out`: rows W 3
-// floats, and behind them the gather's three counts, cleared here ahead of the launch (stars.hip).  The march's block carries
-// the view's camera and the frame's shape; the kernel reads nothing else of it.
-int32_t bhr_launch_stars_gather(bhr_ctx *ctx, const bhr_camera *cam, const BhrRayMapArgs &m, float rot_c, float rot_s, float *out, hipStream_t stream) {
-    const bhr_stars *st = ctx->stars;
-    if (!st || st->n <= 0) return bhr_fail(BHR_ERR_STATE, "star gather: no star catalogue (bhr_set_stars)");
+// The star plane of the map `m` under the catalogue `st`, seen from `cam` -- the build camera turned about z by (rot_c, rot_s) --
+// into `out`: rows W 3 floats, and behind them the gather's three counts, cleared here ahead of the launch (stars.hip).  The
+// march's block carries the view's camera and the frame's shape; the kernel reads nothing else of it -- and those are the words a
+// Kerr block of the view begins with, so a Kerr map's plane is gathered under the same block by the same kernel.
+int32_t bhr_launch_stars_gather(bhr_ctx *ctx, const bhr_stars *st, const bhr_camera *cam, const BhrRayMapArgs &m, float rot_c, float rot_s, float *out, hipStream_t stream) {
+    if (!st || st->n <= 0) return bhr_fail(BHR_ERR_STATE, "star gather: no star catalogue (bhr_set_stars, bhr_set_kerr_stars)");
     const bhr_march_call call = {cam, BHR_FORCE_STRICT | BHR_SKIP_BLOOM, stream, /* slot */ -1, false, false, 1, false};
     BhrMarchArgs a;
     march_args(ctx, call, nullptr, 1, false, a);

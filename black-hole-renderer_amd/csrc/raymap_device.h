@@ -23,7 +23,12 @@ __device__ __forceinline__ void raymap_pixel_values(const BhrMarchArgs &a, bool 
                                                     const float *star = nullptr) {
     V3 bg = mk(0, 0, 0);
     if (escaped) bg = sample_skybox(a.sc, dir);
-    if (star) bg = bg + mk(star[0], star[1], star[2]);
+    if (star) {
+        // a statement of its own, kept out of contraction (the Kerr object contracts within an expression; the strict object not
+        // at all, where the pragma does nothing): the sky sample keeps the bits it has without a catalogue, the sum is one f32 addition
+#pragma clang fp contract(off)
+        bg = bg + mk(star[0], star[1], star[2]);
+    }
     float k = 1.0f - sh.alpha_total;
     bk[0] = __fmul_rn(bg.x, k);
     bk[1] = __fmul_rn(bg.y, k);

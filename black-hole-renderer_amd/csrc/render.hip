@@ -117,13 +117,13 @@ bhr_march_part raymap_fix_part(const bhr_raymap &rm) {
 
 // The launches of one frame from the map `rm` under `call`: the shade kernel over the stored records, turned by (c, s), then the
 // strict fix kernel over the overflow list (which, unless the call defers it, records the ring slot's march-end event).
-// With a star catalogue set (bhr_set_stars) the view's star plane comes first -- the cached one of the build view, or the gather
-// of the turned view into the slot's own plane, on the frame's stream ahead of its march bracket -- and the shade kernel is the
-// STARS one.  Stars are the Schwarzschild kind's: a Kerr map's frame does not ask for the catalogue.
+// With a star catalogue of the map's own kind set (bhr_set_stars; a Kerr map's bhr_set_kerr_stars) the view's star plane comes
+// first -- the cached one of the build view, or the gather of the turned view into the slot's own plane, on the frame's stream
+// ahead of its march bracket -- and the shade kernel is the STARS one.  A map asks its own kind's catalogue and never the other.
 // Under call's Kerr variant both launches take the Kerr map's kernels (march_launch.hip).
 int32_t raymap_frame_launches(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm, float c, float s) {
     const float *stars = nullptr;
-    if (rm.kind == BHR_RAYMAP_SCHWARZSCHILD && bhr_have_stars(ctx)) BHR_TRY(bhr_stars_frame_plane(ctx, call.cam, c, s, &stars));
+    if (bhr_have_stars(ctx, rm.kind)) BHR_TRY(bhr_stars_frame_plane(ctx, rm.kind, call.cam, c, s, &stars));
     BHR_TRY(bhr_launch_raymap_shade(ctx, call, rm.a, rm.diff != 0, c, s, stars));
     const bhr_march_part part = raymap_fix_part(rm);
     return bhr_launch_march(ctx, call, &part);
@@ -148,7 +148,7 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_raymap &rm, const bhr_camera *cam
     // a polarisation is set (bhr_set_polarization): the Stokes pass over the same records into the slot's own planes, behind the
     // frame's march bracket and ahead of its post-pass -- the frame's end event covers it, so a read waits for it like for the rest.
     // It reads the scene (shade_hit samples the disk texture), so it replaces f.march_done by an event of the slot's own behind it.
-    // The Schwarzschild kind's alone, like the stars.
+    // The Schwarzschild kind's alone.
     if (!kerr && bhr_have_polar(ctx)) {
         BHR_TRY(bhr_polar_frame(ctx, call, rm));
         ctx->stokes_slot = k;
@@ -384,6 +384,7 @@ int32_t bhr_kerr_raymap_render(bhr_ctx *ctx, float t_offset, uint32_t flags) {
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     bhr_camera cam = ctx->kerr_raymap->cam;
     cam.t_offset = t_offset;
+    if (bhr_have_stars(ctx, BHR_RAYMAP_KERR)) BHR_TRY(bhr_stars_ensure_plane(ctx, BHR_RAYMAP_KERR));   // the build view's star plane, once per (Kerr map, Kerr catalogue)
     return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, *ctx->kerr_raymap, &cam, flags, k, ring, fm); });
 }
 
@@ -394,6 +395,7 @@ int32_t bhr_kerr_raymap_render_view(bhr_ctx *ctx, const bhr_camera *cam, uint32_
     BHR_TRY(bhr_kerr_raymap_check_render(ctx, "bhr_kerr_raymap_render_view", cam, cam->t_offset, flags, &rot_c, &rot_s));
     BHR_HIP(hipSetDevice(ctx->cfg.device));
     const bhr_camera view = *cam;
+    if (bhr_have_stars(ctx, BHR_RAYMAP_KERR) && rot_c == 1.0f && rot_s == 0.0f) BHR_TRY(bhr_stars_ensure_plane(ctx, BHR_RAYMAP_KERR));   // angle 0: bhr_kerr_raymap_render's plane
     return frame_on_next_slot(ctx, flags, false, [&](int k, int ring, frame_marches *fm) { return raymap_on_slot(ctx, *ctx->kerr_raymap, &view, flags, k, ring, fm, rot_c, rot_s); });
 }
 

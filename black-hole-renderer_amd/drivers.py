@@ -145,13 +145,16 @@ def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, 
                   tex_h=1024, r_max=10.0, disk_texture_path=None, r_disk_inner=R_DISK_INNER_DEFAULT,
                   r_disk_outer=R_DISK_OUTER_DEFAULT, disk_tilt=0.0, lens_flare=False, anti_alias="disabled",
                   aa_strength=1.0, disk_rotation_speed=0.1, device_index=0, rows=None, frame_slots=None, math=None,
-                  supersample=1, supersample_threshold=None, spin=0.0, redshift="model", stars=None):
+                  supersample=1, supersample_threshold=None, spin=0.0, redshift="model", stars=None, kerr_stars=None):
     """Renderer with a placeholder (or file) disk texture, as the reference's entry points build it
     (render.py:4044-4064, 4627-4644).  Returns (renderer, use_lifecycle, n_r, n_phi).
     ``stars``: None, or the point stars of check_stars -- the procedural sky is then built WITHOUT its baked star blobs and its
     ``n_stars`` stars become the renderer's catalogue (HipRenderer.set_stars), with the solid angle of a pixel of the view
-    (cam_pos, fov) in their flux, so that the look does not depend on the resolution."""
+    (cam_pos, fov) in their flux, so that the look does not depend on the resolution.
+    ``kerr_stars``: None, or the Kerr point stars of check_kerr_stars -- the same for a spinning hole: the starless sky, and the
+    catalogue set as the KERR ray map's (HipRenderer.set_kerr_stars)."""
     stars = check_stars(stars, skybox_path=skybox_path, supersample=supersample, spin=spin, redshift=redshift)
+    kerr_stars = check_kerr_stars(kerr_stars, spin=spin, redshift=redshift, skybox_path=skybox_path, stars=stars is not None, supersample=supersample)
     # procedural sky: the host draws its random tables, the device rasterises them (nebula resize, star blobs in
     # NumPy's accumulation order, Milky-Way glow; skyglow.hip); an image file is loaded as it is
     procedural_sky = not (skybox_path and os.path.isfile(skybox_path))
@@ -175,13 +178,15 @@ def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, 
                            frame_slots=frame_slots, supersample=supersample, supersample_threshold=supersample_threshold,
                            **({} if math is None else {"math": math}), **({"spin": spin} if spin != 0 else {}),
                            **({"redshift": redshift} if redshift != "model" else {}))
-    if procedural_sky and stars is not None:
+    if procedural_sky and (stars is not None or kerr_stars is not None):
         from .skybox import sky_tables
         from .stars import catalog_from_tables
+        # (the checks have refused both at once: the catalogue is the Schwarzschild map's or the Kerr map's)
+        points, set_catalog = (stars, renderer.set_stars) if stars is not None else (kerr_stars, renderer.set_kerr_stars)
         renderer.build_procedural_skybox(seed=42, n_stars=n_stars, starless=True)
         cam = renderer.camera_uniforms(cam_pos, fov, 0)
-        dirs, flux = catalog_from_tables(sky_tables(tex_w, tex_h, 42, n_stars), stars["gain"], float(cam.pixel_width) * float(cam.pixel_height))
-        renderer.set_stars(dirs, flux, max_magnification=stars["max_magnification"])
+        dirs, flux = catalog_from_tables(sky_tables(tex_w, tex_h, 42, n_stars), points["gain"], float(cam.pixel_width) * float(cam.pixel_height))
+        set_catalog(dirs, flux, max_magnification=points["max_magnification"])
     elif procedural_sky:
         renderer.build_procedural_skybox(seed=42, n_stars=n_stars)
     return renderer, use_lifecycle, n_r, n_phi
@@ -220,6 +225,77 @@ def check_stars(stars, skybox_path=None, supersample=1, spin: float = 0.0, redsh
     return out
 
 
+def check_kerr_stars(kerr_stars, spin: float = 0.0, redshift: str = "model", skybox_path=None, stars: bool = False, supersample=1,
+                     spin_map_supersample: int = 1, spin_shutter_map: bool = False, shutter: float = 0.0, spin_observer: bool = False,
+                     spin_projection: bool = False, gpus: int = 1, world: int = 1, video: bool = False, spin_map: bool = False):
+    """--spin_stars point / kerr_stars=dict(gain=, max_magnification=): the procedural sky's stars as a catalogue of lensed points
+    rendered through the KERR ray map of a spinning hole (HipRenderer.set_kerr_stars).  -> the dict with its defaults filled in,
+    or None.  It needs a spin or the exact redshift (the Kerr march); a still builds a Kerr ray map of the view, a video needs
+    spin_map.  Raises ValueError naming --spin_stars and the other flag, before any device work, for what Kerr point stars do not
+    take: a sky image (it has no catalogue), --stars point (the Schwarzschild map's), supersampling of the frame or of the Kerr
+    map, shutter frames, the Kerr camera, several GPUs or ranks, a video without spin_map."""
+    if kerr_stars is None:
+        return None
+    who = "--spin_stars"
+    from .stars import DEFAULT_MAX_MAGNIFICATION, DEFAULT_STAR_GAIN
+    out = {"gain": DEFAULT_STAR_GAIN, "max_magnification": DEFAULT_MAX_MAGNIFICATION}
+    unknown = set(kerr_stars) - set(out)
+    if unknown:
+        raise ValueError(f"{who} takes gain and max_magnification, got {sorted(unknown)}")
+    out.update(kerr_stars)
+    if not (out["gain"] > 0 and np.isfinite(out["gain"])):
+        raise ValueError(f"{who}: --star_gain must be greater than 0, got {out['gain']}")
+    if not 1.0 <= out["max_magnification"] <= 1e6:
+        raise ValueError(f"{who}: --star_max_magnification must be between 1 and 1e6, got {out['max_magnification']}")
+    if spin == 0 and redshift == "model":
+        raise ValueError(f"{who} needs --spin or --redshift exact: they are the point stars of the Kerr ray map; a hole that does not spin takes --stars point")
+    if skybox_path is not None:
+        raise ValueError(f"{who} does not combine with --texture: a sky image has no catalogue")
+    if stars:
+        raise ValueError(f"{who} does not combine with --stars point: that is the catalogue of the map of Schwarzschild rays")
+    if supersample not in (None, 1):
+        raise ValueError(f"{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
+    if spin_map_supersample != 1:
+        raise ValueError(f"{who} does not combine with --spin_map_supersample other than 1: point stars need a Kerr ray map with one ray per pixel")
+    if spin_shutter_map:
+        raise ValueError(f"{who} does not combine with --spin_shutter_map: shutter frames from the Kerr map have no point stars")
+    if shutter > 0:
+        raise ValueError(f"{who} does not combine with --shutter: shutter frames are marched, point stars are rendered through the Kerr ray map")
+    if spin_observer:
+        raise ValueError(f"{who} does not combine with --spin_observer: a Kerr ray map holds the rays of the camera at rest")
+    if spin_projection:
+        raise ValueError(f"{who} does not combine with --spin_projection: a Kerr ray map holds the rays of the pinhole camera")
+    if gpus != 1 or world != 1:
+        raise ValueError(f"{who} does not combine with --gpus other than 1 or several ranks: a ray map lives on one GPU")
+    if video and not spin_map:
+        raise ValueError(f"{who} with --video needs --spin_map: point stars are rendered through the Kerr ray map")
+    return out
+
+
+def check_kerr_passes(kerr_passes_path, spin: float = 0.0, redshift: str = "model", supersample=1, spin_observer: bool = False,
+                      spin_projection: bool = False, gpus: int = 1, video: bool = False) -> None:
+    """--spin_passes PATH.npz / kerr_passes_path: the geometry passes of a still under a spin, from a Kerr ray map of the view.
+    Raises ValueError naming --spin_passes and the other flag, before any device work: it needs a spin or the exact redshift and
+    a .npz path, and takes neither supersampling, the Kerr camera, several GPUs nor a video."""
+    if kerr_passes_path is None:
+        return
+    who = "--spin_passes"
+    if spin == 0 and redshift == "model":
+        raise ValueError(f"{who} needs --spin or --redshift exact: the passes come from the Kerr ray map; a hole that does not spin takes --passes")
+    if video:
+        raise ValueError(f"{who} writes the passes of a still image: it does not combine with --video")
+    if not str(kerr_passes_path).lower().endswith(".npz"):
+        raise ValueError(f"{who} writes a .npz file, got {kerr_passes_path!r}")
+    if supersample not in (None, 1):
+        raise ValueError(f"{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
+    if spin_observer:
+        raise ValueError(f"{who} does not combine with --spin_observer: a Kerr ray map holds the rays of the camera at rest")
+    if spin_projection:
+        raise ValueError(f"{who} does not combine with --spin_projection: a Kerr ray map holds the rays of the pinhole camera")
+    if gpus != 1:
+        raise ValueError(f"{who} does not combine with --gpus other than 1: a ray map lives on one GPU")
+
+
 def render_image(width: int, height: int, cam_pos: List[float], fov: float, step_size: float,
                  skybox_path: Optional[str] = None, n_stars: int = 6000, tex_w: int = 2048, tex_h: int = 1024,
                  r_max: float = 10.0, device: str = "hip", disk_texture_path: Optional[str] = None,
@@ -234,7 +310,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  observer=None, observer_sky: bool = True, stars: Optional[dict] = None,
                  projection: Optional[str] = None, projection_fov=None, light_delay=None, polarization: Optional[dict] = None,
                  stokes_path: Optional[str] = None, ticks_path: Optional[str] = None, kerr_polarization: Optional[dict] = None,
-                 kerr_view: Optional[dict] = None) -> np.ndarray:
+                 kerr_view: Optional[dict] = None, kerr_stars: Optional[dict] = None, kerr_passes_path: Optional[str] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -263,7 +339,11 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     grid, the field, Pi_0, the convention and the camera as a compressed .npz (bhr_amd.polarization.write_stokes) and ``ticks_path``
     the frame with a polarisation tick per cell drawn over it (draw_ticks) as a PNG.  ``kerr_view``: None, or the Kerr camera of a
     spinning hole (check_kerr_view: a named or fixed velocity, the sky's shift, an equirect or fisheye projection) -- the frame is
-    HipRenderer.render_async(kerr_observer=, kerr_projection=)'s."""
+    HipRenderer.render_async(kerr_observer=, kerr_projection=)'s.  ``kerr_stars``: None, or dict(gain=, max_magnification=) --
+    point stars around a spinning hole (check_kerr_stars): the starless sky, the catalogue as the Kerr map's, a Kerr ray map of the
+    view, and the still from that map -- kerr_polarization's route, with which it combines.  ``kerr_passes_path``: ``passes_path``
+    for a still under a spin (check_kerr_passes): also builds the Kerr ray map of the view and writes its passes, the frame's bg /
+    disk / blur layers, and the hole's spin and redshift there; the image itself is rendered as without it."""
     check_depth_and_dither(bit_depth, dither=dither)
     kerr_view = check_kerr_view(kerr_view, spin=spin, redshift=redshift, disk_tilt=disk_tilt, anti_alias=anti_alias, disk_model=disk_model,
                                 supersample_threshold=supersample_threshold, gpus=gpus, observer=observer is not None,
@@ -302,6 +382,12 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     if (spin != 0 or redshift != "model") and (gpus > 1 or passes_path is not None or disk_model != "texture"):
         raise ValueError("a spin renders on one GPU with the texture disk source and writes no passes: row-block tiles, ray maps "
                          "and Disk V2 are Schwarzschild's")
+    # the Kerr point stars and the Kerr passes, behind every refusal above: each names --spin_stars / --spin_passes and the other flag
+    view_proj = kerr_view is not None and kerr_view["projection"] is not None
+    kerr_stars = check_kerr_stars(kerr_stars, spin=spin, redshift=redshift, skybox_path=skybox_path, stars=stars is not None, supersample=supersample,
+                                  spin_observer=kerr_view is not None and not view_proj, spin_projection=view_proj, gpus=gpus)
+    check_kerr_passes(kerr_passes_path, spin=spin, redshift=redshift, supersample=supersample, spin_observer=kerr_view is not None and not view_proj,
+                      spin_projection=view_proj, gpus=gpus)
     if gpus > 1:
         from .multigpu import render_image_tiled
         return render_image_tiled(width, height, cam_pos, fov, gpus, step_size=step_size, skybox_path=skybox_path,
@@ -314,7 +400,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         width, height, cam_pos, fov, step_size, skybox_path, n_stars, tex_w, tex_h, r_max, disk_texture_path,
         r_disk_inner, r_disk_outer, disk_tilt, lens_flare, anti_alias, aa_strength, disk_rotation_speed, math=math,
         supersample=supersample, supersample_threshold=supersample_threshold, spin=spin,
-        **({"redshift": redshift} if redshift != "model" else {}), **({} if stars is None else {"stars": stars}))
+        **({"redshift": redshift} if redshift != "model" else {}), **({} if stars is None else {"stars": stars}),
+        **({} if kerr_stars is None else {"kerr_stars": kerr_stars}))
     if use_analytic_disk(renderer, disk_model):
         pass
     elif use_lifecycle:
@@ -326,9 +413,10 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         renderer.set_grade(**grade)
     if polarization is not None:
         renderer.set_polarization(**polarization)          # ahead of the frame: its Stokes pass rides behind the shade launch
-    if kerr_polarization is not None:
+    if kerr_polarization is not None or kerr_stars is not None:
         from . import _lib
-        renderer.set_kerr_polarization(**kerr_polarization)   # ahead of the build: the map then keeps the photon momenta
+        if kerr_polarization is not None:
+            renderer.set_kerr_polarization(**kerr_polarization)   # ahead of the build: the map then keeps the photon momenta
         renderer.build_kerr_ray_map(cam_pos, fov)
         renderer.render_from_kerr_ray_map_async(frame=0)
         img = renderer.read_layer(_lib.LAYER_FINAL)
@@ -346,6 +434,10 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     if stars is not None:
         si = renderer.stars_info()
         print(f"Point stars: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
+              f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
+    if kerr_stars is not None:
+        si = renderer.kerr_stars_info()
+        print(f"Kerr point stars: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
               f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
     if polarization is not None:
         from . import polarization as pol_mod
@@ -374,6 +466,16 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         info = renderer.ray_map_info()
         print(f"Saved: {passes_path} (ray map: {info['slots']} slots, {info['crossings_stored']} crossings, "
               f"{info['overflow_pixels']} overflow pixels)")
+    if kerr_passes_path is not None:
+        from . import _lib
+        layers = {"bg": renderer.read_layer(_lib.LAYER_BG), "disk": renderer.read_layer(_lib.LAYER_DISK),
+                  "blur": renderer.read_layer(_lib.LAYER_BLUR)}
+        if not renderer.kerr_ray_map_info()["built"]:          # (a still with Kerr point stars or a Kerr polarisation came from the view's map)
+            renderer.build_kerr_ray_map(cam_pos, fov)
+        info = renderer.kerr_ray_map_info()
+        write_passes(kerr_passes_path, renderer.kerr_ray_map_passes(), layers, hole=dict(spin=info["spin"], redshift=info["redshift"]))
+        print(f"Saved: {kerr_passes_path} (Kerr ray map, spin {info['spin']:g}, {info['redshift']} redshift: {info['slots']} slots, "
+              f"{info['crossings_stored']} crossings, {info['overflow_pixels']} overflow pixels)")
     dt = time.time() - t0
     print(f"Done in {dt:.3f}s  (march {c['march_ms']:.2f} ms, bloom {c['bloom_ms']:.2f} ms, "
           f"{c['ray_steps'] / 1e6:.1f} Mray-steps, {c['ray_steps'] / max(c['march_ms'], 1e-6) / 1e3:.0f} Mray-steps/s)")
@@ -971,7 +1073,7 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
                     bit_depth=8, dither="none", shutter=0.0, shutter_samples=8, grade=None, ray_map=False, orbit_map=False,
                     shutter_map=False, map_supersample=1, video_hdr=None, hdr_white=203.0, hdr_exposure=0.0, observer=None,
                     stars=None, projection=None, light_delay=None, polarization=None, spin_map=False, kerr_view=None,
-                    spin_map_supersample=1, spin_shutter_map=False) -> dict:
+                    spin_map_supersample=1, spin_shutter_map=False, kerr_stars=None) -> dict:
     """The ``params`` of a progress record: the reference's five, and the output settings that change the frame files only
     where they are not the defaults -- a record written before those settings existed still matches a default run.  A
     resume whose params differ from the record's starts over."""
@@ -1015,6 +1117,8 @@ def progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, vi
         params.update(polarization={"field": list(polarization["field"]), "fraction": polarization["fraction"], "cell": polarization["cell"]})
     if kerr_view is not None:
         params.update(kerr_view={k: (list(v) if isinstance(v, tuple) else v) for k, v in kerr_view.items()})
+    if kerr_stars is not None:
+        params.update(kerr_stars=dict(kerr_stars))
     return params
 
 
@@ -1056,7 +1160,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
                  light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, spin_map: bool = False,
                  kerr_polarization: Optional[dict] = None, kerr_view: Optional[dict] = None, spin_map_supersample: int = 1,
-                 spin_shutter_map: bool = False,
+                 spin_shutter_map: bool = False, kerr_stars: Optional[dict] = None,
                  **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
@@ -1311,6 +1415,18 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             raise ValueError("point stars render on one GPU: a ray map lives on one GPU")
         if renderer.stars_info()["n"] == 0:
             raise ValueError("point stars: the renderer has no star catalogue (make_renderer(stars=...) sets it)")
+    # ``kerr_stars`` (needs ``spin_map=True``): point stars around a spinning hole, behind every refusal above -- the renderer
+    # carries the Kerr catalogue (make_renderer(kerr_stars=)) and every frame from the Kerr map shows it; under ``orbit`` each frame
+    # gathers the star plane of its turned view.  The progress record names the stars only when there are any.
+    if kerr_stars is not None:                                  # (without them the renderer is not asked anything, as ever)
+        kerr_stars = check_kerr_stars(kerr_stars, spin=renderer.spin, redshift=renderer.redshift, stars=stars is not None,
+                                      supersample=renderer.supersample if supersample is None else supersample,
+                                      spin_map_supersample=spin_map_supersample, spin_shutter_map=spin_shutter_map, shutter=shutter,
+                                      spin_observer=kerr_view is not None and kerr_view.get("projection") is None,
+                                      spin_projection=kerr_view is not None and kerr_view.get("projection") is not None,
+                                      world=world, video=True, spin_map=spin_map)
+        if renderer.kerr_stars_info()["n"] == 0:
+            raise ValueError("--spin_stars: the renderer has no Kerr star catalogue (make_renderer(kerr_stars=...) sets it)")
     if video_codec not in VIDEO_CODECS:
         raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
     check_depth_and_dither(bit_depth, dither=dither, video_codec=video_codec)
@@ -1335,7 +1451,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                              **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}),
                              **({} if light_delay is None else {"light_delay": light_delay}),
                              **({} if polarization is None else {"polarization": polarization}), spin_map=spin_map, kerr_view=kerr_view,
-                             spin_map_supersample=spin_map_supersample, **({"spin_shutter_map": True} if spin_shutter_map else {}))
+                             spin_map_supersample=spin_map_supersample, **({"spin_shutter_map": True} if spin_shutter_map else {}),
+                             **({} if kerr_stars is None else {"kerr_stars": kerr_stars}))
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never

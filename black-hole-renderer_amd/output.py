@@ -386,10 +386,12 @@ def hit_polar(hits: np.ndarray, crossings: np.ndarray):
     return np.where(none, np.float32(np.nan), r).astype(np.float32), np.where(none, np.float32(np.nan), phi).astype(np.float32)
 
 
-def write_passes(path: str, passes: dict, layers: dict = None) -> None:
+def write_passes(path: str, passes: dict, layers: dict = None, hole: dict = None) -> None:
     """The geometry passes of a ray map (HipRenderer.ray_map_passes) and, with ``layers``, the frame's ``bg`` / ``disk`` /
     ``blur`` layers ((H, W, 3) float32 each) as one compressed ``.npz``: the integer passes as int32, everything else as
-    float32, under the keys they came with.  A host function; needs no device."""
+    float32, under the keys they came with.  ``hole``: dict(spin=, redshift=) of a Kerr ray map's passes
+    (HipRenderer.kerr_ray_map_passes), stored as ``spin`` (float32) and ``redshift`` ("model" or "exact").  A host function; needs
+    no device."""
     if not str(path).lower().endswith(".npz"):
         raise ValueError(f"the passes are written as a .npz file, got {path!r}")
     missing = [k for k in ("steps", "status", "escape_dir", "crossings", "hits") if k not in passes]
@@ -415,5 +417,10 @@ def write_passes(path: str, passes: dict, layers: dict = None) -> None:
         if a.shape != shape + (3,):
             raise ValueError(f"layer {name!r} has shape {a.shape} in a {shape} frame")
         out[name] = a
+    if hole is not None:
+        if set(hole) != {"spin", "redshift"} or hole["redshift"] not in ("model", "exact"):
+            raise ValueError(f"hole takes spin and redshift ('model' or 'exact'), got {hole!r}")
+        out["spin"] = np.float32(hole["spin"])
+        out["redshift"] = np.array(hole["redshift"])
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     np.savez_compressed(path, **out)

@@ -800,11 +800,15 @@ class HipRenderer:
         capped at it; one whose escape directions are more than ``max_span_deg`` apart contributes nothing.  Marched frames
         (render_async and its kin) ignore the catalogue; shutter frames from the map and supersampled maps refuse it.
         Synchronises."""
+        self._set_catalog(self._lib.bhr_set_stars, dirs, flux, max_magnification, max_span_deg)
+
+    def _set_catalog(self, setter, dirs, flux, max_magnification, max_span_deg) -> None:
+        """bhr_set_stars or bhr_set_kerr_stars with a checked catalogue."""
         from . import stars as stars_mod
         d, f = stars_mod.check_catalog(dirs, flux)
         rec = np.ascontiguousarray(np.concatenate([d, f], axis=1), dtype=np.float32)      # bhr_star: dir[3], flux[3]
         par = _lib.StarParams(float(max_magnification), float(max_span_deg))
-        _lib.check(self._lib.bhr_set_stars(self._ctx, rec.ctypes.data if len(rec) else None, len(rec), C.byref(par)))
+        _lib.check(setter(self._ctx, rec.ctypes.data if len(rec) else None, len(rec), C.byref(par)))
 
     def clear_stars(self) -> None:
         """Remove the star catalogue (bhr_set_stars with n = 0): every frame is again what it is without one."""
@@ -813,8 +817,11 @@ class HipRenderer:
     def stars_info(self) -> dict:
         """The catalogue (bhr_get_stars_info): n (0: none), bins_theta, bins_phi, max_magnification, max_span_deg, device_bytes,
         and of the last gather launched: images (deposits), capped and skipped_span (triangles)."""
+        return self._catalog_info(self._lib.bhr_get_stars_info)
+
+    def _catalog_info(self, getter) -> dict:
         info = _lib.StarsInfo()
-        _lib.check(self._lib.bhr_get_stars_info(self._ctx, C.byref(info)))
+        _lib.check(getter(self._ctx, C.byref(info)))
         out = {name: int(getattr(info, name)) for name in ("n", "bins_theta", "bins_phi", "device_bytes", "images", "capped", "skipped_span")}
         out["max_magnification"] = float(info.params.max_magnification)
         out["max_span_deg"] = float(info.params.max_span_deg)
@@ -833,6 +840,39 @@ class HipRenderer:
         turned view."""
         out = (C.c_int32 * 3)()
         _lib.check(self._lib.bhr_stars_resources(1 if turned else 0, out))
+        return {"vgprs": int(out[0]), "lds_bytes": int(out[1]), "scratch_bytes": int(out[2])}
+
+    # ------------------------------------------------------------------ Kerr point stars
+    def set_kerr_stars(self, dirs, flux, max_magnification: float = 32.0, max_span_deg: float = 10.0) -> None:
+        """Set the star catalogue the frames from the KERR ray map render as lensed points (bhr_set_kerr_stars; include/bhr.h
+        "Kerr point stars"): the arguments and the model of set_stars, read over the Kerr map's escape directions.  A catalogue of
+        its own beside set_stars', which every Kerr frame ignores -- as this one is ignored by everything but
+        render_from_kerr_ray_map_async and read_kerr_star_plane.  Shutter frames from the Kerr map and supersampled Kerr maps
+        refuse it; overflow pixels get no star light.  Synchronises."""
+        self._set_catalog(self._lib.bhr_set_kerr_stars, dirs, flux, max_magnification, max_span_deg)
+
+    def clear_kerr_stars(self) -> None:
+        """Remove the Kerr star catalogue (bhr_set_kerr_stars with n = 0): every Kerr map frame is again what it is without one."""
+        _lib.check(self._lib.bhr_set_kerr_stars(self._ctx, None, 0, None))
+
+    def kerr_stars_info(self) -> dict:
+        """The Kerr catalogue and its last gather (bhr_get_kerr_stars_info): the keys of stars_info."""
+        return self._catalog_info(self._lib.bhr_get_kerr_stars_info)
+
+    def read_kerr_star_plane(self) -> np.ndarray:
+        """The star plane of the Kerr ray map's build view, (rows, width, 3) float32 (bhr_kerr_raymap_read, BHR_RAYMAP_STARS):
+        what a frame from the Kerr map adds to its sky sample.  Gathered now if the map or the catalogue changed since."""
+        out = np.empty((self.rows, self.width, 3), dtype=np.float32)
+        _lib.check(self._lib.bhr_kerr_raymap_read(self._ctx, _lib.RAYMAP_STARS, out.ctypes.data, out.nbytes))
+        return out
+
+    def kerr_stars_resources(self, redshift: str = "model", turned: bool = False) -> dict:
+        """Registers, LDS bytes and scratch bytes of the Kerr map's STARS shade kernel of a redshift mode
+        (bhr_kerr_stars_resources); ``turned``: the one of a turned view."""
+        if redshift not in ("model", "exact"):
+            raise ValueError(f"redshift mode {redshift!r}: 'model' or 'exact'")
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_kerr_stars_resources(1 if redshift == "exact" else 0, 1 if turned else 0, out))
         return {"vgprs": int(out[0]), "lds_bytes": int(out[1]), "scratch_bytes": int(out[2])}
 
     # ------------------------------------------------------------------ polarisation

@@ -429,7 +429,8 @@ BHR_API int32_t bhr_raymap_free(bhr_ctx *ctx);
  * computed per frame into storage of the frame slot.  A view at angle 0 uses the cached plane and is bhr_raymap_render's frame
  * bit for bit.  Refused with BHR_ERR_STATE naming the stars, nothing launched, map and catalogue kept:
  * bhr_raymap_render_shutter, and any render from (or plane read of) a map with supersample > 1.  Without a catalogue every call is exactly what it
- * is without this section.  bhr_render, bhr_render_shutter, bhr_render_observer and the Kerr march IGNORE the catalogue.
+ * is without this section.  bhr_render, bhr_render_shutter, bhr_render_observer, the Kerr march and the Kerr ray map IGNORE the
+ * catalogue (the Kerr map has one of its own: bhr_set_kerr_stars, below).
  * bhr_raymap_read(ctx, BHR_RAYMAP_STARS, out, rows * W * 12) returns the build view's plane, computing it if needed;
  * BHR_ERR_STATE without a map or without a catalogue.
  * bhr_get_stars_info: the catalogue (n = 0: none) and the counts of the last gather launched -- images: deposits (star, used
@@ -660,8 +661,8 @@ BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, 
  * bit for bit.
  * bhr_kerr_raymap_read hands out BHR_RAYMAP_STEPS / _STATUS / _ESCAPE_DIR / _CROSSINGS as (rows, W[, 3]) and _HITS as
  * (K, rows, W, 5); bhr_kerr_raymap_info never fails for want of a map (built = 0 then); bhr_kerr_raymap_free is ordered behind
- * the frames in flight, and bhr_destroy releases the map.  The Schwarzschild map of the context, point stars and the
- * polarisation neither see nor are changed by any of these calls.
+ * the frames in flight, and bhr_destroy releases the map.  The Schwarzschild map of the context, its point stars (bhr_set_stars)
+ * and its polarisation neither see nor are changed by any of these calls.
  * Supersampled Kerr maps.  Option "kerr_raymap_supersample" (1, 2, 4 or 8; default 1) is the Kerr map's OWN factor k, read by
  * bhr_kerr_raymap_build as "raymap_slots" is; the map in memory keeps the factor it was built with, and a build with another
  * one reallocates.  ("raymap_supersample" stays the Schwarzschild map's and is refused here unless 1.)  The context's
@@ -712,7 +713,33 @@ BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, 
  * message names the sample index): BHR_ERR_INVALID; a Kerr polarisation being set (bhr_set_kerr_polarization: a mean of frames
  * has no Stokes planes): BHR_ERR_STATE.  bhr_render_shutter keeps refusing a spin and bhr_raymap_render_shutter a Kerr context:
  * this is the call for the combination.
- * Not available: point stars or a Kerr polarisation on a supersampled map, several devices.
+ * Kerr point stars (csrc/march_kerr_raymap.hip, csrc/api_stars.hip; DESIGN 4 "Kerr point stars").  The model is "point stars"
+ * above, word for word, read over the Kerr map: the cells and triangles T0 / T1 of the Kerr map's stored escape directions, the
+ * span rule, the Van Oosterom-Strackee solid angles, the difference form of the determinants, the cap at max_magnification, the
+ * bilinear deposit and the star plane S -- gathered by the same kernel (csrc/stars.hip) over the Kerr map's status and direction
+ * planes, from the camera-side pixel directions both marches launch their rays along.
+ * bhr_set_kerr_stars(ctx, stars, n, p) sets the Kerr map's OWN catalogue: bhr_set_stars' checks, binning, defaults, n = 0
+ * removal, whole-frame requirement, synchronisation and error codes, with this call's name in the messages.  It needs no spin.
+ * The two catalogues are independent: bhr_set_stars' is ignored by every Kerr frame, and this one by everything but
+ * bhr_kerr_raymap_render, bhr_kerr_raymap_render_view and bhr_kerr_raymap_read -- the Kerr march, bhr_render_kerr_observer and
+ * every Schwarzschild call neither read nor change it.  A context without a Kerr catalogue launches exactly what it launches
+ * without this paragraph.
+ * With one set, bhr_kerr_raymap_render and bhr_kerr_raymap_render_view launch the gather kernel and the Kerr STARS shade kernel:
+ * BG = fl(fl(sky_sample + S) * (1 - alpha_total)) per channel, the sky sample with the bits it has without a catalogue and the
+ * sum one f32 addition; DISK is untouched; a pixel on the map's overflow list is stored by the Kerr fix kernel as without a
+ * catalogue and receives NO star light.  The build view's plane is gathered once per (Kerr map, Kerr catalogue) -- a build, a
+ * free and a new catalogue invalidate it -- and a turned view's plane per frame into storage of the frame slot, on the frame's
+ * stream ahead of its march bracket, from the escape directions turned exactly as the Kerr shade kernel turns them.  A view at
+ * angle 0 takes the cached plane and the un-turned kernels: bhr_kerr_raymap_render's frame bit for bit.  A Kerr polarisation may
+ * be set at the same time: the Stokes pass runs behind the STARS shade and its planes do not depend on the catalogue.
+ * bhr_kerr_raymap_read(ctx, BHR_RAYMAP_STARS, out, rows * W * 12) returns the build view's plane, computing it if needed.
+ * bhr_get_kerr_stars_info: bhr_get_stars_info of this catalogue and its last gather.  bhr_kerr_stars_resources(exact, rot, out):
+ * VGPRs, LDS bytes and scratch bytes of the Kerr STARS shade kernel of the model (exact = 0) or exact redshift, plain or turned.
+ * Refused with BHR_ERR_STATE naming the stars, nothing launched, map and catalogue kept: bhr_kerr_raymap_render_shutter while a
+ * Kerr catalogue is set; a render, a view or a BHR_RAYMAP_STARS read from a map with "kerr_raymap_supersample" > 1 while one is
+ * set; a BHR_RAYMAP_STARS read without a Kerr catalogue (or without a map).  bhr_destroy frees both catalogues.
+ * Not available: point stars or a Kerr polarisation on a supersampled map, point stars in shutter frames, on overflow pixels, in
+ * marched Kerr frames and under the Kerr camera, several devices.
  *   BHR_ERR_STATE:  build without the Kerr march (no spin, not forced, no exact redshift): bhr_raymap_build is the call for a
  *                    hole that does not spin; render or read before a build (or after bhr_kerr_raymap_free); render while the
  *                    context's spin or redshift mode is no longer the build's (the message names both).
@@ -743,6 +770,9 @@ BHR_API int32_t bhr_kerr_raymap_read(bhr_ctx *ctx, int32_t plane, void *out, int
 BHR_API int32_t bhr_kerr_raymap_info(bhr_ctx *ctx, bhr_kerr_raymap_desc *out);
 BHR_API int32_t bhr_kerr_raymap_get_supersample(bhr_ctx *ctx, int32_t *k);
 BHR_API int32_t bhr_kerr_raymap_free(bhr_ctx *ctx);
+BHR_API int32_t bhr_set_kerr_stars(bhr_ctx *ctx, const bhr_star *stars, int32_t n, const bhr_star_params *p);
+BHR_API int32_t bhr_get_kerr_stars_info(bhr_ctx *ctx, bhr_stars_info *out);
+BHR_API int32_t bhr_kerr_stars_resources(int32_t exact, int32_t rot, int32_t out[3]);
 /* A moving observer: one frame as a camera sees it that moves through bhr_camera.pos with velocity beta (a 3-vector in units of
  * c, |beta| <= 0.995) as the static observer there measures it.  That observer's local frame is identified with the coordinate
  * axes, as the camera that stands still identifies it; the camera basis is the moving camera's own.  With n' the pixel's
