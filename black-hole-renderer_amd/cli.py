@@ -308,74 +308,25 @@ def parse_args(argv=None) -> argparse.Namespace:
     args = p.parse_args(argv)
     fov_given = args.fov is not None                # --projection refuses an explicit --fov; the default is 90 as ever
     args.fov = 90 if args.fov is None else args.fov
-    if args.shutter > 0 and not args.video:
-        p.error("--shutter needs --video: a still image is an instantaneous exposure")
-    if hasattr(args, "spin_shutter_map"):     # (no key without the flag, as for --spin_map)
-        # motion blur from the Kerr ray map (drivers.check_spin_shutter_map has these refusals): ahead of every other check, so that
-        # each names --spin_shutter_map
-        from . import drivers
-        view = kerr_view_from_args(args).get("kerr_view", {})
+    # What does not combine: the rows of rules.FEATURES, feature by feature in this order, so that a line refused without a flag is
+    # refused with the same words with it; between them the checks of a flag's own value.  Every refusal is an argparse error.
+    from . import drivers, rules
+    from .camera import orbit_position
+    f = facts_from_args(args, fov_given)
+
+    def refuse(features, surface="cli"):
         try:
-            drivers.check_spin_shutter_map(
-                True, spin=args.spin, redshift=args.redshift, video=args.video, shutter=args.shutter, spin_map=hasattr(args, "spin_map"),
-                ray_map=args.ray_map, orbit_map=args.orbit_map, shutter_map=args.shutter_map, supersample=args.supersample,
-                map_supersample=args.map_supersample, spin_polarization=hasattr(args, "spin_polarization"),
-                spin_observer=bool(view) and view.get("projection") is None and view.get("projection_fov") is None,
-                spin_projection=view.get("projection") is not None or view.get("projection_fov") is not None,
-                observer=any(v is not None for v in (args.observer, args.observer_velocity, args.observer_sky, args.infall_to)),
-                projection=args.projection != "perspective" or args.projection_fov is not None, light_delay=hasattr(args, "light_delay"),
-                stars=args.stars == "point",
-                # (its four companions count as --polarization's unless --spin_polarization, which they serve too, is there)
-                polarization=hasattr(args, "polarization") or (not hasattr(args, "spin_polarization") and any(
-                    hasattr(args, n) for n in ("polarization_fraction", "polarization_cell", "stokes_output", "polarization_ticks"))),
-                gpus=args.gpus)
+            rules.refuse_on(features, f, surface)
         except ValueError as e:
             p.error(str(e))
-    if hasattr(args, "spin_map_supersample"):     # (no key without the flag, likewise)
-        if not (hasattr(args, "spin_map") or hasattr(args, "spin_shutter_map")):
-            p.error("--spin_map_supersample needs --spin_map: it is the Kerr ray map's factor (marched frames take --supersample)")
-        if hasattr(args, "spin_polarization"):
-            p.error("--spin_map_supersample does not combine with --spin_polarization: the Stokes planes need a Kerr ray map with one ray per pixel")
-    if hasattr(args, "spin_map"):     # (the namespace of a line without the flag is what it was: no key)
-        # the Kerr ray map of a video (drivers.check_spin_map has the same refusals): ahead of a spin's own, so that each names --spin_map
-        if args.spin == 0 and args.redshift == "model":
-            p.error("--spin_map needs --spin or --redshift exact: it is the ray map of the Kerr march; a hole that does not spin takes "
-                    "--ray_map or --orbit_map")
-        if not args.video:
-            p.error("--spin_map needs --video: it is the ray map of a video")
-        if args.shutter > 0:
-            p.error("--spin_map does not combine with --shutter: shutter frames are marched")
-        if args.supersample != 1:
-            p.error("--spin_map does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
-        if args.map_supersample != 1:
-            p.error("--spin_map does not combine with --map_supersample other than 1: a Kerr ray map has no supersampled form")
-        if args.gpus != 1:
-            p.error("--spin_map does not combine with --gpus other than 1: a ray map lives on one GPU")
-        for flag, on in (("--ray_map", args.ray_map), ("--orbit_map", args.orbit_map), ("--shutter_map", args.shutter_map)):
-            if on:
-                p.error(f"--spin_map does not combine with {flag}: that is a map of Schwarzschild rays")
-        for flag, on in (("--observer", args.observer is not None), ("--observer_velocity", args.observer_velocity is not None),
-                         ("--observer_sky", args.observer_sky is not None), ("--infall_to", args.infall_to is not None),
-                         ("--projection", args.projection != "perspective" or args.projection_fov is not None),
-                         ("--light_delay", hasattr(args, "light_delay")), ("--stars point", args.stars == "point"),
-                         # (its four companions count as --polarization's unless --spin_polarization, which they serve too, is there)
-                         ("--polarization", hasattr(args, "polarization") or (not hasattr(args, "spin_polarization") and any(
-                             hasattr(args, n) for n in ("polarization_fraction", "polarization_cell", "stokes_output", "polarization_ticks"))))):
-            if on:
-                p.error(f"--spin_map does not combine with {flag}: it is a Schwarzschild march's or the Schwarzschild ray map's")
+    refuse("shutter")
+    refuse("spin_shutter_map", "api")             # (the drivers' words: ahead of every other check, so that each names --spin_shutter_map)
+    refuse("spin_map_supersample spin_map")       # ahead of a spin's own, so that each names --spin_map
     view = kerr_view_from_args(args)
     if view:
-        # the Kerr camera (drivers.check_kerr_view: the refusal table's row): ahead of a spin's own refusals, so that each names it
-        from . import drivers
-        from .camera import orbit_position
+        # the Kerr camera (the drivers' words): ahead of a spin's own refusals, so that each names it
         try:
-            checked = drivers.check_kerr_view(
-                view["kerr_view"], spin=args.spin, redshift=args.redshift, disk_tilt=args.disk_tilt, anti_alias=args.anti_alias,
-                disk_model=args.disk_model, supersample_threshold=args.supersample_threshold, gpus=args.gpus,
-                observer=any(v is not None for v in (args.observer, args.observer_velocity, args.observer_sky, args.infall_to)),
-                projection=args.projection != "perspective" or args.projection_fov is not None, light_delay=hasattr(args, "light_delay"),
-                passes=args.passes is not None, shutter=args.shutter, maps=args.ray_map or args.orbit_map or args.shutter_map,
-                stars=args.stars == "point", spin_map=hasattr(args, "spin_map") or hasattr(args, "spin_polarization"))
+            checked = drivers.checked("kerr_view", view["kerr_view"], f)
             if fov_given and checked["projection"] is not None:
                 raise ValueError(f"--spin_projection {checked['projection']} does not combine with --fov: that is the pinhole camera's "
                                  "field of view (--spin_projection_fov is this one's)")
@@ -384,63 +335,18 @@ def parse_args(argv=None) -> argparse.Namespace:
                                    if args.video and args.orbit else args.pov, args.spin)
         except ValueError as e:
             p.error(str(e))
-    if args.spin != 0 or args.redshift == "exact":
-        from .kerr import SPIN_MAX
-        # the Kerr march: asked for by a spin, or by the exact redshift at spin 0
-        who = "--spin" if args.spin != 0 else "--redshift exact (the Kerr march, as with --spin)"
+    if rules.FEATURES["spin"]["on"](f):             # the Kerr march: asked for by a spin, or by the exact redshift at spin 0
+        from .kerr import SPIN_MAX, camera_f, camera_outside_static_limit
         if not abs(args.spin) <= SPIN_MAX:
             p.error(f"--spin is a/M with |a/M| <= {SPIN_MAX}, got {args.spin}")
-        if args.disk_tilt != 0:
-            p.error(f"{who} does not combine with --disk_tilt other than 0: the spin axis is the disk normal")
-        if args.anti_alias != "disabled":
-            p.error(f"{who} does not combine with --anti_alias lod_radius: ray differentials around a spinning hole need Kerr's variational equations")
-        if args.disk_model != "texture":
-            p.error(f"{who} does not combine with --disk_model other than texture: the Kerr march shades the disk texture")
-        if args.supersample_threshold is not None:
-            p.error(f"{who} does not combine with --supersample_threshold: the Kerr march has no refinement kernels (plain --supersample works)")
-        if args.ray_map or args.orbit_map or args.shutter_map or args.passes is not None:
-            p.error(f"{who} does not combine with --ray_map, --orbit_map, --shutter_map or --passes: a ray map holds Schwarzschild rays")
-        if args.shutter > 0 and not hasattr(args, "spin_shutter_map"):     # (with it the samples come from the Kerr ray map)
-            p.error(f"{who} does not combine with --shutter: shutter frames march Schwarzschild rays")
-        if args.gpus != 1:
-            p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march Schwarzschild rays")
-        from .kerr import camera_f, camera_outside_static_limit
+        refuse("spin")
         if not camera_outside_static_limit(args.pov, args.spin):
+            who = rules.FEATURES["spin"]["words"]["who"](f)
             p.error(f"{who} needs --pov outside the static limit of the hole: at {args.pov} f = r / S = {camera_f(args.pov, args.spin)[0]:.4g} "
                     f"(f < 1 is needed: r > 1 in the disk plane), no static observer and no photon along every pixel direction there")
-    moving = args.observer is not None or args.observer_velocity is not None
-    if moving or args.observer_sky is not None or args.infall_to is not None:
+    if f["observer"]:
         from . import observer as obs
-        from .camera import orbit_position
-        who = "--observer" if args.observer is not None else "--observer_velocity" if args.observer_velocity is not None else \
-            "--observer_sky" if args.observer_sky is not None else "--infall_to"
-        if args.observer is not None and args.observer_velocity is not None:
-            p.error("--observer names a velocity and --observer_velocity gives one: take one of the two")
-        if not moving:
-            p.error(f"{who} needs --observer or --observer_velocity: it belongs to a camera that moves")
-        if args.spin != 0:
-            p.error(f"{who} does not combine with --spin: the observer march is Schwarzschild's")
-        if args.redshift == "exact":
-            p.error(f"{who} does not combine with --redshift exact: its observer is static")
-        if args.anti_alias != "disabled":
-            p.error(f"{who} does not combine with --anti_alias lod_radius: the differential seeds under aberration are not implemented")
-        if args.disk_model != "texture":
-            p.error(f"{who} does not combine with --disk_model other than texture: the observer march shades the disk texture")
-        if args.supersample_threshold is not None:
-            p.error(f"{who} does not combine with --supersample_threshold: the observer march has no refinement kernels (plain --supersample works)")
-        if args.gpus != 1:
-            p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march the camera that stands still")
-        if args.shutter > 0:
-            p.error(f"{who} does not combine with --shutter: shutter frames march the camera that stands still")
-        if args.ray_map or args.orbit_map or args.shutter_map or args.passes is not None:
-            p.error(f"{who} does not combine with --ray_map, --orbit_map, --shutter_map or --passes: a ray map holds the rays of the camera that stands still")
-        if args.infall_to is not None:
-            if args.observer != "infall":
-                p.error("--infall_to needs --observer infall: it is the path of the falling camera")
-            if not args.video:
-                p.error("--infall_to needs --video: a still image stays at --pov")
-            if args.orbit:
-                p.error("--infall_to does not combine with --orbit: the camera falls radially")
+        refuse("observer")
         try:
             if args.observer_velocity is not None:
                 obs.check_beta(args.observer_velocity)
@@ -453,280 +359,49 @@ def parse_args(argv=None) -> argparse.Namespace:
                 if args.infall_to is not None:
                     obs.velocity(args.observer, obs.frame_plan(2, args.pov, "infall", infall_to=args.infall_to)[-1][0])
         except ValueError as e:
-            p.error(f"{who}: {e}")
-    observer_flags = moving or args.observer_sky is not None or args.infall_to is not None
+            p.error(f"{rules.observer_flag(f)}: {e}")
     args.observer_sky = "shift" if args.observer_sky is None else args.observer_sky
-    if args.map_supersample > 1 and not (args.ray_map or args.orbit_map or args.shutter_map):
-        p.error("--map_supersample needs --ray_map, --orbit_map or --shutter_map: it is a ray map's factor (marched frames take --supersample)")
-    if args.shutter_map:
-        if not args.video:
-            p.error("--shutter_map needs --video: it is the ray map of a motion-blurred video")
-        if not args.shutter > 0:
-            p.error("--shutter_map needs --shutter > 0: an instantaneous exposure takes --ray_map or --orbit_map")
-        if args.ray_map:
-            p.error("--shutter_map does not combine with --ray_map: that is the map of an instantaneous exposure")
-        if args.orbit_map:
-            p.error("--shutter_map does not combine with --orbit_map: that is the map of an instantaneous exposure")
-        if args.orbit and args.disk_tilt != 0:
-            p.error("--shutter_map with --orbit needs --disk_tilt 0: the orbit is a symmetry of an untilted disk only")
-        if args.supersample != 1:
-            p.error("--shutter_map does not combine with --supersample other than 1: a ray map holds one ray per pixel")
-        if args.disk_model != "texture":
-            p.error("--shutter_map does not combine with --disk_model other than texture: a ray map shades the disk texture")
-        if args.gpus != 1:
-            p.error("--shutter_map does not combine with --gpus other than 1: a ray map lives on one GPU")
-    if args.orbit_map:
-        if not args.video:
-            p.error("--orbit_map needs --video: it is the ray map of an orbit video")
-        if not args.orbit:
-            p.error("--orbit_map needs --orbit: a camera that stands still takes --ray_map")
-        if args.ray_map:
-            p.error("--orbit_map does not combine with --ray_map: that is the map of a camera that stands still")
-        if args.disk_tilt != 0:
-            p.error("--orbit_map needs --disk_tilt 0: the orbit is a symmetry of an untilted disk only")
-        if args.shutter > 0:
-            p.error("--orbit_map does not combine with --shutter: shutter frames are marched")
-        if args.supersample != 1:
-            p.error("--orbit_map does not combine with --supersample other than 1: a ray map holds one ray per pixel")
-        if args.disk_model != "texture":
-            p.error("--orbit_map does not combine with --disk_model other than texture: a ray map shades the disk texture")
-        if args.gpus != 1:
-            p.error("--orbit_map does not combine with --gpus other than 1: a ray map lives on one GPU")
-    if args.ray_map:
-        if not args.video:
-            p.error("--ray_map needs --video: a still image is marched once anyway (--passes writes its ray map's passes)")
-        if args.orbit:
-            p.error("--ray_map does not combine with --orbit: a ray map is one view")
-        if args.shutter > 0:
-            p.error("--ray_map does not combine with --shutter: shutter frames are marched")
-        if args.supersample != 1:
-            p.error("--ray_map does not combine with --supersample other than 1: a ray map holds one ray per pixel")
-        if args.disk_model != "texture":
-            p.error("--ray_map does not combine with --disk_model other than texture: a ray map shades the disk texture")
-        if args.gpus != 1:
-            p.error("--ray_map does not combine with --gpus other than 1: a ray map lives on one GPU")
-    if args.video_hdr is None:
-        if args.hdr_white is not None:
-            p.error("--hdr_white needs --video_hdr pq: it is the display level of the PQ stream's scene value 1.0")
-        if args.hdr_exposure is not None:
-            p.error("--hdr_exposure needs --video_hdr: it is the exposure of the HDR stream")
-    else:
-        if not args.video:
-            p.error("--video_hdr needs --video: it is the HDR stream of a video (still images take --hdr_output)")
-        if args.video_hdr == "hlg" and args.hdr_white is not None:
-            p.error("--hdr_white is PQ's: HLG is scene-referred and places scene value 1.0 at its 75 % reference white")
-        if args.video_codec == "mjpeg":
-            p.error("--video_hdr does not combine with --video_codec mjpeg: that mode writes no stream")
-        if args.video_stream == "off":
-            p.error("--video_hdr is a video stream: it does not combine with --video_stream off")
+    refuse("map_supersample shutter_map orbit_map ray_map")
+    refuse("no_video_hdr video_hdr")
     args.hdr_white = 203.0 if args.hdr_white is None else args.hdr_white
     args.hdr_exposure = 0.0 if args.hdr_exposure is None else args.hdr_exposure
-    if args.passes is not None:
-        if args.video:
-            p.error("--passes writes the passes of a still image: it does not combine with --video")
-        if not args.passes.lower().endswith(".npz"):
-            p.error(f"--passes writes a .npz file, got {args.passes!r}")
-        if args.gpus != 1 or args.supersample != 1 or args.disk_model != "texture":
-            p.error("--passes needs one GPU, --supersample 1 and --disk_model texture: the passes come from a ray map")
-    # point stars, behind every refusal above: a line that was refused without --stars point is refused with the same words
+    refuse("passes stars")
     if args.stars == "point":
-        if args.texture is not None:
-            p.error("--stars point does not combine with --texture: a sky image has no catalogue")
-        if args.spin != 0 or args.redshift == "exact":
-            p.error("--stars point does not combine with --spin or --redshift exact: a ray map holds Schwarzschild rays")
-        if observer_flags:
-            p.error("--stars point does not combine with --observer, --observer_velocity, --observer_sky or --infall_to: a ray map holds "
-                    "the rays of the camera that stands still")
-        if args.video and not (args.ray_map or args.orbit_map or args.shutter_map):
-            p.error("--stars point with --video needs --ray_map or --orbit_map: point stars are rendered through a ray map")
-        if args.shutter_map:
-            p.error("--stars point does not combine with --shutter_map: shutter frames from the map have no point stars")
-        if args.map_supersample > 1:
-            p.error("--stars point does not combine with --map_supersample other than 1: point stars need a map with one ray per pixel")
-        if args.supersample != 1:
-            p.error("--stars point does not combine with --supersample other than 1: point stars need a map with one ray per pixel")
-        if args.gpus != 1:
-            p.error("--stars point does not combine with --gpus other than 1: a ray map lives on one GPU")
-        if args.disk_model != "texture":
-            p.error("--stars point does not combine with --disk_model other than texture: a ray map shades the disk texture")
         if not (args.star_gain > 0 and math.isfinite(args.star_gain)):
             p.error(f"--star_gain must be greater than 0, got {args.star_gain}")
         if not 1.0 <= args.star_max_magnification <= 1e6:
             p.error(f"--star_max_magnification must be between 1 and 1e6, got {args.star_max_magnification}")
-    # a projection, behind every refusal above: a line that was refused without --projection is refused with the same words
-    if args.projection == "perspective":
-        if args.projection_fov is not None:
-            p.error("--projection_fov needs --projection equirect or fisheye: it is the field of view of that camera (the pinhole takes --fov)")
-    else:
-        who = f"--projection {args.projection}"
-        if fov_given:
-            p.error(f"{who} does not combine with --fov: that is the pinhole camera's field of view (--projection_fov is this one's)")
-        if args.spin != 0:
-            p.error(f"{who} does not combine with --spin: the projected march is Schwarzschild's")
-        if args.redshift == "exact":
-            p.error(f"{who} does not combine with --redshift exact: that is the Kerr march's")
-        if args.anti_alias != "disabled":
-            p.error(f"{who} does not combine with --anti_alias lod_radius: the projected march has no ray differentials")
-        if args.disk_model != "texture":
-            p.error(f"{who} does not combine with --disk_model other than texture: the projected march shades the disk texture")
-        if args.supersample_threshold is not None:
-            p.error(f"{who} does not combine with --supersample_threshold: the projected march has no refinement kernels (plain --supersample works)")
-        if args.gpus != 1:
-            p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march the pinhole camera")
-        if args.shutter > 0:
-            p.error(f"{who} does not combine with --shutter: shutter frames march the pinhole camera")
-        for flag, on in (("--ray_map", args.ray_map), ("--orbit_map", args.orbit_map), ("--shutter_map", args.shutter_map),
-                         ("--passes", args.passes is not None)):
-            if on:
-                p.error(f"{who} does not combine with {flag}: a ray map holds the rays of the pinhole camera")
-        if args.stars == "point":
-            p.error(f"{who} does not combine with --stars point: point stars are rendered through a ray map of the pinhole camera")
+    refuse("projection")
+    if args.projection != "perspective":
         try:
             from .projection import check
             check(args.projection, args.projection_fov)
         except ValueError as e:
-            p.error(f"{who} --projection_fov: {e}")
-    # light delay, behind every refusal above: a line that was refused without --light_delay is refused with the same words.  The
-    # option has no default in the namespace: it is there only when the flag was given
-    delay = getattr(args, "light_delay", None)
-    if delay is not None:
-        who = "--light_delay"
-        if not 0.0 <= delay <= 16.0:               # a NaN fails the comparison too
-            p.error(f"{who} is a scale in [0, 16], got {delay}")
-        if args.anti_alias != "disabled":
-            p.error(f"{who} does not combine with --anti_alias lod_radius: the delayed march has no ray differentials")
-        if args.disk_model != "texture":
-            p.error(f"{who} does not combine with --disk_model other than texture: the delayed march shades the disk texture")
-        if args.supersample_threshold is not None:
-            p.error(f"{who} does not combine with --supersample_threshold: the delayed march has no refinement kernels (plain --supersample works)")
-        if args.gpus != 1:
-            p.error(f"{who} does not combine with --gpus other than 1: row-block tiles march without the light's travel time")
-        if args.spin != 0:
-            p.error(f"{who} does not combine with --spin: the delayed march is Schwarzschild's")
-        if args.redshift == "exact":
-            p.error(f"{who} does not combine with --redshift exact: that is the Kerr march's")
-        if observer_flags:
-            p.error(f"{who} does not combine with --observer, --observer_velocity, --observer_sky or --infall_to: the delayed march is "
-                    "the camera's that stands still")
-        if args.projection != "perspective":
-            p.error(f"{who} does not combine with --projection {args.projection}: the delayed march is the pinhole camera's")
-        if args.shutter > 0:
-            p.error(f"{who} does not combine with --shutter: shutter frames march without the light's travel time")
-        for flag, on in (("--ray_map", args.ray_map), ("--orbit_map", args.orbit_map), ("--shutter_map", args.shutter_map),
-                         ("--passes", args.passes is not None)):
-            if on:
-                p.error(f"{who} does not combine with {flag}: a ray map's records hold no travel time")
-        if args.stars == "point":
-            p.error(f"{who} does not combine with --stars point: point stars are rendered through a ray map, whose records hold no travel time")
-    # polarisation, behind every refusal above, light delay's included: a line that was refused without --polarization is refused
-    # with the same words.  Its five options have no default in the namespace: they are there only when the flag was given
+            p.error(f"--projection {args.projection} --projection_fov: {e}")
+    # the options from here on have no default in the namespace: they are there only when the flag was given
+    if hasattr(args, "light_delay"):
+        if not 0.0 <= args.light_delay <= 16.0:               # a NaN fails the comparison too
+            p.error(f"--light_delay is a scale in [0, 16], got {args.light_delay}")
+        refuse("light_delay")
     pol = getattr(args, "polarization", None)
     spin_pol = getattr(args, "spin_polarization", None)
     for flag in ("polarization_fraction", "polarization_cell", "stokes_output", "polarization_ticks"):
         if pol is None and spin_pol is None and getattr(args, flag, None) is not None:
             p.error(f"--{flag} needs --polarization: it belongs to the Stokes maps")
-    if pol is not None:
-        who = "--polarization"
-        from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check, parse_field
-        try:
-            check(parse_field(pol), getattr(args, "polarization_fraction", DEFAULT_FRACTION), getattr(args, "polarization_cell", DEFAULT_CELL))
-        except ValueError as e:
-            p.error(f"{who}: {e}")
-        if args.spin != 0:
-            p.error(f"{who} does not combine with --spin: the transport rule is Schwarzschild's and a ray map holds Schwarzschild rays")
-        if args.redshift == "exact":
-            p.error(f"{who} does not combine with --redshift exact: that is the Kerr march's")
-        if observer_flags:
-            p.error(f"{who} does not combine with --observer, --observer_velocity, --observer_sky or --infall_to: a ray map holds the rays "
-                    "of the camera that stands still")
-        if args.projection != "perspective":
-            p.error(f"{who} does not combine with --projection {args.projection}: a ray map holds the rays of the pinhole camera")
-        if delay is not None:
-            p.error(f"{who} does not combine with --light_delay: a ray map's records hold no travel time")
-        if args.orbit_map:
-            p.error(f"{who} does not combine with --orbit_map: the Stokes planes are the build view's, turned views have none")
-        if args.shutter_map:
-            p.error(f"{who} does not combine with --shutter_map: shutter frames from the map have no Stokes planes")
-        if args.shutter > 0:
-            p.error(f"{who} does not combine with --shutter: shutter frames are marched, the Stokes planes come from a ray map")
-        if args.map_supersample != 1:
-            p.error(f"{who} does not combine with --map_supersample other than 1: the Stokes planes need a map with one ray per pixel")
-        if args.supersample != 1:
-            p.error(f"{who} does not combine with --supersample other than 1: the Stokes planes need a map with one ray per pixel")
-        if args.disk_model != "texture":
-            p.error(f"{who} does not combine with --disk_model other than texture: a ray map shades the disk texture")
-        if args.gpus != 1:
-            p.error(f"{who} does not combine with --gpus other than 1: a ray map lives on one GPU")
-        if args.video and not args.ray_map:
-            p.error(f"{who} with --video needs --ray_map: the Stokes planes come from the ray map of a camera that stands still")
-        if args.video and getattr(args, "polarization_ticks", None) is not None:
-            p.error("--polarization_ticks is a still image's overlay: it does not combine with --video (the cell grids go to --stokes_output)")
-        if not getattr(args, "stokes_output", "x.npz").lower().endswith(".npz"):
-            p.error(f"--stokes_output writes a .npz file, got {args.stokes_output!r}")
-        if not getattr(args, "polarization_ticks", "x.png").lower().endswith(".png"):
-            p.error(f"--polarization_ticks writes a .png file, got {args.polarization_ticks!r}")
-    # the Kerr polarisation (drivers.check_kerr_polarization has the same refusals), behind --polarization's: each names --spin_polarization
-    if spin_pol is not None:
-        who = "--spin_polarization"
-        from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check, parse_field
-        try:
-            check(parse_field(spin_pol), getattr(args, "polarization_fraction", DEFAULT_FRACTION), getattr(args, "polarization_cell", DEFAULT_CELL))
-        except ValueError as e:
-            p.error(f"{who}: {e}")
-        if pol is not None:
-            p.error(f"{who} does not combine with --polarization: that is the hole that does not spin")
-        if args.spin == 0 and args.redshift == "model":
-            p.error(f"{who} needs --spin or --redshift exact: it is the polarisation of the Kerr march; a hole that does not spin takes --polarization")
-        if args.video and not hasattr(args, "spin_map"):
-            p.error(f"{who} with --video needs --spin_map: the Stokes planes come from the Kerr ray map")
-        if args.video and args.orbit:
-            p.error(f"{who} does not combine with --orbit: the Stokes planes are the build view's, turned views have none")
-        if args.shutter > 0:
-            p.error(f"{who} does not combine with --shutter: shutter frames are marched")
-        if args.supersample != 1 or args.supersample_threshold is not None:
-            p.error(f"{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
-        if args.map_supersample != 1:
-            p.error(f"{who} does not combine with --map_supersample other than 1: a Kerr ray map has no supersampled form")
-        if args.gpus != 1:
-            p.error(f"{who} does not combine with --gpus other than 1: a ray map lives on one GPU")
-        for flag, on in (("--ray_map", args.ray_map), ("--orbit_map", args.orbit_map), ("--shutter_map", args.shutter_map),
-                         ("--passes", args.passes is not None)):
-            if on:
-                p.error(f"{who} does not combine with {flag}: that is a map of Schwarzschild rays")
-        for flag, on in (("--observer, --observer_velocity, --observer_sky or --infall_to", bool(observer_flags)),
-                         ("--projection", args.projection != "perspective" or args.projection_fov is not None),
-                         ("--light_delay", hasattr(args, "light_delay")), ("--stars point", args.stars == "point")):
-            if on:
-                p.error(f"{who} does not combine with {flag}: it is a Schwarzschild march's or the Schwarzschild ray map's")
-        if args.disk_model != "texture":
-            p.error(f"{who} does not combine with --disk_model other than texture: a ray map shades the disk texture")
-        if args.video and getattr(args, "polarization_ticks", None) is not None:
-            p.error("--polarization_ticks is a still image's overlay: it does not combine with --video (the cell grids go to --stokes_output)")
-        if not getattr(args, "stokes_output", "x.npz").lower().endswith(".npz"):
-            p.error(f"--stokes_output writes a .npz file, got {args.stokes_output!r}")
-        if not getattr(args, "polarization_ticks", "x.png").lower().endswith(".png"):
-            p.error(f"--polarization_ticks writes a .png file, got {args.polarization_ticks!r}")
-    # the Kerr point stars and the Kerr passes (drivers.check_kerr_stars / check_kerr_passes have the same refusals), behind every
-    # refusal above: a line that was refused without them is refused with the same words.  Neither has a default in the namespace
-    if hasattr(args, "spin_stars") or hasattr(args, "spin_passes"):
-        from . import drivers
-        view = kerr_view_from_args(args).get("kerr_view", {})
-        spin_projection = view.get("projection") is not None or view.get("projection_fov") is not None
-        spin_observer = bool(view) and not spin_projection
-        try:
-            if hasattr(args, "spin_stars"):
-                drivers.check_kerr_stars(
-                    kerr_stars_from_args(args), spin=args.spin, redshift=args.redshift, skybox_path=args.texture, stars=args.stars == "point",
-                    supersample=args.supersample, spin_map_supersample=getattr(args, "spin_map_supersample", 1),
-                    spin_shutter_map=hasattr(args, "spin_shutter_map"), shutter=args.shutter, spin_observer=spin_observer,
-                    spin_projection=spin_projection, gpus=args.gpus, video=args.video, spin_map=hasattr(args, "spin_map"))
-                if spin_pol is not None:
-                    raise ValueError("--spin_stars does not combine with --spin_polarization on one command line: take one of the two")
-            if hasattr(args, "spin_passes"):
-                drivers.check_kerr_passes(args.spin_passes, spin=args.spin, redshift=args.redshift, supersample=args.supersample,
-                                          spin_observer=spin_observer, spin_projection=spin_projection, gpus=args.gpus, video=args.video)
-        except ValueError as e:
-            p.error(str(e))
+    for who, field, feature in (("--polarization", pol, "polarization"), ("--spin_polarization", spin_pol, "kerr_polarization")):
+        if field is not None:
+            from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check, parse_field
+            try:
+                check(parse_field(field), getattr(args, "polarization_fraction", DEFAULT_FRACTION), getattr(args, "polarization_cell", DEFAULT_CELL))
+            except ValueError as e:
+                p.error(f"{who}: {e}")
+            refuse(feature)
+    # the Kerr point stars and the Kerr passes (the drivers' words), behind every refusal above
+    try:
+        drivers.checked("kerr_stars", kerr_stars_from_args(args), f, "cli")
+    except ValueError as e:
+        p.error(str(e))
+    refuse("kerr_passes", "api")
     # --exposure, --white, --transfer and --hdr_output without --tonemap mean --tonemap clip
     if args.tonemap is None and any(v is not None for v in (args.exposure, args.white, args.transfer, args.hdr_output)):
         args.tonemap = "clip"
@@ -735,6 +410,33 @@ def parse_args(argv=None) -> argparse.Namespace:
         args.white = 2.5 if args.white is None else args.white
         args.transfer = "linear" if args.transfer is None else args.transfer
     return args
+
+
+def facts_from_args(args, fov_given: bool):
+    """What the rules look at (rules.FACTS), from the namespace of a command line.  A flag whose companions alone are given counts as
+    given, so that the refusal names the combination first: the observer's four, --projection_fov, the Kerr camera's five."""
+    from . import rules
+    view = kerr_view_from_args(args).get("kerr_view", {})
+    spin_projection = view.get("projection") is not None or view.get("projection_fov") is not None
+    spin_polarization = hasattr(args, "spin_polarization")
+    return rules.Facts(dict(
+        video=args.video, orbit=args.orbit, shutter=args.shutter, supersample=args.supersample, supersample_threshold=args.supersample_threshold,
+        map_supersample=args.map_supersample, spin_map_supersample=getattr(args, "spin_map_supersample", 1),
+        spin_map_supersample_given=hasattr(args, "spin_map_supersample"), gpus=args.gpus, disk_model=args.disk_model,
+        disk_tilt=args.disk_tilt, anti_alias=args.anti_alias, spin=args.spin, redshift=args.redshift, skybox_path=args.texture, fov_given=fov_given,
+        flag_observer=args.observer, flag_observer_velocity=args.observer_velocity, flag_observer_sky=args.observer_sky, flag_infall_to=args.infall_to,
+        observer=any(v is not None for v in (args.observer, args.observer_velocity, args.observer_sky, args.infall_to)),
+        projection=args.projection != "perspective" or args.projection_fov is not None, projection_name=args.projection,
+        light_delay=hasattr(args, "light_delay"), stars=args.stars == "point", kerr_polarization=spin_polarization,
+        # (its four companions count as --polarization's unless --spin_polarization, which they serve too, is there)
+        polarization=hasattr(args, "polarization") or (not spin_polarization and any(
+            hasattr(args, n) for n in ("polarization_fraction", "polarization_cell", "stokes_output", "polarization_ticks"))),
+        stokes_path=getattr(args, "stokes_output", None), ticks_path=getattr(args, "polarization_ticks", None),
+        spin_observer=bool(view) and not spin_projection, spin_projection=spin_projection, kerr_stars=hasattr(args, "spin_stars"),
+        passes=args.passes is not None, passes_path=args.passes, kerr_passes_path=getattr(args, "spin_passes", None), ray_map=args.ray_map,
+        orbit_map=args.orbit_map, shutter_map=args.shutter_map, spin_map=hasattr(args, "spin_map"), spin_shutter_map=hasattr(args, "spin_shutter_map"),
+        video_hdr=args.video_hdr, hdr_white_given=args.hdr_white is not None, hdr_exposure_given=args.hdr_exposure is not None, video_codec=args.video_codec,
+        video_stream=args.video_stream))
 
 
 def grade_from_args(args):
@@ -870,10 +572,8 @@ def validate_args(args) -> None:
             raise ValueError("--supersample_threshold needs --supersample 2, 4 or 8")
         if getattr(args, "gpus", 1) > 1:
             raise ValueError("--supersample_threshold renders on one GPU: it does not combine with --gpus > 1")
-    if getattr(args, "bit_depth", 8) == 16 and getattr(args, "dither", "none") != "none":
-        raise ValueError("--bit_depth 16 is not dithered: --dither blue applies to 8-bit output")
-    if getattr(args, "bit_depth", 8) == 16 and getattr(args, "video_codec", "auto") == "mjpeg":
-        raise ValueError("--bit_depth 16 does not combine with --video_codec mjpeg: JPEG frames are 8-bit")
+    from . import rules
+    rules.refuse_on("bit_depth_16", {name: getattr(args, name) for name in ("bit_depth", "dither", "video_codec") if hasattr(args, name)})
     if getattr(args, "bit_depth", 8) == 16 and not args.video and not args.output.lower().endswith(".png"):
         raise ValueError(f"--bit_depth 16 writes PNG files, got {args.output!r}")
     if not (0.0 <= getattr(args, "shutter", 0.0) <= 1.0):

@@ -19,6 +19,7 @@ from typing import List, Optional
 
 import numpy as np
 
+from . import rules
 from .camera import orbit_position
 from .lifecycle import make_factories
 from .output import Y4MStream, FrameSink, VIDEO_LEVEL, DEVICE, DITHERS, png_write, quantize, quantize16, write_passes
@@ -33,10 +34,7 @@ def check_depth_and_dither(bit_depth: int, dither: str, video_codec: str = "auto
         raise ValueError(f"bit_depth must be 8 or 16, got {bit_depth!r}")
     if dither not in DITHERS:
         raise ValueError(f"dither must be one of {DITHERS}, got {dither!r}")
-    if bit_depth == 16 and dither != "none":
-        raise ValueError("--bit_depth 16 is not dithered: --dither blue applies to 8-bit output")
-    if bit_depth == 16 and video_codec == "mjpeg":
-        raise ValueError("--bit_depth 16 does not combine with --video_codec mjpeg: JPEG frames are 8-bit")
+    rules.refuse_on("bit_depth_16", locals())
 
 
 def save_image(image: np.ndarray, path: str, bit_depth: int = 8, dither: str = "none") -> None:
@@ -192,110 +190,6 @@ def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, 
     return renderer, use_lifecycle, n_r, n_phi
 
 
-def check_stars(stars, skybox_path=None, supersample=1, spin: float = 0.0, redshift: str = "model", gpus: int = 1,
-                disk_model: str = "texture", observer=None):
-    """--stars point / stars=dict(gain=, max_magnification=): the procedural sky's stars as a catalogue of lensed points rendered
-    through a ray map.  -> the dict with its defaults filled in, or None.  Raises ValueError, naming the combination, for what
-    point stars do not take: a sky image (it has no catalogue), supersampling, several GPUs, Disk V2, a spin or the exact
-    redshift, a moving observer."""
-    if stars is None:
-        return None
-    from .stars import DEFAULT_MAX_MAGNIFICATION, DEFAULT_STAR_GAIN
-    out = {"gain": DEFAULT_STAR_GAIN, "max_magnification": DEFAULT_MAX_MAGNIFICATION}
-    unknown = set(stars) - set(out)
-    if unknown:
-        raise ValueError(f"stars takes gain and max_magnification, got {sorted(unknown)}")
-    out.update(stars)
-    if not (out["gain"] > 0 and np.isfinite(out["gain"])):
-        raise ValueError(f"star gain must be greater than 0, got {out['gain']}")
-    if not 1.0 <= out["max_magnification"] <= 1e6:
-        raise ValueError(f"star max_magnification must be between 1 and 1e6, got {out['max_magnification']}")
-    if skybox_path is not None:
-        raise ValueError("point stars do not combine with a sky texture: a sky image has no catalogue")
-    if supersample not in (None, 1):
-        raise ValueError("point stars do not combine with supersample > 1: they need a ray map with one ray per pixel")
-    if gpus != 1:
-        raise ValueError("point stars render on one GPU: a ray map lives on one GPU")
-    if disk_model != "texture":
-        raise ValueError("point stars do not combine with disk_model v2 / v2_volume: a ray map shades the disk texture")
-    if spin != 0 or redshift != "model":
-        raise ValueError("point stars do not combine with a spin or the exact redshift: a ray map holds Schwarzschild rays")
-    if observer is not None:
-        raise ValueError("point stars do not combine with a moving observer: a ray map holds the rays of the camera that stands still")
-    return out
-
-
-def check_kerr_stars(kerr_stars, spin: float = 0.0, redshift: str = "model", skybox_path=None, stars: bool = False, supersample=1,
-                     spin_map_supersample: int = 1, spin_shutter_map: bool = False, shutter: float = 0.0, spin_observer: bool = False,
-                     spin_projection: bool = False, gpus: int = 1, world: int = 1, video: bool = False, spin_map: bool = False):
-    """--spin_stars point / kerr_stars=dict(gain=, max_magnification=): the procedural sky's stars as a catalogue of lensed points
-    rendered through the KERR ray map of a spinning hole (HipRenderer.set_kerr_stars).  -> the dict with its defaults filled in,
-    or None.  It needs a spin or the exact redshift (the Kerr march); a still builds a Kerr ray map of the view, a video needs
-    spin_map.  Raises ValueError naming --spin_stars and the other flag, before any device work, for what Kerr point stars do not
-    take: a sky image (it has no catalogue), --stars point (the Schwarzschild map's), supersampling of the frame or of the Kerr
-    map, shutter frames, the Kerr camera, several GPUs or ranks, a video without spin_map."""
-    if kerr_stars is None:
-        return None
-    who = "--spin_stars"
-    from .stars import DEFAULT_MAX_MAGNIFICATION, DEFAULT_STAR_GAIN
-    out = {"gain": DEFAULT_STAR_GAIN, "max_magnification": DEFAULT_MAX_MAGNIFICATION}
-    unknown = set(kerr_stars) - set(out)
-    if unknown:
-        raise ValueError(f"{who} takes gain and max_magnification, got {sorted(unknown)}")
-    out.update(kerr_stars)
-    if not (out["gain"] > 0 and np.isfinite(out["gain"])):
-        raise ValueError(f"{who}: --star_gain must be greater than 0, got {out['gain']}")
-    if not 1.0 <= out["max_magnification"] <= 1e6:
-        raise ValueError(f"{who}: --star_max_magnification must be between 1 and 1e6, got {out['max_magnification']}")
-    if spin == 0 and redshift == "model":
-        raise ValueError(f"{who} needs --spin or --redshift exact: they are the point stars of the Kerr ray map; a hole that does not spin takes --stars point")
-    if skybox_path is not None:
-        raise ValueError(f"{who} does not combine with --texture: a sky image has no catalogue")
-    if stars:
-        raise ValueError(f"{who} does not combine with --stars point: that is the catalogue of the map of Schwarzschild rays")
-    if supersample not in (None, 1):
-        raise ValueError(f"{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
-    if spin_map_supersample != 1:
-        raise ValueError(f"{who} does not combine with --spin_map_supersample other than 1: point stars need a Kerr ray map with one ray per pixel")
-    if spin_shutter_map:
-        raise ValueError(f"{who} does not combine with --spin_shutter_map: shutter frames from the Kerr map have no point stars")
-    if shutter > 0:
-        raise ValueError(f"{who} does not combine with --shutter: shutter frames are marched, point stars are rendered through the Kerr ray map")
-    if spin_observer:
-        raise ValueError(f"{who} does not combine with --spin_observer: a Kerr ray map holds the rays of the camera at rest")
-    if spin_projection:
-        raise ValueError(f"{who} does not combine with --spin_projection: a Kerr ray map holds the rays of the pinhole camera")
-    if gpus != 1 or world != 1:
-        raise ValueError(f"{who} does not combine with --gpus other than 1 or several ranks: a ray map lives on one GPU")
-    if video and not spin_map:
-        raise ValueError(f"{who} with --video needs --spin_map: point stars are rendered through the Kerr ray map")
-    return out
-
-
-def check_kerr_passes(kerr_passes_path, spin: float = 0.0, redshift: str = "model", supersample=1, spin_observer: bool = False,
-                      spin_projection: bool = False, gpus: int = 1, video: bool = False) -> None:
-    """--spin_passes PATH.npz / kerr_passes_path: the geometry passes of a still under a spin, from a Kerr ray map of the view.
-    Raises ValueError naming --spin_passes and the other flag, before any device work: it needs a spin or the exact redshift and
-    a .npz path, and takes neither supersampling, the Kerr camera, several GPUs nor a video."""
-    if kerr_passes_path is None:
-        return
-    who = "--spin_passes"
-    if spin == 0 and redshift == "model":
-        raise ValueError(f"{who} needs --spin or --redshift exact: the passes come from the Kerr ray map; a hole that does not spin takes --passes")
-    if video:
-        raise ValueError(f"{who} writes the passes of a still image: it does not combine with --video")
-    if not str(kerr_passes_path).lower().endswith(".npz"):
-        raise ValueError(f"{who} writes a .npz file, got {kerr_passes_path!r}")
-    if supersample not in (None, 1):
-        raise ValueError(f"{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
-    if spin_observer:
-        raise ValueError(f"{who} does not combine with --spin_observer: a Kerr ray map holds the rays of the camera at rest")
-    if spin_projection:
-        raise ValueError(f"{who} does not combine with --spin_projection: a Kerr ray map holds the rays of the pinhole camera")
-    if gpus != 1:
-        raise ValueError(f"{who} does not combine with --gpus other than 1: a ray map lives on one GPU")
-
-
 def render_image(width: int, height: int, cam_pos: List[float], fov: float, step_size: float,
                  skybox_path: Optional[str] = None, n_stars: int = 6000, tex_w: int = 2048, tex_h: int = 1024,
                  r_max: float = 10.0, device: str = "hip", disk_texture_path: Optional[str] = None,
@@ -345,49 +239,36 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     for a still under a spin (check_kerr_passes): also builds the Kerr ray map of the view and writes its passes, the frame's bg /
     disk / blur layers, and the hole's spin and redshift there; the image itself is rendered as without it."""
     check_depth_and_dither(bit_depth, dither=dither)
-    kerr_view = check_kerr_view(kerr_view, spin=spin, redshift=redshift, disk_tilt=disk_tilt, anti_alias=anti_alias, disk_model=disk_model,
-                                supersample_threshold=supersample_threshold, gpus=gpus, observer=observer is not None,
-                                projection=projection is not None, light_delay=light_delay is not None, passes=passes_path is not None,
-                                stars=stars is not None, spin_map=kerr_polarization is not None)
+    # the facts of this call, built once; the features are refused in this order (rules.py has what each refuses)
+    f = rules.Facts(dict(
+        gpus=gpus, disk_model=disk_model, disk_tilt=disk_tilt, anti_alias=anti_alias, supersample=supersample, supersample_threshold=supersample_threshold,
+        spin=spin, redshift=redshift, skybox_path=skybox_path, observer=observer is not None, projection=projection is not None, projection_fov=projection_fov,
+        light_delay=light_delay is not None, stars=stars is not None, polarization=polarization is not None, kerr_polarization=kerr_polarization is not None,
+        kerr_stars=kerr_stars is not None, passes=passes_path is not None, passes_path=passes_path, kerr_passes_path=kerr_passes_path, stokes_path=stokes_path,
+        ticks_path=ticks_path, **_kerr_view_facts(kerr_view)))
+    kerr_view = checked("kerr_view", kerr_view, f)
     if kerr_view is not None:                                  # refused ahead of any device work, like the rest
         kerr_view_beta(kerr_view, cam_pos, spin)
-    facts = dict(anti_alias=anti_alias, disk_model=disk_model, supersample_threshold=supersample_threshold, gpus=gpus, spin=spin,
-                 redshift=redshift, passes=passes_path is not None)      # what the three variant checks take alike
-    check_light_delay(light_delay, observer=observer is not None, projection=projection is not None, stars=stars is not None, **facts)
-    check_projection(projection, projection_fov=projection_fov, stars=stars is not None, **facts)
-    stars = check_stars(stars, skybox_path=skybox_path, supersample=supersample, spin=spin, redshift=redshift, gpus=gpus,
-                        disk_model=disk_model, observer=observer)
-    check_observer(observer, **facts)
-    check_passes(passes_path, gpus=gpus, supersample=supersample, disk_model=disk_model)
+    checked("light_delay", light_delay, f)
+    checked("projection", projection, f)
+    stars = checked("stars", stars, f)
+    checked("observer", observer, f)
+    rules.refuse_on("passes", f)
     # ``kerr_polarization``: the same dict for a spinning hole (check_kerr_polarization): the view's KERR ray map is built with the
     # photon momenta and the frame is shaded from it, the Kerr Stokes pass behind the shade; stokes_path and ticks_path serve it too
-    kerr_polarization = check_kerr_polarization(kerr_polarization, polarization=polarization is not None, spin=spin, redshift=redshift,
-                                                supersample=supersample, supersample_threshold=supersample_threshold, gpus=gpus, disk_model=disk_model,
-                                                observer=observer is not None, projection=projection is not None, light_delay=light_delay is not None,
-                                                stars=stars is not None, passes=passes_path is not None, stokes_path=stokes_path, ticks_path=ticks_path)
+    kerr_polarization = checked("kerr_polarization", kerr_polarization, f)
     if kerr_polarization is None:
-        polarization = check_polarization(polarization, supersample=supersample, disk_model=disk_model, gpus=gpus, spin=spin, redshift=redshift,
-                                          observer=observer is not None, projection=projection is not None, light_delay=light_delay is not None,
-                                          stokes_path=stokes_path, ticks_path=ticks_path)
-    grade = check_grade(grade)
+        polarization = checked("polarization", polarization, f)
+    grade = f["grade"] = check_grade(grade)
     if hdr_path is not None:
         check_hdr_path(hdr_path)
         if grade is None:
             raise ValueError("hdr_path needs a grade: the HDR plane is written by the grading stage (tonemap 'clip' keeps the picture as it is)")
         grade["keep_hdr"] = True
-    if gpus > 1 and grade is not None:
-        raise ValueError("a grade renders on one GPU: row-block tiles store their rows from inside the V pass")
-    if gpus > 1 and supersample != 1:
-        raise ValueError("supersample > 1 renders on one GPU: row-block tiles march one ray per pixel")
-    if (spin != 0 or redshift != "model") and (gpus > 1 or passes_path is not None or disk_model != "texture"):
-        raise ValueError("a spin renders on one GPU with the texture disk source and writes no passes: row-block tiles, ray maps "
-                         "and Disk V2 are Schwarzschild's")
+    rules.refuse_on("tiles spin", f)
     # the Kerr point stars and the Kerr passes, behind every refusal above: each names --spin_stars / --spin_passes and the other flag
-    view_proj = kerr_view is not None and kerr_view["projection"] is not None
-    kerr_stars = check_kerr_stars(kerr_stars, spin=spin, redshift=redshift, skybox_path=skybox_path, stars=stars is not None, supersample=supersample,
-                                  spin_observer=kerr_view is not None and not view_proj, spin_projection=view_proj, gpus=gpus)
-    check_kerr_passes(kerr_passes_path, spin=spin, redshift=redshift, supersample=supersample, spin_observer=kerr_view is not None and not view_proj,
-                      spin_projection=view_proj, gpus=gpus)
+    kerr_stars = checked("kerr_stars", kerr_stars, f)
+    rules.refuse_on("kerr_passes", f)
     if gpus > 1:
         from .multigpu import render_image_tiled
         return render_image_tiled(width, height, cam_pos, fov, gpus, step_size=step_size, skybox_path=skybox_path,
@@ -431,14 +312,10 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     else:
         img = renderer.render(cam_pos, fov, frame=0, observer=observer, observer_sky=observer_sky, projection=projection,
                               projection_fov=projection_fov, light_delay=light_delay)
-    if stars is not None:
-        si = renderer.stars_info()
-        print(f"Point stars: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
-              f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
-    if kerr_stars is not None:
-        si = renderer.kerr_stars_info()
-        print(f"Kerr point stars: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
-              f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
+    for label, si in (("Point stars", stars and renderer.stars_info()), ("Kerr point stars", kerr_stars and renderer.kerr_stars_info())):
+        if si:
+            print(f"{label}: {si['n']} stars, {si['images']} images, {si['capped']} triangles capped at magnification "
+                  f"{si['max_magnification']:g}, {si['skipped_span']} over the span")
     if polarization is not None:
         from . import polarization as pol_mod
         planes, cells = renderer.stokes(), renderer.stokes_cells()
@@ -457,25 +334,22 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     if hdr_path is not None:
         save_hdr(renderer.read_hdr(), hdr_path)
     c = renderer.counters()
-    if passes_path is not None:
+    if passes_path is not None or kerr_passes_path is not None:          # (the checks have refused both at once: the passes of one map)
         from . import _lib
         layers = {"bg": renderer.read_layer(_lib.LAYER_BG), "disk": renderer.read_layer(_lib.LAYER_DISK),
                   "blur": renderer.read_layer(_lib.LAYER_BLUR)}
-        renderer.build_ray_map(cam_pos, fov)
-        write_passes(passes_path, renderer.ray_map_passes(), layers)
-        info = renderer.ray_map_info()
-        print(f"Saved: {passes_path} (ray map: {info['slots']} slots, {info['crossings_stored']} crossings, "
+        if passes_path is not None:
+            renderer.build_ray_map(cam_pos, fov)
+            passes, info, hole, label = renderer.ray_map_passes(), renderer.ray_map_info(), {}, "ray map"
+        else:
+            if not renderer.kerr_ray_map_info()["built"]:      # (a still with Kerr point stars or a Kerr polarisation came from the view's map)
+                renderer.build_kerr_ray_map(cam_pos, fov)
+            info, passes = renderer.kerr_ray_map_info(), renderer.kerr_ray_map_passes()
+            hole, label = {"hole": dict(spin=info["spin"], redshift=info["redshift"])}, f"Kerr ray map, spin {info['spin']:g}, {info['redshift']} redshift"
+        path = passes_path if passes_path is not None else kerr_passes_path
+        write_passes(path, passes, layers, **hole)
+        print(f"Saved: {path} ({label}: {info['slots']} slots, {info['crossings_stored']} crossings, "
               f"{info['overflow_pixels']} overflow pixels)")
-    if kerr_passes_path is not None:
-        from . import _lib
-        layers = {"bg": renderer.read_layer(_lib.LAYER_BG), "disk": renderer.read_layer(_lib.LAYER_DISK),
-                  "blur": renderer.read_layer(_lib.LAYER_BLUR)}
-        if not renderer.kerr_ray_map_info()["built"]:          # (a still with Kerr point stars or a Kerr polarisation came from the view's map)
-            renderer.build_kerr_ray_map(cam_pos, fov)
-        info = renderer.kerr_ray_map_info()
-        write_passes(kerr_passes_path, renderer.kerr_ray_map_passes(), layers, hole=dict(spin=info["spin"], redshift=info["redshift"]))
-        print(f"Saved: {kerr_passes_path} (Kerr ray map, spin {info['spin']:g}, {info['redshift']} redshift: {info['slots']} slots, "
-              f"{info['crossings_stored']} crossings, {info['overflow_pixels']} overflow pixels)")
     dt = time.time() - t0
     print(f"Done in {dt:.3f}s  (march {c['march_ms']:.2f} ms, bloom {c['bloom_ms']:.2f} ms, "
           f"{c['ray_steps'] / 1e6:.1f} Mray-steps, {c['ray_steps'] / max(c['march_ms'], 1e-6) / 1e3:.0f} Mray-steps/s)")
@@ -483,97 +357,57 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     return img
 
 
-# What a frame marched by a variant of the march -- a moving observer, a projection, light delay -- does not take.
-# _VARIANT_REFUSALS: every condition some variant refuses -- its name, whether the check's keywords ``f`` violate it, and the
-# refusal behind the variant's noun, with the variant's own words in braces.  _VARIANTS: per variant those words and the
-# conditions it refuses (an observer takes any ``world``: frame-sharded observer videos are legal).
-_VARIANT_REFUSALS = (
-    ("no_spin", lambda f: f["spin"] == 0 and f["redshift"] == "model",
-     "needs --spin or --redshift exact: it is the camera of the Kerr march; a hole that does not spin takes --observer and --projection"),
-    ("spin_map", lambda f: f["spin_map"], "does not combine with --spin_map or --spin_polarization: {map}"),
-    ("schwarzschild_marches", lambda f: f["observer"] or f["projection"] or f["light_delay"],
-     "does not combine with --observer, --projection or --light_delay: those marches are Schwarzschild's"),
-    ("disk_tilt", lambda f: f["disk_tilt"] != 0, "does not combine with disk_tilt other than 0: the spin axis is the disk normal"),
-    ("anti_alias", lambda f: f["anti_alias"] not in ("disabled", 0, False, None), "does not combine with anti_alias: {no_diff}"),
-    ("disk_model", lambda f: f["disk_model"] != "texture", "does not combine with disk_model v2 / v2_volume: the {march} march shades the disk texture"),
-    ("supersample_threshold", lambda f: f["supersample_threshold"] is not None,
-     "does not combine with supersample_threshold: the {march} march has no refinement kernels (plain supersample works)"),
-    ("gpus_or_world", lambda f: f["gpus"] != 1 or f["world"] != 1, "renders on one GPU: row-block tiles and frame-sharded ranks march {cam}"),
-    ("gpus", lambda f: f["gpus"] != 1, "renders on one GPU: row-block tiles march {cam}"),
-    ("world", lambda f: f["world"] != 1, "renders on one rank: frame-sharded ranks march {cam}"),
-    ("spin", lambda f: f["spin"] != 0 or f["redshift"] != "model",
-     "does not combine with a spin or the exact redshift: the {march} march is Schwarzschild's, {no_exact}"),
-    ("observer", lambda f: f["observer"], "does not combine with a moving observer: the {march} march is the camera's that stands still"),
-    ("projection", lambda f: f["projection"], "does not combine with a projection: the {march} march is the pinhole camera's"),
-    ("passes", lambda f: f["passes"], "writes no passes: {map}"),
-    ("shutter", lambda f: f["shutter"] > 0, "does not combine with shutter: shutter frames march {cam}"),
-    ("maps", lambda f: f["maps"], "does not combine with ray_map, orbit_map or shutter_map: {map}"),
-    ("stars", lambda f: f["stars"], "does not combine with point stars: they are rendered through a ray map{of_map}"),
-)
-_VARIANTS = {
-    "observer": dict(noun="a moving observer", march="observer", cam="the camera that stands still",
-                     no_diff="the differential seeds under aberration are not implemented", no_exact="the exact redshift's observer static",
-                     map="a ray map holds the rays of the camera that stands still",
-                     refuses="anti_alias disk_model supersample_threshold gpus spin passes shutter maps"),
-    "projection": dict(noun="a projection", march="projected", cam="the pinhole camera", no_diff="the projected march has no ray differentials",
-                       no_exact="with the model redshift", map="a ray map holds the rays of the pinhole camera", of_map=" of the pinhole camera",
-                       refuses="anti_alias disk_model supersample_threshold gpus_or_world spin passes shutter maps stars"),
-    "light_delay": dict(noun="light_delay", march="delayed", cam="without the light's travel time", no_diff="the delayed march has no ray differentials",
-                        no_exact="with the model redshift", map="a ray map's records hold no travel time", of_map=", whose records hold no travel time",
-                        refuses="anti_alias disk_model supersample_threshold gpus world spin observer projection passes shutter maps stars"),
-    # the Kerr camera (--spin_observer, --spin_projection and their companions; HipRenderer.render_async(kerr_observer=, kerr_projection=))
-    "kerr_view": dict(noun="--spin_observer / --spin_projection", march="Kerr", cam="Schwarzschild rays",
-                      no_diff="ray differentials around a spinning hole need Kerr's variational equations",
-                      map="a ray map holds the rays of the pinhole camera at rest", of_map=" of Schwarzschild rays",
-                      refuses="no_spin spin_map schwarzschild_marches disk_tilt anti_alias disk_model supersample_threshold gpus passes shutter maps stars"),
-}
+# ---- what may be rendered together --------------------------------------------------------------------------------------------------------
+# Every check_* below validates its feature's own value (_VALID) and then asks rules.py for the feature's refusals, with its keywords as
+# the facts; render_image and render_video build their facts once and go through checked() in their own order.  All of it raises
+# ValueError, naming the combination, before any device work.
+def _valid_points(who: str, gain: str, magnification: str):
+    def valid(points, f):
+        if points is None:
+            return None
+        from .stars import DEFAULT_MAX_MAGNIFICATION, DEFAULT_STAR_GAIN
+        out = {"gain": DEFAULT_STAR_GAIN, "max_magnification": DEFAULT_MAX_MAGNIFICATION}
+        unknown = set(points) - set(out)
+        if unknown:
+            raise ValueError(f"{who} takes gain and max_magnification, got {sorted(unknown)}")
+        out.update(points)
+        if not (out["gain"] > 0 and np.isfinite(out["gain"])):
+            raise ValueError(f"{gain} must be greater than 0, got {out['gain']}")
+        if not 1.0 <= out["max_magnification"] <= 1e6:
+            raise ValueError(f"{magnification} must be between 1 and 1e6, got {out['max_magnification']}")
+        return out
+    return valid
 
 
-def _check_variant(variant: str, f: dict) -> None:
-    """Raises ValueError for the first of the variant's refusals that the keywords ``f`` of its check violate."""
-    words = _VARIANTS[variant]
-    for condition, violated, refusal in _VARIANT_REFUSALS:
-        if condition in words["refuses"].split() and violated(f):
-            raise ValueError(f"{words['noun']} {refusal.format(**words)}")
+def _valid_stokes(who: str):
+    def valid(polarization, f):
+        if polarization is None:
+            if who == "polarization" and (f["stokes_path"] is not None or f["ticks_path"] is not None):
+                raise ValueError("stokes_output and polarization_ticks need a polarization: they are its outputs")
+            return None
+        from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check
+        unknown = set(polarization) - {"field", "fraction", "cell"}
+        if unknown or "field" not in polarization:
+            raise ValueError(f"{who} takes field, fraction and cell, got {sorted(polarization)}")
+        return check(polarization["field"], polarization.get("fraction", DEFAULT_FRACTION), polarization.get("cell", DEFAULT_CELL))
+    return valid
 
 
-def check_observer(observer, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None, gpus: int = 1,
-                   world: int = 1, spin: float = 0.0, redshift: str = "model", passes: bool = False, shutter: float = 0.0,
-                   maps: bool = False) -> None:
-    """What a frame of a moving observer takes: a velocity within |beta| <= 0.995, one device, the texture disk source, the
-    Schwarzschild hole with the model redshift, marched frames without anti-aliasing, adaptive supersampling, shutter or ray
-    map.  Raises ValueError before any device work; None: the camera stands still and nothing is checked."""
-    if observer is None:
-        return
+def _valid_observer(observer, f):
     from .observer import check_beta
-    check_beta(observer)
-    _check_variant("observer", locals())
+    return None if observer is None else check_beta(observer)
 
 
-def check_projection(projection, projection_fov=None, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None,
-                     gpus: int = 1, world: int = 1, spin: float = 0.0, redshift: str = "model", passes: bool = False, shutter: float = 0.0,
-                     maps: bool = False, stars: bool = False):
-    """What a frame under a projection takes (bhr_amd.projection.check: "equirect" or "fisheye" and its angles): one device, the
-    texture disk source, the Schwarzschild hole with the model redshift, marched frames without anti-aliasing, adaptive
-    supersampling, shutter, ray map or point stars -- the observer march's terms.  Raises ValueError, naming the combination,
-    before any device work; -> (kind, fov_h, fov_v), or None without a projection (``projection_fov`` alone is an error)."""
+def _valid_projection(projection, f):
     if projection is None:
-        if projection_fov is not None:
+        if f["projection_fov"] is not None:
             raise ValueError("projection_fov needs a projection: it is the field of view of an equirect or fisheye camera")
         return None
     from .projection import check
-    out = check(projection, projection_fov)
-    _check_variant("projection", locals())
-    return out
+    return check(projection, f["projection_fov"])
 
 
-def check_light_delay(scale, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None, gpus: int = 1,
-                      world: int = 1, spin: float = 0.0, redshift: str = "model", observer: bool = False, projection: bool = False,
-                      passes: bool = False, shutter: float = 0.0, maps: bool = False, stars: bool = False):
-    """What a frame with light delay takes: a scale in [0, 16], one device and one rank, the texture disk source, the
-    Schwarzschild hole with the model redshift, the pinhole camera that stands still, marched frames without anti-aliasing,
-    adaptive supersampling, shutter, ray map or point stars.  Raises ValueError, naming the combination, before any device work;
-    -> the scale as a float, or None without one (nothing is checked)."""
+def _valid_light_delay(scale, f):
     if scale is None:
         return None
     try:
@@ -582,21 +416,10 @@ def check_light_delay(scale, anti_alias="disabled", disk_model: str = "texture",
         raise ValueError(f"light_delay is a scale in [0, 16], got {scale!r}") from None
     if not 0.0 <= out <= 16.0:            # a NaN fails the comparison too
         raise ValueError(f"light_delay is a scale in [0, 16], got {scale!r}")
-    _check_variant("light_delay", locals())
     return out
 
 
-def check_kerr_view(kerr_view, spin: float = 0.0, redshift: str = "model", disk_tilt: float = 0.0, anti_alias="disabled",
-                    disk_model: str = "texture", supersample_threshold=None, gpus: int = 1, observer: bool = False, projection: bool = False,
-                    light_delay: bool = False, passes: bool = False, shutter: float = 0.0, maps: bool = False, stars: bool = False,
-                    spin_map: bool = False):
-    """kerr_view=dict(observer=, velocity=, sky=, projection=, projection_fov=): the Kerr camera of a spinning hole (--spin_observer
-    and its companions) -> the dict with its defaults filled in, or None without one.  ``observer``: "static", "circular" or
-    "zamo" (bhr_amd.observer.kerr_velocity) or ``velocity``: a fixed beta, one of the two at most; ``sky``: "shift" (default) or
-    "plain"; ``projection``: "equirect" or "fisheye" with ``projection_fov`` (bhr_amd.projection.check).  It needs a spin or the
-    exact redshift and takes what the Kerr march takes, on one GPU, marched: no Kerr ray map or Kerr polarisation, none of the
-    Schwarzschild marches, no shutter, ray map, passes or point stars.  Raises ValueError, naming the combination, before any
-    device work."""
+def _valid_kerr_view(kerr_view, f):
     if kerr_view is None:
         return None
     from . import observer as obs_mod
@@ -625,8 +448,92 @@ def check_kerr_view(kerr_view, spin: float = 0.0, redshift: str = "model", disk_
         out["projection_fov"] = (fov_h, fov_v) if out["projection"] == "equirect" else (fov_h,)
     if out["observer"] is None and out["velocity"] is None and out["projection"] is None:
         raise ValueError("kerr_view needs an observer, a velocity or a projection")
-    _check_variant("kerr_view", locals())
     return out
+
+
+_VALID = {
+    "stars": _valid_points("stars", "star gain", "star max_magnification"),
+    "kerr_stars": _valid_points("--spin_stars", "--spin_stars: --star_gain", "--spin_stars: --star_max_magnification"),
+    "polarization": _valid_stokes("polarization"), "kerr_polarization": _valid_stokes("--spin_polarization"),
+    "observer": _valid_observer, "projection": _valid_projection, "light_delay": _valid_light_delay, "kerr_view": _valid_kerr_view,
+}
+
+
+def checked(feature: str, value, facts, surface: str = "api"):
+    """A feature's value checked -> the value with its defaults filled in, or None without one (nothing is refused then): its own
+    validation, then the feature's refusals of rules.FEATURES against ``facts`` (a dict of rules.FACTS, or a rules.Facts)."""
+    f = facts if isinstance(facts, rules.Facts) else rules.Facts(facts)
+    out = _VALID[feature](value, f)
+    if value is not None:
+        rules.refuse(feature, f, surface)
+    return out
+
+
+def check_stars(stars, skybox_path=None, supersample=1, spin: float = 0.0, redshift: str = "model", gpus: int = 1,
+                disk_model: str = "texture", observer=None):
+    """--stars point / stars=dict(gain=, max_magnification=): the procedural sky's stars as a catalogue of lensed points rendered
+    through a ray map.  -> the dict with its defaults filled in, or None.  (``observer``: the camera's velocity, or None.)"""
+    return checked("stars", stars, dict(locals(), observer=observer is not None))
+
+
+def check_kerr_stars(kerr_stars, spin: float = 0.0, redshift: str = "model", skybox_path=None, stars: bool = False, supersample=1,
+                     spin_map_supersample: int = 1, spin_shutter_map: bool = False, shutter: float = 0.0, spin_observer: bool = False,
+                     spin_projection: bool = False, gpus: int = 1, world: int = 1, video: bool = False, spin_map: bool = False):
+    """--spin_stars point / kerr_stars=dict(gain=, max_magnification=): the procedural sky's stars as a catalogue of lensed points
+    rendered through the KERR ray map of a spinning hole (HipRenderer.set_kerr_stars).  -> the dict with its defaults filled in,
+    or None.  It needs a spin or the exact redshift (the Kerr march); a still builds a Kerr ray map of the view, a video needs
+    spin_map."""
+    return checked("kerr_stars", kerr_stars, locals())
+
+
+def check_kerr_passes(kerr_passes_path, spin: float = 0.0, redshift: str = "model", supersample=1, spin_observer: bool = False,
+                      spin_projection: bool = False, gpus: int = 1, video: bool = False) -> None:
+    """--spin_passes PATH.npz / kerr_passes_path: the geometry passes of a still under a spin, from a Kerr ray map of the view."""
+    if kerr_passes_path is not None:
+        rules.refuse("kerr_passes", locals())
+
+
+def check_observer(observer, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None, gpus: int = 1,
+                   world: int = 1, spin: float = 0.0, redshift: str = "model", passes: bool = False, shutter: float = 0.0,
+                   maps: bool = False) -> None:
+    """What a frame of a moving observer takes: a velocity within |beta| <= 0.995 and what rules.FEATURES["observer"] does not
+    refuse (an observer takes any ``world``: frame-sharded observer videos are legal).  None: the camera stands still and nothing
+    is checked."""
+    checked("observer", observer, locals())
+
+
+def check_projection(projection, projection_fov=None, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None,
+                     gpus: int = 1, world: int = 1, spin: float = 0.0, redshift: str = "model", passes: bool = False, shutter: float = 0.0,
+                     maps: bool = False, stars: bool = False):
+    """What a frame under a projection takes (bhr_amd.projection.check: "equirect" or "fisheye" and its angles) -- the observer
+    march's terms.  -> (kind, fov_h, fov_v), or None without a projection (``projection_fov`` alone is an error)."""
+    return checked("projection", projection, locals())
+
+
+def check_light_delay(scale, anti_alias="disabled", disk_model: str = "texture", supersample_threshold=None, gpus: int = 1,
+                      world: int = 1, spin: float = 0.0, redshift: str = "model", observer: bool = False, projection: bool = False,
+                      passes: bool = False, shutter: float = 0.0, maps: bool = False, stars: bool = False):
+    """What a frame with light delay takes: a scale in [0, 16], one device and one rank, the strict Schwarzschild march of the
+    pinhole camera that stands still.  -> the scale as a float, or None without one (nothing is checked)."""
+    return checked("light_delay", scale, locals())
+
+
+def check_kerr_view(kerr_view, spin: float = 0.0, redshift: str = "model", disk_tilt: float = 0.0, anti_alias="disabled",
+                    disk_model: str = "texture", supersample_threshold=None, gpus: int = 1, observer: bool = False, projection: bool = False,
+                    light_delay: bool = False, passes: bool = False, shutter: float = 0.0, maps: bool = False, stars: bool = False,
+                    spin_map: bool = False):
+    """kerr_view=dict(observer=, velocity=, sky=, projection=, projection_fov=): the Kerr camera of a spinning hole (--spin_observer
+    and its companions) -> the dict with its defaults filled in, or None without one.  ``observer``: "static", "circular" or
+    "zamo" (bhr_amd.observer.kerr_velocity) or ``velocity``: a fixed beta, one of the two at most; ``sky``: "shift" (default) or
+    "plain"; ``projection``: "equirect" or "fisheye" with ``projection_fov`` (bhr_amd.projection.check).  It needs a spin or the
+    exact redshift and takes what the Kerr march takes, on one GPU, marched (``spin_map``: a Kerr ray map or a Kerr polarisation)."""
+    return checked("kerr_view", kerr_view, dict(locals(), kerr_map=spin_map))
+
+
+def _kerr_view_facts(kerr_view) -> dict:
+    """The Kerr camera as the rules see it: one that moves, or one with a projection (which may move as well)."""
+    return dict(spin_observer=kerr_view is not None and kerr_view.get("projection") is None,
+                spin_projection=kerr_view is not None and kerr_view.get("projection") is not None)
 
 
 def kerr_view_beta(kerr_view: dict, pos, spin: float):
@@ -648,16 +555,8 @@ def _kerr_view_kw(kerr_view: dict, beta) -> dict:
 
 def check_passes(passes_path, gpus: int = 1, supersample: int = 1, disk_model: str = "texture") -> None:
     """What a still image with geometry passes takes: a .npz path, one device, one ray per pixel, the texture source."""
-    if passes_path is None:
-        return
-    if not str(passes_path).lower().endswith(".npz"):
-        raise ValueError(f"the passes are written as a .npz file, got {passes_path!r}")
-    if gpus != 1:
-        raise ValueError("the passes come from a ray map, which lives on one GPU: --passes does not combine with --gpus > 1")
-    if supersample != 1:
-        raise ValueError("a ray map holds one ray per pixel: --passes does not combine with --supersample > 1")
-    if disk_model != "texture":
-        raise ValueError("a ray map shades the disk texture: --passes does not combine with --disk_model v2 / v2_volume")
+    if passes_path is not None:
+        rules.refuse("passes", locals())
 
 
 def check_polarization(polarization, video: bool = False, ray_map: bool = False, orbit_map: bool = False, shutter_map: bool = False,
@@ -666,134 +565,8 @@ def check_polarization(polarization, video: bool = False, ray_map: bool = False,
                        light_delay: bool = False, stokes_path=None, ticks_path=None):
     """polarization=dict(field=, fraction=, cell=) (bhr_amd.polarization.check: a preset or three numbers, Pi_0 in [0, 1], a cell
     of 8, 16 or 32 pixels): Stokes Q / U maps of the disk, computed through a ray map of the view.  -> the dict with its defaults
-    filled in, or None without one (``stokes_path`` / ``ticks_path`` alone are an error).  Raises ValueError, naming the
-    combination, before any device work, for what polarization does not take: a spin or the exact redshift (the transport rule is
-    Schwarzschild's), a moving observer, a projection, light delay, the orbit and shutter maps, shutter, supersampling of the frame
-    or of the map, Disk V2, several GPUs or ranks, a video without ray_map, and outputs that are not .npz / .png."""
-    if polarization is None:
-        if stokes_path is not None or ticks_path is not None:
-            raise ValueError("stokes_output and polarization_ticks need a polarization: they are its outputs")
-        return None
-    from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check
-    unknown = set(polarization) - {"field", "fraction", "cell"}
-    if unknown or "field" not in polarization:
-        raise ValueError(f"polarization takes field, fraction and cell, got {sorted(polarization)}")
-    out = check(polarization["field"], polarization.get("fraction", DEFAULT_FRACTION), polarization.get("cell", DEFAULT_CELL))
-    if spin != 0 or redshift != "model":
-        raise ValueError("polarization does not combine with a spin or the exact redshift: the transport rule is Schwarzschild's and a ray map holds Schwarzschild rays")
-    if observer:
-        raise ValueError("polarization does not combine with a moving observer: a ray map holds the rays of the camera that stands still")
-    if projection:
-        raise ValueError("polarization does not combine with a projection: a ray map holds the rays of the pinhole camera")
-    if light_delay:
-        raise ValueError("polarization does not combine with light_delay: a ray map's records hold no travel time")
-    if orbit_map:
-        raise ValueError("polarization does not combine with orbit_map: the Stokes planes are the build view's, turned views have none")
-    if shutter_map:
-        raise ValueError("polarization does not combine with shutter_map: shutter frames from the map have no Stokes planes")
-    if shutter > 0:
-        raise ValueError("polarization does not combine with shutter: shutter frames are marched, the Stokes planes come from a ray map")
-    if map_supersample != 1:
-        raise ValueError("polarization does not combine with map_supersample > 1: the Stokes planes need a map with one ray per pixel")
-    if supersample not in (None, 1):
-        raise ValueError("polarization does not combine with supersample > 1: the Stokes planes need a map with one ray per pixel")
-    if disk_model != "texture":
-        raise ValueError("polarization does not combine with disk_model v2 / v2_volume: a ray map shades the disk texture")
-    if gpus != 1 or world != 1:
-        raise ValueError("polarization renders on one GPU: a ray map lives on one GPU")
-    if video and not ray_map:
-        raise ValueError("polarization in a video needs ray_map: the Stokes planes come from the ray map of a camera that stands still")
-    if video and ticks_path is not None:
-        raise ValueError("polarization_ticks is a still image's overlay: a video writes its cell grids to stokes_output")
-    if stokes_path is not None and not str(stokes_path).lower().endswith(".npz"):
-        raise ValueError(f"stokes_output is written as a .npz file, got {stokes_path!r}")
-    if ticks_path is not None and not str(ticks_path).lower().endswith(".png"):
-        raise ValueError(f"polarization_ticks is written as a .png file, got {ticks_path!r}")
-    return out
-
-
-# What a video from ONE ray map does not take.  _MAP_REFUSALS: every condition some map mode refuses -- whether the check's
-# keywords ``f`` violate it, and the refusal, with the mode's own words in braces.  _MAPS: per mode those words and the
-# conditions it refuses, in the order it names them (the first one violated is the one raised).
-_MAP_REFUSALS = {
-    "no_spin": (lambda f: f["spin"] == 0 and f["redshift"] == "model",
-                "{flag} needs --spin or --redshift exact: it is the ray map of the Kerr march; a hole that does not spin takes {plain}"),
-    "no_video": (lambda f: not f["video"], "{flag} needs --video: it is the ray map of {video}"),
-    "no_orbit": (lambda f: not f["orbit"], "{flag} needs --orbit: a camera that stands still takes --ray_map"),
-    "no_shutter": (lambda f: not f["shutter"] > 0, "{flag} needs --shutter > 0: an instantaneous exposure takes {instant}"),
-    "orbit": (lambda f: f["orbit"], "a ray map is one view: {flag} does not combine with --orbit"),
-    "ray_map": (lambda f: f["ray_map"], "{flag} does not combine with --ray_map: that is {other_map}"),
-    "orbit_map": (lambda f: f["orbit_map"], "{flag} does not combine with --orbit_map: that is {other_map}"),
-    "shutter_map": (lambda f: f["shutter_map"], "{flag} does not combine with --shutter_map: that is {other_map}"),
-    "spin_map": (lambda f: f["spin_map"], "{flag} does not combine with --spin_map: that is the map of an instantaneous exposure"),
-    "disk_tilt": (lambda f: f["disk_tilt"] != 0, "the orbit is a symmetry of an untilted disk only: {flag} needs --disk_tilt 0"),
-    "orbit_disk_tilt": (lambda f: f["orbit"] and f["disk_tilt"] != 0,
-                        "the orbit is a symmetry of an untilted disk only: {flag} with --orbit needs --disk_tilt 0"),
-    "shutter": (lambda f: f["shutter"] > 0, "shutter frames are marched: {flag} does not combine with --shutter"),
-    "supersample": (lambda f: f["supersample"] not in (None, 1), "{a_map} holds one ray per pixel: {flag} does not combine with --supersample > 1"),
-    "supersample_unset": (lambda f: f["supersample"] != 1, "{a_map} holds one ray per pixel: {flag} does not combine with --supersample > 1"),
-    "map_supersample": (lambda f: f["map_supersample"] != 1, "{a_map} has no supersampled form: {flag} does not combine with --map_supersample > 1"),
-    "disk_model": (lambda f: f["disk_model"] != "texture", "a ray map shades the disk texture: {flag} does not combine with --disk_model v2 / v2_volume"),
-    "gpus": (lambda f: f["gpus"] != 1 or f["world"] != 1, "a ray map lives on one GPU: {flag} does not combine with --gpus > 1 or several ranks"),
-    "observer": (lambda f: f["observer"], "{flag} does not combine with --observer: the observer march is Schwarzschild's"),
-    "projection": (lambda f: f["projection"], "{flag} does not combine with --projection: the projected march is Schwarzschild's"),
-    "light_delay": (lambda f: f["light_delay"], "{flag} does not combine with --light_delay: the delayed march is Schwarzschild's"),
-    "stars": (lambda f: f["stars"], "{flag} does not combine with --stars point: point stars are rendered through the map of Schwarzschild rays"),
-    "polarization": (lambda f: f["polarization"], "{flag} does not combine with --polarization: the transport rule is Schwarzschild's"),
-    "spin_polarization": (lambda f: f["spin_polarization"],
-                          "{flag} does not combine with --spin_polarization: shutter frames from the Kerr map have no Stokes planes"),
-    "spin_observer": (lambda f: f["spin_observer"], "{flag} does not combine with --spin_observer: a Kerr ray map holds the rays of the camera at rest"),
-    "spin_projection": (lambda f: f["spin_projection"], "{flag} does not combine with --spin_projection: a Kerr ray map holds the rays of the pinhole camera"),
-}
-_MAPS = {
-    "ray_map": dict(flag="--ray_map", a_map="a ray map", refuses="orbit shutter supersample disk_model gpus"),
-    "orbit_map": dict(flag="--orbit_map", a_map="a ray map", video="an orbit video", other_map="the map of a camera that stands still",
-                      refuses="no_video no_orbit ray_map disk_tilt shutter supersample disk_model gpus"),
-    "shutter_map": dict(flag="--shutter_map", a_map="a ray map", other_map="the map of an instantaneous exposure", instant="--ray_map or --orbit_map",
-                        refuses="no_shutter ray_map orbit_map orbit_disk_tilt supersample disk_model gpus"),
-    "spin_map": dict(flag="--spin_map", a_map="a Kerr ray map", video="a video", other_map="a map of Schwarzschild rays", plain="--ray_map or --orbit_map",
-                     refuses="no_spin no_video shutter supersample_unset map_supersample gpus ray_map orbit_map shutter_map "
-                             "observer projection light_delay stars polarization"),
-    "spin_shutter_map": dict(flag="--spin_shutter_map", a_map="a Kerr ray map", video="a motion-blurred video", other_map="a map of Schwarzschild rays",
-                             plain="--shutter_map", instant="--spin_map",
-                             refuses="no_spin no_video no_shutter spin_map ray_map orbit_map shutter_map supersample_unset map_supersample "
-                                     "spin_polarization spin_observer spin_projection observer projection light_delay stars polarization gpus"),
-}
-
-
-def _check_map(mode: str, f: dict) -> None:
-    """Raises ValueError for the first of the mode's refusals that the keywords ``f`` of its check violate."""
-    words = _MAPS[mode]
-    for condition in words["refuses"].split():
-        violated, refusal = _MAP_REFUSALS[condition]
-        if violated(f):
-            raise ValueError(refusal.format(**words))
-
-
-def check_ray_map(ray_map: bool, orbit: bool = False, shutter: float = 0.0, supersample=1, disk_model: str = "texture",
-                  gpus: int = 1, world: int = 1) -> None:
-    """What a video from a ray map takes: a camera that stands still, an instantaneous exposure, one ray per pixel, the
-    texture disk source, one GPU.  Raises ValueError before any device work."""
-    if ray_map:
-        _check_map("ray_map", locals())
-
-
-def check_orbit_map(orbit_map: bool, video: bool = True, orbit: bool = True, ray_map: bool = False, disk_tilt: float = 0.0,
-                    shutter: float = 0.0, supersample=1, disk_model: str = "texture", gpus: int = 1, world: int = 1) -> None:
-    """What an orbit video from ONE ray map takes: --video --orbit, a disk that is not tilted (the orbit's turn about z is then
-    a symmetry of everything a ray's path depends on), an instantaneous exposure, one ray per pixel, the texture disk source,
-    one GPU -- and not --ray_map, which is the map of a camera that stands still.  Raises ValueError before any device work."""
-    if orbit_map:
-        _check_map("orbit_map", locals())
-
-
-def check_shutter_map(shutter_map: bool, shutter: float = 0.5, orbit: bool = False, ray_map: bool = False, orbit_map: bool = False,
-                      disk_tilt: float = 0.0, supersample=1, disk_model: str = "texture", gpus: int = 1, world: int = 1) -> None:
-    """What a motion-blurred video from ONE ray map takes: an open shutter, one ray per pixel, the texture disk source, one GPU,
-    and under --orbit a disk that is not tilted (a camera that stands still takes any disk) -- and neither --ray_map nor
-    --orbit_map, which are the maps of instantaneous exposures.  Raises ValueError before any device work."""
-    if shutter_map:
-        _check_map("shutter_map", locals())
+    filled in, or None without one (``stokes_path`` / ``ticks_path`` alone are an error)."""
+    return checked("polarization", polarization, locals())
 
 
 def check_kerr_polarization(kerr_polarization, polarization: bool = False, video: bool = False, spin_map: bool = False, orbit: bool = False,
@@ -804,47 +577,34 @@ def check_kerr_polarization(kerr_polarization, polarization: bool = False, video
     """kerr_polarization=dict(field=, fraction=, cell=): Stokes Q / U maps of the disk of a SPINNING hole, carried along each ray
     by the Walker-Penrose constant (--spin_polarization; HipRenderer.set_kerr_polarization) -> the dict with its defaults filled
     in, or None without one.  It needs a spin or the exact redshift (the Kerr march); a still builds a Kerr ray map of the view,
-    a video needs spin_map and a camera that stands still.  Raises ValueError naming --spin_polarization and the other flag,
-    before any device work, for what a Kerr ray map does not take (check_spin_map) and for supersample > 1."""
-    if kerr_polarization is None:
-        return None
-    who = "--spin_polarization"
-    from .polarization import DEFAULT_CELL, DEFAULT_FRACTION, check
-    unknown = set(kerr_polarization) - {"field", "fraction", "cell"}
-    if unknown or "field" not in kerr_polarization:
-        raise ValueError(f"{who} takes field, fraction and cell, got {sorted(kerr_polarization)}")
-    out = check(kerr_polarization["field"], kerr_polarization.get("fraction", DEFAULT_FRACTION), kerr_polarization.get("cell", DEFAULT_CELL))
-    if polarization:
-        raise ValueError(f"{who} does not combine with --polarization: that is the hole that does not spin")
-    if spin == 0 and redshift == "model":
-        raise ValueError(f"{who} needs --spin or --redshift exact: it is the polarisation of the Kerr march; a hole that does not spin takes --polarization")
-    if video and not spin_map:
-        raise ValueError(f"{who} with --video needs --spin_map: the Stokes planes come from the Kerr ray map")
-    if video and orbit:
-        raise ValueError(f"{who} does not combine with --orbit: the Stokes planes are the build view's, turned views have none")
-    if video and ticks_path is not None:
-        raise ValueError("polarization_ticks is a still image's overlay: a video writes its cell grids to stokes_output")
-    if shutter > 0:
-        raise ValueError(f"{who} does not combine with --shutter: shutter frames are marched")
-    if supersample != 1 or supersample_threshold is not None:
-        raise ValueError(f"{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel")
-    if map_supersample != 1:
-        raise ValueError(f"{who} does not combine with --map_supersample other than 1: a Kerr ray map has no supersampled form")
-    if gpus != 1 or world != 1:
-        raise ValueError(f"{who} does not combine with --gpus other than 1: a ray map lives on one GPU")
-    for flag, on in (("--ray_map", ray_map), ("--orbit_map", orbit_map), ("--shutter_map", shutter_map), ("--passes", passes)):
-        if on:
-            raise ValueError(f"{who} does not combine with {flag}: that is a map of Schwarzschild rays")
-    for flag, on in (("--observer", observer), ("--projection", projection), ("--light_delay", light_delay), ("--stars point", stars)):
-        if on:
-            raise ValueError(f"{who} does not combine with {flag}: it is a Schwarzschild march's or the Schwarzschild ray map's")
-    if disk_model != "texture":
-        raise ValueError(f"{who} does not combine with --disk_model other than texture: a ray map shades the disk texture")
-    if stokes_path is not None and not str(stokes_path).lower().endswith(".npz"):
-        raise ValueError(f"stokes_output is written as a .npz file, got {stokes_path!r}")
-    if ticks_path is not None and not str(ticks_path).lower().endswith(".png"):
-        raise ValueError(f"polarization_ticks is written as a .png file, got {ticks_path!r}")
-    return out
+    a video needs spin_map and a camera that stands still."""
+    return checked("kerr_polarization", kerr_polarization, locals())
+
+
+def check_ray_map(ray_map: bool, orbit: bool = False, shutter: float = 0.0, supersample=1, disk_model: str = "texture",
+                  gpus: int = 1, world: int = 1) -> None:
+    """What a video from a ray map takes: a camera that stands still, an instantaneous exposure, one ray per pixel, the
+    texture disk source, one GPU."""
+    if ray_map:
+        rules.refuse("ray_map", locals())
+
+
+def check_orbit_map(orbit_map: bool, video: bool = True, orbit: bool = True, ray_map: bool = False, disk_tilt: float = 0.0,
+                    shutter: float = 0.0, supersample=1, disk_model: str = "texture", gpus: int = 1, world: int = 1) -> None:
+    """What an orbit video from ONE ray map takes: --video --orbit, a disk that is not tilted (the orbit's turn about z is then
+    a symmetry of everything a ray's path depends on), an instantaneous exposure, one ray per pixel, the texture disk source,
+    one GPU -- and not --ray_map, which is the map of a camera that stands still."""
+    if orbit_map:
+        rules.refuse("orbit_map", locals())
+
+
+def check_shutter_map(shutter_map: bool, shutter: float = 0.5, orbit: bool = False, ray_map: bool = False, orbit_map: bool = False,
+                      disk_tilt: float = 0.0, supersample=1, disk_model: str = "texture", gpus: int = 1, world: int = 1) -> None:
+    """What a motion-blurred video from ONE ray map takes: an open shutter, one ray per pixel, the texture disk source, one GPU,
+    and under --orbit a disk that is not tilted (a camera that stands still takes any disk) -- and neither --ray_map nor
+    --orbit_map, which are the maps of instantaneous exposures."""
+    if shutter_map:
+        rules.refuse("shutter_map", locals())
 
 
 def check_spin_map(spin_map: bool, spin: float = 0.0, redshift: str = "model", video: bool = True, shutter: float = 0.0, supersample=1,
@@ -854,9 +614,9 @@ def check_spin_map(spin_map: bool, spin: float = 0.0, redshift: str = "model", v
     """--spin_map is the Kerr ray map of a video (render_video): one march of a spinning hole's view, every frame shaded from it
     -- under --orbit turned about the spin axis to the frame's camera.  It needs a spin or the exact redshift (the Kerr march),
     a video, an instantaneous exposure, one ray per pixel and one GPU, and none of the Schwarzschild maps or of what a spin
-    refuses anyway.  Raises ValueError naming --spin_map and the other flag, before any device work."""
+    refuses anyway."""
     if spin_map:
-        _check_map("spin_map", locals())
+        rules.refuse("spin_map", locals())
 
 
 def check_spin_shutter_map(spin_shutter_map: bool, spin: float = 0.0, redshift: str = "model", video: bool = True, shutter: float = 0.5,
@@ -867,11 +627,9 @@ def check_spin_shutter_map(spin_shutter_map: bool, spin: float = 0.0, redshift: 
     """--spin_shutter_map is motion blur from ONE Kerr ray map (render_video): a spinning hole's view marched once, every sample of
     every exposure shaded from it -- the disk's roll and, under --orbit, the camera's turn about the spin axis are what the map
     leaves free.  It needs a spin or the exact redshift (the Kerr march), a video, an open shutter, one ray per pixel of the
-    context (--spin_map_supersample is the map's own factor) and one GPU, and none of --spin_map (the map of an instantaneous
-    exposure), the Schwarzschild maps, the Kerr polarisation, the Kerr camera or what a spin refuses anyway.  Raises ValueError
-    naming --spin_shutter_map and the other flag, before any device work."""
+    context (--spin_map_supersample is the map's own factor) and one GPU."""
     if spin_shutter_map:
-        _check_map("spin_shutter_map", locals())
+        rules.refuse("spin_shutter_map", dict(locals(), kerr_polarization=spin_polarization))
 
 
 # A video's map as render_video drives it: per mode the build of its one map, with the line it prints, the frame from it and the
@@ -1006,9 +764,7 @@ def check_map_supersample(k, ray_map: bool = False, orbit_map: bool = False, shu
     device work."""
     if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4, 8):
         raise ValueError(f"map_supersample must be 1, 2, 4 or 8, got {k!r}")
-    if k > 1 and not (ray_map or orbit_map or shutter_map):
-        raise ValueError("--map_supersample is a ray map's factor: it needs --ray_map, --orbit_map or --shutter_map "
-                         "(marched frames take --supersample)")
+    rules.refuse_on("map_supersample", rules.Facts(dict(locals(), map_supersample=k)))
 
 
 def check_spin_map_supersample(k, spin_map: bool = False, spin_polarization: bool = False, spin_shutter_map: bool = False) -> None:
@@ -1019,10 +775,7 @@ def check_spin_map_supersample(k, spin_map: bool = False, spin_polarization: boo
     device work."""
     if isinstance(k, bool) or not isinstance(k, int) or k not in (1, 2, 4, 8):
         raise ValueError(f"spin_map_supersample must be 1, 2, 4 or 8, got {k!r}")
-    if k > 1 and not (spin_map or spin_shutter_map):
-        raise ValueError("--spin_map_supersample is the Kerr ray map's factor: it needs --spin_map (marched frames take --supersample)")
-    if k > 1 and spin_polarization:
-        raise ValueError("--spin_map_supersample does not combine with --spin_polarization: the Stokes planes need a Kerr ray map with one ray per pixel")
+    rules.refuse_on("spin_map_supersample", rules.Facts(dict(locals(), spin_map_supersample=k, kerr_polarization=spin_polarization)))
 
 
 VIDEO_HDRS = ("pq", "hlg")
@@ -1041,14 +794,7 @@ def check_video_hdr(video_hdr, hdr_white=203.0, hdr_exposure=0.0, width: int = 2
         raise ValueError(f"video_hdr must be one of {VIDEO_HDRS}, got {video_hdr!r}")
     from .output import check_hdr
     hdr = check_hdr(dict(transfer=video_hdr, exposure=hdr_exposure, white_nits=hdr_white))
-    if world > 1:
-        raise ValueError("the HDR stream is written by one rank in frame order: --video_hdr does not combine with several ranks")
-    if video_codec == "mjpeg":
-        raise ValueError("--video_hdr does not combine with --video_codec mjpeg: that mode writes no stream")
-    if video_stream == "off":
-        raise ValueError("--video_hdr is a video stream: it does not combine with --video_stream off")
-    if width % 2 or height % 2:
-        raise ValueError(f"the HDR stream is 4:2:0 and needs even frame sizes, got {width}x{height}")
+    rules.refuse("video_hdr", locals())
     return hdr
 
 
@@ -1164,6 +910,9 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
+    What does not combine is refused with ValueError, naming the combination, before any device work: every feature below refuses
+    the rows of its entry in rules.FEATURES, in the order of the calls at the top of this function.
+
     ``video_stream``: the reference assembles the MP4 by reading every PNG back (render.py:4497-4503).  Here a
     single-rank, non-resumed session can also hand the frames straight to the encoder as a yuv420p YUV4MPEG2
     stream converted on the device (output.Y4MStream): "auto" pipes it into ``ffmpeg -f yuv4mpegpipe`` when an
@@ -1208,9 +957,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     ``ray_map=True`` (a camera that stands still): the view is marched ONCE, before the loop (HipRenderer.build_ray_map), and
     every frame is shaded from that map under the frame's texture (render_from_ray_map_async) instead of being marched again.
     The frames are the STRICT arithmetic's whatever the renderer's ``math``: byte for byte those of a math="strict" run
-    without the flag.  Refused with ValueError, before any device work, together with ``orbit``, ``shutter > 0``, a
-    supersampling factor other than 1, a Disk V2 source or several ranks.  The progress record carries ``ray_map`` when it
-    is set, and a resume with the other setting starts over.
+    without the flag.  The progress record carries ``ray_map`` when it is set, and a resume with the other setting starts over.
 
     ``orbit_map=True`` (with ``orbit``, a disk that is not tilted): ONE ray map serves the whole orbit.  The orbit turns the
     camera rigidly about z, which is a symmetry of the hole, the untilted disk and the escape sphere, so the rays of frame f are
@@ -1218,32 +965,28 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     is shaded from it turned to orbit_position(static_cam_pos, f, ...) (render_from_ray_map_async(cam_pos=...)).  Frame 0 is
     byte for byte the math="strict" frame; a later frame is the strict march of the SYMMETRIC rays, not byte-identical to the
     marched frame of its view: as far from it as two strict marches of symmetric views are from each other (f32 rounding of
-    the march, per-channel RMSE of a few 1e-5).  Refused with ValueError, before any device work, without ``orbit``, together
-    with ``ray_map``, ``shutter > 0``, a tilted disk, a supersampling factor other than 1, a Disk V2 source or several ranks.
-    The progress record carries ``orbit_map`` when it is set, and a resume with the other setting starts over.
+    the march, per-channel RMSE of a few 1e-5).  The progress record carries ``orbit_map`` when it is set, and a resume with the other setting starts over.
 
     ``spin_map=True`` (a renderer with a spin or the exact redshift): ONE Kerr ray map serves the whole video
     (HipRenderer.build_kerr_ray_map).  A camera that stands still: its view is marched once, before the loop, and every frame is
     shaded from the map (render_from_kerr_ray_map_async), bit for bit the marched frame.  With ``orbit``: the spin axis is z, so
     the orbit is an exact symmetry of everything a Kerr ray's path depends on; frame 0's view is marched once and every frame is
     shaded from the map turned to the frame's camera -- frame 0 is the marched frame, the others are as far from theirs as two
-    Kerr marches of symmetric views are from each other.  The map is freed at the end.  Refused with ValueError, before any
-    device work, with what check_spin_map names.  The progress record carries ``spin_map`` when it is set, and a resume with the
-    other setting starts over.
+    Kerr marches of symmetric views are from each other.  The map is freed at the end.  The progress record carries ``spin_map``
+    when it is set, and a resume with the other setting starts over.
 
     ``spin_map_supersample`` = k in {1, 2, 4, 8} (with ``spin_map=True``): the Kerr map's own factor
     (HipRenderer.build_kerr_ray_map(supersample=k)) -- k x k records per pixel, every frame from the map resolved with
     set_supersample's filter; with a camera that stands still the frames are byte for byte those of the marched video of a
     renderer with ``supersample=k``, and no march runs per frame.  ``supersample`` and ``map_supersample`` stay 1 with this map.
-    Refused with ValueError, before any device work, for another value, for k > 1 without ``spin_map`` and with
-    ``kerr_polarization`` (check_spin_map_supersample).  The progress record carries ``spin_map_supersample`` when it is above 1,
+    The progress record carries ``spin_map_supersample`` when it is above 1,
     and a resume with another factor starts over.
 
     ``spin_shutter_map=True`` (a renderer with a spin or the exact redshift, ``shutter > 0``): motion blur from ONE Kerr ray map
     -- ``shutter_map`` for the spinning hole.  The map is built once (frame 0's view under ``orbit``, else ``static_cam_pos``; with
     ``spin_map_supersample`` = k its own factor) and every frame is render_shutter_from_kerr_ray_map_async of exactly the sample
-    times, positions and t_offsets the ``shutter_map`` loop hands render_shutter_from_ray_map_async; no sample is marched.  Refused
-    with ValueError, before any device work, with what check_spin_shutter_map names.  The progress record carries
+    times, positions and t_offsets the ``shutter_map`` loop hands render_shutter_from_ray_map_async; no sample is marched.
+    The progress record carries
     ``spin_shutter_map`` when it is set, and a resume with the other setting starts over.
 
     ``shutter_map=True`` (with ``shutter > 0``): motion blur from ONE ray map.  What differs between the samples of an exposure
@@ -1253,14 +996,11 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     render_shutter_async.  The bg and disk layers are the STRICT arithmetic's whatever the renderer's ``math``, the post-pass is
     the renderer's own (exact f32 under math="strict", split f16 under fast / hybrid).  With a camera that stands still and
     math="strict" the frames are byte for byte those of the shutter video without the flag; under ``orbit`` they are the means
-    of orbit-map frames (see above).  Refused with ValueError, before any device work, with ``shutter == 0``, together with ``ray_map`` or
-    ``orbit_map``, with ``orbit`` over a tilted disk, a supersampling factor other than 1, a Disk V2 source or several ranks.
-    The progress record carries ``shutter_map`` when it is set, and a resume with the other setting starts over.
+    of orbit-map frames (see above).  The progress record carries ``shutter_map`` when it is set, and a resume with the other setting starts over.
 
     ``map_supersample`` = k in {1, 2, 4, 8}: the factor of the one map the three modes above build
     (HipRenderer.build_ray_map(supersample=k)) -- k x k records per pixel, every frame from the map resolved with
-    set_supersample's filter; ``supersample`` itself stays 1 with a map.  Refused with ValueError, before any device work, for
-    another value or for k > 1 without one of the three maps (check_map_supersample).  The progress record carries
+    set_supersample's filter; ``supersample`` itself stays 1 with a map.  The progress record carries
     ``map_supersample`` when it is above 1, and a resume with another factor starts over.
 
     ``video_hdr`` = "pq" or "hlg": the loop's stream is the HDR one (output.Y4MStream(hdr=...); include/bhr_output.h states the
@@ -1280,86 +1020,57 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     camera moves.  Every frame is render_async(..., observer=beta_f, observer_sky=...) with the named velocity evaluated at
     that frame's own camera position (bhr_amd.observer.frame_plan), so an ``orbit`` with "circular" is the view from the
     orbiting camera.  ``infall_to`` = R (with "infall", without ``orbit``) moves the camera radially from |static_cam_pos| to R
-    along static_cam_pos, uniformly in the falling observer's proper time.  Refused with ValueError, before any device work, with
-    both given, ``shutter > 0``, a ray map, anti-aliasing, a Disk V2 source, adaptive supersampling or a spin.  The progress
+    along static_cam_pos, uniformly in the falling observer's proper time.  The progress
     record carries the observer's settings when one is given, and a resume with others starts over.
 
     ``projection`` ("equirect" or "fisheye") with ``projection_fov``: every frame is render_async(..., projection=...) -- the
     width x height frames through that camera instead of the pinhole, ``fov`` unused -- from the moving camera when an observer
-    is given as well.  Refused with ValueError, before any device work, with what check_projection names.  The progress record
+    is given as well.  The progress record
     carries the projection when one is given, and a resume under another starts over.  A full-sphere equirect video muxed by
     this package (Motion-JPEG, PNG-in-MP4) carries the Spherical Video V1 box (assemble_video).
 
     ``light_delay`` (a scale in [0, 16]): every frame is render_async(..., light_delay=scale) with the frame's own camera
-    position and t_offset, with and without ``orbit`` -- each disk crossing shaded at the time its light left the gas.  Refused
-    with ValueError, before any device work, with what check_light_delay names.  The progress record carries the scale when one
+    position and t_offset, with and without ``orbit`` -- each disk crossing shaded at the time its light left the gas.
+    The progress record carries the scale when one
     is given, and a resume under another starts over.
 
     ``polarization`` (dict(field=, fraction=, cell=); needs ``ray_map=True``): every frame from the map is followed by the Stokes
     pass (HipRenderer.set_polarization), and the frames' cell grids -- never the full planes -- are collected into ONE compressed
     .npz at ``stokes_path`` (default ``<output stem>.stokes.npz``) with ``cells`` of shape (n_frames, gh, gw, 3).  Refused with
-    ValueError, before any device work, with what check_polarization names, and with a resume that finds frames already rendered
-    (their grids are gone).  The renderer's polarisation is switched off on return.  The progress record names the polarisation
+    a resume that finds frames already rendered (their grids are gone).  The renderer's polarisation is switched off on return.  The progress record names the polarisation
     only when it is set.
 
     ``kerr_view`` (check_kerr_view's dict; the renderer has a spin or the exact redshift set): every frame is
     render_async(..., kerr_observer=beta_f, kerr_projection=...) -- the Kerr march through the Kerr camera, with the named velocity
     evaluated at that frame's own camera position (bhr_amd.observer.kerr_frame_plan), so an ``orbit`` with "circular" is the
-    fly-around on the equatorial geodesic.  Refused with ValueError, before any device work, with what check_kerr_view names.  The
-    progress record carries the camera when one is given, and a resume under another starts over."""
-    # the Kerr map's own factor: refused first, before the renderer is asked anything
-    check_spin_map_supersample(spin_map_supersample, spin_map=spin_map, spin_polarization=kerr_polarization is not None,
-                               **({"spin_shutter_map": True} if spin_shutter_map else {}))
-    if spin_shutter_map:
-        # motion blur from the Kerr map: ahead of every other check, so that each refusal names it -- first what the call itself
-        # says, before the renderer is asked anything, then with the renderer's spin, redshift and supersampling
-        said = dict(video=True, shutter=shutter, spin_map=spin_map, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map,
-                    map_supersample=map_supersample, spin_polarization=kerr_polarization is not None,
-                    spin_observer=kerr_view is not None and kerr_view.get("projection") is None,
-                    spin_projection=kerr_view is not None and kerr_view.get("projection") is not None,
-                    observer=observer is not None or observer_velocity is not None or infall_to is not None,
-                    projection=projection is not None or projection_fov is not None, light_delay=light_delay is not None,
-                    stars=stars is not None, polarization=polarization is not None or (stokes_path is not None and kerr_polarization is None),
-                    world=world)
-        check_spin_shutter_map(True, spin=1.0, supersample=1 if supersample is None else supersample, **said)
-        check_spin_shutter_map(True, spin=renderer.spin, redshift=renderer.redshift,
-                               supersample=renderer.supersample if supersample is None else supersample, **said)
-    kerr_plan = None
-    if kerr_view is not None:                                   # (without one the renderer is not asked anything, as ever)
-        from . import observer as obs_mod
-        kerr_view = check_kerr_view(kerr_view, spin=renderer.spin, redshift=renderer.redshift, disk_tilt=renderer.disk_tilt,
-                                    anti_alias=renderer.anti_alias, disk_model="texture" if getattr(renderer, "_dv2", None) is None else "v2",
-                                    supersample_threshold=supersample_threshold if supersample is not None or supersample_threshold is not None
-                                    else getattr(renderer, "supersample_threshold", None),
-                                    observer=observer is not None or observer_velocity is not None or infall_to is not None,
-                                    projection=projection is not None or projection_fov is not None, light_delay=light_delay is not None,
-                                    shutter=shutter, maps=ray_map or orbit_map or shutter_map, stars=stars is not None,
-                                    spin_map=spin_map or kerr_polarization is not None)
-        if kerr_view["observer"] is not None or kerr_view["velocity"] is not None:
-            kerr_plan = obs_mod.kerr_frame_plan(n_frames, static_cam_pos, renderer.spin, kerr_view["observer"], kerr_view["velocity"], orbit, orbit_degrees)
+    fly-around on the equatorial geodesic.  The progress record carries the camera when one is given, and a resume under another starts over."""
+    # the facts of this call, built once: what the call says, and what the renderer is set to -- which is read when the first rule asks
+    # for it and not before (without a feature that needs them the renderer is not asked anything, as ever)
     moving = observer is not None or observer_velocity is not None or infall_to is not None
-    projected = projection is not None or projection_fov is not None
-    disk_model = "texture" if getattr(renderer, "_dv2", None) is None else "v2"
-    if spin_map:                                                # (without it the renderer is not asked anything, as ever)
-        check_spin_map(spin_map, spin=renderer.spin, redshift=renderer.redshift, video=True, shutter=shutter,
-                       supersample=renderer.supersample if supersample is None else supersample, map_supersample=map_supersample, world=world,
-                       ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map, observer=moving, projection=projected,
-                       light_delay=light_delay is not None, stars=stars is not None,
-                       polarization=polarization is not None or (stokes_path is not None and kerr_polarization is None))
+    f = rules.Facts(dict(
+        video=True, orbit=orbit, shutter=shutter, world=world, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map, spin_map=spin_map,
+        spin_shutter_map=spin_shutter_map, map_supersample=map_supersample, spin_map_supersample=spin_map_supersample, supersample_said=supersample,
+        observer=moving, projection=projection is not None or projection_fov is not None, projection_fov=projection_fov, light_delay=light_delay is not None,
+        stars=stars is not None, kerr_polarization=kerr_polarization is not None, kerr_stars=kerr_stars is not None, stokes_path=stokes_path,
+        # (stokes_path alone counts as polarization's unless kerr_polarization, which it serves too, is there)
+        polarization=polarization is not None or (stokes_path is not None and kerr_polarization is None), **_kerr_view_facts(kerr_view),
+        spin=lambda f: renderer.spin, redshift=lambda f: renderer.redshift, disk_tilt=lambda f: renderer.disk_tilt, anti_alias=lambda f: renderer.anti_alias,
+        disk_model=lambda f: "texture" if getattr(renderer, "_dv2", None) is None else "v2",
+        supersample=lambda f: renderer.supersample if supersample is None else supersample,
+        supersample_threshold=lambda f: supersample_threshold if supersample is not None or supersample_threshold is not None
+        else getattr(renderer, "supersample_threshold", None)))
+    # the features are refused in this order (rules.py has what each refuses); the Kerr map's own factor first, then motion blur from
+    # the Kerr map, so that each refusal names it
+    check_spin_map_supersample(spin_map_supersample, spin_map=spin_map, spin_polarization=f["kerr_polarization"], spin_shutter_map=spin_shutter_map)
+    rules.refuse_on("spin_shutter_map", f, "video")
+    kerr_view, kerr_plan = checked("kerr_view", kerr_view, f, "video"), None
+    if kerr_view is not None and (kerr_view["observer"] is not None or kerr_view["velocity"] is not None):
+        from . import observer as obs_mod
+        kerr_plan = obs_mod.kerr_frame_plan(n_frames, static_cam_pos, renderer.spin, kerr_view["observer"], kerr_view["velocity"], orbit, orbit_degrees)
+    rules.refuse_on("spin_map", f, "video")
     # ``kerr_polarization`` (needs ``spin_map=True`` and no ``orbit``): polarization's outputs for a spinning hole -- set ahead of
     # the map's build, which then keeps the photon momenta; every frame's cell grid is collected into the one .npz
-    if kerr_polarization is not None:                           # (without one the renderer is not asked anything, as ever)
-        kerr_polarization = check_kerr_polarization(kerr_polarization, polarization=polarization is not None, video=True, spin_map=spin_map,
-                                                    orbit=orbit, spin=renderer.spin, redshift=renderer.redshift, shutter=shutter,
-                                                    supersample=renderer.supersample if supersample is None else supersample,
-                                                    map_supersample=map_supersample, world=world, disk_model=disk_model, ray_map=ray_map,
-                                                    orbit_map=orbit_map, shutter_map=shutter_map, observer=moving, projection=projected,
-                                                    light_delay=light_delay is not None, stars=stars is not None, stokes_path=stokes_path)
-    if moving or projected or light_delay is not None:
-        # what the three variant checks take from the renderer and the call
-        thr = supersample_threshold if supersample is not None or supersample_threshold is not None else getattr(renderer, "supersample_threshold", None)
-        facts = dict(anti_alias=renderer.anti_alias, disk_model=disk_model, supersample_threshold=thr, spin=renderer.spin, redshift=renderer.redshift,
-                     shutter=shutter, maps=ray_map or orbit_map or shutter_map)
+    kerr_polarization = checked("kerr_polarization", kerr_polarization, f, "video")
     plan = None
     if moving:
         from . import observer as obs_mod
@@ -1367,21 +1078,14 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
             raise ValueError("observer names a velocity and observer_velocity gives one: take one of the two")
         if infall_to is not None and observer != "infall":
             raise ValueError("infall_to is the path of observer='infall'")
-        check_observer((0.0, 0.0, 0.0), **facts)
+        rules.refuse("observer", f, "video")
         plan = obs_mod.frame_plan(n_frames, static_cam_pos, observer, observer_velocity, orbit, orbit_degrees, infall_to)
-    proj = None
-    if projected:
-        proj = check_projection(projection, projection_fov=projection_fov, world=world, stars=stars is not None, **facts)
-    if light_delay is not None:
-        light_delay = check_light_delay(light_delay, world=world, observer=moving, projection=projected, stars=stars is not None, **facts)
+    proj = checked("projection", projection, f, "video")
+    light_delay = checked("light_delay", light_delay, f, "video")
     check_map_supersample(map_supersample, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map)
     check_shutter(shutter, shutter_samples=shutter_samples)
-    if kerr_polarization is None and (polarization is not None or stokes_path is not None):     # (without one the renderer is not asked anything, as ever)
-        polarization = check_polarization(polarization, video=True, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map, shutter=shutter,
-                                          supersample=renderer.supersample if supersample is None else supersample,
-                                          map_supersample=map_supersample, disk_model=disk_model, world=world, spin=renderer.spin,
-                                          redshift=renderer.redshift, observer=moving, projection=projected, light_delay=light_delay is not None,
-                                          stokes_path=stokes_path)
+    if kerr_polarization is None:
+        polarization = checked("polarization", polarization, f, "video")
     if video_stream not in ("auto", "y4m", "off"):
         raise ValueError(f"video_stream must be 'auto', 'y4m' or 'off', got {video_stream!r}")
     hdr = check_video_hdr(video_hdr, hdr_white=hdr_white, hdr_exposure=hdr_exposure, width=width, height=height, world=world,
@@ -1389,44 +1093,19 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     grade = check_grade(grade)
     if grade is not None:
         grade["keep_hdr"] = False
-    if shutter_map:
-        check_shutter_map(shutter_map, shutter=shutter, orbit=orbit, ray_map=ray_map, orbit_map=orbit_map, disk_tilt=renderer.disk_tilt,
-                          supersample=renderer.supersample if supersample is None else supersample, disk_model=disk_model, world=world)
-    if orbit_map:
-        check_orbit_map(orbit_map, video=True, orbit=orbit, ray_map=ray_map, disk_tilt=renderer.disk_tilt, shutter=shutter,
-                        supersample=renderer.supersample if supersample is None else supersample, disk_model=disk_model, world=world)
-    if ray_map:
-        check_ray_map(ray_map, orbit=orbit, shutter=shutter, supersample=renderer.supersample if supersample is None else supersample,
-                      disk_model=disk_model, world=world)
+    rules.refuse_on("shutter_map orbit_map ray_map", f, "video")
     # the checks have refused every combination of two: the video's one map, or none
-    mode = next((m for m, on in (("ray_map", ray_map), ("orbit_map", orbit_map), ("shutter_map", shutter_map), ("spin_map", spin_map),
-                                 ("spin_shutter_map", spin_shutter_map)) if on), None)
+    mode = next((m for m in ("ray_map", "orbit_map", "shutter_map", "spin_map", "spin_shutter_map") if f[m]), None)
     # point stars: the renderer carries the catalogue (make_renderer(stars=)); the frames that show it are the map's
-    if stars is not None:
-        stars = check_stars(stars, supersample=renderer.supersample if supersample is None else supersample, spin=renderer.spin,
-                            redshift=renderer.redshift, disk_model=disk_model, observer=None if plan is None else observer or observer_velocity)
-        if shutter_map:
-            raise ValueError("point stars do not combine with shutter_map: shutter frames from the map have no point stars")
-        if not (ray_map or orbit_map):
-            raise ValueError("point stars in a video need ray_map or orbit_map: they are rendered through a ray map")
-        if map_supersample != 1:
-            raise ValueError("point stars do not combine with map_supersample > 1: they need a ray map with one ray per pixel")
-        if world != 1:
-            raise ValueError("point stars render on one GPU: a ray map lives on one GPU")
-        if renderer.stars_info()["n"] == 0:
-            raise ValueError("point stars: the renderer has no star catalogue (make_renderer(stars=...) sets it)")
+    stars = checked("stars", stars, f, "video")
+    if stars is not None and renderer.stars_info()["n"] == 0:
+        raise ValueError("point stars: the renderer has no star catalogue (make_renderer(stars=...) sets it)")
     # ``kerr_stars`` (needs ``spin_map=True``): point stars around a spinning hole, behind every refusal above -- the renderer
     # carries the Kerr catalogue (make_renderer(kerr_stars=)) and every frame from the Kerr map shows it; under ``orbit`` each frame
     # gathers the star plane of its turned view.  The progress record names the stars only when there are any.
-    if kerr_stars is not None:                                  # (without them the renderer is not asked anything, as ever)
-        kerr_stars = check_kerr_stars(kerr_stars, spin=renderer.spin, redshift=renderer.redshift, stars=stars is not None,
-                                      supersample=renderer.supersample if supersample is None else supersample,
-                                      spin_map_supersample=spin_map_supersample, spin_shutter_map=spin_shutter_map, shutter=shutter,
-                                      spin_observer=kerr_view is not None and kerr_view.get("projection") is None,
-                                      spin_projection=kerr_view is not None and kerr_view.get("projection") is not None,
-                                      world=world, video=True, spin_map=spin_map)
-        if renderer.kerr_stars_info()["n"] == 0:
-            raise ValueError("--spin_stars: the renderer has no Kerr star catalogue (make_renderer(kerr_stars=...) sets it)")
+    kerr_stars = checked("kerr_stars", kerr_stars, f, "video")
+    if kerr_stars is not None and renderer.kerr_stars_info()["n"] == 0:
+        raise ValueError("--spin_stars: the renderer has no Kerr star catalogue (make_renderer(kerr_stars=...) sets it)")
     if video_codec not in VIDEO_CODECS:
         raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
     check_depth_and_dither(bit_depth, dither=dither, video_codec=video_codec)
@@ -1442,17 +1121,14 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     temp_dir = _frames_dir(output_path)
     submitted: List[int] = []
     progress_file = os.path.join(temp_dir, f"progress.json" if world == 1 else f"progress.rank{rank}.json")
-    params = progress_params(n_frames, fov, orbit, disk_rotation_speed, orbit_degrees, video_codec, video_quality, bit_depth, dither,
-                             shutter, shutter_samples, grade, ray_map, orbit_map, shutter_map, map_supersample,
-                             video_hdr, hdr_white, hdr_exposure,
-                             observer=None if plan is None else {"kind": observer, "velocity": None if observer_velocity is None else list(observer_velocity),
-                                                                 "sky": bool(observer_sky), "infall_to": infall_to},
-                             **({} if stars is None else {"stars": stars}),
-                             **({} if proj is None else {"projection": {"kind": proj[0], "fov": [proj[1], proj[2]]}}),
-                             **({} if light_delay is None else {"light_delay": light_delay}),
-                             **({} if polarization is None else {"polarization": polarization}), spin_map=spin_map, kerr_view=kerr_view,
-                             spin_map_supersample=spin_map_supersample, **({"spin_shutter_map": True} if spin_shutter_map else {}),
-                             **({} if kerr_stars is None else {"kerr_stars": kerr_stars}))
+    params = progress_params(
+        n_frames=n_frames, fov=fov, orbit=orbit, disk_rotation_speed=disk_rotation_speed, orbit_degrees=orbit_degrees, video_codec=video_codec,
+        video_quality=video_quality, bit_depth=bit_depth, dither=dither, shutter=shutter, shutter_samples=shutter_samples, grade=grade, ray_map=ray_map,
+        orbit_map=orbit_map, shutter_map=shutter_map, map_supersample=map_supersample, video_hdr=video_hdr, hdr_white=hdr_white, hdr_exposure=hdr_exposure,
+        observer=None if plan is None else {"kind": observer, "velocity": None if observer_velocity is None else list(observer_velocity),
+                                            "sky": bool(observer_sky), "infall_to": infall_to},
+        stars=stars, projection=None if proj is None else {"kind": proj[0], "fov": [proj[1], proj[2]]}, light_delay=light_delay, polarization=polarization,
+        spin_map=spin_map, kerr_view=kerr_view, spin_map_supersample=spin_map_supersample, spin_shutter_map=spin_shutter_map, kerr_stars=kerr_stars)
 
     # Resume (render.py:4380-4434).  With several ranks the decision to start over is taken ONCE: every rank looks
     # at the same merged record of all ranks' progress files, only frame files and progress files are removed (never
