@@ -9,7 +9,8 @@ catalogue of lensed points rendered through a ray map), ``--light_delay`` (every
 time its light left the gas), ``--projection`` / ``--projection_fov`` (equirectangular 360-degree
 frames and fisheye dome masters instead of the pinhole camera), ``--polarization`` (Stokes Q / U maps of the disk through a ray map),
 ``--spin_observer`` / ``--spin_projection`` and their companions (the moving and the panoramic camera of a spinning hole),
-``--spin_stars point`` (the catalogue of lensed points through a Kerr ray map) and ``--spin_passes`` (a Kerr ray map's passes of a still).
+``--spin_stars point`` (the catalogue of lensed points through a Kerr ray map), ``--spin_passes`` (a Kerr ray map's passes of a still)
+and ``--spin_anti_alias lod_radius`` / ``--spin_aa_strength`` (ray differentials and mip LOD for the spinning hole's disk).
 """
 from __future__ import annotations
 
@@ -76,6 +77,15 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "Marched in Kerr-Schild form by a kernel of its own, whatever --math says.  Not with --disk_tilt, "
                         "--anti_alias lod_radius, --disk_model v2 / v2_volume, --supersample_threshold, --shutter (unless --spin_shutter_map), the "
                         "ray-map flags, --passes or --gpus > 1; plain --supersample works")
+    p.add_argument("--spin_anti_alias", type=str, default=argparse.SUPPRESS, choices=["lod_radius"],
+                   help="--spin / --redshift exact: anti-aliasing of the spinning hole's disk.  lod_radius: every Kerr ray carries ray "
+                        "differentials (the variational equations of the Kerr march, integrated beside the ray) and every disk crossing "
+                        "samples the mip level of its footprint, as --anti_alias lod_radius does for the hole that does not spin.  "
+                        "Still images and --video [--orbit]; combines with --supersample, --redshift exact, --lens_flare, the grade "
+                        "and every sink.  Not without --spin / --redshift exact, with --spin_map, --spin_shutter_map, "
+                        "--spin_polarization, --spin_stars, --spin_passes, --spin_observer / --spin_projection or --gpus > 1")
+    p.add_argument("--spin_aa_strength", type=float, default=argparse.SUPPRESS, metavar="S",
+                   help="--spin_anti_alias lod_radius: LOD multiplier, finite and not negative (default: 1.0)")
     p.add_argument("--redshift", type=str, default="model", choices=["model", "exact"],
                    help="redshift of the disk around the hole of --spin.  model (default): the reference's g-factor model with "
                         "Kerr's orbital frequency.  exact: the g-factor of the Kerr metric -- frame dragging, the Doppler term from "
@@ -319,6 +329,13 @@ def parse_args(argv=None) -> argparse.Namespace:
             rules.refuse_on(features, f, surface)
         except ValueError as e:
             p.error(str(e))
+    # the Kerr anti-aliasing (the drivers' words), ahead of everything else, so that each refusal names --spin_anti_alias
+    if hasattr(args, "spin_aa_strength") and not hasattr(args, "spin_anti_alias"):
+        p.error("--spin_aa_strength needs --spin_anti_alias lod_radius: it is that anti-aliasing's LOD multiplier")
+    try:
+        drivers._checked_kerr_anti_alias(kerr_anti_alias_from_args(args).get("kerr_anti_alias"), f)
+    except ValueError as e:
+        p.error(str(e))
     refuse("shutter")
     refuse("spin_shutter_map", "api")             # (the drivers' words: ahead of every other check, so that each names --spin_shutter_map)
     refuse("spin_map_supersample spin_map")       # ahead of a spin's own, so that each names --spin_map
@@ -436,7 +453,14 @@ def facts_from_args(args, fov_given: bool):
         passes=args.passes is not None, passes_path=args.passes, kerr_passes_path=getattr(args, "spin_passes", None), ray_map=args.ray_map,
         orbit_map=args.orbit_map, shutter_map=args.shutter_map, spin_map=hasattr(args, "spin_map"), spin_shutter_map=hasattr(args, "spin_shutter_map"),
         video_hdr=args.video_hdr, hdr_white_given=args.hdr_white is not None, hdr_exposure_given=args.hdr_exposure is not None, video_codec=args.video_codec,
-        video_stream=args.video_stream))
+        video_stream=args.video_stream, kerr_anti_alias=hasattr(args, "spin_anti_alias")))
+
+
+def kerr_anti_alias_from_args(args) -> dict:
+    """The Kerr anti-aliasing of a command line as drivers.render_image / render_video take it: {} without --spin_anti_alias."""
+    if not hasattr(args, "spin_anti_alias"):
+        return {}
+    return dict(kerr_anti_alias=float(getattr(args, "spin_aa_strength", 1.0)))
 
 
 def grade_from_args(args):
@@ -638,6 +662,8 @@ def main(argv=None) -> int:
     delay_kw = light_delay_from_args(args)
     # ... and the polarisation
     pol_kw = polarization_from_args(args)
+    # ... and the Kerr anti-aliasing
+    aa_kw = kerr_anti_alias_from_args(args)
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))
@@ -657,6 +683,9 @@ def main(argv=None) -> int:
         if kerr_stars_kw:
             drivers.check_kerr_stars(kerr_stars_kw["kerr_stars"], spin=args.spin, redshift=args.redshift, world=world, video=True,
                                      spin_map=hasattr(args, "spin_map"))
+        if aa_kw:
+            from . import rules
+            rules.refuse("kerr_anti_alias", dict(spin=args.spin, redshift=args.redshift, world=world))
         if "BHR_FORCE_DEVICE" in os.environ:        # rehearsal: several ranks sharing one card
             local_rank = int(os.environ["BHR_FORCE_DEVICE"])
         elif world > 1:                             # a launcher that shows every rank only its own GPU: ordinal 0
@@ -685,7 +714,7 @@ def main(argv=None) -> int:
                              **({"spin_map": True} if hasattr(args, "spin_map") else {}),
                              **({"spin_shutter_map": True} if hasattr(args, "spin_shutter_map") else {}),
                              **({"spin_map_supersample": args.spin_map_supersample} if hasattr(args, "spin_map_supersample") else {}),
-                             **kerr_stars_kw)
+                             **kerr_stars_kw, **aa_kw)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -711,6 +740,6 @@ def main(argv=None) -> int:
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
         grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw, **stars_kw,
         **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw,
-        **kerr_stars_kw, **({"kerr_passes_path": args.spin_passes} if hasattr(args, "spin_passes") else {}))
+        **kerr_stars_kw, **({"kerr_passes_path": args.spin_passes} if hasattr(args, "spin_passes") else {}), **aa_kw)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

@@ -113,6 +113,8 @@ int32_t bhr_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flag
     // the map's own factor: the map of the fine frame, k rows x k W (the context's own supersampling stays off, check_context)
     const int32_t ss = ctx->opt.kerr_raymap_ss;
     BHR_TRY(check_context(ctx, who, ss));
+    if (ctx->kerr_aa)
+        return bhr_fail(BHR_ERR_INVALID, "%s: the Kerr anti-aliasing is on (bhr_set_kerr_anti_alias) and a Kerr ray map's record has no differential words; switch it off first", who);
     const int32_t K = ctx->opt.raymap_slots;
     if (K < 1 || K > 8) return bhr_fail(BHR_ERR_INVALID, "%s: raymap_slots %d (1 .. 8)", who, K);
     if (ctx->opt.raymap_ss != 1)

@@ -596,6 +596,8 @@ struct bhr_ctx {
     int32_t kerr_on;
     float kerr_spin;
     int32_t kerr_redshift;     // bhr_set_redshift: BHR_REDSHIFT_MODEL (0) or BHR_REDSHIFT_EXACT, which needs kerr_on
+    int32_t kerr_aa;           // bhr_set_kerr_anti_alias: the Kerr march carries ray differentials (needs kerr_on); its strength
+    float kerr_aa_strength;
 
     // the Kerr ray map (api_kerr_raymap.hip): a map object of its own -- nothing of `raymap` above is shared, its stars and polarisation
     // never see it; it carries the spin and the redshift mode it was built under
@@ -645,6 +647,10 @@ inline unsigned long long *bhr_steps_cell(const bhr_ctx *ctx, int32_t slot) { re
 // anti_alias "disabled": the reference still integrates the differentials (skip_diff = 0 on
 // the CLI path) but never reads them (render.py:2957-2959) => skipping them is pixel-identical.
 inline bool bhr_want_diff(const bhr_ctx *ctx, uint32_t flags) { return ctx->cfg.anti_alias != 0 && !(flags & BHR_SKIP_DIFFERENTIALS); }
+// ... of a march of variant v: the Kerr march's own switch (bhr_set_kerr_anti_alias) for its two variants, else the above
+inline bool bhr_want_diff(const bhr_ctx *ctx, uint32_t flags, bhr_march_variant v) {
+    return v == BHR_MV_KERR || v == BHR_MV_KERR_EXACT ? ctx->kerr_aa != 0 : bhr_want_diff(ctx, flags);
+}
 
 // A row block's packed H-blur planes as a neighbour's split-f16 H pass stores its halo rows into them (bhr_launch_bloom_h;
 // group.hip fills the array for the duration of one group / tile render)
@@ -736,7 +742,7 @@ const bhr_variant_row &bhr_variant_row_of(bhr_march_variant v);   // the table
 // the variant of a frame: what its entry point asks for, else what the context is set to (a spin, the exact redshift) -- the
 // one place that reads kerr_on for it; everything else switches on the result
 bhr_march_variant bhr_variant_of(const bhr_ctx *ctx, bhr_march_variant asked = BHR_MV_NONE);
-int32_t bhr_note_frame_kernel(bhr_ctx *ctx);                               // its registers / LDS into the counters (bhr_create, bhr_set_spin, bhr_set_redshift)
+int32_t bhr_note_frame_kernel(bhr_ctx *ctx);                               // its registers / LDS into the counters (bhr_create, bhr_set_spin, bhr_set_redshift, bhr_set_kerr_anti_alias)
 // what a frame of variant v does not combine with: BHR_ERR_INVALID naming it -- `flags` of the call, the context's state (tilt,
 // anti-aliasing, Disk V2, adaptive supersampling, spin and redshift, row block).  spin: a / M as printed (bhr_set_spin: the candidate)
 int32_t bhr_variant_frame_check(const bhr_ctx *ctx, bhr_march_variant v, uint32_t flags, const char *who, double spin);
@@ -789,7 +795,7 @@ const void *bhr_march_kernel_raymap(bhr_march_kernel k, int32_t diff, int32_t ss
 const void *bhr_march_kernel_observer(bhr_march_kernel k, int32_t diff, int32_t ss);   // march_observer.hip -> march_observer.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_projected(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_projected.hip -> march_projected.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_delay(bhr_march_kernel k, int32_t diff, int32_t ss);      // march_delay.hip -> march_delay.o (BHR_MK_TILE, diff 0 only)
-const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT, diff 0 only)
+const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT; diff: the Ray with differentials, bhr_set_kerr_anti_alias)
 const void *bhr_march_kernel_kerr_view(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_kerr_observer.hip -> march_kerr_observer.o (as bhr_march_kernel_kerr)
 const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact, int32_t ss);   // march_kerr_raymap.hip -> march_kerr_raymap.o (exact: the exact redshift's; ss: a supersampled map's)
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o

@@ -41,7 +41,9 @@
 // and per march variant (bhr_internal.h: bhr_march_variant, with a row of what the host knows of it) a ray_<v>.h with a
 // Ray<false, 0> of its own and a march_<v>.hip -> march_<v>.o with the tile schedule's plain and supersampled kernel:
 //   kerr       a spinning hole in Kerr-Schild coordinates, RK4 on (x, p), its own sampler and g-factor, model or exact
-//              (bhr_set_spin, bhr_set_redshift); the Schwarzschild Rays know nothing of it; -ffp-contract=on, no fast-math
+//              (bhr_set_spin, bhr_set_redshift), and each once more over its Ray<true, RS>: two ray tangents beside (x, p)
+//              and the mip level of every crossing (bhr_set_kerr_anti_alias); the Schwarzschild Rays know nothing of it;
+//              -ffp-contract=on, no fast-math
 //              (and march_kerr_raymap.hip -> march_kerr_raymap.o over the same Ray: the Kerr ray map's build, shade and
 //              overflow kernels, with the Kerr object's flags; its table is bhr_march_kernel_kerr_raymap)
 //   kerr_observer  the Kerr Ray launched along the aberrated pinhole, equirectangular or fisheye direction of a camera that may

@@ -184,7 +184,7 @@ int32_t bhr_ensure_tile_order(bhr_ctx *ctx, int32_t ss) {
 int32_t bhr_march_resources(const char *who, bhr_march_variant v, int32_t math, int32_t diff, int32_t ss, int32_t out[3]) {
     if (!out) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
     const bhr_variant_row &r = bhr_variant_row_of(v);
-    const void *f = v != BHR_MV_NONE         ? r.kernels(r.name, 0, ss ? 1 : 0)
+    const void *f = v != BHR_MV_NONE         ? r.kernels(r.name, r.kerr ? diff : 0, ss ? 1 : 0)
                     : math == BHR_MATH_FAST ? bhr_march_kernel_fast(BHR_MK_TILE, diff, ss ? 1 : 0)
                                             : bhr_march_kernel_strict_ilp(BHR_MK_TILE_ILP, diff, ss ? 1 : 0);
     if (!f) return bhr_fail(BHR_ERR_STATE, "%s: no such march kernel in this library", who);
@@ -322,6 +322,7 @@ static void *variant_args(const bhr_ctx *ctx, const bhr_variant_request &req, Bh
         const double A = (double)ctx->kerr_spin;
         k.kerr_a = (float)(0.5 * A);
         k.kerr_rplus = (float)(0.5 * (1.0 + sqrt(1.0 - A * A)));
+        if (ctx->kerr_aa) k.aa_strength = ctx->kerr_aa_strength;       // the Kerr march's own LOD strength (bhr_set_kerr_anti_alias)
         // ... and, for the exact-redshift kernels alone, the ISCO of the disk's sense of rotation (prograde for A >= 0) with the
         // energy and angular momentum of its orbit (Bardeen, Press, Teukolsky 1972; M = 1/2, signed a, an orbit in the +phi sense)
         k.isco_r = k.isco_e = k.isco_l = 0.0f;
@@ -442,7 +443,7 @@ int32_t bhr_launch_march(bhr_ctx *ctx, const bhr_march_call &call, const bhr_mar
     if (flags & BHR_PERSISTENT) BHR_HIP(hipMemsetAsync(bhr_slot(ctx).d_queue, 0, sizeof(unsigned int), stream));
     // timed launches (bhr_render) use their ring slot's events, the others the context's scalar ones
     if (first_part && !call.keep_start) BHR_HIP(hipEventRecord(bhr_march_start_event(ctx, slot), stream));
-    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags), variant);
+    const MarchKernel k = march_kernel(ctx, a, part, math, flags, bhr_want_diff(ctx, flags, variant), variant);
     if (!k.fn && !(part && part->n <= 0 && part->repair != 2))
         return bhr_fail(BHR_ERR_STATE, "bhr_render: no march kernel for this launch (supersampling %d, flags %u)", call.ss, flags);
     if (k.fn) {

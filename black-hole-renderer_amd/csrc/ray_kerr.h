@@ -18,11 +18,20 @@
 // coordinate velocity along the pixel direction; by time reversal and a -> -a that is the image of a hole that turns with
 // this project's disk (v_hat = r_hat x n, clockwise seen from +z) for A > 0.  DESIGN.md "Kerr" has the conventions.
 //
-// No ray differentials (they would need the variational equations of this system) and one disk source, the texture at
-// level 0.  The Ray's second parameter, the disk source everywhere else, selects the disk's redshift here: Ray<false, 0> has
-// the reference's g-factor model with Kerr's orbital frequency, Ray<false, KERR_EXACT> the g-factor of the Kerr metric
-// (kerr_g_exact below; bhr_set_redshift).  The march is one and the same; the two differ in what a crossing parks and in
-// how its shade makes g.
+// One disk source, the texture.  The Ray's second parameter, the disk source everywhere else, selects the disk's redshift
+// here: Ray<DIFF, 0> has the reference's g-factor model with Kerr's orbital frequency, Ray<DIFF, KERR_EXACT> the g-factor of
+// the Kerr metric (kerr_g_exact below; bhr_set_redshift).  The march is one and the same; the two differ in what a crossing
+// parks and in how its shade makes g.
+//
+// Ray differentials (DIFF, bhr_set_kerr_anti_alias): beside (x, p) the ray carries two tangents (xi, pi), one per pixel axis,
+// d(x, p) / d(pixel).  They obey the variational equations of the system above, which are kerr_rhs differentiated line by
+// line in forward mode (kerr_rhs_tangent: every reciprocal and root it needs is one the primal stage has already made), and
+// are integrated by the same RK4 step with the same h, h being a constant of the step as in the strict Ray's variational pair.
+// Seeds: xi = 0, and pi the differential of the camera's momentum p = s d + f Lam l under d -> d + delta d, with delta d
+// pixel_ray<true>'s and f, l constants of the camera.  A crossing parks the x and y components of the two new xi (the
+// reference's convention: the end of the crossing step, not projected onto the plane) and its shade picks the mip level
+// from them (kerr_lod).  The primal march is not touched: Ray<true, RS> marches the bits Ray<false, RS> marches.
+// tests/kerr_aa_ref.py states the same in NumPy.
 #pragma once
 #define BHR_RAY_STRICT 1   // the shared samplers in the reference's evaluation order (march_device.h: BHR_BILERP)
 #include "march_device.h"
@@ -34,7 +43,7 @@ namespace {
 __device__ __forceinline__ const BhrKerrMarchArgs &kerr(const BhrMarchArgs &a) { return static_cast<const BhrKerrMarchArgs &>(a); }
 // ... and the exact-redshift kernels' block with the ISCO's numbers behind that (BhrKerrExactMarchArgs); theirs alone
 __device__ __forceinline__ const BhrKerrExactMarchArgs &kerr_exact(const BhrMarchArgs &a) { return static_cast<const BhrKerrExactMarchArgs &>(a); }
-constexpr int KERR_EXACT = 1;   // Ray<false, KERR_EXACT>: the exact redshift
+constexpr int KERR_EXACT = 1;   // Ray<DIFF, KERR_EXACT>: the exact redshift
 
 // v_rsq of x and v_rcp of y back to back (march_device.h: rsq2 / rcp2 say why)
 __device__ __forceinline__ void rsq_rcp(float x, float y, float &rs, float &rc) {
@@ -60,7 +69,41 @@ __device__ __forceinline__ KerrGeom kerr_geom(float a2, V3 x) {
     g.r2 = 0.5f * (g.w + g.S);
     return g;
 }
-// dx/dl and dp/dl at (x, p)
+// What a right-hand side evaluation leaves behind for the tangents of the same stage (kerr_rhs_tangent)
+struct KerrStage {
+    float w, S, iS, r2, Q, r, ir, iQ, f, u, fu, gg, sxy, N, dr, c1;
+    V3 l, gr, gS, gf, gl;
+};
+// dx/dl and dp/dl at (x, p), with the stage's record: kerr_rhs below, value for value
+__device__ __forceinline__ void kerr_rhs_stage(float a, float a2, V3 x, V3 p, V3 &v, V3 &dp, KerrStage &s) {
+    const KerrGeom g = kerr_geom(a2, x);
+    const float Q = g.r2 + a2;
+    float y_r, y_q;
+    rsq_rcp(g.r2, Q, y_r, y_q);
+    float r, ir;
+    sqrt_both(g.r2, y_r, r, ir);
+    const float iQ = rcp_rn_s(Q, y_q);
+    const float f = r * g.iS;
+    const V3 l = mk((r * x.x + a * x.y) * iQ, (r * x.y - a * x.x) * iQ, x.z * ir);
+    const float u = 1.0f + dot(l, p);
+    const float fu = f * u;
+    v = mk(p.x - fu * l.x, p.y - fu * l.y, p.z - fu * l.z);
+    const float gg = ir * g.iS;
+    const V3 gr = mk(g.r2 * x.x * gg, g.r2 * x.y * gg, Q * x.z * gg);
+    const float w2 = 2.0f * g.w;
+    const V3 gS = mk(w2 * x.x * g.iS, w2 * x.y * g.iS, (w2 + 4.0f * a2) * x.z * g.iS);
+    const V3 gf = mk((gr.x - f * gS.x) * g.iS, (gr.y - f * gS.y) * g.iS, (gr.z - f * gS.z) * g.iS);
+    const float sxy = x.x * p.x + x.y * p.y;
+    const float N = r * sxy + a * (x.y * p.x - x.x * p.y);
+    const float dr = sxy * iQ - 2.0f * r * N * iQ * iQ - x.z * p.z * ir * ir;
+    const V3 gl = mk((r * p.x - a * p.y) * iQ + dr * gr.x, (a * p.x + r * p.y) * iQ + dr * gr.y, p.z * ir + dr * gr.z);
+    const float c1 = 0.5f * u * u;
+    dp = mk(c1 * gf.x + fu * gl.x, c1 * gf.y + fu * gl.y, c1 * gf.z + fu * gl.z);
+    s.w = g.w; s.S = g.S; s.iS = g.iS; s.r2 = g.r2; s.Q = Q; s.r = r; s.ir = ir; s.iQ = iQ; s.f = f; s.u = u; s.fu = fu;
+    s.gg = gg; s.sxy = sxy; s.N = N; s.dr = dr; s.c1 = c1; s.l = l; s.gr = gr; s.gS = gS; s.gf = gf; s.gl = gl;
+}
+// ... for a ray without differentials: the same lines without the stage's record (kept as they were written: the objects that
+// inline it stay the bytes they are)
 __device__ __forceinline__ void kerr_rhs(float a, float a2, V3 x, V3 p, V3 &v, V3 &dp, float &r_out) {
     const KerrGeom g = kerr_geom(a2, x);
     const float Q = g.r2 + a2;
@@ -86,6 +129,42 @@ __device__ __forceinline__ void kerr_rhs(float a, float a2, V3 x, V3 p, V3 &v, V
     const V3 gl = mk((r * p.x - a * p.y) * iQ + dr * gr.x, (a * p.x + r * p.y) * iQ + dr * gr.y, p.z * ir + dr * gr.z);
     const float c1 = 0.5f * u * u;
     dp = mk(c1 * gf.x + fu * gl.x, c1 * gf.y + fu * gl.y, c1 * gf.z + fu * gl.z);
+}
+// The tangent of kerr_rhs_stage at (x, p) along (xi, pi): d(dx/dl) and d(dp/dl), every line of the primal differentiated in
+// forward mode with the stage's own values (s) -- no reciprocal, no root:
+//   d(1/S) = -dS / S^2, d(1/Q) = -dQ / Q^2, d(1/r) = -dr / r^2, and for a quotient n / D kept as n iD: d(n iD) = (dn - (n iD) dD) iD
+__device__ __forceinline__ void kerr_rhs_tangent(float a, float a2, V3 x, V3 p, const KerrStage &s, V3 xi, V3 pi, V3 &tv, V3 &tdp) {
+    const float dw = 2.0f * dot(x, xi);
+    const float dS = (s.w * dw + 4.0f * a2 * x.z * xi.z) * s.iS;
+    const float dr2 = 0.5f * (dw + dS);                   // = dQ
+    const float dr = 0.5f * dr2 * s.ir;
+    const float diS = -dS * s.iS * s.iS;
+    const float diQ = -dr2 * s.iQ * s.iQ;
+    const float dir = -dr * s.ir * s.ir;
+    const float df = dr * s.iS + s.r * diS;
+    const V3 dl = mk((dr * x.x + s.r * xi.x + a * xi.y - s.l.x * dr2) * s.iQ, (dr * x.y + s.r * xi.y - a * xi.x - s.l.y * dr2) * s.iQ,
+                     (xi.z - s.l.z * dr) * s.ir);
+    const float du = dot(dl, p) + dot(s.l, pi);
+    const float dfu = df * s.u + s.f * du;
+    tv = mk(pi.x - dfu * s.l.x - s.fu * dl.x, pi.y - dfu * s.l.y - s.fu * dl.y, pi.z - dfu * s.l.z - s.fu * dl.z);
+    const float dgg = dir * s.iS + s.ir * diS;
+    const V3 dgr = mk((dr2 * x.x + s.r2 * xi.x) * s.gg + s.r2 * x.x * dgg, (dr2 * x.y + s.r2 * xi.y) * s.gg + s.r2 * x.y * dgg,
+                      (dr2 * x.z + s.Q * xi.z) * s.gg + s.Q * x.z * dgg);
+    const float w2 = 2.0f * s.w, dw2 = 2.0f * dw, w4 = w2 + 4.0f * a2;
+    const V3 dgS = mk((dw2 * x.x + w2 * xi.x) * s.iS + w2 * x.x * diS, (dw2 * x.y + w2 * xi.y) * s.iS + w2 * x.y * diS,
+                      (dw2 * x.z + w4 * xi.z) * s.iS + w4 * x.z * diS);
+    const V3 dgf = mk((dgr.x - df * s.gS.x - s.f * dgS.x - s.gf.x * dS) * s.iS, (dgr.y - df * s.gS.y - s.f * dgS.y - s.gf.y * dS) * s.iS,
+                      (dgr.z - df * s.gS.z - s.f * dgS.z - s.gf.z * dS) * s.iS);
+    const float dsxy = xi.x * p.x + x.x * pi.x + xi.y * p.y + x.y * pi.y;
+    const float dN = dr * s.sxy + s.r * dsxy + a * (xi.y * p.x + x.y * pi.x - xi.x * p.y - x.x * pi.y);
+    const float ddr = dsxy * s.iQ + s.sxy * diQ - 2.0f * (dr * s.N + s.r * dN) * s.iQ * s.iQ - 4.0f * s.r * s.N * s.iQ * diQ
+                      - (xi.z * p.z + x.z * pi.z) * s.ir * s.ir - 2.0f * x.z * p.z * s.ir * dir;
+    const V3 dgl = mk((dr * p.x + s.r * pi.x - a * pi.y) * s.iQ + (s.r * p.x - a * p.y) * diQ + ddr * s.gr.x + s.dr * dgr.x,
+                      (a * pi.x + dr * p.y + s.r * pi.y) * s.iQ + (a * p.x + s.r * p.y) * diQ + ddr * s.gr.y + s.dr * dgr.y,
+                      pi.z * s.ir + p.z * dir + ddr * s.gr.z + s.dr * dgr.z);
+    const float dc1 = s.u * du;
+    tdp = mk(dc1 * s.gf.x + s.c1 * dgf.x + dfu * s.gl.x + s.fu * dgl.x, dc1 * s.gf.y + s.c1 * dgf.y + dfu * s.gl.y + s.fu * dgl.y,
+             dc1 * s.gf.z + s.c1 * dgf.z + dfu * s.gl.z + s.fu * dgl.z);
 }
 __device__ __forceinline__ float kerr_radius(float a2, V3 x) {
     const KerrGeom g = kerr_geom(a2, x);
@@ -129,6 +208,52 @@ __device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, const 
 }
 __device__ __forceinline__ float4 kerr_sample_disk(const BhrMarchArgs &a, float hit_x, float hit_y, float hit_r) {
     return kerr_sample_disk(a, a, hit_x, hit_y, hit_r);
+}
+// ... at mip level lod_i (Ray<true, RS>): kerr_sample_disk with sample_disk_level's level arithmetic -- u, v, the wrap and the
+// clamp on the level's size.  At level 0 the same values as kerr_sample_disk (n / 2^0 = n).
+__device__ __forceinline__ float4 kerr_sample_disk_level(const BhrMarchArgs &a, float hit_x, float hit_y, float hit_r, int lod_i) {
+    const BhrScene &sc = a.sc;
+    float phi = atan2f(hit_y, hit_x);
+    const float r_safe = fmaxf(hit_r, 1e-3f);
+    phi = phi + a.t_offset * kerr_omega(r_safe, kerr(a).kerr_a);
+    while (phi < 0) phi += BHR_TWO_PI_F;
+    while (phi >= BHR_TWO_PI_F) phi -= BHR_TWO_PI_F;
+    const float scale = (float)(1 << lod_i);
+    const float tex_w_lod = (float)sc.n_phi / scale, tex_h_lod = (float)sc.n_r / scale;
+    const float u = phi / BHR_TWO_PI_F * tex_w_lod;
+    const float v = (hit_r - a.r_inner) / (a.r_outer - a.r_inner) * tex_h_lod;
+    const int u0 = (int)floorf(u), v0 = (int)floorf(v);
+    const float fu = u - (float)u0, fv = v - (float)v0;
+    const int wl = (int)tex_w_lod, vmax = (int)(tex_h_lod - 1.0f);
+    const int u0_w = pymod(u0, wl), u1_w = pymod(u0 + 1, wl);
+    const int v0_h = min(max(v0, 0), vmax), v1_h = min(max(v0 + 1, 0), vmax);
+    const float4 *t = sc.mips + sc.mip_off[lod_i];
+    const int stride = sc.mip_w[lod_i];
+    const float4 c00 = t[(size_t)v0_h * stride + u0_w], c10 = t[(size_t)v0_h * stride + u1_w];
+    const float4 c01 = t[(size_t)v1_h * stride + u0_w], c11 = t[(size_t)v1_h * stride + u1_w];
+    return make_float4(BHR_BILERP(c00.x, c10.x, c01.x, c11.x), BHR_BILERP(c00.y, c10.y, c01.y, c11.y),
+                       BHR_BILERP(c00.z, c10.z, c01.z, c11.z), BHR_BILERP(c00.w, c10.w, c01.w, c11.w));
+}
+// The mip level of a crossing from its hit differentials (hdx, hdy: the x and y components of d hit / d pixel along the two
+// pixel axes): shade_hit's lines (render.py:2964-2988) in the Kerr texture coordinates phi = atan2(hy, hx) and the
+// Boyer-Lindquist r = sqrt(hx^2 + hy^2 - a^2), so dr = (hx xi_x + hy xi_y) / r; the reference's 1e-6 guards; the roll's own
+// derivative ignored, as the reference ignores it.  At a = 0 the reference's expressions.
+__device__ __forceinline__ int kerr_lod(const BhrMarchArgs &a, float hit_x, float hit_y, float hdx_x, float hdx_y, float hdy_x, float hdy_y) {
+    const float ka = kerr(a).kerr_a;
+    const float rho2 = hit_x * hit_x + hit_y * hit_y;
+    const float hit_r_g = sqrtf(rho2 - ka * ka + 1e-6f);
+    const float hit_r_cyl = sqrtf(rho2 + 1e-6f);
+    const float den = hit_r_cyl * hit_r_cyl + 1e-6f;
+    const float w_f = (float)a.sc.n_phi, h_f = (float)a.sc.n_r, span = a.r_outer - a.r_inner;
+    const float dr_dx = (hit_x * hdx_x + hit_y * hdx_y) / hit_r_g;
+    const float dphi_dx = (-hit_y * hdx_x + hit_x * hdx_y) / den;
+    const float dudx = dphi_dx * w_f / (2.0f * BHR_PI_F), dvdx = dr_dx * h_f / span;
+    const float dr_dy = (hit_x * hdy_x + hit_y * hdy_y) / hit_r_g;
+    const float dphi_dy = (-hit_y * hdy_x + hit_x * hdy_y) / den;
+    const float dudy = dphi_dy * w_f / (2.0f * BHR_PI_F), dvdy = dr_dy * h_f / span;
+    const float grad_sq = fmaxf(dudx * dudx + dvdx * dvdx, dudy * dudy + dvdy * dvdy);
+    const float lod = logf(fmaxf(grad_sq, 1.0f)) / logf(2.0f) * a.aa_strength;
+    return min((int)fminf(fmaxf(lod, 0.0f), 3.0f), a.sc.mip_last);
 }
 
 // The g-factor of the Kerr metric for a crossing at Boyer-Lindquist radius r of the plane, g = nu_obs / nu_em with both
@@ -266,14 +391,33 @@ template <int RS>
 __device__ __forceinline__ void kerr_shade_hit(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam, float obs_d = 1.0f) {
     kerr_shade_hit<RS>(a, a, sh, hit_x, hit_y, to_cam, obs_d);
 }
+// ... of a ray with differentials: the texture at the crossing's mip level (kerr_lod); the g-factor and the compositing are
+// kerr_shade_hit's.  A function of its own: the level-0 shade above stays the code it is in every object that inlines it.
+template <int RS>
+__device__ __forceinline__ void kerr_shade_hit_lod(const BhrMarchArgs &a, Shade &sh, float hit_x, float hit_y, V3 to_cam,
+                                                   float hdx_x, float hdx_y, float hdy_x, float hdy_y) {
+    const float hit_r = sqrtf(hit_x * hit_x + hit_y * hit_y - kerr(a).kerr_a * kerr(a).kerr_a);
+    if (!(a.r_outer >= hit_r && hit_r >= a.r_inner)) return;
+    const int lod_i = kerr_lod(a, hit_x, hit_y, hdx_x, hdx_y, hdy_x, hdy_y);
+    const float4 rgba = kerr_sample_disk_level(a, hit_x, hit_y, hit_r, lod_i);
+    const float base_alpha = fminf(rgba.w, 0.999f);
+    const float disk_alpha = 1.0f - powf(1.0f - base_alpha, BHR_DISK_ALPHA_GAIN);
+    const V3 col = kerr_g_factor<RS>(a, a, mk(rgba.x, rgba.y, rgba.z), hit_x, hit_y, hit_r, to_cam);
+    const float front = 1.0f - sh.alpha_total;
+    const float wgt = disk_alpha * front;
+    sh.accum = mk(sh.accum.x + col.x * wgt, sh.accum.y + col.y * wgt, sh.accum.z + col.z * wgt);
+    sh.alpha_total = 1.0f - front * (1.0f - disk_alpha);
+}
 
 // MOM (the Kerr ray map's build under a Kerr polarisation, march_kerr_raymap.hip): a crossing also parks the photon's whole
 // momentum (p_x, p_y, p_z) at the hit, interpolated like the hit point, in words 5..7 of the lane's parking slot -- the words a
 // ray with differentials would use, which the Kerr ray has none of -- and record_mom stores it beside the record.
 template <bool DIFF, int SRC = 0, bool MOM = false>
 struct KerrRay {
-    static_assert(!DIFF && (SRC == 0 || SRC == KERR_EXACT), "the Kerr march has no ray differentials; its second parameter is the redshift, model or exact");
+    static_assert(SRC == 0 || SRC == KERR_EXACT, "the Kerr Ray's second parameter is the redshift, model or exact");
+    static_assert(!(DIFF && MOM), "the hit differentials and the parked momentum both use parking words 5..7");
     V3 x, p;
+    V3 xi[2], pi[2];   // DIFF: the tangents d(x, p) / d(pixel) along the two pixel axes
     float r;       // Kerr-Schild radius of x
     float affine;
     Shade sh;
@@ -286,8 +430,30 @@ struct KerrRay {
     //   s = 1 / sqrt(1 - f (1 - (l.d)^2)),   Lam = (1 + s l.d) / (1 - f),   p = s d + f Lam l
     // (then 1 + l.p = Lam and dx/dl = s d; H = 0).  Outside the loop: IEEE operations.
     __device__ __forceinline__ void init(const BhrMarchArgs &a, int i, int j_local) {
-        V3 unused_x, unused_y;
-        init_along(a, pixel_ray<false>(a, i, j_local, unused_x, unused_y));
+        V3 ddx, ddy;
+        const V3 d = pixel_ray<DIFF>(a, i, j_local, ddx, ddy);
+        init_along(a, d);
+        if (DIFF) {
+            seed(a, d, ddx, 0);
+            seed(a, d, ddy, 1);
+        }
+    }
+    // DIFF: the tangent k of the camera's photon under d -> d + dd, with f and l constants of the camera:
+    //   dc = l.dd,  ds = -s^3 f c dc,  dLam = (c ds + s dc) / (1 - f),  pi = ds d + s dd + f dLam l,  xi = 0
+    __device__ __forceinline__ void seed(const BhrMarchArgs &a, const V3 d, const V3 dd, int k) {
+        const float ka = kerr(a).kerr_a, a2 = ka * ka;
+        const float w = dot(x, x) - a2;
+        const float S = sqrtf(w * w + 4.0f * a2 * (x.z * x.z));
+        const float r2 = 0.5f * (w + S), rc = sqrtf(r2);
+        const float f = rc / S, Q = r2 + a2;
+        const V3 l = mk((rc * x.x + ka * x.y) / Q, (rc * x.y - ka * x.x) / Q, x.z / rc);
+        const float c = dot(l, d);
+        const float s = 1.0f / sqrtf(1.0f - f * (1.0f - c * c));
+        const float dc = dot(l, dd);
+        const float ds = -(s * s * s) * f * c * dc;
+        const float fdl = f * ((c * ds + s * dc) / (1.0f - f));
+        xi[k] = mk(0, 0, 0);
+        pi[k] = mk(ds * d.x + s * dd.x + fdl * l.x, ds * d.y + s * dd.y + fdl * l.y, ds * d.z + s * dd.z + fdl * l.z);
     }
     // the photon leaves the camera along d (ray_kerr_observer.h: a moving or panoramic camera's is not the pinhole pixel's own)
     __device__ __forceinline__ void init_along(const BhrMarchArgs &a, const V3 d) {
@@ -328,19 +494,69 @@ struct KerrRay {
         const float h = a.h_base * __builtin_amdgcn_fmed3f(far_scale * near_damp, 0.2f, 10.0f);
         const float hh = 0.5f * h;
 
-        V3 v1, d1, v, d, sv, sd;
-        float rr;
-        kerr_rhs(ka, a2, x, p, v1, d1, rr);
-        kerr_rhs(ka, a2, fma3(hh, v1, x), fma3(hh, d1, p), v, d, rr);
-        sv = fma3(2.0f, v, v1);
-        sd = fma3(2.0f, d, d1);
-        kerr_rhs(ka, a2, fma3(hh, v, x), fma3(hh, d, p), v, d, rr);
-        sv = fma3(2.0f, v, sv);
-        sd = fma3(2.0f, d, sd);
-        kerr_rhs(ka, a2, fma3(h, v, x), fma3(h, d, p), v, d, rr);
-        const float h6 = h * (1.0f / 6.0f);
-        const V3 nx = fma3(h6, sv + v, x);
-        const V3 np = fma3(h6, sd + d, p);
+        V3 v1, nx, np;
+        V3 nxi[2], npi[2];
+        if constexpr (!DIFF) {
+            V3 d1, v, d, sv, sd;
+            float rr;
+            kerr_rhs(ka, a2, x, p, v1, d1, rr);
+            kerr_rhs(ka, a2, fma3(hh, v1, x), fma3(hh, d1, p), v, d, rr);
+            sv = fma3(2.0f, v, v1);
+            sd = fma3(2.0f, d, d1);
+            kerr_rhs(ka, a2, fma3(hh, v, x), fma3(hh, d, p), v, d, rr);
+            sv = fma3(2.0f, v, sv);
+            sd = fma3(2.0f, d, sd);
+            kerr_rhs(ka, a2, fma3(h, v, x), fma3(h, d, p), v, d, rr);
+            const float h6 = h * (1.0f / 6.0f);
+            nx = fma3(h6, sv + v, x);
+            np = fma3(h6, sd + d, p);
+        } else {
+            // the same primal lines, and the two tangents evaluated stage by stage next to them from the stage's own geometry
+            // (tv, td: the tangent of the stage's (v, d); stv, std: their running RK4 sums)
+            V3 d1, v, d, sv, sd;
+            KerrStage st;
+            V3 tv[2], td[2], stv[2], std[2];
+            kerr_rhs_stage(ka, a2, x, p, v1, d1, st);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                kerr_rhs_tangent(ka, a2, x, p, st, xi[k], pi[k], tv[k], td[k]);
+                stv[k] = tv[k];
+                std[k] = td[k];
+            }
+            V3 xs = fma3(hh, v1, x), ps = fma3(hh, d1, p);
+            kerr_rhs_stage(ka, a2, xs, ps, v, d, st);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                kerr_rhs_tangent(ka, a2, xs, ps, st, fma3(hh, tv[k], xi[k]), fma3(hh, td[k], pi[k]), tv[k], td[k]);
+                stv[k] = fma3(2.0f, tv[k], stv[k]);
+                std[k] = fma3(2.0f, td[k], std[k]);
+            }
+            sv = fma3(2.0f, v, v1);
+            sd = fma3(2.0f, d, d1);
+            xs = fma3(hh, v, x);
+            ps = fma3(hh, d, p);
+            kerr_rhs_stage(ka, a2, xs, ps, v, d, st);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                kerr_rhs_tangent(ka, a2, xs, ps, st, fma3(hh, tv[k], xi[k]), fma3(hh, td[k], pi[k]), tv[k], td[k]);
+                stv[k] = fma3(2.0f, tv[k], stv[k]);
+                std[k] = fma3(2.0f, td[k], std[k]);
+            }
+            sv = fma3(2.0f, v, sv);
+            sd = fma3(2.0f, d, sd);
+            xs = fma3(h, v, x);
+            ps = fma3(h, d, p);
+            kerr_rhs_stage(ka, a2, xs, ps, v, d, st);
+            const float h6 = h * (1.0f / 6.0f);
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                kerr_rhs_tangent(ka, a2, xs, ps, st, fma3(h, tv[k], xi[k]), fma3(h, td[k], pi[k]), tv[k], td[k]);
+                nxi[k] = fma3(h6, stv[k] + tv[k], xi[k]);
+                npi[k] = fma3(h6, std[k] + td[k], pi[k]);
+            }
+            nx = fma3(h6, sv + v, x);
+            np = fma3(h6, sd + d, p);
+        }
         const float rn = kerr_radius(a2, nx);
 
         const float aff = affine + h;
@@ -354,7 +570,7 @@ struct KerrRay {
                 const float hy = x.y + t_frac * (nx.y - x.y);
                 const float hit_r = sqrtf(hx * hx + hy * hy - a2);          // the Boyer-Lindquist radius in the plane
                 if (a.r_outer >= hit_r && hit_r >= a.r_inner) {
-                    Pending<false> hit;
+                    Pending<DIFF> hit;
                     hit.hit_x = hx;
                     hit.hit_y = hy;
                     if (SRC == KERR_EXACT) {
@@ -365,7 +581,10 @@ struct KerrRay {
                     } else {
                         hit.to_cam = mk(-v1.x, -v1.y, -v1.z);               // against dx/dl at the START of the step
                     }
-                    park_store<false>(n_pend, hit);                         // a free slot is guaranteed (march_tile_body flushes at 2)
+                    // DIFF: the hit differentials are the x and y of the two tangents at the END of the step (the reference's
+                    // convention, render.py:2928-2949: committed before the hit is interpolated), in words 5..8
+                    if (DIFF) { hit.dxx = nxi[0].x; hit.dxy = nxi[0].y; hit.dyx = nxi[1].x; hit.dyy = nxi[1].y; }
+                    park_store<DIFF>(n_pend, hit);                          // a free slot is guaranteed (march_tile_body flushes at 2)
                     if (MOM) {
                         g_park[n_pend][5][threadIdx.x] = p.x + t_frac * (np.x - p.x);
                         g_park[n_pend][6][threadIdx.x] = p.y + t_frac * (np.y - p.y);
@@ -377,6 +596,13 @@ struct KerrRay {
             full = __builtin_amdgcn_ballot_w64(n_pend == 2) != 0ull;
         }
         affine = aff;
+        if (DIFF) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                xi[k] = nxi[k];
+                pi[k] = npi[k];
+            }
+        }
         x = nx;
         p = np;
         r = rn;
@@ -392,8 +618,9 @@ struct KerrRay {
 
     __device__ __forceinline__ void flush_one(const BhrMarchArgs &a) {
         if (n_pend > 0) {
-            const Pending<false> h = park_pop<false>(n_pend);
-            kerr_shade_hit<SRC>(a, sh, h.hit_x, h.hit_y, h.to_cam);
+            const Pending<DIFF> h = park_pop<DIFF>(n_pend);
+            if (DIFF) kerr_shade_hit_lod<SRC>(a, sh, h.hit_x, h.hit_y, h.to_cam, h.dxx, h.dxy, h.dyx, h.dyy);
+            else kerr_shade_hit<SRC>(a, sh, h.hit_x, h.hit_y, h.to_cam);
         }
     }
     // The Kerr ray map's build (march_kerr_raymap.hip): where flush_one shades the oldest parked crossing, this stores it as the

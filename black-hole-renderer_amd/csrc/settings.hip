@@ -63,7 +63,8 @@ const bhr_variant_row &bhr_variant_row_of(bhr_march_variant v) {
 // The counters name the kernel that marches a frame: the context's variant's, else its arithmetic's.
 int32_t bhr_note_frame_kernel(bhr_ctx *ctx) {
     int32_t res[3];
-    BHR_TRY(bhr_march_resources("bhr_note_frame_kernel", bhr_variant_of(ctx), ctx->cfg.math_mode, ctx->cfg.anti_alias != 0, 0, res));
+    const bhr_march_variant v = bhr_variant_of(ctx);
+    BHR_TRY(bhr_march_resources("bhr_note_frame_kernel", v, ctx->cfg.math_mode, bhr_want_diff(ctx, 0, v), 0, res));
     ctx->counters.march_vgprs = res[0];
     ctx->counters.march_lds_bytes = res[1];
     return BHR_OK;
@@ -136,6 +137,8 @@ int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr) {
     if (on) BHR_TRY(bhr_variant_frame_check(ctx, BHR_MV_KERR, 0, "bhr_set_spin", (double)a_over_m));
     if (!on && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
         return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin 0 without force_kerr while the exact redshift is set (bhr_set_redshift): it is a Kerr kernel's; set BHR_REDSHIFT_MODEL first");
+    if (!on && ctx->kerr_aa)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin 0 without force_kerr while the Kerr anti-aliasing is on (bhr_set_kerr_anti_alias): it is a Kerr kernel's; switch it off first");
     if (on == ctx->kerr_on && a_over_m == ctx->kerr_spin) return BHR_OK;
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight, like every other change of what a frame is
     ctx->kerr_on = on;
@@ -155,6 +158,26 @@ int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode) {
     ctx->kerr_redshift = mode;
     if (bhr_have_kerr_polar(ctx)) bhr_polar_invalidate(ctx);   // ... and that mode's gas
     return bhr_note_frame_kernel(ctx);
+}
+
+int32_t bhr_set_kerr_anti_alias(bhr_ctx *ctx, int32_t on, float strength) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_kerr_anti_alias: null ctx");
+    if (!(strength >= 0.0f) || !isfinite(strength))
+        return bhr_fail(BHR_ERR_INVALID, "bhr_set_kerr_anti_alias: strength %g (finite and not negative)", (double)strength);
+    if (on && !ctx->kerr_on)
+        return bhr_fail(BHR_ERR_STATE, "bhr_set_kerr_anti_alias: Kerr anti-aliasing without the Kerr march: set a spin, or force_kerr at spin 0, first (bhr_set_spin)");
+    const int32_t aa = on ? 1 : 0;
+    if (aa == ctx->kerr_aa && (!aa || strength == ctx->kerr_aa_strength)) return BHR_OK;
+    BHR_TRY(bhr_enter(ctx));            // behind the frames in flight
+    ctx->kerr_aa = aa;
+    ctx->kerr_aa_strength = aa ? strength : 0.0f;
+    return bhr_note_frame_kernel(ctx);
+}
+
+int32_t bhr_kerr_anti_alias_resources(int32_t mode, int32_t ss, int32_t out[3]) {
+    if (mode != BHR_REDSHIFT_MODEL && mode != BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_kerr_anti_alias_resources: unknown mode %d (BHR_REDSHIFT_MODEL = 0, BHR_REDSHIFT_EXACT = 1)", mode);
+    return bhr_march_resources("bhr_kerr_anti_alias_resources", mode == BHR_REDSHIFT_EXACT ? BHR_MV_KERR_EXACT : BHR_MV_KERR, 0, 1, ss, out);
 }
 
 int32_t bhr_observer_resources(int32_t ss, int32_t out[3]) { return bhr_march_resources("bhr_observer_resources", BHR_MV_OBSERVER, 0, 0, ss, out); }

@@ -204,7 +204,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  observer=None, observer_sky: bool = True, stars: Optional[dict] = None,
                  projection: Optional[str] = None, projection_fov=None, light_delay=None, polarization: Optional[dict] = None,
                  stokes_path: Optional[str] = None, ticks_path: Optional[str] = None, kerr_polarization: Optional[dict] = None,
-                 kerr_view: Optional[dict] = None, kerr_stars: Optional[dict] = None, kerr_passes_path: Optional[str] = None) -> np.ndarray:
+                 kerr_view: Optional[dict] = None, kerr_stars: Optional[dict] = None, kerr_passes_path: Optional[str] = None,
+                 kerr_anti_alias: Optional[float] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -237,7 +238,10 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     point stars around a spinning hole (check_kerr_stars): the starless sky, the catalogue as the Kerr map's, a Kerr ray map of the
     view, and the still from that map -- kerr_polarization's route, with which it combines.  ``kerr_passes_path``: ``passes_path``
     for a still under a spin (check_kerr_passes): also builds the Kerr ray map of the view and writes its passes, the frame's bg /
-    disk / blur layers, and the hole's spin and redshift there; the image itself is rendered as without it."""
+    disk / blur layers, and the hole's spin and redshift there; the image itself is rendered as without it.  ``kerr_anti_alias``: None,
+    or the LOD strength of the Kerr march's anti-aliasing (HipRenderer.set_kerr_anti_alias): ray differentials and mip LOD for a
+    spinning hole's marched frame -- with supersample, the exact redshift, lens flare and a grade; not without a spin, with the Kerr
+    ray map's features, the Kerr camera or several GPUs (rules.FEATURES["kerr_anti_alias"])."""
     check_depth_and_dither(bit_depth, dither=dither)
     # the facts of this call, built once; the features are refused in this order (rules.py has what each refuses)
     f = rules.Facts(dict(
@@ -245,7 +249,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         spin=spin, redshift=redshift, skybox_path=skybox_path, observer=observer is not None, projection=projection is not None, projection_fov=projection_fov,
         light_delay=light_delay is not None, stars=stars is not None, polarization=polarization is not None, kerr_polarization=kerr_polarization is not None,
         kerr_stars=kerr_stars is not None, passes=passes_path is not None, passes_path=passes_path, kerr_passes_path=kerr_passes_path, stokes_path=stokes_path,
-        ticks_path=ticks_path, **_kerr_view_facts(kerr_view)))
+        ticks_path=ticks_path, kerr_anti_alias=kerr_anti_alias is not None, **_kerr_view_facts(kerr_view)))
     kerr_view = checked("kerr_view", kerr_view, f)
     if kerr_view is not None:                                  # refused ahead of any device work, like the rest
         kerr_view_beta(kerr_view, cam_pos, spin)
@@ -269,6 +273,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     # the Kerr point stars and the Kerr passes, behind every refusal above: each names --spin_stars / --spin_passes and the other flag
     kerr_stars = checked("kerr_stars", kerr_stars, f)
     rules.refuse_on("kerr_passes", f)
+    kerr_anti_alias = _checked_kerr_anti_alias(kerr_anti_alias, f)
     if gpus > 1:
         from .multigpu import render_image_tiled
         return render_image_tiled(width, height, cam_pos, fov, gpus, step_size=step_size, skybox_path=skybox_path,
@@ -292,6 +297,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     print(f"HIP: {width}x{height}, cam_pos={list(cam_pos)}, fov={fov}°, step_size={step_size}")
     if grade is not None:
         renderer.set_grade(**grade)
+    if kerr_anti_alias is not None:
+        renderer.set_kerr_anti_alias(True, kerr_anti_alias)
     if polarization is not None:
         renderer.set_polarization(**polarization)          # ahead of the frame: its Stokes pass rides behind the shade launch
     if kerr_polarization is not None or kerr_stars is not None:
@@ -457,6 +464,18 @@ _VALID = {
     "polarization": _valid_stokes("polarization"), "kerr_polarization": _valid_stokes("--spin_polarization"),
     "observer": _valid_observer, "projection": _valid_projection, "light_delay": _valid_light_delay, "kerr_view": _valid_kerr_view,
 }
+
+
+def _checked_kerr_anti_alias(strength, facts):
+    """The LOD strength of the Kerr anti-aliasing as render_image / render_video take it, or None: finite and not negative, and what
+    rules.FEATURES["kerr_anti_alias"] refuses is refused."""
+    if strength is None:
+        return None
+    strength = float(strength)
+    if not (strength >= 0.0 and np.isfinite(strength)):
+        raise ValueError(f"--spin_aa_strength is finite and not negative, got {strength}")
+    rules.refuse("kerr_anti_alias", facts)
+    return strength
 
 
 def checked(feature: str, value, facts, surface: str = "api"):
@@ -906,7 +925,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
                  light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, spin_map: bool = False,
                  kerr_polarization: Optional[dict] = None, kerr_view: Optional[dict] = None, spin_map_supersample: int = 1,
-                 spin_shutter_map: bool = False, kerr_stars: Optional[dict] = None,
+                 spin_shutter_map: bool = False, kerr_stars: Optional[dict] = None, kerr_anti_alias: Optional[float] = None,
                  **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
@@ -1043,11 +1062,16 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     ``kerr_view`` (check_kerr_view's dict; the renderer has a spin or the exact redshift set): every frame is
     render_async(..., kerr_observer=beta_f, kerr_projection=...) -- the Kerr march through the Kerr camera, with the named velocity
     evaluated at that frame's own camera position (bhr_amd.observer.kerr_frame_plan), so an ``orbit`` with "circular" is the
-    fly-around on the equatorial geodesic.  The progress record carries the camera when one is given, and a resume under another starts over."""
+    fly-around on the equatorial geodesic.  The progress record carries the camera when one is given, and a resume under another starts over.
+
+    ``kerr_anti_alias`` (the LOD strength; the renderer has a spin or the exact redshift set): the Kerr march's anti-aliasing
+    (HipRenderer.set_kerr_anti_alias) is switched on for the video's marched frames, still or orbiting, and stays set on return.  A
+    renderer that has it on already counts as asked: either way the Kerr ray map's features, the Kerr camera and several ranks are
+    refused (rules.FEATURES["kerr_anti_alias"]).  The renderer is asked last of all, behind every other refusal."""
     # the facts of this call, built once: what the call says, and what the renderer is set to -- which is read when the first rule asks
     # for it and not before (without a feature that needs them the renderer is not asked anything, as ever)
     moving = observer is not None or observer_velocity is not None or infall_to is not None
-    f = rules.Facts(dict(
+    f = facts = rules.Facts(dict(
         video=True, orbit=orbit, shutter=shutter, world=world, ray_map=ray_map, orbit_map=orbit_map, shutter_map=shutter_map, spin_map=spin_map,
         spin_shutter_map=spin_shutter_map, map_supersample=map_supersample, spin_map_supersample=spin_map_supersample, supersample_said=supersample,
         observer=moving, projection=projection is not None or projection_fov is not None, projection_fov=projection_fov, light_delay=light_delay is not None,
@@ -1113,6 +1137,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     if mjpeg and not (isinstance(video_quality, int) and 1 <= video_quality <= 100):
         raise ValueError(f"video_quality must be an integer between 1 and 100, got {video_quality!r}")
     ext = ".jpg" if mjpeg else ".png"
+    if kerr_anti_alias is not None:                      # its own value and what the call itself says, ahead of any device work
+        kerr_anti_alias = _checked_kerr_anti_alias(kerr_anti_alias, f)
     if supersample is not None:
         renderer.set_supersample(supersample, supersample_threshold)
     elif supersample_threshold is not None:
@@ -1177,6 +1203,12 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         raise ValueError(f"polarization does not resume: {len(completed)} frames are already rendered and their cell grids are gone; "
                          "render without --resume")
 
+    # the Kerr anti-aliasing, behind every refusal above: asked for by the call, or on in the renderer (which is asked here, with the
+    # first device work, and not before)
+    if kerr_anti_alias is not None:
+        renderer.set_kerr_anti_alias(True, kerr_anti_alias)
+    elif getattr(renderer, "_kerr_anti_alias", None) is not None:
+        rules.refuse("kerr_anti_alias", facts)
     total_t0 = time.time()
     rendered = 0
     # the reference saves through a 2-thread PIL pool (render.py:4412-4413); here the frame is quantised

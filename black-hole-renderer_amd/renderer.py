@@ -167,6 +167,7 @@ class HipRenderer:
         # redshift="exact": the disk's g-factor of the Kerr metric instead of the reference's model (set_redshift)
         self._spin, self._force_kerr = 0.0, False
         self._redshift, self._redshift_forced = "model", False
+        self._kerr_anti_alias = None       # the LOD strength while the Kerr march carries ray differentials (set_kerr_anti_alias)
         if spin != 0.0 or redshift != "model":
             try:
                 if spin != 0.0:
@@ -1023,6 +1024,30 @@ class HipRenderer:
     @property
     def redshift(self) -> str:
         return self._redshift
+
+    def set_kerr_anti_alias(self, on: bool = True, strength: float = 1.0) -> None:
+        """Anti-aliasing of the disk around a spinning hole for the frames rendered from now on (bhr_set_kerr_anti_alias;
+        include/bhr.h states the model): the Kerr march carries ray differentials and every disk crossing samples the mip level
+        of its footprint, min(int(clamp(lod * strength, 0, 3)), last level).  It is the Kerr march's own switch
+        (anti_alias="lod_radius" is the Schwarzschild march's and stays refused with a spin): AssertionError without a spin or
+        the exact redshift, ValueError for a negative or non-finite strength.  While it is on, Kerr ray map builds, the Kerr
+        camera (render_async(kerr_observer=...)) and a set_spin that switches the Kerr march off are refused."""
+        _lib.check(self._lib.bhr_set_kerr_anti_alias(self._ctx, 1 if on else 0, float(strength)))
+        self._kerr_anti_alias = float(np.float32(strength)) if on else None
+
+    @property
+    def kerr_anti_alias(self) -> Optional[float]:
+        """The LOD strength of the Kerr anti-aliasing, None while it is off (set_kerr_anti_alias)."""
+        return self._kerr_anti_alias
+
+    def kerr_anti_alias_resources(self, supersampled: bool = False, redshift: str = "model") -> dict:
+        """Registers per lane, LDS and scratch bytes of the anti-aliased Kerr march kernel of a redshift mode
+        (bhr_kerr_anti_alias_resources)."""
+        from . import kerr
+        out = (C.c_int32 * 3)()
+        mode = _lib.REDSHIFT_EXACT if kerr.check_redshift(redshift) == "exact" else _lib.REDSHIFT_MODEL
+        _lib.check(self._lib.bhr_kerr_anti_alias_resources(mode, 1 if supersampled else 0, out))
+        return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
 
     def kerr_info(self) -> dict:
         """Radii of the hole of the current spin, in r_s: a, r_plus, r_isco_prograde, r_isco_retrograde, r_photon_pro,

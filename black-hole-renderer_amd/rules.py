@@ -25,6 +25,7 @@ FACTS = dict(
     # which features are on
     observer=False, projection=False, light_delay=False, stars=False, polarization=False, kerr_polarization=False, spin_observer=False,
     spin_projection=False, kerr_stars=False, passes=False, ray_map=False, orbit_map=False, shutter_map=False, spin_map=False, spin_shutter_map=False,
+    kerr_anti_alias=False,
     # the paths whose suffix is a row, and what a feature's own validation reads beside its value
     passes_path=None, kerr_passes_path=None, stokes_path=None, ticks_path=None, projection_fov=None,
     # the output side: the HDR stream of a video, the bits per sample
@@ -106,6 +107,8 @@ CONDITIONS = {
     "kerr_polarization": lambda f: f["kerr_polarization"],
     "spin_observer": lambda f: f["spin_observer"],
     "spin_projection": lambda f: f["spin_projection"],
+    "kerr_stars": lambda f: f["kerr_stars"],
+    "kerr_passes": lambda f: f["kerr_passes_path"] is not None,
     "sky_texture": lambda f: f["skybox_path"] is not None,
     "fov_given": lambda f: f["fov_given"],
     "video_ticks": lambda f: f["video"] and f["ticks_path"] is not None,
@@ -403,6 +406,21 @@ FEATURES = {
              "supersample": "{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel"},
         words=dict(who="--spin_passes", kerr_own="the passes come from the Kerr ray map", plain="--passes"),
         rows="no_spin video kerr_passes_not_npz supersample spin_observer spin_projection gpus"),
+    # anti-aliasing of the Kerr march (--spin_anti_alias lod_radius; HipRenderer.set_kerr_anti_alias): marched frames of the pinhole
+    # camera at rest, on one GPU -- the same words on both surfaces, each naming both flags
+    "kerr_anti_alias": dict(
+        on=lambda f: f["kerr_anti_alias"],
+        words=dict(who="--spin_anti_alias", no_words="a Kerr ray map's record has no differential words"),
+        say={"no_spin": "{who} needs --spin or --redshift exact: it is the anti-aliasing of the Kerr march; a hole that does not spin takes --anti_alias lod_radius",
+             "spin_map": "{who} does not combine with --spin_map: {no_words}",
+             "spin_shutter_map": "{who} does not combine with --spin_shutter_map: {no_words}",
+             "kerr_polarization": "{who} does not combine with --spin_polarization: {no_words}",
+             "kerr_stars": "{who} does not combine with --spin_stars: {no_words}",
+             "kerr_passes": "{who} does not combine with --spin_passes: {no_words}",
+             "spin_observer": "{who} does not combine with --spin_observer: the differential seeds would need the aberration's Jacobian",
+             "spin_projection": "{who} does not combine with --spin_projection: the differential seeds are the pinhole camera's",
+             "gpus_or_world": "{who} does not combine with --gpus other than 1 or several ranks: row-block tiles and frame-sharded ranks march Schwarzschild rays"},
+        rows="no_spin spin_map spin_shutter_map kerr_polarization kerr_stars kerr_passes spin_observer spin_projection gpus_or_world"),
     # a still image tiled in row blocks over several GPUs (render_image)
     "tiles": dict(on=lambda f: f["gpus"] > 1, rows=dict(api="grade supersample_set", cli=""),
                   say={"grade": "a grade renders on one GPU: row-block tiles store their rows from inside the V pass",

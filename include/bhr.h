@@ -637,6 +637,27 @@ BHR_API int32_t bhr_kerr_resources(int32_t supersampled, int32_t out[3]);
 BHR_API int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode);
 /* bhr_kerr_resources for the kernels of a redshift mode (BHR_REDSHIFT_MODEL: the same numbers). */
 BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, int32_t out[3]);
+/* Anti-aliasing of the disk around a spinning hole: ray differentials and mip LOD for the Kerr march (bhr_config.anti_alias
+ * is the Schwarzschild march's and stays refused with a spin).  on != 0: beside (x, p) every Kerr ray carries two tangents
+ * (xi, pi) = d(x, p) / d(pixel), one per pixel axis, integrated by the same RK4 step with the same h (a constant of the step)
+ * through the variational equations of the Hamiltonian system -- the right-hand side differentiated line by line in forward
+ * mode.  Seeds: xi = 0 and pi the differential of the camera's momentum p = s d + f Lam l under the pinhole's direction
+ * differential (the direction through the next pixel less the pixel's own), f and l being constants of the camera.  A
+ * crossing's hit differentials are the x and y components of the two xi at the end of the crossing step (the reference's
+ * convention, not projected onto the plane); its level of the disk texture's mip chain is
+ * min(int(clamp(lod * strength, 0, 3)), last level) with lod = log2(max(|d(u, v)/dx|^2, |d(u, v)/dy|^2, 1)) in the Kerr texture
+ * coordinates phi = atan2(hy, hx), r = sqrt(hx^2 + hy^2 - a^2) and the reference's 1e-6 guards; the roll's own derivative is
+ * ignored, as the reference ignores it.  The g-factor of both redshift modes and the compositing are unchanged, and so is the
+ * primal march: BG and the step count are the frame's without the switch, and at strength 0 so is DISK, bit for bit.
+ * (DESIGN.md "Kerr anti-aliasing"; tests/kerr_aa_ref.py is the CPU reference.)  Four kernels of the Kerr object of their own
+ * (model / exact redshift, plain / supersampled).  Ordered behind the frames in flight.
+ * BHR_ERR_STATE without the Kerr march (bhr_set_spin); BHR_ERR_INVALID for a negative or non-finite strength.  While the switch
+ * is on, BHR_ERR_INVALID naming the combination from bhr_kerr_raymap_build (a record has no differential words),
+ * bhr_render_kerr_view (the seeds would need the aberration's Jacobian) and from a bhr_set_spin that would switch the Kerr
+ * march off. */
+BHR_API int32_t bhr_set_kerr_anti_alias(bhr_ctx *ctx, int32_t on, float strength);
+/* bhr_kerr_resources for the anti-aliased kernel of a redshift mode. */
+BHR_API int32_t bhr_kerr_anti_alias_resources(int32_t redshift, int32_t supersampled, int32_t out[3]);
 /* The Kerr ray map: the ray map (bhr_raymap_build above) of a spinning hole, an object of its own beside it.  A Kerr ray's path
  * depends on the camera, the geometry of bhr_config and the spin, not on the skybox, the disk texture or t_offset.
  * bhr_kerr_raymap_build(ctx, cam, 0) marches the whole-frame view `cam` once with the Kerr march of the context's redshift
