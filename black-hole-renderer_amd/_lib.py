@@ -35,6 +35,7 @@ SYMBOLS = (
     "bhr_fill_comp_slice", "bhr_set_compose_stats", "bhr_compose_texture", "bhr_eval_noise", "bhr_render", "bhr_render_shutter",
     "bhr_set_spin", "bhr_kerr_resources", "bhr_set_redshift", "bhr_kerr_redshift_resources",
     "bhr_set_kerr_anti_alias", "bhr_kerr_anti_alias_resources",
+    "bhr_set_kerr_disk_source", "bhr_kerr_disk_resources",
     "bhr_render_observer", "bhr_observer_resources", "bhr_render_delayed", "bhr_delayed_resources",
     "bhr_render_projected", "bhr_projected_resources", "bhr_render_kerr_view", "bhr_kerr_view_resources",
     "bhr_raymap_build", "bhr_raymap_render", "bhr_raymap_render_view", "bhr_raymap_render_shutter", "bhr_raymap_read", "bhr_raymap_get_info", "bhr_raymap_free",
@@ -235,6 +236,8 @@ def load() -> C.CDLL:
     lib.bhr_kerr_redshift_resources.argtypes = [I32, I32, C.POINTER(C.c_int32)]
     lib.bhr_set_kerr_anti_alias.argtypes = [P, I32, C.c_float]
     lib.bhr_kerr_anti_alias_resources.argtypes = [I32, I32, C.POINTER(C.c_int32)]
+    lib.bhr_set_kerr_disk_source.argtypes = [P, I32, C.c_void_p, C.c_double, C.c_double, C.c_double]
+    lib.bhr_kerr_disk_resources.argtypes = [I32, I32, I32, C.POINTER(C.c_int32)]
     lib.bhr_render_observer.argtypes = [P, C.POINTER(Camera), C.POINTER(Observer), C.c_uint32]
     lib.bhr_observer_resources.argtypes = [I32, C.POINTER(C.c_int32)]
     lib.bhr_render_delayed.argtypes = [P, C.POINTER(Camera), C.POINTER(LightDelay), C.c_uint32]

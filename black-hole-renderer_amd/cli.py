@@ -10,7 +10,8 @@ time its light left the gas), ``--projection`` / ``--projection_fov`` (equirecta
 frames and fisheye dome masters instead of the pinhole camera), ``--polarization`` (Stokes Q / U maps of the disk through a ray map),
 ``--spin_observer`` / ``--spin_projection`` and their companions (the moving and the panoramic camera of a spinning hole),
 ``--spin_stars point`` (the catalogue of lensed points through a Kerr ray map), ``--spin_passes`` (a Kerr ray map's passes of a still)
-and ``--spin_anti_alias lod_radius`` / ``--spin_aa_strength`` (ray differentials and mip LOD for the spinning hole's disk).
+``--spin_anti_alias lod_radius`` / ``--spin_aa_strength`` (ray differentials and mip LOD for the spinning hole's disk) and
+``--spin_disk_model v2 | v2_volume`` (the analytic Disk V2 sources under a spin).
 """
 from __future__ import annotations
 
@@ -84,6 +85,13 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "Still images and --video [--orbit]; combines with --supersample, --redshift exact, --lens_flare, the grade "
                         "and every sink.  Not without --spin / --redshift exact, with --spin_map, --spin_shutter_map, "
                         "--spin_polarization, --spin_stars, --spin_passes, --spin_observer / --spin_projection or --gpus > 1")
+    p.add_argument("--spin_disk_model", type=str, default=argparse.SUPPRESS, choices=["v2", "v2_volume"],
+                   help="with --spin or --redshift exact: the Kerr march shades the analytic Disk V2 model instead of the disk texture -- "
+                        "v2: the thin disk's temperature law on the plane, inner edge at --disk_inner_radius; v2_volume: the "
+                        "finite-thickness emission-absorption integral (the model redshift only).  Stills and --video [--orbit], "
+                        "with --supersample, --lens_flare and a grade.  Not with --disk_model v2 / v2_volume, --spin_map, "
+                        "--spin_shutter_map, --spin_polarization, --spin_stars, --spin_passes, --spin_observer, --spin_projection, "
+                        "--spin_anti_alias or --gpus > 1")
     p.add_argument("--spin_aa_strength", type=float, default=argparse.SUPPRESS, metavar="S",
                    help="--spin_anti_alias lod_radius: LOD multiplier, finite and not negative (default: 1.0)")
     p.add_argument("--redshift", type=str, default="model", choices=["model", "exact"],
@@ -336,6 +344,7 @@ def parse_args(argv=None) -> argparse.Namespace:
         drivers._checked_kerr_anti_alias(kerr_anti_alias_from_args(args).get("kerr_anti_alias"), f)
     except ValueError as e:
         p.error(str(e))
+    refuse("kerr_disk_model", "api")              # (the drivers' words, likewise ahead of everything else: each names --spin_disk_model)
     refuse("shutter")
     refuse("spin_shutter_map", "api")             # (the drivers' words: ahead of every other check, so that each names --spin_shutter_map)
     refuse("spin_map_supersample spin_map")       # ahead of a spin's own, so that each names --spin_map
@@ -453,7 +462,7 @@ def facts_from_args(args, fov_given: bool):
         passes=args.passes is not None, passes_path=args.passes, kerr_passes_path=getattr(args, "spin_passes", None), ray_map=args.ray_map,
         orbit_map=args.orbit_map, shutter_map=args.shutter_map, spin_map=hasattr(args, "spin_map"), spin_shutter_map=hasattr(args, "spin_shutter_map"),
         video_hdr=args.video_hdr, hdr_white_given=args.hdr_white is not None, hdr_exposure_given=args.hdr_exposure is not None, video_codec=args.video_codec,
-        video_stream=args.video_stream, kerr_anti_alias=hasattr(args, "spin_anti_alias")))
+        video_stream=args.video_stream, kerr_anti_alias=hasattr(args, "spin_anti_alias"), kerr_disk_model=getattr(args, "spin_disk_model", "texture")))
 
 
 def kerr_anti_alias_from_args(args) -> dict:
@@ -664,6 +673,8 @@ def main(argv=None) -> int:
     pol_kw = polarization_from_args(args)
     # ... and the Kerr anti-aliasing
     aa_kw = kerr_anti_alias_from_args(args)
+    # ... and the Kerr march's Disk V2 source
+    dv2_kw = {"kerr_disk_model": args.spin_disk_model} if hasattr(args, "spin_disk_model") else {}
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))
@@ -686,6 +697,9 @@ def main(argv=None) -> int:
         if aa_kw:
             from . import rules
             rules.refuse("kerr_anti_alias", dict(spin=args.spin, redshift=args.redshift, world=world))
+        if dv2_kw:
+            from . import rules
+            rules.refuse("kerr_disk_model", dict(spin=args.spin, redshift=args.redshift, world=world, **dv2_kw))
         if "BHR_FORCE_DEVICE" in os.environ:        # rehearsal: several ranks sharing one card
             local_rank = int(os.environ["BHR_FORCE_DEVICE"])
         elif world > 1:                             # a launcher that shows every rank only its own GPU: ordinal 0
@@ -714,7 +728,7 @@ def main(argv=None) -> int:
                              **({"spin_map": True} if hasattr(args, "spin_map") else {}),
                              **({"spin_shutter_map": True} if hasattr(args, "spin_shutter_map") else {}),
                              **({"spin_map_supersample": args.spin_map_supersample} if hasattr(args, "spin_map_supersample") else {}),
-                             **kerr_stars_kw, **aa_kw)
+                             **kerr_stars_kw, **aa_kw, **dv2_kw)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -740,6 +754,6 @@ def main(argv=None) -> int:
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
         grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw, **stars_kw,
         **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw,
-        **kerr_stars_kw, **({"kerr_passes_path": args.spin_passes} if hasattr(args, "spin_passes") else {}), **aa_kw)
+        **kerr_stars_kw, **({"kerr_passes_path": args.spin_passes} if hasattr(args, "spin_passes") else {}), **aa_kw, **dv2_kw)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

@@ -49,34 +49,85 @@ extern "C" int32_t bhr_disk_v2_eval(bhr_ctx *ctx, const bhr_disk_v2_params *p, i
     return BHR_OK;
 }
 
-extern "C" int32_t bhr_set_disk_source(bhr_ctx *ctx, int32_t source, const bhr_disk_v2_params *p, double norm_shear,
-                                       double norm_hotspot, double t_peak) {
-    if (!ctx || (source != BHR_DISK_TEXTURE && source != BHR_DISK_V2 && source != BHR_DISK_V2_VOLUME))
-        return bhr_fail(BHR_ERR_INVALID, "bhr_set_disk_source: bad argument");
+// The disk source of one of the context's two slots -- kerr false: the Schwarzschild marches' (bhr_set_disk_source), true: the Kerr
+// march's (bhr_set_kerr_disk_source) -- behind the entry point's own refusals: the argument checks, then behind the frames in
+// flight the parameter block's upload, the norms and the volume's bounding slab into the slot's own fields.
+static int32_t set_source(bhr_ctx *ctx, const char *who, bool kerr, int32_t source, const bhr_disk_v2_params *p, double norm_shear, double norm_hotspot,
+                          double t_peak) {
+    if (source != BHR_DISK_TEXTURE && source != BHR_DISK_V2 && source != BHR_DISK_V2_VOLUME) return bhr_fail(BHR_ERR_INVALID, "%s: bad argument", who);
     BHR_TRY(bhr_enter(ctx));
     if (source != BHR_DISK_TEXTURE) {
         if (!p || !(norm_shear > 0.0) || !(norm_hotspot > 0.0) || !(t_peak > 0.0))
-            return bhr_fail(BHR_ERR_INVALID, "bhr_set_disk_source: Disk V2 needs parameters and positive normalisation constants");
+            return bhr_fail(BHR_ERR_INVALID, "%s: Disk V2 needs parameters and positive normalisation constants", who);
         if (!(p->r_out > p->r_in) || !(p->r_in > 0.0) || !(p->h0 > 0.0) || p->shear_components < 0 ||
             p->shear_components > BHR_DV2_MAX_TERMS || p->hotspot_count < 0 || p->hotspot_count > BHR_DV2_MAX_TERMS)
-            return bhr_fail(BHR_ERR_INVALID, "bhr_set_disk_source: inconsistent Disk V2 parameters");
-        if (!ctx->d_dv2_params) BHR_HIP(hipMalloc((void **)&ctx->d_dv2_params, sizeof(bhr_disk_v2_params)));
-        BHR_HIP(hipMemcpyAsync(ctx->d_dv2_params, p, sizeof(*p), hipMemcpyHostToDevice, ctx->stream));
+            return bhr_fail(BHR_ERR_INVALID, "%s: inconsistent Disk V2 parameters", who);
+        bhr_disk_v2_params *&d_params = kerr ? ctx->d_kerr_dv2_params : ctx->d_dv2_params;
+        double *norm = kerr ? ctx->kerr_dv2_norm : ctx->dv2_norm, *bound = kerr ? ctx->kerr_vol_bound : ctx->vol_opts + 2;
+        if (!d_params) BHR_HIP(hipMalloc((void **)&d_params, sizeof(bhr_disk_v2_params)));
+        BHR_HIP(hipMemcpyAsync(d_params, p, sizeof(*p), hipMemcpyHostToDevice, ctx->stream));
         BHR_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->dv2_norm[0] = norm_shear;
-        ctx->dv2_norm[1] = norm_hotspot;
-        ctx->dv2_norm[2] = t_peak;
+        norm[0] = norm_shear;
+        norm[1] = norm_hotspot;
+        norm[2] = t_peak;
         // bounding slab of the volume: H(r) = h0 r (r / r_in)^beta is monotonic, its maximum sits at an end
         const double h_in = p->h0 * p->r_in, h_out = p->h0 * p->r_out * pow(p->r_out / p->r_in, p->beta_h);
-        ctx->vol_opts[2] = h_in > h_out ? h_in : h_out;
-        ctx->vol_opts[3] = sqrt(p->r_out * p->r_out + ctx->vol_opts[2] * ctx->vol_opts[2]);
+        bound[0] = h_in > h_out ? h_in : h_out;
+        bound[1] = sqrt(p->r_out * p->r_out + bound[0] * bound[0]);
         if (ctx->vol_substeps == 0) {   // options never set: defaults
             ctx->vol_opts[0] = 4.0;
             ctx->vol_opts[1] = 1.0;
             ctx->vol_substeps = 2;
         }
     }
-    ctx->disk_source = source;
+    (kerr ? ctx->kerr_disk_source : ctx->disk_source) = source;
+    return BHR_OK;
+}
+
+extern "C" int32_t bhr_set_disk_source(bhr_ctx *ctx, int32_t source, const bhr_disk_v2_params *p, double norm_shear,
+                                       double norm_hotspot, double t_peak) {
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "bhr_set_disk_source: bad argument");
+    return set_source(ctx, "bhr_set_disk_source", false, source, p, norm_shear, norm_hotspot, t_peak);
+}
+
+// The Kerr march's own disk source (include/bhr_disk_v2.h).  Everything it does not combine with is refused here or where the
+// other side is set, each naming the combination; then set_source, and the counters name the kernel that marches the frames.
+extern "C" int32_t bhr_set_kerr_disk_source(bhr_ctx *ctx, int32_t source, const bhr_disk_v2_params *p, double norm_shear,
+                                            double norm_hotspot, double t_peak) {
+    const char *who = "bhr_set_kerr_disk_source";
+    if (!ctx) return bhr_fail(BHR_ERR_INVALID, "%s: null ctx", who);
+    if (source != BHR_DISK_TEXTURE && source != BHR_DISK_V2 && source != BHR_DISK_V2_VOLUME)
+        return bhr_fail(BHR_ERR_INVALID, "%s: unknown source %d (BHR_DISK_TEXTURE = 0, BHR_DISK_V2 = 1, BHR_DISK_V2_VOLUME = 2)", who, source);
+    if (source != BHR_DISK_TEXTURE) {
+        if (!ctx->kerr_on)
+            return bhr_fail(BHR_ERR_STATE, "%s: a Kerr Disk V2 source without the Kerr march: set a spin, or force_kerr at spin 0, first (bhr_set_spin)", who);
+        if (source == BHR_DISK_V2_VOLUME && ctx->kerr_redshift == BHR_REDSHIFT_EXACT)
+            return bhr_fail(BHR_ERR_INVALID, "%s: the Disk V2 volume with the exact redshift (bhr_set_redshift): gas off the equatorial plane has no four-velocity in this model; "
+                            "set BHR_REDSHIFT_MODEL first", who);
+        if (ctx->kerr_aa)
+            return bhr_fail(BHR_ERR_INVALID, "%s: a Kerr Disk V2 source with the Kerr anti-aliasing on (bhr_set_kerr_anti_alias): the analytic source has no mip chain; switch it off first", who);
+        if (ctx->kerr_raymap && ctx->kerr_raymap->built)
+            return bhr_fail(BHR_ERR_INVALID, "%s: a Kerr Disk V2 source while a Kerr ray map is built (bhr_kerr_raymap_build): a frame from the map shades the disk texture; free it first (bhr_kerr_raymap_free)", who);
+    }
+    BHR_TRY(set_source(ctx, who, true, source, p, norm_shear, norm_hotspot, t_peak));
+    return bhr_note_frame_kernel(ctx);
+}
+
+extern "C" int32_t bhr_kerr_disk_resources(int32_t source, int32_t mode, int32_t ss, int32_t out[3]) {
+    const char *who = "bhr_kerr_disk_resources";
+    if (!out) return bhr_fail(BHR_ERR_INVALID, "%s: null argument", who);
+    if (source != BHR_DISK_V2 && source != BHR_DISK_V2_VOLUME) return bhr_fail(BHR_ERR_INVALID, "%s: source %d (BHR_DISK_V2 = 1 or BHR_DISK_V2_VOLUME = 2)", who, source);
+    if (mode != BHR_REDSHIFT_MODEL && mode != BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "%s: unknown mode %d (BHR_REDSHIFT_MODEL = 0, BHR_REDSHIFT_EXACT = 1)", who, mode);
+    if (source == BHR_DISK_V2_VOLUME && mode == BHR_REDSHIFT_EXACT)
+        return bhr_fail(BHR_ERR_INVALID, "%s: the Disk V2 volume with the exact redshift: there is no such kernel", who);
+    const void *f = bhr_kerr_dv2_kernel(source, mode, ss ? 1 : 0);
+    if (!f) return bhr_fail(BHR_ERR_STATE, "%s: no such march kernel in this library", who);
+    hipFuncAttributes at;
+    BHR_HIP(hipFuncGetAttributes(&at, f));
+    out[0] = at.numRegs;
+    out[1] = (int32_t)at.sharedSizeBytes;
+    out[2] = (int32_t)at.localSizeBytes;
     return BHR_OK;
 }
 

@@ -70,6 +70,7 @@ int32_t bhr_kerr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cam
         return bhr_fail(BHR_ERR_INVALID, "%s: flags %u (BHR_SKIP_BLOOM and BHR_LENS_FLARE only)", who, flags);
     for (int j = 0; j < n; ++j)
         if (!isfinite(cams[j].t_offset)) return bhr_fail(BHR_ERR_INVALID, "%s: sample %d: t_offset is not finite", who, j);
+    BHR_TRY(bhr_kerr_disk_refuse(ctx, who, "a shutter frame from the Kerr ray map shades the disk texture"));
     // the Kerr Stokes kernel walks one frame's records: a mean of frames has no Stokes planes (bhr_raymap_render_shutter likewise)
     if (bhr_have_kerr_polar(ctx))
         return bhr_fail(BHR_ERR_STATE, "%s: a Kerr polarisation is set (bhr_set_kerr_polarization) and shutter frames from the map have no Stokes planes -- switch it off (NULL) first", who);
@@ -113,6 +114,7 @@ int32_t bhr_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flag
     // the map's own factor: the map of the fine frame, k rows x k W (the context's own supersampling stays off, check_context)
     const int32_t ss = ctx->opt.kerr_raymap_ss;
     BHR_TRY(check_context(ctx, who, ss));
+    BHR_TRY(bhr_kerr_disk_refuse(ctx, who, "a frame from the Kerr ray map shades the disk texture"));
     if (ctx->kerr_aa)
         return bhr_fail(BHR_ERR_INVALID, "%s: the Kerr anti-aliasing is on (bhr_set_kerr_anti_alias) and a Kerr ray map's record has no differential words; switch it off first", who);
     const int32_t K = ctx->opt.raymap_slots;

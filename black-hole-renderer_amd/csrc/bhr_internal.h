@@ -616,6 +616,14 @@ struct bhr_ctx {
     // the Kerr ray map, into the same slot planes
     int32_t kerr_polar_on;
     bhr_polarization kerr_polar;
+
+    // the Kerr march's own disk source (bhr_set_kerr_disk_source; api_disk_v2.hip): BHR_DISK_TEXTURE, or a Disk V2 source with a
+    // parameter block, norms and bounding slab of its own beside disk_source's above (which stays refused with a spin); absorption,
+    // grazing gain and substeps are vol_opts[0], [1] and vol_substeps for both
+    int32_t kerr_disk_source;
+    bhr_disk_v2_params *d_kerr_dv2_params;
+    double kerr_dv2_norm[3];   // max|raw shear|, max|raw hotspot|, peak T_mid
+    double kerr_vol_bound[2];  // max half thickness H_max; sqrt(r_out^2 + H_max^2), the largest Kerr-Schild radius of the volume
 };
 
 // The active frame slot: the one bhr_activate_slot / bhr_render last pointed the launchers at.
@@ -750,6 +758,8 @@ int32_t bhr_variant_frame_check(const bhr_ctx *ctx, bhr_march_variant v, uint32_
 int32_t bhr_kerr_refuse(const bhr_ctx *ctx, const char *who, const char *what);
 // a camera inside the static limit: BHR_ERR_INVALID, before anything is launched
 int32_t bhr_kerr_camera_check(const bhr_ctx *ctx, const bhr_camera *cam, const char *who);
+// a call that has no form over the Kerr march's Disk V2 source (bhr_set_kerr_disk_source): BHR_ERR_INVALID while one is set
+int32_t bhr_kerr_disk_refuse(const bhr_ctx *ctx, const char *who, const char *what);
 
 // ---- counters.hip -------------------------------------------------------------------------------------------------------------------
 float bhr_ev_ms(hipEvent_t a, hipEvent_t b);                               // milliseconds between two recorded events, -1 where there are none
@@ -796,6 +806,9 @@ const void *bhr_march_kernel_observer(bhr_march_kernel k, int32_t diff, int32_t 
 const void *bhr_march_kernel_projected(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_projected.hip -> march_projected.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_delay(bhr_march_kernel k, int32_t diff, int32_t ss);      // march_delay.hip -> march_delay.o (BHR_MK_TILE, diff 0 only)
 const void *bhr_march_kernel_kerr(bhr_march_kernel k, int32_t diff, int32_t ss);       // march_kerr.hip -> march_kerr.o (BHR_MK_TILE or BHR_MK_KERR_EXACT; diff: the Ray with differentials, bhr_set_kerr_anti_alias)
+const void *bhr_march_kernel_kerr_dv2(bhr_march_kernel k, int32_t diff, int32_t ss);   // march_kerr_dv2.hip -> march_kerr_dv2.o (BHR_MK_DV2, BHR_MK_KERR_EXACT: the Disk V2 surface, model / exact; BHR_MK_VOLUME; diff 0 only)
+// the kernel that marches a Kerr frame over the Kerr disk source `source` (not the texture) under redshift `mode`; null: none
+const void *bhr_kerr_dv2_kernel(int32_t source, int32_t mode, int32_t ss);
 const void *bhr_march_kernel_kerr_view(bhr_march_kernel k, int32_t diff, int32_t ss);  // march_kerr_observer.hip -> march_kerr_observer.o (as bhr_march_kernel_kerr)
 const void *bhr_march_kernel_kerr_raymap(bhr_march_kernel k, int32_t exact, int32_t ss);   // march_kerr_raymap.hip -> march_kerr_raymap.o (exact: the exact redshift's; ss: a supersampled map's)
 int32_t bhr_selftest_strict(bhr_ctx *ctx, unsigned long long *d_out4);                 // march_strict.hip -> march_strict.o

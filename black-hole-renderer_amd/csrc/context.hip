@@ -203,7 +203,7 @@ void bhr_destroy(bhr_ctx *ctx) {
     if (ctx->sync_ev) (void)hipEventDestroy(ctx->sync_ev);
     void *bufs[] = {ctx->d_skybox,
                     ctx->d_wtab, ctx->d_wsum_h, ctx->d_wsum_v, ctx->d_ray_steps, ctx->d_noise_in,
-                    ctx->d_noise_out, ctx->d_steps_ring, ctx->d_steps_fold, ctx->d_pool, ctx->d_pairs, ctx->d_stats_scratch, ctx->d_wext, ctx->d_w16, ctx->d_dv2_params,
+                    ctx->d_noise_out, ctx->d_steps_ring, ctx->d_steps_fold, ctx->d_pool, ctx->d_pairs, ctx->d_stats_scratch, ctx->d_wext, ctx->d_w16, ctx->d_dv2_params, ctx->d_kerr_dv2_params,
                     ctx->d_flare_prog, ctx->d_tile_order, ctx->d_row_steps, ctx->d_gather, ctx->d_dither};
     for (void *b : bufs)
         if (b) (void)hipFree(b);

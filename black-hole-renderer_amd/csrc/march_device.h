@@ -46,6 +46,9 @@
 //              -ffp-contract=on, no fast-math
 //              (and march_kerr_raymap.hip -> march_kerr_raymap.o over the same Ray: the Kerr ray map's build, shade and
 //              overflow kernels, with the Kerr object's flags; its table is bhr_march_kernel_kerr_raymap)
+//              (and march_kerr_dv2.hip -> march_kerr_dv2.o over ray_kerr_dv2.h's Ray, derived from the Kerr one: the Kerr march over
+//              the analytic Disk V2 sources, surface and volume (bhr_set_kerr_disk_source); the Kerr object's flags; its table is
+//              bhr_march_kernel_kerr_dv2, picked by march_kernel under the Kerr variants while a Kerr source is set)
 //   kerr_observer  the Kerr Ray launched along the aberrated pinhole, equirectangular or fisheye direction of a camera that may
 //              move, its Doppler factor in the disk's g and on the sky (bhr_render_kerr_view); the Kerr object's flags;
 //              camera_device.h holds what it shares with the next two (the projections' directions, the sky's scaling)

@@ -69,6 +69,7 @@ float fast_sqrt(float s) {
 //
 //   arithmetic     request                                              kernel (object)
 //   any            a march variant v (call.req.variant), whole block    its row's kernel: kernels(name, 0, ss) of bhr_variant_row_of(v)
+//   any            BHR_MV_KERR / _EXACT under a Kerr Disk V2 source      march_kerr_dv2[_exact | _volume][_ss]_kernel (kerr_dv2)
 //   any            a Kerr variant, fix list (part->repair == 2)         kerr_raymap_fix_kernel<RS, ss> (kerr_raymap)
 //   any            hybrid part with n <= 0, not the fix list            none
 //   strict         hybrid fix list (part->repair == 2)                  march_fix_kernel<diff> (strict_ilp)
@@ -112,7 +113,10 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
             k.grid = dim3((a.fix_cap / 64 + 3) / 4);
             return k;
         }
-        if (!part && !persistent && !a.row_steps && !a.dv2) k.fn = r.kernels(r.name, diff, ss);
+        // the Kerr march's own Disk V2 source (bhr_set_kerr_disk_source): march_kerr_dv2.o's kernel of the source and the redshift
+        const bool kerr_dv2 = (v == BHR_MV_KERR || v == BHR_MV_KERR_EXACT) && ctx->kerr_disk_source != BHR_DISK_TEXTURE;
+        if (!part && !persistent && !a.row_steps && !a.dv2)
+            k.fn = kerr_dv2 ? (diff ? nullptr : bhr_kerr_dv2_kernel(ctx->kerr_disk_source, v == BHR_MV_KERR_EXACT, ss)) : r.kernels(r.name, diff, ss);
         return k;
     }
     if (part && part->n <= 0 && part->repair != 2) return k;
@@ -160,6 +164,12 @@ MarchKernel march_kernel(bhr_ctx *ctx, BhrMarchArgs &a, const bhr_march_part *pa
 }
 
 }  // namespace
+
+const void *bhr_kerr_dv2_kernel(int32_t source, int32_t mode, int32_t ss) {
+    if (source == BHR_DISK_V2_VOLUME) return mode == BHR_REDSHIFT_EXACT ? nullptr : bhr_march_kernel_kerr_dv2(BHR_MK_VOLUME, 0, ss);
+    if (source == BHR_DISK_V2) return bhr_march_kernel_kerr_dv2(mode == BHR_REDSHIFT_EXACT ? BHR_MK_KERR_EXACT : BHR_MK_DV2, 0, ss);
+    return nullptr;
+}
 
 // The arithmetic of a march: the context's math_mode unless the call forces one.  Hybrid is launches over complementary tile
 // lists (hybrid.hip); the schedules and disk sources that have no list form run strict.  bhr_frame_begin picks the frame's
@@ -323,6 +333,16 @@ static void *variant_args(const bhr_ctx *ctx, const bhr_variant_request &req, Bh
         k.kerr_a = (float)(0.5 * A);
         k.kerr_rplus = (float)(0.5 * (1.0 + sqrt(1.0 - A * A)));
         if (ctx->kerr_aa) k.aa_strength = ctx->kerr_aa_strength;       // the Kerr march's own LOD strength (bhr_set_kerr_anti_alias)
+        // the Kerr march's own Disk V2 source (bhr_set_kerr_disk_source), for march_kerr_dv2.o's kernels alone: its parameter block,
+        // norms and slab in the march block's Disk V2 words -- vol_r_max with the spin in it, sqrt(R^2 + a^2) (ray_kerr_dv2.h: the cull)
+        if ((req.variant == BHR_MV_KERR || req.variant == BHR_MV_KERR_EXACT) && ctx->kerr_disk_source != BHR_DISK_TEXTURE) {
+            k.dv2 = ctx->d_kerr_dv2_params;
+            k.dv2_norm_shear = ctx->kerr_dv2_norm[0];
+            k.dv2_norm_hotspot = ctx->kerr_dv2_norm[1];
+            k.dv2_t_peak = ctx->kerr_dv2_norm[2];
+            k.vol_h_max = ctx->kerr_vol_bound[0];
+            k.vol_r_max = sqrt(ctx->kerr_vol_bound[1] * ctx->kerr_vol_bound[1] + 0.25 * A * A);
+        }
         // ... and, for the exact-redshift kernels alone, the ISCO of the disk's sense of rotation (prograde for A >= 0) with the
         // energy and angular momentum of its orbit (Bardeen, Press, Teukolsky 1972; M = 1/2, signed a, an orbit in the +phi sense)
         k.isco_r = k.isco_e = k.isco_l = 0.0f;

@@ -675,10 +675,12 @@ struct KerrRay {
 };
 
 // The Ray the schedules and the Kerr map's kernels march: the Kerr one itself, unless the Ray header that included this file
-// derives its own from it (ray_kerr_observer.h) -- the idiom of ray_strict.h.
+// derives its own from it (ray_kerr_observer.h, ray_kerr_dv2.h) -- the idiom of ray_strict.h.
 #ifndef BHR_RAY_KERR_OBSERVER
+#ifndef BHR_RAY_KERR_DV2
 template <bool DIFF, int SRC = 0, bool MOM = false>
 using Ray = KerrRay<DIFF, SRC, MOM>;
+#endif
 #endif
 
 }  // namespace

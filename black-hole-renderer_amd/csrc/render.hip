@@ -321,6 +321,7 @@ int32_t bhr_render_kerr_view(bhr_ctx *ctx, const bhr_camera *cam, const bhr_obse
         return bhr_fail(BHR_ERR_INVALID, "%s: a Kerr view without the Kerr march: set a spin, or force_kerr at spin 0, first (bhr_set_spin)", who);
     if (ctx->kerr_aa)
         return bhr_fail(BHR_ERR_INVALID, "%s: a Kerr view with the Kerr anti-aliasing on (bhr_set_kerr_anti_alias): the differential seeds would need the aberration's Jacobian; switch it off first", who);
+    BHR_TRY(bhr_kerr_disk_refuse(ctx, who, "the Kerr camera's march shades the disk texture"));
     if (proj) BHR_TRY(projection_check(proj, who));
     const bhr_observer o = obs ? *obs : observer_at_rest;
     BHR_TRY(observer_beta_check(&o, who));

@@ -64,7 +64,10 @@ const bhr_variant_row &bhr_variant_row_of(bhr_march_variant v) {
 int32_t bhr_note_frame_kernel(bhr_ctx *ctx) {
     int32_t res[3];
     const bhr_march_variant v = bhr_variant_of(ctx);
-    BHR_TRY(bhr_march_resources("bhr_note_frame_kernel", v, ctx->cfg.math_mode, bhr_want_diff(ctx, 0, v), 0, res));
+    if ((v == BHR_MV_KERR || v == BHR_MV_KERR_EXACT) && ctx->kerr_disk_source != BHR_DISK_TEXTURE)
+        BHR_TRY(bhr_kerr_disk_resources(ctx->kerr_disk_source, ctx->kerr_redshift, 0, res));       // the Kerr march's own Disk V2 source: march_kerr_dv2.o's
+    else
+        BHR_TRY(bhr_march_resources("bhr_note_frame_kernel", v, ctx->cfg.math_mode, bhr_want_diff(ctx, 0, v), 0, res));
     ctx->counters.march_vgprs = res[0];
     ctx->counters.march_lds_bytes = res[1];
     return BHR_OK;
@@ -128,6 +131,12 @@ int32_t bhr_kerr_camera_check(const bhr_ctx *ctx, const bhr_camera *cam, const c
     return BHR_OK;
 }
 
+// A call that has no form over the Kerr march's own Disk V2 source; the refusal names the combination.
+int32_t bhr_kerr_disk_refuse(const bhr_ctx *ctx, const char *who, const char *what) {
+    if (!ctx || ctx->kerr_disk_source == BHR_DISK_TEXTURE) return BHR_OK;
+    return bhr_fail(BHR_ERR_INVALID, "%s: a Kerr Disk V2 source is set (bhr_set_kerr_disk_source, %d) and %s; set BHR_DISK_TEXTURE first", who, ctx->kerr_disk_source, what);
+}
+
 extern "C" {
 
 int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr) {
@@ -139,6 +148,8 @@ int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr) {
         return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin 0 without force_kerr while the exact redshift is set (bhr_set_redshift): it is a Kerr kernel's; set BHR_REDSHIFT_MODEL first");
     if (!on && ctx->kerr_aa)
         return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin 0 without force_kerr while the Kerr anti-aliasing is on (bhr_set_kerr_anti_alias): it is a Kerr kernel's; switch it off first");
+    if (!on && ctx->kerr_disk_source != BHR_DISK_TEXTURE)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_set_spin: spin 0 without force_kerr while a Kerr Disk V2 source is set (bhr_set_kerr_disk_source): it is a Kerr kernel's; set BHR_DISK_TEXTURE first");
     if (on == ctx->kerr_on && a_over_m == ctx->kerr_spin) return BHR_OK;
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight, like every other change of what a frame is
     ctx->kerr_on = on;
@@ -153,6 +164,9 @@ int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode) {
         return bhr_fail(BHR_ERR_INVALID, "bhr_set_redshift: unknown mode %d (BHR_REDSHIFT_MODEL = 0, BHR_REDSHIFT_EXACT = 1)", mode);
     if (mode == BHR_REDSHIFT_EXACT && !ctx->kerr_on)
         return bhr_fail(BHR_ERR_INVALID, "bhr_set_redshift: the exact redshift without the Kerr march: set a spin, or force_kerr at spin 0, first (bhr_set_spin)");
+    if (mode == BHR_REDSHIFT_EXACT && ctx->kerr_disk_source == BHR_DISK_V2_VOLUME)
+        return bhr_fail(BHR_ERR_INVALID, "bhr_set_redshift: the exact redshift with the Disk V2 volume (bhr_set_kerr_disk_source): gas off the equatorial plane has no four-velocity in this model; "
+                        "set the surface source (BHR_DISK_V2) or BHR_DISK_TEXTURE first");
     if (mode == ctx->kerr_redshift) return BHR_OK;
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight
     ctx->kerr_redshift = mode;
@@ -166,6 +180,7 @@ int32_t bhr_set_kerr_anti_alias(bhr_ctx *ctx, int32_t on, float strength) {
         return bhr_fail(BHR_ERR_INVALID, "bhr_set_kerr_anti_alias: strength %g (finite and not negative)", (double)strength);
     if (on && !ctx->kerr_on)
         return bhr_fail(BHR_ERR_STATE, "bhr_set_kerr_anti_alias: Kerr anti-aliasing without the Kerr march: set a spin, or force_kerr at spin 0, first (bhr_set_spin)");
+    if (on) BHR_TRY(bhr_kerr_disk_refuse(ctx, "bhr_set_kerr_anti_alias", "the analytic source has no mip chain for the Kerr anti-aliasing"));
     const int32_t aa = on ? 1 : 0;
     if (aa == ctx->kerr_aa && (!aa || strength == ctx->kerr_aa_strength)) return BHR_OK;
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight

@@ -139,6 +139,28 @@ def use_analytic_disk(renderer: HipRenderer, disk_model: str) -> bool:
     return True
 
 
+KERR_DISK_MODELS = ("texture", "v2", "v2_volume")
+
+
+def use_kerr_analytic_disk(renderer: HipRenderer, kerr_disk_model: str) -> bool:
+    """--spin_disk_model v2 / v2_volume: use_analytic_disk for the Kerr march (HipRenderer.use_kerr_disk_v2)."""
+    if kerr_disk_model == "texture":
+        return False
+    from .disk_v2 import DiskV2Params
+    renderer.use_kerr_disk_v2(DiskV2Params(r_in=renderer.r_disk_inner, r_out=renderer.r_disk_outer), seed=42,
+                              volume=kerr_disk_model == "v2_volume")
+    return True
+
+
+def _checked_kerr_disk_model(kerr_disk_model, facts) -> str:
+    """The Kerr march's disk source as render_image / render_video take it: one of KERR_DISK_MODELS, and what
+    rules.FEATURES["kerr_disk_model"] refuses is refused."""
+    if kerr_disk_model not in KERR_DISK_MODELS:
+        raise ValueError(f"--spin_disk_model is one of {KERR_DISK_MODELS}, got {kerr_disk_model!r}")
+    rules.refuse_on("kerr_disk_model", facts)
+    return kerr_disk_model
+
+
 def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, n_stars=6000, tex_w=2048,
                   tex_h=1024, r_max=10.0, disk_texture_path=None, r_disk_inner=R_DISK_INNER_DEFAULT,
                   r_disk_outer=R_DISK_OUTER_DEFAULT, disk_tilt=0.0, lens_flare=False, anti_alias="disabled",
@@ -205,7 +227,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  projection: Optional[str] = None, projection_fov=None, light_delay=None, polarization: Optional[dict] = None,
                  stokes_path: Optional[str] = None, ticks_path: Optional[str] = None, kerr_polarization: Optional[dict] = None,
                  kerr_view: Optional[dict] = None, kerr_stars: Optional[dict] = None, kerr_passes_path: Optional[str] = None,
-                 kerr_anti_alias: Optional[float] = None) -> np.ndarray:
+                 kerr_anti_alias: Optional[float] = None, kerr_disk_model: str = "texture") -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -241,7 +263,11 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     disk / blur layers, and the hole's spin and redshift there; the image itself is rendered as without it.  ``kerr_anti_alias``: None,
     or the LOD strength of the Kerr march's anti-aliasing (HipRenderer.set_kerr_anti_alias): ray differentials and mip LOD for a
     spinning hole's marched frame -- with supersample, the exact redshift, lens flare and a grade; not without a spin, with the Kerr
-    ray map's features, the Kerr camera or several GPUs (rules.FEATURES["kerr_anti_alias"])."""
+    ray map's features, the Kerr camera or several GPUs (rules.FEATURES["kerr_anti_alias"]).  ``kerr_disk_model``: "texture", or
+    "v2" / "v2_volume" -- the Kerr march shades the Disk V2 model with the renderer's radii and default structure, as a surface on
+    the plane or as the finite-thickness volume (HipRenderer.use_kerr_disk_v2; use_kerr_analytic_disk): with supersample, the
+    exact redshift (v2), lens flare and a grade; not without a spin, with disk_model, the Kerr ray map's features, the Kerr camera,
+    the Kerr anti-aliasing or several GPUs (rules.FEATURES["kerr_disk_model"])."""
     check_depth_and_dither(bit_depth, dither=dither)
     # the facts of this call, built once; the features are refused in this order (rules.py has what each refuses)
     f = rules.Facts(dict(
@@ -249,7 +275,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         spin=spin, redshift=redshift, skybox_path=skybox_path, observer=observer is not None, projection=projection is not None, projection_fov=projection_fov,
         light_delay=light_delay is not None, stars=stars is not None, polarization=polarization is not None, kerr_polarization=kerr_polarization is not None,
         kerr_stars=kerr_stars is not None, passes=passes_path is not None, passes_path=passes_path, kerr_passes_path=kerr_passes_path, stokes_path=stokes_path,
-        ticks_path=ticks_path, kerr_anti_alias=kerr_anti_alias is not None, **_kerr_view_facts(kerr_view)))
+        ticks_path=ticks_path, kerr_anti_alias=kerr_anti_alias is not None, kerr_disk_model=kerr_disk_model, **_kerr_view_facts(kerr_view)))
+    kerr_disk_model = _checked_kerr_disk_model(kerr_disk_model, f)      # ahead of the rest, so that each refusal names --spin_disk_model
     kerr_view = checked("kerr_view", kerr_view, f)
     if kerr_view is not None:                                  # refused ahead of any device work, like the rest
         kerr_view_beta(kerr_view, cam_pos, spin)
@@ -288,7 +315,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         supersample=supersample, supersample_threshold=supersample_threshold, spin=spin,
         **({"redshift": redshift} if redshift != "model" else {}), **({} if stars is None else {"stars": stars}),
         **({} if kerr_stars is None else {"kerr_stars": kerr_stars}))
-    if use_analytic_disk(renderer, disk_model):
+    if use_analytic_disk(renderer, disk_model) or use_kerr_analytic_disk(renderer, kerr_disk_model):
         pass
     elif use_lifecycle:
         factories = init_lifecycle_system(renderer, n_r, n_phi, seed=42)
@@ -925,7 +952,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  infall_to: Optional[float] = None, stars: Optional[dict] = None, projection: Optional[str] = None, projection_fov=None,
                  light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, spin_map: bool = False,
                  kerr_polarization: Optional[dict] = None, kerr_view: Optional[dict] = None, spin_map_supersample: int = 1,
-                 spin_shutter_map: bool = False, kerr_stars: Optional[dict] = None, kerr_anti_alias: Optional[float] = None,
+                 spin_shutter_map: bool = False, kerr_stars: Optional[dict] = None, kerr_anti_alias: Optional[float] = None, kerr_disk_model: str = "texture",
                  **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
@@ -1067,7 +1094,10 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     ``kerr_anti_alias`` (the LOD strength; the renderer has a spin or the exact redshift set): the Kerr march's anti-aliasing
     (HipRenderer.set_kerr_anti_alias) is switched on for the video's marched frames, still or orbiting, and stays set on return.  A
     renderer that has it on already counts as asked: either way the Kerr ray map's features, the Kerr camera and several ranks are
-    refused (rules.FEATURES["kerr_anti_alias"]).  The renderer is asked last of all, behind every other refusal."""
+    refused (rules.FEATURES["kerr_anti_alias"]).  The renderer is asked last of all, behind every other refusal.
+    ``kerr_disk_model``: "texture", or "v2" / "v2_volume" -- the Kerr march's Disk V2 source (HipRenderer.use_kerr_disk_v2 with the
+    renderer's radii and default structure) for the video's marched frames, still or orbiting; it stays set on return.  What
+    rules.FEATURES["kerr_disk_model"] refuses is refused ahead of everything else."""
     # the facts of this call, built once: what the call says, and what the renderer is set to -- which is read when the first rule asks
     # for it and not before (without a feature that needs them the renderer is not asked anything, as ever)
     moving = observer is not None or observer_velocity is not None or infall_to is not None
@@ -1078,6 +1108,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         stars=stars is not None, kerr_polarization=kerr_polarization is not None, kerr_stars=kerr_stars is not None, stokes_path=stokes_path,
         # (stokes_path alone counts as polarization's unless kerr_polarization, which it serves too, is there)
         polarization=polarization is not None or (stokes_path is not None and kerr_polarization is None), **_kerr_view_facts(kerr_view),
+        kerr_disk_model=kerr_disk_model, kerr_anti_alias=lambda f: kerr_anti_alias is not None or getattr(renderer, "_kerr_anti_alias", None) is not None,
         spin=lambda f: renderer.spin, redshift=lambda f: renderer.redshift, disk_tilt=lambda f: renderer.disk_tilt, anti_alias=lambda f: renderer.anti_alias,
         disk_model=lambda f: "texture" if getattr(renderer, "_dv2", None) is None else "v2",
         supersample=lambda f: renderer.supersample if supersample is None else supersample,
@@ -1085,6 +1116,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         else getattr(renderer, "supersample_threshold", None)))
     # the features are refused in this order (rules.py has what each refuses); the Kerr map's own factor first, then motion blur from
     # the Kerr map, so that each refusal names it
+    kerr_disk_model = _checked_kerr_disk_model(kerr_disk_model, f)      # ahead of the rest, so that each refusal names --spin_disk_model
     check_spin_map_supersample(spin_map_supersample, spin_map=spin_map, spin_polarization=f["kerr_polarization"], spin_shutter_map=spin_shutter_map)
     rules.refuse_on("spin_shutter_map", f, "video")
     kerr_view, kerr_plan = checked("kerr_view", kerr_view, f, "video"), None
@@ -1209,6 +1241,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         renderer.set_kerr_anti_alias(True, kerr_anti_alias)
     elif getattr(renderer, "_kerr_anti_alias", None) is not None:
         rules.refuse("kerr_anti_alias", facts)
+    # the Kerr march's Disk V2 source (kerr_disk_model): set for the video's marched frames, still or orbiting, and stays set on return
+    use_kerr_analytic_disk(renderer, kerr_disk_model)
     total_t0 = time.time()
     rendered = 0
     # the reference saves through a 2-thread PIL pool (render.py:4412-4413); here the frame is quantised

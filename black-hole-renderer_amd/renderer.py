@@ -167,6 +167,7 @@ class HipRenderer:
         # redshift="exact": the disk's g-factor of the Kerr metric instead of the reference's model (set_redshift)
         self._spin, self._force_kerr = 0.0, False
         self._redshift, self._redshift_forced = "model", False
+        self._kerr_dv2 = None              # "v2" / "v2_volume" while the Kerr march shades a Disk V2 source (use_kerr_disk_v2)
         self._kerr_anti_alias = None       # the LOD strength while the Kerr march carries ray differentials (set_kerr_anti_alias)
         if spin != 0.0 or redshift != "model":
             try:
@@ -433,6 +434,42 @@ class HipRenderer:
             _lib.check(lib.bhr_set_disk_volume_options(self._ctx, absorption, grazing_gain, substeps))
         _lib.check(lib.bhr_set_disk_source(self._ctx, 2 if volume else 1, C.byref(cp), m_sh, m_hs, t_peak))
         self._dv2 = (cp, m_sh, m_hs, t_peak)
+
+    def use_kerr_disk_v2(self, params=None, structure_params=None, seed: int = 42, volume: bool = False,
+                         absorption: float = 4.0, grazing_gain: float = 1.0, substeps: int = 2) -> None:
+        """use_disk_v2 for a spinning hole: the Kerr march shades the Disk V2 model instead of the texture for the frames
+        rendered from now on (include/bhr_disk_v2.h: bhr_set_kerr_disk_source states the model).  ``volume=False``: the
+        mid-plane fields at every crossing of the plane z = 0, with the model or the exact redshift; ``volume=True``: the
+        finite-thickness emission-absorption integral along every ray (the model redshift only).  It is the Kerr march's own
+        setting (use_disk_v2 is the Schwarzschild marches' and stays refused with a spin): AssertionError without a spin or the
+        forced Kerr march.  While it is set, Kerr ray map builds, the Kerr camera, the Kerr anti-aliasing and a set_spin that
+        switches the Kerr march off are refused.  ``params=None``: back to the texture."""
+        from . import disk_v2 as dv
+        lib = self._lib
+        lib.bhr_set_disk_volume_options.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int32]
+        lib.bhr_set_disk_volume_options.restype = C.c_int32
+        if params is None:
+            _lib.check(lib.bhr_set_kerr_disk_source(self._ctx, 0, None, 0.0, 0.0, 0.0))
+            self._kerr_dv2 = None
+            return
+        cp, m_sh, m_hs, t_peak = dv.reference_norms(params, structure_params, seed, ctx=self._ctx)
+        if volume:
+            _lib.check(lib.bhr_set_disk_volume_options(self._ctx, absorption, grazing_gain, substeps))
+        _lib.check(lib.bhr_set_kerr_disk_source(self._ctx, 2 if volume else 1, C.byref(cp), m_sh, m_hs, t_peak))
+        self._kerr_dv2 = "v2_volume" if volume else "v2"
+
+    @property
+    def kerr_disk_model(self) -> str:
+        """The Kerr march's disk source: "texture", "v2" or "v2_volume" (use_kerr_disk_v2)."""
+        return self._kerr_dv2 or "texture"
+
+    def kerr_disk_resources(self, volume: bool = False, supersampled: bool = False, redshift: str = "model") -> dict:
+        """Registers per lane, LDS and scratch bytes of the Kerr march kernel over a Disk V2 source (bhr_kerr_disk_resources)."""
+        from . import kerr
+        out = (C.c_int32 * 3)()
+        mode = _lib.REDSHIFT_EXACT if kerr.check_redshift(redshift) == "exact" else _lib.REDSHIFT_MODEL
+        _lib.check(self._lib.bhr_kerr_disk_resources(2 if volume else 1, mode, 1 if supersampled else 0, out))
+        return dict(vgprs=int(out[0]), lds_bytes=int(out[1]), scratch_bytes=int(out[2]))
 
     # ------------------------------------------------------------------ rendering
     def camera_uniforms(self, cam_pos, fov: float, frame: int = 0, t_offset: Optional[float] = None) -> _lib.Camera:

@@ -25,7 +25,7 @@ FACTS = dict(
     # which features are on
     observer=False, projection=False, light_delay=False, stars=False, polarization=False, kerr_polarization=False, spin_observer=False,
     spin_projection=False, kerr_stars=False, passes=False, ray_map=False, orbit_map=False, shutter_map=False, spin_map=False, spin_shutter_map=False,
-    kerr_anti_alias=False,
+    kerr_anti_alias=False, kerr_disk_model="texture",
     # the paths whose suffix is a row, and what a feature's own validation reads beside its value
     passes_path=None, kerr_passes_path=None, stokes_path=None, ticks_path=None, projection_fov=None,
     # the output side: the HDR stream of a video, the bits per sample
@@ -109,6 +109,8 @@ CONDITIONS = {
     "spin_projection": lambda f: f["spin_projection"],
     "kerr_stars": lambda f: f["kerr_stars"],
     "kerr_passes": lambda f: f["kerr_passes_path"] is not None,
+    "kerr_anti_alias": lambda f: f["kerr_anti_alias"],
+    "kerr_volume_exact": lambda f: f["kerr_disk_model"] == "v2_volume" and f["redshift"] == "exact",
     "sky_texture": lambda f: f["skybox_path"] is not None,
     "fov_given": lambda f: f["fov_given"],
     "video_ticks": lambda f: f["video"] and f["ticks_path"] is not None,
@@ -421,6 +423,25 @@ FEATURES = {
              "spin_projection": "{who} does not combine with --spin_projection: the differential seeds are the pinhole camera's",
              "gpus_or_world": "{who} does not combine with --gpus other than 1 or several ranks: row-block tiles and frame-sharded ranks march Schwarzschild rays"},
         rows="no_spin spin_map spin_shutter_map kerr_polarization kerr_stars kerr_passes spin_observer spin_projection gpus_or_world"),
+    # the Kerr march's own Disk V2 sources (--spin_disk_model v2 | v2_volume; HipRenderer.use_kerr_disk_v2): marched frames of the pinhole
+    # camera at rest, on one GPU, stills and videos -- the same words on both surfaces, each naming both flags
+    "kerr_disk_model": dict(
+        on=lambda f: f["kerr_disk_model"] != "texture",
+        words=dict(who="--spin_disk_model", texture="shades the disk texture"),
+        say={"no_spin": "{who} needs --spin or --redshift exact: it is the Disk V2 source of the Kerr march; a hole that does not spin takes --disk_model",
+             "disk_model": "{who} does not combine with --disk_model other than texture: that is the Schwarzschild march's source, which a spin refuses",
+             "spin_map": "{who} does not combine with --spin_map: a frame from the Kerr ray map {texture}",
+             "spin_shutter_map": "{who} does not combine with --spin_shutter_map: a frame from the Kerr ray map {texture}",
+             "kerr_polarization": "{who} does not combine with --spin_polarization: a frame from the Kerr ray map {texture}",
+             "kerr_stars": "{who} does not combine with --spin_stars: a frame from the Kerr ray map {texture}",
+             "kerr_passes": "{who} does not combine with --spin_passes: a frame from the Kerr ray map {texture}",
+             "spin_observer": "{who} does not combine with --spin_observer: the Kerr camera's march {texture}",
+             "spin_projection": "{who} does not combine with --spin_projection: the Kerr camera's march {texture}",
+             "kerr_anti_alias": "{who} does not combine with --spin_anti_alias: the analytic source has no mip chain",
+             "gpus_or_world": "{who} does not combine with --gpus other than 1 or several ranks: row-block tiles and frame-sharded ranks march Schwarzschild rays",
+             "kerr_volume_exact": "{who} v2_volume does not combine with --redshift exact: gas off the equatorial plane has no four-velocity in this model (v2 takes it)"},
+        rows="no_spin disk_model spin_map spin_shutter_map kerr_polarization kerr_stars kerr_passes spin_observer spin_projection kerr_anti_alias gpus_or_world "
+             "kerr_volume_exact"),
     # a still image tiled in row blocks over several GPUs (render_image)
     "tiles": dict(on=lambda f: f["gpus"] > 1, rows=dict(api="grade supersample_set", cli=""),
                   say={"grade": "a grade renders on one GPU: row-block tiles store their rows from inside the V pass",

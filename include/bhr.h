@@ -631,7 +631,9 @@ BHR_API int32_t bhr_kerr_resources(int32_t supersampled, int32_t out[3]);
  * and the crossings do not change, two kernels of the Kerr object of their own shade the disk.
  * EXACT needs the Kerr march: BHR_ERR_INVALID naming the combination without a spin or force_kerr (bhr_set_spin), for an
  * unknown mode, and from a bhr_set_spin that would switch the Kerr march off while EXACT is set.  A context that never calls
- * this launches what it always launched.  Ordered behind the frames in flight. */
+ * this launches what it always launched.  Ordered behind the frames in flight.  EXACT is also refused (BHR_ERR_INVALID) while the
+ * Kerr march's disk source is the Disk V2 volume (bhr_disk_v2.h: bhr_set_kerr_disk_source), whose gas off the plane has no
+ * four-velocity in this model; the Disk V2 surface takes both modes. */
 #define BHR_REDSHIFT_MODEL 0
 #define BHR_REDSHIFT_EXACT 1
 BHR_API int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode);
@@ -654,7 +656,8 @@ BHR_API int32_t bhr_kerr_redshift_resources(int32_t mode, int32_t supersampled, 
  * BHR_ERR_STATE without the Kerr march (bhr_set_spin); BHR_ERR_INVALID for a negative or non-finite strength.  While the switch
  * is on, BHR_ERR_INVALID naming the combination from bhr_kerr_raymap_build (a record has no differential words),
  * bhr_render_kerr_view (the seeds would need the aberration's Jacobian) and from a bhr_set_spin that would switch the Kerr
- * march off. */
+ * march off; and from this call while a Kerr Disk V2 source is set (bhr_disk_v2.h: bhr_set_kerr_disk_source -- the analytic
+ * source has no mip chain). */
 BHR_API int32_t bhr_set_kerr_anti_alias(bhr_ctx *ctx, int32_t on, float strength);
 /* bhr_kerr_resources for the anti-aliased kernel of a redshift mode. */
 BHR_API int32_t bhr_kerr_anti_alias_resources(int32_t redshift, int32_t supersampled, int32_t out[3]);

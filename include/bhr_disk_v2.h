@@ -76,6 +76,26 @@ BHR_API int32_t bhr_set_disk_source(bhr_ctx *ctx, int32_t source, const bhr_disk
 /* Defaults: absorption 4.0 per unit length at rho = 1, grazing_gain 1.0, substeps 2 (1..16). */
 BHR_API int32_t bhr_set_disk_volume_options(bhr_ctx *ctx, double absorption, double grazing_gain, int32_t substeps);
 
+/* The disk source of the Kerr march (bhr_set_spin): a setting of its own beside bhr_set_disk_source, which keeps refusing a spin.
+ * BHR_DISK_TEXTURE (default) is the Kerr march as it was; BHR_DISK_V2 shades every crossing of the plane z = 0 with the Disk V2
+ * model, BHR_DISK_V2_VOLUME integrates the finite-thickness volume around it (csrc/ray_kerr_dv2.h; DESIGN.md "Kerr Disk V2";
+ * tests/kerr_dv2_ref.py is the CPU reference).  Units r_s = 1, Kerr-Schild Cartesian positions, the disk normal is the spin axis.
+ * The model's cylinder coordinates of a point x with Kerr-Schild radius r are varpi = sqrt(max(r^2 - z^2, 0)) -- the
+ * Boyer-Lindquist r sin(theta), on the plane the hit radius sqrt(x^2 + y^2 - a^2) -- zeta = z and phi = atan2(y, x); the pattern
+ * turns with the model's own omega_scale; the orbital frequency of Kerr enters through the redshift alone.  Parameters, norms and
+ * the colour mapping are bhr_set_disk_source's; the context keeps them in a second block of the Kerr march's own.  Absorption,
+ * grazing gain and substeps are bhr_set_disk_volume_options'.  Behind the frames in flight.
+ *   BHR_ERR_INVALID: what bhr_set_disk_source refuses of its arguments; the volume while the exact redshift is set (and
+ *     bhr_set_redshift(BHR_REDSHIFT_EXACT) while the volume is); a source while the Kerr anti-aliasing is on or a Kerr ray map is built.
+ *   BHR_ERR_STATE: a Disk V2 source without the Kerr march (no spin and no force_kerr).
+ * While a Disk V2 source is set, bhr_set_spin(0) without force_kerr, bhr_set_kerr_anti_alias(on), bhr_render_kerr_view,
+ * bhr_kerr_raymap_build and bhr_kerr_raymap_render_shutter are refused (BHR_ERR_INVALID), each naming the combination. */
+BHR_API int32_t bhr_set_kerr_disk_source(bhr_ctx *ctx, int32_t source, const bhr_disk_v2_params *params, double norm_shear,
+                                         double norm_hotspot, double t_peak);
+/* {VGPRs, LDS bytes, scratch bytes per lane} of the kernel that marches a Kerr frame over `source` (BHR_DISK_V2 or
+ * BHR_DISK_V2_VOLUME) under `redshift` (BHR_REDSHIFT_MODEL / _EXACT; the volume has the model only); supersampled: its twin. */
+BHR_API int32_t bhr_kerr_disk_resources(int32_t source, int32_t redshift, int32_t supersampled, int32_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif
