@@ -26,6 +26,10 @@ REDSHIFT_MODEL, REDSHIFT_EXACT = 0, 1
 RAYMAP_STEPS, RAYMAP_STATUS, RAYMAP_ESCAPE_DIR, RAYMAP_CROSSINGS, RAYMAP_HITS = 0, 1, 2, 3, 4
 RAYMAP_STARS = 5
 RAYMAP_MOMENTUM = 6   # bhr_kerr_raymap_read alone: a Kerr map built under a Kerr polarisation
+RAYMAP_LINE_G, RAYMAP_LINE_W = 7, 8   # bhr_kerr_raymap_read alone: the per-record planes of a Kerr line pass that kept them
+LINE_POWERLAW, LINE_TEXTURE = 0, 1
+LINE_FIRST, LINE_ALL = 0, 1
+LINE_MAX_BINS = 4096
 
 # every symbol include/bhr.h declares (tests check the .so exports exactly these)
 SYMBOLS = (
@@ -44,6 +48,7 @@ SYMBOLS = (
     "bhr_set_kerr_stars", "bhr_get_kerr_stars_info", "bhr_kerr_stars_resources",
     "bhr_set_polarization", "bhr_read_stokes", "bhr_read_stokes_cells", "bhr_stokes_resources",
     "bhr_set_kerr_polarization", "bhr_kerr_stokes_resources",
+    "bhr_set_kerr_line", "bhr_kerr_line_reserve", "bhr_kerr_line_read", "bhr_kerr_line_info", "bhr_kerr_line_resources",
     "bhr_read_layer", "bhr_write_layer", "bhr_bloom", "bhr_set_outputs", "bhr_set_supersample", "bhr_set_adaptive_supersample", "bhr_adaptive_info", "bhr_set_option", "bhr_debug_read", "bhr_lens_flare", "bhr_lens_flare_sums", "bhr_read_final_u8", "bhr_read_final_u16", "bhr_set_dither", "bhr_dither_matrix", "bhr_set_grade", "bhr_grade_frame", "bhr_get_counters", "bhr_get_row_costs_split", "bhr_mip_lds_level", "bhr_hybrid_info", "bhr_hybrid_repairs", "bhr_timing_reset", "bhr_timing_dump", "bhr_get_row_costs", "bhr_selftest", "bhr_group_render", "bhr_group_render_subset", "bhr_group_sync", "bhr_read_gathered", "bhr_read_gathered_u8", "bhr_tile_export", "bhr_tile_connect", "bhr_tile_render", "bhr_disk_v2_eval", "bhr_set_disk_source", "bhr_set_disk_volume_options", "bhr_entity_profile_upload", "bhr_entity_profile_reset", "bhr_accumulate_entities", "bhr_accumulate_population",
     "bhr_stats_prepare", "bhr_stats_select", "bhr_stats_row_statistics",
     "bhr_png_bound16", "bhr_png_encode16", "bhr_png_write16", "bhr_png16_device_bound", "bhr_png16_device_max_width", "bhr_png16_encode_device", "bhr_sink_create_png16",
@@ -138,6 +143,14 @@ class Polarization(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class KerrLine(C.Structure):
+    """bhr_kerr_line: the histogram, the weight's exponents, the emissivity, the orders and the annulus of a Kerr line profile;
+    reserved is 0."""
+    _fields_ = [("n_bins", C.c_int32), ("g_min", C.c_float), ("g_max", C.c_float), ("power", C.c_float), ("index", C.c_float),
+                ("emissivity", C.c_int32), ("orders", C.c_int32), ("r_inner", C.c_float), ("r_outer", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
 TILE_SHM_WORDS = 8
 
 
@@ -220,6 +233,11 @@ def load() -> C.CDLL:
     lib.bhr_stokes_resources.argtypes = [I32, C.POINTER(C.c_int32)]
     lib.bhr_set_kerr_polarization.argtypes = [P, C.POINTER(Polarization)]
     lib.bhr_kerr_stokes_resources.argtypes = [I32, C.POINTER(C.c_int32)]
+    lib.bhr_set_kerr_line.argtypes = [P, C.POINTER(KerrLine)]
+    lib.bhr_kerr_line_reserve.argtypes = [P, I32]
+    lib.bhr_kerr_line_read.argtypes = [P, I32, I32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.bhr_kerr_line_info.argtypes = [P, I32, C.POINTER(C.c_int64)]
+    lib.bhr_kerr_line_resources.argtypes = [I32, I32, C.POINTER(C.c_int32)]
     lib.bhr_read_layer.argtypes = [P, I32, F]
     lib.bhr_read_gathered.argtypes = [P, F]
     PI32 = C.POINTER(C.c_int32)

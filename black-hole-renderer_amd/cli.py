@@ -92,6 +92,30 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "with --supersample, --lens_flare and a grade.  Not with --disk_model v2 / v2_volume, --spin_map, "
                         "--spin_shutter_map, --spin_polarization, --spin_stars, --spin_passes, --spin_observer, --spin_projection, "
                         "--spin_anti_alias or --gpus > 1")
+    p.add_argument("--spin_line", type=str, default=argparse.SUPPRESS, metavar="PATH.npz",
+                   help="--spin / --redshift exact: the disk's relativistically broadened emission line (the Fe K alpha profile) -- the flux "
+                        "g^4 x emissivity x solid angle of every disk crossing, binned in g = E_obs / E_em, from a Kerr ray map of the view; "
+                        "written as a .npz (edges, flux, counts, g_mean, g_red, g_blue, energy).  A still builds the map and renders the "
+                        "frame from it; with --video --spin_map the file holds one spectrum per frame.  May stand beside "
+                        "--spin_polarization, --spin_stars and --spin_passes.  Not with --orbit, --shutter, --supersample, "
+                        "--spin_map_supersample, --spin_shutter_map, --spin_observer / --spin_projection, --spin_anti_alias, "
+                        "--spin_disk_model or --gpus > 1")
+    p.add_argument("--spin_line_bins", type=int, default=argparse.SUPPRESS, metavar="N", help="--spin_line: bins of the histogram, 1 .. 4096 (default: 256)")
+    p.add_argument("--spin_line_range", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("GMIN", "GMAX"),
+                   help="--spin_line: the histogram's range [GMIN, GMAX) of g (default: 0 2); what falls outside is counted in under / over")
+    p.add_argument("--spin_line_index", type=float, default=argparse.SUPPRESS, metavar="Q",
+                   help="--spin_line: the emissivity's power law (r / r_inner)^-Q, 0 .. 16 (default: 3)")
+    p.add_argument("--spin_line_emissivity", type=str, default=argparse.SUPPRESS, choices=["powerlaw", "texture"],
+                   help="--spin_line: powerlaw (default) is the power law alone; texture multiplies it by the disk texture's opacity under the "
+                        "frame's roll, which makes a video's spectrum move")
+    p.add_argument("--spin_line_orders", type=str, default=argparse.SUPPRESS, choices=["first", "all"],
+                   help="--spin_line: first (default) counts a pixel's first disk crossing, an opaque disk; all counts every crossing (under "
+                        "texture weighted by the transmittance in front of it)")
+    p.add_argument("--spin_line_energy", type=float, default=argparse.SUPPRESS, metavar="KEV",
+                   help="--spin_line: the line's rest energy in keV (default: 6.4); it only labels energy = g x E0 in the file")
+    p.add_argument("--spin_g_map", type=str, default=argparse.SUPPRESS, metavar="PATH.png",
+                   help="--spin / --redshift exact, still images: the redshift map -- the g of each pixel's first disk crossing in false colour, "
+                        "diverging about g = 1 (blue above, red below, black where no disk is hit); takes --spin_line's companions")
     p.add_argument("--spin_aa_strength", type=float, default=argparse.SUPPRESS, metavar="S",
                    help="--spin_anti_alias lod_radius: LOD multiplier, finite and not negative (default: 1.0)")
     p.add_argument("--redshift", type=str, default="model", choices=["model", "exact"],
@@ -428,6 +452,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     except ValueError as e:
         p.error(str(e))
     refuse("kerr_passes", "api")
+    # the Kerr line profile and the redshift map (the drivers' words), likewise
+    for flag in ("spin_line_bins", "spin_line_range", "spin_line_index", "spin_line_emissivity", "spin_line_orders", "spin_line_energy"):
+        if hasattr(args, flag) and not f["kerr_line"]:
+            p.error(f"--{flag} needs --spin_line or --spin_g_map: it belongs to the line profile")
+    try:
+        drivers._checked_kerr_line(kerr_line_from_args(args).get("kerr_line"), f)
+    except ValueError as e:
+        p.error(str(e))
     # --exposure, --white, --transfer and --hdr_output without --tonemap mean --tonemap clip
     if args.tonemap is None and any(v is not None for v in (args.exposure, args.white, args.transfer, args.hdr_output)):
         args.tonemap = "clip"
@@ -462,7 +494,21 @@ def facts_from_args(args, fov_given: bool):
         passes=args.passes is not None, passes_path=args.passes, kerr_passes_path=getattr(args, "spin_passes", None), ray_map=args.ray_map,
         orbit_map=args.orbit_map, shutter_map=args.shutter_map, spin_map=hasattr(args, "spin_map"), spin_shutter_map=hasattr(args, "spin_shutter_map"),
         video_hdr=args.video_hdr, hdr_white_given=args.hdr_white is not None, hdr_exposure_given=args.hdr_exposure is not None, video_codec=args.video_codec,
-        video_stream=args.video_stream, kerr_anti_alias=hasattr(args, "spin_anti_alias"), kerr_disk_model=getattr(args, "spin_disk_model", "texture")))
+        video_stream=args.video_stream, kerr_anti_alias=hasattr(args, "spin_anti_alias"), kerr_disk_model=getattr(args, "spin_disk_model", "texture"),
+        kerr_line=hasattr(args, "spin_line") or hasattr(args, "spin_g_map"), kerr_line_path=getattr(args, "spin_line", None),
+        g_map_path=getattr(args, "spin_g_map", None)))
+
+
+def kerr_line_from_args(args) -> dict:
+    """The Kerr line profile of a command line as drivers.render_image / render_video take it: {} without --spin_line and --spin_g_map."""
+    if not (hasattr(args, "spin_line") or hasattr(args, "spin_g_map")):
+        return {}
+    line = dict(path=getattr(args, "spin_line", None), g_map_path=getattr(args, "spin_g_map", None))
+    for flag, key in (("spin_line_bins", "n_bins"), ("spin_line_range", "g_range"), ("spin_line_index", "index"), ("spin_line_emissivity", "emissivity"),
+                      ("spin_line_orders", "orders"), ("spin_line_energy", "energy_kev")):
+        if hasattr(args, flag):
+            line[key] = tuple(getattr(args, flag)) if key == "g_range" else getattr(args, flag)
+    return dict(kerr_line=line)
 
 
 def kerr_anti_alias_from_args(args) -> dict:
@@ -675,6 +721,8 @@ def main(argv=None) -> int:
     aa_kw = kerr_anti_alias_from_args(args)
     # ... and the Kerr march's Disk V2 source
     dv2_kw = {"kerr_disk_model": args.spin_disk_model} if hasattr(args, "spin_disk_model") else {}
+    # ... and the Kerr line profile
+    line_kw = kerr_line_from_args(args)
 
     if args.video:
         rank = int(os.environ.get("RANK", "0"))
@@ -700,6 +748,9 @@ def main(argv=None) -> int:
         if dv2_kw:
             from . import rules
             rules.refuse("kerr_disk_model", dict(spin=args.spin, redshift=args.redshift, world=world, **dv2_kw))
+        if line_kw:
+            from . import rules
+            rules.refuse("kerr_line", dict(spin=args.spin, redshift=args.redshift, world=world, video=True, spin_map=hasattr(args, "spin_map")))
         if "BHR_FORCE_DEVICE" in os.environ:        # rehearsal: several ranks sharing one card
             local_rank = int(os.environ["BHR_FORCE_DEVICE"])
         elif world > 1:                             # a launcher that shows every rank only its own GPU: ordinal 0
@@ -728,7 +779,7 @@ def main(argv=None) -> int:
                              **({"spin_map": True} if hasattr(args, "spin_map") else {}),
                              **({"spin_shutter_map": True} if hasattr(args, "spin_shutter_map") else {}),
                              **({"spin_map_supersample": args.spin_map_supersample} if hasattr(args, "spin_map_supersample") else {}),
-                             **kerr_stars_kw, **aa_kw, **dv2_kw)
+                             **kerr_stars_kw, **aa_kw, **dv2_kw, **line_kw)
         if world > 1:
             from . import distributed as D
             dist = D.init("gloo")          # a barrier is all the ranks exchange: frames are independent
@@ -754,6 +805,6 @@ def main(argv=None) -> int:
         supersample_threshold=args.supersample_threshold, bit_depth=args.bit_depth, dither=args.dither,
         grade=grade_from_args(args), hdr_path=args.hdr_output, passes_path=args.passes, **spin_kw, **stars_kw,
         **(dict(observer=observer_beta(args), observer_sky=sky) if moving else {}), **proj_kw, **delay_kw, **pol_kw, **view_kw,
-        **kerr_stars_kw, **({"kerr_passes_path": args.spin_passes} if hasattr(args, "spin_passes") else {}), **aa_kw, **dv2_kw)
+        **kerr_stars_kw, **({"kerr_passes_path": args.spin_passes} if hasattr(args, "spin_passes") else {}), **aa_kw, **dv2_kw, **line_kw)
     drivers.save_image(img, args.output, bit_depth=args.bit_depth, dither=args.dither)
     return 0

@@ -54,6 +54,8 @@ int32_t bhr_kerr_raymap_check_render(bhr_ctx *ctx, const char *who, const bhr_ca
         if (!rm->has_mom)
             return bhr_fail(BHR_ERR_STATE, "%s: a Kerr polarisation is set (bhr_set_kerr_polarization) and the map was built without the photon momenta it needs; build it again (bhr_kerr_raymap_build)", who);
     }
+    // a Kerr line (bhr_set_kerr_line): the line pass walks the build view's records of a k = 1 map into a reserved row
+    BHR_TRY(bhr_kerr_line_check_render(ctx, rm, who, cam && !(*rot_c == 1.0f && *rot_s == 0.0f), false));
     // Kerr point stars (bhr_set_kerr_stars): a supersampled Kerr map's shade kernels have no STARS variant
     return bhr_stars_check_map(ctx, BHR_RAYMAP_KERR, who);
 }
@@ -74,6 +76,8 @@ int32_t bhr_kerr_raymap_check_render_shutter(bhr_ctx *ctx, const bhr_camera *cam
     // the Kerr Stokes kernel walks one frame's records: a mean of frames has no Stokes planes (bhr_raymap_render_shutter likewise)
     if (bhr_have_kerr_polar(ctx))
         return bhr_fail(BHR_ERR_STATE, "%s: a Kerr polarisation is set (bhr_set_kerr_polarization) and shutter frames from the map have no Stokes planes -- switch it off (NULL) first", who);
+    // ... and no line profile (bhr_set_kerr_line)
+    if (ctx->kerr_raymap) BHR_TRY(bhr_kerr_line_check_render(ctx, ctx->kerr_raymap, who, false, true));
     float c1 = 1.0f, s0 = 0.0f;
     BHR_TRY(bhr_kerr_raymap_check_render(ctx, who, nullptr, 0.0f, flags, &c1, &s0));
     const bhr_camera &b = ctx->kerr_raymap->cam;
@@ -127,6 +131,9 @@ int32_t bhr_kerr_raymap_build(bhr_ctx *ctx, const bhr_camera *cam, uint32_t flag
     // the momentum build and the Kerr Stokes kernel have no supersampled twin
     if (ss > 1 && bhr_have_kerr_polar(ctx))
         return bhr_fail(BHR_ERR_INVALID, "%s: kerr_raymap_supersample %d while a Kerr polarisation is set (bhr_set_kerr_polarization); the Stokes planes need a map with one ray per pixel -- set the factor to 1 or switch the polarisation off (NULL) first", who, ss);
+    // ... and the Kerr line pass none either
+    if (ss > 1 && bhr_have_kerr_line(ctx))
+        return bhr_fail(BHR_ERR_INVALID, "%s: kerr_raymap_supersample %d while a Kerr line is set (bhr_set_kerr_line); the line pass needs a map with one ray per pixel -- set the factor to 1 or switch the line off (NULL) first", who, ss);
     BHR_TRY(bhr_kerr_camera_check(ctx, cam, who));
     // k x k Kerr rays per pixel, no differentials; the context's variant (BHR_MV_KERR or BHR_MV_KERR_EXACT) marches them
     return bhr_raymap_build_into(ctx, &ctx->kerr_raymap, who, cam, BHR_SKIP_DIFFERENTIALS, bhr_variant_of(ctx), K, ss);
@@ -138,6 +145,8 @@ int32_t bhr_kerr_raymap_read(bhr_ctx *ctx, int32_t which, void *out, int64_t byt
     if (!ctx->kerr_raymap || !ctx->kerr_raymap->built) return bhr_fail(BHR_ERR_STATE, "%s: no Kerr ray map has been built (bhr_kerr_raymap_build)", who);
     // the build view's star plane under the Kerr catalogue, gathered now if the map or the catalogue changed since
     if (which == BHR_RAYMAP_STARS) return bhr_stars_read_plane(ctx, BHR_RAYMAP_KERR, who, out, bytes);
+    // the per-record g and w planes of the last frame whose Kerr line pass kept them (option "kerr_line_samples")
+    if (which == BHR_RAYMAP_LINE_G || which == BHR_RAYMAP_LINE_W) return bhr_kerr_line_read_samples(ctx, who, which, out, bytes);
     if (which == BHR_RAYMAP_MOMENTUM) {
         // the momentum planes of a build under a Kerr polarisation: [slot][component][pixel] on the device, [slot][pixel][component] out
         const bhr_raymap *rm = ctx->kerr_raymap;

@@ -283,6 +283,19 @@ struct BhrStokesArgs {
     int32_t width, rows;
 };
 
+// Third argument of kerr_line_kernel (march_kerr_line.hip), behind the Kerr block of the map's view and the map: the line of the
+// frame (bhr_set_kerr_line; include/bhr.h states the model) -- wave-uniform, so scalars -- the device row the histogram goes into
+// and, where the frame keeps them, the sample planes.
+struct BhrKerrLineArgs {
+    unsigned long long *row;     // n_bins sums of Q, then under, over (sums of Q), samples, overflow pixels skipped
+    float *g_out, *w_out;        // null, or (slots, rows, W) each: g and w per record, 0 where a record does not count
+    float g_min, scale, unit;    // t = (g - g_min) * scale; Q = llrintf(w * unit): both factors rounded once on the host
+    float power, index;          // p of g^p, q of (r / r_in)^-q
+    float r_in, r_out;           // the line's annulus
+    int32_t n_bins;
+    int32_t all;                 // BHR_LINE_ALL: every counted record contributes; else the first one of the pixel
+};
+
 // Second argument of stars_gather_kernel (stars.hip), behind the march's block of the view (its camera fields and frame shape):
 // the map's two planes it reads, the turn of the view, the binned catalogue and the plane it fills.
 struct BhrStarsArgs {
@@ -359,6 +372,8 @@ struct bhr_options {
     int32_t shutter_timing;     // BHR_SHUTTER_TIMING: 1 a shutter frame brackets each accumulation launch with HIP events (bhr_debug_read, which = 5); default 0
     int32_t raymap_slots;       // BHR_RAYMAP_SLOTS / option "raymap_slots": crossings a map keeps per pixel (1..8, default 4), read by bhr_raymap_build, which refuses anything else
     int32_t raymap_ss;          // BHR_RAYMAP_SUPERSAMPLE / option "raymap_supersample": the next map's own factor (1, 2, 4, 8; default 1), read by bhr_raymap_build likewise
+    int32_t kerr_line_row;      // option "kerr_line_row": the device row the Kerr line pass of the next frame from the Kerr map fills (api_kerr_line.hip); default 0
+    int32_t kerr_line_samples;  // option "kerr_line_samples": 1 that pass also stores the per-record g and w planes; default 0
     int32_t kerr_raymap_ss;     // BHR_KERR_RAYMAP_SUPERSAMPLE / option "kerr_raymap_supersample": the next Kerr map's own factor (1, 2, 4, 8; default 1), read by bhr_kerr_raymap_build
 };
 
@@ -463,6 +478,12 @@ struct bhr_frame_slot {
     // the last reader of the scene in the slot's last frame (bhr_enter_scene_write): the end of its last march, borrowed from the
     // timing ring -- or, for a map frame with a polarisation set, stokes_done: its Stokes pass samples the disk texture behind the march
     hipEvent_t march_done;
+    // the Kerr line pass of the slot's last map frame (api_kerr_line.hip): its sample planes g | w, (slots, rows, W) each, on first
+    // use; line_keep: the slots of the frame that filled them (0: the slot has none); line_row: the device row that frame's pass
+    // wrote (-1 after a change of the line); line_done: the slot's own event behind the pass, which reads the scene like the Stokes pass
+    float *d_line_samples;
+    int32_t line_keep, line_alloc, line_row;
+    hipEvent_t line_done;
     hipEvent_t stokes_done; // the slot's own, on first use (api_polar.hip): behind the Stokes pass of its last map frame
     int32_t allocated;
     int32_t in_flight;      // rendered since the last join
@@ -616,6 +637,15 @@ struct bhr_ctx {
     // the Kerr ray map, into the same slot planes
     int32_t kerr_polar_on;
     bhr_polarization kerr_polar;
+
+    // the Kerr line profile (api_kerr_line.hip): kerr_line_on = a line is set (bhr_set_kerr_line), kerr_line = it with the annulus
+    // resolved; d_line_rows = line_rows_n device rows of kerr_line.n_bins + 4 cells; line_slot = the frame slot that holds the
+    // sample planes of the last frame that kept them (-1: none)
+    int32_t kerr_line_on;
+    bhr_kerr_line kerr_line;
+    unsigned long long *d_line_rows;
+    int32_t line_rows_n;
+    int32_t line_slot;
 
     // the Kerr march's own disk source (bhr_set_kerr_disk_source; api_disk_v2.hip): BHR_DISK_TEXTURE, or a Disk V2 source with a
     // parameter block, norms and bounding slab of its own beside disk_source's above (which stays refused with a spin); absorption,
@@ -961,6 +991,20 @@ const void *bhr_stokes_cells_kernel(void);
 inline bool bhr_have_kerr_polar(const bhr_ctx *ctx) { return ctx->kerr_polar_on != 0; }
 int32_t bhr_kerr_polar_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm);
 const void *bhr_kerr_stokes_kernel(int32_t exact);                         // march_kerr_polar.hip -> march_kerr_polar.o
+// the Kerr line profile (bhr_set_kerr_line; api_kerr_line.hip): the pass of a frame from the k = 1 Kerr map `rm` on frame slot k
+// into the row of option "kerr_line_row", behind the frame's shade and Stokes pass; what a render and a build are refused for
+// while a line is set; the sample planes of the last frame that kept them; the state's release
+inline bool bhr_have_kerr_line(const bhr_ctx *ctx) { return ctx->kerr_line_on != 0; }
+inline int32_t bhr_kerr_line_cells(const bhr_ctx *ctx) { return ctx->kerr_line.n_bins + 4; }
+int32_t bhr_kerr_line_frame(bhr_ctx *ctx, const bhr_march_call &call, const bhr_raymap &rm, int k);
+int32_t bhr_kerr_line_check_render(const bhr_ctx *ctx, const bhr_raymap *rm, const char *who, bool turned, bool shutter);
+int32_t bhr_kerr_line_read_samples(bhr_ctx *ctx, const char *who, int32_t which, void *out, int64_t bytes);
+void bhr_kerr_line_invalidate(bhr_ctx *ctx);
+void bhr_kerr_line_release(bhr_ctx *ctx);
+// its launch (march_launch.hip): the kernel of call's Kerr variant and of the emissivity over the shade kernel's tiles, a
+// capped grid of workgroups that stride over them, (n_bins + 4) cells of dynamic LDS
+int32_t bhr_launch_kerr_line(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, const BhrKerrLineArgs &s, bool texture);
+const void *bhr_kerr_line_kernel(int32_t exact, int32_t texture);           // march_kerr_line.hip -> march_kerr_line.o
 
 // ---- lifecycle.hip, texture.hip, disk_v2.hip ------------------------------------------------------------------------------------------
 void bhr_population_free(bhr_ctx *ctx);

@@ -135,6 +135,7 @@ int32_t bhr_create(const bhr_config *cfg, bhr_ctx **out) {
     ctx->ss = 1;
     ctx->ada_info_slot = -1;
     ctx->stokes_slot = -1;
+    bhr_kerr_line_invalidate(ctx);
 
     auto bail = [&](int32_t rc) { bhr_destroy(ctx); return rc; };
     if (hipSetDevice(cfg->device) != hipSuccess) return bail(bhr_fail(BHR_ERR_HIP, "hipSetDevice(%d) failed", cfg->device));
@@ -192,6 +193,7 @@ void bhr_destroy(bhr_ctx *ctx) {
     bhr_raymap_release(ctx, &ctx->kerr_raymap);
     bhr_stars_release(ctx, BHR_RAYMAP_SCHWARZSCHILD);
     bhr_stars_release(ctx, BHR_RAYMAP_KERR);
+    bhr_kerr_line_release(ctx);
     bhr_population_free(ctx);
     bhr_hybrid_free(ctx);
     bhr_pipe_free(ctx);
@@ -258,6 +260,11 @@ int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value) {
             return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: kerr_raymap_supersample %g (1, 2, 4 or 8)", value);
         o.kerr_raymap_ss = v;
     }
+    else if (n == "kerr_line_row") {   // read by the next bhr_kerr_raymap_render under a Kerr line, which refuses a row that is not reserved
+        if (!(value >= 0.0 && value <= 65535.0)) return bhr_fail(BHR_ERR_INVALID, "bhr_set_option: kerr_line_row %g (0 .. 65535)", value);
+        o.kerr_line_row = v;
+    }
+    else if (n == "kerr_line_samples") o.kerr_line_samples = v != 0;
     else if (n == "png16_menu") {   // the tables are rebuilt at the next encode; no encode may be running on the old ones
         BHR_TRY(bhr_enter(ctx));
         BHR_HIP(hipStreamSynchronize(ctx->scene_stream));

@@ -74,11 +74,12 @@ int32_t bhr_alloc_slot(bhr_ctx *ctx, int k) {
 void bhr_free_slot(bhr_ctx *ctx, int k) {
     bhr_frame_slot &f = ctx->slots[k];
     void *bufs[] = {f.d_bg, f.d_disk, f.d_blur, f.d_final, f.d_final_u8, f.d_final_u16, f.d_hblur_base, f.d_pa, f.d_pb, f.d_sum, f.d_queue,
-                    f.d_glow_hw, f.d_glow_wh, f.d_flare_c0, f.d_flare_c12, f.d_flare_sums, f.d_ada_list, f.d_ada_mask, f.d_ada_counts, f.d_acc_bg, f.d_acc_disk, f.d_hdr, f.d_star_plane, f.d_stokes, f.d_stokes_cells};
+                    f.d_glow_hw, f.d_glow_wh, f.d_flare_c0, f.d_flare_c12, f.d_flare_sums, f.d_ada_list, f.d_ada_mask, f.d_ada_counts, f.d_acc_bg, f.d_acc_disk, f.d_hdr, f.d_star_plane, f.d_stokes, f.d_stokes_cells, f.d_line_samples};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (f.done) (void)hipEventDestroy(f.done);
     if (f.stokes_done) (void)hipEventDestroy(f.stokes_done);
+    if (f.line_done) (void)hipEventDestroy(f.line_done);
     if (f.stream &&f.stream != ctx->scene_stream) (void)hipStreamDestroy(f.stream);
     if (f.aux_stream) (void)hipStreamDestroy(f.aux_stream);      // idle: bhr_destroy has waited for every slot's
     if (f.aux_fork) (void)hipEventDestroy(f.aux_fork);

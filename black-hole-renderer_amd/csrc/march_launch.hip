@@ -710,6 +710,35 @@ int32_t bhr_launch_stokes(bhr_ctx *ctx, const bhr_march_call &call, const BhrRay
     return BHR_OK;
 }
 
+// The Kerr line pass of a frame from the k = 1 Kerr map (march_kerr_line.hip; api_kerr_line.hip owns the rows and the planes): the
+// kernel of call's redshift and of the emissivity under the Kerr block the shade launch of the same frame was given, over the
+// shade kernel's tiles.  The grid is capped at BHR_LINE_MAX_BLOCKS workgroups of four waves, which stride over the tiles: a
+// workgroup clears and flushes its n_bins + 4 LDS cells once, however many tiles it walks.  Stores no layer.
+#define BHR_LINE_MAX_BLOCKS 1024
+int32_t bhr_launch_kerr_line(bhr_ctx *ctx, const bhr_march_call &call, const BhrRayMapArgs &m, const BhrKerrLineArgs &s, bool texture) {
+    const char *who = "Kerr line profile";
+    const bhr_march_variant v = call.req.variant;
+    if (v != BHR_MV_KERR && v != BHR_MV_KERR_EXACT) return bhr_fail(BHR_ERR_STATE, "%s: the frame is not a Kerr variant's", who);
+    if (call.ss != 1) return bhr_fail(BHR_ERR_STATE, "%s: the kernel has no supersampled twin (factor %d)", who, call.ss);
+    if (texture && !ctx->d_mips) return bhr_fail(BHR_ERR_STATE, "%s: no disk texture set (bhr_set_disk_texture)", who);
+    BhrMarchArgs a;
+    march_args(ctx, call, nullptr, 1, false, a);
+    if ((int64_t)a.width * a.rows != m.plane || m.comps != 5 || m.slots < 1 || m.slots > 8) return bhr_fail(BHR_ERR_STATE, "%s: the map does not fit the frame", who);
+    if (s.n_bins < 1 || s.n_bins > BHR_LINE_MAX_BINS || !s.row || (s.g_out == nullptr) != (s.w_out == nullptr))
+        return bhr_fail(BHR_ERR_STATE, "%s: %d bins (1 .. %d), a row and both sample planes or none", who, s.n_bins, BHR_LINE_MAX_BINS);
+    const void *fn = bhr_kerr_line_kernel(v == BHR_MV_KERR_EXACT ? 1 : 0, texture ? 1 : 0);
+    if (!fn) return bhr_fail(BHR_ERR_STATE, "%s: no line kernel in this library", who);
+    VariantArgs va;
+    BhrRayMapArgs mm = m;
+    BhrKerrLineArgs ss = s;
+    void *args[] = {variant_args(ctx, call.req, a, va), &mm, &ss};
+    const int blocks = (a.n_tiles + 3) / 4;
+    const size_t lds = (size_t)(s.n_bins + 4) * sizeof(unsigned long long);
+    (void)hipLaunchKernel(fn, dim3(blocks < BHR_LINE_MAX_BLOCKS ? blocks : BHR_LINE_MAX_BLOCKS), dim3(256), args, lds, call.stream);
+    BHR_HIP(hipGetLastError());
+    return BHR_OK;
+}
+
 // All samples of a shutter frame from the map in one launch (the fused route of bhr_raymap_render_shutter and
 // bhr_kerr_raymap_render_shutter): the shade kernel's grid, the block of call.cam's frame -- the fields of it that a shade kernel
 // reads of a camera, t_offset and the position, are taken from the samples' table inside the kernel instead -- the map, and that

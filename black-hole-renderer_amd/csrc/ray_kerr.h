@@ -370,6 +370,32 @@ template <int RS>
 __device__ __forceinline__ V3 kerr_g_factor(const BhrMarchArgs &a, V3 base_color, float hit_x, float hit_y, float hit_r, V3 to_cam, float obs_d = 1.0f) {
     return kerr_g_factor<RS>(a, a, base_color, hit_x, hit_y, hit_r, to_cam, obs_d);
 }
+// The model's g alone, cap included: kerr_g_factor<0>'s own lines up to its g, for the Kerr line pass (march_kerr_line.hip), which
+// bins g itself.  A function of its own beside it: kerr_g_factor stays the code it is in every object that inlines it.
+__device__ __forceinline__ float kerr_g_model(const BhrMarchArgs &a, const BhrMarchArgs &f, float hit_x, float hit_y, float hit_r, V3 to_cam, float obs_d = 1.0f) {
+    const float rs_f = BHR_RS;
+    V3 cam_pos = ld3(f.cp);
+    asm volatile("" : "+v"(cam_pos.x));          // recomputed per hit, as kerr_g_factor does
+    const float r_obs = sqrtf(dot(cam_pos, cam_pos));
+    const float r_em = hit_r;
+    const float r_safe = fmaxf(r_em, rs_f + 1e-3f);
+    const float omega = kerr_omega(r_safe, kerr(a).kerr_a);
+    const float lorentz = sqrtf(fmaxf(1.0f - rs_f / r_safe, 1e-6f));
+    const float beta = fminf(r_safe * omega / fmaxf(lorentz, 1e-6f), 0.99f);
+    const float gamma = 1.0f / sqrtf(fmaxf(1.0f - beta * beta, 1e-6f));
+    const float inv = 1.0f / sqrtf(hit_x * hit_x + hit_y * hit_y);
+    const float rx = inv * hit_x, ry = inv * hit_y;
+    float vx = ry, vy = -rx;                     // v_hat = r_hat x n, n = (0, 0, 1)
+    const float v_norm = sqrtf(vx * vx + vy * vy);
+    if (v_norm > 1e-6f) { vx = vx / v_norm; vy = vy / v_norm; } else { vx = 0.0f; vy = 1.0f; }
+    const float ti = 1.0f / sqrtf(dot(to_cam, to_cam));
+    const float cos_theta = vx * (ti * to_cam.x) + vy * (ti * to_cam.y);
+    const float denom = fmaxf(1.0f - beta * cos_theta, 1e-3f);
+    const float g_doppler = 1.0f / (gamma * denom);
+    const float grav_num = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_obs, rs_f + 1e-3f), 1e-6f));
+    const float grav_den = sqrtf(fmaxf(1.0f - rs_f / fmaxf(r_em, rs_f + 1e-3f), 1e-6f));
+    return fminf(g_doppler * (grav_num / grav_den) * obs_d, BHR_G_FACTOR_CAP);
+}
 
 // one disk crossing, shaded and composited front to back (render.py:2951-3002 without the mip levels); obs_d: the moving
 // camera's factor of g ahead of its cap in both redshift modes (1: the camera at rest); f: the block the frame's own fields

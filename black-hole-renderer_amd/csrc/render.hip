@@ -158,6 +158,8 @@ int32_t raymap_on_slot(bhr_ctx *ctx, const bhr_raymap &rm, const bhr_camera *cam
         BHR_TRY(bhr_kerr_polar_frame(ctx, call, rm));
         ctx->stokes_slot = k;
     }
+    // ... and under a Kerr line (bhr_set_kerr_line) by the line pass into the device row of option "kerr_line_row", behind both
+    if (kerr && bhr_have_kerr_line(ctx)) BHR_TRY(bhr_kerr_line_frame(ctx, call, rm, k));
     return post_on_slot(ctx, flags, k, ring);
 }
 

@@ -155,6 +155,7 @@ int32_t bhr_set_spin(bhr_ctx *ctx, float a_over_m, int32_t force_kerr) {
     ctx->kerr_on = on;
     ctx->kerr_spin = on ? a_over_m : 0.0f;
     if (bhr_have_kerr_polar(ctx)) bhr_polar_invalidate(ctx);   // the Stokes planes of a Kerr map frame are that spin's
+    if (bhr_have_kerr_line(ctx)) bhr_kerr_line_invalidate(ctx);   // ... and the line's sample planes
     return bhr_note_frame_kernel(ctx);
 }
 
@@ -171,6 +172,7 @@ int32_t bhr_set_redshift(bhr_ctx *ctx, int32_t mode) {
     BHR_TRY(bhr_enter(ctx));            // behind the frames in flight
     ctx->kerr_redshift = mode;
     if (bhr_have_kerr_polar(ctx)) bhr_polar_invalidate(ctx);   // ... and that mode's gas
+    if (bhr_have_kerr_line(ctx)) bhr_kerr_line_invalidate(ctx);
     return bhr_note_frame_kernel(ctx);
 }
 

@@ -161,6 +161,50 @@ def _checked_kerr_disk_model(kerr_disk_model, facts) -> str:
     return kerr_disk_model
 
 
+KERR_LINE_KEYS = ("path", "g_map_path", "n_bins", "g_range", "index", "power", "emissivity", "orders", "r_inner", "r_outer", "energy_kev")
+
+
+def _checked_kerr_line(kerr_line, facts):
+    """--spin_line PATH.npz / --spin_g_map PATH.png / kerr_line=dict(path=, g_map_path=, n_bins=, g_range=, index=, power=,
+    emissivity=, orders=, r_inner=, r_outer=, energy_kev=): the relativistically broadened emission line of a spinning hole's disk
+    and its redshift map, from the Kerr ray map of the view (HipRenderer.set_kerr_line; bhr_amd.line) -> dict(settings=, path=,
+    g_map_path=, energy_kev=) with the defaults filled in, or None.  What rules.FEATURES["kerr_line"] refuses is refused first, then
+    the values."""
+    if kerr_line is None:
+        return None
+    from . import line as line_mod
+    unknown = sorted(set(kerr_line) - set(KERR_LINE_KEYS))
+    if unknown:
+        raise ValueError(f"--spin_line: unknown settings {unknown} (known: {', '.join(KERR_LINE_KEYS)})")
+    rules.refuse_on("kerr_line", facts)
+    if kerr_line.get("path") is None and kerr_line.get("g_map_path") is None:
+        raise ValueError("--spin_line: neither a path for the profile nor one for the redshift map: nothing to write")
+    settings = line_mod.check_settings(**{k: kerr_line[k] for k in line_mod.DEFAULTS if k in kerr_line})
+    energy = float(kerr_line.get("energy_kev", line_mod.DEFAULT_ENERGY_KEV))
+    if not (energy > 0 and energy < float("inf")):
+        raise ValueError(f"--spin_line_energy is the line's rest energy in keV, finite and greater than 0, got {energy}")
+    return dict(settings=settings, path=kerr_line.get("path"), g_map_path=kerr_line.get("g_map_path"), energy_kev=energy)
+
+
+def _kerr_line_facts(kerr_line) -> dict:
+    if kerr_line is None:
+        return {}
+    return dict(kerr_line=True, kerr_line_path=kerr_line.get("path"), g_map_path=kerr_line.get("g_map_path"))
+
+
+def _save_kerr_line(renderer, kerr_line, n_rows=None) -> None:
+    """The profile of device row 0 -- or of rows 0 .. n_rows - 1, one per frame -- to the line's .npz."""
+    from . import line as line_mod
+    prof = renderer.kerr_line(0, n_rows, energy_kev=kerr_line["energy_kev"])
+    info = renderer.kerr_line_info(0)
+    if kerr_line["path"] is not None:
+        line_mod.save_npz(kerr_line["path"], prof)
+    frames = "" if n_rows is None else f"{n_rows} frames, frame 0: "
+    print(f"Line profile: {prof['settings']['n_bins']} bins, {frames}{info['samples']} samples, {info['overflow_pixels']} overflow pixels skipped, "
+          f"g from {np.ravel(prof['g_red'])[0]:.3f} to {np.ravel(prof['g_blue'])[0]:.3f}, mean {np.ravel(prof['g_mean'])[0]:.3f}"
+          + ("" if kerr_line["path"] is None else f"; saved: {kerr_line['path']}"))
+
+
 def make_renderer(width, height, cam_pos, fov, step_size=0.1, skybox_path=None, n_stars=6000, tex_w=2048,
                   tex_h=1024, r_max=10.0, disk_texture_path=None, r_disk_inner=R_DISK_INNER_DEFAULT,
                   r_disk_outer=R_DISK_OUTER_DEFAULT, disk_tilt=0.0, lens_flare=False, anti_alias="disabled",
@@ -227,7 +271,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
                  projection: Optional[str] = None, projection_fov=None, light_delay=None, polarization: Optional[dict] = None,
                  stokes_path: Optional[str] = None, ticks_path: Optional[str] = None, kerr_polarization: Optional[dict] = None,
                  kerr_view: Optional[dict] = None, kerr_stars: Optional[dict] = None, kerr_passes_path: Optional[str] = None,
-                 kerr_anti_alias: Optional[float] = None, kerr_disk_model: str = "texture") -> np.ndarray:
+                 kerr_anti_alias: Optional[float] = None, kerr_disk_model: str = "texture", kerr_line: Optional[dict] = None) -> np.ndarray:
     """One frame -> (H, W, 3) float32 (render.py:4031-4076).  ``gpus > 1`` tiles the frame in row
     blocks over that many devices of this node (bhr_group_render).  ``math``: march arithmetic
     ("strict" | "hybrid" | "fast"; None = HipRenderer's default, strict).  ``supersample``: k x k rays per
@@ -267,7 +311,11 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     "v2" / "v2_volume" -- the Kerr march shades the Disk V2 model with the renderer's radii and default structure, as a surface on
     the plane or as the finite-thickness volume (HipRenderer.use_kerr_disk_v2; use_kerr_analytic_disk): with supersample, the
     exact redshift (v2), lens flare and a grade; not without a spin, with disk_model, the Kerr ray map's features, the Kerr camera,
-    the Kerr anti-aliasing or several GPUs (rules.FEATURES["kerr_disk_model"])."""
+    the Kerr anti-aliasing or several GPUs (rules.FEATURES["kerr_disk_model"]).  ``kerr_line``: dict(path=, g_map_path=, n_bins=,
+    g_range=, index=, power=, emissivity=, orders=, energy_kev=) -- the disk's emission line profile and redshift map of a still under a
+    spin (_checked_kerr_line): builds the Kerr ray map of the view, as kerr_passes_path does, renders the still from it with the line
+    pass behind the shade, and writes the profile as a .npz and the map as a .png; kerr_polarization, kerr_stars and
+    kerr_passes_path may stand beside it."""
     check_depth_and_dither(bit_depth, dither=dither)
     # the facts of this call, built once; the features are refused in this order (rules.py has what each refuses)
     f = rules.Facts(dict(
@@ -275,7 +323,8 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         spin=spin, redshift=redshift, skybox_path=skybox_path, observer=observer is not None, projection=projection is not None, projection_fov=projection_fov,
         light_delay=light_delay is not None, stars=stars is not None, polarization=polarization is not None, kerr_polarization=kerr_polarization is not None,
         kerr_stars=kerr_stars is not None, passes=passes_path is not None, passes_path=passes_path, kerr_passes_path=kerr_passes_path, stokes_path=stokes_path,
-        ticks_path=ticks_path, kerr_anti_alias=kerr_anti_alias is not None, kerr_disk_model=kerr_disk_model, **_kerr_view_facts(kerr_view)))
+        ticks_path=ticks_path, kerr_anti_alias=kerr_anti_alias is not None, kerr_disk_model=kerr_disk_model, **_kerr_view_facts(kerr_view),
+        **_kerr_line_facts(kerr_line)))
     kerr_disk_model = _checked_kerr_disk_model(kerr_disk_model, f)      # ahead of the rest, so that each refusal names --spin_disk_model
     kerr_view = checked("kerr_view", kerr_view, f)
     if kerr_view is not None:                                  # refused ahead of any device work, like the rest
@@ -301,6 +350,7 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
     kerr_stars = checked("kerr_stars", kerr_stars, f)
     rules.refuse_on("kerr_passes", f)
     kerr_anti_alias = _checked_kerr_anti_alias(kerr_anti_alias, f)
+    kerr_line = _checked_kerr_line(kerr_line, f)
     if gpus > 1:
         from .multigpu import render_image_tiled
         return render_image_tiled(width, height, cam_pos, fov, gpus, step_size=step_size, skybox_path=skybox_path,
@@ -328,14 +378,22 @@ def render_image(width: int, height: int, cam_pos: List[float], fov: float, step
         renderer.set_kerr_anti_alias(True, kerr_anti_alias)
     if polarization is not None:
         renderer.set_polarization(**polarization)          # ahead of the frame: its Stokes pass rides behind the shade launch
-    if kerr_polarization is not None or kerr_stars is not None:
+    if kerr_polarization is not None or kerr_stars is not None or kerr_line is not None:
         from . import _lib
         if kerr_polarization is not None:
             renderer.set_kerr_polarization(**kerr_polarization)   # ahead of the build: the map then keeps the photon momenta
+        if kerr_line is not None:                                 # the line pass rides behind the shade launch; the planes feed the map
+            renderer.set_kerr_line(samples=kerr_line["g_map_path"] is not None, **kerr_line["settings"])
         renderer.build_kerr_ray_map(cam_pos, fov)
         renderer.render_from_kerr_ray_map_async(frame=0)
         img = renderer.read_layer(_lib.LAYER_FINAL)
         polarization = kerr_polarization                       # the outputs below are the same
+        if kerr_line is not None:
+            _save_kerr_line(renderer, kerr_line)
+            if kerr_line["g_map_path"] is not None:
+                from . import line as line_mod
+                line_mod.save_g_map(kerr_line["g_map_path"], renderer.kerr_line_samples()["g"])
+                print(f"Saved: {kerr_line['g_map_path']}")
     elif stars is not None or polarization is not None:
         from . import _lib
         renderer.build_ray_map(cam_pos, fov)
@@ -953,6 +1011,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                  light_delay=None, polarization: Optional[dict] = None, stokes_path: Optional[str] = None, spin_map: bool = False,
                  kerr_polarization: Optional[dict] = None, kerr_view: Optional[dict] = None, spin_map_supersample: int = 1,
                  spin_shutter_map: bool = False, kerr_stars: Optional[dict] = None, kerr_anti_alias: Optional[float] = None, kerr_disk_model: str = "texture",
+                 kerr_line: Optional[dict] = None,
                  **_deprecated_kwargs) -> None:
     """N frames -> PNGs (+ MP4) (render.py:4356-4511).  Frame f is rendered by rank f % world.
 
@@ -1097,7 +1156,11 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     refused (rules.FEATURES["kerr_anti_alias"]).  The renderer is asked last of all, behind every other refusal.
     ``kerr_disk_model``: "texture", or "v2" / "v2_volume" -- the Kerr march's Disk V2 source (HipRenderer.use_kerr_disk_v2 with the
     renderer's radii and default structure) for the video's marched frames, still or orbiting; it stays set on return.  What
-    rules.FEATURES["kerr_disk_model"] refuses is refused ahead of everything else."""
+    rules.FEATURES["kerr_disk_model"] refuses is refused ahead of everything else.
+
+    ``kerr_line`` (needs ``spin_map=True`` and no ``orbit``): render_image's dict -- a dynamic spectrum.  Every frame's line pass fills a
+    device row of its own (HipRenderer.kerr_line_reserve(n_frames)); the rows are read once at the end and the .npz holds ``flux`` and
+    ``counts`` of shape (n_frames, n_bins).  One GPU, no resume; a redshift map is a still's."""
     # the facts of this call, built once: what the call says, and what the renderer is set to -- which is read when the first rule asks
     # for it and not before (without a feature that needs them the renderer is not asked anything, as ever)
     moving = observer is not None or observer_velocity is not None or infall_to is not None
@@ -1109,7 +1172,7 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
         # (stokes_path alone counts as polarization's unless kerr_polarization, which it serves too, is there)
         polarization=polarization is not None or (stokes_path is not None and kerr_polarization is None), **_kerr_view_facts(kerr_view),
         kerr_disk_model=kerr_disk_model, kerr_anti_alias=lambda f: kerr_anti_alias is not None or getattr(renderer, "_kerr_anti_alias", None) is not None,
-        spin=lambda f: renderer.spin, redshift=lambda f: renderer.redshift, disk_tilt=lambda f: renderer.disk_tilt, anti_alias=lambda f: renderer.anti_alias,
+        **_kerr_line_facts(kerr_line), spin=lambda f: renderer.spin, redshift=lambda f: renderer.redshift, disk_tilt=lambda f: renderer.disk_tilt, anti_alias=lambda f: renderer.anti_alias,
         disk_model=lambda f: "texture" if getattr(renderer, "_dv2", None) is None else "v2",
         supersample=lambda f: renderer.supersample if supersample is None else supersample,
         supersample_threshold=lambda f: supersample_threshold if supersample is not None or supersample_threshold is not None
@@ -1162,6 +1225,9 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     kerr_stars = checked("kerr_stars", kerr_stars, f, "video")
     if kerr_stars is not None and renderer.kerr_stars_info()["n"] == 0:
         raise ValueError("--spin_stars: the renderer has no Kerr star catalogue (make_renderer(kerr_stars=...) sets it)")
+    kerr_line = _checked_kerr_line(kerr_line, f)
+    if kerr_line is not None and resume:
+        raise ValueError("--spin_line does not combine with --resume: the spectra of the frames rendered earlier are not on disk")
     if video_codec not in VIDEO_CODECS:
         raise ValueError(f"video_codec must be one of {VIDEO_CODECS}, got {video_codec!r}")
     check_depth_and_dither(bit_depth, dither=dither, video_codec=video_codec)
@@ -1293,6 +1359,9 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
     print(f"  lifecycle system ready (n_r={n_r}, n_phi={n_phi}), rank {rank}/{world}")
     if kerr_polarization is not None:
         renderer.set_kerr_polarization(**kerr_polarization)     # ahead of the build: the map then keeps the photon momenta
+    if kerr_line is not None:
+        renderer.set_kerr_line(**kerr_line["settings"])
+        renderer.kerr_line_reserve(n_frames)                    # a device row per frame, read once at the end
     if mode is not None:
         # the one march of the video.  A camera that stands still: its view; an orbit: frame 0's (the orbit's radius is |pov|, not
         # the pov's xy norm: not the pov itself), which every frame's camera is a turn of about z
@@ -1324,6 +1393,8 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                     fr["positions"] = [orbit_position(static_cam_pos, u, n_frames, orbit_degrees) if orbit else static_cam_pos for u in times]
                     fr["t_offsets"] = [(u - frame) * disk_rotation_speed for u in times]
                 if mode is not None:                               # from the video's map: shade, no march
+                    if kerr_line is not None:
+                        renderer.set_kerr_line_row(frame)
                     _MAP_MODES[mode]["frame"](renderer, fr)
                     if polarization is not None or kerr_polarization is not None:      # (ray_map, or spin_map under kerr_polarization)
                         stokes_grids[frame] = renderer.stokes_cells()      # the frame's cell grid (synchronises: a few kB per frame)
@@ -1356,8 +1427,14 @@ def render_video(renderer: HipRenderer, width: int, height: int, n_frames: int, 
                 renderer.set_polarization(None)
             if kerr_polarization is not None:
                 renderer.set_kerr_polarization(None)
+            if kerr_line is not None and rendered != n_frames:
+                renderer.set_kerr_line(None)
         frames_written, bytes_written = sink.drain()
         sink.close()
+        if kerr_line is not None:
+            # one GPU and no resume (above): every frame was rendered here, so every row is filled
+            _save_kerr_line(renderer, kerr_line, n_frames)
+            renderer.set_kerr_line(None)
         hole = {} if kerr_polarization is None else {"hole": dict(spin=renderer.spin, redshift=renderer.redshift)}
         polarization = polarization if kerr_polarization is None else kerr_polarization
         if polarization is not None:

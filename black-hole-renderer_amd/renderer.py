@@ -982,6 +982,100 @@ class HipRenderer:
         _lib.check(self._lib.bhr_kerr_stokes_resources(_lib.REDSHIFT_EXACT if redshift == "exact" else _lib.REDSHIFT_MODEL, out))
         return {"vgprs": int(out[0]), "lds_bytes": int(out[1]), "scratch_bytes": int(out[2])}
 
+    # ------------------------------------------------------------------ Kerr line profile
+    def set_kerr_line(self, n_bins=256, g_range=(0.0, 2.0), index: float = 3.0, power: float = 4.0, emissivity: str = "powerlaw",
+                      orders: str = "first", r_inner: Optional[float] = None, r_outer: Optional[float] = None, samples: bool = False) -> None:
+        """Set the emission line the frames from the KERR ray map compute the profile of (bhr_set_kerr_line; include/bhr.h "Kerr
+        line profile" states the model): the flux g^power eps dOmega of every counted disk crossing, binned in g over
+        ``g_range`` into ``n_bins`` bins.  ``emissivity`` "powerlaw" is (r / r_inner)^-index, "texture" that times the disk
+        texture's opacity under the frame's roll; ``orders`` "first" counts a pixel's first crossing (an opaque disk), "all"
+        every one.  ``r_inner`` / ``r_outer``: the line's annulus inside the disk's (neither: the disk's).  ``samples`` makes
+        the pass keep the per-record g and w planes (kerr_line_samples()).  ``n_bins=None`` switches the line off.  It needs
+        a spin or the forced Kerr march; the frames themselves are what they are without it.  Turned views, shutter frames and
+        supersampled Kerr maps are refused while it is set.  Synchronises; reserves two device rows."""
+        if n_bins is None:
+            _lib.check(self._lib.bhr_set_kerr_line(self._ctx, None))
+            self._kerr_line = None
+            return
+        from . import line as line_mod
+        s = line_mod.check_settings(n_bins, g_range, index, power, emissivity, orders, r_inner, r_outer)
+        par = _lib.KerrLine(s["n_bins"], s["g_range"][0], s["g_range"][1], s["power"], s["index"],
+                            _lib.LINE_TEXTURE if s["emissivity"] == "texture" else _lib.LINE_POWERLAW,
+                            _lib.LINE_ALL if s["orders"] == "all" else _lib.LINE_FIRST,
+                            0.0 if s["r_inner"] is None else s["r_inner"], 0.0 if s["r_outer"] is None else s["r_outer"])
+        _lib.check(self._lib.bhr_set_kerr_line(self._ctx, C.byref(par)))
+        self.set_option("kerr_line_samples", 1 if samples else 0)
+        self.set_option("kerr_line_row", 0)
+        self._kerr_line = s
+
+    def clear_kerr_line(self) -> None:
+        """Switch the Kerr line off (bhr_set_kerr_line with NULL)."""
+        self.set_kerr_line(None)
+
+    def kerr_line_reserve(self, n_rows: int) -> None:
+        """``n_rows`` zeroed device rows for the line's histograms, e.g. one per frame of a video (bhr_kerr_line_reserve); the
+        row a frame fills is ``set_kerr_line_row``'s.  Synchronises."""
+        _lib.check(self._lib.bhr_kerr_line_reserve(self._ctx, int(n_rows)))
+
+    def set_kerr_line_row(self, row: int) -> None:
+        """The device row the line pass of the next frame from the Kerr map fills (option "kerr_line_row")."""
+        self.set_option("kerr_line_row", int(row))
+
+    def kerr_line_counts(self, first_row: int = 0, n_rows: int = 1):
+        """The raw integers of rows [first_row, first_row + n_rows): (bins (n_rows, n_bins), under (n_rows,), over (n_rows,)),
+        uint64 (bhr_kerr_line_read).  Synchronises."""
+        s = getattr(self, "_kerr_line", None)
+        if s is None:
+            raise AssertionError("no Kerr line is set (set_kerr_line)")
+        bins = np.zeros((int(n_rows), s["n_bins"]), dtype=np.uint64)
+        uo = np.zeros((int(n_rows), 2), dtype=np.uint64)
+        _lib.check(self._lib.bhr_kerr_line_read(self._ctx, int(first_row), int(n_rows), bins.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                uo.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return bins, uo[:, 0].copy(), uo[:, 1].copy()
+
+    def kerr_line_info(self, row: int = 0) -> dict:
+        """``overflow_pixels`` (pixels on the map's overflow list, which contribute nothing) and ``samples`` (counted records)
+        of a device row (bhr_kerr_line_info)."""
+        out = (C.c_int64 * 2)()
+        _lib.check(self._lib.bhr_kerr_line_info(self._ctx, int(row), out))
+        return {"overflow_pixels": int(out[0]), "samples": int(out[1])}
+
+    def kerr_line(self, first_row: int = 0, n_rows: Optional[int] = None, energy_kev: float = 6.4) -> dict:
+        """The line profile of a device row -- or, with ``n_rows``, of that many rows, one per frame: ``edges`` (n_bins + 1),
+        ``flux`` per unit g, ``counts`` (the raw integers), ``under``, ``over``, ``g_mean``, ``g_red`` and ``g_blue`` (the outer
+        edges of the outermost non-empty bins), ``energy`` = g E0 at the bin centres, ``spin``, ``redshift`` and the
+        ``settings`` (bhr_amd.line.profile).  One row: 1-D arrays and numbers; several: a leading frame axis."""
+        from . import line as line_mod
+        bins, under, over = self.kerr_line_counts(first_row, 1 if n_rows is None else n_rows)
+        if n_rows is None:
+            bins, under, over = bins[0], under[0], over[0]
+        return line_mod.profile(bins, under, over, self._kerr_line, self._spin, self._redshift, energy_kev)
+
+    def kerr_line_samples(self) -> dict:
+        """The per-record planes ``g`` and ``w`` of the last frame whose line pass kept them (set_kerr_line(samples=True)), (K, rows,
+        width) float32 each in record order, 0 where a record does not count (bhr_kerr_raymap_read, BHR_RAYMAP_LINE_G / _W)."""
+        info = self.kerr_ray_map_info()
+        if not info["built"]:
+            raise AssertionError("no Kerr ray map has been built (build_kerr_ray_map)")
+        out = {}
+        for name, which in (("g", _lib.RAYMAP_LINE_G), ("w", _lib.RAYMAP_LINE_W)):
+            a = np.empty((info["slots"], info["rows"], info["width"]), dtype=np.float32)
+            _lib.check(self._lib.bhr_kerr_raymap_read(self._ctx, which, a.ctypes.data, a.nbytes))
+            out[name] = a
+        return out
+
+    def kerr_line_resources(self, redshift: str = "model", emissivity: str = "powerlaw") -> dict:
+        """Registers, static LDS bytes and scratch bytes of the Kerr line kernel of a redshift mode and emissivity
+        (bhr_kerr_line_resources); the histogram itself is dynamic LDS, (n_bins + 4) * 8 bytes."""
+        if redshift not in ("model", "exact"):
+            raise ValueError(f"redshift mode {redshift!r}: 'model' or 'exact'")
+        if emissivity not in ("powerlaw", "texture"):
+            raise ValueError(f"emissivity {emissivity!r}: 'powerlaw' or 'texture'")
+        out = (C.c_int32 * 3)()
+        _lib.check(self._lib.bhr_kerr_line_resources(_lib.REDSHIFT_EXACT if redshift == "exact" else _lib.REDSHIFT_MODEL,
+                                                     1 if emissivity == "texture" else 0, out))
+        return {"vgprs": int(out[0]), "lds_bytes": int(out[1]), "scratch_bytes": int(out[2])}
+
     def sync(self) -> None:
         _lib.check(self._lib.bhr_sync(self._ctx))
 

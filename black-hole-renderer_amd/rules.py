@@ -25,9 +25,9 @@ FACTS = dict(
     # which features are on
     observer=False, projection=False, light_delay=False, stars=False, polarization=False, kerr_polarization=False, spin_observer=False,
     spin_projection=False, kerr_stars=False, passes=False, ray_map=False, orbit_map=False, shutter_map=False, spin_map=False, spin_shutter_map=False,
-    kerr_anti_alias=False, kerr_disk_model="texture",
+    kerr_anti_alias=False, kerr_disk_model="texture", kerr_line=False,
     # the paths whose suffix is a row, and what a feature's own validation reads beside its value
-    passes_path=None, kerr_passes_path=None, stokes_path=None, ticks_path=None, projection_fov=None,
+    passes_path=None, kerr_passes_path=None, stokes_path=None, ticks_path=None, projection_fov=None, kerr_line_path=None, g_map_path=None,
     # the output side: the HDR stream of a video, the bits per sample
     video_hdr=None, hdr_white_given=False, hdr_exposure_given=False, video_codec="auto", video_stream="auto", width=2, height=2, bit_depth=8, dither="none",
     # the command line's observer flags one by one, and its projection by name
@@ -110,6 +110,10 @@ CONDITIONS = {
     "kerr_stars": lambda f: f["kerr_stars"],
     "kerr_passes": lambda f: f["kerr_passes_path"] is not None,
     "kerr_anti_alias": lambda f: f["kerr_anti_alias"],
+    "kerr_disk_model": lambda f: f["kerr_disk_model"] != "texture",
+    "kerr_line_not_npz": lambda f: _suffix(f["kerr_line_path"], ".npz"),
+    "g_map_not_png": lambda f: _suffix(f["g_map_path"], ".png"),
+    "g_map_video": lambda f: f["video"] and f["g_map_path"] is not None,
     "kerr_volume_exact": lambda f: f["kerr_disk_model"] == "v2_volume" and f["redshift"] == "exact",
     "sky_texture": lambda f: f["skybox_path"] is not None,
     "fov_given": lambda f: f["fov_given"],
@@ -442,6 +446,29 @@ FEATURES = {
              "kerr_volume_exact": "{who} v2_volume does not combine with --redshift exact: gas off the equatorial plane has no four-velocity in this model (v2 takes it)"},
         rows="no_spin disk_model spin_map spin_shutter_map kerr_polarization kerr_stars kerr_passes spin_observer spin_projection kerr_anti_alias gpus_or_world "
              "kerr_volume_exact"),
+    # the Kerr line profile and the redshift map (--spin_line, --spin_g_map; HipRenderer.set_kerr_line): a pass over the k = 1 Kerr ray
+    # map of the camera at rest, on one GPU -- the same words on both surfaces; --spin_polarization, --spin_stars and --spin_passes may
+    # stand beside it
+    "kerr_line": dict(
+        on=lambda f: f["kerr_line"],
+        words=dict(who="--spin_line / --spin_g_map", one_ray="the line pass needs a Kerr ray map with one ray per pixel"),
+        say={"no_spin": "{who} needs --spin or --redshift exact: the line profile is a pass over the Kerr ray map",
+             "video_no_spin_map": "{who} with --video needs --spin_map: the line profile comes from the Kerr ray map",
+             "video_orbit": "{who} does not combine with --orbit: the line pass walks the build view's records, turned views have none",
+             "shutter": "{who} does not combine with --shutter: a mean of frames has no line profile",
+             "supersample_or_threshold": "{who} does not combine with --supersample other than 1: a Kerr ray map holds one ray per pixel",
+             "spin_map_supersample": "{who} does not combine with --spin_map_supersample other than 1: {one_ray}",
+             "spin_shutter_map": "{who} does not combine with --spin_shutter_map: a mean of frames has no line profile",
+             "spin_observer": "{who} does not combine with --spin_observer: a Kerr ray map holds the rays of the camera at rest",
+             "spin_projection": "{who} does not combine with --spin_projection: the solid angle of a pixel is the pinhole camera's",
+             "kerr_anti_alias": "{who} does not combine with --spin_anti_alias: a Kerr ray map's record has no differential words",
+             "kerr_disk_model": "{who} does not combine with --spin_disk_model other than texture: a frame from the Kerr ray map shades the disk texture",
+             "gpus_or_world": "{who} does not combine with --gpus other than 1 or several ranks: a ray map lives on one GPU",
+             "kerr_line_not_npz": "--spin_line writes a .npz file, got {kerr_line_path!r}",
+             "g_map_not_png": "--spin_g_map writes a .png file, got {g_map_path!r}",
+             "g_map_video": "--spin_g_map is a still image's map: it does not combine with --video (the spectra go to --spin_line)"},
+        rows="no_spin video_no_spin_map video_orbit shutter supersample_or_threshold spin_map_supersample spin_shutter_map spin_observer spin_projection "
+             "kerr_anti_alias kerr_disk_model gpus_or_world kerr_line_not_npz g_map_not_png g_map_video"),
     # a still image tiled in row blocks over several GPUs (render_image)
     "tiles": dict(on=lambda f: f["gpus"] > 1, rows=dict(api="grade supersample_set", cli=""),
                   say={"grade": "a grade renders on one GPU: row-block tiles store their rows from inside the V pass",

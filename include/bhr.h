@@ -797,6 +797,77 @@ BHR_API int32_t bhr_kerr_raymap_free(bhr_ctx *ctx);
 BHR_API int32_t bhr_set_kerr_stars(bhr_ctx *ctx, const bhr_star *stars, int32_t n, const bhr_star_params *p);
 BHR_API int32_t bhr_get_kerr_stars_info(bhr_ctx *ctx, bhr_stars_info *out);
 BHR_API int32_t bhr_kerr_stars_resources(int32_t exact, int32_t rot, int32_t out[3]);
+/* ---- Kerr line profile: the disk's relativistically broadened emission line from the Kerr ray map
+ * (csrc/march_kerr_line.hip, csrc/api_kerr_line.hip; DESIGN 4 "Kerr line profile") ----
+ * A narrow line of rest energy E0 emitted by the gas with emissivity eps is observed at E = g E0 with the specific intensity
+ * g^4 eps delta(E - g E0) (Cunningham's transfer with a delta line), so the line flux is
+ *   F(g) dg = sum over the image of g^p eps dOmega, binned in g = E_obs / E_em,      p = `power`, 4 by default.
+ * With a line set, every bhr_kerr_raymap_render launches one more pass behind the frame's shade, over the records of the k = 1
+ * Kerr map, with the Kerr Stokes kernel's mapping (a lane per pixel, an 8 x 8 tile per wave).  Per pixel the records are walked
+ * front to back; of each record (hx, hy, v) -- v words 2..4: to_cam under BHR_REDSHIFT_MODEL, the photon's momentum under
+ * BHR_REDSHIFT_EXACT -- all in f32:
+ *   r      = sqrt(hx^2 + hy^2 - a^2), the Boyer-Lindquist hit radius; the record COUNTS iff r_inner <= r <= r_outer (the line's
+ *            annulus, inside the disk's) and, under BHR_LINE_FIRST, no earlier record of the pixel counted;
+ *   g      the context's redshift mode's g of the record, its cap (1.5) included: kerr_g_exact under the exact redshift, the
+ *            model's g as the frame's g-factor computes it under the model (csrc/ray_kerr.h: kerr_g_model);
+ *   dOmega = cos^3 theta, cos theta = D . forward for the pixel's unit ray direction D: the pinhole pixel's solid angle relative
+ *            to the central pixel's;
+ *   eps    BHR_LINE_POWERLAW: (r / r_inner)^(-index), independent of time;
+ *          BHR_LINE_TEXTURE:  that times the disk texture's opacity at the crossing under the frame's roll (t_offset),
+ *            alpha = 1 - (1 - min(A, 0.999))^6 with A the texture's fourth channel there (the frame's own disk_alpha);
+ *   T      the transmittance in front of the record, 1 - alpha_total, accumulated over every record of the pixel inside the
+ *            DISK's annulus exactly as the frame composites (alpha_total' = 1 - (1 - alpha_total) (1 - alpha)) -- under
+ *            BHR_LINE_TEXTURE with BHR_LINE_ALL only; 1 otherwise: BHR_LINE_FIRST is an opaque disk of which the first counted
+ *            crossing is seen whole, BHR_LINE_POWERLAW with BHR_LINE_ALL a transparent one;
+ *   w      = ((powf(g, p) eps) dOmega) T.
+ * A pixel on the map's overflow list (more crossings than slots) contributes nothing; their number is reported.
+ * The histogram: t = (g - g_min) * scale with scale = (float)(n_bins / (g_max - g_min)), computed once on the host (binary64,
+ * rounded once); t < 0 (or NaN) goes to `under`, else bin = (int)floorf(t), and bin >= n_bins to `over`.  A sample adds the integer
+ * Q = llrintf(w * unit), unit = (float)(2^32 / 1.5^p), to a 64-bit unsigned cell: w unit <= 2^32 (g <= 1.5, eps, dOmega, T <= 1),
+ * so the sum over 8 records of a 7680 x 4320 frame stays under 2^3 2^25 2^32 = 2^60 < 2^61.  Integer adds commute: whatever the
+ * order of the LDS and global atomics, the cells are a function of the samples alone, run after run.  Flux = Q / unit / bin width.
+ * A device ROW is n_bins cells, then under, over (sums of Q like the bins), the number of samples and the number of overflow pixels
+ * skipped.  The pass of a frame goes into the row option "kerr_line_row" names at the call (default 0), which is cleared on the
+ * frame's stream first; a frame whose row another frame slot's frame in flight wrote is ordered behind that frame.
+ * Option "kerr_line_samples" = 1 makes the pass also store, per record, g and w as (slots, rows, W) f32 planes of the frame slot,
+ * 0 where a record does not count: bhr_kerr_raymap_read(ctx, BHR_RAYMAP_LINE_G / BHR_RAYMAP_LINE_W, out, slots rows W 4) reads
+ * those of the last such frame (BHR_ERR_STATE without one).
+ * The frame itself -- BG, DISK, FINAL, the u8 rows -- is bit for bit what it is without the line; the map is only read.
+ * bhr_set_kerr_line(ctx, p): sets the line (NULL: off).  BHR_ERR_STATE without the Kerr march (bhr_set_spin); BHR_ERR_INVALID
+ *   naming the field for n_bins outside 1..4096, a range that is not finite with g_min < g_max, power outside [0, 8], index outside
+ *   [0, 16], an unknown emissivity or orders, an annulus that is not inside the disk's (r_inner = r_outer = 0: the disk's own),
+ *   reserved words other than 0, a row-block context.  It synchronises, drops the device rows and reserves two anew, zeroed.
+ * bhr_kerr_line_reserve(ctx, n_rows): n_rows (1 .. 65536) zeroed device rows, e.g. one per frame of a video; synchronises.
+ * bhr_kerr_line_read(ctx, first_row, n_rows, bins, under_over): bins n_rows x n_bins, under_over n_rows x 2; synchronises.
+ * bhr_kerr_line_info(ctx, row, out): out = {overflow pixels skipped, samples} of the row; synchronises.
+ * bhr_kerr_line_resources(redshift, texture, out): VGPRs, LDS bytes (static; the histogram is dynamic LDS, (n_bins + 4) 8 bytes)
+ *   and scratch bytes of the kernel of a redshift mode and emissivity.
+ * While a line is set, with nothing launched and the context as it was: bhr_kerr_raymap_build with "kerr_raymap_supersample" > 1
+ * is BHR_ERR_INVALID (and with a Kerr Disk V2 source or the Kerr anti-aliasing on, as ever); bhr_kerr_raymap_render from a
+ * supersampled map or with "kerr_line_row" outside the reserved rows, bhr_kerr_raymap_render_view with a turned camera and
+ * bhr_kerr_raymap_render_shutter are BHR_ERR_STATE.  A Kerr polarisation and Kerr point stars may be set beside it. */
+#define BHR_LINE_POWERLAW 0
+#define BHR_LINE_TEXTURE 1
+#define BHR_LINE_FIRST 0
+#define BHR_LINE_ALL 1
+#define BHR_LINE_MAX_BINS 4096
+#define BHR_RAYMAP_LINE_G 7
+#define BHR_RAYMAP_LINE_W 8
+typedef struct {
+    int32_t n_bins;                     /* 1 .. BHR_LINE_MAX_BINS */
+    float g_min, g_max;                 /* the histogram's range [g_min, g_max) */
+    float power;                        /* p of g^p: 4 for a line's flux */
+    float index;                        /* q of the power-law emissivity */
+    int32_t emissivity;                 /* BHR_LINE_POWERLAW or BHR_LINE_TEXTURE */
+    int32_t orders;                     /* BHR_LINE_FIRST or BHR_LINE_ALL */
+    float r_inner, r_outer;             /* the line's annulus; 0, 0: the disk's */
+    int32_t reserved[3];                /* 0 */
+} bhr_kerr_line;
+BHR_API int32_t bhr_set_kerr_line(bhr_ctx *ctx, const bhr_kerr_line *p);
+BHR_API int32_t bhr_kerr_line_reserve(bhr_ctx *ctx, int32_t n_rows);
+BHR_API int32_t bhr_kerr_line_read(bhr_ctx *ctx, int32_t first_row, int32_t n_rows, uint64_t *bins, uint64_t *under_over);
+BHR_API int32_t bhr_kerr_line_info(bhr_ctx *ctx, int32_t row, int64_t out[2]);
+BHR_API int32_t bhr_kerr_line_resources(int32_t redshift, int32_t texture, int32_t out[3]);
 /* A moving observer: one frame as a camera sees it that moves through bhr_camera.pos with velocity beta (a 3-vector in units of
  * c, |beta| <= 0.995) as the static observer there measures it.  That observer's local frame is identified with the coordinate
  * axes, as the camera that stands still identifies it; the camera basis is the moving camera's own.  With n' the pixel's
@@ -968,6 +1039,9 @@ BHR_API int32_t bhr_delayed_resources(int32_t supersampled, int32_t out[3]);
  *                                         pixels in one launch, 0 sample by sample with the accumulation launches (the same bits; A/B runs)
  *   "kerr_raymap_shutter_fused" BHR_KERR_RAYMAP_SHUTTER_FUSED 1 (default) bhr_kerr_raymap_render_shutter shades all samples of a k = 1 Kerr
  *                                         map without overflow pixels in one launch, 0 sample by sample likewise (the same bits; A/B runs)
+ *   "kerr_line_row"   (no variable)       the device row the Kerr line pass of the next bhr_kerr_raymap_render fills (bhr_set_kerr_line;
+ *                                         0 .. 65535, default 0; the render refuses a row that is not reserved)
+ *   "kerr_line_samples" (no variable)     1 the Kerr line pass also stores the per-record g and w planes (BHR_RAYMAP_LINE_G / _W); default 0
  * (bhr_create only: BHR_FRAME_SLOTS.) */
 BHR_API int32_t bhr_set_option(bhr_ctx *ctx, const char *name, double value);
 /* Diagnostics (tests): the split-f16 post-pass's packed intermediates of the last frame as raw bytes -- which = 0 the H pass's
